@@ -19,6 +19,10 @@ step i scans class i mod 16, class 0 = the label :P of SURVEY.md §8d first — 
 timed ones between two fences (barrier + torch.cuda.synchronize()); `value` = sum over the K steps (and over the ranks) of
 the traversed edges (sum over hops of flops) / max-over-ranks wall time.
 
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's call) as DIR/nnz.npy, DIR/checksum.npy and
+DIR/flops.npy: fgpu_expand_count's three u64 results, each as its [high, low] 32-bit halves in float64 (exact).  The
+inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
 READ `value` WITH `roofline.hop.frac`.  "TEPS" here is ALGEBRAIC: the edges the reference's GrB_mxm chain would traverse
 (sum over hops of flops, verified against the oracle), not edges this engine touches one by one — a bit-parallel pull over A'
 serves ~100 counted edges per physical row gather, so TEPS x 4 bytes exceeds the HBM peak by construction.  How well the
@@ -719,6 +723,20 @@ def _kernel_rows(prof, top=10):
             for k in sorted(prof, key=lambda k: -k["ms"])[:top]]
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, 64 MB at most in all."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def u64_halves(x):
+    return np.array([x >> 32, x & 0xFFFFFFFF], dtype=np.float64)
+
+
 def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, reduce_sum):
     """THE timed region of the bench line (module docstring): K WHOLE-FRONTIER calls of the 3-hop MATCH — one
     fgpu_expand_count per label scan, all ~N/16 sources of the label in the call, clean layers, count + checksum — W untimed
@@ -755,9 +773,9 @@ def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, redu
     t1 = time.perf_counter()
     tot_f = tot_n = 0
     cs = 0
-    scan0 = None
+    scan0 = last = None
     for b in timed:
-        nn, c, f = engine.expand_count(ctx, b, *clean)
+        nn, c, f = last = engine.expand_count(ctx, b, *clean)
         if scan0 is None:
             scan0 = (nn, c, f)
         tot_n += nn
@@ -765,6 +783,8 @@ def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, redu
         cs = (cs + c) & 0xFFFFFFFFFFFFFFFF
     fence()
     dt = reduce_max(time.perf_counter() - t1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: u64_halves(v) for k, v in zip(("nnz", "checksum", "flops"), last)})
     flops_all = reduce_sum(tot_f)
     nnz_all = reduce_sum(tot_n)
     line = {"value": round(flops_all / dt, 1), "ms_per_step": round(dt / max(args.steps, 1) * 1e3, 4)}
@@ -1443,7 +1463,11 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (traffic = committed / null)")
     ap.add_argument("--bfs-steps", type=int, default=64)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the results of the last timed k-hop step as DIR/<name>.npy (module docstring)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.leg != "khop" or args.steps < 1):
+        ap.error("--dump-outputs needs the k-hop leg and --steps >= 1")
     if args.pmc_child:
         return pmc_child(args)
 

@@ -481,3 +481,28 @@ def test_bench_line_with_two_ranks_on_one_device(tmp_path):
     assert d["metric"].startswith("traversed edges/sec (TEPS) on k-hop MATCH")
     assert d["parity"]["ok"] is True and d["value"] > 0
     assert "2 GPUs" in d["config"]["parallelism"]
+
+
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes fgpu_expand_count's (nnz, checksum, flops) of the LAST timed step.  With two steps
+    the DETAIL line pins that step: the timed totals minus step 0 (the checksum sum is modulo 2^64)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--scale", "18",
+           "--quick", "--no-parity", "--no-lanes-sweep", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    det = json.loads([l for l in r.stdout.splitlines() if l.startswith("DETAIL ")][-1][len("DETAIL "):])
+    t = det["headline"]["timed"]
+    assert t["steps"] == 2
+    want = {"nnz": t["out_nnz"] - t["step0"]["nnz"], "flops": t["flops"] - t["step0"]["flops"],
+            "checksum": (int(t["rank0_checksum"], 16) - int(t["step0"]["checksum"], 16)) % 2 ** 64}
+    assert sorted(p.name for p in out.iterdir()) == ["checksum.npy", "flops.npy", "nnz.npy"]
+    for name, v in want.items():
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (2,)
+        assert (int(a[0]) << 32) | int(a[1]) == v, name
+    assert want["nnz"] > 0 and want["flops"] > 0
