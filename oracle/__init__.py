@@ -131,6 +131,26 @@ class CSR:
         r, c = self.pairs()
         return set(zip(r.tolist(), c.tolist()))
 
+    def has_edges(self, rows, cols) -> np.ndarray:
+        """Per pair: is (rows[i], cols[i]) a stored entry?  A binary search in each row's sorted column ids, vectorised over
+        the pairs (no edge set on the host: usable at RMAT-24 sizes)."""
+        rows = np.asarray(rows, dtype=np.int64)
+        cols = np.asarray(cols, dtype=U64)
+        lo = self.rowptr[rows].astype(np.int64)
+        end = self.rowptr[rows + 1].astype(np.int64)
+        hi = end.copy()
+        while True:
+            act = lo < hi
+            if not act.any():
+                break
+            mid = (lo + hi) // 2
+            less = self.colidx[np.where(act, mid, 0)] < cols
+            lo = np.where(act & less, mid + 1, lo)
+            hi = np.where(act & ~less, mid, hi)
+        found = lo < end
+        found[found] = self.colidx[lo[found]] == cols[found]
+        return found
+
     def __eq__(self, o):
         return (self.nrows == o.nrows and self.ncols == o.ncols and np.array_equal(self.rowptr, o.rowptr)
                 and np.array_equal(self.colidx, o.colidx))

@@ -100,6 +100,40 @@ def test_slab_partitioned_bfs_matches_oracle(ctx, nranks, force, protocol):
             ctx.set_stream(None)
 
 
+@pytest.mark.parametrize("protocol", ["fused", "stepped"])
+@pytest.mark.parametrize("force", [0, 1, 2])
+def test_slab_partitioned_bfs_at_eight_ranks(ctx, force, protocol):
+    """The Python-driven level loop (dist.run_levels over HipSlabBackend: fused and stepped kernels, the all-gather by
+    device copies) with 8 equal slabs of RMAT-16: levels against the oracle for the hub, a vertex of the last slab and a
+    vertex with no out-edge, whole searches and max_level 3, and the per-rank shares of edges / reached."""
+    scale, nranks = 16, 8
+    a = oracle.rmat_csr(scale)
+    A = ctx.mat_rmat(scale)
+    n = a.nrows
+    deg = np.diff(a.rowptr.astype(np.int64))
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        ctx.set_stream(s.cuda_stream)
+        try:
+            gang = Gang(ctx, A, nranks, dev, protocol)
+            for b in gang.backs:
+                b.plan.tune(force_direction=force)
+            for src in [int(np.argmax(deg)), int(np.nonzero(deg > 0)[0][-1]), int(np.nonzero(deg == 0)[0][0])]:
+                full, _, ref_edges = oracle.bfs(a, src, -1)
+                for max_level in (-1, 3):
+                    fdist.run_levels(gang, gang.gather, src, max_level)
+                    ref = full if max_level < 0 else np.where(full <= max_level, full, -1)
+                    np.testing.assert_array_equal(gang.levels(n), ref)
+                    if max_level < 0:
+                        assert sum(b.plan.stats()["edges_traversed"] for b in gang.backs) == ref_edges
+                        if protocol == "fused":
+                            assert sum(b.plan.stats()["reached"] for b in gang.backs) == int((ref >= 0).sum())
+        finally:
+            torch.cuda.synchronize()
+            ctx.set_stream(None)
+
+
 @pytest.mark.parametrize("nranks", [1, 2, 3])
 def test_row_sharded_expand_concatenates_to_the_whole_batch(ctx, nranks):
     """k-hop MATCH over ranks: shard the source rows with dist.shard_rows, run every share
@@ -217,6 +251,121 @@ def test_in_library_dist_loop_matches_the_oracle(ctx, nranks, force):
                 assert sum(x["edges_traversed"] for x in st) == ref_edges
             lm, cm, nl = plans[0].dist_times()
             assert nl >= int(ref.max()) and (lm > 0) == (max_level < 0)
+
+
+def _assemble(plans, splits, n, want_parent):
+    """The slab owners' shares of the level (and parent) vectors, assembled: plan r fills [splits[r], splits[r + 1])."""
+    level = np.full(n, -1, dtype=np.int32)
+    parent = np.full(n, -1, dtype=np.int64) if want_parent else None
+    for r, p in enumerate(plans):
+        lv, par = p.fetch(want_parent=want_parent)
+        lo, hi = int(splits[r]), int(min(splits[r + 1], n))
+        level[lo:hi] = lv[lo:hi]
+        if want_parent:
+            parent[lo:hi] = par[lo:hi]
+        del lv, par
+    return level, parent
+
+
+def _check_parents(a, level, parent, src):
+    """Every reached vertex but the root has a parent one level up, joined to it by a stored edge; the unreached have none."""
+    assert parent[src] == src
+    child = np.nonzero(level > 0)[0]
+    p = parent[child]
+    assert (p >= 0).all() and (level[p] + 1 == level[child]).all()
+    assert a.has_edges(p, child.astype(np.uint64)).all()
+    assert (parent[level < 0] == -1).all()
+
+
+@pytest.mark.parametrize("kind", ["balanced", "equal"])
+def test_in_library_dist_loop_at_eight_ranks(ctx, kind):
+    """fgpu_bfs_dist_run over 8 column slabs of RMAT-18 on one device: nnz-balanced (uneven) slabs from
+    fgpu_mat_balanced_splits and the equal slabs of fgpu_bfs_plan_create; every direction mode; the hub (its entries are
+    spread over every slab's hub list), a vertex with no out-edge and one in the last 4096 ids; max_level -1 and 3 with
+    parents — levels, parents and the per-plan shares of reached / edges_traversed against the oracle."""
+    scale, nranks = 18, 8
+    a = oracle.rmat_csr(scale)
+    A = ctx.mat_rmat(scale)
+    n = a.nrows
+    deg = np.diff(a.rowptr.astype(np.int64))
+    if kind == "balanced":
+        splits = A.balanced_splits(nranks)
+        assert len({int(splits[r + 1] - splits[r]) for r in range(nranks)}) > 1    # uneven slabs
+        plans, keep = _gang_plans(ctx, A, nranks, splits)
+    else:
+        lo, hi, _, _ = fdist.slab_layout(n, nranks)
+        splits = lo + [hi[-1]]
+        plans, keep = [], []
+        for r in range(nranks):
+            a_slab = A.col_slab(int(lo[r]), int(min(hi[r], n)))
+            at_slab = a_slab.transpose()
+            keep += [a_slab, at_slab]
+            plans.append(engine.BfsPlan(ctx, a_slab, at_slab, r, nranks))
+    tail = np.nonzero(deg[n - 4096:] > 0)[0]
+    roots = [int(np.argmax(deg)), int(np.nonzero(deg == 0)[0][0]), int(n - 4096 + tail[-1])]
+    assert roots[2] >= int(splits[nranks - 1])                                   # (in the last slab)
+    refs = {src: oracle.bfs(a, src, -1) for src in roots}
+    try:
+        for force in (0, 1, 2):
+            for p in plans:
+                p.tune(force_direction=force)
+            for src in roots:
+                full, _, ref_edges = refs[src]
+                for max_level in (-1, 3):
+                    ref = full if max_level < 0 else np.where(full <= max_level, full, -1)
+                    engine.bfs_dist_run(plans, src, max_level, want_parent=True)
+                    level, parent = _assemble(plans, splits, n, True)
+                    np.testing.assert_array_equal(level, ref, err_msg=f"{kind} force={force} src={src} max_level={max_level}")
+                    _check_parents(a, level, parent, src)
+                    if max_level < 0:
+                        st = [p.stats() for p in plans]
+                        assert sum(x["reached"] for x in st) == int((ref >= 0).sum())
+                        assert sum(x["edges_traversed"] for x in st) == ref_edges
+        assert int((refs[roots[0]][0] >= 0).sum()) > n // 3 and int((refs[roots[1]][0] >= 0).sum()) == 1
+    finally:
+        for p in plans:
+            p.free()
+        for m_ in keep:
+            m_.free()
+        A.free()
+
+
+@pytest.mark.parametrize("scale", [24, 26])
+def test_in_library_dist_loop_at_eight_ranks_on_the_bench_graphs(ctx, bench_graphs, scale):
+    """8 nnz-balanced column slabs of the bench's RMAT-24 / RMAT-26 (the multi-GPU BFS target's partition, one device
+    holding every rank's slab): two bench roots through fgpu_bfs_dist_run, max_level -1 and 3 — levels and traversed
+    edges against the OpenMP oracle, parents as well at RMAT-24 (at RMAT-26 the host would have to hold the edge list
+    twice over)."""
+    nranks = 8
+    A, At, a = bench_graphs(scale)
+    rows, _, _ = A.extract(0, 4095)
+    roots = [int(r) for r in np.unique(rows)[:2]]            # bench.py pick_roots: the first ids with out-degree > 0
+    n = A.nrows
+    splits = A.balanced_splits(nranks)
+    assert len({int(splits[r + 1] - splits[r]) for r in range(nranks)}) > 1
+    want_parent = scale <= 24
+    plans, keep = [], []
+    try:
+        plans, keep = _gang_plans(ctx, A, nranks, splits)
+        for src in roots:
+            full, ref_edges = oracle.bfs_omp(a, None, src, -1)
+            for max_level in (-1, 3):
+                ref = full if max_level < 0 else np.where(full <= max_level, full, -1)
+                engine.bfs_dist_run(plans, src, max_level, want_parent=want_parent)
+                level, parent = _assemble(plans, splits, n, want_parent)
+                np.testing.assert_array_equal(level, ref, err_msg=f"rmat-{scale} src={src} max_level={max_level}")
+                if want_parent:
+                    _check_parents(a, level, parent, src)
+                if max_level < 0:
+                    st = [p.stats() for p in plans]
+                    assert sum(x["edges_traversed"] for x in st) == ref_edges
+                    assert sum(x["reached"] for x in st) == int((ref >= 0).sum()) > n // 3
+                del level, parent
+    finally:
+        for p in plans:
+            p.free()
+        for m_ in keep:
+            m_.free()
 
 
 def test_in_library_loop_over_an_rccl_communicator_of_one(ctx):

@@ -387,7 +387,8 @@ def test_whole_frontier_call_matches_the_oracle(ctx, rmat20, dirty):
     ref = (nnz, cs, flops)
     layers = ([A] * 3, [dp] * 3, [dm] * 3) if dirty else ([A] * 3,)
     seen = set()
-    for rows_, lanes, mode in ((1024, 3, 0), (1024, 1, 0), (256, 4, 0), (512, 2, 2), (64, 3, 0)):
+    for rows_, lanes, mode in ((1024, 3, 0), (1024, 1, 0), (256, 4, 0), (512, 2, 2), (64, 3, 0), (2048, 3, 0),
+                               (4096, 2, 0), (4096, 1, 2)):
         old = _scan_opts(ctx, expand_scan_rows=rows_, expand_scan_lanes=lanes, expand_mode=mode)
         try:
             got = engine.expand_count(ctx, src, *layers)

@@ -489,6 +489,78 @@ def test_bfs_heavy_push_levels_by_propagation_blocking(ctx, scale, min_edges, fo
         ctx.set_option("bfs_pb_min_edges", 2 << 20)
 
 
+@pytest.fixture(scope="module")
+def rmat20_host():
+    return oracle.rmat_csr(20)
+
+
+@pytest.mark.parametrize("n,armed", [((1 << 26) + 64, True), (1 << 27, True), ((1 << 27) + 64, False)])
+def test_bfs_propagation_blocking_at_its_widest_windows(ctx, rmat20_host, n, armed):
+    """Direction 3 at the window sizes the plan rule reaches only on huge id spaces: RMAT-20's vertices spread over [0, n)
+    (vertex v -> floor(v n / 2^20) + mix64(v) mod floor(n / 2^20): ascending, up to the top of the id space).  n = 2^26 + 64
+    is the smallest plan with 2^19-vertex windows (64 KiB of LDS in bfs_pb_apply_kernel), 2^27 the largest plan that arms the
+    path (windows over the whole id range), 2^27 + 64 one word past the cap: no blocked push there, the atomic push instead.
+    Levels, parents (with and without: the binned sources are only kept with parents), traversed edges, reached and max_level 2
+    against the oracle's BFS of the compact graph, mapped through the same relabelling; `bfs_pb_last_levels` says whether the
+    path ran."""
+    a = rmat20_host
+    k = a.nrows
+    v = np.arange(k, dtype=np.uint64)
+    stride = n // k
+    ids = ((v * np.uint64(n)) >> np.uint64(20)) + oracle.mix64(v) % np.uint64(stride)
+    assert (np.diff(ids.astype(np.int64)) > 0).all() and n - 256 <= int(ids[-1]) < n
+    rows, cols = a.pairs()
+    A = ctx.mat_from_coo(n, n, ids[rows.astype(np.int64)], ids[cols.astype(np.int64)])
+    At = A.transpose()
+    assert A.nvals == a.nnz
+    deg = np.diff(a.rowptr.astype(np.int64))
+    roots = [int(np.argmax(deg)), int(np.nonzero(deg > 0)[0][0]), int(np.nonzero(deg > 0)[0][-1])]
+    plan = None
+    try:
+        ctx.set_option("bfs_pb", 2)
+        ctx.set_option("bfs_pb_min_edges", 20000)
+        plan = engine.BfsPlan(ctx, A, At)
+        ran = 0
+        for force in (1, 0):
+            plan.tune(force_direction=force)
+            for src in (roots if force == 1 else roots[:1]):
+                ref_small, _, ref_edges = oracle.bfs(a, src, -1)
+                ref = np.full(n, -1, dtype=np.int32)
+                ref[ids.astype(np.int64)] = ref_small
+                big = int(ids[src])
+                for want_parent in (True, False):
+                    plan.run(big, -1, want_parent=want_parent)
+                    level, parent = plan.fetch(want_parent=want_parent)
+                    np.testing.assert_array_equal(level, ref, err_msg=f"n={n} force={force} src={src} parent={want_parent}")
+                    st = plan.stats()
+                    ran += ctx.get_option("bfs_pb_last_levels")
+                    assert st["edges_traversed"] == ref_edges
+                    assert st["reached"] == int(np.count_nonzero(ref_small >= 0))
+                    if want_parent:
+                        assert parent[big] == big
+                        child = ids[ref_small > 0].astype(np.int64)
+                        p = parent[child]
+                        assert (p >= 0).all() and (level[p] + 1 == level[child]).all()
+                        pu = np.searchsorted(ids, p.astype(np.uint64))           # back to the compact ids
+                        assert (ids[np.minimum(pu, k - 1)] == p.astype(np.uint64)).all()
+                        assert a.has_edges(pu, np.searchsorted(ids, child.astype(np.uint64)).astype(np.uint64)).all()
+                        assert int(np.count_nonzero(parent >= 0)) == len(child) + 1
+                    del level, parent
+                plan.run(big, 2)
+                np.testing.assert_array_equal(plan.fetch()[0], np.where(ref <= 2, ref, -1))
+        if armed:
+            assert ran > 0, "no level went by propagation blocking"
+        else:
+            assert ran == 0, "a plan past the window cap armed propagation blocking"
+    finally:
+        ctx.set_option("bfs_pb", 1)
+        ctx.set_option("bfs_pb_min_edges", 2 << 20)
+        if plan is not None:
+            plan.free()
+        At.free()
+        A.free()
+
+
 def test_bfs_listed_frontiers_and_listed_candidate_pulls(ctx):
     """The two other jobs of bfs_pb_list_kernel (plans with the propagation-blocking launches; forced on here): a push level
     whose frontier is a sparse bitmap is listed into the queue first, and a pull level with few rows left to discover runs as
@@ -853,6 +925,52 @@ def test_expand32_and_both_emission_forms_agree_with_the_oracle(ctx, rmat18, emi
     finally:
         ctx.set_option("expand_emit_sort", 1)
         DM.free()
+
+
+@pytest.mark.parametrize("k", [1100, 4200])
+def test_pair_emission_over_more_than_sixteen_words_per_row(ctx, rmat18, k):
+    """bp_pairs_kernel with w > 16 words per vertex row: a row's 16 lanes take its words in several rounds, each round going
+    on from the row's running offset (s_row) the previous one left.  1100 source rows (one NULL: 1099 live, w = 18 — a
+    partial second round) and 4200 (w = 66, five rounds), 2 hops forced into the bit-parallel form and emitted by pairs +
+    sort (expand_emit_sort = 2), with and without a destination label: row pointers and column ids entry by entry against
+    the oracle's delta_lmxm chain, and the profile shows that the pairs kernel made the rows."""
+    A, a = rmat18
+    src = np.linspace(3, a.nrows - 1, k).astype(U64)
+    src[7] = np.iinfo(np.uint64).max
+    keep = src != np.iinfo(np.uint64).max
+    assert -(-int(keep.sum()) // 64) > 16
+    f = oracle.build_csr(len(src), a.nrows, np.nonzero(keep)[0].astype(U64), src[keep])
+    fl = 0
+    for _ in range(2):
+        f, x = oracle.delta_lmxm_omp(f, a, None, None, 8)
+        fl += x
+    label = oracle.mix64(np.arange(a.nrows, dtype=U64)) % U64(5) != 0
+    bits = oracle.bits_from_ids(a.nrows, np.nonzero(label)[0])
+    sel = label[f.colidx.astype(np.int64)]
+    rows = np.repeat(np.arange(f.nrows), np.diff(f.rowptr).astype(np.int64))[sel]
+    want_rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=f.nrows))])
+    old_mode = ctx.get_option("expand_mode")
+    try:
+        ctx.set_option("expand_emit_sort", 2)
+        ctx.set_option("expand_mode", 2)
+        for lab in (None, bits):
+            ctx.prof_enable(True)
+            rowptr, dest, flops = engine.expand32(ctx, src, [A, A], dst_label_bitmap=lab)
+            prof = {p["kernel"]: p["launches"] for p in ctx.prof_read()}
+            ctx.prof_enable(False)
+            assert prof.get("bp_pairs_kernel<fill>", 0) > 0, sorted(prof)
+            assert flops == fl
+            if lab is None:
+                np.testing.assert_array_equal(rowptr, f.rowptr.astype(np.uint32))
+                np.testing.assert_array_equal(dest, f.colidx.astype(np.uint32))
+            else:
+                np.testing.assert_array_equal(rowptr, want_rp.astype(np.uint32))
+                np.testing.assert_array_equal(dest, f.colidx[sel].astype(np.uint32))
+        assert f.nnz > 1_000_000 and rowptr[8] == rowptr[7]
+    finally:
+        ctx.prof_enable(False)
+        ctx.set_option("expand_emit_sort", 1)
+        ctx.set_option("expand_mode", old_mode)
 
 
 @pytest.mark.parametrize("chunk_rows,dest_bits", [(1, 64), (7, 32), (64, 64), (4096, 32)])
