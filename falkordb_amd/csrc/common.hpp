@@ -121,6 +121,8 @@ struct fgpu_options {  // fgpu_set_option
     int pinned_results = 1;    // result arrays >= 256 KiB come from the context's pinned-host pool and are filled by DMA (0 = the
                                // caller's allocator / malloc + staged copies, the round-3 path; A/B)
     int pinned_pool_mb = 4096; // pinned blocks kept for reuse after fgpu_free (beyond it they go back to the OS)
+    int wcc_mode = 0;          // fgpu_wcc: 0 auto (Afforest from 4096 vertices), 1 Afforest with sampling and skip, 2 one full link
+                               // pass over every entry of A (wcc.hip)
 };
 
 struct fgpu_lane {  // one per host thread using the context

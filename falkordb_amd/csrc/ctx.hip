@@ -803,6 +803,7 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "expand_scan_lanes")) *value = ctx->opt.expand_scan_lanes;
     else if (!strcmp(name, "expand_nt")) *value = ctx->opt.expand_nt;
     else if (!strcmp(name, "bfs_pb")) *value = ctx->opt.bfs_pb;
+    else if (!strcmp(name, "wcc_mode")) *value = ctx->opt.wcc_mode;
     else if (!strcmp(name, "bfs_pb_min_edges")) *value = ctx->opt.bfs_pb_min_edges;
     else if (!strcmp(name, "bfs_cp_last_mask")) *value = ctx->bfs_cp_last.load(std::memory_order_relaxed);
     else if (!strcmp(name, "bfs_pb_last_levels")) *value = ctx->bfs_pb_last.load(std::memory_order_relaxed);
@@ -837,6 +838,9 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     } else if (!strcmp(name, "pagerank_parts")) {
         FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "pagerank_parts must be 0 (off), 1 (by size) or 2 (always)");
         ctx->opt.pagerank_parts = (int)value;
+    } else if (!strcmp(name, "wcc_mode")) {
+        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "wcc_mode must be 0 (auto), 1 (Afforest) or 2 (full pass)");
+        ctx->opt.wcc_mode = (int)value;
     } else if (!strcmp(name, "expand_first_hop")) {
         ctx->opt.expand_first_hop = value != 0;
     } else if (!strcmp(name, "expand_xcd")) {

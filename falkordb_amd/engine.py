@@ -517,6 +517,19 @@ def pagerank(ctx: Context, A: Mat, At: Mat | None = None, active_bitmap=None, da
     return out, it.value
 
 
+def wcc(ctx: Context, A: Mat, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
+    """fgpu_wcc: LAGr_ConnectedComponents' partition for algo.WCC, every component labelled by its smallest vertex id (-1 for
+    vertices outside active_bitmap).  At = None promises a symmetric pattern.  out: an int64 array to fill instead of a fresh
+    one (a Context.host_array() block is filled by DMA).  Returns (component int64[n], stats) — stats the four counters
+    [components, entries read, link launches, sampled giant size] when stats=True, else None."""
+    n = A.nrows
+    comp = out if out is not None else np.zeros(n, dtype=np.int64)
+    act = _u64(active_bitmap) if active_bitmap is not None else None
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_wcc(ctx._h, A._h, At._h if At else None, _p(act), _p(comp, i64p), _p(st)))
+    return comp, ([int(x) for x in st] if stats else None)
+
+
 class BfsPlan:
     """fgpu_bfs_plan: resident BFS workspace (+ slab partition state for multi-rank runs)."""
 

@@ -505,6 +505,16 @@ class Graph:
                                     C.byref(scores), C.byref(n)))
         return _take(nodes, n.value), _take(scores, n.value, np.float64)
 
+    def algo_wcc(self, labels=(), types=()):
+        """CALL algo.WCC({nodeLabels, relationshipTypes}) YIELD node, componentId -> (nodes, component_ids int64).  Several
+        labels select the union of their nodes; with labels the componentId is a compact index (see fh_algo_wcc)."""
+        nodes = u64p()
+        comp = C.POINTER(C.c_int64)()
+        n = C.c_uint64()
+        _ck(self.L.fh_algo_wcc(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.byref(nodes), C.byref(comp),
+                               C.byref(n)))
+        return _take(nodes, n.value), _take(comp, n.value, np.int64)
+
     def algo_bfs(self, source, max_depth=-1, rel_type=None, want_edges=False):
         has = C.c_int()
         nodes, edges = u64p(), u64p()

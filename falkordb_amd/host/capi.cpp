@@ -706,4 +706,24 @@ int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint6
     });
 }
 
+// algo.WCC: labels / types = comma lists, "" = all
+int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, int64_t** component_ids, uint64_t* n) {
+    return guard([&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::string> ls, ts;
+        for (auto& l : split(labels ? labels : "", ','))
+            if (!l.empty()) ls.push_back(l);
+        for (auto& t : split(types ? types : "", ','))
+            if (!t.empty()) ts.push_back(t);
+        WccResult r = algo_wcc(g->g, ls, ts);
+        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        *nodes = hand(r.nodes);
+        int64_t* c = (int64_t*)malloc((r.component_ids.size() ? r.component_ids.size() : 1) * sizeof(int64_t));
+        if (c && !r.component_ids.empty()) memcpy(c, r.component_ids.data(), r.component_ids.size() * sizeof(int64_t));
+        *component_ids = c;
+        *n = r.nodes.size();
+        return 0;
+    });
+}
+
 }  // extern "C"

@@ -871,4 +871,55 @@ PageRankResult algo_pagerank(const Graph& g, const std::optional<std::string>& l
     return res;
 }
 
+// ---- algo.WCC -------------------------------------------------------------------------------------------
+WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types) {
+    WccResult res;
+    const u64 n = g.node_cap();
+    u64 live = 0;
+    for (u64 v = 0; v < n; ++v) live += g.is_node_deleted(v) ? 0 : 1;
+    if (live == 0) return res;                                           // node_count() == 0 (:801-803)
+    // labels: the union of the labels' live nodes (collect_node_ids, :456-477) as an induced subgraph — the reference's compact
+    // graph (:817-826), here selected by a bitmap over the full id space
+    std::vector<u64> active;
+    const bool filtered = !labels.empty();
+    if (filtered) {
+        active.assign((n + 63) / 64, 0);
+        for (auto& l : labels)
+            if (auto lid = g.label_id(l)) {                              // an unknown label selects no node
+                const std::vector<u64> bits = g.label_bitmap({*lid});
+                for (size_t w = 0; w < active.size(); ++w) active[w] |= bits[w];
+            }
+        u64 cnt = 0;
+        for (u64 v = 0; v < n; ++v) {
+            if (g.is_node_deleted(v)) active[v >> 6] &= ~(1ull << (v & 63));
+            cnt += (active[v >> 6] >> (v & 63)) & 1ull;
+        }
+        if (cnt == 0) return res;                                        // :822-824
+    }
+    // the plain adjacency and its per-snapshot cached transpose: the undirected view without building A (+) A' per call
+    // (build_symmetric_adjacency_matrix, :813); unknown types contribute no edges.  Deleted ids stay in the unfiltered run
+    // as isolated vertices (n = node_count + deleted_nodes_count, :814-816).
+    Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894
+    Matrix adj_t = adj.transpose();
+    std::vector<int64_t> comp(n);
+    check(fgpu_wcc(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? active.data() : nullptr, comp.data(), nullptr),
+          "LAGr_ConnectedComponents");
+    // a filtered run's componentId is the representative's COMPACT index — its rank among the selected ids in ascending
+    // order (:617-626) — which the reference never maps back to a node id (:854-868)
+    std::vector<int64_t> rank;
+    if (filtered) {
+        rank.assign(n, -1);
+        int64_t k = 0;
+        for (u64 v = 0; v < n; ++v)
+            if ((active[v >> 6] >> (v & 63)) & 1ull) rank[v] = k++;
+    }
+    for (u64 v = 0; v < n; ++v) {
+        if (g.is_node_deleted(v)) continue;                              // :857-859
+        if (filtered && comp[v] < 0) continue;
+        res.nodes.push_back(v);
+        res.component_ids.push_back(filtered ? rank[(size_t)comp[v]] : comp[v]);
+    }
+    return res;
+}
+
 }  // namespace falkor

@@ -593,4 +593,12 @@ struct PageRankResult {
 PageRankResult algo_pagerank(const Graph& g, const std::optional<std::string>& label,
                              const std::optional<std::string>& rel_type);
 
+struct WccResult {
+    std::vector<u64> nodes;
+    std::vector<int64_t> component_ids;   // Column::Ints
+};
+// algo.WCC (runtime/functions/algo_procedures.rs:789-880): labels / types empty = all; several labels select the UNION of
+// their nodes (collect_node_ids, :456-477)
+WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types);
+
 }  // namespace falkor

@@ -1,18 +1,20 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
-// exporting the LAGraph entry points the reference's BFS / PageRank procedures bind, on the MI355X engine.  With them next
+// exporting the LAGraph entry points the reference's BFS / PageRank / WCC procedures bind, on the MI355X engine.  With them next
 // to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
 //                  GrB_Vector_extractTuples_INT64 on level / parent (:431-447) -> GrB_Vector_free -> G->A = NULL; LAGraph_Delete
 //   algo.pageRank  algo_procedures.rs:734-760    LAGraph_New -> LAGraph_Cached_AT + LAGraph_Cached_OutDegree ->
 //                  LAGr_PageRank(0.85, 1e-4, 100) (lagraph_bindings.rs:549-558) -> GrB_Vector_extractTuples_FP64 (:415-429)
+//   algo.WCC       algo_procedures.rs:816-871    GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(UNDIRECTED), is_symmetric_structure
+//                  = TRUE -> LAGr_ConnectedComponents (lagraph_bindings.rs:521-526) -> GrB_Vector_extractTuples_INT64
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
-// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank, pinned against the oracle.
-// The seven other LAGraph algorithms algo_procedures.rs calls (WCC, betweenness, harmonic centrality, max-flow, CDLP, MSF
-// and the EMin property) are outside this engine's path (out of scope): they are exported so the file links,
-// and return GrB_NOT_IMPLEMENTED with a message instead of computing anything.
+// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc, pinned against the oracle
+// (WCC against the checker of its tests).  The six other LAGraph algorithms algo_procedures.rs calls (betweenness, harmonic
+// centrality, max-flow, CDLP, MSF and the EMin property) are outside this engine's path (out of scope): they are
+// exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of computing anything.
 //
 // One source, two libraries: -DFG_LAGRAPHX builds the LAGraphX (experimental) symbols, without it the LAGraph core ones.
 #include "shim_internal.hpp"
@@ -236,9 +238,34 @@ int LAGr_PageRank(GrB_Vector* centrality, int* iters, LAGraph_Graph G, float dam
         return GrB_SUCCESS;
     });
 }
+// LAGr_ConnectedComponents (lagraph_bindings.rs:521-526) as algo.WCC calls it (algo_procedures.rs:816-871): an undirected
+// graph, or one whose G->is_symmetric_structure is cached TRUE; component is a full GrB_INT64 vector, component(i) = the
+// smallest vertex of i's component (the labelling LAGraph's FastSV converges to).  A directed graph of unknown symmetry is
+// refused with GrB_NOT_IMPLEMENTED — LAGraph proper returns LAGRAPH_SYMMETRIC_STRUCTURE_REQUIRED (-1001) there; the code the
+// shim has always returned for it is kept, with a message that names the requirement.
+int LAGr_ConnectedComponents(GrB_Vector* component, LAGraph_Graph G, char* msg) {
+    clear_msg(msg);
+    if (!component) return fail(msg, GrB_NULL_POINTER, "component is NULL");
+    *component = nullptr;
+    if (const int r = check_graph(G, msg)) return r;
+    const bool symmetric = G->kind == 0 || G->is_symmetric_structure == 1;
+    if (!symmetric)
+        return fail(msg, GrB_NOT_IMPLEMENTED,
+                    "LAGr_ConnectedComponents: symmetric structure required (an undirected graph, or G->is_symmetric_structure = true)");
+    return guarded(msg, [&]() -> int {
+        falkor::Context* c = fgshim::context();
+        const uint64_t n = G->A->m.nrows();
+        int64_t* comp = nullptr;
+        check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(int64_t), (void**)&comp), "LAGr_ConnectedComponents");
+        GrB_Vector out = fgshim::vector_over_pinned(fgshim::type_int64(), n, comp, 0);
+        const fgpu_info r = fgpu_wcc(c->raw(), G->A->m.snapshot(), nullptr, nullptr, comp, nullptr);
+        if (r != FGPU_OK) { GrB_Vector_free(&out); check(r, "LAGr_ConnectedComponents"); }
+        *component = out;
+        return GrB_SUCCESS;
+    });
+}
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank only)")
-int LAGr_ConnectedComponents(GrB_Vector* component, LAGraph_Graph, char* msg) { if (component) *component = nullptr; FG_NOT_ON_PATH(LAGr_ConnectedComponents); }
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC only)")
 int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph, const GrB_Index*, int32_t, char* msg) { if (centrality) *centrality = nullptr; FG_NOT_ON_PATH(LAGr_Betweenness); }
 int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
 #else
@@ -280,7 +307,7 @@ int LAGr_BreadthFirstSearch_Extended(GrB_Vector* level, GrB_Vector* parent, LAGr
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC only)")
 int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable, LAGraph_Graph, GrB_Vector, char* msg) {
     if (scores) *scores = nullptr;
     if (reachable) *reachable = nullptr;

@@ -143,7 +143,8 @@ int fh_cond_traverse_batch(fh_graph* g, const char* spec, const int64_t* src, co
                            uint64_t k, int* batched, uint64_t** out_row, uint64_t** out_dest,
                            int64_t** out_edge, uint64_t* n, uint64_t** null_rows, uint64_t* n_null,
                            uint64_t* flops);                                            /* cond_traverse.rs:452-751 */
-/* duration (ns) of the C++ operator inside this thread's last fh_cond_traverse_batch / fh_algo_bfs / fh_algo_pagerank call:
+/* duration (ns) of the C++ operator inside this thread's last fh_cond_traverse_batch / fh_algo_bfs / fh_algo_pagerank /
+ * fh_algo_wcc call:
  * what the operator costs without the ctypes harness' result copies (tools/bench_paths.py host) */
 uint64_t fh_last_op_ns(void);
 int fh_cond_traverse_eligible(const char* spec);                                       /* cond_traverse.rs:308-316 */
@@ -206,6 +207,13 @@ int fh_plan_fuse(const char* plan_text, int lower_id, char** out_text, char** sp
 /* label / rel_type NULL = all; nodes ascending, scores[k] = centrality of nodes[k] (free both with fh_free) */
 int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint64_t** nodes, double** scores,
                      uint64_t* n);                                                          /* algo_procedures.rs:687-783 */
+
+/* algo.WCC (algo_procedures.rs:789-880; LAGr_ConnectedComponents through lagraph_bindings.rs:521-526 is fgpu_wcc): labels /
+ * types = comma lists, "" / NULL = all; several labels select the UNION of their nodes.  Rows in ascending node id, deleted
+ * nodes dropped.  component_ids[k] = the smallest node id of nodes[k]'s component — or, with labels, that node's COMPACT
+ * index (its rank among the selected nodes in ascending id order), as the reference returns it.  Free both with fh_free. */
+int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, int64_t** component_ids,
+                uint64_t* n);
 
 #ifdef __cplusplus
 }

@@ -112,7 +112,8 @@ fgpu_info fgpu_sync(fgpu_ctx* ctx);
  * the unvisited share over the vertices that have an in-edge; 0 = over all vertices), "expand_emit_sort" (bit state -> rows of
  * fgpu_expand*: 2 = (row, vertex) pairs + a stable sort by row, 0 = ballot transpose, 1 = pairs + sort unless the result
  * holds more than 8 entries per vertex; the default), "pinned_results" / "pinned_pool_mb" (result arrays from 256 KiB up to
- * the pool's size come from the context's pinned pool and are filled by DMA; blocks kept for reuse up to that many MiB). */
+ * the pool's size come from the context's pinned pool and are filled by DMA; blocks kept for reuse up to that many MiB),
+ * "wcc_mode" (fgpu_wcc: 0 = auto, 1 = Afforest with sampling and skip, 2 = one full link pass over every entry of A). */
 fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
 /* Read-back of measurement / test counters kept by the context (a subset of the option names plus counters that
  * have no setter): "dist_force_self" (test-only, set through fgpu_set_option: a communicator of ONE rank still issues the
@@ -121,7 +122,7 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  * far: the launch count of a batch is a difference of two reads), "bfs_pb_last_levels" (levels the search fgpu_bfs_stats last
  * read ran by propagation blocking), "bfs_cp_last_mask" (bit k: fused launch k of that search ran behind the list kernel — a
  * sparse frontier listed into the queue, or a pull of listed candidates), "expand_scan_last_live" / "expand_scan_last_passes" (live source rows and passes of the
- * last whole-frontier fgpu_expand_count).  Unknown names return FGPU_INVALID. */
+ * last whole-frontier fgpu_expand_count), "wcc_mode".  Unknown names return FGPU_INVALID. */
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value);
 /* name[256]; returns CU count, wave size, LDS bytes per block, total HBM bytes. */
 fgpu_info fgpu_device_info(fgpu_ctx* ctx, char* name, int32_t* cus, int32_t* wave,
@@ -393,6 +394,19 @@ fgpu_info fgpu_pagerank(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, co
 fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
                                float damping, float tol, int32_t itermax, float* centrality, int32_t* iters,
                                int32_t* converged);
+
+/* Weakly connected components: replaces LAGr_ConnectedComponents(&component, G, msg) as called by algo.WCC
+ * (algo_procedures.rs:789-880; binding lagraph_bindings.rs:521-526).  The graph is undirected: every stored entry (i, j) of
+ * A joins i and j.  `At` (nullable) is A's transpose; NULL is the caller's promise that A's pattern is symmetric (LAGraph's
+ * is_symmetric_structure) — the Afforest path skips the giant component's rows and needs both directions of every edge.
+ * `active_bitmap` (nullable, nrows bits, as fgpu_pagerank) restricts the run to the induced subgraph of the flagged vertices;
+ * the other slots get -1.  component[nrows] is a HOST array (filled by DMA when pinned — fgpu_host_alloc — by staging
+ * otherwise): component[v] = the smallest vertex id of v's component, the labelling LAGraph's FastSV converges to.
+ * stats (nullable): [0] components among the active vertices, [1] adjacency entries read by the link kernels, [2] link
+ * launches, [3] size of the component the sampling phase picked as the giant (0 when it did not run).  Option "wcc_mode":
+ * 0 auto, 1 Afforest with sampling and skip, 2 one full link pass over every entry of A.  nrows == 0 is a no-op. */
+fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
+                   int64_t* component, uint64_t stats[4]);
 
 /* Level-synchronous BFS: replaces LAGr_BreadthFirstSearch_Extended(level, parent, G,
  * src, max_level, -1, false) as called by algo.BFS (algo_procedures.rs:1079-1088;

@@ -12,7 +12,11 @@
 
   pagerank  algo.pageRank's core (fgpu_pagerank, FP32 plus_second pull SpMV) on RMAT-<scale>: ms per iteration
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|all] [scale]
+  wcc     algo.WCC's core (fgpu_wcc) on RMAT-22 and RMAT-24 (or RMAT-<scale>): (A, At) and the symmetrised A with At = NULL,
+          wcc_mode 1 (Afforest, sampling + skip) and 2 (one full link pass); median of 10 synchronised calls, the stats,
+          and the full-pass bound (4 nnz(A) + 4 (n + 1) bytes at 8 TB/s)
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|all] [scale]
 """
 import json
 import sys
@@ -217,6 +221,29 @@ def bench_host(scale):
                       "note": "cpp = CondTraverseOp::expand_batch alone (label probes, fgpu_expand, result columns); through_ctypes adds the test harness' copies into numpy"}), flush=True)
 
 
+def bench_wcc(ctx, scale):
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    At = A.transpose()
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    rows = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp.astype(np.int64)))
+    S = ctx.mat_from_coo(n, n, np.concatenate([rows, ci]), np.concatenate([ci, rows]))   # A (+) A'
+    del rp, ci, rows
+    for label, a, at in (("A+At", A, At), ("symmetric", S, None)):
+        nnz = a.nvals
+        bound_ms = (4 * nnz + 4 * (n + 1)) / 8e12 * 1e3
+        out = ctx.host_array(n, np.int64)
+        for mode in (1, 2):
+            ctx.set_option("wcc_mode", mode)
+            t, (_, st) = timed(ctx, lambda: engine.wcc(ctx, a, at, stats=True, out=out), reps=10, warm=2)
+            print(json.dumps({"path": "wcc", "scale": scale, "input": label, "wcc_mode": mode, "n": n, "nnz": nnz,
+                              "ms": round(t * 1e3, 3), "components": st[0], "entries_read": st[1], "link_launches": st[2],
+                              "giant": st[3], "full_pass_bound_ms": round(bound_ms, 4),
+                              "note": "host clock around a synchronised call, median of 10 after 2 warm-up; bound = "
+                                      "(4 nnz(A) + 4 (n + 1)) bytes at 8 TB/s, one read of the CSR"}), flush=True)
+    ctx.set_option("wcc_mode", 0)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     scale = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -251,6 +278,11 @@ if __name__ == "__main__":
     if what in ("pagerank", "all"):
         c = engine.Context(0)
         bench_pagerank(c, scale or 22)
+        c.close()
+    if what in ("wcc", "all"):
+        c = engine.Context(0)
+        for sc in ([scale] if scale else [22, 24]):
+            bench_wcc(c, sc)
         c.close()
     if what in ("host", "all"):
         bench_host(scale or 18)
