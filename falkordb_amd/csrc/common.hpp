@@ -123,6 +123,8 @@ struct fgpu_options {  // fgpu_set_option
     int pinned_pool_mb = 4096; // pinned blocks kept for reuse after fgpu_free (beyond it they go back to the OS)
     int wcc_mode = 0;          // fgpu_wcc: 0 auto (Afforest from 4096 vertices), 1 Afforest with sampling and skip, 2 one full link
                                // pass over every entry of A (wcc.hip)
+    int bc_batch = 0;          // fgpu_betweenness: sources per batch, 0 auto (16 / 32 / 64 by nsrc, halved to fit free memory), 1-64 forced
+    int bc_direction = 0;      // fgpu_betweenness forward levels: 0 auto (push / pull by entries to read), 1 push over A, 2 pull over At
 };
 
 struct fgpu_lane {  // one per host thread using the context

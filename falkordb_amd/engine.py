@@ -530,6 +530,22 @@ def wcc(ctx: Context, A: Mat, At: Mat | None = None, active_bitmap=None, stats: 
     return comp, ([int(x) for x in st] if stats else None)
 
 
+def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
+    """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
+    as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached
+    transpose.  out: a float64 array to fill instead of a fresh one (a Context.host_array() block is filled by DMA).  Returns
+    (centrality float64[n], stats) — stats the four counters [batches, forward levels, adjacency entries read, deepest level]
+    when stats=True, else None."""
+    n = A.nrows
+    cent = out if out is not None else np.zeros(n, dtype=np.float64)
+    src = _u64(sources)
+    act = _u64(active_bitmap) if active_bitmap is not None else None
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_betweenness(ctx._h, A._h, At._h if At else None, _p(act), _p(src) if len(src) else None, len(src),
+                                   cent.ctypes.data_as(C.POINTER(C.c_double)), _p(st)))
+    return cent, ([int(x) for x in st] if stats else None)
+
+
 class BfsPlan:
     """fgpu_bfs_plan: resident BFS workspace (+ slab partition state for multi-rank runs)."""
 

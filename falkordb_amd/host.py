@@ -78,6 +78,15 @@ def _take(ptr, n, dtype=np.uint64):
     return out
 
 
+def betweenness_sources(n_nodes, sampling_size=16, sampling_seed=0):
+    """algo.betweenness' source indices out of 0..n_nodes (fh_betweenness_sources; no GPU)"""
+    out = u64p()
+    n = C.c_uint64()
+    _ck(load().fh_betweenness_sources(C.c_uint64(n_nodes), C.c_int64(sampling_size), C.c_int64(sampling_seed), C.byref(out),
+                                      C.byref(n)))
+    return _take(out, n.value)
+
+
 def should_fold(d, tx, base):
     return bool(load().fh_should_fold(C.c_uint64(d), C.c_uint64(tx), C.c_uint64(base)))
 
@@ -514,6 +523,16 @@ class Graph:
         _ck(self.L.fh_algo_wcc(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.byref(nodes), C.byref(comp),
                                C.byref(n)))
         return _take(nodes, n.value), _take(comp, n.value, np.int64)
+
+    def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
+        """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
+        (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""
+        nodes = u64p()
+        scores = C.POINTER(C.c_double)()
+        n = C.c_uint64()
+        _ck(self.L.fh_algo_betweenness(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.c_int64(sampling_size),
+                                       C.c_int64(sampling_seed), C.byref(nodes), C.byref(scores), C.byref(n)))
+        return _take(nodes, n.value), _take(scores, n.value, np.float64)
 
     def algo_bfs(self, source, max_depth=-1, rel_type=None, want_edges=False):
         has = C.c_int()

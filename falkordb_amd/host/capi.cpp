@@ -726,4 +726,34 @@ int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** n
     });
 }
 
+// algo.betweenness: labels / types = comma lists, "" = all
+int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
+                        uint64_t** nodes, double** scores, uint64_t* n) {
+    return guard([&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::string> ls, ts;
+        for (auto& l : split(labels ? labels : "", ','))
+            if (!l.empty()) ls.push_back(l);
+        for (auto& t : split(types ? types : "", ','))
+            if (!t.empty()) ts.push_back(t);
+        BetweennessResult r = algo_betweenness(g->g, ls, ts, sampling_size, sampling_seed);
+        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        *nodes = hand(r.nodes);
+        double* sc = (double*)malloc((r.scores.size() ? r.scores.size() : 1) * sizeof(double));
+        if (sc && !r.scores.empty()) memcpy(sc, r.scores.data(), r.scores.size() * sizeof(double));
+        *scores = sc;
+        *n = r.nodes.size();
+        return 0;
+    });
+}
+
+int fh_betweenness_sources(uint64_t n_nodes, int64_t sampling_size, int64_t sampling_seed, uint64_t** out, uint64_t* n) {
+    return guard([&] {
+        const std::vector<u64> s = betweenness_sources(n_nodes, sampling_size, sampling_seed);
+        *out = hand(s);
+        *n = s.size();
+        return 0;
+    });
+}
+
 }  // extern "C"

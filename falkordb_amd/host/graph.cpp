@@ -922,4 +922,81 @@ WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const
     return res;
 }
 
+// ---- algo.betweenness -----------------------------------------------------------------------------------
+std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t sampling_seed) {
+    if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // :900-905
+    // `*n as i32` keeps the low 32 bits, `as usize` sign-extends them: 2^32 + 5 -> 5, 2^31 -> 2^64 - 2^31 ("all nodes")
+    const u64 size = (u64)(int64_t)(int32_t)(uint32_t)(uint64_t)sampling_size;
+    const u64 seed = (u64)sampling_seed;                                 // `*n as u64`: negative seeds wrap (:909-913)
+    std::vector<u64> out;
+    if (n_nodes == 0) return out;                                        // :954-955
+    if (size >= n_nodes) {                                               // :956-957
+        out.resize(n_nodes);
+        for (u64 i = 0; i < n_nodes; ++i) out[i] = i;
+        return out;
+    }
+    std::vector<uint8_t> used(n_nodes, 0);
+    u64 rng = seed;
+    for (u64 i = 0; i < size; ++i) {                                     // :958-974
+        u64 idx;
+        if (seed == 0) {
+            idx = i % n_nodes;
+        } else {
+            rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+            idx = (rng >> 33) % n_nodes;
+        }
+        if (!used[idx]) {
+            used[idx] = 1;
+            out.push_back(idx);
+        }
+    }
+    return out;
+}
+
+BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                                   int64_t sampling_size, int64_t sampling_seed) {
+    BetweennessResult res;
+    const u64 n = g.node_cap();
+    u64 live = 0;
+    for (u64 v = 0; v < n; ++v) live += g.is_node_deleted(v) ? 0 : 1;
+    if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // before the graph (:900-905)
+    if (live == 0) return res;                                           // node_count() == 0 (:916-918)
+    // labels: the union of the labels' live nodes (collect_node_ids) as an induced subgraph — the reference's compact graph
+    // (build_compact_adj_from_tensors, :935-940), here selected by a bitmap over the full id space
+    std::vector<u64> active;
+    std::vector<u64> selected;                                           // compact index -> node id (compact_to_id)
+    const bool filtered = !labels.empty();
+    if (filtered) {
+        active.assign((n + 63) / 64, 0);
+        for (auto& l : labels)
+            if (auto lid = g.label_id(l)) {                              // an unknown label selects no node
+                const std::vector<u64> bits = g.label_bitmap({*lid});
+                for (size_t w = 0; w < active.size(); ++w) active[w] |= bits[w];
+            }
+        for (u64 v = 0; v < n; ++v) {
+            if (g.is_node_deleted(v)) active[v >> 6] &= ~(1ull << (v & 63));
+            if ((active[v >> 6] >> (v & 63)) & 1ull) selected.push_back(v);
+        }
+        if (selected.empty()) return res;
+    }
+    // n_nodes: node_count + deleted_nodes_count unfiltered (deleted ids stay as vertices and can be sources), else the
+    // selected nodes (:949-952)
+    std::vector<u64> sources = betweenness_sources(filtered ? selected.size() : n, sampling_size, sampling_seed);
+    if (filtered)
+        for (auto& s : sources) s = selected[s];
+    Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894; unknown types add no edges
+    Matrix adj_t = adj.transpose();                                      // LAGraph_Cached_AT (:945)
+    std::vector<double> cent(n);
+    check(fgpu_betweenness(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? active.data() : nullptr, sources.data(),
+                           sources.size(), cent.data(), nullptr),
+          "LAGr_Betweenness");
+    for (u64 v = 0; v < n; ++v) {
+        if (g.is_node_deleted(v)) continue;                              // :1003-1005
+        if (filtered && !((active[v >> 6] >> (v & 63)) & 1ull)) continue;
+        res.nodes.push_back(v);
+        res.scores.push_back(cent[v]);
+    }
+    return res;
+}
+
 }  // namespace falkor

@@ -601,4 +601,17 @@ struct WccResult {
 // their nodes (collect_node_ids, :456-477)
 WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types);
 
+struct BetweennessResult {
+    std::vector<u64> nodes;
+    std::vector<double> scores;   // Column::Floats
+};
+// algo.betweenness' source rule (runtime/functions/algo_procedures.rs:898-975): samplingSize <= 0 throws; the value is cast
+// `as i32` then `as usize`, the seed `as u64`; n_nodes <= size gives every index, otherwise `size` draws (seed 0: i % n_nodes,
+// else an LCG), repeats dropped, first-seen order kept
+std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t sampling_seed);
+// algo.betweenness (runtime/functions/algo_procedures.rs:884-1017): labels / types empty = all; several labels select the
+// UNION of their nodes, and a source index then means the k-th selected node in ascending id order
+BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                                   int64_t sampling_size, int64_t sampling_seed);
+
 }  // namespace falkor

@@ -193,6 +193,7 @@ falkor::Context* context() { return ctx(); }
 GB_Type_opaque* type_int32() { return &t_i32; }
 GB_Type_opaque* type_int64() { return &t_i64; }
 GB_Type_opaque* type_fp32() { return &t_f32; }
+GB_Type_opaque* type_fp64() { return &t_f64; }
 GB_Vector_opaque* vector_over_pinned(GB_Type_opaque* type, GrB_Index n, void* pinned, int absent) {
     GB_Vector_opaque* v = vec_new(type, n);
     v->data = pinned; v->nbytes = n * type->size; v->nstored = n; v->absent = absent;

@@ -1,6 +1,6 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
-// exporting the LAGraph entry points the reference's BFS / PageRank / WCC procedures bind, on the MI355X engine.  With them next
-// to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
+// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness procedures bind, on the MI355X engine.
+// With them next to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
 //                  GrB_Vector_extractTuples_INT64 on level / parent (:431-447) -> GrB_Vector_free -> G->A = NULL; LAGraph_Delete
@@ -8,13 +8,16 @@
 //                  LAGr_PageRank(0.85, 1e-4, 100) (lagraph_bindings.rs:549-558) -> GrB_Vector_extractTuples_FP64 (:415-429)
 //   algo.WCC       algo_procedures.rs:816-871    GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(UNDIRECTED), is_symmetric_structure
 //                  = TRUE -> LAGr_ConnectedComponents (lagraph_bindings.rs:521-526) -> GrB_Vector_extractTuples_INT64
+//   algo.betweenness algo_procedures.rs:925-1017 GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(DIRECTED) -> LAGraph_Cached_AT +
+//                  LAGraph_Cached_OutDegree -> LAGr_Betweenness (lagraph_bindings.rs:539-546) -> GrB_Vector_extractTuples_FP64
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
-// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc, pinned against the oracle
-// (WCC against the checker of its tests).  The six other LAGraph algorithms algo_procedures.rs calls (betweenness, harmonic
-// centrality, max-flow, CDLP, MSF and the EMin property) are outside this engine's path (out of scope): they are
-// exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of computing anything.
+// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness, pinned
+// against the oracle (WCC and betweenness against the checkers of their tests).  The five other LAGraph algorithms
+// algo_procedures.rs calls (harmonic centrality, max-flow, CDLP, MSF and the EMin property) are outside this engine's path
+// (out of scope): they are exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of
+// computing anything.
 //
 // One source, two libraries: -DFG_LAGRAPHX builds the LAGraphX (experimental) symbols, without it the LAGraph core ones.
 #include "shim_internal.hpp"
@@ -264,9 +267,36 @@ int LAGr_ConnectedComponents(GrB_Vector* component, LAGraph_Graph G, char* msg) 
         return GrB_SUCCESS;
     });
 }
+// LAGr_Betweenness (lagraph_bindings.rs:539-546) as algo.betweenness calls it (algo_procedures.rs:884-1017): an Advanced
+// method — G->AT must be cached for a directed graph whose structure is not known to be symmetric (LAGRAPH_NOT_CACHED
+// otherwise; an undirected or symmetric graph uses A).  centrality is a full GrB_FP64 vector of the unnormalised scores over
+// the ns sources as given (batched Brandes, fgpu_betweenness); a source >= n is GrB_INVALID_INDEX.
+int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* sources, int32_t ns, char* msg) {
+    clear_msg(msg);
+    if (!centrality || !sources) return fail(msg, GrB_NULL_POINTER, "centrality / sources is NULL");
+    *centrality = nullptr;
+    if (const int r = check_graph(G, msg)) return r;
+    if (ns < 0) return fail(msg, GrB_INVALID_VALUE, "ns is negative");
+    const bool symmetric = G->kind == 0 || (G->kind == 1 && G->is_symmetric_structure == 1);
+    GrB_Matrix AT = symmetric ? G->A : G->AT;
+    if (!AT) return fail(msg, LAGRAPH_NOT_CACHED, "G->AT is required");
+    const uint64_t n = G->A->m.nrows();
+    for (int32_t i = 0; i < ns; ++i)
+        if (sources[i] >= n) return fail(msg, GrB_INVALID_INDEX, "invalid source node");
+    return guarded(msg, [&]() -> int {
+        falkor::Context* c = fgshim::context();
+        double* score = nullptr;
+        check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(double), (void**)&score), "LAGr_Betweenness");
+        GrB_Vector out = fgshim::vector_over_pinned(fgshim::type_fp64(), n, score, 0);
+        const fgpu_info r = fgpu_betweenness(c->raw(), G->A->m.snapshot(), AT->m.snapshot(), nullptr, (const uint64_t*)sources,
+                                             (uint64_t)ns, score, nullptr);
+        if (r != FGPU_OK) { GrB_Vector_free(&out); check(r, "LAGr_Betweenness"); }
+        *centrality = out;
+        return GrB_SUCCESS;
+    });
+}
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC only)")
-int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph, const GrB_Index*, int32_t, char* msg) { if (centrality) *centrality = nullptr; FG_NOT_ON_PATH(LAGr_Betweenness); }
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness only)")
 int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
 #else
 // ---- LAGraphX -----------------------------------------------------------------------------------------------------------
@@ -307,7 +337,7 @@ int LAGr_BreadthFirstSearch_Extended(GrB_Vector* level, GrB_Vector* parent, LAGr
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness only)")
 int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable, LAGraph_Graph, GrB_Vector, char* msg) {
     if (scores) *scores = nullptr;
     if (reachable) *reachable = nullptr;

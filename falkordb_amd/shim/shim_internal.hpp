@@ -108,6 +108,7 @@ falkor::Context* context();                      // the context GxB_init made; n
 GB_Type_opaque* type_int32();
 GB_Type_opaque* type_int64();
 GB_Type_opaque* type_fp32();
+GB_Type_opaque* type_fp64();
 // a vector of n entries over a pinned result block of the engine (fgpu_host_alloc; released with fgpu_free): absent == 0
 // every entry is stored, 1: negative entries are absent (BFS level / parent), 2: zero entries are absent (degrees)
 GB_Vector_opaque* vector_over_pinned(GB_Type_opaque* type, GrB_Index n, void* pinned, int absent);

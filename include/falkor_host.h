@@ -144,7 +144,7 @@ int fh_cond_traverse_batch(fh_graph* g, const char* spec, const int64_t* src, co
                            int64_t** out_edge, uint64_t* n, uint64_t** null_rows, uint64_t* n_null,
                            uint64_t* flops);                                            /* cond_traverse.rs:452-751 */
 /* duration (ns) of the C++ operator inside this thread's last fh_cond_traverse_batch / fh_algo_bfs / fh_algo_pagerank /
- * fh_algo_wcc call:
+ * fh_algo_wcc / fh_algo_betweenness call:
  * what the operator costs without the ctypes harness' result copies (tools/bench_paths.py host) */
 uint64_t fh_last_op_ns(void);
 int fh_cond_traverse_eligible(const char* spec);                                       /* cond_traverse.rs:308-316 */
@@ -214,6 +214,17 @@ int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint6
  * index (its rank among the selected nodes in ascending id order), as the reference returns it.  Free both with fh_free. */
 int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, int64_t** component_ids,
                 uint64_t* n);
+
+/* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
+ * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
+ * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).
+ * Rows in ascending node id, deleted nodes dropped; scores[k] = the unnormalised centrality of nodes[k].  samplingSize <= 0
+ * fails with "samplingSize must be a positive integer".  Free both with fh_free. */
+int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
+                        uint64_t** nodes, double** scores, uint64_t* n);
+/* the procedure's source rule alone (algo_procedures.rs:898-975, no GPU): the source indices out of 0..n_nodes, in the order
+ * LAGr_Betweenness receives them.  Free *out with fh_free. */
+int fh_betweenness_sources(uint64_t n_nodes, int64_t sampling_size, int64_t sampling_seed, uint64_t** out, uint64_t* n);
 
 #ifdef __cplusplus
 }

@@ -113,7 +113,10 @@ fgpu_info fgpu_sync(fgpu_ctx* ctx);
  * fgpu_expand*: 2 = (row, vertex) pairs + a stable sort by row, 0 = ballot transpose, 1 = pairs + sort unless the result
  * holds more than 8 entries per vertex; the default), "pinned_results" / "pinned_pool_mb" (result arrays from 256 KiB up to
  * the pool's size come from the context's pinned pool and are filled by DMA; blocks kept for reuse up to that many MiB),
- * "wcc_mode" (fgpu_wcc: 0 = auto, 1 = Afforest with sampling and skip, 2 = one full link pass over every entry of A). */
+ * "wcc_mode" (fgpu_wcc: 0 = auto, 1 = Afforest with sampling and skip, 2 = one full link pass over every entry of A),
+ * "bc_batch" (fgpu_betweenness: sources per batch; 0 = auto, the smallest of 16 / 32 / 64 that covers nsrc, halved until the
+ * workspace fits 3/4 of the free device memory; 1-64 force a width), "bc_direction" (fgpu_betweenness forward levels: 0 = auto,
+ * push or pull by the entries each would read, 1 = push over A only, 2 = pull over At only). */
 fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
 /* Read-back of measurement / test counters kept by the context (a subset of the option names plus counters that
  * have no setter): "dist_force_self" (test-only, set through fgpu_set_option: a communicator of ONE rank still issues the
@@ -122,7 +125,7 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  * far: the launch count of a batch is a difference of two reads), "bfs_pb_last_levels" (levels the search fgpu_bfs_stats last
  * read ran by propagation blocking), "bfs_cp_last_mask" (bit k: fused launch k of that search ran behind the list kernel — a
  * sparse frontier listed into the queue, or a pull of listed candidates), "expand_scan_last_live" / "expand_scan_last_passes" (live source rows and passes of the
- * last whole-frontier fgpu_expand_count), "wcc_mode".  Unknown names return FGPU_INVALID. */
+ * last whole-frontier fgpu_expand_count), "wcc_mode", "bc_batch", "bc_direction".  Unknown names return FGPU_INVALID. */
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value);
 /* name[256]; returns CU count, wave size, LDS bytes per block, total HBM bytes. */
 fgpu_info fgpu_device_info(fgpu_ctx* ctx, char* name, int32_t* cus, int32_t* wave,
@@ -407,6 +410,21 @@ fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat*
  * 0 auto, 1 Afforest with sampling and skip, 2 one full link pass over every entry of A.  nrows == 0 is a no-op. */
 fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
                    int64_t* component, uint64_t stats[4]);
+
+/* Betweenness centrality (batched Brandes): replaces LAGr_Betweenness(&centrality, G, sources, ns, msg) as called by
+ * algo.betweenness (algo_procedures.rs:884-1017; binding lagraph_bindings.rs:539-546).  centrality[v] = the sum over the
+ * sources s of delta_s(v) = sum over out-neighbours w of v with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),
+ * sigma the number of shortest directed paths over A's out-edges, d the BFS depth.  A source never scores for itself; a
+ * duplicate source counts twice; nsrc == 0 gives all zeros; scores are not normalised.  `At` (nullable) is A's transpose —
+ * NULL uses the snapshot's cached transpose (built on first use).  `active_bitmap` (nullable, nrows bits, as fgpu_pagerank)
+ * restricts the run to the induced subgraph of the flagged vertices; the other slots get 0.  centrality[nrows] is a HOST
+ * array (filled by DMA when pinned — fgpu_host_alloc — by staging otherwise).  stats (nullable): [0] batches, [1] forward
+ * levels expanded, summed over batches, [2] adjacency entries read (forward and backward), [3] deepest level.  Errors: NULL
+ * A / centrality, or NULL sources with nsrc > 0: FGPU_NULL_POINTER; non-square A or a mismatched At: FGPU_DIM_MISMATCH; a
+ * source >= nrows: FGPU_OUT_OF_BOUNDS; a source outside active_bitmap: FGPU_INVALID.  Options "bc_batch", "bc_direction".
+ * Repeated calls and every bc_direction give bit-identical output.  nrows == 0 is a no-op. */
+fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
+                           const uint64_t* sources, uint64_t nsrc, double* centrality, uint64_t stats[4]);
 
 /* Level-synchronous BFS: replaces LAGr_BreadthFirstSearch_Extended(level, parent, G,
  * src, max_level, -1, false) as called by algo.BFS (algo_procedures.rs:1079-1088;

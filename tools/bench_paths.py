@@ -16,7 +16,13 @@
           wcc_mode 1 (Afforest, sampling + skip) and 2 (one full link pass); median of 10 synchronised calls, the stats,
           and the full-pass bound (4 nnz(A) + 4 (n + 1) bytes at 8 TB/s)
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|all] [scale]
+  betweenness  algo.betweenness' core (fgpu_betweenness) on RMAT-22 and RMAT-24 (or RMAT-<scale>): 16 sources of seed 0 (ids
+          0..15, R-MAT's hubs), 16 and 256 LCG-drawn sources (samplingSeed 10), each under bc_direction 0 / 1 / 2; median of
+          10 synchronised calls, the stats, fgpu_bfs once per source as a yardstick, and the bound (per batch: the CSR read
+          forward and backward, 2 (4 nnz + 4 (n + 1)) bytes, plus the per-(vertex, source) state written and read,
+          2 n B (8 + 8 + 4) bytes, at 8 TB/s)
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|betweenness|all] [scale]
 """
 import json
 import sys
@@ -244,6 +250,32 @@ def bench_wcc(ctx, scale):
     ctx.set_option("wcc_mode", 0)
 
 
+def bench_betweenness(ctx, scale):
+    from falkordb_amd import host
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    At = A.transpose()
+    n, nnz = A.nrows, A.nvals
+    out = ctx.host_array(n, np.float64)
+    level = ctx.host_array(n, np.int32)
+    for label, src in (("seed0_16", host.betweenness_sources(n, 16, 0)), ("lcg_16", host.betweenness_sources(n, 16, 10)),
+                       ("lcg_256", host.betweenness_sources(n, 256, 10))):
+        tb, _ = timed(ctx, lambda: [engine.bfs(ctx, A, At, int(s), -1, want_parent=False, level_out=level) for s in src],
+                      reps=5, warm=1)
+        for d in (0, 1, 2):
+            ctx.set_option("bc_direction", d)
+            t, (_, st) = timed(ctx, lambda: engine.betweenness(ctx, A, src, At, stats=True, out=out), reps=10, warm=2)
+            width = 16 if len(src) <= 16 else 64
+            bound_ms = st[0] * (2 * (4 * nnz + 4 * (n + 1)) + 2 * n * width * 20) / 8e12 * 1e3
+            print(json.dumps({"path": "betweenness", "scale": scale, "sources": label, "nsrc": len(src), "bc_direction": d,
+                              "n": n, "nnz": nnz, "ms": round(t * 1e3, 3), "batches": st[0], "forward_levels": st[1],
+                              "entries_read": st[2], "deepest": st[3], "bound_ms": round(bound_ms, 4),
+                              "bfs_x_sources_ms": round(tb * 1e3, 3),
+                              "note": "host clock around a synchronised call, median of 10 after 2 warm-up; bfs = fgpu_bfs "
+                                      "once per source, median of 5; bound = per batch 2 (4 nnz + 4 (n + 1)) + 2 n B 20 "
+                                      "bytes at 8 TB/s"}), flush=True)
+    ctx.set_option("bc_direction", 0)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     scale = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -283,6 +315,11 @@ if __name__ == "__main__":
         c = engine.Context(0)
         for sc in ([scale] if scale else [22, 24]):
             bench_wcc(c, sc)
+        c.close()
+    if what in ("betweenness", "all"):
+        c = engine.Context(0)
+        for sc in ([scale] if scale else [22, 24]):
+            bench_betweenness(c, sc)
         c.close()
     if what in ("host", "all"):
         bench_host(scale or 18)
