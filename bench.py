@@ -33,8 +33,13 @@ replicated, no collective on the data path (k-hop MATCH shards i
 RMAT-26 BFS over column slabs with one RCCL frontier all-gather-v per level (BASELINE config 4) runs as a secondary leg
 of the same line (`secondary.bfs26_dist`; its single-GPU base point is `secondary.bfs26` of the N = 1 line).
 
-Rank 0 prints TWO lines: `DETAIL {...}` (every leg in full; also written to bench_detail.json) and then, LAST, the
-compact bench line (< 4 KB, asserted): metric / value / config of the headline, `roofline` of its dominant kernel
+A plain run does only what the headline needs: it builds the inputs, runs the W + K steps, dumps the outputs when asked and
+prints the line below with `roofline` / `cpu_baseline` null, `parity` {"checked": false} and `secondary` empty.  `--full`
+adds every untimed leg after the timed region (the fields below, the secondary legs, the live PMC passes); `--quick` and
+the `--no-*` switches then trim that set.
+
+Rank 0 prints TWO lines: `DETAIL {...}` (every leg that ran; also written to bench_detail.json) and then, LAST, the
+compact bench line (< 4 KB, asserted): metric / value / config of the headline, with --full `roofline` of its dominant kernel
 (xp_stream_kernel: HIP-event average over one scan replayed, compulsory bytes per launch, live PMC traffic; `hop` = the
 count hop, stream + fold, against the same bytes), `cpu_baseline` (the oracle's OpenMP Gustavson chain on this box's host
 cores, bounded sample, quartiles; `probe` = what was looked for of the reference's own CPU library; `scipy` = a second point),
@@ -740,10 +745,11 @@ def u64_halves(x):
 def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, reduce_sum):
     """THE timed region of the bench line (module docstring): K WHOLE-FRONTIER calls of the 3-hop MATCH — one
     fgpu_expand_count per label scan, all ~N/16 sources of the label in the call, clean layers, count + checksum — W untimed
-    calls before.  Returns (line fields, detail, graph tuple)."""
+    calls before; with --full (rank 0) the untimed legs over the same label after them.  Returns (line fields, detail, graph
+    tuple)."""
     hops, B = 3, 1024
     t0 = time.time()
-    want_host = rank == 0 and not args.no_parity
+    want_host = rank == 0 and args.full and not args.no_parity
     A, dp, dm, host = khop_inputs(ctx, scale, args.edge_factor, want_host=want_host)
     ctx.sync()
     t_build = time.time() - t0
@@ -794,7 +800,7 @@ def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, redu
     # what a NEW matrix version costs once the pools are warm (t_prep above also grew them): a second snapshot of the same
     # matrix (transposed twice on the device: no cache is shared with A), its first batch against a steady one
     snap_prep = None
-    if rank == 0 and scale <= 24:
+    if rank == 0 and args.full and scale <= 24:
         try:
             t_ = time.perf_counter()
             engine.expand_count(ctx, batch0, *clean)
@@ -824,7 +830,7 @@ def khop_headline(ctx, engine, args, scale, rank, world, fence, reduce_max, redu
            "timed": {"steps": args.steps, "warmup": args.warmup, "seconds": round(dt, 5), "flops": int(flops_all),
                      "out_nnz": int(nnz_all), "rank0_checksum": f"{cs:016x}", "TEPS": line["value"],
                      "step0": {"nnz": int(scan0[0]), "checksum": f"{scan0[1]:016x}", "flops": int(scan0[2])} if scan0 else None}}
-    if rank != 0:
+    if rank != 0 or not args.full:
         return line, det, (A, dp, dm, host, batch0, None)
     # ---- untimed legs over the same label: the calls it replaces, count only, dirty layers, lanes, kernel table -------
     P = srcs[:args.sources_per_call] if args.sources_per_call > 0 else srcs
@@ -1452,7 +1458,10 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="--leg bfs: run the multi-rank code path even with one rank")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (fgpu_set_option)")
-    ap.add_argument("--quick", action="store_true", help="headline + parity + CPU baseline only (no secondary legs, no PMC)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every untimed leg: kernel table and roofline, oracle parity, CPU baseline, "
+                         "secondary legs, live PMC passes (off: the headline alone; --quick and the --no-* switches trim this set)")
+    ap.add_argument("--quick", action="store_true", help="--full: headline legs + parity + CPU baseline only (no secondary legs, no PMC)")
     ap.add_argument("--khop-extra-scales", default="24,26", help="further scales of the k-hop leg (secondary)")
     ap.add_argument("--bfs-threads", type=int, default=0, help="--leg bfs: also run the searches from this many query threads")
     ap.add_argument("--no-lanes-sweep", action="store_true", help="skip the run of the timed batches from 2 / 3 / 4 query threads")
@@ -1579,7 +1588,7 @@ def main():
     detail = {"headline": head, "device": info}
     sec = {}
     roofline = parity = cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         first, roofline, scan0 = extra
         key = "khop%d" % scale
         sec[key] = {"count_only_TEPS": head["count_only"]["TEPS"], "count_only_ms": head["count_only"]["ms_per_call"],
@@ -1615,10 +1624,10 @@ def main():
             if args.no_cpu_baseline:
                 cpu = None
     host = None
-    full = rank == 0 and world == 1 and not args.quick
+    legs = args.full and rank == 0 and world == 1 and not args.quick
     pmc = None
     bfs22 = None
-    if full:
+    if legs:
         # ---- BFS + boolean SpMV at the headline scale (BASELINE config 2 when it is 22), on the same adjacency -------
         if not args.no_bfs:
             bfs22, _, At, roots, _ = bfs_single_leg(ctx, engine, args, scale, A=A, steps=args.bfs_steps, warmup=8)
@@ -1627,7 +1636,7 @@ def main():
             At.free()
             detail["bfs%d" % scale] = bfs22
     dp.free(); dm.free(); A.free()
-    if full:
+    if legs:
         # ---- k-hop at the other scales (BASELINE config 3 = RMAT-24; the metric's RMAT-26) ---------------------------
         for sc in [int(x) for x in args.khop_extra_scales.split(",") if x.strip() and int(x) != scale]:
             leg, (KA, Kdp, Kdm, Khost, kb) = khop_leg(ctx, engine, args, sc, 16 if sc <= 24 else 4,
@@ -1697,7 +1706,7 @@ def main():
                     d["traffic"] = hbm(d["kernel"])
             if bfs22 and bfs22.get("spmv_full_pass"):
                 bfs22["spmv_full_pass"]["traffic"] = hbm(bfs22["spmv_full_pass"]["kernel"])
-    elif world > 1:
+    elif world > 1 and args.full:
         # ---- N > 1: the k-hop metric at its OTHER scale, RMAT-26 (north_star names it), the same way: every rank scans its own
         # slice of a label over a replicated adjacency (4.3 GB), no collective; the sums meet in one all-reduce afterwards -------
         if not args.quick and not one_device:

@@ -500,7 +500,7 @@ def test_bench_spawns_its_own_ranks_from_a_plain_shell():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(FGPU_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "18",
-           "--no-cpu-baseline", "--no-pmc", "--no-varlen"]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--no-varlen"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -620,7 +620,7 @@ def test_bench_line_with_two_ranks_on_one_device(tmp_path):
     env = dict(os.environ, FGPU_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--scale", "18",
-           "--no-cpu-baseline", "--no-pmc", "--no-varlen"]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--no-varlen"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -655,3 +655,25 @@ def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
         assert a.dtype == np.float64 and a.shape == (2,)
         assert (int(a[0]) << 32) | int(a[1]) == v, name
     assert want["nnz"] > 0 and want["flops"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """A run without --full builds the inputs, runs the warm-up and timed steps and prints the line: the headline fields as a
+    --full run states them, and none of the untimed legs (roofline, CPU baseline, parity, secondary figures) behind it."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--scale", "18"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("traversed edges/sec (TEPS) on k-hop MATCH") and d["unit"] == "TEPS"
+    assert d["higher_is_better"] is True and d["dtype"] == "u32" and d["n_gpus"] == 1
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] == {"checked": False} and d["secondary"] == {}
+    det = json.loads([l for l in r.stdout.splitlines() if l.startswith("DETAIL ")][-1][len("DETAIL "):])
+    assert sorted(det) == ["device", "headline"]
+    assert det["headline"]["timed"]["steps"] == 2 and "kernels" not in det["headline"] and "batch_1024" not in det["headline"]
