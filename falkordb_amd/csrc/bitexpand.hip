@@ -1338,8 +1338,11 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
     const bool will_sparse = m->nnz && s.flag.p != nullptr && s.nz_rows * 8 < (u64)s.n &&
                              bp_sparse_fits(ctx, mode == 2 ? (size_t)s.w * 256 * sizeof(u64) : 0);
     const BpXPlan* xp = nullptr;
-    if (ca && t && !will_sparse && !s.lazy && s.ws >= 2 && s.ws <= 16 && (u64)s.n * s.ws * 8 >= (u64)ctx->opt.expand_xcd_min_mb << 20)
+    if (ca && t && !will_sparse && !s.lazy && s.ws >= 2 && s.ws <= 16 && (u64)s.n * s.ws * 8 >= (u64)ctx->opt.expand_xcd_min_mb << 20) {
         FGPU_TRY(bp_xplan(ctx, m, t, &xp));
+        // (a fold whose checksum tables and stage do not fit the LDS limit: the plain pull, like a plan that is not usable)
+        if (xp && !bp_xfold_fits(ctx, s.ws, mode, mode == 2 ? (size_t)s.w * 256 * sizeof(u64) : 0)) xp = nullptr;
+    }
     // the layout of the state: the count hop reads what its plan gathers from (hot-first per partition when the partitioned
     // form runs, vertex order otherwise); a mid-chain hop about to feed such a count hop WRITES its rows in that layout
     if (ca) FGPU_TRY(bp_relayout(ctx, s, xp ? bp_xplan_perm(xp) : nullptr));

@@ -54,5 +54,7 @@ const u32* bp_xplan_perm(const BpXPlan* p);   // slot of row u of X in the state
 // their side-buffer slot; `side` is zeroed by the caller, the delta fix-ups and the side-row count follow in bp_hop_impl
 fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,
                          u64* side, size_t lds_tables, u64 xrows);
+// whether the fold of a row width / mode fits the LDS limit next to `lds_tables` bytes of checksum tables (MODE 2)
+bool bp_xfold_fits(const fgpu_ctx* ctx, u32 ws, int mode, size_t lds_tables);
 
 }  // namespace fgpu

@@ -54,8 +54,16 @@ struct BpXPlan {
     uint8_t* cshared = nullptr;    // 1: that run began in an earlier chunk (its pieces meet through atomics)
     u32* zrows = nullptr;          // the partial rows that receive pieces from several chunks (zeroed before every hop)
     u32 nzrows = 0;
-    u64* ne = nullptr;             // [8][ng] bit r: (partition, row 64 g + r) has entries
+    u64* ne = nullptr;             // [8][ng] bit r: (partition, row 64 g + r) has entries in the stream
     u32* pbase = nullptr;          // [8][ng] partial row of the group's first non-empty row
+    // direct entries (expand_xp_direct = 1): a (partition, row) run of ONE entry is left out of the stream — its partial row would
+    // be a copy of one row of X, gathered, flushed through the tile, written and read back — and the fold reads that row of X
+    // itself.  At RMAT-22 these are 43 % of the runs (the partial rows) and 5 % of the entries, most of them hot rows of X.
+    int direct = 0;                // the mode the plan was built under (0: every run is streamed, de / dbase / dcol stay null)
+    u64 ndirect = 0;
+    u64* de = nullptr;             // [8][ng] bit r: (partition, row 64 g + r) is one direct entry
+    u32* dbase = nullptr;          // [8][ng] index in dcol of the group's first direct entry
+    u32* dcol = nullptr;           // the direct entries' columns (slots of X, like pcol's), partition-major, rows ascending
     // slot of X's row u in the state this plan gathers from (nullptr: slot = u).  Rows are ranked by how often they are gathered
     // (out-degree of u in m, descending) and dealt to the partitions in turn — slot = (rank % 8) x range + rank / 8 — so every
     // partition holds an eighth of the hot rows, packed hot-first: a 128-byte line then carries two rows (64-byte rows) of about
@@ -65,12 +73,16 @@ struct BpXPlan {
 };
 const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm : nullptr; }
 
+static void xp_free_buffers(fgpu_ctx* ctx, BpXPlan* p) {
+    for (void** b : {(void**)&p->pcol, (void**)&p->pstart_dev, (void**)&p->cstart, (void**)&p->crun0, (void**)&p->cshared, (void**)&p->zrows,
+                     (void**)&p->ne, (void**)&p->pbase, (void**)&p->perm, (void**)&p->de, (void**)&p->dbase, (void**)&p->dcol}) {
+        ctx->dev_free(*b);
+        *b = nullptr;
+    }
+}
 void bp_xplan_release(fgpu_ctx* ctx, BpXPlan* p) {
     if (!p) return;
-    if (ctx) {
-        ctx->dev_free(p->pcol); ctx->dev_free(p->pstart_dev); ctx->dev_free(p->cstart); ctx->dev_free(p->crun0); ctx->dev_free(p->cshared); ctx->dev_free(p->zrows);
-        ctx->dev_free(p->ne); ctx->dev_free(p->pbase); ctx->dev_free(p->perm);
-    }
+    if (ctx) xp_free_buffers(ctx, p);
     delete p;
 }
 
@@ -173,6 +185,46 @@ __global__ void xp_chunks_kernel(const u32* __restrict__ off, const u32* __restr
     }
 }
 
+// direct entries (expand_xp_direct = 1).  keep[p] = 0 when entry p is a run of its own: it opens a run and the next entry opens
+// another (a partition's first entry opens one) or the stream ends.  The exclusive scan of keep maps every position of the old
+// stream to the new one — of an entry that stays: its slot; of one that goes: the next staying entry's — so the run starts
+// off[] and the partition starts remap through it, and p - pos[p] numbers the direct entries in stream order.
+__global__ void xp_keep_kernel(const u32* __restrict__ pcol, u32 nnz, u32* __restrict__ keep) {
+    for (u32 p = blockIdx.x * 256 + threadIdx.x; p <= nnz; p += gridDim.x * 256)
+        keep[p] = p < nnz && !((pcol[p] & XP_FIRST) && (p + 1 == nnz || (pcol[p + 1] & XP_FIRST))) ? 1u : 0u;
+}
+__global__ void xp_split_kernel(const u32* __restrict__ pcol, const u32* __restrict__ pos, u32 nnz, u32* __restrict__ kept,
+                                u32* __restrict__ dcol) {
+    for (u32 p = blockIdx.x * 256 + threadIdx.x; p < nnz; p += gridDim.x * 256) {
+        const u32 w = pcol[p], q = pos[p];
+        if (pos[p + 1] != q) kept[q] = w;
+        else dcol[p - q] = w & ~XP_FIRST;
+    }
+}
+// a wavefront per (partition, group), over the OLD run starts: the direct bitmap and the direct index of the group's first row
+__global__ __launch_bounds__(256) void xp_direct_groups_kernel(const u32* __restrict__ off, const u32* __restrict__ pos, u32 n, u32 ng,
+                                                               u64* __restrict__ de, u32* __restrict__ dbase) {
+    const u32 lane = lane_id();
+    const u32 wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    for (u32 t = wave; t < 8 * ng; t += nwaves) {
+        const u32 x = t / ng, g = t % ng;
+        const u32 v = g * 64 + lane;
+        const size_t i = (size_t)x * n + (v < n ? v : n - 1);
+        const u64 dw = __ballot(v < n && off[i + 1] - off[i] == 1u);
+        if (lane == 0) {
+            const u32 o = off[(size_t)x * n + (size_t)g * 64];
+            de[t] = dw;
+            dbase[t] = o - pos[o];
+        }
+    }
+}
+// the run starts and the partition starts, moved to the stream of the staying entries (in place: a thread per word)
+__global__ void xp_remap_kernel(u32* __restrict__ off, u64 total, const u32* __restrict__ pos, u32* __restrict__ pstart) {
+    const u64 i0 = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i0 < 9) pstart[i0] = pos[pstart[i0]];
+    for (u64 i = i0; i <= total; i += (u64)gridDim.x * 256) off[i] = pos[off[i]];
+}
+
 __global__ void xp_shared_rows_kernel(const u32* __restrict__ crun0, const uint8_t* __restrict__ cshared, u32 nchunks,
                                       u32* __restrict__ zrows, u32* __restrict__ count) {
     const u32 c = blockIdx.x * 256 + threadIdx.x;
@@ -195,37 +247,36 @@ __global__ void xp_rank_kernel(const u32* __restrict__ by_rank, u32 n, u32 prang
     for (u32 r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) perm[by_rank[r]] = (r & 7u) * prange + (r >> 3);
 }
 
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out);
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, const BpXPlan** out);
 // The plan is an optional accelerator: when its build fails (its temporaries are large — 64 bytes per vertex and 8 per entry) the
 // half-built plan's buffers are freed, it stays attached as "not usable" (no second attempt per snapshot), the error is dropped
 // and the hop falls back to the plain pull.
+// A plan is kept per expand_xp_direct mode (a plan built under one mode is never handed to a hop expecting the other); the fold
+// takes the form of its plan.
 fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
-    const fgpu_info i = bp_xplan_build(ctx, m, t, out);
+    const int direct = ctx->opt.expand_xp_direct ? 1 : 0;
+    const fgpu_info i = bp_xplan_build(ctx, m, t, direct, out);
     if (i == FGPU_OK) return FGPU_OK;
     *out = nullptr;
-    if (t && t->bp_xplan && !t->bp_xplan->usable) {
-        BpXPlan* p = t->bp_xplan;
-        ctx->dev_free(p->pcol); ctx->dev_free(p->pstart_dev); ctx->dev_free(p->cstart); ctx->dev_free(p->crun0); ctx->dev_free(p->cshared);
-        ctx->dev_free(p->zrows); ctx->dev_free(p->ne); ctx->dev_free(p->pbase); ctx->dev_free(p->perm);
-        p->pcol = nullptr; p->pstart_dev = nullptr; p->cstart = nullptr; p->crun0 = nullptr; p->cshared = nullptr; p->zrows = nullptr;
-        p->ne = nullptr; p->pbase = nullptr; p->perm = nullptr;
+    if (t && t->bp_xplan[direct] && !t->bp_xplan[direct]->usable) {
+        xp_free_buffers(ctx, t->bp_xplan[direct]);
         (void)hipGetLastError();
         set_error("%s", "");
         return FGPU_OK;
     }
     return i;                                                // (failed before a plan was attached: an argument / state error)
 }
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, const BpXPlan** out) {
     *out = nullptr;
     if (!ctx->opt.expand_xcd || !t || t->is_hyper()) return FGPU_OK;
     if (t->ncols >= (1ull << 31) || t->nrows >= 0xFFFFFFC0ull || t->nnz < 4096 || t->nnz >= 0x7FFFFFFFull) return FGPU_OK;
     std::lock_guard<std::mutex> idx_guard(m->idx_mu);
-    if (t->bp_xplan) { if (t->bp_xplan->usable) *out = t->bp_xplan; return FGPU_OK; }
+    if (t->bp_xplan[direct]) { if (t->bp_xplan[direct]->usable) *out = t->bp_xplan[direct]; return FGPU_OK; }
     BpXPlan* xp = new (std::nothrow) BpXPlan();
     FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
-    t->bp_xplan = xp;                                          // (published as "not usable" until the build below completes)
+    t->bp_xplan[direct] = xp;                                  // (published as "not usable" until the build below completes)
     const u32 n = (u32)t->nrows, ng = (n + 63) / 64;
-    xp->n = n; xp->ng = ng; xp->nentries = t->nnz;
+    xp->n = n; xp->ng = ng; xp->nentries = t->nnz; xp->direct = direct;
     hipStream_t st = ctx->stream();
     const u64 total = 8ull * n;
     DevBuf<u32> off, ridx;
@@ -258,6 +309,35 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         hipLaunchKernelGGL(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, (u32)t->nnz,
                            xp->pcol, off.p);
         hipLaunchKernelGGL(xp_run_tails_kernel, dim3(64, 8), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, off.p);
+        FGPU_HIP(hipGetLastError());
+    }
+    if (direct) {   // the single-entry runs leave the stream; everything below is built over the runs that stay
+        const u32 nnz = (u32)t->nnz;
+        DevBuf<u32> pos;
+        FGPU_TRY(pos.alloc(ctx, (size_t)nnz + 1));
+        u32 egrid = cdiv((u64)nnz + 1, 256 * 4);
+        if (egrid > (u32)ctx->cus * 16) egrid = ctx->cus * 16;
+        hipLaunchKernelGGL(xp_keep_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, nnz, pos.p);
+        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(scan_u32(ctx, pos.p, pos.p, (u64)nnz + 1, nullptr));
+        u32 nkept = 0;
+        FGPU_TRY(read_u32(ctx, pos.p + nnz, &nkept));
+        xp->ndirect = nnz - nkept;
+        u32* kept = nullptr;
+        FGPU_TRY(ctx->dev_alloc((void**)&kept, ((size_t)nkept + 64) * sizeof(u32)));
+        FGPU_TRY(ctx->dev_alloc((void**)&xp->dcol, ((size_t)xp->ndirect + 1) * sizeof(u32)));
+        FGPU_HIP(hipMemsetAsync(xp->dcol, 0, sizeof(u32), st));   // (index 0 is what the fold loads for a row without one)
+        hipLaunchKernelGGL(xp_split_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, (const u32*)pos.p, nnz, kept, xp->dcol);
+        FGPU_HIP(hipGetLastError());
+        ctx->dev_free(xp->pcol);
+        xp->pcol = kept;
+        FGPU_TRY(ctx->dev_alloc((void**)&xp->de, (size_t)8 * ng * sizeof(u64)));
+        FGPU_TRY(ctx->dev_alloc((void**)&xp->dbase, ((size_t)8 * ng + 1) * sizeof(u32)));
+        u32 ggrid = cdiv((u64)8 * ng, 4);
+        if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
+        hipLaunchKernelGGL(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng, xp->de, xp->dbase);
+        FGPU_HIP(hipGetLastError());
+        hipLaunchKernelGGL(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev);
         FGPU_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(xp_nonempty_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, total, ridx.p);
@@ -443,14 +523,19 @@ __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ 
 // the fold: Y[v] = OR over the partitions of v's partial rows, then exactly what the plain pull does with a finished row —
 // a touched row (a delta layer names it) goes to its slot of the side buffer, any other is counted (MODE 2: and its checksum
 // terms summed through the nibble tables in LDS) and never written.  A wavefront per 64-row group, 64 / QL rows per step,
-// the (up to) 8 partial rows of a vertex in flight together.
+// the (up to) 8 partial rows of a vertex in flight together.  DIRECT: a (partition, row) pair that is one direct entry reads
+// that entry's row of X in place of a partial row — the columns of the group's direct entries are loaded once per group, a
+// lane per row, and every step takes its rows' ones by a shuffle, so a step still issues its 8 loads together, each from an
+// address picked without a branch (partial row, row of X or the zero row).
 __device__ __forceinline__ u64 xp_uniform64(u64 v) {
     return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32)) << 32) | (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)v);
 }
-template <int QL, int MODE, bool NT>
+template <int QL, int MODE, bool NT, bool DIRECT>
 __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __restrict__ ne, const u32* __restrict__ pbase, u32 ng,
                                                       const uint4* __restrict__ partial, BpFinal fin, uint4* __restrict__ side,
-                                                      u32 zrow /* an all-zero partial row */) {
+                                                      u32 zrow /* an all-zero partial row */, const u64* __restrict__ de,
+                                                      const u32* __restrict__ dbase, const u32* __restrict__ dcol,
+                                                      const uint4* __restrict__ x) {
     constexpr int SLOTS = 64 / QL;
     extern __shared__ u64 s_tab[];
     if (MODE == 2) {
@@ -464,8 +549,8 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
     u64* stg = s_tab + (MODE == 2 ? (size_t)fin.w * 256 : 0) + (size_t)(threadIdx.x >> 6) * (32 * STR);   // MODE 2: 32 staged rows a wavefront
     u64 f_cnt = 0, f_sum = 0;
     for (u32 g = wave; g < ng; g += nwaves) {
-        u64 nw[8];
-        u32 pb[8];
+        u64 nw[8], dw[8];
+        u32 pb[8], dc[8];
         u64 any = 0ull;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -473,7 +558,29 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
             pb[k] = (u32)__builtin_amdgcn_readfirstlane((int)pbase[(size_t)k * ng + g]);
             any |= nw[k];
         }
+        if (DIRECT) {
+            // lane k < 8 loads partition k's direct word and base (two loads, one round trip) and every lane takes them by
+            // shuffles: they stay in vector registers — as 24 more scalars next to nw / pb they ran the kernel out of SGPRs, and
+            // hipcc then issued the group's header loads one round trip at a time (a fold 45 % slower)
+            const size_t kl = (size_t)(lane & 7u) * ng + g;
+            const u64 dl = de[kl];
+            const u32 bl = dbase[kl];
+            u64 dany = 0ull;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                dw[k] = ((u64)(u32)__shfl((int)(u32)(dl >> 32), k, 64) << 32) | (u64)(u32)__shfl((int)(u32)dl, k, 64);
+                dc[k] = (u32)__shfl((int)bl, k, 64);
+                dany |= dw[k];
+            }
+            any |= xp_uniform64(dany);
+        }
         if (!any) continue;
+        if (DIRECT) {
+            const u64 lanes_below = (1ull << lane) - 1ull;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)     // lane r: the column of (partition k, row 64 g + r) when that is a direct entry
+                dc[k] = dcol[((dw[k] >> lane) & 1ull) ? dc[k] + (u32)__popcll(dw[k] & lanes_below) : 0u];
+        }
         const u64 tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
         const u32 tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
         const u64 lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
@@ -503,7 +610,12 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
                 } else {
                     idx = ((nw[k] >> r) & 1ull) ? pb[k] + (u32)__popcll(nw[k] & below) : zrow;
                 }
-                pv[k] = NT ? xp_load_nt(&partial[(size_t)idx * QL + wl]) : partial[(size_t)idx * QL + wl];
+                const uint4* src = partial + (size_t)idx * QL + wl;
+                if (DIRECT) {
+                    const u32 u = (u32)__shfl((int)dc[k], (int)r, 64);
+                    src = ((dw[k] >> r) & 1ull) ? x + (size_t)u * QL + wl : src;
+                }
+                pv[k] = NT ? xp_load_nt(src) : *src;
             }
             uint4 a = or4(or4(or4(pv[0], pv[1]), or4(pv[2], pv[3])), or4(or4(pv[4], pv[5]), or4(pv[6], pv[7])));
             const bool touched = (tw >> r) & 1ull;
@@ -562,10 +674,19 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
     bp_block_add2(f_cnt, MODE == 2 ? f_sum : 0ull, fin.acc);
 }
 
+// LDS of the fold: MODE 2's checksum tables + a stage of 32 rows per wavefront
+static size_t xp_fold_lds(u32 ws, int mode, size_t lds_tables) {
+    return mode == 2 ? lds_tables + (size_t)(XP_FOLD_THREADS / 64) * 32 * (ws + 1) * sizeof(u64) : 0;
+}
+bool bp_xfold_fits(const fgpu_ctx* ctx, u32 ws, int mode, size_t lds_tables) {
+    return xp_fold_lds(ws, mode, lds_tables) <= (size_t)ctx->opt.lds_limit;
+}
+
 fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,
                          u64* side, size_t lds_tables, u64 xrows) {
     FGPU_REQUIRE(xp && xp->usable && ws >= 2 && ws <= 16 && (ws & (ws - 1)) == 0, FGPU_INVALID, "partitioned pull: bad plan / row width");
     FGPU_REQUIRE(mode == 1 || mode == 2, FGPU_INVALID, "partitioned pull: counting hops only");
+    ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
     const u32 ql = ws / 2;
     hipStream_t st = ctx->stream();
     DevBuf<uint4> partial;
@@ -618,16 +739,18 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
         const u32 fthreads = XP_FOLD_THREADS;
         u32 grid = cdiv(xp->ng, fthreads / 64);
         if (grid > (u32)ctx->cus * (2048u / fthreads)) grid = ctx->cus * (2048u / fthreads);
-        // MODE 2: the checksum tables + a stage of 32 rows per wavefront (xp_fold_kernel)
-        const size_t lds = mode == 2 ? lds_tables + (size_t)(fthreads / 64) * 32 * (2 * ql + 1) * sizeof(u64) : 0;
+        // (the count-hop planner takes the plain pull when this does not fit: bp_xfold_fits)
+        const size_t lds = xp_fold_lds(ws, mode, lds_tables);
         FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID, "partitioned pull: the fold needs %zu B of LDS", lds);
-#define XP_FOLD3(Q, M, N)                                                                                                        \
+#define XP_FOLD4(Q, M, N, D)                                                                                                     \
         do {                                                                                                                     \
             if (lds > 48 * 1024)                                                                                                 \
-                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_kernel<Q, M, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((xp_fold_kernel<Q, M, N>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase, xp->ng,  \
-                               (const uint4*)partial.p, fin, (uint4*)side, xp->nprows);                                                                         \
+                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_kernel<Q, M, N, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((xp_fold_kernel<Q, M, N, D>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase, xp->ng,  \
+                               (const uint4*)partial.p, fin, (uint4*)side, xp->nprows, (const u64*)xp->de, (const u32*)xp->dbase,                 \
+                               (const u32*)xp->dcol, (const uint4*)x);                                                                             \
         } while (0)
+#define XP_FOLD3(Q, M, N) do { if (xp->direct) XP_FOLD4(Q, M, N, true); else XP_FOLD4(Q, M, N, false); } while (0)
 #define XP_FOLD2(Q, M) do { if (ctx->opt.expand_nt & 4) XP_FOLD3(Q, M, true); else XP_FOLD3(Q, M, false); } while (0)
 #define XP_FOLD(Q) do { if (mode == 2) XP_FOLD2(Q, 2); else XP_FOLD2(Q, 1); } while (0)
         switch (ql) {
@@ -639,6 +762,7 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
 #undef XP_FOLD
 #undef XP_FOLD2
 #undef XP_FOLD3
+#undef XP_FOLD4
         FGPU_HIP(hipGetLastError());
     }
     (void)t;

@@ -105,6 +105,8 @@ struct fgpu_options {  // fgpu_set_option
                                // partition, partial rows folded per vertex (bitpart.hip), 0 = every workgroup gathers from all of X (A/B)
     int expand_xcd_relabel = 1; // ... and the state it reads is laid out hot-first per partition by the hop that produces it (0 = vertex order; A/B)
     int expand_xcd_min_mb = 32; // ... when the bit state holds at least this many MiB (8 L2s of 4 MiB; below that the plain pull)
+    int expand_xp_direct = 1;   // ... 1 = a (partition, row) run of ONE entry leaves the stream: the fold reads that row of X itself
+                               // instead of a partial row the stream kernel copied out of it (bitpart.hip), 0 = every run is streamed (A/B)
     int expand_scan_min = 2048; // fgpu_expand_count: a call with more source rows than this is a WHOLE-FRONTIER call (spgemm.hip
                                // expand_count_scan): live rows filtered and compacted on the device, cut into passes (0 = never)
     int expand_scan_rows = 1024; // ... live rows per pass: 1024 = 16 words = one 128-byte line per vertex of the bit state
@@ -188,6 +190,7 @@ struct fgpu_ctx {
     std::atomic<uint32_t> bfs_cp_last{0};   // ... and the fused launches of that search that ran behind bfs_pb_list_kernel ("bfs_cp_last_mask")
     std::atomic<uint32_t> bfs_pb_last{0};   // levels the search fgpu_bfs_stats last read ran by propagation blocking ("bfs_pb_last_levels")
     std::atomic<uint32_t> scan_last_live{0}, scan_last_passes{0};   // the last such call: live source rows, passes ("expand_scan_*")
+    std::atomic<uint64_t> xp_last_direct{0};    // single-entry runs the fold read from X in the last partitioned count hop ("expand_xp_last_direct")
     std::atomic<uint64_t> expand_launches{0};   // kernels launched by fgpu_expand* (fgpu_get_option "expand_kernel_launches")
     // kernel profiler (measurement hook): off unless fgpu_prof_enable(ctx, 1)
     bool prof_on = false;
@@ -345,8 +348,9 @@ struct fgpu_mat {
     mutable uint32_t n_bp_sitems = 0;
     mutable uint64_t* bp_split_bits = nullptr;  // on the cached transpose: bit v set <=> row v is cut into several items
     mutable fgpu::PrParts* pr_parts = nullptr;  // pagerank.hip: this matrix split into 8 column ranges (one per XCD), lazily, owned
-    mutable fgpu::BpXPlan* bp_xplan = nullptr; // on the cached transpose: the XCD-partitioned layout of the dense count hop
-                                               // (bitpart.hip, built on the first such hop; released by bp_xplan_release)
+    mutable fgpu::BpXPlan* bp_xplan[2] = {nullptr, nullptr};   // on the cached transpose: the XCD-partitioned layout of the dense
+                                               // count hop, one per expand_xp_direct mode (bitpart.hip, built on the first such hop
+                                               // under that mode; released by bp_xplan_release)
     bool is_hyper() const { return hrows != nullptr; }
 };
 

@@ -811,6 +811,8 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "bfs_pb_last_levels")) *value = ctx->bfs_pb_last.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_scan_last_live")) *value = ctx->scan_last_live.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_scan_last_passes")) *value = ctx->scan_last_passes.load(std::memory_order_relaxed);
+    else if (!strcmp(name, "expand_xp_direct")) *value = ctx->opt.expand_xp_direct;
+    else if (!strcmp(name, "expand_xp_last_direct")) *value = (int64_t)ctx->xp_last_direct.load(std::memory_order_relaxed);
     else { set_error("fgpu_get_option: unknown name '%s'", name); return FGPU_INVALID; }
     return FGPU_OK;
 }
@@ -858,6 +860,9 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     } else if (!strcmp(name, "expand_xcd_min_mb")) {
         FGPU_REQUIRE(value >= 0 && value <= (1 << 20), FGPU_INVALID, "expand_xcd_min_mb out of range");
         ctx->opt.expand_xcd_min_mb = (int)value;
+    } else if (!strcmp(name, "expand_xp_direct")) {
+        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_direct must be 0 (every run streamed) or 1 (single-entry runs read by the fold)");
+        ctx->opt.expand_xp_direct = (int)value;
     } else if (!strcmp(name, "expand_scan_min")) {
         FGPU_REQUIRE(value >= 0 && value <= (1ll << 31), FGPU_INVALID, "expand_scan_min out of range");
         ctx->opt.expand_scan_min = (int)value;
