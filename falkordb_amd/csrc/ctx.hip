@@ -802,7 +802,10 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "expand_scan_rows")) *value = ctx->opt.expand_scan_rows;
     else if (!strcmp(name, "expand_scan_lanes")) *value = ctx->opt.expand_scan_lanes;
     else if (!strcmp(name, "expand_nt")) *value = ctx->opt.expand_nt;
-    else if (!strcmp(name, "bfs_pb")) *value = ctx->opt.bfs_pb;
+    else if (!strcmp(name, "expand_xcd")) *value = ctx->opt.expand_xcd ? 1 : 0;
+    else if (!strcmp(name, "expand_xcd_relabel")) *value = ctx->opt.expand_xcd_relabel ? 1 : 0;
+    else if (!strcmp(name, "expand_xcd_min_mb")) *value = ctx->opt.expand_xcd_min_mb;
+    else if (!strcmp(name, "bfs_pb"))*value = ctx->opt.bfs_pb;
     else if (!strcmp(name, "wcc_mode")) *value = ctx->opt.wcc_mode;
     else if (!strcmp(name, "bc_batch")) *value = ctx->opt.bc_batch;
     else if (!strcmp(name, "bc_direction")) *value = ctx->opt.bc_direction;

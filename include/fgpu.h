@@ -126,7 +126,9 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  * read ran by propagation blocking), "bfs_cp_last_mask" (bit k: fused launch k of that search ran behind the list kernel — a
  * sparse frontier listed into the queue, or a pull of listed candidates), "expand_scan_last_live" / "expand_scan_last_passes" (live source rows and passes of the
  * last whole-frontier fgpu_expand_count), "expand_xp_direct" and "expand_xp_last_direct" (entries of A' the last XCD-partitioned count hop
- * read straight from X as single-entry runs, 0 when its plan streams every run), "wcc_mode", "bc_batch", "bc_direction".  Unknown
+ * read straight from X as single-entry runs, 0 when its plan streams every run), "expand_xcd", "expand_xcd_relabel" and
+ * "expand_xcd_min_mb" (the settings of the partitioned count hop, so that a caller can put back what it found), "expand_mode",
+ * "expand_nt", "wcc_mode", "bc_batch", "bc_direction".  Unknown
  * names return FGPU_INVALID. */
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value);
 /* name[256]; returns CU count, wave size, LDS bytes per block, total HBM bytes. */

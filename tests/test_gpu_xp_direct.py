@@ -35,20 +35,23 @@ def device(ctx, a: oracle.CSR):
 
 
 class Forced:
-    """The partitioned form on any state size, the bit-parallel chain, the given direct mode (and whole-frontier settings);
-    the defaults come back on exit."""
-    DEFAULTS = dict(expand_mode=0, expand_xcd_min_mb=32, expand_xp_direct=1, expand_scan_min=2048, expand_scan_rows=1024)
+    """The partitioned form on any state size, the bit-parallel chain, the given direct mode (and whole-frontier settings or any
+    other option that has a read-back, expand_mode included); what was set before comes back on exit."""
 
     def __init__(self, ctx, direct, **extra):
-        self.ctx, self.opts = ctx, dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_direct=direct, **extra)
+        self.ctx, self.opts = ctx, dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_direct=direct)
+        self.opts.update(extra)
+        self.found = {}
 
     def __enter__(self):
         for k, v in self.opts.items():
+            self.found[k] = self.ctx.get_option(k)
             self.ctx.set_option(k, v)
 
     def __exit__(self, *exc):
-        for k in self.opts:
-            self.ctx.set_option(k, self.DEFAULTS[k])
+        for k, v in reversed(list(self.found.items())):
+            self.ctx.set_option(k, v)
+        self.found = {}
 
 
 # ---- a hand-built graph whose destinations cover every case of the fold ---------------------------------------------------
