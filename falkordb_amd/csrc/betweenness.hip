@@ -34,15 +34,11 @@
 // Every hand-off between phases is a kernel boundary: nothing reads, inside one launch, a word another workgroup writes in it
 // (the kernels that atomically add into sigma[w] / N[w] never read them).  No dynamic LDS; the largest static LDS is the
 // reduce buffer of the hub kernels, 2 KiB per workgroup.
-#include "common.hpp"
+#include "algo.hpp"
 
 namespace fgpu {
 
 constexpr u64 BC_PULL_RATIO = 2;            // auto direction: pull when its entries < ratio x the push entries (not tuned)
-
-__device__ __forceinline__ bool bc_on(const u64* __restrict__ act, u32 v) {
-    return !act || ((act[v >> 6] >> (v & 63)) & 1ull);
-}
 
 // the bits of pred over the calling lane's group of 2^lg lanes, lane 0 of the group in bit 0
 __device__ __forceinline__ u64 bc_group_ballot(bool pred, u32 lg) {
@@ -50,20 +46,6 @@ __device__ __forceinline__ u64 bc_group_ballot(bool pred, u32 lg) {
     if (lg == 6) return m;
     const u32 base = lane_id() & ~((1u << lg) - 1u);
     return (m >> base) & ((1ull << (1u << lg)) - 1ull);
-}
-
-// adds a 256-thread workgroup's x into *dst with one atomic (as wcc.hip's block_add_u64)
-__device__ __forceinline__ void bc_block_add(u64 x, unsigned long long* dst) {
-    __shared__ u64 s_part[4];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    if (lane_id() == 0) s_part[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const u64 t = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        if (t) atomicAdd(dst, (unsigned long long)t);
-    }
-    __syncthreads();
 }
 
 struct BcDev {   // one batch's workspace (device pointers), passed by value
@@ -106,11 +88,11 @@ __global__ __launch_bounds__(256) void bc_settle_kernel(BcDev s, const u32* __re
             mf += rpA[v + 1] - rpA[v];
         }
         s.F[v] = 0;
-        if (rpAt && (vis & s.full) != s.full && bc_on(act, v)) mu += rpAt[v + 1] - rpAt[v];
+        if (rpAt && (vis & s.full) != s.full && vertex_on(act, v)) mu += rpAt[v + 1] - rpAt[v];
     }
-    bc_block_add(nf, &cnt[0]);
-    bc_block_add(mf, &cnt[1]);
-    bc_block_add(mu, &cnt[2]);
+    block_add_u64(nf, &cnt[0]);
+    block_add_u64(mf, &cnt[1]);
+    block_add_u64(mu, &cnt[2]);
 }
 
 // push, rows shorter than HUB_DEG: a lane group per frontier row u of A
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(256) void bc_push_kernel(BcDev s, CsrView a, const 
             u64 mj = 0;
             if (base + k < e) {
                 wj = a.colidx[base + k];
-                if (bc_on(act, wj)) mj = fu & ~s.V[wj];
+                if (vertex_on(act, wj)) mj = fu & ~s.V[wj];
             }
             const u32 cnt = e - base < G ? e - base : G;
             for (u32 j = 0; j < cnt; ++j) {
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(256) void bc_push_hub_kernel(BcDev s, const u32* __
             u64 mj = 0;
             if (base + k < e) {
                 wj = col[base + k];
-                if (bc_on(act, wj)) mj = fu & ~s.V[wj];
+                if (vertex_on(act, wj)) mj = fu & ~s.V[wj];
             }
             const u32 cnt = e - base < G ? e - base : G;
             for (u32 j = 0; j < cnt; ++j) {
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(256) void bc_pull_kernel(BcDev s, CsrView at, const
     const u64 stride = ((u64)gridDim.x * blockDim.x) >> s.lg;
     for (u64 vv = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> s.lg; vv < n; vv += stride) {
         const u32 v = (u32)vv;
-        if (!bc_on(act, v)) continue;
+        if (!vertex_on(act, v)) continue;
         const u64 unv = s.full & ~s.V[v];
         if (!unv) continue;
         const u32 b = at.rowptr[v], e = at.rowptr[v + 1];
@@ -219,7 +201,7 @@ __global__ __launch_bounds__(256) void bc_pull_hub_kernel(BcDev s, const u32* __
     const u32 gi = threadIdx.x >> s.lg, ng = 256u >> s.lg;
     for (u32 h = blockIdx.x; h < n_hub; h += gridDim.x) {
         const u32 v = hub[3 * h], b = hub[3 * h + 1], e = hub[3 * h + 2];
-        if (!bc_on(act, v)) continue;
+        if (!vertex_on(act, v)) continue;
         const u64 unv = s.full & ~s.V[v];   // V does not change during the launch: the same value in every thread
         if (!unv) continue;
         double acc = 0.0;
@@ -290,7 +272,7 @@ __global__ __launch_bounds__(256) void bc_back_kernel(BcDev s, CsrView a, u32 n,
         const double acc = bc_dep_sum(s, a.colidx, b, e, G, k, G, mine, d);
         if (mine) s.delta[(size_t)v * s.B + k] = s.sigma[(size_t)v * s.B + k] * acc;
     }
-    bc_block_add(seen, entries);
+    block_add_u64(seen, entries);
 }
 
 // backward at depth d, hub chunks of A: part[h][k] = the chunk's sum (lane groups strided over the chunk, then a fixed tree)
@@ -314,7 +296,7 @@ __global__ __launch_bounds__(256) void bc_back_hub_kernel(BcDev s, const u32* __
         }
         __syncthreads();
     }
-    bc_block_add(seen, entries);
+    block_add_u64(seen, entries);
 }
 
 // backward at depth d, hub rows: a lane group per hub chunk that opens a row sums the row's chunks in chunk order (one row's
@@ -380,10 +362,7 @@ using namespace fgpu;
 extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
                                       const uint64_t* sources, uint64_t nsrc, double* centrality, uint64_t stats[4]) {
     FGPU_REQUIRE(ctx && A && centrality && (sources || nsrc == 0), FGPU_NULL_POINTER, "fgpu_betweenness: NULL argument");
-    FGPU_REQUIRE(A->nrows == A->ncols, FGPU_DIM_MISMATCH, "fgpu_betweenness: adjacency must be square");
-    FGPU_REQUIRE(!At || (At->nrows == A->nrows && At->ncols == A->ncols), FGPU_DIM_MISMATCH,
-                 "fgpu_betweenness: transpose has different dimensions");
-    FGPU_REQUIRE(A->nrows < 0xFFFFFFFFull, FGPU_INVALID, "fgpu_betweenness: too many vertices");
+    FGPU_TRY(check_adjacency("fgpu_betweenness", A, At));
     const u32 n = (u32)A->nrows;
     for (u64 i = 0; i < nsrc; ++i) {
         FGPU_REQUIRE(sources[i] < n, FGPU_OUT_OF_BOUNDS, "fgpu_betweenness: source %llu out of range",
@@ -394,153 +373,130 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
     if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
     if (n == 0) return FGPU_OK;
     const int dir = ctx->opt.bc_direction;
-    // dense row pointers are indexed below: hypersparse inputs are densified first
-    fgpu_mat *dA = nullptr, *dAt = nullptr;
-    fgpu_info info = FGPU_OK;
-    if (A->is_hyper()) {
-        info = mat_merge_entries(ctx, &dA, A, nullptr, nullptr, false, A->nrows, A->ncols, true);
-        A = dA;
-    }
+    DenseInputs in;
+    FGPU_TRY(in.a(ctx, A));
     if (dir == 1) At = nullptr;   // push only: the transpose is never read
-    else if (info == FGPU_OK && !At) info = bc_cached_transpose(ctx, A, &At);
-    if (info == FGPU_OK && At && At->is_hyper()) {
-        info = mat_merge_entries(ctx, &dAt, At, nullptr, nullptr, false, At->nrows, At->ncols, true);
-        At = dAt;
-    }
-    auto run = [&]() -> fgpu_info {
-        FGPU_TRY(mat_ensure_finalized(A));   // the hub lists
-        if (At) FGPU_TRY(mat_ensure_finalized(At));
-        DevBuf<double> cent;
-        FGPU_TRY(cent.alloc(ctx, n));
-        FGPU_HIP(hipMemsetAsync(cent.p, 0, (size_t)n * sizeof(double), ctx->stream()));
-        u64 st[4] = {0, 0, 0, 0};
-        if (nsrc > 0) {
-            // batch width: bc_batch, or the smallest of 16 / 32 / 64 that covers nsrc, halved until the workspace fits 3/4 of
-            // the free device memory
-            u32 B = (u32)ctx->opt.bc_batch;
-            if (B == 0) {
-                B = nsrc <= 16 ? 16 : nsrc <= 32 ? 32 : 64;
-                size_t free_b = 0, total_b = 0;
-                FGPU_HIP(hipMemGetInfo(&free_b, &total_b));
-                const u64 budget = (u64)free_b / 4 * 3;
-                while (B > 1 && bc_workspace_bytes(n, B, A->n_hub_chunks) > budget) B >>= 1;
-            }
-            DevBuf<u64> act, F, N, V, src;
-            DevBuf<double> sigma, delta, part;
-            DevBuf<u32> depth;
-            DevBuf<unsigned long long> cnt;
-            if (active_bitmap) {
-                const size_t words = ((size_t)n + 63) / 64;
-                FGPU_TRY(act.alloc(ctx, words));
-                FGPU_TRY(ctx->h2d(act.p, active_bitmap, words * sizeof(u64)));
-                if (n & 63) {   // bits past n are not vertices
-                    const u64 last = active_bitmap[words - 1] & ((1ull << (n & 63)) - 1ull);
-                    FGPU_TRY(ctx->h2d(act.p + words - 1, &last, sizeof(u64)));
-                }
-            }
-            FGPU_TRY(F.alloc(ctx, n));
-            FGPU_TRY(N.alloc(ctx, n));
-            FGPU_TRY(V.alloc(ctx, n));
-            FGPU_TRY(sigma.alloc(ctx, (size_t)n * B));
-            FGPU_TRY(delta.alloc(ctx, (size_t)n * B));
-            FGPU_TRY(depth.alloc(ctx, (size_t)n * B));
-            FGPU_TRY(part.alloc(ctx, (size_t)(A->n_hub_chunks ? A->n_hub_chunks : 1) * B));
-            FGPU_TRY(src.alloc(ctx, nsrc));
-            FGPU_TRY(ctx->h2d(src.p, sources, nsrc * sizeof(u64)));
-            FGPU_TRY(cnt.alloc(ctx, 4));   // per step: new frontier, push entries, pull entries; [3] backward entries
-            FGPU_HIP(hipMemsetAsync(cnt.p, 0, 4 * sizeof(unsigned long long), ctx->stream()));
-            BcDev s;
-            s.B = B;
-            s.lg = bc_log2_group(B);
-            const u32 G = 1u << s.lg;
-            s.sigma = sigma.p;
-            s.delta = delta.p;
-            s.depth = depth.p;
-            const u64* a = act.p;
-            const CsrView va = view_of(A);
-            const CsrView vat = At ? view_of(At) : va;
-            const u32 ggrid = bc_grid(ctx, (u64)n * G);
-            const u32 hgA = A->n_hub_chunks < (u32)ctx->cus * 8 ? A->n_hub_chunks : (u32)ctx->cus * 8;
-            const u32 hgAt = At ? (At->n_hub_chunks < (u32)ctx->cus * 8 ? At->n_hub_chunks : (u32)ctx->cus * 8) : 0;
-            for (u64 first = 0; first < nsrc; first += B) {
-                const u32 nb = (u32)(nsrc - first < B ? nsrc - first : B);
-                s.full = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
-                s.F = F.p;
-                s.N = N.p;
-                s.V = V.p;
-                FGPU_HIP(hipMemsetAsync(F.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
-                FGPU_HIP(hipMemsetAsync(N.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
-                FGPU_HIP(hipMemsetAsync(V.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
-                FGPU_HIP(hipMemsetAsync(sigma.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
-                FGPU_HIP(hipMemsetAsync(delta.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
-                FGPU_HIP(hipMemsetAsync(depth.p, 0xFF, (size_t)n * B * sizeof(u32), ctx->stream()));   // unreached
-                hipLaunchKernelGGL(bc_seed_kernel, dim3(1), dim3(64), 0, ctx->stream(), s, (const u64*)src.p + first, nb);
+    else if (!At) FGPU_TRY(bc_cached_transpose(ctx, A, &At));   // a missing transpose: A's cached one
+    FGPU_TRY(in.at(ctx, At));
+    FGPU_TRY(mat_ensure_finalized(A));   // the hub lists
+    if (At) FGPU_TRY(mat_ensure_finalized(At));
+    DevBuf<double> cent;
+    FGPU_TRY(cent.alloc(ctx, n));
+    FGPU_HIP(hipMemsetAsync(cent.p, 0, (size_t)n * sizeof(double), ctx->stream()));
+    u64 st[4] = {0, 0, 0, 0};
+    if (nsrc > 0) {
+        // batch width: bc_batch, or the smallest of 16 / 32 / 64 that covers nsrc, halved until the workspace fits 3/4 of
+        // the free device memory
+        u32 B = (u32)ctx->opt.bc_batch;
+        if (B == 0) {
+            B = nsrc <= 16 ? 16 : nsrc <= 32 ? 32 : 64;
+            size_t free_b = 0, total_b = 0;
+            FGPU_HIP(hipMemGetInfo(&free_b, &total_b));
+            const u64 budget = (u64)free_b / 4 * 3;
+            while (B > 1 && bc_workspace_bytes(n, B, A->n_hub_chunks) > budget) B >>= 1;
+        }
+        DevBuf<u64> act, F, N, V, src;
+        DevBuf<double> sigma, delta, part;
+        DevBuf<u32> depth;
+        DevBuf<unsigned long long> cnt;
+        if (active_bitmap) FGPU_TRY(upload_active(ctx, act, active_bitmap, n));
+        FGPU_TRY(F.alloc(ctx, n));
+        FGPU_TRY(N.alloc(ctx, n));
+        FGPU_TRY(V.alloc(ctx, n));
+        FGPU_TRY(sigma.alloc(ctx, (size_t)n * B));
+        FGPU_TRY(delta.alloc(ctx, (size_t)n * B));
+        FGPU_TRY(depth.alloc(ctx, (size_t)n * B));
+        FGPU_TRY(part.alloc(ctx, (size_t)(A->n_hub_chunks ? A->n_hub_chunks : 1) * B));
+        FGPU_TRY(src.alloc(ctx, nsrc));
+        FGPU_TRY(ctx->h2d(src.p, sources, nsrc * sizeof(u64)));
+        FGPU_TRY(cnt.alloc(ctx, 4));   // per step: new frontier, push entries, pull entries; [3] backward entries
+        FGPU_HIP(hipMemsetAsync(cnt.p, 0, 4 * sizeof(unsigned long long), ctx->stream()));
+        BcDev s;
+        s.B = B;
+        s.lg = bc_log2_group(B);
+        const u32 G = 1u << s.lg;
+        s.sigma = sigma.p;
+        s.delta = delta.p;
+        s.depth = depth.p;
+        const u64* a = act.p;
+        const CsrView va = view_of(A);
+        const CsrView vat = At ? view_of(At) : va;
+        const u32 ggrid = bc_grid(ctx, (u64)n * G);
+        const u32 hgA = hub_grid(ctx, A), hgAt = At ? hub_grid(ctx, At) : 0;
+        for (u64 first = 0; first < nsrc; first += B) {
+            const u32 nb = (u32)(nsrc - first < B ? nsrc - first : B);
+            s.full = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
+            s.F = F.p;
+            s.N = N.p;
+            s.V = V.p;
+            FGPU_HIP(hipMemsetAsync(F.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
+            FGPU_HIP(hipMemsetAsync(N.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
+            FGPU_HIP(hipMemsetAsync(V.p, 0, (size_t)n * sizeof(u64), ctx->stream()));
+            FGPU_HIP(hipMemsetAsync(sigma.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
+            FGPU_HIP(hipMemsetAsync(delta.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
+            FGPU_HIP(hipMemsetAsync(depth.p, 0xFF, (size_t)n * B * sizeof(u32), ctx->stream()));   // unreached
+            hipLaunchKernelGGL(bc_seed_kernel, dim3(1), dim3(64), 0, ctx->stream(), s, (const u64*)src.p + first, nb);
+            FGPU_HIP(hipGetLastError());
+            // forward: settle the frontier of depth d1, read its counters, expand it to depth d1 + 1
+            u32 d1 = 0;
+            for (;;) {
+                FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
+                hipLaunchKernelGGL(bc_settle_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, (const u32*)A->rowptr,
+                                   At ? (const u32*)At->rowptr : nullptr, a, n, d1, cnt.p);
                 FGPU_HIP(hipGetLastError());
-                // forward: settle the frontier of depth d1, read its counters, expand it to depth d1 + 1
-                u32 d1 = 0;
-                for (;;) {
-                    FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
-                    hipLaunchKernelGGL(bc_settle_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, (const u32*)A->rowptr,
-                                       At ? (const u32*)At->rowptr : nullptr, a, n, d1, cnt.p);
+                std::swap(s.F, s.N);   // the settled frontier is read next; the cleared one collects the next depth
+                u32 w[6];
+                FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 6, w));
+                const u64 nf = w[0] | ((u64)w[1] << 32), mf = w[2] | ((u64)w[3] << 32), mu = w[4] | ((u64)w[5] << 32);
+                if (nf == 0) break;
+                const bool pull = dir == 2 || (dir == 0 && At && mu < BC_PULL_RATIO * mf);
+                if (pull) {
+                    hipLaunchKernelGGL(bc_pull_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, vat, a, n);
                     FGPU_HIP(hipGetLastError());
-                    std::swap(s.F, s.N);   // the settled frontier is read next; the cleared one collects the next depth
-                    u32 w[6];
-                    FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 6, w));
-                    const u64 nf = w[0] | ((u64)w[1] << 32), mf = w[2] | ((u64)w[3] << 32), mu = w[4] | ((u64)w[5] << 32);
-                    if (nf == 0) break;
-                    const bool pull = dir == 2 || (dir == 0 && At && mu < BC_PULL_RATIO * mf);
-                    if (pull) {
-                        hipLaunchKernelGGL(bc_pull_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, vat, a, n);
+                    if (hgAt) {
+                        hipLaunchKernelGGL(bc_pull_hub_kernel, dim3(hgAt), dim3(256), 0, ctx->stream(), s,
+                                           (const u32*)At->hub_chunks, At->n_hub_chunks, (const u32*)At->colidx, a);
                         FGPU_HIP(hipGetLastError());
-                        if (hgAt) {
-                            hipLaunchKernelGGL(bc_pull_hub_kernel, dim3(hgAt), dim3(256), 0, ctx->stream(), s,
-                                               (const u32*)At->hub_chunks, At->n_hub_chunks, (const u32*)At->colidx, a);
-                            FGPU_HIP(hipGetLastError());
-                        }
-                        st[2] += mu;
-                    } else {
-                        hipLaunchKernelGGL(bc_push_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, a, n);
-                        FGPU_HIP(hipGetLastError());
-                        if (hgA) {
-                            hipLaunchKernelGGL(bc_push_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s,
-                                               (const u32*)A->hub_chunks, A->n_hub_chunks, (const u32*)A->colidx, a);
-                            FGPU_HIP(hipGetLastError());
-                        }
-                        st[2] += mf;
                     }
-                    ++st[1];
-                    ++d1;
-                }
-                const u32 deepest = d1 - 1;   // d1 = the first depth that came out empty
-                if (deepest > st[3]) st[3] = deepest;
-                ++st[0];
-                if (deepest < 2) continue;     // no vertex between a source and a deeper one: every delta is 0
-                for (u32 d = deepest - 1; d >= 1; --d) {
-                    hipLaunchKernelGGL(bc_back_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, n, d, cnt.p + 3);
+                    st[2] += mu;
+                } else {
+                    hipLaunchKernelGGL(bc_push_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, a, n);
                     FGPU_HIP(hipGetLastError());
                     if (hgA) {
-                        hipLaunchKernelGGL(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
-                                           A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3);
-                        FGPU_HIP(hipGetLastError());
-                        hipLaunchKernelGGL(bc_back_hub_finish_kernel, dim3(bc_grid(ctx, (u64)A->n_hub_chunks * G)), dim3(256), 0,
-                                           ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p);
+                        hipLaunchKernelGGL(bc_push_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s,
+                                           (const u32*)A->hub_chunks, A->n_hub_chunks, (const u32*)A->colidx, a);
                         FGPU_HIP(hipGetLastError());
                     }
+                    st[2] += mf;
                 }
-                hipLaunchKernelGGL(bc_reduce_kernel, dim3(bc_grid(ctx, n)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p);
-                FGPU_HIP(hipGetLastError());
+                ++st[1];
+                ++d1;
             }
-            u64 back = 0;
-            FGPU_TRY(read_u64(ctx, (const u64*)(cnt.p + 3), &back));
-            st[2] += back;
+            const u32 deepest = d1 - 1;   // d1 = the first depth that came out empty
+            if (deepest > st[3]) st[3] = deepest;
+            ++st[0];
+            if (deepest < 2) continue;     // no vertex between a source and a deeper one: every delta is 0
+            for (u32 d = deepest - 1; d >= 1; --d) {
+                hipLaunchKernelGGL(bc_back_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, n, d, cnt.p + 3);
+                FGPU_HIP(hipGetLastError());
+                if (hgA) {
+                    hipLaunchKernelGGL(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
+                                       A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3);
+                    FGPU_HIP(hipGetLastError());
+                    hipLaunchKernelGGL(bc_back_hub_finish_kernel, dim3(bc_grid(ctx, (u64)A->n_hub_chunks * G)), dim3(256), 0,
+                                       ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p);
+                    FGPU_HIP(hipGetLastError());
+                }
+            }
+            hipLaunchKernelGGL(bc_reduce_kernel, dim3(bc_grid(ctx, n)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p);
+            FGPU_HIP(hipGetLastError());
         }
-        FGPU_TRY(ctx->d2h(centrality, cent.p, (size_t)n * sizeof(double)));   // one DMA when centrality[] is pinned
-        if (stats) memcpy(stats, st, sizeof(st));
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        return FGPU_OK;
-    };
-    if (info == FGPU_OK) info = run();
-    if (dA) mat_release(dA);
-    if (dAt) mat_release(dAt);
-    return info;
+        u64 back = 0;
+        FGPU_TRY(read_u64(ctx, (const u64*)(cnt.p + 3), &back));
+        st[2] += back;
+    }
+    FGPU_TRY(ctx->d2h(centrality, cent.p, (size_t)n * sizeof(double)));   // one DMA when centrality[] is pinned
+    if (stats) memcpy(stats, st, sizeof(st));
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+    return FGPU_OK;
 }

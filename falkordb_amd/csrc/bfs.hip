@@ -25,7 +25,7 @@
 //    issued by the host loop between step() and commit() (RCCL over xGMI).
 #include <chrono>
 
-#include "common.hpp"
+#include "algo.hpp"
 
 namespace fgpu {
 
@@ -3618,23 +3618,17 @@ fgpu_info fgpu_bfs(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, uint64_
     FGPU_REQUIRE(ctx && A && level, FGPU_NULL_POINTER, "fgpu_bfs: NULL argument");
     // a hypersparse snapshot (an adjacency with few populated rows, or an empty one) is re-emitted with a
     // dense row-pointer array for the level kernels; plans themselves only take the dense form
-    fgpu_mat *dA = nullptr, *dAt = nullptr;
+    DenseInputs in;
+    FGPU_TRY(in.a(ctx, A));
+    FGPU_TRY(in.at(ctx, At));   // a NULL At is passed through to the plan
     fgpu_info i = FGPU_OK;
-    if (A->is_hyper()) {
-        i = mat_merge_entries(ctx, &dA, A, nullptr, nullptr, false, A->nrows, A->ncols, true);
-        A = dA;
-    }
-    if (i == FGPU_OK && At && At->is_hyper()) {
-        i = mat_merge_entries(ctx, &dAt, At, nullptr, nullptr, false, At->nrows, At->ncols, true);
-        At = dAt;
-    }
     // The plan of the previous call over the same (A, At) is kept on A (common.hpp: bfs_plan): a caller that cannot hold a
     // plan — the reference's procedure call is one function — pays plan creation once per snapshot pair.  A second thread
     // searching the same adjacency at the same time, and the re-emitted hypersparse forms, take a plan of their own.
     fgpu_bfs_plan* p = nullptr;
     bool cached = false;
     std::unique_lock<std::mutex> lk(A->bfs_mu, std::defer_lock);
-    if (i == FGPU_OK && !dA && !dAt) {
+    if (!in.densified()) {
         // links change under the process-wide link mutex (taken before any matrix' bfs_mu, released before the search)
         std::lock_guard<std::mutex> link(bfs_link_mu());
         if (lk.try_lock()) {
@@ -3680,8 +3674,6 @@ fgpu_info fgpu_bfs(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, uint64_
         *edges_traversed = st[2];
     }
     if (p && !cached) fgpu_bfs_plan_free(p);
-    if (dA) mat_release(dA);
-    if (dAt) mat_release(dAt);
     return i;
 }
 

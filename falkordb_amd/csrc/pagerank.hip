@@ -23,23 +23,19 @@
 // rows >= HUB_DEG by the static hub chunk list: a partial per chunk, then one fixed-order sum per row — fused with
 // the |t - r| partials, (3) fixed-order reductions of the partials.
 // Bytes per iteration: 4 nnz (column ids) + gathers of w (16 MB at RMAT-22, L2 / MALL resident) + 6 n-vectors.
-#include "common.hpp"
+#include "algo.hpp"
 
 namespace fgpu {
-
-__device__ __forceinline__ bool pr_active(const u64* __restrict__ act, u32 v) {
-    return !act || ((act[v >> 6] >> (v & 63)) & 1ull);
-}
 
 // out-degree inside the active subgraph (only launched when `active` is given)
 __global__ void pr_degree_kernel(CsrView a, const u64* __restrict__ act, u32 n, u32* __restrict__ deg) {
     const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     u32 d = 0;
-    if (pr_active(act, v)) {
+    if (vertex_on(act, v)) {
         u32 b, e;
         row_range(a, v, b, e);
-        for (u32 i = b; i < e; ++i) d += pr_active(act, a.colidx[i]) ? 1u : 0u;
+        for (u32 i = b; i < e; ++i) d += vertex_on(act, a.colidx[i]) ? 1u : 0u;
     }
     deg[v] = d;
 }
@@ -49,7 +45,7 @@ __global__ void pr_init_kernel(CsrView a, const u64* __restrict__ act, const u32
                                unsigned char* __restrict__ sink) {
     const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
-    const bool on = pr_active(act, v);
+    const bool on = vertex_on(act, v);
     u32 dg;
     if (deg_in) dg = deg_in[v];
     else { u32 b, e; row_range(a, v, b, e); dg = e - b; }
@@ -82,7 +78,7 @@ __global__ __launch_bounds__(256) void pr_prep_kernel(const float* __restrict__ 
     double rs = 0.0;
     if (v < n) {
         const float tv = t[v];
-        w[v] = pr_active(act, v) ? tv / d[v] : 0.0f;
+        w[v] = vertex_on(act, v) ? tv / d[v] : 0.0f;
         rs = sink[v] ? (double)tv : 0.0;
     }
     const double tot = block_sum_256(rs, s_red);
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(256) void pr_spmv_kernel(CsrView at, const u64* __r
         const u32 vc = v < n ? v : n - 1;
         const u32 rb = at.rowptr[vc];
         const u32 re = at.rowptr[vc + 1];
-        const bool on = v < n && pr_active(act, v);
+        const bool on = v < n && vertex_on(act, v);
         const bool hub = re - rb >= HUB_DEG;
         const u32 deg = (on && !hub) ? re - rb : 0u;
         u32 inc = deg;
@@ -196,7 +192,7 @@ __global__ __launch_bounds__(256) void pr_hub_kernel(const u32* __restrict__ hub
     for (u32 h = blockIdx.x; h < n_hub; h += gridDim.x) {
         const u32 row = hub[3 * h], b = hub[3 * h + 1], e = hub[3 * h + 2];
         double s = 0.0;
-        if (pr_active(act, row))   // block-uniform
+        if (vertex_on(act, row))   // block-uniform
             for (u32 i = b + threadIdx.x; i < e; i += 256) s += (double)w[col[i]];
         const double tot = block_sum_256(s, s_red);
         if (threadIdx.x == 0) hpart[h] = tot;
@@ -226,7 +222,7 @@ __global__ __launch_bounds__(256) void pr_hub_finish_kernel(const u32* __restric
         if (cnt > n_hub - h) cnt = n_hub - h;
         double s = 0.0;
         for (u32 k = 0; k < cnt; ++k) s += hpart[h + k];
-        const float rv = pr_active(act, row) ? (float)((double)tp + s) : 0.0f;
+        const float rv = vertex_on(act, row) ? (float)((double)tp + s) : 0.0f;
         r[row] = rv;
         x += fabs((double)t[row] - (double)rv);
     }
@@ -410,7 +406,7 @@ __global__ __launch_bounds__(256) void pr_part_combine_kernel(const double* __re
         double s = 0.0;
 #pragma unroll
         for (u32 p = 0; p < PR_NPARTS; ++p) s += part[(size_t)p * n + v];
-        const bool on = pr_active(act, v);
+        const bool on = vertex_on(act, v);
         const float rv = on ? (float)((double)tp + s) : 0.0f;
         r[v] = rv;
         diff += fabs((double)t[v] - (double)rv);
@@ -455,9 +451,7 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
                                           int32_t* converged) {
     FGPU_REQUIRE(ctx && A && centrality, FGPU_NULL_POINTER, "fgpu_pagerank: NULL argument");
     if (converged) *converged = 1;                // (the paths that run no iteration: nothing left to converge)
-    FGPU_REQUIRE(A->nrows == A->ncols, FGPU_DIM_MISMATCH, "fgpu_pagerank: adjacency must be square");
-    FGPU_REQUIRE(!At || (At->nrows == A->nrows && At->ncols == A->ncols), FGPU_DIM_MISMATCH,
-                 "fgpu_pagerank: transpose has different dimensions");
+    FGPU_TRY(check_adjacency("fgpu_pagerank", A, At));
     FGPU_REQUIRE(damping > 0.0f && damping <= 1.0f, FGPU_INVALID, "fgpu_pagerank: damping out of (0, 1]");
     const u32 n = (u32)A->nrows;
     if (iters) *iters = 0;
@@ -478,182 +472,156 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
         if (converged) *converged = (itermax > 0 || !(tol < 1.0f)) ? 1 : 0;
         return FGPU_OK;
     }
-    // dense row pointers are indexed directly below: hypersparse inputs are densified, a missing transpose is built
-    fgpu_mat *dA = nullptr, *dAt = nullptr;
-    fgpu_info info = FGPU_OK;
-    if (A->is_hyper()) {
-        info = mat_merge_entries(ctx, &dA, A, nullptr, nullptr, false, A->nrows, A->ncols, true);
-        A = dA;
+    DenseInputs in;
+    FGPU_TRY(in.a(ctx, A));
+    if (!At) {   // a missing transpose is built for the call
+        FGPU_TRY(fgpu_mat_transpose(ctx, &in.dAt, A));
+        At = in.dAt;
     }
-    if (info == FGPU_OK && !At) {
-        info = fgpu_mat_transpose(ctx, &dAt, A);
-        At = dAt;
-    }
-    if (info == FGPU_OK && At->is_hyper()) {
-        fgpu_mat* dense = nullptr;
-        info = mat_merge_entries(ctx, &dense, At, nullptr, nullptr, false, At->nrows, At->ncols, true);
-        if (dAt) mat_release(dAt);
-        dAt = dense;
-        At = dense;
-    }
-    auto run = [&]() -> fgpu_info {
-        FGPU_TRY(mat_ensure_finalized(At));
-        const u32 nb = cdiv(n, 256);
-        const u32 grid = (u32)ctx->cus * 8 < cdiv(cdiv(n, 64), 4) ? (u32)ctx->cus * 8 : cdiv(cdiv(n, 64), 4);
-        DevBuf<u64> act;
-        DevBuf<u32> deg;
-        DevBuf<float> r, t, w, d, scal;
-        DevBuf<double> part, part2, hpart;
-        DevBuf<unsigned char> sink;
-        u64 n_act = n;
-        if (active_bitmap) {
-            const size_t words = ((size_t)n + 63) / 64;
-            n_act = 0;
-            for (size_t k = 0; k < words; ++k) {
-                u64 x = active_bitmap[k];
-                if (k == words - 1 && (n & 63)) x &= (1ull << (n & 63)) - 1ull;
-                n_act += (u64)__builtin_popcountll(x);
-            }
-            FGPU_TRY(act.alloc(ctx, words));
-            FGPU_TRY(ctx->h2d(act.p, active_bitmap, words * sizeof(u64)));
-            FGPU_TRY(deg.alloc(ctx, n));
-            hipLaunchKernelGGL(pr_degree_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p, n,
-                               deg.p);
-            FGPU_HIP(hipGetLastError());
-        }
-        FGPU_TRY(r.alloc(ctx, n));
-        FGPU_TRY(t.alloc(ctx, n));
-        FGPU_TRY(w.alloc(ctx, n));
-        FGPU_TRY(d.alloc(ctx, n));
-        FGPU_TRY(sink.alloc(ctx, n));
-        FGPU_TRY(part.alloc(ctx, nb));
-        // the column-range form (PrParts above) when the score vector does not fit one XCD's L2 next to the stream
-        const PrParts* parts = nullptr;
-        if (ctx->opt.pagerank_parts == 2 || (ctx->opt.pagerank_parts == 1 && (u64)n * sizeof(float) > (2ull << 20)))
-            FGPU_TRY(pr_parts_build(ctx, At, &parts));
-        const u32 cgrid = parts ? ((u32)ctx->cus * 8 < nb ? (u32)ctx->cus * 8 : nb) : 0u;
-        DevBuf<double> ppart;
-        if (parts) FGPU_TRY(ppart.alloc(ctx, (size_t)PR_NPARTS * n));
-        FGPU_TRY(part2.alloc(ctx, (size_t)(grid > cgrid ? grid : cgrid) + 1));
-        FGPU_TRY(scal.alloc(ctx, 2));
-        FGPU_TRY(hpart.alloc(ctx, (size_t)At->n_hub_chunks + 1));
-        if (n_act == 0) {
-            memset(centrality, 0, (size_t)n * sizeof(float));
-            return FGPU_OK;
-        }
-        const float fn = (float)n_act;
-        hipLaunchKernelGGL(pr_init_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p,
-                           (const u32*)deg.p, n, 1.0f / fn, damping, r.p, d.p, sink.p);
+    FGPU_TRY(in.at(ctx, At));
+    FGPU_TRY(mat_ensure_finalized(At));
+    const u32 nb = cdiv(n, 256);
+    const u32 grid = (u32)ctx->cus * 8 < cdiv(cdiv(n, 64), 4) ? (u32)ctx->cus * 8 : cdiv(cdiv(n, 64), 4);
+    DevBuf<u64> act;
+    DevBuf<u32> deg;
+    DevBuf<float> r, t, w, d, scal;
+    DevBuf<double> part, part2, hpart;
+    DevBuf<unsigned char> sink;
+    u64 n_act = n;
+    if (active_bitmap) {
+        FGPU_TRY(upload_active(ctx, act, active_bitmap, n, &n_act));
+        FGPU_TRY(deg.alloc(ctx, n));
+        hipLaunchKernelGGL(pr_degree_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p, n,
+                           deg.p);
         FGPU_HIP(hipGetLastError());
-        const float teleport0 = (1.0f - damping) / fn, damp_over_n = damping / fn;
-        const CsrView vat = view_of(At);
-        // Iterations are enqueued blind, PR_BATCH at a time; every kernel returns at once when the device-side `stop` is up,
-        // and the closing reduction of an iteration counts it and raises `stop` on convergence (same test, same order of
-        // operations as a host loop that reads rdiff after every iteration: the scores are bit-identical) — one
-        // synchronisation per batch instead of one per iteration.
-        constexpr int PR_BATCH = 4;
-        DevBuf<int> state;
-        FGPU_TRY(state.alloc(ctx, 2));
-        FGPU_HIP(hipMemsetAsync(state.p, 0, 2 * sizeof(int), ctx->stream()));
-        int it = 0;
-        bool stopped = !(1.0f > tol);   // (the host loop started from rdiff = 1)
-        float* rp = r.p;   // current scores
-        float* tp = t.p;   // previous scores
-        const bool timing = getenv("FGPU_PR_TIMING") != nullptr;
-        hipEvent_t ev[6];
-        float acc_ms[5] = {0, 0, 0, 0, 0};
-        if (timing) for (auto& e : ev) (void)hipEventCreate(&e);
-        if (parts && itermax > 0 && !stopped) {
-            // the range form prepares iteration i + 1 inside iteration i's combine pass: only the first w / teleport come from here
-            hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)rp,
+    }
+    FGPU_TRY(r.alloc(ctx, n));
+    FGPU_TRY(t.alloc(ctx, n));
+    FGPU_TRY(w.alloc(ctx, n));
+    FGPU_TRY(d.alloc(ctx, n));
+    FGPU_TRY(sink.alloc(ctx, n));
+    FGPU_TRY(part.alloc(ctx, nb));
+    // the column-range form (PrParts above) when the score vector does not fit one XCD's L2 next to the stream
+    const PrParts* parts = nullptr;
+    if (ctx->opt.pagerank_parts == 2 || (ctx->opt.pagerank_parts == 1 && (u64)n * sizeof(float) > (2ull << 20)))
+        FGPU_TRY(pr_parts_build(ctx, At, &parts));
+    const u32 cgrid = parts ? ((u32)ctx->cus * 8 < nb ? (u32)ctx->cus * 8 : nb) : 0u;
+    DevBuf<double> ppart;
+    if (parts) FGPU_TRY(ppart.alloc(ctx, (size_t)PR_NPARTS * n));
+    FGPU_TRY(part2.alloc(ctx, (size_t)(grid > cgrid ? grid : cgrid) + 1));
+    FGPU_TRY(scal.alloc(ctx, 2));
+    FGPU_TRY(hpart.alloc(ctx, (size_t)At->n_hub_chunks + 1));
+    if (n_act == 0) {
+        memset(centrality, 0, (size_t)n * sizeof(float));
+        return FGPU_OK;
+    }
+    const float fn = (float)n_act;
+    hipLaunchKernelGGL(pr_init_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p,
+                       (const u32*)deg.p, n, 1.0f / fn, damping, r.p, d.p, sink.p);
+    FGPU_HIP(hipGetLastError());
+    const float teleport0 = (1.0f - damping) / fn, damp_over_n = damping / fn;
+    const CsrView vat = view_of(At);
+    // Iterations are enqueued blind, PR_BATCH at a time; every kernel returns at once when the device-side `stop` is up,
+    // and the closing reduction of an iteration counts it and raises `stop` on convergence (same test, same order of
+    // operations as a host loop that reads rdiff after every iteration: the scores are bit-identical) — one
+    // synchronisation per batch instead of one per iteration.
+    constexpr int PR_BATCH = 4;
+    DevBuf<int> state;
+    FGPU_TRY(state.alloc(ctx, 2));
+    FGPU_HIP(hipMemsetAsync(state.p, 0, 2 * sizeof(int), ctx->stream()));
+    int it = 0;
+    bool stopped = !(1.0f > tol);   // (the host loop started from rdiff = 1)
+    float* rp = r.p;   // current scores
+    float* tp = t.p;   // previous scores
+    const bool timing = getenv("FGPU_PR_TIMING") != nullptr;
+    hipEvent_t ev[6];
+    float acc_ms[5] = {0, 0, 0, 0, 0};
+    if (timing) for (auto& e : ev) (void)hipEventCreate(&e);
+    if (parts && itermax > 0 && !stopped) {
+        // the range form prepares iteration i + 1 inside iteration i's combine pass: only the first w / teleport come from here
+        hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)rp,
+                           (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
+                           (const int*)state.p);
+        hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
+                           teleport0, damp_over_n, scal.p, state.p, 0, 0.0f);
+        FGPU_HIP(hipGetLastError());
+    }
+    while (it < itermax && !stopped) {
+        const int batch = timing ? 1 : (itermax - it < PR_BATCH ? itermax - it : PR_BATCH);
+        for (int bi = 0; bi < batch; ++bi) {
+            float* tmp = tp; tp = rp; rp = tmp;   // t = old r
+            if (timing) (void)hipEventRecord(ev[0], ctx->stream());
+            if (parts) {
+                if (timing) (void)hipEventRecord(ev[1], ctx->stream());
+                const u32 nblk = cdiv(n, PR_RB);
+                hipLaunchKernelGGL(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp,
+                                   (const u32*)parts->pcol, n, (const float*)w.p, ppart.p, (const int*)state.p);
+                if (timing) (void)hipEventRecord(ev[2], ctx->stream());
+                hipLaunchKernelGGL(pr_part_combine_kernel, dim3(cgrid), dim3(256), 0, ctx->stream(), (const double*)ppart.p,
+                                   (const u64*)act.p, n, (const float*)scal.p, (const float*)tp, (const float*)d.p,
+                                   (const unsigned char*)sink.p, rp, w.p, part2.p, part.p, (const int*)state.p);
+                if (timing) (void)hipEventRecord(ev[3], ctx->stream());
+                hipLaunchKernelGGL(pr_reduce2_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p,
+                                   (const double*)part.p, cgrid, teleport0, damp_over_n, scal.p, state.p, tol);
+                if (timing) (void)hipEventRecord(ev[4], ctx->stream());
+                FGPU_HIP(hipGetLastError());
+                continue;
+            }
+            hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)tp,
                                (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
                                (const int*)state.p);
             hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
                                teleport0, damp_over_n, scal.p, state.p, 0, 0.0f);
+            if (timing) (void)hipEventRecord(ev[1], ctx->stream());
+            hipLaunchKernelGGL(pr_spmv_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vat, (const u64*)act.p, n,
+                               (const float*)w.p, (const float*)scal.p, (const float*)tp, rp, part2.p + 1,
+                               (const int*)state.p);
+            if (timing) (void)hipEventRecord(ev[2], ctx->stream());
+            if (At->n_hub_chunks) {
+                hipLaunchKernelGGL(pr_hub_kernel, dim3(hub_grid(ctx, At)), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                                   At->n_hub_chunks, (const u32*)At->colidx, (const u64*)act.p, (const float*)w.p, hpart.p,
+                                   (const int*)state.p);
+                hipLaunchKernelGGL(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                                   At->n_hub_chunks, (const u32*)At->rowptr, (const u64*)act.p, (const double*)hpart.p,
+                                   (const float*)scal.p, (const float*)tp, rp, part2.p, (const int*)state.p);
+            } else {
+                FGPU_HIP(hipMemsetAsync(part2.p, 0, sizeof(double), ctx->stream()));
+            }
+            if (timing) (void)hipEventRecord(ev[3], ctx->stream());
+            hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p, grid + 1,
+                               0.0f, 1.0f, scal.p + 1, state.p, 1, tol);
+            if (timing) (void)hipEventRecord(ev[4], ctx->stream());
             FGPU_HIP(hipGetLastError());
         }
-        while (it < itermax && !stopped) {
-            const int batch = timing ? 1 : (itermax - it < PR_BATCH ? itermax - it : PR_BATCH);
-            for (int bi = 0; bi < batch; ++bi) {
-                float* tmp = tp; tp = rp; rp = tmp;   // t = old r
-                if (timing) (void)hipEventRecord(ev[0], ctx->stream());
-                if (parts) {
-                    if (timing) (void)hipEventRecord(ev[1], ctx->stream());
-                    const u32 nblk = cdiv(n, PR_RB);
-                    hipLaunchKernelGGL(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp,
-                                       (const u32*)parts->pcol, n, (const float*)w.p, ppart.p, (const int*)state.p);
-                    if (timing) (void)hipEventRecord(ev[2], ctx->stream());
-                    hipLaunchKernelGGL(pr_part_combine_kernel, dim3(cgrid), dim3(256), 0, ctx->stream(), (const double*)ppart.p,
-                                       (const u64*)act.p, n, (const float*)scal.p, (const float*)tp, (const float*)d.p,
-                                       (const unsigned char*)sink.p, rp, w.p, part2.p, part.p, (const int*)state.p);
-                    if (timing) (void)hipEventRecord(ev[3], ctx->stream());
-                    hipLaunchKernelGGL(pr_reduce2_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p,
-                                       (const double*)part.p, cgrid, teleport0, damp_over_n, scal.p, state.p, tol);
-                    if (timing) (void)hipEventRecord(ev[4], ctx->stream());
-                    FGPU_HIP(hipGetLastError());
-                    continue;
-                }
-                hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)tp,
-                                   (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
-                                   (const int*)state.p);
-                hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
-                                   teleport0, damp_over_n, scal.p, state.p, 0, 0.0f);
-                if (timing) (void)hipEventRecord(ev[1], ctx->stream());
-                hipLaunchKernelGGL(pr_spmv_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vat, (const u64*)act.p, n,
-                                   (const float*)w.p, (const float*)scal.p, (const float*)tp, rp, part2.p + 1,
-                                   (const int*)state.p);
-                if (timing) (void)hipEventRecord(ev[2], ctx->stream());
-                if (At->n_hub_chunks) {
-                    const u32 hg = At->n_hub_chunks < (u32)ctx->cus * 8 ? At->n_hub_chunks : (u32)ctx->cus * 8;
-                    hipLaunchKernelGGL(pr_hub_kernel, dim3(hg), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
-                                       At->n_hub_chunks, (const u32*)At->colidx, (const u64*)act.p, (const float*)w.p, hpart.p,
-                                       (const int*)state.p);
-                    hipLaunchKernelGGL(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
-                                       At->n_hub_chunks, (const u32*)At->rowptr, (const u64*)act.p, (const double*)hpart.p,
-                                       (const float*)scal.p, (const float*)tp, rp, part2.p, (const int*)state.p);
-                } else {
-                    FGPU_HIP(hipMemsetAsync(part2.p, 0, sizeof(double), ctx->stream()));
-                }
-                if (timing) (void)hipEventRecord(ev[3], ctx->stream());
-                hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p, grid + 1,
-                                   0.0f, 1.0f, scal.p + 1, state.p, 1, tol);
-                if (timing) (void)hipEventRecord(ev[4], ctx->stream());
-                FGPU_HIP(hipGetLastError());
-            }
-            int hstate[2] = {0, 0};
-            if (timing) {   // (the events below must have completed)
-                FGPU_HIP(hipMemcpyAsync(ctx->pinned(), state.p, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream()));
-                FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-                memcpy(hstate, ctx->pinned(), sizeof(hstate));
-            } else {        // one-thread publish kernel + a polled pinned line: 8 us instead of the runtime's 22 (ctx.hip read_words)
-                FGPU_TRY(read_words(ctx, (const u32*)state.p, 2, (u32*)hstate));
-            }
-            stopped = hstate[0] != 0;
-            it = hstate[1];
-            if (timing) {
-                for (int k = 0; k < 4; ++k) {
-                    float ms = 0;
-                    (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-                    acc_ms[k] += ms;
-                }
-            }
+        int hstate[2] = {0, 0};
+        if (timing) {   // (the events below must have completed)
+            FGPU_HIP(hipMemcpyAsync(ctx->pinned(), state.p, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream()));
+            FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+            memcpy(hstate, ctx->pinned(), sizeof(hstate));
+        } else {        // one-thread publish kernel + a polled pinned line: 8 us instead of the runtime's 22 (ctx.hip read_words)
+            FGPU_TRY(read_words(ctx, (const u32*)state.p, 2, (u32*)hstate));
         }
-        // the scores of iteration `it` sit in t's buffer after an odd number of executed iterations, in r's after an even one
-        rp = (it & 1) ? t.p : r.p;
+        stopped = hstate[0] != 0;
+        it = hstate[1];
         if (timing) {
-            fprintf(stderr, "fgpu_pagerank timing over %d iterations (ms): prep+reduce %.3f  spmv %.3f  hubs %.3f  "
-                            "final reduce %.3f  (n_hub_chunks %u)\n", it, acc_ms[0], acc_ms[1], acc_ms[2], acc_ms[3],
-                    At->n_hub_chunks);
-            for (auto& e : ev) (void)hipEventDestroy(e);
+            for (int k = 0; k < 4; ++k) {
+                float ms = 0;
+                (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+                acc_ms[k] += ms;
+            }
         }
-        if (iters) *iters = it;
-        if (converged) *converged = stopped ? 1 : 0;   // the last executed iteration moved the scores by no more than tol
-        FGPU_TRY(ctx->d2h(centrality, rp, (size_t)n * sizeof(float)));
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        return FGPU_OK;
-    };
-    if (info == FGPU_OK) info = run();
-    if (dA) mat_release(dA);
-    if (dAt) mat_release(dAt);
-    return info;
+    }
+    // the scores of iteration `it` sit in t's buffer after an odd number of executed iterations, in r's after an even one
+    rp = (it & 1) ? t.p : r.p;
+    if (timing) {
+        fprintf(stderr, "fgpu_pagerank timing over %d iterations (ms): prep+reduce %.3f  spmv %.3f  hubs %.3f  "
+                        "final reduce %.3f  (n_hub_chunks %u)\n", it, acc_ms[0], acc_ms[1], acc_ms[2], acc_ms[3],
+                At->n_hub_chunks);
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    if (iters) *iters = it;
+    if (converged) *converged = stopped ? 1 : 0;   // the last executed iteration moved the scores by no more than tol
+    FGPU_TRY(ctx->d2h(centrality, rp, (size_t)n * sizeof(float)));
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+    return FGPU_OK;
 }

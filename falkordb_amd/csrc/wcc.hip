@@ -28,7 +28,7 @@
 // Compression is pointer jumping by whole launches (parent[v] = parent[parent[v]]) until a launch changes nothing: each halves
 // the depth of every tree, so a path of n vertices hooked in id order costs log2(n) launches, not a walk of n per vertex.
 // No dynamic LDS; the static LDS of the word kernel is 2 KiB per workgroup, the sample kernel's 4 KiB.
-#include "common.hpp"
+#include "algo.hpp"
 
 namespace fgpu {
 
@@ -38,10 +38,6 @@ constexpr u64 WCC_SEED = 0x57CC2018ull;
 constexpr u32 WCC_NONE = 0xFFFFFFFFu;
 constexpr u32 WCC_MAX_JUMPS = 40;      // pointer-jumping launches of one compress: 33 flatten any forest of < 2^32 vertices
 constexpr u32 WCC_AUTO_MIN_N = 4096;   // wcc_mode 0: Afforest from this many vertices, the full pass below
-
-__device__ __forceinline__ bool wcc_on(const u64* __restrict__ act, u32 v) {
-    return !act || ((act[v >> 6] >> (v & 63)) & 1ull);
-}
 
 // root of x by plain loads with path halving (see the rules above)
 __device__ __forceinline__ u32 wcc_find(u32* parent, u32 x) {
@@ -67,20 +63,6 @@ __device__ __forceinline__ void wcc_link(u32* parent, u32 u, u32 w) {
     }
 }
 
-// adds a 256-thread workgroup's x into *dst with ONE atomic: one per wave onto a single word serialises (16 K waves of a
-// grid-stride launch at RMAT-22 made the count passes 0.26-0.53 ms)
-__device__ __forceinline__ void block_add_u64(u64 x, unsigned long long* dst) {
-    __shared__ u64 s_part[4];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    if (lane_id() == 0) s_part[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const u64 t = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        if (t) atomicAdd(dst, (unsigned long long)t);
-    }
-}
-
 __global__ void wcc_init_kernel(u32* __restrict__ parent, u32 n) {
     for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) parent[v] = v;
 }
@@ -90,12 +72,12 @@ __global__ __launch_bounds__(256) void wcc_link_round_kernel(CsrView a, const u6
                                                             unsigned long long* entries) {
     u64 took = 0;
     for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
-        if (!wcc_on(act, v)) continue;
+        if (!vertex_on(act, v)) continue;
         const u32 b = a.rowptr[v], e = a.rowptr[v + 1];
         if (e - b <= r) continue;
         const u32 w = a.colidx[b + r];
         ++took;
-        if (wcc_on(act, w)) wcc_link(parent, v, w);
+        if (vertex_on(act, w)) wcc_link(parent, v, w);
     }
     block_add_u64(took, entries);
 }
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(256) void wcc_link_words_kernel(CsrView a, const u6
         const u32 v = (g << 6) + lane;
         u32 rb = 0, re = 0;
         if (v < n) { rb = a.rowptr[v]; re = a.rowptr[v + 1]; }
-        const bool take = v < n && re - rb > first && re - rb < HUB_DEG && wcc_on(act, v) && (c == WCC_NONE || parent[v] != c);
+        const bool take = v < n && re - rb > first && re - rb < HUB_DEG && vertex_on(act, v) && (c == WCC_NONE || parent[v] != c);
         const u32 len = take ? re - rb - first : 0u;
         u32 inc = len;
 #pragma unroll
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(256) void wcc_link_words_kernel(CsrView a, const u6
                 if (off[mid] <= e) lo = mid; else hi = mid;
             }
             const u32 w = col[rbs[lo] + (e - off[lo])];
-            if (wcc_on(act, w)) wcc_link(parent, (g << 6) + lo, w);
+            if (vertex_on(act, w)) wcc_link(parent, (g << 6) + lo, w);
         }
     }
     block_add_u64(seen, entries);
@@ -164,7 +146,7 @@ __global__ __launch_bounds__(256) void wcc_link_hubs_kernel(const u32* __restric
         const u32 lo = rowptr[row] + first;
         if (b < lo) b = lo;
         // one decision for the whole workgroup (the threads' plain loads of parent[row] need not agree)
-        if (threadIdx.x == 0) s_take = (b < e && wcc_on(act, row) && (c == WCC_NONE || parent[row] != c)) ? 1u : 0u;
+        if (threadIdx.x == 0) s_take = (b < e && vertex_on(act, row) && (c == WCC_NONE || parent[row] != c)) ? 1u : 0u;
         __syncthreads();
         const bool take = s_take != 0;
         __syncthreads();
@@ -172,7 +154,7 @@ __global__ __launch_bounds__(256) void wcc_link_hubs_kernel(const u32* __restric
         if (threadIdx.x == 0) seen += e - b;
         for (u32 i = b + threadIdx.x; i < e; i += 256) {
             const u32 w = col[i];
-            if (wcc_on(act, w)) wcc_link(parent, row, w);
+            if (vertex_on(act, w)) wcc_link(parent, row, w);
         }
     }
     if (threadIdx.x == 0 && seen) atomicAdd(entries, (unsigned long long)seen);
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(WCC_SAMPLES) void wcc_sample_kernel(const u32* __re
     __shared__ unsigned long long best;
     const u32 t = threadIdx.x;
     const u32 v = (u32)(mix64(WCC_SEED + t) % n);
-    s[t] = wcc_on(act, v) ? parent[v] : WCC_NONE;
+    s[t] = vertex_on(act, v) ? parent[v] : WCC_NONE;
     if (t == 0) best = 0ull;
     __syncthreads();
     for (u32 k = 2; k <= WCC_SAMPLES; k <<= 1) {
@@ -231,14 +213,13 @@ __global__ __launch_bounds__(256) void wcc_finish_kernel(const u32* __restrict__
     const u32 gc = c != WCC_NONE ? parent[c] : WCC_NONE;
     u64 roots = 0, gsz = 0;
     for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
-        if (!wcc_on(act, v)) { out[v] = -1; continue; }
+        if (!vertex_on(act, v)) { out[v] = -1; continue; }
         const u32 r = parent[v];
         out[v] = (long long)r;
         roots += r == v ? 1u : 0u;
         gsz += r == gc ? 1u : 0u;
     }
     block_add_u64(roots, &cnt[0]);
-    __syncthreads();
     block_add_u64(gsz, &cnt[1]);
 }
 
@@ -276,9 +257,8 @@ static fgpu_info wcc_link_rows(fgpu_ctx* ctx, const fgpu_mat* m, const u64* act,
     FGPU_HIP(hipGetLastError());
     ++*launches;
     if (m->n_hub_chunks) {
-        const u32 hg = m->n_hub_chunks < (u32)ctx->cus * 8 ? m->n_hub_chunks : (u32)ctx->cus * 8;
-        hipLaunchKernelGGL(wcc_link_hubs_kernel, dim3(hg), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks, m->n_hub_chunks,
-                           (const u32*)m->rowptr, (const u32*)m->colidx, act, parent, first, giant, entries);
+        hipLaunchKernelGGL(wcc_link_hubs_kernel, dim3(hub_grid(ctx, m)), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks,
+                           m->n_hub_chunks, (const u32*)m->rowptr, (const u32*)m->colidx, act, parent, first, giant, entries);
         FGPU_HIP(hipGetLastError());
         ++*launches;
     }
@@ -292,88 +272,65 @@ using namespace fgpu;
 extern "C" fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
                               int64_t* component, uint64_t stats[4]) {
     FGPU_REQUIRE(ctx && A && component, FGPU_NULL_POINTER, "fgpu_wcc: NULL argument");
-    FGPU_REQUIRE(A->nrows == A->ncols, FGPU_DIM_MISMATCH, "fgpu_wcc: adjacency must be square");
-    FGPU_REQUIRE(!At || (At->nrows == A->nrows && At->ncols == A->ncols), FGPU_DIM_MISMATCH,
-                 "fgpu_wcc: transpose has different dimensions");
-    FGPU_REQUIRE(A->nrows < WCC_NONE, FGPU_INVALID, "fgpu_wcc: too many vertices");
+    FGPU_TRY(check_adjacency("fgpu_wcc", A, At));
     if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
     const u32 n = (u32)A->nrows;
     if (n == 0) return FGPU_OK;
     const int mode = ctx->opt.wcc_mode ? ctx->opt.wcc_mode : (n >= WCC_AUTO_MIN_N ? 1 : 2);
     const bool afforest = mode == 1;
-    if (!afforest) At = nullptr;   // the full pass reads every entry of A once: each joins both of its endpoints
-    // dense row pointers are indexed below: hypersparse inputs are densified first
-    fgpu_mat *dA = nullptr, *dAt = nullptr;
-    fgpu_info info = FGPU_OK;
-    if (A->is_hyper()) {
-        info = mat_merge_entries(ctx, &dA, A, nullptr, nullptr, false, A->nrows, A->ncols, true);
-        A = dA;
-    }
-    if (info == FGPU_OK && At && At->is_hyper()) {
-        info = mat_merge_entries(ctx, &dAt, At, nullptr, nullptr, false, At->nrows, At->ncols, true);
-        At = dAt;
-    }
-    auto run = [&]() -> fgpu_info {
-        FGPU_TRY(mat_ensure_finalized(A));   // the hub lists
-        if (At) FGPU_TRY(mat_ensure_finalized(At));
-        DevBuf<u64> act;
-        DevBuf<u32> parent, giant, flags;
-        DevBuf<unsigned long long> cnt;
-        DevBuf<long long> wide;
-        if (active_bitmap) {
-            const size_t words = ((size_t)n + 63) / 64;
-            FGPU_TRY(act.alloc(ctx, words));
-            FGPU_TRY(ctx->h2d(act.p, active_bitmap, words * sizeof(u64)));
-            if (n & 63) {   // bits past n are not vertices
-                const u64 last = active_bitmap[words - 1] & ((1ull << (n & 63)) - 1ull);
-                FGPU_TRY(ctx->h2d(act.p + words - 1, &last, sizeof(u64)));
-            }
-        }
-        FGPU_TRY(parent.alloc(ctx, n));
-        FGPU_TRY(giant.alloc(ctx, 1));
-        FGPU_TRY(flags.alloc(ctx, WCC_MAX_JUMPS));
-        FGPU_TRY(cnt.alloc(ctx, 3));   // entries read, roots, giant size
-        FGPU_TRY(wide.alloc(ctx, n));
-        FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
-        FGPU_HIP(hipMemsetAsync(giant.p, 0xFF, sizeof(u32), ctx->stream()));
-        const u64* a = act.p;
-        const u32 grid = wcc_grid(ctx, n, 256);
-        hipLaunchKernelGGL(wcc_init_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent.p, n);
-        FGPU_HIP(hipGetLastError());
-        u64 launches = 0;
-        if (afforest) {
-            for (u32 r = 0; r < WCC_ROUNDS; ++r) {
-                hipLaunchKernelGGL(wcc_link_round_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(A), a, parent.p, n, r,
-                                   cnt.p);
-                FGPU_HIP(hipGetLastError());
-                ++launches;
-                FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
-            }
-            hipLaunchKernelGGL(wcc_sample_kernel, dim3(1), dim3(WCC_SAMPLES), 0, ctx->stream(), (const u32*)parent.p, a, n, giant.p);
+    // a NULL At is the caller's promise of a symmetric pattern; the full pass reads every entry of A once, each joins both of
+    // its endpoints, and never needs At
+    if (!afforest) At = nullptr;
+    DenseInputs in;
+    FGPU_TRY(in.a(ctx, A));
+    FGPU_TRY(in.at(ctx, At));
+    FGPU_TRY(mat_ensure_finalized(A));   // the hub lists
+    if (At) FGPU_TRY(mat_ensure_finalized(At));
+    DevBuf<u64> act;
+    DevBuf<u32> parent, giant, flags;
+    DevBuf<unsigned long long> cnt;
+    DevBuf<long long> wide;
+    if (active_bitmap) FGPU_TRY(upload_active(ctx, act, active_bitmap, n));
+    FGPU_TRY(parent.alloc(ctx, n));
+    FGPU_TRY(giant.alloc(ctx, 1));
+    FGPU_TRY(flags.alloc(ctx, WCC_MAX_JUMPS));
+    FGPU_TRY(cnt.alloc(ctx, 3));   // entries read, roots, giant size
+    FGPU_TRY(wide.alloc(ctx, n));
+    FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(giant.p, 0xFF, sizeof(u32), ctx->stream()));
+    const u64* a = act.p;
+    const u32 grid = wcc_grid(ctx, n, 256);
+    hipLaunchKernelGGL(wcc_init_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent.p, n);
+    FGPU_HIP(hipGetLastError());
+    u64 launches = 0;
+    if (afforest) {
+        for (u32 r = 0; r < WCC_ROUNDS; ++r) {
+            hipLaunchKernelGGL(wcc_link_round_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(A), a, parent.p, n, r,
+                               cnt.p);
             FGPU_HIP(hipGetLastError());
-            FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, WCC_ROUNDS, giant.p, cnt.p, &launches));
-            if (At) FGPU_TRY(wcc_link_rows(ctx, At, a, parent.p, n, 0, giant.p, cnt.p, &launches));
-        } else {
-            FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, 0, nullptr, cnt.p, &launches));
+            ++launches;
+            FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
         }
-        FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
-        hipLaunchKernelGGL(wcc_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)parent.p, a, n,
-                           afforest ? (const u32*)giant.p : nullptr, wide.p, cnt.p + 1);
+        hipLaunchKernelGGL(wcc_sample_kernel, dim3(1), dim3(WCC_SAMPLES), 0, ctx->stream(), (const u32*)parent.p, a, n, giant.p);
         FGPU_HIP(hipGetLastError());
-        FGPU_TRY(ctx->d2h(component, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when component[] is pinned
-        if (stats) {
-            unsigned long long h[3];
-            FGPU_TRY(ctx->d2h(h, cnt.p, sizeof(h)));
-            stats[0] = h[1];
-            stats[1] = h[0];
-            stats[2] = launches;
-            stats[3] = afforest ? h[2] : 0;
-        }
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        return FGPU_OK;
-    };
-    if (info == FGPU_OK) info = run();
-    if (dA) mat_release(dA);
-    if (dAt) mat_release(dAt);
-    return info;
+        FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, WCC_ROUNDS, giant.p, cnt.p, &launches));
+        if (At) FGPU_TRY(wcc_link_rows(ctx, At, a, parent.p, n, 0, giant.p, cnt.p, &launches));
+    } else {
+        FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, 0, nullptr, cnt.p, &launches));
+    }
+    FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
+    hipLaunchKernelGGL(wcc_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)parent.p, a, n,
+                       afforest ? (const u32*)giant.p : nullptr, wide.p, cnt.p + 1);
+    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(ctx->d2h(component, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when component[] is pinned
+    if (stats) {
+        unsigned long long h[3];
+        FGPU_TRY(ctx->d2h(h, cnt.p, sizeof(h)));
+        stats[0] = h[1];
+        stats[1] = h[0];
+        stats[2] = launches;
+        stats[3] = afforest ? h[2] : 0;
+    }
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+    return FGPU_OK;
 }

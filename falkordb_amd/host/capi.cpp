@@ -31,9 +31,11 @@ static int guard(F f) {
     }
 }
 
-static uint64_t* hand(const std::vector<u64>& v) {
-    uint64_t* p = (uint64_t*)malloc((v.size() ? v.size() : 1) * sizeof(uint64_t));
-    if (p && !v.empty()) memcpy(p, v.data(), v.size() * sizeof(uint64_t));
+// a malloc'ed copy of v for the caller to fh_free (never NULL for an empty v)
+template <class T>
+static T* hand(const std::vector<T>& v) {
+    T* p = (T*)malloc((v.size() ? v.size() : 1) * sizeof(T));
+    if (p && !v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
     return p;
 }
 
@@ -46,7 +48,20 @@ static std::vector<std::string> split(const std::string& s, char sep) {
     return out;
 }
 
+// a comma list argument ("" or NULL = none; empty items are dropped)
+static std::vector<std::string> csv(const char* s) { return split(s ? s : "", ','); }
+
 static thread_local uint64_t g_last_op_ns = 0;   // duration of the last timed operator inside this thread (fh_last_op_ns)
+
+// runs op() as this thread's timed operator.  The interval is op() alone: arguments are unpacked before it unless op does
+// that itself, results are copied out after it; an op() that throws leaves the previous duration in place.
+template <class F>
+static auto timed(F op) {
+    const auto t0 = std::chrono::steady_clock::now();
+    auto r = op();
+    g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    return r;
+}
 
 static CondTraverseOp parse_spec(const char* spec) {
     CondTraverseOp op;
@@ -454,9 +469,7 @@ int fh_cond_traverse_batch(fh_graph* g, const char* spec, const int64_t* src, co
         static thread_local ExpandedRows rows;
         static thread_local std::vector<u64> nulls;
         u64 fl = 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool ok = op.expand_batch(g->g, s, to_bound ? &tb : nullptr, rows, nulls, &fl);
-        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        bool ok = timed([&] { return op.expand_batch(g->g, s, to_bound ? &tb : nullptr, rows, nulls, &fl); });
         *batched = ok ? 1 : 0;
         const size_t n_rows = rows.size();
         int64_t* e = (int64_t*)malloc((rows.size() ? rows.size() : 1) * sizeof(int64_t));
@@ -525,7 +538,7 @@ int fh_expand_into(fh_graph* g, const char* types, int bidirectional, int emit_r
                    uint64_t** out_dst, uint64_t** out_edge, uint64_t* n) {
     return guard([&] {
         ExpandIntoOp op;
-        op.types = split(types ? types : "", ',');
+        op.types = csv(types);
         op.bidirectional = bidirectional != 0;
         op.emit_relationship = emit_relationship != 0;
         std::vector<std::vector<std::array<u64, 3>>> per_row(k);
@@ -552,8 +565,8 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
                         uint64_t stats[3]) {
     return guard([&] {
         CondVarLenTraverseOp op;
-        op.types = split(types ? types : "", ',');
-        op.dst_labels = split(dst_labels ? dst_labels : "", ',');
+        op.types = csv(types);
+        op.dst_labels = csv(dst_labels);
         op.reversed = reversed != 0;
         op.bidirectional = bidirectional != 0;
         op.min_hops = min_hops;
@@ -580,19 +593,27 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
     });
 }
 
+// fh_algo_bfs and fh_algo_bfs_multi: one call but for the gang (nullptr: the graph's own context); only the single-context
+// entry is a timed operator
+static int algo_bfs_c(fh_graph* g, const std::vector<Context*>* gang, int64_t source, int64_t max_depth, const char* rel_type,
+                      int want_edges, int* has_row, uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, uint64_t* n_edges) {
+    auto run = [&] {
+        return algo_bfs(g->g, source >= 0 ? std::optional<u64>((u64)source) : std::nullopt, max_depth,
+                        rel_type ? std::optional<std::string>(rel_type) : std::nullopt, want_edges != 0, gang);
+    };
+    BfsResult r = gang ? run() : timed(run);
+    *has_row = r.has_row ? 1 : 0;
+    *nodes = hand(r.nodes);
+    *n_nodes = r.nodes.size();
+    *edges = hand(r.edges);
+    *n_edges = r.edges.size();
+    return 0;
+}
+
 int fh_algo_bfs(fh_graph* g, int64_t source, int64_t max_depth, const char* rel_type, int want_edges, int* has_row,
                 uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, uint64_t* n_edges) {
     return guard([&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        BfsResult r = algo_bfs(g->g, source >= 0 ? std::optional<u64>((u64)source) : std::nullopt, max_depth,
-                               rel_type ? std::optional<std::string>(rel_type) : std::nullopt, want_edges != 0);
-        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        *has_row = r.has_row ? 1 : 0;
-        *nodes = hand(r.nodes);
-        *n_nodes = r.nodes.size();
-        *edges = hand(r.edges);
-        *n_edges = r.edges.size();
-        return 0;
+        return algo_bfs_c(g, nullptr, source, max_depth, rel_type, want_edges, has_row, nodes, n_nodes, edges, n_edges);
     });
 }
 
@@ -602,14 +623,7 @@ int fh_algo_bfs_multi(fh_graph* g, fh_ctx* const* gang, int n_gang, int64_t sour
     return guard([&] {
         std::vector<Context*> cs;
         for (int i = 0; i < n_gang; ++i) cs.push_back(&gang[i]->c);
-        BfsResult r = algo_bfs(g->g, source >= 0 ? std::optional<u64>((u64)source) : std::nullopt, max_depth,
-                               rel_type ? std::optional<std::string>(rel_type) : std::nullopt, want_edges != 0, &cs);
-        *has_row = r.has_row ? 1 : 0;
-        *nodes = hand(r.nodes);
-        *n_nodes = r.nodes.size();
-        *edges = hand(r.edges);
-        *n_edges = r.edges.size();
-        return 0;
+        return algo_bfs_c(g, &cs, source, max_depth, rel_type, want_edges, has_row, nodes, n_nodes, edges, n_edges);
     });
 }
 
@@ -652,9 +666,7 @@ int fh_mat_encode(fh_mat* m, uint8_t** bytes, uint64_t* len) {
 // build_adjacency_matrix / build_symmetric_adjacency_matrix (graph.rs:3870-3907); types = comma list, "" = all
 int fh_graph_build_adjacency(fh_graph* g, const char* types, int symmetric, fh_mat** out) {
     return guard([&] {
-        std::vector<std::string> ts;
-        for (auto& t : split(types ? types : "", ','))
-            if (!t.empty()) ts.push_back(t);
+        const std::vector<std::string> ts = csv(types);
         *out = new fh_mat{symmetric ? g->g.build_symmetric_adjacency_matrix(ts) : g->g.build_adjacency_matrix(ts)};
         return 0;
     });
@@ -693,14 +705,12 @@ int fh_plan_fuse(const char* plan_text, int lower_id, char** out_text, char** sp
 int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint64_t** nodes, double** scores,
                      uint64_t* n) {
     return guard([&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        PageRankResult r = algo_pagerank(g->g, label ? std::optional<std::string>(label) : std::nullopt,
-                                         rel_type ? std::optional<std::string>(rel_type) : std::nullopt);
-        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        PageRankResult r = timed([&] {
+            return algo_pagerank(g->g, label ? std::optional<std::string>(label) : std::nullopt,
+                                 rel_type ? std::optional<std::string>(rel_type) : std::nullopt);
+        });
         *nodes = hand(r.nodes);
-        double* sc = (double*)malloc((r.scores.size() ? r.scores.size() : 1) * sizeof(double));
-        if (sc && !r.scores.empty()) memcpy(sc, r.scores.data(), r.scores.size() * sizeof(double));
-        *scores = sc;
+        *scores = hand(r.scores);
         *n = r.nodes.size();
         return 0;
     });
@@ -709,18 +719,9 @@ int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint6
 // algo.WCC: labels / types = comma lists, "" = all
 int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, int64_t** component_ids, uint64_t* n) {
     return guard([&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<std::string> ls, ts;
-        for (auto& l : split(labels ? labels : "", ','))
-            if (!l.empty()) ls.push_back(l);
-        for (auto& t : split(types ? types : "", ','))
-            if (!t.empty()) ts.push_back(t);
-        WccResult r = algo_wcc(g->g, ls, ts);
-        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        WccResult r = timed([&] { return algo_wcc(g->g, csv(labels), csv(types)); });
         *nodes = hand(r.nodes);
-        int64_t* c = (int64_t*)malloc((r.component_ids.size() ? r.component_ids.size() : 1) * sizeof(int64_t));
-        if (c && !r.component_ids.empty()) memcpy(c, r.component_ids.data(), r.component_ids.size() * sizeof(int64_t));
-        *component_ids = c;
+        *component_ids = hand(r.component_ids);
         *n = r.nodes.size();
         return 0;
     });
@@ -730,18 +731,9 @@ int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** n
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {
     return guard([&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<std::string> ls, ts;
-        for (auto& l : split(labels ? labels : "", ','))
-            if (!l.empty()) ls.push_back(l);
-        for (auto& t : split(types ? types : "", ','))
-            if (!t.empty()) ts.push_back(t);
-        BetweennessResult r = algo_betweenness(g->g, ls, ts, sampling_size, sampling_seed);
-        g_last_op_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        BetweennessResult r = timed([&] { return algo_betweenness(g->g, csv(labels), csv(types), sampling_size, sampling_seed); });
         *nodes = hand(r.nodes);
-        double* sc = (double*)malloc((r.scores.size() ? r.scores.size() : 1) * sizeof(double));
-        if (sc && !r.scores.empty()) memcpy(sc, r.scores.data(), r.scores.size() * sizeof(double));
-        *scores = sc;
+        *scores = hand(r.scores);
         *n = r.nodes.size();
         return 0;
     });

@@ -811,9 +811,7 @@ BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
     }
     if (want_edges && !res.nodes.empty()) {
         // edges[k] = first id of get_src_dest_relationships(parent, child, types), batched per type
-        std::vector<u64> tids;
-        if (rel_type) { if (auto id = g.type_id(*rel_type)) tids.push_back(*id); }
-        else for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+        const std::vector<u64> tids = resolve_types(g, types);
         std::vector<std::optional<u64>> rep(ps.size());
         for (u64 t : tids) {
             std::vector<std::vector<u64>> ids;
@@ -828,46 +826,71 @@ BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
     return res;
 }
 
+// ---- what algo.pageRank, algo.WCC and algo.betweenness share ---------------------------------------------
+// The nodes a procedure runs over: the union of the labels' nodes minus the deleted ids (collect_node_ids, :456-477), as a
+// bitmap over the full id space — the reference's compact graph (build_compact_adj_from_tensors), here an induced subgraph.
+// An unknown label selects no node.  `ids` (nullable) receives the selected ids in ascending order (compact_to_id).
+struct NodeSelection {
+    std::vector<u64> bits;
+    u64 count = 0;
+    bool has(u64 v) const { return (bits[v >> 6] >> (v & 63)) & 1ull; }
+};
+static NodeSelection select_nodes(const Graph& g, const std::vector<std::string>& labels, std::vector<u64>* ids = nullptr) {
+    const u64 n = g.node_cap();
+    NodeSelection sel;
+    sel.bits.assign((n + 63) / 64, 0);
+    for (auto& l : labels)
+        if (auto lid = g.label_id(l)) {
+            const std::vector<u64> bits = g.label_bitmap({*lid});
+            for (size_t w = 0; w < sel.bits.size(); ++w) sel.bits[w] |= bits[w];
+        }
+    for (u64 v = 0; v < n; ++v) {
+        if (g.is_node_deleted(v)) sel.bits[v >> 6] &= ~(1ull << (v & 63));
+        if (!sel.has(v)) continue;
+        ++sel.count;
+        if (ids) ids->push_back(v);
+    }
+    return sel;
+}
+
+// one result row per live node (sel, nullable: that is also selected), in id order; value(v) is the row's second column
+template <typename T, typename F>
+static void emit_rows(const Graph& g, const NodeSelection* sel, std::vector<u64>& nodes, std::vector<T>& values, F value) {
+    for (u64 v = 0; v < g.node_cap(); ++v) {
+        if (g.is_node_deleted(v)) continue;
+        if (sel && !sel->has(v)) continue;
+        nodes.push_back(v);
+        values.push_back(value(v));
+    }
+}
+
 // ---- algo.pageRank -------------------------------------------------------------------------------------
 PageRankResult algo_pagerank(const Graph& g, const std::optional<std::string>& label,
                              const std::optional<std::string>& rel_type) {
     PageRankResult res;
     const u64 n = g.node_cap();
-    u64 live = 0;
-    for (u64 v = 0; v < n; ++v) live += g.is_node_deleted(v) ? 0 : 1;
+    const u64 live = g.live_nodes();
     if (live == 0) return res;                                           // node_count() == 0 (:699-701)
     std::vector<std::string> types;
     if (rel_type) types.push_back(*rel_type);
     // a label that covers every live node is the unfiltered run (:711-713); otherwise the labelled nodes form a
     // compact graph of their own (:725-733) — here the induced subgraph selected by a bitmap
-    std::vector<u64> active;
+    NodeSelection sel;
     bool filtered = false;
     if (label) {
-        auto lid = g.label_id(*label);
-        if (!lid) return res;                                            // no node carries an unknown label
-        active = g.label_bitmap({*lid});
-        u64 cnt = 0;
-        for (u64 v = 0; v < n; ++v) {
-            if (g.is_node_deleted(v)) active[v >> 6] &= ~(1ull << (v & 63));
-            cnt += (active[v >> 6] >> (v & 63)) & 1ull;
-        }
-        filtered = cnt != live;
-        if (cnt == 0) return res;
+        sel = select_nodes(g, {*label});
+        if (sel.count == 0) return res;                                  // (no node carries an unknown label)
+        filtered = sel.count != live;
     }
     Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894
     std::vector<float> score(n);
     int32_t iters = 0;
     // deleted ids stay in the unfiltered matrix as isolated vertices (n = node_count + deleted_nodes_count, :718-720)
     Matrix adj_t = adj.transpose();                                      // LAGraph_Cached_AT (:736-737); cached per snapshot
-    check(fgpu_pagerank(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? active.data() : nullptr, 0.85f, 1e-4f, 100,
+    check(fgpu_pagerank(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? sel.bits.data() : nullptr, 0.85f, 1e-4f, 100,
                         score.data(), &iters),
           "LAGr_PageRank");
-    for (u64 v = 0; v < n; ++v) {
-        if (g.is_node_deleted(v)) continue;                              // :768-770
-        if (filtered && !((active[v >> 6] >> (v & 63)) & 1ull)) continue;
-        res.nodes.push_back(v);
-        res.scores.push_back((double)score[v]);
-    }
+    emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.scores, [&](u64 v) { return (double)score[v]; });   // :768-770
     return res;
 }
 
@@ -875,26 +898,13 @@ PageRankResult algo_pagerank(const Graph& g, const std::optional<std::string>& l
 WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types) {
     WccResult res;
     const u64 n = g.node_cap();
-    u64 live = 0;
-    for (u64 v = 0; v < n; ++v) live += g.is_node_deleted(v) ? 0 : 1;
-    if (live == 0) return res;                                           // node_count() == 0 (:801-803)
-    // labels: the union of the labels' live nodes (collect_node_ids, :456-477) as an induced subgraph — the reference's compact
-    // graph (:817-826), here selected by a bitmap over the full id space
-    std::vector<u64> active;
+    if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:801-803)
+    // labels: the union of the labels' live nodes as an induced subgraph — the reference's compact graph (:817-826)
+    NodeSelection sel;
     const bool filtered = !labels.empty();
     if (filtered) {
-        active.assign((n + 63) / 64, 0);
-        for (auto& l : labels)
-            if (auto lid = g.label_id(l)) {                              // an unknown label selects no node
-                const std::vector<u64> bits = g.label_bitmap({*lid});
-                for (size_t w = 0; w < active.size(); ++w) active[w] |= bits[w];
-            }
-        u64 cnt = 0;
-        for (u64 v = 0; v < n; ++v) {
-            if (g.is_node_deleted(v)) active[v >> 6] &= ~(1ull << (v & 63));
-            cnt += (active[v >> 6] >> (v & 63)) & 1ull;
-        }
-        if (cnt == 0) return res;                                        // :822-824
+        sel = select_nodes(g, labels);
+        if (sel.count == 0) return res;                                  // :822-824
     }
     // the plain adjacency and its per-snapshot cached transpose: the undirected view without building A (+) A' per call
     // (build_symmetric_adjacency_matrix, :813); unknown types contribute no edges.  Deleted ids stay in the unfiltered run
@@ -902,7 +912,7 @@ WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const
     Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894
     Matrix adj_t = adj.transpose();
     std::vector<int64_t> comp(n);
-    check(fgpu_wcc(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? active.data() : nullptr, comp.data(), nullptr),
+    check(fgpu_wcc(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? sel.bits.data() : nullptr, comp.data(), nullptr),
           "LAGr_ConnectedComponents");
     // a filtered run's componentId is the representative's COMPACT index — its rank among the selected ids in ascending
     // order (:617-626) — which the reference never maps back to a node id (:854-868)
@@ -911,14 +921,11 @@ WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const
         rank.assign(n, -1);
         int64_t k = 0;
         for (u64 v = 0; v < n; ++v)
-            if ((active[v >> 6] >> (v & 63)) & 1ull) rank[v] = k++;
+            if (sel.has(v)) rank[v] = k++;
     }
-    for (u64 v = 0; v < n; ++v) {
-        if (g.is_node_deleted(v)) continue;                              // :857-859
-        if (filtered && comp[v] < 0) continue;
-        res.nodes.push_back(v);
-        res.component_ids.push_back(filtered ? rank[(size_t)comp[v]] : comp[v]);
-    }
+    // (fgpu_wcc writes comp[v] = -1 exactly for the unselected v)
+    emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.component_ids,
+              [&](u64 v) { return filtered ? rank[(size_t)comp[v]] : comp[v]; });   // :857-859
     return res;
 }
 
@@ -957,26 +964,14 @@ BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string
                                    int64_t sampling_size, int64_t sampling_seed) {
     BetweennessResult res;
     const u64 n = g.node_cap();
-    u64 live = 0;
-    for (u64 v = 0; v < n; ++v) live += g.is_node_deleted(v) ? 0 : 1;
     if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // before the graph (:900-905)
-    if (live == 0) return res;                                           // node_count() == 0 (:916-918)
-    // labels: the union of the labels' live nodes (collect_node_ids) as an induced subgraph — the reference's compact graph
-    // (build_compact_adj_from_tensors, :935-940), here selected by a bitmap over the full id space
-    std::vector<u64> active;
+    if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:916-918)
+    // labels: the union of the labels' live nodes as an induced subgraph — the reference's compact graph (:935-940)
+    NodeSelection sel;
     std::vector<u64> selected;                                           // compact index -> node id (compact_to_id)
     const bool filtered = !labels.empty();
     if (filtered) {
-        active.assign((n + 63) / 64, 0);
-        for (auto& l : labels)
-            if (auto lid = g.label_id(l)) {                              // an unknown label selects no node
-                const std::vector<u64> bits = g.label_bitmap({*lid});
-                for (size_t w = 0; w < active.size(); ++w) active[w] |= bits[w];
-            }
-        for (u64 v = 0; v < n; ++v) {
-            if (g.is_node_deleted(v)) active[v >> 6] &= ~(1ull << (v & 63));
-            if ((active[v >> 6] >> (v & 63)) & 1ull) selected.push_back(v);
-        }
+        sel = select_nodes(g, labels, &selected);
         if (selected.empty()) return res;
     }
     // n_nodes: node_count + deleted_nodes_count unfiltered (deleted ids stay as vertices and can be sources), else the
@@ -987,15 +982,10 @@ BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string
     Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894; unknown types add no edges
     Matrix adj_t = adj.transpose();                                      // LAGraph_Cached_AT (:945)
     std::vector<double> cent(n);
-    check(fgpu_betweenness(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? active.data() : nullptr, sources.data(),
+    check(fgpu_betweenness(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), filtered ? sel.bits.data() : nullptr, sources.data(),
                            sources.size(), cent.data(), nullptr),
           "LAGr_Betweenness");
-    for (u64 v = 0; v < n; ++v) {
-        if (g.is_node_deleted(v)) continue;                              // :1003-1005
-        if (filtered && !((active[v >> 6] >> (v & 63)) & 1ull)) continue;
-        res.nodes.push_back(v);
-        res.scores.push_back(cent[v]);
-    }
+    emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.scores, [&](u64 v) { return cent[v]; });   // :1003-1005
     return res;
 }
 

@@ -335,6 +335,13 @@ class Graph {
     void delete_node(u64 node) { deleted_[node] = true; }
     bool is_node_deleted(u64 node) const { return !deleted_.empty() && deleted_.count(node) != 0; }
     u64 deleted_nodes_count() const { return deleted_.size(); }   // graph.rs deleted_nodes_count
+    // graph.rs node_count: the ids below node_cap() that are not deleted (delete_node takes any id: one at or past the
+    // capacity is in deleted_nodes_count() and is not a node)
+    u64 live_nodes() const {
+        u64 live = n_;
+        for (auto& d : deleted_) live -= d.first < n_ ? 1 : 0;
+        return live;
+    }
     // create one edge of `type` (adjacency + tensor), the write-side minimum the tests need
     void create_edge(u64 type, u64 src, u64 dst, u64 edge_id);             // graph.rs:1493-1560 (effect only)
     void delete_edge(u64 type, u64 src, u64 dst, u64 edge_id);             // graph.rs:1623-1700 (effect only)

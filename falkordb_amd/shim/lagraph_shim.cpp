@@ -90,6 +90,30 @@ int check_graph(LAGraph_Graph G, char* msg) {
     return GrB_SUCCESS;
 }
 void check(fgpu_info i, const char* where) { falkor::check(i, where); }
+// A serves as its own transpose: an undirected graph, or a directed one whose structure is cached symmetric (check_graph
+// has refused every kind but 0 and 1 by the time this is asked)
+bool symmetric(LAGraph_Graph G) { return G->kind == 0 || G->is_symmetric_structure == 1; }
+
+// a full result vector of n entries of T over a pinned block of the engine's result pool (`absent` as vector_over_pinned):
+// the engine fills `data`; the vector is freed with the scope unless release() handed it to the caller
+template <typename T>
+struct ResultVector {
+    T* data = nullptr;
+    GrB_Vector vec = nullptr;
+    ResultVector() {}
+    ResultVector(const ResultVector&) = delete;
+    ResultVector& operator=(const ResultVector&) = delete;
+    ~ResultVector() { GrB_Vector_free(&vec); }
+    void alloc(GrB_Type type, uint64_t n, int absent, const char* where) {
+        check(fgpu_host_alloc(fgshim::context()->raw(), (n ? n : 1) * sizeof(T), (void**)&data), where);
+        vec = fgshim::vector_over_pinned(type, n, data, absent);
+    }
+    GrB_Vector release() {
+        GrB_Vector v = vec;
+        vec = nullptr;
+        return v;
+    }
+};
 
 #ifndef FG_LAGRAPHX
 // degree(i) = entries of A(i,:) as a GrB_INT64 vector that stores only the non-zero degrees (lagraph_bindings.rs:115-116)
@@ -217,27 +241,22 @@ int LAGr_PageRank(GrB_Vector* centrality, int* iters, LAGraph_Graph G, float dam
     if (!centrality || !iters) return fail(msg, GrB_NULL_POINTER, "centrality / iters is NULL");
     *centrality = nullptr;
     if (const int r = check_graph(G, msg)) return r;
-    const bool symmetric = G->kind == 0 || (G->kind == 1 && G->is_symmetric_structure == 1);
-    GrB_Matrix AT = symmetric ? G->A : G->AT;
+    GrB_Matrix AT = symmetric(G) ? G->A : G->AT;
     if (!AT) return fail(msg, LAGRAPH_NOT_CACHED, "G->AT is required");
     if (!G->out_degree) return fail(msg, LAGRAPH_NOT_CACHED, "G->out_degree is required");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
-        const uint64_t n = G->A->m.nrows();
-        float* score = nullptr;
-        check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(float), (void**)&score), "LAGr_PageRank");
-        GrB_Vector out = fgshim::vector_over_pinned(fgshim::type_fp32(), n, score, 0);
+        ResultVector<float> out;
+        out.alloc(fgshim::type_fp32(), G->A->m.nrows(), 0, "LAGr_PageRank");
         int32_t it = 0, converged = 1;
-        fgpu_info r = fgpu_pagerank_status(c->raw(), G->A->m.snapshot(), AT->m.snapshot(), nullptr, damping, tol, itermax, score, &it,
-                                           &converged);
+        const fgpu_info r = fgpu_pagerank_status(fgshim::context()->raw(), G->A->m.snapshot(), AT->m.snapshot(), nullptr, damping, tol,
+                                                 itermax, out.data, &it, &converged);
         if (r == FGPU_OK && itermax > 0 && !converged) {   // itermax iterations did not reach tol (one run: the engine reports it)
             *iters = it;
-            GrB_Vector_free(&out);
             return fail(msg, LAGRAPH_CONVERGENCE_FAILURE, "pagerank failed to converge");
         }
-        if (r != FGPU_OK) { GrB_Vector_free(&out); check(r, "LAGr_PageRank"); }
+        check(r, "LAGr_PageRank");
         *iters = it;
-        *centrality = out;
+        *centrality = out.release();
         return GrB_SUCCESS;
     });
 }
@@ -251,19 +270,15 @@ int LAGr_ConnectedComponents(GrB_Vector* component, LAGraph_Graph G, char* msg) 
     if (!component) return fail(msg, GrB_NULL_POINTER, "component is NULL");
     *component = nullptr;
     if (const int r = check_graph(G, msg)) return r;
-    const bool symmetric = G->kind == 0 || G->is_symmetric_structure == 1;
-    if (!symmetric)
+    if (!symmetric(G))
         return fail(msg, GrB_NOT_IMPLEMENTED,
                     "LAGr_ConnectedComponents: symmetric structure required (an undirected graph, or G->is_symmetric_structure = true)");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
-        const uint64_t n = G->A->m.nrows();
-        int64_t* comp = nullptr;
-        check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(int64_t), (void**)&comp), "LAGr_ConnectedComponents");
-        GrB_Vector out = fgshim::vector_over_pinned(fgshim::type_int64(), n, comp, 0);
-        const fgpu_info r = fgpu_wcc(c->raw(), G->A->m.snapshot(), nullptr, nullptr, comp, nullptr);
-        if (r != FGPU_OK) { GrB_Vector_free(&out); check(r, "LAGr_ConnectedComponents"); }
-        *component = out;
+        ResultVector<int64_t> out;
+        out.alloc(fgshim::type_int64(), G->A->m.nrows(), 0, "LAGr_ConnectedComponents");
+        check(fgpu_wcc(fgshim::context()->raw(), G->A->m.snapshot(), nullptr, nullptr, out.data, nullptr),
+              "LAGr_ConnectedComponents");
+        *component = out.release();
         return GrB_SUCCESS;
     });
 }
@@ -277,21 +292,18 @@ int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* s
     *centrality = nullptr;
     if (const int r = check_graph(G, msg)) return r;
     if (ns < 0) return fail(msg, GrB_INVALID_VALUE, "ns is negative");
-    const bool symmetric = G->kind == 0 || (G->kind == 1 && G->is_symmetric_structure == 1);
-    GrB_Matrix AT = symmetric ? G->A : G->AT;
+    GrB_Matrix AT = symmetric(G) ? G->A : G->AT;
     if (!AT) return fail(msg, LAGRAPH_NOT_CACHED, "G->AT is required");
     const uint64_t n = G->A->m.nrows();
     for (int32_t i = 0; i < ns; ++i)
         if (sources[i] >= n) return fail(msg, GrB_INVALID_INDEX, "invalid source node");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
-        double* score = nullptr;
-        check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(double), (void**)&score), "LAGr_Betweenness");
-        GrB_Vector out = fgshim::vector_over_pinned(fgshim::type_fp64(), n, score, 0);
-        const fgpu_info r = fgpu_betweenness(c->raw(), G->A->m.snapshot(), AT->m.snapshot(), nullptr, (const uint64_t*)sources,
-                                             (uint64_t)ns, score, nullptr);
-        if (r != FGPU_OK) { GrB_Vector_free(&out); check(r, "LAGr_Betweenness"); }
-        *centrality = out;
+        ResultVector<double> out;
+        out.alloc(fgshim::type_fp64(), n, 0, "LAGr_Betweenness");
+        check(fgpu_betweenness(fgshim::context()->raw(), G->A->m.snapshot(), AT->m.snapshot(), nullptr, (const uint64_t*)sources,
+                               (uint64_t)ns, out.data, nullptr),
+              "LAGr_Betweenness");
+        *centrality = out.release();
         return GrB_SUCCESS;
     });
 }
@@ -316,23 +328,17 @@ int LAGr_BreadthFirstSearch_Extended(GrB_Vector* level, GrB_Vector* parent, LAGr
     if (src >= n) return fail(msg, GrB_INVALID_INDEX, "invalid source node");
     if (dest >= 0) return fail(msg, GrB_NOT_IMPLEMENTED, "LAGr_BreadthFirstSearch_Extended: dest >= 0 is not provided");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
-        int32_t* lv = nullptr;
-        int64_t* pa = nullptr;
-        check(fgpu_host_alloc(c->raw(), n * sizeof(int32_t), (void**)&lv), "LAGr_BreadthFirstSearch");
-        GrB_Vector lvec = fgshim::vector_over_pinned(fgshim::type_int32(), n, lv, 1), pvec = nullptr;
-        if (parent) {
-            const fgpu_info r = fgpu_host_alloc(c->raw(), n * sizeof(int64_t), (void**)&pa);
-            if (r != FGPU_OK) { GrB_Vector_free(&lvec); check(r, "LAGr_BreadthFirstSearch"); }
-            pvec = fgshim::vector_over_pinned(fgshim::type_int64(), n, pa, 1);
-        }
+        ResultVector<int32_t> lv;   // always computed: the search fills levels whether or not the caller takes them
+        ResultVector<int64_t> pa;
+        lv.alloc(fgshim::type_int32(), n, 1, "LAGr_BreadthFirstSearch");
+        if (parent) pa.alloc(fgshim::type_int64(), n, 1, "LAGr_BreadthFirstSearch");
         // pull needs A'; a directed graph without a cached AT gets the engine's per-snapshot transpose (built once)
-        const bool symmetric = G->kind == 0 || (G->kind == 1 && G->is_symmetric_structure == 1);
-        Matrix at = symmetric ? G->A->m : (G->AT ? G->AT->m : G->A->m.transpose());
-        const fgpu_info r = fgpu_bfs(c->raw(), G->A->m.snapshot(), at.snapshot(), src, max_level < 0 ? -1 : max_level, lv, pa, nullptr);
-        if (r != FGPU_OK) { GrB_Vector_free(&lvec); GrB_Vector_free(&pvec); check(r, "LAGr_BreadthFirstSearch"); }
-        if (level) *level = lvec; else GrB_Vector_free(&lvec);
-        if (parent) *parent = pvec;
+        Matrix at = symmetric(G) ? G->A->m : (G->AT ? G->AT->m : G->A->m.transpose());
+        check(fgpu_bfs(fgshim::context()->raw(), G->A->m.snapshot(), at.snapshot(), src, max_level < 0 ? -1 : max_level, lv.data,
+                       pa.data, nullptr),
+              "LAGr_BreadthFirstSearch");
+        if (level) *level = lv.release();
+        if (parent) *parent = pa.release();
         return GrB_SUCCESS;
     });
 }

@@ -45,6 +45,15 @@ def bitmap(act):
     return np.packbits(bits, bitorder="little").view(np.uint64)
 
 
+def hypersparse(ctx, m):
+    """The same entries stored as a delta layer stores them: the ids of the non-empty rows + a row-pointer array over those."""
+    rp, ci, _ = m.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.nonzero(deg)[0].astype(U64)
+    short = np.concatenate([[0], np.cumsum(deg[deg > 0])]).astype(U64)
+    return ctx.mat_from_csr(m.nrows, m.ncols, short, ci, hyper_rows=rows)
+
+
 def run_dirs(ctx, A, At, sources, act=None):
     """the three directions: bit-identical; returns (centrality, stats of the auto run)"""
     out = {}
@@ -149,6 +158,56 @@ def test_active_bitmap_induced_subgraph(ctx, seed):
     got, _ = run_dirs(ctx, A, A.transpose(), src, bitmap(act))
     close(got, want)
     assert (got[~act] == 0).all()
+
+
+def test_hypersparse_inputs_give_the_bits_of_the_dense_rows(ctx):
+    """A and / or A' stored hypersparse (row list + short row pointers) are densified for the call: identical scores and
+    counters in every direction, with the caller's transpose and with the cached one, with and without an active bitmap —
+    and the one-shot fgpu_bfs, which shares that prelude, returns identical levels, parents and edge counts."""
+    n = 6000
+    rng = np.random.default_rng(43)
+    some = rng.choice(n, 400, replace=False)                            # most rows and columns are empty
+    rows = np.concatenate([rng.choice(some, 3000), np.full(4500, some[0])])
+    cols = np.concatenate([rng.choice(some, 3000), rng.choice(n, 4500, replace=False)])   # + a hub row of 4500 out-edges
+    A, rp, ci = up(ctx, n, rows, cols)
+    At = A.transpose()
+    hA, hAt = hypersparse(ctx, A), hypersparse(ctx, At)
+    src = np.concatenate([some[:20], [some[0]]])
+    for act in (None, bitmap(np.isin(np.arange(n), some) | (rng.random(n) < 0.5))):
+        want, st = run_dirs(ctx, A, At, src, act)
+        for A_, At_ in ((hA, hAt), (hA, At), (A, hAt), (hA, None)):
+            got, st_ = run_dirs(ctx, A_, At_, src, act)
+            assert np.array_equal(got, want) and st_ == st
+    close(run_dirs(ctx, hA, hAt, src)[0], betweenness(n, rp, ci, src)[0])
+    for s in (int(some[0]), int(some[7])):
+        want = engine.bfs(ctx, A, At, s, -1, want_parent=True)
+        for A_, At_ in ((hA, hAt), (hA, At), (A, hAt), (hA, None)):
+            got = engine.bfs(ctx, A_, At_, s, -1, want_parent=True)
+            assert np.array_equal(got[0], want[0]) and got[2] == want[2]
+            assert ((got[0] >= 0) == (got[1] >= 0)).all()               # (which parent wins a level is the kernels' choice)
+            reached = np.flatnonzero((got[0] > 0))
+            assert (want[0][got[1][reached]] == got[0][reached] - 1).all()
+        assert (want[0] >= 0).sum() > 1
+
+
+def test_bits_past_n_in_the_active_bitmap_are_not_vertices(ctx):
+    """n is not a multiple of 64: the last word's bits at and past n are ignored — scores and counters are those of the clean
+    bitmap in every direction."""
+    n = 5000 - 23
+    rng = np.random.default_rng(9)
+    rows, cols = rng.integers(0, n, 12000), rng.integers(0, n, 12000)
+    A, rp, ci = up(ctx, n, rows, cols)
+    At = A.transpose()
+    active = rng.random(n) < 0.7
+    clean = bitmap(active)
+    dirty = clean.copy()
+    dirty[-1] |= U64(~((1 << (n % 64)) - 1) & 0xFFFFFFFFFFFFFFFF)
+    assert n % 64 and dirty[-1] != clean[-1]
+    src = np.flatnonzero(active)[-20:]                                   # (the last word's vertices among them)
+    want, st = run_dirs(ctx, A, At, src, clean)
+    got, st_ = run_dirs(ctx, A, At, src, dirty)
+    assert np.array_equal(got, want) and st_ == st
+    close(got, betweenness(n, rp, ci, src, active)[0])
 
 
 def test_rmat22_sixteen_sources(ctx, bench_graphs):

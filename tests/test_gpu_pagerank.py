@@ -41,6 +41,15 @@ def up(ctx, a):
     return ctx.mat_from_csr(a.nrows, a.ncols, a.rowptr, a.colidx)
 
 
+def hypersparse(ctx, m):
+    """The same entries stored as a delta layer stores them: the ids of the non-empty rows + a row-pointer array over those."""
+    rp, ci, _ = m.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.nonzero(deg)[0].astype(U64)
+    short = np.concatenate([[0], np.cumsum(deg[deg > 0])]).astype(U64)
+    return ctx.mat_from_csr(m.nrows, m.ncols, short, ci, hyper_rows=rows)
+
+
 RTOL = 1e-6   # north_star: "within 1e-6 rel for PLUS_TIMES float semirings"
 
 
@@ -160,3 +169,50 @@ def test_empty_and_edgeless_graphs(ctx):
     np.testing.assert_allclose(got, np.full(5, 0.2, dtype=np.float32), rtol=1e-6)
     got, it = engine.pagerank(ctx, up(ctx, a), None, np.zeros(1, dtype=U64))
     assert (got == 0).all() and it == 0
+
+
+def sparse_rows_graph():
+    """6000 vertices, entries only between 300 of them (most rows and columns empty) + a star of 4500 in-edges into one"""
+    n = 6000
+    rng = np.random.default_rng(77)
+    some = rng.choice(n, 300, replace=False)
+    rows = np.concatenate([rng.choice(some, 2000), rng.choice(n, 4500, replace=False)]).astype(U64)
+    cols = np.concatenate([rng.choice(some, 2000), np.full(4500, some[0])]).astype(U64)
+    return oracle.build_csr(n, n, rows, cols)
+
+
+def test_hypersparse_inputs_give_the_bits_of_the_dense_rows(ctx):
+    """A and / or A' stored hypersparse (row list + short row pointers) are densified for the call: identical scores, with
+    and without a transpose from the caller, with and without an active bitmap."""
+    a = sparse_rows_graph()
+    A = up(ctx, a)
+    At = A.transpose()
+    hA, hAt = hypersparse(ctx, A), hypersparse(ctx, At)
+    act = oracle.bits_from_ids(a.nrows, np.arange(0, a.nrows, 3))
+    for bits in (None, act):
+        want, it = engine.pagerank(ctx, A, At, bits)
+        for A_, At_ in ((hA, hAt), (hA, At), (A, hAt), (hA, None)):
+            got, it_ = engine.pagerank(ctx, A_, At_, bits)
+            assert it_ == it and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    ref, it_ref = opr.pagerank(a)
+    compare(engine.pagerank(ctx, hA, hAt)[0], it_ref, ref, it_ref)
+
+
+def test_bits_past_n_in_the_active_bitmap_are_not_vertices(ctx):
+    """n is not a multiple of 64: the last word's bits at and past n are ignored — the count of active vertices (1 / n_act is
+    every score's start) and the scores are those of the clean bitmap."""
+    n = 6000 - 37
+    rng = np.random.default_rng(3)
+    a = oracle.build_csr(n, n, rng.integers(0, n, 20000).astype(U64), rng.integers(0, n, 20000).astype(U64))
+    A = up(ctx, a)
+    active = rng.random(n) < 0.5
+    clean = oracle.bits_from_ids(n, np.nonzero(active)[0])
+    dirty = clean.copy()
+    dirty[-1] |= U64(~((1 << (n % 64)) - 1) & 0xFFFFFFFFFFFFFFFF)
+    assert n % 64 and dirty[-1] != clean[-1] and len(clean) == (n + 63) // 64
+    for At in (None, A.transpose()):
+        want, it = engine.pagerank(ctx, A, At, clean)
+        got, it_ = engine.pagerank(ctx, A, At, dirty)
+        assert it_ == it and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    ref, it_ref = opr.pagerank(a, active=active)
+    compare(got, it, ref, it_ref)

@@ -45,6 +45,15 @@ def bitmap(act):
     return np.packbits(bits, bitorder="little").view(np.uint64)
 
 
+def hypersparse(ctx, m):
+    """The same entries stored as a delta layer stores them: the ids of the non-empty rows + a row-pointer array over those."""
+    rp, ci, _ = m.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.nonzero(deg)[0].astype(U64)
+    short = np.concatenate([[0], np.cumsum(deg[deg > 0])]).astype(U64)
+    return ctx.mat_from_csr(m.nrows, m.ncols, short, ci, hyper_rows=rows)
+
+
 def run_both(ctx, n, rows, cols, active=None):
     """the directed entries with At, and the symmetrised pattern with At = None: both must give the checker's labels"""
     A, rp, ci = up(ctx, n, rows, cols)
@@ -148,6 +157,49 @@ def test_active_bitmap_induced_subgraph(ctx, seed):
     act[4] = False
     got = run_both(ctx, 10, np.arange(9), np.arange(1, 10), act)
     assert got.tolist() == [0, 0, 0, 0, -1, 5, 5, 5, 5, 5]
+
+
+def test_hypersparse_inputs_give_the_labels_of_the_dense_rows(ctx):
+    """A and / or A' stored hypersparse (row list + short row pointers) are densified for the call: identical labels and
+    component counts, with a transpose and (symmetric pattern) without, with and without an active bitmap."""
+    n = 6000
+    rng = np.random.default_rng(41)
+    some = rng.choice(n, 400, replace=False)                            # most rows and columns are empty
+    rows, cols = rng.choice(some, 1500), rng.choice(some, 1500)
+    A, rp, ci = up(ctx, n, rows, cols)
+    At = A.transpose()
+    hA, hAt = hypersparse(ctx, A), hypersparse(ctx, At)
+    sr, sc = sym(rows, cols)
+    S = ctx.mat_from_coo(n, n, sr.astype(U64), sc.astype(U64))
+    hS = hypersparse(ctx, S)
+    for act in (None, bitmap(rng.random(n) < 0.7)):
+        want, st = engine.wcc(ctx, A, At, act, stats=True)
+        for A_, At_ in ((hA, hAt), (hA, At), (A, hAt)):
+            got, st_ = engine.wcc(ctx, A_, At_, act, stats=True)
+            assert np.array_equal(got, want) and st_[0] == st[0]           # (entries read depend on the order of the hooks)
+        want2, st2 = engine.wcc(ctx, S, None, act, stats=True)
+        got2, st2_ = engine.wcc(ctx, hS, None, act, stats=True)
+        assert np.array_equal(got2, want2) and st2_[0] == st2[0] and np.array_equal(want2, want)
+    assert np.array_equal(engine.wcc(ctx, hA, hAt)[0], wcc_labels(n, rp, ci))
+
+
+def test_bits_past_n_in_the_active_bitmap_are_not_vertices(ctx):
+    """n is not a multiple of 64: the last word's bits at and past n are ignored (the sample and the link kernels test
+    neighbours' bits, never one past n) — labels and component count are those of the clean bitmap."""
+    n = 5000 - 23
+    rng = np.random.default_rng(8)
+    rows, cols = rng.integers(0, n, 6000), rng.integers(0, n, 6000)
+    A, rp, ci = up(ctx, n, rows, cols)
+    At = A.transpose()
+    active = rng.random(n) < 0.6
+    clean = bitmap(active)
+    dirty = clean.copy()
+    dirty[-1] |= U64(~((1 << (n % 64)) - 1) & 0xFFFFFFFFFFFFFFFF)
+    assert n % 64 and dirty[-1] != clean[-1]
+    want, st = engine.wcc(ctx, A, At, clean, stats=True)
+    got, st_ = engine.wcc(ctx, A, At, dirty, stats=True)
+    assert np.array_equal(got, want) and st_[0] == st[0]                   # (entries read depend on the order of the hooks)
+    assert np.array_equal(got, wcc_labels(n, rp, ci, active))
 
 
 _RMAT22 = {}
