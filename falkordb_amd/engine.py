@@ -530,6 +530,20 @@ def wcc(ctx: Context, A: Mat, At: Mat | None = None, active_bitmap=None, stats: 
     return comp, ([int(x) for x in st] if stats else None)
 
 
+def cdlp(ctx: Context, S: Mat, active_bitmap=None, itermax: int = 10, stats: bool = False, out=None):
+    """fgpu_cdlp: LAGraph_cdlp's labels for algo.labelPropagation over the symmetric pattern S — synchronous label propagation
+    from label[v] = v, the most frequent neighbour label winning, ties to the smallest (-1 for vertices outside
+    active_bitmap).  out: an int64 array to fill instead of a fresh one (a Context.host_array() block is filled by DMA).
+    Returns (label int64[n], stats) — stats the four counters [iterations run, labels changed in the last iteration, entries
+    read, distinct labels] when stats=True, else None."""
+    n = S.nrows
+    lab = out if out is not None else np.zeros(n, dtype=np.int64)
+    act = _u64(active_bitmap) if active_bitmap is not None else None
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_cdlp(ctx._h, S._h, _p(act), C.c_int32(itermax), _p(lab, i64p), _p(st)))
+    return lab, ([int(x) for x in st] if stats else None)
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

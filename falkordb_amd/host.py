@@ -524,6 +524,17 @@ class Graph:
                                C.byref(n)))
         return _take(nodes, n.value), _take(comp, n.value, np.int64)
 
+    def algo_label_propagation(self, labels=(), types=(), max_iterations=10):
+        """CALL algo.labelPropagation({nodeLabels, relationshipTypes, maxIterations}) YIELD node, communityId ->
+        (nodes, community_ids int64).  Several labels select the union of their nodes; with labels the communityId is a compact
+        index (see fh_algo_cdlp)."""
+        nodes = u64p()
+        comm = C.POINTER(C.c_int64)()
+        n = C.c_uint64()
+        _ck(self.L.fh_algo_cdlp(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.c_int64(max_iterations),
+                                C.byref(nodes), C.byref(comm), C.byref(n)))
+        return _take(nodes, n.value), _take(comm, n.value, np.int64)
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

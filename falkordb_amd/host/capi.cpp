@@ -727,6 +727,18 @@ int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** n
     });
 }
 
+// algo.labelPropagation: labels / types = comma lists, "" = all
+int fh_algo_cdlp(fh_graph* g, const char* labels, const char* types, int64_t max_iterations, uint64_t** nodes,
+                 int64_t** community_ids, uint64_t* n) {
+    return guard([&] {
+        CdlpResult r = timed([&] { return algo_cdlp(g->g, csv(labels), csv(types), max_iterations); });
+        *nodes = hand(r.nodes);
+        *community_ids = hand(r.community_ids);
+        *n = r.nodes.size();
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

@@ -929,6 +929,43 @@ WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const
     return res;
 }
 
+// ---- algo.labelPropagation ------------------------------------------------------------------------------
+CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                     int64_t max_iterations) {
+    if (max_iterations <= 0) throw std::invalid_argument("maxIterations must be a positive integer");   // :1184-1193
+    CdlpResult res;
+    const u64 n = g.node_cap();
+    if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:1196-1198)
+    // labels: the union of the labels' live nodes as an induced subgraph — the reference's compact graph (:1215-1222)
+    NodeSelection sel;
+    const bool filtered = !labels.empty();
+    if (filtered) {
+        sel = select_nodes(g, labels);
+        if (sel.count == 0) return res;                                  // :1217-1219
+    }
+    // A (+) A' (:1208); unknown types contribute no edges.  Deleted ids stay in the unfiltered run as isolated vertices
+    // (n = node_count + deleted_nodes_count, :1211-1212).
+    Matrix sym = g.build_symmetric_adjacency_matrix(types);              // graph.rs:3898-3907
+    std::vector<int64_t> comm(n);
+    const int32_t itermax = max_iterations > INT32_MAX ? INT32_MAX : (int32_t)max_iterations;   // (`*n as i32`, :1190)
+    check(fgpu_cdlp(g.ctx().raw(), sym.snapshot(), filtered ? sel.bits.data() : nullptr, itermax, comm.data(), nullptr),
+          "LAGraph_cdlp");
+    // a filtered run's communityId is the label's COMPACT index — its rank among the selected ids in ascending order — which
+    // the reference never maps back to a node id (:1244-1258).  Exact: ranks keep the order of the ids, so every tie-break of
+    // the compact run picks the same vertex
+    std::vector<int64_t> rank;
+    if (filtered) {
+        rank.assign(n, -1);
+        int64_t k = 0;
+        for (u64 v = 0; v < n; ++v)
+            if (sel.has(v)) rank[v] = k++;
+    }
+    // (fgpu_cdlp writes comm[v] = -1 exactly for the unselected v)
+    emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.community_ids,
+              [&](u64 v) { return filtered ? rank[(size_t)comm[v]] : comm[v]; });   // :1249-1258
+    return res;
+}
+
 // ---- algo.betweenness -----------------------------------------------------------------------------------
 std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t sampling_seed) {
     if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // :900-905

@@ -608,6 +608,15 @@ struct WccResult {
 // their nodes (collect_node_ids, :456-477)
 WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types);
 
+struct CdlpResult {
+    std::vector<u64> nodes;
+    std::vector<int64_t> community_ids;   // Column::Ints
+};
+// algo.labelPropagation (runtime/functions/algo_procedures.rs:1168-1270): labels / types empty = all; several labels select
+// the UNION of their nodes; max_iterations <= 0 throws "maxIterations must be a positive integer" (:1184-1193, default 10)
+CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                     int64_t max_iterations);
+
 struct BetweennessResult {
     std::vector<u64> nodes;
     std::vector<double> scores;   // Column::Floats

@@ -1,5 +1,6 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
-// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness procedures bind, on the MI355X engine.
+// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation procedures bind, on
+// the MI355X engine.
 // With them next to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
@@ -10,12 +11,14 @@
 //                  = TRUE -> LAGr_ConnectedComponents (lagraph_bindings.rs:521-526) -> GrB_Vector_extractTuples_INT64
 //   algo.betweenness algo_procedures.rs:925-1017 GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(DIRECTED) -> LAGraph_Cached_AT +
 //                  LAGraph_Cached_OutDegree -> LAGr_Betweenness (lagraph_bindings.rs:539-546) -> GrB_Vector_extractTuples_FP64
+//   algo.labelPropagation algo_procedures.rs:1207-1261 GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(UNDIRECTED),
+//                  is_symmetric_structure = TRUE -> LAGraph_cdlp (lagraphx_bindings.rs:218-223) -> GrB_Vector_extractTuples_INT64
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
-// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness, pinned
-// against the oracle (WCC and betweenness against the checkers of their tests).  The five other LAGraph algorithms
-// algo_procedures.rs calls (harmonic centrality, max-flow, CDLP, MSF and the EMin property) are outside this engine's path
+// lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness /
+// fgpu_cdlp, pinned against the oracle (WCC, betweenness and CDLP against the checkers of their tests).  The four other LAGraph
+// algorithms algo_procedures.rs calls (harmonic centrality, max-flow, MSF and the EMin property) are outside this engine's path
 // (out of scope): they are exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of
 // computing anything.
 //
@@ -308,7 +311,7 @@ int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* s
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation only)")
 int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
 #else
 // ---- LAGraphX -----------------------------------------------------------------------------------------------------------
@@ -342,8 +345,31 @@ int LAGr_BreadthFirstSearch_Extended(GrB_Vector* level, GrB_Vector* parent, LAGr
         return GrB_SUCCESS;
     });
 }
+// LAGraph_cdlp (lagraphx_bindings.rs:218-223) as algo.labelPropagation calls it (algo_procedures.rs:1207-1261): an undirected
+// graph, or one whose G->is_symmetric_structure is cached TRUE; CDLP_handle receives a full GrB_INT64 vector, entry i = the
+// label vertex i holds after at most itermax synchronous iterations from label(i) = i (fgpu_cdlp; include/fgpu.h states the
+// rules — LAGraph numbers its labels from 1, the partition is the same).  LAGraph proper also handles directed graphs;
+// algo.labelPropagation never sends one: a directed graph of unknown symmetry is refused with GrB_NOT_IMPLEMENTED and a
+// message that names the requirement, as LAGr_ConnectedComponents does.
+int LAGraph_cdlp(GrB_Vector* CDLP_handle, LAGraph_Graph G, int itermax, char* msg) {
+    clear_msg(msg);
+    if (!CDLP_handle) return fail(msg, GrB_NULL_POINTER, "CDLP_handle is NULL");
+    *CDLP_handle = nullptr;
+    if (const int r = check_graph(G, msg)) return r;
+    if (!symmetric(G))
+        return fail(msg, GrB_NOT_IMPLEMENTED,
+                    "LAGraph_cdlp: symmetric structure required (an undirected graph, or G->is_symmetric_structure = true)");
+    if (itermax < 0) return fail(msg, GrB_INVALID_VALUE, "itermax is negative");
+    return guarded(msg, [&]() -> int {
+        ResultVector<int64_t> out;
+        out.alloc(fgshim::type_int64(), G->A->m.nrows(), 0, "LAGraph_cdlp");
+        check(fgpu_cdlp(fgshim::context()->raw(), G->A->m.snapshot(), nullptr, itermax, out.data, nullptr), "LAGraph_cdlp");
+        *CDLP_handle = out.release();
+        return GrB_SUCCESS;
+    });
+}
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation only)")
 int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable, LAGraph_Graph, GrB_Vector, char* msg) {
     if (scores) *scores = nullptr;
     if (reachable) *reachable = nullptr;
@@ -355,7 +381,6 @@ int LAGr_MaxFlow(double* f, GrB_Matrix* flow, GrB_Matrix* res, LAGraph_Graph, Gr
     if (res) *res = nullptr;
     FG_NOT_ON_PATH(LAGr_MaxFlow);
 }
-int LAGraph_cdlp(GrB_Vector* out, LAGraph_Graph, int, char* msg) { if (out) *out = nullptr; FG_NOT_ON_PATH(LAGraph_cdlp); }
 int LAGraph_msf(GrB_Matrix* forest, GrB_Vector* comp, GrB_Matrix, bool, char* msg) {
     if (forest) *forest = nullptr;
     if (comp) *comp = nullptr;

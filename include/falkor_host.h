@@ -215,6 +215,15 @@ int fh_algo_pagerank(fh_graph* g, const char* label, const char* rel_type, uint6
 int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, int64_t** component_ids,
                 uint64_t* n);
 
+/* algo.labelPropagation (algo_procedures.rs:1168-1270; LAGraph_cdlp through lagraphx_bindings.rs:218-223 is fgpu_cdlp, whose
+ * comment in fgpu.h states the rules): labels / types = comma lists, "" / NULL = all; several labels select the UNION of their
+ * nodes (an induced subgraph of the undirected view).  max_iterations as the procedure's maxIterations (default 10); <= 0
+ * fails with "maxIterations must be a positive integer".  Rows in ascending node id, deleted nodes dropped.
+ * community_ids[k] = the label nodes[k] ends with, a node id — or, with labels, that node's COMPACT index (its rank among the
+ * selected nodes in ascending id order), as the reference returns it.  Free both with fh_free. */
+int fh_algo_cdlp(fh_graph* g, const char* labels, const char* types, int64_t max_iterations, uint64_t** nodes,
+                 int64_t** community_ids, uint64_t* n);
+
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
  * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).

@@ -415,6 +415,29 @@ fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat*
 fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* active_bitmap,
                    int64_t* component, uint64_t stats[4]);
 
+/* Community detection by label propagation: replaces LAGraph_cdlp(&out, G, itermax, msg) as called by algo.labelPropagation
+ * (algo_procedures.rs:1168-1270; binding lagraphx_bindings.rs:218-223).  Synchronous label propagation as LDBC Graphalytics
+ * defines CDLP and as LAGraph computes it for an undirected graph (LAGraph's source is not vendored; these are the rules):
+ *   - label_0[v] = v;
+ *   - iteration t computes every label_t[v] from label_{t-1} only (two buffers);
+ *   - label_t[v] = the label that occurs most often among the stored entries (v, w) of v's row, each entry voting once with
+ *     label_{t-1}[w]; ties go to the smallest label;
+ *   - a stored diagonal entry votes like any other entry; a vertex with no voting entry keeps its label;
+ *   - the run stops after itermax iterations, or earlier after the first iteration that changes no label.  Running out of
+ *     iterations is not an error: the usual period-2 oscillation on bipartite structure is part of the algorithm.
+ * LAGraph numbers its initial labels from 1 (label_0[v] = v + 1): the partition is identical, because the tie-break order is
+ * the same, and every label here is LAGraph's minus 1.
+ * `S` is the symmetric pattern (A (+) A'); symmetry is the caller's promise, like At == NULL in fgpu_wcc, and there is no
+ * (A, At) form.  The matrix is a boolean pattern: a (row, col) pair given twice to a builder is one entry and one vote.
+ * `active_bitmap` (nullable, nrows bits, as fgpu_pagerank) selects the induced subgraph: entries whose column is inactive do
+ * not vote, and the inactive slots of label[] get -1.  label[nrows] is a HOST array (filled by DMA when pinned —
+ * fgpu_host_alloc — by staging otherwise).  stats (nullable): [0] iterations run, [1] vertices whose label changed in the last
+ * iteration run (0 = converged), [2] adjacency entries read, summed over the iterations, [3] distinct labels among the active
+ * vertices at the end.  Errors: NULL ctx / S / label: FGPU_NULL_POINTER; non-square S: FGPU_DIM_MISMATCH; itermax < 0:
+ * FGPU_INVALID.  itermax == 0 returns the identity labelling; nrows == 0 is a no-op.  The output is deterministic. */
+fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t* active_bitmap, int32_t itermax, int64_t* label,
+                    uint64_t stats[4]);
+
 /* Betweenness centrality (batched Brandes): replaces LAGr_Betweenness(&centrality, G, sources, ns, msg) as called by
  * algo.betweenness (algo_procedures.rs:884-1017; binding lagraph_bindings.rs:539-546).  centrality[v] = the sum over the
  * sources s of delta_s(v) = sum over out-neighbours w of v with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),

@@ -22,7 +22,12 @@
           forward and backward, 2 (4 nnz + 4 (n + 1)) bytes, plus the per-(vertex, source) state written and read,
           2 n B (8 + 8 + 4) bytes, at 8 TB/s)
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|betweenness|all] [scale]
+  cdlp    algo.labelPropagation's core (fgpu_cdlp) on the symmetrised RMAT-22 and RMAT-24 (or RMAT-<scale>), itermax = 10;
+          median of 10 synchronised calls after 2 warm-ups, the stats, ms per iteration, the bytes an iteration must move
+          (4 nnz column ids + 4 nnz gathered labels + 8 n for the two label arrays) as a share of 8 TB/s, and fgpu_pagerank's
+          time per iteration on the same matrix (the same columns read, one 4-byte gather per entry: the nearest yardstick)
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|betweenness|all] [scale]
 """
 import json
 import sys
@@ -250,6 +255,38 @@ def bench_wcc(ctx, scale):
     ctx.set_option("wcc_mode", 0)
 
 
+def bench_cdlp(ctx, scale):
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    rows = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp.astype(np.int64)))
+    S = ctx.mat_from_coo(n, n, np.concatenate([rows, ci]), np.concatenate([ci, rows]))   # A (+) A'
+    del rp, ci, rows, A
+    nnz = S.nvals
+    out = ctx.host_array(n, np.int64)
+    t, (_, st) = timed(ctx, lambda: engine.cdlp(ctx, S, None, 10, stats=True, out=out), reps=10, warm=2)
+    its = max(st[0], 1)
+    # the marginal iteration: a 1-iteration call carries the whole fixed part (row classes, hub scratch, the 8 n-byte copy-out)
+    t1, _ = timed(ctx, lambda: engine.cdlp(ctx, S, None, 1, out=out), reps=10, warm=1)
+    per_iter = (t - t1) / (its - 1) if its > 1 else t
+    # fgpu_pagerank on the same matrix (S is its own transpose), tol 0: fixed iteration counts, the marginal iteration
+    pr = {}
+    for k in (10, 30):
+        pr[k], _ = timed(ctx, lambda: engine.pagerank(ctx, S, S, None, 0.85, 0.0, k), reps=5, warm=1)
+    pr_iter = (pr[30] - pr[10]) / 20
+    b_iter = 4 * nnz + 4 * nnz + 8 * n
+    print(json.dumps({"path": "cdlp", "scale": scale, "n": n, "nnz": nnz, "itermax": 10, "ms": round(t * 1e3, 3),
+                      "iterations": st[0], "changed_last": st[1], "entries_read": st[2], "distinct_labels": st[3],
+                      "ms_one_iteration_call": round(t1 * 1e3, 3), "ms_per_iteration": round(per_iter * 1e3, 3),
+                      "ms_per_iteration_whole_call": round(t / its * 1e3, 3),
+                      "bytes_per_iteration": b_iter, "share_of_8TBps": round(b_iter / 8e12 / per_iter, 4) if per_iter > 0 else None,
+                      "pagerank_ms_per_iteration": round(pr_iter * 1e3, 3),
+                      "ratio_to_pagerank": round(per_iter / pr_iter, 2) if pr_iter > 0 else None,
+                      "note": "host clock around a synchronised call, median of 10 after 2 warm-up; ms_per_iteration = (the "
+                              "10-iteration call - a 1-iteration call) / (iterations - 1); bytes = 4 nnz + 4 nnz + 8 n; pagerank = "
+                              "fgpu_pagerank on the same matrix, (30 iterations - 10 iterations) / 20"}), flush=True)
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -315,6 +352,11 @@ if __name__ == "__main__":
         c = engine.Context(0)
         for sc in ([scale] if scale else [22, 24]):
             bench_wcc(c, sc)
+        c.close()
+    if what in ("cdlp", "all"):
+        c = engine.Context(0)
+        for sc in ([scale] if scale else [22, 24]):
+            bench_cdlp(c, sc)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
