@@ -544,6 +544,23 @@ def cdlp(ctx: Context, S: Mat, active_bitmap=None, itermax: int = 10, stats: boo
     return lab, ([int(x) for x in st] if stats else None)
 
 
+def harmonic(ctx: Context, A: Mat, active_bitmap=None, stats: bool = False, registers: bool = False, out=None):
+    """fgpu_harmonic: LAGr_HarmonicCentrality's HyperBall scores for algo.HarmonicCentrality over the directed pattern A — a
+    1024-register HyperLogLog sketch of every vertex' out-ball, merged along the out-entries until no sketch changes (0.0 / -1
+    for vertices outside active_bitmap).  out: a (score float64[n], reachable int64[n]) pair to fill instead of fresh arrays
+    (Context.host_array() blocks are filled by DMA).  Returns (score, reachable, registers, stats) — registers the final
+    uint8[n, 1024] sketches when registers=True, stats the four counters [iterations that changed a sketch, sketch changes,
+    largest reachable, vertices with a non-zero score] when stats=True, else None."""
+    n = A.nrows
+    score, reach = out if out is not None else (np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64))
+    act = _u64(active_bitmap) if active_bitmap is not None else None
+    regs = np.zeros((n, 1024), dtype=np.uint8) if registers else None
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_harmonic(ctx._h, A._h, _p(act), _p(score, C.POINTER(C.c_double)), _p(reach, i64p),
+                                _p(regs, C.POINTER(C.c_uint8)), _p(st)))
+    return score, reach, regs, ([int(x) for x in st] if stats else None)
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

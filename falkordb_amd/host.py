@@ -535,6 +535,18 @@ class Graph:
                                 C.byref(nodes), C.byref(comm), C.byref(n)))
         return _take(nodes, n.value), _take(comm, n.value, np.int64)
 
+    def algo_harmonic_centrality(self, labels=(), types=()):
+        """CALL algo.HarmonicCentrality({nodeLabels, relationshipTypes}) YIELD node, score, reachable ->
+        (nodes, scores float64, reachable int64).  Several labels select the union of their nodes; an unknown relationship type
+        is an error (see fh_algo_harmonic_centrality)."""
+        nodes = u64p()
+        scores = C.POINTER(C.c_double)()
+        reach = C.POINTER(C.c_int64)()
+        n = C.c_uint64()
+        _ck(self.L.fh_algo_harmonic_centrality(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.byref(nodes),
+                                               C.byref(scores), C.byref(reach), C.byref(n)))
+        return _take(nodes, n.value), _take(scores, n.value, np.float64), _take(reach, n.value, np.int64)
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

@@ -739,6 +739,19 @@ int fh_algo_cdlp(fh_graph* g, const char* labels, const char* types, int64_t max
     });
 }
 
+// algo.HarmonicCentrality: labels / types = comma lists, "" = all
+int fh_algo_harmonic_centrality(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, double** scores,
+                                int64_t** reachable, uint64_t* n) {
+    return guard([&] {
+        HarmonicResult r = timed([&] { return algo_harmonic_centrality(g->g, csv(labels), csv(types)); });
+        *nodes = hand(r.nodes);
+        *scores = hand(r.scores);
+        *reachable = hand(r.reachable);
+        *n = r.nodes.size();
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

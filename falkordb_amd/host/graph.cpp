@@ -966,6 +966,40 @@ CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, con
     return res;
 }
 
+// ---- algo.HarmonicCentrality ----------------------------------------------------------------------------
+HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::string>& labels,
+                                        const std::vector<std::string>& types) {
+    for (auto& t : types)                                                // before the empty-graph exit (:2648-2652)
+        if (!g.type_id(t)) throw std::invalid_argument("Relationship type '" + t + "' does not exist");
+    HarmonicResult res;
+    const u64 n = g.node_cap();
+    if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:2654-2656)
+    // labels: the union of the labels' live nodes as an induced subgraph — the reference's compact graph (:2658-2666,
+    // :2704-2708); the sketches hash the node ids, not the compact indices
+    NodeSelection sel;
+    const bool filtered = !labels.empty();
+    if (filtered) {
+        sel = select_nodes(g, labels);
+        if (sel.count == 0) return res;                                  // :2664-2666
+    }
+    // the directed adjacency over the selected types (:2676).  Deleted ids stay in the unfiltered run as isolated vertices
+    // (n = node_count + deleted_nodes_count, :2701-2702) and leave the rows (:2760-2762).
+    Matrix adj = g.build_adjacency_matrix(types);                        // graph.rs:3870-3894
+    std::vector<double> score(n);
+    std::vector<int64_t> reach(n);
+    check(fgpu_harmonic(g.ctx().raw(), adj.snapshot(), filtered ? sel.bits.data() : nullptr, score.data(), reach.data(), nullptr,
+                        nullptr),
+          "LAGr_HarmonicCentrality");
+    for (u64 v = 0; v < n; ++v) {                                        // :2755-2767
+        if (g.is_node_deleted(v)) continue;
+        if (filtered && !sel.has(v)) continue;
+        res.nodes.push_back(v);
+        res.scores.push_back(score[v]);
+        res.reachable.push_back(reach[v]);
+    }
+    return res;
+}
+
 // ---- algo.betweenness -----------------------------------------------------------------------------------
 std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t sampling_seed) {
     if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // :900-905

@@ -617,6 +617,16 @@ struct CdlpResult {
 CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
                      int64_t max_iterations);
 
+struct HarmonicResult {
+    std::vector<u64> nodes;
+    std::vector<double> scores;       // Column::Floats
+    std::vector<int64_t> reachable;   // Column::Ints
+};
+// algo.HarmonicCentrality (runtime/functions/algo_procedures.rs:2623-2784): labels / types empty = all; several labels select
+// the UNION of their nodes; an unknown relationship type throws "Relationship type '<t>' does not exist" (:2648-2652)
+HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::string>& labels,
+                                        const std::vector<std::string>& types);
+
 struct BetweennessResult {
     std::vector<u64> nodes;
     std::vector<double> scores;   // Column::Floats

@@ -6,6 +6,8 @@
 // the host layer's Matrix (host.hpp), i.e. on fgpu_* calls.  With it the UNMODIFIED Rust wrapper (matrix.rs) can link
 // against this engine: every call form matrix.rs issues on the traversal path is accepted; any other form returns
 // GrB_NOT_IMPLEMENTED instead of computing something else.  GrB_Info codes are the reference's (mod.rs:274-296).
+// On top of that list: what the algo.* procedures call around LAGraph (algo_procedures.rs) — the vector read-backs, and for
+// algo.HarmonicCentrality GrB_ONEB_BOOL, GrB_ALL, GrB_Matrix_eWiseMult_BinaryOp (:11250) and GrB_Vector_assign_BOOL (:12005).
 //
 // Semantics kept from GraphBLAS where the wrapper depends on them: non-blocking mode (writes queue as pending tuples until
 // GrB_Matrix_wait / a reading call), in-place output with C aliasing an input (matrix.rs:935-943), GrB_NO_VALUE from
@@ -113,7 +115,8 @@ void take_vector(falkor::ByteReader& r, GB_Vector_opaque* v) {
 }
 constexpr char BLOB_IDS[8] = {'F', 'G', 'I', 'D', 'L', 'S', 'T', '1'};   // = serialize.cpp PLAIN_MAGIC: BOOL vector, the set indices
 constexpr char BLOB_U64[8] = {'F', 'G', 'V', 'E', 'C', 'U', '6', '4'};   // UINT64 vector: length, count, (index, value) pairs
-GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2};
+GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2}, op_oneb_bool{3};
+const GrB_Index all_indices = 0;   // what GrB_ALL points at: only its address is looked at
 GB_UnaryOp_opaque op_one_bool{0};
 GB_Semiring_opaque sr_any_pair_bool{0};
 GB_Global_opaque global_obj{0};
@@ -212,6 +215,8 @@ GrB_Type GrB_UINT64 = &t_u64;
 GrB_BinaryOp GxB_ANY_BOOL = &op_any_bool;
 GrB_BinaryOp GrB_SECOND_UINT64 = &op_second_u64;
 GrB_BinaryOp GxB_ANY_UINT64 = &op_any_u64;
+GrB_BinaryOp GrB_ONEB_BOOL = &op_oneb_bool;          // algo.HarmonicCentrality's iso rebuild (algo_procedures.rs:2689-2700)
+const GrB_Index* GrB_ALL = &all_indices;             // mod.rs:3036
 GrB_UnaryOp GxB_ONE_BOOL = &op_one_bool;
 GrB_Semiring GxB_ANY_PAIR_BOOL = &sr_any_pair_bool;
 GrB_Global GrB_GLOBAL = &global_obj;
@@ -462,6 +467,22 @@ GrB_Info GrB_Matrix_eWiseMult_Semiring(GrB_Matrix C, GrB_Matrix Mask, GrB_Binary
     });
 }
 
+// C = pattern(A) & pattern(B), every value true: GrB_ONEB_BOOL over BOOL matrices, no mask, no accum — the form
+// algo.HarmonicCentrality issues with A == B to hand LAGraph an iso adjacency (algo_procedures.rs:2689-2700; mod.rs:11250-11258)
+GrB_Info GrB_Matrix_eWiseMult_BinaryOp(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_BinaryOp mult, GrB_Matrix A,
+                                       GrB_Matrix B, GrB_Descriptor desc) {
+    if (!C || !A || !B || !mult) return GrB_NULL_POINTER;
+    if (Mask || accum || mult != GrB_ONEB_BOOL || (desc && !desc_is(desc, false, false, false, false, false))) return GrB_NOT_IMPLEMENTED;
+    if (C->m.type() != Type::Bool || A->m.type() != Type::Bool || B->m.type() != Type::Bool) return GrB_NOT_IMPLEMENTED;
+    if (A->m.nrows() != B->m.nrows() || A->m.ncols() != B->m.ncols() || C->m.nrows() != A->m.nrows() || C->m.ncols() != A->m.ncols())
+        return GrB_DIMENSION_MISMATCH;
+    return guarded([&]() -> GrB_Info {
+        if (same(A, B)) { if (!same(A, C)) C->m = A->m.dup(); }          // the pattern itself (shares A's device snapshot)
+        else C->m.element_wise_multiply(same(A, C) ? nullptr : &A->m, same(B, C) ? nullptr : &B->m);
+        return GrB_SUCCESS;
+    });
+}
+
 // C<Mask> U= pattern(A) as all-true entries (GrB_Matrix_apply with accum GxB_ANY_BOOL and GxB_ONE_BOOL, matrix.rs:906-924)
 GrB_Info GrB_Matrix_apply(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_UnaryOp op, GrB_Matrix A, GrB_Descriptor desc) {
     if (!C || !A || !op) return GrB_NULL_POINTER;
@@ -631,6 +652,18 @@ static GrB_Info vec_set(GrB_Vector v, uint64_t x, GrB_Index i) {
 }
 GrB_Info GrB_Vector_setElement_BOOL(GrB_Vector v, bool x, GrB_Index i) { return vec_set(v, x ? 1 : 0, i); }
 GrB_Info GrB_Vector_setElement_UINT64(GrB_Vector v, uint64_t x, GrB_Index i) { return vec_set(v, x, i); }
+// w(:) = x — the GrB_ALL, no-mask, no-accum form (mod.rs:12005-12013; algo_procedures.rs:2729-2737 fills node_weights with
+// it): the vector becomes full and iso, one stored byte standing for every entry
+GrB_Info GrB_Vector_assign_BOOL(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, bool x, const GrB_Index* I, GrB_Index, GrB_Descriptor desc) {
+    if (!w) return GrB_NULL_POINTER;
+    if (mask || accum || I != GrB_ALL || w->type != GrB_BOOL || (desc && !desc_is(desc, false, false, false, false, false)))
+        return GrB_NOT_IMPLEMENTED;
+    return guarded([&]() -> GrB_Info {
+        const uint8_t byte = x ? 1 : 0;
+        vec_set_array(w, w->type, &byte, 1, w->n);
+        return GrB_SUCCESS;
+    });
+}
 GrB_Info GrB_Vector_removeElement(GrB_Vector v, GrB_Index i) {
     if (!v) return GrB_NULL_POINTER;
     if (v->data) return GrB_NOT_IMPLEMENTED;

@@ -1,6 +1,6 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
-// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation procedures bind, on
-// the MI355X engine.
+// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality
+// procedures bind, on the MI355X engine.
 // With them next to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
@@ -13,12 +13,16 @@
 //                  LAGraph_Cached_OutDegree -> LAGr_Betweenness (lagraph_bindings.rs:539-546) -> GrB_Vector_extractTuples_FP64
 //   algo.labelPropagation algo_procedures.rs:1207-1261 GrB_Matrix_dup + GrB_Matrix_resize -> LAGraph_New(UNDIRECTED),
 //                  is_symmetric_structure = TRUE -> LAGraph_cdlp (lagraphx_bindings.rs:218-223) -> GrB_Vector_extractTuples_INT64
+//   algo.HarmonicCentrality algo_procedures.rs:2676-2774 GrB_Matrix_new + GrB_Matrix_eWiseMult_BinaryOp(GrB_ONEB_BOOL, adj, adj) +
+//                  GrB_Matrix_resize -> LAGraph_New(DIRECTED) -> GrB_Vector_new + GrB_Vector_assign_BOOL(true, GrB_ALL) ->
+//                  LAGr_HarmonicCentrality (lagraphx_bindings.rs:486-492) -> GrB_Vector_extractTuples_FP64 / _INT64
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
 // lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness /
-// fgpu_cdlp, pinned against the oracle (WCC, betweenness and CDLP against the checkers of their tests).  The four other LAGraph
-// algorithms algo_procedures.rs calls (harmonic centrality, max-flow, MSF and the EMin property) are outside this engine's path
+// fgpu_cdlp / fgpu_harmonic, pinned against the oracle (WCC, betweenness, CDLP and harmonic centrality against the checkers of
+// their tests).  The three other LAGraph algorithms algo_procedures.rs calls (max-flow, MSF and the EMin property) are outside
+// this engine's path
 // (out of scope): they are exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of
 // computing anything.
 //
@@ -311,7 +315,7 @@ int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* s
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality only)")
 int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
 #else
 // ---- LAGraphX -----------------------------------------------------------------------------------------------------------
@@ -368,13 +372,49 @@ int LAGraph_cdlp(GrB_Vector* CDLP_handle, LAGraph_Graph G, int itermax, char* ms
         return GrB_SUCCESS;
     });
 }
-// ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation only)")
-int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable, LAGraph_Graph, GrB_Vector, char* msg) {
-    if (scores) *scores = nullptr;
-    if (reachable) *reachable = nullptr;
-    FG_NOT_ON_PATH(LAGr_HarmonicCentrality);
+// LAGr_HarmonicCentrality (lagraphx_bindings.rs:486-492) as algo.HarmonicCentrality calls it (algo_procedures.rs:2676-2774):
+// reads only G->A, of any kind; scores receives a full GrB_FP64 vector and reachable_nodes (nullable) a full GrB_INT64 vector of
+// G->A's dimension (fgpu_harmonic; include/fgpu.h states the rules, reachable does not count the vertex itself).  node_weights
+// is NULL, or what the procedure sends: a full BOOL vector of true with one entry per vertex; weights of any other form are
+// refused with GrB_NOT_IMPLEMENTED and a message.
+static bool all_true(GrB_Vector w, uint64_t n) {
+    if (!w->type || w->type->code != 0 || w->n != n) return false;
+    if (w->data) {
+        if (w->absent) return false;
+        const uint8_t* b = (const uint8_t*)w->data;
+        for (uint64_t i = 0; i < w->nstored; ++i)   // (1 byte for an iso array, n otherwise)
+            if (!b[i]) return false;
+        return w->nstored == 1 || w->nstored == n;
+    }
+    if (w->s.size() != n) return false;
+    for (auto& kv : w->s)
+        if (!kv.second) return false;
+    return true;
 }
+int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable_nodes, LAGraph_Graph G, GrB_Vector node_weights, char* msg) {
+    clear_msg(msg);
+    if (reachable_nodes) *reachable_nodes = nullptr;
+    if (!scores) return fail(msg, GrB_NULL_POINTER, "scores is NULL");
+    *scores = nullptr;
+    if (const int r = check_graph(G, msg)) return r;
+    const uint64_t n = G->A->m.nrows();
+    if (node_weights && !all_true(node_weights, n))
+        return fail(msg, GrB_NOT_IMPLEMENTED,
+                    "LAGr_HarmonicCentrality: node_weights must be NULL or a full BOOL vector of true, one entry per vertex");
+    return guarded(msg, [&]() -> int {
+        ResultVector<double> sc;
+        ResultVector<int64_t> re;
+        sc.alloc(fgshim::type_fp64(), n, 0, "LAGr_HarmonicCentrality");
+        re.alloc(fgshim::type_int64(), n, 0, "LAGr_HarmonicCentrality");
+        check(fgpu_harmonic(fgshim::context()->raw(), G->A->m.snapshot(), nullptr, sc.data, re.data, nullptr, nullptr),
+              "LAGr_HarmonicCentrality");
+        *scores = sc.release();
+        if (reachable_nodes) *reachable_nodes = re.release();
+        return GrB_SUCCESS;
+    });
+}
+// ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality only)")
 int LAGr_MaxFlow(double* f, GrB_Matrix* flow, GrB_Matrix* res, LAGraph_Graph, GrB_Index, GrB_Index, char* msg) {
     if (f) *f = 0;
     if (flow) *flow = nullptr;

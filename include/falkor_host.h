@@ -224,6 +224,15 @@ int fh_algo_wcc(fh_graph* g, const char* labels, const char* types, uint64_t** n
 int fh_algo_cdlp(fh_graph* g, const char* labels, const char* types, int64_t max_iterations, uint64_t** nodes,
                  int64_t** community_ids, uint64_t* n);
 
+/* algo.HarmonicCentrality (algo_procedures.rs:2623-2784; LAGr_HarmonicCentrality is fgpu_harmonic, whose comment in fgpu.h
+ * states the rules): labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced
+ * subgraph of the directed adjacency; the sketches hash the node ids).  An unknown relationship type fails with "Relationship
+ * type '<t>' does not exist"; an empty graph or an empty selection gives no rows.  Rows in ascending node id, deleted nodes
+ * dropped.  scores[k] = the HyperBall estimate of the sum over the nodes w that nodes[k] reaches of 1 / d(nodes[k], w);
+ * reachable[k] = the estimated number of such w, nodes[k] itself not counted.  Free the three with fh_free. */
+int fh_algo_harmonic_centrality(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, double** scores,
+                                int64_t** reachable, uint64_t* n);
+
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
  * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).

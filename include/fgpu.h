@@ -438,6 +438,40 @@ fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const u
 fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t* active_bitmap, int32_t itermax, int64_t* label,
                     uint64_t stats[4]);
 
+/* Harmonic centrality by HyperBall: replaces LAGr_HarmonicCentrality(&scores, &reachable, G, node_weights, msg) as called by
+ * algo.HarmonicCentrality (algo_procedures.rs:2623-2784) with an iso boolean directed adjacency.  Every vertex carries a
+ * HyperLogLog sketch of its out-ball; an iteration is a pull over the semiring (merge = bytewise max, second).  The sketch
+ * operators are those of the reference's PreJIT kernels; LAGraph's driver and its hash are not vendored, these are the rules:
+ *   - sketch: m = 1024 registers of uint8 (1 KiB per vertex); the monoid identity is all zeros, merge is the bytewise max;
+ *   - hash: a vertex v is its row index in A (ids fit u32).  h = (u32)v; h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13;
+ *     h *= 0xc2b2ae35; h ^= h >> 16 (mod 2^32: the murmur3 32-bit finaliser, a bijection).  slot = h >> 22; w = h & 0x3FFFFF;
+ *     rank = 1 + the number of leading zeros of w written in 22 bits (1..22), 23 when w == 0.  Vertex 0: slot 0, rank 23;
+ *   - count(C): S = sum 2^-C[i] (exact in FP64 in any order: dyadic terms >= 2^-23, sum <= 1024); E = amm / S with
+ *     amm = 0.7213 / (1 + 1.079 / 1024) * 1024^2; if E <= 2560 and Z, the number of zero registers, is > 0:
+ *     E = 1024 log(1024 / Z); else if E > 2^32 / 30: E = -2^32 log(1 - E / 2^32).  All FP64;
+ *   - C_0[v] is zero except v's own (slot, rank); est_0[v] = count(C_0[v]); score[v] = 0;
+ *   - iteration t = 1, 2, ...: C_t[v] = the bytewise max of C_{t-1}[v] and of C_{t-1}[w] over the stored entries (v, w) of
+ *     row v, from C_{t-1} only (two buffers).  A boolean pattern: a duplicate entry is one entry, a diagonal entry is harmless.
+ *     If C_t[v] differs bytewise from C_{t-1}[v]: score[v] += (count(C_t[v]) - est_{t-1}[v]) / t and est_t[v] = the new count;
+ *     otherwise nothing changes for v, exactly;
+ *   - the run ends after the first iteration that changes no sketch (it contributes nothing).  Registers only grow: at most
+ *     diameter + 1 iterations, and no itermax, as in the LAGraph signature.
+ * score[v] is FP64.  reachable[v] = llround(est_final[v]) - 1, the vertices v reaches NOT counting v itself — this engine's
+ * decision (the reference's tests only order it).  A vertex with no out-entry has score exactly 0.0 and reachable 0.
+ * `active_bitmap` (nullable, nrows bits, as fgpu_pagerank) selects the induced subgraph: inactive columns contribute nothing,
+ * inactive slots get score 0.0, reachable -1 and a zero sketch; the hashes stay those of the original row indices.
+ * Every merge order gives the same bytes, so the output is deterministic; an implementation may skip entries whose column
+ * did not change in the previous iteration (HyperBall's "modified" rule) — the result is bit-identical.
+ * score[nrows] and reachable[nrows] are HOST arrays (filled by DMA when pinned — fgpu_host_alloc — by staging otherwise);
+ * registers (nullable) receives the final nrows x 1024 sketch bytes.  stats (nullable): [0] iterations that changed at least
+ * one sketch, [1] sketch changes summed over the iterations, [2] the largest reachable, [3] vertices with a non-zero score.
+ * Workspace: 2 nrows KiB plus a few vectors; an allocation that does not fit returns FGPU_OOM, nothing is truncated.
+ * Errors: NULL ctx / A / score / reachable: FGPU_NULL_POINTER; non-square A: FGPU_DIM_MISMATCH; nrows >= 2^32 - 1:
+ * FGPU_INVALID.  nrows == 0 is a no-op.  fgpu_get_option "harmonic_last_entries" / "harmonic_last_gathered": the entries of
+ * the rows the last call recomputed and the sketches it gathered, summed over its iterations. */
+fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint64_t* active_bitmap, double* score, int64_t* reachable,
+                        uint8_t* registers, uint64_t stats[4]);
+
 /* Betweenness centrality (batched Brandes): replaces LAGr_Betweenness(&centrality, G, sources, ns, msg) as called by
  * algo.betweenness (algo_procedures.rs:884-1017; binding lagraph_bindings.rs:539-546).  centrality[v] = the sum over the
  * sources s of delta_s(v) = sum over out-neighbours w of v with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),

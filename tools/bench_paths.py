@@ -27,7 +27,14 @@
           (4 nnz column ids + 4 nnz gathered labels + 8 n for the two label arrays) as a share of 8 TB/s, and fgpu_pagerank's
           time per iteration on the same matrix (the same columns read, one 4-byte gather per entry: the nearest yardstick)
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|betweenness|all] [scale]
+  harmonic  algo.HarmonicCentrality's core (fgpu_harmonic, HyperBall over 1 KiB sketches) on the RMAT-22 adjacency (or
+          RMAT-<scale>): median of 5 synchronised calls after 1 warm-up, the stats, the iterations, ms per iteration (the call
+          less the fixed part — the same call on an empty matrix of that size: clearing 2 n KiB, the init pass, the copy-out —
+          over the iterations), and the gathered bytes per second: entries of the recomputed rows x 1 KiB, and the sketches
+          the kernels actually loaded x 1 KiB (entries whose column did not change are not loaded), against the 5.5 TB/s
+          measured for register gathers of random 1152-byte rows
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|all] [scale]
 """
 import json
 import sys
@@ -287,6 +294,29 @@ def bench_cdlp(ctx, scale):
                               "fgpu_pagerank on the same matrix, (30 iterations - 10 iterations) / 20"}), flush=True)
 
 
+def bench_harmonic(ctx, scale):
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    n, nnz = A.nrows, A.nvals
+    out = (ctx.host_array(n, np.float64), ctx.host_array(n, np.int64))
+    t, (_, _, _, st) = timed(ctx, lambda: engine.harmonic(ctx, A, stats=True, out=out), reps=5, warm=1)
+    entries, gathered = ctx.get_option("harmonic_last_entries"), ctx.get_option("harmonic_last_gathered")
+    E = ctx.mat_new(n, n)
+    t0, _ = timed(ctx, lambda: engine.harmonic(ctx, E, out=out), reps=5, warm=1)
+    its = st[0] + 1                                           # the iteration that changed nothing ran as well
+    work = max(t - t0, 1e-9)
+    print(json.dumps({"path": "harmonic", "scale": scale, "n": n, "nnz": nnz, "ms": round(t * 1e3, 3),
+                      "ms_fixed_part": round(t0 * 1e3, 3), "iterations_changing": st[0], "iterations_run": its,
+                      "sketch_changes": st[1], "largest_reachable": st[2], "nonzero_scores": st[3],
+                      "ms_per_iteration": round(work / its * 1e3, 3), "ms_per_iteration_whole_call": round(t / its * 1e3, 3),
+                      "entries_of_recomputed_rows": entries, "sketches_gathered": gathered,
+                      "TBps_entries_of_recomputed_rows": round(entries * 1024 / work / 1e12, 3),
+                      "TBps_sketches_gathered": round(gathered * 1024 / work / 1e12, 3),
+                      "share_of_5.5TBps_entries": round(entries * 1024 / work / 5.5e12, 3),
+                      "share_of_5.5TBps_gathered": round(gathered * 1024 / work / 5.5e12, 3),
+                      "note": "host clock around a synchronised call, median of 5 after 1 warm-up; fixed part = the same call on an "
+                              "empty n x n matrix; per-iteration and TB/s figures use the call less the fixed part"}), flush=True)
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -357,6 +387,10 @@ if __name__ == "__main__":
         c = engine.Context(0)
         for sc in ([scale] if scale else [22, 24]):
             bench_cdlp(c, sc)
+        c.close()
+    if what in ("harmonic", "all"):
+        c = engine.Context(0)
+        bench_harmonic(c, scale if scale else 22)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
