@@ -1,4 +1,4 @@
-// algo.hpp — the prelude the whole-graph procedures share (pagerank.hip, wcc.hip, betweenness.hip and the one-shot fgpu_bfs):
+// algo.hpp — the prelude the whole-graph procedures share (pagerank.hip, wcc.hip, betweenness.hip, msf.hip and the one-shot fgpu_bfs):
 // each rule below is decided here once.  Header only; what an algorithm does about a MISSING transpose stays at its call site.
 #pragma once
 #include "common.hpp"
@@ -38,15 +38,16 @@ struct DenseInputs {
         if (dAt) mat_release(dAt);
     }
     bool densified() const { return dA || dAt; }   // (a temporary stands in for an input: it has no cached indexes or plans)
-    fgpu_info a(fgpu_ctx* ctx, const fgpu_mat*& A) { return dense(ctx, A, dA); }
+    // keep_vals: the dense form carries A's UINT64 values (fgpu_msf reads them); the pattern-only algorithms drop them
+    fgpu_info a(fgpu_ctx* ctx, const fgpu_mat*& A, bool keep_vals = false) { return dense(ctx, A, dA, keep_vals); }
     fgpu_info at(fgpu_ctx* ctx, const fgpu_mat*& At) { return dense(ctx, At, dAt); }   // NULL stays NULL
 
    private:
-    static fgpu_info dense(fgpu_ctx* ctx, const fgpu_mat*& m, fgpu_mat*& own) {
+    static fgpu_info dense(fgpu_ctx* ctx, const fgpu_mat*& m, fgpu_mat*& own, bool keep_vals = false) {
         if (!m || !m->is_hyper()) return FGPU_OK;
         fgpu_mat* prev = own;   // m itself when the caller built it into this slot: replaced by its dense form
         own = nullptr;
-        const fgpu_info i = mat_merge_entries(ctx, &own, m, nullptr, nullptr, false, m->nrows, m->ncols, true);
+        const fgpu_info i = mat_merge_entries(ctx, &own, m, nullptr, nullptr, false, m->nrows, m->ncols, !(keep_vals && m->vals));
         if (prev) mat_release(prev);
         FGPU_TRY(i);
         m = own;

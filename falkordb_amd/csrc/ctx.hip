@@ -817,6 +817,8 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "expand_xp_direct")) *value = ctx->opt.expand_xp_direct;
     else if (!strcmp(name, "expand_xp_last_direct")) *value = (int64_t)ctx->xp_last_direct.load(std::memory_order_relaxed);
     else if (!strcmp(name, "harmonic_last_entries")) *value = (int64_t)ctx->hc_last_entries.load(std::memory_order_relaxed);
+    else if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32)
+        *value = (int64_t)ctx->msf_round_entries[atoi(name + 22)].load(std::memory_order_relaxed);
     else if (!strcmp(name, "harmonic_last_gathered")) *value = (int64_t)ctx->hc_last_gathered.load(std::memory_order_relaxed);
     else { set_error("fgpu_get_option: unknown name '%s'", name); return FGPU_INVALID; }
     return FGPU_OK;

@@ -561,6 +561,26 @@ def harmonic(ctx: Context, A: Mat, active_bitmap=None, stats: bool = False, regi
     return score, reach, regs, ([int(x) for x in st] if stats else None)
 
 
+def msf(ctx: Context, W: Mat, active_bitmap=None, stats: bool = False, out=None):
+    """fgpu_msf: LAGraph_msf's forest for algo.MSF over the symmetric weighted matrix W — a valued snapshot carries one binary64
+    bit pattern per entry, a BOOL one means every weight is 1.0; ties go to the smaller (min, max) pair, so the forest is
+    unique.  out: an int64 array to fill with the components instead of a fresh one (a Context.host_array() block is filled by
+    DMA).  Returns (component int64[n], rows uint64[k], cols uint64[k], weights float64[k], stats) — component labelled as by
+    wcc (-1 outside active_bitmap), the forest once per edge as row < col sorted by (row, col), stats the four counters
+    [rounds, forest edges, entries read, components] when stats=True, else None."""
+    n = W.nrows
+    comp = out if out is not None else np.zeros(n, dtype=np.int64)
+    act = _u64(active_bitmap) if active_bitmap is not None else None
+    r, c, w = u64p(), u64p(), C.POINTER(C.c_double)()
+    k = C.c_uint64()
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_msf(ctx._h, W._h, _p(act), _p(comp, i64p), C.byref(r), C.byref(c), C.byref(w), C.byref(k), _p(st)))
+    rows = ctx._take(r, k.value)
+    cols = ctx._take(c, k.value)
+    weights = ctx._take(w, k.value, dtype=np.float64)
+    return comp, rows, cols, weights, ([int(x) for x in st] if stats else None)
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

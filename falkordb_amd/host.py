@@ -547,6 +547,27 @@ class Graph:
                                                C.byref(scores), C.byref(reach), C.byref(n)))
         return _take(nodes, n.value), _take(scores, n.value, np.float64), _take(reach, n.value, np.int64)
 
+    def algo_msf(self, labels=(), types=(), maximize=False, weights=None):
+        """CALL algo.MSF({nodeLabels, relationshipTypes, weightAttribute, objective}) YIELD nodes, edges -> a list of
+        (nodes uint64[], edges uint64[]) per tree, in ascending order of the trees' smallest node id.  weights: None = no
+        weightAttribute, else a {relationship id: number} dict — a relationship that is missing from it has no attribute (see
+        fh_algo_msf).  An unknown relationship type is an error."""
+        ids = wts = None
+        if weights is not None:
+            ids = np.ascontiguousarray(list(weights.keys()), dtype=np.uint64)
+            wts = np.ascontiguousarray([float(x) for x in weights.values()], dtype=np.float64)
+        nt = C.c_uint64()
+        noff, nodes, eoff, edges = u64p(), u64p(), u64p(), u64p()
+        _ck(self.L.fh_algo_msf(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.c_int(1 if maximize else 0),
+                               ids.ctypes.data_as(u64p) if ids is not None else None,
+                               wts.ctypes.data_as(C.POINTER(C.c_double)) if wts is not None else None,
+                               C.c_uint64(len(ids) if ids is not None else 0), C.byref(nt), C.byref(noff), C.byref(nodes),
+                               C.byref(eoff), C.byref(edges)))
+        t = nt.value
+        no, eo = _take(noff, t + 1), _take(eoff, t + 1)
+        nv, ev = _take(nodes, int(no[-1])), _take(edges, int(eo[-1]))
+        return [(nv[int(no[i]):int(no[i + 1])], ev[int(eo[i]):int(eo[i + 1])]) for i in range(t)]
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

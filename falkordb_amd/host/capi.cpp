@@ -752,6 +752,28 @@ int fh_algo_harmonic_centrality(fh_graph* g, const char* labels, const char* typ
     });
 }
 
+// algo.MSF: labels / types = comma lists, "" = all; the trees as two CSR-like lists
+int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize, const uint64_t* edge_ids, const double* weights,
+                uint64_t n_weights, uint64_t* n_trees, uint64_t** node_off, uint64_t** nodes, uint64_t** edge_off,
+                uint64_t** edges) {
+    return guard([&] {
+        MsfResult r = timed([&] { return algo_msf(g->g, csv(labels), csv(types), maximize != 0, edge_ids, weights, n_weights); });
+        std::vector<u64> no(1, 0), nv, eo(1, 0), ev;
+        for (size_t t = 0; t < r.tree_nodes.size(); ++t) {
+            nv.insert(nv.end(), r.tree_nodes[t].begin(), r.tree_nodes[t].end());
+            ev.insert(ev.end(), r.tree_edges[t].begin(), r.tree_edges[t].end());
+            no.push_back(nv.size());
+            eo.push_back(ev.size());
+        }
+        *n_trees = r.tree_nodes.size();
+        *node_off = hand(no);
+        *nodes = hand(nv);
+        *edge_off = hand(eo);
+        *edges = hand(ev);
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

@@ -1,6 +1,9 @@
 // graph.cpp — the traversal-facing slice of graph.rs plus the operators that sit on it:
 // CondTraverseOp::expand_batch / expand_row, ExpandIntoOp, algo.BFS.
 #include <algorithm>
+#include <cstring>
+#include <limits>
+#include <unordered_map>
 
 #include "host.hpp"
 
@@ -997,6 +1000,94 @@ HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::s
         res.scores.push_back(score[v]);
         res.reachable.push_back(reach[v]);
     }
+    return res;
+}
+
+// ---- algo.MSF -------------------------------------------------------------------------------------------
+MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types, bool maximize,
+                   const u64* edge_ids, const double* weights, u64 n_weights) {
+    std::vector<u64> tids;
+    for (auto& t : types) {                                              // before the empty-graph exit (:1287-1295)
+        const auto tid = g.type_id(t);
+        if (!tid) throw std::invalid_argument("Relationship type '" + t + "' does not exist");
+        tids.push_back(*tid);
+    }
+    MsfResult res;
+    const u64 n = g.node_cap();
+    if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:1323-1325)
+    // the nodes of the run: the labels' live nodes, or every live node (collect_node_ids, :1328-1331).  The reference
+    // renumbers them 0..k-1; here they are an induced subgraph, and the order of the ids — all the forest depends on — is kept
+    NodeSelection sel;
+    if (!labels.empty()) {
+        sel = select_nodes(g, labels);
+    } else {
+        sel.bits.assign((n + 63) / 64, 0);
+        for (u64 v = 0; v < n; ++v)
+            if (!g.is_node_deleted(v)) { sel.bits[v >> 6] |= 1ull << (v & 63); ++sel.count; }
+    }
+    if (sel.count == 0) return res;
+    if (types.empty())
+        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+    // the score of a relationship (msf_score, :143-165)
+    const bool unit = edge_ids == nullptr;
+    std::unordered_map<u64, double> attr;
+    if (!unit) {
+        attr.reserve(n_weights * 2);
+        for (u64 k = 0; k < n_weights; ++k) attr[edge_ids[k]] = weights[k];
+    }
+    auto score_of = [&](u64 edge) {
+        if (unit) return 1.0;
+        const auto it = attr.find(edge);
+        if (it == attr.end()) return std::numeric_limits<double>::infinity();   // (-inf negated under maximize)
+        return maximize ? -it->second : it->second;
+    };
+    // one (score, relationship) per unordered pair: over the selected tensors' effective edges, multi-edges included, both
+    // directions folded together (msf_keep_min_score, :237-255)
+    struct Scored { double score; u64 edge; };
+    std::unordered_map<u64, Scored> best;
+    for (u64 t : tids) {
+        for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
+            if (e.row == e.col || !sel.has(e.row) || !sel.has(e.col)) continue;
+            const u64 lo = e.row < e.col ? e.row : e.col, hi = e.row < e.col ? e.col : e.row;
+            const Scored y{score_of(e.val), e.val};
+            auto [it, fresh] = best.try_emplace((lo << 32) | hi, y);
+            if (fresh) continue;
+            Scored& x = it->second;
+            if (y.score < x.score || (y.score == x.score && y.edge < x.edge)) x = y;
+        }
+    }
+    // the symmetric weighted matrix, one binary64 bit pattern per entry (weighted_adj, :1690-1704)
+    std::vector<u64> rows, cols, bits;
+    rows.reserve(2 * best.size()); cols.reserve(2 * best.size()); bits.reserve(2 * best.size());
+    for (auto& kv : best) {
+        const u64 lo = kv.first >> 32, hi = kv.first & 0xFFFFFFFFull;
+        u64 b;
+        memcpy(&b, &kv.second.score, sizeof b);
+        rows.push_back(lo); cols.push_back(hi); bits.push_back(b);
+        rows.push_back(hi); cols.push_back(lo); bits.push_back(b);
+    }
+    Matrix w(g.ctx(), Type::UInt64, n, n);
+    if (!rows.empty()) w.build(rows, cols, &bits);
+    std::vector<int64_t> comp(n);
+    u64 *fr = nullptr, *fc = nullptr, k = 0;
+    double* fw = nullptr;
+    check(fgpu_msf(g.ctx().raw(), w.snapshot(), sel.bits.data(), comp.data(), &fr, &fc, &fw, &k, nullptr), "LAGraph_msf");
+    // trees in ascending order of their smallest node id = their component label (:1778-1848)
+    std::vector<int64_t> tree_of(n, -1);
+    for (u64 v = 0; v < n; ++v) {
+        if (comp[v] < 0) continue;
+        if ((u64)comp[v] == v) {
+            tree_of[v] = (int64_t)res.tree_nodes.size();
+            res.tree_nodes.emplace_back();
+            res.tree_edges.emplace_back();
+        }
+        res.tree_nodes[(size_t)tree_of[(size_t)comp[v]]].push_back(v);   // (comp[v] <= v: its tree exists already)
+    }
+    for (u64 i = 0; i < k; ++i)
+        res.tree_edges[(size_t)tree_of[(size_t)comp[fr[i]]]].push_back(best.at((fr[i] << 32) | fc[i]).edge);
+    fgpu_free(g.ctx().raw(), fr);
+    fgpu_free(g.ctx().raw(), fc);
+    fgpu_free(g.ctx().raw(), fw);
     return res;
 }
 

@@ -640,4 +640,18 @@ std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t
 BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
                                    int64_t sampling_size, int64_t sampling_seed);
 
+struct MsfResult {
+    std::vector<std::vector<u64>> tree_nodes;   // per tree, ascending node ids
+    std::vector<std::vector<u64>> tree_edges;   // per tree, the relationship id of every forest pair, in forest order
+};
+// algo.MSF (runtime/functions/algo_procedures.rs:1272-1857): labels / types empty = all; several labels select the UNION of
+// their nodes; an unknown relationship type throws "Relationship type '<t>' does not exist" (:1287-1295).  The host mirror has
+// no attribute store: the weight attribute arrives as (edge_ids[k], weights[k]), k < n_weights; edge_ids == nullptr means no
+// weightAttribute (every score 1.0), an edge id that is not listed is the missing-attribute case and scores +inf under either
+// objective (msf_score, :143-165).  Every unordered node pair keeps the relationship with the smallest score over the selected
+// types and its multi-edges, ties to the smallest id (msf_keep_min_score, :237-255); the forest is fgpu_msf's.  Trees come in
+// ascending order of their smallest node id; an isolated selected node is a tree without edges.
+MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types, bool maximize,
+                   const u64* edge_ids, const double* weights, u64 n_weights);
+
 }  // namespace falkor

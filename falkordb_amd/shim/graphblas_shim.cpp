@@ -115,7 +115,7 @@ void take_vector(falkor::ByteReader& r, GB_Vector_opaque* v) {
 }
 constexpr char BLOB_IDS[8] = {'F', 'G', 'I', 'D', 'L', 'S', 'T', '1'};   // = serialize.cpp PLAIN_MAGIC: BOOL vector, the set indices
 constexpr char BLOB_U64[8] = {'F', 'G', 'V', 'E', 'C', 'U', '6', '4'};   // UINT64 vector: length, count, (index, value) pairs
-GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2}, op_oneb_bool{3};
+GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2}, op_oneb_bool{3}, op_min_fp64{4};
 const GrB_Index all_indices = 0;   // what GrB_ALL points at: only its address is looked at
 GB_UnaryOp_opaque op_one_bool{0};
 GB_Semiring_opaque sr_any_pair_bool{0};
@@ -224,6 +224,7 @@ GrB_Type GrB_INT32 = &t_i32;       // types of the vectors LAGraph hands back (l
 GrB_Type GrB_INT64 = &t_i64;
 GrB_Type GrB_FP32 = &t_f32;
 GrB_Type GrB_FP64 = &t_f64;
+GrB_BinaryOp GrB_MIN_FP64 = &op_min_fp64;            // algo.MSF's weighted build (mod.rs:1964)
 
 // the 31 predefined descriptors (mod.rs:424-612; matrix.rs:313-351 maps all of them): R = replace, S = structural mask,
 // C = complemented mask, T0 / T1 = transpose the first / second input
@@ -287,7 +288,10 @@ GrB_Info GrB_Matrix_new(GrB_Matrix* A, GrB_Type type, GrB_Index nrows, GrB_Index
     if (!A || !type) return GrB_NULL_POINTER;
     SHIM_REQUIRE_INIT();
     return guarded([&]() -> GrB_Info {
-        *A = new GB_Matrix_opaque(Matrix(*ctx(), type == GrB_UINT64 ? Type::UInt64 : Type::Bool, nrows, ncols));
+        // GrB_FP64 (algo.MSF's weighted adjacency, algo_procedures.rs:1357-1358): a UINT64 matrix of bit patterns under a tag
+        const bool fp64 = type == GrB_FP64;
+        *A = new GB_Matrix_opaque(Matrix(*ctx(), type == GrB_UINT64 || fp64 ? Type::UInt64 : Type::Bool, nrows, ncols));
+        (*A)->fp64 = fp64;
         return GrB_SUCCESS;
     });
 }
@@ -301,6 +305,7 @@ GrB_Info GrB_Matrix_dup(GrB_Matrix* C, GrB_Matrix A) {
         GB_Matrix_opaque* c = new GB_Matrix_opaque(A->m.dup());
         c->sparsity_control = A->sparsity_control;
         c->orientation = A->orientation;
+        c->fp64 = A->fp64;
         *C = c;
         return GrB_SUCCESS;
     });
@@ -313,7 +318,7 @@ GrB_Info GrB_Matrix_nvals(GrB_Index* n, GrB_Matrix A) {
 }
 GrB_Info GxB_Matrix_type(GrB_Type* type, GrB_Matrix A) {
     if (!type || !A) return GrB_NULL_POINTER;
-    *type = A->m.type() == Type::UInt64 ? GrB_UINT64 : GrB_BOOL;
+    *type = A->fp64 ? GrB_FP64 : A->m.type() == Type::UInt64 ? GrB_UINT64 : GrB_BOOL;
     return GrB_SUCCESS;
 }
 GrB_Info GrB_Matrix_wait(GrB_Matrix A, int /* GrB_COMPLETE | GrB_MATERIALIZE */) {
@@ -357,7 +362,7 @@ GrB_Info GxB_Matrix_build_Scalar(GrB_Matrix C, const GrB_Index* I, const GrB_Ind
 GrB_Info GrB_Matrix_build_UINT64(GrB_Matrix C, const GrB_Index* I, const GrB_Index* J, const uint64_t* X, GrB_Index nvals,
                                  GrB_BinaryOp dup) {
     if (!C || (nvals && (!I || !J || !X))) return GrB_NULL_POINTER;
-    if (C->m.type() != Type::UInt64) return GrB_DOMAIN_MISMATCH;
+    if (C->m.type() != Type::UInt64 || C->fp64) return GrB_DOMAIN_MISMATCH;
     if (dup && dup != GrB_SECOND_UINT64) return GrB_NOT_IMPLEMENTED;      // the wrapper passes SECOND (matrix.rs:1186-1210)
     return guarded([&]() -> GrB_Info {
         if (C->m.nvals()) return GrB_OUTPUT_NOT_EMPTY;
@@ -398,6 +403,75 @@ GrB_Info GrB_Matrix_extractElement_UINT64(uint64_t* x, GrB_Matrix A, GrB_Index i
         auto v = A->m.get(i, j);
         if (!v) return GrB_NO_VALUE;
         *x = *v;
+        return GrB_SUCCESS;
+    });
+}
+// ---- GrB_FP64 matrices (mod.rs:9609, 9765, 9877, 10021): what algo.MSF builds, hands to LAGraph_msf and reads back ----------
+// The values travel as binary64 bit patterns in a UINT64 matrix (GB_Matrix_opaque::fp64); nvals / wait / free / resize / dup
+// work on it like on any other matrix.  dup: NULL (a duplicate is GrB_INVALID_VALUE, as the specification has it) or GrB_MIN_FP64.
+GrB_Info GrB_Matrix_build_FP64(GrB_Matrix C, const GrB_Index* I, const GrB_Index* J, const double* X, GrB_Index nvals,
+                               GrB_BinaryOp dup) {
+    if (!C || (nvals && (!I || !J || !X))) return GrB_NULL_POINTER;
+    if (!C->fp64) return GrB_DOMAIN_MISMATCH;
+    if (dup && dup != GrB_MIN_FP64) return GrB_NOT_IMPLEMENTED;
+    for (GrB_Index k = 0; k < nvals; ++k)
+        if (I[k] >= C->m.nrows() || J[k] >= C->m.ncols()) return GrB_INDEX_OUT_OF_BOUNDS;
+    return guarded([&]() -> GrB_Info {
+        if (C->m.nvals()) return GrB_OUTPUT_NOT_EMPTY;
+        std::map<std::pair<GrB_Index, GrB_Index>, double> seen;
+        for (GrB_Index k = 0; k < nvals; ++k) {
+            auto [it, fresh] = seen.try_emplace({I[k], J[k]}, X[k]);
+            if (fresh) continue;
+            if (!dup) return GrB_INVALID_VALUE;
+            if (X[k] < it->second) it->second = X[k];
+        }
+        std::vector<uint64_t> r, c, v;
+        r.reserve(seen.size()); c.reserve(seen.size()); v.reserve(seen.size());
+        for (auto& kv : seen) {
+            uint64_t b;
+            memcpy(&b, &kv.second, sizeof b);
+            r.push_back(kv.first.first); c.push_back(kv.first.second); v.push_back(b);
+        }
+        C->m.build(r, c, &v);
+        return GrB_SUCCESS;
+    });
+}
+GrB_Info GrB_Matrix_setElement_FP64(GrB_Matrix C, double x, GrB_Index i, GrB_Index j) {
+    if (!C) return GrB_NULL_POINTER;
+    if (!C->fp64) return GrB_DOMAIN_MISMATCH;
+    if (i >= C->m.nrows() || j >= C->m.ncols()) return GrB_INVALID_INDEX;
+    uint64_t b;
+    memcpy(&b, &x, sizeof b);
+    return guarded([&]() -> GrB_Info { C->m.set_element(i, j, b); return GrB_SUCCESS; });
+}
+GrB_Info GrB_Matrix_extractElement_FP64(double* x, GrB_Matrix A, GrB_Index i, GrB_Index j) {
+    if (!x || !A) return GrB_NULL_POINTER;
+    if (!A->fp64) return GrB_DOMAIN_MISMATCH;
+    if (i >= A->m.nrows() || j >= A->m.ncols()) return GrB_INVALID_INDEX;
+    return guarded([&]() -> GrB_Info {
+        auto v = A->m.get(i, j);
+        if (!v) return GrB_NO_VALUE;
+        memcpy(x, &*v, sizeof *x);
+        return GrB_SUCCESS;
+    });
+}
+// *nvals: the room in I / J / X on entry (GrB_INSUFFICIENT_SPACE when it is too small), the entries written on return; the
+// tuples come in ascending (row, col) order.  I / J / X may each be NULL (not wanted).
+GrB_Info GrB_Matrix_extractTuples_FP64(GrB_Index* I, GrB_Index* J, double* X, GrB_Index* nvals, GrB_Matrix A) {
+    if (!nvals || !A) return GrB_NULL_POINTER;
+    if (!A->fp64) return GrB_DOMAIN_MISMATCH;
+    return guarded([&]() -> GrB_Info {
+        const GrB_Index have = A->m.nvals();
+        if (*nvals < have) return GrB_INSUFFICIENT_SPACE;
+        GrB_Index k = 0;
+        if (have)
+            for (const falkor::Entry& e : A->m.iter(0, A->m.nrows() - 1)) {
+                if (I) I[k] = e.row;
+                if (J) J[k] = e.col;
+                if (X) memcpy(&X[k], &e.val, sizeof(double));
+                ++k;
+            }
+        *nvals = k;
         return GrB_SUCCESS;
     });
 }

@@ -1,6 +1,6 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
-// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality
-// procedures bind, on the MI355X engine.
+// exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality /
+// MSF procedures bind, on the MI355X engine.
 // With them next to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
@@ -16,13 +16,18 @@
 //   algo.HarmonicCentrality algo_procedures.rs:2676-2774 GrB_Matrix_new + GrB_Matrix_eWiseMult_BinaryOp(GrB_ONEB_BOOL, adj, adj) +
 //                  GrB_Matrix_resize -> LAGraph_New(DIRECTED) -> GrB_Vector_new + GrB_Vector_assign_BOOL(true, GrB_ALL) ->
 //                  LAGr_HarmonicCentrality (lagraphx_bindings.rs:486-492) -> GrB_Vector_extractTuples_FP64 / _INT64
+//   algo.MSF       algo_procedures.rs:1357-1358, 1704-1744 GrB_Matrix_new(GrB_FP64) ... GrB_Matrix_wait -> LAGraph_msf(sanitize =
+//                  false) (lagraphx_bindings.rs:261-267) -> GrB_Matrix_nvals + GrB_Matrix_extractTuples_FP64 on the forest,
+//                  GrB_Vector_extractTuples_INT64 on componentId.  The UDT scoring pipeline in front of the call (GrB_Type_new,
+//                  index-unary operators with host callbacks, UDT monoids, :1403-1701) is not part of this boundary: that pair
+//                  reduction is what the host layer's algo_msf does
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
 // lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness /
-// fgpu_cdlp / fgpu_harmonic, pinned against the oracle (WCC, betweenness, CDLP and harmonic centrality against the checkers of
-// their tests).  The three other LAGraph algorithms algo_procedures.rs calls (max-flow, MSF and the EMin property) are outside
-// this engine's path
+// fgpu_cdlp / fgpu_harmonic / fgpu_msf, pinned against the oracle (WCC, betweenness, CDLP, harmonic centrality and MSF against
+// the checkers of their tests).  The two other LAGraph entry points algo_procedures.rs calls (max-flow and the EMin property) are
+// outside this engine's path
 // (out of scope): they are exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of
 // computing anything.
 //
@@ -315,7 +320,7 @@ int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* s
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality / MSF only)")
 int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
 #else
 // ---- LAGraphX -----------------------------------------------------------------------------------------------------------
@@ -414,17 +419,55 @@ int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable_nodes, LAG
     });
 }
 // ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality only)")
+#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality / MSF only)")
 int LAGr_MaxFlow(double* f, GrB_Matrix* flow, GrB_Matrix* res, LAGraph_Graph, GrB_Index, GrB_Index, char* msg) {
     if (f) *f = 0;
     if (flow) *flow = nullptr;
     if (res) *res = nullptr;
     FG_NOT_ON_PATH(LAGr_MaxFlow);
 }
-int LAGraph_msf(GrB_Matrix* forest, GrB_Vector* comp, GrB_Matrix, bool, char* msg) {
-    if (forest) *forest = nullptr;
-    if (comp) *comp = nullptr;
-    FG_NOT_ON_PATH(LAGraph_msf);
+// LAGraph_msf (lagraphx_bindings.rs:261-267) as algo.MSF calls it (algo_procedures.rs:1707-1717): A is a symmetric GrB_FP64
+// matrix over compact node ids (a BOOL matrix means every weight is 1.0), sanitize = false.  forest_edges receives an n x n
+// GrB_FP64 matrix holding every forest edge once, at (min, max), with its weight; componentId (nullable) a full GrB_INT64
+// vector, entry i = the smallest vertex of i's tree (fgpu_msf; include/fgpu.h states the edge order that makes the forest
+// unique).  sanitize = true asks LAGraph to symmetrise A first — a form the procedure never sends: refused rather than
+// guessed, as dest >= 0 is in the BFS.
+int LAGraph_msf(GrB_Matrix* forest_edges, GrB_Vector* componentId, GrB_Matrix A, bool sanitize, char* msg) {
+    clear_msg(msg);
+    if (componentId) *componentId = nullptr;
+    if (!forest_edges) return fail(msg, GrB_NULL_POINTER, "forest_edges is NULL");
+    *forest_edges = nullptr;
+    if (!A) return fail(msg, GrB_NULL_POINTER, "A is NULL");
+    if (sanitize) return fail(msg, GrB_NOT_IMPLEMENTED, "LAGraph_msf: sanitize = true is not provided (pass a symmetric matrix)");
+    if (!A->fp64 && A->m.type() != Type::Bool)
+        return fail(msg, GrB_NOT_IMPLEMENTED, "LAGraph_msf: A must be a GrB_FP64 or GrB_BOOL matrix");
+    if (A->m.nrows() != A->m.ncols()) return fail(msg, GrB_DIMENSION_MISMATCH, "LAGraph_msf: A must be square");
+    return guarded(msg, [&]() -> int {
+        falkor::Context* c = fgshim::context();
+        const uint64_t n = A->m.nrows();
+        ResultVector<int64_t> comp;
+        if (componentId) comp.alloc(fgshim::type_int64(), n, 0, "LAGraph_msf");
+        uint64_t *fr = nullptr, *fc = nullptr, k = 0;
+        double* fw = nullptr;
+        check(fgpu_msf(c->raw(), A->m.snapshot(), nullptr, comp.data, &fr, &fc, &fw, &k, nullptr), "LAGraph_msf");
+        std::unique_ptr<GB_Matrix_opaque> f;
+        try {
+            f.reset(new GB_Matrix_opaque(Matrix(*c, Type::UInt64, n, n)));
+            f->fp64 = true;
+            if (k) {
+                std::vector<uint64_t> bits(k);
+                memcpy(bits.data(), fw, k * sizeof(uint64_t));
+                f->m.build(std::vector<uint64_t>(fr, fr + k), std::vector<uint64_t>(fc, fc + k), &bits);
+            }
+        } catch (...) {
+            fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fw);
+            throw;
+        }
+        fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fw);
+        *forest_edges = f.release();
+        if (componentId) *componentId = comp.release();
+        return GrB_SUCCESS;
+    });
 }
 #endif
 

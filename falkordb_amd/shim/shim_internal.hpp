@@ -31,7 +31,7 @@ typedef int GrB_Info;
 
 struct GB_Type_opaque { int code; const char* name; size_t size; };   // 0 = BOOL, 1 = UINT64; 2.. = the integer types a
                                                                        // GxB_Container's p / h / i / b vectors come in
-struct GB_BinaryOp_opaque { int code; };        // 0 = ANY_BOOL, 1 = SECOND_UINT64, 2 = ANY_UINT64
+struct GB_BinaryOp_opaque { int code; };        // 0 = ANY_BOOL, 1 = SECOND_UINT64, 2 = ANY_UINT64, 3 = ONEB_BOOL, 4 = MIN_FP64
 struct GB_UnaryOp_opaque { int code; };         // 0 = ONE_BOOL
 struct GB_Semiring_opaque { int code; };        // 0 = ANY_PAIR_BOOL
 struct GB_Descriptor_opaque { bool replace, structural, complement, t0, t1; };
@@ -41,6 +41,8 @@ struct GB_Matrix_opaque {
     Matrix m;
     int32_t sparsity_control = 3;   // GxB_HYPERSPARSE | GxB_SPARSE
     int32_t orientation = 0;        // GrB_ROWMAJOR
+    bool fp64 = false;              // a GrB_FP64 matrix: `m` is UINT64 and every value is a binary64 bit pattern (algo.MSF's
+                                    // weighted adjacency and forest; the host layer's Type enum knows nothing of it)
     explicit GB_Matrix_opaque(Matrix mm) : m(std::move(mm)) {}
 };
 // GrB_Vector as the wrapper uses it (vector.rs): (a) a sparse BOOL / UINT64 vector filled by setElement and walked by the

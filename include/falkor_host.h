@@ -233,6 +233,21 @@ int fh_algo_cdlp(fh_graph* g, const char* labels, const char* types, int64_t max
 int fh_algo_harmonic_centrality(fh_graph* g, const char* labels, const char* types, uint64_t** nodes, double** scores,
                                 int64_t** reachable, uint64_t* n);
 
+/* algo.MSF (algo_procedures.rs:1272-1857; LAGraph_msf through lagraphx_bindings.rs:261-267 is fgpu_msf, whose comment in fgpu.h
+ * states the edge order): labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes.  An
+ * unknown relationship type fails with "Relationship type '<t>' does not exist"; an empty graph or an empty selection gives no
+ * trees.  maximize != 0 is objective: 'maximize' (scores negated).  The host mirror has no attribute store, so the weight
+ * attribute is data: weights[k] is the attribute of relationship edge_ids[k], k < n_weights (an Int attribute widened by the
+ * caller).  edge_ids == NULL means no weightAttribute: every score is 1.0.  A relationship that is not listed has no such
+ * attribute and scores +inf under either objective.  Every unordered node pair keeps its smallest-score relationship over the
+ * selected types' effective edges (pending additions and deletions applied, multi-edges included), ties to the smallest id.
+ * Result, CSR-like: n_trees trees in ascending order of their smallest node id; nodes[node_off[t] .. node_off[t + 1]) the
+ * tree's nodes ascending; edges[edge_off[t] .. edge_off[t + 1]) the chosen relationship of each of its forest pairs, the
+ * pairs in ascending (min, max) order.  An isolated selected node is a tree without edges.  Free the four with fh_free. */
+int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize, const uint64_t* edge_ids, const double* weights,
+                uint64_t n_weights, uint64_t* n_trees, uint64_t** node_off, uint64_t** nodes, uint64_t** edge_off,
+                uint64_t** edges);
+
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
  * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).

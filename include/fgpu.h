@@ -472,6 +472,38 @@ fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t* active_bit
 fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint64_t* active_bitmap, double* score, int64_t* reachable,
                         uint8_t* registers, uint64_t stats[4]);
 
+/* Minimum spanning forest (Boruvka): replaces LAGraph_msf(&forest_edges, &component_id, A, sanitize = false, msg) as called by
+ * algo.MSF (algo_procedures.rs:1272-1857; binding lagraphx_bindings.rs:261-267) with a symmetric FP64 matrix over compact
+ * node ids.  LAGraph's source is not vendored; these are the rules:
+ *   - W is square and symmetric — pattern AND values — by the caller's promise (LAGraph's sanitize = false, like At == NULL in
+ *     fgpu_wcc).  A valued snapshot holds one IEEE-754 binary64 BIT PATTERN per entry in its uint64 value; a BOOL snapshot
+ *     means every weight is 1.0;
+ *   - diagonal entries are ignored.  `active_bitmap` (nullable, nrows bits, as fgpu_pagerank) selects the induced subgraph:
+ *     entries with an inactive end are ignored;
+ *   - every unordered pair {v, w} is ONE edge with the key (K(bits), min(v, w), max(v, w)), compared lexicographically.  K
+ *     replaces 0x8000000000000000 (-0.0) by 0, then flips all bits of a negative pattern and only the sign bit of a
+ *     non-negative one: the IEEE totalOrder with -0.0 = +0.0.  +-inf are ordinary weights (the reference scores a missing
+ *     attribute +inf); a NaN is not an error, it sorts beyond the infinity of its sign;
+ *   - that order is strict and total, so the minimum spanning forest under it is UNIQUE: it is the result, whatever order the
+ *     kernels race in, bit-identical from run to run.
+ * component (nullable, HOST array of nrows, filled by DMA when pinned — fgpu_host_alloc): component[v] = the smallest vertex
+ * id of v's tree, the labelling of fgpu_wcc; -1 for inactive vertices.  The forest comes back once per edge as (row < col),
+ * sorted ascending by (row, col), in three engine-owned arrays released with fgpu_free (pinned from 256 KiB up, like the
+ * arrays of fgpu_mat_export_csr; NULL when the forest is empty).  forest_weights[k] is the stored value of entry (row, col),
+ * bit-exact (-0.0 stays -0.0), or 1.0 for a BOOL W.  *n_forest = the active vertices minus the components.
+ * Broken promise: if W(v, w) and W(w, v) differ, or only one of them is stored, WHICH forest comes back is unspecified, but the
+ * call still returns FGPU_OK and the result is still a forest of (active - components) edges whose ends share a component: an
+ * edge is recorded only by the hook that actually joined two trees, never because a component merely chose it.
+ * stats (nullable): [0] Boruvka rounds, [1] forest edges, [2] adjacency entries read, summed over the rounds (rows whose
+ * entries were all internal in an earlier round are not read again), [3] components among the active vertices.
+ * Errors: NULL ctx / W / any of the four forest outputs: FGPU_NULL_POINTER; non-square W: FGPU_DIM_MISMATCH; nrows >= 2^32 - 1:
+ * FGPU_INVALID; an allocation that does not fit: FGPU_OOM.  nrows == 0 is a no-op with *n_forest = 0.  fgpu_get_option
+ * "msf_last_entries_round<k>", k = 0..31: the entries the last call read in round k (the round that found nothing included; the
+ * rounds past 31 are added into 31). */
+fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* active_bitmap, int64_t* component,
+                   uint64_t** forest_rows, uint64_t** forest_cols, double** forest_weights, uint64_t* n_forest,
+                   uint64_t stats[4]);
+
 /* Betweenness centrality (batched Brandes): replaces LAGr_Betweenness(&centrality, G, sources, ns, msg) as called by
  * algo.betweenness (algo_procedures.rs:884-1017; binding lagraph_bindings.rs:539-546).  centrality[v] = the sum over the
  * sources s of delta_s(v) = sum over out-neighbours w of v with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),

@@ -317,6 +317,49 @@ def bench_harmonic(ctx, scale):
                               "empty n x n matrix; per-iteration and TB/s figures use the call less the fixed part"}), flush=True)
 
 
+def bench_msf(ctx, scale):
+    """fgpu_msf on the symmetrised R-MAT graph: every pair's weight is a fixed hash of (lo, hi) mapped into [0, 100); a second run
+    on the BOOL pattern (all ties: the pair order alone decides).  The yardstick beside it is fgpu_wcc with wcc_mode 2 on the same
+    matrix: one link pass over every entry."""
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    rows = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp.astype(np.int64)))
+    keep = rows != ci
+    lo, hi = np.minimum(rows, ci)[keep], np.maximum(rows, ci)[keep]
+    key = np.unique(lo * np.uint64(n) + hi)                  # every unordered pair once
+    lo, hi = key // np.uint64(n), key % np.uint64(n)
+    del rp, ci, rows, keep, A
+    h = key * np.uint64(0x9E3779B97F4A7C15)                  # (mod 2^64)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(32)
+    w = (h >> np.uint64(11)).astype(np.float64) * (100.0 / 2.0**53)
+    r2, c2 = np.concatenate([lo, hi]), np.concatenate([hi, lo])
+    W = ctx.mat_from_coo(n, n, r2, c2, np.concatenate([w, w]).view(np.uint64))
+    S = ctx.mat_from_coo(n, n, r2, c2)
+    del lo, hi, key, h, w, r2, c2
+    nnz = W.nvals
+    out = ctx.host_array(n, np.int64)
+    ctx.set_option("wcc_mode", 2)
+    t_wcc, (_, wst) = timed(ctx, lambda: engine.wcc(ctx, S, None, stats=True, out=out), reps=5, warm=2)
+    ctx.set_option("wcc_mode", 0)
+    for label, m, per_entry in (("weighted", W, 12), ("bool", S, 4)):
+        t, res = timed(ctx, lambda: engine.msf(ctx, m, stats=True, out=out), reps=5, warm=2)
+        st = res[4]
+        per_round = [ctx.get_option("msf_last_entries_round%d" % k) for k in range(min(st[0] + 1, 32))]
+        print(json.dumps({"path": "msf", "scale": scale, "input": label, "n": n, "nnz": nnz, "ms": round(t * 1e3, 3),
+                          "rounds": st[0], "forest_edges": st[1], "entries_read": st[2], "components": st[3],
+                          "entries_read_per_round": per_round, "entries_read_over_nnz": round(st[2] / nnz, 3),
+                          "GBps_entries_read": round(st[2] * per_entry / t / 1e9, 1),
+                          "wcc_mode2_ms": round(t_wcc * 1e3, 3), "wcc_mode2_entries": wst[1],
+                          "ratio_to_wcc_mode2": round(t / t_wcc, 2),
+                          "note": "host clock around a synchronised call, median of 5 after 2 warm-up; a weighted round reads its "
+                                  "live rows twice (min weight, min pair), both counted; bytes per entry read = 4 (column id) + 8 "
+                                  "(value) weighted, 4 bool, the gathers of comp[] counted as cache traffic; wcc = fgpu_wcc, "
+                                  "wcc_mode 2, on the same pattern"}), flush=True)
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -391,6 +434,10 @@ if __name__ == "__main__":
     if what in ("harmonic", "all"):
         c = engine.Context(0)
         bench_harmonic(c, scale if scale else 22)
+        c.close()
+    if what in ("msf", "all"):
+        c = engine.Context(0)
+        bench_msf(c, scale if scale else 22)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
