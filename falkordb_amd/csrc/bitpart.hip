@@ -674,12 +674,210 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
     bp_block_add2(f_cnt, MODE == 2 ? f_sum : 0ull, fin.acc);
 }
 
-// LDS of the fold: MODE 2's checksum tables + a stage of 32 rows per wavefront
-static size_t xp_fold_lds(u32 ws, int mode, size_t lds_tables) {
-    return mode == 2 ? lds_tables + (size_t)(XP_FOLD_THREADS / 64) * 32 * (ws + 1) * sizeof(u64) : 0;
+// the fold by PIECE (expand_xp_fold = 1).  The slot fold above builds, at every step and on all 64 lanes, an index and an address
+// for each of the 8 partitions — the QL lanes of a slot the same one QL times — and loads 8 rows per destination whether they
+// exist or not: at RMAT-22 three of four are the plan's zero row, and the kernel is bound by instruction issue (VALU busy ~3/4 of
+// its time, profiles/NOTES_r12.md), not by memory.  Here the index work is done ONCE per group with a lane per ROW: lane r finds
+// which of (partition k, row 64 g + r) is a partial row, a direct entry or nothing, and where its pieces start in the group's
+// list — the counts it needs are the popcounts it has just taken, so there is no scan.  The half group's lanes write their
+// pieces (partial row, or XP_PIECE_X | slot of X; the row beside it) into a list in LDS, a slot of QL lanes takes one list
+// entry, loads it — XP_INFL entries in flight per slot, from addresses picked without a branch — and ORs it into the row's
+// words of the LDS stage (ds_or_b64), and the second phase of the slot fold, a lane per row, counts / looks up the staged words
+// and leaves the stage zero.  Slots past the list's end load its first entry again and do not OR it in.
+constexpr u32 XP_PIECE_X = 0x80000000u;   // bit 31 of a list entry: a row of X (partial rows < nnz < 2^31, slots of X < ncols < 2^31)
+constexpr u32 XP_HALF_PIECES = 32 * 8;    // a half group's list: 32 rows x 8 partitions
+constexpr int XP_INFL = 4;
+template <int QL, int MODE, bool NT, bool DIRECT>
+__global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u64* __restrict__ ne, const u32* __restrict__ pbase, u32 ng,
+                                                             const uint4* __restrict__ partial, BpFinal fin, uint4* __restrict__ side,
+                                                             const u64* __restrict__ de, const u32* __restrict__ dbase,
+                                                             const u32* __restrict__ dcol, const uint4* __restrict__ x) {
+    constexpr u32 SLOTS = 64 / QL;
+    constexpr u32 STR = 2 * QL + 1;                          // stage row stride in words (odd: a lane per row reads without conflicts)
+    constexpr u32 NW = XP_FOLD_THREADS / 64;
+    extern __shared__ u64 s_tab[];
+    const u32 ntab = MODE == 2 ? fin.w * 256 : 0u;
+    const u32 lane = lane_id(), wl = lane % QL, slot = lane / QL, wib = threadIdx.x >> 6;
+    u64* stg = s_tab + ntab + (size_t)wib * (32 * STR);      // 32 staged rows a wavefront, zero between the halves
+    u32* lst = reinterpret_cast<u32*>(s_tab + ntab + (size_t)NW * (32 * STR)) + (size_t)wib * XP_HALF_PIECES;
+    uint8_t* lrow = reinterpret_cast<uint8_t*>(s_tab + ntab + (size_t)NW * (32 * STR)) + (size_t)NW * XP_HALF_PIECES * sizeof(u32) +
+                    (size_t)wib * XP_HALF_PIECES;
+    if (MODE == 2)
+        for (u32 i = threadIdx.x; i < ntab; i += blockDim.x) s_tab[i] = fin.tab[i];
+    for (u32 i = lane; i < 32 * STR; i += 64) stg[i] = 0ull;
+    __syncthreads();
+    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+    const u64 lanes_below = (1ull << lane) - 1ull;
+    const u32 row = lane & 31u, hw = lane >> 5;              // second phase: lanes 0-31 the first QL words of a row, 32-63 the others
+    u64 f_cnt = 0, f_sum = 0;
+    for (u32 g = wave; g < ng; g += nwaves) {
+        u64 nw[8], dw[8];
+        u32 pb[8], ent[8];
+        u64 any = 0ull;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            nw[k] = xp_uniform64(ne[(size_t)k * ng + g]);
+            pb[k] = (u32)__builtin_amdgcn_readfirstlane((int)pbase[(size_t)k * ng + g]);
+            any |= nw[k];
+        }
+        if (DIRECT) {   // (lane k < 8 loads partition k's direct word and base: see xp_fold_kernel)
+            const size_t kl = (size_t)(lane & 7u) * ng + g;
+            const u64 dl = de[kl];
+            const u32 bl = dbase[kl];
+            u64 dany = 0ull;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                dw[k] = ((u64)(u32)__shfl((int)(u32)(dl >> 32), k, 64) << 32) | (u64)(u32)__shfl((int)(u32)dl, k, 64);
+                ent[k] = (u32)__shfl((int)bl, k, 64);
+                dany |= dw[k];
+            }
+            any |= xp_uniform64(dany);
+        }
+        if (!any) continue;
+        // lane r: its pieces, and how many the rows before it have (a run is a partial row OR a direct entry, never both)
+        u32 have = 0, pref = 0;
+        if (DIRECT) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const u32 db = (u32)__popcll(dw[k] & lanes_below);
+                const u32 dbit = (u32)(dw[k] >> lane) & 1u;
+                ent[k] = dcol[dbit ? ent[k] + db : 0u] | XP_PIECE_X;
+                have |= dbit << k;
+                pref += db;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const u32 nb = (u32)__popcll(nw[k] & lanes_below);
+            const u32 bit = (u32)(nw[k] >> lane) & 1u;
+            if (DIRECT) ent[k] = bit ? pb[k] + nb : ent[k];
+            else ent[k] = pb[k] + nb;
+            have |= bit << k;
+            pref += nb;
+        }
+        const u64 tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
+        const u32 tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
+        const u64 lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
+        const u32 tot0 = (u32)__builtin_amdgcn_readlane((int)pref, 32);   // pieces of rows 0 .. 31
+        const u32 tot = (u32)__builtin_amdgcn_readlane((int)(pref + (u32)__popc(have)), 63);
+#pragma unroll 1
+        for (u32 hf = 0; hf < 2; ++hf) {
+            const u32 np = hf ? tot - tot0 : tot0;           // (wave-uniform) pieces of this half
+            if (!np) continue;
+            if (hw == hf) {
+                u32 pos = pref - (hf ? tot0 : 0u);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if ((have >> k) & 1u) {
+                        lst[pos] = ent[k];
+                        lrow[pos] = (uint8_t)row;
+                        ++pos;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+            for (u32 j0 = 0; j0 < np; j0 += SLOTS * XP_INFL) {
+                // (the list reads, then the loads, then the ORs — each kind issued together: left to itself hipcc interleaves them
+                // and waits for every list read before the load that uses it)
+                uint4 pv[XP_INFL];
+                u32 pe[XP_INFL], pr[XP_INFL];
+#pragma unroll
+                for (int u = 0; u < XP_INFL; ++u) {
+                    const u32 j = j0 + (u32)u * SLOTS + slot;
+                    const u32 jc = j < np ? j : 0u;
+                    pe[u] = lst[jc];
+                    pr[u] = (u32)lrow[jc];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < XP_INFL; ++u) {
+                    const uint4* src = partial + (size_t)pe[u] * QL + wl;
+                    if (DIRECT) src = (pe[u] & XP_PIECE_X) ? x + (size_t)(pe[u] & ~XP_PIECE_X) * QL + wl : src;
+                    pv[u] = NT ? xp_load_nt(src) : *src;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < XP_INFL; ++u) {
+                    if (j0 + (u32)u * SLOTS + slot < np) {
+                        unsigned long long* d = reinterpret_cast<unsigned long long*>(stg) + (size_t)pr[u] * STR + 2 * wl;
+                        atomicOr(d, ((unsigned long long)pv[u].y << 32) | pv[u].x);
+                        atomicOr(d + 1, ((unsigned long long)pv[u].w << 32) | pv[u].z);
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // rows a delta layer names leave for their slot of the side buffer (few: a slot pass over the half)
+            const u32 twh = (u32)((tw & any) >> (32 * hf));
+            if (twh) {
+                for (u32 r0 = 0; r0 < 32; r0 += SLOTS) {
+                    const u32 r = r0 + slot;
+                    if (r < 32 && ((twh >> r) & 1u)) {
+                        const u64 w0 = stg[(size_t)r * STR + 2 * wl], w1 = stg[(size_t)r * STR + 2 * wl + 1];
+                        if (w0 | w1) {
+                            const u32 sl = tp + (u32)__popcll(tw & ((1ull << (32 * hf + r)) - 1ull));
+                            side[(size_t)sl * QL + wl] = make_uint4((u32)w0, (u32)(w0 >> 32), (u32)w1, (u32)(w1 >> 32));   // the only writer of this slot
+                        }
+                    }
+                }
+            }
+            // a lane per row: count, look up, clear
+            const u32 rg = 32 * hf + row;
+            const bool counted = !((tw >> rg) & 1ull) && ((lb >> rg) & 1ull);
+            u64 rs = 0;
+            u32 pc = 0;
+#pragma unroll 2
+            for (u32 kk = 0; kk < (u32)QL; ++kk) {
+                const u32 k = hw * QL + kk;
+                const u64 sw = stg[(size_t)row * STR + k];
+                stg[(size_t)row * STR + k] = 0ull;
+                const u64 w = counted ? sw : 0ull;
+                pc += (u32)__popcll(w);
+                if (MODE == 2) {
+                    // (an all-zero word looks up entry 0 of its tables — zero; words at or past fin.w are zero by construction)
+                    // the 16 reads of a word are issued together and summed as a tree: as a chain into one sum hipcc waits for every
+                    // read before it issues the next, and a wavefront spends a look-up's LDS latency 16 times per word; without the
+                    // scheduling barrier it still pairs them up to save registers
+                    const u64* tk = s_tab + (size_t)(k < fin.w ? k : 0u) * 256;
+                    u64 tv[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) tv[j] = tk[j * 16 + (u32)((w >> (4 * j)) & 15ull)];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int d = 8; d >= 1; d >>= 1)
+#pragma unroll
+                        for (int j = 0; j < d; ++j) tv[j] += tv[j + d];
+                    rs += tv[0];
+                }
+            }
+            f_cnt += (u64)pc;
+            if (MODE == 2) {
+                rs += (u64)__shfl_xor((long long)rs, 32, 64);                 // the two halves of a row
+                if (hw == 0) f_sum += rs * cs_dest_hash(g * 64 + rg);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");           // (cleared before the next half ORs into the stage)
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    bp_block_add2(f_cnt, MODE == 2 ? f_sum : 0ull, fin.acc);
+}
+
+// LDS of the fold: MODE 2's checksum tables + a stage of 32 rows per wavefront; the piece fold stages in both modes and keeps a
+// list of XP_HALF_PIECES entries (4 bytes + the row's byte) per wavefront
+static size_t xp_fold_lds(u32 ws, int mode, size_t lds_tables, int pieces) {
+    const size_t stage = (size_t)(XP_FOLD_THREADS / 64) * 32 * (ws + 1) * sizeof(u64);
+    if (pieces) return (mode == 2 ? lds_tables : 0) + stage + (size_t)(XP_FOLD_THREADS / 64) * XP_HALF_PIECES * (sizeof(u32) + 1);
+    return mode == 2 ? lds_tables + stage : 0;
+}
+// which fold a row width gets: the piece fold from expand_xp_fold_min_words words up (narrow rows: NOTES_r12 section 3.5)
+static int xp_fold_by_pieces(const fgpu_ctx* ctx, u32 ws) {
+    return ctx->opt.expand_xp_fold && ws >= (u32)ctx->opt.expand_xp_fold_min_words ? 1 : 0;
 }
 bool bp_xfold_fits(const fgpu_ctx* ctx, u32 ws, int mode, size_t lds_tables) {
-    return xp_fold_lds(ws, mode, lds_tables) <= (size_t)ctx->opt.lds_limit;
+    return xp_fold_lds(ws, mode, lds_tables, xp_fold_by_pieces(ctx, ws)) <= (size_t)ctx->opt.lds_limit;
 }
 
 fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,
@@ -733,6 +931,7 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
     {
         // (no algorithmic bytes of its own: everything it reads is the stream kernel's intermediate — bench.py quotes the hop,
         // stream + fold, against the stream kernel's bytes)
+        // (the scope names the STEP, whichever of the two fold kernels runs it: bench.py quotes stream + fold under this name)
         ProfScope ps(ctx, "xp_fold_kernel", 0);
         // (4 or 8 wavefronts sharing one copy of the checksum tables, 16 or 32 resident per CU: the same 214 / 148 us with and
         // without the checksum at RMAT-22 — the kernel is not short of wavefronts)
@@ -740,7 +939,12 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
         u32 grid = cdiv(xp->ng, fthreads / 64);
         if (grid > (u32)ctx->cus * (2048u / fthreads)) grid = ctx->cus * (2048u / fthreads);
         // (the count-hop planner takes the plain pull when this does not fit: bp_xfold_fits)
-        const size_t lds = xp_fold_lds(ws, mode, lds_tables);
+        const int pieces = xp_fold_by_pieces(ctx, ws);
+        // (a list entry tags a slot of X with bit 31: the plan's own limits — nnz and columns below 2^31 — keep both kinds below it)
+        FGPU_REQUIRE(!pieces || ((u64)xp->nprows < XP_PIECE_X && t->ncols < XP_PIECE_X), FGPU_INVALID,
+                     "partitioned pull: the piece fold needs partial rows and columns below 2^31");
+        (pieces ? ctx->xp_piece_folds : ctx->xp_slot_folds).fetch_add(1, std::memory_order_relaxed);
+        const size_t lds = xp_fold_lds(ws, mode, lds_tables, pieces);
         FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID, "partitioned pull: the fold needs %zu B of LDS", lds);
 #define XP_FOLD4(Q, M, N, D)                                                                                                     \
         do {                                                                                                                     \
@@ -750,7 +954,20 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
                                (const uint4*)partial.p, fin, (uint4*)side, xp->nprows, (const u64*)xp->de, (const u32*)xp->dbase,                 \
                                (const u32*)xp->dcol, (const uint4*)x);                                                                             \
         } while (0)
-#define XP_FOLD3(Q, M, N) do { if (xp->direct) XP_FOLD4(Q, M, N, true); else XP_FOLD4(Q, M, N, false); } while (0)
+#define XP_PIECES4(Q, M, N, D)                                                                                                   \
+        do {                                                                                                                     \
+            if (lds > 48 * 1024)                                                                                                 \
+                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_pieces_kernel<Q, M, N, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((xp_fold_pieces_kernel<Q, M, N, D>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase,  \
+                               xp->ng, (const uint4*)partial.p, fin, (uint4*)side, (const u64*)xp->de, (const u32*)xp->dbase,                  \
+                               (const u32*)xp->dcol, (const uint4*)x);                                                                          \
+        } while (0)
+#define XP_FOLD3(Q, M, N)                                                                                                        \
+        do {                                                                                                                     \
+            if (pieces) { if (xp->direct) XP_PIECES4(Q, M, N, true); else XP_PIECES4(Q, M, N, false); }                          \
+            else if (xp->direct) XP_FOLD4(Q, M, N, true);                                                                        \
+            else XP_FOLD4(Q, M, N, false);                                                                                       \
+        } while (0)
 #define XP_FOLD2(Q, M) do { if (ctx->opt.expand_nt & 4) XP_FOLD3(Q, M, true); else XP_FOLD3(Q, M, false); } while (0)
 #define XP_FOLD(Q) do { if (mode == 2) XP_FOLD2(Q, 2); else XP_FOLD2(Q, 1); } while (0)
         switch (ql) {
@@ -763,6 +980,7 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
 #undef XP_FOLD2
 #undef XP_FOLD3
 #undef XP_FOLD4
+#undef XP_PIECES4
         FGPU_HIP(hipGetLastError());
     }
     (void)t;

@@ -107,6 +107,11 @@ struct fgpu_options {  // fgpu_set_option
     int expand_xcd_min_mb = 32; // ... when the bit state holds at least this many MiB (8 L2s of 4 MiB; below that the plain pull)
     int expand_xp_direct = 1;   // ... 1 = a (partition, row) run of ONE entry leaves the stream: the fold reads that row of X itself
                                // instead of a partial row the stream kernel copied out of it (bitpart.hip), 0 = every run is streamed (A/B)
+    int expand_xp_fold = 1;     // ... the fold of the partial rows: 1 = the index work once per row and one load per piece that exists
+                               // (xp_fold_pieces_kernel), 0 = a slot per row and step, 8 loads each, most of them the zero row (A/B)
+    int expand_xp_fold_min_words = 8; // ... the piece fold runs on bit rows of at least this many 64-bit words, narrower rows keep the slot
+                               // fold: at 2 and 4 words the piece fold is 30 us per launch SLOWER (its fixed work per group outweighs
+                               // the few look-ups of a narrow row), at 8 it is 24 us faster, at 16 103 us (profiles/NOTES_r12.md section 3.5)
     int expand_scan_min = 2048; // fgpu_expand_count: a call with more source rows than this is a WHOLE-FRONTIER call (spgemm.hip
                                // expand_count_scan): live rows filtered and compacted on the device, cut into passes (0 = never)
     int expand_scan_rows = 1024; // ... live rows per pass: 1024 = 16 words = one 128-byte line per vertex of the bit state
@@ -190,6 +195,7 @@ struct fgpu_ctx {
     std::atomic<uint32_t> bfs_cp_last{0};   // ... and the fused launches of that search that ran behind bfs_pb_list_kernel ("bfs_cp_last_mask")
     std::atomic<uint32_t> bfs_pb_last{0};   // levels the search fgpu_bfs_stats last read ran by propagation blocking ("bfs_pb_last_levels")
     std::atomic<uint32_t> scan_last_live{0}, scan_last_passes{0};   // the last such call: live source rows, passes ("expand_scan_*")
+    std::atomic<uint64_t> xp_piece_folds{0}, xp_slot_folds{0};   // launches of the two folds so far ("expand_xp_piece_folds" / "expand_xp_slot_folds")
     std::atomic<uint64_t> xp_last_direct{0};    // single-entry runs the fold read from X in the last partitioned count hop ("expand_xp_last_direct")
     std::atomic<uint64_t> hc_last_entries{0}, hc_last_gathered{0};   // the last fgpu_harmonic call: entries of the recomputed rows, sketches gathered ("harmonic_last_*")
     std::atomic<uint64_t> msf_round_entries[32] = {};   // the last fgpu_msf call: entries read in round k, the rounds past 31 in [31] ("msf_last_entries_round<k>")

@@ -815,6 +815,10 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "expand_scan_last_live")) *value = ctx->scan_last_live.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_scan_last_passes")) *value = ctx->scan_last_passes.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_xp_direct")) *value = ctx->opt.expand_xp_direct;
+    else if (!strcmp(name, "expand_xp_fold")) *value = ctx->opt.expand_xp_fold;
+    else if (!strcmp(name, "expand_xp_fold_min_words")) *value = ctx->opt.expand_xp_fold_min_words;
+    else if (!strcmp(name, "expand_xp_piece_folds")) *value = (int64_t)ctx->xp_piece_folds.load(std::memory_order_relaxed);
+    else if (!strcmp(name, "expand_xp_slot_folds")) *value = (int64_t)ctx->xp_slot_folds.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_xp_last_direct")) *value = (int64_t)ctx->xp_last_direct.load(std::memory_order_relaxed);
     else if (!strcmp(name, "harmonic_last_entries")) *value = (int64_t)ctx->hc_last_entries.load(std::memory_order_relaxed);
     else if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32)
@@ -870,6 +874,13 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     } else if (!strcmp(name, "expand_xp_direct")) {
         FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_direct must be 0 (every run streamed) or 1 (single-entry runs read by the fold)");
         ctx->opt.expand_xp_direct = (int)value;
+    } else if (!strcmp(name, "expand_xp_fold")) {
+        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_fold must be 0 (a slot per row and step) or 1 (a slot per existing piece)");
+        ctx->opt.expand_xp_fold = (int)value;
+    } else if (!strcmp(name, "expand_xp_fold_min_words")) {
+        FGPU_REQUIRE(value >= 2 && value <= 32 && (value & (value - 1)) == 0, FGPU_INVALID,
+                     "expand_xp_fold_min_words must be 2, 4, 8, 16 or 32 (32: no row is that wide, the slot fold everywhere)");
+        ctx->opt.expand_xp_fold_min_words = (int)value;
     } else if (!strcmp(name, "expand_scan_min")) {
         FGPU_REQUIRE(value >= 0 && value <= (1ll << 31), FGPU_INVALID, "expand_scan_min out of range");
         ctx->opt.expand_scan_min = (int)value;

@@ -125,7 +125,12 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  * far: the launch count of a batch is a difference of two reads), "bfs_pb_last_levels" (levels the search fgpu_bfs_stats last
  * read ran by propagation blocking), "bfs_cp_last_mask" (bit k: fused launch k of that search ran behind the list kernel — a
  * sparse frontier listed into the queue, or a pull of listed candidates), "expand_scan_last_live" / "expand_scan_last_passes" (live source rows and passes of the
- * last whole-frontier fgpu_expand_count), "expand_xp_direct" and "expand_xp_last_direct" (entries of A' the last XCD-partitioned count hop
+ * last whole-frontier fgpu_expand_count), "expand_xp_fold" (set through fgpu_set_option; the fold of the XCD-partitioned
+ * count hop: 1 = a lane per row does the index work and a slot loads each partial row / direct entry that exists, 0 = a slot
+ * per row and step loads all 8 partitions' rows; results are identical), "expand_xp_fold_min_words" (set through fgpu_set_option:
+ * the piece fold runs on bit rows of at least this many 64-bit words — 2, 4, 8, 16, or 32 for none — and narrower rows keep the
+ * slot fold), "expand_xp_piece_folds" / "expand_xp_slot_folds" (launches of either fold on this context so far: which fold a
+ * call ran, and that the partitioned hop ran at all, is a difference of two reads), "expand_xp_direct" and "expand_xp_last_direct" (entries of A' the last XCD-partitioned count hop
  * read straight from X as single-entry runs, 0 when its plan streams every run), "expand_xcd", "expand_xcd_relabel" and
  * "expand_xcd_min_mb" (the settings of the partitioned count hop, so that a caller can put back what it found), "expand_mode",
  * "expand_nt", "wcc_mode", "bc_batch", "bc_direction".  Unknown
