@@ -10,6 +10,13 @@ __device__ __forceinline__ bool vertex_on(const u64* __restrict__ act, u32 v) {
     return !act || ((act[v >> 6] >> (v & 63)) & 1ull);
 }
 
+// the sort key (msf.hip, maxflow.hip's minimum value) of a stored binary64 pattern: -0.0 is +0.0, then all bits of a negative pattern flip and the sign bit of a
+// non-negative one (NaNs sort beyond the infinity of their sign)
+__host__ __device__ __forceinline__ u64 msf_key(u64 b) {
+    if (b == 0x8000000000000000ull) b = 0;
+    return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
+}
+
 // adds a 256-thread workgroup's x into *dst with ONE atomic: one per wave onto a single word serialises (16 K waves of a
 // grid-stride launch at RMAT-22 made the count passes 0.26-0.53 ms).  Ends in a barrier: s_part is free again on return,
 // so a kernel may call it several times in a row.

@@ -131,6 +131,7 @@ struct fgpu_options {  // fgpu_set_option
     int wcc_mode = 0;          // fgpu_wcc: 0 auto (Afforest from 4096 vertices), 1 Afforest with sampling and skip, 2 one full link
                                // pass over every entry of A (wcc.hip)
     int bc_batch = 0;          // fgpu_betweenness: sources per batch, 0 auto (16 / 32 / 64 by nsrc, halved to fit free memory), 1-64 forced
+    int maxflow_global_every = 0;   // fgpu_maxflow: pulses between two global relabels (0 = MF_GLOBAL_EVERY of maxflow.hip; A/B)
     int bc_direction = 0;      // fgpu_betweenness forward levels: 0 auto (push / pull by entries to read), 1 push over A, 2 pull over At
 };
 

@@ -809,6 +809,7 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "wcc_mode")) *value = ctx->opt.wcc_mode;
     else if (!strcmp(name, "bc_batch")) *value = ctx->opt.bc_batch;
     else if (!strcmp(name, "bc_direction")) *value = ctx->opt.bc_direction;
+    else if (!strcmp(name, "maxflow_global_every")) *value = ctx->opt.maxflow_global_every;
     else if (!strcmp(name, "bfs_pb_min_edges")) *value = ctx->opt.bfs_pb_min_edges;
     else if (!strcmp(name, "bfs_cp_last_mask")) *value = ctx->bfs_cp_last.load(std::memory_order_relaxed);
     else if (!strcmp(name, "bfs_pb_last_levels")) *value = ctx->bfs_pb_last.load(std::memory_order_relaxed);
@@ -862,6 +863,9 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     } else if (!strcmp(name, "bc_direction")) {
         FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "bc_direction must be 0 (auto), 1 (push) or 2 (pull)");
         ctx->opt.bc_direction = (int)value;
+    } else if (!strcmp(name, "maxflow_global_every")) {
+        FGPU_REQUIRE(value >= 0 && value <= (1 << 20), FGPU_INVALID, "maxflow_global_every must be 0 (default) or a pulse count");
+        ctx->opt.maxflow_global_every = (int)value;
     } else if (!strcmp(name, "expand_first_hop")) {
         ctx->opt.expand_first_hop = value != 0;
     } else if (!strcmp(name, "expand_xcd")) {

@@ -38,13 +38,6 @@ constexpr u64 MSF_NONE = ~0ull;
 constexpr u32 MSF_MAX_JUMPS = 40;   // pointer-jumping launches of one compress: 33 flatten any forest of < 2^32 vertices
 constexpr u64 MSF_ONE = 0x3FF0000000000000ull;   // 1.0
 
-// the sort key of a stored binary64 pattern: -0.0 is +0.0, then all bits of a negative pattern flip and the sign bit of a
-// non-negative one (NaNs sort beyond the infinity of their sign)
-__host__ __device__ __forceinline__ u64 msf_key(u64 b) {
-    if (b == 0x8000000000000000ull) b = 0;
-    return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
-}
-
 // root of x by plain loads with path halving (wcc_find's rules)
 __device__ __forceinline__ u32 msf_find(u32* parent, u32 x) {
     for (;;) {

@@ -581,6 +581,24 @@ def msf(ctx: Context, W: Mat, active_bitmap=None, stats: bool = False, out=None)
     return comp, rows, cols, weights, ([int(x) for x in st] if stats else None)
 
 
+def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
+    """fgpu_maxflow: LAGr_MaxFlow's result for algo.maxFlow over the capacity matrix C_ — a valued snapshot carries one binary64
+    bit pattern per entry, a BOOL one means capacity 1.0; diagonal entries and capacities <= 0 are ignored, a NaN or infinite
+    one is an error.  Returns (value, rows uint64[k], cols uint64[k], flows float64[k], stats) — the arcs that carry flow > 0
+    sorted by (row, col); the value is unique, the assignment is one of the maximum flows; stats the four counters [pulses,
+    global relabels, residual arcs, pushes] when stats=True, else None."""
+    r, c, f = u64p(), u64p(), C.POINTER(C.c_double)()
+    k = C.c_uint64()
+    val = C.c_double()
+    st = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_maxflow(ctx._h, C_._h, C.c_uint64(src), C.c_uint64(sink), C.byref(val), C.byref(r), C.byref(c),
+                               C.byref(f), C.byref(k), _p(st)))
+    rows = ctx._take(r, k.value)
+    cols = ctx._take(c, k.value)
+    flows = ctx._take(f, k.value, dtype=np.float64)
+    return val.value, rows, cols, flows, ([int(x) for x in st] if stats else None)
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

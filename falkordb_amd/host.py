@@ -568,6 +568,32 @@ class Graph:
         nv, ev = _take(nodes, int(no[-1])), _take(edges, int(eo[-1]))
         return [(nv[int(no[i]):int(no[i + 1])], ev[int(eo[i]):int(eo[i + 1])]) for i in range(t)]
 
+    def algo_maxflow(self, sources, targets, types, capacities=None, default_capacity=None, labels=(), attribute_exists=None):
+        """CALL algo.maxFlow({sourceNodes, targetNodes, relationshipTypes, capacityProperty, defaultCapacity, nodeLabels})
+        YIELD nodes, edges, edgeFlows, maxFlow -> (nodes uint64[], edges uint64[], flows float64[], max_flow).  capacities: a
+        {relationship id: value} dict standing for the capacity attribute — a value that is no number (a string, a list) counts
+        as missing, like an id that is not listed; attribute_exists: whether the graph knows the attribute name at all
+        (default: capacities is not None).  See fh_algo_maxflow for the rules and the failures."""
+        if attribute_exists is None:
+            attribute_exists = capacities is not None
+        num = {k: float(v) for k, v in (capacities or {}).items() if isinstance(v, (int, float)) and not isinstance(v, bool)}
+        ids = np.ascontiguousarray(list(num.keys()), dtype=np.uint64)
+        cps = np.ascontiguousarray(list(num.values()), dtype=np.float64)
+        src = np.ascontiguousarray(list(sources), dtype=np.uint64)
+        dst = np.ascontiguousarray(list(targets), dtype=np.uint64)
+        nodes, edges = u64p(), u64p()
+        flows = C.POINTER(C.c_double)()
+        nn, ne = C.c_uint64(), C.c_uint64()
+        val = C.c_double()
+        _ck(self.L.fh_algo_maxflow(self.h, ",".join(labels).encode(), ",".join(types).encode(), src.ctypes.data_as(u64p),
+                                   C.c_uint64(len(src)), dst.ctypes.data_as(u64p), C.c_uint64(len(dst)),
+                                   C.c_int(1 if attribute_exists else 0), ids.ctypes.data_as(u64p),
+                                   cps.ctypes.data_as(C.POINTER(C.c_double)), C.c_uint64(len(ids)),
+                                   C.c_int(0 if default_capacity is None else 1),
+                                   C.c_double(0.0 if default_capacity is None else float(default_capacity)), C.byref(nodes),
+                                   C.byref(nn), C.byref(edges), C.byref(flows), C.byref(ne), C.byref(val)))
+        return _take(nodes, nn.value), _take(edges, ne.value), _take(flows, ne.value, np.float64), val.value
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

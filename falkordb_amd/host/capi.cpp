@@ -774,6 +774,27 @@ int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize
     });
 }
 
+// algo.maxFlow: labels / types = comma lists; the capacity attribute as (edge_ids[k], caps[k])
+int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const uint64_t* sources, uint64_t n_sources,
+                    const uint64_t* targets, uint64_t n_targets, int has_attribute, const uint64_t* edge_ids, const double* caps,
+                    uint64_t n_caps, int has_default, double default_capacity, uint64_t** nodes, uint64_t* n_nodes,
+                    uint64_t** edges, double** flows, uint64_t* n_edges, double* max_flow) {
+    return guard([&] {
+        const std::vector<u64> src(sources, sources + (sources ? n_sources : 0)), dst(targets, targets + (targets ? n_targets : 0));
+        MaxFlowResult r = timed([&] {
+            return algo_maxflow(g->g, csv(labels), csv(types), src, dst, has_attribute != 0, edge_ids, caps, n_caps, has_default != 0,
+                                default_capacity);
+        });
+        *nodes = hand(r.nodes);
+        *n_nodes = r.nodes.size();
+        *edges = hand(r.edges);
+        *flows = hand(r.flows);
+        *n_edges = r.edges.size();
+        *max_flow = r.max_flow;
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

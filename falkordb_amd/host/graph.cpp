@@ -4,6 +4,8 @@
 #include <cstring>
 #include <limits>
 #include <unordered_map>
+#include <unordered_set>
+#include <cmath>
 
 #include "host.hpp"
 
@@ -1088,6 +1090,126 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
     fgpu_free(g.ctx().raw(), fr);
     fgpu_free(g.ctx().raw(), fc);
     fgpu_free(g.ctx().raw(), fw);
+    return res;
+}
+
+// ---- algo.maxFlow ---------------------------------------------------------------------------------------
+MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                           const std::vector<u64>& sources, const std::vector<u64>& targets, bool has_attribute,
+                           const u64* edge_ids, const double* caps, u64 n_caps, bool has_default, double default_capacity) {
+    if (types.size() != 1)                                               // :2809-2813
+        throw std::invalid_argument("algo.maxFlow: exactly one relationship type must be given in 'relationshipTypes'");
+    if (sources.empty() || targets.empty())                              // :2841-2845
+        throw std::invalid_argument("algo.maxFlow expects at least one source node and one target node");
+    const std::unordered_set<u64> src_set(sources.begin(), sources.end());
+    for (u64 t : targets)                                                // :2847-2853
+        if (src_set.count(t)) throw std::invalid_argument("algo.maxFlow: the source set and the target set must be disjoint");
+    if (has_default && !(default_capacity >= 0.0))                       // :2864-2875
+        throw std::invalid_argument("algo.maxFlow: 'defaultCapacity' must be a number that is not negative");
+    const auto tid = g.type_id(types[0]);
+    if (!tid) throw std::invalid_argument("algo.maxFlow: relationship type '" + types[0] + "' is unknown");   // :2879-2884
+    const Tensor& tensor = g.relationship_tensors()[*tid];
+    if (tensor.has_multi_edge())                                         // :2885-2890
+        throw std::invalid_argument("algo.maxFlow: relationship type '" + types[0] +
+                                    "' holds multi-edges, which a capacity matrix cannot express");
+    const char* no_capacity = "algo.maxFlow: a relationship has an invalid or missing attribute and no default capacity was given";
+    if (!has_attribute && !has_default) throw std::invalid_argument(no_capacity);   // :2894-2898
+    NodeSelection sel;
+    const bool filtered = !labels.empty();
+    if (filtered) sel = select_nodes(g, labels);                         // :2900-2905
+    std::unordered_map<u64, double> attr;
+    if (has_attribute && edge_ids) {
+        attr.reserve(n_caps * 2);
+        for (u64 k = 0; k < n_caps; ++k) attr[edge_ids[k]] = caps[k];
+    }
+    // the type's effective edges whose two ends are selected, each with its capacity (:2907-2951)
+    struct Arc { u64 src, dst, edge; double cap; };
+    std::vector<Arc> arcs;
+    for (const Entry& e : tensor.iter_edges()) {
+        if (filtered && (!sel.has(e.row) || !sel.has(e.col))) continue;
+        double c = default_capacity;
+        const auto it = attr.find(e.val);
+        if (it != attr.end() && it->second >= 0.0) c = it->second;
+        else if (!has_default) throw std::invalid_argument(no_capacity);
+        arcs.push_back(Arc{e.row, e.col, e.val, c});
+    }
+    MaxFlowResult res;
+    if (arcs.empty()) return res;                                        // one row of three empty lists and 0.0 (:2953-2960)
+    const bool multi_src = sources.size() > 1, multi_sink = targets.size() > 1;
+    // identity ids when nothing was filtered out and no id is a tombstone, else the sorted distinct ends (:2965-3102)
+    const bool identity = !filtered && g.deleted_nodes_count() == 0;
+    std::vector<u64> compact_to_id;
+    std::unordered_map<u64, u64> id_to_compact;
+    u64 base = g.node_cap();
+    if (!identity) {
+        compact_to_id.assign(sources.begin(), sources.end());
+        compact_to_id.insert(compact_to_id.end(), targets.begin(), targets.end());
+        for (const Arc& a : arcs) { compact_to_id.push_back(a.src); compact_to_id.push_back(a.dst); }
+        std::sort(compact_to_id.begin(), compact_to_id.end());
+        compact_to_id.erase(std::unique(compact_to_id.begin(), compact_to_id.end()), compact_to_id.end());
+        for (u64 k = 0; k < compact_to_id.size(); ++k) id_to_compact[compact_to_id[k]] = k;
+        base = compact_to_id.size();
+    }
+    auto compact = [&](u64 id) { return identity ? id : id_to_compact.at(id); };
+    for (u64 v : sources)
+        if (identity && v >= base) throw std::invalid_argument("algo.maxFlow: a source node is not in the graph");
+    for (u64 v : targets)
+        if (identity && v >= base) throw std::invalid_argument("algo.maxFlow: a target node is not in the graph");
+    const u64 super_src = base, super_sink = base + (multi_src ? 1 : 0);
+    const u64 total = base + (multi_src ? 1 : 0) + (multi_sink ? 1 : 0);
+    std::vector<u64> rows, cols, bits;
+    std::vector<const Arc*> kept;                                        // the arcs with capacity > 0, in tensor order
+    double min_cap = std::numeric_limits<double>::infinity(), max_cap = 0.0;
+    auto add = [&](u64 u, u64 v, double c) {
+        u64 b;
+        memcpy(&b, &c, sizeof b);
+        rows.push_back(u); cols.push_back(v); bits.push_back(b);
+    };
+    for (const Arc& a : arcs) {
+        if (!(a.cap > 0.0)) continue;
+        add(compact(a.src), compact(a.dst), a.cap);
+        kept.push_back(&a);
+        if (a.cap < min_cap) min_cap = a.cap;
+        if (a.cap > max_cap) max_cap = a.cap;
+    }
+    const double big = 2147483647.0;                                     // i32::MAX
+    u64 src_id = compact(sources[0]), sink_id = compact(targets[0]);
+    if (multi_src) {
+        src_id = super_src;
+        std::unordered_set<u64> once;                                    // (a node listed twice hangs under it once)
+        for (u64 v : sources)
+            if (once.insert(v).second) add(src_id, compact(v), big);
+    }
+    if (multi_sink) {
+        sink_id = super_sink;
+        std::unordered_set<u64> once;
+        for (u64 v : targets)
+            if (once.insert(v).second) add(compact(v), sink_id, big);
+    }
+    if (std::isfinite(min_cap) && max_cap >= min_cap * 4294967295.0)     // :3104-3110
+        throw std::invalid_argument("algo.maxFlow: capacity range too wide: the largest capacity is at least 2^32 - 1 times the "
+                                    "smallest, which the solver's arithmetic cannot keep apart");
+    Matrix cap(g.ctx(), Type::UInt64, total, total);
+    if (!rows.empty()) cap.build(rows, cols, &bits);                     // (every position once: no multi-edge, super arcs once)
+    u64 *fr = nullptr, *fc = nullptr, k = 0;
+    double* fv = nullptr;
+    check(fgpu_maxflow(g.ctx().raw(), cap.snapshot(), src_id, sink_id, &res.max_flow, &fr, &fc, &fv, &k, nullptr), "LAGr_MaxFlow");
+    std::unordered_map<u64, double> flow_of;                             // (row << 32 | col) -> flow; ids fit 32 bits (fgpu_maxflow)
+    flow_of.reserve(k * 2);
+    for (u64 i = 0; i < k; ++i) flow_of[(fr[i] << 32) | fc[i]] = fv[i];
+    fgpu_free(g.ctx().raw(), fr);
+    fgpu_free(g.ctx().raw(), fc);
+    fgpu_free(g.ctx().raw(), fv);
+    std::set<u64> used;
+    for (const Arc* a : kept) {                                          // :3218-3232
+        const auto it = flow_of.find((compact(a->src) << 32) | compact(a->dst));
+        if (it == flow_of.end() || it->second == 0.0) continue;
+        used.insert(a->src);
+        used.insert(a->dst);
+        res.edges.push_back(a->edge);
+        res.flows.push_back(it->second);
+    }
+    res.nodes.assign(used.begin(), used.end());
     return res;
 }
 

@@ -654,4 +654,23 @@ struct MsfResult {
 MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types, bool maximize,
                    const u64* edge_ids, const double* weights, u64 n_weights);
 
+struct MaxFlowResult {
+    std::vector<u64> nodes;      // ascending endpoints of the relationships with non-zero flow
+    std::vector<u64> edges;      // those relationships, in the order Tensor::iter_edges yields the type's edges
+    std::vector<double> flows;   // their flows
+    double max_flow = 0.0;
+};
+// algo.maxFlow (runtime/functions/algo_procedures.rs:2786-3248).  Exactly one relationship type, which must exist and hold no
+// multi-edge; sources / targets non-empty and disjoint; labels empty = all nodes, else an edge counts when both its ends carry
+// one of the labels.  The host mirror has no attribute store: the capacity attribute arrives as (edge_ids[k], caps[k]),
+// k < n_caps, has_attribute says whether the graph knows the attribute name at all.  A relationship whose listed capacity is
+// >= 0 uses it; any other relationship (not listed, negative, NaN) uses default_capacity when has_default, else the call fails.
+// Capacities <= 0 are dropped before the solve; max >= min * (2^32 - 1) over the positive ones fails.  Node ids are used as
+// they are when there is no label filter and no deleted node, else they are compacted (sorted distinct ends, sources and
+// targets); several sources (targets) hang under a super-source (-sink) by arcs of 2^31 - 1, which never show in the result.
+// The flow is fgpu_maxflow's: the value is unique, the assignment is one of the maximum flows.
+MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
+                           const std::vector<u64>& sources, const std::vector<u64>& targets, bool has_attribute,
+                           const u64* edge_ids, const double* caps, u64 n_caps, bool has_default, double default_capacity);
+
 }  // namespace falkor

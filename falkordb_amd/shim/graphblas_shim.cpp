@@ -115,7 +115,7 @@ void take_vector(falkor::ByteReader& r, GB_Vector_opaque* v) {
 }
 constexpr char BLOB_IDS[8] = {'F', 'G', 'I', 'D', 'L', 'S', 'T', '1'};   // = serialize.cpp PLAIN_MAGIC: BOOL vector, the set indices
 constexpr char BLOB_U64[8] = {'F', 'G', 'V', 'E', 'C', 'U', '6', '4'};   // UINT64 vector: length, count, (index, value) pairs
-GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2}, op_oneb_bool{3}, op_min_fp64{4};
+GB_BinaryOp_opaque op_any_bool{0}, op_second_u64{1}, op_any_u64{2}, op_oneb_bool{3}, op_min_fp64{4}, op_max_fp64{5};
 const GrB_Index all_indices = 0;   // what GrB_ALL points at: only its address is looked at
 GB_UnaryOp_opaque op_one_bool{0};
 GB_Semiring_opaque sr_any_pair_bool{0};
@@ -197,6 +197,7 @@ GB_Type_opaque* type_int32() { return &t_i32; }
 GB_Type_opaque* type_int64() { return &t_i64; }
 GB_Type_opaque* type_fp32() { return &t_f32; }
 GB_Type_opaque* type_fp64() { return &t_f64; }
+GB_Type_opaque* type_bool() { return &t_bool; }
 GB_Vector_opaque* vector_over_pinned(GB_Type_opaque* type, GrB_Index n, void* pinned, int absent) {
     GB_Vector_opaque* v = vec_new(type, n);
     v->data = pinned; v->nbytes = n * type->size; v->nstored = n; v->absent = absent;
@@ -225,6 +226,7 @@ GrB_Type GrB_INT64 = &t_i64;
 GrB_Type GrB_FP32 = &t_f32;
 GrB_Type GrB_FP64 = &t_f64;
 GrB_BinaryOp GrB_MIN_FP64 = &op_min_fp64;            // algo.MSF's weighted build (mod.rs:1964)
+GrB_BinaryOp GrB_MAX_FP64 = &op_max_fp64;            // algo.maxFlow's capacity build (algo_procedures.rs:3141-3148)
 
 // the 31 predefined descriptors (mod.rs:424-612; matrix.rs:313-351 maps all of them): R = replace, S = structural mask,
 // C = complemented mask, T0 / T1 = transpose the first / second input
@@ -270,7 +272,7 @@ GrB_Info GxB_Global_Option_set_INT32(int, int32_t) { return ctx() ? GrB_SUCCESS 
 GrB_Info GrB_Scalar_new(GrB_Scalar* s, GrB_Type type) {
     if (!s || !type) return GrB_NULL_POINTER;
     if (type != GrB_BOOL) return GrB_NOT_IMPLEMENTED;
-    *s = new (std::nothrow) GB_Scalar_opaque{false, false};
+    *s = new (std::nothrow) GB_Scalar_opaque{false, false, type, 0};
     return *s ? GrB_SUCCESS : GrB_OUT_OF_MEMORY;
 }
 GrB_Info GrB_Scalar_setElement_BOOL(GrB_Scalar s, bool x) {
@@ -408,12 +410,13 @@ GrB_Info GrB_Matrix_extractElement_UINT64(uint64_t* x, GrB_Matrix A, GrB_Index i
 }
 // ---- GrB_FP64 matrices (mod.rs:9609, 9765, 9877, 10021): what algo.MSF builds, hands to LAGraph_msf and reads back ----------
 // The values travel as binary64 bit patterns in a UINT64 matrix (GB_Matrix_opaque::fp64); nvals / wait / free / resize / dup
-// work on it like on any other matrix.  dup: NULL (a duplicate is GrB_INVALID_VALUE, as the specification has it) or GrB_MIN_FP64.
+// work on it like on any other matrix.  dup: NULL (a duplicate is GrB_INVALID_VALUE, as the specification has it), GrB_MIN_FP64
+// (algo.MSF) or GrB_MAX_FP64 (algo.maxFlow).
 GrB_Info GrB_Matrix_build_FP64(GrB_Matrix C, const GrB_Index* I, const GrB_Index* J, const double* X, GrB_Index nvals,
                                GrB_BinaryOp dup) {
     if (!C || (nvals && (!I || !J || !X))) return GrB_NULL_POINTER;
     if (!C->fp64) return GrB_DOMAIN_MISMATCH;
-    if (dup && dup != GrB_MIN_FP64) return GrB_NOT_IMPLEMENTED;
+    if (dup && dup != GrB_MIN_FP64 && dup != GrB_MAX_FP64) return GrB_NOT_IMPLEMENTED;
     for (GrB_Index k = 0; k < nvals; ++k)
         if (I[k] >= C->m.nrows() || J[k] >= C->m.ncols()) return GrB_INDEX_OUT_OF_BOUNDS;
     return guarded([&]() -> GrB_Info {
@@ -423,7 +426,7 @@ GrB_Info GrB_Matrix_build_FP64(GrB_Matrix C, const GrB_Index* I, const GrB_Index
             auto [it, fresh] = seen.try_emplace({I[k], J[k]}, X[k]);
             if (fresh) continue;
             if (!dup) return GrB_INVALID_VALUE;
-            if (X[k] < it->second) it->second = X[k];
+            if (dup == GrB_MAX_FP64 ? X[k] > it->second : X[k] < it->second) it->second = X[k];
         }
         std::vector<uint64_t> r, c, v;
         r.reserve(seen.size()); c.reserve(seen.size()); v.reserve(seen.size());

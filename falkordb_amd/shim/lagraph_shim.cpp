@@ -1,6 +1,6 @@
 // lagraph_shim.cpp — the LAGraph-named part of the tier-2 boundary: `liblagraph.so` / `liblagraphx.so`,
 // exporting the LAGraph entry points the reference's BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality /
-// MSF procedures bind, on the MI355X engine.
+// MSF / maxFlow procedures bind, on the MI355X engine.
 // With them next to libgraphblas.so (graphblas_shim.cpp) the reference's UNMODIFIED call sequences run on the GPU:
 //   algo.BFS       algo_procedures.rs:1060-1165  LAGraph_New (borrowed adjacency, :389-405) -> LAGr_BreadthFirstSearch_Extended
 //                  (lagraphx_bindings.rs:585-594; level, parent|NULL, src, max_level, -1, false) -> GrB_Vector_nvals +
@@ -21,15 +21,16 @@
 //                  GrB_Vector_extractTuples_INT64 on componentId.  The UDT scoring pipeline in front of the call (GrB_Type_new,
 //                  index-unary operators with host callbacks, UDT monoids, :1403-1701) is not part of this boundary: that pair
 //                  reduction is what the host layer's algo_msf does
+//   algo.maxFlow   algo_procedures.rs:3112-3216  GrB_Matrix_new(GrB_FP64) + GrB_Matrix_build_FP64(GrB_MAX_FP64) + GrB_Matrix_wait ->
+//                  LAGraph_New(DIRECTED) -> LAGraph_Cached_AT + LAGraph_Cached_EMin -> LAGr_MaxFlow(&f, &flow_mtx, NULL, G, src,
+//                  sink) (lagraphx_bindings.rs:610-618) -> GrB_Matrix_nvals + GrB_Matrix_extractTuples_FP64 on the flow matrix
 //   matrix::init / shutdown  matrix.rs:174-183, 215-221  LAGraph_Init after GxB_init, LAGraph_Finalize
 // LAGraph itself is an un-vendored dependency (build.rs:50-52 links prebuilt static archives); what is restated here is its
 // published contract as the bindings' own doc comments state it (argument meaning, cached-property rules, return codes:
 // lagraph_bindings.rs:23-31) — the algorithms are the engine's fgpu_bfs / fgpu_pagerank / fgpu_wcc / fgpu_betweenness /
-// fgpu_cdlp / fgpu_harmonic / fgpu_msf, pinned against the oracle (WCC, betweenness, CDLP, harmonic centrality and MSF against
-// the checkers of their tests).  The two other LAGraph entry points algo_procedures.rs calls (max-flow and the EMin property) are
-// outside this engine's path
-// (out of scope): they are exported so the file links, and return GrB_NOT_IMPLEMENTED with a message instead of
-// computing anything.
+// fgpu_cdlp / fgpu_harmonic / fgpu_msf / fgpu_maxflow, pinned against the oracle (WCC, betweenness, CDLP, harmonic centrality, MSF
+// and max flow against the checkers of their tests).  Every LAGraph entry point algo_procedures.rs calls computes: none answers
+// GrB_NOT_IMPLEMENTED for the forms the procedures send.
 //
 // One source, two libraries: -DFG_LAGRAPHX builds the LAGraphX (experimental) symbols, without it the LAGraph core ones.
 #include "shim_internal.hpp"
@@ -319,9 +320,26 @@ int LAGr_Betweenness(GrB_Vector* centrality, LAGraph_Graph G, const GrB_Index* s
         return GrB_SUCCESS;
     });
 }
-// ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality / MSF only)")
-int LAGraph_Cached_EMin(LAGraph_Graph, char* msg) { FG_NOT_ON_PATH(LAGraph_Cached_EMin); }
+// LAGraph_Cached_EMin (lagraph_bindings.rs:233-237) as algo.maxFlow calls it (algo_procedures.rs:3159): G->emin = a scalar of
+// A's type holding the smallest stored value of A, emin_state = LAGraph_VALUE; left alone when it exists already.  The
+// reduction runs on the device (fgpu_mat_min_val).  An A without entries has no smallest entry: the property stays unknown.
+// A of a type other than GrB_FP64 / GrB_BOOL is GrB_NOT_IMPLEMENTED (UINT64 matrices carry edge ids, not weights).
+int LAGraph_Cached_EMin(LAGraph_Graph G, char* msg) {
+    clear_msg(msg);
+    if (const int r = check_graph(G, msg)) return r;
+    if (G->emin) return GrB_SUCCESS;
+    const bool is_bool = G->A->m.type() == Type::Bool;
+    if (!G->A->fp64 && !is_bool) return fail(msg, GrB_NOT_IMPLEMENTED, "LAGraph_Cached_EMin: A must be a GrB_FP64 or GrB_BOOL matrix");
+    return guarded(msg, [&]() -> int {
+        uint64_t bits = 0;
+        int found = 0;
+        check(fgpu_mat_min_val(fgshim::context()->raw(), G->A->m.snapshot(), &bits, &found), "LAGraph_Cached_EMin");
+        if (!found) return GrB_SUCCESS;
+        G->emin = new GB_Scalar_opaque{true, is_bool, is_bool ? fgshim::type_bool() : fgshim::type_fp64(), is_bool ? 1 : bits};
+        G->emin_state = 0;   // LAGraph_VALUE
+        return GrB_SUCCESS;
+    });
+}
 #else
 // ---- LAGraphX -----------------------------------------------------------------------------------------------------------
 // LAGr_BreadthFirstSearch_Extended (lagraphx_bindings.rs:585-594) as algo.BFS calls it (algo_procedures.rs:1079-1088):
@@ -418,13 +436,53 @@ int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable_nodes, LAG
         return GrB_SUCCESS;
     });
 }
-// ---- outside the engine's path: exported so algo_procedures.rs links, loud when called --------------------------------------
-#define FG_NOT_ON_PATH(NAME) return fail(msg, GrB_NOT_IMPLEMENTED, #NAME ": not provided by the MI355X engine (traversal / BFS / PageRank / WCC / betweenness / labelPropagation / HarmonicCentrality / MSF only)")
-int LAGr_MaxFlow(double* f, GrB_Matrix* flow, GrB_Matrix* res, LAGraph_Graph, GrB_Index, GrB_Index, char* msg) {
-    if (f) *f = 0;
-    if (flow) *flow = nullptr;
-    if (res) *res = nullptr;
-    FG_NOT_ON_PATH(LAGr_MaxFlow);
+// LAGr_MaxFlow (lagraphx_bindings.rs:610-618) as algo.maxFlow calls it (algo_procedures.rs:3161-3170): G holds a GrB_FP64 (or
+// GrB_BOOL: capacity 1.0) adjacency of capacities over compact node ids.  An Advanced method — G->AT and G->emin must be cached
+// (LAGRAPH_NOT_CACHED otherwise, as LAGr_PageRank treats its properties; the engine builds its own residual network and reads
+// neither, and an A without entries has no emin to cache).  *f = the value of a maximum src -> sink flow; *flow_mtx (nullable)
+// an n x n GrB_FP64 matrix of the positive flows (fgpu_maxflow; include/fgpu.h states what that flow satisfies).  src or sink
+// out of range is GrB_INVALID_INDEX, src == sink GrB_INVALID_VALUE.  res_mtx != NULL asks for the residual matrix as well — a
+// form the procedure never sends: refused rather than guessed, as dest >= 0 is in the BFS.
+int LAGr_MaxFlow(double* f, GrB_Matrix* flow_mtx, GrB_Matrix* res_mtx, LAGraph_Graph G, GrB_Index src, GrB_Index sink, char* msg) {
+    clear_msg(msg);
+    if (flow_mtx) *flow_mtx = nullptr;
+    if (!f) return fail(msg, GrB_NULL_POINTER, "f is NULL");
+    *f = 0;
+    if (res_mtx) { *res_mtx = nullptr; return fail(msg, GrB_NOT_IMPLEMENTED, "LAGr_MaxFlow: res_mtx != NULL is not provided"); }
+    if (const int r = check_graph(G, msg)) return r;
+    if (!G->A->fp64 && G->A->m.type() != Type::Bool)
+        return fail(msg, GrB_NOT_IMPLEMENTED, "LAGr_MaxFlow: A must be a GrB_FP64 or GrB_BOOL matrix");
+    if (!(symmetric(G) ? G->A : G->AT)) return fail(msg, LAGRAPH_NOT_CACHED, "G->AT is required");
+    const uint64_t n = G->A->m.nrows();
+    if (!G->emin && G->A->m.nvals()) return fail(msg, LAGRAPH_NOT_CACHED, "G->emin is required");
+    if (src >= n || sink >= n) return fail(msg, GrB_INVALID_INDEX, "invalid source / sink node");
+    if (src == sink) return fail(msg, GrB_INVALID_VALUE, "source and sink must differ");
+    return guarded(msg, [&]() -> int {
+        falkor::Context* c = fgshim::context();
+        uint64_t *fr = nullptr, *fc = nullptr, k = 0;
+        double* fv = nullptr;
+        double value = 0;
+        check(fgpu_maxflow(c->raw(), G->A->m.snapshot(), src, sink, &value, &fr, &fc, &fv, &k, nullptr), "LAGr_MaxFlow");
+        std::unique_ptr<GB_Matrix_opaque> out;
+        try {
+            if (flow_mtx) {
+                out.reset(new GB_Matrix_opaque(Matrix(*c, Type::UInt64, n, n)));
+                out->fp64 = true;
+                if (k) {
+                    std::vector<uint64_t> bits(k);
+                    memcpy(bits.data(), fv, k * sizeof(uint64_t));
+                    out->m.build(std::vector<uint64_t>(fr, fr + k), std::vector<uint64_t>(fc, fc + k), &bits);
+                }
+            }
+        } catch (...) {
+            fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fv);
+            throw;
+        }
+        fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fv);
+        *f = value;
+        if (flow_mtx) *flow_mtx = out.release();
+        return GrB_SUCCESS;
+    });
 }
 // LAGraph_msf (lagraphx_bindings.rs:261-267) as algo.MSF calls it (algo_procedures.rs:1707-1717): A is a symmetric GrB_FP64
 // matrix over compact node ids (a BOOL matrix means every weight is 1.0), sanitize = false.  forest_edges receives an n x n

@@ -31,12 +31,16 @@ typedef int GrB_Info;
 
 struct GB_Type_opaque { int code; const char* name; size_t size; };   // 0 = BOOL, 1 = UINT64; 2.. = the integer types a
                                                                        // GxB_Container's p / h / i / b vectors come in
-struct GB_BinaryOp_opaque { int code; };        // 0 = ANY_BOOL, 1 = SECOND_UINT64, 2 = ANY_UINT64, 3 = ONEB_BOOL, 4 = MIN_FP64
+struct GB_BinaryOp_opaque { int code; };        // 0 = ANY_BOOL, 1 = SECOND_UINT64, 2 = ANY_UINT64, 3 = ONEB_BOOL, 4 = MIN_FP64, 5 = MAX_FP64
 struct GB_UnaryOp_opaque { int code; };         // 0 = ONE_BOOL
 struct GB_Semiring_opaque { int code; };        // 0 = ANY_PAIR_BOOL
 struct GB_Descriptor_opaque { bool replace, structural, complement, t0, t1; };
 struct GB_Global_opaque { int dummy; };
-struct GB_Scalar_opaque { bool has; bool value; };
+struct GB_Scalar_opaque {
+    bool has; bool value;                       // the BOOL scalar of GxB_Matrix_build_Scalar
+    GB_Type_opaque* type = nullptr;             // a cached LAGraph property (G->emin): its type (BOOL: `value`, FP64: `bits`)
+    uint64_t bits = 0;
+};
 struct GB_Matrix_opaque {
     Matrix m;
     int32_t sparsity_control = 3;   // GxB_HYPERSPARSE | GxB_SPARSE
@@ -111,6 +115,7 @@ GB_Type_opaque* type_int32();
 GB_Type_opaque* type_int64();
 GB_Type_opaque* type_fp32();
 GB_Type_opaque* type_fp64();
+GB_Type_opaque* type_bool();
 // a vector of n entries over a pinned result block of the engine (fgpu_host_alloc; released with fgpu_free): absent == 0
 // every entry is stored, 1: negative entries are absent (BFS level / parent), 2: zero entries are absent (degrees)
 GB_Vector_opaque* vector_over_pinned(GB_Type_opaque* type, GrB_Index n, void* pinned, int absent);

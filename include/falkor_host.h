@@ -248,6 +248,29 @@ int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize
                 uint64_t n_weights, uint64_t* n_trees, uint64_t** node_off, uint64_t** nodes, uint64_t** edge_off,
                 uint64_t** edges);
 
+/* algo.maxFlow (algo_procedures.rs:2786-3248; LAGr_MaxFlow through lagraphx_bindings.rs:610-618 is fgpu_maxflow, whose comment
+ * in fgpu.h states what the returned flow satisfies): labels = a comma list, "" / NULL = all nodes, else a relationship counts
+ * when both its ends carry one of the labels; types = exactly one relationship type.  sources / targets: the node ids of
+ * sourceNodes / targetNodes.  The host mirror has no attribute store, so the capacity attribute is data: caps[k] is the
+ * attribute of relationship edge_ids[k], k < n_caps (an Int attribute widened by the caller; a value that is no number is left
+ * out); has_attribute = 0 means the graph does not know the attribute name at all.  A relationship whose listed capacity is
+ * >= 0 uses it, every other one uses default_capacity when has_default != 0.  Failures, each with a message that holds the
+ * quoted phrase: not exactly one type; an unknown type; a type with "multi-edges"; an empty source or target list ("expects at
+ * least one source"); overlapping sets ("disjoint"); a relationship without a usable capacity and no default ("invalid or
+ * missing attribute"); max >= min * (2^32 - 1) over the positive capacities ("capacity range too wide").
+ * The relationships are the type's effective edges (pending additions and deletions applied); capacities <= 0 are dropped
+ * before the solve; no surviving relationship gives three empty lists and 0.0.  Node ids are used as they are when there is no
+ * label filter and no deleted node, otherwise compacted; several sources (targets) hang under a super-source (-sink) by arcs of
+ * 2^31 - 1, which never appear in the result.
+ * Result: nodes = the ascending ends of the relationships with non-zero flow; edges / flows = those relationships and their
+ * flows in the order the tensor's edge iteration yields the type's edges — Tensor::iter_edges (tensor.rs:920-933) walks the
+ * effective forward matrix row-major, and a type without multi-edges has nothing behind it: ascending (source id, target id);
+ * *max_flow = the value.  The value is unique, the assignment is one of the maximum flows.  Free the three with fh_free. */
+int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const uint64_t* sources, uint64_t n_sources,
+                    const uint64_t* targets, uint64_t n_targets, int has_attribute, const uint64_t* edge_ids, const double* caps,
+                    uint64_t n_caps, int has_default, double default_capacity, uint64_t** nodes, uint64_t* n_nodes,
+                    uint64_t** edges, double** flows, uint64_t* n_edges, double* max_flow);
+
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
  * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).

@@ -509,6 +509,45 @@ fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* active_bitm
                    uint64_t** forest_rows, uint64_t** forest_cols, double** forest_weights, uint64_t* n_forest,
                    uint64_t stats[4]);
 
+/* Maximum flow (synchronous push-relabel): replaces LAGr_MaxFlow(&f, &flow_mtx, NULL, G, src, sink, msg) as called by
+ * algo.maxFlow (algo_procedures.rs:2786-3248, the call at 3112-3216) with an FP64 capacity matrix over compact node ids.
+ * LAGraph's source is not vendored; these are the rules:
+ *   - C is square; C(u, v) is the capacity of the arc u -> v.  A valued snapshot holds one IEEE-754 binary64 BIT PATTERN per
+ *     entry in its uint64 value; a BOOL snapshot means every capacity is 1.0.  A hypersparse C is accepted;
+ *   - a diagonal entry, and an entry whose capacity is <= 0 (-0.0 included), carries no flow and is ignored;
+ *   - a NaN or infinite capacity anywhere in C is FGPU_INVALID: inf - inf must never reach a residual;
+ *   - there is no active bitmap: the caller compacts the node ids, as the reference does.
+ * *max_flow = the value of a maximum src -> sink flow.  The three engine-owned arrays (released with fgpu_free, pinned from
+ * 256 KiB up like fgpu_msf's forest arrays; NULL when empty) hold one entry per arc of C that carries flow > 0, sorted
+ * ascending by (row, col).  What comes back is a FLOW, not a preflow:
+ *   - 0 < f(u, v) <= C(u, v) for every returned entry;
+ *   - inflow = outflow at every vertex other than src and sink;
+ *   - the net outflow of src = the net inflow of sink = *max_flow;
+ *   - where both C(u, v) and C(v, u) exist, at most one of the two carries flow.
+ * The VALUE is unique.  The ASSIGNMENT is not: which maximum flow comes back depends on the order the kernels' atomics land
+ * in and may differ from run to run; every one of them satisfies the rules above.
+ * Arithmetic is FP64 throughout, sums and differences of capacities only.  Every operation is EXACT when all capacities are
+ * integers, or dyadic rationals with a common exponent, and their sum stays below 2^53 (in units of that exponent): then the
+ * rules above hold with equality, bit for bit.  Otherwise they hold to the rounding of the sums (conservation to a few ulps
+ * of the largest capacity per arc of the vertex).
+ * No path from src to sink: 0.0 and *n_flow = 0.
+ * stats (nullable): [0] push / relabel pulses that had an active vertex, [1] global relabels, [2] arcs of the residual network
+ * (two per unordered pair of vertices joined by a live arc), [3] pushes.
+ * Errors: NULL ctx / C / max_flow / n_flow / any of the three flow outputs: FGPU_NULL_POINTER; non-square C:
+ * FGPU_DIM_MISMATCH; src or sink >= nrows, src == sink, nrows >= 2^32 - 1, nnz >= 2^31 - 2^24 (the residual
+ * network holds up to 2 nnz entries at 32-bit positions): FGPU_INVALID.  The pulse loop has
+ * a hard cap of 4 (n^2 + n) pulses — beyond the relabel bound of the algorithm, never reached by a correct run — past which
+ * the call returns FGPU_INVALID with a message instead of running on.  fgpu_set_option "maxflow_global_every": pulses between
+ * two global relabels (0 = the built-in choice). */
+fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src, uint64_t sink, double* max_flow,
+                       uint64_t** flow_rows, uint64_t** flow_cols, double** flow_vals, uint64_t* n_flow,
+                       uint64_t stats[4]);
+
+/* The smallest stored value of A under the order of fgpu_msf's K (the IEEE totalOrder with -0.0 = +0.0), as a binary64 bit
+ * pattern (LAGraph_Cached_EMin).  *found = 0 when A has no entry; a BOOL snapshot answers 1.0.  A device reduction: no entry
+ * visits the host. */
+fgpu_info fgpu_mat_min_val(fgpu_ctx* ctx, const fgpu_mat* A, uint64_t* bits, int* found);
+
 /* Betweenness centrality (batched Brandes): replaces LAGr_Betweenness(&centrality, G, sources, ns, msg) as called by
  * algo.betweenness (algo_procedures.rs:884-1017; binding lagraph_bindings.rs:539-546).  centrality[v] = the sum over the
  * sources s of delta_s(v) = sum over out-neighbours w of v with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),

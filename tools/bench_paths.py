@@ -360,6 +360,61 @@ def bench_msf(ctx, scale):
                                   "wcc_mode 2, on the same pattern"}), flush=True)
 
 
+def bench_maxflow(ctx, scale, sweep=False):
+    """fgpu_maxflow on the directed R-MAT graph with integer capacities 1..100, a fixed hash of (row, col); src = the vertex with
+    the most out-entries, sink = the one with the most in-entries among the rest.  For scale, from the same run: one full-pass
+    boolean vxm (every frontier bit set) and one fgpu_bfs from src over the same matrix.  sweep: the pulses between two global
+    relabels (maxflow_global_every) over 8 .. 1024 instead of the built-in choice."""
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.repeat(np.arange(n, dtype=np.uint64), deg)
+    h = (rows * np.uint64(n) + ci) * np.uint64(0x9E3779B97F4A7C15)   # (mod 2^64)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(32)
+    caps = ((h >> np.uint64(11)) % np.uint64(100) + np.uint64(1)).astype(np.float64)
+    Cm = ctx.mat_from_coo(n, n, rows, ci, caps.view(np.uint64))
+    src = int(np.argmax(deg))
+    indeg = np.bincount(ci.astype(np.int64), minlength=n)
+    indeg[src] = -1
+    sink = int(np.argmax(indeg))
+    del rp, ci, rows, h, caps
+    At = A.transpose()
+    nnz = A.nvals
+    full = np.full((n + 63) // 64, ~np.uint64(0), dtype=np.uint64)
+    if n % 64:
+        full[-1] = np.uint64((1 << (n % 64)) - 1)
+    t_vxm, _ = timed(ctx, lambda: engine.vxm(ctx, full, None, A, At), reps=5, warm=1)
+    level = ctx.host_array(n, np.int32)
+    t_bfs, _ = timed(ctx, lambda: engine.bfs(ctx, A, At, src, -1, want_parent=False, level_out=level), reps=5, warm=1)
+    # the fixed part of a call: the same matrix from a vertex without any entry — the residual network is built, the labels are
+    # set by one global relabel, one empty batch of pulses runs, nothing flows
+    lone = np.nonzero((deg == 0) & (indeg == 0))[0]
+    t_fixed = None
+    if len(lone):
+        t_fixed, r0 = timed(ctx, lambda: engine.maxflow(ctx, Cm, int(lone[0]), sink), reps=3, warm=1)
+        assert r0[0] == 0.0
+    for k in ((8, 16, 32, 64, 128, 256, 1024) if sweep else (0,)):
+        ctx.set_option("maxflow_global_every", k)
+        t, res = timed(ctx, lambda: engine.maxflow(ctx, Cm, src, sink, stats=True), reps=3, warm=1)
+        st = res[4]
+        print(json.dumps({"path": "maxflow", "scale": scale, "n": n, "nnz": nnz, "src": src, "sink": sink,
+                          "out_degree_src": int(deg[src]), "in_degree_sink": int(indeg[sink]), "maxflow_global_every": k,
+                          "ms": round(t * 1e3, 3), "value": res[0], "flow_entries": len(res[1]), "pulses": st[0],
+                          "global_relabels": st[1], "residual_arcs": st[2], "pushes": st[3],
+                          "Mpushes_per_s": round(st[3] / t / 1e6, 2), "full_vxm_ms": round(t_vxm * 1e3, 3),
+                          "bfs_ms": round(t_bfs * 1e3, 3),
+                          "ms_call_without_flow": round(t_fixed * 1e3, 3) if t_fixed is not None else None,
+                          "note": "host clock around a synchronised call, median of 3 after 1 warm-up (the residual network is "
+                                  "built inside every call); call_without_flow = the same call from a vertex without entries: "
+                                  "network build + one global relabel + one empty batch of pulses; pushes per second over the whole call; vxm = fgpu_vxm with every "
+                                  "frontier bit set, bfs = fgpu_bfs from src, levels only, both median of 5; no outside number "
+                                  "exists to compare with"}), flush=True)
+    ctx.set_option("maxflow_global_every", 0)
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -438,6 +493,10 @@ if __name__ == "__main__":
     if what in ("msf", "all"):
         c = engine.Context(0)
         bench_msf(c, scale if scale else 22)
+        c.close()
+    if what in ("maxflow", "maxflow_sweep", "all"):
+        c = engine.Context(0)
+        bench_maxflow(c, scale if scale else 22, sweep=what == "maxflow_sweep")
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
