@@ -325,12 +325,6 @@ __global__ __launch_bounds__(256) void bc_reduce_kernel(BcDev s, u32 nb, u32 n, 
     }
 }
 
-static u32 bc_grid(fgpu_ctx* ctx, u64 threads) {
-    const u64 g = (threads + 255) / 256;
-    const u64 cap = (u64)ctx->cus * 16;
-    return (u32)(g < 1 ? 1 : (g < cap ? g : cap));
-}
-
 static u32 bc_log2_group(u32 B) {
     u32 lg = 0;
     while ((1u << lg) < B) ++lg;
@@ -421,7 +415,7 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
         const u64* a = act.p;
         const CsrView va = view_of(A);
         const CsrView vat = At ? view_of(At) : va;
-        const u32 ggrid = bc_grid(ctx, (u64)n * G);
+        const u32 ggrid = capped_grid(ctx, (u64)n * G, 256, 16);
         const u32 hgA = hub_grid(ctx, A), hgAt = At ? hub_grid(ctx, At) : 0;
         for (u64 first = 0; first < nsrc; first += B) {
             const u32 nb = (u32)(nsrc - first < B ? nsrc - first : B);
@@ -483,12 +477,12 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
                     hipLaunchKernelGGL(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
                                        A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3);
                     FGPU_HIP(hipGetLastError());
-                    hipLaunchKernelGGL(bc_back_hub_finish_kernel, dim3(bc_grid(ctx, (u64)A->n_hub_chunks * G)), dim3(256), 0,
+                    hipLaunchKernelGGL(bc_back_hub_finish_kernel, dim3(capped_grid(ctx, (u64)A->n_hub_chunks * G, 256, 16)), dim3(256), 0,
                                        ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p);
                     FGPU_HIP(hipGetLastError());
                 }
             }
-            hipLaunchKernelGGL(bc_reduce_kernel, dim3(bc_grid(ctx, n)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p);
+            hipLaunchKernelGGL(bc_reduce_kernel, dim3(capped_grid(ctx, n, 256, 16)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p);
             FGPU_HIP(hipGetLastError());
         }
         u64 back = 0;

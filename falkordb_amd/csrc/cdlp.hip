@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void cdlp_fill_kernel(const u32* __restrict__ 
             u32 at = 0;
             if (lane == first) at = atomicAdd(&cursor[k - 1], (u32)__builtin_popcountll(m));
             at = __shfl(at, first, 64);
-            if (b == k) rows[ls.off[k - 1] + at + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (u32)v;
+            if (b == k) rows[ls.off[k - 1] + at + wave_slot(m, lane)] = (u32)v;
         }
     }
 }
@@ -368,16 +368,11 @@ __global__ __launch_bounds__(256) void cdlp_popcount_kernel(const u32* __restric
     block_add_u64(c, dst);
 }
 
-static u32 cdlp_grid(fgpu_ctx* ctx, u64 blocks) {
-    const u64 cap = (u64)ctx->cus * 8;
-    return (u32)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
-}
-
 template <u32 G>
 static void cdlp_launch_short(fgpu_ctx* ctx, CsrView a, const u64* act, const u32* in, u32* out, const u32* rows, u32 count,
                               const unsigned long long* prev, unsigned long long* chg) {
     if (!count) return;
-    hipLaunchKernelGGL(cdlp_short_kernel<G>, dim3(cdlp_grid(ctx, cdiv(count, 256 / G))), dim3(256), 0, ctx->stream(), a, act, in,
+    hipLaunchKernelGGL(cdlp_short_kernel<G>, dim3(capped_grid(ctx, count, 256 / G, 8)), dim3(256), 0, ctx->stream(), a, act, in,
                        out, rows, count, prev, chg);
 }
 
@@ -412,7 +407,7 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
     FGPU_TRY(mark.alloc(ctx, mark_words));
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, 8 * sizeof(unsigned long long), st));
     FGPU_HIP(hipMemsetAsync(mark.p, 0, (size_t)mark_words * sizeof(u32), st));
-    const u32 vgrid = cdlp_grid(ctx, cdiv(n, 256));
+    const u32 vgrid = capped_grid(ctx, n, 256, 8);
     hipLaunchKernelGGL(cdlp_init_kernel, dim3(vgrid), dim3(256), 0, st, lab.p, n);
     FGPU_HIP(hipGetLastError());
     u32* buf[2] = {lab.p, lab.p + n};
@@ -444,7 +439,7 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
             FGPU_TRY(clen.alloc(ctx, nch));
             FGPU_TRY(coff.alloc(ctx, nch));
             FGPU_TRY(hubmem.alloc(ctx, hub_words));
-            hipLaunchKernelGGL(cdlp_chunk_len_kernel, dim3(cdlp_grid(ctx, cdiv(nch, 256))), dim3(256), 0, st,
+            hipLaunchKernelGGL(cdlp_chunk_len_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st,
                                (const u32*)S->hub_chunks, nch, clen.p);
             FGPU_HIP(hipGetLastError());
             FGPU_TRY(scan_u32(ctx, clen.p, coff.p, nch, nullptr));
@@ -471,14 +466,14 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
                 cdlp_launch_short<32>(ctx, sv, a, src, dst, rows.p + ls.off[2], ls.off[3] - ls.off[2], prev, c);
                 cdlp_launch_short<64>(ctx, sv, a, src, dst, rows.p + ls.off[3], ls.off[4] - ls.off[3], prev, c);
                 if (const u32 nmid = ls.off[5] - ls.off[4])
-                    hipLaunchKernelGGL(cdlp_mid_kernel, dim3(cdlp_grid(ctx, nmid)), dim3(256), 0, st, sv, a, src, dst,
+                    hipLaunchKernelGGL(cdlp_mid_kernel, dim3(capped_grid(ctx, nmid, 1, 8)), dim3(256), 0, st, sv, a, src, dst,
                                        (const u32*)(rows.p + ls.off[4]), nmid, prev, c);
                 if (nch) {
-                    hipLaunchKernelGGL(cdlp_clear_kernel, dim3(cdlp_grid(ctx, cdiv(hub_words, 1024))), dim3(256), 0, st, hubmem.p,
+                    hipLaunchKernelGGL(cdlp_clear_kernel, dim3(capped_grid(ctx, hub_words, 1024, 8)), dim3(256), 0, st, hubmem.p,
                                        hub_words, prev);
                     hipLaunchKernelGGL(cdlp_hub_encode_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, sv.colidx, a, src, prev);
                     hipLaunchKernelGGL(cdlp_hub_reduce_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, a, prev);
-                    hipLaunchKernelGGL(cdlp_hub_pick_kernel, dim3(cdlp_grid(ctx, cdiv(nch, 256))), dim3(256), 0, st, hb, sv.rowptr,
+                    hipLaunchKernelGGL(cdlp_hub_pick_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st, hb, sv.rowptr,
                                        src, dst, prev, c);
                 }
                 FGPU_HIP(hipGetLastError());
@@ -494,7 +489,7 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
         }
     }
     hipLaunchKernelGGL(cdlp_finish_kernel, dim3(vgrid), dim3(256), 0, st, (const u32*)buf[cur], a, n, wide.p, mark.p);
-    hipLaunchKernelGGL(cdlp_popcount_kernel, dim3(cdlp_grid(ctx, cdiv(mark_words, 256))), dim3(256), 0, st, (const u32*)mark.p,
+    hipLaunchKernelGGL(cdlp_popcount_kernel, dim3(capped_grid(ctx, mark_words, 256, 8)), dim3(256), 0, st, (const u32*)mark.p,
                        mark_words, cnt.p + 7);
     FGPU_HIP(hipGetLastError());
     FGPU_TRY(ctx->d2h(label, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when label[] is pinned

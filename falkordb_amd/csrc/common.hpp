@@ -303,6 +303,33 @@ struct DevBuf {
     T* take() { T* q = p; p = nullptr; n = 0; return q; }
 };
 
+// RAII: a snapshot no other thread has seen (a temporary of one call), released on every exit.
+void mat_release(fgpu_mat* m);
+struct MatRef {
+    fgpu_mat* m = nullptr;
+    MatRef() {}   // (filled through &m by a builder)
+    explicit MatRef(fgpu_mat* take) : m(take) {}
+    MatRef(const MatRef&) = delete;
+    MatRef& operator=(const MatRef&) = delete;
+    ~MatRef() { if (m) mat_release(m); }
+};
+
+// RAII: a block of ctx->result_alloc, freed unless release() handed it to the caller.
+struct ResultBuf {
+    fgpu_ctx* ctx = nullptr;
+    void* p = nullptr;
+    ResultBuf() {}
+    ResultBuf(const ResultBuf&) = delete;
+    ResultBuf& operator=(const ResultBuf&) = delete;
+    ~ResultBuf() { if (p) ctx->host_free(p); }
+    bool alloc(fgpu_ctx* c, size_t bytes) {
+        ctx = c;
+        p = c->result_alloc(bytes);
+        return p != nullptr;
+    }
+    void* release() { void* q = p; p = nullptr; return q; }
+};
+
 }  // namespace fgpu
 
 // ---- matrix snapshot -----------------------------------------------------------

@@ -274,11 +274,6 @@ __global__ __launch_bounds__(256) void hc_finish_kernel(const double* __restrict
     block_add_u64(nz, &tot[1]);
 }
 
-static u32 hc_grid(fgpu_ctx* ctx, u64 blocks) {
-    const u64 cap = (u64)ctx->cus * 8;
-    return (u32)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
-}
-
 }  // namespace fgpu
 
 using namespace fgpu;
@@ -317,12 +312,12 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
     FGPU_HIP(hipMemsetAsync(regs.p, 0, 2 * row_bytes, st));
     FGPU_HIP(hipMemsetAsync(sc, 0, (size_t)n * sizeof(double), st));
     FGPU_HIP(hipMemsetAsync(work, 0, 4 * sizeof(unsigned long long), st));
-    const u32 vgrid = hc_grid(ctx, cdiv(n, 256));
+    const u32 vgrid = capped_grid(ctx, n, 256, 8);
     hipLaunchKernelGGL(hc_init_kernel, dim3(vgrid), dim3(256), 0, st, a, n, regs.p, est, chg.p);
     FGPU_HIP(hipGetLastError());
     uint8_t* buf[2] = {regs.p, regs.p + row_bytes};
     uint8_t* flag[2] = {chg.p, chg.p + n};
-    const u32 rgrid = hc_grid(ctx, cdiv(n, 4));   // a wave per row
+    const u32 rgrid = capped_grid(ctx, n, 4, 8);   // a wave per row
     const u32 hgrid = hub_grid(ctx, A);
     u64 iters = 0, changes = 0;
     u32 cur = 0, t = 0;   // buf[cur] and flag[cur] hold C_t and "changed in iteration t"
@@ -339,7 +334,7 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
             if (nch) {
                 hipLaunchKernelGGL(hc_hub_partial_kernel, dim3(hgrid), dim3(256), 0, st, (const u32*)A->hub_chunks, nch, av.colidx,
                                    a, src, (const uint8_t*)flag[cur], partial.p, prev, work);
-                hipLaunchKernelGGL(hc_hub_fold_kernel, dim3(hc_grid(ctx, cdiv(nch, 4))), dim3(256), 0, st,
+                hipLaunchKernelGGL(hc_hub_fold_kernel, dim3(capped_grid(ctx, nch, 4, 8)), dim3(256), 0, st,
                                    (const u32*)A->hub_chunks, nch, av.rowptr, a, src, dst, (const uint4*)partial.p, flag[cur ^ 1],
                                    est, sc, t + j + 1, prev, c, work);
             }

@@ -37,7 +37,7 @@
 // reads as >= 2n.  Levels are batched like pulses.
 // Read-out: f(a) = cap[a] - r[a] where positive — of two opposite arcs at most one is — compacted, sorted by the COO builder.
 //
-// Concurrency rules (per-XCD L2s are not coherent inside a launch; wcc.hip has the long form): inside a launch a word another
+// Concurrency rules (per-XCD L2s are not coherent inside a launch; MI355X_MICROARCH.md): inside a launch a word another
 // workgroup may write is only touched by device-scope atomics (e[], the mirror residuals, bud / took / newh, the BFS claim of
 // h[], list counters); a vertex' own budget is read by an atomic load.  Plain stores go to words with one writer in the launch
 // (r[a] of an admissible arc, h[v] of the relabelling owner, list slots handed out by the counter).  Phases are kernel
@@ -93,7 +93,7 @@ __device__ __forceinline__ void mf_append(bool yes, u32 v, u32* __restrict__ lis
     u32 base = 0;
     if (lane == 0) base = atomicAdd(cnt, (u32)__builtin_popcountll(mask));
     base = __shfl(base, 0, 64);
-    if (yes) list[base + (u32)__builtin_popcountll(mask & ((1ull << lane) - 1ull))] = v;
+    if (yes) list[base + wave_slot(mask, lane)] = v;
 }
 
 // one push of d along arc a of the owner (its r[a] is ra); true when the head has to be listed
@@ -116,12 +116,7 @@ __global__ __launch_bounds__(256) void mf_arcs_kernel(CsrView c, const u64* __re
         bool live = false;
         u32 u = 0, v = 0;
         if (i < nnz) {
-            u32 lo = 0, hi = c.nrows;   // the row u with rowptr[u] <= i < rowptr[u + 1]
-            while (hi - lo > 1) {
-                const u32 mid = (lo + hi) >> 1;
-                if (c.rowptr[mid] <= i) lo = mid; else hi = mid;
-            }
-            u = lo;
+            u = csr_row_of(c.rowptr, c.nrows, i);
             v = c.colidx[i];
             double x = 1.0;
             if (vals) {
@@ -137,7 +132,7 @@ __global__ __launch_bounds__(256) void mf_arcs_kernel(CsrView c, const u64* __re
         if (lane == 0) base = atomicAdd(&cnt[0], 2ull * (u64)__builtin_popcountll(mask));
         base = __shfl(base, 0, 64);
         if (live) {
-            const u64 at = base + 2ull * (u64)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+            const u64 at = base + 2ull * wave_slot(mask, lane);   // (an arc and its mirror)
             rows[at] = u; cols[at] = v;
             rows[at + 1] = v; cols[at + 1] = u;
         }
@@ -160,12 +155,7 @@ __device__ __forceinline__ u32 mf_find(const u32* __restrict__ rowptr, const u32
 __global__ __launch_bounds__(256) void mf_net_kernel(CsrView rv, u32 m, CsrView c, const u64* __restrict__ vals,
                                                     double* __restrict__ cap, double* __restrict__ r, u32* __restrict__ rev) {
     for (u32 a = blockIdx.x * blockDim.x + threadIdx.x; a < m; a += gridDim.x * blockDim.x) {
-        u32 lo = 0, hi = rv.nrows;
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (rv.rowptr[mid] <= a) lo = mid; else hi = mid;
-        }
-        const u32 u = lo, v = rv.colidx[a];
+        const u32 u = csr_row_of(rv.rowptr, rv.nrows, a), v = rv.colidx[a];
         double x = 0.0;
         const u32 at = mf_find(c.rowptr, c.colidx, u, v);
         if (at != MF_UNSET) {
@@ -492,41 +482,26 @@ __global__ __launch_bounds__(256) void mf_flow_kernel(CsrView rv, u32 m, const d
         if (lane == 0) base = atomicAdd(cnt, (unsigned long long)__builtin_popcountll(mask));
         base = __shfl(base, 0, 64);
         if (yes) {
-            u32 lo = 0, hi = rv.nrows;
-            while (hi - lo > 1) {
-                const u32 mid = (lo + hi) >> 1;
-                if (rv.rowptr[mid] <= a) lo = mid; else hi = mid;
-            }
-            const u64 at = base + (u64)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            rows[at] = lo;
+            const u64 at = base + wave_slot(mask, lane);
+            rows[at] = csr_row_of(rv.rowptr, rv.nrows, a);
             cols[at] = rv.colidx[a];
             vals[at] = (u64)__double_as_longlong(f);
         }
     }
 }
 
-// the sorted flow CSR -> (row, col, value) triples
-__global__ __launch_bounds__(256) void mf_emit_kernel(CsrView f, u32 k, const u64* __restrict__ vals, u64* __restrict__ orow,
-                                                     u64* __restrict__ ocol, u64* __restrict__ oval) {
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
-        u32 lo = 0, hi = f.nrows;
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (f.rowptr[mid] <= i) lo = mid; else hi = mid;
-        }
-        orow[i] = lo;
-        ocol[i] = f.colidx[i];
-        oval[i] = vals[i];
-    }
-}
+// the value of the flow entry at position i for csr_edge_list: the sorted flow CSR's own
+struct MfFlowValue {
+    const u64* vals;
+    __device__ __forceinline__ u64 operator()(u32 i, u32, u32) const { return vals[i]; }
+};
 
-// smallest stored value of a valued matrix under msf_key's order (LAGraph_Cached_EMin): a block reduce, one atomicMin per workgroup
-
+// smallest stored value of a valued matrix under fp64_sort_key's order (LAGraph_Cached_EMin): a block reduce, one atomicMin per workgroup
 __global__ __launch_bounds__(256) void mf_min_kernel(const u64* __restrict__ vals, u64 nnz, unsigned long long* best) {
     __shared__ u64 s_part[4];
     u64 key = ~0ull;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (u64)gridDim.x * blockDim.x) {
-        const u64 k = msf_key(vals[i]);
+        const u64 k = fp64_sort_key(vals[i]);
         key = k < key ? k : key;
     }
 #pragma unroll
@@ -540,12 +515,6 @@ __global__ __launch_bounds__(256) void mf_min_kernel(const u64* __restrict__ val
         for (int j = 1; j < 4; ++j) key = s_part[j] < key ? s_part[j] : key;
         atomicMin(best, (unsigned long long)key);
     }
-}
-
-static u32 mf_grid(fgpu_ctx* ctx, u64 items, u32 per_block) {
-    u32 g = cdiv(items ? items : 1, per_block);
-    const u32 cap = (u32)ctx->cus * 8;
-    return g < cap ? g : cap;
 }
 
 struct MfRun {
@@ -596,11 +565,11 @@ extern "C" fgpu_info fgpu_mat_min_val(fgpu_ctx* ctx, const fgpu_mat* A, uint64_t
     DevBuf<unsigned long long> best;
     FGPU_TRY(best.alloc(ctx, 1));
     FGPU_HIP(hipMemsetAsync(best.p, 0xFF, sizeof(unsigned long long), ctx->stream()));
-    hipLaunchKernelGGL(mf_min_kernel, dim3(mf_grid(ctx, A->nnz, 1024)), dim3(256), 0, ctx->stream(), (const u64*)A->vals, A->nnz, best.p);
+    hipLaunchKernelGGL(mf_min_kernel, dim3(capped_grid(ctx, A->nnz, 1024, 8)), dim3(256), 0, ctx->stream(), (const u64*)A->vals, A->nnz, best.p);
     FGPU_HIP(hipGetLastError());
     u64 key = 0;
     FGPU_TRY(read_u64(ctx, (const u64*)best.p, &key));
-    *bits = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;   // msf_key's inverse (-0.0 comes back as +0.0)
+    *bits = fp64_from_sort_key(key);   // (-0.0 comes back as +0.0)
     return FGPU_OK;
 }
 
@@ -628,26 +597,23 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     // leaves 2^25 of headroom below 2^32, so no counter wraps
     FGPU_REQUIRE(C->nnz < 0x7F000000ull, FGPU_INVALID, "fgpu_maxflow: too many entries for a residual network with 32-bit positions");
     // the residual network
-    fgpu_mat* R = nullptr;
+    MatRef net;
     u64 npairs = 0;
     if (C->nnz) {
         DevBuf<u32> rows, cols;
         FGPU_TRY(rows.alloc(ctx, 2 * (size_t)C->nnz));
         FGPU_TRY(cols.alloc(ctx, 2 * (size_t)C->nnz));
-        hipLaunchKernelGGL(mf_arcs_kernel, dim3(mf_grid(ctx, C->nnz, 256)), dim3(256), 0, st, view_of(C), (const u64*)C->vals,
+        hipLaunchKernelGGL(mf_arcs_kernel, dim3(capped_grid(ctx, C->nnz, 256, 8)), dim3(256), 0, st, view_of(C), (const u64*)C->vals,
                            (u32)C->nnz, rows.p, cols.p, cnt.p);
         FGPU_HIP(hipGetLastError());
         u32 w[4];
         FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 4, w));
         npairs = (u64)w[0] | ((u64)w[1] << 32);
         FGPU_REQUIRE(!(w[2] | w[3]), FGPU_INVALID, "fgpu_maxflow: a capacity is NaN or infinite");
-        if (npairs) FGPU_TRY(mat_from_device_coo(ctx, &R, n, n, rows.p, cols.p, npairs));
+        if (npairs) FGPU_TRY(mat_from_device_coo(ctx, &net.m, n, n, rows.p, cols.p, npairs));
     }
-    if (!R || R->nnz == 0) {   // no live arc: no flow
-        if (R) mat_release(R);
-        return FGPU_OK;
-    }
-    struct Guard { fgpu_mat* m; ~Guard() { mat_release(m); } } guard{R};
+    const fgpu_mat* R = net.m;
+    if (!R || R->nnz == 0) return FGPU_OK;   // no live arc: no flow
     FGPU_TRY(mat_ensure_finalized(R));   // the hub list
     const u32 m = (u32)R->nnz, nch = R->n_hub_chunks;
     DevBuf<double> cap, r, e, bud;
@@ -669,7 +635,7 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     FGPU_HIP(hipMemsetAsync(cnt3.p, 0, 6 * sizeof(u32), st));
     FGPU_HIP(hipMemsetAsync(bud.p, 0, 2 * (size_t)(nch ? nch : 1) * sizeof(double), st));
     FGPU_HIP(hipMemsetAsync(newh.p, 0, (size_t)(nch ? nch : 1) * sizeof(u32), st));
-    hipLaunchKernelGGL(mf_net_kernel, dim3(mf_grid(ctx, m, 256)), dim3(256), 0, st, view_of(R), m, view_of(C), (const u64*)C->vals,
+    hipLaunchKernelGGL(mf_net_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, view_of(C), (const u64*)C->vals,
                        cap.p, r.p, rev.p);
     if (nch) hipLaunchKernelGGL(mf_hfirst_kernel, dim3(cdiv(nch, 256)), dim3(256), 0, st, (const u32*)R->hub_chunks, nch, hfirst.p);
     FGPU_HIP(hipGetLastError());
@@ -699,9 +665,9 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     s.bcnt3 = cnt3.p + 3;
     s.moved = moved.p;
     s.stat = cnt.p + 2;
-    s.grid = mf_grid(ctx, n, 4);
+    s.grid = capped_grid(ctx, n, 4, 8);
     s.hgrid = nch ? hub_grid(ctx, R) : 0;
-    const u32 sgrid = nch ? mf_grid(ctx, nch, 256) : 0;
+    const u32 sgrid = nch ? capped_grid(ctx, nch, 256, 8) : 0;
     // start: src's arcs saturated into list 0 (the length lands in cnt3[0]), labels by a global relabel, the hub rows armed
     hipLaunchKernelGGL(mf_start_kernel, dim3(1), dim3(256), 0, st, s.g, s.list[0], s.cnt3);
     FGPU_HIP(hipGetLastError());
@@ -748,7 +714,7 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     FGPU_TRY(frows.alloc(ctx, m / 2));   // (of two opposite arcs at most one carries flow)
     FGPU_TRY(fcols.alloc(ctx, m / 2));
     FGPU_TRY(fvals.alloc(ctx, m / 2));
-    hipLaunchKernelGGL(mf_flow_kernel, dim3(mf_grid(ctx, m, 256)), dim3(256), 0, st, view_of(R), m, (const double*)cap.p,
+    hipLaunchKernelGGL(mf_flow_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, (const double*)cap.p,
                        (const double*)r.p, (const u32*)rev.p, frows.p, fcols.p, fvals.p, cnt.p + 4);
     FGPU_HIP(hipGetLastError());
     unsigned long long hc[5];
@@ -760,33 +726,8 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     if (k) {
         fgpu_mat* f = nullptr;
         FGPU_TRY(mat_from_device_coo_vals(ctx, &f, n, n, frows.p, fcols.p, fvals.p, k));
-        DevBuf<u64> trip;
-        fgpu_info i = f->nnz == k ? trip.alloc(ctx, 3 * (size_t)k) : FGPU_DEVICE;
-        if (i == FGPU_DEVICE) set_error("fgpu_maxflow: the flow lost entries in the sort");
-        u64 *orow = nullptr, *ocol = nullptr, *oval = nullptr;
-        if (i == FGPU_OK) {
-            hipLaunchKernelGGL(mf_emit_kernel, dim3(mf_grid(ctx, k, 256)), dim3(256), 0, st, view_of(f), (u32)k, (const u64*)f->vals,
-                               trip.p, trip.p + k, trip.p + 2 * k);
-            if (hipGetLastError() != hipSuccess) { set_error("fgpu_maxflow: launch failed"); i = FGPU_DEVICE; }
-        }
-        if (i == FGPU_OK) {
-            orow = (u64*)ctx->result_alloc(k * sizeof(u64));
-            ocol = (u64*)ctx->result_alloc(k * sizeof(u64));
-            oval = (u64*)ctx->result_alloc(k * sizeof(u64));
-            if (!orow || !ocol || !oval) { set_error("fgpu_maxflow: host allocation failed"); i = FGPU_OOM; }
-        }
-        if (i == FGPU_OK) i = ctx->d2h(orow, trip.p, k * sizeof(u64));
-        if (i == FGPU_OK) i = ctx->d2h(ocol, trip.p + k, k * sizeof(u64));
-        if (i == FGPU_OK) i = ctx->d2h(oval, trip.p + 2 * k, k * sizeof(u64));
-        if (i == FGPU_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("fgpu_maxflow: synchronize failed"); i = FGPU_DEVICE; }
-        mat_release(f);
-        if (i != FGPU_OK) {
-            ctx->host_free(orow); ctx->host_free(ocol); ctx->host_free(oval);
-            return i;
-        }
-        *flow_rows = orow;
-        *flow_cols = ocol;
-        *flow_vals = (double*)oval;
+        FGPU_TRY(csr_edge_list(ctx, "fgpu_maxflow", "the flow lost entries in the sort", f, k, MfFlowValue{(const u64*)f->vals}, 8,
+                               flow_rows, flow_cols, flow_vals));
         *n_flow = k;
     }
     *max_flow = value;

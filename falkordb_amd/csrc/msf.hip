@@ -1,15 +1,15 @@
 // msf.hip — algo.MSF's numeric core: LAGraph_msf (called from graph/src/runtime/functions/algo_procedures.rs:1711-1717 through
-// lagraphx_bindings.rs:261-267) over a symmetric weighted matrix W.  Boruvka over the union-find forest of wcc.hip; the rules
+// lagraphx_bindings.rs:261-267) over a symmetric weighted matrix W.  Boruvka over the prelude's union-find forest (algo.hpp); the rules
 // (the edge order, what counts as an entry, the broken-promise guarantee) are written out in include/fgpu.h.
 //
-// Every unordered pair {v, w} is one edge with the key (K(bits), min, max); K (msf_key) is the IEEE totalOrder with -0.0 = +0.0
+// Every unordered pair {v, w} is one edge with the key (K(bits), min, max); K (fp64_sort_key) is the IEEE totalOrder with -0.0 = +0.0
 // on the stored bit pattern.  The order is strict and total, so the minimum spanning forest is unique and the kernels may race
 // in any order.  A round, over comp[] = the flat parent forest of the previous round:
 //   1. min weight  (valued W only) every live row reduces K over its external entries (comp[v] != comp[w], both ends active,
 //      no diagonal) and issues ONE atomicMin into best_w[comp[v]]; its own minimum is kept in rowmin[v].
 //   2. min pair    the live rows whose rowmin equals best_w[comp] scan again: the entries with K == best_w[comp] compete with
 //      one atomicMin of (lo << 32 | hi) per row into best_e[comp].  A BOOL W (every weight 1.0) has only this pass.
-//   3. hook        a thread per root with a chosen pair joins the two trees (the wcc_link discipline).  The thread whose CAS
+//   3. hook        a thread per root with a chosen pair joins the two trees (forest_hook).  The thread whose CAS
 //      turned the root `hi` into a non-root writes the pair into edge_of[hi]: a vertex stops being a root once, so the slot
 //      has one writer, a mutual choice is recorded once, and an edge is recorded ONLY by a hook that joined two trees —
 //      whatever W holds, the recorded pairs are a forest with (active vertices - roots) edges.
@@ -23,8 +23,7 @@
 // The forest leaves in (row < col) order sorted by (row, col): the recorded pairs are compacted, built into a CSR by the COO
 // builder (mat_from_device_coo: its rows come out ascending and sorted), and one thread per pair probes W for the weight.
 //
-// Concurrency rules (per-XCD L2s are not coherent inside a launch; wcc.hip has the long form):
-//   - hooks are atomicCAS(&parent[hi], hi, lo) with lo < hi, a retry continues from the word the CAS returned;
+// Concurrency rules (per-XCD L2s are not coherent inside a launch; the forest's own are in algo.hpp):
 //   - best_w / best_e are only ever lowered by atomicMin inside a launch; the plain load in front of the atomic is a filter:
 //     a stale word is a LARGER one, so a skipped atomic would have changed nothing;
 //   - comp[], best_w (pass 2), done[], rowmin[] are written by the launch before the one that reads them, done / rowmin words
@@ -35,28 +34,11 @@
 namespace fgpu {
 
 constexpr u64 MSF_NONE = ~0ull;
-constexpr u32 MSF_MAX_JUMPS = 40;   // pointer-jumping launches of one compress: 33 flatten any forest of < 2^32 vertices
 constexpr u64 MSF_ONE = 0x3FF0000000000000ull;   // 1.0
-
-// root of x by plain loads with path halving (wcc_find's rules)
-__device__ __forceinline__ u32 msf_find(u32* parent, u32 x) {
-    for (;;) {
-        const u32 p = parent[x];
-        if (p == x) return x;
-        const u32 gp = parent[p];
-        if (gp == p) return p;
-        parent[x] = gp;
-        x = gp;
-    }
-}
 
 // lowers *dst to x; the plain load only filters (see the rules above)
 __device__ __forceinline__ void msf_lower(u64* dst, u64 x) {
     if (*dst > x) atomicMin((unsigned long long*)dst, (unsigned long long)x);
-}
-
-__global__ void msf_init_kernel(u32* __restrict__ parent, u32 n) {
-    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) parent[v] = v;
 }
 
 // passes 1 (WPASS) and 2 over the rows shorter than HUB_DEG.  `best` is best_w in pass 1 and best_e in pass 2; `bw` is best_w
@@ -127,8 +109,8 @@ __global__ __launch_bounds__(256) void msf_rows_kernel(CsrView a, const u64* __r
                 const u32 c = cvs[lo];
                 if (w != rv && vertex_on(act, w) && comp[w] != c) {
                     const u64 pair = rv < w ? ((u64)rv << 32) | w : ((u64)w << 32) | rv;
-                    if (WPASS) key = msf_key(vals[idx]);
-                    else if (VALUED) key = msf_key(vals[idx]) == bw[c] ? pair : MSF_NONE;
+                    if (WPASS) key = fp64_sort_key(vals[idx]);
+                    else if (VALUED) key = fp64_sort_key(vals[idx]) == bw[c] ? pair : MSF_NONE;
                     else key = pair;
                     if (MARKS) alive[lo] = 1u;
                 }
@@ -187,8 +169,8 @@ __global__ __launch_bounds__(256) void msf_hubs_kernel(const u32* __restrict__ h
             any = 1;
             const u64 pair = row < w ? ((u64)row << 32) | w : ((u64)w << 32) | row;
             u64 k;
-            if (WPASS) k = msf_key(vals[i]);
-            else if (VALUED) k = msf_key(vals[i]) == want ? pair : MSF_NONE;
+            if (WPASS) k = fp64_sort_key(vals[i]);
+            else if (VALUED) k = fp64_sort_key(vals[i]) == want ? pair : MSF_NONE;
             else k = pair;
             key = k < key ? k : key;
         }
@@ -223,28 +205,9 @@ __global__ __launch_bounds__(256) void msf_hook_kernel(u32* parent, u64* __restr
         best_e[v] = MSF_NONE;
         if (best_w) best_w[v] = MSF_NONE;
         ++took;
-        u32 a = msf_find(parent, (u32)(e >> 32)), b = msf_find(parent, (u32)e);
-        while (a != b) {
-            const u32 hi = a > b ? a : b, lo = a > b ? b : a;
-            const u32 old = atomicCAS(&parent[hi], hi, lo);
-            if (old == hi) { edge_of[hi] = e; break; }
-            a = msf_find(parent, old);   // old < hi: continue from the returned word
-            b = msf_find(parent, lo);
-        }
+        forest_hook(parent, (u32)(e >> 32), (u32)e, [=](u32 hi) { edge_of[hi] = e; });
     }
     block_add_u64(took, chosen);
-}
-
-// one pointer-jumping step (wcc_jump_kernel's rules): flags[k] = 1 when it changed a word
-__global__ __launch_bounds__(256) void msf_jump_kernel(u32* parent, u32 n, u32* flags, u32 k) {
-    if (k > 0 && flags[k - 1] == 0) return;
-    bool changed = false;
-    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
-        const u32 p = parent[v];
-        const u32 gp = parent[p];
-        if (gp != p) { parent[v] = gp; changed = true; }
-    }
-    if (__ballot(changed) != 0ull && lane_id() == 0) flags[k] = 1u;
 }
 
 // the flat forest -> int64 labels (-1 for inactive vertices); cnt[0] += roots among the active vertices; the recorded pairs
@@ -275,7 +238,7 @@ __global__ __launch_bounds__(256) void msf_finish_kernel(const u32* __restrict__
         if (lane == 0) base = atomicAdd(&cnt[1], (unsigned long long)__builtin_popcountll(mask));
         base = __shfl(base, 0, 64);
         if (e != MSF_NONE) {
-            const u64 at = base + (u64)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+            const u64 at = base + wave_slot(mask, lane);
             rows[at] = (u32)(e >> 32);
             cols[at] = (u32)e;
         }
@@ -295,47 +258,17 @@ __device__ __forceinline__ bool msf_probe(const CsrView& a, const u64* __restric
     return true;
 }
 
-// the sorted forest CSR f -> (row, col, weight) triples, a thread per pair.  The weight is the stored value of W(row, col),
-// of W(col, row) when a caller who broke the symmetry promise stored only that one; 1.0 for a BOOL W.
-__global__ __launch_bounds__(256) void msf_emit_kernel(CsrView f, u32 k, CsrView w, const u64* __restrict__ vals,
-                                                      u64* __restrict__ orow, u64* __restrict__ ocol, u64* __restrict__ ow) {
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
-        u32 lo = 0, hi = f.nrows;   // the row r with rowptr[r] <= i < rowptr[r + 1]
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (f.rowptr[mid] <= i) lo = mid; else hi = mid;
-        }
-        const u32 c = f.colidx[i];
+// the weight of the forest pair (r, c) for csr_edge_list: the stored value of W(r, c), of W(c, r) when a caller who broke the
+// symmetry promise stored only that one; 1.0 for a BOOL W
+struct MsfWeight {
+    CsrView w;
+    const u64* vals;
+    __device__ __forceinline__ u64 operator()(u32, u32 r, u32 c) const {
         u64 x = MSF_ONE;
-        if (vals && !msf_probe(w, vals, lo, c, x)) msf_probe(w, vals, c, lo, x);
-        orow[i] = lo;
-        ocol[i] = c;
-        ow[i] = x;
+        if (vals && !msf_probe(w, vals, r, c, x)) msf_probe(w, vals, c, r, x);
+        return x;
     }
-}
-
-static u32 msf_grid(fgpu_ctx* ctx, u64 items, u32 per_block) {
-    u32 g = cdiv(items ? items : 1, per_block);
-    const u32 cap = (u32)ctx->cus * 4;
-    return g < cap ? g : cap;
-}
-
-// pointer jumping until a launch changes nothing: MSF_BATCH launches per read-back
-static fgpu_info msf_compress(fgpu_ctx* ctx, u32* parent, u32 n, u32* flags) {
-    constexpr u32 MSF_BATCH = 4;
-    FGPU_HIP(hipMemsetAsync(flags, 0, MSF_MAX_JUMPS * sizeof(u32), ctx->stream()));
-    const u32 grid = msf_grid(ctx, n, 256);
-    for (u32 k = 0; k < MSF_MAX_JUMPS;) {
-        for (u32 b = 0; b < MSF_BATCH && k < MSF_MAX_JUMPS; ++b, ++k)
-            hipLaunchKernelGGL(msf_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent, n, flags, k);
-        FGPU_HIP(hipGetLastError());
-        u32 f = 0;
-        FGPU_TRY(read_u32(ctx, flags + k - 1, &f));
-        if (!f) return FGPU_OK;
-    }
-    set_error("fgpu_msf: the parent forest did not flatten in %u pointer-jumping steps", MSF_MAX_JUMPS);
-    return FGPU_DEVICE;
-}
+};
 
 struct MsfState {
     const fgpu_mat* W;
@@ -393,7 +326,7 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
     DevBuf<long long> wide;
     if (active_bitmap) FGPU_TRY(upload_active(ctx, act, active_bitmap, n));
     FGPU_TRY(parent.alloc(ctx, n));
-    FGPU_TRY(flags.alloc(ctx, MSF_MAX_JUMPS));
+    FGPU_TRY(flags.alloc(ctx, FOREST_MAX_JUMPS));
     FGPU_TRY(done.alloc(ctx, nwords));
     FGPU_TRY(best.alloc(ctx, (valued ? 2 : 1) * (size_t)n));   // best_e, best_w
     FGPU_TRY(edge_of.alloc(ctx, n));
@@ -408,9 +341,8 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
     FGPU_HIP(hipMemsetAsync(best.p, 0xFF, (valued ? 2 : 1) * (size_t)n * sizeof(u64), st));
     FGPU_HIP(hipMemsetAsync(edge_of.p, 0xFF, (size_t)n * sizeof(u64), st));
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, 4 * sizeof(unsigned long long), st));
-    const u32 grid = msf_grid(ctx, n, 256);
-    hipLaunchKernelGGL(msf_init_kernel, dim3(grid), dim3(256), 0, st, parent.p, n);
-    FGPU_HIP(hipGetLastError());
+    const u32 grid = capped_grid(ctx, n, 256, 4);
+    FGPU_TRY(forest_init(ctx, parent.p, n));
     MsfState s;
     s.W = W;
     s.act = act.p;
@@ -443,7 +375,7 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
         ++round_no;
         if (!chosen) break;   // no component has an external entry
         ++rounds;
-        FGPU_TRY(msf_compress(ctx, parent.p, n, flags.p));
+        FGPU_TRY(forest_compress(ctx, "fgpu_msf", parent.p, n, flags.p));
     }
     FGPU_TRY(wide.alloc(ctx, n));
     FGPU_TRY(rows.alloc(ctx, n));
@@ -460,33 +392,8 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
         // the pairs sorted by (row, col): a CSR of the forest, then the triples
         fgpu_mat* f = nullptr;
         FGPU_TRY(mat_from_device_coo(ctx, &f, n, n, rows.p, cols.p, k));
-        DevBuf<u64> trip;
-        fgpu_info i = f->nnz == k ? trip.alloc(ctx, 3 * (size_t)k) : FGPU_DEVICE;
-        if (i == FGPU_DEVICE) set_error("fgpu_msf: the forest lost pairs in the sort");
-        u64 *orow = nullptr, *ocol = nullptr, *ow = nullptr;
-        if (i == FGPU_OK) {
-            hipLaunchKernelGGL(msf_emit_kernel, dim3(msf_grid(ctx, k, 256)), dim3(256), 0, st, view_of(f), (u32)k, view_of(W),
-                               (const u64*)W->vals, trip.p, trip.p + k, trip.p + 2 * k);
-            if (hipGetLastError() != hipSuccess) { set_error("fgpu_msf: launch failed"); i = FGPU_DEVICE; }
-        }
-        if (i == FGPU_OK) {
-            orow = (u64*)ctx->result_alloc(k * sizeof(u64));
-            ocol = (u64*)ctx->result_alloc(k * sizeof(u64));
-            ow = (u64*)ctx->result_alloc(k * sizeof(u64));
-            if (!orow || !ocol || !ow) { set_error("fgpu_msf: host allocation failed"); i = FGPU_OOM; }
-        }
-        if (i == FGPU_OK) i = ctx->d2h(orow, trip.p, k * sizeof(u64));
-        if (i == FGPU_OK) i = ctx->d2h(ocol, trip.p + k, k * sizeof(u64));
-        if (i == FGPU_OK) i = ctx->d2h(ow, trip.p + 2 * k, k * sizeof(u64));
-        if (i == FGPU_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("fgpu_msf: synchronize failed"); i = FGPU_DEVICE; }
-        mat_release(f);
-        if (i != FGPU_OK) {
-            ctx->host_free(orow); ctx->host_free(ocol); ctx->host_free(ow);
-            return i;
-        }
-        *forest_rows = orow;
-        *forest_cols = ocol;
-        *forest_weights = (double*)ow;
+        FGPU_TRY(csr_edge_list(ctx, "fgpu_msf", "the forest lost pairs in the sort", f, k, MsfWeight{view_of(W), (const u64*)W->vals},
+                               4, forest_rows, forest_cols, forest_weights));
         *n_forest = k;
     }
     if (stats) {

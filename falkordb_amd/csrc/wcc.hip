@@ -16,17 +16,8 @@
 // rows hold both directions.  wcc_mode 2 (and small graphs under auto) is one link pass over every entry of A: each stored
 // entry joins its two endpoints, so At is not needed there.
 //
-// Concurrency rules (inside one launch a plain load can keep returning a word another XCD has since rewritten — per-XCD L2s
-// are not coherent; MI355X_MICROARCH.md):
-//   - every hook is atomicCAS(&parent[hi], hi, lo) with lo < hi: parent links only point to smaller ids, the forest has no
-//     cycles, and a tree's root is its smallest vertex;
-//   - a failed CAS continues from the value the CAS RETURNED (fresh, strictly smaller than hi), never from a plain re-load of
-//     parent[hi]: the larger of the two roots strictly drops on every retry, so the loop ends within n steps;
-//   - the find walk uses plain loads: a stale word is still an ancestor with a smaller id, so the walk ends.  Its path-halving
-//     stores write such an ancestor into a word that is already a non-root, which no CAS can succeed on;
-//   - kernel boundaries separate the link, compress, sample and count phases.  Nothing polls or spins on a plain load.
-// Compression is pointer jumping by whole launches (parent[v] = parent[parent[v]]) until a launch changes nothing: each halves
-// the depth of every tree, so a path of n vertices hooked in id order costs log2(n) launches, not a walk of n per vertex.
+// The parent forest, its hooks and its compression are the prelude's (algo.hpp, "the union-find forest", with the concurrency
+// rules): every link below is a forest_hook, and kernel boundaries separate the link, compress, sample and count phases.
 // No dynamic LDS; the static LDS of the word kernel is 2 KiB per workgroup, the sample kernel's 4 KiB.
 #include "algo.hpp"
 
@@ -36,36 +27,7 @@ constexpr u32 WCC_ROUNDS = 2;          // Afforest's neighbour rounds
 constexpr u32 WCC_SAMPLES = 1024;      // vertices sampled for the giant component (one workgroup)
 constexpr u64 WCC_SEED = 0x57CC2018ull;
 constexpr u32 WCC_NONE = 0xFFFFFFFFu;
-constexpr u32 WCC_MAX_JUMPS = 40;      // pointer-jumping launches of one compress: 33 flatten any forest of < 2^32 vertices
 constexpr u32 WCC_AUTO_MIN_N = 4096;   // wcc_mode 0: Afforest from this many vertices, the full pass below
-
-// root of x by plain loads with path halving (see the rules above)
-__device__ __forceinline__ u32 wcc_find(u32* parent, u32 x) {
-    for (;;) {
-        const u32 p = parent[x];
-        if (p == x) return x;
-        const u32 gp = parent[p];
-        if (gp == p) return p;
-        parent[x] = gp;
-        x = gp;
-    }
-}
-
-// join the trees of u and w
-__device__ __forceinline__ void wcc_link(u32* parent, u32 u, u32 w) {
-    u32 a = wcc_find(parent, u), b = wcc_find(parent, w);
-    while (a != b) {
-        const u32 hi = a > b ? a : b, lo = a > b ? b : a;
-        const u32 old = atomicCAS(&parent[hi], hi, lo);
-        if (old == hi) return;
-        a = wcc_find(parent, old);   // old < hi: continue from the returned word
-        b = wcc_find(parent, lo);
-    }
-}
-
-__global__ void wcc_init_kernel(u32* __restrict__ parent, u32 n) {
-    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) parent[v] = v;
-}
 
 // phase 2: round r links v to the r-th entry of its row
 __global__ __launch_bounds__(256) void wcc_link_round_kernel(CsrView a, const u64* __restrict__ act, u32* parent, u32 n, u32 r,
@@ -77,7 +39,7 @@ __global__ __launch_bounds__(256) void wcc_link_round_kernel(CsrView a, const u6
         if (e - b <= r) continue;
         const u32 w = a.colidx[b + r];
         ++took;
-        if (vertex_on(act, w)) wcc_link(parent, v, w);
+        if (vertex_on(act, w)) forest_hook(parent, v, w);
     }
     block_add_u64(took, entries);
 }
@@ -127,7 +89,7 @@ __global__ __launch_bounds__(256) void wcc_link_words_kernel(CsrView a, const u6
                 if (off[mid] <= e) lo = mid; else hi = mid;
             }
             const u32 w = col[rbs[lo] + (e - off[lo])];
-            if (vertex_on(act, w)) wcc_link(parent, (g << 6) + lo, w);
+            if (vertex_on(act, w)) forest_hook(parent, (g << 6) + lo, w);
         }
     }
     block_add_u64(seen, entries);
@@ -154,23 +116,10 @@ __global__ __launch_bounds__(256) void wcc_link_hubs_kernel(const u32* __restric
         if (threadIdx.x == 0) seen += e - b;
         for (u32 i = b + threadIdx.x; i < e; i += 256) {
             const u32 w = col[i];
-            if (vertex_on(act, w)) wcc_link(parent, row, w);
+            if (vertex_on(act, w)) forest_hook(parent, row, w);
         }
     }
     if (threadIdx.x == 0 && seen) atomicAdd(entries, (unsigned long long)seen);
-}
-
-// one pointer-jumping step; flags[k] = 1 when it changed a word.  A launch after one that changed nothing returns at once.
-// (No hooks run here: a vertex whose parent's parent is its parent points at a root.)
-__global__ __launch_bounds__(256) void wcc_jump_kernel(u32* parent, u32 n, u32* flags, u32 k) {
-    if (k > 0 && flags[k - 1] == 0) return;
-    bool changed = false;
-    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
-        const u32 p = parent[v];
-        const u32 gp = parent[p];
-        if (gp != p) { parent[v] = gp; changed = true; }
-    }
-    if (__ballot(changed) != 0ull && lane_id() == 0) flags[k] = 1u;
 }
 
 // phase 3: the most frequent root among WCC_SAMPLES fixed-seed samples (ties: the smaller root); inactive samples do not vote.
@@ -223,29 +172,6 @@ __global__ __launch_bounds__(256) void wcc_finish_kernel(const u32* __restrict__
     block_add_u64(gsz, &cnt[1]);
 }
 
-static u32 wcc_grid(fgpu_ctx* ctx, u64 items, u32 per_block) {
-    u32 g = cdiv(items ? items : 1, per_block);
-    const u32 cap = (u32)ctx->cus * 4;   // grid-stride: 1 K workgroups of 256 fill the chip and keep the count atomics few
-    return g < cap ? g : cap;
-}
-
-// pointer jumping until a launch changes nothing: launched WCC_BATCH at a time, one read-back per batch
-static fgpu_info wcc_compress(fgpu_ctx* ctx, u32* parent, u32 n, u32* flags) {
-    constexpr u32 WCC_BATCH = 4;
-    FGPU_HIP(hipMemsetAsync(flags, 0, WCC_MAX_JUMPS * sizeof(u32), ctx->stream()));
-    const u32 grid = wcc_grid(ctx, n, 256);
-    for (u32 k = 0; k < WCC_MAX_JUMPS;) {
-        for (u32 b = 0; b < WCC_BATCH && k < WCC_MAX_JUMPS; ++b, ++k)
-            hipLaunchKernelGGL(wcc_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent, n, flags, k);
-        FGPU_HIP(hipGetLastError());
-        u32 f = 0;
-        FGPU_TRY(read_u32(ctx, flags + k - 1, &f));
-        if (!f) return FGPU_OK;
-    }
-    set_error("fgpu_wcc: the parent forest did not flatten in %u pointer-jumping steps", WCC_MAX_JUMPS);
-    return FGPU_DEVICE;
-}
-
 // entries [first, deg) of every row of M (giant: skip the rows of that tree; nullptr = none): the word pass + the hub chunks
 static fgpu_info wcc_link_rows(fgpu_ctx* ctx, const fgpu_mat* m, const u64* act, u32* parent, u32 n, u32 first, const u32* giant,
                                unsigned long long* entries, u64* launches) {
@@ -293,15 +219,14 @@ extern "C" fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* 
     if (active_bitmap) FGPU_TRY(upload_active(ctx, act, active_bitmap, n));
     FGPU_TRY(parent.alloc(ctx, n));
     FGPU_TRY(giant.alloc(ctx, 1));
-    FGPU_TRY(flags.alloc(ctx, WCC_MAX_JUMPS));
+    FGPU_TRY(flags.alloc(ctx, FOREST_MAX_JUMPS));
     FGPU_TRY(cnt.alloc(ctx, 3));   // entries read, roots, giant size
     FGPU_TRY(wide.alloc(ctx, n));
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
     FGPU_HIP(hipMemsetAsync(giant.p, 0xFF, sizeof(u32), ctx->stream()));
     const u64* a = act.p;
-    const u32 grid = wcc_grid(ctx, n, 256);
-    hipLaunchKernelGGL(wcc_init_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent.p, n);
-    FGPU_HIP(hipGetLastError());
+    const u32 grid = capped_grid(ctx, n, 256, 4);   // keeps the count atomics few
+    FGPU_TRY(forest_init(ctx, parent.p, n));
     u64 launches = 0;
     if (afforest) {
         for (u32 r = 0; r < WCC_ROUNDS; ++r) {
@@ -309,7 +234,7 @@ extern "C" fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* 
                                cnt.p);
             FGPU_HIP(hipGetLastError());
             ++launches;
-            FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
+            FGPU_TRY(forest_compress(ctx, "fgpu_wcc", parent.p, n, flags.p));
         }
         hipLaunchKernelGGL(wcc_sample_kernel, dim3(1), dim3(WCC_SAMPLES), 0, ctx->stream(), (const u32*)parent.p, a, n, giant.p);
         FGPU_HIP(hipGetLastError());
@@ -318,7 +243,7 @@ extern "C" fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* 
     } else {
         FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, 0, nullptr, cnt.p, &launches));
     }
-    FGPU_TRY(wcc_compress(ctx, parent.p, n, flags.p));
+    FGPU_TRY(forest_compress(ctx, "fgpu_wcc", parent.p, n, flags.p));
     hipLaunchKernelGGL(wcc_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)parent.p, a, n,
                        afforest ? (const u32*)giant.p : nullptr, wide.p, cnt.p + 1);
     FGPU_HIP(hipGetLastError());

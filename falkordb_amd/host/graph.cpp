@@ -857,6 +857,23 @@ static NodeSelection select_nodes(const Graph& g, const std::vector<std::string>
     }
     return sel;
 }
+// ... every live node (a procedure called without labels whose engine call wants the bitmap all the same)
+static NodeSelection select_live_nodes(const Graph& g) {
+    const u64 n = g.node_cap();
+    NodeSelection sel;
+    sel.bits.assign((n + 63) / 64, 0);
+    for (u64 v = 0; v < n; ++v)
+        if (!g.is_node_deleted(v)) { sel.bits[v >> 6] |= 1ull << (v & 63); ++sel.count; }
+    return sel;
+}
+// rank[v] = v's index among the selected ids in ascending order (the reference's compact index), -1 for the others
+static std::vector<int64_t> compact_ranks(const NodeSelection& sel, u64 n) {
+    std::vector<int64_t> rank(n, -1);
+    int64_t k = 0;
+    for (u64 v = 0; v < n; ++v)
+        if (sel.has(v)) rank[v] = k++;
+    return rank;
+}
 
 // one result row per live node (sel, nullable: that is also selected), in id order; value(v) is the row's second column
 template <typename T, typename F>
@@ -921,13 +938,7 @@ WccResult algo_wcc(const Graph& g, const std::vector<std::string>& labels, const
           "LAGr_ConnectedComponents");
     // a filtered run's componentId is the representative's COMPACT index — its rank among the selected ids in ascending
     // order (:617-626) — which the reference never maps back to a node id (:854-868)
-    std::vector<int64_t> rank;
-    if (filtered) {
-        rank.assign(n, -1);
-        int64_t k = 0;
-        for (u64 v = 0; v < n; ++v)
-            if (sel.has(v)) rank[v] = k++;
-    }
+    const std::vector<int64_t> rank = filtered ? compact_ranks(sel, n) : std::vector<int64_t>();
     // (fgpu_wcc writes comp[v] = -1 exactly for the unselected v)
     emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.component_ids,
               [&](u64 v) { return filtered ? rank[(size_t)comp[v]] : comp[v]; });   // :857-859
@@ -958,13 +969,7 @@ CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, con
     // a filtered run's communityId is the label's COMPACT index — its rank among the selected ids in ascending order — which
     // the reference never maps back to a node id (:1244-1258).  Exact: ranks keep the order of the ids, so every tie-break of
     // the compact run picks the same vertex
-    std::vector<int64_t> rank;
-    if (filtered) {
-        rank.assign(n, -1);
-        int64_t k = 0;
-        for (u64 v = 0; v < n; ++v)
-            if (sel.has(v)) rank[v] = k++;
-    }
+    const std::vector<int64_t> rank = filtered ? compact_ranks(sel, n) : std::vector<int64_t>();
     // (fgpu_cdlp writes comm[v] = -1 exactly for the unselected v)
     emit_rows(g, filtered ? &sel : nullptr, res.nodes, res.community_ids,
               [&](u64 v) { return filtered ? rank[(size_t)comm[v]] : comm[v]; });   // :1249-1258
@@ -1019,14 +1024,7 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
     if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:1323-1325)
     // the nodes of the run: the labels' live nodes, or every live node (collect_node_ids, :1328-1331).  The reference
     // renumbers them 0..k-1; here they are an induced subgraph, and the order of the ids — all the forest depends on — is kept
-    NodeSelection sel;
-    if (!labels.empty()) {
-        sel = select_nodes(g, labels);
-    } else {
-        sel.bits.assign((n + 63) / 64, 0);
-        for (u64 v = 0; v < n; ++v)
-            if (!g.is_node_deleted(v)) { sel.bits[v >> 6] |= 1ull << (v & 63); ++sel.count; }
-    }
+    const NodeSelection sel = labels.empty() ? select_live_nodes(g) : select_nodes(g, labels);
     if (sel.count == 0) return res;
     if (types.empty())
         for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
@@ -1071,9 +1069,8 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
     Matrix w(g.ctx(), Type::UInt64, n, n);
     if (!rows.empty()) w.build(rows, cols, &bits);
     std::vector<int64_t> comp(n);
-    u64 *fr = nullptr, *fc = nullptr, k = 0;
-    double* fw = nullptr;
-    check(fgpu_msf(g.ctx().raw(), w.snapshot(), sel.bits.data(), comp.data(), &fr, &fc, &fw, &k, nullptr), "LAGraph_msf");
+    EdgeList forest(g.ctx());
+    msf(g.ctx(), w.snapshot(), sel.bits.data(), comp.data(), forest);
     // trees in ascending order of their smallest node id = their component label (:1778-1848)
     std::vector<int64_t> tree_of(n, -1);
     for (u64 v = 0; v < n; ++v) {
@@ -1085,11 +1082,9 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
         }
         res.tree_nodes[(size_t)tree_of[(size_t)comp[v]]].push_back(v);   // (comp[v] <= v: its tree exists already)
     }
-    for (u64 i = 0; i < k; ++i)
-        res.tree_edges[(size_t)tree_of[(size_t)comp[fr[i]]]].push_back(best.at((fr[i] << 32) | fc[i]).edge);
-    fgpu_free(g.ctx().raw(), fr);
-    fgpu_free(g.ctx().raw(), fc);
-    fgpu_free(g.ctx().raw(), fw);
+    for (u64 i = 0; i < forest.n; ++i)
+        res.tree_edges[(size_t)tree_of[(size_t)comp[forest.rows[i]]]].push_back(
+            best.at((forest.rows[i] << 32) | forest.cols[i]).edge);
     return res;
 }
 
@@ -1191,15 +1186,11 @@ MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& label
                                     "smallest, which the solver's arithmetic cannot keep apart");
     Matrix cap(g.ctx(), Type::UInt64, total, total);
     if (!rows.empty()) cap.build(rows, cols, &bits);                     // (every position once: no multi-edge, super arcs once)
-    u64 *fr = nullptr, *fc = nullptr, k = 0;
-    double* fv = nullptr;
-    check(fgpu_maxflow(g.ctx().raw(), cap.snapshot(), src_id, sink_id, &res.max_flow, &fr, &fc, &fv, &k, nullptr), "LAGr_MaxFlow");
+    EdgeList flow(g.ctx());
+    maxflow(g.ctx(), cap.snapshot(), src_id, sink_id, &res.max_flow, flow);
     std::unordered_map<u64, double> flow_of;                             // (row << 32 | col) -> flow; ids fit 32 bits (fgpu_maxflow)
-    flow_of.reserve(k * 2);
-    for (u64 i = 0; i < k; ++i) flow_of[(fr[i] << 32) | fc[i]] = fv[i];
-    fgpu_free(g.ctx().raw(), fr);
-    fgpu_free(g.ctx().raw(), fc);
-    fgpu_free(g.ctx().raw(), fv);
+    flow_of.reserve(flow.n * 2);
+    for (u64 i = 0; i < flow.n; ++i) flow_of[(flow.rows[i] << 32) | flow.cols[i]] = flow.vals[i];
     std::set<u64> used;
     for (const Arc* a : kept) {                                          // :3218-3232
         const auto it = flow_of.find((compact(a->src) << 32) | compact(a->dst));

@@ -640,6 +640,28 @@ std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t
 BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
                                    int64_t sampling_size, int64_t sampling_seed);
 
+// The (row, col, value) result arrays of one engine call (fgpu_msf's forest, fgpu_maxflow's flow): n triples in (row, col)
+// order, owned here and returned to the context's result pool with the scope.
+struct EdgeList {
+    u64 *rows = nullptr, *cols = nullptr, n = 0;
+    double* vals = nullptr;
+    explicit EdgeList(const Context& ctx) : ctx_(ctx.raw()) {}
+    EdgeList(const EdgeList&) = delete;
+    EdgeList& operator=(const EdgeList&) = delete;
+    ~EdgeList() { fgpu_free(ctx_, rows); fgpu_free(ctx_, cols); fgpu_free(ctx_, vals); }
+
+   private:
+    fgpu_ctx* ctx_;
+};
+// fgpu_msf / fgpu_maxflow into an EdgeList of `ctx`; a failure throws as check() does, named after the LAGraph call
+inline void msf(const Context& ctx, const fgpu_mat* w, const u64* active_bitmap, int64_t* component, EdgeList& forest) {
+    check(fgpu_msf(ctx.raw(), w, active_bitmap, component, &forest.rows, &forest.cols, &forest.vals, &forest.n, nullptr),
+          "LAGraph_msf");
+}
+inline void maxflow(const Context& ctx, const fgpu_mat* cap, u64 src, u64 sink, double* value, EdgeList& flow) {
+    check(fgpu_maxflow(ctx.raw(), cap, src, sink, value, &flow.rows, &flow.cols, &flow.vals, &flow.n, nullptr), "LAGr_MaxFlow");
+}
+
 struct MsfResult {
     std::vector<std::vector<u64>> tree_nodes;   // per tree, ascending node ids
     std::vector<std::vector<u64>> tree_edges;   // per tree, the relationship id of every forest pair, in forest order

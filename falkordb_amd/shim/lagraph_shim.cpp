@@ -436,6 +436,17 @@ int LAGr_HarmonicCentrality(GrB_Vector* scores, GrB_Vector* reachable_nodes, LAG
         return GrB_SUCCESS;
     });
 }
+// an n x n GrB_FP64 matrix of the triples (what LAGr_MaxFlow and LAGraph_msf hand out)
+static std::unique_ptr<GB_Matrix_opaque> fp64_matrix_from(const falkor::EdgeList& e, uint64_t n) {
+    std::unique_ptr<GB_Matrix_opaque> out(new GB_Matrix_opaque(Matrix(*fgshim::context(), Type::UInt64, n, n)));
+    out->fp64 = true;
+    if (e.n) {
+        std::vector<uint64_t> bits(e.n);
+        memcpy(bits.data(), e.vals, e.n * sizeof(uint64_t));
+        out->m.build(std::vector<uint64_t>(e.rows, e.rows + e.n), std::vector<uint64_t>(e.cols, e.cols + e.n), &bits);
+    }
+    return out;
+}
 // LAGr_MaxFlow (lagraphx_bindings.rs:610-618) as algo.maxFlow calls it (algo_procedures.rs:3161-3170): G holds a GrB_FP64 (or
 // GrB_BOOL: capacity 1.0) adjacency of capacities over compact node ids.  An Advanced method — G->AT and G->emin must be cached
 // (LAGRAPH_NOT_CACHED otherwise, as LAGr_PageRank treats its properties; the engine builds its own residual network and reads
@@ -458,27 +469,11 @@ int LAGr_MaxFlow(double* f, GrB_Matrix* flow_mtx, GrB_Matrix* res_mtx, LAGraph_G
     if (src >= n || sink >= n) return fail(msg, GrB_INVALID_INDEX, "invalid source / sink node");
     if (src == sink) return fail(msg, GrB_INVALID_VALUE, "source and sink must differ");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
-        uint64_t *fr = nullptr, *fc = nullptr, k = 0;
-        double* fv = nullptr;
+        falkor::EdgeList flow(*fgshim::context());
         double value = 0;
-        check(fgpu_maxflow(c->raw(), G->A->m.snapshot(), src, sink, &value, &fr, &fc, &fv, &k, nullptr), "LAGr_MaxFlow");
+        falkor::maxflow(*fgshim::context(), G->A->m.snapshot(), src, sink, &value, flow);
         std::unique_ptr<GB_Matrix_opaque> out;
-        try {
-            if (flow_mtx) {
-                out.reset(new GB_Matrix_opaque(Matrix(*c, Type::UInt64, n, n)));
-                out->fp64 = true;
-                if (k) {
-                    std::vector<uint64_t> bits(k);
-                    memcpy(bits.data(), fv, k * sizeof(uint64_t));
-                    out->m.build(std::vector<uint64_t>(fr, fr + k), std::vector<uint64_t>(fc, fc + k), &bits);
-                }
-            }
-        } catch (...) {
-            fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fv);
-            throw;
-        }
-        fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fv);
+        if (flow_mtx) out = fp64_matrix_from(flow, n);
         *f = value;
         if (flow_mtx) *flow_mtx = out.release();
         return GrB_SUCCESS;
@@ -501,27 +496,12 @@ int LAGraph_msf(GrB_Matrix* forest_edges, GrB_Vector* componentId, GrB_Matrix A,
         return fail(msg, GrB_NOT_IMPLEMENTED, "LAGraph_msf: A must be a GrB_FP64 or GrB_BOOL matrix");
     if (A->m.nrows() != A->m.ncols()) return fail(msg, GrB_DIMENSION_MISMATCH, "LAGraph_msf: A must be square");
     return guarded(msg, [&]() -> int {
-        falkor::Context* c = fgshim::context();
         const uint64_t n = A->m.nrows();
         ResultVector<int64_t> comp;
         if (componentId) comp.alloc(fgshim::type_int64(), n, 0, "LAGraph_msf");
-        uint64_t *fr = nullptr, *fc = nullptr, k = 0;
-        double* fw = nullptr;
-        check(fgpu_msf(c->raw(), A->m.snapshot(), nullptr, comp.data, &fr, &fc, &fw, &k, nullptr), "LAGraph_msf");
-        std::unique_ptr<GB_Matrix_opaque> f;
-        try {
-            f.reset(new GB_Matrix_opaque(Matrix(*c, Type::UInt64, n, n)));
-            f->fp64 = true;
-            if (k) {
-                std::vector<uint64_t> bits(k);
-                memcpy(bits.data(), fw, k * sizeof(uint64_t));
-                f->m.build(std::vector<uint64_t>(fr, fr + k), std::vector<uint64_t>(fc, fc + k), &bits);
-            }
-        } catch (...) {
-            fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fw);
-            throw;
-        }
-        fgpu_free(c->raw(), fr); fgpu_free(c->raw(), fc); fgpu_free(c->raw(), fw);
+        falkor::EdgeList forest(*fgshim::context());
+        falkor::msf(*fgshim::context(), A->m.snapshot(), nullptr, comp.data, forest);
+        std::unique_ptr<GB_Matrix_opaque> f = fp64_matrix_from(forest, n);
         *forest_edges = f.release();
         if (componentId) *componentId = comp.release();
         return GrB_SUCCESS;

@@ -68,6 +68,19 @@ def test_path_with_a_bottleneck_returns_the_excess_to_src(ctx, n):
     assert st[0] > 0 and st[3] > 0
 
 
+# the read-out of the sorted flow (csr_edge_list): k = 1, 256 and 257 entries are one thread, exactly one workgroup of the emit
+# kernel, and one element into the second
+@pytest.mark.parametrize("n", [2, 257, 258])
+def test_path_flow_comes_out_as_its_triples_in_order(ctx, n):
+    caps = 10.0 + np.arange(n - 1) % 7
+    caps[(n - 1) // 2] = 3.25   # the one strict minimum
+    value, fr, fc, fv, st = solve(ctx, n, np.arange(n - 1), np.arange(1, n), caps, 0, n - 1)
+    assert value == 3.25
+    assert len(fr) == len(fc) == len(fv) == n - 1
+    assert np.array_equal(fr, np.arange(n - 1, dtype=U64)) and np.array_equal(fc, np.arange(1, n, dtype=U64))
+    assert np.all(fv == 3.25)
+
+
 def test_no_path_is_zero_and_empty(ctx):
     # two islands; src's island fills up and hands everything back
     value, fr, fc, fv, st = solve(ctx, 8, [0, 1, 2, 5, 6], [1, 2, 3, 6, 7], [4.0, 3.0, 2.0, 5.0, 5.0], 0, 7)

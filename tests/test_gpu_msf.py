@@ -220,6 +220,48 @@ def test_repeatable_equals_wcc_and_fills_a_host_array(ctx):
     assert c[0] is out and np.array_equal(out, a[0])
 
 
+# the read-out of the sorted forest (csr_edge_list): k = 1, 256 and 257 pairs are one thread, exactly one workgroup of the
+# emit kernel, and one element into the second
+def weighted_path(n):
+    """the path 0 - 1 - ... - (n-1); the weights (i * 37) % (n - 1) + 0.5 are distinct: 37 is coprime to 1, 256 and 257"""
+    lo = np.arange(n - 1)
+    return lo, lo + 1, (lo * 37) % (n - 1) + 0.5
+
+
+@pytest.mark.parametrize("valued", [True, False], ids=["valued", "bool"])
+@pytest.mark.parametrize("n", [2, 257, 258])
+def test_path_forest_comes_out_as_its_triples_in_order(ctx, n, valued):
+    lo, hi, w = weighted_path(n)
+    rows, cols, bits = sym(lo, hi, bits_of(w) if valued else None)
+    W = upload(ctx, n, rows, cols, bits)
+    comp, fr, fc, fw, st = engine.msf(ctx, W, stats=True)
+    assert st[1] == len(fr) == len(fc) == len(fw) == n - 1
+    assert np.array_equal(fr, lo.astype(U64)) and np.array_equal(fc, hi.astype(U64))   # (row, col) order, first and last row
+    assert np.array_equal(fw.view(U64), bits_of(w if valued else np.ones(n - 1)))
+    wc, _ = engine.wcc(ctx, W, None)
+    assert np.array_equal(comp, wc) and np.all(comp == 0)
+
+
+@pytest.mark.parametrize("n", [2, 257, 258])
+def test_path_with_two_active_vertices_is_one_triple_or_none(ctx, n):
+    lo, hi, w = weighted_path(n)
+    rows, cols, bits = sym(lo, hi, bits_of(w))
+    W = upload(ctx, n, rows, cols, bits)
+    pairs = [(n - 2, n - 1)] + ([(0, n - 1)] if n > 2 else [])   # neighbours: their edge; the two ends: nothing
+    for a, b in pairs:
+        active = np.zeros(n, dtype=bool)
+        active[[a, b]] = True
+        comp, fr, fc, fw, st = engine.msf(ctx, W, bitmap(active), stats=True)
+        want = np.full(n, -1, dtype=np.int64)
+        if b == a + 1:
+            want[[a, b]] = a
+            assert fr.tolist() == [a] and fc.tolist() == [b] and np.array_equal(fw.view(U64), bits_of(w[a:a + 1]))
+        else:
+            want[a], want[b] = a, b
+            assert len(fr) == len(fc) == len(fw) == 0
+        assert np.array_equal(comp, want) and st[1] == len(fr)
+
+
 def acyclic(n, fr, fc):
     parent = list(range(n))
 
