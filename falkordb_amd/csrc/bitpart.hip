@@ -38,10 +38,18 @@ constexpr u32 XP_SPAN = 768;       // a chunk spans < XP_SPAN of the key (entry 
 constexpr u32 XP_RUNW = 8;         //   <= XP_SPAN entries and <= XP_RUNS runs (the rows of its LDS tile)
 constexpr int XP_FOLD_THREADS = 512;   // 8 wavefronts share one copy of the checksum tables
 constexpr u32 XP_RUNS = XP_SPAN / XP_RUNW;
+constexpr u32 XP_NO_VTX = 0xFFFFFFFFu; // gvtx of a padded slot of the last dense group (rows < 0xFFFFFFC0)
 
 struct BpXPlan {
     bool usable = false;
-    u32 n = 0, ng = 0;             // rows of A' (destinations), 64-row groups
+    u32 n = 0, ng = 0;             // rows of A' (destinations), 64-row groups of the fold (of vertex ids, or of ranks: `dense`)
+    // dense groups (expand_xp_dense = 1): a row of A' without an entry never has a piece, and at RMAT-22 that is 52 % of the rows,
+    // spread evenly (scrambled ids) — in every group of 64 vertex ids about 33 lanes do the index work, and then the look-ups, of
+    // a row that is zero by construction.  The rows that HAVE an entry are ranked in vertex order, the group tables below are
+    // built over 64 consecutive RANKS, and gvtx names the vertex of a slot where the fold needs it (hash, label, touched bit).
+    int dense = 0;                 // the form the plan was built under (0: group g = vertices 64 g .. 64 g + 63, gvtx stays null)
+    u32 nd = 0;                    // rows of A' with at least one entry (dense form; ng = ceil(nd / 64))
+    u32* gvtx = nullptr;           // [ng * 64] vertex of slot 64 g + r, XP_NO_VTX past rank nd - 1 (a padded slot: no piece, no vertex)
     u64 nentries = 0;
     u32 nprows = 0;                // partial rows = runs = non-empty (partition, row) pairs
     u32 nchunks = 0;
@@ -54,7 +62,7 @@ struct BpXPlan {
     uint8_t* cshared = nullptr;    // 1: that run began in an earlier chunk (its pieces meet through atomics)
     u32* zrows = nullptr;          // the partial rows that receive pieces from several chunks (zeroed before every hop)
     u32 nzrows = 0;
-    u64* ne = nullptr;             // [8][ng] bit r: (partition, row 64 g + r) has entries in the stream
+    u64* ne = nullptr;             // [8][ng] bit r: (partition, row 64 g + r — dense: the row of slot 64 g + r) has entries in the stream
     u32* pbase = nullptr;          // [8][ng] partial row of the group's first non-empty row
     // direct entries (expand_xp_direct = 1): a (partition, row) run of ONE entry is left out of the stream — its partial row would
     // be a copy of one row of X, gathered, flushed through the tile, written and read back — and the fold reads that row of X
@@ -75,7 +83,7 @@ const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm : nullptr; }
 
 static void xp_free_buffers(fgpu_ctx* ctx, BpXPlan* p) {
     for (void** b : {(void**)&p->pcol, (void**)&p->pstart_dev, (void**)&p->cstart, (void**)&p->crun0, (void**)&p->cshared, (void**)&p->zrows,
-                     (void**)&p->ne, (void**)&p->pbase, (void**)&p->perm, (void**)&p->de, (void**)&p->dbase, (void**)&p->dcol}) {
+                     (void**)&p->ne, (void**)&p->pbase, (void**)&p->perm, (void**)&p->de, (void**)&p->dbase, (void**)&p->dcol, (void**)&p->gvtx}) {
         ctx->dev_free(*b);
         *b = nullptr;
     }
@@ -139,19 +147,33 @@ __global__ __launch_bounds__(256) void xp_run_tails_kernel(const uint2* __restri
 __global__ void xp_nonempty_kernel(const u32* __restrict__ off, u64 total, u32* __restrict__ nz) {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i <= total; i += (u64)gridDim.x * 256) nz[i] = (i < total && off[i + 1] != off[i]) ? 1u : 0u;
 }
-// a wavefront per (partition, group): the non-empty bitmap and the partial row of the group's first non-empty row
+// the dense form's slots: flag[v] = row v of A' has an entry (flag[n] = 0), and — after the exclusive scan of the flags —
+// gvtx[rank] = v.  (The slots of the last group past rank nd - 1 keep XP_NO_VTX from the memset.)
+__global__ void xp_has_entry_kernel(const u32* __restrict__ rowptr, u32 n, u32* __restrict__ flag) {
+    for (u32 v = blockIdx.x * 256 + threadIdx.x; v <= n; v += gridDim.x * 256) flag[v] = v < n && rowptr[v + 1] != rowptr[v] ? 1u : 0u;
+}
+__global__ void xp_slots_kernel(const u32* __restrict__ rank, u32 n, u32* __restrict__ gvtx) {
+    for (u32 v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
+        if (rank[v + 1] != rank[v]) gvtx[rank[v]] = v;
+}
+// a wavefront per (partition, group): the non-empty bitmap and the partial row of the group's first non-empty row.  Slot
+// 64 g + r is vertex 64 g + r (gvtx null, nslots = n) or the row of that rank (nslots = nd): the rows between two ranked
+// rows have no run in any partition, so the run index at the group's first row is the group's base in both forms.
 __global__ __launch_bounds__(256) void xp_groups_kernel(const u32* __restrict__ off, const u32* __restrict__ ridx, u32 n, u32 ng,
-                                                        u64* __restrict__ ne, u32* __restrict__ pbase) {
+                                                        const u32* __restrict__ gvtx, u32 nslots, u64* __restrict__ ne,
+                                                        u32* __restrict__ pbase) {
     const u32 lane = lane_id();
     const u32 wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
     for (u32 t = wave; t < 8 * ng; t += nwaves) {
         const u32 x = t / ng, g = t % ng;
-        const u32 v = g * 64 + lane;
-        const size_t i = (size_t)x * n + (v < n ? v : n - 1);
-        const u64 nw = __ballot(v < n && off[i + 1] != off[i]);
+        const u32 s = g * 64 + lane;
+        const bool live = s < nslots;
+        const u32 v = !live ? 0u : gvtx ? gvtx[s] : s;        // (lane 0 is always live)
+        const size_t i = (size_t)x * n + v;
+        const u64 nw = __ballot(live && off[i + 1] != off[i]);
         if (lane == 0) {
             ne[t] = nw;
-            pbase[t] = ridx[(size_t)x * n + (size_t)g * 64];
+            pbase[t] = ridx[i];
         }
     }
 }
@@ -203,16 +225,19 @@ __global__ void xp_split_kernel(const u32* __restrict__ pcol, const u32* __restr
 }
 // a wavefront per (partition, group), over the OLD run starts: the direct bitmap and the direct index of the group's first row
 __global__ __launch_bounds__(256) void xp_direct_groups_kernel(const u32* __restrict__ off, const u32* __restrict__ pos, u32 n, u32 ng,
-                                                               u64* __restrict__ de, u32* __restrict__ dbase) {
+                                                               const u32* __restrict__ gvtx, u32 nslots, u64* __restrict__ de,
+                                                               u32* __restrict__ dbase) {
     const u32 lane = lane_id();
     const u32 wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
     for (u32 t = wave; t < 8 * ng; t += nwaves) {
         const u32 x = t / ng, g = t % ng;
-        const u32 v = g * 64 + lane;
-        const size_t i = (size_t)x * n + (v < n ? v : n - 1);
-        const u64 dw = __ballot(v < n && off[i + 1] - off[i] == 1u);
+        const u32 s = g * 64 + lane;                         // (slots as in xp_groups_kernel)
+        const bool live = s < nslots;
+        const u32 v = !live ? 0u : gvtx ? gvtx[s] : s;
+        const size_t i = (size_t)x * n + v;
+        const u64 dw = __ballot(live && off[i + 1] - off[i] == 1u);
         if (lane == 0) {
-            const u32 o = off[(size_t)x * n + (size_t)g * 64];
+            const u32 o = off[i];
             de[t] = dw;
             dbase[t] = o - pos[o];
         }
@@ -247,37 +272,56 @@ __global__ void xp_rank_kernel(const u32* __restrict__ by_rank, u32 n, u32 prang
     for (u32 r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) perm[by_rank[r]] = (r & 7u) * prange + (r >> 3);
 }
 
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, const BpXPlan** out);
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, const BpXPlan** out);
 // The plan is an optional accelerator: when its build fails (its temporaries are large — 64 bytes per vertex and 8 per entry) the
 // half-built plan's buffers are freed, it stays attached as "not usable" (no second attempt per snapshot), the error is dropped
 // and the hop falls back to the plain pull.
-// A plan is kept per expand_xp_direct mode (a plan built under one mode is never handed to a hop expecting the other); the fold
-// takes the form of its plan.
+// A plan is kept per (expand_xp_direct, expand_xp_dense) pair (a plan built under one pair is never handed to a hop expecting
+// another); the fold takes the form of its plan.
 fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
-    const int direct = ctx->opt.expand_xp_direct ? 1 : 0;
-    const fgpu_info i = bp_xplan_build(ctx, m, t, direct, out);
+    const int direct = ctx->opt.expand_xp_direct ? 1 : 0, dense = ctx->opt.expand_xp_dense ? 1 : 0;
+    const int which = direct + 2 * dense;
+    const fgpu_info i = bp_xplan_build(ctx, m, t, direct, dense, out);
     if (i == FGPU_OK) return FGPU_OK;
     *out = nullptr;
-    if (t && t->bp_xplan[direct] && !t->bp_xplan[direct]->usable) {
-        xp_free_buffers(ctx, t->bp_xplan[direct]);
+    if (t && t->bp_xplan[which] && !t->bp_xplan[which]->usable) {
+        xp_free_buffers(ctx, t->bp_xplan[which]);
         (void)hipGetLastError();
         set_error("%s", "");
         return FGPU_OK;
     }
     return i;                                                // (failed before a plan was attached: an argument / state error)
 }
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, const BpXPlan** out) {
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, const BpXPlan** out) {
     *out = nullptr;
     if (!ctx->opt.expand_xcd || !t || t->is_hyper()) return FGPU_OK;
     if (t->ncols >= (1ull << 31) || t->nrows >= 0xFFFFFFC0ull || t->nnz < 4096 || t->nnz >= 0x7FFFFFFFull) return FGPU_OK;
     std::lock_guard<std::mutex> idx_guard(m->idx_mu);
-    if (t->bp_xplan[direct]) { if (t->bp_xplan[direct]->usable) *out = t->bp_xplan[direct]; return FGPU_OK; }
+    const int which = direct + 2 * dense;
+    if (t->bp_xplan[which]) { if (t->bp_xplan[which]->usable) *out = t->bp_xplan[which]; return FGPU_OK; }
     BpXPlan* xp = new (std::nothrow) BpXPlan();
     FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
-    t->bp_xplan[direct] = xp;                                  // (published as "not usable" until the build below completes)
-    const u32 n = (u32)t->nrows, ng = (n + 63) / 64;
-    xp->n = n; xp->ng = ng; xp->nentries = t->nnz; xp->direct = direct;
+    t->bp_xplan[which] = xp;                                   // (published as "not usable" until the build below completes)
+    const u32 n = (u32)t->nrows;
+    u32 ng = (n + 63) / 64, nslots = n;
+    xp->n = n; xp->nentries = t->nnz; xp->direct = direct; xp->dense = dense;
     hipStream_t st = ctx->stream();
+    if (dense) {   // the rows with an entry, ranked in vertex order: slot = rank, groups of 64 slots
+        DevBuf<u32> rank;
+        FGPU_TRY(rank.alloc(ctx, (size_t)n + 1));
+        hipLaunchKernelGGL(xp_has_entry_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, n, rank.p);
+        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(scan_u32(ctx, rank.p, rank.p, (u64)n + 1, nullptr));
+        FGPU_TRY(read_u32(ctx, rank.p + n, &xp->nd));
+        FGPU_REQUIRE(xp->nd >= 1 && xp->nd <= n, FGPU_INVALID, "partitioned pull: %u of %u rows have an entry", xp->nd, n);
+        nslots = xp->nd;
+        ng = (nslots + 63) / 64;
+        FGPU_TRY(ctx->dev_alloc((void**)&xp->gvtx, (size_t)ng * 64 * sizeof(u32)));
+        FGPU_HIP(hipMemsetAsync(xp->gvtx, 0xFF, (size_t)ng * 64 * sizeof(u32), st));    // XP_NO_VTX
+        hipLaunchKernelGGL(xp_slots_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)rank.p, n, xp->gvtx);
+        FGPU_HIP(hipGetLastError());
+    }
+    xp->ng = ng;
     const u64 total = 8ull * n;
     DevBuf<u32> off, ridx;
     FGPU_TRY(off.alloc(ctx, total + 1));
@@ -335,7 +379,8 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(ctx->dev_alloc((void**)&xp->dbase, ((size_t)8 * ng + 1) * sizeof(u32)));
         u32 ggrid = cdiv((u64)8 * ng, 4);
         if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
-        hipLaunchKernelGGL(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng, xp->de, xp->dbase);
+        hipLaunchKernelGGL(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng,
+                           (const u32*)xp->gvtx, nslots, xp->de, xp->dbase);
         FGPU_HIP(hipGetLastError());
         hipLaunchKernelGGL(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev);
         FGPU_HIP(hipGetLastError());
@@ -359,7 +404,8 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     FGPU_TRY(ctx->dev_alloc((void**)&xp->pbase, ((size_t)8 * ng + 1) * sizeof(u32)));
     u32 ggrid = cdiv((u64)8 * ng, 4);
     if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
-    hipLaunchKernelGGL(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng, xp->ne, xp->pbase);
+    hipLaunchKernelGGL(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng,
+                       (const u32*)xp->gvtx, nslots, xp->ne, xp->pbase);
     FGPU_HIP(hipGetLastError());
     FGPU_TRY(ctx->dev_alloc((void**)&xp->cstart, ((size_t)xp->nchunks + 1) * sizeof(u32)));
     FGPU_TRY(ctx->dev_alloc((void**)&xp->crun0, ((size_t)xp->nchunks + 1) * sizeof(u32)));
@@ -530,12 +576,39 @@ __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ 
 __device__ __forceinline__ u64 xp_uniform64(u64 v) {
     return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32)) << 32) | (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)v);
 }
-template <int QL, int MODE, bool NT, bool DIRECT>
+// DENSE: the groups are 64 consecutive slots of the plan's gvtx (the rows that have an entry), and lane r's slot names its
+// vertex — what the hash, the label bit and the touched bit are taken from.  The touched and label words then differ by lane:
+// each lane gathers its own (only when a bitmap exists: wave-uniform, and not on the clean path), a ballot turns the bits into
+// the group's 64-bit words that the rest of the fold tests as before, and the side-buffer slot of a touched row, which no
+// longer follows from the group's word, is computed by the row's lane and taken by a shuffle.  A padded slot has no piece and
+// reads nothing through its gvtx entry.
+struct XpLaneRow {
+    u32 vh;    // the vertex of this lane's row (0 on a padded slot: multiplied by an all-zero row)
+    u32 sl;    // its side-buffer slot when it is touched
+    u64 tw, lb;   // (wave-uniform) the group's touched rows and rows inside the label
+};
+__device__ __forceinline__ XpLaneRow xp_lane_row(u32 v, const BpFinal& fin) {
+    XpLaneRow o;
+    const bool live = v != XP_NO_VTX;
+    const u32 vw = live ? v >> 6 : 0u, vb = v & 63u;
+    o.vh = live ? v : 0u;
+    o.sl = 0;
+    o.tw = 0ull;
+    o.lb = ~0ull;
+    if (fin.tbits) {
+        const u64 t = fin.tbits[vw];
+        o.sl = fin.tpref[vw] + (u32)__popcll(t & ((1ull << vb) - 1ull));
+        o.tw = __ballot(live && ((t >> vb) & 1ull));
+    }
+    if (fin.label) o.lb = __ballot(live && ((fin.label[vw] >> vb) & 1ull));
+    return o;
+}
+template <int QL, int MODE, bool NT, bool DIRECT, bool DENSE>
 __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __restrict__ ne, const u32* __restrict__ pbase, u32 ng,
                                                       const uint4* __restrict__ partial, BpFinal fin, uint4* __restrict__ side,
                                                       u32 zrow /* an all-zero partial row */, const u64* __restrict__ de,
                                                       const u32* __restrict__ dbase, const u32* __restrict__ dcol,
-                                                      const uint4* __restrict__ x) {
+                                                      const uint4* __restrict__ x, const u32* __restrict__ gvtx) {
     constexpr int SLOTS = 64 / QL;
     extern __shared__ u64 s_tab[];
     if (MODE == 2) {
@@ -558,6 +631,7 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
             pb[k] = (u32)__builtin_amdgcn_readfirstlane((int)pbase[(size_t)k * ng + g]);
             any |= nw[k];
         }
+        const u32 gv = DENSE ? gvtx[(size_t)g * 64 + lane] : 0u;   // lane r: the vertex of row r (one coalesced load with the header)
         if (DIRECT) {
             // lane k < 8 loads partition k's direct word and base (two loads, one round trip) and every lane takes them by
             // shuffles: they stay in vector registers — as 24 more scalars next to nw / pb they ran the kernel out of SGPRs, and
@@ -581,9 +655,18 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
             for (int k = 0; k < 8; ++k)     // lane r: the column of (partition k, row 64 g + r) when that is a direct entry
                 dc[k] = dcol[((dw[k] >> lane) & 1ull) ? dc[k] + (u32)__popcll(dw[k] & lanes_below) : 0u];
         }
-        const u64 tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
-        const u32 tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
-        const u64 lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
+        u64 tw, lb;
+        u32 tp = 0;
+        XpLaneRow lr = {0u, 0u, 0ull, 0ull};
+        if (DENSE) {
+            lr = xp_lane_row(gv, fin);
+            tw = xp_uniform64(lr.tw);
+            lb = xp_uniform64(lr.lb);
+        } else {
+            tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
+            tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
+            lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
+        }
         // Where the time goes (PMC, round 6, checksum on): not the partial rows — two steps of loads in flight changed nothing —
         // but LDS: 83 % of the LDS-active cycles were bank conflicts.  With a row's words spread over QL lanes, one look-up
         // instruction reads 2 QL different tables, and entry e of EVERY table sits in the same bank pair: 64 random 8-byte reads
@@ -620,8 +703,9 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
             uint4 a = or4(or4(or4(pv[0], pv[1]), or4(pv[2], pv[3])), or4(or4(pv[4], pv[5]), or4(pv[6], pv[7])));
             const bool touched = (tw >> r) & 1ull;
             const bool counted = !touched && ((lb >> r) & 1ull);
+            const u32 slr = DENSE && tw ? (u32)__shfl((int)lr.sl, (int)r, 64) : 0u;   // (every lane: before the branch)
             if (touched && any4(a)) {
-                const u32 sl = tp + (u32)__popcll(tw & below);
+                const u32 sl = DENSE ? slr : tp + (u32)__popcll(tw & below);
                 side[(size_t)sl * QL + wl] = a;              // the only writer of this slot before the delta fix-ups
             }
             const u32 pc = (u32)(__popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w));
@@ -644,7 +728,7 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
                     for (int j = 0; j < 16; ++j) rs += t0[j * 16 + (u32)((w0 >> (4 * j)) & 15ull)];
 #pragma unroll
                     for (int j = 0; j < 16; ++j) rs += t1[j * 16 + (u32)((w1 >> (4 * j)) & 15ull)];
-                    f_sum += rs * cs_dest_hash(g * 64 + r);
+                    f_sum += rs * cs_dest_hash(DENSE ? (u32)__shfl((int)lr.vh, (int)r, 64) : g * 64 + r);
                 }
             }
         }
@@ -665,7 +749,8 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
                 for (int j = 0; j < 16; ++j) rs += tk[j * 16 + (u32)((w >> (4 * j)) & 15ull)];
             }
             rs += (u64)__shfl_xor((long long)rs, 32, 64);                 // the two halves of a row
-            if (hw == 0 && on) f_sum += rs * cs_dest_hash(g * 64 + hf0 + row);
+            const u32 vr = DENSE ? (u32)__shfl((int)lr.vh, (int)(hf0 + row), 64) : g * 64 + hf0 + row;
+            if (hw == 0 && on) f_sum += rs * cs_dest_hash(vr);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // (read before the next half overwrites the stage)
             __builtin_amdgcn_wave_barrier();
         }
@@ -687,11 +772,12 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_kernel(const u64* __r
 constexpr u32 XP_PIECE_X = 0x80000000u;   // bit 31 of a list entry: a row of X (partial rows < nnz < 2^31, slots of X < ncols < 2^31)
 constexpr u32 XP_HALF_PIECES = 32 * 8;    // a half group's list: 32 rows x 8 partitions
 constexpr int XP_INFL = 4;
-template <int QL, int MODE, bool NT, bool DIRECT>
+template <int QL, int MODE, bool NT, bool DIRECT, bool DENSE>
 __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u64* __restrict__ ne, const u32* __restrict__ pbase, u32 ng,
                                                              const uint4* __restrict__ partial, BpFinal fin, uint4* __restrict__ side,
                                                              const u64* __restrict__ de, const u32* __restrict__ dbase,
-                                                             const u32* __restrict__ dcol, const uint4* __restrict__ x) {
+                                                             const u32* __restrict__ dcol, const uint4* __restrict__ x,
+                                                             const u32* __restrict__ gvtx /* DENSE: see xp_fold_kernel */) {
     constexpr u32 SLOTS = 64 / QL;
     constexpr u32 STR = 2 * QL + 1;                          // stage row stride in words (odd: a lane per row reads without conflicts)
     constexpr u32 NW = XP_FOLD_THREADS / 64;
@@ -721,6 +807,7 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u
             pb[k] = (u32)__builtin_amdgcn_readfirstlane((int)pbase[(size_t)k * ng + g]);
             any |= nw[k];
         }
+        const u32 gv = DENSE ? gvtx[(size_t)g * 64 + lane] : 0u;   // lane r: the vertex of row r (one coalesced load with the header)
         if (DIRECT) {   // (lane k < 8 loads partition k's direct word and base: see xp_fold_kernel)
             const size_t kl = (size_t)(lane & 7u) * ng + g;
             const u64 dl = de[kl];
@@ -756,9 +843,18 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u
             have |= bit << k;
             pref += nb;
         }
-        const u64 tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
-        const u32 tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
-        const u64 lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
+        u64 tw, lb;
+        u32 tp = 0;
+        XpLaneRow lr = {0u, 0u, 0ull, 0ull};
+        if (DENSE) {
+            lr = xp_lane_row(gv, fin);
+            tw = xp_uniform64(lr.tw);
+            lb = xp_uniform64(lr.lb);
+        } else {
+            tw = fin.tbits ? xp_uniform64(fin.tbits[g]) : 0ull;      // (clean layers: no touched rows, no bitmap)
+            tp = fin.tbits ? (u32)__builtin_amdgcn_readfirstlane((int)fin.tpref[g]) : 0u;
+            lb = fin.label ? xp_uniform64(fin.label[g]) : ~0ull;
+        }
         const u32 tot0 = (u32)__builtin_amdgcn_readlane((int)pref, 32);   // pieces of rows 0 .. 31
         const u32 tot = (u32)__builtin_amdgcn_readlane((int)(pref + (u32)__popc(have)), 63);
 #pragma unroll 1
@@ -815,10 +911,11 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u
             if (twh) {
                 for (u32 r0 = 0; r0 < 32; r0 += SLOTS) {
                     const u32 r = r0 + slot;
+                    const u32 slr = DENSE ? (u32)__shfl((int)lr.sl, (int)((32 * hf + r) & 63u), 64) : 0u;   // (every lane: before the branch)
                     if (r < 32 && ((twh >> r) & 1u)) {
                         const u64 w0 = stg[(size_t)r * STR + 2 * wl], w1 = stg[(size_t)r * STR + 2 * wl + 1];
                         if (w0 | w1) {
-                            const u32 sl = tp + (u32)__popcll(tw & ((1ull << (32 * hf + r)) - 1ull));
+                            const u32 sl = DENSE ? slr : tp + (u32)__popcll(tw & ((1ull << (32 * hf + r)) - 1ull));
                             side[(size_t)sl * QL + wl] = make_uint4((u32)w0, (u32)(w0 >> 32), (u32)w1, (u32)(w1 >> 32));   // the only writer of this slot
                         }
                     }
@@ -856,7 +953,8 @@ __global__ __launch_bounds__(XP_FOLD_THREADS) void xp_fold_pieces_kernel(const u
             f_cnt += (u64)pc;
             if (MODE == 2) {
                 rs += (u64)__shfl_xor((long long)rs, 32, 64);                 // the two halves of a row
-                if (hw == 0) f_sum += rs * cs_dest_hash(g * 64 + rg);
+                const u32 vr = DENSE ? (u32)__shfl((int)lr.vh, (int)rg, 64) : g * 64 + rg;
+                if (hw == 0) f_sum += rs * cs_dest_hash(vr);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");           // (cleared before the next half ORs into the stage)
             __builtin_amdgcn_wave_barrier();
@@ -884,7 +982,9 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
                          u64* side, size_t lds_tables, u64 xrows) {
     FGPU_REQUIRE(xp && xp->usable && ws >= 2 && ws <= 16 && (ws & (ws - 1)) == 0, FGPU_INVALID, "partitioned pull: bad plan / row width");
     FGPU_REQUIRE(mode == 1 || mode == 2, FGPU_INVALID, "partitioned pull: counting hops only");
+    FGPU_REQUIRE(!xp->dense == !xp->gvtx, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
     ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
+    ctx->xp_last_groups.store(xp->ng, std::memory_order_relaxed);
     const u32 ql = ws / 2;
     hipStream_t st = ctx->stream();
     DevBuf<uint4> partial;
@@ -946,28 +1046,29 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
         (pieces ? ctx->xp_piece_folds : ctx->xp_slot_folds).fetch_add(1, std::memory_order_relaxed);
         const size_t lds = xp_fold_lds(ws, mode, lds_tables, pieces);
         FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID, "partitioned pull: the fold needs %zu B of LDS", lds);
-#define XP_FOLD4(Q, M, N, D)                                                                                                     \
+#define XP_FOLD4(Q, M, N, D, G)                                                                                                  \
         do {                                                                                                                     \
             if (lds > 48 * 1024)                                                                                                 \
-                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_kernel<Q, M, N, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((xp_fold_kernel<Q, M, N, D>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase, xp->ng,  \
+                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_kernel<Q, M, N, D, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((xp_fold_kernel<Q, M, N, D, G>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase, xp->ng,  \
                                (const uint4*)partial.p, fin, (uint4*)side, xp->nprows, (const u64*)xp->de, (const u32*)xp->dbase,                 \
-                               (const u32*)xp->dcol, (const uint4*)x);                                                                             \
+                               (const u32*)xp->dcol, (const uint4*)x, (const u32*)xp->gvtx);                                                       \
         } while (0)
-#define XP_PIECES4(Q, M, N, D)                                                                                                   \
+#define XP_PIECES4(Q, M, N, D, G)                                                                                                \
         do {                                                                                                                     \
             if (lds > 48 * 1024)                                                                                                 \
-                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_pieces_kernel<Q, M, N, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((xp_fold_pieces_kernel<Q, M, N, D>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase,  \
+                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_pieces_kernel<Q, M, N, D, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((xp_fold_pieces_kernel<Q, M, N, D, G>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase,  \
                                xp->ng, (const uint4*)partial.p, fin, (uint4*)side, (const u64*)xp->de, (const u32*)xp->dbase,                  \
-                               (const u32*)xp->dcol, (const uint4*)x);                                                                          \
+                               (const u32*)xp->dcol, (const uint4*)x, (const u32*)xp->gvtx);                                                    \
         } while (0)
-#define XP_FOLD3(Q, M, N)                                                                                                        \
+#define XP_FOLD35(Q, M, N, G)                                                                                                    \
         do {                                                                                                                     \
-            if (pieces) { if (xp->direct) XP_PIECES4(Q, M, N, true); else XP_PIECES4(Q, M, N, false); }                          \
-            else if (xp->direct) XP_FOLD4(Q, M, N, true);                                                                        \
-            else XP_FOLD4(Q, M, N, false);                                                                                       \
+            if (pieces) { if (xp->direct) XP_PIECES4(Q, M, N, true, G); else XP_PIECES4(Q, M, N, false, G); }                    \
+            else if (xp->direct) XP_FOLD4(Q, M, N, true, G);                                                                     \
+            else XP_FOLD4(Q, M, N, false, G);                                                                                    \
         } while (0)
+#define XP_FOLD3(Q, M, N) do { if (xp->dense) XP_FOLD35(Q, M, N, true); else XP_FOLD35(Q, M, N, false); } while (0)
 #define XP_FOLD2(Q, M) do { if (ctx->opt.expand_nt & 4) XP_FOLD3(Q, M, true); else XP_FOLD3(Q, M, false); } while (0)
 #define XP_FOLD(Q) do { if (mode == 2) XP_FOLD2(Q, 2); else XP_FOLD2(Q, 1); } while (0)
         switch (ql) {
@@ -979,6 +1080,7 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
 #undef XP_FOLD
 #undef XP_FOLD2
 #undef XP_FOLD3
+#undef XP_FOLD35
 #undef XP_FOLD4
 #undef XP_PIECES4
         FGPU_HIP(hipGetLastError());

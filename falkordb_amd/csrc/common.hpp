@@ -112,6 +112,8 @@ struct fgpu_options {  // fgpu_set_option
     int expand_xp_fold_min_words = 8; // ... the piece fold runs on bit rows of at least this many 64-bit words, narrower rows keep the slot
                                // fold: at 2 and 4 words the piece fold is 30 us per launch SLOWER (its fixed work per group outweighs
                                // the few look-ups of a narrow row), at 8 it is 24 us faster, at 16 103 us (profiles/NOTES_r12.md section 3.5)
+    int expand_xp_dense = 1;    // ... the fold's groups: 1 = 64 consecutive RANKS among the rows that have an in-edge (at RMAT-22 48 % of
+                               // the rows: half the groups, no lane on a row that cannot hold a piece), 0 = 64 consecutive vertex ids (A/B)
     int expand_scan_min = 2048; // fgpu_expand_count: a call with more source rows than this is a WHOLE-FRONTIER call (spgemm.hip
                                // expand_count_scan): live rows filtered and compacted on the device, cut into passes (0 = never)
     int expand_scan_rows = 1024; // ... live rows per pass: 1024 = 16 words = one 128-byte line per vertex of the bit state
@@ -198,6 +200,7 @@ struct fgpu_ctx {
     std::atomic<uint32_t> scan_last_live{0}, scan_last_passes{0};   // the last such call: live source rows, passes ("expand_scan_*")
     std::atomic<uint64_t> xp_piece_folds{0}, xp_slot_folds{0};   // launches of the two folds so far ("expand_xp_piece_folds" / "expand_xp_slot_folds")
     std::atomic<uint64_t> xp_last_direct{0};    // single-entry runs the fold read from X in the last partitioned count hop ("expand_xp_last_direct")
+    std::atomic<uint64_t> xp_last_groups{0};    // 64-row groups the fold of the last partitioned count hop looped over ("expand_xp_last_groups")
     std::atomic<uint64_t> hc_last_entries{0}, hc_last_gathered{0};   // the last fgpu_harmonic call: entries of the recomputed rows, sketches gathered ("harmonic_last_*")
     std::atomic<uint64_t> msf_round_entries[32] = {};   // the last fgpu_msf call: entries read in round k, the rounds past 31 in [31] ("msf_last_entries_round<k>")
     std::atomic<uint64_t> expand_launches{0};   // kernels launched by fgpu_expand* (fgpu_get_option "expand_kernel_launches")
@@ -384,9 +387,10 @@ struct fgpu_mat {
     mutable uint32_t n_bp_sitems = 0;
     mutable uint64_t* bp_split_bits = nullptr;  // on the cached transpose: bit v set <=> row v is cut into several items
     mutable fgpu::PrParts* pr_parts = nullptr;  // pagerank.hip: this matrix split into 8 column ranges (one per XCD), lazily, owned
-    mutable fgpu::BpXPlan* bp_xplan[2] = {nullptr, nullptr};   // on the cached transpose: the XCD-partitioned layout of the dense
-                                               // count hop, one per expand_xp_direct mode (bitpart.hip, built on the first such hop
-                                               // under that mode; released by bp_xplan_release)
+    mutable fgpu::BpXPlan* bp_xplan[4] = {nullptr, nullptr, nullptr, nullptr};   // on the cached transpose: the XCD-partitioned
+                                               // layout of the dense count hop, one per (expand_xp_direct, expand_xp_dense) pair —
+                                               // index direct + 2 x dense (bitpart.hip, built on the first such hop under that pair;
+                                               // released by bp_xplan_release)
     bool is_hyper() const { return hrows != nullptr; }
 };
 

@@ -821,6 +821,8 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     else if (!strcmp(name, "expand_xp_piece_folds")) *value = (int64_t)ctx->xp_piece_folds.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_xp_slot_folds")) *value = (int64_t)ctx->xp_slot_folds.load(std::memory_order_relaxed);
     else if (!strcmp(name, "expand_xp_last_direct")) *value = (int64_t)ctx->xp_last_direct.load(std::memory_order_relaxed);
+    else if (!strcmp(name, "expand_xp_dense")) *value = ctx->opt.expand_xp_dense;
+    else if (!strcmp(name, "expand_xp_last_groups")) *value = (int64_t)ctx->xp_last_groups.load(std::memory_order_relaxed);
     else if (!strcmp(name, "harmonic_last_entries")) *value = (int64_t)ctx->hc_last_entries.load(std::memory_order_relaxed);
     else if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32)
         *value = (int64_t)ctx->msf_round_entries[atoi(name + 22)].load(std::memory_order_relaxed);
@@ -878,6 +880,9 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     } else if (!strcmp(name, "expand_xp_direct")) {
         FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_direct must be 0 (every run streamed) or 1 (single-entry runs read by the fold)");
         ctx->opt.expand_xp_direct = (int)value;
+    } else if (!strcmp(name, "expand_xp_dense")) {
+        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_dense must be 0 (groups of 64 vertex ids) or 1 (groups of 64 rows that have an in-edge)");
+        ctx->opt.expand_xp_dense = (int)value;
     } else if (!strcmp(name, "expand_xp_fold")) {
         FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_fold must be 0 (a slot per row and step) or 1 (a slot per existing piece)");
         ctx->opt.expand_xp_fold = (int)value;

@@ -131,7 +131,10 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  * the piece fold runs on bit rows of at least this many 64-bit words — 2, 4, 8, 16, or 32 for none — and narrower rows keep the
  * slot fold), "expand_xp_piece_folds" / "expand_xp_slot_folds" (launches of either fold on this context so far: which fold a
  * call ran, and that the partitioned hop ran at all, is a difference of two reads), "expand_xp_direct" and "expand_xp_last_direct" (entries of A' the last XCD-partitioned count hop
- * read straight from X as single-entry runs, 0 when its plan streams every run), "expand_xcd", "expand_xcd_relabel" and
+ * read straight from X as single-entry runs, 0 when its plan streams every run), "expand_xp_dense" (set through fgpu_set_option:
+ * 1 = the fold's groups are 64 consecutive ranks among the destination rows that have an in-edge, 0 = 64 consecutive vertex
+ * ids; results are identical) and "expand_xp_last_groups" (groups the fold of the last partitioned count hop looped over:
+ * ceil(rows with an in-edge / 64) or ceil(rows / 64)), "expand_xcd", "expand_xcd_relabel" and
  * "expand_xcd_min_mb" (the settings of the partitioned count hop, so that a caller can put back what it found), "expand_mode",
  * "expand_nt", "wcc_mode", "bc_batch", "bc_direction".  Unknown
  * names return FGPU_INVALID. */
