@@ -791,185 +791,54 @@ fgpu_info fgpu_prof_read(fgpu_ctx* ctx, const char** names, double* ms, uint64_t
     return FGPU_OK;
 }
 
+// Read-only counters of the context ("<name>" of fgpu_get_option); the settable options are the table of options.hpp.
+struct CounterRow {
+    const char* name;
+    int64_t (*load)(const fgpu_ctx*);
+};
+#define FGPU_COUNTER(name, member) \
+    {name, [](const fgpu_ctx* c) { return (int64_t)c->member.load(std::memory_order_relaxed); }}
+static const CounterRow COUNTERS[] = {
+    FGPU_COUNTER("dist_self_calls", dist_self_calls),
+    FGPU_COUNTER("expand_kernel_launches", expand_launches),
+    FGPU_COUNTER("bfs_cp_last_mask", bfs_cp_last),
+    FGPU_COUNTER("bfs_pb_last_levels", bfs_pb_last),
+    FGPU_COUNTER("expand_scan_last_live", scan_last_live),
+    FGPU_COUNTER("expand_scan_last_passes", scan_last_passes),
+    FGPU_COUNTER("expand_xp_piece_folds", xp_piece_folds),
+    FGPU_COUNTER("expand_xp_slot_folds", xp_slot_folds),
+    FGPU_COUNTER("expand_xp_last_direct", xp_last_direct),
+    FGPU_COUNTER("expand_xp_last_groups", xp_last_groups),
+    FGPU_COUNTER("harmonic_last_entries", hc_last_entries),
+    FGPU_COUNTER("harmonic_last_gathered", hc_last_gathered),
+};
+#undef FGPU_COUNTER
+
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     FGPU_REQUIRE(ctx && name && value, FGPU_NULL_POINTER, "fgpu_get_option: NULL argument");
-    if (!strcmp(name, "dist_force_self")) *value = ctx->opt.dist_force_self;
-    else if (!strcmp(name, "dist_self_calls")) *value = (int64_t)ctx->dist_self_calls.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "dist_collective")) *value = ctx->opt.dist_collective;
-    else if (!strcmp(name, "expand_kernel_launches")) *value = (int64_t)ctx->expand_launches.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_mode")) *value = ctx->opt.expand_mode;
-    else if (!strcmp(name, "expand_scan_min")) *value = ctx->opt.expand_scan_min;
-    else if (!strcmp(name, "expand_scan_rows")) *value = ctx->opt.expand_scan_rows;
-    else if (!strcmp(name, "expand_scan_lanes")) *value = ctx->opt.expand_scan_lanes;
-    else if (!strcmp(name, "expand_nt")) *value = ctx->opt.expand_nt;
-    else if (!strcmp(name, "expand_xcd")) *value = ctx->opt.expand_xcd ? 1 : 0;
-    else if (!strcmp(name, "expand_xcd_relabel")) *value = ctx->opt.expand_xcd_relabel ? 1 : 0;
-    else if (!strcmp(name, "expand_xcd_min_mb")) *value = ctx->opt.expand_xcd_min_mb;
-    else if (!strcmp(name, "bfs_pb"))*value = ctx->opt.bfs_pb;
-    else if (!strcmp(name, "wcc_mode")) *value = ctx->opt.wcc_mode;
-    else if (!strcmp(name, "bc_batch")) *value = ctx->opt.bc_batch;
-    else if (!strcmp(name, "bc_direction")) *value = ctx->opt.bc_direction;
-    else if (!strcmp(name, "maxflow_global_every")) *value = ctx->opt.maxflow_global_every;
-    else if (!strcmp(name, "bfs_pb_min_edges")) *value = ctx->opt.bfs_pb_min_edges;
-    else if (!strcmp(name, "bfs_cp_last_mask")) *value = ctx->bfs_cp_last.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "bfs_pb_last_levels")) *value = ctx->bfs_pb_last.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_scan_last_live")) *value = ctx->scan_last_live.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_scan_last_passes")) *value = ctx->scan_last_passes.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_xp_direct")) *value = ctx->opt.expand_xp_direct;
-    else if (!strcmp(name, "expand_xp_fold")) *value = ctx->opt.expand_xp_fold;
-    else if (!strcmp(name, "expand_xp_fold_min_words")) *value = ctx->opt.expand_xp_fold_min_words;
-    else if (!strcmp(name, "expand_xp_piece_folds")) *value = (int64_t)ctx->xp_piece_folds.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_xp_slot_folds")) *value = (int64_t)ctx->xp_slot_folds.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_xp_last_direct")) *value = (int64_t)ctx->xp_last_direct.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "expand_xp_dense")) *value = ctx->opt.expand_xp_dense;
-    else if (!strcmp(name, "expand_xp_last_groups")) *value = (int64_t)ctx->xp_last_groups.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "harmonic_last_entries")) *value = (int64_t)ctx->hc_last_entries.load(std::memory_order_relaxed);
-    else if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32)
+    if (const OptRow* r = opt_find(name)) { *value = opt_load(ctx->opt, *r); return FGPU_OK; }
+    for (const CounterRow& c : COUNTERS)
+        if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
+    if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32) {
         *value = (int64_t)ctx->msf_round_entries[atoi(name + 22)].load(std::memory_order_relaxed);
-    else if (!strcmp(name, "harmonic_last_gathered")) *value = (int64_t)ctx->hc_last_gathered.load(std::memory_order_relaxed);
-    else { set_error("fgpu_get_option: unknown name '%s'", name); return FGPU_INVALID; }
-    return FGPU_OK;
+        return FGPU_OK;
+    }
+    set_error("fgpu_get_option: unknown name '%s'", name);
+    return FGPU_INVALID;
 }
 
 fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     FGPU_REQUIRE(ctx && name, FGPU_NULL_POINTER, "fgpu_set_option: NULL argument");
     ctx->opt_epoch.fetch_add(1, std::memory_order_relaxed);
-    if (!strcmp(name, "tiled_u")) {
-        FGPU_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, FGPU_INVALID,
-                     "tiled_u must be 1, 2, 4 or 8");
-        ctx->opt.tiled_u = (int)value;
-    } else if (!strcmp(name, "bfs_wgs_per_cu")) {
-        FGPU_REQUIRE(value >= 1 && value <= 64, FGPU_INVALID, "bfs_wgs_per_cu out of range");
-        ctx->opt.bfs_wgs_per_cu = (int)value;
-    } else if (!strcmp(name, "expand_mode")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "expand_mode must be 0 (auto), 1 (sorted CSR) or 2 (bit-parallel)");
-        ctx->opt.expand_mode = (int)value;
-    } else if (!strcmp(name, "transpose_wb")) {
+    if (!strcmp(name, "transpose_wb")) {   // process-wide, no field and no range: not a row of the table
         ks_set_wb_override((int)value);
-
-    } else if (!strcmp(name, "expand_row_groups")) {
-        ctx->opt.expand_row_groups = value != 0;
-    } else if (!strcmp(name, "expand_fuse_count")) {
-        ctx->opt.expand_fuse_count = value != 0;
-    } else if (!strcmp(name, "expand_compact")) {
-        ctx->opt.expand_compact = value != 0;
-    } else if (!strcmp(name, "pagerank_parts")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "pagerank_parts must be 0 (off), 1 (by size) or 2 (always)");
-        ctx->opt.pagerank_parts = (int)value;
-    } else if (!strcmp(name, "wcc_mode")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "wcc_mode must be 0 (auto), 1 (Afforest) or 2 (full pass)");
-        ctx->opt.wcc_mode = (int)value;
-    } else if (!strcmp(name, "bc_batch")) {
-        FGPU_REQUIRE(value >= 0 && value <= 64, FGPU_INVALID, "bc_batch must be 0 (auto) or 1-64 sources per batch");
-        ctx->opt.bc_batch = (int)value;
-    } else if (!strcmp(name, "bc_direction")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "bc_direction must be 0 (auto), 1 (push) or 2 (pull)");
-        ctx->opt.bc_direction = (int)value;
-    } else if (!strcmp(name, "maxflow_global_every")) {
-        FGPU_REQUIRE(value >= 0 && value <= (1 << 20), FGPU_INVALID, "maxflow_global_every must be 0 (default) or a pulse count");
-        ctx->opt.maxflow_global_every = (int)value;
-    } else if (!strcmp(name, "expand_first_hop")) {
-        ctx->opt.expand_first_hop = value != 0;
-    } else if (!strcmp(name, "expand_xcd")) {
-        ctx->opt.expand_xcd = value != 0;
-    } else if (!strcmp(name, "expand_xcd_relabel")) {
-        ctx->opt.expand_xcd_relabel = value != 0;
-    } else if (!strcmp(name, "expand_xcd_min_mb")) {
-        FGPU_REQUIRE(value >= 0 && value <= (1 << 20), FGPU_INVALID, "expand_xcd_min_mb out of range");
-        ctx->opt.expand_xcd_min_mb = (int)value;
-    } else if (!strcmp(name, "expand_xp_direct")) {
-        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_direct must be 0 (every run streamed) or 1 (single-entry runs read by the fold)");
-        ctx->opt.expand_xp_direct = (int)value;
-    } else if (!strcmp(name, "expand_xp_dense")) {
-        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_dense must be 0 (groups of 64 vertex ids) or 1 (groups of 64 rows that have an in-edge)");
-        ctx->opt.expand_xp_dense = (int)value;
-    } else if (!strcmp(name, "expand_xp_fold")) {
-        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "expand_xp_fold must be 0 (a slot per row and step) or 1 (a slot per existing piece)");
-        ctx->opt.expand_xp_fold = (int)value;
-    } else if (!strcmp(name, "expand_xp_fold_min_words")) {
-        FGPU_REQUIRE(value >= 2 && value <= 32 && (value & (value - 1)) == 0, FGPU_INVALID,
-                     "expand_xp_fold_min_words must be 2, 4, 8, 16 or 32 (32: no row is that wide, the slot fold everywhere)");
-        ctx->opt.expand_xp_fold_min_words = (int)value;
-    } else if (!strcmp(name, "expand_scan_min")) {
-        FGPU_REQUIRE(value >= 0 && value <= (1ll << 31), FGPU_INVALID, "expand_scan_min out of range");
-        ctx->opt.expand_scan_min = (int)value;
-    } else if (!strcmp(name, "expand_scan_rows")) {
-        FGPU_REQUIRE(value >= 64 && value <= 4096 && (value & (value - 1)) == 0, FGPU_INVALID,
-                     "expand_scan_rows must be a power of two in 64 .. 4096");
-        ctx->opt.expand_scan_rows = (int)value;
-    } else if (!strcmp(name, "expand_scan_lanes")) {
-        FGPU_REQUIRE(value >= 1 && value <= 16, FGPU_INVALID, "expand_scan_lanes must be 1 .. 16");
-        ctx->opt.expand_scan_lanes = (int)value;
-    } else if (!strcmp(name, "expand_emit_sort")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "expand_emit_sort is 0 (ballot transpose), 1 (by density) or 2 (pairs + sort)");
-        ctx->opt.expand_emit_sort = (int)value;
-    } else if (!strcmp(name, "expand_records")) {
-        ctx->opt.expand_records = value != 0;
-    } else if (!strcmp(name, "expand_nt")) {
-        FGPU_REQUIRE(value >= 0 && value <= 7, FGPU_INVALID, "expand_nt is a mask of 1 | 2 | 4");
-        ctx->opt.expand_nt = (int)value;
-    } else if (!strcmp(name, "expand_bits_ratio")) {
-        FGPU_REQUIRE(value >= 1 && value <= 1024, FGPU_INVALID, "expand_bits_ratio out of range");
-        ctx->opt.expand_bits_ratio = (int)value;
-    } else if (!strcmp(name, "blocked_variant")) {
-        FGPU_REQUIRE(value >= 0 && value <= 3, FGPU_INVALID, "blocked_variant must be 0..3");
-        ctx->opt.blocked_variant = (int)value;
-    } else if (!strcmp(name, "tiled_layout")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "tiled_layout must be 0 (auto), 1 (tiled) or 2 (blocked)");
-        ctx->opt.tiled_layout = (int)value;
-    } else if (!strcmp(name, "bfs_tiny")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "bfs_tiny must be 0, 1 or 2");
-        ctx->opt.bfs_tiny = (int)value;
-    } else if (!strcmp(name, "bfs_alive_rule")) {
-        ctx->opt.bfs_alive_rule = value != 0;
-    } else if (!strcmp(name, "bfs_pb")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID, "bfs_pb must be 0, 1 or 2");
-        ctx->opt.bfs_pb = (int)value;
-    } else if (!strcmp(name, "bfs_pb_min_edges")) {
-        FGPU_REQUIRE(value >= 1, FGPU_INVALID, "bfs_pb_min_edges must be positive");
-        ctx->opt.bfs_pb_min_edges = (long long)value;
-    } else if (!strcmp(name, "bfs_prof_split")) {
-        ctx->opt.bfs_prof_split = value != 0;
-    } else if (!strcmp(name, "bfs_hub_first")) {
-        ctx->opt.bfs_hub_first = value != 0;
-    } else if (!strcmp(name, "dist_timing")) {
-        ctx->opt.dist_timing = value != 0;
-    } else if (!strcmp(name, "pinned_results")) {
-        ctx->opt.pinned_results = value != 0;
-    } else if (!strcmp(name, "pinned_pool_mb")) {
-        FGPU_REQUIRE(value >= 0 && value <= (1 << 20), FGPU_INVALID, "pinned_pool_mb out of range");
-        ctx->opt.pinned_pool_mb = (int)value;
-    } else if (!strcmp(name, "dist_test_delay_us")) {
-        FGPU_REQUIRE(value >= 0 && value <= 100000, FGPU_INVALID, "dist_test_delay_us out of range");
-        ctx->opt.dist_test_delay_us = (int)value;
-    } else if (!strcmp(name, "dist_force_self")) {
-        ctx->opt.dist_force_self = value != 0;
-    } else if (!strcmp(name, "dist_collective")) {
-        FGPU_REQUIRE(value == 0 || value == 1, FGPU_INVALID, "dist_collective must be 0 (send/recv) or 1 (broadcasts)");
-        ctx->opt.dist_collective = (int)value;
-    } else if (!strcmp(name, "transpose_mode")) {
-        FGPU_REQUIRE(value >= 0 && value <= 3, FGPU_INVALID,
-                     "transpose_mode must be 0 (counting sort, form picked), 1 (COO rebuild), 2 (LDS-staged levels) or 3 (two levels)");
-        ctx->opt.transpose_mode = (int)value;
-    } else if (!strcmp(name, "merge_items")) {
-        ctx->opt.merge_items = value != 0;
-    } else if (!strcmp(name, "merge_mode")) {
-        FGPU_REQUIRE(value >= 0 && value <= 2, FGPU_INVALID,
-                     "merge_mode must be 0 (entry-parallel), 1 (row-wave) or 2 (entry-parallel, base layer marked entry by entry)");
-        ctx->opt.merge_mode = (int)value;
-    } else if (!strcmp(name, "tiled_nt")) {
-        ctx->opt.tiled_nt = value != 0;
-    } else if (!strcmp(name, "tiled_threads")) {
-        FGPU_REQUIRE(value == 256 || value == 512 || value == 1024, FGPU_INVALID,
-                     "tiled_threads must be 256, 512 or 1024");
-        ctx->opt.tiled_threads = (int)value;
-    } else if (!strcmp(name, "tiled_wgs")) {
-        FGPU_REQUIRE(value >= 0 && value <= 65536, FGPU_INVALID, "tiled_wgs out of range");
-        ctx->opt.tiled_wgs = (int)value;
-    } else {
-        set_error("fgpu_set_option: unknown option '%s'", name);
-        return FGPU_INVALID;
+        return FGPU_OK;
     }
+    const OptRow* r = opt_find(name);
+    FGPU_REQUIRE(r, FGPU_INVALID, "fgpu_set_option: unknown option '%s'", name);
+    FGPU_REQUIRE(opt_accepts(*r, value), FGPU_INVALID, "fgpu_set_option: %s must be %s%lld .. %lld, not %lld", name,
+                 r->kind == OPT_POW2 ? "a power of two in " : "", (long long)r->lo, (long long)r->hi, (long long)value);
+    opt_store(ctx->opt, *r, value);
     return FGPU_OK;
 }
 

@@ -26,20 +26,37 @@ def _p(a, t=u64p):
     return a.ctypes.data_as(t) if a is not None else None
 
 
+def _env_options():
+    """A/B plumbing for the tools and the test-suite: FGPU_OPTS="name=value,name=value" sets library options on every context this
+    process opens (e.g. the whole parity suite under an experiment switch) — the library itself reads no environment for them."""
+    opts = []
+    for kv in filter(None, os.environ.get("FGPU_OPTS", "").split(",")):
+        name, eq, value = kv.partition("=")
+        try:
+            if not eq or not name.strip():
+                raise ValueError
+            opts.append((name.strip(), int(value)))
+        except ValueError:
+            raise ValueError(f"FGPU_OPTS: malformed entry {kv!r}, expected name=integer") from None
+    return opts
+
+
 class Context:
     """fgpu_ctx: one per process+device (matrix::init analogue, matrix.rs:116-185)."""
 
     def __init__(self, device: int = 0):
+        opts = _env_options()         # parsed before anything is opened: a malformed entry leaves no context behind
         self.lib = _ffi.load()
         self._h = C.c_void_p()
         self._live_views = 0          # result arrays handed out as views of library memory (_take) and not yet dropped
         self._close_pending = False
         check(self.lib.fgpu_init(C.byref(self._h), device, None, None))
-        # A/B plumbing for the tools and the test-suite: FGPU_OPTS="name=value,name=value" sets library options on every context this
-        # process opens (e.g. the whole parity suite under an experiment switch) — the library itself reads no environment for them
-        for kv in filter(None, os.environ.get("FGPU_OPTS", "").split(",")):
-            k, v = kv.split("=")
-            self.set_option(k.strip(), int(v))
+        try:
+            for k, v in opts:
+                self.set_option(k, v)
+        except Exception:
+            self.close()
+            raise
 
     @property
     def handle(self):

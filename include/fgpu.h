@@ -89,55 +89,81 @@ fgpu_info fgpu_host_alloc(fgpu_ctx* ctx, uint64_t bytes, void** out);
 fgpu_info fgpu_set_stream(fgpu_ctx* ctx, void* hip_stream);
 /* Wait for the work the calling thread has queued on its lane. */
 fgpu_info fgpu_sync(fgpu_ctx* ctx);
-/* Engine tunables (the analogue of GrB_Global_set_INT32, matrix.rs:151-159): "tiled_u" (items in
- * flight per wavefront of the LDS-tiled vxm: 1/2/4/8), "tiled_threads" (256/512/1024),
- * "tiled_wgs" (grid of that kernel, 0 = fill the CUs), "tiled_nt" (nontemporal entry loads),
- * "transpose_mode" (pattern transpose: 0 = counting transpose, 1 = COO rebuild through the sorter), "transpose_wb"
- * (low-digit bits of the counting transpose, 0 = pick; a process-wide experiment knob),
- * "expand_mode" (fgpu_expand: 0 = pick per hop, 1 = sorted-CSR products only, 2 = bit-parallel from the
- * first hop), "expand_fuse_count" (fgpu_expand_count: 1 = the last bit-parallel hop counts its rows where it produces
- * them, 0 = it writes them and a separate pass counts), "expand_row_groups" (sparse mid-chain pull of the bit-parallel
- * form: 1 = a wavefront per 32-row group, 0 = a wavefront per row item), "bfs_wgs_per_cu" (grid of the fused BFS level kernel), "merge_mode" (fgpu_mat_merge:
- * 0 = entry-parallel with the base layer's keep bits cleared from the delta side, 1 = one wavefront per row, pattern
- * layers only, 2 = entry-parallel with every base entry of a touched row searching the deltas), "bfs_tiny" (consecutive tiny BFS levels in one single-workgroup launch: 0 off, 1 on,
- * 2 = when the plan's previous search took more than 12 levels), "dist_collective" (frontier exchange of
- * fgpu_bfs_dist_run: 0 = grouped ncclSend / ncclRecv, 1 = one ncclBroadcast per rank), "dist_timing" (1 = fgpu_bfs_dist_run
- * records HIP events around every level kernel and exchange for fgpu_bfs_dist_times; off by default, the events cost
- * ~20 us of stream idle time per level), "bfs_prof_split" (1 = a profiled plan launches
- * the push / pull twins of the level kernel so rocprofv3 can tell them apart by name), "bfs_hub_first" (1 = BFS plans
- * read the pull direction from a copy of At whose rows are reordered by descending out-degree class), "bfs_pb" (heavy push
- * levels of a BFS by propagation blocking — the frontier's edges binned by destination window, a workgroup per window marking
- * its discoveries in LDS: 0 off, 1 = plans of at least 2^24 vertices, 2 = every single-rank plan) with "bfs_pb_min_edges" (a
- * push level with at least this many edges goes that way; default 2 Mi), "bfs_alive_rule" (1 = the push <-> pull rule takes
- * the unvisited share over the vertices that have an in-edge; 0 = over all vertices), "expand_emit_sort" (bit state -> rows of
- * fgpu_expand*: 2 = (row, vertex) pairs + a stable sort by row, 0 = ballot transpose, 1 = pairs + sort unless the result
- * holds more than 8 entries per vertex; the default), "pinned_results" / "pinned_pool_mb" (result arrays from 256 KiB up to
- * the pool's size come from the context's pinned pool and are filled by DMA; blocks kept for reuse up to that many MiB),
- * "wcc_mode" (fgpu_wcc: 0 = auto, 1 = Afforest with sampling and skip, 2 = one full link pass over every entry of A),
- * "bc_batch" (fgpu_betweenness: sources per batch; 0 = auto, the smallest of 16 / 32 / 64 that covers nsrc, halved until the
- * workspace fits 3/4 of the free device memory; 1-64 force a width), "bc_direction" (fgpu_betweenness forward levels: 0 = auto,
- * push or pull by the entries each would read, 1 = push over A only, 2 = pull over At only). */
+/* Engine options (the analogue of GrB_Global_set_INT32, matrix.rs:151-159).  One name per line: accepted values, meaning;
+ * "A/B" marks a switch kept for measurements, whose two sides give identical results.  A value outside what a line accepts,
+ * and an unknown name, return FGPU_INVALID and leave the stored value as it was.  The defaults, and the measurements behind
+ * them, are on the fields of fgpu_options (falkordb_amd/csrc/options.hpp).  Every option below except "transpose_wb" can be
+ * read back with fgpu_get_option.
+ *   LDS-tiled / blocked vxm
+ *   "tiled_u"                   1, 2, 4, 8          items in flight per wavefront of the tiled kernel
+ *   "tiled_nt"                  0 / not 0           nontemporal entry loads
+ *   "tiled_threads"             256, 512, 1024      its workgroup size
+ *   "tiled_wgs"                 0 .. 65536          its grid, 0 = one workgroup per CU
+ *   "tiled_layout"              0 .. 2              full-pass pull layout: 0 = by size, 1 = tiled (x tile in LDS), 2 = blocked (output window in LDS too)
+ *   "blocked_variant"           0 .. 3              kernel variant of the blocked layout (trips in flight / workgroups per CU)
+ *   fgpu_expand* (k-hop chains)
+ *   "expand_mode"               0 .. 2              0 = pick per hop, 1 = sorted-CSR products only, 2 = bit-parallel from the first hop
+ *   "expand_bits_ratio"         1 .. 1024           expand_mode 0: a hop goes to bit form when its traversed edges exceed nnz / ratio
+ *   "expand_row_groups"         0 / not 0           sparse mid-chain pull: 1 = a wavefront per 32-row group, 0 = a wavefront per row item
+ *   "expand_records"            0 / not 0           sparse mid-chain pull: rows of at most 4 bits are read as records of source indices (A/B)
+ *   "expand_fuse_count"         0 / not 0           fgpu_expand_count: 1 = the last bit-parallel hop counts its rows where it produces them, 0 = a separate pass counts
+ *   "expand_compact"            0 / not 0           empty source rows are dropped before the chain goes to bits when that halves the row width (A/B)
+ *   "expand_first_hop"          0 / not 0           a clean first hop from one-entry rows copies the source rows (A/B)
+ *   "expand_emit_sort"          0 .. 2              bit state -> rows: 0 = ballot transpose, 2 = (row, vertex) pairs + stable sort by row, 1 = pairs + sort unless the result holds more than 8 entries per vertex
+ *   "expand_xcd"                0 / not 0           dense count hop: 1 = rows of X gathered by the XCD that owns their partition, partial rows folded per vertex (A/B)
+ *   "expand_xcd_relabel"        0 / not 0           ... the state it reads is laid out hot-first per partition (A/B)
+ *   "expand_xcd_min_mb"         0 .. 1048576        ... taken when the bit state holds at least this many MiB
+ *   "expand_nt"                 0 .. 7              ... streaming hints, a mask: 1 = partial rows stored non-temporal, 2 = column ids read non-temporal, 4 = the fold reads non-temporal
+ *   "expand_xp_direct"          0, 1                ... 1 = a single-entry run is read from X by the fold, 0 = every run is streamed (A/B)
+ *   "expand_xp_fold"            0, 1                ... the fold: 1 = index work once per row, one load per piece that exists, 0 = a slot per row and step loads all 8 partitions' rows (A/B)
+ *   "expand_xp_fold_min_words"  2, 4, 8, 16, 32     ... the piece fold runs on bit rows of at least this many 64-bit words (32: none), narrower rows keep the slot fold
+ *   "expand_xp_dense"           0, 1                ... the fold's groups: 1 = 64 consecutive ranks among the rows that have an in-edge, 0 = 64 consecutive vertex ids (A/B)
+ *   "expand_scan_min"           0 .. 2^31 - 1       fgpu_expand_count: a call with more source rows than this is a whole-frontier call, cut into passes (0 = never)
+ *   "expand_scan_rows"          64 .. 4096, 2^k     ... live rows per pass
+ *   "expand_scan_lanes"         1 .. 16             ... lanes the passes are dealt to
+ *   fgpu_bfs
+ *   "bfs_wgs_per_cu"            1 .. 64             grid of the fused BFS level kernel, workgroups per CU
+ *   "bfs_tiny"                  0 .. 2              consecutive tiny levels in one single-workgroup launch: 0 off, 1 on, 2 = when the plan's previous search took more than 12 levels
+ *   "bfs_hub_first"             0 / not 0           pull levels read a copy of At whose rows are reordered by descending out-degree class
+ *   "bfs_alive_rule"            0 / not 0           push <-> pull rule: 1 = the unvisited share over the vertices that have an in-edge, 0 = over all vertices
+ *   "bfs_pb"                    0 .. 2              heavy push levels by propagation blocking: 0 off, 1 = plans of at least 2^24 vertices, 2 = every single-rank plan
+ *   "bfs_pb_min_edges"          1 .. 2^63 - 1       ... a push level with at least this many edges goes that way
+ *   "bfs_prof_split"            0 / not 0           a profiled plan launches the push / pull twins of the level kernel, told apart by name
+ *   merges, transposes, results
+ *   "merge_mode"                0 .. 2              fgpu_mat_merge: 0 = entry-parallel, 1 = a wavefront per row (pattern layers only), 2 = entry-parallel, every base entry of a touched row searching the deltas
+ *   "merge_items"               0 / not 0           merge scatter: 1 = shifted copy by 2048-entry items, 0 = per word / per entry (A/B)
+ *   "transpose_mode"            0 .. 3              pattern transpose / COO build: 0 = counting sort, 1 = COO rebuild through the sorter, 2 = LDS-staged levels, 3 = two levels
+ *   "transpose_wb"              any                 low-digit bits of the counting transpose, 0 = pick; PROCESS-wide experiment knob, unchecked, not readable
+ *   "pinned_results"            0 / not 0           result arrays from 256 KiB up come from the context's pinned pool and are filled by DMA
+ *   "pinned_pool_mb"            0 .. 1048576        pinned blocks kept for reuse after fgpu_free, MiB
+ *   algorithms
+ *   "pagerank_parts"            0 .. 2              PageRank SpMV over 8 column ranges, one per XCD: 0 off, 1 = when the score vector exceeds one L2, 2 = always
+ *   "wcc_mode"                  0 .. 2              fgpu_wcc: 0 = auto, 1 = Afforest with sampling and skip, 2 = one full link pass over every entry of A
+ *   "bc_batch"                  0 .. 64             fgpu_betweenness: sources per batch, 0 = auto (16 / 32 / 64 by nsrc, halved to fit 3/4 of the free device memory)
+ *   "bc_direction"              0 .. 2              fgpu_betweenness forward levels: 0 = auto by the entries each would read, 1 = push over A, 2 = pull over At
+ *   "maxflow_global_every"      0 .. 1048576        fgpu_maxflow: pulses between two global relabels, 0 = the built-in period
+ *   multi-GPU BFS (fgpu_bfs_dist_run)
+ *   "dist_collective"           0, 1                frontier exchange: 0 = grouped ncclSend / ncclRecv, 1 = one ncclBroadcast per rank
+ *   "dist_timing"               0 / not 0           HIP events around every level kernel and exchange for fgpu_bfs_dist_times (~20 us of stream idle time per level)
+ *   "dist_force_self"           0 / not 0           TEST ONLY: a communicator of ONE rank still issues the self send / recv, broadcast and all-reduce of a multi-rank exchange
+ *   "dist_test_delay_us"        0 .. 100000         TEST ONLY: a kernel spinning this many microseconds behind every level kernel of this context's rank */
 fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
-/* Read-back of measurement / test counters kept by the context (a subset of the option names plus counters that
- * have no setter): "dist_force_self" (test-only, set through fgpu_set_option: a communicator of ONE rank still issues the
- * grouped self ncclSend / ncclRecv, ncclBroadcast and ncclAllReduce of a multi-rank exchange — tests/test_gpu_dist.py),
- * "dist_self_calls" (how many such calls ran), "expand_kernel_launches" (kernels launched by fgpu_expand* on this context so
- * far: the launch count of a batch is a difference of two reads), "bfs_pb_last_levels" (levels the search fgpu_bfs_stats last
- * read ran by propagation blocking), "bfs_cp_last_mask" (bit k: fused launch k of that search ran behind the list kernel — a
- * sparse frontier listed into the queue, or a pull of listed candidates), "expand_scan_last_live" / "expand_scan_last_passes" (live source rows and passes of the
- * last whole-frontier fgpu_expand_count), "expand_xp_fold" (set through fgpu_set_option; the fold of the XCD-partitioned
- * count hop: 1 = a lane per row does the index work and a slot loads each partial row / direct entry that exists, 0 = a slot
- * per row and step loads all 8 partitions' rows; results are identical), "expand_xp_fold_min_words" (set through fgpu_set_option:
- * the piece fold runs on bit rows of at least this many 64-bit words — 2, 4, 8, 16, or 32 for none — and narrower rows keep the
- * slot fold), "expand_xp_piece_folds" / "expand_xp_slot_folds" (launches of either fold on this context so far: which fold a
- * call ran, and that the partitioned hop ran at all, is a difference of two reads), "expand_xp_direct" and "expand_xp_last_direct" (entries of A' the last XCD-partitioned count hop
- * read straight from X as single-entry runs, 0 when its plan streams every run), "expand_xp_dense" (set through fgpu_set_option:
- * 1 = the fold's groups are 64 consecutive ranks among the destination rows that have an in-edge, 0 = 64 consecutive vertex
- * ids; results are identical) and "expand_xp_last_groups" (groups the fold of the last partitioned count hop looped over:
- * ceil(rows with an in-edge / 64) or ceil(rows / 64)), "expand_xcd", "expand_xcd_relabel" and
- * "expand_xcd_min_mb" (the settings of the partitioned count hop, so that a caller can put back what it found), "expand_mode",
- * "expand_nt", "wcc_mode", "bc_batch", "bc_direction".  Unknown
- * names return FGPU_INVALID. */
+/* Reads the current value of any option fgpu_set_option stores (all of the list above but "transpose_wb"; 0 / not 0 options
+ * read as 0 or 1), so a caller can put back what it found, or one of the measurement counters the context keeps.  The
+ * counters have no setter; unknown names return FGPU_INVALID.
+ *   "expand_kernel_launches"    kernels launched by fgpu_expand* on this context so far (the count of a batch is a difference of two reads)
+ *   "expand_scan_last_live"     live source rows of the last whole-frontier fgpu_expand_count
+ *   "expand_scan_last_passes"   ... and its passes
+ *   "expand_xp_piece_folds"     launches of the piece fold of the XCD-partitioned count hop so far (which fold a call ran, and that the hop ran at all, is a difference of two reads)
+ *   "expand_xp_slot_folds"      ... and of the slot fold
+ *   "expand_xp_last_direct"     entries of A' the last partitioned count hop read straight from X as single-entry runs, 0 when its plan streams every run
+ *   "expand_xp_last_groups"     groups its fold looped over: ceil(rows with an in-edge / 64), or ceil(rows / 64)
+ *   "bfs_pb_last_levels"        levels the search fgpu_bfs_stats last read ran by propagation blocking
+ *   "bfs_cp_last_mask"          bit k: fused launch k of that search ran behind the list kernel (a sparse frontier listed into the queue, or a pull of listed candidates)
+ *   "dist_self_calls"           forced self collectives issued so far (dist_force_self; tests/test_gpu_dist.py)
+ *   "harmonic_last_entries"     the last fgpu_harmonic call: entries of the recomputed rows
+ *   "harmonic_last_gathered"    ... and sketches gathered
+ *   "msf_last_entries_round<k>" the last fgpu_msf call: entries read in round k = 0 .. 31, the rounds past 31 in 31 */
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value);
 /* name[256]; returns CU count, wave size, LDS bytes per block, total HBM bytes. */
 fgpu_info fgpu_device_info(fgpu_ctx* ctx, char* name, int32_t* cus, int32_t* wave,
