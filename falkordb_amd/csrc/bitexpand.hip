@@ -303,29 +303,46 @@ __global__ __launch_bounds__(256) void bp_flag_bits_kernel(const uint8_t* __rest
     }
 }
 
-// coarse filter over the flag bits for the sparse pull: bit j <=> any flag among the 64 << g vertices of block j.  It is
-// small enough for LDS (<= 16 KiB), and after a hop from ~10^4 frontier vertices it is ~90 % zeros: most of the 263 M
+// coarse filter over the flags for the sparse pull: bit j <=> any flag among the 1 << cshift vertices of block j.  It is
+// staged in LDS (<= BP_COARSE_LDS), and after a hop from ~10^4 frontier vertices it is mostly zeros: most of the 263 M
 // probes of an RMAT-24 pull are answered from LDS instead of from L2 (where random 4-byte loads run at ~110 G/s: the
-// probes, not bytes, were what the sparse hop cost — 2.4 ms for 3 GB of traffic)
-__global__ __launch_bounds__(256) void bp_coarse_bits_kernel(const u64* __restrict__ bits, u32 nwords, u32 g,
+// probes, not bytes, were what the sparse hop cost — 2.4 ms for 3 GB of traffic).  A block may be smaller than a word of
+// the flag bitmap (16 vertices at RMAT-22): with 2 * 10^4 flagged vertices over 65 536 blocks of 64, every fourth probe of
+// an UNflagged neighbour passed the map and paid a round trip to L2 to learn so (profiles/NOTES_r15.md).  The map is
+// built from the flag BYTES, a lane per block and a ballot per 64 blocks, so it needs no bitmap before it.
+constexpr size_t BP_COARSE_LDS = 32 * 1024;
+static u32 bp_coarse_shift(u32 n) {   // the smallest block of >= 8 vertices whose map fits BP_COARSE_LDS
+    u32 cshift = 3;
+    while (((((u64)n + (1ull << cshift) - 1) >> cshift) + 63) / 64 * sizeof(u64) > BP_COARSE_LDS) ++cshift;
+    return cshift;
+}
+__global__ __launch_bounds__(256) void bp_coarse_flags_kernel(const uint8_t* __restrict__ flag, u32 n, u32 cshift,
                                                              u64* __restrict__ coarse, u32 ncoarse_words) {
     const u32 lane = lane_id();
     const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const u32 nwaves = (gridDim.x * 256) >> 6;
+    const u64 per = 1ull << (cshift - 3);               // 8-byte words of flags per block
     for (u32 cw = wave; cw < ncoarse_words; cw += nwaves) {
-        const u64 first = ((u64)cw * 64 + lane) << g;   // first fine word of this lane's block
+        const u64 first = (((u64)cw * 64 + lane) << cshift);   // first vertex of this lane's block
         u64 any = 0ull;
-        for (u32 k = 0; k < (1u << g); ++k)
-            if (first + k < nwords) any |= bits[first + k];
+        for (u64 k = 0; k < per; ++k) {
+            const u64 v = first + 8 * k;
+            if (v + 8 <= (u64)n) {
+                any |= *reinterpret_cast<const u64*>(flag + v);
+            } else {
+                for (u32 j = 0; j < 8u; ++j)
+                    if (v + j < (u64)n) any |= flag[v + j];
+            }
+        }
         const u64 m = __ballot(any != 0ull);
         if (lane == 0) coarse[cw] = m;
     }
 }
 
 struct BpProbe {
-    const u64* bits;    // flag bit per vertex
-    const u64* coarse;  // flag bit per block of 64 << g vertices (staged in LDS)
-    u32 cshift;         // vertex >> cshift = coarse bit (6 + g)
+    const u64* bits;    // flag bit per vertex (null where the records answer the fine probe)
+    const u64* coarse;  // flag bit per block of 1 << cshift vertices (staged in LDS)
+    u32 cshift;         // vertex >> cshift = coarse bit
     u32 cwords;         // 64-bit words of the coarse map
 };
 
@@ -334,13 +351,13 @@ struct BpProbe {
 // summed through the LDS nibble tables) and never written, except for "touched" rows — rows cut into several items or
 // named by a delta layer — which go to their slot of the side buffer `y` (BpFinal, bitexpand.hpp).
 template <int LN, bool SPARSE, int MODE>
-__global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void bp_pull_kernel(CsrView at, const u32* __restrict__ items, u32 nitems, u32 ws,
+__global__ __launch_bounds__(MODE == 2 || SPARSE ? 1024 : 256) void bp_pull_kernel(CsrView at, const u32* __restrict__ items, u32 nitems, u32 ws,
                                                      const u64* __restrict__ x, BpProbe pr,
                                                      u64* __restrict__ y, uint8_t* __restrict__ yflag, BpFinal fin,
                                                      const u32* __restrict__ yperm /* MODE 0, nullable: row v of Y is stored at slot yperm[v] */) {
     // MODE 2 runs 1024-thread workgroups: the 2 KiB-per-word tables are shared by 16 wavefronts, so the LDS they take
     // does not cost resident wavefronts (the gathers are latency-bound: 20 instead of 32 waves per CU made the dense
-    // hop 1.6 x slower when every 256-thread workgroup carried its own copy)
+    // hop 1.6 x slower when every 256-thread workgroup carried its own copy); SPARSE does the same for its coarse flag map
     extern __shared__ u64 s_tab[];
     const u64* __restrict__ xbits = pr.bits;
     const u32* s_co = reinterpret_cast<const u32*>(s_tab + (MODE == 2 ? fin.w * 256 : 0));   // coarse flag map (SPARSE)
@@ -488,6 +505,9 @@ __global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void bp_pull_kernel(CsrView
 // 635 us at RMAT-22 against 354 us for the same hop at half the row width).  rec[u] = the bits of X[u] as up to four 16-bit
 // source indices (0xFFFF = none), or BP_REC_ESC when the row holds more: a lane per live entry then loads 8 bytes and sets
 // the bits in the group's LDS accumulator itself; only the entries that meet an ESC row go through the row gathers.
+// rec[] is defined for EVERY vertex: an unflagged one holds ~0ull, the "no source" pattern a flagged but all-zero row gets
+// from the loop below (flags are "maybe non-zero").  So a record answers "has u bits?" as well as "which", and the pulls
+// that read records need no probe of the flag bitmap before them — one dependent round trip less per entry.
 constexpr u64 BP_REC_ESC = 0xFFFFFFFFFFFFFFFEull;
 __global__ __launch_bounds__(256) void bp_records_kernel(const uint8_t* __restrict__ flag, u32 n, u32 ws, const u64* __restrict__ x,
                                                         u64* __restrict__ rec) {
@@ -497,6 +517,9 @@ __global__ __launch_bounds__(256) void bp_records_kernel(const uint8_t* __restri
     const u32 tiles = (n + 2047u) >> 11;
     for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         if (tid == 0) s_cnt = 0;
+        // (coalesced; the records of the tile's flagged vertices overwrite theirs behind the barrier below)
+        for (u32 i = tid; i < 2048u; i += 256u)
+            if ((tile << 11) + i < n) rec[(tile << 11) + i] = ~0ull;
         __syncthreads();
         const u32 base = (tile << 11) + tid * 8u;
         u64 f = 0;
@@ -543,8 +566,12 @@ __global__ __launch_bounds__(256) void bp_records_kernel(const uint8_t* __restri
 // LDS (ds_or_b64), and the non-zero rows are written to Y once, coalesced.  Rows of more than BP_ITEM entries are left
 // to the item kernel (bp_sitems): they OR into Y with atomics and would stall a group.
 constexpr u32 BP_GROUP = 32;
-constexpr u32 BP_GROUP_WAVES = 8;   // wavefronts per workgroup
-template <int LN>
+constexpr u32 BP_GROUP_WAVES = 16;  // wavefronts per workgroup at most: they share one copy of the coarse map (32 KiB + 16 x 6.4 KiB
+                                    // with 128-byte rows: 16 wavefronts per CU, what two workgroups of 8 gave under an 8 KiB map)
+// REC: `rec` holds a record for every vertex (bp_records_kernel) and answers the fine probe itself — an entry that passes
+// the LDS map loads rec[u]: ~0ull = not live, source indices = OR-ed into the row's accumulator by the lane that loaded
+// them, BP_REC_ESC = compacted into the list for the row gathers.  pr.bits is not read.
+template <int LN, bool REC>
 __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(CsrView at, u32 nrows, const u64* __restrict__ x,
                                                                              BpProbe pr, u64* __restrict__ y,
                                                                              uint8_t* __restrict__ yflag,
@@ -552,7 +579,7 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
                                                                              unsigned long long* __restrict__ stats,
                                                                              const u64* __restrict__ later_bits,
                                                                              const u32* __restrict__ yperm /* nullable: row v of Y at slot yperm[v] */,
-                                                                             const u64* __restrict__ rec /* nullable: bp_records_kernel's form of X */) {
+                                                                             const u64* __restrict__ rec /* REC: bp_records_kernel's form of X */) {
     // stats (nullable, with next_rowptr): [0] += popcount(Y[v]) * out-degree of v in the next hop's matrix, [1] += rows
     // written — what bp_flops / bp_count_flags would find in a pass of their own.  Rows flagged in `later_bits`
     // (nullable: destinations of a delta layer, whose rows change after this kernel) are left to bp_split_stats_kernel.
@@ -619,51 +646,30 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
                 const u32 c = at.colidx[tc + base[t < total ? lo : R - 1u]];
                 un[k] = (t < total) ? c : 0xFFFFFFFFu;
             }
-            u64 live[4];
-            u64 fw[4];
             bool sv[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const u32 cb = (un[k] != 0xFFFFFFFFu ? un[k] : 0u) >> pr.cshift;
-                sv[k] = un[k] != 0xFFFFFFFFu && ((s_co[cb >> 5] >> (cb & 31)) & 1u);
-                fw[k] = pr.bits[sv[k] ? (un[k] >> 6) : 0u];
+                sv[k] = (un[k] != 0xFFFFFFFFu) & (((s_co[cb >> 5] >> (cb & 31)) & 1u) != 0u);   // (no `&&`: it is a branch per trip)
             }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) live[k] = __ballot(sv[k] && ((fw[k] >> (un[k] & 63)) & 1ull));
             u32 n_live = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if ((live[k] >> lane) & 1ull) list[n_live + (u32)__popcll(live[k] & below)] = ((u64)rw[k] << 32) | un[k];
-                n_live += (u32)__popcll(live[k]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (rec) {
-                // a lane per live entry (<= 256 of them: four per lane, their records in flight together): the record's source
-                // indices are set in the row's accumulator; entries whose neighbour holds more than four bits are compacted to
-                // the front of the list and take the row gathers below
-                u64 pe[4], rc[4];
+            if (REC) {
+                // a lane per entry, the four records in flight together; only the entries whose neighbour holds more than
+                // four bits are listed, and take the row gathers below
+                u64 rc[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const u32 i = 64u * k + lane;
-                    pe[k] = (i < n_live) ? list[i] : ~0ull;
+                    const u64 r = rec[sv[k] ? un[k] : 0u];
+                    rc[k] = sv[k] ? r : ~0ull;
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const u64 r = rec[pe[k] != ~0ull ? (u32)pe[k] : 0u];
-                    rc[k] = (pe[k] != ~0ull) ? r : ~0ull;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (every lane has read its list entries before any is rewritten)
-                __builtin_amdgcn_wave_barrier();
-                u32 n_esc = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const bool esc = pe[k] != ~0ull && rc[k] == BP_REC_ESC;
+                    const bool esc = rc[k] == BP_REC_ESC;
                     const u64 em = __ballot(esc);
-                    if (esc) list[n_esc + (u32)__popcll(em & below)] = pe[k];
-                    n_esc += (u32)__popcll(em);
+                    if (esc) list[n_live + (u32)__popcll(em & below)] = ((u64)rw[k] << 32) | un[k];
+                    n_live += (u32)__popcll(em);
                     if (!esc) {
-                        u64* arow = acc + (size_t)(u32)(pe[k] >> 32) * LN;
+                        u64* arow = acc + (size_t)rw[k] * LN;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const u32 sid = (u32)(rc[k] >> (16 * j)) & 0xFFFFu;
@@ -671,10 +677,21 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
                         }
                     }
                 }
-                n_live = n_esc;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+            } else {
+                u64 live[4];
+                u64 fw[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) fw[k] = pr.bits[sv[k] ? (un[k] >> 6) : 0u];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) live[k] = __ballot(sv[k] && ((fw[k] >> (un[k] & 63)) & 1ull));
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if ((live[k] >> lane) & 1ull) list[n_live + (u32)__popcll(live[k] & below)] = ((u64)rw[k] << 32) | un[k];
+                    n_live += (u32)__popcll(live[k]);
+                }
             }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
             for (u32 i0 = 0; i0 < n_live; i0 += 4 * SLOTS) {
                 u64 pu[4];
 #pragma unroll
@@ -718,6 +735,117 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
         __builtin_amdgcn_wave_barrier();
     }
     if (stats) bp_block_add2(st_flops, (u64)st_rows, stats);   // (wave-uniform condition: every wavefront of the workgroup arrives)
+}
+
+// ---------------------------------------------------------------------------------
+// sparse pull, the items of split rows through records (the row-group form's other half)
+// ---------------------------------------------------------------------------------
+// Rows of more than BP_ITEM entries are the hubs: 55 % of the entries of A' at RMAT-22, ~68 live ones in an item of 256.
+// bp_pull_kernel<.., SPARSE> gathers a whole row of X per live entry — 16 rows a round, 4 rounds in flight, 4 to 5 dependent
+// rounds an item — to convey the one or two bits a record holds in 8 bytes.  Here a wavefront takes an item a lane per
+// entry: the four 64-entry column loads issue together, then (behind the LDS map) the four record loads; a record's source
+// indices are set in the wavefront's accumulator in LDS by the lane that loaded it, and only the entries that meet a
+// BP_REC_ESC row are compacted and take the row gathers.  The accumulator's non-zero words leave by atomicOr, as every
+// item of a split row does.  The accumulator is kept in BP_IREC_COPIES copies, chosen by lane: 64 lanes setting bits in
+// 16 words would serialise on the same LDS words.
+constexpr u32 BP_IREC_COPIES = 4;
+static_assert(64 % BP_IREC_COPIES == 0 && BP_IREC_COPIES * 16 <= 64, "bp_pull_items_rec_kernel: a lane per accumulator word clears the copies");
+template <int LN>
+__global__ __launch_bounds__(1024) void bp_pull_items_rec_kernel(CsrView at, const u32* __restrict__ items, u32 nitems,
+                                                                 const u64* __restrict__ x, const u64* __restrict__ rec, BpProbe pr,
+                                                                 u64* __restrict__ y, uint8_t* __restrict__ yflag,
+                                                                 const u32* __restrict__ yperm /* nullable: row v of Y at slot yperm[v] */) {
+    constexpr int SLOTS = 64 / LN;
+    constexpr u32 C = BP_IREC_COPIES;
+    extern __shared__ u64 s_mem[];
+    const u32* s_co = reinterpret_cast<const u32*>(s_mem);
+    for (u32 i = threadIdx.x; i < pr.cwords; i += blockDim.x) s_mem[i] = pr.coarse[i];
+    const u32 lane = lane_id();
+    u64* acc = s_mem + pr.cwords + (size_t)(threadIdx.x >> 6) * (C * LN + BP_ITEM / 2);   // C copies of LN words
+    u32* list = reinterpret_cast<u32*>(acc + C * LN);                                      // ids of up to BP_ITEM ESC neighbours
+    if (lane < C * LN) acc[lane] = 0ull;
+    __syncthreads();
+    const u32 wl = lane % LN, slot = lane / LN;
+    u64* mine = acc + (lane % C) * LN;
+    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+    const u64 below = (1ull << lane) - 1ull;
+    for (u32 it = wave; it < nitems; it += nwaves) {
+        const u32 v = (u32)__builtin_amdgcn_readfirstlane((int)items[3 * it]);
+        const u32 b = (u32)__builtin_amdgcn_readfirstlane((int)items[3 * it + 1]);
+        const u32 e = (u32)__builtin_amdgcn_readfirstlane((int)items[3 * it + 2]) & 0x7FFFFFFFu;
+        const u32 yv = yperm ? yperm[v] : v;   // (requested here, with the column ids)
+        u32 un[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u32 q = b + 64 * k + lane;
+            un[k] = at.colidx[q < e ? q : e - 1u];           // (clamped, not conditional: see bp_pull_groups_kernel)
+        }
+        // (all four loads are issued before the first is looked at: left to itself hipcc puts the first trip's select, and the
+        // wait it needs, in front of the fourth load)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (b + 64 * k + lane >= e) un[k] = 0xFFFFFFFFu;
+        u64 rc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // (the map word is read for every lane, from a clamped block: a short-circuit `&&` here is a branch per trip, and
+            // hipcc then waits for the first trip's column ids before it issues the loads of the other three)
+            const u32 cb = (un[k] != 0xFFFFFFFFu ? un[k] : 0u) >> pr.cshift;
+            const bool sv = (un[k] != 0xFFFFFFFFu) & (((s_co[cb >> 5] >> (cb & 31)) & 1u) != 0u);
+            const u64 r = rec[sv ? un[k] : 0u];
+            rc[k] = sv ? r : ~0ull;
+        }
+        u32 n_esc = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool esc = rc[k] == BP_REC_ESC;
+            const u64 em = __ballot(esc);
+            if (esc) list[n_esc + (u32)__popcll(em & below)] = un[k];
+            n_esc += (u32)__popcll(em);
+            if (!esc) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32 sid = (u32)(rc[k] >> (16 * j)) & 0xFFFFu;
+                    if (sid < 0xFFFEu) atomicOr((unsigned long long*)&mine[sid >> 6], 1ull << (sid & 63u));
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the list is read by other lanes of this wavefront
+        __builtin_amdgcn_wave_barrier();
+        for (u32 i0 = 0; i0 < n_esc; i0 += 4 * SLOTS) {
+            u32 u[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const u32 i = i0 + k * SLOTS + slot;
+                u[k] = (i < n_esc) ? list[i] : 0xFFFFFFFFu;
+            }
+            u64 xv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const u64 r = x[(size_t)(u[k] != 0xFFFFFFFFu ? u[k] : 0u) * LN + wl];
+                xv[k] = (u[k] != 0xFFFFFFFFu) ? r : 0ull;
+            }
+            const u64 o = (xv[0] | xv[1]) | (xv[2] | xv[3]);
+            if (o) atomicOr((unsigned long long*)&acc[(slot % C) * LN + wl], (unsigned long long)o);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        u64 a = 0ull;
+        if (lane < LN) {
+#pragma unroll
+            for (u32 c = 0; c < C; ++c) a |= acc[c * LN + lane];
+        }
+        if (a) atomicOr((unsigned long long*)&y[(size_t)yv * LN + lane], (unsigned long long)a);
+        const bool any = __ballot(a != 0ull) != 0ull;
+        if (any && lane == 0) yflag[v] = 1;   // "maybe non-zero": benign races, never cleared within a hop
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (every copy is read before it is cleared)
+        __builtin_amdgcn_wave_barrier();
+        if (any && lane < C * LN) acc[lane] = 0ull;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
 }
 
 // the same two sums over the rows the item kernel finished with atomics (rows of more than BP_ITEM entries: `bits`).
@@ -1118,7 +1246,7 @@ static fgpu_info bp_alloc_flags(fgpu_ctx* ctx, BitState& s) {
 }
 
 // LDS the sparse pull needs beside the checksum tables of a counting hop: the coarse flag map and the live lists
-constexpr size_t BP_SPARSE_LDS = 16384 + 16 * BP_ITEM * sizeof(u32);
+constexpr size_t BP_SPARSE_LDS = BP_COARSE_LDS + 16 * BP_ITEM * sizeof(u32);
 static bool bp_sparse_fits(const fgpu_ctx* ctx, size_t table_bytes) { return table_bytes + BP_SPARSE_LDS <= (size_t)ctx->opt.lds_limit; }
 
 static fgpu_info bp_count_flags(fgpu_ctx* ctx, BitState& s) {
@@ -1408,7 +1536,7 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
         const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
         FGPU_TRY(bp_xpull_count(ctx, xp, t, (const u64*)s.x.p, s.ws, mode, fin, side.p, lds, xrows));
     } else if (m->nnz) {
-        // (the sparse form stages a <= 16 KiB coarse flag map in LDS next to the checksum tables of MODE 2)
+        // (the sparse form stages a coarse flag map of <= BP_COARSE_LDS in LDS next to the checksum tables of MODE 2)
         const bool sparse = s.flag.p != nullptr && s.nz_rows * 8 < (u64)s.n && bp_sparse_fits(ctx, lds);
         FGPU_REQUIRE(sparse || !s.lazy, FGPU_INVALID, "bit-parallel hop: a lazily zeroed state needs the sparse pull");
         // row-group form: rows of <= BP_ITEM entries by bp_pull_groups_kernel, the split rows' items by the item kernel
@@ -1421,8 +1549,8 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
         const CsrView tv = view_of(t);
         u32 grid = cdiv(nitems ? nitems : 1, 4);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        const u32 threads = mode == 2 ? 1024 : 256;
-        if (mode == 2) {                              // 16-wavefront workgroups: same wavefront count, a quarter of the grid
+        const u32 threads = (mode == 2 || sparse) ? 1024 : 256;
+        if (threads == 1024) {                        // 16-wavefront workgroups: same wavefront count, a quarter of the grid
             grid = cdiv(nitems ? nitems : 1, 16);
             if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
         }
@@ -1431,21 +1559,25 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
         DevBuf<u64> xbits, xcoarse;
         BpProbe pr = {nullptr, nullptr, 0, 0};
         size_t lds_co = 0;
+        // the state's non-zero rows as records of <= 4 source indices (bp_records_kernel), one for EVERY vertex: what both kernels
+        // of the row-group form read per entry that passes the LDS map, instead of a flag bit and then the whole row
+        const bool use_rec = groups && ctx->opt.expand_records && s.nsrc < 0xFFFEu && s.nz_rows * 8 < (u64)s.n;
         if (sparse) {
-            const u32 nw = (u32)(((size_t)s.n + 63) / 64);
-            FGPU_TRY(xbits.alloc(ctx, (size_t)nw + 1));
-            hipLaunchKernelGGL(bp_flag_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p,
-                               s.n, xbits.p);
-            FGPU_HIP(hipGetLastError());
-            u32 g = 0;                                    // coarse map <= 16 KiB = 2048 words of 64 blocks
-            while ((((u64)nw + (1ull << g) - 1) >> g) > 2048ull * 64ull) ++g;
-            const u32 nblocks = (u32)(((u64)nw + (1ull << g) - 1) >> g);
+            if (!use_rec) {
+                const u32 nw = (u32)(((size_t)s.n + 63) / 64);
+                FGPU_TRY(xbits.alloc(ctx, (size_t)nw + 1));
+                hipLaunchKernelGGL(bp_flag_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p,
+                                   s.n, xbits.p);
+                FGPU_HIP(hipGetLastError());
+            }
+            const u32 cshift = bp_coarse_shift(s.n);
+            const u32 nblocks = (u32)(((u64)s.n + (1ull << cshift) - 1) >> cshift);
             const u32 cwords = (nblocks + 63) / 64;
             FGPU_TRY(xcoarse.alloc(ctx, (size_t)cwords + 1));
-            hipLaunchKernelGGL(bp_coarse_bits_kernel, dim3(cdiv(cwords, 4)), dim3(256), 0, ctx->stream(), (const u64*)xbits.p, nw, g,
-                               xcoarse.p, cwords);
+            hipLaunchKernelGGL(bp_coarse_flags_kernel, dim3(cdiv(cwords, 4)), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n,
+                               cshift, xcoarse.p, cwords);
             FGPU_HIP(hipGetLastError());
-            pr = BpProbe{xbits.p, xcoarse.p, 6 + g, cwords};
+            pr = BpProbe{xbits.p, xcoarse.p, cshift, cwords};
             lds_co = (size_t)cwords * sizeof(u64);
         }
         // algorithmic bytes of the launch: the column ids of A' and the item list once, every non-zero X row once
@@ -1491,9 +1623,7 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
             }
         }
         DevBuf<u64> recs;
-        if (groups && ctx->opt.expand_records && s.nsrc < 0xFFFEu && s.nz_rows * 8 < (u64)s.n) {
-            // the state's non-zero rows as records of <= 4 source indices (bp_records_kernel): what the row-group pull reads per
-            // live entry instead of the whole row
+        if (use_rec) {
             FGPU_TRY(recs.alloc(ctx, (size_t)s.n + 1));
             ProfScope psr(ctx, "bp_records_kernel", (u64)s.n + s.nz_rows * (s.ws * 8 + 8));
             const u32 tiles = (s.n + 2047u) >> 11;
@@ -1505,21 +1635,30 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
         if (groups) {
             ProfScope pg(ctx, "sparse pull: row groups", 0);   // (nested in the hop's record: the split between the two launches)
             const size_t per_wave = ((size_t)BP_GROUP * s.ws + 256 + 32) * sizeof(u64);
-            const size_t lds_g = lds_co + BP_GROUP_WAVES * per_wave;
+            // the map is paid once per workgroup: as many wavefronts share it as the LDS holds beside it, 16 at most, and the
+            // grid keeps 16 wavefronts on a CU where they fit (32 KiB + 16 x 6.4 KiB with 128-byte rows: one workgroup)
+            u32 gwaves = (u32)(((size_t)ctx->opt.lds_limit - lds_co) / per_wave);
+            if (gwaves > BP_GROUP_WAVES) gwaves = BP_GROUP_WAVES;
+            FGPU_REQUIRE(gwaves >= 1, FGPU_INVALID, "sparse pull: a row group needs %zu B of LDS beside the %zu B flag map (limit %d)",
+                         per_wave, lds_co, ctx->opt.lds_limit);
+            const size_t lds_g = lds_co + gwaves * per_wave;
             u32 wgs = (u32)((size_t)ctx->opt.lds_limit / lds_g);
-            if (wgs < 1) wgs = 1;
-            if (wgs > 4) wgs = 4;
+            if (wgs * gwaves > 32) wgs = 32 / gwaves;
             const u32 ggrid = (u32)ctx->cus * wgs;
-#define BP_GROUPS(LN)                                                                                                   \
+#define BP_GROUPS2(LN, RC)                                                                                              \
     do {                                                                                                                \
         if (lds_g > 48 * 1024)                                                                                          \
-            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_groups_kernel<LN>,                                        \
+            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_groups_kernel<LN, RC>,                                    \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));                      \
-        hipLaunchKernelGGL(bp_pull_groups_kernel<LN>, dim3(ggrid), dim3(BP_GROUP_WAVES * 64), lds_g, ctx->stream(),     \
+        hipLaunchKernelGGL((bp_pull_groups_kernel<LN, RC>), dim3(ggrid), dim3(gwaves * 64), lds_g, ctx->stream(),       \
                            view_of(t), (u32)t->nrows, (const u64*)s.x.p, pr, ydst, yflag,                               \
                            fuse_stats ? (const u32*)next_m->rowptr : (const u32*)nullptr,                               \
                            fuse_stats ? (unsigned long long*)gstats.p : (unsigned long long*)nullptr,                   \
                            (const u64*)later.p, operm, (const u64*)recs.p);                                             \
+    } while (0)
+#define BP_GROUPS(LN)                                                                                                   \
+    do {                                                                                                                \
+        if (recs.p) BP_GROUPS2(LN, true); else BP_GROUPS2(LN, false);                                                   \
     } while (0)
             switch (s.ws) {
                 case 1: BP_GROUPS(1); break;
@@ -1529,9 +1668,32 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
                 default: BP_GROUPS(16); break;
             }
 #undef BP_GROUPS
+#undef BP_GROUPS2
             FGPU_HIP(hipGetLastError());
         }
-        if (nitems) switch (ln) {
+        if (nitems && recs.p) {
+            // the items of the split rows, a lane per entry through the records (groups => s.ws <= 16 = the row's lanes)
+            ProfScope pi(ctx, "bp_pull_items_rec_kernel", 0);   // (nested in the hop's record, like the row groups)
+            const size_t lds_i = lds_co + 16 * ((size_t)BP_IREC_COPIES * s.ws + BP_ITEM / 2) * sizeof(u64);
+            u32 igrid = cdiv(nitems, 16);
+            if (igrid > (u32)ctx->cus * 2) igrid = ctx->cus * 2;     // 32 wavefronts on a CU: all it holds
+#define BP_ITEMS_REC(LN)                                                                                                \
+    do {                                                                                                                \
+        if (lds_i > 48 * 1024)                                                                                          \
+            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_items_rec_kernel<LN>,                                     \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_i));                      \
+        hipLaunchKernelGGL(bp_pull_items_rec_kernel<LN>, dim3(igrid), dim3(1024), lds_i, ctx->stream(), tv, item_list,  \
+                           nitems, (const u64*)s.x.p, (const u64*)recs.p, pr, ydst, yflag, operm);                      \
+    } while (0)
+            switch (s.ws) {
+                case 1: BP_ITEMS_REC(1); break;
+                case 2: BP_ITEMS_REC(2); break;
+                case 4: BP_ITEMS_REC(4); break;
+                case 8: BP_ITEMS_REC(8); break;
+                default: BP_ITEMS_REC(16); break;
+            }
+#undef BP_ITEMS_REC
+        } else if (nitems) switch (ln) {
             case 1: BP_LAUNCH(1); break;
             case 2: BP_LAUNCH(2); break;
             case 4: BP_LAUNCH(4); break;
