@@ -1381,32 +1381,42 @@ fgpu_info bp_accumulate(fgpu_ctx* ctx, BitState& u, const BitState& x) {
     return FGPU_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// the steps of a hop: bp_count, bp_hop and bp_hop_count below compose them
+// ---------------------------------------------------------------------------------
+// the checksum look-up tables live in LDS: 2 KiB per word of the row, i.e. batches of up to 4096 source rows per pass
+static size_t bp_table_bytes(const BitState& s) { return (size_t)s.w * 256 * sizeof(u64); }
+
+static fgpu_info bp_cs_tables(fgpu_ctx* ctx, const BitState& s, DevBuf<u64>& tab) {
+    const size_t lds = bp_table_bytes(s);
+    FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID,
+                 "expand checksum: %u source rows need %zu B of LDS tables (limit %d); batch the sources", s.nsrc, lds,
+                 ctx->opt.lds_limit);
+    FGPU_TRY(tab.alloc(ctx, (size_t)s.w * 256));
+    return launch(bp_cs_table_kernel, dim3(s.w), dim3(256), 0, ctx->stream(), s.w, tab.p, s.rowmap.p, s.nsrc);
+}
+
+// count `nrows` rows of y into acc — with `tab` their checksum too; at most `per_cu` workgroups a CU, a quarter of that with the
+// tables (every workgroup copies them once); `rowmap` (nullable) names the vertex of a row
+static fgpu_info bp_count_rows(fgpu_ctx* ctx, const BitState& s, const u64* y, u32 nrows, const u64* label, const u64* tab, u64* acc,
+                               u32 per_cu, const u32* rowmap) {
+    u32 grid = cdiv((u64)nrows * s.w, 256);
+    const u32 cap = (u32)ctx->cus * (tab ? per_cu / 4 : per_cu);
+    if (grid > cap) grid = cap;
+    return pick(tab != nullptr, [&](auto with_sum) {
+        return launch(bp_count_kernel<decltype(with_sum)::value>, dim3(grid), dim3(256), tab ? bp_table_bytes(s) : 0, ctx->stream(), y, nrows,
+                      s.w, s.ws, label, tab, (unsigned long long*)acc, rowmap);
+    });
+}
+
 fgpu_info bp_count(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, u64* nnz, u64* checksum) {
     DevBuf<u64> acc, tab;
     FGPU_TRY(bp_acc_alloc(ctx, acc));
     const u64 total = (u64)s.n * s.w;
     if (total) {
-        // the look-up tables live in LDS: 2 KiB per word of the row, i.e. batches of up to 4096 source rows per pass
-        const size_t lds = checksum ? (size_t)s.w * 256 * sizeof(u64) : 0;
-        FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID,
-                     "expand checksum: %u source rows need %zu B of LDS tables (limit %d); batch the sources", s.nsrc, lds,
-                     ctx->opt.lds_limit);
         ProfScope ps(ctx, checksum ? "bp_count_kernel<checksum>" : "bp_count_kernel<count>", total * sizeof(u64));
-        u32 grid = cdiv(total, 256);
-        const u32 cap = checksum ? (u32)ctx->cus * 8 : (u32)ctx->cus * 32;   // every workgroup copies the tables once
-        if (grid > cap) grid = cap;
-        if (checksum) {
-            FGPU_TRY(tab.alloc(ctx, (size_t)s.w * 256));
-            hipLaunchKernelGGL(bp_cs_table_kernel, dim3(s.w), dim3(256), 0, ctx->stream(), s.w, tab.p, (const u32*)s.rowmap.p, s.nsrc);
-            if (lds > 48 * 1024)
-                FGPU_HIP(hipFuncSetAttribute((const void*)bp_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(bp_count_kernel<true>, dim3(grid), dim3(256), lds, ctx->stream(), (const u64*)s.x.p, s.n,
-                               s.w, s.ws, label_dev, (const u64*)tab.p, (unsigned long long*)acc.p, (const u32*)nullptr);
-        } else {
-            hipLaunchKernelGGL(bp_count_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n,
-                               s.w, s.ws, label_dev, (const u64*)nullptr, (unsigned long long*)acc.p, (const u32*)nullptr);
-        }
-        FGPU_HIP(hipGetLastError());
+        if (checksum) FGPU_TRY(bp_cs_tables(ctx, s, tab));
+        FGPU_TRY(bp_count_rows(ctx, s, s.x.p, s.n, label_dev, tab.p, acc.p, 32, nullptr));
     }
     return bp_acc_read(ctx, acc.p, nnz, checksum);
 }
@@ -1428,357 +1438,283 @@ static fgpu_info bp_flops(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* a, u
     return FGPU_OK;
 }
 
-// one delta_lmxm in bit form: s.x <- ((X·m) & ~(X·dm)) | (X·dp)
-// what the counting form of a hop needs beside the hop itself
-struct CountArgs {
-    const u64* label;   // destination-label bitmap on the device (nullable)
-    u64* nnz;
-    u64* checksum;      // nullable
+// ---------------------------------------------------------------------------------
+// one delta_lmxm in bit form: Y <- ((X·m) & ~(X·dm)) | (X·dp).  bp_hop (mid-chain: Y becomes the state) and bp_hop_count (the
+// counting end of a chain: Y is counted where it is produced) decide their form once — HopPlan — and then run its steps.
+// ---------------------------------------------------------------------------------
+struct HopPlan {
+    int mode;                  // 0: mid-chain hop; 1 / 2: counting hop without / with the checksum
+    const fgpu_mat* t;         // the cached transpose of m with its item lists (null: m is empty, nothing is pulled)
+    const fgpu_mat *dm, *dp;   // the delta layers that hold entries (null otherwise)
+    size_t lds_tables;         // LDS bytes of the checksum tables (mode 2)
+    bool sparse;               // fewer than 1 row in 8 flagged: a flag probe per neighbour first beats gathering 8 W-byte rows
+    bool groups;               // ... by row groups: rows of <= BP_ITEM entries by bp_pull_groups_kernel, the split rows' items after
+    bool use_rec;              // ... reading records of <= 4 source indices (bp_records_kernel) instead of a flag bit, then the row
+    bool fuse_stats;           // ... summing the next hop's traversed-edge count and the flagged rows on the way
+    const BpXPlan* xp;         // the counting hop runs in its XCD-partitioned form (bitpart.hip) under this plan
+    bool no_touched;           // ... over clean layers: the fold completes every row — no bitmap, prefix, side buffer or read-back
+    const u32* operm;          // mid-chain: the layout the counting hop after this one gathers from (null: vertex order)
+};
+// where the rows of Y go: the new state and its flags, or — counting hop — the touched rows' slots of the side buffer
+struct HopOut {
+    u64* y;
+    uint8_t* flag;
+    BpFinal fin;
 };
 
-static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm,
-                             u64* flops, const CountArgs* ca, const fgpu_mat* next_m = nullptr, const fgpu_mat* count_next = nullptr) {
+// the partitioned form is for states well past one L2 whose rows are 16 to 128 bytes
+static bool bp_xcd_applies(const fgpu_ctx* ctx, u32 n, u32 ws) {
+    return ws >= 2 && ws <= 16 && (u64)n * ws * 8 >= (u64)ctx->opt.expand_xcd_min_mb << 20;
+}
+
+// checks, and the traversed-edge count of the hop unless the hop that produced X summed it already
+static fgpu_info bp_hop_enter(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, u64* flops, bool counting) {
     FGPU_REQUIRE(m->nrows == s.n, FGPU_DIM_MISMATCH, "bit-parallel hop: matrix has %llu rows, frontier %u",
                  (unsigned long long)m->nrows, s.n);
     FGPU_REQUIRE(m->nnz < 0x7FFFFFFFull, FGPU_INVALID, "bit-parallel hop: nnz must be < 2^31");
-    FGPU_REQUIRE(ca || !s.perm, FGPU_INVALID, "bit-parallel hop: a mid-chain hop met a state laid out for a count hop");
+    FGPU_REQUIRE(counting || !s.perm, FGPU_INVALID, "bit-parallel hop: a mid-chain hop met a state laid out for a count hop");
     if (flops) {
         if (s.pre_for == m) *flops += s.pre_flops;     // summed by the hop that produced X
         else FGPU_TRY(bp_flops(ctx, s, m, flops));
         if (dp && dp->nnz) FGPU_TRY(bp_flops(ctx, s, dp, flops));
     }
     s.pre_for = nullptr;
-    const bool has_dm = dm && dm->nnz, has_dp = dp && dp->nnz;
-    const u32 n_out = (u32)m->ncols;
-    const fgpu_mat* t = nullptr;
-    if (m->nnz) FGPU_TRY(transposed_with_items(ctx, m, &t));
-    BitState o;
-    bp_layout(o, n_out, s.nsrc);
-    // ---- counting hop: touched bitmap (split rows + delta destinations), its prefix, the side buffer, the tables
-    DevBuf<u64> tbits, side, tab, acc;
-    DevBuf<u32> tpc, tpref, ttot;
-    BpFinal fin = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    u32 ntouched = 0;
-    const int mode = !ca ? 0 : (ca->checksum ? 2 : 1);
-    size_t lds = 0;
-    // the dense count hop runs in its XCD-partitioned form (bitpart.hip) when the state is well past one L2: the sparse
-    // form, rows wider than 128 bytes, 8-byte rows and mid-chain hops keep the plain pull
-    const bool will_sparse = m->nnz && s.flag.p != nullptr && s.nz_rows * 8 < (u64)s.n &&
-                             bp_sparse_fits(ctx, mode == 2 ? (size_t)s.w * 256 * sizeof(u64) : 0);
-    const BpXPlan* xp = nullptr;
-    if (ca && t && !will_sparse && !s.lazy && s.ws >= 2 && s.ws <= 16 && (u64)s.n * s.ws * 8 >= (u64)ctx->opt.expand_xcd_min_mb << 20) {
-        FGPU_TRY(bp_xplan(ctx, m, t, &xp));
+    return FGPU_OK;
+}
+
+// `next_m` (nullable): the matrix of the hop after a mid-chain one; `count_next` (nullable): that matrix when the hop is the counting one
+static fgpu_info bp_hop_plan(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, int mode,
+                             const fgpu_mat* next_m, const fgpu_mat* count_next, HopPlan& p) {
+    p = HopPlan{};
+    p.mode = mode;
+    p.dm = dm && dm->nnz ? dm : nullptr;
+    p.dp = dp && dp->nnz ? dp : nullptr;
+    if (m->nnz) FGPU_TRY(transposed_with_items(ctx, m, &p.t));
+    p.lds_tables = mode == 2 ? bp_table_bytes(s) : 0;
+    // (the sparse form stages a coarse flag map of <= BP_COARSE_LDS in LDS next to the checksum tables of mode 2)
+    p.sparse = m->nnz && s.flag.p != nullptr && s.nz_rows * 8 < (u64)s.n && bp_sparse_fits(ctx, p.lds_tables);
+    FGPU_REQUIRE(!m->nnz || p.sparse || !s.lazy, FGPU_INVALID, "bit-parallel hop: a lazily zeroed state needs the sparse pull");
+    p.groups = p.sparse && mode == 0 && s.ws <= 16 && ctx->opt.expand_row_groups;
+    p.use_rec = p.groups && ctx->opt.expand_records && s.nsrc < 0xFFFEu;
+    // (the next matrix must be plain CSR over the same vertices; rows a delta fix-up changes after the pull are summed after it)
+    p.fuse_stats = p.groups && next_m && !next_m->is_hyper() && next_m->nrows == m->ncols;
+    // the sparse form, rows wider than 128 bytes, 8-byte rows and mid-chain hops keep the plain pull
+    if (mode && p.t && !p.sparse && !s.lazy && bp_xcd_applies(ctx, s.n, s.ws)) {
+        FGPU_TRY(bp_xplan(ctx, m, p.t, &p.xp));
         // (a fold whose checksum tables and stage do not fit the LDS limit: the plain pull, like a plan that is not usable)
-        if (xp && !bp_xfold_fits(ctx, s.ws, mode, mode == 2 ? (size_t)s.w * 256 * sizeof(u64) : 0)) xp = nullptr;
+        if (p.xp && !bp_xfold_fits(ctx, s.ws, mode, p.lds_tables)) p.xp = nullptr;
     }
-    // the layout of the state: the count hop reads what its plan gathers from (hot-first per partition when the partitioned
-    // form runs, vertex order otherwise); a mid-chain hop about to feed such a count hop WRITES its rows in that layout
-    if (ca) FGPU_TRY(bp_relayout(ctx, s, xp ? bp_xplan_perm(xp) : nullptr));
-    const u32* operm = nullptr;
-    if (!ca && count_next && count_next->nnz && !count_next->is_hyper() && count_next->nrows == m->ncols && o.ws >= 2 && o.ws <= 16 &&
-        (u64)o.n * o.ws * 8 >= (u64)ctx->opt.expand_xcd_min_mb << 20) {
+    p.no_touched = p.xp && !p.dm && !p.dp;
+    // a mid-chain hop about to feed a partitioned count hop WRITES its rows in the layout that hop's plan gathers from (the new
+    // state has m->ncols rows of the same width)
+    if (!mode && count_next && count_next->nnz && !count_next->is_hyper() && count_next->nrows == m->ncols &&
+        bp_xcd_applies(ctx, (u32)m->ncols, s.ws)) {
         const fgpu_mat* tn = nullptr;
         const BpXPlan* nxp = nullptr;
         FGPU_TRY(transposed_with_items(ctx, count_next, &tn));
         FGPU_TRY(bp_xplan(ctx, count_next, tn, &nxp));
-        operm = bp_xplan_perm(nxp);
+        p.operm = bp_xplan_perm(nxp);
     }
-    // clean layers in the partitioned form: the fold completes every row, nothing is "touched" — no bitmap, no prefix, no side
-    // buffer, no read-back (six launches and a host round trip per batch)
-    const bool no_touched = ca && xp && !has_dm && !has_dp;
-    if (ca && !no_touched) {
-        const u32 nwords = (n_out + 63) / 64;
-        FGPU_TRY(tbits.alloc(ctx, (size_t)nwords + 2));
-        if (xp)   // every row is completed by the fold: only the destinations of a delta layer are "touched"
-            FGPU_HIP(hipMemsetAsync(tbits.p, 0, (size_t)nwords * sizeof(u64), ctx->stream()));
-        else if (t && t->bp_split_bits)
-            FGPU_HIP(hipMemcpyAsync(tbits.p, t->bp_split_bits, (size_t)nwords * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream()));
-        else
-            FGPU_HIP(hipMemsetAsync(tbits.p, 0, (size_t)nwords * sizeof(u64), ctx->stream()));
-        for (const fgpu_mat* d : {has_dm ? dm : nullptr, has_dp ? dp : nullptr}) {
-            if (!d) continue;
-            u32 grid = cdiv(d->nnz, 256);
-            if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
-            hipLaunchKernelGGL(bp_mark_cols_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)d->colidx, (u32)d->nnz, tbits.p);
-        }
-        FGPU_TRY(tpc.alloc(ctx, (size_t)nwords + 2));
-        FGPU_TRY(tpref.alloc(ctx, (size_t)nwords + 2));
-        FGPU_TRY(ttot.alloc(ctx, 1));
-        hipLaunchKernelGGL(bp_word_popc_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)tbits.p,
-                           nwords, tpc.p);
-        FGPU_HIP(hipGetLastError());
-        FGPU_TRY(scan_u32(ctx, tpc.p, tpref.p, (u64)nwords + 1, ttot.p));
-        FGPU_TRY(read_u32(ctx, ttot.p, &ntouched));
-        FGPU_TRY(side.alloc(ctx, (size_t)(ntouched ? ntouched : 1) * s.ws));
-        FGPU_HIP(hipMemsetAsync(side.p, 0, (size_t)(ntouched ? ntouched : 1) * s.ws * sizeof(u64), ctx->stream()));
+    return FGPU_OK;
+}
+
+// bits <- `seed` (null: zero), then the destinations of the delta layers
+static fgpu_info bp_touched_bits(fgpu_ctx* ctx, const HopPlan& p, u32 n_out, const u64* seed, DevBuf<u64>& bits) {
+    const u32 nwords = (n_out + 63) / 64;
+    FGPU_TRY(bits.alloc(ctx, (size_t)nwords + 2));
+    if (seed) FGPU_HIP(hipMemcpyAsync(bits.p, seed, (size_t)nwords * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream()));
+    else FGPU_HIP(hipMemsetAsync(bits.p, 0, (size_t)nwords * sizeof(u64), ctx->stream()));
+    for (const fgpu_mat* d : {p.dm, p.dp}) {
+        if (!d) continue;
+        u32 grid = cdiv(d->nnz, 256);
+        if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
+        FGPU_TRY(launch(bp_mark_cols_kernel, dim3(grid), dim3(256), 0, ctx->stream(), d->colidx, (u32)d->nnz, bits.p));
     }
-    if (ca) {
-        FGPU_TRY(bp_acc_alloc(ctx, acc));
-        if (mode == 2) {
-            lds = (size_t)s.w * 256 * sizeof(u64);
-            FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID,
-                         "expand checksum: %u source rows need %zu B of LDS tables (limit %d); batch the sources", s.nsrc, lds,
-                         ctx->opt.lds_limit);
-            FGPU_TRY(tab.alloc(ctx, (size_t)s.w * 256));
-            hipLaunchKernelGGL(bp_cs_table_kernel, dim3(s.w), dim3(256), 0, ctx->stream(), s.w, tab.p, (const u32*)s.rowmap.p, s.nsrc);
-        }
-        fin = BpFinal{tbits.p, tpref.p, ca->label, tab.p, (unsigned long long*)acc.p, s.w};
-    } else {
-        FGPU_TRY(bp_alloc_zero(ctx, o.x, o));
-        FGPU_TRY(bp_alloc_flags(ctx, o));
+    return FGPU_OK;
+}
+
+// counting hop: the touched bitmap (rows cut into several items + delta destinations; in the partitioned form the fold completes
+// every row, so the delta destinations only), its prefix, and a zeroed side buffer of one slot per touched row
+static fgpu_info bp_touched_side(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, u32 n_out, DevBuf<u64>& tbits, DevBuf<u32>& tpref,
+                                 DevBuf<u64>& side, u32* ntouched) {
+    FGPU_TRY(bp_touched_bits(ctx, p, n_out, p.xp || !p.t ? nullptr : p.t->bp_split_bits, tbits));
+    const u32 nwords = (n_out + 63) / 64;
+    DevBuf<u32> tpc, ttot;
+    FGPU_TRY(tpc.alloc(ctx, (size_t)nwords + 2));
+    FGPU_TRY(tpref.alloc(ctx, (size_t)nwords + 2));
+    FGPU_TRY(ttot.alloc(ctx, 1));
+    FGPU_TRY(launch(bp_word_popc_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), tbits.p, nwords, tpc.p));
+    FGPU_TRY(scan_u32(ctx, tpc.p, tpref.p, (u64)nwords + 1, ttot.p));
+    FGPU_TRY(read_u32(ctx, ttot.p, ntouched));
+    const size_t words = (size_t)(*ntouched ? *ntouched : 1) * s.ws;
+    FGPU_TRY(side.alloc(ctx, words));
+    FGPU_HIP(hipMemsetAsync(side.p, 0, words * sizeof(u64), ctx->stream()));
+    return FGPU_OK;
+}
+
+// what the sparse forms probe before they gather a row: a flag bit per vertex (not when records answer instead) behind a coarse
+// map that a workgroup stages in LDS
+struct BpProbeMaps {
+    DevBuf<u64> bits, coarse;
+    BpProbe pr = {nullptr, nullptr, 0, 0};
+    size_t lds = 0;
+};
+static fgpu_info bp_probe_maps(fgpu_ctx* ctx, const BitState& s, bool with_bits, BpProbeMaps& pm) {
+    if (with_bits) {
+        FGPU_TRY(pm.bits.alloc(ctx, ((size_t)s.n + 63) / 64 + 1));
+        FGPU_TRY(launch(bp_flag_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), s.flag.p, s.n, pm.bits.p));
     }
-    bool fuse_stats = false;
-    DevBuf<u64> gstats, later;
-    u64* ydst = ca ? side.p : o.x.p;          // rows of Y, or the slots of the side buffer
-    uint8_t* yflag = ca ? nullptr : o.flag.p;
-    int pull_idx = -1;
-    if (m->nnz && xp) {
-        const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
-        FGPU_TRY(bp_xpull_count(ctx, xp, t, (const u64*)s.x.p, s.ws, mode, fin, side.p, lds, xrows));
-    } else if (m->nnz) {
-        // (the sparse form stages a coarse flag map of <= BP_COARSE_LDS in LDS next to the checksum tables of MODE 2)
-        const bool sparse = s.flag.p != nullptr && s.nz_rows * 8 < (u64)s.n && bp_sparse_fits(ctx, lds);
-        FGPU_REQUIRE(sparse || !s.lazy, FGPU_INVALID, "bit-parallel hop: a lazily zeroed state needs the sparse pull");
-        // row-group form: rows of <= BP_ITEM entries by bp_pull_groups_kernel, the split rows' items by the item kernel
-        const bool groups = sparse && mode == 0 && s.ws <= 16 && ctx->opt.expand_row_groups;
-        // ... and it can sum the next hop's traversed-edge count and the flagged rows on its way (the next matrix must be
-        // plain CSR over the same vertices); rows a delta fix-up changes after the pull are summed after it
-        fuse_stats = groups && next_m && !next_m->is_hyper() && next_m->nrows == m->ncols;
-        const u32 nitems = groups ? t->n_bp_sitems : t->n_bp_items;
-        const u32* item_list = groups ? t->bp_sitems : t->bp_items;
-        const CsrView tv = view_of(t);
-        u32 grid = cdiv(nitems ? nitems : 1, 4);
-        if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        const u32 threads = (mode == 2 || sparse) ? 1024 : 256;
-        if (threads == 1024) {                        // 16-wavefront workgroups: same wavefront count, a quarter of the grid
-            grid = cdiv(nitems ? nitems : 1, 16);
-            if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
-        }
-        const u32 ln = s.ws < 64 ? s.ws : 64;
-        // fewer than 1 row in 8 flagged: probing a flag bit per neighbour first beats gathering 8 W-byte rows
-        DevBuf<u64> xbits, xcoarse;
-        BpProbe pr = {nullptr, nullptr, 0, 0};
-        size_t lds_co = 0;
-        // the state's non-zero rows as records of <= 4 source indices (bp_records_kernel), one for EVERY vertex: what both kernels
-        // of the row-group form read per entry that passes the LDS map, instead of a flag bit and then the whole row
-        const bool use_rec = groups && ctx->opt.expand_records && s.nsrc < 0xFFFEu && s.nz_rows * 8 < (u64)s.n;
-        if (sparse) {
-            if (!use_rec) {
-                const u32 nw = (u32)(((size_t)s.n + 63) / 64);
-                FGPU_TRY(xbits.alloc(ctx, (size_t)nw + 1));
-                hipLaunchKernelGGL(bp_flag_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p,
-                                   s.n, xbits.p);
-                FGPU_HIP(hipGetLastError());
-            }
-            const u32 cshift = bp_coarse_shift(s.n);
-            const u32 nblocks = (u32)(((u64)s.n + (1ull << cshift) - 1) >> cshift);
-            const u32 cwords = (nblocks + 63) / 64;
-            FGPU_TRY(xcoarse.alloc(ctx, (size_t)cwords + 1));
-            hipLaunchKernelGGL(bp_coarse_flags_kernel, dim3(cdiv(cwords, 4)), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n,
-                               cshift, xcoarse.p, cwords);
-            FGPU_HIP(hipGetLastError());
-            pr = BpProbe{xbits.p, xcoarse.p, cshift, cwords};
-            lds_co = (size_t)cwords * sizeof(u64);
-        }
-        // algorithmic bytes of the launch: the column ids of A' and the item list once, every non-zero X row once
-        // (the per-entry row gathers beyond that are cache traffic), the flag bitmap in the sparse form; the
-        // non-zero Y rows a mid-chain hop writes are added once they are counted (bp_count_flags below)
-        const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
-        const char* nm = ca ? (sparse ? "bp_pull_kernel<sparse, count>" : "bp_pull_kernel<dense, count>")
-                            : (sparse ? "bp_pull_kernel<sparse>" : "bp_pull_kernel<dense>");
-        ProfScope ps(ctx, nm, 4 * (u64)t->nnz + 12 * (u64)nitems + xrows * 8 * s.w +
-                                  (sparse ? (u64)s.n / 8 : 0));
-        ps.idx_out = &pull_idx;
-#define BP_LAUNCH3(LN, SP, MD)                                                                                          \
-    do {                                                                                                                \
-        const size_t lds_all = (MD == 2 ? lds : 0) + (SP ? lds_co + (threads / 64) * BP_ITEM * sizeof(u32) : 0);        \
-        if (lds_all > 48 * 1024)                                                                                        \
-            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_kernel<LN, SP, MD>,                                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all));                    \
-        hipLaunchKernelGGL((bp_pull_kernel<LN, SP, MD>), dim3(grid), dim3(threads), lds_all, ctx->stream(),             \
-                           tv, item_list, nitems, s.ws, (const u64*)s.x.p, pr, ydst, yflag, fin, MD == 0 ? operm : (const u32*)nullptr); \
-    } while (0)
-#define BP_LAUNCH(LN)                                                                                                   \
-    do {                                                                                                                \
-        if (mode == 0) { if (sparse) BP_LAUNCH3(LN, true, 0); else BP_LAUNCH3(LN, false, 0); }                          \
-        else if (mode == 1) { if (sparse) BP_LAUNCH3(LN, true, 1); else BP_LAUNCH3(LN, false, 1); }                     \
-        else { if (sparse) BP_LAUNCH3(LN, true, 2); else BP_LAUNCH3(LN, false, 2); }                                    \
-    } while (0)
-        if (fuse_stats) {
-            FGPU_TRY(bp_acc_alloc(ctx, gstats));
-            if (has_dm || has_dp) {   // split rows + delta destinations: the rows summed after the fix-ups
-                const u32 nwords = (n_out + 63) / 64;
-                FGPU_TRY(later.alloc(ctx, (size_t)nwords + 2));
-                if (t->bp_split_bits)
-                    FGPU_HIP(hipMemcpyAsync(later.p, t->bp_split_bits, (size_t)nwords * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream()));
-                else
-                    FGPU_HIP(hipMemsetAsync(later.p, 0, (size_t)nwords * sizeof(u64), ctx->stream()));
-                for (const fgpu_mat* d : {has_dm ? dm : nullptr, has_dp ? dp : nullptr}) {
-                    if (!d) continue;
-                    u32 grid = cdiv(d->nnz, 256);
-                    if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
-                    hipLaunchKernelGGL(bp_mark_cols_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)d->colidx, (u32)d->nnz, later.p);
-                }
-                FGPU_HIP(hipGetLastError());
-            }
-        }
-        DevBuf<u64> recs;
-        if (use_rec) {
-            FGPU_TRY(recs.alloc(ctx, (size_t)s.n + 1));
-            ProfScope psr(ctx, "bp_records_kernel", (u64)s.n + s.nz_rows * (s.ws * 8 + 8));
-            const u32 tiles = (s.n + 2047u) >> 11;
-            const u32 rgrid = tiles < (u32)ctx->cus * 8u ? tiles : (u32)ctx->cus * 8u;
-            hipLaunchKernelGGL(bp_records_kernel, dim3(rgrid ? rgrid : 1), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n, s.ws,
-                               (const u64*)s.x.p, recs.p);
-            FGPU_HIP(hipGetLastError());
-        }
-        if (groups) {
-            ProfScope pg(ctx, "sparse pull: row groups", 0);   // (nested in the hop's record: the split between the two launches)
-            const size_t per_wave = ((size_t)BP_GROUP * s.ws + 256 + 32) * sizeof(u64);
-            // the map is paid once per workgroup: as many wavefronts share it as the LDS holds beside it, 16 at most, and the
-            // grid keeps 16 wavefronts on a CU where they fit (32 KiB + 16 x 6.4 KiB with 128-byte rows: one workgroup)
-            u32 gwaves = (u32)(((size_t)ctx->opt.lds_limit - lds_co) / per_wave);
-            if (gwaves > BP_GROUP_WAVES) gwaves = BP_GROUP_WAVES;
-            FGPU_REQUIRE(gwaves >= 1, FGPU_INVALID, "sparse pull: a row group needs %zu B of LDS beside the %zu B flag map (limit %d)",
-                         per_wave, lds_co, ctx->opt.lds_limit);
-            const size_t lds_g = lds_co + gwaves * per_wave;
-            u32 wgs = (u32)((size_t)ctx->opt.lds_limit / lds_g);
-            if (wgs * gwaves > 32) wgs = 32 / gwaves;
-            const u32 ggrid = (u32)ctx->cus * wgs;
-#define BP_GROUPS2(LN, RC)                                                                                              \
-    do {                                                                                                                \
-        if (lds_g > 48 * 1024)                                                                                          \
-            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_groups_kernel<LN, RC>,                                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));                      \
-        hipLaunchKernelGGL((bp_pull_groups_kernel<LN, RC>), dim3(ggrid), dim3(gwaves * 64), lds_g, ctx->stream(),       \
-                           view_of(t), (u32)t->nrows, (const u64*)s.x.p, pr, ydst, yflag,                               \
-                           fuse_stats ? (const u32*)next_m->rowptr : (const u32*)nullptr,                               \
-                           fuse_stats ? (unsigned long long*)gstats.p : (unsigned long long*)nullptr,                   \
-                           (const u64*)later.p, operm, (const u64*)recs.p);                                             \
-    } while (0)
-#define BP_GROUPS(LN)                                                                                                   \
-    do {                                                                                                                \
-        if (recs.p) BP_GROUPS2(LN, true); else BP_GROUPS2(LN, false);                                                   \
-    } while (0)
-            switch (s.ws) {
-                case 1: BP_GROUPS(1); break;
-                case 2: BP_GROUPS(2); break;
-                case 4: BP_GROUPS(4); break;
-                case 8: BP_GROUPS(8); break;
-                default: BP_GROUPS(16); break;
-            }
-#undef BP_GROUPS
-#undef BP_GROUPS2
-            FGPU_HIP(hipGetLastError());
-        }
-        if (nitems && recs.p) {
-            // the items of the split rows, a lane per entry through the records (groups => s.ws <= 16 = the row's lanes)
-            ProfScope pi(ctx, "bp_pull_items_rec_kernel", 0);   // (nested in the hop's record, like the row groups)
-            const size_t lds_i = lds_co + 16 * ((size_t)BP_IREC_COPIES * s.ws + BP_ITEM / 2) * sizeof(u64);
-            u32 igrid = cdiv(nitems, 16);
-            if (igrid > (u32)ctx->cus * 2) igrid = ctx->cus * 2;     // 32 wavefronts on a CU: all it holds
-#define BP_ITEMS_REC(LN)                                                                                                \
-    do {                                                                                                                \
-        if (lds_i > 48 * 1024)                                                                                          \
-            FGPU_HIP(hipFuncSetAttribute((const void*)bp_pull_items_rec_kernel<LN>,                                     \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_i));                      \
-        hipLaunchKernelGGL(bp_pull_items_rec_kernel<LN>, dim3(igrid), dim3(1024), lds_i, ctx->stream(), tv, item_list,  \
-                           nitems, (const u64*)s.x.p, (const u64*)recs.p, pr, ydst, yflag, operm);                      \
-    } while (0)
-            switch (s.ws) {
-                case 1: BP_ITEMS_REC(1); break;
-                case 2: BP_ITEMS_REC(2); break;
-                case 4: BP_ITEMS_REC(4); break;
-                case 8: BP_ITEMS_REC(8); break;
-                default: BP_ITEMS_REC(16); break;
-            }
-#undef BP_ITEMS_REC
-        } else if (nitems) switch (ln) {
-            case 1: BP_LAUNCH(1); break;
-            case 2: BP_LAUNCH(2); break;
-            case 4: BP_LAUNCH(4); break;
-            case 8: BP_LAUNCH(8); break;
-            case 16: BP_LAUNCH(16); break;
-            case 32: BP_LAUNCH(32); break;
-            default: BP_LAUNCH(64); break;
-        }
-#undef BP_LAUNCH
-#undef BP_LAUNCH3
-        FGPU_HIP(hipGetLastError());
+    const u32 cshift = bp_coarse_shift(s.n);
+    const u32 nblocks = (u32)(((u64)s.n + (1ull << cshift) - 1) >> cshift);
+    const u32 cwords = (nblocks + 63) / 64;
+    FGPU_TRY(pm.coarse.alloc(ctx, (size_t)cwords + 1));
+    pm.pr = BpProbe{pm.bits.p, pm.coarse.p, cshift, cwords};
+    pm.lds = (size_t)cwords * sizeof(u64);
+    return launch(bp_coarse_flags_kernel, dim3(cdiv(cwords, 4)), dim3(256), 0, ctx->stream(), s.flag.p, s.n, cshift, pm.coarse.p, cwords);
+}
+
+// the plain item pull: a wavefront per item of <= BP_ITEM entries, dense or behind the flag probe, in every mode
+static fgpu_info bp_pull_items(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const u32* items, u32 nitems, const BpProbeMaps& pm,
+                               const HopOut& out) {
+    if (!nitems) return FGPU_OK;
+    // (16-wavefront workgroups in the sparse and checksum forms: same wavefront count, a quarter of the grid)
+    const u32 threads = (p.mode == 2 || p.sparse) ? 1024 : 256;
+    u32 grid = cdiv(nitems, threads / 64);
+    const u32 cap = (u32)ctx->cus * (threads == 1024 ? 8 : 32);
+    if (grid > cap) grid = cap;
+    const size_t lds = p.lds_tables + (p.sparse ? pm.lds + (threads / 64) * BP_ITEM * sizeof(u32) : 0);
+    return pick<1, 2, 4, 8, 16, 32, 64>((int)s.ws, [&](auto ln) { return pick(p.sparse, [&](auto sp) { return pick<0, 1, 2>(p.mode, [&](auto md) {
+        return launch(bp_pull_kernel<decltype(ln)::value, decltype(sp)::value, decltype(md)::value>, dim3(grid), dim3(threads), lds, ctx->stream(),
+                      view_of(p.t), items, nitems, s.ws, s.x.p, pm.pr, out.y, out.flag, out.fin, p.operm);
+    }); }); });
+}
+
+// what the row-group form sums for the next hop on its way: the two sums, and the rows that are summed after the fix-ups
+struct FusedStats {
+    DevBuf<u64> sums, later;
+};
+
+// the state's non-zero rows as records of <= 4 source indices, one for EVERY vertex: what both kernels of the row-group form read
+// per entry that passes the LDS map, instead of a flag bit and then the whole row
+static fgpu_info bp_records(fgpu_ctx* ctx, const BitState& s, DevBuf<u64>& recs) {
+    FGPU_TRY(recs.alloc(ctx, (size_t)s.n + 1));
+    ProfScope ps(ctx, "bp_records_kernel", (u64)s.n + s.nz_rows * (s.ws * 8 + 8));
+    const u32 tiles = (s.n + 2047u) >> 11;
+    const u32 grid = tiles < (u32)ctx->cus * 8u ? tiles : (u32)ctx->cus * 8u;
+    return launch(bp_records_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), s.flag.p, s.n, s.ws, s.x.p, recs.p);
+}
+
+// the rows of <= BP_ITEM entries, 64 to a wavefront
+static fgpu_info bp_pull_group_rows(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const BpProbeMaps& pm, const HopOut& out,
+                                    const fgpu_mat* next_m, const FusedStats& st, const u64* recs) {
+    ProfScope pg(ctx, "sparse pull: row groups", 0);   // (nested in the hop's record: the split between the two launches)
+    const size_t per_wave = ((size_t)BP_GROUP * s.ws + 256 + 32) * sizeof(u64);
+    // the map is paid once per workgroup: as many wavefronts share it as the LDS holds beside it, 16 at most, and the
+    // grid keeps 16 wavefronts on a CU where they fit (32 KiB + 16 x 6.4 KiB with 128-byte rows: one workgroup)
+    u32 gwaves = (u32)(((size_t)ctx->opt.lds_limit - pm.lds) / per_wave);
+    if (gwaves > BP_GROUP_WAVES) gwaves = BP_GROUP_WAVES;
+    FGPU_REQUIRE(gwaves >= 1, FGPU_INVALID, "sparse pull: a row group needs %zu B of LDS beside the %zu B flag map (limit %d)",
+                 per_wave, pm.lds, ctx->opt.lds_limit);
+    const size_t lds = pm.lds + gwaves * per_wave;
+    u32 wgs = (u32)((size_t)ctx->opt.lds_limit / lds);
+    if (wgs * gwaves > 32) wgs = 32 / gwaves;
+    return pick<1, 2, 4, 8, 16>((int)s.ws, [&](auto ln) { return pick(recs != nullptr, [&](auto rec) {
+        return launch(bp_pull_groups_kernel<decltype(ln)::value, decltype(rec)::value>, dim3((u32)ctx->cus * wgs), dim3(gwaves * 64), lds,
+                      ctx->stream(), view_of(p.t), (u32)p.t->nrows, s.x.p, pm.pr, out.y, out.flag, p.fuse_stats ? next_m->rowptr : nullptr,
+                      (unsigned long long*)st.sums.p, st.later.p, p.operm, recs);
+    }); });
+}
+
+// the items of the split rows, a lane per entry through the records (groups => s.ws <= 16 = the row's lanes)
+static fgpu_info bp_pull_items_rec(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const BpProbeMaps& pm, const HopOut& out,
+                                   const u64* recs) {
+    const u32 nitems = p.t->n_bp_sitems;
+    if (!nitems) return FGPU_OK;
+    ProfScope pi(ctx, "bp_pull_items_rec_kernel", 0);   // (nested in the hop's record, like the row groups)
+    const size_t lds = pm.lds + 16 * ((size_t)BP_IREC_COPIES * s.ws + BP_ITEM / 2) * sizeof(u64);
+    u32 grid = cdiv(nitems, 16);
+    if (grid > (u32)ctx->cus * 2) grid = ctx->cus * 2;     // 32 wavefronts on a CU: all it holds
+    return pick<1, 2, 4, 8, 16>((int)s.ws, [&](auto ln) {
+        return launch(bp_pull_items_rec_kernel<decltype(ln)::value>, dim3(grid), dim3(1024), lds, ctx->stream(), view_of(p.t), p.t->bp_sitems,
+                      nitems, s.x.p, recs, pm.pr, out.y, out.flag, p.operm);
+    });
+}
+
+// the sparse pull of a mid-chain hop by row groups: the rows of <= BP_ITEM entries by the group kernel, the split rows' items by
+// an item kernel after it
+static fgpu_info bp_pull_groups(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const BpProbeMaps& pm, const HopOut& out,
+                                const fgpu_mat* next_m, FusedStats& st) {
+    if (p.fuse_stats) {
+        FGPU_TRY(bp_acc_alloc(ctx, st.sums));
+        // split rows + delta destinations: the rows summed after the fix-ups
+        if (p.dm || p.dp) FGPU_TRY(bp_touched_bits(ctx, p, (u32)p.t->nrows, p.t->bp_split_bits, st.later));
     }
-    {
-        u32 ln = 1;                               // lanes per delta entry: a power of two covering the row words
-        while (ln < s.w && ln < 64) ln <<= 1;
-        const u32 *wr_dm = nullptr, *wr_dp = nullptr;
-        if (has_dm) FGPU_TRY(mat_wordrow(ctx, dm, &wr_dm));
-        if (has_dp) FGPU_TRY(mat_wordrow(ctx, dp, &wr_dp));
-        if (has_dm) {
-            ProfScope ps(ctx, "bp_delta_kernel<dm>", (u64)dm->nnz * (4 + 16 * s.w));
-            u32 grid = cdiv((u64)dm->nnz * ln, 256);
-            if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-            hipLaunchKernelGGL(bp_delta_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(dm), (u32)dm->nnz,
-                               s.w, s.ws, ln, (const u64*)s.x.p, ydst, yflag, fin.tbits, fin.tpref,
-                               s.lazy ? (const uint8_t*)s.flag.p : (const uint8_t*)nullptr, wr_dm, s.perm, ca ? (const u32*)nullptr : operm);
-            FGPU_HIP(hipGetLastError());
-        }
-        if (has_dp) {
-            ProfScope ps(ctx, "bp_delta_kernel<dp>", (u64)dp->nnz * (4 + 16 * s.w));
-            u32 grid = cdiv((u64)dp->nnz * ln, 256);
-            if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-            hipLaunchKernelGGL(bp_delta_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(dp), (u32)dp->nnz,
-                               s.w, s.ws, ln, (const u64*)s.x.p, ydst, yflag, fin.tbits, fin.tpref,
-                               s.lazy ? (const uint8_t*)s.flag.p : (const uint8_t*)nullptr, wr_dp, s.perm, ca ? (const u32*)nullptr : operm);
-            FGPU_HIP(hipGetLastError());
-        }
-    }
-    if (ca) {
-        if (ntouched) {
-            ProfScope ps(ctx, "bp_count_kernel<side rows>", (u64)ntouched * s.w * 8);
-            DevBuf<u32> vmap;
-            FGPU_TRY(vmap.alloc(ctx, (size_t)ntouched + 1));
-            hipLaunchKernelGGL(bp_slot_vertex_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u64*)tbits.p,
-                               (const u32*)tpref.p, n_out, vmap.p);
-            const u64 total = (u64)ntouched * s.w;
-            u32 grid = cdiv(total, 256);
-            const u32 cap = mode == 2 ? (u32)ctx->cus * 4 : (u32)ctx->cus * 16;
-            if (grid > cap) grid = cap;
-            if (mode == 2) {
-                if (lds > 48 * 1024)
-                    FGPU_HIP(hipFuncSetAttribute((const void*)bp_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(bp_count_kernel<true>, dim3(grid), dim3(256), lds, ctx->stream(), (const u64*)side.p, ntouched,
-                                   s.w, s.ws, ca->label, (const u64*)tab.p, (unsigned long long*)acc.p, (const u32*)vmap.p);
-            } else {
-                hipLaunchKernelGGL(bp_count_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), (const u64*)side.p, ntouched,
-                                   s.w, s.ws, ca->label, (const u64*)nullptr, (unsigned long long*)acc.p, (const u32*)vmap.p);
-            }
-            FGPU_HIP(hipGetLastError());
-        }
-        FGPU_TRY(bp_acc_read(ctx, acc.p, ca->nnz, ca->checksum));   // ONE read-back for both sums
-        bp_recycle_state(ctx, s);   // the chain ends here: no state is left behind (the block goes back zeroed when that is cheap)
-        s.n = n_out;
-        return FGPU_OK;
-    }
-    if (fuse_stats) {
-        if (t->n_bp_sitems || later.p) {
+    DevBuf<u64> recs;
+    if (p.use_rec) FGPU_TRY(bp_records(ctx, s, recs));
+    FGPU_TRY(bp_pull_group_rows(ctx, p, s, pm, out, next_m, st, recs.p));
+    if (p.use_rec) return bp_pull_items_rec(ctx, p, s, pm, out, recs.p);
+    return bp_pull_items(ctx, p, s, p.t->bp_sitems, p.t->n_bp_sitems, pm, out);
+}
+
+// the pull of a hop in its plain and sparse forms, under the hop's profiler record (`pull_idx`: bp_hop adds the rows it wrote)
+static fgpu_info bp_pull(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const HopOut& out, const fgpu_mat* next_m,
+                         FusedStats* st, int* pull_idx) {
+    BpProbeMaps pm;
+    if (p.sparse) FGPU_TRY(bp_probe_maps(ctx, s, !p.use_rec, pm));
+    // algorithmic bytes of the launch: the column ids of A' and the item list once, every non-zero X row once
+    // (the per-entry row gathers beyond that are cache traffic), the flag bitmap in the sparse form; the
+    // non-zero Y rows a mid-chain hop writes are added once they are counted (bp_hop_finish)
+    const u32 nitems = p.groups ? p.t->n_bp_sitems : p.t->n_bp_items;
+    const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
+    const char* nm = p.mode ? (p.sparse ? "bp_pull_kernel<sparse, count>" : "bp_pull_kernel<dense, count>")
+                            : (p.sparse ? "bp_pull_kernel<sparse>" : "bp_pull_kernel<dense>");
+    ProfScope ps(ctx, nm, 4 * (u64)p.t->nnz + 12 * (u64)nitems + xrows * 8 * s.w + (p.sparse ? (u64)s.n / 8 : 0));
+    ps.idx_out = pull_idx;
+    if (p.groups) return bp_pull_groups(ctx, p, s, pm, out, next_m, *st);   // (mid-chain hops only)
+    return bp_pull_items(ctx, p, s, p.t->bp_items, p.t->n_bp_items, pm, out);
+}
+
+// Y[v] &= ~X[u] for the entries (u, v) of dm, Y[v] |= X[u] for those of dp
+static fgpu_info bp_delta_fixup(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const fgpu_mat* d, bool is_dm, const u32* wordrow,
+                                const HopOut& out) {
+    u32 ln = 1;                               // lanes per delta entry: a power of two covering the row words
+    while (ln < s.w && ln < 64) ln <<= 1;
+    ProfScope ps(ctx, is_dm ? "bp_delta_kernel<dm>" : "bp_delta_kernel<dp>", (u64)d->nnz * (4 + 16 * s.w));
+    u32 grid = cdiv((u64)d->nnz * ln, 256);
+    if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
+    return pick(is_dm, [&](auto k) {
+        return launch(bp_delta_kernel<decltype(k)::value>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(d), (u32)d->nnz, s.w, s.ws, ln,
+                      s.x.p, out.y, out.flag, out.fin.tbits, out.fin.tpref, s.lazy ? s.flag.p : nullptr, wordrow, s.perm, p.operm);
+    });
+}
+static fgpu_info bp_delta_fixups(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, const HopOut& out) {
+    const u32 *wr_dm = nullptr, *wr_dp = nullptr;
+    if (p.dm) FGPU_TRY(mat_wordrow(ctx, p.dm, &wr_dm));
+    if (p.dp) FGPU_TRY(mat_wordrow(ctx, p.dp, &wr_dp));
+    if (p.dm) FGPU_TRY(bp_delta_fixup(ctx, p, s, p.dm, true, wr_dm, out));
+    if (p.dp) FGPU_TRY(bp_delta_fixup(ctx, p, s, p.dp, false, wr_dp, out));
+    return FGPU_OK;
+}
+
+// mid-chain epilogue: the non-zero rows of the new state (and, fused, the next hop's traversed edges), then `o` becomes the state
+static fgpu_info bp_hop_finish(fgpu_ctx* ctx, const HopPlan& p, BitState& s, BitState& o, const fgpu_mat* next_m, const FusedStats& st,
+                               int pull_idx) {
+    if (p.fuse_stats) {
+        if (p.t->n_bp_sitems || st.later.p) {
             u32 lnsh = 0;
             while ((2u << lnsh) <= s.ws && lnsh < 6) ++lnsh;
-            hipLaunchKernelGGL(bp_split_stats_kernel, dim3(ctx->cus * 2), dim3(256), 0, ctx->stream(),
-                               later.p ? (const u64*)later.p : (const u64*)t->bp_split_bits,
-                               n_out, s.ws, lnsh, (const u64*)o.x.p, (const u32*)next_m->rowptr, (unsigned long long*)gstats.p, operm);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(bp_split_stats_kernel, dim3(ctx->cus * 2), dim3(256), 0, ctx->stream(), st.later.p ? st.later.p : p.t->bp_split_bits,
+                            o.n, s.ws, lnsh, o.x.p, next_m->rowptr, (unsigned long long*)st.sums.p, p.operm));
         }
-        u64 st[2] = {0, 0};
-        FGPU_TRY(bp_acc_read(ctx, gstats.p, &st[0], &st[1]));
-        o.nz_rows = st[1];
+        FGPU_TRY(bp_acc_read(ctx, st.sums.p, &o.pre_flops, &o.nz_rows));
         o.pre_for = next_m;
-        o.pre_flops = st[0];
     } else {
         FGPU_TRY(bp_count_flags(ctx, o));
     }
     prof_add_bytes(ctx, pull_idx, o.nz_rows * 8 * s.w);
     s.x = std::move(o.x);
     s.flag = std::move(o.flag);
-    s.perm = operm;
+    s.perm = p.operm;
     s.nz_rows = o.nz_rows;
     s.lazy = false;            // o.x was zeroed as a whole
     s.pre_for = o.pre_for;
@@ -1787,15 +1723,59 @@ static fgpu_info bp_hop_impl(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, cons
     return FGPU_OK;
 }
 
+// counting epilogue: the touched rows are counted from the side buffer, ONE read-back fetches both sums, and the chain's last
+// state goes back to the pool (zeroed when that is cheap)
+static fgpu_info bp_count_finish(fgpu_ctx* ctx, BitState& s, u32 n_out, u32 ntouched, const HopOut& out, u64* nnz, u64* checksum) {
+    if (ntouched) {
+        ProfScope ps(ctx, "bp_count_kernel<side rows>", (u64)ntouched * s.w * 8);
+        DevBuf<u32> vmap;
+        FGPU_TRY(vmap.alloc(ctx, (size_t)ntouched + 1));
+        FGPU_TRY(launch(bp_slot_vertex_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), out.fin.tbits, out.fin.tpref, n_out, vmap.p));
+        FGPU_TRY(bp_count_rows(ctx, s, out.y, ntouched, out.fin.label, out.fin.tab, (u64*)out.fin.acc, 16, vmap.p));
+    }
+    FGPU_TRY(bp_acc_read(ctx, (u64*)out.fin.acc, nnz, checksum));
+    bp_recycle_state(ctx, s);
+    s.n = n_out;
+    return FGPU_OK;
+}
+
 fgpu_info bp_hop(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, u64* flops,
                  const fgpu_mat* next_m, const fgpu_mat* count_next) {
-    return bp_hop_impl(ctx, s, m, dp, dm, flops, nullptr, next_m, count_next);
+    HopPlan p;
+    FGPU_TRY(bp_hop_enter(ctx, s, m, dp, flops, false));
+    FGPU_TRY(bp_hop_plan(ctx, s, m, dp, dm, 0, next_m, count_next, p));
+    BitState o;
+    bp_layout(o, (u32)m->ncols, s.nsrc);
+    FGPU_TRY(bp_alloc_zero(ctx, o.x, o));
+    FGPU_TRY(bp_alloc_flags(ctx, o));
+    const HopOut out = {o.x.p, o.flag.p, BpFinal{nullptr, nullptr, nullptr, nullptr, nullptr, 0}};
+    FusedStats st;
+    int pull_idx = -1;
+    if (p.t) FGPU_TRY(bp_pull(ctx, p, s, out, next_m, &st, &pull_idx));
+    FGPU_TRY(bp_delta_fixups(ctx, p, s, out));
+    return bp_hop_finish(ctx, p, s, o, next_m, st, pull_idx);
 }
 
 fgpu_info bp_hop_count(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, u64* flops,
                        const u64* label_dev, u64* nnz, u64* checksum) {
-    CountArgs ca{label_dev, nnz, checksum};
-    return bp_hop_impl(ctx, s, m, dp, dm, flops, &ca);
+    HopPlan p;
+    FGPU_TRY(bp_hop_enter(ctx, s, m, dp, flops, true));
+    FGPU_TRY(bp_hop_plan(ctx, s, m, dp, dm, checksum ? 2 : 1, nullptr, nullptr, p));
+    // the state in the layout the pull reads: hot-first per partition for the partitioned form, vertex order otherwise
+    FGPU_TRY(bp_relayout(ctx, s, bp_xplan_perm(p.xp)));
+    const u32 n_out = (u32)m->ncols;
+    DevBuf<u64> tbits, side, tab, acc;
+    DevBuf<u32> tpref;
+    u32 ntouched = 0;
+    if (!p.no_touched) FGPU_TRY(bp_touched_side(ctx, p, s, n_out, tbits, tpref, side, &ntouched));
+    FGPU_TRY(bp_acc_alloc(ctx, acc));
+    if (p.mode == 2) FGPU_TRY(bp_cs_tables(ctx, s, tab));
+    const HopOut out = {side.p, nullptr, BpFinal{tbits.p, tpref.p, label_dev, tab.p, (unsigned long long*)acc.p, s.w}};
+    const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
+    if (p.xp) FGPU_TRY(bp_xpull_count(ctx, p.xp, p.t, s.x.p, s.ws, p.mode, out.fin, side.p, p.lds_tables, xrows));
+    else if (p.t) FGPU_TRY(bp_pull(ctx, p, s, out, nullptr, nullptr, nullptr));
+    FGPU_TRY(bp_delta_fixups(ctx, p, s, out));
+    return bp_count_finish(ctx, s, n_out, ntouched, out, nnz, checksum);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2131,10 +2111,6 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
     const size_t lds_rows = (size_t)BP_ROWS_NB * 64 * (wmax + 1) * sizeof(u64) + (size_t)wmax * 64 * sizeof(u32) + BP_VCHUNK;
     FGPU_REQUIRE(lds_rows <= (size_t)ctx->opt.lds_limit, FGPU_INVALID,
                  "emission tile of a %u-word row needs %zu B of LDS, the device / lds_limit allows %d", s.w, lds_rows, ctx->opt.lds_limit);
-    if (lds_rows > 48 * 1024) {
-        FGPU_HIP(hipFuncSetAttribute((const void*)bp_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-        FGPU_HIP(hipFuncSetAttribute((const void*)bp_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-    }
     // algorithmic bytes of the emission (the north_star's "ballot / prefix-scan output compaction"): per pass the flags of
     // every row and the words of the non-zero rows once, the counts / offsets table once, and 4 B per emitted destination.
     // (Tried and dropped: staging the rows of block i + 1 in registers while block i is balloted — 16 staged words per
@@ -2142,9 +2118,8 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
     const u64 nzr = (s.flag.p && s.nz_rows < (u64)s.n) ? s.nz_rows : (u64)s.n;
     {
         ProfScope ps(ctx, "bp_rows_kernel<count>", nzr * s.w * 8 + (u64)s.n + 4 * (u64)ncnt);
-        hipLaunchKernelGGL(bp_rows_kernel<false>, dim3(grid), dim3(256), lds_rows, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws,
-                           nchunks, label_dev, cnt.p, (const u64*)nullptr, (u32*)nullptr, (const uint8_t*)s.flag.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_rows_kernel<false>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks, label_dev, cnt.p,
+                        nullptr, nullptr, s.flag.p));
     }
     {
         ProfScope ps(ctx, "scan (row x chunk counts)", 12 * (u64)ncnt);
@@ -2175,8 +2150,9 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
                        (const u64*)off.p, s.nsrc, nchunks, o->rowptr);
     if (nnz) {
         ProfScope ps(ctx, "bp_rows_kernel<emit>", nzr * s.w * 8 + (u64)s.n + 8 * (u64)ncnt + 4 * nnz);
-        hipLaunchKernelGGL(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), (const u64*)s.x.p, s.n, s.w,
-                           s.ws, nchunks, label_dev, (u32*)nullptr, (const u64*)off.p, o->colidx, (const uint8_t*)s.flag.p);
+        const fgpu_info li = launch(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks,
+                                    label_dev, nullptr, off.p, o->colidx, s.flag.p);
+        if (li != FGPU_OK) { mat_release(o); return li; }
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());

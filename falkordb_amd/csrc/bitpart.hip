@@ -978,6 +978,69 @@ bool bp_xfold_fits(const fgpu_ctx* ctx, u32 ws, int mode, size_t lds_tables) {
     return xp_fold_lds(ws, mode, lds_tables, xp_fold_by_pieces(ctx, ws)) <= (size_t)ctx->opt.lds_limit;
 }
 
+// the partial rows that no chunk of the stream completes: the stream ORs into them, so they start from zero
+static fgpu_info xp_zero_rows(fgpu_ctx* ctx, const BpXPlan* xp, u32 ql, uint4* partial) {
+    if (!xp->nzrows) return FGPU_OK;
+    u32 grid = cdiv(xp->nzrows, 256 / ql);
+    if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
+    return launch(xp_zero_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), xp->zrows, xp->nzrows, ql, partial);
+}
+
+static fgpu_info xp_stream(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, uint4* partial, u64 xrows) {
+    // algorithmic bytes = what the HOP needs (SURVEY.md §8d's pull row): the entries of A' and its row pointers once, every
+    // non-zero row of X once.  The partial rows are NOT in it — they exist only because of the partition, are written here and
+    // read straight back by the fold (counting them made the kernel look 2.5 x closer to the roofline than the hop is)
+    ProfScope ps(ctx, "xp_stream_kernel", 4 * xp->nentries + 4 * ((u64)xp->n + 1) + xrows * 8 * ws);
+    const u32 ql = ws / 2;
+    const size_t lds = (size_t)4 * XP_RUNS * ql * sizeof(uint4);
+    u32 per_cu = (u32)((size_t)ctx->opt.lds_limit / lds);
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    u32 most = 0;
+    for (int k = 0; k < 8; ++k) most = std::max(most, xp->cbase[k + 1] - xp->cbase[k]);
+    u32 grid = (u32)ctx->cus * per_cu;
+    const u32 need = 8 * cdiv(most ? most : 1, 4);
+    if (grid > need) grid = need;
+    grid = (grid + 7) & ~7u;
+    const bool wide = (u64)xp->n * ws * 8 > (1ull << 32) || (u64)t->ncols * ws * 8 > (1ull << 32);
+    return pick<1, 2, 4, 8>((int)ql, [&](auto q) { return pick(wide, [&](auto w) { return pick<1, 2, 3, 0>(ctx->opt.expand_nt & 3, [&](auto nt) {
+        return launch(xp_stream_kernel<decltype(q)::value, decltype(w)::value, decltype(nt)::value>, dim3(grid), dim3(256), lds, ctx->stream(),
+                      xp->pcol, xp->pstart_dev, xp->cstart, xp->crun0, xp->cshared, (const uint4*)x, partial);
+    }); }); });
+}
+
+static fgpu_info xp_fold(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,
+                         u64* side, size_t lds_tables, const uint4* partial) {
+    // (no algorithmic bytes of its own: everything it reads is the stream kernel's intermediate — bench.py quotes the hop,
+    // stream + fold, against the stream kernel's bytes)
+    // (the scope names the STEP, whichever of the two fold kernels runs it: bench.py quotes stream + fold under this name)
+    ProfScope ps(ctx, "xp_fold_kernel", 0);
+    // (4 or 8 wavefronts sharing one copy of the checksum tables, 16 or 32 resident per CU: the same 214 / 148 us with and
+    // without the checksum at RMAT-22 — the kernel is not short of wavefronts)
+    const u32 fthreads = XP_FOLD_THREADS;
+    u32 grid = cdiv(xp->ng, fthreads / 64);
+    if (grid > (u32)ctx->cus * (2048u / fthreads)) grid = ctx->cus * (2048u / fthreads);
+    // (the count-hop planner takes the plain pull when this does not fit: bp_xfold_fits)
+    const int pieces = xp_fold_by_pieces(ctx, ws);
+    // (a list entry tags a slot of X with bit 31: the plan's own limits — nnz and columns below 2^31 — keep both kinds below it)
+    FGPU_REQUIRE(!pieces || ((u64)xp->nprows < XP_PIECE_X && t->ncols < XP_PIECE_X), FGPU_INVALID,
+                 "partitioned pull: the piece fold needs partial rows and columns below 2^31");
+    (pieces ? ctx->xp_piece_folds : ctx->xp_slot_folds).fetch_add(1, std::memory_order_relaxed);
+    const size_t lds = xp_fold_lds(ws, mode, lds_tables, pieces);
+    FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID, "partitioned pull: the fold needs %zu B of LDS", lds);
+    return pick<1, 2, 4, 8>((int)(ws / 2), [&](auto q) { return pick<2, 1>(mode, [&](auto md) { return pick((ctx->opt.expand_nt & 4) != 0, [&](auto nt) {
+        return pick(xp->dense != 0, [&](auto dense) { return pick(xp->direct != 0, [&](auto direct) {
+            constexpr int Q = decltype(q)::value, M = decltype(md)::value;
+            constexpr bool N = decltype(nt)::value, D = decltype(direct)::value, G = decltype(dense)::value;
+            if (pieces)
+                return launch(xp_fold_pieces_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne, xp->pbase, xp->ng,
+                              partial, fin, (uint4*)side, xp->de, xp->dbase, xp->dcol, (const uint4*)x, xp->gvtx);
+            return launch(xp_fold_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne, xp->pbase, xp->ng,
+                          partial, fin, (uint4*)side, xp->nprows, xp->de, xp->dbase, xp->dcol, (const uint4*)x, xp->gvtx);
+        }); });
+    }); }); });
+}
+
 fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,
                          u64* side, size_t lds_tables, u64 xrows) {
     FGPU_REQUIRE(xp && xp->usable && ws >= 2 && ws <= 16 && (ws & (ws - 1)) == 0, FGPU_INVALID, "partitioned pull: bad plan / row width");
@@ -985,108 +1048,11 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
     FGPU_REQUIRE(!xp->dense == !xp->gvtx, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
     ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
     ctx->xp_last_groups.store(xp->ng, std::memory_order_relaxed);
-    const u32 ql = ws / 2;
-    hipStream_t st = ctx->stream();
     DevBuf<uint4> partial;
-    FGPU_TRY(partial.alloc(ctx, ((size_t)xp->nprows + 1) * ql));
-    if (xp->nzrows) {
-        u32 zg = cdiv(xp->nzrows, 256 / ql);
-        if (zg > (u32)ctx->cus * 4) zg = ctx->cus * 4;
-        hipLaunchKernelGGL(xp_zero_rows_kernel, dim3(zg), dim3(256), 0, st, (const u32*)xp->zrows, xp->nzrows, ql, partial.p);
-        FGPU_HIP(hipGetLastError());
-    }
-    {
-        // algorithmic bytes = what the HOP needs (SURVEY.md §8d's pull row): the entries of A' and its row pointers once, every
-        // non-zero row of X once.  The partial rows are NOT in it — they exist only because of the partition, are written here and
-        // read straight back by the fold (counting them made the kernel look 2.5 x closer to the roofline than the hop is)
-        ProfScope ps(ctx, "xp_stream_kernel", 4 * xp->nentries + 4 * ((u64)xp->n + 1) + xrows * 8 * ws);
-        const size_t lds = (size_t)4 * XP_RUNS * ql * sizeof(uint4);
-        u32 per_cu = (u32)((size_t)ctx->opt.lds_limit / lds);
-        if (per_cu > 8) per_cu = 8;
-        if (per_cu < 1) per_cu = 1;
-        u32 most = 0;
-        for (int k = 0; k < 8; ++k) most = std::max(most, xp->cbase[k + 1] - xp->cbase[k]);
-        u32 grid = (u32)ctx->cus * per_cu;
-        const u32 need = 8 * cdiv(most ? most : 1, 4);
-        if (grid > need) grid = need;
-        grid = (grid + 7) & ~7u;
-        const bool wide = (u64)xp->n * ws * 8 > (1ull << 32) || (u64)t->ncols * ws * 8 > (1ull << 32);
-#define XP_PULL3(Q, W, N) hipLaunchKernelGGL((xp_stream_kernel<Q, W, N>), dim3(grid), dim3(256), lds, st, (const u32*)xp->pcol,  \
-                                          (const u32*)xp->pstart_dev, (const u32*)xp->cstart, (const u32*)xp->crun0,           \
-                                          (const uint8_t*)xp->cshared, (const uint4*)x, partial.p)
-#define XP_PULL2(Q, W) do { switch (ctx->opt.expand_nt & 3) { case 1: XP_PULL3(Q, W, 1); break; case 2: XP_PULL3(Q, W, 2); break;  \
-                                                              case 3: XP_PULL3(Q, W, 3); break; default: XP_PULL3(Q, W, 0); break; } } while (0)
-#define XP_PULL(Q) do { if (wide) XP_PULL2(Q, true); else XP_PULL2(Q, false); } while (0)
-        switch (ql) {
-            case 1: XP_PULL(1); break;
-            case 2: XP_PULL(2); break;
-            case 4: XP_PULL(4); break;
-            default: XP_PULL(8); break;
-        }
-#undef XP_PULL3
-#undef XP_PULL2
-#undef XP_PULL
-        FGPU_HIP(hipGetLastError());
-    }
-    {
-        // (no algorithmic bytes of its own: everything it reads is the stream kernel's intermediate — bench.py quotes the hop,
-        // stream + fold, against the stream kernel's bytes)
-        // (the scope names the STEP, whichever of the two fold kernels runs it: bench.py quotes stream + fold under this name)
-        ProfScope ps(ctx, "xp_fold_kernel", 0);
-        // (4 or 8 wavefronts sharing one copy of the checksum tables, 16 or 32 resident per CU: the same 214 / 148 us with and
-        // without the checksum at RMAT-22 — the kernel is not short of wavefronts)
-        const u32 fthreads = XP_FOLD_THREADS;
-        u32 grid = cdiv(xp->ng, fthreads / 64);
-        if (grid > (u32)ctx->cus * (2048u / fthreads)) grid = ctx->cus * (2048u / fthreads);
-        // (the count-hop planner takes the plain pull when this does not fit: bp_xfold_fits)
-        const int pieces = xp_fold_by_pieces(ctx, ws);
-        // (a list entry tags a slot of X with bit 31: the plan's own limits — nnz and columns below 2^31 — keep both kinds below it)
-        FGPU_REQUIRE(!pieces || ((u64)xp->nprows < XP_PIECE_X && t->ncols < XP_PIECE_X), FGPU_INVALID,
-                     "partitioned pull: the piece fold needs partial rows and columns below 2^31");
-        (pieces ? ctx->xp_piece_folds : ctx->xp_slot_folds).fetch_add(1, std::memory_order_relaxed);
-        const size_t lds = xp_fold_lds(ws, mode, lds_tables, pieces);
-        FGPU_REQUIRE(lds <= (size_t)ctx->opt.lds_limit, FGPU_INVALID, "partitioned pull: the fold needs %zu B of LDS", lds);
-#define XP_FOLD4(Q, M, N, D, G)                                                                                                  \
-        do {                                                                                                                     \
-            if (lds > 48 * 1024)                                                                                                 \
-                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_kernel<Q, M, N, D, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((xp_fold_kernel<Q, M, N, D, G>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase, xp->ng,  \
-                               (const uint4*)partial.p, fin, (uint4*)side, xp->nprows, (const u64*)xp->de, (const u32*)xp->dbase,                 \
-                               (const u32*)xp->dcol, (const uint4*)x, (const u32*)xp->gvtx);                                                       \
-        } while (0)
-#define XP_PIECES4(Q, M, N, D, G)                                                                                                \
-        do {                                                                                                                     \
-            if (lds > 48 * 1024)                                                                                                 \
-                FGPU_HIP(hipFuncSetAttribute((const void*)xp_fold_pieces_kernel<Q, M, N, D, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((xp_fold_pieces_kernel<Q, M, N, D, G>), dim3(grid), dim3(fthreads), lds, st, (const u64*)xp->ne, (const u32*)xp->pbase,  \
-                               xp->ng, (const uint4*)partial.p, fin, (uint4*)side, (const u64*)xp->de, (const u32*)xp->dbase,                  \
-                               (const u32*)xp->dcol, (const uint4*)x, (const u32*)xp->gvtx);                                                    \
-        } while (0)
-#define XP_FOLD35(Q, M, N, G)                                                                                                    \
-        do {                                                                                                                     \
-            if (pieces) { if (xp->direct) XP_PIECES4(Q, M, N, true, G); else XP_PIECES4(Q, M, N, false, G); }                    \
-            else if (xp->direct) XP_FOLD4(Q, M, N, true, G);                                                                     \
-            else XP_FOLD4(Q, M, N, false, G);                                                                                    \
-        } while (0)
-#define XP_FOLD3(Q, M, N) do { if (xp->dense) XP_FOLD35(Q, M, N, true); else XP_FOLD35(Q, M, N, false); } while (0)
-#define XP_FOLD2(Q, M) do { if (ctx->opt.expand_nt & 4) XP_FOLD3(Q, M, true); else XP_FOLD3(Q, M, false); } while (0)
-#define XP_FOLD(Q) do { if (mode == 2) XP_FOLD2(Q, 2); else XP_FOLD2(Q, 1); } while (0)
-        switch (ql) {
-            case 1: XP_FOLD(1); break;
-            case 2: XP_FOLD(2); break;
-            case 4: XP_FOLD(4); break;
-            default: XP_FOLD(8); break;
-        }
-#undef XP_FOLD
-#undef XP_FOLD2
-#undef XP_FOLD3
-#undef XP_FOLD35
-#undef XP_FOLD4
-#undef XP_PIECES4
-        FGPU_HIP(hipGetLastError());
-    }
-    (void)t;
-    return FGPU_OK;
+    FGPU_TRY(partial.alloc(ctx, ((size_t)xp->nprows + 1) * (ws / 2)));
+    FGPU_TRY(xp_zero_rows(ctx, xp, ws / 2, partial.p));
+    FGPU_TRY(xp_stream(ctx, xp, t, x, ws, partial.p, xrows));
+    return xp_fold(ctx, xp, t, x, ws, mode, fin, side, lds_tables, partial.p);
 }
 
 }  // namespace fgpu
