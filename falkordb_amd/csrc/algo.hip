@@ -23,8 +23,7 @@ __global__ __launch_bounds__(256) void forest_jump_kernel(u32* parent, u32 n, u3
 
 // (grid-stride: 1 K workgroups of 256 fill the chip)
 fgpu_info forest_init(fgpu_ctx* ctx, u32* parent, u32 n) {
-    hipLaunchKernelGGL(forest_init_kernel, dim3(capped_grid(ctx, n, 256, 4)), dim3(256), 0, ctx->stream(), parent, n);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(forest_init_kernel, dim3(capped_grid(ctx, n, 256, 4)), dim3(256), 0, ctx->stream(), parent, n));
     return FGPU_OK;
 }
 
@@ -34,8 +33,7 @@ fgpu_info forest_compress(fgpu_ctx* ctx, const char* who, u32* parent, u32 n, u3
     const u32 grid = capped_grid(ctx, n, 256, 4);
     for (u32 k = 0; k < FOREST_MAX_JUMPS;) {
         for (u32 b = 0; b < BATCH && k < FOREST_MAX_JUMPS; ++b, ++k)
-            hipLaunchKernelGGL(forest_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent, n, flags, k);
-        FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(forest_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream(), parent, n, flags, k));
         u32 f = 0;
         FGPU_TRY(read_u32(ctx, flags + k - 1, &f));
         if (!f) return FGPU_OK;

@@ -206,9 +206,9 @@ fgpu_info csr_edge_list(fgpu_ctx* ctx, const char* who, const char* lost, fgpu_m
     FGPU_REQUIRE(f->nnz == k, FGPU_DEVICE, "%s: %s", who, lost);
     DevBuf<u64> trip;
     FGPU_TRY(trip.alloc(ctx, 3 * (size_t)k));
-    hipLaunchKernelGGL((csr_edge_list_kernel<V>), dim3(capped_grid(ctx, k, 256, per_cu)), dim3(256), 0, ctx->stream(), view_of(f),
-                       (u32)k, value, trip.p, trip.p + k, trip.p + 2 * k);
-    FGPU_REQUIRE(hipGetLastError() == hipSuccess, FGPU_DEVICE, "%s: launch failed", who);
+    FGPU_REQUIRE(launch(csr_edge_list_kernel<V>, dim3(capped_grid(ctx, k, 256, per_cu)), dim3(256), 0, ctx->stream(), view_of(f), (u32)k,
+                        value, trip.p, trip.p + k, trip.p + 2 * k) == FGPU_OK,
+                 FGPU_DEVICE, "%s: launch failed", who);
     ResultBuf out[3];
     for (int j = 0; j < 3; ++j)
         FGPU_REQUIRE(out[j].alloc(ctx, k * sizeof(u64)), FGPU_OOM, "%s: host allocation failed", who);

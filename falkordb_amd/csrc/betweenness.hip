@@ -429,15 +429,13 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
             FGPU_HIP(hipMemsetAsync(sigma.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
             FGPU_HIP(hipMemsetAsync(delta.p, 0, (size_t)n * B * sizeof(double), ctx->stream()));
             FGPU_HIP(hipMemsetAsync(depth.p, 0xFF, (size_t)n * B * sizeof(u32), ctx->stream()));   // unreached
-            hipLaunchKernelGGL(bc_seed_kernel, dim3(1), dim3(64), 0, ctx->stream(), s, (const u64*)src.p + first, nb);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(bc_seed_kernel, dim3(1), dim3(64), 0, ctx->stream(), s, (const u64*)src.p + first, nb));
             // forward: settle the frontier of depth d1, read its counters, expand it to depth d1 + 1
             u32 d1 = 0;
             for (;;) {
                 FGPU_HIP(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), ctx->stream()));
-                hipLaunchKernelGGL(bc_settle_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, (const u32*)A->rowptr,
-                                   At ? (const u32*)At->rowptr : nullptr, a, n, d1, cnt.p);
-                FGPU_HIP(hipGetLastError());
+                FGPU_TRY(launch(bc_settle_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, (const u32*)A->rowptr,
+                                At ? (const u32*)At->rowptr : nullptr, a, n, d1, cnt.p));
                 std::swap(s.F, s.N);   // the settled frontier is read next; the cleared one collects the next depth
                 u32 w[6];
                 FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 6, w));
@@ -445,21 +443,17 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
                 if (nf == 0) break;
                 const bool pull = dir == 2 || (dir == 0 && At && mu < BC_PULL_RATIO * mf);
                 if (pull) {
-                    hipLaunchKernelGGL(bc_pull_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, vat, a, n);
-                    FGPU_HIP(hipGetLastError());
+                    FGPU_TRY(launch(bc_pull_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, vat, a, n));
                     if (hgAt) {
-                        hipLaunchKernelGGL(bc_pull_hub_kernel, dim3(hgAt), dim3(256), 0, ctx->stream(), s,
-                                           (const u32*)At->hub_chunks, At->n_hub_chunks, (const u32*)At->colidx, a);
-                        FGPU_HIP(hipGetLastError());
+                        FGPU_TRY(launch(bc_pull_hub_kernel, dim3(hgAt), dim3(256), 0, ctx->stream(), s,
+                                        (const u32*)At->hub_chunks, At->n_hub_chunks, (const u32*)At->colidx, a));
                     }
                     st[2] += mu;
                 } else {
-                    hipLaunchKernelGGL(bc_push_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, a, n);
-                    FGPU_HIP(hipGetLastError());
+                    FGPU_TRY(launch(bc_push_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, a, n));
                     if (hgA) {
-                        hipLaunchKernelGGL(bc_push_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s,
-                                           (const u32*)A->hub_chunks, A->n_hub_chunks, (const u32*)A->colidx, a);
-                        FGPU_HIP(hipGetLastError());
+                        FGPU_TRY(launch(bc_push_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s,
+                                        (const u32*)A->hub_chunks, A->n_hub_chunks, (const u32*)A->colidx, a));
                     }
                     st[2] += mf;
                 }
@@ -471,19 +465,15 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
             ++st[0];
             if (deepest < 2) continue;     // no vertex between a source and a deeper one: every delta is 0
             for (u32 d = deepest - 1; d >= 1; --d) {
-                hipLaunchKernelGGL(bc_back_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, n, d, cnt.p + 3);
-                FGPU_HIP(hipGetLastError());
+                FGPU_TRY(launch(bc_back_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, n, d, cnt.p + 3));
                 if (hgA) {
-                    hipLaunchKernelGGL(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
-                                       A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3);
-                    FGPU_HIP(hipGetLastError());
-                    hipLaunchKernelGGL(bc_back_hub_finish_kernel, dim3(capped_grid(ctx, (u64)A->n_hub_chunks * G, 256, 16)), dim3(256), 0,
-                                       ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p);
-                    FGPU_HIP(hipGetLastError());
+                    FGPU_TRY(launch(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
+                                    A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3));
+                    FGPU_TRY(launch(bc_back_hub_finish_kernel, dim3(capped_grid(ctx, (u64)A->n_hub_chunks * G, 256, 16)), dim3(256), 0,
+                                    ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p));
                 }
             }
-            hipLaunchKernelGGL(bc_reduce_kernel, dim3(capped_grid(ctx, n, 256, 16)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(bc_reduce_kernel, dim3(capped_grid(ctx, n, 256, 16)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p));
         }
         u64 back = 0;
         FGPU_TRY(read_u64(ctx, (const u64*)(cnt.p + 3), &back));

@@ -129,6 +129,12 @@ struct BfsCtrl {
 constexpr u32 PB_BINS = 256;
 constexpr u32 PB_C = 8192;          // edges per chunk: 8 per thread of a 1024-thread workgroup
 constexpr u32 PB_T = 1024;
+// dynamic LDS of the count and scatter kernels (66.6 / 69.6 KB) and the most an apply window takes (2^19 vertices): beyond the
+// 48 KiB a kernel gets unasked, so plan_create raises the limits — to these constants: the limit belongs to the function, a
+// plan-sized value from a small plan would lower it under a large one — and pb_launches launches with launch_raised()
+constexpr size_t PB_LDS_COUNT = ((size_t)2 * (PB_C + 2) + PB_BINS) * sizeof(u32);
+constexpr size_t PB_LDS_SCAT = ((size_t)2 * (PB_C + 2) + 4 * PB_BINS) * sizeof(u32);
+constexpr size_t PB_LDS_APPLY_MAX = 64 * 1024;
 struct PbPart { u64 count, mf, scanned; u32 hub; u32 pad[9]; };   // a window's / workgroup's share of the level statistics (one 64-byte line)
 struct BfsPb {
     u32 nlist, nchunks, total, shift;   // rows of the compacted frontier, chunks, edges of the level; log2(vertices per window)
@@ -2429,18 +2435,16 @@ static fgpu_info ensure_pull_order(fgpu_ctx* ctx, const fgpu_mat* At, const fgpu
     if (i == FGPU_OK) i = cnt.alloc(ctx, (size_t)nrows + 1);
     if (i == FGPU_OK) {
         const u32 grid = ctx->cus * 16;
-        hipLaunchKernelGGL(pull_key_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)At->colidx, nnz,
-                           (const u32*)A->rowptr, (u32)A->nrows, idbits, keys);
-        hipLaunchKernelGGL(pull_seg_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)At->rowptr, nrows, off.p, dirty.p);
-        i = segsort_unique(ctx, keys, off.p, nrows, 0xFFFFFFFFu, cnt.p, dirty.p);
-        if (i == FGPU_OK) {
-            hipLaunchKernelGGL(pull_unkey_kernel, dim3(grid), dim3(256), 0, ctx->stream(), keys, nnz,
-                               idbits >= 32 ? 0xFFFFFFFFu : ((1u << idbits) - 1u));
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());
-            if (e != hipSuccess) { set_error("pull order build failed: %s", hipGetErrorString(e)); i = FGPU_DEVICE; }
-        }
+        i = launch(pull_key_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)At->colidx, nnz, (const u32*)A->rowptr,
+                   (u32)A->nrows, idbits, keys);
+        if (i == FGPU_OK)
+            i = launch(pull_seg_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, nrows,
+                       off.p, dirty.p);
+        if (i == FGPU_OK) i = segsort_unique(ctx, keys, off.p, nrows, 0xFFFFFFFFu, cnt.p, dirty.p);
+        if (i == FGPU_OK)
+            i = launch(pull_unkey_kernel, dim3(grid), dim3(256), 0, ctx->stream(), keys, nnz,
+                       idbits >= 32 ? 0xFFFFFFFFu : ((1u << idbits) - 1u));
+        if (i == FGPU_OK) i = fgpu_sync(ctx);
     }
     if (i != FGPU_OK) { ctx->dev_free(keys); return i; }
     At->pull_col = keys;   // built and synchronised above
@@ -2617,6 +2621,15 @@ fgpu_info fgpu_bfs_plan_create_slab(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fg
     return plan_create(ctx, out, A_slab, At_slab, rank, nranks, splits);
 }
 
+// a plan with the blocked push raises its five kernels' LDS limits (PB_LDS_*), on its own context's device
+static fgpu_info pb_raise_limits() {
+    FGPU_TRY(raise_lds(bfs_pb_count_kernel, PB_LDS_COUNT));
+    FGPU_TRY(raise_lds(bfs_pb_scatter_kernel<false>, PB_LDS_SCAT));
+    FGPU_TRY(raise_lds(bfs_pb_scatter_kernel<true>, PB_LDS_SCAT));
+    FGPU_TRY(raise_lds(bfs_pb_apply_kernel<false>, PB_LDS_APPLY_MAX));
+    return raise_lds(bfs_pb_apply_kernel<true>, PB_LDS_APPLY_MAX);
+}
+
 static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat* A, const fgpu_mat* At, int rank,
                              int nranks, const uint64_t* splits) {
     FGPU_REQUIRE(ctx && out && A, FGPU_NULL_POINTER, "fgpu_bfs_plan_create: NULL argument");
@@ -2680,9 +2693,8 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
         if (At) {
             p->pull_colidx = (At->pull_col && ctx->opt.bfs_hub_first) ? At->pull_col : At->colidx;
             if ((i = ctx->dev_alloc((void**)&p->pull_head, (size_t)p->nw * 64 * sizeof(headv))) != FGPU_OK) break;
-            hipLaunchKernelGGL(pull_head_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr,
-                               p->pull_colidx, p->n, p->nw * 64, p->pull_head);
-            if (hipGetLastError() != hipSuccess) { set_error("bfs plan: head build failed"); i = FGPU_DEVICE; break; }
+            if ((i = launch(pull_head_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->pull_colidx,
+                            p->n, p->nw * 64, p->pull_head)) != FGPU_OK) break;
         }
     } while (0);
     if (i == FGPU_OK) {
@@ -2708,10 +2720,8 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
             DevBuf<u32> cnt;
             i = cnt.alloc(ctx, 1);
             if (i == FGPU_OK && hipMemsetAsync(cnt.p, 0, sizeof(u32), ctx->stream()) != hipSuccess) i = FGPU_DEVICE;
-            if (i == FGPU_OK) {
-                hipLaunchKernelGGL(bfs_count_alive_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, cnt.p);
-                i = read_u32(ctx, cnt.p, &p->n_alive);
-            }
+            if (i == FGPU_OK) i = launch(bfs_count_alive_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, cnt.p);
+            if (i == FGPU_OK) i = read_u32(ctx, cnt.p, &p->n_alive);
         }
     }
     // propagation blocking of heavy push levels: plans of >= 2^24 vertices (option bfs_pb; 2 = any).  With alpha as it was tuned for
@@ -2741,10 +2751,8 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
         }
         if (pi == FGPU_OK && At) {
             pi = ctx->dev_alloc((void**)&p->alive, (size_t)p->nw * sizeof(u64));
-            if (pi == FGPU_OK) {
-                hipLaunchKernelGGL(bfs_alive_bits_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, p->nw, p->alive);
-                if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream()) != hipSuccess) pi = FGPU_DEVICE;
-            }
+            if (pi == FGPU_OK) pi = launch(bfs_alive_bits_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, p->nw, p->alive);
+            if (pi == FGPU_OK) pi = fgpu_sync(ctx);
         }
         if (pi != FGPU_OK) {
             ctx->dev_free(p->alive); p->alive = nullptr;
@@ -2754,6 +2762,7 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
             set_error("%s", "");
         }
     }
+    if (i == FGPU_OK && p->pb) i = pb_raise_limits();
     if (i != FGPU_OK) { fgpu_bfs_plan_free(p); return i; }
     memset(p->h_ctrl, 0, sizeof(BfsCtrl));
     {
@@ -2849,9 +2858,8 @@ fgpu_info fgpu_bfs_part_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level)
     FGPU_HIP(hipMemsetAsync(p->ctrl, 0, sizeof(BfsCtrl), ctx->stream()));
     i32 ml = max_level < 0 ? -1 : (max_level > 0x7FFFFFFF ? 0x7FFFFFFF : (i32)max_level);
     BfsArgs a = make_args(p);
-    hipLaunchKernelGGL(bfs_init_kernel, dim3(1), dim3(1), 0, ctx->stream(), a, (u32)src, ml, p->At ? 1u : 0u,
-                       (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull, 0ull);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bfs_init_kernel, dim3(1), dim3(1), 0, ctx->stream(), a, (u32)src, ml, p->At ? 1u : 0u,
+                    (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull, 0ull));
     return FGPU_OK;
 }
 
@@ -2912,20 +2920,17 @@ fgpu_info fgpu_bfs_slab_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level,
     BfsArgs a = slab_args(p);
     u64* z0 = p->inplace ? p->slab_ring[1] + (p->lo >> 6) : p->slab_send[0];
     u64* z1 = p->inplace ? p->slab_ring[2] + (p->lo >> 6) : p->slab_send[1];
-    hipLaunchKernelGGL(bfs_slab_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, z0, z1, (u32)src, ml, p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha,
-                       p->At ? p->At->nnz : 0ull);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bfs_slab_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, z0, z1, (u32)src, ml, p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha,
+                    p->At ? p->At->nnz : 0ull));
     return FGPU_OK;
 }
 
 fgpu_info fgpu_bfs_slab_level(fgpu_bfs_plan* p, int* send_index) {
     FGPU_REQUIRE(p, FGPU_NULL_POINTER, "fgpu_bfs_slab_level: NULL plan");
     BfsArgs a = slab_args(p);
-    if (p->want_parent)
-        hipLaunchKernelGGL((bfs_fused_kernel<true, 0>), dim3(p->fgrid), dim3(256), 0, p->ctx->stream(), a);
-    else
-        hipLaunchKernelGGL((bfs_fused_kernel<false, 0>), dim3(p->fgrid), dim3(256), 0, p->ctx->stream(), a);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(pick(p->want_parent, [&](auto par) {
+        return launch(bfs_fused_kernel<decltype(par)::value, 0>, dim3(p->fgrid), dim3(256), 0, p->ctx->stream(), a);
+    }));
     if (send_index) *send_index = (int)(p->launch & 1);
     p->launch += 1;
     return FGPU_OK;
@@ -3008,9 +3013,8 @@ static fgpu_info dist_setup(fgpu_bfs_plan* const* P, int np) {
         for (int k = 1; k < np; ++k) {
             FGPU_HIP(hipStreamSynchronize(P[k]->ctx->stream()));
             FGPU_HIP(hipMemcpyAsync(tmp.p, P[k]->dist_deg, (size_t)P[0]->n * sizeof(u32), hipMemcpyDefault, c0->stream()));
-            hipLaunchKernelGGL(add_u32_kernel, dim3(c0->cus * 8), dim3(256), 0, c0->stream(), P[0]->dist_deg,
-                               (const u32*)tmp.p, (u64)P[0]->n);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(add_u32_kernel, dim3(c0->cus * 8), dim3(256), 0, c0->stream(), P[0]->dist_deg,
+                            (const u32*)tmp.p, (u64)P[0]->n));
         }
         FGPU_HIP(hipStreamSynchronize(c0->stream()));
         for (int k = 1; k < np; ++k) {
@@ -3109,8 +3113,7 @@ fgpu_info fgpu_bfs_dist_run(fgpu_bfs_plan* const* plans, int nplans, uint64_t sr
             if (timed) FGPU_TRY(dist_event(plans[k], 3 * nlev));
             FGPU_TRY(fgpu_bfs_slab_level(plans[k], &idx[k]));
             if (plans[k]->ctx->opt.dist_test_delay_us > 0) {
-                hipLaunchKernelGGL(dist_test_delay_kernel, dim3(1), dim3(1), 0, plans[k]->ctx->stream(), (u32)plans[k]->ctx->opt.dist_test_delay_us);
-                FGPU_HIP(hipGetLastError());
+                FGPU_TRY(launch(dist_test_delay_kernel, dim3(1), dim3(1), 0, plans[k]->ctx->stream(), (u32)plans[k]->ctx->opt.dist_test_delay_us));
             }
             if (timed) FGPU_TRY(dist_event(plans[k], 3 * nlev + 1));
         }
@@ -3135,9 +3138,8 @@ fgpu_info fgpu_bfs_dist_run(fgpu_bfs_plan* const* plans, int nplans, uint64_t sr
                     for (int d = 0; d < nplans; ++d) pd.p[d] = plans[d]->slab_glob[plans[d]->launch & 1] + offs[s];   // what the NEXT launch reads
                     u32 gx = (u32)((cnts[s] / 2 + 255) / 256);
                     if (gx > 64) gx = 64;
-                    hipLaunchKernelGGL(dist_scatter_kernel, dim3(gx ? gx : 1, nplans), dim3(256), 0, plans[s]->ctx->stream(),
-                                       (const u64*)plans[s]->dist_send[idx[s]], cnts[s], pd);
-                    FGPU_HIP(hipGetLastError());
+                    FGPU_TRY(launch(dist_scatter_kernel, dim3(gx ? gx : 1, nplans), dim3(256), 0, plans[s]->ctx->stream(),
+                                    (const u64*)plans[s]->dist_send[idx[s]], cnts[s], pd));
                 }
                 FGPU_HIP(hipEventRecord(copied[s], plans[s]->ctx->stream()));
             }
@@ -3238,10 +3240,9 @@ static fgpu_info fused_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level) 
     p->fused_idx = 0;
     p->levels_masked = false;
     p->mask_visited = p->bm_block + 3 * (size_t)p->nw;
-    hipLaunchKernelGGL(bfs_fused_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, (u32)src, ml,
-                       p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull,
-                       (u64)(ctx->opt.bfs_pb_min_edges > 0 ? ctx->opt.bfs_pb_min_edges : 1), p->pb ? p->pb_mask : 0u, ctx->opt.bfs_alive_rule ? p->n_alive : 0u, p->pb ? p->cp_mask : 0u);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bfs_fused_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, (u32)src, ml,
+                    p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull,
+                    (u64)(ctx->opt.bfs_pb_min_edges > 0 ? ctx->opt.bfs_pb_min_edges : 1), p->pb ? p->pb_mask : 0u, ctx->opt.bfs_alive_rule ? p->n_alive : 0u, p->pb ? p->cp_mask : 0u));
     return FGPU_OK;
 }
 
@@ -3280,50 +3281,30 @@ static fgpu_info pb_launches(fgpu_bfs_plan* p, bool list_only = false) {
     else { g.At.rowptr = nullptr; g.At.colidx = nullptr; g.At.hrows = nullptr; g.At.nvec = 0; g.At.nrows = 0; }
     g.head = p->pull_head;
     if (list_only) {   // the list kernel for a sparse frontier -> queue or a candidate set, and the pull of the latter
-        hipLaunchKernelGGL(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g);
-        if (p->alive) {
-            if (p->want_parent) hipLaunchKernelGGL(bfs_lp_kernel<true>, dim3(PB_BINS), dim3(PB_T), 0, st, g);
-            else hipLaunchKernelGGL(bfs_lp_kernel<false>, dim3(PB_BINS), dim3(PB_T), 0, st, g);
-        }
-        FGPU_HIP(hipGetLastError());
-        return FGPU_OK;
+        FGPU_TRY(launch(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g));
+        if (!p->alive) return FGPU_OK;
+        return pick(p->want_parent, [&](auto par) {
+            return launch(bfs_lp_kernel<decltype(par)::value>, dim3(PB_BINS), dim3(PB_T), 0, st, g);
+        });
     }
-    const size_t lds_count = ((size_t)2 * (PB_C + 2) + PB_BINS) * sizeof(u32);
-    const size_t lds_scat = ((size_t)2 * (PB_C + 2) + 4 * PB_BINS) * sizeof(u32);
     u32 shift = 6;
     while (((u64)PB_BINS << shift) < (u64)p->nw * 64) ++shift;
-    const size_t lds_apply = ((size_t)1 << shift) / 8;
-    static std::once_flag once;
-    std::call_once(once, [&]() {
-        (void)hipFuncSetAttribute((const void*)bfs_pb_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count);
-        (void)hipFuncSetAttribute((const void*)bfs_pb_scatter_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scat);
-        (void)hipFuncSetAttribute((const void*)bfs_pb_scatter_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scat);
-        (void)hipFuncSetAttribute((const void*)bfs_pb_apply_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)bfs_pb_apply_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    });
+    const size_t lds_apply = ((size_t)1 << shift) / 8;   // (<= PB_LDS_APPLY_MAX: plan_create admits windows of at most 2^19 vertices)
     const u32 cgrid = (u32)ctx->cus * 2;
-    hipLaunchKernelGGL(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g);
-    hipLaunchKernelGGL(bfs_pb_prefix_kernel, dim3(PB_LMAX / PB_T / PB_PPT), dim3(PB_T), 0, st, g);
-    hipLaunchKernelGGL(bfs_pb_count_kernel, dim3(cgrid), dim3(PB_T), lds_count, st, g);
-    if (p->want_parent) {
-        hipLaunchKernelGGL(bfs_pb_scatter_kernel<true>, dim3(cgrid), dim3(PB_T), lds_scat, st, g);
-        hipLaunchKernelGGL(bfs_pb_apply_kernel<true>, dim3(PB_BINS), dim3(PB_T), lds_apply, st, g);
-    } else {
-        hipLaunchKernelGGL(bfs_pb_scatter_kernel<false>, dim3(cgrid), dim3(PB_T), lds_scat, st, g);
-        hipLaunchKernelGGL(bfs_pb_apply_kernel<false>, dim3(PB_BINS), dim3(PB_T), lds_apply, st, g);
-    }
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    FGPU_TRY(launch(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g));
+    FGPU_TRY(launch(bfs_pb_prefix_kernel, dim3(PB_LMAX / PB_T / PB_PPT), dim3(PB_T), 0, st, g));
+    FGPU_TRY(launch_raised(bfs_pb_count_kernel, dim3(cgrid), dim3(PB_T), PB_LDS_COUNT, st, g));
+    return pick(p->want_parent, [&](auto par) {
+        FGPU_TRY(launch_raised(bfs_pb_scatter_kernel<decltype(par)::value>, dim3(cgrid), dim3(PB_T), PB_LDS_SCAT, st, g));
+        return launch_raised(bfs_pb_apply_kernel<decltype(par)::value>, dim3(PB_BINS), dim3(PB_T), lds_apply, st, g);
+    });
 }
 
 static fgpu_info tiny_levels(fgpu_bfs_plan* p) {
     BfsArgs a = make_args(p, true);
-    if (p->want_parent)
-        hipLaunchKernelGGL(bfs_tiny_kernel<true>, dim3(1), dim3(256), 0, p->ctx->stream(), a);
-    else
-        hipLaunchKernelGGL(bfs_tiny_kernel<false>, dim3(1), dim3(256), 0, p->ctx->stream(), a);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    return pick(p->want_parent, [&](auto par) {
+        return launch(bfs_tiny_kernel<decltype(par)::value>, dim3(1), dim3(256), 0, p->ctx->stream(), a);
+    });
 }
 
 static fgpu_info fused_level(fgpu_bfs_plan* p) {
@@ -3331,12 +3312,9 @@ static fgpu_info fused_level(fgpu_bfs_plan* p) {
     if (p->pb && p->fused_idx < 32 && ((p->pb_mask >> p->fused_idx) & 1u)) FGPU_TRY(pb_launches(p));
     else if (p->pb && p->fused_idx < 32 && ((p->cp_mask >> p->fused_idx) & 1u)) FGPU_TRY(pb_launches(p, true));
     const u32 grid = p->fgrid | (p->fused_idx++ & 1u);   // launch k carries its parity in the grid size (see the head of bfs_fused_kernel)
-    if (p->want_parent)
-        hipLaunchKernelGGL((bfs_fused_kernel<true, 0>), dim3(grid), dim3(256), 0, p->ctx->stream(), a);
-    else
-        hipLaunchKernelGGL((bfs_fused_kernel<false, 0>), dim3(grid), dim3(256), 0, p->ctx->stream(), a);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    return pick(p->want_parent, [&](auto par) {
+        return launch(bfs_fused_kernel<decltype(par)::value, 0>, dim3(grid), dim3(256), 0, p->ctx->stream(), a);
+    });
 }
 
 static fgpu_info timed_begin(fgpu_bfs_plan* p) {
@@ -3347,12 +3325,9 @@ static fgpu_info timed_begin(fgpu_bfs_plan* p) {
 fgpu_info fgpu_bfs_part_step(fgpu_bfs_plan* p) {
     FGPU_REQUIRE(p, FGPU_NULL_POINTER, "fgpu_bfs_part_step: NULL plan");
     BfsArgs a = make_args(p);
-    if (p->want_parent)
-        hipLaunchKernelGGL(bfs_step_kernel<true>, dim3(p->grid), dim3(256), 0, p->ctx->stream(), a);
-    else
-        hipLaunchKernelGGL(bfs_step_kernel<false>, dim3(p->grid), dim3(256), 0, p->ctx->stream(), a);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    return pick(p->want_parent, [&](auto par) {
+        return launch(bfs_step_kernel<decltype(par)::value>, dim3(p->grid), dim3(256), 0, p->ctx->stream(), a);
+    });
 }
 
 fgpu_info fgpu_bfs_part_commit(fgpu_bfs_plan* p) {
@@ -3360,10 +3335,8 @@ fgpu_info fgpu_bfs_part_commit(fgpu_bfs_plan* p) {
     BfsArgs a = make_args(p);
     u32 grid = cdiv(p->nw, 4);
     if (grid > p->grid * 2) grid = p->grid * 2;
-    hipLaunchKernelGGL(bfs_commit_kernel, dim3(grid), dim3(256), 0, p->ctx->stream(), a);
-    FGPU_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bfs_ctrl_kernel, dim3(1), dim3(64), 0, p->ctx->stream(), p->ctrl);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bfs_commit_kernel, dim3(grid), dim3(256), 0, p->ctx->stream(), a));
+    FGPU_TRY(launch(bfs_ctrl_kernel, dim3(1), dim3(64), 0, p->ctx->stream(), p->ctrl));
     return FGPU_OK;
 }
 
@@ -3401,15 +3374,11 @@ static fgpu_info profiled_level(fgpu_bfs_plan* p) {
     // "bfs_prof_split" (rocprofv3 PMC passes, which can tell launches apart by kernel name alone) does the pass
     // launch the <.., 1> / <.., 2> twins that name a launch push / pull.
     const int hint = ctx->opt.bfs_prof_split ? dir : 0;
-    if (p->want_parent) {
-        if (hint == 1) hipLaunchKernelGGL((bfs_fused_kernel<true, 1>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-        else if (hint == 2) hipLaunchKernelGGL((bfs_fused_kernel<true, 2>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-        else hipLaunchKernelGGL((bfs_fused_kernel<true, 0>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-    } else {
-        if (hint == 1) hipLaunchKernelGGL((bfs_fused_kernel<false, 1>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-        else if (hint == 2) hipLaunchKernelGGL((bfs_fused_kernel<false, 2>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-        else hipLaunchKernelGGL((bfs_fused_kernel<false, 0>), dim3(pgrid), dim3(256), 0, ctx->stream(), a);
-    }
+    FGPU_TRY(pick(p->want_parent, [&](auto par) {
+        return pick<1, 2, 0>(hint, [&](auto h) {
+            return launch(bfs_fused_kernel<decltype(par)::value, decltype(h)::value>, dim3(pgrid), dim3(256), 0, ctx->stream(), a);
+        });
+    }));
     FGPU_HIP(hipEventRecord(p->ev1, ctx->stream()));
     FGPU_HIP(hipEventSynchronize(p->ev1));
     FGPU_HIP(hipEventElapsedTime(&ms, p->ev0, p->ev1));
@@ -3552,9 +3521,8 @@ fgpu_info fgpu_bfs_fetch(fgpu_bfs_plan* p, int32_t* level, int64_t* parent) {
     const u32 lo = p->lo, hi = p->hi < p->n ? p->hi : p->n;
     if (hi <= lo) return FGPU_OK;
     if (p->mask_visited && !p->levels_masked) {
-        hipLaunchKernelGGL(bfs_mask_levels_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->level,
-                           p->mask_visited, p->nw * 64);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bfs_mask_levels_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->level,
+                        p->mask_visited, p->nw * 64));
         p->levels_masked = true;
     }
     if (level) FGPU_TRY(ctx->d2h(level + lo, p->level + lo, (size_t)(hi - lo) * sizeof(i32)));   // (one DMA when level[] is pinned)
@@ -3564,9 +3532,8 @@ fgpu_info fgpu_bfs_fetch(fgpu_bfs_plan* p, int32_t* level, int64_t* parent) {
         // level[] (DMA into pinned memory, the staging ring into pageable memory)
         DevBuf<long long> wide;
         FGPU_TRY(wide.alloc(ctx, hi - lo));
-        hipLaunchKernelGGL(bfs_parent_out_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->parent + lo, p->level + lo,
-                           wide.p, hi - lo);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bfs_parent_out_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->parent + lo, p->level + lo,
+                        wide.p, hi - lo));
         FGPU_TRY(ctx->d2h(parent + lo, wide.p, (size_t)(hi - lo) * sizeof(int64_t)));
     }
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
@@ -3730,12 +3697,11 @@ fgpu_info fgpu_vxm(fgpu_ctx* ctx, uint64_t* w, const uint64_t* f, const uint64_t
     if (direction == 3)
         FGPU_TRY(tiles_mxv(ctx, At->tiles, df.p, nw, mask ? dm.p : nullptr, dw.p, false));
     else if (pull)
-        hipLaunchKernelGGL(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
-                           (const u64*)(mask ? dm.p : nullptr), dw.p);
+        FGPU_TRY(launch(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
+                        (const u64*)(mask ? dm.p : nullptr), dw.p));
     else
-        hipLaunchKernelGGL(vxm_push_kernel, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
-                           (const u64*)(mask ? dm.p : nullptr));
-    FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(vxm_push_kernel, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
+                        (const u64*)(mask ? dm.p : nullptr)));
     FGPU_TRY(ctx->d2h(w, dw.p, nw_user * sizeof(u64)));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
     return FGPU_OK;
@@ -3788,32 +3754,27 @@ fgpu_info fgpu_bench_spmv(fgpu_ctx* ctx, const fgpu_mat* A, int which, int iters
     FGPU_HIP(hipEventCreate(&e0));
     FGPU_HIP(hipEventCreate(&e1));
     const u32 grid = ctx->cus * 8;
-    auto launch = [&]() {
-        if (which == 2)
-            (void)tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, true);
-        else if (which == 0)
-            hipLaunchKernelGGL(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
-                               (const u64*)nullptr, dw.p);
-        else
-            hipLaunchKernelGGL(vxm_push_kernel, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
-                               (const u64*)nullptr);
+    auto pass = [&]() -> fgpu_info {
+        if (which == 2) return tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, true);
+        if (which == 0)
+            return launch(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p, (const u64*)nullptr, dw.p);
+        return launch(vxm_push_kernel, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p, (const u64*)nullptr);
     };
     FGPU_HIP(hipMemsetAsync(dw.p, 0, nw * sizeof(u64), ctx->stream()));
-    launch();  // warm
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(pass());  // warm
     // HIP events bracket the kernel alone (the output clear of the tiled variant sits outside), on
     // the stream the kernel runs on, so the figure is comparable with rocprofv3's kernel duration
     double total_ms = 0;
     for (int i = 0; i < iters; ++i) {
         if (cold)
-            hipLaunchKernelGGL(evict_read_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), (const uint4*)scratch.p,
-                               scratch_words / 2, (u32*)(scratch.p + scratch_words));
+            FGPU_TRY(launch(evict_read_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), (const uint4*)scratch.p,
+                            scratch_words / 2, (u32*)(scratch.p + scratch_words)));
         if (which == 2) FGPU_HIP(hipMemsetAsync(dw.p, 0, nw * sizeof(u64), ctx->stream()));
         FGPU_HIP(hipEventRecord(e0, ctx->stream()));
         if (which == 2)
-            (void)tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, false);
+            FGPU_TRY(tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, false));
         else
-            launch();
+            FGPU_TRY(pass());
         FGPU_HIP(hipEventRecord(e1, ctx->stream()));
         FGPU_HIP(hipEventSynchronize(e1));
         float ms1 = 0;

@@ -58,8 +58,7 @@ static fgpu_info bp_acc_read(fgpu_ctx* ctx, u64* acc, u64* a, u64* b) {
     u32* pub = nullptr;
     u32 seq = 0;
     const bool mapped = pub_begin(ctx, &pub, &seq);
-    hipLaunchKernelGGL(bp_acc_fold_kernel, dim3(1), dim3(256), 0, ctx->stream(), (unsigned long long*)acc, mapped ? pub : (u32*)nullptr, seq);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bp_acc_fold_kernel, dim3(1), dim3(256), 0, ctx->stream(), (unsigned long long*)acc, mapped ? pub : (u32*)nullptr, seq));
     u32 w[4] = {0, 0, 0, 0};
     if (mapped) FGPU_TRY(pub_wait(ctx, seq, 4, w));
     else FGPU_TRY(read_words(ctx, (const u32*)(acc + 2), 4, w));
@@ -134,39 +133,37 @@ static fgpu_info transposed_with_items(fgpu_ctx* ctx, const fgpu_mat* m, const f
         DevBuf<u32> cnt, off;
         FGPU_TRY(cnt.alloc(ctx, (size_t)nrows + 1));
         FGPU_TRY(off.alloc(ctx, (size_t)nrows + 1));
-        hipLaunchKernelGGL(bp_item_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)t->rowptr, nrows, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_item_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
+                        (const u32*)t->rowptr, nrows, cnt.p));
         FGPU_TRY(scan_u32(ctx, cnt.p, off.p, (u64)nrows + 1, nullptr));
         u32 n = 0;
         FGPU_TRY(read_u32(ctx, off.p + nrows, &n));
         u32* items = nullptr;
         FGPU_TRY(ctx->dev_alloc((void**)&items, (size_t)(n ? n : 1) * 3 * sizeof(u32)));
-        hipLaunchKernelGGL(bp_item_fill_kernel<false>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)t->rowptr, nrows, (const u32*)off.p, items);
+        FGPU_TRY(launch(bp_item_fill_kernel<false>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(),
+                        (const u32*)t->rowptr, nrows, (const u32*)off.p, items));
         // the split rows' items once more, on their own: the row-group form of the sparse pull leaves exactly these
         // to the item kernel
-        hipLaunchKernelGGL(bp_sitem_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)t->rowptr, nrows, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_sitem_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
+                        (const u32*)t->rowptr, nrows, cnt.p));
         FGPU_TRY(scan_u32(ctx, cnt.p, off.p, (u64)nrows + 1, nullptr));
         u32 ns = 0;
         FGPU_TRY(read_u32(ctx, off.p + nrows, &ns));
         u32* sitems = nullptr;
         fgpu_info ssi = ctx->dev_alloc((void**)&sitems, (size_t)(ns ? ns : 1) * 3 * sizeof(u32));
         if (ssi != FGPU_OK) { ctx->dev_free(items); return ssi; }
+        fgpu_info si = FGPU_OK;
         if (ns)
-            hipLaunchKernelGGL(bp_item_fill_kernel<true>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(),
-                               (const u32*)t->rowptr, nrows, (const u32*)off.p, sitems);
+            si = launch(bp_item_fill_kernel<true>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows,
+                        (const u32*)off.p, sitems);
         u64* sbits = nullptr;
-        fgpu_info si = ctx->dev_alloc((void**)&sbits, ((size_t)nrows / 64 + 2) * sizeof(u64));
+        if (si == FGPU_OK) si = ctx->dev_alloc((void**)&sbits, ((size_t)nrows / 64 + 2) * sizeof(u64));
+        if (si == FGPU_OK) {
+            t->bp_split_bits = sbits;   // (owned by t from here on, whatever follows)
+            si = launch(bp_split_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows, sbits);
+        }
+        if (si == FGPU_OK) si = fgpu_sync(ctx);
         if (si != FGPU_OK) { ctx->dev_free(items); ctx->dev_free(sitems); return si; }
-        hipLaunchKernelGGL(bp_split_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr,
-                           nrows, sbits);
-        t->bp_split_bits = sbits;
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());
-        if (e != hipSuccess) { ctx->dev_free(items); ctx->dev_free(sitems); set_error("item list build failed: %s", hipGetErrorString(e)); return FGPU_DEVICE; }
         t->n_bp_sitems = ns;
         t->bp_sitems = sitems;
         t->n_bp_items = n;
@@ -1203,9 +1200,8 @@ static fgpu_info bp_relayout(fgpu_ctx* ctx, BitState& s, const u32* want) {
     const u32 grid = tiles < (u32)ctx->cus * 8u ? tiles : (u32)ctx->cus * 8u;
     {
         ProfScope ps(ctx, "bp_move_rows_kernel", (u64)s.n + 2 * s.nz_rows * s.ws * 8);
-        hipLaunchKernelGGL(bp_move_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n, ws2, lsh,
-                           (uint4*)s.x.p, (uint4*)q, s.perm, want);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_move_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n, ws2, lsh,
+                        (uint4*)s.x.p, (uint4*)q, s.perm, want));
     }
     ctx->dev_free_zeroed(s.x.take(), words * sizeof(u64));   // every row that held bits was cleared on the way
     s.x.ctx = ctx; s.x.p = (u64*)q; s.x.n = words;
@@ -1224,9 +1220,8 @@ static void bp_recycle_state(fgpu_ctx* ctx, BitState& s) {
         const u32 tiles = (s.n + 2047u) >> 11;
         const u32 grid = tiles < (u32)ctx->cus * 8u ? tiles : (u32)ctx->cus * 8u;
         ProfScope ps(ctx, "bp_rezero_rows_kernel", (u64)s.n + s.nz_rows * s.ws * 8);
-        hipLaunchKernelGGL(bp_rezero_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n,
-                           ws2, lsh, (uint4*)s.x.p, s.perm);
-        if (hipGetLastError() == hipSuccess) {
+        if (launch(bp_rezero_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n, ws2, lsh,
+                   (uint4*)s.x.p, s.perm) == FGPU_OK) {
             ctx->dev_free_zeroed(s.x.take(), words * sizeof(u64));
             s.flag.release();
             return;
@@ -1257,9 +1252,8 @@ static fgpu_info bp_count_flags(fgpu_ctx* ctx, BitState& s) {
         ProfScope ps(ctx, "bp_flag_count_kernel", (u64)s.n);
         u32 grid = cdiv(s.n, 256 * 8);
         if (grid > (u32)ctx->cus * 2) grid = ctx->cus * 2;
-        hipLaunchKernelGGL(bp_flag_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n,
-                           (unsigned long long*)acc.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_flag_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const uint8_t*)s.flag.p, s.n,
+                        (unsigned long long*)acc.p));
     }
     return read_u64(ctx, acc.p, &s.nz_rows);
 }
@@ -1278,17 +1272,15 @@ fgpu_info bp_from_csr(fgpu_ctx* ctx, BitState& s, const fgpu_mat* f) {
         while ((2u << lnsh) <= s.ws && lnsh < 6) ++lnsh;
         u32 grid = cdiv((u64)f->nnz << lnsh, 256);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(bp_zero_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->colidx, (u32)f->nnz, s.ws,
-                           lnsh, s.x.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_zero_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->colidx, (u32)f->nnz, s.ws,
+                        lnsh, s.x.p));
     }
     if (f->nnz) {
         ProfScope ps(ctx, "bp_scatter_csr_kernel", 4 * (u64)f->nnz + 4 * ((u64)f->nrows + 1) + 16 * (u64)f->nnz);
         u32 grid = cdiv(f->nnz, 256);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(bp_scatter_csr_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), (u32)f->nrows,
-                           (u32)f->nnz, s.ws, s.x.p, s.flag.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_scatter_csr_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), (u32)f->nrows,
+                        (u32)f->nnz, s.ws, s.x.p, s.flag.p));
     }
     s.nz_rows = f->nnz < f->ncols ? f->nnz : f->ncols;   // an upper bound is all the next hop needs
     return FGPU_OK;
@@ -1344,13 +1336,10 @@ fgpu_info bp_push_from_csr(fgpu_ctx* ctx, BitState& s, const fgpu_mat* f, const 
         for (auto& st : steps) {
             if (!st.a || st.a->nnz == 0) continue;
             ProfScope ps(ctx, st.name, 12 * (u64)f->nnz);
-            if (st.op == 0)
-                hipLaunchKernelGGL(bp_push_csr_kernel<0>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), (u32)f->nnz,
-                                   view_of(st.a), s.ws, s.x.p, s.flag.p);
-            else
-                hipLaunchKernelGGL(bp_push_csr_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), (u32)f->nnz,
-                                   view_of(st.a), s.ws, s.x.p, s.flag.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY((pick<0, 1>(st.op, [&](auto op) {
+                return launch(bp_push_csr_kernel<decltype(op)::value>, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), (u32)f->nnz,
+                              view_of(st.a), s.ws, s.x.p, s.flag.p);
+            })));
         }
     }
     return bp_count_flags(ctx, s);
@@ -1375,8 +1364,7 @@ fgpu_info bp_accumulate(fgpu_ctx* ctx, BitState& u, const BitState& x) {
         ProfScope ps(ctx, "bp_or_kernel", 3 * words * sizeof(u64));
         u32 grid = cdiv(words, 256);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(bp_or_kernel, dim3(grid), dim3(256), 0, ctx->stream(), u.x.p, (const u64*)x.x.p, words);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_or_kernel, dim3(grid), dim3(256), 0, ctx->stream(), u.x.p, (const u64*)x.x.p, words));
     }
     return FGPU_OK;
 }
@@ -1429,9 +1417,8 @@ static fgpu_info bp_flops(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* a, u
     ProfScope ps(ctx, "bp_flops_kernel", 4 * ((u64)a->nvec + 1) + (u64)s.n + (s.nz_rows < s.n ? s.nz_rows : (u64)s.n) * s.w * 8);
     u32 grid = cdiv(a->nvec ? a->nvec : 1, 256);
     if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-    hipLaunchKernelGGL(bp_flops_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), s.w, s.ws,
-                       (const u64*)s.x.p, (const uint8_t*)s.flag.p, (unsigned long long*)acc.p, s.perm);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bp_flops_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), s.w, s.ws,
+                    (const u64*)s.x.p, (const uint8_t*)s.flag.p, (unsigned long long*)acc.p, s.perm));
     u64 v = 0;
     FGPU_TRY(read_u64(ctx, acc.p, &v));
     *flops += v;
@@ -1845,9 +1832,8 @@ fgpu_info bp_probe_rows(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* m, con
         ProfScope ps(ctx, "bp_probe_rows_kernel", (u64)k * 16);
         u32 grid = cdiv(k, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(bp_probe_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(t), dst_dev, bit_dev, k,
-                           (const u64*)s.x.p, s.ws, hit_m);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_probe_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(t), dst_dev, bit_dev, k,
+                        (const u64*)s.x.p, s.ws, hit_m));
     }
     struct { const fgpu_mat* d; uint8_t* hit; } layers[2] = {{dm, hit_dm}, {dp, hit_dp}};
     for (auto& l : layers) {
@@ -1856,9 +1842,8 @@ fgpu_info bp_probe_rows(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* m, con
         FGPU_TRY(mat_wordrow(ctx, l.d, &wr));
         u32 grid = cdiv(l.d->nnz, 256);
         if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
-        hipLaunchKernelGGL(bp_probe_delta_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(l.d), (u32)l.d->nnz, wr, sdst_dev,
-                           srow_dev, k, bit_dev, (const u64*)s.x.p, s.ws, l.hit);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_probe_delta_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(l.d), (u32)l.d->nnz, wr, sdst_dev,
+                        srow_dev, k, bit_dev, (const u64*)s.x.p, s.ws, l.hit));
     }
     return FGPU_OK;
 }
@@ -2042,9 +2027,8 @@ static fgpu_info bp_to_csr_sorted(fgpu_ctx* ctx, const BitState& s, const u64* l
     const u64 nzr = (s.flag.p && s.nz_rows < (u64)s.n) ? s.nz_rows : (u64)s.n;
     {
         ProfScope ps(ctx, "bp_pairs_kernel<count>", nzr * s.w * 8 + (u64)s.n);
-        hipLaunchKernelGGL(bp_pairs_kernel<false>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
-                           (const uint8_t*)s.flag.p, label_dev, s.perm, tcnt.p, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bp_pairs_kernel<false>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
+                        (const uint8_t*)s.flag.p, label_dev, s.perm, tcnt.p, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr));
     }
     DevBuf<u64> toff;
     FGPU_TRY(toff.alloc(ctx, (size_t)ntiles + 1));
@@ -2065,9 +2049,8 @@ static fgpu_info bp_to_csr_sorted(fgpu_ctx* ctx, const BitState& s, const u64* l
         if (i == FGPU_OK) i = val.alloc(ctx, nnz);
         if (i == FGPU_OK) {
             ProfScope ps(ctx, "bp_pairs_kernel<fill>", nzr * s.w * 8 + (u64)s.n + 8 * nnz);
-            hipLaunchKernelGGL(bp_pairs_kernel<true>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
-                               (const uint8_t*)s.flag.p, label_dev, s.perm, (u32*)nullptr, (const u64*)toff.p, key.p, val.p);
-            if (hipGetLastError() != hipSuccess) { set_error("bit-parallel emission failed"); i = FGPU_DEVICE; }
+            i = launch(bp_pairs_kernel<true>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
+                       (const uint8_t*)s.flag.p, label_dev, s.perm, (u32*)nullptr, (const u64*)toff.p, key.p, val.p);
         }
         if (i == FGPU_OK) {
             ProfScope ps(ctx, "emission sort (pairs by row)", 16 * nnz + 4 * nnz);
@@ -2079,9 +2062,8 @@ static fgpu_info bp_to_csr_sorted(fgpu_ctx* ctx, const BitState& s, const u64* l
     if (i == FGPU_OK && s.nsrc_full) {
         // compacted source rows: row i of the result is live row rowrank[i] (an empty source row starts and ends where the next
         // live one starts)
-        hipLaunchKernelGGL(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)rp_live.p, (const u32*)s.rowrank.p, out_rows, o->rowptr);
-        if (hipGetLastError() != hipSuccess) i = FGPU_DEVICE;
+        i = launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
+                   (const u32*)s.rowrank.p, out_rows, o->rowptr);
     }
     if (i == FGPU_OK && hipStreamSynchronize(ctx->stream()) != hipSuccess) { set_error("bit-parallel emission failed"); i = FGPU_DEVICE; }
     if (i != FGPU_OK) { mat_release(o); return i; }
@@ -2134,33 +2116,29 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
     const u32 out_rows = s.nsrc_full ? s.nsrc_full : s.nsrc;
     FGPU_TRY(mat_alloc(ctx, &o, out_rows, s.n, nnz, false, 0, false));
     // rows >= nsrc are empty, so off[nsrc * nchunks] == nnz already
+    fgpu_info i = FGPU_OK;
+    DevBuf<u32> rp_live;
     if (s.nsrc_full) {
         // compacted source rows: row i of the result is live row rowrank[i] (an empty source row starts — and ends — where
         // the next live one starts); the entries themselves are emitted in live-row order, which IS the order of the rows
-        DevBuf<u32> rp_live;
-        fgpu_info ai = rp_live.alloc(ctx, (size_t)s.nsrc + 1);
-        if (ai != FGPU_OK) { mat_release(o); return ai; }
-        hipLaunchKernelGGL(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u64*)off.p, s.nsrc, nchunks, rp_live.p);
-        hipLaunchKernelGGL(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)rp_live.p, (const u32*)s.rowrank.p, out_rows, o->rowptr);
-        if (hipStreamSynchronize(ctx->stream()) != hipSuccess) { mat_release(o); set_error("bit-parallel emission failed"); return FGPU_DEVICE; }
-    } else
-    hipLaunchKernelGGL(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(),
-                       (const u64*)off.p, s.nsrc, nchunks, o->rowptr);
-    if (nnz) {
+        i = rp_live.alloc(ctx, (size_t)s.nsrc + 1);
+        if (i == FGPU_OK)
+            i = launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
+                       nchunks, rp_live.p);
+        if (i == FGPU_OK)
+            i = launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
+                       (const u32*)s.rowrank.p, out_rows, o->rowptr);
+    } else {
+        i = launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
+                   nchunks, o->rowptr);
+    }
+    if (i == FGPU_OK && nnz) {
         ProfScope ps(ctx, "bp_rows_kernel<emit>", nzr * s.w * 8 + (u64)s.n + 8 * (u64)ncnt + 4 * nnz);
-        const fgpu_info li = launch(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks,
-                                    label_dev, nullptr, off.p, o->colidx, s.flag.p);
-        if (li != FGPU_OK) { mat_release(o); return li; }
+        i = launch(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks, label_dev,
+                   nullptr, off.p, o->colidx, s.flag.p);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());
-    if (e != hipSuccess) {
-        mat_release(o);
-        set_error("bit-parallel emission failed: %s", hipGetErrorString(e));
-        return FGPU_DEVICE;
-    }
+    if (i == FGPU_OK) i = fgpu_sync(ctx);   // (rp_live returns to the pool)
+    if (i != FGPU_OK) { mat_release(o); return i; }
     *out = o;
     return FGPU_OK;
 }

@@ -2,29 +2,8 @@
 // bitpart.hip: the XCD-partitioned form of the dense counting hop).
 #pragma once
 #include "common.hpp"
-#include <type_traits>
 
 namespace fgpu {
-
-// ---- launching -------------------------------------------------------------------------------------------------------------
-// One kernel launch: beyond 48 KiB of dynamic LDS the kernel's own limit is raised first.  The arguments convert to the kernel's
-// parameter types (a bare nullptr is fine); the result is the launch's error.
-template <typename... P, typename... A>
-inline fgpu_info launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
-    if (lds > 48 * 1024) FGPU_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
-}
-// A run-time value as a compile-time one: pick<1, 2, 4>(v, f) calls f(std::integral_constant<int, V>{}) for the listed V equal
-// to v — for the LAST one when none is — so a generic lambda names a kernel specialisation by `decltype(c)::value`.
-template <int V, int... Rest, typename F>
-inline fgpu_info pick(int v, F&& f) {
-    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
-    else return v == V ? f(std::integral_constant<int, V>{}) : pick<Rest...>(v, f);
-}
-template <typename F>
-inline fgpu_info pick(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // Two 64-bit sums of a kernel (nnz + checksum, flops + rows) without same-address atomics: every wavefront adding into ONE
 // pair of words costs ~5.6 ns per atomic at the memory side — 65 K wavefronts ending together made a ~100 us

@@ -309,8 +309,7 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     if (dense) {   // the rows with an entry, ranked in vertex order: slot = rank, groups of 64 slots
         DevBuf<u32> rank;
         FGPU_TRY(rank.alloc(ctx, (size_t)n + 1));
-        hipLaunchKernelGGL(xp_has_entry_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, n, rank.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_has_entry_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, n, rank.p));
         FGPU_TRY(scan_u32(ctx, rank.p, rank.p, (u64)n + 1, nullptr));
         FGPU_TRY(read_u32(ctx, rank.p + n, &xp->nd));
         FGPU_REQUIRE(xp->nd >= 1 && xp->nd <= n, FGPU_INVALID, "partitioned pull: %u of %u rows have an entry", xp->nd, n);
@@ -318,8 +317,7 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         ng = (nslots + 63) / 64;
         FGPU_TRY(ctx->dev_alloc((void**)&xp->gvtx, (size_t)ng * 64 * sizeof(u32)));
         FGPU_HIP(hipMemsetAsync(xp->gvtx, 0xFF, (size_t)ng * 64 * sizeof(u32), st));    // XP_NO_VTX
-        hipLaunchKernelGGL(xp_slots_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)rank.p, n, xp->gvtx);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_slots_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)rank.p, n, xp->gvtx));
     }
     xp->ng = ng;
     const u64 total = 8ull * n;
@@ -336,11 +334,9 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(by_rank.alloc(ctx, nu));
         FGPU_TRY(kptr.alloc(ctx, 65536 + 1));
         FGPU_TRY(ctx->dev_alloc((void**)&xp->perm, (size_t)nu * sizeof(u32)));
-        hipLaunchKernelGGL(xp_deg_key_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)m->rowptr, nu, dkey.p, dval.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_deg_key_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)m->rowptr, nu, dkey.p, dval.p));
         FGPU_TRY(sort_u32_pairs_by_key(ctx, dkey.p, dval.p, nu, 65536, by_rank.p, kptr.p));
-        hipLaunchKernelGGL(xp_rank_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)by_rank.p, nu, prange, xp->perm);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_rank_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)by_rank.p, nu, prange, xp->perm));
     }
     FGPU_TRY(ctx->dev_alloc((void**)&xp->pstart_dev, 27 * sizeof(u32)));
     FGPU_TRY(ctx->dev_alloc((void**)&xp->pcol, ((size_t)t->nnz + 64) * sizeof(u32)));
@@ -350,10 +346,9 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(partition_csr_entries(ctx, t->colidx, t->rowptr, n, t->nnz, xp->perm, prange, 8, pairs.p, xp->pstart_dev));
         u32 rgrid = cdiv(t->nnz, 256 * 4);
         if (rgrid > (u32)ctx->cus * 16) rgrid = ctx->cus * 16;
-        hipLaunchKernelGGL(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, (u32)t->nnz,
-                           xp->pcol, off.p);
-        hipLaunchKernelGGL(xp_run_tails_kernel, dim3(64, 8), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, off.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, (u32)t->nnz,
+                        xp->pcol, off.p));
+        FGPU_TRY(launch(xp_run_tails_kernel, dim3(64, 8), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, off.p));
     }
     if (direct) {   // the single-entry runs leave the stream; everything below is built over the runs that stay
         const u32 nnz = (u32)t->nnz;
@@ -361,8 +356,7 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(pos.alloc(ctx, (size_t)nnz + 1));
         u32 egrid = cdiv((u64)nnz + 1, 256 * 4);
         if (egrid > (u32)ctx->cus * 16) egrid = ctx->cus * 16;
-        hipLaunchKernelGGL(xp_keep_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, nnz, pos.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_keep_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, nnz, pos.p));
         FGPU_TRY(scan_u32(ctx, pos.p, pos.p, (u64)nnz + 1, nullptr));
         u32 nkept = 0;
         FGPU_TRY(read_u32(ctx, pos.p + nnz, &nkept));
@@ -371,22 +365,18 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(ctx->dev_alloc((void**)&kept, ((size_t)nkept + 64) * sizeof(u32)));
         FGPU_TRY(ctx->dev_alloc((void**)&xp->dcol, ((size_t)xp->ndirect + 1) * sizeof(u32)));
         FGPU_HIP(hipMemsetAsync(xp->dcol, 0, sizeof(u32), st));   // (index 0 is what the fold loads for a row without one)
-        hipLaunchKernelGGL(xp_split_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, (const u32*)pos.p, nnz, kept, xp->dcol);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_split_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, (const u32*)pos.p, nnz, kept, xp->dcol));
         ctx->dev_free(xp->pcol);
         xp->pcol = kept;
         FGPU_TRY(ctx->dev_alloc((void**)&xp->de, (size_t)8 * ng * sizeof(u64)));
         FGPU_TRY(ctx->dev_alloc((void**)&xp->dbase, ((size_t)8 * ng + 1) * sizeof(u32)));
         u32 ggrid = cdiv((u64)8 * ng, 4);
         if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
-        hipLaunchKernelGGL(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng,
-                           (const u32*)xp->gvtx, nslots, xp->de, xp->dbase);
-        FGPU_HIP(hipGetLastError());
-        hipLaunchKernelGGL(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng,
+                        (const u32*)xp->gvtx, nslots, xp->de, xp->dbase));
+        FGPU_TRY(launch(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev));
     }
-    hipLaunchKernelGGL(xp_nonempty_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, total, ridx.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(xp_nonempty_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, total, ridx.p));
     FGPU_TRY(scan_u32(ctx, ridx.p, ridx.p, total + 1, nullptr));
     FGPU_TRY(read_u32(ctx, ridx.p + total, &xp->nprows));
     u32 hp[27];                                              // pstart[9] | cbase[9] | first run of partition k [9]
@@ -404,24 +394,21 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     FGPU_TRY(ctx->dev_alloc((void**)&xp->pbase, ((size_t)8 * ng + 1) * sizeof(u32)));
     u32 ggrid = cdiv((u64)8 * ng, 4);
     if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
-    hipLaunchKernelGGL(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng,
-                       (const u32*)xp->gvtx, nslots, xp->ne, xp->pbase);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng,
+                    (const u32*)xp->gvtx, nslots, xp->ne, xp->pbase));
     FGPU_TRY(ctx->dev_alloc((void**)&xp->cstart, ((size_t)xp->nchunks + 1) * sizeof(u32)));
     FGPU_TRY(ctx->dev_alloc((void**)&xp->crun0, ((size_t)xp->nchunks + 1) * sizeof(u32)));
     FGPU_TRY(ctx->dev_alloc((void**)&xp->cshared, (size_t)xp->nchunks + 8));
     FGPU_HIP(hipMemsetAsync(xp->cshared, 0, (size_t)xp->nchunks + 8, st));
-    hipLaunchKernelGGL(xp_chunks_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n,
-                       (const u32*)xp->pstart_dev, xp->cstart, xp->crun0, xp->cshared);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(xp_chunks_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n,
+                    (const u32*)xp->pstart_dev, xp->cstart, xp->crun0, xp->cshared));
     {   // the shared rows, compacted once (a few thousand among ~10^5 chunks)
         DevBuf<u32> zc;
         FGPU_TRY(zc.alloc(ctx, 1));
         FGPU_HIP(hipMemsetAsync(zc.p, 0, sizeof(u32), st));
         FGPU_TRY(ctx->dev_alloc((void**)&xp->zrows, ((size_t)xp->nchunks + 1) * sizeof(u32)));
-        hipLaunchKernelGGL(xp_shared_rows_kernel, dim3(cdiv(xp->nchunks ? xp->nchunks : 1, 256)), dim3(256), 0, st, (const u32*)xp->crun0,
-                           (const uint8_t*)xp->cshared, xp->nchunks, xp->zrows, zc.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(xp_shared_rows_kernel, dim3(cdiv(xp->nchunks ? xp->nchunks : 1, 256)), dim3(256), 0, st, (const u32*)xp->crun0,
+                        (const uint8_t*)xp->cshared, xp->nchunks, xp->zrows, zc.p));
         FGPU_TRY(read_u32(ctx, zc.p, &xp->nzrows));
         // ... and the spare row after the last run: the all-zero partial row the fold reads for (row, partition) pairs without one
         FGPU_TRY(ctx->h2d(xp->zrows + xp->nzrows, &xp->nprows, sizeof(u32)));

@@ -279,8 +279,6 @@ fgpu_info blocked_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 
         case 3: fn = blocked_mxv_kernel<4, 8>; break;
         default: break;
     }
-    if (lds > 48 * 1024)
-        FGPU_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     BlockedView v{t->bk_seg_off, t->bk_entries, t->bk_wbits, t->bk_nwindows, t->ntiles, t->bk_nsplit};
     u32 per_cu = (u32)(ctx->opt.lds_limit / lds);
     if (per_cu > max_per_cu) per_cu = max_per_cu;    // 2 x 1024 threads fill a CU
@@ -288,10 +286,7 @@ fgpu_info blocked_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 
     u32 grid = ctx->opt.tiled_wgs ? (u32)ctx->opt.tiled_wgs : (u32)ctx->cus * per_cu;
     const u32 nunits = t->bk_nwindows * t->bk_nsplit;
     if (grid > nunits) grid = nunits;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(1024), lds, ctx->stream(), v, (const u32*)x_dev, x_words64 * 2, mask_dev,
-                       out_dev, t->ngroups);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    return launch(fn, dim3(grid), dim3(1024), lds, ctx->stream(), v, (const u32*)x_dev, x_words64 * 2, mask_dev, out_dev, t->ngroups);
 }
 
 // fills the blocked members of `t` (t->ngroups is set by the caller)
@@ -312,11 +307,10 @@ fgpu_info blocked_build(fgpu_ctx* ctx, const fgpu_mat* m, CsrView mv, fgpu_tiles
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)nbuckets + 1) * sizeof(u32), ctx->stream()));
     u32 grid = cdiv(nrows, 4);
     if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-    hipLaunchKernelGGL(bk_scatter_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)nrows, wbits, ntiles, cnt.p,
-                       (const u32*)nullptr, (u32*)nullptr);
-    hipLaunchKernelGGL(bk_pad_count_kernel, dim3(cdiv((u64)nblocks + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p,
-                       nblocks, padded.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bk_scatter_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)nrows, wbits, ntiles, cnt.p,
+                    (const u32*)nullptr, (u32*)nullptr));
+    FGPU_TRY(launch(bk_pad_count_kernel, dim3(cdiv((u64)nblocks + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p,
+                    nblocks, padded.p));
     DevBuf<u64> off64;
     FGPU_TRY(off64.alloc(ctx, (size_t)nbuckets + 1));
     FGPU_TRY(scan_u32_to_u64(ctx, padded.p, off64.p, (u64)nbuckets + 1, nullptr));
@@ -328,13 +322,12 @@ fgpu_info blocked_build(fgpu_ctx* ctx, const fgpu_mat* m, CsrView mv, fgpu_tiles
     FGPU_TRY(ctx->dev_alloc((void**)&t->bk_entries, (size_t)(total ? total : 4) * sizeof(u32)));
     FGPU_TRY(scan_u32(ctx, padded.p, seg_off.p, (u64)nbuckets + 1, nullptr));                  // the same prefix in 32 bits
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)nbuckets + 1) * sizeof(u32), ctx->stream()));
-    hipLaunchKernelGGL(bk_scatter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)nrows, wbits, ntiles, cnt.p,
-                       (const u32*)seg_off.p, t->bk_entries);
-    hipLaunchKernelGGL(bk_pad_fill_kernel, dim3(cdiv(nbuckets, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p,
-                       (const u32*)seg_off.p, nbuckets, t->bk_entries);
-    hipLaunchKernelGGL(bk_block_off_kernel, dim3(cdiv((u64)nblocks + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)seg_off.p,
-                       nblocks, t->bk_seg_off);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(bk_scatter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)nrows, wbits, ntiles, cnt.p,
+                    (const u32*)seg_off.p, t->bk_entries));
+    FGPU_TRY(launch(bk_pad_fill_kernel, dim3(cdiv(nbuckets, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p,
+                    (const u32*)seg_off.p, nbuckets, t->bk_entries));
+    FGPU_TRY(launch(bk_block_off_kernel, dim3(cdiv((u64)nblocks + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)seg_off.p,
+                    nblocks, t->bk_seg_off));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
     t->kind = 1;
     t->bk_wbits = wbits;

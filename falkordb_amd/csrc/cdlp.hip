@@ -369,11 +369,11 @@ __global__ __launch_bounds__(256) void cdlp_popcount_kernel(const u32* __restric
 }
 
 template <u32 G>
-static void cdlp_launch_short(fgpu_ctx* ctx, CsrView a, const u64* act, const u32* in, u32* out, const u32* rows, u32 count,
-                              const unsigned long long* prev, unsigned long long* chg) {
-    if (!count) return;
-    hipLaunchKernelGGL(cdlp_short_kernel<G>, dim3(capped_grid(ctx, count, 256 / G, 8)), dim3(256), 0, ctx->stream(), a, act, in,
-                       out, rows, count, prev, chg);
+static fgpu_info cdlp_launch_short(fgpu_ctx* ctx, CsrView a, const u64* act, const u32* in, u32* out, const u32* rows, u32 count,
+                                   const unsigned long long* prev, unsigned long long* chg) {
+    if (!count) return FGPU_OK;
+    return launch(cdlp_short_kernel<G>, dim3(capped_grid(ctx, count, 256 / G, 8)), dim3(256), 0, ctx->stream(), a, act, in, out,
+                  rows, count, prev, chg);
 }
 
 }  // namespace fgpu
@@ -408,15 +408,13 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, 8 * sizeof(unsigned long long), st));
     FGPU_HIP(hipMemsetAsync(mark.p, 0, (size_t)mark_words * sizeof(u32), st));
     const u32 vgrid = capped_grid(ctx, n, 256, 8);
-    hipLaunchKernelGGL(cdlp_init_kernel, dim3(vgrid), dim3(256), 0, st, lab.p, n);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(cdlp_init_kernel, dim3(vgrid), dim3(256), 0, st, lab.p, n));
     u32* buf[2] = {lab.p, lab.p + n};
     u64 iters = 0, changed_last = 0, row_entries = 0;
     u32 cur = 0;   // buf[cur] holds the labels
     if (itermax > 0) {
         // the classes, once per call
-        hipLaunchKernelGGL(cdlp_count_kernel, dim3(vgrid), dim3(256), 0, st, sv.rowptr, a, n, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(cdlp_count_kernel, dim3(vgrid), dim3(256), 0, st, sv.rowptr, a, n, cnt.p));
         unsigned long long hc[7];
         FGPU_TRY(ctx->d2h(hc, cnt.p, sizeof(hc)));
         row_entries = hc[6];
@@ -428,8 +426,7 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
         if (ls.off[CDLP_BINS]) {
             FGPU_TRY(cursor.alloc(ctx, CDLP_BINS));
             FGPU_HIP(hipMemsetAsync(cursor.p, 0, CDLP_BINS * sizeof(u32), st));
-            hipLaunchKernelGGL(cdlp_fill_kernel, dim3(vgrid), dim3(256), 0, st, sv.rowptr, a, n, ls, rows.p, cursor.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(cdlp_fill_kernel, dim3(vgrid), dim3(256), 0, st, sv.rowptr, a, n, ls, rows.p, cursor.p));
         }
         CdlpHub hb = {};
         const u32 nch = S->n_hub_chunks;
@@ -439,9 +436,8 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
             FGPU_TRY(clen.alloc(ctx, nch));
             FGPU_TRY(coff.alloc(ctx, nch));
             FGPU_TRY(hubmem.alloc(ctx, hub_words));
-            hipLaunchKernelGGL(cdlp_chunk_len_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st,
-                               (const u32*)S->hub_chunks, nch, clen.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(cdlp_chunk_len_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st,
+                            (const u32*)S->hub_chunks, nch, clen.p));
             FGPU_TRY(scan_u32(ctx, clen.p, coff.p, nch, nullptr));
             hb.chunks = S->hub_chunks;
             hb.n_chunks = nch;
@@ -460,23 +456,22 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
                 unsigned long long* c = chg.p + j;
                 const u32* src = buf[cur];
                 u32* dst = buf[cur ^ 1];
-                hipLaunchKernelGGL(cdlp_small_kernel, dim3(vgrid), dim3(256), 0, st, sv, a, src, dst, n, prev, c);
-                cdlp_launch_short<8>(ctx, sv, a, src, dst, rows.p + ls.off[0], ls.off[1] - ls.off[0], prev, c);
-                cdlp_launch_short<16>(ctx, sv, a, src, dst, rows.p + ls.off[1], ls.off[2] - ls.off[1], prev, c);
-                cdlp_launch_short<32>(ctx, sv, a, src, dst, rows.p + ls.off[2], ls.off[3] - ls.off[2], prev, c);
-                cdlp_launch_short<64>(ctx, sv, a, src, dst, rows.p + ls.off[3], ls.off[4] - ls.off[3], prev, c);
+                FGPU_TRY(launch(cdlp_small_kernel, dim3(vgrid), dim3(256), 0, st, sv, a, src, dst, n, prev, c));
+                FGPU_TRY(cdlp_launch_short<8>(ctx, sv, a, src, dst, rows.p + ls.off[0], ls.off[1] - ls.off[0], prev, c));
+                FGPU_TRY(cdlp_launch_short<16>(ctx, sv, a, src, dst, rows.p + ls.off[1], ls.off[2] - ls.off[1], prev, c));
+                FGPU_TRY(cdlp_launch_short<32>(ctx, sv, a, src, dst, rows.p + ls.off[2], ls.off[3] - ls.off[2], prev, c));
+                FGPU_TRY(cdlp_launch_short<64>(ctx, sv, a, src, dst, rows.p + ls.off[3], ls.off[4] - ls.off[3], prev, c));
                 if (const u32 nmid = ls.off[5] - ls.off[4])
-                    hipLaunchKernelGGL(cdlp_mid_kernel, dim3(capped_grid(ctx, nmid, 1, 8)), dim3(256), 0, st, sv, a, src, dst,
-                                       (const u32*)(rows.p + ls.off[4]), nmid, prev, c);
+                    FGPU_TRY(launch(cdlp_mid_kernel, dim3(capped_grid(ctx, nmid, 1, 8)), dim3(256), 0, st, sv, a, src, dst,
+                                    (const u32*)(rows.p + ls.off[4]), nmid, prev, c));
                 if (nch) {
-                    hipLaunchKernelGGL(cdlp_clear_kernel, dim3(capped_grid(ctx, hub_words, 1024, 8)), dim3(256), 0, st, hubmem.p,
-                                       hub_words, prev);
-                    hipLaunchKernelGGL(cdlp_hub_encode_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, sv.colidx, a, src, prev);
-                    hipLaunchKernelGGL(cdlp_hub_reduce_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, a, prev);
-                    hipLaunchKernelGGL(cdlp_hub_pick_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st, hb, sv.rowptr,
-                                       src, dst, prev, c);
+                    FGPU_TRY(launch(cdlp_clear_kernel, dim3(capped_grid(ctx, hub_words, 1024, 8)), dim3(256), 0, st, hubmem.p,
+                                    hub_words, prev));
+                    FGPU_TRY(launch(cdlp_hub_encode_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, sv.colidx, a, src, prev));
+                    FGPU_TRY(launch(cdlp_hub_reduce_kernel, dim3(hgrid), dim3(256), 0, st, hb, sv.rowptr, a, prev));
+                    FGPU_TRY(launch(cdlp_hub_pick_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st, hb, sv.rowptr,
+                                    src, dst, prev, c));
                 }
-                FGPU_HIP(hipGetLastError());
                 cur ^= 1;
             }
             u32 w[2 * CDLP_BATCH];
@@ -488,10 +483,9 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
             }
         }
     }
-    hipLaunchKernelGGL(cdlp_finish_kernel, dim3(vgrid), dim3(256), 0, st, (const u32*)buf[cur], a, n, wide.p, mark.p);
-    hipLaunchKernelGGL(cdlp_popcount_kernel, dim3(capped_grid(ctx, mark_words, 256, 8)), dim3(256), 0, st, (const u32*)mark.p,
-                       mark_words, cnt.p + 7);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(cdlp_finish_kernel, dim3(vgrid), dim3(256), 0, st, (const u32*)buf[cur], a, n, wide.p, mark.p));
+    FGPU_TRY(launch(cdlp_popcount_kernel, dim3(capped_grid(ctx, mark_words, 256, 8)), dim3(256), 0, st, (const u32*)mark.p,
+                    mark_words, cnt.p + 7));
     FGPU_TRY(ctx->d2h(label, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when label[] is pinned
     if (stats) {
         unsigned long long distinct = 0;

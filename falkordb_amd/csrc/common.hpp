@@ -1,4 +1,4 @@
-// common.hpp — context, device pool, error plumbing and the device-side CSR view
+// common.hpp — context, device pool, error plumbing, kernel launching and the device-side CSR view
 // shared by every translation unit of libfgpu.  gfx950 (MI355X) only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fgpu.h"
@@ -51,6 +52,37 @@ const char* get_error();
             return (code);                  \
         }                                   \
     } while (0)
+
+// ---- launching ---------------------------------------------------------------
+// Every kernel of the engine is launched by launch(): its error comes back as an fgpu_info, so no launch goes unchecked.
+// Beyond 48 KiB of dynamic LDS the kernel's own limit is raised first, to this launch's `lds`.  The arguments convert to the
+// kernel's parameter types (a bare nullptr is fine).  A caller that raised the limit itself (raise_lds(), once, to a constant at
+// least as large as any `lds` it will pass — the BFS does, per plan) uses launch_raised(), which is the launch half alone.
+template <typename... P>
+inline fgpu_info raise_lds(void (*kernel)(P...), size_t bytes) {
+    FGPU_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return FGPU_OK;
+}
+template <typename... P, typename... A>
+inline fgpu_info launch_raised(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    FGPU_HIP(hipGetLastError());
+    return FGPU_OK;
+}
+template <typename... P, typename... A>
+inline fgpu_info launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (lds > 48 * 1024) FGPU_TRY(raise_lds(kernel, lds));
+    return launch_raised(kernel, grid, block, lds, st, args...);
+}
+// A run-time value as a compile-time one: pick<1, 2, 4>(v, f) calls f(std::integral_constant<int, V>{}) for the listed V equal
+// to v — for the LAST one when none is — so a generic lambda names a kernel specialisation by `decltype(c)::value`.
+template <int V, int... Rest, typename F>
+inline fgpu_info pick(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : pick<Rest...>(v, f);
+}
+template <typename F>
+inline fgpu_info pick(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 }  // namespace fgpu
 

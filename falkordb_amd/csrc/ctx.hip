@@ -40,8 +40,7 @@ fgpu_info read_words(fgpu_ctx* ctx, const u32* dev, int nwords, u32* host) {   /
     u32* dst = nullptr;
     u32 seq = 0;
     (void)pub_begin(ctx, &dst, &seq);
-    hipLaunchKernelGGL(publish_words_kernel, dim3(1), dim3(64), 0, l->stream, dev, nwords, dst, seq);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(publish_words_kernel, dim3(1), dim3(64), 0, l->stream, dev, nwords, dst, seq));
     return pub_wait(ctx, seq, nwords, host);
 }
 
@@ -442,8 +441,7 @@ fgpu_info widen_on_device(fgpu_ctx* ctx, u64* out_dev, const u32* in_dev, size_t
     if (!n) return FGPU_OK;
     size_t grid = (n / 4 + 255) / 256;
     if (grid > (size_t)ctx->cus * 16) grid = (size_t)ctx->cus * 16;
-    hipLaunchKernelGGL(widen_u32_u64_kernel, dim3(grid ? (u32)grid : 1), dim3(256), 0, ctx->stream(), in_dev, out_dev, n);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(widen_u32_u64_kernel, dim3(grid ? (u32)grid : 1), dim3(256), 0, ctx->stream(), in_dev, out_dev, n));
     return FGPU_OK;
 }
 }  // namespace fgpu

@@ -114,8 +114,7 @@ fgpu_info comm_allgatherv_u64(fgpu_ctx* ctx, const u64* send, u64* buf, const u6
     if (counts[me] && send != buf + offs[me]) {   // (in-place plans produce their words where the bitmap keeps them)
         u64 g = (counts[me] + 1023) / 1024;
         if (g > (u64)ctx->cus * 4) g = (u64)ctx->cus * 4;
-        hipLaunchKernelGGL(own_words_kernel, dim3((u32)g), dim3(256), 0, st, send, buf + offs[me], counts[me]);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(own_words_kernel, dim3((u32)g), dim3(256), 0, st, send, buf + offs[me], counts[me]));
     }
     // test-only (option dist_force_self): a communicator of ONE rank still issues the grouped calls of a multi-rank
     // exchange, addressed to itself — a self ncclSend / ncclRecv pair inside ncclGroupStart / End, or (dist_collective 1)
@@ -139,8 +138,7 @@ fgpu_info comm_allgatherv_u64(fgpu_ctx* ctx, const u64* send, u64* buf, const u6
         FGPU_NCCL(R->GroupEnd());
         u64 g = (counts[me] + 1023) / 1024;
         if (g > (u64)ctx->cus * 4) g = (u64)ctx->cus * 4;
-        hipLaunchKernelGGL(own_words_kernel, dim3((u32)g), dim3(256), 0, st, (const u64*)scratch.p, buf + offs[me], counts[me]);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(own_words_kernel, dim3((u32)g), dim3(256), 0, st, (const u64*)scratch.p, buf + offs[me], counts[me]));
         ctx->dist_self_calls.fetch_add(1, std::memory_order_relaxed);
         return FGPU_OK;
     }
@@ -321,9 +319,8 @@ fgpu_info fgpu_mat_balanced_splits(fgpu_ctx* ctx, const fgpu_mat* a, int nparts,
         FGPU_HIP(hipMemsetAsync(dh.p, 0, (size_t)nblocks * sizeof(unsigned long long), ctx->stream()));
         u32 grid = cdiv(a->nnz, 256 * 64);
         if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
-        hipLaunchKernelGGL(colblock_hist_kernel, dim3(grid ? grid : 1), dim3(256), (size_t)nblocks * sizeof(u32), ctx->stream(),
-                           (const u32*)a->colidx, (u64)a->nnz, shift, nblocks, dh.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(colblock_hist_kernel, dim3(grid ? grid : 1), dim3(256), (size_t)nblocks * sizeof(u32), ctx->stream(),
+                        (const u32*)a->colidx, (u64)a->nnz, shift, nblocks, dh.p));
         FGPU_TRY(ctx->d2h(h.data(), dh.p, (size_t)nblocks * sizeof(unsigned long long)));
         FGPU_HIP(hipStreamSynchronize(ctx->stream()));
     }

@@ -313,8 +313,7 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
     FGPU_HIP(hipMemsetAsync(sc, 0, (size_t)n * sizeof(double), st));
     FGPU_HIP(hipMemsetAsync(work, 0, 4 * sizeof(unsigned long long), st));
     const u32 vgrid = capped_grid(ctx, n, 256, 8);
-    hipLaunchKernelGGL(hc_init_kernel, dim3(vgrid), dim3(256), 0, st, a, n, regs.p, est, chg.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(hc_init_kernel, dim3(vgrid), dim3(256), 0, st, a, n, regs.p, est, chg.p));
     uint8_t* buf[2] = {regs.p, regs.p + row_bytes};
     uint8_t* flag[2] = {chg.p, chg.p + n};
     const u32 rgrid = capped_grid(ctx, n, 4, 8);   // a wave per row
@@ -329,16 +328,15 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
             unsigned long long* c = cnt.p + j;
             const uint4* src = (const uint4*)buf[cur];
             uint4* dst = (uint4*)buf[cur ^ 1];
-            hipLaunchKernelGGL(hc_rows_kernel, dim3(rgrid), dim3(256), 0, st, av, a, src, dst, (const uint8_t*)flag[cur],
-                               flag[cur ^ 1], est, sc, n, t + j + 1, prev, c, work);
+            FGPU_TRY(launch(hc_rows_kernel, dim3(rgrid), dim3(256), 0, st, av, a, src, dst, (const uint8_t*)flag[cur],
+                            flag[cur ^ 1], est, sc, n, t + j + 1, prev, c, work));
             if (nch) {
-                hipLaunchKernelGGL(hc_hub_partial_kernel, dim3(hgrid), dim3(256), 0, st, (const u32*)A->hub_chunks, nch, av.colidx,
-                                   a, src, (const uint8_t*)flag[cur], partial.p, prev, work);
-                hipLaunchKernelGGL(hc_hub_fold_kernel, dim3(capped_grid(ctx, nch, 4, 8)), dim3(256), 0, st,
-                                   (const u32*)A->hub_chunks, nch, av.rowptr, a, src, dst, (const uint4*)partial.p, flag[cur ^ 1],
-                                   est, sc, t + j + 1, prev, c, work);
+                FGPU_TRY(launch(hc_hub_partial_kernel, dim3(hgrid), dim3(256), 0, st, (const u32*)A->hub_chunks, nch, av.colidx,
+                                a, src, (const uint8_t*)flag[cur], partial.p, prev, work));
+                FGPU_TRY(launch(hc_hub_fold_kernel, dim3(capped_grid(ctx, nch, 4, 8)), dim3(256), 0, st,
+                                (const u32*)A->hub_chunks, nch, av.rowptr, a, src, dst, (const uint4*)partial.p, flag[cur ^ 1],
+                                est, sc, t + j + 1, prev, c, work));
             }
-            FGPU_HIP(hipGetLastError());
             cur ^= 1;
         }
         u32 w[2 * HC_BATCH];
@@ -350,9 +348,8 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
             else { ++iters; changes += moved; }
         }
     }
-    hipLaunchKernelGGL(hc_finish_kernel, dim3(vgrid), dim3(256), 0, st, (const double*)est, (const double*)sc, a, n, reach.p,
-                       work + 2);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(hc_finish_kernel, dim3(vgrid), dim3(256), 0, st, (const double*)est, (const double*)sc, a, n, reach.p,
+                    work + 2));
     FGPU_TRY(ctx->d2h(score, sc, (size_t)n * sizeof(double)));   // one DMA each when the arrays are pinned
     FGPU_TRY(ctx->d2h(reachable, reach.p, (size_t)n * sizeof(int64_t)));
     if (registers) FGPU_TRY(ctx->d2h(registers, buf[cur], row_bytes));

@@ -135,9 +135,8 @@ static fgpu_info build_hub_list(const fgpu_mat* m, u32 deg_min, u32 chunk, u32**
     FGPU_TRY(meta.alloc(ctx, 2));
     FGPU_TRY(chunks.alloc(ctx, (size_t)cap * 3));
     FGPU_HIP(hipMemsetAsync(meta.p, 0, 2 * sizeof(u32), ctx->stream()));
-    hipLaunchKernelGGL(hub_scan_kernel, dim3(cdiv(m->nvec, 256)), dim3(256), 0, ctx->stream(), m->rowptr, m->nvec,
-                       meta.p, meta.p + 1, chunks.p, cap, m->hrows, deg_min, chunk);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(hub_scan_kernel, dim3(cdiv(m->nvec, 256)), dim3(256), 0, ctx->stream(), m->rowptr, m->nvec,
+                    meta.p, meta.p + 1, chunks.p, cap, m->hrows, deg_min, chunk));
     u32 h[2];
     FGPU_HIP(hipMemcpyAsync(ctx->pinned(), meta.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream()));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
@@ -210,8 +209,7 @@ fgpu_info mat_from_device_coo(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncol
     FGPU_HIP(hipMemsetAsync(hist.p, 0, (nrows + 1) * sizeof(u32), ctx->stream()));
     u32 grid = ctx->cus * 16;
     if (n) {
-        hipLaunchKernelGGL(coo_hist_kernel, dim3(grid), dim3(256), 0, ctx->stream(), rows, n, hist.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(coo_hist_kernel, dim3(grid), dim3(256), 0, ctx->stream(), rows, n, hist.p));
     }
     FGPU_TRY(scan_u32_to_u64(ctx, hist.p, off.p, nrows + 1, tot.p));
     u64 nvalid = 0;
@@ -221,9 +219,8 @@ fgpu_info mat_from_device_coo(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncol
     FGPU_HIP(hipMemsetAsync(hist.p, 0, (nrows + 1) * sizeof(u32), ctx->stream()));
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, (nrows + 1) * sizeof(u32), ctx->stream()));
     if (n) {
-        hipLaunchKernelGGL(coo_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), rows, cols, n, off.p, hist.p,
-                           tmp.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(coo_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), rows, cols, n, off.p, hist.p,
+                        tmp.p));
     }
     hist.release();
     FGPU_TRY(segsort_unique(ctx, tmp.p, off.p, (u32)nrows, (u32)ncols, cnt.p, nullptr));
@@ -587,8 +584,7 @@ fgpu_info mat_transpose_pattern(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
     FGPU_TRY(cols.alloc(ctx, a->nnz));
     u32 grid = cdiv(a->nvec, 4);
     if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-    hipLaunchKernelGGL(csr_to_coo_t_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), rows.p, cols.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(csr_to_coo_t_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), rows.p, cols.p));
     return mat_from_device_coo(ctx, out, a->ncols, a->nrows, rows.p, cols.p, a->nnz);
 }
 }  // namespace fgpu
@@ -758,9 +754,8 @@ static fgpu_info mat_rmat_impl(fgpu_ctx* ctx, fgpu_mat** out, int scale, int edg
     DevBuf<u32> rows, cols;
     FGPU_TRY(rows.alloc(ctx, nedges));
     FGPU_TRY(cols.alloc(ctx, nedges));
-    hipLaunchKernelGGL(rmat_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), scale, nedges, seed, a32, ab32,
-                       abc32, rows.p, cols.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(rmat_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), scale, nedges, seed, a32, ab32,
+                    abc32, rows.p, cols.p));
     return mat_from_device_coo(ctx, out, n, n, rows.p, cols.p, nedges);
 }
 
@@ -773,9 +768,8 @@ fgpu_info fgpu_mat_sample(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a, uint
     FGPU_TRY(cols.alloc(ctx, a->nnz));
     u32 grid = cdiv(a->nvec, 4);
     if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-    hipLaunchKernelGGL(sample_coo_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), seed, denom, rows.p,
-                       cols.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(sample_coo_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), seed, denom, rows.p,
+                    cols.p));
     FGPU_TRY(mat_from_device_coo(ctx, out, a->nrows, a->ncols, rows.p, cols.p, a->nnz));
     return ctx->publish();
 }
@@ -920,10 +914,9 @@ fgpu_info fgpu_mat_probe(fgpu_ctx* ctx, const fgpu_mat* m, const uint64_t* rows,
     if (vals) FGPU_TRY(dv.alloc(ctx, n));
     FGPU_TRY(ctx->h2d(dr.p, rows, n * sizeof(u64)));
     FGPU_TRY(ctx->h2d(dc.p, cols, n * sizeof(u64)));
-    hipLaunchKernelGGL(probe_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream(), view_of(m),
-                       (const u64*)m->vals, (const u64*)dr.p, (const u64*)dc.p, n, m->nrows, m->ncols, dp.p,
-                       vals ? dv.p : (u64*)nullptr);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(probe_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream(), view_of(m),
+                    (const u64*)m->vals, (const u64*)dr.p, (const u64*)dc.p, n, m->nrows, m->ncols, dp.p,
+                    vals ? dv.p : (u64*)nullptr));
     FGPU_TRY(ctx->d2h(present, dp.p, n));
     if (vals) FGPU_TRY(ctx->d2h(vals, dv.p, n * sizeof(u64)));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
@@ -947,13 +940,11 @@ fgpu_info mat_merge_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, con
     FGPU_TRY(tot.alloc(ctx, 1));
     FGPU_TRY(dirty.alloc(ctx, nrows + 1));
     FGPU_HIP(hipMemsetAsync(dirty.p, 0, nrows + 1, ctx->stream()));
-    hipLaunchKernelGGL(row_len_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), view_of(m),
-                       (u32)nrows, ub.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(row_len_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), view_of(m),
+                    (u32)nrows, ub.p));
     if (has_dp) {
-        hipLaunchKernelGGL(add_stored_row_len_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(),
-                           view_of(dp), ub.p, dirty.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(add_stored_row_len_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(),
+                        view_of(dp), ub.p, dirty.p));
     }
     FGPU_TRY(scan_u32_to_u64(ctx, ub.p, off.p, nrows + 1, tot.p));
     u64 total = 0;
@@ -965,9 +956,8 @@ fgpu_info mat_merge_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, con
     if (nrows) {
         u32 grid = cdiv(nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(merge_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vm, vdp, vdm, has_dp, has_dm,
-                           dm_masks_dp, (u32)nrows, (const u64*)off.p, tmp.p, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(merge_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vm, vdp, vdm, has_dp, has_dm,
+                        dm_masks_dp, (u32)nrows, (const u64*)off.p, tmp.p, cnt.p));
     }
     if (has_dp && nrows) {
         // dirty rows (those that received dp entries) need a sort+unique over their exact extent;
@@ -979,15 +969,13 @@ fgpu_info mat_merge_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, con
         FGPU_TRY(off2.alloc(ctx, 2 * nrows + 1));
         FGPU_TRY(cnt2.alloc(ctx, 2 * nrows));
         FGPU_TRY(dirty2.alloc(ctx, 2 * nrows));
-        hipLaunchKernelGGL(tight_off_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p,
-                           (const u32*)cnt.p, (const uint8_t*)dirty.p, (u32)nrows, off2.p, cnt2.p, dirty2.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(tight_off_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p,
+                        (const u32*)cnt.p, (const uint8_t*)dirty.p, (u32)nrows, off2.p, cnt2.p, dirty2.p));
         FGPU_HIP(hipMemcpyAsync(off2.p + 2 * nrows, off.p + nrows, sizeof(u64), hipMemcpyDeviceToDevice,
                                 ctx->stream()));
         FGPU_TRY(segsort_unique(ctx, tmp.p, off2.p, (u32)(2 * nrows), (u32)m->ncols, cnt2.p, dirty2.p));
-        hipLaunchKernelGGL(take_even_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt2.p,
-                           (u32)nrows, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(take_even_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt2.p,
+                        (u32)nrows, cnt.p));
     }
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
@@ -1013,9 +1001,8 @@ fgpu_info dense_rowptr(fgpu_ctx* ctx, const fgpu_mat* a, DevBuf<u32>& rp) {
     }
     FGPU_HIP(hipMemsetAsync(rp.p, 0, (a->nrows + 1) * sizeof(u32), ctx->stream()));
     if (a->nvec) {
-        hipLaunchKernelGGL(dense_rowptr_len_kernel, dim3(cdiv(a->nvec, 256)), dim3(256), 0, ctx->stream(), view_of(a),
-                           rp.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(dense_rowptr_len_kernel, dim3(cdiv(a->nvec, 256)), dim3(256), 0, ctx->stream(), view_of(a),
+                        rp.p));
     }
     return scan_u32(ctx, rp.p, rp.p, a->nrows + 1, nullptr);
 }
@@ -1050,10 +1037,9 @@ static fgpu_info intersect_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
     if (nrows && a->nnz && b->nnz) {
         u32 grid = cdiv(nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(intersect_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), view_of(b),
-                           (const u64*)b->vals, (u32)nrows, tmp.p, with_vals ? tmpv.p : (u64*)nullptr, cnt.p,
-                           (const u32*)arp.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(intersect_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), view_of(b),
+                        (const u64*)b->vals, (u32)nrows, tmp.p, with_vals ? tmpv.p : (u64*)nullptr, cnt.p,
+                        (const u32*)arp.p));
     }
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
@@ -1067,10 +1053,9 @@ static fgpu_info intersect_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
     if (nrows && nnz) {
         u32 grid = cdiv(nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(compact32_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)tmp.p,
-                           (const u64*)(with_vals ? tmpv.p : nullptr), (const u32*)arp.p, (const u32*)o->rowptr,
-                           (u32)nrows, o->colidx, o->vals);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(compact32_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)tmp.p,
+                        (const u64*)(with_vals ? tmpv.p : nullptr), (const u32*)arp.p, (const u32*)o->rowptr,
+                        (u32)nrows, o->colidx, o->vals));
     }
     fgpu_info i = mat_finalize(o);
     if (i != FGPU_OK) { mat_release(o); return i; }
@@ -1093,9 +1078,8 @@ fgpu_info fgpu_mat_row_degrees(fgpu_ctx* ctx, const fgpu_mat* a, uint32_t* out_d
     DevBuf<u32> rp;
     FGPU_TRY(dense_rowptr(ctx, a, rp));
     if (a->nrows) {
-        hipLaunchKernelGGL(row_degree_kernel, dim3(cdiv(a->nrows, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)rp.p, (u32)a->nrows, out_dev);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(row_degree_kernel, dim3(cdiv(a->nrows, 256)), dim3(256), 0, ctx->stream(),
+                        (const u32*)rp.p, (u32)a->nrows, out_dev));
     }
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));   // `rp` may return to the pool
     return FGPU_OK;
@@ -1111,9 +1095,8 @@ static fgpu_info mat_col_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
     FGPU_TRY(cnt.alloc(ctx, nrows + 1));
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, (nrows + 1) * sizeof(u32), ctx->stream()));
     if (nrows) {
-        hipLaunchKernelGGL(col_slab_count_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), view_of(a),
-                           (u32)lo, (u32)hi, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(col_slab_count_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), view_of(a),
+                        (u32)lo, (u32)hi, cnt.p));
     }
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
@@ -1125,9 +1108,8 @@ static fgpu_info mat_col_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
     if (nrows && nnz) {
         u32 grid = cdiv(nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(col_slab_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), (u32)lo,
-                           (u32)hi, (const u32*)o->rowptr, o->colidx);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(col_slab_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), (u32)lo,
+                        (u32)hi, (const u32*)o->rowptr, o->colidx));
     }
     fgpu_info i = mat_finalize(o);
     if (i != FGPU_OK) { mat_release(o); return i; }
@@ -1143,9 +1125,8 @@ static fgpu_info mat_row_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
     const u64 nrows = a->nrows;
     DevBuf<u32> cnt, rowptr;
     FGPU_TRY(cnt.alloc(ctx, nrows + 1));
-    hipLaunchKernelGGL(row_slab_count_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), view_of(a),
-                       (u32)lo, (u32)hi, cnt.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(row_slab_count_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), view_of(a),
+                    (u32)lo, (u32)hi, cnt.p));
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
     u32 nnz = 0;

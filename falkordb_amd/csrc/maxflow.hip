@@ -532,12 +532,11 @@ struct MfRun {
 // one backward BFS: labels base + dist for the unlabelled vertices that reach `seed`
 static fgpu_info mf_bfs(MfRun& s, u32 seed, u32 base) {
     hipStream_t st = s.ctx->stream();
-    hipLaunchKernelGGL(mf_seed_kernel, dim3(1), dim3(1), 0, st, s.g, seed, s.bfs[0], s.bcnt3);
+    FGPU_TRY(launch(mf_seed_kernel, dim3(1), dim3(1), 0, st, s.g, seed, s.bfs[0], s.bcnt3));
     for (u32 level = 0;;) {
         for (u32 b = 0; b < MF_BATCH; ++b, ++level)
-            hipLaunchKernelGGL(mf_bfs_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)s.bfs[level & 1], s.bfs[(level + 1) & 1],
-                               s.bcnt3, level, base);
-        FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(mf_bfs_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)s.bfs[level & 1], s.bfs[(level + 1) & 1],
+                            s.bcnt3, level, base));
         u32 left = 0;
         FGPU_TRY(read_u32(s.ctx, s.bcnt3 + level % 3, &left));
         if (!left) return FGPU_OK;
@@ -565,8 +564,7 @@ extern "C" fgpu_info fgpu_mat_min_val(fgpu_ctx* ctx, const fgpu_mat* A, uint64_t
     DevBuf<unsigned long long> best;
     FGPU_TRY(best.alloc(ctx, 1));
     FGPU_HIP(hipMemsetAsync(best.p, 0xFF, sizeof(unsigned long long), ctx->stream()));
-    hipLaunchKernelGGL(mf_min_kernel, dim3(capped_grid(ctx, A->nnz, 1024, 8)), dim3(256), 0, ctx->stream(), (const u64*)A->vals, A->nnz, best.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(mf_min_kernel, dim3(capped_grid(ctx, A->nnz, 1024, 8)), dim3(256), 0, ctx->stream(), (const u64*)A->vals, A->nnz, best.p));
     u64 key = 0;
     FGPU_TRY(read_u64(ctx, (const u64*)best.p, &key));
     *bits = fp64_from_sort_key(key);   // (-0.0 comes back as +0.0)
@@ -603,9 +601,8 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
         DevBuf<u32> rows, cols;
         FGPU_TRY(rows.alloc(ctx, 2 * (size_t)C->nnz));
         FGPU_TRY(cols.alloc(ctx, 2 * (size_t)C->nnz));
-        hipLaunchKernelGGL(mf_arcs_kernel, dim3(capped_grid(ctx, C->nnz, 256, 8)), dim3(256), 0, st, view_of(C), (const u64*)C->vals,
-                           (u32)C->nnz, rows.p, cols.p, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(mf_arcs_kernel, dim3(capped_grid(ctx, C->nnz, 256, 8)), dim3(256), 0, st, view_of(C), (const u64*)C->vals,
+                        (u32)C->nnz, rows.p, cols.p, cnt.p));
         u32 w[4];
         FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 4, w));
         npairs = (u64)w[0] | ((u64)w[1] << 32);
@@ -635,10 +632,9 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     FGPU_HIP(hipMemsetAsync(cnt3.p, 0, 6 * sizeof(u32), st));
     FGPU_HIP(hipMemsetAsync(bud.p, 0, 2 * (size_t)(nch ? nch : 1) * sizeof(double), st));
     FGPU_HIP(hipMemsetAsync(newh.p, 0, (size_t)(nch ? nch : 1) * sizeof(u32), st));
-    hipLaunchKernelGGL(mf_net_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, view_of(C), (const u64*)C->vals,
-                       cap.p, r.p, rev.p);
-    if (nch) hipLaunchKernelGGL(mf_hfirst_kernel, dim3(cdiv(nch, 256)), dim3(256), 0, st, (const u32*)R->hub_chunks, nch, hfirst.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(mf_net_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, view_of(C), (const u64*)C->vals,
+                    cap.p, r.p, rev.p));
+    if (nch) FGPU_TRY(launch(mf_hfirst_kernel, dim3(cdiv(nch, 256)), dim3(256), 0, st, (const u32*)R->hub_chunks, nch, hfirst.p));
     MfRun s;
     s.ctx = ctx;
     s.g.rowptr = R->rowptr;
@@ -669,8 +665,7 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     s.hgrid = nch ? hub_grid(ctx, R) : 0;
     const u32 sgrid = nch ? capped_grid(ctx, nch, 256, 8) : 0;
     // start: src's arcs saturated into list 0 (the length lands in cnt3[0]), labels by a global relabel, the hub rows armed
-    hipLaunchKernelGGL(mf_start_kernel, dim3(1), dim3(256), 0, st, s.g, s.list[0], s.cnt3);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(mf_start_kernel, dim3(1), dim3(256), 0, st, s.g, s.list[0], s.cnt3));
     FGPU_TRY(mf_global_relabel(s));
     u64 relabels = 1;
     int64_t every = MF_GLOBAL_EVERY;
@@ -680,24 +675,22 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     u64 pulse = 0;
     if (nch) {
         // (pulse "-1": lists into list[0] behind what the start left there)
-        hipLaunchKernelGGL(mf_hub_step_kernel, dim3(sgrid), dim3(256), 0, st, s.g, s.hb, s.list[0], s.cnt3, 2u);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(mf_hub_step_kernel, dim3(sgrid), dim3(256), 0, st, s.g, s.hb, s.list[0], s.cnt3, 2u));
     }
     for (;;) {
         for (u32 b = 0; b < MF_BATCH; ++b, ++pulse) {
             const u32 p = (u32)(pulse % 6);   // (the list parity and the counter rotation repeat every 6 pulses)
             u32* cur = s.list[p & 1];
             u32* next = s.list[(p + 1) & 1];
-            hipLaunchKernelGGL(mf_push_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)cur, next, s.cnt3, p, s.moved, s.stat);
-            if (nch) hipLaunchKernelGGL(mf_hub_push_kernel, dim3(s.hgrid), dim3(256), 0, st, s.g, s.hb, next, (const u32*)s.cnt3, p, s.stat);
-            hipLaunchKernelGGL(mf_relabel_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)cur, (const u32*)s.cnt3, p,
-                               (const uint8_t*)s.moved);
+            FGPU_TRY(launch(mf_push_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)cur, next, s.cnt3, p, s.moved, s.stat));
+            if (nch) FGPU_TRY(launch(mf_hub_push_kernel, dim3(s.hgrid), dim3(256), 0, st, s.g, s.hb, next, (const u32*)s.cnt3, p, s.stat));
+            FGPU_TRY(launch(mf_relabel_kernel, dim3(s.grid), dim3(256), 0, st, s.g, (const u32*)cur, (const u32*)s.cnt3, p,
+                            (const uint8_t*)s.moved));
             if (nch) {
-                hipLaunchKernelGGL(mf_hub_relabel_kernel, dim3(s.hgrid), dim3(256), 0, st, s.g, s.hb);
-                hipLaunchKernelGGL(mf_hub_step_kernel, dim3(sgrid), dim3(256), 0, st, s.g, s.hb, next, s.cnt3, p);
+                FGPU_TRY(launch(mf_hub_relabel_kernel, dim3(s.hgrid), dim3(256), 0, st, s.g, s.hb));
+                FGPU_TRY(launch(mf_hub_step_kernel, dim3(sgrid), dim3(256), 0, st, s.g, s.hb, next, s.cnt3, p));
             }
         }
-        FGPU_HIP(hipGetLastError());
         u32 left = 0;
         FGPU_TRY(read_u32(ctx, s.cnt3 + (pulse % 6) % 3, &left));
         if (!left) break;
@@ -714,9 +707,8 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     FGPU_TRY(frows.alloc(ctx, m / 2));   // (of two opposite arcs at most one carries flow)
     FGPU_TRY(fcols.alloc(ctx, m / 2));
     FGPU_TRY(fvals.alloc(ctx, m / 2));
-    hipLaunchKernelGGL(mf_flow_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, (const double*)cap.p,
-                       (const double*)r.p, (const u32*)rev.p, frows.p, fcols.p, fvals.p, cnt.p + 4);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(mf_flow_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, (const double*)cap.p,
+                    (const double*)r.p, (const u32*)rev.p, frows.p, fcols.p, fvals.p, cnt.p + 4));
     unsigned long long hc[5];
     double value = 0.0;
     FGPU_TRY(ctx->d2h(hc, cnt.p, sizeof(hc)));

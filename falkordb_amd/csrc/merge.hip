@@ -403,15 +403,13 @@ fgpu_info mat_wordrow(fgpu_ctx* ctx, const fgpu_mat* a, const u32** out) {
         const u32 nwords = (u32)((a->nnz + 63) >> 6);
         u32* wr = nullptr;
         FGPU_TRY(ctx->dev_alloc((void**)&wr, ((size_t)nwords + 1) * sizeof(u32)));
-        hipLaunchKernelGGL(wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(),
-                           (const u32*)a->rowptr, a->nvec, nwords, wr);
-        hipError_t e = hipGetLastError();
+        fgpu_info i = launch(wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)a->rowptr,
+                             a->nvec, nwords, wr);
         // complete on the device before it is published: other lanes read it from their own streams
-        if (e == hipSuccess && ctx->multi_lane()) e = hipStreamSynchronize(ctx->stream());
-        if (e != hipSuccess) {
+        if (i == FGPU_OK && ctx->multi_lane()) i = fgpu_sync(ctx);
+        if (i != FGPU_OK) {
             ctx->dev_free(wr);
-            set_error("wordrow build failed: %s", hipGetErrorString(e));
-            return FGPU_DEVICE;
+            return i;
         }
         a->wordrow = wr;
     }
@@ -464,97 +462,87 @@ fgpu_info mat_merge_entries(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, co
         FGPU_TRY(rowbits.alloc(ctx, nb));
         FGPU_HIP(hipMemsetAsync(rowbits.p, 0, nb * sizeof(u32), ctx->stream()));
         if (has_dp) {
-            hipLaunchKernelGGL(rowbits_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(), lp.v, rowbits.p);
+            FGPU_TRY(launch(rowbits_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(), lp.v, rowbits.p));
             if (has_dm && !(ctx->opt.merge_items && !clip && ctx->opt.merge_mode != 2 && !dm_masks_dp && !m->is_hyper())) {
                 // the rows dp stores, on their own: only they need a cross-rank lookup when m is scattered by merge_scatter_kernel
                 FGPU_TRY(rowbits_dp.alloc(ctx, nb));
                 FGPU_HIP(hipMemsetAsync(rowbits_dp.p, 0, nb * sizeof(u32), ctx->stream()));
-                hipLaunchKernelGGL(rowbits_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(), lp.v, rowbits_dp.p);
+                FGPU_TRY(launch(rowbits_kernel, dim3(cdiv(dp->nvec, 256)), dim3(256), 0, ctx->stream(), lp.v, rowbits_dp.p));
             }
         }
         if (has_dm)
-            hipLaunchKernelGGL(rowbits_kernel, dim3(cdiv(dm->nvec, 256)), dim3(256), 0, ctx->stream(), ld.v, rowbits.p);
-        FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(rowbits_kernel, dim3(cdiv(dm->nvec, 256)), dim3(256), 0, ctx->stream(), ld.v, rowbits.p));
     }
     Keep km, kp;
     FGPU_TRY(km.alloc(ctx, lm.nnz));
     FGPU_TRY(kp.alloc(ctx, has_dp ? lp.nnz : 0));
     if (lm.nnz && !clip && ctx->opt.merge_mode != 2) {
         const u32 nwords = (lm.nnz + 63) >> 6;
-        hipLaunchKernelGGL(merge_markall_kernel, dim3(cdiv(nwords, 256)), dim3(256), 0, ctx->stream(), lm.nnz, km.kb.p);
+        FGPU_TRY(launch(merge_markall_kernel, dim3(cdiv(nwords, 256)), dim3(256), 0, ctx->stream(), lm.nnz, km.kb.p));
         for (const Layer* d : {has_dm ? &ld : nullptr, has_dp ? &lp : nullptr}) {
             if (!d) continue;
-            hipLaunchKernelGGL(merge_unmark_kernel, dim3(entry_grid(ctx, d->nnz)), dim3(256), 0, ctx->stream(), *d, lm, km.kb.p);
+            FGPU_TRY(launch(merge_unmark_kernel, dim3(entry_grid(ctx, d->nnz)), dim3(256), 0, ctx->stream(), *d, lm, km.kb.p));
         }
-        hipLaunchKernelGGL(merge_popc_kernel, dim3(cdiv(nwords, 256)), dim3(256), 0, ctx->stream(), (const u64*)km.kb.p, nwords,
-                           km.ks.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(merge_popc_kernel, dim3(cdiv(nwords, 256)), dim3(256), 0, ctx->stream(), (const u64*)km.kb.p, nwords,
+                        km.ks.p));
     } else if (lm.nnz) {
-        hipLaunchKernelGGL(merge_mark_kernel<true>, dim3(entry_grid(ctx, lm.nnz)), dim3(256), 0, ctx->stream(), lm, lp,
-                           ld, has_dp, has_dm, dm_masks_dp, (const u32*)rowbits.p, (u32)out_nrows, (u32)out_ncols,
-                           km.kb.p, km.ks.p, clip);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(merge_mark_kernel<true>, dim3(entry_grid(ctx, lm.nnz)), dim3(256), 0, ctx->stream(), lm, lp,
+                        ld, has_dp, has_dm, dm_masks_dp, (const u32*)rowbits.p, (u32)out_nrows, (u32)out_ncols,
+                        km.kb.p, km.ks.p, clip));
     }
     FGPU_TRY(scan_u32(ctx, km.ks.p, km.ks.p, ((u64)(lm.nnz + 63) >> 6) + 1, nullptr));
     if (has_dp) {
-        hipLaunchKernelGGL(merge_mark_kernel<false>, dim3(entry_grid(ctx, lp.nnz)), dim3(256), 0, ctx->stream(), lp, lm,
-                           ld, lm.nnz != 0, has_dm, dm_masks_dp, (const u32*)rowbits.p, (u32)out_nrows,
-                           (u32)out_ncols, kp.kb.p, kp.ks.p, clip);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(merge_mark_kernel<false>, dim3(entry_grid(ctx, lp.nnz)), dim3(256), 0, ctx->stream(), lp, lm,
+                        ld, lm.nnz != 0, has_dm, dm_masks_dp, (const u32*)rowbits.p, (u32)out_nrows,
+                        (u32)out_ncols, kp.kb.p, kp.ks.p, clip));
         FGPU_TRY(scan_u32(ctx, kp.ks.p, kp.ks.p, ((u64)(lp.nnz + 63) >> 6) + 1, nullptr));
     }
     DevBuf<u32> orp;
     FGPU_TRY(orp.alloc(ctx, out_nrows + 1));
-    hipLaunchKernelGGL(merge_rowlen_kernel, dim3(cdiv(out_nrows + 1, 256)), dim3(256), 0, ctx->stream(), lm, lp, has_dp,
-                       (const u32*)rowbits.p, (const u64*)km.kb.p, (const u32*)km.ks.p, (const u64*)kp.kb.p,
-                       (const u32*)kp.ks.p, (u32)out_nrows, orp.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(merge_rowlen_kernel, dim3(cdiv(out_nrows + 1, 256)), dim3(256), 0, ctx->stream(), lm, lp, has_dp,
+                    (const u32*)rowbits.p, (const u64*)km.kb.p, (const u32*)km.ks.p, (const u64*)kp.kb.p,
+                    (const u32*)kp.ks.p, (u32)out_nrows, orp.p));
     FGPU_TRY(scan_u32(ctx, orp.p, orp.p, out_nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, orp.p + out_nrows, &nnz));
     fgpu_mat* o = nullptr;
     FGPU_TRY(mat_alloc(ctx, &o, out_nrows, out_ncols, nnz, with_vals, 0, false));
-    hipError_t e = hipMemcpyAsync(o->rowptr, orp.p, (out_nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice,
-                                  ctx->stream());
     // shifted-copy scatter (above) for the common shape: same dims, a plain CSR base, every dp entry kept
     const bool by_items = ctx->opt.merge_items && !clip && ctx->opt.merge_mode != 2 && !dm_masks_dp && !m->is_hyper() && lm.nnz && nnz;
-    DevBuf<u32> Q, ibase;
-    if (e == hipSuccess && by_items) {
-        const u32 nQ = has_dp ? lp.nnz : 0u;
-        const u32 nitems = cdiv(lm.nnz, MS_ITEM);
-        fgpu_info ai = Q.alloc(ctx, (size_t)nQ + 64);
-        if (ai == FGPU_OK) ai = ibase.alloc(ctx, (size_t)nitems + 1);
-        if (ai != FGPU_OK) { mat_release(o); return ai; }
-        if (nQ) hipLaunchKernelGGL(merge_qpos_kernel, dim3(entry_grid(ctx, nQ)), dim3(256), 0, ctx->stream(), lp, lm, Q.p);
-        hipLaunchKernelGGL(merge_ibase_kernel, dim3(cdiv(nitems, 256)), dim3(256), 0, ctx->stream(), (const u32*)Q.p, nQ, nitems, ibase.p);
-        u32 grid = cdiv(nitems, 4);
-        if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(merge_copy_items_kernel, dim3(grid), dim3(256), 0, ctx->stream(), lm, (const u64*)km.kb.p, (const u32*)km.ks.p,
-                           (const u32*)Q.p, nQ, (const u32*)ibase.p, nitems, o->colidx, o->vals);
-        if (nQ) hipLaunchKernelGGL(merge_dp_place_kernel, dim3(cdiv(nQ, 256)), dim3(256), 0, ctx->stream(), lp, (const u32*)Q.p,
-                                   (const u64*)km.kb.p, (const u32*)km.ks.p, o->colidx, o->vals);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !by_items && lm.nnz && nnz) {
-        hipLaunchKernelGGL(merge_scatter_kernel<true>, dim3(entry_grid(ctx, lm.nnz)), dim3(256), 0, ctx->stream(), lm,
-                           lp, has_dp, (const u32*)rowbits.p, (const u64*)km.kb.p, (const u32*)km.ks.p,
-                           (const u64*)kp.kb.p, (const u32*)kp.ks.p, (const u32*)o->rowptr, o->colidx, o->vals, clip,
-                           (const u32*)rowbits_dp.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !by_items && has_dp && nnz) {
-        hipLaunchKernelGGL(merge_scatter_kernel<false>, dim3(entry_grid(ctx, lp.nnz)), dim3(256), 0, ctx->stream(), lp,
-                           lm, lm.nnz != 0, (const u32*)rowbits.p, (const u64*)kp.kb.p, (const u32*)kp.ks.p,
-                           (const u64*)km.kb.p, (const u32*)km.ks.p, (const u32*)o->rowptr, o->colidx, o->vals, clip,
-                           (const u32*)nullptr);
-        e = hipGetLastError();
-    }
-    // the scratch buffers above go back to the pool when this returns: the kernels reading them must be done
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());
-    if (e != hipSuccess) {
-        set_error("merge failed: %s", hipGetErrorString(e));
+    auto fill = [&]() -> fgpu_info {
+        FGPU_HIP(hipMemcpyAsync(o->rowptr, orp.p, (out_nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
+        DevBuf<u32> Q, ibase;
+        if (by_items) {
+            const u32 nQ = has_dp ? lp.nnz : 0u;
+            const u32 nitems = cdiv(lm.nnz, MS_ITEM);
+            FGPU_TRY(Q.alloc(ctx, (size_t)nQ + 64));
+            FGPU_TRY(ibase.alloc(ctx, (size_t)nitems + 1));
+            if (nQ) FGPU_TRY(launch(merge_qpos_kernel, dim3(entry_grid(ctx, nQ)), dim3(256), 0, ctx->stream(), lp, lm, Q.p));
+            FGPU_TRY(launch(merge_ibase_kernel, dim3(cdiv(nitems, 256)), dim3(256), 0, ctx->stream(), (const u32*)Q.p, nQ, nitems,
+                            ibase.p));
+            u32 grid = cdiv(nitems, 4);
+            if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
+            FGPU_TRY(launch(merge_copy_items_kernel, dim3(grid), dim3(256), 0, ctx->stream(), lm, (const u64*)km.kb.p,
+                            (const u32*)km.ks.p, (const u32*)Q.p, nQ, (const u32*)ibase.p, nitems, o->colidx, o->vals));
+            if (nQ)
+                FGPU_TRY(launch(merge_dp_place_kernel, dim3(cdiv(nQ, 256)), dim3(256), 0, ctx->stream(), lp, (const u32*)Q.p,
+                                (const u64*)km.kb.p, (const u32*)km.ks.p, o->colidx, o->vals));
+        }
+        if (!by_items && lm.nnz && nnz)
+            FGPU_TRY(launch(merge_scatter_kernel<true>, dim3(entry_grid(ctx, lm.nnz)), dim3(256), 0, ctx->stream(), lm, lp, has_dp,
+                            (const u32*)rowbits.p, (const u64*)km.kb.p, (const u32*)km.ks.p, (const u64*)kp.kb.p,
+                            (const u32*)kp.ks.p, (const u32*)o->rowptr, o->colidx, o->vals, clip, (const u32*)rowbits_dp.p));
+        if (!by_items && has_dp && nnz)
+            FGPU_TRY(launch(merge_scatter_kernel<false>, dim3(entry_grid(ctx, lp.nnz)), dim3(256), 0, ctx->stream(), lp, lm,
+                            lm.nnz != 0, (const u32*)rowbits.p, (const u64*)kp.kb.p, (const u32*)kp.ks.p, (const u64*)km.kb.p,
+                            (const u32*)km.ks.p, (const u32*)o->rowptr, o->colidx, o->vals, clip, (const u32*)nullptr));
+        // the scratch buffers above go back to the pool when this returns: the kernels reading them must be done
+        return fgpu_sync(ctx);
+    };
+    const fgpu_info fi = fill();
+    if (fi != FGPU_OK) {
         mat_release(o);
-        return FGPU_DEVICE;
+        return fi;
     }
     // hub list / max degree are computed when a BFS plan first needs them (mat_ensure_finalized)
     *out = o;
@@ -592,19 +580,16 @@ fgpu_info mat_from_device_coo_vals(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64
         if (a->nnz == 0) break;
         DevBuf<u32> win;
         if ((i = win.alloc(ctx, a->nnz)) != FGPU_OK) break;
-        hipError_t e = hipMemsetAsync(win.p, 0, a->nnz * sizeof(u32), ctx->stream());
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(coo_winner_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), rows, cols, n,
-                               (const u32*)a->rowptr, (const u32*)a->colidx, win.p);
-            hipLaunchKernelGGL(coo_take_winner_kernel, dim3(cdiv(a->nnz, 256)), dim3(256), 0, ctx->stream(),
-                               (const u32*)win.p, vals, (u32)a->nnz, a->vals);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());  // `win` returns to the pool
-        if (e != hipSuccess) {
+        if (hipError_t e = hipMemsetAsync(win.p, 0, a->nnz * sizeof(u32), ctx->stream())) {
             set_error("valued COO build failed: %s", hipGetErrorString(e));
             i = FGPU_DEVICE;
+            break;
         }
+        if ((i = launch(coo_winner_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), rows, cols, n, (const u32*)a->rowptr,
+                        (const u32*)a->colidx, win.p)) != FGPU_OK) break;
+        if ((i = launch(coo_take_winner_kernel, dim3(cdiv(a->nnz, 256)), dim3(256), 0, ctx->stream(), (const u32*)win.p, vals,
+                        (u32)a->nnz, a->vals)) != FGPU_OK) break;
+        i = fgpu_sync(ctx);   // `win` returns to the pool
     } while (0);
     if (i != FGPU_OK) { mat_release(a); return i; }
     *out = a;
@@ -643,14 +628,9 @@ fgpu_info mat_transpose_vals(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a) {
         if (a->nnz == 0) break;
         Layer la{};
         if ((i = layer_of(ctx, a, la)) != FGPU_OK) break;
-        hipLaunchKernelGGL(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la,
-                           (const u32*)t->rowptr, (const u32*)t->colidx, t->vals);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream());
-        if (e != hipSuccess) {
-            set_error("valued transpose failed: %s", hipGetErrorString(e));
-            i = FGPU_DEVICE;
-        }
+        if ((i = launch(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la, (const u32*)t->rowptr,
+                        (const u32*)t->colidx, t->vals)) != FGPU_OK) break;
+        i = fgpu_sync(ctx);
     } while (0);
     if (i != FGPU_OK) { mat_release(t); return i; }
     *out = t;

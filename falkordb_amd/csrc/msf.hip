@@ -287,13 +287,12 @@ static fgpu_info msf_scan(fgpu_ctx* ctx, const MsfState& s) {
     u32 grid = cdiv(cdiv(n, 64), 4);
     if (grid > (u32)ctx->cus * 8) grid = (u32)ctx->cus * 8;
     u64* best = WPASS ? s.best_w : s.best_e;
-    hipLaunchKernelGGL((msf_rows_kernel<VALUED, WPASS>), dim3(grid), dim3(256), 0, ctx->stream(), view_of(W), (const u64*)W->vals,
-                       s.act, (const u32*)s.parent, n, s.done, s.rowmin, (const u64*)s.best_w, best, s.entries);
+    FGPU_TRY(launch((msf_rows_kernel<VALUED, WPASS>), dim3(grid), dim3(256), 0, ctx->stream(), view_of(W), (const u64*)W->vals,
+                    s.act, (const u32*)s.parent, n, s.done, s.rowmin, (const u64*)s.best_w, best, s.entries));
     if (W->n_hub_chunks)
-        hipLaunchKernelGGL((msf_hubs_kernel<VALUED, WPASS>), dim3(hub_grid(ctx, W)), dim3(256), 0, ctx->stream(),
-                           (const u32*)W->hub_chunks, W->n_hub_chunks, (const u32*)W->colidx, (const u64*)W->vals, s.act,
-                           (const u32*)s.parent, s.cdone, s.chunkmin, (const u64*)s.best_w, best, s.entries);
-    FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch((msf_hubs_kernel<VALUED, WPASS>), dim3(hub_grid(ctx, W)), dim3(256), 0, ctx->stream(),
+                        (const u32*)W->hub_chunks, W->n_hub_chunks, (const u32*)W->colidx, (const u64*)W->vals, s.act,
+                        (const u32*)s.parent, s.cdone, s.chunkmin, (const u64*)s.best_w, best, s.entries));
     return FGPU_OK;
 }
 
@@ -365,8 +364,7 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
             FGPU_TRY((msf_scan<false, false>(ctx, s)));
         }
         FGPU_HIP(hipMemsetAsync(cnt.p + 1, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(msf_hook_kernel, dim3(grid), dim3(256), 0, st, parent.p, s.best_w, s.best_e, edge_of.p, n, cnt.p + 1);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(msf_hook_kernel, dim3(grid), dim3(256), 0, st, parent.p, s.best_w, s.best_e, edge_of.p, n, cnt.p + 1));
         u32 w[4];   // entries read so far, roots that chose a pair: one round trip
         FGPU_TRY(read_words(ctx, (const u32*)cnt.p, 4, w));
         const u64 read = (u64)w[0] | ((u64)w[1] << 32), chosen = (u64)w[2] | ((u64)w[3] << 32);
@@ -380,9 +378,8 @@ extern "C" fgpu_info fgpu_msf(fgpu_ctx* ctx, const fgpu_mat* W, const uint64_t* 
     FGPU_TRY(wide.alloc(ctx, n));
     FGPU_TRY(rows.alloc(ctx, n));
     FGPU_TRY(cols.alloc(ctx, n));
-    hipLaunchKernelGGL(msf_finish_kernel, dim3(grid), dim3(256), 0, st, (const u32*)parent.p, (const u64*)act.p, n,
-                       (const u64*)edge_of.p, wide.p, rows.p, cols.p, cnt.p + 2);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(msf_finish_kernel, dim3(grid), dim3(256), 0, st, (const u32*)parent.p, (const u64*)act.p, n,
+                    (const u64*)edge_of.p, wide.p, rows.p, cols.p, cnt.p + 2));
     if (component) FGPU_TRY(ctx->d2h(component, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when component[] is pinned
     unsigned long long h[4];
     FGPU_TRY(ctx->d2h(h, cnt.p, sizeof(h)));

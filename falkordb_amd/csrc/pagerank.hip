@@ -314,18 +314,16 @@ static fgpu_info pr_parts_build(fgpu_ctx* ctx, const fgpu_mat* At, const PrParts
     const size_t words = (size_t)PR_NPARTS * (n + 1);
     fgpu_info i = ctx->dev_alloc((void**)&pp->prp, (words + 1) * sizeof(u32));
     if (i == FGPU_OK) i = ctx->dev_alloc((void**)&pp->pcol, (size_t)(At->nnz ? At->nnz : 1) * sizeof(u32));
-    if (i == FGPU_OK) {
-        hipLaunchKernelGGL(pr_part_count_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, pp->prp);
-        if (hipGetLastError() != hipSuccess) i = FGPU_DEVICE;
-    }
+    if (i == FGPU_OK)
+        i = launch(pr_part_count_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, pp->prp);
     // one exclusive scan over the range-major counts IS the layout: range p's rows follow range p - 1's (the extra slot per
     // range holds 0, so prp[p][n] = prp[p + 1][0])
     if (i == FGPU_OK) i = scan_u32(ctx, pp->prp, pp->prp, words, nullptr);
     if (i == FGPU_OK && At->nnz) {
         u32 grid = cdiv(n, 4);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(pr_part_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, (const u32*)pp->prp, pp->pcol);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream()) != hipSuccess) i = FGPU_DEVICE;
+        i = launch(pr_part_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, (const u32*)pp->prp, pp->pcol);
+        if (i == FGPU_OK) i = fgpu_sync(ctx);
     }
     if (i != FGPU_OK) { pr_parts_release(ctx, pp); if (i == FGPU_DEVICE) set_error("pagerank: column-range layout build failed"); return i; }
     At->pr_parts = pp;
@@ -491,9 +489,8 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
     if (active_bitmap) {
         FGPU_TRY(upload_active(ctx, act, active_bitmap, n, &n_act));
         FGPU_TRY(deg.alloc(ctx, n));
-        hipLaunchKernelGGL(pr_degree_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p, n,
-                           deg.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(pr_degree_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p, n,
+                        deg.p));
     }
     FGPU_TRY(r.alloc(ctx, n));
     FGPU_TRY(t.alloc(ctx, n));
@@ -516,9 +513,8 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
         return FGPU_OK;
     }
     const float fn = (float)n_act;
-    hipLaunchKernelGGL(pr_init_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p,
-                       (const u32*)deg.p, n, 1.0f / fn, damping, r.p, d.p, sink.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(pr_init_kernel, dim3(nb), dim3(256), 0, ctx->stream(), view_of(A), (const u64*)act.p,
+                    (const u32*)deg.p, n, 1.0f / fn, damping, r.p, d.p, sink.p));
     const float teleport0 = (1.0f - damping) / fn, damp_over_n = damping / fn;
     const CsrView vat = view_of(At);
     // Iterations are enqueued blind, PR_BATCH at a time; every kernel returns at once when the device-side `stop` is up,
@@ -539,12 +535,11 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
     if (timing) for (auto& e : ev) (void)hipEventCreate(&e);
     if (parts && itermax > 0 && !stopped) {
         // the range form prepares iteration i + 1 inside iteration i's combine pass: only the first w / teleport come from here
-        hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)rp,
-                           (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
-                           (const int*)state.p);
-        hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
-                           teleport0, damp_over_n, scal.p, state.p, 0, 0.0f);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)rp,
+                        (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
+                        (const int*)state.p));
+        FGPU_TRY(launch(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
+                        teleport0, damp_over_n, scal.p, state.p, 0, 0.0f));
     }
     while (it < itermax && !stopped) {
         const int batch = timing ? 1 : (itermax - it < PR_BATCH ? itermax - it : PR_BATCH);
@@ -554,44 +549,42 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
             if (parts) {
                 if (timing) (void)hipEventRecord(ev[1], ctx->stream());
                 const u32 nblk = cdiv(n, PR_RB);
-                hipLaunchKernelGGL(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp,
-                                   (const u32*)parts->pcol, n, (const float*)w.p, ppart.p, (const int*)state.p);
+                FGPU_TRY(launch(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp,
+                                (const u32*)parts->pcol, n, (const float*)w.p, ppart.p, (const int*)state.p));
                 if (timing) (void)hipEventRecord(ev[2], ctx->stream());
-                hipLaunchKernelGGL(pr_part_combine_kernel, dim3(cgrid), dim3(256), 0, ctx->stream(), (const double*)ppart.p,
-                                   (const u64*)act.p, n, (const float*)scal.p, (const float*)tp, (const float*)d.p,
-                                   (const unsigned char*)sink.p, rp, w.p, part2.p, part.p, (const int*)state.p);
+                FGPU_TRY(launch(pr_part_combine_kernel, dim3(cgrid), dim3(256), 0, ctx->stream(), (const double*)ppart.p,
+                                (const u64*)act.p, n, (const float*)scal.p, (const float*)tp, (const float*)d.p,
+                                (const unsigned char*)sink.p, rp, w.p, part2.p, part.p, (const int*)state.p));
                 if (timing) (void)hipEventRecord(ev[3], ctx->stream());
-                hipLaunchKernelGGL(pr_reduce2_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p,
-                                   (const double*)part.p, cgrid, teleport0, damp_over_n, scal.p, state.p, tol);
+                FGPU_TRY(launch(pr_reduce2_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p,
+                                (const double*)part.p, cgrid, teleport0, damp_over_n, scal.p, state.p, tol));
                 if (timing) (void)hipEventRecord(ev[4], ctx->stream());
-                FGPU_HIP(hipGetLastError());
                 continue;
             }
-            hipLaunchKernelGGL(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)tp,
-                               (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
-                               (const int*)state.p);
-            hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
-                               teleport0, damp_over_n, scal.p, state.p, 0, 0.0f);
+            FGPU_TRY(launch(pr_prep_kernel, dim3(nb), dim3(256), 0, ctx->stream(), (const float*)tp,
+                            (const float*)d.p, (const unsigned char*)sink.p, (const u64*)act.p, n, w.p, part.p,
+                            (const int*)state.p));
+            FGPU_TRY(launch(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part.p, nb,
+                            teleport0, damp_over_n, scal.p, state.p, 0, 0.0f));
             if (timing) (void)hipEventRecord(ev[1], ctx->stream());
-            hipLaunchKernelGGL(pr_spmv_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vat, (const u64*)act.p, n,
-                               (const float*)w.p, (const float*)scal.p, (const float*)tp, rp, part2.p + 1,
-                               (const int*)state.p);
+            FGPU_TRY(launch(pr_spmv_kernel, dim3(grid), dim3(256), 0, ctx->stream(), vat, (const u64*)act.p, n,
+                            (const float*)w.p, (const float*)scal.p, (const float*)tp, rp, part2.p + 1,
+                            (const int*)state.p));
             if (timing) (void)hipEventRecord(ev[2], ctx->stream());
             if (At->n_hub_chunks) {
-                hipLaunchKernelGGL(pr_hub_kernel, dim3(hub_grid(ctx, At)), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
-                                   At->n_hub_chunks, (const u32*)At->colidx, (const u64*)act.p, (const float*)w.p, hpart.p,
-                                   (const int*)state.p);
-                hipLaunchKernelGGL(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
-                                   At->n_hub_chunks, (const u32*)At->rowptr, (const u64*)act.p, (const double*)hpart.p,
-                                   (const float*)scal.p, (const float*)tp, rp, part2.p, (const int*)state.p);
+                FGPU_TRY(launch(pr_hub_kernel, dim3(hub_grid(ctx, At)), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                                At->n_hub_chunks, (const u32*)At->colidx, (const u64*)act.p, (const float*)w.p, hpart.p,
+                                (const int*)state.p));
+                FGPU_TRY(launch(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                                At->n_hub_chunks, (const u32*)At->rowptr, (const u64*)act.p, (const double*)hpart.p,
+                                (const float*)scal.p, (const float*)tp, rp, part2.p, (const int*)state.p));
             } else {
                 FGPU_HIP(hipMemsetAsync(part2.p, 0, sizeof(double), ctx->stream()));
             }
             if (timing) (void)hipEventRecord(ev[3], ctx->stream());
-            hipLaunchKernelGGL(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p, grid + 1,
-                               0.0f, 1.0f, scal.p + 1, state.p, 1, tol);
+            FGPU_TRY(launch(pr_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const double*)part2.p, grid + 1,
+                            0.0f, 1.0f, scal.p + 1, state.p, 1, tol));
             if (timing) (void)hipEventRecord(ev[4], ctx->stream());
-            FGPU_HIP(hipGetLastError());
         }
         int hstate[2] = {0, 0};
         if (timing) {   // (the events below must have completed)

@@ -104,20 +104,17 @@ static fgpu_info scan_impl(fgpu_ctx* ctx, const Tin* in, Tout* out, u64 n, Tout*
     }
     u32 nblocks = cdiv(n, SCAN_TILE);
     if (nblocks == 1) {
-        hipLaunchKernelGGL((scan_apply_kernel<Tin, Tout>), dim3(1), dim3(SCAN_THREADS), 0, ctx->stream(), in, out,
-                           n, (const Tout*)nullptr, total_dev);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch((scan_apply_kernel<Tin, Tout>), dim3(1), dim3(SCAN_THREADS), 0, ctx->stream(), in, out,
+                        n, (const Tout*)nullptr, total_dev));
         return FGPU_OK;
     }
     DevBuf<Tout> sums;
     FGPU_TRY(sums.alloc(ctx, nblocks));
-    hipLaunchKernelGGL((scan_reduce_kernel<Tin, Tout>), dim3(nblocks), dim3(SCAN_THREADS), 0, ctx->stream(), in,
-                       n, sums.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch((scan_reduce_kernel<Tin, Tout>), dim3(nblocks), dim3(SCAN_THREADS), 0, ctx->stream(), in,
+                    n, sums.p));
     FGPU_TRY((scan_impl<Tout, Tout>(ctx, sums.p, sums.p, nblocks, (Tout*)nullptr)));
-    hipLaunchKernelGGL((scan_apply_kernel<Tin, Tout>), dim3(nblocks), dim3(SCAN_THREADS), 0, ctx->stream(), in,
-                       out, n, (const Tout*)sums.p, total_dev);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch((scan_apply_kernel<Tin, Tout>), dim3(nblocks), dim3(SCAN_THREADS), 0, ctx->stream(), in,
+                    out, n, (const Tout*)sums.p, total_dev));
     return FGPU_OK;
 }
 
@@ -307,17 +304,15 @@ fgpu_info segsort_unique(fgpu_ctx* ctx, u32* data, const u64* off, u32 nseg, u32
     // a wavefront per segment: 2^26 rows (RMAT-26) would be 2^32 threads in one grid, past what a launch accepts
     for (u64 base = 0; base < nseg; base += (1ull << 24)) {
         const u32 part = (u32)((nseg - base < (1ull << 24)) ? nseg - base : (1ull << 24));
-        hipLaunchKernelGGL(segsort_wave_kernel, dim3(cdiv(part, 4)), dim3(256), 0, ctx->stream(), data, off, nseg, cnt,
-                           mid.p, big.p, counts.p, dirty, (u32)base);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(segsort_wave_kernel, dim3(cdiv(part, 4)), dim3(256), 0, ctx->stream(), data, off, nseg, cnt,
+                        mid.p, big.p, counts.p, dirty, (u32)base));
     }
     // mid segments: grid-stride over the device-side list, no host round trip
     {
         u32 grid = ctx->cus * 8;
         if (grid > nseg) grid = nseg;
-        hipLaunchKernelGGL(segsort_block_kernel, dim3(grid), dim3(256), 0, ctx->stream(), data, off, mid.p, counts.p,
-                           cnt);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(segsort_block_kernel, dim3(grid), dim3(256), 0, ctx->stream(), data, off, mid.p, counts.p,
+                        cnt));
     }
     // big segments need their count on the host to size the bitmap workspace
     u32 nbig = 0;
@@ -334,12 +329,10 @@ fgpu_info segsort_unique(fgpu_ctx* ctx, u32* data, const u64* off, u32 nseg, u32
         FGPU_HIP(hipMemsetAsync(bitmaps.p, 0, (size_t)slots * words * sizeof(u32), ctx->stream()));
         for (u32 first = 0; first < nbig; first += slots) {
             u32 ns = (nbig - first < slots) ? (nbig - first) : slots;
-            hipLaunchKernelGGL(segsort_big_scatter_kernel, dim3(64, ns), dim3(256), 0, ctx->stream(), data, off,
-                               big.p, first, ns, bitmaps.p, words);
-            FGPU_HIP(hipGetLastError());
-            hipLaunchKernelGGL(segsort_big_emit_kernel, dim3(ns), dim3(1024), 0, ctx->stream(), data, off, big.p,
-                               first, bitmaps.p, words, cnt);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(segsort_big_scatter_kernel, dim3(64, ns), dim3(256), 0, ctx->stream(), data, off,
+                            big.p, first, ns, bitmaps.p, words));
+            FGPU_TRY(launch(segsort_big_emit_kernel, dim3(ns), dim3(1024), 0, ctx->stream(), data, off, big.p,
+                            first, bitmaps.p, words, cnt));
         }
     }
     return FGPU_OK;
@@ -371,9 +364,8 @@ fgpu_info compact_segments(fgpu_ctx* ctx, const u32* data, const u64* off, const
     u32 grid = cdiv(nseg, 4);
     u32 cap = ctx->cus * 16;
     if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(compact_segments_kernel, dim3(grid), dim3(256), 0, ctx->stream(), data, off, rowptr, nseg,
-                       col_out);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(compact_segments_kernel, dim3(grid), dim3(256), 0, ctx->stream(), data, off, rowptr, nseg,
+                    col_out));
     return FGPU_OK;
 }
 

@@ -134,9 +134,8 @@ static fgpu_info mxm_flops(fgpu_ctx* ctx, const fgpu_mat* F, const fgpu_mat* B, 
     FGPU_TRY(deg.alloc(ctx, (size_t)nnzf + 1));
     FGPU_TRY(eoff.alloc(ctx, (size_t)nnzf + 1));
     FGPU_TRY(tot.alloc(ctx, 1));
-    hipLaunchKernelGGL(entry_deg_kernel, dim3(cdiv((u64)nnzf + 1, 256)), dim3(256), 0, ctx->stream(), view_of(F),
-                       view_of(B), nnzf, deg.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(entry_deg_kernel, dim3(cdiv((u64)nnzf + 1, 256)), dim3(256), 0, ctx->stream(), view_of(F),
+                    view_of(B), nnzf, deg.p));
     FGPU_TRY(scan_u32_to_u64(ctx, deg.p, eoff.p, (u64)nnzf + 1, tot.p));
     return read_u64(ctx, tot.p, T);
 }
@@ -182,16 +181,14 @@ fgpu_info mxm_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* F, const fgp
     FGPU_TRY(deg.alloc(ctx, (size_t)nnzf + 1));
     FGPU_TRY(eoff.alloc(ctx, (size_t)nnzf + 1));
     FGPU_TRY(tot.alloc(ctx, 1));
-    hipLaunchKernelGGL(entry_deg_kernel, dim3(cdiv((u64)nnzf + 1, 256)), dim3(256), 0, ctx->stream(), view_of(F),
-                       view_of(B), nnzf, deg.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(entry_deg_kernel, dim3(cdiv((u64)nnzf + 1, 256)), dim3(256), 0, ctx->stream(), view_of(F),
+                    view_of(B), nnzf, deg.p));
     FGPU_TRY(scan_u32_to_u64(ctx, deg.p, eoff.p, (u64)nnzf + 1, tot.p));
     FGPU_TRY(roff.alloc(ctx, k + 1));
     FGPU_TRY(maxlen.alloc(ctx, 1));
     FGPU_HIP(hipMemsetAsync(maxlen.p, 0, sizeof(u32), ctx->stream()));
-    hipLaunchKernelGGL(gather_u64_kernel, dim3(cdiv(k + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)eoff.p,
-                       (const u32*)frp.p, (u32)k, roff.p, maxlen.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(gather_u64_kernel, dim3(cdiv(k + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)eoff.p,
+                    (const u32*)frp.p, (u32)k, roff.p, maxlen.p));
     u64 T = 0;
     FGPU_TRY(read_u64(ctx, tot.p, &T));
     u32 ml = 0;
@@ -207,15 +204,13 @@ fgpu_info mxm_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* F, const fgp
         ProfScope ps(ctx, "gather_rows_kernel", 12 * (u64)nnzf + 8 * T);   // F entry + B row-pointer pair, B row read + written
         u32 grid = cdiv(nnzf, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(F), view_of(B), nnzf,
-                           (const u64*)eoff.p, tmp.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(gather_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(F), view_of(B), nnzf,
+                        (const u64*)eoff.p, tmp.p));
     }
     FGPU_TRY(cnt.alloc(ctx, k + 1));
     if (ml <= 1) {
-        hipLaunchKernelGGL(seg_len_kernel, dim3(cdiv(k + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)roff.p,
-                           (u32)k, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(seg_len_kernel, dim3(cdiv(k + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)roff.p,
+                        (u32)k, cnt.p));
     } else {
         FGPU_HIP(hipMemsetAsync(cnt.p, 0, (k + 1) * sizeof(u32), ctx->stream()));
         ProfScope ps(ctx, "segsort_unique (product rows)", 8 * T);
@@ -276,9 +271,8 @@ static fgpu_info filter_by_bitmap(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat*
     u32 grid = cdiv(nrows ? nrows : 1, 4);
     if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
     if (nrows && c->nnz) {
-        hipLaunchKernelGGL(bitmap_filter_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c), bitmap_dev,
-                           (u32)nrows, tmp.p, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(bitmap_filter_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c), bitmap_dev,
+                        (u32)nrows, tmp.p, cnt.p));
     }
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
@@ -288,9 +282,8 @@ static fgpu_info filter_by_bitmap(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat*
     FGPU_TRY(mat_alloc(ctx, &o, nrows, c->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
     if (nnz) {
-        hipLaunchKernelGGL(compact_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)tmp.p,
-                           (const u32*)c->rowptr, (const u32*)o->rowptr, (u32)nrows, o->colidx);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(compact_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)tmp.p,
+                        (const u32*)c->rowptr, (const u32*)o->rowptr, (u32)nrows, o->colidx));
     }
     *out = o;
     return FGPU_OK;
@@ -442,9 +435,8 @@ static fgpu_info first_hop_rows(fgpu_ctx* ctx, const fgpu_mat* f, const fgpu_mat
     FGPU_TRY(rp.alloc(ctx, (size_t)k + 1));
     FGPU_TRY(tot.alloc(ctx, 1));
     FGPU_TRY(tn.alloc(ctx, 64 * 16));
-    hipLaunchKernelGGL(first_hop_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream(), view_of(f), view_of(m), k, rp.p, tot.p,
-                       (unsigned long long*)tn.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(first_hop_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream(), view_of(f), view_of(m), k, rp.p, tot.p,
+                    (unsigned long long*)tn.p));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, tot.p, &nnz));
     *T0 = nnz;
@@ -455,21 +447,20 @@ static fgpu_info first_hop_rows(fgpu_ctx* ctx, const fgpu_mat* f, const fgpu_mat
     {
         u32 grid = cdiv(nnz ? nnz : 1, 256 * 4);
         if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
-        hipLaunchKernelGGL(first_hop_copy_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), view_of(f), view_of(m), k,
-                           (const u32*)rp.p, nnz, c->rowptr, c->colidx, sum_next ? (const u32*)next->rowptr : (const u32*)nullptr,
-                           sum_next ? (u32)next->nrows : 0u, sum_next ? (unsigned long long*)tn.p : (unsigned long long*)nullptr);
-        if (hipGetLastError() != hipSuccess) i = FGPU_DEVICE;
+        i = launch(first_hop_copy_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), view_of(f), view_of(m), k,
+                   (const u32*)rp.p, nnz, c->rowptr, c->colidx, sum_next ? (const u32*)next->rowptr : (const u32*)nullptr,
+                   sum_next ? (u32)next->nrows : 0u, sum_next ? (unsigned long long*)tn.p : (unsigned long long*)nullptr);
     }
     if (i == FGPU_OK && sum_next) {
         u32* pub = nullptr;
         u32 seq = 0;
         const bool mapped = pub_begin(ctx, &pub, &seq);
-        hipLaunchKernelGGL(first_hop_fold_kernel, dim3(1), dim3(64), 0, ctx->stream(), (unsigned long long*)tn.p, mapped ? pub : (u32*)nullptr, seq);
-        if (mapped) {
+        i = launch(first_hop_fold_kernel, dim3(1), dim3(64), 0, ctx->stream(), (unsigned long long*)tn.p, mapped ? pub : (u32*)nullptr, seq);
+        if (i == FGPU_OK && mapped) {
             u32 w[2] = {0, 0};
-            i = hipGetLastError() == hipSuccess ? pub_wait(ctx, seq, 2, w) : FGPU_DEVICE;
+            i = pub_wait(ctx, seq, 2, w);
             *Tnext = (u64)w[0] | ((u64)w[1] << 32);
-        } else {
+        } else if (i == FGPU_OK) {
             i = read_u64(ctx, tn.p + 1, Tnext);
         }
         *have_next = i == FGPU_OK;
@@ -651,8 +642,7 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
         return v;
     };
     const CsrView vm = view_of(m), vdp = view_or_empty(dp), vdm = view_or_empty(dm), vf = view_of(f);
-    hipLaunchKernelGGL(fhd_scan_kernel, dim3(1), dim3(1024), 0, st, vf, vm, vdp, k, cm.p, cp.p, tot.p, (unsigned long long*)tn.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(fhd_scan_kernel, dim3(1), dim3(1024), 0, st, vf, vm, vdp, k, cm.p, cp.p, tot.p, (unsigned long long*)tn.p));
     u32 w2[2] = {0, 0};
     FGPU_TRY(read_words(ctx, tot.p, 2, w2));
     const u32 ncm = w2[0], ncp = w2[1];
@@ -664,10 +654,9 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
     if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
     FGPU_HIP(hipMemsetAsync(keepm.p + ncm, 0, sizeof(u32), st));
     FGPU_HIP(hipMemsetAsync(keepp.p + ncp, 0, sizeof(u32), st));
-    hipLaunchKernelGGL(fhd_cand_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p, (const u32*)cp.p,
-                       ncm, ncp, keepm.p, keepp.p, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr, (u32*)nullptr,
-                       (const u32*)nullptr, 0u, (unsigned long long*)nullptr);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(fhd_cand_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p, (const u32*)cp.p,
+                    ncm, ncp, keepm.p, keepp.p, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr, (u32*)nullptr,
+                    (const u32*)nullptr, 0u, (unsigned long long*)nullptr));
     FGPU_TRY(scan_u32(ctx, keepm.p, pm.p, (u64)ncm + 1, nullptr));
     FGPU_TRY(scan_u32(ctx, keepp.p, pp.p, (u64)ncp + 1, nullptr));
     DevBuf<u32> rp;
@@ -677,9 +666,8 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
         u32* pub = nullptr;
         u32 seq = 0;
         const bool mapped = pub_begin(ctx, &pub, &seq);
-        hipLaunchKernelGGL(fhd_rowptr_kernel, dim3(1), dim3(1024), 0, st, (const u32*)cm.p, (const u32*)cp.p, (const u32*)pm.p,
-                           (const u32*)pp.p, k, rp.p, mapped ? pub : (u32*)nullptr, seq, tot.p + 2);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(fhd_rowptr_kernel, dim3(1), dim3(1024), 0, st, (const u32*)cm.p, (const u32*)cp.p, (const u32*)pm.p,
+                        (const u32*)pp.p, k, rp.p, mapped ? pub : (u32*)nullptr, seq, tot.p + 2));
         if (mapped) { u32 w[1] = {0}; FGPU_TRY(pub_wait(ctx, seq, 1, w)); nnz = w[0]; }
         else FGPU_TRY(read_u32(ctx, tot.p + 2, &nnz));
     }
@@ -689,22 +677,21 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
     fgpu_info i = FGPU_OK;
     if (hipMemcpyAsync(c->rowptr, rp.p, ((size_t)k + 1) * sizeof(u32), hipMemcpyDeviceToDevice, st) != hipSuccess) i = FGPU_DEVICE;
     if (i == FGPU_OK && nnz) {
-        hipLaunchKernelGGL(fhd_cand_kernel<true>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p,
-                           (const u32*)cp.p, ncm, ncp, (u32*)nullptr, (u32*)nullptr, (const u32*)pm.p, (const u32*)pp.p, (const u32*)rp.p,
-                           c->colidx, sum_next ? (const u32*)next->rowptr : (const u32*)nullptr, sum_next ? (u32)next->nrows : 0u,
-                           sum_next ? (unsigned long long*)tn.p : (unsigned long long*)nullptr);
-        if (hipGetLastError() != hipSuccess) i = FGPU_DEVICE;
+        i = launch(fhd_cand_kernel<true>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p,
+                   (const u32*)cp.p, ncm, ncp, (u32*)nullptr, (u32*)nullptr, (const u32*)pm.p, (const u32*)pp.p, (const u32*)rp.p,
+                   c->colidx, sum_next ? (const u32*)next->rowptr : (const u32*)nullptr, sum_next ? (u32)next->nrows : 0u,
+                   sum_next ? (unsigned long long*)tn.p : (unsigned long long*)nullptr);
     }
     if (i == FGPU_OK && sum_next) {
         u32* pub = nullptr;
         u32 seq = 0;
         const bool mapped = pub_begin(ctx, &pub, &seq);
-        hipLaunchKernelGGL(first_hop_fold_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)tn.p, mapped ? pub : (u32*)nullptr, seq);
-        if (mapped) {
+        i = launch(first_hop_fold_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)tn.p, mapped ? pub : (u32*)nullptr, seq);
+        if (i == FGPU_OK && mapped) {
             u32 w[2] = {0, 0};
-            i = hipGetLastError() == hipSuccess ? pub_wait(ctx, seq, 2, w) : FGPU_DEVICE;
+            i = pub_wait(ctx, seq, 2, w);
             *Tnext = (u64)w[0] | ((u64)w[1] << 32);
-        } else {
+        } else if (i == FGPU_OK) {
             i = read_u64(ctx, tn.p + 1, Tnext);
         }
         *have_next = i == FGPU_OK;
@@ -785,15 +772,13 @@ static fgpu_info compact_source_rows(fgpu_ctx* ctx, const fgpu_mat* f, fgpu_mat*
     u32* pub = nullptr;
     u32 seq = 0;
     if (k <= 4095 && pub_begin(ctx, &pub, &seq)) {
-        hipLaunchKernelGGL(cr_rank_kernel, dim3(1), dim3(1024), 0, ctx->stream(), (const u32*)f->rowptr, k, rank.p, pub, seq);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(cr_rank_kernel, dim3(1), dim3(1024), 0, ctx->stream(), (const u32*)f->rowptr, k, rank.p, pub, seq));
         u32 w[1] = {0};
         FGPU_TRY(pub_wait(ctx, seq, 1, w));
         nlive = w[0];
     } else {
         FGPU_TRY(flag.alloc(ctx, (size_t)k + 1));
-        hipLaunchKernelGGL(cr_flag_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, k, flag.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(cr_flag_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, k, flag.p));
         FGPU_TRY(scan_u32(ctx, flag.p, rank.p, (u64)k + 1, nullptr));
         FGPU_TRY(read_u32(ctx, rank.p + k, &nlive));
     }
@@ -805,12 +790,8 @@ static fgpu_info compact_source_rows(fgpu_ctx* ctx, const fgpu_mat* f, fgpu_mat*
         u32 grid = cdiv((u64)k + 1, 256);
         const u32 want = cdiv(f->nnz, 256 * 8);
         if (grid < want) grid = want < (u32)ctx->cus * 4 ? want : (u32)ctx->cus * 4;
-        hipLaunchKernelGGL(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
-                           (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive);
-        if (hipGetLastError() != hipSuccess) {
-            set_error("compact_source_rows: device call failed");
-            i = FGPU_DEVICE;
-        }
+        i = launch(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
+                   (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive);
     }
     if (i != FGPU_OK) { mat_release(c); return i; }
     rank_out = std::move(rank);        // rank[i] = live rows before source row i, rank[k] = nlive: the way back (bp_to_csr)
@@ -1162,15 +1143,14 @@ static fgpu_info count_csr_result(fgpu_ctx* ctx, const fgpu_mat* r, const u32* r
     if (r->nnz / r->nrows >= 1024 && r->nnz < 0xFFFFFFFFull) {
         u32 grid = cdiv(r->nnz, 256);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(checksum_entries_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
-                           (u32)r->nrows, (u32)r->nnz, (unsigned long long*)acc.p, rowmap);
+        FGPU_TRY(launch(checksum_entries_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
+                        (u32)r->nrows, (u32)r->nnz, (unsigned long long*)acc.p, rowmap));
     } else {
         u32 grid = cdiv(r->nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-        hipLaunchKernelGGL(checksum_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
-                           (u32)r->nrows, (unsigned long long*)acc.p, rowmap);
+        FGPU_TRY(launch(checksum_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
+                        (u32)r->nrows, (unsigned long long*)acc.p, rowmap));
     }
-    FGPU_HIP(hipGetLastError());
     return read_u64(ctx, acc.p, checksum);
 }
 
@@ -1237,9 +1217,9 @@ static fgpu_info scan_one_pass(ScanJob& j, u32 p, u64* nnz, u64* cs, u64* fl) {
     DevBuf<u32> rm;
     FGPU_TRY(rm.alloc(ctx, k));
     FGPU_TRY(mat_alloc(ctx, &f, k, j.m[0]->nrows, k, false, 0, false));
-    hipLaunchKernelGGL(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, first, k, f->rowptr,
-                       f->colidx, rm.p);
-    if (hipGetLastError() != hipSuccess) { mat_release(f); set_error("expand scan: device call failed"); return FGPU_DEVICE; }
+    const fgpu_info li = launch(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, first, k,
+                                f->rowptr, f->colidx, rm.p);
+    if (li != FGPU_OK) { mat_release(f); return li; }
     ChainSources pre;
     pre.f = f;
     pre.rowmap = &rm;
@@ -1290,9 +1270,8 @@ static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
     FGPU_TRY(pos.alloc(ctx, (size_t)n + 1));
     FGPU_TRY(ctx->h2d(dids.p, ids.data(), (size_t)n * sizeof(u32)));
     const fgpu_mat* dp0 = dp && dp[0] && dp[0]->nnz ? dp[0] : nullptr;
-    hipLaunchKernelGGL(scan_live_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, n, view_of(m[0]),
-                       dp0 ? view_of(dp0) : view_of(m[0]), dp0 ? 1u : 0u, flag.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(scan_live_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, n, view_of(m[0]),
+                    dp0 ? view_of(dp0) : view_of(m[0]), dp0 ? 1u : 0u, flag.p));
     FGPU_TRY(scan_u32(ctx, flag.p, pos.p, (u64)n + 1, nullptr));
     u32 nlive = 0;
     FGPU_TRY(read_u32(ctx, pos.p + n, &nlive));
@@ -1303,9 +1282,8 @@ static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
     if (nlive == 0) return FGPU_OK;
     FGPU_TRY(lid.alloc(ctx, nlive));
     FGPU_TRY(lrow.alloc(ctx, nlive));
-    hipLaunchKernelGGL(scan_compact_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, (const u32*)flag.p,
-                       (const u32*)pos.p, n, lid.p, lrow.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(scan_compact_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, (const u32*)flag.p,
+                    (const u32*)pos.p, n, lid.p, lrow.p));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));           // the other lanes read the live list
     ScanJob j;
     j.ctx = ctx; j.lid = lid.p; j.lrow = lrow.p; j.nlive = nlive;
@@ -1403,9 +1381,8 @@ static fgpu_info expand_pairs_impl(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
         }
         if (any) {
             FGPU_TRY(ctx->h2d(pin.p, hp.data(), (size_t)k * sizeof(u32)));
-            hipLaunchKernelGGL(pairs_len_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, st, (const u32*)r->rowptr, (const u32*)r->colidx,
-                               (const u32*)pin.p, k, len.p, pos.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(pairs_len_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, st, (const u32*)r->rowptr, (const u32*)r->colidx,
+                            (const u32*)pin.p, k, len.p, pos.p));
             FGPU_TRY(scan_u32(ctx, len.p, newptr.p, (u64)k + 1, total.p));
             u32 t = 0;
             FGPU_TRY(read_u32(ctx, total.p, &t));
@@ -1426,13 +1403,14 @@ static fgpu_info expand_pairs_impl(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
         u32 grid = cdiv(n, 256 * 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
         if (!grid) grid = 1;
-#define PAIRS_FILL(RT, DT)                                                                                                     \
-        hipLaunchKernelGGL((pairs_fill_kernel<RT, DT>), dim3(grid), dim3(256), 0, st, rowptr, first, (const u32*)r->colidx, k, n, \
-                           (RT*)drow.p, (DT*)ddest.p)
-        if (row_bits == 16) { if (dest_bits == 64) PAIRS_FILL(uint16_t, u64); else PAIRS_FILL(uint16_t, u32); }
-        else { if (dest_bits == 64) PAIRS_FILL(u32, u64); else PAIRS_FILL(u32, u32); }
-#undef PAIRS_FILL
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(pick(row_bits == 16, [&](auto r16) {
+            return pick(dest_bits == 64, [&](auto d64) {
+                using RT = std::conditional_t<decltype(r16)::value, uint16_t, u32>;
+                using DT = std::conditional_t<decltype(d64)::value, u64, u32>;
+                return launch(pairs_fill_kernel<RT, DT>, dim3(grid), dim3(256), 0, st, rowptr, first, (const u32*)r->colidx, k, n,
+                              (RT*)drow.p, (DT*)ddest.p);
+            });
+        }));
     }
     void* hrow = ctx->result_alloc(n * rb);
     void* hdest = ctx->result_alloc(n * db);
@@ -1518,10 +1496,9 @@ fgpu_info fgpu_expand_probe(fgpu_ctx* ctx, const uint64_t* src_ids, const uint64
             none.rowptr = nullptr; none.colidx = nullptr; none.hrows = nullptr; none.nvec = 0; none.nrows = 0;
             u32 grid = cdiv(k, 4);
             if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-            hipLaunchKernelGGL(probe_csr_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), view_of(ml),
-                               (dml && dml->nnz) ? view_of(dml) : none, (dpl && dpl->nnz) ? view_of(dpl) : none, (const u32*)d_dst.p, k,
-                               hits.p, hits.p + k, hits.p + 2 * (size_t)k);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(probe_csr_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(f), view_of(ml),
+                            (dml && dml->nnz) ? view_of(dml) : none, (dpl && dpl->nnz) ? view_of(dpl) : none, (const u32*)d_dst.p, k,
+                            hits.p, hits.p + k, hits.p + 2 * (size_t)k));
         }
     } else {
         FGPU_TRY(bp_probe_rows(ctx, bs, ml, dpl, dml, d_dst.p, d_bit.p, d_sdst.p, d_srow.p, k, hits.p, hits.p + k, hits.p + 2 * (size_t)k));
@@ -1831,9 +1808,8 @@ extern "C" fgpu_info fgpu_expand_trail_counts(fgpu_ctx* ctx, const uint64_t* src
         if (c1->nnz) {
             u32 grid = cdiv(nsrc, 4);
             if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-            hipLaunchKernelGGL(row_weight_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), view_of(eff[0]),
-                               weighted ? (const u64*)eff[0]->vals : (const u64*)nullptr, (const u32*)dsrc.p, (u32)nsrc, w1.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(row_weight_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), view_of(eff[0]),
+                            weighted ? (const u64*)eff[0]->vals : (const u64*)nullptr, (const u32*)dsrc.p, (u32)nsrc, w1.p));
         }
         const fgpu_mat* res = c1;
         const u64* res_cnt = w1.p;
@@ -1844,10 +1820,9 @@ extern "C" fgpu_info fgpu_expand_trail_counts(fgpu_ctx* ctx, const uint64_t* src
             if (c1->nnz && c2->nnz) {
                 u32 grid = cdiv(c1->nnz, 4);
                 if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-                hipLaunchKernelGGL(trail2_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), (const u64*)w1.p,
-                                   view_of(eff[1]), weighted ? (const u64*)eff[1]->vals : (const u64*)nullptr, view_of(c2),
-                                   (const u32*)dsrc.p, (u32)c1->nnz, (unsigned long long*)cnt.p);
-                FGPU_HIP(hipGetLastError());
+                FGPU_TRY(launch(trail2_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), (const u64*)w1.p,
+                                view_of(eff[1]), weighted ? (const u64*)eff[1]->vals : (const u64*)nullptr, view_of(c2),
+                                (const u32*)dsrc.p, (u32)c1->nnz, (unsigned long long*)cnt.p));
             }
             res = c2;
             res_cnt = cnt.p;

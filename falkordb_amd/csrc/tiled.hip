@@ -405,8 +405,6 @@ fgpu_info tiles_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 x_
     const size_t lds = ((size_t)1 << t->tile_bits) / 8 + 16;
     FGPU_REQUIRE((int)lds <= ctx->opt.lds_limit, FGPU_INVALID,
                  "tiled kernel needs %zu B of LDS per workgroup but the device offers %d", lds, ctx->opt.lds_limit);
-    if (lds > 48 * 1024)
-        FGPU_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const u32 threads = (u32)ctx->opt.tiled_threads;
     u32 per_cu = (u32)(ctx->opt.lds_limit / lds);
     if (per_cu < 1) per_cu = 1;
@@ -421,10 +419,7 @@ fgpu_info tiles_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 x_
     if (wpt > max_wpt) wpt = max_wpt ? max_wpt : 1;
     const u32 nvirt = wpt * t->ntiles;
     if (grid > nvirt) grid = nvirt;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, ctx->stream(), view_of(t), x_dev, x_words64 * 2, mask_dev,
-                       out_dev, wpt);
-    FGPU_HIP(hipGetLastError());
-    return FGPU_OK;
+    return launch(fn, dim3(grid), dim3(threads), lds, ctx->stream(), view_of(t), x_dev, x_words64 * 2, mask_dev, out_dev, wpt);
 }
 
 // Built once per snapshot under its index mutex (first dense-frontier vxm on it); `rebuild` = the measurement hook
@@ -501,9 +496,8 @@ fgpu_info tiles_build(fgpu_ctx* ctx, const fgpu_mat* m, int tile_bits, int vec, 
         if ((info = ctx->dev_alloc((void**)&t->tile_item, ((size_t)ntiles + 1) * sizeof(u32))) != FGPU_OK) break;
         u32 grid = cdiv(ngroups, 4);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        hipLaunchKernelGGL(tiles_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows,
-                           ngroups, (u32)tile_bits, ntiles, (u32)vec, cap, cnt_e.p, cnt_i.p, t->row_has);
-        if (hipGetLastError() != hipSuccess) { set_error("tiles_count launch failed"); info = FGPU_DEVICE; break; }
+        if ((info = launch(tiles_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits,
+                           ntiles, (u32)vec, cap, cnt_e.p, cnt_i.p, t->row_has)) != FGPU_OK) break;
         if ((info = scan_u32_to_u64(ctx, cnt_e.p, eoff.p, nslots + 1, nullptr)) != FGPU_OK) break;
         if ((info = scan_u32(ctx, cnt_i.p, ioff.p, nslots + 1, nullptr)) != FGPU_OK) break;
         u64 total_e = 0;
@@ -521,14 +515,12 @@ fgpu_info tiles_build(fgpu_ctx* ctx, const fgpu_mat* m, int tile_bits, int vec, 
         if ((info = ctx->dev_alloc((void**)&t->entries, (size_t)total_e * sizeof(u32))) != FGPU_OK) break;
         if ((info = ctx->dev_alloc((void**)&t->item_off, ((size_t)total_i + 1) * sizeof(u32))) != FGPU_OK) break;
         if ((info = ctx->dev_alloc((void**)&t->item_group, ((size_t)total_i + 1) * sizeof(u32))) != FGPU_OK) break;
-        hipLaunchKernelGGL(tiles_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups,
-                           (u32)tile_bits, ntiles, (u32)vec, cap, (const u64*)eoff.p, (const u32*)ioff.p, t->entries, t->item_off,
-                           t->item_group);
-        if (hipGetLastError() != hipSuccess) { set_error("tiles_fill launch failed"); info = FGPU_DEVICE; break; }
-        hipLaunchKernelGGL(tiles_finish_kernel, dim3(cdiv((u64)ntiles + 1, 64)), dim3(64), 0, ctx->stream(),
-                           (const u32*)ioff.p, (const u64*)eoff.p, ngroups, ntiles, (u32)tile_bits, t->tile_item,
-                           t->item_off, t->entries);
-        if (hipGetLastError() != hipSuccess) { set_error("tiles_finish launch failed"); info = FGPU_DEVICE; break; }
+        if ((info = launch(tiles_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits,
+                           ntiles, (u32)vec, cap, (const u64*)eoff.p, (const u32*)ioff.p, t->entries, t->item_off,
+                           t->item_group)) != FGPU_OK) break;
+        if ((info = launch(tiles_finish_kernel, dim3(cdiv((u64)ntiles + 1, 64)), dim3(64), 0, ctx->stream(), (const u32*)ioff.p,
+                           (const u64*)eoff.p, ngroups, ntiles, (u32)tile_bits, t->tile_item, t->item_off,
+                           t->entries)) != FGPU_OK) break;
         if (hipStreamSynchronize(ctx->stream()) != hipSuccess) { set_error("tiles build failed"); info = FGPU_DEVICE; break; }
     } while (0);
     if (info != FGPU_OK) { tiles_release(t); return info; }

@@ -290,38 +290,27 @@ fgpu_info sort_pairs_by_key(fgpu_ctx* ctx, const u32* key, const u32* val, const
     const size_t lds1 = (size_t)g.B * sizeof(u32);
     {
         ProfScope ps(ctx, "ks_count_kernel", 4 * n + 4 * ncnt);
-        if (implicit)
-            hipLaunchKernelGGL(ks_count_kernel<true>, dim3(g.nblk), dim3(256), lds1, ctx->stream(), key, val, n, g, cnt.p);
-        else
-            hipLaunchKernelGGL(ks_count_kernel<false>, dim3(g.nblk), dim3(256), lds1, ctx->stream(), key, val, n, g, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(pick(implicit, [&](auto imp) {
+            return launch(ks_count_kernel<decltype(imp)::value>, dim3(g.nblk), dim3(256), lds1, ctx->stream(), key, val, n, g, cnt.p);
+        }));
     }
     FGPU_TRY(scan_u32(ctx, cnt.p, pos.p, ncnt, tot.p));
     {
         ProfScope ps(ctx, "ks_scatter_kernel", (implicit ? 4 : 8) * n + 8 * n + 4 * ncnt);
-        if (implicit)
-            hipLaunchKernelGGL(ks_scatter_kernel<true>, dim3(g.nblk), dim3(64), lds1, ctx->stream(), key, val, rowptr,
-                               nrows, n, g, (const u32*)pos.p, pairs.p);
-        else
-            hipLaunchKernelGGL(ks_scatter_kernel<false>, dim3(g.nblk), dim3(64), lds1, ctx->stream(), key, val, rowptr,
-                               nrows, n, g, (const u32*)pos.p, pairs.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(pick(implicit, [&](auto imp) {
+            return launch(ks_scatter_kernel<decltype(imp)::value>, dim3(g.nblk), dim3(64), lds1, ctx->stream(), key, val, rowptr, nrows,
+                          n, g, (const u32*)pos.p, pairs.p);
+        }));
     }
     u32 n_valid = (u32)n;   // implicit values are never dropped: no read-back, no host sync
     if (!implicit) FGPU_TRY(read_u32(ctx, tot.p, &n_valid));
     const size_t lds2 = (size_t)4 * (1u << g.wb) * sizeof(u32);
-    if (lds2 > 48 * 1024)
-        FGPU_HIP(hipFuncSetAttribute((const void*)ks_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     {
         ProfScope ps(ctx, "ks_bucket_kernel", 16 * (u64)n_valid + 4 * (u64)n_valid + 4 * (nkeys + 1));
-        hipLaunchKernelGGL(ks_bucket_kernel, dim3(g.B), dim3(256), lds2, ctx->stream(), (const uint2*)pairs.p,
-                           (const u32*)pos.p, n_valid, nkeys, g, keyptr, out_val);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(ks_bucket_kernel, dim3(g.B), dim3(256), lds2, ctx->stream(), (const uint2*)pairs.p,
+                        (const u32*)pos.p, n_valid, nkeys, g, keyptr, out_val));
     }
-    if ((nkeys & ((1ull << g.wb) - 1)) == 0) {
-        hipLaunchKernelGGL(ks_tail_kernel, dim3(1), dim3(1), 0, ctx->stream(), keyptr, nkeys, n_valid);
-        FGPU_HIP(hipGetLastError());
-    }
+    if ((nkeys & ((1ull << g.wb) - 1)) == 0) FGPU_TRY(launch(ks_tail_kernel, dim3(1), dim3(1), 0, ctx->stream(), keyptr, nkeys, n_valid));
     if (n_valid_out) *n_valid_out = n_valid;
     return FGPU_OK;
 }
@@ -708,8 +697,7 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
     if (implicit) FGPU_TRY(brows.alloc(ctx, n / KP_EB + 16));
     FGPU_TRY(cnt.alloc(ctx, (size_t)dmax * nb_top + 2));
     FGPU_TRY(pos.alloc(ctx, (size_t)dmax * nb_top + 2));
-    hipLaunchKernelGGL(kp_first_kernel, dim3(1), dim3(1), 0, st, (u32)n, segstart.p, blkstart.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(kp_first_kernel, dim3(1), dim3(1), 0, st, (u32)n, segstart.p, blkstart.p));
     u32 done = 0;
     const uint2* in = nullptr;
     for (int l = 0; l < L; ++l) {
@@ -722,19 +710,16 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
         const bool first = l == 0, last = l == L - 1;
         const u64 nb_max = (n / KP_EB + 1 + lv.S + 7) & ~7ull;
         const size_t ncnt = (size_t)lv.D * nb_max + 1;
-        hipLaunchKernelGGL(kp_blk_table_kernel, dim3(cdiv(nb_max, 256)), dim3(256), 0, st, (const u32*)segstart.p, (const u32*)blkstart.p, lv,
-                           (u32)nb_max, desc.p, first && implicit ? rowptr : (const u32*)nullptr, nrows, brows.p, cnt.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(kp_blk_table_kernel, dim3(cdiv(nb_max, 256)), dim3(256), 0, st, (const u32*)segstart.p, (const u32*)blkstart.p, lv,
+                        (u32)nb_max, desc.p, first && implicit ? rowptr : (const u32*)nullptr, nrows, brows.p, cnt.p));
         {
             static const char* const names[] = {"kp_count_kernel L1", "kp_count_kernel L2", "kp_count_kernel L3", "kp_count_kernel L4"};
             ProfScope ps(ctx, names[l < 4 ? l : 3], (first ? 4 : 8) * n + 4 * ncnt);
-            if (first)
-                hipLaunchKernelGGL((kp_count_kernel<true, false>), dim3((u32)nb_max), dim3(256), 0, st, key, val, (const uint2*)nullptr, lv,
-                                   (const uint4*)desc.p, cnt.p, (const u32*)nullptr, (u32*)nullptr);
-            else
-                hipLaunchKernelGGL((kp_count_kernel<false, false>), dim3((u32)nb_max), dim3(256), 0, st, (const u32*)nullptr, (const u32*)nullptr, in, lv,
-                                   (const uint4*)desc.p, cnt.p, (const u32*)nullptr, (u32*)nullptr);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(pick(first, [&](auto f) {   // the first level reads (key, val), the later ones the pairs of the level before
+                constexpr bool F = decltype(f)::value;
+                return launch(kp_count_kernel<F, false>, dim3((u32)nb_max), dim3(256), 0, st, F ? key : nullptr, F ? val : nullptr,
+                              F ? nullptr : in, lv, (const uint4*)desc.p, cnt.p, (const u32*)nullptr, (u32*)nullptr);
+            }));
         }
         FGPU_TRY(scan_u32(ctx, cnt.p, pos.p, ncnt, nullptr));
         uint2* outp = last ? nullptr : (l == 0 ? bufA.p : (in == bufA.p ? bufB.p : bufA.p));
@@ -742,40 +727,33 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
         {
             static const char* const names[] = {"kp_scatter_kernel L1", "kp_scatter_kernel L2", "kp_scatter_kernel L3", "kp_scatter_kernel L4"};
             ProfScope ps(ctx, names[l < 4 ? l : 3], (first ? (implicit ? 4 : 8) : 8) * n + (last ? 4 : 8) * n + 4 * ncnt);
-#define KP_SCATTER(F, I, LA)                                                                                                              \
-            do {                                                                                                                          \
-                if (lds > 48 * 1024)                                                                                                      \
-                    FGPU_HIP(hipFuncSetAttribute((const void*)kp_scatter_kernel<F, I, LA, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                hipLaunchKernelGGL((kp_scatter_kernel<F, I, LA, false>), dim3((u32)nb_max), dim3(256), lds, st, key, val, rowptr, nrows, in, lv,  \
-                                   (const uint4*)desc.p, (const uint2*)brows.p, (const u32*)pos.p, outp, out_val, (const u32*)nullptr);    \
-            } while (0)
-            if (first) {
-                if (implicit) { if (last) KP_SCATTER(true, true, true); else KP_SCATTER(true, true, false); }
-                else { if (last) KP_SCATTER(true, false, true); else KP_SCATTER(true, false, false); }
-            } else {
-                if (last) KP_SCATTER(false, false, true); else KP_SCATTER(false, false, false);
-            }
-#undef KP_SCATTER
-            FGPU_HIP(hipGetLastError());
+            // (`implicit` means something at the first level only: the later ones read pairs)
+            FGPU_TRY(pick(first, [&](auto f) {
+                return pick(implicit, [&](auto i) {
+                    return pick(last, [&](auto la) {
+                        constexpr bool F = decltype(f)::value, I = F && decltype(i)::value;
+                        return launch(kp_scatter_kernel<F, I, decltype(la)::value, false>, dim3((u32)nb_max), dim3(256), lds, st, key, val,
+                                      rowptr, nrows, in, lv, (const uint4*)desc.p, (const uint2*)brows.p, (const u32*)pos.p, outp,
+                                      out_val, (const u32*)nullptr);
+                    });
+                });
+            }));
         }
         // the next level's segments (or, after the last level, the key pointers)
         const u64 nseg_next = (u64)lv.S * lv.D;
         if (last) {
-            hipLaunchKernelGGL(kp_seg_kernel, dim3(cdiv(nkeys + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv, nkeys,
-                               keyptr, (u32*)nullptr);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(kp_seg_kernel, dim3(cdiv(nkeys + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv, nkeys,
+                            keyptr, (u32*)nullptr));
             if (n_valid_out) {
                 if (implicit) *n_valid_out = (u32)n;
                 else FGPU_TRY(read_u32(ctx, keyptr + nkeys, n_valid_out));
             }
         } else {
-            hipLaunchKernelGGL(kp_seg_kernel, dim3(cdiv(nseg_next + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv,
-                               nseg_next, segnext.p, nblk.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(kp_seg_kernel, dim3(cdiv(nseg_next + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv,
+                            nseg_next, segnext.p, nblk.p));
             std::swap(segstart, segnext);
             if (nseg_next + 1 <= KP_SMALL_SCAN) {
-                hipLaunchKernelGGL(kp_small_scan_kernel, dim3(1), dim3(1024), 0, st, (const u32*)nblk.p, (u32)(nseg_next + 1), blkstart.p);
-                FGPU_HIP(hipGetLastError());
+                FGPU_TRY(launch(kp_small_scan_kernel, dim3(1), dim3(1024), 0, st, (const u32*)nblk.p, (u32)(nseg_next + 1), blkstart.p));
             } else {
                 FGPU_TRY(scan_u32(ctx, nblk.p, blkstart.p, nseg_next + 1, nullptr));
             }
@@ -861,28 +839,24 @@ fgpu_info partition_csr_entries(fgpu_ctx* ctx, const u32* colidx, const u32* row
     FGPU_TRY(brows.alloc(ctx, nb_max + 1));
     FGPU_TRY(cnt.alloc(ctx, ncnt + 1));
     FGPU_TRY(pos.alloc(ctx, ncnt + 1));
-    hipLaunchKernelGGL(kp_first_kernel, dim3(1), dim3(1), 0, st, (u32)nnz, segstart.p, blkstart.p);
-    hipLaunchKernelGGL(kp_blk_table_kernel, dim3(cdiv(nb_max, 256)), dim3(256), 0, st, (const u32*)segstart.p, (const u32*)blkstart.p, lv,
-                       (u32)nb_max, desc.p, rowptr, nrows, brows.p, cnt.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(kp_first_kernel, dim3(1), dim3(1), 0, st, (u32)nnz, segstart.p, blkstart.p));
+    FGPU_TRY(launch(kp_blk_table_kernel, dim3(cdiv(nb_max, 256)), dim3(256), 0, st, (const u32*)segstart.p, (const u32*)blkstart.p, lv,
+                    (u32)nb_max, desc.p, rowptr, nrows, brows.p, cnt.p));
     {
         ProfScope ps(ctx, "kp_count_kernel part", 4 * nnz + 4 * ncnt);
-        hipLaunchKernelGGL((kp_count_kernel<true, true>), dim3((u32)nb_max), dim3(256), 0, st, colidx, (const u32*)nullptr, (const uint2*)nullptr, lv,
-                           (const uint4*)desc.p, cnt.p, slot_of, slot_of ? slots.p : (u32*)nullptr);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch((kp_count_kernel<true, true>), dim3((u32)nb_max), dim3(256), 0, st, colidx, (const u32*)nullptr, (const uint2*)nullptr, lv,
+                        (const uint4*)desc.p, cnt.p, slot_of, slot_of ? slots.p : (u32*)nullptr));
     }
     FGPU_TRY(scan_u32(ctx, cnt.p, pos.p, ncnt, nullptr));
     {
         ProfScope ps(ctx, "kp_scatter_kernel part", 4 * nnz + 8 * nnz + 4 * ncnt);
         const size_t lds = ((size_t)2 * KP_EB + (size_t)6 * lv.D) * sizeof(u32);
-        hipLaunchKernelGGL((kp_scatter_kernel<true, true, false, true>), dim3((u32)nb_max), dim3(256), lds, st,
-                           slot_of ? (const u32*)slots.p : colidx, (const u32*)nullptr, rowptr, nrows, (const uint2*)nullptr, lv,
-                           (const uint4*)desc.p, (const uint2*)brows.p, (const u32*)pos.p, out_pairs, (u32*)nullptr, (const u32*)nullptr);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch((kp_scatter_kernel<true, true, false, true>), dim3((u32)nb_max), dim3(256), lds, st,
+                        slot_of ? (const u32*)slots.p : colidx, (const u32*)nullptr, rowptr, nrows, (const uint2*)nullptr, lv,
+                        (const uint4*)desc.p, (const uint2*)brows.p, (const u32*)pos.p, out_pairs, (u32*)nullptr, (const u32*)nullptr));
     }
-    hipLaunchKernelGGL(kp_seg_kernel, dim3(cdiv((u64)nparts + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv,
-                       (u64)nparts, pstart_dev, (u32*)nullptr);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(kp_seg_kernel, dim3(cdiv((u64)nparts + 1, 256)), dim3(256), 0, st, (const u32*)pos.p, (const u32*)blkstart.p, lv,
+                    (u64)nparts, pstart_dev, (u32*)nullptr));
     return FGPU_OK;
 }
 
@@ -924,8 +898,7 @@ fgpu_info mat_from_device_coo_counting(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows,
     FGPU_TRY(byr_col.alloc(ctx, nv));
     FGPU_TRY(rowptr.alloc(ctx, nrows + 1));
     // the column-major form is a CSR over `ncols` rows whose "column ids" are the original rows
-    fgpu_info i = sort_pairs(ctx, byc_row.p, nullptr, colptr.p, (u32)ncols, nv, nrows, byr_col.p, rowptr.p, nullptr);
-    if (i != FGPU_OK) return i;
+    FGPU_TRY(sort_pairs(ctx, byc_row.p, nullptr, colptr.p, (u32)ncols, nv, nrows, byr_col.p, rowptr.p, nullptr));
     byc_row.release();
     DevBuf<u32> keep, newpos, tot;
     FGPU_TRY(keep.alloc(ctx, (size_t)nv + 1));
@@ -933,22 +906,21 @@ fgpu_info mat_from_device_coo_counting(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows,
     FGPU_TRY(tot.alloc(ctx, 1));
     u32 grid = cdiv(nv, 256);
     if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-    hipLaunchKernelGGL(dedup_flag_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p, (u32)nrows,
-                       (const u32*)byr_col.p, nv, keep.p);
-    hipLaunchKernelGGL(dedup_rowstart_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
-                       (u32)nrows, nv, keep.p);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(dedup_flag_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p, (u32)nrows,
+                    (const u32*)byr_col.p, nv, keep.p));
+    FGPU_TRY(launch(dedup_rowstart_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
+                    (u32)nrows, nv, keep.p));
     FGPU_TRY(scan_u32(ctx, keep.p, newpos.p, nv, tot.p));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, tot.p, &nnz));
     fgpu_mat* m = nullptr;
     FGPU_TRY(mat_alloc(ctx, &m, nrows, ncols, nnz, false, 0, false));
-    hipLaunchKernelGGL(dedup_rowptr_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
-                       (u32)nrows, nv, (const u32*)newpos.p, nnz, m->rowptr);
-    hipLaunchKernelGGL(dedup_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)byr_col.p,
-                       (const u32*)keep.p, (const u32*)newpos.p, nv, m->colidx);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("COO build failed: %s", hipGetErrorString(e)); mat_release(m); return FGPU_DEVICE; }
+    fgpu_info i = launch(dedup_rowptr_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
+                         (u32)nrows, nv, (const u32*)newpos.p, nnz, m->rowptr);
+    if (i == FGPU_OK)
+        i = launch(dedup_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)byr_col.p, (const u32*)keep.p,
+                   (const u32*)newpos.p, nv, m->colidx);
+    if (i != FGPU_OK) { mat_release(m); return i; }
     *out = m;
     return FGPU_OK;
 }

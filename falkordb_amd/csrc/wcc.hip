@@ -178,14 +178,12 @@ static fgpu_info wcc_link_rows(fgpu_ctx* ctx, const fgpu_mat* m, const u64* act,
     const u32 nwords = cdiv(n, 64);
     u32 grid = cdiv(nwords, 4);
     if (grid > (u32)ctx->cus * 8) grid = (u32)ctx->cus * 8;
-    hipLaunchKernelGGL(wcc_link_words_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(m), act, parent, n, first, giant,
-                       entries);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(wcc_link_words_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(m), act, parent, n, first, giant,
+                    entries));
     ++*launches;
     if (m->n_hub_chunks) {
-        hipLaunchKernelGGL(wcc_link_hubs_kernel, dim3(hub_grid(ctx, m)), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks,
-                           m->n_hub_chunks, (const u32*)m->rowptr, (const u32*)m->colidx, act, parent, first, giant, entries);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(wcc_link_hubs_kernel, dim3(hub_grid(ctx, m)), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks,
+                        m->n_hub_chunks, (const u32*)m->rowptr, (const u32*)m->colidx, act, parent, first, giant, entries));
         ++*launches;
     }
     return FGPU_OK;
@@ -230,23 +228,20 @@ extern "C" fgpu_info fgpu_wcc(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* 
     u64 launches = 0;
     if (afforest) {
         for (u32 r = 0; r < WCC_ROUNDS; ++r) {
-            hipLaunchKernelGGL(wcc_link_round_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(A), a, parent.p, n, r,
-                               cnt.p);
-            FGPU_HIP(hipGetLastError());
+            FGPU_TRY(launch(wcc_link_round_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(A), a, parent.p, n, r,
+                            cnt.p));
             ++launches;
             FGPU_TRY(forest_compress(ctx, "fgpu_wcc", parent.p, n, flags.p));
         }
-        hipLaunchKernelGGL(wcc_sample_kernel, dim3(1), dim3(WCC_SAMPLES), 0, ctx->stream(), (const u32*)parent.p, a, n, giant.p);
-        FGPU_HIP(hipGetLastError());
+        FGPU_TRY(launch(wcc_sample_kernel, dim3(1), dim3(WCC_SAMPLES), 0, ctx->stream(), (const u32*)parent.p, a, n, giant.p));
         FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, WCC_ROUNDS, giant.p, cnt.p, &launches));
         if (At) FGPU_TRY(wcc_link_rows(ctx, At, a, parent.p, n, 0, giant.p, cnt.p, &launches));
     } else {
         FGPU_TRY(wcc_link_rows(ctx, A, a, parent.p, n, 0, nullptr, cnt.p, &launches));
     }
     FGPU_TRY(forest_compress(ctx, "fgpu_wcc", parent.p, n, flags.p));
-    hipLaunchKernelGGL(wcc_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)parent.p, a, n,
-                       afforest ? (const u32*)giant.p : nullptr, wide.p, cnt.p + 1);
-    FGPU_HIP(hipGetLastError());
+    FGPU_TRY(launch(wcc_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)parent.p, a, n,
+                    afforest ? (const u32*)giant.p : nullptr, wide.p, cnt.p + 1));
     FGPU_TRY(ctx->d2h(component, wide.p, (size_t)n * sizeof(int64_t)));   // one DMA when component[] is pinned
     if (stats) {
         unsigned long long h[3];
