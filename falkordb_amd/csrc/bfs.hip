@@ -24,6 +24,7 @@
 //    + A'[lo:hi,:]); the only exchange is an all-gather of the owned new-frontier words,
 //    issued by the host loop between step() and commit() (RCCL over xGMI).
 #include <chrono>
+#include <memory>
 
 #include "algo.hpp"
 
@@ -2451,40 +2452,80 @@ static fgpu_info ensure_pull_order(fgpu_ctx* ctx, const fgpu_mat* At, const fgpu
     return FGPU_OK;
 }
 
+// RAII: a pooled pinned block for control words a device writes and the host polls (fgpu_ctx::flag_alloc), typed by what
+// it holds — it goes back to its context's pool, a plan never calls hipHostFree — and a HIP event
+template <typename T>
+struct PinnedFlag {
+    fgpu_ctx* ctx = nullptr;
+    T* p = nullptr;
+    PinnedFlag() {}
+    PinnedFlag(const PinnedFlag&) = delete;
+    PinnedFlag& operator=(const PinnedFlag&) = delete;
+    ~PinnedFlag() { if (p) ctx->flag_release(p); }
+    bool alloc(fgpu_ctx* c) { ctx = c; p = (T*)c->flag_alloc(); return p != nullptr; }
+    T* operator->() const { return p; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() {}
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }   // (move-only: a std::vector of them may grow)
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }   // on the current device
+};
+
+// propagation blocking of heavy push levels (bfs_pb_*): the control / statistics block, one allocation for the small arrays
+// (list | P | S | crow | per-workgroup histograms), the bins, and the vertices with an in-edge as a bitmap (plans with a
+// transpose: bfs_lp_kernel's candidates).  All or nothing: a plan holds the whole bundle or an empty one
+struct PbBufs {
+    DevBuf<BfsPb> ctl;
+    DevBuf<u32> small, dst, src;
+    DevBuf<u64> alive;
+    u32 maxchunks = 0;
+    u32 shift = 6;   // log2(vertices per window): the smallest at which PB_BINS windows cover the bitmap
+    explicit operator bool() const { return ctl.p != nullptr; }
+};
+
+// Every device block below is a DevBuf, every pinned block a PinnedFlag, every event an Event: deleting the plan releases
+// them.  The raw pointers beside them are VIEWS the kernels read; each says what it points into.
 struct fgpu_bfs_plan {
     fgpu_ctx* ctx = nullptr;
     const fgpu_mat* A = nullptr;
     const fgpu_mat* At = nullptr;
     int rank = 0, nranks = 1;
     u32 n = 0, slab = 0, lo = 0, hi = 0, nw = 0, slabw = 0;
-    u64 *cur = nullptr, *nxt_local = nullptr, *nxt_global = nullptr, *visited = nullptr;
-    bool external_bufs = false;
-    u64* bm_block = nullptr;  // single-rank fused path: [bm0 | bm1 | bm2 | visited] in one allocation
-    u32* queue_block = nullptr;  // single-rank fused path: two frontier queues of QCAP ids
-    u32* h_done = nullptr;       // pinned host word the last level writes (host view)
-    u32* d_done = nullptr;       // the same word as the device sees it
+    DevBuf<u64> cur, visited;
+    DevBuf<u64> own_global, own_local;   // the library's own frontier pair (own_local: multi-rank plans only), until adopt_buffers
+    // views: own_global / own_local (one rank: both own_global), or caller memory (fgpu_bfs_part_set_buffers,
+    // fgpu_bfs_slab_set_buffers), or dist_glob (dist_setup)
+    u64 *nxt_local = nullptr, *nxt_global = nullptr;
+    DevBuf<u64> bm_block;     // single-rank fused path: [bm0 | bm1 | bm2 | visited] in one allocation (fused_views)
+    DevBuf<u32> queue_block;  // single-rank fused path: two frontier queues of QCAP ids
+    PinnedFlag<u32> h_done;      // pinned host words the last level writes (host view)
+    u32* d_done = nullptr;       // the same words as the device sees them (view of h_done)
     int enqueued = 0;            // levels enqueued since the last begin
     bool levels_masked = false;  // level[] already holds -1 for unreached vertices (set by fgpu_bfs_fetch)
-    const u64* mask_visited = nullptr;  // the visited bitmap fgpu_bfs_fetch masks level[] with (fused paths)
-    u64* slab_send[2] = {nullptr, nullptr};  // fused slab path: double-buffered send slabs (caller-owned)
-    u64* slab_glob[2] = {nullptr, nullptr};  // the gathered frontier launch L reads = slab_glob[L & 1]: one buffer twice, except in
-                                             // the peer exchange of a single-process gang, where peers write level L + 1's bitmap
-                                             // while a slower rank may still be reading level L's
-    u64* dist_glob2 = nullptr;               // (library-owned second bitmap of that mode)
+    const u64* mask_visited = nullptr;  // the visited bitmap fgpu_bfs_fetch masks level[] with (fused paths): view of visited or bm_block
+    // fused slab path: double-buffered send slabs — views of caller memory, or of dist_send[] (dist_setup)
+    u64* slab_send[2] = {nullptr, nullptr};
+    // the gathered frontier launch L reads = slab_glob[L & 1]: one buffer twice (nxt_global), except in the peer exchange of a
+    // single-process gang, where peers write level L + 1's bitmap while a slower rank may still be reading level L's — views
+    // of dist_glob and dist_glob2 there
+    u64* slab_glob[2] = {nullptr, nullptr};
     // in-place exchange (RCCL / one rank): three global bitmaps in rotation — level L reads ring[L % 3], ORs its owned
     // words straight into ring[(L + 1) % 3] (which the exchange then completes with the peers' words) and zeroes its
-    // owned words of ring[(L + 2) % 3]: no send buffers, no copy of the rank's own words per level
+    // owned words of ring[(L + 2) % 3]: no send buffers, no copy of the rank's own words per level.  Views of dist_glob,
+    // ring_own[0] and ring_own[1]
     u64* slab_ring[3] = {nullptr, nullptr, nullptr};
     bool inplace = false;
-    const u32* pull_colidx = nullptr;        // the column ids of A' the pull levels read (hub-first copy or the matrix's own), fixed at creation
-    headv* pull_head = nullptr;              // leading PULL_H entries of every row of that array, nw * 64 rows (owned)
-    const u32* gdeg = nullptr;               // fused slab path: global out-degrees (caller-owned, nullable)
+    const u32* pull_colidx = nullptr;        // the column ids of A' the pull levels read (hub-first copy or the matrix's own: view of At), fixed at creation
+    DevBuf<headv> pull_head;                 // leading PULL_H entries of every row of that array, nw * 64 rows
+    const u32* gdeg = nullptr;               // fused slab path: global out-degrees (view of caller memory or of dist_deg, nullable)
     u32 launch = 0;                          // fused slab path: level launches since begin
     int last_levels = 0;         // levels the previous search of this plan took (sizes the next blind batch)
-    i32* level = nullptr;
-    u32* parent = nullptr;
-    BfsCtrl* ctrl = nullptr;
-    BfsCtrl* h_ctrl = nullptr;  // pinned
+    DevBuf<i32> level;
+    DevBuf<u32> parent;
+    DevBuf<BfsCtrl> ctrl;
+    PinnedFlag<BfsCtrl> h_ctrl;
     double alpha = 32.0, beta = 24.0;
     int force_dir = 0;
     bool want_parent = false;
@@ -2492,68 +2533,93 @@ struct fgpu_bfs_plan {
     int last_heavy = -1;  // span of the non-tiny levels of the previous search (-1: no search yet)
     double last_wait_us = 0;  // how long fgpu_bfs_wait polled last time (sets when the next wait starts querying the stream)
     std::vector<ProfSlot> prof;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     u32 grid = 0;   // multi-rank step kernel
     u32 fgrid = 0;  // fused single-rank level kernel: every workgroup resident at once
-    // in-library multi-GPU loop (fgpu_bfs_dist_run): slab boundaries of every rank, library-owned exchange buffers,
-    // the global out-degree vector, and the time split compute / collective of the last search
+    // in-library multi-GPU loop (fgpu_bfs_dist_run): slab boundaries of every rank, library-owned exchange buffers
+    // (dist_glob2: the second bitmap of the peer exchange; ring_own: blocks 1 and 2 of the in-place ring), the global
+    // out-degree vector, and the time split compute / collective of the last search
     std::vector<u64> splits;            // nranks + 1 vertex ids, multiples of 4096; empty = equal slabs
-    u64* dist_send[2] = {nullptr, nullptr};
-    u64* dist_glob = nullptr;
-    u32* dist_deg = nullptr;
+    DevBuf<u64> dist_send[2], dist_glob, dist_glob2, ring_own[2];
+    DevBuf<u32> dist_deg;
     u32 fused_idx = 0;                       // fused launches enqueued since fused_begin: launch k runs the instantiation of parity k & 1
-    u32* own_deg = nullptr;                  // single-rank plans: out-degree of every vertex (one 4-byte read per discovery)
-    // propagation blocking of heavy push levels (bfs_pb_*): the control / statistics block, one allocation for the small arrays
-    // (list | P | S | crow | per-workgroup histograms) and the bins; pb_mask = the fused launches of the search in flight that have the four
-    // launches in front of them
-    BfsPb* pb = nullptr;
-    u32* pb_small = nullptr;
-    u32 *pb_dst = nullptr, *pb_src = nullptr;
-    u32 pb_maxchunks = 0, pb_mask = 0;
+    DevBuf<u32> own_deg;                     // single-rank plans: out-degree of every vertex (one 4-byte read per discovery)
+    PbBufs pb;                               // empty unless the plan blocks its heavy push levels (plan_pb)
+    u32 pb_mask = 0;                         // the fused launches of the search in flight that have the four launches in front of them
     u32 n_alive = 0;                         // vertices with an in-edge (0 when the plan has no transpose)
-    u64* alive = nullptr;                    // ... as a bitmap (plans with the propagation-blocking launches: bfs_lp_kernel's candidates)
     u32 cp_mask = 0, cp_seen = 0, pb_epoch = 0;   // the list kernel alone in front of those fused launches (frontier -> queue), learnt like pb_seen
     u32 pb_seen = 0, pb_searches = 0;        // fused launches that were such levels in this plan's searches so far; searches run
     bool dist_ready = false;
-    std::vector<hipEvent_t> dist_ev;    // 3 per level: before the level kernel, after it, after the collective
-    hipEvent_t dist_copied = nullptr;   // peer exchange: "this rank has delivered its words of the level" (kept across searches)
+    std::vector<Event> dist_ev;         // 3 per level: before the level kernel, after it, after the collective
+    Event dist_copied;                  // peer exchange: "this rank has delivered its words of the level" (kept across searches)
     double dist_level_ms = 0, dist_coll_ms = 0;
     u64 dist_levels = 0;
+
+    // install other memory as the frontier pair: the library's own pair goes back to the pool
+    void adopt_buffers(u64* local, u64* global) {
+        own_local.release();
+        own_global.release();
+        nxt_local = local;
+        nxt_global = global;
+    }
 };
 
+// A' as the pull levels read it (the plan's column order); all null for a plan without a transpose
+static CsrView at_view(const fgpu_bfs_plan* p) {
+    if (!p->At) return CsrView{nullptr, nullptr, nullptr, 0, 0};
+    CsrView v = view_of(p->At);
+    if (p->pull_colidx) v.colidx = p->pull_colidx;
+    return v;
+}
+
+// the single-rank fused path's carving of bm_block and queue_block
+struct FusedViews {
+    u64* bm[3];
+    u64* visited;
+    u32* queue[2];
+};
+static FusedViews fused_views(const fgpu_bfs_plan* p) {
+    u64* b = p->bm_block.p;
+    const size_t nw = p->nw;
+    return {{b, b + nw, b + 2 * nw}, b + 3 * nw, {p->queue_block.p, p->queue_block.p + QCAP}};
+}
+
+// clears the frontier pair (one buffer for one rank)
+static hipError_t zero_frontier_pair(fgpu_bfs_plan* p) {
+    hipError_t e = hipMemsetAsync(p->nxt_global, 0, (size_t)p->nw * sizeof(u64), p->ctx->stream());
+    if (e == hipSuccess && p->nxt_local != p->nxt_global)
+        e = hipMemsetAsync(p->nxt_local, 0, (size_t)p->slabw * sizeof(u64), p->ctx->stream());
+    return e;
+}
+
+static i32 clamp_level(int64_t max_level) {
+    return max_level < 0 ? -1 : (max_level > 0x7FFFFFFF ? 0x7FFFFFFF : (i32)max_level);
+}
+
 static BfsArgs make_args(fgpu_bfs_plan* p, bool fused = false) {
-    BfsArgs a;
+    BfsArgs a = {};   // (the fused path's bitmaps, queues and flag stay null elsewhere)
     a.A = view_of(p->A);
-    if (p->At) {
-        a.At = view_of(p->At);
-        if (p->pull_colidx) a.At.colidx = p->pull_colidx;
-    }
-    else { a.At.rowptr = nullptr; a.At.colidx = nullptr; a.At.hrows = nullptr; a.At.nvec = 0; a.At.nrows = 0; }
-    a.head = p->pull_head;
+    a.At = at_view(p);
+    a.head = p->pull_head.p;
     a.hubA = p->A->hub_chunks; a.n_hubA = p->A->n_hub_chunks;
     a.hubP = p->A->push_chunks; a.n_hubP = p->A->n_push_chunks;
     a.hubAt = p->At ? p->At->hub_chunks : nullptr; a.n_hubAt = p->At ? p->At->n_hub_chunks : 0;
     a.n = p->n; a.lo = p->lo; a.hi = p->hi;
-    a.cur = p->cur; a.nxt_local = p->nxt_local; a.nxt_global = p->nxt_global; a.visited = p->visited;
-    a.level = p->level;
-    a.parent = p->want_parent ? p->parent : nullptr;
-    a.ctrl = p->ctrl;
+    a.cur = p->cur.p; a.nxt_local = p->nxt_local; a.nxt_global = p->nxt_global; a.visited = p->visited.p;
+    a.level = p->level.p;
+    a.parent = p->want_parent ? p->parent.p : nullptr;
+    a.ctrl = p->ctrl.p;
     a.nw = p->nw;
-    a.slab_mode = 0; a.slabw = p->slabw; a.slab_nxt = nullptr; a.slab_zero = nullptr; a.gdeg = p->own_deg;
-    a.pb = fused ? p->pb : nullptr;
-    if (p->bm_block && fused) {
-        a.bm[0] = p->bm_block;
-        a.bm[1] = p->bm_block + p->nw;
-        a.bm[2] = p->bm_block + 2 * (size_t)p->nw;
-        a.visited = p->bm_block + 3 * (size_t)p->nw;
+    a.slab_mode = 0; a.slabw = p->slabw; a.slab_nxt = nullptr; a.slab_zero = nullptr; a.gdeg = p->own_deg.p;
+    a.pb = fused ? p->pb.ctl.p : nullptr;
+    if (p->bm_block.p && fused) {
+        const FusedViews f = fused_views(p);
+        for (int k = 0; k < 3; ++k) a.bm[k] = f.bm[k];
+        a.visited = f.visited;
         a.cur = a.bm[0];
-        a.queue[0] = p->queue_block;
-        a.queue[1] = p->queue_block + QCAP;
+        a.queue[0] = f.queue[0];
+        a.queue[1] = f.queue[1];
         a.host_done = p->d_done;
-    } else {
-        a.bm[0] = a.bm[1] = a.bm[2] = nullptr;
-        a.queue[0] = a.queue[1] = nullptr;
-        a.host_done = nullptr;
     }
     return a;
 }
@@ -2570,40 +2636,8 @@ fgpu_info fgpu_debug_bfs_stamps(void* devbuf) {
 
 fgpu_info fgpu_bfs_plan_free(fgpu_bfs_plan* p) {
     if (!p) return FGPU_OK;
-    fgpu_ctx* c = p->ctx;
-    c->fence_lanes();   // the plan may have been driven from another thread's lane before
-    c->dev_free(p->cur);
-    c->dev_free(p->bm_block);
-    c->dev_free(p->queue_block);
-    if (!p->external_bufs) {
-        if (p->nxt_local != p->nxt_global) c->dev_free(p->nxt_local);
-        c->dev_free(p->nxt_global);
-    }
-    c->dev_free(p->visited);
-    c->dev_free(p->level);
-    c->dev_free(p->parent);
-    c->dev_free(p->ctrl);
-    c->dev_free(p->dist_send[0]);
-    c->dev_free(p->dist_send[1]);
-    c->dev_free(p->dist_glob);
-    c->dev_free(p->dist_glob2);
-    c->dev_free(p->pull_head);
-    c->dev_free(p->slab_ring[1]);
-    c->dev_free(p->slab_ring[2]);
-    c->dev_free(p->dist_deg);
-    c->dev_free(p->own_deg);
-    c->dev_free(p->alive);
-    c->dev_free(p->pb);
-    c->dev_free(p->pb_small);
-    c->dev_free(p->pb_dst);
-    c->dev_free(p->pb_src);
-    for (hipEvent_t e : p->dist_ev) (void)hipEventDestroy(e);
-    if (p->dist_copied) (void)hipEventDestroy(p->dist_copied);
-    c->flag_release(p->h_ctrl);   // (pooled: a plan never calls hipHostFree, see fgpu_ctx::flag_alloc)
-    c->flag_release(p->h_done);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    delete p;
+    p->ctx->fence_lanes();   // the plan may have been driven from another thread's lane before; makes the plan's device current
+    delete p;                // every block back to the pool, every event destroyed: the members release themselves
     return FGPU_OK;
 }
 
@@ -2630,6 +2664,168 @@ static fgpu_info pb_raise_limits() {
     return raise_lds(bfs_pb_apply_kernel<true>, PB_LDS_APPLY_MAX);
 }
 
+// plan_create, step by step.  Each step fills its part of a plan the caller holds; a failed step returns, and the plan's
+// members release what the earlier steps took.
+static fgpu_info plan_layout(fgpu_bfs_plan* p, const uint64_t* splits) {
+    const int nranks = p->nranks, rank = p->rank;
+    const u64 nrows = p->A->nrows;
+    if (splits) {
+        // caller-chosen slab boundaries (nnz-balanced, fgpu_mat_balanced_splits): ascending multiples of 4096 from 0 to
+        // the vertex count rounded up to 4096; the global frontier bitmap keeps its plain layout, rank r's words
+        // sit at word splits[r] / 64
+        bool ok = splits[0] == 0 && splits[nranks] >= nrows && splits[nranks] < nrows + 4096 &&
+                  splits[nranks] < 0xFFFFF000ull;
+        for (int r = 0; r < nranks && ok; ++r) ok = splits[r] <= splits[r + 1] && (splits[r + 1] & 4095ull) == 0;
+        FGPU_REQUIRE(ok, FGPU_INVALID, "fgpu_bfs_plan_create_slab: splits must ascend from 0 to ceil4096(n) in multiples of 4096");
+        p->splits.assign(splits, splits + nranks + 1);
+        p->lo = (u32)splits[rank];
+        p->hi = (u32)splits[rank + 1];
+        p->nw = (u32)(splits[nranks] / 64);
+    } else {
+        // equal slabs: the one definition of the rounding lives in fgpu_slab_layout (dist.hip)
+        std::vector<u64> lo(nranks), hi(nranks);
+        FGPU_TRY(fgpu_slab_layout(nullptr, nrows, nranks, lo.data(), hi.data(), nullptr, nullptr));
+        p->lo = (u32)lo[rank];
+        p->hi = (u32)hi[rank];
+        p->nw = (p->hi - p->lo) / 64 * nranks;
+    }
+    p->slab = p->hi - p->lo;
+    p->slabw = p->slab / 64;
+    return FGPU_OK;
+}
+
+static fgpu_info plan_buffers(fgpu_bfs_plan* p) {
+    fgpu_ctx* ctx = p->ctx;
+    const size_t nw = p->nw;
+    FGPU_TRY(p->cur.alloc(ctx, nw));
+    FGPU_TRY(p->own_global.alloc(ctx, nw));
+    if (p->nranks > 1) FGPU_TRY(p->own_local.alloc(ctx, (size_t)p->slabw + 1));
+    p->nxt_global = p->own_global.p;
+    p->nxt_local = p->nranks == 1 ? p->own_global.p : p->own_local.p;
+    FGPU_TRY(p->visited.alloc(ctx, nw));
+    FGPU_TRY(p->level.alloc(ctx, nw * 64));
+    FGPU_TRY(p->parent.alloc(ctx, nw * 64));
+    FGPU_TRY(p->ctrl.alloc(ctx, 1));
+    if (p->nranks == 1) {
+        FGPU_TRY(p->bm_block.alloc(ctx, 4 * nw));
+        FGPU_TRY(p->queue_block.alloc(ctx, 2 * (size_t)QCAP));
+    }
+    return FGPU_OK;
+}
+
+static fgpu_info plan_pull_head(fgpu_bfs_plan* p) {
+    if (!p->At) return FGPU_OK;
+    fgpu_ctx* ctx = p->ctx;
+    p->pull_colidx = (p->At->pull_col && ctx->opt.bfs_hub_first) ? p->At->pull_col : p->At->colidx;
+    FGPU_TRY(p->pull_head.alloc(ctx, (size_t)p->nw * 64));
+    return launch(pull_head_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)p->At->rowptr, p->pull_colidx,
+                  p->n, p->nw * 64, p->pull_head.p);
+}
+
+// the pinned control words, the profiling events (on the plan's device: the allocations above made it current) and a
+// zeroed frontier pair
+static fgpu_info plan_flags(fgpu_bfs_plan* p) {
+    static_assert(sizeof(BfsCtrl) <= 32768, "a plan's control block copy lives in one flag_alloc block");
+    fgpu_ctx* ctx = p->ctx;
+    auto ok = [](hipError_t e) -> fgpu_info {
+        if (e == hipSuccess) return FGPU_OK;
+        set_error("bfs plan setup failed: %s", hipGetErrorString(e));
+        return FGPU_DEVICE;
+    };
+    const bool got_ctrl = p->h_ctrl.alloc(ctx), got_done = p->h_done.alloc(ctx);
+    FGPU_TRY(ok(got_ctrl && got_done ? hipSuccess : hipErrorOutOfMemory));
+    FGPU_TRY(ok(hipHostGetDevicePointer((void**)&p->d_done, p->h_done.p, 0)));
+    *(volatile u32*)p->h_done.p = 0;
+    memset(p->h_ctrl.p, 0, sizeof(BfsCtrl));
+    FGPU_TRY(ok(p->ev0.create()));
+    FGPU_TRY(ok(p->ev1.create()));
+    return ok(zero_frontier_pair(p));
+}
+
+// the degree a discovery adds to the next frontier's edge count: read from a 4-byte array (measured at RMAT-26: the slab path,
+// which always had one, ran its heavy levels faster than the row-pointer pair of the single-rank path once it stopped reading both)
+static fgpu_info plan_alive(fgpu_bfs_plan* p) {
+    if (p->nranks != 1) return FGPU_OK;
+    fgpu_ctx* ctx = p->ctx;
+    FGPU_TRY(p->own_deg.alloc(ctx, (size_t)p->n + 1));
+    FGPU_TRY(fgpu_mat_row_degrees(ctx, p->A, p->own_deg.p));
+    if (!p->At) return FGPU_OK;
+    DevBuf<u32> cnt;                                     // vertices a search can discover at all: those with an in-edge
+    FGPU_TRY(cnt.alloc(ctx, 1));
+    if (hipMemsetAsync(cnt.p, 0, sizeof(u32), ctx->stream()) != hipSuccess) return FGPU_DEVICE;
+    FGPU_TRY(launch(bfs_count_alive_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)p->At->rowptr, p->n, cnt.p));
+    return read_u32(ctx, cnt.p, &p->n_alive);
+}
+
+static fgpu_info pb_build(fgpu_bfs_plan* p, PbBufs& b) {
+    fgpu_ctx* ctx = p->ctx;
+    const u64 nnz = p->A->nnz;
+    while (((u64)PB_BINS << b.shift) < (u64)p->nw * 64) ++b.shift;
+    b.maxchunks = (u32)(nnz / PB_C) + 2;
+    const size_t small = (size_t)4 * PB_LMAX + 8 + (size_t)b.maxchunks + 2 + (size_t)ctx->cus * 2 * PB_BINS + 64;
+    FGPU_TRY(b.ctl.alloc(ctx, 1));
+    FGPU_TRY(b.small.alloc(ctx, small));
+    FGPU_TRY(b.dst.alloc(ctx, (size_t)nnz + PB_C));
+    FGPU_TRY(b.src.alloc(ctx, (size_t)nnz + PB_C));
+    BfsPb h;
+    memset(&h, 0, sizeof(u32) * 32);
+    h.shift = b.shift;
+    if (hipMemsetAsync(b.ctl.p, 0, sizeof(BfsPb), ctx->stream()) != hipSuccess ||
+        hipMemcpyAsync(b.ctl.p, &h, sizeof(u32) * 32, hipMemcpyHostToDevice, ctx->stream()) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream()) != hipSuccess)
+        return FGPU_DEVICE;
+    if (!p->At) return FGPU_OK;
+    FGPU_TRY(b.alive.alloc(ctx, p->nw));
+    FGPU_TRY(launch(bfs_alive_bits_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)p->At->rowptr, p->n, p->nw, b.alive.p));
+    return fgpu_sync(ctx);
+}
+
+// propagation blocking of heavy push levels: plans of >= 2^24 vertices (option bfs_pb; 2 = any).  With alpha as it was tuned for
+// the atomic push RMAT-24 has no level heavy enough (0.513 -> 0.528 ms from the armed launches alone); with the blocked push
+// being 3 x cheaper the rule should push for longer — alpha 8 there: 0.504 -> 0.473 ms.  RMAT-22: 0.196 -> 0.205 ms whatever
+// alpha and threshold (a heavy push of 10^6 edges is 70 us; five launches are 25), windows of at most 2^19
+// vertices (64 KiB of LDS), the bins sized for every edge of A.  An optional accelerator: without its memory the plan
+// simply pushes as before.
+static fgpu_info plan_pb(fgpu_bfs_plan* p) {
+    fgpu_ctx* ctx = p->ctx;
+    if (!(p->nranks == 1 && p->splits.empty() && ctx->opt.bfs_pb && (ctx->opt.bfs_pb == 2 || p->n >= (1u << 24)) &&
+          (u64)p->nw * 64 <= ((u64)PB_BINS << 19) && p->A->nnz + PB_C < 0xFFFFFFFFull))
+        return FGPU_OK;
+    PbBufs b;
+    if (pb_build(p, b) != FGPU_OK) {   // the plan stays without: what was built goes back with `b`, and so does the error
+        (void)hipGetLastError();
+        set_error("%s", "");
+        return FGPU_OK;
+    }
+    p->pb = std::move(b);
+    return pb_raise_limits();
+}
+
+static void plan_grids(fgpu_bfs_plan* p) {
+    fgpu_ctx* ctx = p->ctx;
+    // one launch serves both directions (picked on device): size the grid for the larger of
+    // push items (1024-vertex blocks + hub chunks) and pull trips (4 waves x PULL_R words)
+    u64 push_items = ((u64)p->n + PUSH_VPB - 1) / PUSH_VPB + p->A->n_push_chunks;
+    u64 pull_blocks = (((u64)p->n + 63) / 64 + PULL_R * 4 - 1) / (PULL_R * 4);
+    u64 g = push_items > pull_blocks ? push_items : pull_blocks;
+    if (g < (u64)ctx->cus * 4) g = (u64)ctx->cus * 4;
+    if (g > 65536) g = 65536;
+    p->grid = (u32)g;
+    // one resident round: the hardware admits 7 of these 256-thread workgroups per CU at this
+    // SGPR count (MI355X_MICROARCH.md "Residency"), a grid just above that runs a near-empty second round
+    u64 fg = (u64)ctx->cus * (u64)ctx->opt.bfs_wgs_per_cu;
+    if (fg > g) fg = g;
+    p->fgrid = (u32)fg & ~1u;                     // even: the low bit of a launch's grid size is its parity
+    if (p->fgrid == 0) p->fgrid = 2;
+    if (getenv("FGPU_BFS_OCC")) {
+        int nb0 = 0, nb1 = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb0, bfs_fused_kernel<false, 0>, 256, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb1, bfs_fused_kernel<true, 0>, 256, 0);
+        fprintf(stderr, "bfs_fused_kernel residency (workgroups per CU): %d without / %d with parents; grid %u = %u per CU\n",
+                nb0, nb1, p->fgrid, p->fgrid / (u32)ctx->cus);
+    }
+}
+
 static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat* A, const fgpu_mat* At, int rank,
                              int nranks, const uint64_t* splits) {
     FGPU_REQUIRE(ctx && out && A, FGPU_NULL_POINTER, "fgpu_bfs_plan_create: NULL argument");
@@ -2644,150 +2840,17 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
     FGPU_TRY(mat_ensure_finalized(A));   // hub lists of snapshots that came out of a merge
     if (At) FGPU_TRY(mat_ensure_finalized(At));
     if (At && ctx->opt.bfs_hub_first) FGPU_TRY(ensure_pull_order(ctx, At, A));
-    fgpu_bfs_plan* p = new (std::nothrow) fgpu_bfs_plan();
+    std::unique_ptr<fgpu_bfs_plan, fgpu_info (*)(fgpu_bfs_plan*)> p(new (std::nothrow) fgpu_bfs_plan(), fgpu_bfs_plan_free);
     FGPU_REQUIRE(p, FGPU_OOM, "out of host memory");
     p->ctx = ctx; p->A = A; p->At = At; p->rank = rank; p->nranks = nranks;
     p->n = (u32)A->nrows;
-    if (splits) {
-        // caller-chosen slab boundaries (nnz-balanced, fgpu_mat_balanced_splits): ascending multiples of 4096 from 0 to
-        // the vertex count rounded up to 4096; the global frontier bitmap keeps its plain layout, rank r's words
-        // sit at word splits[r] / 64
-        bool ok = splits[0] == 0 && splits[nranks] >= A->nrows && splits[nranks] < A->nrows + 4096 &&
-                  splits[nranks] < 0xFFFFF000ull;
-        for (int r = 0; r < nranks && ok; ++r) ok = splits[r] <= splits[r + 1] && (splits[r + 1] & 4095ull) == 0;
-        if (!ok) {
-            delete p;
-            set_error("fgpu_bfs_plan_create_slab: splits must ascend from 0 to ceil4096(n) in multiples of 4096");
-            return FGPU_INVALID;
-        }
-        p->splits.assign(splits, splits + nranks + 1);
-        p->lo = (u32)splits[rank];
-        p->hi = (u32)splits[rank + 1];
-        p->slab = p->hi - p->lo;
-        p->slabw = p->slab / 64;
-        p->nw = (u32)(splits[nranks] / 64);
-    } else {
-        // equal slabs: the one definition of the rounding lives in fgpu_slab_layout (dist.hip)
-        std::vector<u64> lo(nranks), hi(nranks);
-        fgpu_info li = fgpu_slab_layout(nullptr, A->nrows, nranks, lo.data(), hi.data(), nullptr, nullptr);
-        if (li != FGPU_OK) { delete p; return li; }
-        p->lo = (u32)lo[rank];
-        p->hi = (u32)hi[rank];
-        p->slab = p->hi - p->lo;
-        p->slabw = p->slab / 64;
-        p->nw = p->slabw * nranks;
-    }
-    fgpu_info i = FGPU_OK;
-    const size_t wb = (size_t)p->nw * sizeof(u64);
-    do {
-        if ((i = ctx->dev_alloc((void**)&p->cur, wb)) != FGPU_OK) break;
-        if ((i = ctx->dev_alloc((void**)&p->nxt_global, wb)) != FGPU_OK) break;
-        if (nranks == 1) p->nxt_local = p->nxt_global;
-        else if ((i = ctx->dev_alloc((void**)&p->nxt_local, ((size_t)p->slabw + 1) * sizeof(u64))) != FGPU_OK) break;
-        if ((i = ctx->dev_alloc((void**)&p->visited, wb)) != FGPU_OK) break;
-        if ((i = ctx->dev_alloc((void**)&p->level, (size_t)p->nw * 64 * sizeof(i32))) != FGPU_OK) break;
-        if ((i = ctx->dev_alloc((void**)&p->parent, (size_t)p->nw * 64 * sizeof(u32))) != FGPU_OK) break;
-        if ((i = ctx->dev_alloc((void**)&p->ctrl, sizeof(BfsCtrl))) != FGPU_OK) break;
-        if (nranks == 1 && (i = ctx->dev_alloc((void**)&p->bm_block, 4 * wb)) != FGPU_OK) break;
-        if (nranks == 1 && (i = ctx->dev_alloc((void**)&p->queue_block, 2 * (size_t)QCAP * sizeof(u32))) != FGPU_OK) break;
-        if (At) {
-            p->pull_colidx = (At->pull_col && ctx->opt.bfs_hub_first) ? At->pull_col : At->colidx;
-            if ((i = ctx->dev_alloc((void**)&p->pull_head, (size_t)p->nw * 64 * sizeof(headv))) != FGPU_OK) break;
-            if ((i = launch(pull_head_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->pull_colidx,
-                            p->n, p->nw * 64, p->pull_head)) != FGPU_OK) break;
-        }
-    } while (0);
-    if (i == FGPU_OK) {
-        static_assert(sizeof(BfsCtrl) <= 32768, "a plan's control block copy lives in one flag_alloc block");
-        p->h_ctrl = (BfsCtrl*)ctx->flag_alloc();
-        p->h_done = (u32*)ctx->flag_alloc();
-        hipError_t e = (p->h_ctrl && p->h_done) ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&p->d_done, p->h_done, 0);
-        if (e == hipSuccess) *(volatile u32*)p->h_done = 0;
-        if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-        if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-        if (e == hipSuccess) e = hipMemsetAsync(p->nxt_global, 0, wb, ctx->stream());
-        if (e == hipSuccess && nranks > 1)
-            e = hipMemsetAsync(p->nxt_local, 0, (size_t)p->slabw * sizeof(u64), ctx->stream());
-        if (e != hipSuccess) { set_error("bfs plan setup failed: %s", hipGetErrorString(e)); i = FGPU_DEVICE; }
-    }
-    // the degree a discovery adds to the next frontier's edge count: read from a 4-byte array (measured at RMAT-26: the slab path,
-    // which always had one, ran its heavy levels faster than the row-pointer pair of the single-rank path once it stopped reading both)
-    if (i == FGPU_OK && nranks == 1) {
-        i = ctx->dev_alloc((void**)&p->own_deg, ((size_t)p->n + 1) * sizeof(u32));
-        if (i == FGPU_OK) i = fgpu_mat_row_degrees(ctx, A, p->own_deg);
-        if (i == FGPU_OK && At) {                            // vertices a search can discover at all: those with an in-edge
-            DevBuf<u32> cnt;
-            i = cnt.alloc(ctx, 1);
-            if (i == FGPU_OK && hipMemsetAsync(cnt.p, 0, sizeof(u32), ctx->stream()) != hipSuccess) i = FGPU_DEVICE;
-            if (i == FGPU_OK) i = launch(bfs_count_alive_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, cnt.p);
-            if (i == FGPU_OK) i = read_u32(ctx, cnt.p, &p->n_alive);
-        }
-    }
-    // propagation blocking of heavy push levels: plans of >= 2^24 vertices (option bfs_pb; 2 = any).  With alpha as it was tuned for
-    // the atomic push RMAT-24 has no level heavy enough (0.513 -> 0.528 ms from the armed launches alone); with the blocked push
-    // being 3 x cheaper the rule should push for longer — alpha 8 there: 0.504 -> 0.473 ms.  RMAT-22: 0.196 -> 0.205 ms whatever
-    // alpha and threshold (a heavy push of 10^6 edges is 70 us; five launches are 25), windows of at most 2^19
-    // vertices (64 KiB of LDS), the bins sized for every edge of A.  An optional accelerator: without its memory the plan
-    // simply pushes as before.
-    if (i == FGPU_OK && nranks == 1 && !splits && ctx->opt.bfs_pb &&
-        (ctx->opt.bfs_pb == 2 || p->n >= (1u << 24)) && (u64)p->nw * 64 <= ((u64)PB_BINS << 19) && A->nnz + PB_C < 0xFFFFFFFFull) {
-        u32 shift = 6;
-        while (((u64)PB_BINS << shift) < (u64)p->nw * 64) ++shift;
-        p->pb_maxchunks = (u32)(A->nnz / PB_C) + 2;
-        const size_t small = (size_t)4 * PB_LMAX + 8 + (size_t)p->pb_maxchunks + 2 + (size_t)ctx->cus * 2 * PB_BINS + 64;
-        fgpu_info pi = ctx->dev_alloc((void**)&p->pb, sizeof(BfsPb));
-        if (pi == FGPU_OK) pi = ctx->dev_alloc((void**)&p->pb_small, small * sizeof(u32));
-        if (pi == FGPU_OK) pi = ctx->dev_alloc((void**)&p->pb_dst, ((size_t)A->nnz + PB_C) * sizeof(u32));
-        if (pi == FGPU_OK) pi = ctx->dev_alloc((void**)&p->pb_src, ((size_t)A->nnz + PB_C) * sizeof(u32));
-        if (pi == FGPU_OK) {
-            BfsPb h;
-            memset(&h, 0, sizeof(u32) * 32);
-            h.shift = shift;
-            if (hipMemsetAsync(p->pb, 0, sizeof(BfsPb), ctx->stream()) != hipSuccess ||
-                hipMemcpyAsync(p->pb, &h, sizeof(u32) * 32, hipMemcpyHostToDevice, ctx->stream()) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream()) != hipSuccess)
-                pi = FGPU_DEVICE;
-        }
-        if (pi == FGPU_OK && At) {
-            pi = ctx->dev_alloc((void**)&p->alive, (size_t)p->nw * sizeof(u64));
-            if (pi == FGPU_OK) pi = launch(bfs_alive_bits_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, p->n, p->nw, p->alive);
-            if (pi == FGPU_OK) pi = fgpu_sync(ctx);
-        }
-        if (pi != FGPU_OK) {
-            ctx->dev_free(p->alive); p->alive = nullptr;
-            ctx->dev_free(p->pb); ctx->dev_free(p->pb_small); ctx->dev_free(p->pb_dst); ctx->dev_free(p->pb_src);
-            p->pb = nullptr; p->pb_small = nullptr; p->pb_dst = nullptr; p->pb_src = nullptr;
-            (void)hipGetLastError();
-            set_error("%s", "");
-        }
-    }
-    if (i == FGPU_OK && p->pb) i = pb_raise_limits();
-    if (i != FGPU_OK) { fgpu_bfs_plan_free(p); return i; }
-    memset(p->h_ctrl, 0, sizeof(BfsCtrl));
-    {
-        // one launch serves both directions (picked on device): size the grid for the larger of
-        // push items (1024-vertex blocks + hub chunks) and pull trips (4 waves x PULL_R words)
-        u64 push_items = ((u64)p->n + PUSH_VPB - 1) / PUSH_VPB + A->n_push_chunks;
-        u64 pull_blocks = (((u64)p->n + 63) / 64 + PULL_R * 4 - 1) / (PULL_R * 4);
-        u64 g = push_items > pull_blocks ? push_items : pull_blocks;
-        if (g < (u64)ctx->cus * 4) g = (u64)ctx->cus * 4;
-        if (g > 65536) g = 65536;
-        p->grid = (u32)g;
-        // one resident round: the hardware admits 7 of these 256-thread workgroups per CU at this
-        // SGPR count (MI355X_MICROARCH.md "Residency"), a grid just above that runs a near-empty second round
-        u64 fg = (u64)ctx->cus * (u64)ctx->opt.bfs_wgs_per_cu;
-        if (fg > g) fg = g;
-        p->fgrid = (u32)fg & ~1u;                     // even: the low bit of a launch's grid size is its parity
-        if (p->fgrid == 0) p->fgrid = 2;
-        if (getenv("FGPU_BFS_OCC")) {
-            int nb0 = 0, nb1 = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb0, bfs_fused_kernel<false, 0>, 256, 0);
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb1, bfs_fused_kernel<true, 0>, 256, 0);
-            fprintf(stderr, "bfs_fused_kernel residency (workgroups per CU): %d without / %d with parents; grid %u = %u per CU\n",
-                    nb0, nb1, p->fgrid, p->fgrid / (u32)ctx->cus);
-        }
-    }
+    FGPU_TRY(plan_layout(p.get(), splits));
+    FGPU_TRY(plan_buffers(p.get()));
+    FGPU_TRY(plan_pull_head(p.get()));
+    FGPU_TRY(plan_flags(p.get()));
+    FGPU_TRY(plan_alive(p.get()));
+    FGPU_TRY(plan_pb(p.get()));
+    plan_grids(p.get());
     // Default push -> pull switch factor.  A pull level probes the N-bit frontier bitmap once per scanned in-edge: while
     // the bitmap sits in every XCD's 4 MiB L2 (<= 2 MiB: up to 2^24 vertices) pulling early pays, alpha = 32 (RMAT-22:
     // 286.6 GTEPS at 32, 283.3 at 24, 278.5 at 20; RMAT-24 flat from 16 to 32); once it does not (RMAT-26: 8 MiB) the same
@@ -2802,7 +2865,7 @@ static fgpu_info plan_create(fgpu_ctx* ctx, fgpu_bfs_plan** out, const fgpu_mat*
     // with a 1 M-edge threshold**, 0.490 at 20.
     if (p->pb) p->alpha = ((size_t)p->nw * sizeof(u64) > (2u << 20)) ? 6.0 : 8.0;
     p->prof = {{"bfs_fused_kernel<false, 1> (push level)"}, {"bfs_fused_kernel<false, 2> (pull level)"}};
-    *out = p;
+    *out = p.release();
     return FGPU_OK;
 }
 
@@ -2828,18 +2891,8 @@ fgpu_info fgpu_bfs_part_set_buffers(fgpu_bfs_plan* p, void* local_words, void* g
     FGPU_REQUIRE(p && local_words && global_words, FGPU_NULL_POINTER, "fgpu_bfs_part_set_buffers: NULL argument");
     FGPU_REQUIRE(p->nranks == 1 ? true : local_words != global_words, FGPU_INVALID,
                  "multi-rank plans need distinct local and global buffers");
-    fgpu_ctx* c = p->ctx;
-    if (!p->external_bufs) {
-        if (p->nxt_local != p->nxt_global) c->dev_free(p->nxt_local);
-        c->dev_free(p->nxt_global);
-    }
-    p->external_bufs = true;
-    p->nxt_local = (u64*)local_words;
-    p->nxt_global = (u64*)global_words;
-    if (p->nranks == 1) p->nxt_local = p->nxt_global;
-    FGPU_HIP(hipMemsetAsync(p->nxt_global, 0, (size_t)p->nw * sizeof(u64), c->stream()));
-    if (p->nxt_local != p->nxt_global)
-        FGPU_HIP(hipMemsetAsync(p->nxt_local, 0, (size_t)p->slabw * sizeof(u64), c->stream()));
+    p->adopt_buffers((u64*)(p->nranks == 1 ? global_words : local_words), (u64*)global_words);
+    FGPU_HIP(zero_frontier_pair(p));
     return FGPU_OK;
 }
 
@@ -2849,36 +2902,31 @@ fgpu_info fgpu_bfs_part_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level)
     fgpu_ctx* ctx = p->ctx;
     p->levels_masked = true;   // bfs_init_kernel clears level[] itself on this path
     const size_t wb = (size_t)p->nw * sizeof(u64);
-    FGPU_HIP(hipMemsetAsync(p->cur, 0, wb, ctx->stream()));
-    FGPU_HIP(hipMemsetAsync(p->visited, 0, wb, ctx->stream()));
-    FGPU_HIP(hipMemsetAsync(p->nxt_global, 0, wb, ctx->stream()));
-    if (p->nxt_local != p->nxt_global)
-        FGPU_HIP(hipMemsetAsync(p->nxt_local, 0, (size_t)p->slabw * sizeof(u64), ctx->stream()));
-    FGPU_HIP(hipMemsetAsync(p->level + p->lo, 0xFF, (size_t)p->slab * sizeof(i32), ctx->stream()));
-    FGPU_HIP(hipMemsetAsync(p->ctrl, 0, sizeof(BfsCtrl), ctx->stream()));
-    i32 ml = max_level < 0 ? -1 : (max_level > 0x7FFFFFFF ? 0x7FFFFFFF : (i32)max_level);
+    FGPU_HIP(hipMemsetAsync(p->cur.p, 0, wb, ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(p->visited.p, 0, wb, ctx->stream()));
+    FGPU_HIP(zero_frontier_pair(p));
+    FGPU_HIP(hipMemsetAsync(p->level.p + p->lo, 0xFF, (size_t)p->slab * sizeof(i32), ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(p->ctrl.p, 0, sizeof(BfsCtrl), ctx->stream()));
     BfsArgs a = make_args(p);
-    FGPU_TRY(launch(bfs_init_kernel, dim3(1), dim3(1), 0, ctx->stream(), a, (u32)src, ml, p->At ? 1u : 0u,
+    FGPU_TRY(launch(bfs_init_kernel, dim3(1), dim3(1), 0, ctx->stream(), a, (u32)src, clamp_level(max_level), p->At ? 1u : 0u,
                     (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull, 0ull));
     return FGPU_OK;
 }
 
 // fused slab path (multi-rank v2) ----------------------------------------------------------
+// one gathered bitmap (also the frontier pair) and two send slabs: the caller's, or the plan's own dist_* blocks
+static void slab_install(fgpu_bfs_plan* p, u64* send0, u64* send1, u64* global) {
+    p->adopt_buffers(global, global);
+    p->slab_glob[0] = p->slab_glob[1] = global;
+    p->slab_send[0] = send0;
+    p->slab_send[1] = send1;
+}
+
 fgpu_info fgpu_bfs_slab_set_buffers(fgpu_bfs_plan* p, void* send0, void* send1, void* global_words) {
     FGPU_REQUIRE(p && send0 && send1 && global_words, FGPU_NULL_POINTER, "fgpu_bfs_slab_set_buffers: NULL argument");
     FGPU_REQUIRE(send0 != send1 && send0 != global_words && send1 != global_words, FGPU_INVALID,
                  "fgpu_bfs_slab_set_buffers: the three buffers must be distinct");
-    fgpu_ctx* c = p->ctx;
-    if (!p->external_bufs) {
-        if (p->nxt_local != p->nxt_global) c->dev_free(p->nxt_local);
-        c->dev_free(p->nxt_global);
-    }
-    p->external_bufs = true;
-    p->nxt_global = (u64*)global_words;
-    p->nxt_local = p->nxt_global;
-    p->slab_glob[0] = p->slab_glob[1] = p->nxt_global;
-    p->slab_send[0] = (u64*)send0;
-    p->slab_send[1] = (u64*)send1;
+    slab_install(p, (u64*)send0, (u64*)send1, (u64*)global_words);
     return FGPU_OK;
 }
 
@@ -2911,16 +2959,15 @@ fgpu_info fgpu_bfs_slab_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level,
     FGPU_REQUIRE(p->slab_send[0] && p->slab_send[1], FGPU_INVALID, "fgpu_bfs_slab_begin: call fgpu_bfs_slab_set_buffers first");
     FGPU_REQUIRE(src < p->n, FGPU_OUT_OF_BOUNDS, "BFS source %llu >= %u vertices", (unsigned long long)src, p->n);
     fgpu_ctx* ctx = p->ctx;
-    i32 ml = max_level < 0 ? -1 : (max_level > 0x7FFFFFFF ? 0x7FFFFFFF : (i32)max_level);
     p->want_parent = want_parent != 0;
     p->launch = 0;
     p->levels_masked = false;
-    p->mask_visited = p->visited;
-    *(volatile u32*)p->h_done = 0;
+    p->mask_visited = p->visited.p;
+    *(volatile u32*)p->h_done.p = 0;
     BfsArgs a = slab_args(p);
     u64* z0 = p->inplace ? p->slab_ring[1] + (p->lo >> 6) : p->slab_send[0];
     u64* z1 = p->inplace ? p->slab_ring[2] + (p->lo >> 6) : p->slab_send[1];
-    FGPU_TRY(launch(bfs_slab_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, z0, z1, (u32)src, ml, p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha,
+    FGPU_TRY(launch(bfs_slab_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, z0, z1, (u32)src, clamp_level(max_level), p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha,
                     p->At ? p->At->nnz : 0ull));
     return FGPU_OK;
 }
@@ -2933,6 +2980,42 @@ fgpu_info fgpu_bfs_slab_level(fgpu_bfs_plan* p, int* send_index) {
     }));
     if (send_index) *send_index = (int)(p->launch & 1);
     p->launch += 1;
+    return FGPU_OK;
+}
+
+// the wait for a search's end -----------------------------------------------------------------
+// The last level raises the plan's pinned flag.  It is polled WITHOUT touching the stream for as long as a search may
+// reasonably take (twice the previous wait + 100 us): a stream query makes the runtime put a system-scope fence on the
+// next dispatch of the stream — 5.6-5.8 us of idle stream in front of every search when the query sat in the poll loop
+// (rocprofv3 kernel trace, tools/trace_levels.py).  Past that budget the stream is looked at now and then, so a search
+// that needs more levels than were enqueued (or a failed launch) is noticed.
+struct PollState {
+    const char* what;   // opens the message of a failed stream
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double quiet_us;    // no stream query before this
+    bool querying = false;
+    // ... twice the previous wait, but no more than 30 us per enqueued level (a level of an R-MAT search averages 20 us at
+    // scale 22, 200 us at scale 26 — there a 6 us fence no longer matters), and not at all once a top-up was needed
+    PollState(const char* w, double last_wait_us, int levels) : what(w), quiet_us(2.0 * last_wait_us + 100.0) {
+        if (quiet_us > 100.0 + 30.0 * levels) quiet_us = 100.0 + 30.0 * levels;
+    }
+    double waited_us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+};
+// returns once the plan's flag is raised (*done) or its stream has drained without it
+static fgpu_info poll_done(fgpu_bfs_plan* p, PollState& s, bool* done) {
+    volatile u32* flag = (volatile u32*)p->h_done.p;
+    for (u32 spin = 0; (*flag & 0x80000000u) == 0; ++spin) {
+        if (!s.querying && (spin & 0x3Fu) == 0x3Fu) s.querying = s.waited_us() > s.quiet_us;
+        if (s.querying && (spin & 0x3FFu) == 0x3FFu) {
+            hipError_t q = hipStreamQuery(p->ctx->stream());
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) {
+                set_error("%s: %s", s.what, hipGetErrorString(q));
+                return FGPU_DEVICE;
+            }
+        }
+    }
+    *done = (*flag & 0x80000000u) != 0;
     return FGPU_OK;
 }
 
@@ -2950,6 +3033,8 @@ __global__ void add_u32_kernel(u32* __restrict__ acc, const u32* __restrict__ x,
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) acc[i] += x[i];
 }
 
+static bool over_rccl(const fgpu_bfs_plan* p0) { return p0->ctx->comm != nullptr && p0->nranks > 1; }
+
 static fgpu_info dist_setup(fgpu_bfs_plan* const* P, int np) {
     bool all_ready = true;
     for (int k = 0; k < np; ++k) all_ready = all_ready && P[k]->dist_ready;
@@ -2957,19 +3042,24 @@ static fgpu_info dist_setup(fgpu_bfs_plan* const* P, int np) {
     for (int k = 0; k < np; ++k) {
         fgpu_bfs_plan* p = P[k];
         fgpu_ctx* c = p->ctx;
-        if (!p->dist_send[0]) {
-            FGPU_TRY(c->dev_alloc((void**)&p->dist_send[0], ((size_t)p->slabw + 1) * sizeof(u64)));
-            FGPU_TRY(c->dev_alloc((void**)&p->dist_send[1], ((size_t)p->slabw + 1) * sizeof(u64)));
-            FGPU_TRY(c->dev_alloc((void**)&p->dist_glob, ((size_t)p->nw + 1) * sizeof(u64)));
-            FGPU_TRY(c->dev_alloc((void**)&p->dist_deg, ((size_t)p->n + 1) * sizeof(u32)));
-            FGPU_TRY(fgpu_bfs_slab_set_buffers(p, p->dist_send[0], p->dist_send[1], p->dist_glob));
-            p->external_bufs = true;   // dist_* are released by fgpu_bfs_plan_free through their own fields
+        if (!p->dist_send[0].p) {   // all four or none: a failed allocation leaves the plan as it was
+            DevBuf<u64> s0, s1, g;
+            DevBuf<u32> deg;
+            FGPU_TRY(s0.alloc(c, (size_t)p->slabw + 1));
+            FGPU_TRY(s1.alloc(c, (size_t)p->slabw + 1));
+            FGPU_TRY(g.alloc(c, (size_t)p->nw + 1));
+            FGPU_TRY(deg.alloc(c, (size_t)p->n + 1));
+            p->dist_send[0] = std::move(s0);
+            p->dist_send[1] = std::move(s1);
+            p->dist_glob = std::move(g);
+            p->dist_deg = std::move(deg);
+            slab_install(p, p->dist_send[0].p, p->dist_send[1].p, p->dist_glob.p);
         }
         // global out-degrees: a column slab holds only its share of every row; the owner of a vertex accounts the
         // whole degree at discovery (edges_traversed) and feeds its push / pull rule with it
-        FGPU_TRY(fgpu_mat_row_degrees(c, p->A, p->dist_deg));
+        FGPU_TRY(fgpu_mat_row_degrees(c, p->A, p->dist_deg.p));
     }
-    const bool rccl = P[0]->ctx->comm != nullptr && P[0]->nranks > 1;
+    const bool rccl = over_rccl(P[0]);
     if (!rccl && np > 1) {   // peer exchange: a second frontier bitmap per rank (see slab_glob), peer access between the devices
         FGPU_REQUIRE(np <= 16, FGPU_INVALID, "fgpu_bfs_dist_run: the peer exchange of a single-process gang takes at most 16 ranks");
         for (int k = 0; k < np; ++k)
@@ -2989,21 +3079,23 @@ static fgpu_info dist_setup(fgpu_bfs_plan* const* P, int np) {
     if (rccl || np == 1)
         for (int k = 0; k < np; ++k) {
             fgpu_bfs_plan* p = P[k];
-            p->slab_ring[0] = p->dist_glob;
-            for (int j = 1; j < 3; ++j)
-                if (!p->slab_ring[j]) FGPU_TRY(p->ctx->dev_alloc((void**)&p->slab_ring[j], ((size_t)p->nw + 1) * sizeof(u64)));
+            p->slab_ring[0] = p->dist_glob.p;
+            for (int j = 0; j < 2; ++j) {
+                if (!p->ring_own[j].p) FGPU_TRY(p->ring_own[j].alloc(p->ctx, (size_t)p->nw + 1));
+                p->slab_ring[j + 1] = p->ring_own[j].p;
+            }
             p->inplace = true;
         }
     if (!rccl && np > 1)
         for (int k = 0; k < np; ++k) {
             fgpu_bfs_plan* p = P[k];
-            if (!p->dist_glob2) FGPU_TRY(p->ctx->dev_alloc((void**)&p->dist_glob2, ((size_t)p->nw + 1) * sizeof(u64)));
-            p->slab_glob[0] = p->dist_glob;
-            p->slab_glob[1] = p->dist_glob2;
+            if (!p->dist_glob2.p) FGPU_TRY(p->dist_glob2.alloc(p->ctx, (size_t)p->nw + 1));
+            p->slab_glob[0] = p->dist_glob.p;
+            p->slab_glob[1] = p->dist_glob2.p;
         }
     if (rccl || (np == 1 && P[0]->ctx->comm && P[0]->ctx->opt.dist_force_self)) {   // (second form: test-only, one rank on real RCCL)
         if (np > 1) FGPU_TRY(comm_group_begin());
-        for (int k = 0; k < np; ++k) FGPU_TRY(comm_allreduce_sum_u32(P[k]->ctx, P[k]->dist_deg, P[k]->n));
+        for (int k = 0; k < np; ++k) FGPU_TRY(comm_allreduce_sum_u32(P[k]->ctx, P[k]->dist_deg.p, P[k]->n));
         if (np > 1) FGPU_TRY(comm_group_end());
     } else if (np > 1) {
         // gang without a communicator (several slabs driven by one process, e.g. on one device): sum on plan 0, copy back
@@ -3012,19 +3104,19 @@ static fgpu_info dist_setup(fgpu_bfs_plan* const* P, int np) {
         FGPU_TRY(tmp.alloc(c0, (size_t)P[0]->n + 1));
         for (int k = 1; k < np; ++k) {
             FGPU_HIP(hipStreamSynchronize(P[k]->ctx->stream()));
-            FGPU_HIP(hipMemcpyAsync(tmp.p, P[k]->dist_deg, (size_t)P[0]->n * sizeof(u32), hipMemcpyDefault, c0->stream()));
-            FGPU_TRY(launch(add_u32_kernel, dim3(c0->cus * 8), dim3(256), 0, c0->stream(), P[0]->dist_deg,
+            FGPU_HIP(hipMemcpyAsync(tmp.p, P[k]->dist_deg.p, (size_t)P[0]->n * sizeof(u32), hipMemcpyDefault, c0->stream()));
+            FGPU_TRY(launch(add_u32_kernel, dim3(c0->cus * 8), dim3(256), 0, c0->stream(), P[0]->dist_deg.p,
                             (const u32*)tmp.p, (u64)P[0]->n));
         }
         FGPU_HIP(hipStreamSynchronize(c0->stream()));
         for (int k = 1; k < np; ++k) {
-            FGPU_HIP(hipMemcpyAsync(P[k]->dist_deg, P[0]->dist_deg, (size_t)P[0]->n * sizeof(u32), hipMemcpyDefault,
+            FGPU_HIP(hipMemcpyAsync(P[k]->dist_deg.p, P[0]->dist_deg.p, (size_t)P[0]->n * sizeof(u32), hipMemcpyDefault,
                                     P[k]->ctx->stream()));
             FGPU_HIP(hipStreamSynchronize(P[k]->ctx->stream()));
         }
     }
     for (int k = 0; k < np; ++k) {
-        FGPU_TRY(fgpu_bfs_slab_set_degrees(P[k], P[k]->dist_deg));
+        FGPU_TRY(fgpu_bfs_slab_set_degrees(P[k], P[k]->dist_deg.p));
         FGPU_HIP(hipStreamSynchronize(P[k]->ctx->stream()));
         P[k]->dist_ready = true;
     }
@@ -3056,11 +3148,11 @@ __global__ __launch_bounds__(256) void dist_scatter_kernel(const u64* __restrict
 static fgpu_info dist_event(fgpu_bfs_plan* p, size_t idx) {
     (void)p->ctx->lane();   // the plan's device must be current when its events are created (a gang spans devices)
     while (p->dist_ev.size() <= idx) {
-        hipEvent_t e = nullptr;
-        FGPU_HIP(hipEventCreate(&e));
-        p->dist_ev.push_back(e);
+        Event e;
+        FGPU_HIP(e.create());
+        p->dist_ev.push_back(std::move(e));
     }
-    FGPU_HIP(hipEventRecord(p->dist_ev[idx], p->ctx->stream()));
+    FGPU_HIP(hipEventRecord(p->dist_ev[idx].e, p->ctx->stream()));
     return FGPU_OK;
 }
 
@@ -3071,7 +3163,19 @@ __global__ void dist_test_delay_kernel(u32 us) {
     while (wall_clock64() - t0 < (u64)us * 100ull) __builtin_amdgcn_s_sleep(16);
 }
 
-fgpu_info fgpu_bfs_dist_run(fgpu_bfs_plan* const* plans, int nplans, uint64_t src, int64_t max_level, int want_parent) {
+// one search of fgpu_bfs_dist_run: what its steps share
+struct DistRun {
+    fgpu_bfs_plan* const* plans;
+    int np;
+    bool rccl, peer;         // the exchange: through the communicator; by stores into the peers' bitmaps (neither: one rank)
+    bool timed;              // three timing events per rank and level keep the stream waiting ~20 us a level (measured: 6 + 10 us
+                             // of gaps around the exchange at RMAT-26): recorded only when the "dist_timing" option asks for the time split
+    std::vector<u64> offs, cnts;
+    std::vector<int> idx;    // the send slab every rank's last level filled
+    u64 nlev = 0;            // levels enqueued so far
+};
+
+static fgpu_info dist_check(fgpu_bfs_plan* const* plans, int nplans) {
     FGPU_REQUIRE(plans && nplans >= 1 && plans[0], FGPU_NULL_POINTER, "fgpu_bfs_dist_run: NULL plans");
     fgpu_bfs_plan* p0 = plans[0];
     FGPU_REQUIRE(nplans == 1 || nplans == p0->nranks, FGPU_INVALID,
@@ -3081,144 +3185,137 @@ fgpu_info fgpu_bfs_dist_run(fgpu_bfs_plan* const* plans, int nplans, uint64_t sr
                      FGPU_INVALID, "fgpu_bfs_dist_run: plan %d does not belong to the same partition", k);
         FGPU_REQUIRE(nplans == 1 || plans[k]->rank == k, FGPU_INVALID, "fgpu_bfs_dist_run: plans must come in rank order");
     }
-    const bool rccl = p0->ctx->comm != nullptr && p0->nranks > 1;
+    const bool rccl = over_rccl(p0);
     FGPU_REQUIRE(nplans == p0->nranks || rccl, FGPU_INVALID,
                  "fgpu_bfs_dist_run: rank %d of %d has no communicator (fgpu_comm_init_rank / fgpu_comm_init_all)",
                  p0->rank, p0->nranks);
     FGPU_REQUIRE(!rccl || (p0->ctx->comm_nranks == p0->nranks && (nplans > 1 || p0->ctx->comm_rank == p0->rank)),
                  FGPU_INVALID, "fgpu_bfs_dist_run: the plan's rank / size differ from its context's communicator");
-    FGPU_TRY(dist_setup(plans, nplans));
-    std::vector<u64> offs, cnts;
-    FGPU_TRY(slab_layout(p0, offs, cnts));
-    for (int k = 0; k < nplans; ++k) FGPU_TRY(fgpu_bfs_slab_begin(plans[k], src, max_level, want_parent));
-    std::vector<hipEvent_t> copied(nplans, nullptr);   // peer mode only: "rank s has delivered its words of this level"
-    const bool peer = !rccl && nplans > 1;
-    if (peer)
-        for (int k = 0; k < nplans; ++k) {
-            if (!plans[k]->dist_copied) {
-                (void)plans[k]->ctx->lane();   // events of plan k live on plan k's device
-                FGPU_HIP(hipEventCreateWithFlags(&plans[k]->dist_copied, hipEventDisableTiming));
-            }
-            copied[k] = plans[k]->dist_copied;
-        }
-    fgpu_info rc = FGPU_OK;
-    int budget = p0->last_levels ? (p0->last_levels + 1 > 4 ? p0->last_levels + 1 : 4) : 6;
-    u64 nlev = 0;
-    std::vector<int> idx(nplans, 0);
-    // three timing events per rank and level keep the stream waiting ~20 us a level (measured: 6 + 10 us of gaps around
-    // the exchange at RMAT-26): they are recorded only when the "dist_timing" option asks for the time split
-    const bool timed = p0->ctx->opt.dist_timing != 0;
-    auto one_level = [&]() -> fgpu_info {
-        for (int k = 0; k < nplans; ++k) {
-            if (timed) FGPU_TRY(dist_event(plans[k], 3 * nlev));
-            FGPU_TRY(fgpu_bfs_slab_level(plans[k], &idx[k]));
-            if (plans[k]->ctx->opt.dist_test_delay_us > 0) {
-                FGPU_TRY(launch(dist_test_delay_kernel, dim3(1), dim3(1), 0, plans[k]->ctx->stream(), (u32)plans[k]->ctx->opt.dist_test_delay_us));
-            }
-            if (timed) FGPU_TRY(dist_event(plans[k], 3 * nlev + 1));
-        }
-        if (!peer) {
-            if (rccl && nplans > 1) FGPU_TRY(comm_group_begin());
-            for (int k = 0; k < nplans; ++k) {
-                fgpu_bfs_plan* p = plans[k];
-                // in place: the level just wrote its owned words where the gathered bitmap keeps them (launch was advanced)
-                u64* g = p->inplace ? p->slab_ring[p->launch % 3] : p->dist_glob;
-                const u64* snd = p->inplace ? g + offs[p->rank] : p->dist_send[idx[k]];
-                FGPU_TRY(comm_allgatherv_u64(p->ctx, snd, g, offs.data(), cnts.data()));
-            }
-            if (rccl && nplans > 1) FGPU_TRY(comm_group_end());
-        } else {
-            // every rank's slab goes to every rank's bitmap: one scatter launch per SOURCE rank on its own stream (right
-            // behind the level kernel that produced the words); a rank's next level — which reads its whole bitmap and
-            // clears the send buffer it is about to reuse — waits for every source's scatter
-            for (int s = 0; s < nplans; ++s) {
-                if (cnts[s]) {
-                    (void)plans[s]->ctx->lane();
-                    PeerDsts pd;
-                    for (int d = 0; d < nplans; ++d) pd.p[d] = plans[d]->slab_glob[plans[d]->launch & 1] + offs[s];   // what the NEXT launch reads
-                    u32 gx = (u32)((cnts[s] / 2 + 255) / 256);
-                    if (gx > 64) gx = 64;
-                    FGPU_TRY(launch(dist_scatter_kernel, dim3(gx ? gx : 1, nplans), dim3(256), 0, plans[s]->ctx->stream(),
-                                    (const u64*)plans[s]->dist_send[idx[s]], cnts[s], pd));
-                }
-                FGPU_HIP(hipEventRecord(copied[s], plans[s]->ctx->stream()));
-            }
-            for (int d = 0; d < nplans; ++d)
-                for (int s = 0; s < nplans; ++s)
-                    if (s != d) FGPU_HIP(hipStreamWaitEvent(plans[d]->ctx->stream(), copied[s], 0));
-        }
-        if (timed)
-            for (int k = 0; k < nplans; ++k) FGPU_TRY(dist_event(plans[k], 3 * nlev + 2));
-        ++nlev;
-        return FGPU_OK;
-    };
-    // Termination: the level that empties the frontier raises every plan's pinned flag (fused_ctrl, slab branch; the
-    // decision is the same on every rank), so the host polls a host word instead of paying a D2H copy + stream sync
-    // per search (~80 us of idle stream between two searches at RMAT-26); the stream is queried now and then so that a
-    // search needing more levels than were enqueued — or a failed launch — is noticed.
-    const auto wt0 = std::chrono::steady_clock::now();
-    auto waited_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - wt0).count(); };
-    double quiet_us = 2.0 * p0->last_wait_us + 100.0;   // no stream query before this (fgpu_bfs_wait says why)
-    if (quiet_us > 100.0 + 30.0 * budget) quiet_us = 100.0 + 30.0 * budget;
-    bool querying = false;
-    int topup = 2;
-    auto wait_flag = [&](fgpu_bfs_plan* p, bool* done) -> fgpu_info {
-        volatile u32* flag = (volatile u32*)p->h_done;
-        (void)p->ctx->lane();
-        for (u32 spin = 0; (*flag & 0x80000000u) == 0; ++spin) {
-            if (!querying && (spin & 0x3Fu) == 0x3Fu) querying = waited_us() > quiet_us;
-            if (querying && (spin & 0x3FFu) == 0x3FFu) {
-                hipError_t q = hipStreamQuery(p->ctx->stream());
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) {
-                    set_error("fgpu_bfs_dist_run: stream failed: %s", hipGetErrorString(q));
-                    return FGPU_DEVICE;
-                }
-            }
-        }
-        *done = (*flag & 0x80000000u) != 0;
-        return FGPU_OK;
-    };
-    while (rc == FGPU_OK) {
-        for (int k = 0; k < budget && rc == FGPU_OK; ++k) rc = one_level();
-        if (rc != FGPU_OK) break;
-        bool done = false;
-        rc = wait_flag(p0, &done);
-        if (rc != FGPU_OK || done) break;
-        rc = fetch_ctrl(p0);   // stream drained without the flag: not done yet, or done without a level having run (max_level 0)
-        if (rc != FGPU_OK || p0->h_ctrl->done) break;
-        querying = true;
-        budget = topup;                      // short of levels: 2 more, then 4, 8, ...
-        if (topup < 512) topup *= 2;
+    return FGPU_OK;
+}
+
+// all-gather-v through the communicator (a self copy for one rank)
+static fgpu_info exchange_comm(const DistRun& r) {
+    const bool group = r.rccl && r.np > 1;
+    if (group) FGPU_TRY(comm_group_begin());
+    for (int k = 0; k < r.np; ++k) {
+        fgpu_bfs_plan* p = r.plans[k];
+        // in place: the level just wrote its owned words where the gathered bitmap keeps them (launch was advanced)
+        u64* g = p->inplace ? p->slab_ring[p->launch % 3] : p->dist_glob.p;
+        const u64* snd = p->inplace ? g + r.offs[p->rank] : p->dist_send[r.idx[k]].p;
+        FGPU_TRY(comm_allgatherv_u64(p->ctx, snd, g, r.offs.data(), r.cnts.data()));
     }
-    if (rc != FGPU_OK) return rc;
-    p0->last_wait_us = waited_us();
-    const u32 fl0 = *(volatile u32*)p0->h_done;
+    if (group) FGPU_TRY(comm_group_end());
+    return FGPU_OK;
+}
+
+// every rank's slab goes to every rank's bitmap: one scatter launch per SOURCE rank on its own stream (right
+// behind the level kernel that produced the words); a rank's next level — which reads its whole bitmap and
+// clears the send buffer it is about to reuse — waits for every source's scatter
+static fgpu_info exchange_peer(const DistRun& r) {
+    for (int s = 0; s < r.np; ++s) {
+        fgpu_bfs_plan* ps = r.plans[s];
+        if (r.cnts[s]) {
+            (void)ps->ctx->lane();
+            PeerDsts pd;
+            for (int d = 0; d < r.np; ++d) pd.p[d] = r.plans[d]->slab_glob[r.plans[d]->launch & 1] + r.offs[s];   // what the NEXT launch reads
+            u32 gx = (u32)((r.cnts[s] / 2 + 255) / 256);
+            if (gx > 64) gx = 64;
+            FGPU_TRY(launch(dist_scatter_kernel, dim3(gx ? gx : 1, r.np), dim3(256), 0, ps->ctx->stream(),
+                            (const u64*)ps->dist_send[r.idx[s]].p, r.cnts[s], pd));
+        }
+        FGPU_HIP(hipEventRecord(ps->dist_copied.e, ps->ctx->stream()));
+    }
+    for (int d = 0; d < r.np; ++d)
+        for (int s = 0; s < r.np; ++s)
+            if (s != d) FGPU_HIP(hipStreamWaitEvent(r.plans[d]->ctx->stream(), r.plans[s]->dist_copied.e, 0));
+    return FGPU_OK;
+}
+
+static fgpu_info dist_level(DistRun& r) {
+    for (int k = 0; k < r.np; ++k) {
+        fgpu_bfs_plan* p = r.plans[k];
+        if (r.timed) FGPU_TRY(dist_event(p, 3 * r.nlev));
+        FGPU_TRY(fgpu_bfs_slab_level(p, &r.idx[k]));
+        if (p->ctx->opt.dist_test_delay_us > 0) {
+            FGPU_TRY(launch(dist_test_delay_kernel, dim3(1), dim3(1), 0, p->ctx->stream(), (u32)p->ctx->opt.dist_test_delay_us));
+        }
+        if (r.timed) FGPU_TRY(dist_event(p, 3 * r.nlev + 1));
+    }
+    FGPU_TRY(r.peer ? exchange_peer(r) : exchange_comm(r));
+    if (r.timed)
+        for (int k = 0; k < r.np; ++k) FGPU_TRY(dist_event(r.plans[k], 3 * r.nlev + 2));
+    ++r.nlev;
+    return FGPU_OK;
+}
+
+// the first plan's search has ended: the rest of the gang, the levels taken, the time split
+static fgpu_info dist_finish(const DistRun& r, PollState& s) {
+    fgpu_bfs_plan* p0 = r.plans[0];
+    p0->last_wait_us = s.waited_us();
+    const u32 fl0 = *(volatile u32*)p0->h_done.p;
     const int levels_taken = (fl0 & 0x80000000u) ? (int)(fl0 & 0xFFFFFFu) : (int)p0->h_ctrl->level;
-    for (int k = 0; k < nplans; ++k) {
-        fgpu_bfs_plan* p = plans[k];
-        bool done = false;
+    for (int k = 0; k < r.np; ++k) {
+        fgpu_bfs_plan* p = r.plans[k];
         if (k) {   // every rank of the gang finishes at the same level
-            FGPU_TRY(wait_flag(p, &done));
+            bool done = false;
+            (void)p->ctx->lane();
+            FGPU_TRY(poll_done(p, s, &done));
             if (!done) FGPU_HIP(hipStreamSynchronize(p->ctx->stream()));
         }
         p->last_levels = levels_taken;
         double lm = 0, cm = 0;
-        if (timed) {
+        if (r.timed) {
             (void)p->ctx->lane();
             FGPU_HIP(hipStreamSynchronize(p->ctx->stream()));
-            for (u64 l = 0; l < nlev; ++l) {
+            for (u64 l = 0; l < r.nlev; ++l) {
                 float a = 0, b = 0;
-                if (hipEventElapsedTime(&a, p->dist_ev[3 * l], p->dist_ev[3 * l + 1]) == hipSuccess) lm += a;
-                if (hipEventElapsedTime(&b, p->dist_ev[3 * l + 1], p->dist_ev[3 * l + 2]) == hipSuccess) cm += b;
+                if (hipEventElapsedTime(&a, p->dist_ev[3 * l].e, p->dist_ev[3 * l + 1].e) == hipSuccess) lm += a;
+                if (hipEventElapsedTime(&b, p->dist_ev[3 * l + 1].e, p->dist_ev[3 * l + 2].e) == hipSuccess) cm += b;
             }
             (void)hipGetLastError();
         }
         p->dist_level_ms = lm;
         p->dist_coll_ms = cm;
-        p->dist_levels = nlev;
+        p->dist_levels = r.nlev;
     }
     return FGPU_OK;
+}
+
+fgpu_info fgpu_bfs_dist_run(fgpu_bfs_plan* const* plans, int nplans, uint64_t src, int64_t max_level, int want_parent) {
+    FGPU_TRY(dist_check(plans, nplans));
+    fgpu_bfs_plan* p0 = plans[0];
+    FGPU_TRY(dist_setup(plans, nplans));
+    DistRun r{plans, nplans, over_rccl(p0), false, p0->ctx->opt.dist_timing != 0, {}, {}, std::vector<int>(nplans, 0)};
+    r.peer = !r.rccl && nplans > 1;
+    FGPU_TRY(slab_layout(p0, r.offs, r.cnts));
+    for (int k = 0; k < nplans; ++k) FGPU_TRY(fgpu_bfs_slab_begin(plans[k], src, max_level, want_parent));
+    if (r.peer)
+        for (int k = 0; k < nplans; ++k)
+            if (!plans[k]->dist_copied.e) {
+                (void)plans[k]->ctx->lane();   // events of plan k live on plan k's device
+                FGPU_HIP(plans[k]->dist_copied.create(hipEventDisableTiming));
+            }
+    // Termination: the level that empties the frontier raises every plan's pinned flag (fused_ctrl, slab branch; the
+    // decision is the same on every rank), so the host polls a host word instead of paying a D2H copy + stream sync
+    // per search (~80 us of idle stream between two searches at RMAT-26); the stream is queried now and then so that a
+    // search needing more levels than were enqueued — or a failed launch — is noticed.
+    int budget = p0->last_levels ? (p0->last_levels + 1 > 4 ? p0->last_levels + 1 : 4) : 6;
+    int topup = 2;
+    PollState s("fgpu_bfs_dist_run: stream failed", p0->last_wait_us, budget);
+    for (;;) {
+        for (int k = 0; k < budget; ++k) FGPU_TRY(dist_level(r));
+        bool done = false;
+        (void)p0->ctx->lane();
+        FGPU_TRY(poll_done(p0, s, &done));
+        if (done) break;
+        FGPU_TRY(fetch_ctrl(p0));   // stream drained without the flag: not done yet, or done without a level having run (max_level 0)
+        if (p0->h_ctrl->done) break;
+        s.querying = true;
+        budget = topup;                      // short of levels: 2 more, then 4, 8, ...
+        if (topup < 512) topup *= 2;
+    }
+    return dist_finish(r, s);
 }
 
 fgpu_info fgpu_bfs_dist_times(fgpu_bfs_plan* p, double* level_ms, double* collective_ms, uint64_t* launches) {
@@ -3233,14 +3330,13 @@ fgpu_info fgpu_bfs_dist_times(fgpu_bfs_plan* p, double* level_ms, double* collec
 static fgpu_info fused_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level) {
     FGPU_REQUIRE(src < p->n, FGPU_OUT_OF_BOUNDS, "BFS source %llu >= %u vertices", (unsigned long long)src, p->n);
     fgpu_ctx* ctx = p->ctx;
-    i32 ml = max_level < 0 ? -1 : (max_level > 0x7FFFFFFF ? 0x7FFFFFFF : (i32)max_level);
     BfsArgs a = make_args(p, true);
-    *(volatile u32*)p->h_done = 0;
+    *(volatile u32*)p->h_done.p = 0;
     p->enqueued = 0;
     p->fused_idx = 0;
     p->levels_masked = false;
-    p->mask_visited = p->bm_block + 3 * (size_t)p->nw;
-    FGPU_TRY(launch(bfs_fused_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, (u32)src, ml,
+    p->mask_visited = fused_views(p).visited;
+    FGPU_TRY(launch(bfs_fused_begin_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), a, (u32)src, clamp_level(max_level),
                     p->At ? 1u : 0u, (u32)p->force_dir, (float)p->alpha, p->At ? p->At->nnz : 0ull,
                     (u64)(ctx->opt.bfs_pb_min_edges > 0 ? ctx->opt.bfs_pb_min_edges : 1), p->pb ? p->pb_mask : 0u, ctx->opt.bfs_alive_rule ? p->n_alive : 0u, p->pb ? p->cp_mask : 0u));
     return FGPU_OK;
@@ -3249,49 +3345,44 @@ static fgpu_info fused_begin(fgpu_bfs_plan* p, uint64_t src, int64_t max_level) 
 // the four launches of a propagation-blocking level (each returns at once unless the control block says direction 3)
 static fgpu_info pb_launches(fgpu_bfs_plan* p, bool list_only = false) {
     fgpu_ctx* ctx = p->ctx;
+    const FusedViews f = fused_views(p);
     PbArgs g;
-    g.ctrl = p->ctrl;
-    g.pb = p->pb;
-    g.queue[0] = p->queue_block;
-    g.queue[1] = p->queue_block + QCAP;
-    g.deg = p->own_deg;
+    g.ctrl = p->ctrl.p;
+    g.pb = p->pb.ctl.p;
+    g.queue[0] = f.queue[0];
+    g.queue[1] = f.queue[1];
+    g.deg = p->own_deg.p;
     g.A = view_of(p->A);
-    g.lst0 = p->pb_small;
+    g.lst0 = p->pb.small.p;
     g.list = g.lst0 + PB_LMAX;
     g.P = g.list + PB_LMAX;
     g.S = g.P + PB_LMAX + 4;
     g.crow = g.S + PB_LMAX + 4;
-    g.wgh = g.crow + p->pb_maxchunks + 2;
-    g.dst = p->pb_dst;
-    g.src = p->pb_src;
-    g.bm[0] = p->bm_block;
-    g.bm[1] = p->bm_block + p->nw;
-    g.bm[2] = p->bm_block + 2 * (size_t)p->nw;
-    g.visited = p->bm_block + 3 * (size_t)p->nw;
-    g.level = p->level;
-    g.parent = p->want_parent ? p->parent : nullptr;
+    g.wgh = g.crow + p->pb.maxchunks + 2;
+    g.dst = p->pb.dst.p;
+    g.src = p->pb.src.p;
+    for (int k = 0; k < 3; ++k) g.bm[k] = f.bm[k];
+    g.visited = f.visited;
+    g.level = p->level.p;
+    g.parent = p->want_parent ? p->parent.p : nullptr;
     g.nw = p->nw;
     g.epoch = ++p->pb_epoch;
     g.n_hubP = p->A->n_push_chunks;
-    g.queue_w[0] = p->queue_block;
-    g.queue_w[1] = p->queue_block + QCAP;
+    g.queue_w[0] = f.queue[0];
+    g.queue_w[1] = f.queue[1];
     hipStream_t st = ctx->stream();
-    g.alive = p->alive;
-    if (p->At) { g.At = view_of(p->At); if (p->pull_colidx) g.At.colidx = p->pull_colidx; }
-    else { g.At.rowptr = nullptr; g.At.colidx = nullptr; g.At.hrows = nullptr; g.At.nvec = 0; g.At.nrows = 0; }
-    g.head = p->pull_head;
+    g.alive = p->pb.alive.p;
+    g.At = at_view(p);
+    g.head = p->pull_head.p;
+    FGPU_TRY(launch(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g));
     if (list_only) {   // the list kernel for a sparse frontier -> queue or a candidate set, and the pull of the latter
-        FGPU_TRY(launch(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g));
-        if (!p->alive) return FGPU_OK;
+        if (!g.alive) return FGPU_OK;
         return pick(p->want_parent, [&](auto par) {
             return launch(bfs_lp_kernel<decltype(par)::value>, dim3(PB_BINS), dim3(PB_T), 0, st, g);
         });
     }
-    u32 shift = 6;
-    while (((u64)PB_BINS << shift) < (u64)p->nw * 64) ++shift;
-    const size_t lds_apply = ((size_t)1 << shift) / 8;   // (<= PB_LDS_APPLY_MAX: plan_create admits windows of at most 2^19 vertices)
+    const size_t lds_apply = ((size_t)1 << p->pb.shift) / 8;   // (<= PB_LDS_APPLY_MAX: plan_pb admits windows of at most 2^19 vertices)
     const u32 cgrid = (u32)ctx->cus * 2;
-    FGPU_TRY(launch(bfs_pb_list_kernel, dim3(PB_LWG), dim3(PB_T), 0, st, g));
     FGPU_TRY(launch(bfs_pb_prefix_kernel, dim3(PB_LMAX / PB_T / PB_PPT), dim3(PB_T), 0, st, g));
     FGPU_TRY(launch_raised(bfs_pb_count_kernel, dim3(cgrid), dim3(PB_T), PB_LDS_COUNT, st, g));
     return pick(p->want_parent, [&](auto par) {
@@ -3317,11 +3408,6 @@ static fgpu_info fused_level(fgpu_bfs_plan* p) {
     });
 }
 
-static fgpu_info timed_begin(fgpu_bfs_plan* p) {
-    if (p->profile) FGPU_HIP(hipEventRecord(p->ev0, p->ctx->stream()));
-    return FGPU_OK;
-}
-
 fgpu_info fgpu_bfs_part_step(fgpu_bfs_plan* p) {
     FGPU_REQUIRE(p, FGPU_NULL_POINTER, "fgpu_bfs_part_step: NULL plan");
     BfsArgs a = make_args(p);
@@ -3336,13 +3422,13 @@ fgpu_info fgpu_bfs_part_commit(fgpu_bfs_plan* p) {
     u32 grid = cdiv(p->nw, 4);
     if (grid > p->grid * 2) grid = p->grid * 2;
     FGPU_TRY(launch(bfs_commit_kernel, dim3(grid), dim3(256), 0, p->ctx->stream(), a));
-    FGPU_TRY(launch(bfs_ctrl_kernel, dim3(1), dim3(64), 0, p->ctx->stream(), p->ctrl));
+    FGPU_TRY(launch(bfs_ctrl_kernel, dim3(1), dim3(64), 0, p->ctx->stream(), p->ctrl.p));
     return FGPU_OK;
 }
 
 static fgpu_info fetch_ctrl(fgpu_bfs_plan* p) {
     // header only (everything before the slot arrays)
-    FGPU_HIP(hipMemcpyAsync(p->h_ctrl, p->ctrl, offsetof(BfsCtrl, slot), hipMemcpyDeviceToHost,
+    FGPU_HIP(hipMemcpyAsync(p->h_ctrl.p, p->ctrl.p, offsetof(BfsCtrl, slot), hipMemcpyDeviceToHost,
                             p->ctx->stream()));
     FGPU_HIP(hipStreamSynchronize(p->ctx->stream()));
     return FGPU_OK;
@@ -3366,7 +3452,7 @@ static fgpu_info profiled_level(fgpu_bfs_plan* p) {
     const u64 nf = p->h_ctrl->n_frontier, reached0 = p->h_ctrl->reached;
     float ms = 0;
     BfsArgs a = make_args(p, true);
-    FGPU_HIP(hipEventRecord(p->ev0, ctx->stream()));
+    FGPU_HIP(hipEventRecord(p->ev0.e, ctx->stream()));
     if (dir == 3) FGPU_TRY(pb_launches(p));              // (the profiled pass knows the direction: pb_mask is all ones there)
     else if (p->h_ctrl->compact || dir == 4) FGPU_TRY(pb_launches(p, true));
     const u32 pgrid = p->fgrid | (p->fused_idx++ & 1u);
@@ -3379,9 +3465,9 @@ static fgpu_info profiled_level(fgpu_bfs_plan* p) {
             return launch(bfs_fused_kernel<decltype(par)::value, decltype(h)::value>, dim3(pgrid), dim3(256), 0, ctx->stream(), a);
         });
     }));
-    FGPU_HIP(hipEventRecord(p->ev1, ctx->stream()));
-    FGPU_HIP(hipEventSynchronize(p->ev1));
-    FGPU_HIP(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    FGPU_HIP(hipEventRecord(p->ev1.e, ctx->stream()));
+    FGPU_HIP(hipEventSynchronize(p->ev1.e));
+    FGPU_HIP(hipEventElapsedTime(&ms, p->ev0.e, p->ev1.e));
     ProfSlot& s = p->prof[(dir != 2 && dir != 4) ? 0 : 1];
     s.ms += ms; s.launches += 1;
     FGPU_TRY(fetch_ctrl(p));
@@ -3403,17 +3489,20 @@ fgpu_info fgpu_bfs_run_async(fgpu_bfs_plan* p, uint64_t src, int64_t max_level, 
                  "fgpu_bfs_run drives single-rank plans; multi-rank plans are stepped by the host loop");
     FGPU_REQUIRE(!p->profile, FGPU_INVALID, "a profiled plan runs synchronously (fgpu_bfs_run)");
     p->want_parent = want_parent != 0;
+    // bfs_tiny: 0 never, 1 always, 2 (default) when the previous search was deep — on an 8-level R-MAT search the two
+    // extra launches cost what the tiny kernel saves (A/B on one box: 0.2256 vs 0.2300 ms), on a path graph it halves
+    // the time per level (18.7 -> 9.6 us, tools/chain_bfs.py)
+    const int tmode = p->ctx->opt.bfs_tiny;
+    const bool use_tiny = tmode == 1 || (tmode == 2 && p->last_levels > 12);
     {   // propagation blocking: its four launches go in front of fused launches 1 .. 3 (levels 2 .. 4: where an R-MAT search has
         // its heavy push) — 4.8 us each when they have nothing to do; not on deep searches (the tiny kernel's sequence)
-        const int tm = p->ctx->opt.bfs_tiny;
-        const bool deep = tm == 1 || (tm == 2 && p->last_levels > 12);
         // (an armed launch costs 4 x 4.8 us: once the plan's searches have shown where their heavy push sits — level 3 of an
         // R-MAT-26 search — only those launches are armed, and every eighth search looks at all three again)
         u32 m = (p->pb_seen && (p->pb_searches & 7u) != 7u) ? (p->pb_seen & 0xEu) : 0xEu;
-        p->pb_mask = (p->pb && !deep) ? m : 0u;
+        p->pb_mask = (p->pb && !use_tiny) ? m : 0u;
         // the list kernel alone in front of launches 4 .. 6 (the push after the last pull), narrowed the same way
         const u32 cm = (p->cp_seen && (p->pb_searches & 7u) != 7u) ? (p->cp_seen & 0x7Eu) : 0x70u;
-        p->cp_mask = (p->pb && !deep) ? (cm & ~p->pb_mask) : 0u;
+        p->cp_mask = (p->pb && !use_tiny) ? (cm & ~p->pb_mask) : 0u;
         p->pb_searches++;
     }
     FGPU_TRY(fused_begin(p, src, max_level));
@@ -3422,11 +3511,6 @@ fgpu_info fgpu_bfs_run_async(fgpu_bfs_plan* p, uint64_t src, int64_t max_level, 
     // different roots differ by at most a level, and fgpu_bfs_wait tops up when the guess was short
     // the blind sequence: [tiny] [fused x heavy] [tiny] [fused] [tiny] — the tiny kernel runs every consecutive
     // tiny level in one launch and returns at once otherwise; `heavy` = the fused levels the previous search needed
-    // bfs_tiny: 0 never, 1 always, 2 (default) when the previous search was deep — on an 8-level R-MAT search the two
-    // extra launches cost what the tiny kernel saves (A/B on one box: 0.2256 vs 0.2300 ms), on a path graph it halves
-    // the time per level (18.7 -> 9.6 us, tools/chain_bfs.py)
-    const int tmode = p->ctx->opt.bfs_tiny;
-    const bool use_tiny = tmode == 1 || (tmode == 2 && p->last_levels > 12);
     if (levels <= 0) {
         if (!p->last_levels) levels = 10;
         else if (use_tiny && p->last_heavy >= 0) levels = p->last_heavy;
@@ -3446,49 +3530,29 @@ fgpu_info fgpu_bfs_run_async(fgpu_bfs_plan* p, uint64_t src, int64_t max_level, 
 fgpu_info fgpu_bfs_wait(fgpu_bfs_plan* p) {
     FGPU_REQUIRE(p, FGPU_NULL_POINTER, "fgpu_bfs_wait: NULL plan");
     FGPU_REQUIRE(p->nranks == 1 && p->enqueued > 0, FGPU_INVALID, "fgpu_bfs_wait: no search in flight");
-    volatile u32* flag = (volatile u32*)p->h_done;
-    // The last level raises the pinned flag.  It is polled WITHOUT touching the stream for as long as a search may
-    // reasonably take (twice the previous wait + 100 us): a hipStreamQuery makes the runtime put a system-scope fence on the
-    // next dispatch of the stream — 5.6-5.8 us of idle stream in front of every search when the query sat in the poll loop
-    // (rocprofv3 kernel trace, tools/trace_levels.py).  Past that budget the stream is looked at now and then, so a search
-    // that needs more levels than were enqueued (or a failed launch) is noticed.
-    const auto t0 = std::chrono::steady_clock::now();
-    auto waited_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    // ... twice the previous wait, but no more than 30 us per enqueued level (a level of an R-MAT search averages 20 us at
-    // scale 22, 200 us at scale 26 — there a 6 us fence no longer matters), and not at all once a top-up was needed
-    double quiet_us = 2.0 * p->last_wait_us + 100.0;
-    if (quiet_us > 100.0 + 30.0 * p->enqueued) quiet_us = 100.0 + 30.0 * p->enqueued;
+    volatile u32* flag = (volatile u32*)p->h_done.p;
+    PollState s("BFS stream failed", p->last_wait_us, p->enqueued);
     int topup = 4;
-    bool querying = false;
     for (;;) {
-        for (u32 spin = 0; (*flag & 0x80000000u) == 0; ++spin) {
-            if (!querying && (spin & 0x3Fu) == 0x3Fu) querying = waited_us() > quiet_us;
-            if (querying && (spin & 0x3FFu) == 0x3FFu) {
-                hipError_t q = hipStreamQuery(p->ctx->stream());
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) {
-                    set_error("BFS stream failed: %s", hipGetErrorString(q));
-                    return FGPU_DEVICE;
-                }
-            }
-        }
-        if (*flag & 0x80000000u) {
-            p->pb_seen |= ((volatile u32*)p->h_done)[1];
-            p->cp_seen |= ((volatile u32*)p->h_done)[2];
+        bool done = false;
+        FGPU_TRY(poll_done(p, s, &done));
+        if (done) {
+            p->pb_seen |= flag[1];
+            p->cp_seen |= flag[2];
             p->last_levels = (int)(*flag & 0xFFFFFFu);
             p->last_heavy = (int)((*flag >> 24) & 0x7Fu);
-            p->last_wait_us = waited_us();
+            p->last_wait_us = s.waited_us();
             return FGPU_OK;
         }
         FGPU_TRY(fetch_ctrl(p));  // stream drained without the flag: not done yet (or it raced the poll)
         if (p->h_ctrl->done) {
             p->last_levels = (int)p->h_ctrl->level;
             p->last_heavy = p->h_ctrl->heavy_begin ? (int)(p->h_ctrl->heavy_end - p->h_ctrl->heavy_begin + 1) : 0;
-            p->last_wait_us = waited_us();
+            p->last_wait_us = s.waited_us();
             return FGPU_OK;
         }
         // short of levels: top up, twice as many each time (a first search over a high-diameter graph)
-        querying = true;
+        s.querying = true;
         if (p->ctx->opt.bfs_tiny) FGPU_TRY(tiny_levels(p));
         for (int k = 0; k < topup; ++k) FGPU_TRY(fused_level(p));
         p->enqueued += topup;
@@ -3521,18 +3585,18 @@ fgpu_info fgpu_bfs_fetch(fgpu_bfs_plan* p, int32_t* level, int64_t* parent) {
     const u32 lo = p->lo, hi = p->hi < p->n ? p->hi : p->n;
     if (hi <= lo) return FGPU_OK;
     if (p->mask_visited && !p->levels_masked) {
-        FGPU_TRY(launch(bfs_mask_levels_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->level,
+        FGPU_TRY(launch(bfs_mask_levels_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->level.p,
                         p->mask_visited, p->nw * 64));
         p->levels_masked = true;
     }
-    if (level) FGPU_TRY(ctx->d2h(level + lo, p->level + lo, (size_t)(hi - lo) * sizeof(i32)));   // (one DMA when level[] is pinned)
+    if (level) FGPU_TRY(ctx->d2h(level + lo, p->level.p + lo, (size_t)(hi - lo) * sizeof(i32)));   // (one DMA when level[] is pinned)
     if (parent) {
         FGPU_REQUIRE(p->want_parent, FGPU_INVALID, "the last run did not track parents");
         // parent[v] = the stored u32 parent for reached vertices, -1 otherwise: widened on the device, then copied out like
         // level[] (DMA into pinned memory, the staging ring into pageable memory)
         DevBuf<long long> wide;
         FGPU_TRY(wide.alloc(ctx, hi - lo));
-        FGPU_TRY(launch(bfs_parent_out_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->parent + lo, p->level + lo,
+        FGPU_TRY(launch(bfs_parent_out_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), p->parent.p + lo, p->level.p + lo,
                         wide.p, hi - lo));
         FGPU_TRY(ctx->d2h(parent + lo, wide.p, (size_t)(hi - lo) * sizeof(int64_t)));
     }
@@ -3543,7 +3607,7 @@ fgpu_info fgpu_bfs_fetch(fgpu_bfs_plan* p, int32_t* level, int64_t* parent) {
 fgpu_info fgpu_bfs_stats(fgpu_bfs_plan* p, uint64_t stats[8]) {
     FGPU_REQUIRE(p && stats, FGPU_NULL_POINTER, "fgpu_bfs_stats: NULL argument");
     FGPU_TRY(fetch_ctrl(p));
-    const BfsCtrl* c = p->h_ctrl;
+    const BfsCtrl* c = p->h_ctrl.p;
     stats[0] = (u64)c->level;
     stats[1] = c->reached;
     stats[2] = c->edges_traversed;

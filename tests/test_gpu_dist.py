@@ -134,6 +134,52 @@ def test_slab_partitioned_bfs_at_eight_ranks(ctx, force, protocol):
             ctx.set_stream(None)
 
 
+def test_caller_buffers_survive_the_plan(ctx):
+    """Frontier buffers a caller installs stay the caller's: a stepped 2-rank gang of RMAT-13 (two slabs of 4096) searches
+    on its first pair of torch tensors per rank, then on a second pair given through part_set_buffers; the plans are freed
+    and all eight tensors filled with -1.  Had the library released any of them into its pool — when the second pair
+    replaced the first, or with the plan — a fresh fused gang on the same context would take them for its own frontier
+    bitmaps (same size classes) and write there: its levels must match the oracle and the tensors must still hold -1."""
+    scale, nranks = 13, 2
+    a = oracle.rmat_csr(scale)
+    A = ctx.mat_rmat(scale)
+    n = a.nrows
+    hub = int(np.argmax(np.diff(a.rowptr)))
+    refs = {src: oracle.bfs(a, src, -1)[0] for src in (hub, 5)}
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        ctx.set_stream(s.cuda_stream)
+        try:
+            gang = Gang(ctx, A, nranks, dev, "stepped")
+            assert [b.words_per_rank for b in gang.backs] == [64, 64]
+            fdist.run_levels(gang, gang.gather, hub, -1)
+            np.testing.assert_array_equal(gang.levels(n), refs[hub])
+            tensors = [t for b in gang.backs for t in (b.local, b.glob)]
+            for b in gang.backs:
+                local, glob = torch.zeros_like(b.local), torch.zeros_like(b.glob)
+                b.plan.part_set_buffers(local.data_ptr(), glob.data_ptr())
+                b.local, b.glob = local, glob
+                tensors += [local, glob]
+            fdist.run_levels(gang, gang.gather, hub, -1)
+            np.testing.assert_array_equal(gang.levels(n), refs[hub])
+            for b in gang.backs:
+                b.plan.free()
+            assert len(tensors) == 8 and len({t.data_ptr() for t in tensors}) == 8
+            for t in tensors:
+                t.fill_(-1)
+            fused = Gang(ctx, A, nranks, dev, "fused")
+            for src in (hub, 5):
+                fdist.run_levels(fused, fused.gather, src, -1)
+                np.testing.assert_array_equal(fused.levels(n), refs[src])
+            torch.cuda.synchronize()
+            for t in tensors:
+                assert bool((t == -1).all())
+        finally:
+            torch.cuda.synchronize()
+            ctx.set_stream(None)
+
+
 @pytest.mark.parametrize("nranks", [1, 2, 3])
 def test_row_sharded_expand_concatenates_to_the_whole_batch(ctx, nranks):
     """k-hop MATCH over ranks: shard the source rows with dist.shard_rows, run every share
@@ -487,6 +533,36 @@ def test_gang_survives_a_peer_that_finishes_its_levels_late(late):
             m_.free()
         for c in ctxs:
             c.close()
+
+
+@pytest.mark.parametrize("nranks", [2, 1])
+def test_in_library_loop_tops_up_and_ends_an_empty_search(ctx, nranks):
+    """The two branches of fgpu_bfs_dist_run's wait that no R-MAT case reaches for certain, on the directed path
+    0 -> 1 -> ... -> 4135 cut at 4096 (two slabs; one slab of 8192 for one rank, the in-place ring).  From 4076 the search
+    takes 59 levels and crosses the slab boundary at level 20: the first blind budget is 6 and the top-ups are 2, 4, 8, 16,
+    32, so it is topped up five times.  From 4076 with max_level 0 no level runs: the stream drains without the done flag
+    and the control block says done.  Then 0 with max_level 7 (a budget sized by the previous search).  Every rank's
+    slab of levels against the oracle after each search."""
+    n = 4136
+    rows = np.arange(n - 1, dtype=np.uint64)
+    a = oracle.build_csr(n, n, rows, rows + np.uint64(1))
+    A = ctx.mat_from_csr(n, n, a.rowptr, a.colidx)
+    splits = np.array([0, 4096, 8192] if nranks == 2 else [0, 8192], dtype=np.uint64)
+    plans, keep = _gang_plans(ctx, A, nranks, splits)
+    try:
+        for src, max_level in [(4076, -1), (4076, 0), (0, 7)]:
+            engine.bfs_dist_run(plans, src, max_level)
+            ref = oracle.bfs(a, src, max_level)[0]
+            level, _ = _assemble(plans, splits, n, False)
+            np.testing.assert_array_equal(level, ref, err_msg=f"src={src} max_level={max_level}")
+            if max_level < 0:
+                assert int(ref.max()) == 59 and ref[4096] == 20
+    finally:
+        for p in plans:
+            p.free()
+        for m_ in keep:
+            m_.free()
+        A.free()
 
 
 def test_bench_spawns_its_own_ranks_from_a_plain_shell():
