@@ -65,28 +65,18 @@ __device__ __forceinline__ void block_add_u64(u64 x, unsigned long long* dst) {
 // The kernels index dense row pointers: a hypersparse input is re-emitted in dense form for the call.  The guard owns those
 // temporaries (and a transpose an algorithm builds into dAt itself) and releases them on every exit.
 struct DenseInputs {
-    fgpu_mat *dA = nullptr, *dAt = nullptr;
-    DenseInputs() {}
-    DenseInputs(const DenseInputs&) = delete;
-    DenseInputs& operator=(const DenseInputs&) = delete;
-    ~DenseInputs() {
-        if (dA) mat_release(dA);
-        if (dAt) mat_release(dAt);
-    }
-    bool densified() const { return dA || dAt; }   // (a temporary stands in for an input: it has no cached indexes or plans)
+    MatRef dA, dAt;
+    bool densified() const { return dA.get() || dAt.get(); }   // (a temporary stands in for an input: it has no cached indexes or plans)
     // keep_vals: the dense form carries A's UINT64 values (fgpu_msf reads them); the pattern-only algorithms drop them
     fgpu_info a(fgpu_ctx* ctx, const fgpu_mat*& A, bool keep_vals = false) { return dense(ctx, A, dA, keep_vals); }
     fgpu_info at(fgpu_ctx* ctx, const fgpu_mat*& At) { return dense(ctx, At, dAt); }   // NULL stays NULL
 
    private:
-    static fgpu_info dense(fgpu_ctx* ctx, const fgpu_mat*& m, fgpu_mat*& own, bool keep_vals = false) {
+    static fgpu_info dense(fgpu_ctx* ctx, const fgpu_mat*& m, MatRef& own, bool keep_vals = false) {
         if (!m || !m->is_hyper()) return FGPU_OK;
-        fgpu_mat* prev = own;   // m itself when the caller built it into this slot: replaced by its dense form
-        own = nullptr;
-        const fgpu_info i = mat_merge_entries(ctx, &own, m, nullptr, nullptr, false, m->nrows, m->ncols, !(keep_vals && m->vals));
-        if (prev) mat_release(prev);
-        FGPU_TRY(i);
-        m = own;
+        MatRef prev(std::move(own));   // m itself when the caller built it into this slot: replaced by its dense form
+        FGPU_TRY(mat_merge_entries(ctx, &own.m, m, nullptr, nullptr, false, m->nrows, m->ncols, !(keep_vals && m->vals)));
+        m = own.get();
         return FGPU_OK;
     }
 };

@@ -2038,36 +2038,34 @@ static fgpu_info bp_to_csr_sorted(fgpu_ctx* ctx, const BitState& s, const u64* l
     if (dense && nnz > BP_DENSE_OUT * (u64)s.n) { *dense = true; return FGPU_OK; }
     FGPU_REQUIRE(nnz < 0xFFFFFFFFull - 4096, FGPU_OOM,
                  "expand: %llu result entries exceed the 32-bit row-pointer space; batch the source rows", (unsigned long long)nnz);
-    fgpu_mat* o = nullptr;
+    MatRef o;
     const u32 out_rows = s.nsrc_full ? s.nsrc_full : s.nsrc;
-    FGPU_TRY(mat_alloc(ctx, &o, out_rows, s.n, nnz, false, 0, false));
-    fgpu_info i = FGPU_OK;
+    FGPU_TRY(mat_alloc(ctx, &o.m, out_rows, s.n, nnz, false, 0, false));
     u32* rp = o->rowptr;
-    if (s.nsrc_full) { i = rp_live.alloc(ctx, (size_t)s.nsrc + 2); rp = rp_live.p; }
-    if (i == FGPU_OK && nnz) {
-        i = key.alloc(ctx, nnz);
-        if (i == FGPU_OK) i = val.alloc(ctx, nnz);
-        if (i == FGPU_OK) {
+    if (s.nsrc_full) { FGPU_TRY(rp_live.alloc(ctx, (size_t)s.nsrc + 2)); rp = rp_live.p; }
+    if (nnz) {
+        FGPU_TRY(key.alloc(ctx, nnz));
+        FGPU_TRY(val.alloc(ctx, nnz));
+        {
             ProfScope ps(ctx, "bp_pairs_kernel<fill>", nzr * s.w * 8 + (u64)s.n + 8 * nnz);
-            i = launch(bp_pairs_kernel<true>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
-                       (const uint8_t*)s.flag.p, label_dev, s.perm, (u32*)nullptr, (const u64*)toff.p, key.p, val.p);
+            FGPU_TRY(launch(bp_pairs_kernel<true>, dim3(ntiles), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, s.w, s.ws, lsh,
+                            (const uint8_t*)s.flag.p, label_dev, s.perm, (u32*)nullptr, (const u64*)toff.p, key.p, val.p));
         }
-        if (i == FGPU_OK) {
+        {
             ProfScope ps(ctx, "emission sort (pairs by row)", 16 * nnz + 4 * nnz);
-            i = sort_u32_pairs_by_key(ctx, key.p, val.p, nnz, s.nsrc, o->colidx, rp);
+            FGPU_TRY(sort_u32_pairs_by_key(ctx, key.p, val.p, nnz, s.nsrc, o->colidx, rp));
         }
-    } else if (i == FGPU_OK) {
-        if (hipMemsetAsync(rp, 0, ((size_t)s.nsrc + 1) * sizeof(u32), ctx->stream()) != hipSuccess) i = FGPU_DEVICE;
+    } else if (hipMemsetAsync(rp, 0, ((size_t)s.nsrc + 1) * sizeof(u32), ctx->stream()) != hipSuccess) {
+        return FGPU_DEVICE;
     }
-    if (i == FGPU_OK && s.nsrc_full) {
+    if (s.nsrc_full) {
         // compacted source rows: row i of the result is live row rowrank[i] (an empty source row starts and ends where the next
         // live one starts)
-        i = launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
-                   (const u32*)s.rowrank.p, out_rows, o->rowptr);
+        FGPU_TRY(launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
+                        (const u32*)s.rowrank.p, out_rows, o->rowptr));
     }
-    if (i == FGPU_OK && hipStreamSynchronize(ctx->stream()) != hipSuccess) { set_error("bit-parallel emission failed"); i = FGPU_DEVICE; }
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_REQUIRE(hipStreamSynchronize(ctx->stream()) == hipSuccess, FGPU_DEVICE, "bit-parallel emission failed");
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -2112,34 +2110,30 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
     FGPU_REQUIRE(nnz < 0xFFFFFFFFull, FGPU_OOM,
                  "expand: %llu result entries exceed the 32-bit row-pointer space; batch the source rows",
                  (unsigned long long)nnz);
-    fgpu_mat* o = nullptr;
+    MatRef o;
     const u32 out_rows = s.nsrc_full ? s.nsrc_full : s.nsrc;
-    FGPU_TRY(mat_alloc(ctx, &o, out_rows, s.n, nnz, false, 0, false));
+    FGPU_TRY(mat_alloc(ctx, &o.m, out_rows, s.n, nnz, false, 0, false));
     // rows >= nsrc are empty, so off[nsrc * nchunks] == nnz already
-    fgpu_info i = FGPU_OK;
     DevBuf<u32> rp_live;
     if (s.nsrc_full) {
         // compacted source rows: row i of the result is live row rowrank[i] (an empty source row starts — and ends — where
         // the next live one starts); the entries themselves are emitted in live-row order, which IS the order of the rows
-        i = rp_live.alloc(ctx, (size_t)s.nsrc + 1);
-        if (i == FGPU_OK)
-            i = launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
-                       nchunks, rp_live.p);
-        if (i == FGPU_OK)
-            i = launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
-                       (const u32*)s.rowrank.p, out_rows, o->rowptr);
+        FGPU_TRY(rp_live.alloc(ctx, (size_t)s.nsrc + 1));
+        FGPU_TRY(launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
+                        nchunks, rp_live.p));
+        FGPU_TRY(launch(bp_rowptr_full_kernel, dim3(cdiv((u64)out_rows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rp_live.p,
+                        (const u32*)s.rowrank.p, out_rows, o->rowptr));
     } else {
-        i = launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
-                   nchunks, o->rowptr);
+        FGPU_TRY(launch(bp_rowptr_kernel, dim3(cdiv((u64)s.nsrc + 1, 256)), dim3(256), 0, ctx->stream(), (const u64*)off.p, s.nsrc,
+                        nchunks, o->rowptr));
     }
-    if (i == FGPU_OK && nnz) {
+    if (nnz) {
         ProfScope ps(ctx, "bp_rows_kernel<emit>", nzr * s.w * 8 + (u64)s.n + 8 * (u64)ncnt + 4 * nnz);
-        i = launch(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks, label_dev,
-                   nullptr, off.p, o->colidx, s.flag.p);
+        FGPU_TRY(launch(bp_rows_kernel<true>, dim3(grid), dim3(256), lds_rows, ctx->stream(), s.x.p, s.n, s.w, s.ws, nchunks, label_dev,
+                        nullptr, off.p, o->colidx, s.flag.p));
     }
-    if (i == FGPU_OK) i = fgpu_sync(ctx);   // (rp_live returns to the pool)
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_TRY(fgpu_sync(ctx));   // (rp_live returns to the pool)
+    *out = o.release();
     return FGPU_OK;
 }
 

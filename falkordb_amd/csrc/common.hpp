@@ -262,7 +262,8 @@ struct DevBuf {
     T* take() { T* q = p; p = nullptr; n = 0; return q; }
 };
 
-// RAII: a snapshot no other thread has seen (a temporary of one call), released on every exit.
+// RAII: a snapshot no other thread has seen (a temporary of one call), released on every exit.  A builder holds its
+// snapshot in one from mat_alloc until `*out = ref.release()`, so every early-return macro in between is safe.
 void mat_release(fgpu_mat* m);
 struct MatRef {
     fgpu_mat* m = nullptr;
@@ -270,10 +271,23 @@ struct MatRef {
     explicit MatRef(fgpu_mat* take) : m(take) {}
     MatRef(const MatRef&) = delete;
     MatRef& operator=(const MatRef&) = delete;
-    ~MatRef() { if (m) mat_release(m); }
+    MatRef(MatRef&& o) noexcept : m(o.m) { o.m = nullptr; }
+    MatRef& operator=(MatRef&& o) noexcept {
+        if (this != &o) { reset(o.m); o.m = nullptr; }
+        return *this;
+    }
+    ~MatRef() { reset(); }
+    void reset(fgpu_mat* take = nullptr) {   // the held snapshot is released NOW (its blocks go back to the lane's pool)
+        if (m) mat_release(m);
+        m = take;
+    }
+    fgpu_mat* release() { fgpu_mat* q = m; m = nullptr; return q; }   // handed out: the caller owns it
+    fgpu_mat* get() const { return m; }
+    fgpu_mat* operator->() const { return m; }
 };
 
-// RAII: a block of ctx->result_alloc, freed unless release() handed it to the caller.
+// RAII: a block of ctx->result_alloc (or, through alloc_host, of the caller's allocator whatever its size), freed unless
+// release() handed it to the caller.
 struct ResultBuf {
     fgpu_ctx* ctx = nullptr;
     void* p = nullptr;
@@ -284,6 +298,11 @@ struct ResultBuf {
     bool alloc(fgpu_ctx* c, size_t bytes) {
         ctx = c;
         p = c->result_alloc(bytes);
+        return p != nullptr;
+    }
+    bool alloc_host(fgpu_ctx* c, size_t bytes) {
+        ctx = c;
+        p = c->host_alloc(bytes);
         return p != nullptr;
     }
     void* release() { void* q = p; p = nullptr; return q; }

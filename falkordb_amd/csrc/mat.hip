@@ -78,26 +78,19 @@ fgpu_info mat_alloc(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, u64 nnz
                  (unsigned long long)nrows, (unsigned long long)ncols);
     FGPU_REQUIRE(nnz < 0xFFFFFFFFull, FGPU_INVALID, "nnz %llu exceeds the 32-bit row-pointer space",
                  (unsigned long long)nnz);
-    fgpu_mat* m = new (std::nothrow) fgpu_mat();
-    FGPU_REQUIRE(m != nullptr, FGPU_OOM, "out of host memory");
+    MatRef m(new (std::nothrow) fgpu_mat());
+    FGPU_REQUIRE(m.get() != nullptr, FGPU_OOM, "out of host memory");
     m->ctx = ctx;
     m->nrows = nrows;
     m->ncols = ncols;
     m->nnz = nnz;
     m->nvec = hyper ? nvec_hyper : (u32)nrows;
-    fgpu_info i;
-    if ((i = ctx->dev_alloc((void**)&m->rowptr, ((size_t)m->nvec + 1) * sizeof(u32))) != FGPU_OK) goto fail;
-    if ((i = ctx->dev_alloc((void**)&m->colidx, (size_t)(nnz ? nnz : 1) * sizeof(u32))) != FGPU_OK) goto fail;
-    if (with_vals)
-        if ((i = ctx->dev_alloc((void**)&m->vals, (size_t)(nnz ? nnz : 1) * sizeof(u64))) != FGPU_OK) goto fail;
-    if (hyper)
-        if ((i = ctx->dev_alloc((void**)&m->hrows, (size_t)(m->nvec ? m->nvec : 1) * sizeof(u32))) != FGPU_OK)
-            goto fail;
-    *out = m;
+    FGPU_TRY(ctx->dev_alloc((void**)&m->rowptr, ((size_t)m->nvec + 1) * sizeof(u32)));
+    FGPU_TRY(ctx->dev_alloc((void**)&m->colidx, (size_t)(nnz ? nnz : 1) * sizeof(u32)));
+    if (with_vals) FGPU_TRY(ctx->dev_alloc((void**)&m->vals, (size_t)(nnz ? nnz : 1) * sizeof(u64)));
+    if (hyper) FGPU_TRY(ctx->dev_alloc((void**)&m->hrows, (size_t)(m->nvec ? m->nvec : 1) * sizeof(u32)));
+    *out = m.release();
     return FGPU_OK;
-fail:
-    mat_release(m);
-    return i;
 }
 
 // max degree + static hub chunk list (rows with >= HUB_DEG entries).
@@ -228,13 +221,12 @@ fgpu_info mat_from_device_coo(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncol
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));  // cnt[nrows] == 0
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
-    fgpu_mat* m = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &m, nrows, ncols, nnz, false, 0, false));
+    MatRef m;
+    FGPU_TRY(mat_alloc(ctx, &m.m, nrows, ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(m->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
-    fgpu_info i = compact_segments(ctx, tmp.p, off.p, m->rowptr, (u32)nrows, m->colidx);
-    if (i == FGPU_OK) i = mat_finalize(m);
-    if (i != FGPU_OK) { mat_release(m); return i; }
-    *out = m;
+    FGPU_TRY(compact_segments(ctx, tmp.p, off.p, m->rowptr, (u32)nrows, m->colidx));
+    FGPU_TRY(mat_finalize(m.get()));
+    *out = m.release();
     return FGPU_OK;
 }
 
@@ -245,21 +237,15 @@ static fgpu_info upload_host_csr(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 n
                                  const std::vector<u32>& hrows_or_empty, bool hyper, const std::vector<u32>& rowptr,
                                  const std::vector<u32>& colidx, const std::vector<u64>* vals) {
     u64 nnz = colidx.size();
-    fgpu_mat* m = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &m, nrows, ncols, nnz, vals != nullptr, (u32)hrows_or_empty.size(), hyper));
+    MatRef m;
+    FGPU_TRY(mat_alloc(ctx, &m.m, nrows, ncols, nnz, vals != nullptr, (u32)hrows_or_empty.size(), hyper));
     // (h2d returns once the host vectors have been consumed: they die with the caller)
-    fgpu_info u = ctx->h2d(m->rowptr, rowptr.data(), rowptr.size() * sizeof(u32));
-    if (u == FGPU_OK && nnz) u = ctx->h2d(m->colidx, colidx.data(), nnz * sizeof(u32));
-    if (u == FGPU_OK && vals && nnz) u = ctx->h2d(m->vals, vals->data(), nnz * sizeof(u64));
-    if (u == FGPU_OK && hyper && !hrows_or_empty.empty())
-        u = ctx->h2d(m->hrows, hrows_or_empty.data(), hrows_or_empty.size() * sizeof(u32));
-    if (u != FGPU_OK) {
-        mat_release(m);
-        return u;
-    }
-    fgpu_info i = mat_finalize(m);
-    if (i != FGPU_OK) { mat_release(m); return i; }
-    *out = m;
+    FGPU_TRY(ctx->h2d(m->rowptr, rowptr.data(), rowptr.size() * sizeof(u32)));
+    if (nnz) FGPU_TRY(ctx->h2d(m->colidx, colidx.data(), nnz * sizeof(u32)));
+    if (vals && nnz) FGPU_TRY(ctx->h2d(m->vals, vals->data(), nnz * sizeof(u64)));
+    if (hyper && !hrows_or_empty.empty()) FGPU_TRY(ctx->h2d(m->hrows, hrows_or_empty.data(), hrows_or_empty.size() * sizeof(u32)));
+    FGPU_TRY(mat_finalize(m.get()));
+    *out = m.release();
     return FGPU_OK;
 }
 
@@ -568,11 +554,11 @@ fgpu_info mat_transpose_pattern(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
         if (a->is_hyper()) return fgpu_mat_new(ctx, out, a->ncols, a->nrows);
         // an empty matrix in the dense-row-pointer form stays in that form (an empty column slab of a partitioned
         // BFS — more ranks than populated vertex blocks — still needs a plan over dense row pointers)
-        fgpu_mat* o = nullptr;
-        FGPU_TRY(mat_alloc(ctx, &o, a->ncols, a->nrows, 0, false, 0, false));
+        MatRef o;
+        FGPU_TRY(mat_alloc(ctx, &o.m, a->ncols, a->nrows, 0, false, 0, false));
         hipError_t e = hipMemsetAsync(o->rowptr, 0, (a->ncols + 1) * sizeof(u32), ctx->stream());
-        if (e != hipSuccess) { mat_release(o); set_error("memset failed: %s", hipGetErrorString(e)); return FGPU_DEVICE; }
-        *out = o;
+        FGPU_REQUIRE(e == hipSuccess, FGPU_DEVICE, "memset failed: %s", hipGetErrorString(e));
+        *out = o.release();
         return FGPU_OK;
     }
     if (ctx->opt.transpose_mode != 1) {   // stable partition by column: rows of the result come out ascending, no sort
@@ -798,38 +784,29 @@ fgpu_info fgpu_mat_export_csr(fgpu_ctx* ctx, const fgpu_mat* m, uint64_t** rowpt
                               uint64_t** vals, uint64_t* nnz) {
     FGPU_REQUIRE(ctx && m && rowptr && colidx && nnz, FGPU_NULL_POINTER, "fgpu_mat_export_csr: NULL argument");
     // (large arrays come pinned from the context's pool and are filled by one DMA each: ctx.hip result_alloc / d2h_widen)
-    u64* orp = (u64*)ctx->result_alloc((m->nrows + 1) * sizeof(u64));
-    u64* oci = (u64*)ctx->result_alloc((m->nnz ? m->nnz : 1) * sizeof(u64));
-    u64* ov = (vals && m->vals) ? (u64*)ctx->result_alloc((m->nnz ? m->nnz : 1) * sizeof(u64)) : nullptr;
-    if (!orp || !oci || (vals && m->vals && !ov)) {
-        ctx->host_free(orp); ctx->host_free(oci); ctx->host_free(ov);
-        set_error("fgpu_mat_export_csr: host allocation failed");
-        return FGPU_OOM;
-    }
+    const bool with_vals = vals && m->vals;
+    ResultBuf brp, bci, bv;
+    FGPU_REQUIRE(brp.alloc(ctx, (m->nrows + 1) * sizeof(u64)) && bci.alloc(ctx, (m->nnz ? m->nnz : 1) * sizeof(u64)) &&
+                     (!with_vals || bv.alloc(ctx, (m->nnz ? m->nnz : 1) * sizeof(u64))),
+                 FGPU_OOM, "fgpu_mat_export_csr: host allocation failed");
+    u64 *orp = (u64*)brp.p, *oci = (u64*)bci.p, *ov = (u64*)bv.p;
     // ids are 32-bit on the device and 64-bit for the caller (GrB_Index): widened chunk by chunk on the way out of the
     // pinned staging halves, straight into the caller's arrays (no intermediate host copy)
-    fgpu_info i = FGPU_OK;
     if (m->is_hyper()) {
         std::vector<u32> rp((size_t)m->nvec + 1), hr(m->nvec);
-        i = ctx->d2h(rp.data(), m->rowptr, rp.size() * sizeof(u32));
-        if (i == FGPU_OK && m->nvec) i = ctx->d2h(hr.data(), m->hrows, (size_t)m->nvec * sizeof(u32));
-        if (i == FGPU_OK) {
-            memset(orp, 0, (m->nrows + 1) * sizeof(u64));
-            for (u32 k = 0; k < m->nvec; ++k) orp[hr[k] + 1] = rp[k + 1] - rp[k];
-            for (u64 r = 0; r < m->nrows; ++r) orp[r + 1] += orp[r];
-        }
+        FGPU_TRY(ctx->d2h(rp.data(), m->rowptr, rp.size() * sizeof(u32)));
+        if (m->nvec) FGPU_TRY(ctx->d2h(hr.data(), m->hrows, (size_t)m->nvec * sizeof(u32)));
+        memset(orp, 0, (m->nrows + 1) * sizeof(u64));
+        for (u32 k = 0; k < m->nvec; ++k) orp[hr[k] + 1] = rp[k + 1] - rp[k];
+        for (u64 r = 0; r < m->nrows; ++r) orp[r + 1] += orp[r];
     } else {
-        i = ctx->d2h_widen(orp, m->rowptr, m->nrows + 1);
+        FGPU_TRY(ctx->d2h_widen(orp, m->rowptr, m->nrows + 1));
     }
-    if (i == FGPU_OK && m->nnz) i = ctx->d2h_widen(oci, m->colidx, m->nnz);
-    if (i == FGPU_OK && ov && m->nnz) i = ctx->d2h(ov, m->vals, m->nnz * sizeof(u64));
-    if (i != FGPU_OK) {
-        ctx->host_free(orp); ctx->host_free(oci); ctx->host_free(ov);
-        return i;
-    }
-    *rowptr = orp;
-    *colidx = oci;
-    if (vals) *vals = ov;
+    if (m->nnz) FGPU_TRY(ctx->d2h_widen(oci, m->colidx, m->nnz));
+    if (ov && m->nnz) FGPU_TRY(ctx->d2h(ov, m->vals, m->nnz * sizeof(u64)));
+    *rowptr = (u64*)brp.release();
+    *colidx = (u64*)bci.release();
+    if (vals) *vals = (u64*)bv.release();
     *nnz = m->nnz;
     return FGPU_OK;
 }
@@ -869,14 +846,11 @@ fgpu_info fgpu_mat_extract(fgpu_ctx* ctx, const fgpu_mat* m, uint64_t min_row, u
         FGPU_TRY(ctx->d2h(vv.data(), m->vals + b, cnt * sizeof(u64)));
     }
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-    u64* orow = (u64*)ctx->host_alloc(cnt * sizeof(u64));
-    u64* ocol = (u64*)ctx->host_alloc(cnt * sizeof(u64));
-    u64* oval = (vals && m->vals) ? (u64*)ctx->host_alloc(cnt * sizeof(u64)) : nullptr;
-    if (!orow || !ocol || (vals && m->vals && !oval)) {
-        ctx->host_free(orow); ctx->host_free(ocol); ctx->host_free(oval);
-        set_error("fgpu_mat_extract: host allocation failed");
-        return FGPU_OOM;
-    }
+    ResultBuf brow, bcol, bval;   // (the caller's allocator, not pinned result blocks)
+    FGPU_REQUIRE(brow.alloc_host(ctx, cnt * sizeof(u64)) && bcol.alloc_host(ctx, cnt * sizeof(u64)) &&
+                     (!(vals && m->vals) || bval.alloc_host(ctx, cnt * sizeof(u64))),
+                 FGPU_OOM, "fgpu_mat_extract: host allocation failed");
+    u64 *orow = (u64*)brow.release(), *ocol = (u64*)bcol.release(), *oval = (u64*)bval.release();   // nothing below can fail
     u64 k = 0;
     for (u32 i = i0; i < i1; ++i) {
         u64 r = m->is_hyper() ? hr[i] : i;
@@ -981,13 +955,12 @@ fgpu_info mat_merge_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, con
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, m->ncols, nnz, false, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, m->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
-    fgpu_info i = compact_segments(ctx, tmp.p, off.p, o->rowptr, (u32)nrows, o->colidx);
-    if (i == FGPU_OK) i = mat_finalize(o);
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_TRY(compact_segments(ctx, tmp.p, off.p, o->rowptr, (u32)nrows, o->colidx));
+    FGPU_TRY(mat_finalize(o.get()));
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -1047,8 +1020,8 @@ static fgpu_info intersect_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
     if (nvals) *nvals = nnz;
     if (!out) return FGPU_OK;
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, a->ncols, nnz, with_vals, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, a->ncols, nnz, with_vals, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
     if (nrows && nnz) {
         u32 grid = cdiv(nrows, 4);
@@ -1057,9 +1030,8 @@ static fgpu_info intersect_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a
                         (const u64*)(with_vals ? tmpv.p : nullptr), (const u32*)arp.p, (const u32*)o->rowptr,
                         (u32)nrows, o->colidx, o->vals));
     }
-    fgpu_info i = mat_finalize(o);
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_TRY(mat_finalize(o.get()));
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -1102,8 +1074,8 @@ static fgpu_info mat_col_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, a->ncols, nnz, false, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, a->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
     if (nrows && nnz) {
         u32 grid = cdiv(nrows, 4);
@@ -1111,9 +1083,8 @@ static fgpu_info mat_col_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
         FGPU_TRY(launch(col_slab_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(a), (u32)lo,
                         (u32)hi, (const u32*)o->rowptr, o->colidx));
     }
-    fgpu_info i = mat_finalize(o);
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_TRY(mat_finalize(o.get()));
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -1131,8 +1102,8 @@ static fgpu_info mat_row_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, a->ncols, nnz, false, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, a->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
     if (nnz) {
         // rows [lo,hi) are contiguous in a's colidx
@@ -1141,9 +1112,8 @@ static fgpu_info mat_row_slab_impl(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat
         FGPU_HIP(hipMemcpyAsync(o->colidx, a->colidx + b, (size_t)nnz * sizeof(u32), hipMemcpyDeviceToDevice,
                                 ctx->stream()));
     }
-    fgpu_info i = mat_finalize(o);
-    if (i != FGPU_OK) { mat_release(o); return i; }
-    *out = o;
+    FGPU_TRY(mat_finalize(o.get()));
+    *out = o.release();
     return FGPU_OK;
 }
 

@@ -505,11 +505,11 @@ fgpu_info mat_merge_entries(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, co
     FGPU_TRY(scan_u32(ctx, orp.p, orp.p, out_nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, orp.p + out_nrows, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, out_nrows, out_ncols, nnz, with_vals, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, out_nrows, out_ncols, nnz, with_vals, 0, false));
     // shifted-copy scatter (above) for the common shape: same dims, a plain CSR base, every dp entry kept
     const bool by_items = ctx->opt.merge_items && !clip && ctx->opt.merge_mode != 2 && !dm_masks_dp && !m->is_hyper() && lm.nnz && nnz;
-    auto fill = [&]() -> fgpu_info {
+    {
         FGPU_HIP(hipMemcpyAsync(o->rowptr, orp.p, (out_nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
         DevBuf<u32> Q, ibase;
         if (by_items) {
@@ -537,15 +537,10 @@ fgpu_info mat_merge_entries(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, co
                             lm.nnz != 0, (const u32*)rowbits.p, (const u64*)kp.kb.p, (const u32*)kp.ks.p, (const u64*)km.kb.p,
                             (const u32*)km.ks.p, (const u32*)o->rowptr, o->colidx, o->vals, clip, (const u32*)nullptr));
         // the scratch buffers above go back to the pool when this returns: the kernels reading them must be done
-        return fgpu_sync(ctx);
-    };
-    const fgpu_info fi = fill();
-    if (fi != FGPU_OK) {
-        mat_release(o);
-        return fi;
+        FGPU_TRY(fgpu_sync(ctx));
     }
     // hub list / max degree are computed when a BFS plan first needs them (mat_ensure_finalized)
-    *out = o;
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -572,27 +567,21 @@ __global__ void coo_take_winner_kernel(const u32* __restrict__ win, const u64* _
 
 fgpu_info mat_from_device_coo_vals(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, const u32* rows,
                                    const u32* cols, const u64* vals, u64 n) {
-    fgpu_mat* a = nullptr;
-    FGPU_TRY(mat_from_device_coo(ctx, &a, nrows, ncols, rows, cols, n));   // dense row pointers
-    fgpu_info i = FGPU_OK;
-    do {
-        if ((i = ctx->dev_alloc((void**)&a->vals, (size_t)(a->nnz ? a->nnz : 1) * sizeof(u64))) != FGPU_OK) break;
-        if (a->nnz == 0) break;
+    MatRef a;
+    FGPU_TRY(mat_from_device_coo(ctx, &a.m, nrows, ncols, rows, cols, n));   // dense row pointers
+    FGPU_TRY(ctx->dev_alloc((void**)&a->vals, (size_t)(a->nnz ? a->nnz : 1) * sizeof(u64)));
+    if (a->nnz) {
         DevBuf<u32> win;
-        if ((i = win.alloc(ctx, a->nnz)) != FGPU_OK) break;
-        if (hipError_t e = hipMemsetAsync(win.p, 0, a->nnz * sizeof(u32), ctx->stream())) {
-            set_error("valued COO build failed: %s", hipGetErrorString(e));
-            i = FGPU_DEVICE;
-            break;
-        }
-        if ((i = launch(coo_winner_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), rows, cols, n, (const u32*)a->rowptr,
-                        (const u32*)a->colidx, win.p)) != FGPU_OK) break;
-        if ((i = launch(coo_take_winner_kernel, dim3(cdiv(a->nnz, 256)), dim3(256), 0, ctx->stream(), (const u32*)win.p, vals,
-                        (u32)a->nnz, a->vals)) != FGPU_OK) break;
-        i = fgpu_sync(ctx);   // `win` returns to the pool
-    } while (0);
-    if (i != FGPU_OK) { mat_release(a); return i; }
-    *out = a;
+        FGPU_TRY(win.alloc(ctx, a->nnz));
+        const hipError_t e = hipMemsetAsync(win.p, 0, a->nnz * sizeof(u32), ctx->stream());
+        FGPU_REQUIRE(e == hipSuccess, FGPU_DEVICE, "valued COO build failed: %s", hipGetErrorString(e));
+        FGPU_TRY(launch(coo_winner_kernel, dim3(ctx->cus * 16), dim3(256), 0, ctx->stream(), rows, cols, n, (const u32*)a->rowptr,
+                        (const u32*)a->colidx, win.p));
+        FGPU_TRY(launch(coo_take_winner_kernel, dim3(cdiv(a->nnz, 256)), dim3(256), 0, ctx->stream(), (const u32*)win.p, vals,
+                        (u32)a->nnz, a->vals));
+        FGPU_TRY(fgpu_sync(ctx));   // `win` returns to the pool
+    }
+    *out = a.release();
     return FGPU_OK;
 }
 
@@ -616,24 +605,21 @@ __global__ __launch_bounds__(256) void transpose_vals_kernel(Layer a, const u32*
 }
 
 fgpu_info mat_transpose_vals(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a) {
-    fgpu_mat* t = nullptr;
-    FGPU_TRY(mat_transpose_pattern(ctx, &t, a));
-    fgpu_info i = FGPU_OK;
-    do {
-        if (t->is_hyper()) {  // empty result: fgpu_mat_new form
-            i = ctx->dev_alloc((void**)&t->vals, sizeof(u64));
-            break;
+    MatRef t;
+    FGPU_TRY(mat_transpose_pattern(ctx, &t.m, a));
+    if (t->is_hyper()) {  // empty result: fgpu_mat_new form
+        FGPU_TRY(ctx->dev_alloc((void**)&t->vals, sizeof(u64)));
+    } else {
+        FGPU_TRY(ctx->dev_alloc((void**)&t->vals, (size_t)(t->nnz ? t->nnz : 1) * sizeof(u64)));
+        if (a->nnz) {
+            Layer la{};
+            FGPU_TRY(layer_of(ctx, a, la));
+            FGPU_TRY(launch(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la, (const u32*)t->rowptr,
+                            (const u32*)t->colidx, t->vals));
+            FGPU_TRY(fgpu_sync(ctx));
         }
-        if ((i = ctx->dev_alloc((void**)&t->vals, (size_t)(t->nnz ? t->nnz : 1) * sizeof(u64))) != FGPU_OK) break;
-        if (a->nnz == 0) break;
-        Layer la{};
-        if ((i = layer_of(ctx, a, la)) != FGPU_OK) break;
-        if ((i = launch(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la, (const u32*)t->rowptr,
-                        (const u32*)t->colidx, t->vals)) != FGPU_OK) break;
-        i = fgpu_sync(ctx);
-    } while (0);
-    if (i != FGPU_OK) { mat_release(t); return i; }
-    *out = t;
+    }
+    *out = t.release();
     return FGPU_OK;
 }
 

@@ -473,8 +473,8 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
     DenseInputs in;
     FGPU_TRY(in.a(ctx, A));
     if (!At) {   // a missing transpose is built for the call
-        FGPU_TRY(fgpu_mat_transpose(ctx, &in.dAt, A));
-        At = in.dAt;
+        FGPU_TRY(fgpu_mat_transpose(ctx, &in.dAt.m, A));
+        At = in.dAt.get();
     }
     FGPU_TRY(in.at(ctx, At));
     FGPU_TRY(mat_ensure_finalized(At));

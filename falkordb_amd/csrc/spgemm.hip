@@ -159,11 +159,11 @@ __global__ __launch_bounds__(256) void checksum_entries_kernel(CsrView c, u32 nr
 }
 
 static fgpu_info empty_dense(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols) {
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, ncols, 0, false, 0, false));
-    hipError_t e = hipMemsetAsync(o->rowptr, 0, (nrows + 1) * sizeof(u32), ctx->stream());
-    if (e != hipSuccess) { mat_release(o); set_error("memset failed: %s", hipGetErrorString(e)); return FGPU_DEVICE; }
-    *out = o;
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, ncols, 0, false, 0, false));
+    const hipError_t e = hipMemsetAsync(o->rowptr, 0, (nrows + 1) * sizeof(u32), ctx->stream());
+    FGPU_REQUIRE(e == hipSuccess, FGPU_DEVICE, "memset failed: %s", hipGetErrorString(e));
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -220,17 +220,15 @@ fgpu_info mxm_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* F, const fgp
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, k + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + k, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, k, B->ncols, nnz, false, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, k, B->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (k + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
-    fgpu_info i;
     {
         ProfScope ps(ctx, "compact_segments_kernel", 8 * (u64)nnz);
-        i = compact_segments(ctx, tmp.p, roff.p, o->rowptr, (u32)k, o->colidx);
+        FGPU_TRY(compact_segments(ctx, tmp.p, roff.p, o->rowptr, (u32)k, o->colidx));
     }
-    if (i != FGPU_OK) { mat_release(o); return i; }
     // hub lists are only needed by BFS; products skip mat_finalize (no extra sync per hop)
-    *out = o;
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -238,27 +236,25 @@ fgpu_info delta_lmxm_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* F, co
                             const fgpu_mat* dm, u64* flops) {
     const bool has_dp = dp && dp->nnz, has_dm = dm && dm->nnz;
     if (!has_dp && !has_dm) return mxm_device(ctx, out, F, m, flops);  // hot path, matrix.rs:1333-1337
-    fgpu_mat *mask = nullptr, *acc = nullptr, *c = nullptr;
-    fgpu_info i = FGPU_OK;
+    MatRef c, acc, mask;
     if (has_dm) {
-        i = mxm_device(ctx, &mask, F, dm, nullptr);
-        if (i == FGPU_OK && mask->nnz == 0) { mat_release(mask); mask = nullptr; }
+        FGPU_TRY(mxm_device(ctx, &mask.m, F, dm, nullptr));
+        if (mask->nnz == 0) mask.reset();
     }
-    if (i == FGPU_OK && has_dp) {
-        i = mxm_device(ctx, &acc, F, dp, flops);
-        if (i == FGPU_OK && acc->nnz == 0) { mat_release(acc); acc = nullptr; }
+    if (has_dp) {
+        FGPU_TRY(mxm_device(ctx, &acc.m, F, dp, flops));
+        if (acc->nnz == 0) acc.reset();
     }
-    if (i == FGPU_OK) i = mxm_device(ctx, &c, F, m, flops);
-    if (i == FGPU_OK && (mask || acc)) {
-        fgpu_mat* merged = nullptr;
+    FGPU_TRY(mxm_device(ctx, &c.m, F, m, flops));
+    if (mask.get() || acc.get()) {
+        MatRef merged;
         // (F.m with MASK removed) U ACCUM — the accumulated dp product is not masked (matrix.rs:1382-1400)
-        i = mat_merge_entries(ctx, &merged, c, acc, mask, false, c->nrows, c->ncols, true);
-        if (i == FGPU_OK) { mat_release(c); c = merged; }
+        FGPU_TRY(mat_merge_entries(ctx, &merged.m, c.get(), acc.get(), mask.get(), false, c->nrows, c->ncols, true));
+        c = std::move(merged);
     }
-    mat_release(mask);
-    mat_release(acc);
-    if (i != FGPU_OK) { mat_release(c); return i; }
-    *out = c;
+    mask.reset();
+    acc.reset();
+    *out = c.release();
     return FGPU_OK;
 }
 
@@ -278,14 +274,14 @@ static fgpu_info filter_by_bitmap(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat*
     FGPU_TRY(scan_u32(ctx, cnt.p, rowptr.p, nrows + 1, nullptr));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, rowptr.p + nrows, &nnz));
-    fgpu_mat* o = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &o, nrows, c->ncols, nnz, false, 0, false));
+    MatRef o;
+    FGPU_TRY(mat_alloc(ctx, &o.m, nrows, c->ncols, nnz, false, 0, false));
     FGPU_HIP(hipMemcpyAsync(o->rowptr, rowptr.p, (nrows + 1) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream()));
     if (nnz) {
         FGPU_TRY(launch(compact_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)tmp.p,
                         (const u32*)c->rowptr, (const u32*)o->rowptr, (u32)nrows, o->colidx));
     }
-    *out = o;
+    *out = o.release();
     return FGPU_OK;
 }
 
@@ -302,24 +298,36 @@ static fgpu_info upload_sources(fgpu_ctx* ctx, fgpu_mat** out, const uint64_t* s
         }
         rp[i + 1] = (u32)ci.size();
     }
-    fgpu_mat* f = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &f, nsrc, ncols0, ci.size(), false, 0, false));
-    fgpu_info u = ctx->h2d(f->rowptr, rp.data(), rp.size() * sizeof(u32));
-    if (u == FGPU_OK && !ci.empty()) u = ctx->h2d(f->colidx, ci.data(), ci.size() * sizeof(u32));
-    if (u != FGPU_OK) { mat_release(f); return u; }
-    *out = f;
+    MatRef f;
+    FGPU_TRY(mat_alloc(ctx, &f.m, nsrc, ncols0, ci.size(), false, 0, false));
+    FGPU_TRY(ctx->h2d(f->rowptr, rp.data(), rp.size() * sizeof(u32)));
+    if (!ci.empty()) FGPU_TRY(ctx->h2d(f->colidx, ci.data(), ci.size() * sizeof(u32)));
+    *out = f.release();
     return FGPU_OK;
 }
 
-static fgpu_info check_hops(const fgpu_mat* const* m, const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
-                            uint64_t nsrc) {
+// The layers of a k-hop chain as the C entries receive them: hop h reads (m[h] \ dm[h]) U dp[h]; `dp` and `dm` are
+// nullable as arrays and per hop.
+struct Layers {
+    const fgpu_mat* const* m;
+    const fgpu_mat* const* dp;
+    const fgpu_mat* const* dm;
+    int nhops;
+    const fgpu_mat* dp_at(int h) const { return dp ? dp[h] : nullptr; }
+    const fgpu_mat* dm_at(int h) const { return dm ? dm[h] : nullptr; }
+};
+
+static fgpu_info check_hops(const Layers& L, uint64_t nsrc) {
+    const fgpu_mat* const* m = L.m;
+    const int nhops = L.nhops;
     FGPU_REQUIRE(nhops >= 1 && m, FGPU_INVALID, "expand: need at least one hop");
     FGPU_REQUIRE(nsrc < 0xFFFFFFFFull, FGPU_INVALID, "expand: too many source rows");
     for (int h = 0; h < nhops; ++h) {
+        const fgpu_mat *dph = L.dp_at(h), *dmh = L.dm_at(h);
         FGPU_REQUIRE(m[h], FGPU_NULL_POINTER, "expand: hop %d base matrix is NULL", h);
-        FGPU_REQUIRE(!dp || !dp[h] || (dp[h]->nrows == m[h]->nrows && dp[h]->ncols == m[h]->ncols),
+        FGPU_REQUIRE(!dph || (dph->nrows == m[h]->nrows && dph->ncols == m[h]->ncols),
                      FGPU_DIM_MISMATCH, "expand: hop %d dp dims differ from m", h);
-        FGPU_REQUIRE(!dm || !dm[h] || (dm[h]->nrows == m[h]->nrows && dm[h]->ncols == m[h]->ncols),
+        FGPU_REQUIRE(!dmh || (dmh->nrows == m[h]->nrows && dmh->ncols == m[h]->ncols),
                      FGPU_DIM_MISMATCH, "expand: hop %d dm dims differ from m", h);
         FGPU_REQUIRE(h == 0 || m[h]->nrows == m[h - 1]->ncols, FGPU_DIM_MISMATCH,
                      "expand: hop %d rows do not match hop %d columns", h, h - 1);
@@ -440,8 +448,8 @@ static fgpu_info first_hop_rows(fgpu_ctx* ctx, const fgpu_mat* f, const fgpu_mat
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, tot.p, &nnz));
     *T0 = nnz;
-    fgpu_mat* c = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &c, k, m->ncols, nnz, false, 0, false));
+    MatRef c;
+    FGPU_TRY(mat_alloc(ctx, &c.m, k, m->ncols, nnz, false, 0, false));
     const bool sum_next = next && !next->is_hyper() && next->nnz && nnz;
     fgpu_info i = FGPU_OK;
     {
@@ -465,8 +473,8 @@ static fgpu_info first_hop_rows(fgpu_ctx* ctx, const fgpu_mat* f, const fgpu_mat
         }
         *have_next = i == FGPU_OK;
     }
-    if (i != FGPU_OK) { mat_release(c); if (i == FGPU_DEVICE) set_error("first hop: device call failed"); return i; }
-    *out = c;
+    if (i != FGPU_OK) { if (i == FGPU_DEVICE) set_error("first hop: device call failed"); return i; }
+    *out = c.release();
     return FGPU_OK;
 }
 
@@ -671,8 +679,8 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
         if (mapped) { u32 w[1] = {0}; FGPU_TRY(pub_wait(ctx, seq, 1, w)); nnz = w[0]; }
         else FGPU_TRY(read_u32(ctx, tot.p + 2, &nnz));
     }
-    fgpu_mat* c = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &c, k, m->ncols, nnz, false, 0, false));
+    MatRef c;
+    FGPU_TRY(mat_alloc(ctx, &c.m, k, m->ncols, nnz, false, 0, false));
     const bool sum_next = next && !next->is_hyper() && next->nnz && nnz;
     fgpu_info i = FGPU_OK;
     if (hipMemcpyAsync(c->rowptr, rp.p, ((size_t)k + 1) * sizeof(u32), hipMemcpyDeviceToDevice, st) != hipSuccess) i = FGPU_DEVICE;
@@ -696,8 +704,8 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
         }
         *have_next = i == FGPU_OK;
     }
-    if (i != FGPU_OK) { mat_release(c); if (i == FGPU_DEVICE) set_error("dirty first hop: device call failed"); return i; }
-    *out = c;
+    if (i != FGPU_OK) { if (i == FGPU_DEVICE) set_error("dirty first hop: device call failed"); return i; }
+    *out = c.release();
     return FGPU_OK;
 }
 
@@ -783,213 +791,230 @@ static fgpu_info compact_source_rows(fgpu_ctx* ctx, const fgpu_mat* f, fgpu_mat*
         FGPU_TRY(read_u32(ctx, rank.p + k, &nlive));
     }
     if (nlive == 0 || bits_stride(nlive) >= bits_stride(k)) return FGPU_OK;
-    fgpu_mat* c = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &c, nlive, f->ncols, f->nnz, false, 0, false));
-    fgpu_info i = map.alloc(ctx, nlive);
-    if (i == FGPU_OK) {
-        u32 grid = cdiv((u64)k + 1, 256);
-        const u32 want = cdiv(f->nnz, 256 * 8);
-        if (grid < want) grid = want < (u32)ctx->cus * 4 ? want : (u32)ctx->cus * 4;
-        i = launch(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
-                   (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive);
-    }
-    if (i != FGPU_OK) { mat_release(c); return i; }
+    MatRef c;
+    FGPU_TRY(mat_alloc(ctx, &c.m, nlive, f->ncols, f->nnz, false, 0, false));
+    FGPU_TRY(map.alloc(ctx, nlive));
+    u32 grid = cdiv((u64)k + 1, 256);
+    const u32 want = cdiv(f->nnz, 256 * 8);
+    if (grid < want) grid = want < (u32)ctx->cus * 4 ? want : (u32)ctx->cus * 4;
+    FGPU_TRY(launch(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
+                    (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive));
     rank_out = std::move(rank);        // rank[i] = live rows before source row i, rank[k] = nlive: the way back (bp_to_csr)
-    *out = c;
+    *out = c.release();
     return FGPU_OK;
 }
 
 // One pass of a whole-frontier call (expand_count_scan below): F is already on the device — one entry per row, no empty
 // rows — and row i of it is row rowmap[i] of the CALL (what the checksum's row hashes need).
 struct ChainSources {
-    fgpu_mat* f = nullptr;           // taken over by the chain
+    MatRef f;                        // taken over by the chain
     DevBuf<u32>* rowmap = nullptr;   // moved into the bit state while the chain runs, handed back when it ends in CSR form
 };
 
-// shared front half of fgpu_expand / fgpu_expand_count: result stays on device
-static fgpu_info expand_device(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,
-                               const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
-                               const uint64_t* dst_label_bitmap, fgpu_mat** result, u64* flops,
-                               u64* count_only = nullptr /* [0] nnz, [1] checksum: no CSR is built when the
-                                                            chain ends in bit form */,
-                               bool want_checksum = true,
-                               BitState* keep_bits = nullptr /* a chain that ends in bit form hands its state over
-                                                                 (*result = nullptr) instead of emitting it */,
-                               ChainSources* pre = nullptr /* the sources are on the device already (src_ids unused) */) {
-    fgpu_mat* f = nullptr;
-    if (pre) {
-        f = pre->f;
-        pre->f = nullptr;
-    } else {
-        FGPU_TRY(check_hops(m, dp, dm, nhops, nsrc));
-        FGPU_TRY(upload_sources(ctx, &f, src_ids, nsrc, m[0]->nrows));
-    }
-    // Hops run on the sorted-CSR products until a hop's gather volume T makes the bit-parallel form
-    // cheaper (bitexpand.hip): it costs one pass over A' gathering max(64, 8 W) bytes per entry,
-    // whatever T is; the CSR product moves ~T entries several times.  Once dense, stay dense.
-    const int mode = ctx->opt.expand_mode;
+// the caller's destination-label bitmap (one bit per column; nullptr: no filter, bm.p stays nullptr) on the device
+static fgpu_info label_to_device(fgpu_ctx* ctx, const uint64_t* host_bitmap, u64 ncols, DevBuf<u64>& bm) {
+    if (!host_bitmap) return FGPU_OK;
+    const u64 nw = (ncols + 63) / 64;
+    FGPU_TRY(bm.alloc(ctx, nw + 1));
+    return ctx->h2d(bm.p, host_bitmap, nw * sizeof(u64));
+}
+
+// What a chain is asked for, and what it hands back.  A chain runs on sorted-CSR products until a hop is cheaper in bit form
+// and stays there; the END says what the caller wants of the form it finished in:
+//   Csr            the result as a snapshot, whatever form the chain ended in (ChainResult::Csr);
+//   Count(+Sum)    nnz (and the checksum): a chain in bit form counts there and builds no CSR (ChainResult::Counts), one
+//                  that stayed in CSR form hands that CSR back for the caller to count (ChainResult::Csr);
+//   Bits           a chain in bit form hands its state over (ChainResult::Bits), one in CSR form its CSR (ChainResult::Csr).
+enum class ChainEnd { Csr, Count, CountSum, Bits };
+struct ChainRequest {
+    const uint64_t* src_ids;          // one source per row, UINT64_MAX = the row stays empty (unused with `pre`)
+    uint64_t nsrc;
+    Layers L;
+    const uint64_t* label;            // destination-label bitmap on the host, nullable
+    u64* flops;                       // nullable: += the traversed edges
+    ChainEnd end;
+    ChainSources* pre = nullptr;      // the sources are on the device already
+    bool counting() const { return end == ChainEnd::Count || end == ChainEnd::CountSum; }
+};
+struct ChainResult {
+    enum Kind { None, Csr, Counts, Bits } kind = None;
+    MatRef mat;                       // Csr
+    u64 nnz = 0, checksum = 0;        // Counts (checksum only for ChainEnd::CountSum)
+    BitState bits;                    // Bits
+};
+
+// the running state of one chain: the frontier as a CSR `f`, or (once `bits`) as the bit state `bs`
+struct Chain {
+    MatRef f;
     bool bits = false;
     BitState bs;
-    if (pre && pre->rowmap) bs.rowmap = std::move(*pre->rowmap);
-    u64 T_known = 0;                      // traversed edges of f over T_for, when an earlier step already summed them
+    u64 T_known = 0;                      // traversed edges of T_f over T_for, when an earlier step already summed them
     const fgpu_mat *T_for = nullptr, *T_f = nullptr;
-    for (int h = 0; h < nhops; ++h) {
-        const fgpu_mat* mh = m[h];
-        const fgpu_mat* dph = dp ? dp[h] : nullptr;
-        const fgpu_mat* dmh = dm ? dm[h] : nullptr;
-        if (h == 0 && mode != 2 && ctx->opt.expand_first_hop && !(dph && dph->nnz) && !(dmh && dmh->nnz)) {
-            // clean first hop from one-entry rows: the source rows of m, copied (first_hop_rows above)
-            fgpu_mat* c = nullptr;
-            u64 T0 = 0, Tn = 0;
-            bool have = false;
-            const fgpu_info fi = first_hop_rows(ctx, f, mh, nhops > 1 ? m[1] : nullptr, &c, &T0, &Tn, &have);
-            if (fi == FGPU_OK) {
-                // (a first hop heavy enough for the bit form — T0 * ratio > nnz — is a batch of hub sources; it is still
-                // correct as a copy, and the next hop's decision sees its true volume)
-                if (flops) *flops += T0;
-                mat_release(f);
-                f = c;
-                if (have) { T_known = Tn; T_for = m[1]; T_f = f; }
-                continue;
-            }
-            if (fi != FGPU_NO_VALUE) { mat_release(f); return fi; }
-        } else if (h == 0 && mode != 2 && ctx->opt.expand_first_hop) {
-            // dirty first hop from one-entry rows: (m[u] \ dm[u]) U dp[u] row by row (first_hop_rows_dirty above)
-            fgpu_mat* c = nullptr;
-            u64 T0 = 0, Tn = 0;
-            bool have = false;
-            const fgpu_info fi = first_hop_rows_dirty(ctx, f, mh, dph, dmh, nhops > 1 ? m[1] : nullptr, &c, &T0, &Tn, &have);
-            if (fi == FGPU_OK) {
-                if (flops) *flops += T0;
-                mat_release(f);
-                f = c;
-                // (the next hop's traversed edges over its BASE matrix only: with a dirty next layer its dp part is summed there)
-                if (have) { T_known = Tn; T_for = m[1]; T_f = f; }
-                continue;
-            }
-            if (fi != FGPU_NO_VALUE) { mat_release(f); return fi; }
-        }
-        if (!bits && mode != 1 && !mh->is_hyper() && mh->nnz && mh->nnz < 0x7FFFFFFFull && f->nnz) {
-            const u64 w = (nsrc + 63) / 64;
-            const u64 mem = 2ull * (mh->nrows > mh->ncols ? mh->nrows : mh->ncols) * (w <= 64 ? 2 * w : w + 64) * 8;
-            bool go = (mode == 2);
-            u64 T = 0;
-            if ((mode == 0 && mem < (64ull << 30)) || go) {
-                fgpu_info i = FGPU_OK;
-                if (T_for == mh && T_f == f) T = T_known;          // summed while the first hop's rows were copied
-                else i = mxm_flops(ctx, f, mh, &T);
-                if (i != FGPU_OK) { mat_release(f); return i; }
-                // measured: a sorted-CSR hop costs ~0.12-0.16 ns per gathered entry (RMAT-22: 6 ms at T = 36 M; RMAT-26:
-                // 12 ms at T ~ 100 M), the first bit hop — the sparse pull, a flag probe per entry of A' — 5.5-6 ps per matrix
-                // entry whatever the row width (1.45 ms at RMAT-24, 6.2 ms at RMAT-26): the chain leaves the CSR form once
-                // T exceeds ~ nnz / 28.  (The round-1 rule, T * 1024 > nnz * row_bytes = nnz / 8 at 1024 rows, dated from a
-                // 41 ps-per-entry pull and kept RMAT-26 batches in an 8.7 ms sort.)
-                if (mode == 0) go = T * ctx->opt.expand_bits_ratio > mh->nnz;
-            }
-            if (go && ctx->opt.expand_compact && !pre) {
-                // the empty source rows stay behind (compact_source_rows above); bp_to_csr finds the way back
-                fgpu_mat* fc = nullptr;
-                const u32 k_full = (u32)f->nrows;
-                fgpu_info i = compact_source_rows(ctx, f, &fc, bs.rowmap, bs.rowrank);
-                if (i != FGPU_OK) { mat_release(f); return i; }
-                if (fc) { mat_release(f); f = fc; bs.nsrc_full = k_full; }
-            }
-            if (go) {
-                // leaving the CSR form: a frontier whose out-edges are FEW beside the matrix is pushed into the bit state
-                // (one 8-byte atomic per traversed edge: measured ~8 G/s on random words of a 2 GiB state — 33 M edges
-                // took 4.06 ms where the sparse pull takes 2.64 ms, so the bar is a 32nd of the matrix, not a quarter),
-                // a heavier one is scattered to a dense X and pulled
-                const fgpu_mat* dph_ = dp ? dp[h] : nullptr;
-                if (T * 32 <= mh->nnz) {
-                    if (flops) {
-                        *flops += T;
-                        if (dph_ && dph_->nnz) {
-                            u64 Tp = 0;
-                            fgpu_info i = mxm_flops(ctx, f, dph_, &Tp);
-                            if (i != FGPU_OK) { mat_release(f); return i; }
-                            *flops += Tp;
-                        }
-                    }
-                    fgpu_info i = bp_push_from_csr(ctx, bs, f, mh, dph_, dmh);
-                    mat_release(f);
-                    f = nullptr;
-                    if (i != FGPU_OK) return i;
-                    bits = true;
-                    continue;                       // this hop is done
-                }
-                fgpu_info i = bp_from_csr(ctx, bs, f);
-                mat_release(f);
-                f = nullptr;
-                if (i != FGPU_OK) return i;
-                bs.pre_for = mh;                    // T is this hop's traversed-edge count over mh: no need to sum it again
-                bs.pre_flops = T;
-                bits = true;
-            }
-        }
-        if (bits) {
-            if (count_only && h == nhops - 1 && ctx->opt.expand_fuse_count) {
-                // the last hop of a count-only chain counts its rows where they are produced: no result state is
-                // written, zeroed or read back (bitexpand.hip bp_hop_count)
-                DevBuf<u64> bm;
-                if (dst_label_bitmap) {
-                    const u64 nw = ((u64)mh->ncols + 63) / 64;
-                    FGPU_TRY(bm.alloc(ctx, nw + 1));
-                    FGPU_TRY(ctx->h2d(bm.p, dst_label_bitmap, nw * sizeof(u64)));
-                }
-                *result = nullptr;
-                return bp_hop_count(ctx, bs, mh, dph, dmh, flops, dst_label_bitmap ? bm.p : nullptr, &count_only[0],
-                                    want_checksum ? &count_only[1] : nullptr);
-            }
-            // (the hop right before a counting end of the chain writes its state in the layout that end gathers from)
-            FGPU_TRY(bp_hop(ctx, bs, mh, dph, dmh, flops, (flops && h + 1 < nhops) ? m[h + 1] : nullptr,
-                            (count_only && ctx->opt.expand_fuse_count && !keep_bits && h + 2 == nhops) ? m[h + 1] : nullptr));
-            continue;
-        }
-        fgpu_mat* c = nullptr;
-        fgpu_info i = delta_lmxm_device(ctx, &c, f, mh, dph, dmh, flops);
-        mat_release(f);
-        if (i != FGPU_OK) return i;
-        f = c;
+};
+
+// The first hop from one-entry rows: the source rows of m copied over a clean layer (first_hop_rows above),
+// (m[u] \ dm[u]) U dp[u] row by row over dirty ones (first_hop_rows_dirty).  *done = false: the shortcut does not apply.
+static fgpu_info chain_first_hop(fgpu_ctx* ctx, const ChainRequest& rq, Chain& ch, bool* done) {
+    const Layers& L = rq.L;
+    const fgpu_mat *dph = L.dp_at(0), *dmh = L.dm_at(0), *next = L.nhops > 1 ? L.m[1] : nullptr;
+    const bool clean = !(dph && dph->nnz) && !(dmh && dmh->nnz);
+    MatRef c;
+    u64 T0 = 0, Tn = 0;
+    bool have = false;
+    const fgpu_info fi = clean ? first_hop_rows(ctx, ch.f.get(), L.m[0], next, &c.m, &T0, &Tn, &have)
+                               : first_hop_rows_dirty(ctx, ch.f.get(), L.m[0], dph, dmh, next, &c.m, &T0, &Tn, &have);
+    *done = fi == FGPU_OK;
+    if (fi == FGPU_NO_VALUE) return FGPU_OK;
+    FGPU_TRY(fi);
+    // (a first hop heavy enough for the bit form — T0 * ratio > nnz — is a batch of hub sources; it is still
+    // correct as a copy, and the next hop's decision sees its true volume)
+    if (rq.flops) *rq.flops += T0;
+    ch.f = std::move(c);
+    // (over dirty layers: the next hop's traversed edges over its BASE matrix only — with a dirty next layer its dp part is
+    // summed there)
+    if (have) { ch.T_known = Tn; ch.T_for = L.m[1]; ch.T_f = ch.f.get(); }
+    return FGPU_OK;
+}
+
+// Hop h of a chain still in CSR form: does it leave that form here?  Hops run on the sorted-CSR products until a hop's
+// gather volume T makes the bit-parallel form cheaper (bitexpand.hip): it costs one pass over A' gathering max(64, 8 W)
+// bytes per entry, whatever T is; the CSR product moves ~T entries several times.  Once dense, stay dense.
+// On return ch.bits says whether it left; *hop_done, that hop h itself is done as well (the push).
+static fgpu_info chain_leave_csr(fgpu_ctx* ctx, const ChainRequest& rq, Chain& ch, int h, bool* hop_done) {
+    *hop_done = false;
+    const int mode = ctx->opt.expand_mode;
+    const fgpu_mat *mh = rq.L.m[h], *dph = rq.L.dp_at(h), *dmh = rq.L.dm_at(h);
+    if (mode == 1 || mh->is_hyper() || !mh->nnz || mh->nnz >= 0x7FFFFFFFull || !ch.f->nnz) return FGPU_OK;
+    const u64 w = (rq.nsrc + 63) / 64;
+    const u64 mem = 2ull * (mh->nrows > mh->ncols ? mh->nrows : mh->ncols) * (w <= 64 ? 2 * w : w + 64) * 8;
+    bool go = (mode == 2);
+    u64 T = 0;
+    if ((mode == 0 && mem < (64ull << 30)) || go) {
+        if (ch.T_for == mh && ch.T_f == ch.f.get()) T = ch.T_known;          // summed while the first hop's rows were copied
+        else FGPU_TRY(mxm_flops(ctx, ch.f.get(), mh, &T));
+        // measured: a sorted-CSR hop costs ~0.12-0.16 ns per gathered entry (RMAT-22: 6 ms at T = 36 M; RMAT-26:
+        // 12 ms at T ~ 100 M), the first bit hop — the sparse pull, a flag probe per entry of A' — 5.5-6 ps per matrix
+        // entry whatever the row width (1.45 ms at RMAT-24, 6.2 ms at RMAT-26): the chain leaves the CSR form once
+        // T exceeds ~ nnz / 28.  (The round-1 rule, T * 1024 > nnz * row_bytes = nnz / 8 at 1024 rows, dated from a
+        // 41 ps-per-entry pull and kept RMAT-26 batches in an 8.7 ms sort.)
+        if (mode == 0) go = T * ctx->opt.expand_bits_ratio > mh->nnz;
     }
-    if (bits && keep_bits) {
-        *keep_bits = std::move(bs);
-        *result = nullptr;
+    if (!go) return FGPU_OK;
+    if (ctx->opt.expand_compact && !rq.pre) {
+        // the empty source rows stay behind (compact_source_rows above); bp_to_csr finds the way back
+        MatRef fc;
+        const u32 k_full = (u32)ch.f->nrows;
+        FGPU_TRY(compact_source_rows(ctx, ch.f.get(), &fc.m, ch.bs.rowmap, ch.bs.rowrank));
+        if (fc.get()) { ch.f = std::move(fc); ch.bs.nsrc_full = k_full; }
+    }
+    // leaving the CSR form: a frontier whose out-edges are FEW beside the matrix is pushed into the bit state
+    // (one 8-byte atomic per traversed edge: measured ~8 G/s on random words of a 2 GiB state — 33 M edges
+    // took 4.06 ms where the sparse pull takes 2.64 ms, so the bar is a 32nd of the matrix, not a quarter),
+    // a heavier one is scattered to a dense X and pulled
+    if (T * 32 <= mh->nnz) {
+        if (rq.flops) {
+            *rq.flops += T;
+            if (dph && dph->nnz) {
+                u64 Tp = 0;
+                FGPU_TRY(mxm_flops(ctx, ch.f.get(), dph, &Tp));
+                *rq.flops += Tp;
+            }
+        }
+        FGPU_TRY(bp_push_from_csr(ctx, ch.bs, ch.f.get(), mh, dph, dmh));
+        ch.f.reset();
+        ch.bits = true;
+        *hop_done = true;
         return FGPU_OK;
     }
-    if (bits) {
-        DevBuf<u64> bm;
-        if (dst_label_bitmap) {
-            const u64 nw = ((u64)bs.n + 63) / 64;
-            FGPU_TRY(bm.alloc(ctx, nw + 1));
-            FGPU_TRY(ctx->h2d(bm.p, dst_label_bitmap, nw * sizeof(u64)));
-        }
-        fgpu_info ri;
-        if (count_only) {
-            *result = nullptr;
-            ri = bp_count(ctx, bs, dst_label_bitmap ? bm.p : nullptr, &count_only[0], want_checksum ? &count_only[1] : nullptr);
-        } else {
-            ri = bp_to_csr(ctx, bs, dst_label_bitmap ? bm.p : nullptr, result);
-        }
-        if (ri == FGPU_OK) bp_finish(ctx, bs);   // the next batch's state finds a zeroed block instead of a 2 GiB memset
-        return ri;
-    }
-    if (dst_label_bitmap) {
-        const u64 nc = f->ncols, nw = (nc + 63) / 64;
-        DevBuf<u64> bm;
-        fgpu_info i = bm.alloc(ctx, nw + 1);
-        if (i == FGPU_OK) {
-            i = ctx->h2d(bm.p, dst_label_bitmap, nw * sizeof(u64));
-        }
-        fgpu_mat* c = nullptr;
-        if (i == FGPU_OK) i = filter_by_bitmap(ctx, &c, f, bm.p);
-        if (i == FGPU_OK) i = (hipStreamSynchronize(ctx->stream()) == hipSuccess) ? FGPU_OK : FGPU_DEVICE;
-        mat_release(f);
-        if (i != FGPU_OK) return i;
-        f = c;
-    }
-    if (pre && pre->rowmap) *pre->rowmap = std::move(bs.rowmap);
-    *result = f;
+    FGPU_TRY(bp_from_csr(ctx, ch.bs, ch.f.get()));
+    ch.f.reset();
+    ch.bs.pre_for = mh;                    // T is this hop's traversed-edge count over mh: no need to sum it again
+    ch.bs.pre_flops = T;
+    ch.bits = true;
     return FGPU_OK;
+}
+
+// the last hop of a counting chain in bit form counts its rows where they are produced: no result state is written,
+// zeroed or read back (bitexpand.hip bp_hop_count)
+static fgpu_info chain_count_hop(fgpu_ctx* ctx, const ChainRequest& rq, Chain& ch, int h, ChainResult& out) {
+    const fgpu_mat* mh = rq.L.m[h];
+    DevBuf<u64> bm;
+    FGPU_TRY(label_to_device(ctx, rq.label, mh->ncols, bm));
+    FGPU_TRY(bp_hop_count(ctx, ch.bs, mh, rq.L.dp_at(h), rq.L.dm_at(h), rq.flops, bm.p, &out.nnz,
+                          rq.end == ChainEnd::CountSum ? &out.checksum : nullptr));
+    out.kind = ChainResult::Counts;
+    return FGPU_OK;
+}
+
+// every hop is done: the form the chain is in, turned into what the request's end asks for
+static fgpu_info chain_end(fgpu_ctx* ctx, const ChainRequest& rq, Chain& ch, ChainResult& out) {
+    if (ch.bits && rq.end == ChainEnd::Bits) {
+        out.bits = std::move(ch.bs);
+        out.kind = ChainResult::Bits;
+        return FGPU_OK;
+    }
+    if (ch.bits) {
+        DevBuf<u64> bm;
+        FGPU_TRY(label_to_device(ctx, rq.label, ch.bs.n, bm));
+        if (rq.counting()) {
+            FGPU_TRY(bp_count(ctx, ch.bs, bm.p, &out.nnz, rq.end == ChainEnd::CountSum ? &out.checksum : nullptr));
+            out.kind = ChainResult::Counts;
+        } else {
+            FGPU_TRY(bp_to_csr(ctx, ch.bs, bm.p, &out.mat.m));
+            out.kind = ChainResult::Csr;
+        }
+        bp_finish(ctx, ch.bs);   // the next batch's state finds a zeroed block instead of a 2 GiB memset
+        return FGPU_OK;
+    }
+    if (rq.label) {
+        DevBuf<u64> bm;
+        FGPU_TRY(label_to_device(ctx, rq.label, ch.f->ncols, bm));
+        MatRef c;
+        FGPU_TRY(filter_by_bitmap(ctx, &c.m, ch.f.get(), bm.p));
+        if (hipStreamSynchronize(ctx->stream()) != hipSuccess) return FGPU_DEVICE;
+        ch.f = std::move(c);
+    }
+    if (rq.pre && rq.pre->rowmap) *rq.pre->rowmap = std::move(ch.bs.rowmap);
+    out.mat = std::move(ch.f);
+    out.kind = ChainResult::Csr;
+    return FGPU_OK;
+}
+
+// the k-hop chain every fgpu_expand* entry runs: the result stays on the device
+static fgpu_info expand_device(fgpu_ctx* ctx, const ChainRequest& rq, ChainResult& out) {
+    const Layers& L = rq.L;
+    Chain ch;
+    if (rq.pre) {
+        ch.f = std::move(rq.pre->f);
+        if (rq.pre->rowmap) ch.bs.rowmap = std::move(*rq.pre->rowmap);
+    } else {
+        FGPU_TRY(check_hops(L, rq.nsrc));
+        FGPU_TRY(upload_sources(ctx, &ch.f.m, rq.src_ids, rq.nsrc, L.m[0]->nrows));
+    }
+    const bool fused_count = rq.counting() && ctx->opt.expand_fuse_count;
+    for (int h = 0; h < L.nhops; ++h) {
+        if (h == 0 && ctx->opt.expand_mode != 2 && ctx->opt.expand_first_hop) {
+            bool done = false;
+            FGPU_TRY(chain_first_hop(ctx, rq, ch, &done));
+            if (done) continue;
+        }
+        if (!ch.bits) {
+            bool hop_done = false;
+            FGPU_TRY(chain_leave_csr(ctx, rq, ch, h, &hop_done));
+            if (hop_done) continue;
+        }
+        if (ch.bits) {
+            if (fused_count && h == L.nhops - 1) return chain_count_hop(ctx, rq, ch, h, out);
+            // (the hop right before a counting end of the chain writes its state in the layout that end gathers from)
+            FGPU_TRY(bp_hop(ctx, ch.bs, L.m[h], L.dp_at(h), L.dm_at(h), rq.flops, (rq.flops && h + 1 < L.nhops) ? L.m[h + 1] : nullptr,
+                            (fused_count && h + 2 == L.nhops) ? L.m[h + 1] : nullptr));
+            continue;
+        }
+        MatRef c;
+        FGPU_TRY(delta_lmxm_device(ctx, &c.m, ch.f.get(), L.m[h], L.dp_at(h), L.dm_at(h), rq.flops));
+        ch.f = std::move(c);
+    }
+    return chain_end(ctx, rq, ch, out);
 }
 
 // ---- exact trail counts for k <= 2 -------------------------------------------------------------
@@ -1197,8 +1222,7 @@ struct ScanJob {
     fgpu_ctx* ctx;
     const u32 *lid, *lrow;
     u32 nlive, pass_rows, npasses;
-    const fgpu_mat* const* m; const fgpu_mat* const* dp; const fgpu_mat* const* dm;
-    int nhops;
+    Layers L;
     const uint64_t* label;
     bool want_cs, want_flops;
     std::atomic<u32> next{0};
@@ -1213,24 +1237,19 @@ static fgpu_info scan_one_pass(ScanJob& j, u32 p, u64* nnz, u64* cs, u64* fl) {
     fgpu_ctx* ctx = j.ctx;
     const u32 first = p * j.pass_rows;
     const u32 k = std::min(j.pass_rows, j.nlive - first);
-    fgpu_mat* f = nullptr;
     DevBuf<u32> rm;
-    FGPU_TRY(rm.alloc(ctx, k));
-    FGPU_TRY(mat_alloc(ctx, &f, k, j.m[0]->nrows, k, false, 0, false));
-    const fgpu_info li = launch(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, first, k,
-                                f->rowptr, f->colidx, rm.p);
-    if (li != FGPU_OK) { mat_release(f); return li; }
     ChainSources pre;
-    pre.f = f;
+    FGPU_TRY(rm.alloc(ctx, k));
+    FGPU_TRY(mat_alloc(ctx, &pre.f.m, k, j.L.m[0]->nrows, k, false, 0, false));
+    FGPU_TRY(launch(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, first, k,
+                    pre.f->rowptr, pre.f->colidx, rm.p));
     pre.rowmap = &rm;
-    fgpu_mat* r = nullptr;
-    u64 cnt[2] = {0, 0};
     *fl = 0;
-    FGPU_TRY(expand_device(ctx, nullptr, k, j.m, j.dp, j.dm, j.nhops, j.label, &r, j.want_flops ? fl : nullptr, cnt, j.want_cs, nullptr, &pre));
-    if (!r) { *nnz = cnt[0]; *cs = cnt[1]; return FGPU_OK; }
-    const fgpu_info i = count_csr_result(ctx, r, rm.p, nnz, j.want_cs ? cs : nullptr);
-    mat_release(r);
-    return i;
+    const ChainRequest rq{nullptr, k, j.L, j.label, j.want_flops ? fl : nullptr, j.want_cs ? ChainEnd::CountSum : ChainEnd::Count, &pre};
+    ChainResult r;
+    FGPU_TRY(expand_device(ctx, rq, r));
+    if (r.kind == ChainResult::Counts) { *nnz = r.nnz; *cs = r.checksum; return FGPU_OK; }
+    return count_csr_result(ctx, r.mat.get(), rm.p, nnz, j.want_cs ? cs : nullptr);
 }
 
 static void scan_worker(ScanJob* j) {
@@ -1242,19 +1261,26 @@ static void scan_worker(ScanJob* j) {
         if (p >= j->npasses) break;
         u64 a = 0, b = 0, c = 0;
         err = scan_one_pass(*j, p, &a, &b, &c);
-        if (err != FGPU_OK) { j->failed.store(true); break; }
+        if (err != FGPU_OK) {
+            // the pass may have left kernels queued on this lane's stream that read lid / lrow, which the caller frees once
+            // the workers are joined: wait for them (whatever the wait returns, the first error is the one reported)
+            (void)hipStreamSynchronize(j->ctx->stream());
+            j->failed.store(true);
+            break;
+        }
         nnz += a; cs += b; flops += c;
     }
-    // (a worker thread's stream has nothing pending here: every pass ends with the read-back of its sums)
+    // (after a successful pass the lane's stream has nothing pending: every pass ends with the read-back of its sums; after a
+    // failed one it was drained above)
     std::lock_guard<std::mutex> g(j->mu);
     j->nnz += nnz; j->cs += cs; j->flops += flops;
     if (err != FGPU_OK && j->err == FGPU_OK) { j->err = err; j->msg = get_error(); }
 }
 
-static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,
-                                   const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
+static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const Layers& L,
                                    const uint64_t* dst_label_bitmap, uint64_t* out_nnz, uint64_t* checksum, uint64_t* flops) {
-    FGPU_TRY(check_hops(m, dp, dm, nhops, nsrc));
+    FGPU_TRY(check_hops(L, nsrc));
+    const fgpu_mat* const* m = L.m;
     const u64 ncols0 = m[0]->nrows;
     const u32 n = (u32)nsrc;
     std::vector<u32> ids(n);
@@ -1269,7 +1295,7 @@ static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
     FGPU_TRY(flag.alloc(ctx, (size_t)n + 1));
     FGPU_TRY(pos.alloc(ctx, (size_t)n + 1));
     FGPU_TRY(ctx->h2d(dids.p, ids.data(), (size_t)n * sizeof(u32)));
-    const fgpu_mat* dp0 = dp && dp[0] && dp[0]->nnz ? dp[0] : nullptr;
+    const fgpu_mat* dp0 = L.dp_at(0) && L.dp_at(0)->nnz ? L.dp_at(0) : nullptr;
     FGPU_TRY(launch(scan_live_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, n, view_of(m[0]),
                     dp0 ? view_of(dp0) : view_of(m[0]), dp0 ? 1u : 0u, flag.p));
     FGPU_TRY(scan_u32(ctx, flag.p, pos.p, (u64)n + 1, nullptr));
@@ -1289,7 +1315,7 @@ static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
     j.ctx = ctx; j.lid = lid.p; j.lrow = lrow.p; j.nlive = nlive;
     j.pass_rows = (u32)ctx->opt.expand_scan_rows;
     j.npasses = cdiv(nlive, j.pass_rows);
-    j.m = m; j.dp = dp; j.dm = dm; j.nhops = nhops; j.label = dst_label_bitmap;
+    j.L = L; j.label = dst_label_bitmap;
     j.want_cs = checksum != nullptr; j.want_flops = flops != nullptr;
     ctx->scan_last_passes.store(j.npasses, std::memory_order_relaxed);
     u32 lanes = (u32)ctx->opt.expand_scan_lanes;
@@ -1335,12 +1361,10 @@ fgpu_info fgpu_expand(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, con
     FGPU_REQUIRE(ctx && out_rowptr && out_dest && out_nnz, FGPU_NULL_POINTER, "fgpu_expand: NULL argument");
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand: NULL src_ids");
     if (flops) *flops = 0;
-    fgpu_mat* r = nullptr;
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops));
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, ChainEnd::Csr}, res));
     uint64_t *vals = nullptr;
-    fgpu_info i = fgpu_mat_export_csr(ctx, r, out_rowptr, out_dest, &vals, out_nnz);
-    mat_release(r);
-    return i;
+    return fgpu_mat_export_csr(ctx, res.mat.get(), out_rowptr, out_dest, &vals, out_nnz);
 }
 
 static fgpu_info expand_pairs_impl(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,
@@ -1354,9 +1378,9 @@ static fgpu_info expand_pairs_impl(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
                  (unsigned long long)nsrc);
     *out_row = nullptr; *out_dest = nullptr; *out_n = 0;
     if (flops) *flops = 0;
-    fgpu_mat* r = nullptr;
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops));
-    struct Rel { fgpu_mat* r; ~Rel() { if (r) mat_release(r); } } rel{r};
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, ChainEnd::Csr}, res));
+    const fgpu_mat* r = res.mat.get();
     if (nsrc == 0 || r->nnz == 0) return FGPU_OK;
     // (the kernels below index the result's row pointers densely, nsrc + 1 of them)
     FGPU_REQUIRE(!r->is_hyper() && r->nrows == nsrc, FGPU_INVALID, "fgpu_expand_pairs: the chain's result is not a dense-row CSR of %llu rows",
@@ -1412,18 +1436,12 @@ static fgpu_info expand_pairs_impl(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
             });
         }));
     }
-    void* hrow = ctx->result_alloc(n * rb);
-    void* hdest = ctx->result_alloc(n * db);
-    if (!hrow || !hdest) {
-        ctx->host_free(hrow); ctx->host_free(hdest);
-        set_error("fgpu_expand_pairs: host allocation failed");
-        return FGPU_OOM;
-    }
-    fgpu_info i = ctx->d2h(hdest, dest_is_colidx ? (const void*)r->colidx : (const void*)ddest.p, n * db);
-    if (i == FGPU_OK) i = ctx->d2h(hrow, drow.p, n * rb);
-    if (i != FGPU_OK) { ctx->host_free(hrow); ctx->host_free(hdest); return i; }
-    *out_row = hrow;
-    *out_dest = hdest;
+    ResultBuf hrow, hdest;
+    FGPU_REQUIRE(hrow.alloc(ctx, n * rb) && hdest.alloc(ctx, n * db), FGPU_OOM, "fgpu_expand_pairs: host allocation failed");
+    FGPU_TRY(ctx->d2h(hdest.p, dest_is_colidx ? (const void*)r->colidx : (const void*)ddest.p, n * db));
+    FGPU_TRY(ctx->d2h(hrow.p, drow.p, n * rb));
+    *out_row = hrow.release();
+    *out_dest = hdest.release();
     *out_n = n;
     return FGPU_OK;
 }
@@ -1449,19 +1467,18 @@ fgpu_info fgpu_expand_probe(fgpu_ctx* ctx, const uint64_t* src_ids, const uint64
                             uint8_t* present, uint64_t* flops) {
     FGPU_REQUIRE(ctx && present && (nsrc == 0 || (src_ids && dst_ids)), FGPU_NULL_POINTER, "fgpu_expand_probe: NULL argument");
     if (flops) *flops = 0;
-    FGPU_TRY(check_hops(m, dp, dm, nhops, nsrc));
+    const Layers L{m, dp, dm, nhops};
+    FGPU_TRY(check_hops(L, nsrc));
     if (nsrc == 0) return FGPU_OK;
     const u32 k = (u32)nsrc;
     memset(present, 0, k);
-    const fgpu_mat* ml = m[nhops - 1];
-    const fgpu_mat* dpl = dp ? dp[nhops - 1] : nullptr;
-    const fgpu_mat* dml = dm ? dm[nhops - 1] : nullptr;
-    // the chain up to the last hop: a sorted-CSR frontier, or the bit state it ended in
-    fgpu_mat* f = nullptr;
-    BitState bs;
-    if (nhops == 1) FGPU_TRY(upload_sources(ctx, &f, src_ids, nsrc, m[0]->nrows));
-    else FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops - 1, nullptr, &f, flops, nullptr, true, &bs));
-    struct Rel { fgpu_mat* f; ~Rel() { if (f) mat_release(f); } } rel{f};
+    const fgpu_mat *ml = m[nhops - 1], *dpl = L.dp_at(nhops - 1), *dml = L.dm_at(nhops - 1);
+    // the chain up to the last hop: a sorted-CSR frontier (f), or the bit state it ended in (bs)
+    ChainResult res;
+    if (nhops == 1) FGPU_TRY(upload_sources(ctx, &res.mat.m, src_ids, nsrc, m[0]->nrows));
+    else FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops - 1}, nullptr, flops, ChainEnd::Bits}, res));
+    const fgpu_mat* f = res.kind == ChainResult::Bits ? nullptr : res.mat.get();
+    BitState& bs = res.bits;
     // destinations (a vertex the last matrix does not have, or one the label filter drops: no match), the bit of every row
     const u64 ncols = ml->ncols;
     std::vector<u32> hdst(k), hbit(k), order(k), sdst(k), srow(k);
@@ -1516,7 +1533,7 @@ struct fgpu_expand_stream {
     static constexpr int NS = 4;
     fgpu_ctx* ctx = nullptr;
     hipStream_t st = nullptr;        // the opening thread's lane
-    fgpu_mat* r = nullptr;           // F on the device
+    MatRef r;                        // F on the device
     std::vector<u32> rp;             // its row pointers (nsrc + 1)
     u64 nsrc = 0, chunk_rows = 0;
     int width = 8;                   // bytes per destination id handed out
@@ -1564,8 +1581,7 @@ fgpu_info fgpu_expand_stream_close(fgpu_expand_stream* s) {
         if (sl.host) ctx->host_free(sl.host);
         if (sl.wide) ctx->dev_free(sl.wide);
     }
-    if (s->r) mat_release(s->r);
-    delete s;
+    delete s;   // (and with it the result on the device)
     return FGPU_OK;
 }
 
@@ -1579,11 +1595,12 @@ fgpu_info fgpu_expand_stream_open(fgpu_ctx* ctx, const uint64_t* src_ids, uint64
     FGPU_REQUIRE(chunk_rows >= 1, FGPU_INVALID, "fgpu_expand_stream_open: chunk_rows must be >= 1");
     *out = nullptr;
     if (flops) *flops = 0;
-    fgpu_mat* r = nullptr;
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops));
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, ChainEnd::Csr}, res));
     fgpu_expand_stream* s = new (std::nothrow) fgpu_expand_stream();
-    if (!s) { mat_release(r); set_error("fgpu_expand_stream_open: out of host memory"); return FGPU_OOM; }
-    s->ctx = ctx; s->st = ctx->stream(); s->r = r; s->nsrc = nsrc; s->chunk_rows = chunk_rows; s->width = dest_bits / 8;
+    FGPU_REQUIRE(s != nullptr, FGPU_OOM, "fgpu_expand_stream_open: out of host memory");
+    const fgpu_mat* r = res.mat.get();
+    s->ctx = ctx; s->st = ctx->stream(); s->r = std::move(res.mat); s->nsrc = nsrc; s->chunk_rows = chunk_rows; s->width = dest_bits / 8;
     fgpu_info i = FGPU_OK;
     s->rp.assign(nsrc + 1, 0);
     if (r->nnz) {
@@ -1654,22 +1671,17 @@ fgpu_info fgpu_expand32(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, c
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand32: NULL src_ids");
     *out_rowptr = nullptr; *out_dest = nullptr; *out_nnz = 0;
     if (flops) *flops = 0;
-    fgpu_mat* r = nullptr;
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops));
-    struct Rel { fgpu_mat* r; ~Rel() { if (r) mat_release(r); } } rel{r};
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, ChainEnd::Csr}, res));
+    const fgpu_mat* r = res.mat.get();
     FGPU_REQUIRE(!r->is_hyper() && r->nrows == nsrc, FGPU_INVALID, "fgpu_expand32: the chain's result is not a dense-row CSR");
     // the device arrays as they are: two DMAs into pinned result blocks, nothing widened anywhere
-    u32* hrp = (u32*)ctx->result_alloc((nsrc + 1) * sizeof(u32));
-    u32* hci = (u32*)ctx->result_alloc((r->nnz ? r->nnz : 1) * sizeof(u32));
-    fgpu_info i = (hrp && hci) ? FGPU_OK : FGPU_OOM;
-    if (i == FGPU_OK) i = ctx->d2h(hrp, r->rowptr, (nsrc + 1) * sizeof(u32));
-    if (i == FGPU_OK && r->nnz) i = ctx->d2h(hci, r->colidx, r->nnz * sizeof(u32));
-    if (i != FGPU_OK) {
-        ctx->host_free(hrp); ctx->host_free(hci);
-        if (i == FGPU_OOM) set_error("fgpu_expand32: host allocation failed");
-        return i;
-    }
-    *out_rowptr = hrp; *out_dest = hci; *out_nnz = r->nnz;
+    ResultBuf hrp, hci;
+    FGPU_REQUIRE(hrp.alloc(ctx, (nsrc + 1) * sizeof(u32)) && hci.alloc(ctx, (r->nnz ? r->nnz : 1) * sizeof(u32)), FGPU_OOM,
+                 "fgpu_expand32: host allocation failed");
+    FGPU_TRY(ctx->d2h(hrp.p, r->rowptr, (nsrc + 1) * sizeof(u32)));
+    if (r->nnz) FGPU_TRY(ctx->d2h(hci.p, r->colidx, r->nnz * sizeof(u32)));
+    *out_rowptr = (u32*)hrp.release(); *out_dest = (u32*)hci.release(); *out_nnz = r->nnz;
     return FGPU_OK;
 }
 
@@ -1679,11 +1691,10 @@ fgpu_info fgpu_expand_mat(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc,
     FGPU_REQUIRE(ctx && out, FGPU_NULL_POINTER, "fgpu_expand_mat: NULL argument");
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand_mat: NULL src_ids");
     if (flops) *flops = 0;
-    fgpu_mat* r = nullptr;
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops));
-    fgpu_info i = ctx->publish();   // the new handle may go to another thread
-    if (i != FGPU_OK) { mat_release(r); return i; }
-    *out = r;
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, ChainEnd::Csr}, res));
+    FGPU_TRY(ctx->publish());   // the new handle may go to another thread
+    *out = res.mat.release();
     return FGPU_OK;
 }
 
@@ -1695,18 +1706,16 @@ fgpu_info fgpu_expand_count(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsr
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand_count: NULL src_ids");
     if (flops) *flops = 0;
     if (ctx->opt.expand_scan_min > 0 && nsrc > (u64)ctx->opt.expand_scan_min && ctx->opt.expand_mode != 1)
-        return expand_count_scan(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, out_nnz, checksum, flops);
-    fgpu_mat* r = nullptr;
-    u64 cnt[2] = {0, 0};
-    FGPU_TRY(expand_device(ctx, src_ids, nsrc, m, dp, dm, nhops, dst_label_bitmap, &r, flops, cnt, checksum != nullptr));
-    if (!r) {   // the chain ended in bit form: counted there, no CSR was materialized
-        *out_nnz = cnt[0];
-        if (checksum) *checksum = cnt[1];
+        return expand_count_scan(ctx, src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, out_nnz, checksum, flops);
+    ChainResult res;
+    FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops}, dst_label_bitmap, flops, checksum ? ChainEnd::CountSum : ChainEnd::Count},
+                           res));
+    if (res.kind == ChainResult::Counts) {   // the chain ended in bit form: counted there, no CSR was materialized
+        *out_nnz = res.nnz;
+        if (checksum) *checksum = res.checksum;
         return FGPU_OK;
     }
-    const fgpu_info i = count_csr_result(ctx, r, nullptr, out_nnz, checksum);
-    mat_release(r);
-    return i;
+    return count_csr_result(ctx, res.mat.get(), nullptr, out_nnz, checksum);
 }
 
 fgpu_info fgpu_expand_levels(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,
@@ -1715,31 +1724,26 @@ fgpu_info fgpu_expand_levels(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t ns
                              uint64_t* union_nnz, uint64_t* union_checksum, uint64_t* flops) {
     FGPU_REQUIRE(ctx && hop_nnz, FGPU_NULL_POINTER, "fgpu_expand_levels: NULL argument");
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand_levels: NULL src_ids");
-    FGPU_TRY(check_hops(m, dp, dm, nhops, nsrc));
+    const Layers L{m, dp, dm, nhops};
+    FGPU_TRY(check_hops(L, nsrc));
     for (int h = 0; h < nhops; ++h)
         FGPU_REQUIRE(!m[h]->is_hyper() && m[h]->nnz < 0x7FFFFFFFull, FGPU_INVALID,
                      "fgpu_expand_levels: hop %d needs a non-hypersparse base matrix with nnz < 2^31", h);
     if (flops) *flops = 0;
     if (union_nnz) *union_nnz = 0;
     if (union_checksum) *union_checksum = 0;
-    fgpu_mat* f = nullptr;
-    FGPU_TRY(upload_sources(ctx, &f, src_ids, nsrc, m[0]->nrows));
+    MatRef f;
+    FGPU_TRY(upload_sources(ctx, &f.m, src_ids, nsrc, m[0]->nrows));
     // the whole chain runs in bit form (one bit per source row): every hop is one pass over the cached
     // transpose whatever the frontier size, and the union over the hops is a word-wise OR
     BitState bs, un;
-    fgpu_info i = bp_from_csr(ctx, bs, f);
-    mat_release(f);
-    if (i != FGPU_OK) return i;
+    FGPU_TRY(bp_from_csr(ctx, bs, f.get()));
+    f.reset();
     DevBuf<u64> bm;
-    const u64* label_dev = nullptr;
     for (int h = 0; h < nhops; ++h) {
-        FGPU_TRY(bp_hop(ctx, bs, m[h], dp ? dp[h] : nullptr, dm ? dm[h] : nullptr, flops));
-        if (dst_label_bitmap && h == 0) {   // the destination label applies to every reported set
-            const u64 nw = ((u64)bs.n + 63) / 64;
-            FGPU_TRY(bm.alloc(ctx, nw + 1));
-            FGPU_TRY(ctx->h2d(bm.p, dst_label_bitmap, nw * sizeof(u64)));
-            label_dev = bm.p;
-        }
+        FGPU_TRY(bp_hop(ctx, bs, m[h], L.dp_at(h), L.dm_at(h), flops));
+        if (h == 0) FGPU_TRY(label_to_device(ctx, dst_label_bitmap, bs.n, bm));   // the destination label applies to every reported set
+        const u64* label_dev = bm.p;
         u64 n = 0, cs = 0;
         FGPU_TRY(bp_count(ctx, bs, label_dev, &n, hop_checksum ? &cs : nullptr));
         hop_nnz[h] = n;
@@ -1748,7 +1752,7 @@ fgpu_info fgpu_expand_levels(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t ns
     }
     if (union_nnz || union_checksum) {
         u64 n = 0, cs = 0;
-        FGPU_TRY(bp_count(ctx, un, label_dev, &n, union_checksum ? &cs : nullptr));
+        FGPU_TRY(bp_count(ctx, un, bm.p, &n, union_checksum ? &cs : nullptr));
         if (union_nnz) *union_nnz = n;
         if (union_checksum) *union_checksum = cs;
     }
@@ -1767,102 +1771,88 @@ extern "C" fgpu_info fgpu_expand_trail_counts(fgpu_ctx* ctx, const uint64_t* src
     FGPU_REQUIRE(nsrc == 0 || src_ids, FGPU_NULL_POINTER, "fgpu_expand_trail_counts: NULL src_ids");
     FGPU_REQUIRE(nhops == 1 || nhops == 2, FGPU_INVALID,
                  "fgpu_expand_trail_counts: trail counts have a product form for 1 or 2 hops only (cond_var_len_traverse.rs keeps the DFS beyond)");
-    FGPU_TRY(check_hops(m, dp, dm, nhops, nsrc));
+    const Layers L{m, dp, dm, nhops};
+    FGPU_TRY(check_hops(L, nsrc));
     for (u64 i = 0; i < nsrc; ++i)
         FGPU_REQUIRE(src_ids[i] != UINT64_MAX, FGPU_INVALID, "fgpu_expand_trail_counts: every row needs a source");
     // `-[:T*1..2]->` walks ONE relationship: the "same edge twice" correction of the two-hop count (the a -> a -> a walk
     // over one self-loop) is only meaningful when both hops read the same layers.  With different layers per hop no
     // edge can repeat and the subtraction would undercount, so that form is refused rather than answered wrongly.
-    FGPU_REQUIRE(nhops == 1 || (m[0] == m[1] && (dp ? dp[0] : nullptr) == (dp ? dp[1] : nullptr) &&
-                                (dm ? dm[0] : nullptr) == (dm ? dm[1] : nullptr)),
+    FGPU_REQUIRE(nhops == 1 || (m[0] == m[1] && L.dp_at(0) == L.dp_at(1) && L.dm_at(0) == L.dm_at(1)),
                  FGPU_INVALID, "fgpu_expand_trail_counts: both hops must read the same relationship layers (one var-length relationship)");
     // effective layers (m \ dm) U dp — real edges, no row-level mask quirk: these are counts of paths, not a delta_lmxm
     std::vector<const fgpu_mat*> eff(nhops, nullptr);
-    std::vector<fgpu_mat*> owned;
-    auto cleanup = [&]() { for (auto* x : owned) mat_release(x); };
-    fgpu_info i = FGPU_OK;
-    for (int h = 0; h < nhops && i == FGPU_OK; ++h) {
-        const fgpu_mat* dph = dp ? dp[h] : nullptr;
-        const fgpu_mat* dmh = dm ? dm[h] : nullptr;
+    std::vector<MatRef> owned;
+    for (int h = 0; h < nhops; ++h) {
+        const fgpu_mat *dph = L.dp_at(h), *dmh = L.dm_at(h);
         const bool dirty = (dph && dph->nnz) || (dmh && dmh->nnz);
         if (!dirty && !m[h]->is_hyper()) { eff[h] = m[h]; continue; }
-        fgpu_mat* e = nullptr;
-        i = mat_merge_entries(ctx, &e, m[h], dph, dmh, false, m[h]->nrows, m[h]->ncols, !weighted);
-        if (i == FGPU_OK) { owned.push_back(e); eff[h] = e; }
+        MatRef e;
+        FGPU_TRY(mat_merge_entries(ctx, &e.m, m[h], dph, dmh, false, m[h]->nrows, m[h]->ncols, !weighted));
+        eff[h] = e.get();
+        owned.push_back(std::move(e));
     }
-    if (i != FGPU_OK) { cleanup(); return i; }
     if (weighted)
         for (int h = 0; h < nhops; ++h)
-            if (!eff[h]->vals) { cleanup(); set_error("fgpu_expand_trail_counts: weighted counts need UINT64 multiplicity layers"); return FGPU_INVALID; }
-    fgpu_mat *f0 = nullptr, *c1 = nullptr, *c2 = nullptr;
+            FGPU_REQUIRE(eff[h]->vals, FGPU_INVALID, "fgpu_expand_trail_counts: weighted counts need UINT64 multiplicity layers");
+    MatRef f0, c1, c2;
     DevBuf<u32> dsrc;
     DevBuf<u64> w1, cnt;
     std::vector<u32> s32(nsrc);
     for (u64 k = 0; k < nsrc; ++k) s32[k] = (u32)src_ids[k];
-    auto run = [&]() -> fgpu_info {
-        FGPU_TRY(upload_sources(ctx, &f0, src_ids, nsrc, eff[0]->nrows));
-        FGPU_TRY(dsrc.alloc(ctx, nsrc));
-        FGPU_TRY(ctx->h2d(dsrc.p, s32.data(), nsrc * sizeof(u32)));
-        FGPU_TRY(mxm_device(ctx, &c1, f0, eff[0], nullptr));
-        FGPU_TRY(w1.alloc(ctx, c1->nnz));
-        if (c1->nnz) {
-            u32 grid = cdiv(nsrc, 4);
+    FGPU_TRY(upload_sources(ctx, &f0.m, src_ids, nsrc, eff[0]->nrows));
+    FGPU_TRY(dsrc.alloc(ctx, nsrc));
+    FGPU_TRY(ctx->h2d(dsrc.p, s32.data(), nsrc * sizeof(u32)));
+    FGPU_TRY(mxm_device(ctx, &c1.m, f0.get(), eff[0], nullptr));
+    FGPU_TRY(w1.alloc(ctx, c1->nnz));
+    if (c1->nnz) {
+        u32 grid = cdiv(nsrc, 4);
+        if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
+        FGPU_TRY(launch(row_weight_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1.get()), view_of(eff[0]),
+                        weighted ? (const u64*)eff[0]->vals : (const u64*)nullptr, (const u32*)dsrc.p, (u32)nsrc, w1.p));
+    }
+    const fgpu_mat* res = c1.get();
+    const u64* res_cnt = w1.p;
+    if (nhops == 2) {
+        FGPU_TRY(mxm_device(ctx, &c2.m, c1.get(), eff[1], nullptr));
+        FGPU_TRY(cnt.alloc(ctx, c2->nnz));
+        FGPU_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(c2->nnz ? c2->nnz : 1) * sizeof(u64), ctx->stream()));
+        if (c1->nnz && c2->nnz) {
+            u32 grid = cdiv(c1->nnz, 4);
             if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-            FGPU_TRY(launch(row_weight_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), view_of(eff[0]),
-                            weighted ? (const u64*)eff[0]->vals : (const u64*)nullptr, (const u32*)dsrc.p, (u32)nsrc, w1.p));
+            FGPU_TRY(launch(trail2_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1.get()), (const u64*)w1.p,
+                            view_of(eff[1]), weighted ? (const u64*)eff[1]->vals : (const u64*)nullptr, view_of(c2.get()),
+                            (const u32*)dsrc.p, (u32)c1->nnz, (unsigned long long*)cnt.p));
         }
-        const fgpu_mat* res = c1;
-        const u64* res_cnt = w1.p;
-        if (nhops == 2) {
-            FGPU_TRY(mxm_device(ctx, &c2, c1, eff[1], nullptr));
-            FGPU_TRY(cnt.alloc(ctx, c2->nnz));
-            FGPU_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(c2->nnz ? c2->nnz : 1) * sizeof(u64), ctx->stream()));
-            if (c1->nnz && c2->nnz) {
-                u32 grid = cdiv(c1->nnz, 4);
-                if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
-                FGPU_TRY(launch(trail2_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(c1), (const u64*)w1.p,
-                                view_of(eff[1]), weighted ? (const u64*)eff[1]->vals : (const u64*)nullptr, view_of(c2),
-                                (const u32*)dsrc.p, (u32)c1->nnz, (unsigned long long*)cnt.p));
-            }
-            res = c2;
-            res_cnt = cnt.p;
-        }
-        // host hand-over: rowptr / dest as fgpu_expand does, counts beside them.  Pairs reached only through the
-        // self-loop walk keep a zero count: they are walks, not trails, and are dropped here.
-        std::vector<u32> rp((size_t)nsrc + 1), ci(res->nnz);
-        std::vector<u64> cv(res->nnz);
-        FGPU_TRY(ctx->d2h(rp.data(), res->rowptr, rp.size() * sizeof(u32)));
-        if (res->nnz) {
-            FGPU_TRY(ctx->d2h(ci.data(), res->colidx, res->nnz * sizeof(u32)));
-            FGPU_TRY(ctx->d2h(cv.data(), res_cnt, res->nnz * sizeof(u64)));
-        }
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        u64 keep = 0;
-        for (u64 k = 0; k < res->nnz; ++k) keep += cv[k] != 0;
-        u64* orp = (u64*)ctx->host_alloc((nsrc + 1) * sizeof(u64));
-        u64* od = (u64*)ctx->host_alloc((keep ? keep : 1) * sizeof(u64));
-        u64* oc = (u64*)ctx->host_alloc((keep ? keep : 1) * sizeof(u64));
-        if (!orp || !od || !oc) {
-            ctx->host_free(orp); ctx->host_free(od); ctx->host_free(oc);
-            set_error("fgpu_expand_trail_counts: host allocation failed");
-            return FGPU_OOM;
-        }
-        u64 o = 0;
-        for (u64 r = 0; r < nsrc; ++r) {
-            orp[r] = o;
-            for (u32 k = rp[r]; k < rp[r + 1]; ++k)
-                if (cv[k]) { od[o] = ci[k]; oc[o] = cv[k]; ++o; }
-        }
-        orp[nsrc] = o;
-        *out_rowptr = orp; *out_dest = od; *out_count = oc; *out_nnz = o;
-        return FGPU_OK;
-    };
-    i = run();
-    if (f0) mat_release(f0);
-    if (c1) mat_release(c1);
-    if (c2) mat_release(c2);
-    cleanup();
-    return i;
+        res = c2.get();
+        res_cnt = cnt.p;
+    }
+    // host hand-over: rowptr / dest as fgpu_expand does, counts beside them.  Pairs reached only through the
+    // self-loop walk keep a zero count: they are walks, not trails, and are dropped here.
+    std::vector<u32> rp((size_t)nsrc + 1), ci(res->nnz);
+    std::vector<u64> cv(res->nnz);
+    FGPU_TRY(ctx->d2h(rp.data(), res->rowptr, rp.size() * sizeof(u32)));
+    if (res->nnz) {
+        FGPU_TRY(ctx->d2h(ci.data(), res->colidx, res->nnz * sizeof(u32)));
+        FGPU_TRY(ctx->d2h(cv.data(), res_cnt, res->nnz * sizeof(u64)));
+    }
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+    u64 keep = 0;
+    for (u64 k = 0; k < res->nnz; ++k) keep += cv[k] != 0;
+    ResultBuf brp, bd, bc;   // (the caller's allocator, not pinned result blocks)
+    FGPU_REQUIRE(brp.alloc_host(ctx, (nsrc + 1) * sizeof(u64)) && bd.alloc_host(ctx, (keep ? keep : 1) * sizeof(u64)) &&
+                     bc.alloc_host(ctx, (keep ? keep : 1) * sizeof(u64)),
+                 FGPU_OOM, "fgpu_expand_trail_counts: host allocation failed");
+    u64 *orp = (u64*)brp.release(), *od = (u64*)bd.release(), *oc = (u64*)bc.release();   // nothing below can fail
+    u64 o = 0;
+    for (u64 r = 0; r < nsrc; ++r) {
+        orp[r] = o;
+        for (u32 k = rp[r]; k < rp[r + 1]; ++k)
+            if (cv[k]) { od[o] = ci[k]; oc[o] = cv[k]; ++o; }
+    }
+    orp[nsrc] = o;
+    *out_rowptr = orp; *out_dest = od; *out_count = oc; *out_nnz = o;
+    return FGPU_OK;
 }
 
 // Public producers of snapshots: the implementation above, then fgpu_ctx::publish().

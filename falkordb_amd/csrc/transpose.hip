@@ -871,13 +871,11 @@ fgpu_info mat_transpose_counting(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* 
     if (a->is_hyper() || a->nnz < 4096 || a->nrows == 0) return FGPU_NO_VALUE;
     bool staged = false;
     if (!ks_applicable(ctx, a->nnz, a->ncols, &staged)) return FGPU_NO_VALUE;
-    fgpu_mat* t = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &t, a->ncols, a->nrows, a->nnz, false, 0, false));
-    fgpu_info i = sort_pairs(ctx, a->colidx, nullptr, a->rowptr, (u32)a->nrows, a->nnz, a->ncols, t->colidx,
-                             t->rowptr, nullptr);
+    MatRef t;
+    FGPU_TRY(mat_alloc(ctx, &t.m, a->ncols, a->nrows, a->nnz, false, 0, false));
+    FGPU_TRY(sort_pairs(ctx, a->colidx, nullptr, a->rowptr, (u32)a->nrows, a->nnz, a->ncols, t->colidx, t->rowptr, nullptr));
     // hub lists / max degree are built when a BFS plan, vxm or PageRank first asks (mat_ensure_finalized)
-    if (i != FGPU_OK) { mat_release(t); return i; }
-    *out = t;
+    *out = t.release();
     return FGPU_OK;
 }
 
@@ -913,15 +911,13 @@ fgpu_info mat_from_device_coo_counting(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows,
     FGPU_TRY(scan_u32(ctx, keep.p, newpos.p, nv, tot.p));
     u32 nnz = 0;
     FGPU_TRY(read_u32(ctx, tot.p, &nnz));
-    fgpu_mat* m = nullptr;
-    FGPU_TRY(mat_alloc(ctx, &m, nrows, ncols, nnz, false, 0, false));
-    fgpu_info i = launch(dedup_rowptr_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
-                         (u32)nrows, nv, (const u32*)newpos.p, nnz, m->rowptr);
-    if (i == FGPU_OK)
-        i = launch(dedup_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)byr_col.p, (const u32*)keep.p,
-                   (const u32*)newpos.p, nv, m->colidx);
-    if (i != FGPU_OK) { mat_release(m); return i; }
-    *out = m;
+    MatRef m;
+    FGPU_TRY(mat_alloc(ctx, &m.m, nrows, ncols, nnz, false, 0, false));
+    FGPU_TRY(launch(dedup_rowptr_kernel, dim3(cdiv(nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)rowptr.p,
+                    (u32)nrows, nv, (const u32*)newpos.p, nnz, m->rowptr));
+    FGPU_TRY(launch(dedup_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)byr_col.p, (const u32*)keep.p,
+                    (const u32*)newpos.p, nv, m->colidx));
+    *out = m.release();
     return FGPU_OK;
 }
 
