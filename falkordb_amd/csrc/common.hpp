@@ -159,6 +159,7 @@ struct fgpu_ctx {
     std::atomic<uint64_t> xp_last_groups{0};    // 64-row groups the fold of the last partitioned count hop looped over ("expand_xp_last_groups")
     std::atomic<uint64_t> hc_last_entries{0}, hc_last_gathered{0};   // the last fgpu_harmonic call: entries of the recomputed rows, sketches gathered ("harmonic_last_*")
     std::atomic<uint64_t> msf_round_entries[32] = {};   // the last fgpu_msf call: entries read in round k, the rounds past 31 in [31] ("msf_last_entries_round<k>")
+    std::atomic<int64_t> sssp_last_delta{0};   // the last fgpu_sssp call: log2 of its bucket width, 1024 = one bucket ("sssp_last_delta_log2")
     std::atomic<uint64_t> expand_launches{0};   // kernels launched by fgpu_expand* (fgpu_get_option "expand_kernel_launches")
     // kernel profiler (measurement hook): off unless fgpu_prof_enable(ctx, 1)
     bool prof_on = false;

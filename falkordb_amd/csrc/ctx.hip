@@ -815,6 +815,8 @@ static const CounterRow COUNTERS[] = {
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     FGPU_REQUIRE(ctx && name && value, FGPU_NULL_POINTER, "fgpu_get_option: NULL argument");
     if (const OptRow* r = opt_find(name)) { *value = opt_load(ctx->opt, *r); return FGPU_OK; }
+    if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }
+    if (!strcmp(name, "sssp_last_delta_log2")) { *value = ctx->sssp_last_delta.load(std::memory_order_relaxed); return FGPU_OK; }
     for (const CounterRow& c : COUNTERS)
         if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
     if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32) {
@@ -830,6 +832,13 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     ctx->opt_epoch.fetch_add(1, std::memory_order_relaxed);
     if (!strcmp(name, "transpose_wb")) {   // process-wide, no field and no range: not a row of the table
         ks_set_wb_override((int)value);
+        return FGPU_OK;
+    }
+    if (!strcmp(name, "sssp_delta_log2")) {   // an exponent or "auto": not a row of the table (options.hpp)
+        FGPU_REQUIRE(value == SSSP_DELTA_AUTO || (value >= SSSP_DELTA_MIN && value <= SSSP_DELTA_MAX), FGPU_INVALID,
+                     "fgpu_set_option: sssp_delta_log2 must be %d .. %d or %d (auto), not %lld", SSSP_DELTA_MIN, SSSP_DELTA_MAX,
+                     SSSP_DELTA_AUTO, (long long)value);
+        ctx->opt.sssp_delta_log2 = (int)value;
         return FGPU_OK;
     }
     const OptRow* r = opt_find(name);

@@ -80,7 +80,11 @@ struct fgpu_options {  // fgpu_set_option
     int bc_batch = 0;          // fgpu_betweenness: sources per batch, 0 auto (16 / 32 / 64 by nsrc, halved to fit free memory), 1-64 forced
     int maxflow_global_every = 0;   // fgpu_maxflow: pulses between two global relabels (0 = MF_GLOBAL_EVERY of maxflow.hip; A/B)
     int bc_direction = 0;      // fgpu_betweenness forward levels: 0 auto (push / pull by entries to read), 1 push over A, 2 pull over At
+    int sssp_delta_log2 = 4096; // fgpu_sssp: the bucket width is 2^value, SSSP_DELTA_AUTO = derived on the device from the mean finite
+                               // weight and the mean degree (sssp.hip).  Set and read by name in ctx.hip, not a row of the table below:
+                               // the table is pinned row for row by tests/test_options_cpu.py
 };
+constexpr int SSSP_DELTA_AUTO = 4096, SSSP_DELTA_MIN = -1074, SSSP_DELTA_MAX = 1023;
 
 namespace fgpu {
 

@@ -616,6 +616,27 @@ def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
     return val.value, rows, cols, flows, ([int(x) for x in st] if stats else None)
 
 
+def sssp(ctx: Context, W: Mat, src: int, want_parent: bool = True, stats: bool = False, out=None):
+    """fgpu_sssp: single-source shortest paths for algo.SPpaths over the weight matrix W — a valued snapshot carries one binary64
+    bit pattern per entry (non-negative; a NaN or negative one is an error), a BOOL one means every weight is 1.0.  out: a
+    (dist float64[n], parent int64[n] | None) pair to fill instead of fresh arrays (Context.host_array() blocks are filled by
+    DMA).  Returns (dist, parent) — dist +inf and parent -1 where no route reaches, parent[src] = src, parent None when
+    want_parent=False — and, when stats=True, a third item: the four counters [relaxation launches, vertices taken off a
+    worklist, entries read, deepest tight-entry depth]."""
+    n = W.nrows
+    if out is not None:
+        dist, parent = out
+    else:
+        dist, parent = np.zeros(n, dtype=np.float64), (np.zeros(n, dtype=np.int64) if want_parent else None)
+    if not want_parent:
+        parent = None
+    st = np.zeros(4, dtype=np.uint64) if stats else None
+    check(ctx.lib.fgpu_sssp(ctx._h, W._h, C.c_uint64(src), _p(dist, C.POINTER(C.c_double)), _p(parent, i64p), _p(st)))
+    if stats:
+        return dist, parent, [int(x) for x in st]
+    return dist, parent
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

@@ -594,6 +594,33 @@ class Graph:
                                    C.byref(nn), C.byref(edges), C.byref(flows), C.byref(ne), C.byref(val)))
         return _take(nodes, nn.value), _take(edges, ne.value), _take(flows, ne.value, np.float64), val.value
 
+    def algo_sp_paths(self, source, target, types=(), direction="outgoing", weights=None, costs=None):
+        """CALL algo.SPpaths({sourceNode, targetNode, relTypes, relDirection, weightProp, costProp, pathCount: 1}) YIELD path,
+        pathWeight, pathCost -> None when there is no path, else (nodes uint64[], edges uint64[], weight, cost).  Only the
+        single-cheapest-path shape is served (no maxLen, no maxCost; see fh_algo_sp_paths).  weights / costs: None = no
+        weightProp / costProp, else a {relationship id: number} dict — a relationship missing from it weighs 1.0 / costs 0.0.
+        A negative weight is an error."""
+        def attr(d):
+            if d is None:
+                return None, None, 0
+            ids = np.ascontiguousarray(list(d.keys()), dtype=np.uint64)
+            vals = np.ascontiguousarray([float(x) for x in d.values()], dtype=np.float64)
+            return ids.ctypes.data_as(u64p), vals.ctypes.data_as(C.POINTER(C.c_double)), len(ids), (ids, vals)
+        w, c = attr(weights), attr(costs)
+        found = C.c_int()
+        nodes, edges = u64p(), u64p()
+        nn = C.c_uint64()
+        weight, cost = C.c_double(), C.c_double()
+        _ck(self.L.fh_algo_sp_paths(self.h, C.c_uint64(source), C.c_uint64(target), ",".join(types).encode(),
+                                    C.c_int({"outgoing": 0, "incoming": 1, "both": 2}[direction]), w[0], w[1], C.c_uint64(w[2]),
+                                    c[0], c[1], C.c_uint64(c[2]), C.byref(found), C.byref(nodes), C.byref(nn), C.byref(edges),
+                                    C.byref(weight), C.byref(cost)))
+        nv = _take(nodes, nn.value)
+        ev = _take(edges, max(nn.value, 1) - 1)
+        if not found.value:
+            return None
+        return nv, ev, weight.value, cost.value
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

@@ -795,6 +795,26 @@ int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const ui
     });
 }
 
+// algo.SPpaths, the single cheapest path: types = a comma list, "" = all; direction 0 outgoing, 1 incoming, 2 both
+int fh_algo_sp_paths(fh_graph* g, uint64_t source, uint64_t target, const char* types, int direction, const uint64_t* w_edge_ids,
+                     const double* w_vals, uint64_t n_w, const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int* found,
+                     uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, double* weight, double* cost) {
+    return guard([&] {
+        if (direction < 0 || direction > 2) throw std::invalid_argument("fh_algo_sp_paths: direction must be 0, 1 or 2");
+        SpPathResult r = timed([&] {
+            return algo_sp_paths(g->g, source, target, csv(types), (Direction)direction, w_edge_ids, w_vals, n_w, c_edge_ids, c_vals,
+                                 n_c);
+        });
+        *found = r.found ? 1 : 0;
+        *nodes = hand(r.nodes);
+        *n_nodes = r.nodes.size();
+        *edges = hand(r.edges);
+        *weight = r.weight;
+        *cost = r.cost;
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

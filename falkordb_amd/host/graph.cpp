@@ -1204,6 +1204,92 @@ MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& label
     return res;
 }
 
+// ---- algo.SPpaths (the single cheapest path) ------------------------------------------------------------
+SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
+                           const u64* w_edge_ids, const double* w_vals, u64 n_w,
+                           const u64* c_edge_ids, const double* c_vals, u64 n_c) {
+    SpPathResult res;
+    const u64 n = g.node_cap();
+    if (source == target) return res;                                    // :2559-2567
+    if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return res;
+    std::vector<u64> tids;                                               // the known ones, each once (graph.rs:1803-1810)
+    if (types.empty())
+        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+    else
+        for (auto& t : types)
+            if (auto id = g.type_id(t))
+                if (std::find(tids.begin(), tids.end(), *id) == tids.end()) tids.push_back(*id);
+    const bool unit = w_edge_ids == nullptr;
+    std::unordered_map<u64, double> wattr, cattr;                        // edge_numeric_attr (:2049-2062)
+    if (!unit) {
+        wattr.reserve(n_w * 2);
+        for (u64 k = 0; k < n_w; ++k) wattr[w_edge_ids[k]] = w_vals[k];
+    }
+    if (c_edge_ids) {
+        cattr.reserve(n_c * 2);
+        for (u64 k = 0; k < n_c; ++k) cattr[c_edge_ids[k]] = c_vals[k];
+    }
+    // one (weight, relationship) per ordered pair in traversal direction
+    struct Kept { double w; u64 edge; };
+    std::unordered_map<u64, Kept> best;
+    auto offer = [&](u64 from, u64 to, const Kept& y) {
+        auto [it, fresh] = best.try_emplace((from << 32) | to, y);
+        if (fresh) return;
+        Kept& x = it->second;
+        if (y.w < x.w || (y.w == x.w && y.edge < x.edge)) x = y;
+    };
+    for (u64 t : tids) {
+        for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
+            if (e.row == e.col) continue;
+            double w = 1.0;
+            if (!unit) {
+                const auto it = wattr.find(e.val);
+                if (it != wattr.end()) w = it->second;
+            }
+            if (!std::isfinite(w)) continue;                             // never relaxed (:2213)
+            if (w < 0.0)
+                throw std::invalid_argument("algo.SPpaths: relationship " + std::to_string(e.val) + " has a negative weight");
+            if (w == 0.0) w = 0.0;                                       // (-0.0)
+            const Kept y{w, e.val};
+            if (dir != Direction::Incoming) offer(e.row, e.col, y);
+            if (dir != Direction::Outgoing) offer(e.col, e.row, y);
+        }
+    }
+    std::vector<u64> rows, cols, bits;
+    rows.reserve(best.size()); cols.reserve(best.size());
+    if (!unit) bits.reserve(best.size());
+    for (auto& kv : best) {
+        rows.push_back(kv.first >> 32); cols.push_back(kv.first & 0xFFFFFFFFull);
+        if (!unit) {
+            u64 b;
+            memcpy(&b, &kv.second.w, sizeof b);
+            bits.push_back(b);
+        }
+    }
+    Matrix w(g.ctx(), unit ? Type::Bool : Type::UInt64, n, n);
+    if (!rows.empty()) w.build(rows, cols, unit ? nullptr : &bits);
+    std::vector<double> dist(n);
+    std::vector<int64_t> parent(n);
+    sssp(g.ctx(), w.snapshot(), source, dist.data(), parent.data());
+    if (!std::isfinite(dist[target])) return res;
+    res.found = true;
+    res.weight = dist[target];
+    for (u64 v = target, steps = 0; v != source; v = (u64)parent[v]) {
+        if (++steps > n || parent[v] < 0 || (u64)parent[v] >= n)
+            throw std::runtime_error("algo.SPpaths: the parent chain does not lead back to the source");
+        res.nodes.push_back(v);
+    }
+    res.nodes.push_back(source);
+    std::reverse(res.nodes.begin(), res.nodes.end());
+    for (size_t k = 0; k + 1 < res.nodes.size(); ++k) {                  // :2250-2254
+        const u64 edge = best.at((res.nodes[k] << 32) | res.nodes[k + 1]).edge;
+        res.edges.push_back(edge);
+        const auto it = cattr.find(edge);
+        res.cost += it != cattr.end() ? it->second : 0.0;
+    }
+    return res;
+}
+
 // ---- algo.betweenness -----------------------------------------------------------------------------------
 std::vector<u64> betweenness_sources(u64 n_nodes, int64_t sampling_size, int64_t sampling_seed) {
     if (sampling_size <= 0) throw std::invalid_argument("samplingSize must be a positive integer");   // :900-905

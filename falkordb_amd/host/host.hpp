@@ -661,6 +661,10 @@ inline void msf(const Context& ctx, const fgpu_mat* w, const u64* active_bitmap,
 inline void maxflow(const Context& ctx, const fgpu_mat* cap, u64 src, u64 sink, double* value, EdgeList& flow) {
     check(fgpu_maxflow(ctx.raw(), cap, src, sink, value, &flow.rows, &flow.cols, &flow.vals, &flow.n, nullptr), "LAGr_MaxFlow");
 }
+// fgpu_sssp into host arrays of nrows entries (the reference calls no library here: the name is the procedure's)
+inline void sssp(const Context& ctx, const fgpu_mat* w, u64 src, double* dist, int64_t* parent) {
+    check(fgpu_sssp(ctx.raw(), w, src, dist, parent, nullptr), "algo.SPpaths");
+}
 
 struct MsfResult {
     std::vector<std::vector<u64>> tree_nodes;   // per tree, ascending node ids
@@ -694,5 +698,31 @@ struct MaxFlowResult {
 MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types,
                            const std::vector<u64>& sources, const std::vector<u64>& targets, bool has_attribute,
                            const u64* edge_ids, const double* caps, u64 n_caps, bool has_default, double default_capacity);
+
+enum class Direction { Outgoing, Incoming, Both };   // relDirection: 'outgoing' | 'incoming' | 'both'
+struct SpPathResult {
+    bool found = false;
+    std::vector<u64> nodes, edges;   // the path source .. target and the relationship of every step
+    double weight = 0, cost = 0;
+};
+// algo.SPpaths (runtime/functions/algo_procedures.rs:2548-2597), its fast branch ONLY: one cheapest path, no maxLen, no
+// maxCost, source != target — what run_path_algo hands to dijkstra_single_path (:2563-2571, :2156-2257).  Every other shape
+// (pathCount 0 or > 1, maxLen, maxCost) and all of algo.SSpaths enumerate simple paths in an exponential host DFS with no matrix
+// work in it; they are not served here.
+// types empty = every tensor; unknown names are dropped and a name listed twice counts once (get_node_relationships_by_type's
+// filter_map).  source == target gives found = false, with or without a self-loop (:2559-2567); so does a source or target that
+// is deleted or out of range.  The host mirror has no attribute store: weightProp arrives as (w_edge_ids[k], w_vals[k]),
+// k < n_w, w_edge_ids == nullptr = not given; a relationship that is not listed weighs 1.0 (edge_numeric_attr, :2049-2062);
+// costProp likewise with 0.0.  A relationship whose weight is NaN or +-inf can never be relaxed in the reference and is left
+// out.  The reference documents negative weights as unsupported with undefined results; here one throws std::invalid_argument
+// naming the relationship.  The search runs over one matrix entry per ordered pair (from, to) in traversal direction — src ->
+// dst (Outgoing), dst -> src (Incoming), both (Both), self-loops dropped — that carries the smallest weight over the selected
+// types and their multi-edges, ties to the smallest relationship id (the engine's rule, as algo_msf's; the reference keeps
+// whichever its iteration meets first): a BOOL matrix without weightProp, binary64 bit patterns otherwise.  The path is
+// fgpu_sssp's parent chain from target back to source; edges[k] is the kept relationship of pair k, weight = dist[target], cost
+// the costs of those relationships folded source -> target in that order (:2250-2254).
+SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
+                           const u64* w_edge_ids, const double* w_vals, u64 n_w,
+                           const u64* c_edge_ids, const double* c_vals, u64 n_c);
 
 }  // namespace falkor

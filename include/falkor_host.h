@@ -271,6 +271,24 @@ int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const ui
                     uint64_t n_caps, int has_default, double default_capacity, uint64_t** nodes, uint64_t* n_nodes,
                     uint64_t** edges, double** flows, uint64_t* n_edges, double* max_flow);
 
+/* algo.SPpaths (algo_procedures.rs:2548-2597), the branch that answers ONE cheapest path: pathCount 1, no maxLen, no maxCost,
+ * source != target — run_path_algo's call of dijkstra_single_path (:2563-2571), computed by fgpu_sssp, whose comment in fgpu.h
+ * states which distance and which parent come back.  The other shapes of algo.SPpaths and all of algo.SSpaths enumerate simple
+ * paths on the host and are not served.  types = a comma list, "" / NULL = every type; unknown names are dropped, a name listed
+ * twice counts once.  direction: 0 outgoing, 1 incoming, 2 both (relDirection).  The host mirror has no attribute store, so
+ * weightProp and costProp are data: w_vals[k] is the weight of relationship w_edge_ids[k], k < n_w; w_edge_ids == NULL means no
+ * weightProp; a relationship that is not listed weighs 1.0.  c_edge_ids / c_vals / n_c likewise for the cost, default 0.0.  A
+ * relationship whose weight is NaN or infinite is left out; a negative weight fails with a message that names the relationship
+ * ("negative weight"; the reference leaves the result undefined).  Self-loops are dropped.  Among the relationships that join
+ * an ordered pair of nodes in traversal direction the cheapest is used, ties to the smallest id.
+ * *found = 0 (and empty lists) when source == target, when either node is deleted or out of range, and when no path exists.
+ * Otherwise nodes[0 .. n_nodes) is the path from source to target, edges[0 .. n_nodes - 1) the relationship of every step,
+ * *weight the sum of their weights added source -> target in FP64, *cost their costs folded in the same order.  Free the two
+ * lists with fh_free. */
+int fh_algo_sp_paths(fh_graph* g, uint64_t source, uint64_t target, const char* types, int direction, const uint64_t* w_edge_ids,
+                     const double* w_vals, uint64_t n_w, const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int* found,
+                     uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, double* weight, double* cost);
+
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).
  * sampling_size / sampling_seed as the procedure's samplingSize / samplingSeed (defaults 16 / 0; fh_betweenness_sources).

@@ -572,6 +572,37 @@ fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src, uint64_t 
                        uint64_t** flow_rows, uint64_t** flow_cols, double** flow_vals, uint64_t* n_flow,
                        uint64_t stats[4]);
 
+/* Single-source shortest paths over non-negative FP64 weights (near / far delta-stepping): the numeric core of algo.SPpaths'
+ * single-path branch (run_path_algo -> dijkstra_single_path, algo_procedures.rs:2548-2597 and 2156-2257).  The reference
+ * issues no LAGraph call here and its tie-breaks are accidents of its heap order; these are the rules:
+ *   - W is square; W(u, v) is the weight of the arc u -> v.  A valued snapshot holds one IEEE-754 binary64 BIT PATTERN per
+ *     entry in its uint64 value; a BOOL snapshot means every weight is 1.0.  A hypersparse W is accepted;
+ *   - a diagonal entry is ignored; there is no active bitmap: the caller compacts the node ids;
+ *   - -0.0 is 0.0.  A NaN, or a weight with the sign bit set other than -0.0, anywhere in W is FGPU_INVALID (one reduction
+ *     pass before the search);
+ *   - a relaxation whose sum dist[u] + w is not finite is skipped (the reference's !far_weight.is_finite()): a +inf entry is
+ *     never used, and neither is a route whose length overflows.
+ * dist[nrows] (a HOST array; a pinned one — fgpu_host_alloc — is filled by DMA, as fgpu_bfs' level[]): dist[src] = +0.0,
+ * +inf for the vertices no route reaches, otherwise the minimum over all src -> v routes of the route's weights added left
+ * to right from the source in FP64.  fl(a + w) is monotone in a for w >= 0, so this value is unique: it is what a heap
+ * Dijkstra computes, bit for bit, and identical from run to run and under every bucket width.
+ * parent[nrows] (nullable HOST array; -1 = unreached, parent[src] = src) is a pure function of dist and W.  An entry (u, v),
+ * u != v, is TIGHT when dist[u] + W(u, v) is finite and equals dist[v].  depth[v] is the BFS depth of v from src over the tight
+ * entries alone; parent[v] is the smallest u with (u, v) tight and depth[u] + 1 == depth[v].  The tight entries span every
+ * reached vertex (a Dijkstra tree consists of them), so the parent chains form a tree rooted at src, whatever zero-weight
+ * cycles or absorbed weights (1.0 + 1e-20 == 1.0) W holds.  The parent search is skipped when parent and stats are both NULL.
+ * stats (nullable): [0] relaxation launches that had work, [1] vertices taken off a worklist, re-insertions counted (divided
+ * by the reached vertices: the work efficiency), [2] entries read (both phases), [3] the deepest depth.
+ * The bucket width is a power of two derived on the device from the mean finite weight and the mean degree (1.0 for a BOOL
+ * W); fgpu_set_option "sssp_delta_log2" = -1074 .. 1023 forces 2^value, 4096 (the default) restores the derived width;
+ * fgpu_get_option reads it back, and "sssp_last_delta_log2" is the width the last call used (1024: one bucket for all).
+ * Errors: NULL ctx / W / dist: FGPU_NULL_POINTER; non-square W: FGPU_DIM_MISMATCH; src >= nrows: FGPU_OUT_OF_BOUNDS;
+ * nrows >= 2^32 - 1: FGPU_INVALID.  nrows == 0 is a no-op.  The step loop (a relaxation of the near pile, or a move to the
+ * next non-empty bucket) has a hard cap of 4 (n^2 + n) + 64 steps — every vertex enters a bucket once and a bucket is a
+ * fixed point within n relaxations, so a correct run stays below n^2 + 2 n — past which the call returns FGPU_INVALID with a
+ * message instead of running on. */
+fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, double* dist, int64_t* parent, uint64_t stats[4]);
+
 /* The smallest stored value of A under the order of fgpu_msf's K (the IEEE totalOrder with -0.0 = +0.0), as a binary64 bit
  * pattern (LAGraph_Cached_EMin).  *found = 0 when A has no entry; a BOOL snapshot answers 1.0.  A device reduction: no entry
  * visits the host. */

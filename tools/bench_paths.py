@@ -34,7 +34,12 @@
           the kernels actually loaded x 1 KiB (entries whose column did not change are not loaded), against the 5.5 TB/s
           measured for register gathers of random 1152-byte rows
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|all] [scale]
+  sssp    algo.SPpaths' core (fgpu_sssp, near / far delta-stepping) on RMAT-22 (or RMAT-<scale>) with hashed weights, integers
+          1..100 and uniform doubles in [0, 1), from the vertex with the most out-entries: median of 3 synchronised calls, the
+          stats, the reached vertices, the bucket width, and one fgpu_bfs and one full-pass vxm over the same pattern;
+          sssp_sweep = the same under nine bucket widths around the derived one
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|all] [scale]
 """
 import json
 import sys
@@ -415,6 +420,58 @@ def bench_maxflow(ctx, scale, sweep=False):
     ctx.set_option("maxflow_global_every", 0)
 
 
+def bench_sssp(ctx, scale, sweep=False):
+    """fgpu_sssp on the directed R-MAT graph with weights that are a fixed hash of (row, col), once as integers 1..100 and once
+    as uniform doubles in [0, 1); src = the vertex with the most out-entries.  For scale, from the same run: one full-pass
+    boolean vxm (every frontier bit set) and one fgpu_bfs from src over the same pattern.  sweep: sssp_delta_log2 over nine
+    exponents around the derived one instead of the derived width alone."""
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.repeat(np.arange(n, dtype=np.uint64), deg)
+    h = (rows * np.uint64(n) + ci) * np.uint64(0x9E3779B97F4A7C15)   # (mod 2^64)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(32)
+    weights = {"int_1_100": ((h >> np.uint64(11)) % np.uint64(100) + np.uint64(1)).astype(np.float64),
+               "uniform_0_1": (h >> np.uint64(11)).astype(np.float64) / float(1 << 53)}
+    src = int(np.argmax(deg))
+    del rows, h
+    At = A.transpose()
+    nnz = A.nvals
+    full = np.full((n + 63) // 64, ~np.uint64(0), dtype=np.uint64)
+    if n % 64:
+        full[-1] = np.uint64((1 << (n % 64)) - 1)
+    t_vxm, _ = timed(ctx, lambda: engine.vxm(ctx, full, None, A, At), reps=5, warm=1)
+    level = ctx.host_array(n, np.int32)
+    t_bfs, _ = timed(ctx, lambda: engine.bfs(ctx, A, At, src, -1, want_parent=False, level_out=level), reps=5, warm=1)
+    out = (ctx.host_array(n, np.float64), ctx.host_array(n, np.int64))
+    for name, w in weights.items():
+        W = ctx.mat_from_csr(n, n, rp, ci, w.view(np.uint64))
+        ctx.set_option("sssp_delta_log2", 4096)
+        engine.sssp(ctx, W, src, want_parent=False, out=out)
+        auto = ctx.get_option("sssp_last_delta_log2")
+        for k in ([auto + d for d in (-4, -3, -2, -1, 0, 1, 2, 3, 4)] if sweep else [4096]):
+            ctx.set_option("sssp_delta_log2", k)
+            t_dist, _ = timed(ctx, lambda: engine.sssp(ctx, W, src, want_parent=False, out=out), reps=3, warm=1)
+            t, (dist, _, st) = timed(ctx, lambda: engine.sssp(ctx, W, src, stats=True, out=out), reps=3, warm=1)
+            reached = int(np.isfinite(dist).sum())
+            print(json.dumps({"path": "sssp", "scale": scale, "weights": name, "n": n, "nnz": nnz, "src": src,
+                              "out_degree_src": int(deg[src]), "sssp_delta_log2": ctx.get_option("sssp_last_delta_log2"),
+                              "derived": k == 4096 or k == auto, "ms": round(t * 1e3, 3), "ms_dist_only": round(t_dist * 1e3, 3),
+                              "launches": st[0], "popped": st[1], "entries_read": st[2], "deepest": st[3], "reached": reached,
+                              "popped_per_reached": round(st[1] / max(reached, 1), 3),
+                              "Medges_per_s": round(nnz / t_dist / 1e6, 1), "full_vxm_ms": round(t_vxm * 1e3, 3),
+                              "bfs_ms": round(t_bfs * 1e3, 3), "x_bfs": round(t_dist / t_bfs, 2),
+                              "note": "host clock around a synchronised call, median of 3 after 1 warm-up; ms = distances + "
+                                      "parents, dist_only = parent NULL and stats NULL (no parent search); vxm = fgpu_vxm with "
+                                      "every frontier bit set, bfs = fgpu_bfs from src, levels only, both median of 5; x_bfs = "
+                                      "dist_only over bfs; no outside number exists to compare with"}), flush=True)
+        W.free()
+    ctx.set_option("sssp_delta_log2", 4096)
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -497,6 +554,10 @@ if __name__ == "__main__":
     if what in ("maxflow", "maxflow_sweep", "all"):
         c = engine.Context(0)
         bench_maxflow(c, scale if scale else 22, sweep=what == "maxflow_sweep")
+        c.close()
+    if what in ("sssp", "sssp_sweep", "all"):
+        c = engine.Context(0)
+        bench_sssp(c, scale if scale else 22, sweep=what == "sssp_sweep")
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
