@@ -336,19 +336,6 @@ static u64 bc_workspace_bytes(u64 n, u32 B, u32 n_hub) {
     return n * 3 * sizeof(u64) + n * (u64)B * (2 * sizeof(double) + sizeof(u32)) + (u64)n_hub * B * sizeof(double);
 }
 
-// A's cached pattern transpose (fgpu_mat::tcache, shared with bitexpand.hip), built once per snapshot
-static fgpu_info bc_cached_transpose(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out) {
-    std::lock_guard<std::mutex> idx_guard(m->idx_mu);
-    if (!m->tcache) {
-        fgpu_mat* t = nullptr;
-        FGPU_TRY(mat_transpose_pattern(ctx, &t, m));
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        m->tcache = t;
-    }
-    *out = m->tcache;
-    return FGPU_OK;
-}
-
 }  // namespace fgpu
 
 using namespace fgpu;
@@ -370,7 +357,7 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
     DenseInputs in;
     FGPU_TRY(in.a(ctx, A));
     if (dir == 1) At = nullptr;   // push only: the transpose is never read
-    else if (!At) FGPU_TRY(bc_cached_transpose(ctx, A, &At));   // a missing transpose: A's cached one
+    else if (!At) FGPU_TRY(mat_cached_transpose(ctx, A, &At));   // a missing transpose: A's cached one
     FGPU_TRY(in.at(ctx, At));
     FGPU_TRY(mat_ensure_finalized(A));   // the hub lists
     if (At) FGPU_TRY(mat_ensure_finalized(At));
@@ -446,14 +433,14 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
                     FGPU_TRY(launch(bc_pull_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, vat, a, n));
                     if (hgAt) {
                         FGPU_TRY(launch(bc_pull_hub_kernel, dim3(hgAt), dim3(256), 0, ctx->stream(), s,
-                                        (const u32*)At->hub_chunks, At->n_hub_chunks, (const u32*)At->colidx, a));
+                                        (const u32*)At->hub_chunks.p, At->n_hub_chunks, (const u32*)At->colidx, a));
                     }
                     st[2] += mu;
                 } else {
                     FGPU_TRY(launch(bc_push_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, a, n));
                     if (hgA) {
                         FGPU_TRY(launch(bc_push_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s,
-                                        (const u32*)A->hub_chunks, A->n_hub_chunks, (const u32*)A->colidx, a));
+                                        (const u32*)A->hub_chunks.p, A->n_hub_chunks, (const u32*)A->colidx, a));
                     }
                     st[2] += mf;
                 }
@@ -467,10 +454,10 @@ extern "C" fgpu_info fgpu_betweenness(fgpu_ctx* ctx, const fgpu_mat* A, const fg
             for (u32 d = deepest - 1; d >= 1; --d) {
                 FGPU_TRY(launch(bc_back_kernel, dim3(ggrid), dim3(256), 0, ctx->stream(), s, va, n, d, cnt.p + 3));
                 if (hgA) {
-                    FGPU_TRY(launch(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks,
+                    FGPU_TRY(launch(bc_back_hub_kernel, dim3(hgA), dim3(256), 0, ctx->stream(), s, (const u32*)A->hub_chunks.p,
                                     A->n_hub_chunks, (const u32*)A->colidx, d, part.p, cnt.p + 3));
                     FGPU_TRY(launch(bc_back_hub_finish_kernel, dim3(capped_grid(ctx, (u64)A->n_hub_chunks * G, 256, 16)), dim3(256), 0,
-                                    ctx->stream(), s, (const u32*)A->hub_chunks, A->n_hub_chunks, d, (const double*)part.p));
+                                    ctx->stream(), s, (const u32*)A->hub_chunks.p, A->n_hub_chunks, d, (const double*)part.p));
                 }
             }
             FGPU_TRY(launch(bc_reduce_kernel, dim3(capped_grid(ctx, n, 256, 16)), dim3(256), 0, ctx->stream(), s, nb, n, cent.p));

@@ -2421,34 +2421,29 @@ __global__ void pull_head_kernel(const u32* __restrict__ rowptr, const u32* __re
 
 static fgpu_info ensure_pull_order(fgpu_ctx* ctx, const fgpu_mat* At, const fgpu_mat* A) {
     std::lock_guard<std::mutex> idx_guard(At->idx_mu);
-    if (At->pull_col || At->nnz == 0 || At->nnz >= 0xFFFFFFFFull) return FGPU_OK;
+    if (At->pull_col.p || At->nnz == 0 || At->nnz >= 0xFFFFFFFFull) return FGPU_OK;
     u32 idbits = 1;
     while (idbits < 32 && (1ull << idbits) < At->ncols) ++idbits;
     if (idbits > 27) return FGPU_OK;   // 5 class bits + id must fit a 32-bit sort key
     const u32 nnz = (u32)At->nnz, nrows = (u32)At->nrows;
-    u32* keys = nullptr;
-    FGPU_TRY(ctx->dev_alloc((void**)&keys, (size_t)nnz * sizeof(u32)));
+    DevBuf<u32> keys;
     DevBuf<u64> off;
     DevBuf<uint8_t> dirty;
     DevBuf<u32> cnt;
-    fgpu_info i = off.alloc(ctx, (size_t)nrows + 1);
-    if (i == FGPU_OK) i = dirty.alloc(ctx, (size_t)nrows + 1);
-    if (i == FGPU_OK) i = cnt.alloc(ctx, (size_t)nrows + 1);
-    if (i == FGPU_OK) {
-        const u32 grid = ctx->cus * 16;
-        i = launch(pull_key_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)At->colidx, nnz, (const u32*)A->rowptr,
-                   (u32)A->nrows, idbits, keys);
-        if (i == FGPU_OK)
-            i = launch(pull_seg_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, nrows,
-                       off.p, dirty.p);
-        if (i == FGPU_OK) i = segsort_unique(ctx, keys, off.p, nrows, 0xFFFFFFFFu, cnt.p, dirty.p);
-        if (i == FGPU_OK)
-            i = launch(pull_unkey_kernel, dim3(grid), dim3(256), 0, ctx->stream(), keys, nnz,
-                       idbits >= 32 ? 0xFFFFFFFFu : ((1u << idbits) - 1u));
-        if (i == FGPU_OK) i = fgpu_sync(ctx);
-    }
-    if (i != FGPU_OK) { ctx->dev_free(keys); return i; }
-    At->pull_col = keys;   // built and synchronised above
+    FGPU_TRY(keys.alloc(ctx, nnz));
+    FGPU_TRY(off.alloc(ctx, (size_t)nrows + 1));
+    FGPU_TRY(dirty.alloc(ctx, (size_t)nrows + 1));
+    FGPU_TRY(cnt.alloc(ctx, (size_t)nrows + 1));
+    const u32 grid = ctx->cus * 16;
+    FGPU_TRY(launch(pull_key_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)At->colidx, nnz, (const u32*)A->rowptr,
+                    (u32)A->nrows, idbits, keys.p));
+    FGPU_TRY(launch(pull_seg_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)At->rowptr, nrows,
+                    off.p, dirty.p));
+    FGPU_TRY(segsort_unique(ctx, keys.p, off.p, nrows, 0xFFFFFFFFu, cnt.p, dirty.p));
+    FGPU_TRY(launch(pull_unkey_kernel, dim3(grid), dim3(256), 0, ctx->stream(), keys.p, nnz,
+                    idbits >= 32 ? 0xFFFFFFFFu : ((1u << idbits) - 1u)));
+    FGPU_TRY(fgpu_sync(ctx));
+    At->pull_col = std::move(keys);   // built and synchronised above
     return FGPU_OK;
 }
 
@@ -2601,9 +2596,9 @@ static BfsArgs make_args(fgpu_bfs_plan* p, bool fused = false) {
     a.A = view_of(p->A);
     a.At = at_view(p);
     a.head = p->pull_head.p;
-    a.hubA = p->A->hub_chunks; a.n_hubA = p->A->n_hub_chunks;
-    a.hubP = p->A->push_chunks; a.n_hubP = p->A->n_push_chunks;
-    a.hubAt = p->At ? p->At->hub_chunks : nullptr; a.n_hubAt = p->At ? p->At->n_hub_chunks : 0;
+    a.hubA = p->A->hub_chunks.p; a.n_hubA = p->A->n_hub_chunks;
+    a.hubP = p->A->push_chunks.p; a.n_hubP = p->A->n_push_chunks;
+    a.hubAt = p->At ? p->At->hub_chunks.p : nullptr; a.n_hubAt = p->At ? p->At->n_hub_chunks : 0;
     a.n = p->n; a.lo = p->lo; a.hi = p->hi;
     a.cur = p->cur.p; a.nxt_local = p->nxt_local; a.nxt_global = p->nxt_global; a.visited = p->visited.p;
     a.level = p->level.p;
@@ -2716,7 +2711,7 @@ static fgpu_info plan_buffers(fgpu_bfs_plan* p) {
 static fgpu_info plan_pull_head(fgpu_bfs_plan* p) {
     if (!p->At) return FGPU_OK;
     fgpu_ctx* ctx = p->ctx;
-    p->pull_colidx = (p->At->pull_col && ctx->opt.bfs_hub_first) ? p->At->pull_col : p->At->colidx;
+    p->pull_colidx = (p->At->pull_col.p && ctx->opt.bfs_hub_first) ? p->At->pull_col.p : p->At->colidx;
     FGPU_TRY(p->pull_head.alloc(ctx, (size_t)p->nw * 64));
     return launch(pull_head_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream(), (const u32*)p->At->rowptr, p->pull_colidx,
                   p->n, p->nw * 64, p->pull_head.p);
@@ -3713,9 +3708,9 @@ static void vxm_args(BfsArgs& a, const fgpu_mat* A, const fgpu_mat* At, u32 n, u
     memset(&a, 0, sizeof(a));
     a.A = view_of(A);
     if (At) a.At = view_of(At);
-    a.hubA = A->hub_chunks; a.n_hubA = A->n_hub_chunks;
-    a.hubP = A->push_chunks; a.n_hubP = A->n_push_chunks;
-    a.hubAt = At ? At->hub_chunks : nullptr; a.n_hubAt = At ? At->n_hub_chunks : 0;
+    a.hubA = A->hub_chunks.p; a.n_hubA = A->n_hub_chunks;
+    a.hubP = A->push_chunks.p; a.n_hubP = A->n_push_chunks;
+    a.hubAt = At ? At->hub_chunks.p : nullptr; a.n_hubAt = At ? At->n_hub_chunks : 0;
     a.head = nullptr;
     a.n = n; a.lo = 0; a.hi = nw * 64;
     a.nxt_local = out_words; a.nxt_global = out_words;
@@ -3759,7 +3754,7 @@ fgpu_info fgpu_vxm(fgpu_ctx* ctx, uint64_t* w, const uint64_t* f, const uint64_t
     const bool pull = (direction == 2);
     const u32 grid = ctx->cus * 8;
     if (direction == 3)
-        FGPU_TRY(tiles_mxv(ctx, At->tiles, df.p, nw, mask ? dm.p : nullptr, dw.p, false));
+        FGPU_TRY(tiles_mxv(ctx, At->tiles.get(), df.p, nw, mask ? dm.p : nullptr, dw.p, false));
     else if (pull)
         FGPU_TRY(launch(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p,
                         (const u64*)(mask ? dm.p : nullptr), dw.p));
@@ -3819,7 +3814,7 @@ fgpu_info fgpu_bench_spmv(fgpu_ctx* ctx, const fgpu_mat* A, int which, int iters
     FGPU_HIP(hipEventCreate(&e1));
     const u32 grid = ctx->cus * 8;
     auto pass = [&]() -> fgpu_info {
-        if (which == 2) return tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, true);
+        if (which == 2) return tiles_mxv(ctx, A->tiles.get(), df.p, nw, nullptr, dw.p, true);
         if (which == 0)
             return launch(vxm_pull_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p, (const u64*)nullptr, dw.p);
         return launch(vxm_push_kernel, dim3(grid), dim3(256), 0, ctx->stream(), a, (const u64*)df.p, (const u64*)nullptr);
@@ -3836,7 +3831,7 @@ fgpu_info fgpu_bench_spmv(fgpu_ctx* ctx, const fgpu_mat* A, int which, int iters
         if (which == 2) FGPU_HIP(hipMemsetAsync(dw.p, 0, nw * sizeof(u64), ctx->stream()));
         FGPU_HIP(hipEventRecord(e0, ctx->stream()));
         if (which == 2)
-            FGPU_TRY(tiles_mxv(ctx, A->tiles, df.p, nw, nullptr, dw.p, false));
+            FGPU_TRY(tiles_mxv(ctx, A->tiles.get(), df.p, nw, nullptr, dw.p, false));
         else
             FGPU_TRY(pass());
         FGPU_HIP(hipEventRecord(e1, ctx->stream()));

@@ -117,20 +117,16 @@ __global__ void bp_item_fill_kernel(const u32* __restrict__ rowptr, u32 nrows, c
 }
 
 // pattern transpose of `m`, built once per snapshot and owned by it (the reference keeps the same
-// thing per relationship type: Tensor::matrix_t, tensor.rs:886-888)
+// thing per relationship type: Tensor::matrix_t, tensor.rs:886-888), with its rows cut into items
 static fgpu_info transposed_with_items(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out) {
-    std::lock_guard<std::mutex> idx_guard(m->idx_mu);   // one builder; the build is synchronised before it is published
-    if (!m->tcache) {
-        fgpu_mat* t = nullptr;
-        FGPU_TRY(mat_transpose_pattern(ctx, &t, m));
-        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
-        m->tcache = t;
-    }
-    const fgpu_mat* t = m->tcache;   // reachable only through m: m's mutex covers its item list too
-    if (!t->bp_items && t->nnz) {
+    std::lock_guard<std::mutex> idx_guard(m->idx_mu);   // one builder; the build is synchronised before it is moved in
+    const fgpu_mat* t = nullptr;   // reachable only through m: m's mutex covers its item lists too
+    FGPU_TRY(mat_cached_transpose_locked(ctx, m, &t));
+    if (!t->bp_items.p && t->nnz) {
         FGPU_REQUIRE(!t->is_hyper(), FGPU_INVALID, "bit-parallel expansion needs a non-hypersparse transpose");
         const u32 nrows = (u32)t->nrows;
-        DevBuf<u32> cnt, off;
+        DevBuf<u32> cnt, off, items, sitems;
+        DevBuf<u64> sbits;
         FGPU_TRY(cnt.alloc(ctx, (size_t)nrows + 1));
         FGPU_TRY(off.alloc(ctx, (size_t)nrows + 1));
         FGPU_TRY(launch(bp_item_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
@@ -138,10 +134,9 @@ static fgpu_info transposed_with_items(fgpu_ctx* ctx, const fgpu_mat* m, const f
         FGPU_TRY(scan_u32(ctx, cnt.p, off.p, (u64)nrows + 1, nullptr));
         u32 n = 0;
         FGPU_TRY(read_u32(ctx, off.p + nrows, &n));
-        u32* items = nullptr;
-        FGPU_TRY(ctx->dev_alloc((void**)&items, (size_t)(n ? n : 1) * 3 * sizeof(u32)));
+        FGPU_TRY(items.alloc(ctx, (size_t)(n ? n : 1) * 3));
         FGPU_TRY(launch(bp_item_fill_kernel<false>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(),
-                        (const u32*)t->rowptr, nrows, (const u32*)off.p, items));
+                        (const u32*)t->rowptr, nrows, (const u32*)off.p, items.p));
         // the split rows' items once more, on their own: the row-group form of the sparse pull leaves exactly these
         // to the item kernel
         FGPU_TRY(launch(bp_sitem_count_kernel, dim3(cdiv((u64)nrows + 1, 256)), dim3(256), 0, ctx->stream(),
@@ -149,25 +144,19 @@ static fgpu_info transposed_with_items(fgpu_ctx* ctx, const fgpu_mat* m, const f
         FGPU_TRY(scan_u32(ctx, cnt.p, off.p, (u64)nrows + 1, nullptr));
         u32 ns = 0;
         FGPU_TRY(read_u32(ctx, off.p + nrows, &ns));
-        u32* sitems = nullptr;
-        fgpu_info ssi = ctx->dev_alloc((void**)&sitems, (size_t)(ns ? ns : 1) * 3 * sizeof(u32));
-        if (ssi != FGPU_OK) { ctx->dev_free(items); return ssi; }
-        fgpu_info si = FGPU_OK;
+        FGPU_TRY(sitems.alloc(ctx, (size_t)(ns ? ns : 1) * 3));
         if (ns)
-            si = launch(bp_item_fill_kernel<true>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows,
-                        (const u32*)off.p, sitems);
-        u64* sbits = nullptr;
-        if (si == FGPU_OK) si = ctx->dev_alloc((void**)&sbits, ((size_t)nrows / 64 + 2) * sizeof(u64));
-        if (si == FGPU_OK) {
-            t->bp_split_bits = sbits;   // (owned by t from here on, whatever follows)
-            si = launch(bp_split_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows, sbits);
-        }
-        if (si == FGPU_OK) si = fgpu_sync(ctx);
-        if (si != FGPU_OK) { ctx->dev_free(items); ctx->dev_free(sitems); return si; }
+            FGPU_TRY(launch(bp_item_fill_kernel<true>, dim3(cdiv(nrows, 256)), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows,
+                            (const u32*)off.p, sitems.p));
+        FGPU_TRY(sbits.alloc(ctx, (size_t)nrows / 64 + 2));
+        FGPU_TRY(launch(bp_split_bits_kernel, dim3(ctx->cus * 4), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, nrows, sbits.p));
+        FGPU_TRY(fgpu_sync(ctx));
+        // attached together (bp_split_bits used to go first): nothing reads it before bp_items is set, and both are set under m->idx_mu
+        t->bp_split_bits = std::move(sbits);
         t->n_bp_sitems = ns;
-        t->bp_sitems = sitems;
+        t->bp_sitems = std::move(sitems);
         t->n_bp_items = n;
-        t->bp_items = items;
+        t->bp_items = std::move(items);
     }
     *out = t;
     return FGPU_OK;
@@ -1524,7 +1513,7 @@ static fgpu_info bp_touched_bits(fgpu_ctx* ctx, const HopPlan& p, u32 n_out, con
 // every row, so the delta destinations only), its prefix, and a zeroed side buffer of one slot per touched row
 static fgpu_info bp_touched_side(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, u32 n_out, DevBuf<u64>& tbits, DevBuf<u32>& tpref,
                                  DevBuf<u64>& side, u32* ntouched) {
-    FGPU_TRY(bp_touched_bits(ctx, p, n_out, p.xp || !p.t ? nullptr : p.t->bp_split_bits, tbits));
+    FGPU_TRY(bp_touched_bits(ctx, p, n_out, p.xp || !p.t ? nullptr : p.t->bp_split_bits.p, tbits));
     const u32 nwords = (n_out + 63) / 64;
     DevBuf<u32> tpc, ttot;
     FGPU_TRY(tpc.alloc(ctx, (size_t)nwords + 2));
@@ -1622,7 +1611,7 @@ static fgpu_info bp_pull_items_rec(fgpu_ctx* ctx, const HopPlan& p, const BitSta
     u32 grid = cdiv(nitems, 16);
     if (grid > (u32)ctx->cus * 2) grid = ctx->cus * 2;     // 32 wavefronts on a CU: all it holds
     return pick<1, 2, 4, 8, 16>((int)s.ws, [&](auto ln) {
-        return launch(bp_pull_items_rec_kernel<decltype(ln)::value>, dim3(grid), dim3(1024), lds, ctx->stream(), view_of(p.t), p.t->bp_sitems,
+        return launch(bp_pull_items_rec_kernel<decltype(ln)::value>, dim3(grid), dim3(1024), lds, ctx->stream(), view_of(p.t), p.t->bp_sitems.p,
                       nitems, s.x.p, recs, pm.pr, out.y, out.flag, p.operm);
     });
 }
@@ -1634,13 +1623,13 @@ static fgpu_info bp_pull_groups(fgpu_ctx* ctx, const HopPlan& p, const BitState&
     if (p.fuse_stats) {
         FGPU_TRY(bp_acc_alloc(ctx, st.sums));
         // split rows + delta destinations: the rows summed after the fix-ups
-        if (p.dm || p.dp) FGPU_TRY(bp_touched_bits(ctx, p, (u32)p.t->nrows, p.t->bp_split_bits, st.later));
+        if (p.dm || p.dp) FGPU_TRY(bp_touched_bits(ctx, p, (u32)p.t->nrows, p.t->bp_split_bits.p, st.later));
     }
     DevBuf<u64> recs;
     if (p.use_rec) FGPU_TRY(bp_records(ctx, s, recs));
     FGPU_TRY(bp_pull_group_rows(ctx, p, s, pm, out, next_m, st, recs.p));
     if (p.use_rec) return bp_pull_items_rec(ctx, p, s, pm, out, recs.p);
-    return bp_pull_items(ctx, p, s, p.t->bp_sitems, p.t->n_bp_sitems, pm, out);
+    return bp_pull_items(ctx, p, s, p.t->bp_sitems.p, p.t->n_bp_sitems, pm, out);
 }
 
 // the pull of a hop in its plain and sparse forms, under the hop's profiler record (`pull_idx`: bp_hop adds the rows it wrote)
@@ -1658,7 +1647,7 @@ static fgpu_info bp_pull(fgpu_ctx* ctx, const HopPlan& p, const BitState& s, con
     ProfScope ps(ctx, nm, 4 * (u64)p.t->nnz + 12 * (u64)nitems + xrows * 8 * s.w + (p.sparse ? (u64)s.n / 8 : 0));
     ps.idx_out = pull_idx;
     if (p.groups) return bp_pull_groups(ctx, p, s, pm, out, next_m, *st);   // (mid-chain hops only)
-    return bp_pull_items(ctx, p, s, p.t->bp_items, p.t->n_bp_items, pm, out);
+    return bp_pull_items(ctx, p, s, p.t->bp_items.p, p.t->n_bp_items, pm, out);
 }
 
 // Y[v] &= ~X[u] for the entries (u, v) of dm, Y[v] |= X[u] for those of dp
@@ -1690,7 +1679,7 @@ static fgpu_info bp_hop_finish(fgpu_ctx* ctx, const HopPlan& p, BitState& s, Bit
         if (p.t->n_bp_sitems || st.later.p) {
             u32 lnsh = 0;
             while ((2u << lnsh) <= s.ws && lnsh < 6) ++lnsh;
-            FGPU_TRY(launch(bp_split_stats_kernel, dim3(ctx->cus * 2), dim3(256), 0, ctx->stream(), st.later.p ? st.later.p : p.t->bp_split_bits,
+            FGPU_TRY(launch(bp_split_stats_kernel, dim3(ctx->cus * 2), dim3(256), 0, ctx->stream(), st.later.p ? st.later.p : p.t->bp_split_bits.p,
                             o.n, s.ws, lnsh, o.x.p, next_m->rowptr, (unsigned long long*)st.sums.p, p.operm));
         }
         FGPU_TRY(bp_acc_read(ctx, st.sums.p, &o.pre_flops, &o.nz_rows));

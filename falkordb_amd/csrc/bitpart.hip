@@ -49,50 +49,38 @@ struct BpXPlan {
     // built over 64 consecutive RANKS, and gvtx names the vertex of a slot where the fold needs it (hash, label, touched bit).
     int dense = 0;                 // the form the plan was built under (0: group g = vertices 64 g .. 64 g + 63, gvtx stays null)
     u32 nd = 0;                    // rows of A' with at least one entry (dense form; ng = ceil(nd / 64))
-    u32* gvtx = nullptr;           // [ng * 64] vertex of slot 64 g + r, XP_NO_VTX past rank nd - 1 (a padded slot: no piece, no vertex)
+    DevBuf<u32> gvtx;              // [ng * 64] vertex of slot 64 g + r, XP_NO_VTX past rank nd - 1 (a padded slot: no piece, no vertex)
     u64 nentries = 0;
     u32 nprows = 0;                // partial rows = runs = non-empty (partition, row) pairs
     u32 nchunks = 0;
-    u32* pcol = nullptr;           // the entries, partition-major, rows ascending inside a partition: XP_FIRST | column id
+    DevBuf<u32> pcol;              // the entries, partition-major, rows ascending inside a partition: XP_FIRST | column id
     u32 pstart[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // first entry of partition k
     u32 cbase[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};    // first chunk of partition k
-    u32* pstart_dev = nullptr;     // [9] + cbase [9]
-    u32* cstart = nullptr;         // first entry of the chunk
-    u32* crun0 = nullptr;          // run (= partial row) of the chunk's first entry
-    uint8_t* cshared = nullptr;    // 1: that run began in an earlier chunk (its pieces meet through atomics)
-    u32* zrows = nullptr;          // the partial rows that receive pieces from several chunks (zeroed before every hop)
+    DevBuf<u32> pstart_dev;        // [9] + cbase [9]
+    DevBuf<u32> cstart;            // first entry of the chunk
+    DevBuf<u32> crun0;             // run (= partial row) of the chunk's first entry
+    DevBuf<uint8_t> cshared;       // 1: that run began in an earlier chunk (its pieces meet through atomics)
+    DevBuf<u32> zrows;             // the partial rows that receive pieces from several chunks (zeroed before every hop)
     u32 nzrows = 0;
-    u64* ne = nullptr;             // [8][ng] bit r: (partition, row 64 g + r — dense: the row of slot 64 g + r) has entries in the stream
-    u32* pbase = nullptr;          // [8][ng] partial row of the group's first non-empty row
+    DevBuf<u64> ne;                // [8][ng] bit r: (partition, row 64 g + r — dense: the row of slot 64 g + r) has entries in the stream
+    DevBuf<u32> pbase;             // [8][ng] partial row of the group's first non-empty row
     // direct entries (expand_xp_direct = 1): a (partition, row) run of ONE entry is left out of the stream — its partial row would
     // be a copy of one row of X, gathered, flushed through the tile, written and read back — and the fold reads that row of X
     // itself.  At RMAT-22 these are 43 % of the runs (the partial rows) and 5 % of the entries, most of them hot rows of X.
     int direct = 0;                // the mode the plan was built under (0: every run is streamed, de / dbase / dcol stay null)
     u64 ndirect = 0;
-    u64* de = nullptr;             // [8][ng] bit r: (partition, row 64 g + r) is one direct entry
-    u32* dbase = nullptr;          // [8][ng] index in dcol of the group's first direct entry
-    u32* dcol = nullptr;           // the direct entries' columns (slots of X, like pcol's), partition-major, rows ascending
+    DevBuf<u64> de;                // [8][ng] bit r: (partition, row 64 g + r) is one direct entry
+    DevBuf<u32> dbase;             // [8][ng] index in dcol of the group's first direct entry
+    DevBuf<u32> dcol;              // the direct entries' columns (slots of X, like pcol's), partition-major, rows ascending
     // slot of X's row u in the state this plan gathers from (nullptr: slot = u).  Rows are ranked by how often they are gathered
     // (out-degree of u in m, descending) and dealt to the partitions in turn — slot = (rank % 8) x range + rank / 8 — so every
     // partition holds an eighth of the hot rows, packed hot-first: a 128-byte line then carries two rows (64-byte rows) of about
     // the same heat, where vertex order puts a hot row next to a random one — the L2's capacity for hot rows doubles
     // (simulated: hit rate 0.75 -> 0.85 at RMAT-22).  The hop that PRODUCES the state writes row v at slot perm[v] (bitexpand.hip).
-    u32* perm = nullptr;
+    DevBuf<u32> perm;
 };
-const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm : nullptr; }
-
-static void xp_free_buffers(fgpu_ctx* ctx, BpXPlan* p) {
-    for (void** b : {(void**)&p->pcol, (void**)&p->pstart_dev, (void**)&p->cstart, (void**)&p->crun0, (void**)&p->cshared, (void**)&p->zrows,
-                     (void**)&p->ne, (void**)&p->pbase, (void**)&p->perm, (void**)&p->de, (void**)&p->dbase, (void**)&p->dcol, (void**)&p->gvtx}) {
-        ctx->dev_free(*b);
-        *b = nullptr;
-    }
-}
-void bp_xplan_release(fgpu_ctx* ctx, BpXPlan* p) {
-    if (!p) return;
-    if (ctx) xp_free_buffers(ctx, p);
-    delete p;
-}
+const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm.p : nullptr; }
+void BpXPlanDelete::operator()(BpXPlan* p) const { delete p; }
 
 // ---- plan build (once per snapshot) ----------------------------------------------------------------------------------------
 // The entries of A' arrive partitioned by the slot range of their column (partition_csr_entries, transpose.hip: one
@@ -272,36 +260,11 @@ __global__ void xp_rank_kernel(const u32* __restrict__ by_rank, u32 n, u32 prang
     for (u32 r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) perm[by_rank[r]] = (r & 7u) * prange + (r >> 3);
 }
 
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, const BpXPlan** out);
-// The plan is an optional accelerator: when its build fails (its temporaries are large — 64 bytes per vertex and 8 per entry) the
-// half-built plan's buffers are freed, it stays attached as "not usable" (no second attempt per snapshot), the error is dropped
-// and the hop falls back to the plain pull.
-// A plan is kept per (expand_xp_direct, expand_xp_dense) pair (a plan built under one pair is never handed to a hop expecting
-// another); the fold takes the form of its plan.
-fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
-    const int direct = ctx->opt.expand_xp_direct ? 1 : 0, dense = ctx->opt.expand_xp_dense ? 1 : 0;
-    const int which = direct + 2 * dense;
-    const fgpu_info i = bp_xplan_build(ctx, m, t, direct, dense, out);
-    if (i == FGPU_OK) return FGPU_OK;
-    *out = nullptr;
-    if (t && t->bp_xplan[which] && !t->bp_xplan[which]->usable) {
-        xp_free_buffers(ctx, t->bp_xplan[which]);
-        (void)hipGetLastError();
-        set_error("%s", "");
-        return FGPU_OK;
-    }
-    return i;                                                // (failed before a plan was attached: an argument / state error)
-}
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, const BpXPlan** out) {
-    *out = nullptr;
-    if (!ctx->opt.expand_xcd || !t || t->is_hyper()) return FGPU_OK;
-    if (t->ncols >= (1ull << 31) || t->nrows >= 0xFFFFFFC0ull || t->nnz < 4096 || t->nnz >= 0x7FFFFFFFull) return FGPU_OK;
-    std::lock_guard<std::mutex> idx_guard(m->idx_mu);
-    const int which = direct + 2 * dense;
-    if (t->bp_xplan[which]) { if (t->bp_xplan[which]->usable) *out = t->bp_xplan[which]; return FGPU_OK; }
-    BpXPlan* xp = new (std::nothrow) BpXPlan();
+// builds the plan of `t` (= m') under one (direct, dense) pair; the caller holds m->idx_mu.  *out is set when the plan is
+// complete on the device; an error frees whatever was built so far
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, BpXPlanPtr* out) {
+    BpXPlanPtr xp(new (std::nothrow) BpXPlan());
     FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
-    t->bp_xplan[which] = xp;                                   // (published as "not usable" until the build below completes)
     const u32 n = (u32)t->nrows;
     u32 ng = (n + 63) / 64, nslots = n;
     xp->n = n; xp->nentries = t->nnz; xp->direct = direct; xp->dense = dense;
@@ -315,9 +278,9 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_REQUIRE(xp->nd >= 1 && xp->nd <= n, FGPU_INVALID, "partitioned pull: %u of %u rows have an entry", xp->nd, n);
         nslots = xp->nd;
         ng = (nslots + 63) / 64;
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->gvtx, (size_t)ng * 64 * sizeof(u32)));
-        FGPU_HIP(hipMemsetAsync(xp->gvtx, 0xFF, (size_t)ng * 64 * sizeof(u32), st));    // XP_NO_VTX
-        FGPU_TRY(launch(xp_slots_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)rank.p, n, xp->gvtx));
+        FGPU_TRY(xp->gvtx.alloc(ctx, (size_t)ng * 64));
+        FGPU_HIP(hipMemsetAsync(xp->gvtx.p, 0xFF, (size_t)ng * 64 * sizeof(u32), st));    // XP_NO_VTX
+        FGPU_TRY(launch(xp_slots_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)rank.p, n, xp->gvtx.p));
     }
     xp->ng = ng;
     const u64 total = 8ull * n;
@@ -333,22 +296,22 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(dval.alloc(ctx, nu));
         FGPU_TRY(by_rank.alloc(ctx, nu));
         FGPU_TRY(kptr.alloc(ctx, 65536 + 1));
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->perm, (size_t)nu * sizeof(u32)));
+        FGPU_TRY(xp->perm.alloc(ctx, (size_t)nu));
         FGPU_TRY(launch(xp_deg_key_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)m->rowptr, nu, dkey.p, dval.p));
         FGPU_TRY(sort_u32_pairs_by_key(ctx, dkey.p, dval.p, nu, 65536, by_rank.p, kptr.p));
-        FGPU_TRY(launch(xp_rank_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)by_rank.p, nu, prange, xp->perm));
+        FGPU_TRY(launch(xp_rank_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)by_rank.p, nu, prange, xp->perm.p));
     }
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->pstart_dev, 27 * sizeof(u32)));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->pcol, ((size_t)t->nnz + 64) * sizeof(u32)));
+    FGPU_TRY(xp->pstart_dev.alloc(ctx, 27));
+    FGPU_TRY(xp->pcol.alloc(ctx, ((size_t)t->nnz + 64)));
     {
         DevBuf<uint2> pairs;
         FGPU_TRY(pairs.alloc(ctx, t->nnz));
-        FGPU_TRY(partition_csr_entries(ctx, t->colidx, t->rowptr, n, t->nnz, xp->perm, prange, 8, pairs.p, xp->pstart_dev));
+        FGPU_TRY(partition_csr_entries(ctx, t->colidx, t->rowptr, n, t->nnz, xp->perm.p, prange, 8, pairs.p, xp->pstart_dev.p));
         u32 rgrid = cdiv(t->nnz, 256 * 4);
         if (rgrid > (u32)ctx->cus * 16) rgrid = ctx->cus * 16;
-        FGPU_TRY(launch(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, (u32)t->nnz,
-                        xp->pcol, off.p));
-        FGPU_TRY(launch(xp_run_tails_kernel, dim3(64, 8), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev, n, off.p));
+        FGPU_TRY(launch(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev.p, n, (u32)t->nnz,
+                        xp->pcol.p, off.p));
+        FGPU_TRY(launch(xp_run_tails_kernel, dim3(64, 8), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev.p, n, off.p));
     }
     if (direct) {   // the single-entry runs leave the stream; everything below is built over the runs that stay
         const u32 nnz = (u32)t->nnz;
@@ -356,31 +319,30 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(pos.alloc(ctx, (size_t)nnz + 1));
         u32 egrid = cdiv((u64)nnz + 1, 256 * 4);
         if (egrid > (u32)ctx->cus * 16) egrid = ctx->cus * 16;
-        FGPU_TRY(launch(xp_keep_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, nnz, pos.p));
+        FGPU_TRY(launch(xp_keep_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol.p, nnz, pos.p));
         FGPU_TRY(scan_u32(ctx, pos.p, pos.p, (u64)nnz + 1, nullptr));
         u32 nkept = 0;
         FGPU_TRY(read_u32(ctx, pos.p + nnz, &nkept));
         xp->ndirect = nnz - nkept;
-        u32* kept = nullptr;
-        FGPU_TRY(ctx->dev_alloc((void**)&kept, ((size_t)nkept + 64) * sizeof(u32)));
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->dcol, ((size_t)xp->ndirect + 1) * sizeof(u32)));
-        FGPU_HIP(hipMemsetAsync(xp->dcol, 0, sizeof(u32), st));   // (index 0 is what the fold loads for a row without one)
-        FGPU_TRY(launch(xp_split_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol, (const u32*)pos.p, nnz, kept, xp->dcol));
-        ctx->dev_free(xp->pcol);
-        xp->pcol = kept;
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->de, (size_t)8 * ng * sizeof(u64)));
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->dbase, ((size_t)8 * ng + 1) * sizeof(u32)));
+        DevBuf<u32> kept;
+        FGPU_TRY(kept.alloc(ctx, (size_t)nkept + 64));
+        FGPU_TRY(xp->dcol.alloc(ctx, ((size_t)xp->ndirect + 1)));
+        FGPU_HIP(hipMemsetAsync(xp->dcol.p, 0, sizeof(u32), st));   // (index 0 is what the fold loads for a row without one)
+        FGPU_TRY(launch(xp_split_kernel, dim3(egrid), dim3(256), 0, st, (const u32*)xp->pcol.p, (const u32*)pos.p, nnz, kept.p, xp->dcol.p));
+        xp->pcol = std::move(kept);   // (the full stream goes now)
+        FGPU_TRY(xp->de.alloc(ctx, (size_t)8 * ng));
+        FGPU_TRY(xp->dbase.alloc(ctx, ((size_t)8 * ng + 1)));
         u32 ggrid = cdiv((u64)8 * ng, 4);
         if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
         FGPU_TRY(launch(xp_direct_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)pos.p, n, ng,
-                        (const u32*)xp->gvtx, nslots, xp->de, xp->dbase));
-        FGPU_TRY(launch(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev));
+                        (const u32*)xp->gvtx.p, nslots, xp->de.p, xp->dbase.p));
+        FGPU_TRY(launch(xp_remap_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, off.p, total, (const u32*)pos.p, xp->pstart_dev.p));
     }
     FGPU_TRY(launch(xp_nonempty_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, total, ridx.p));
     FGPU_TRY(scan_u32(ctx, ridx.p, ridx.p, total + 1, nullptr));
     FGPU_TRY(read_u32(ctx, ridx.p + total, &xp->nprows));
     u32 hp[27];                                              // pstart[9] | cbase[9] | first run of partition k [9]
-    FGPU_TRY(read_words(ctx, xp->pstart_dev, 9, hp));
+    FGPU_TRY(read_words(ctx, xp->pstart_dev.p, 9, hp));
     for (int k = 0; k <= 8; ++k) FGPU_TRY(read_u32(ctx, ridx.p + (size_t)k * n, &hp[18 + k]));
     hp[9] = 0;
     for (int k = 0; k < 8; ++k) {
@@ -389,34 +351,61 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     }
     for (int k = 0; k <= 8; ++k) { xp->pstart[k] = hp[k]; xp->cbase[k] = hp[9 + k]; }
     xp->nchunks = xp->cbase[8];
-    FGPU_TRY(ctx->h2d(xp->pstart_dev, hp, 27 * sizeof(u32)));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->ne, (size_t)8 * ng * sizeof(u64)));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->pbase, ((size_t)8 * ng + 1) * sizeof(u32)));
+    FGPU_TRY(ctx->h2d(xp->pstart_dev.p, hp, 27 * sizeof(u32)));
+    FGPU_TRY(xp->ne.alloc(ctx, (size_t)8 * ng));
+    FGPU_TRY(xp->pbase.alloc(ctx, ((size_t)8 * ng + 1)));
     u32 ggrid = cdiv((u64)8 * ng, 4);
     if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
     FGPU_TRY(launch(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng,
-                    (const u32*)xp->gvtx, nslots, xp->ne, xp->pbase));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->cstart, ((size_t)xp->nchunks + 1) * sizeof(u32)));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->crun0, ((size_t)xp->nchunks + 1) * sizeof(u32)));
-    FGPU_TRY(ctx->dev_alloc((void**)&xp->cshared, (size_t)xp->nchunks + 8));
-    FGPU_HIP(hipMemsetAsync(xp->cshared, 0, (size_t)xp->nchunks + 8, st));
+                    (const u32*)xp->gvtx.p, nslots, xp->ne.p, xp->pbase.p));
+    FGPU_TRY(xp->cstart.alloc(ctx, ((size_t)xp->nchunks + 1)));
+    FGPU_TRY(xp->crun0.alloc(ctx, ((size_t)xp->nchunks + 1)));
+    FGPU_TRY(xp->cshared.alloc(ctx, (size_t)xp->nchunks + 8));
+    FGPU_HIP(hipMemsetAsync(xp->cshared.p, 0, (size_t)xp->nchunks + 8, st));
     FGPU_TRY(launch(xp_chunks_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n,
-                    (const u32*)xp->pstart_dev, xp->cstart, xp->crun0, xp->cshared));
+                    (const u32*)xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p));
     {   // the shared rows, compacted once (a few thousand among ~10^5 chunks)
         DevBuf<u32> zc;
         FGPU_TRY(zc.alloc(ctx, 1));
         FGPU_HIP(hipMemsetAsync(zc.p, 0, sizeof(u32), st));
-        FGPU_TRY(ctx->dev_alloc((void**)&xp->zrows, ((size_t)xp->nchunks + 1) * sizeof(u32)));
-        FGPU_TRY(launch(xp_shared_rows_kernel, dim3(cdiv(xp->nchunks ? xp->nchunks : 1, 256)), dim3(256), 0, st, (const u32*)xp->crun0,
-                        (const uint8_t*)xp->cshared, xp->nchunks, xp->zrows, zc.p));
+        FGPU_TRY(xp->zrows.alloc(ctx, ((size_t)xp->nchunks + 1)));
+        FGPU_TRY(launch(xp_shared_rows_kernel, dim3(cdiv(xp->nchunks ? xp->nchunks : 1, 256)), dim3(256), 0, st, (const u32*)xp->crun0.p,
+                        (const uint8_t*)xp->cshared.p, xp->nchunks, xp->zrows.p, zc.p));
         FGPU_TRY(read_u32(ctx, zc.p, &xp->nzrows));
         // ... and the spare row after the last run: the all-zero partial row the fold reads for (row, partition) pairs without one
-        FGPU_TRY(ctx->h2d(xp->zrows + xp->nzrows, &xp->nprows, sizeof(u32)));
+        FGPU_TRY(ctx->h2d(xp->zrows.p + xp->nzrows, &xp->nprows, sizeof(u32)));
         xp->nzrows += 1;
     }
     FGPU_HIP(hipStreamSynchronize(st));
     xp->usable = true;
-    *out = xp;
+    *out = std::move(xp);
+    return FGPU_OK;
+}
+
+// The plan is an optional accelerator: when its build fails (its temporaries are large — 64 bytes per vertex and 8 per entry) the
+// half-built plan is freed, an empty one is attached as "not usable" (no second attempt per snapshot), the error is dropped
+// and the hop falls back to the plain pull.  (idx_mu is held from the look-up to the attachment: no reader
+// can tell this from attaching the plan first and finishing it afterwards.)
+// A plan is kept per (expand_xp_direct, expand_xp_dense) pair (a plan built under one pair is never handed to a hop expecting
+// another); the fold takes the form of its plan.
+fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
+    *out = nullptr;
+    if (!ctx->opt.expand_xcd || !t || t->is_hyper()) return FGPU_OK;
+    if (t->ncols >= (1ull << 31) || t->nrows >= 0xFFFFFFC0ull || t->nnz < 4096 || t->nnz >= 0x7FFFFFFFull) return FGPU_OK;
+    const int direct = ctx->opt.expand_xp_direct ? 1 : 0, dense = ctx->opt.expand_xp_dense ? 1 : 0;
+    std::lock_guard<std::mutex> idx_guard(m->idx_mu);
+    BpXPlanPtr& slot = t->bp_xplan[direct + 2 * dense];
+    if (!slot) {
+        BpXPlanPtr xp;
+        if (bp_xplan_build(ctx, m, t, direct, dense, &xp) != FGPU_OK) {
+            xp.reset(new (std::nothrow) BpXPlan());
+            FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
+            (void)hipGetLastError();
+            set_error("%s", "");
+        }
+        slot = std::move(xp);
+    }
+    if (slot->usable) *out = slot.get();
     return FGPU_OK;
 }
 
@@ -970,7 +959,7 @@ static fgpu_info xp_zero_rows(fgpu_ctx* ctx, const BpXPlan* xp, u32 ql, uint4* p
     if (!xp->nzrows) return FGPU_OK;
     u32 grid = cdiv(xp->nzrows, 256 / ql);
     if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
-    return launch(xp_zero_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), xp->zrows, xp->nzrows, ql, partial);
+    return launch(xp_zero_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), xp->zrows.p, xp->nzrows, ql, partial);
 }
 
 static fgpu_info xp_stream(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, uint4* partial, u64 xrows) {
@@ -992,7 +981,7 @@ static fgpu_info xp_stream(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, 
     const bool wide = (u64)xp->n * ws * 8 > (1ull << 32) || (u64)t->ncols * ws * 8 > (1ull << 32);
     return pick<1, 2, 4, 8>((int)ql, [&](auto q) { return pick(wide, [&](auto w) { return pick<1, 2, 3, 0>(ctx->opt.expand_nt & 3, [&](auto nt) {
         return launch(xp_stream_kernel<decltype(q)::value, decltype(w)::value, decltype(nt)::value>, dim3(grid), dim3(256), lds, ctx->stream(),
-                      xp->pcol, xp->pstart_dev, xp->cstart, xp->crun0, xp->cshared, (const uint4*)x, partial);
+                      xp->pcol.p, xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p, (const uint4*)x, partial);
     }); }); });
 }
 
@@ -1020,10 +1009,10 @@ static fgpu_info xp_fold(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
             constexpr int Q = decltype(q)::value, M = decltype(md)::value;
             constexpr bool N = decltype(nt)::value, D = decltype(direct)::value, G = decltype(dense)::value;
             if (pieces)
-                return launch(xp_fold_pieces_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne, xp->pbase, xp->ng,
-                              partial, fin, (uint4*)side, xp->de, xp->dbase, xp->dcol, (const uint4*)x, xp->gvtx);
-            return launch(xp_fold_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne, xp->pbase, xp->ng,
-                          partial, fin, (uint4*)side, xp->nprows, xp->de, xp->dbase, xp->dcol, (const uint4*)x, xp->gvtx);
+                return launch(xp_fold_pieces_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne.p, xp->pbase.p, xp->ng,
+                              partial, fin, (uint4*)side, xp->de.p, xp->dbase.p, xp->dcol.p, (const uint4*)x, xp->gvtx.p);
+            return launch(xp_fold_kernel<Q, M, N, D, G>, dim3(grid), dim3(fthreads), lds, ctx->stream(), xp->ne.p, xp->pbase.p, xp->ng,
+                          partial, fin, (uint4*)side, xp->nprows, xp->de.p, xp->dbase.p, xp->dcol.p, (const uint4*)x, xp->gvtx.p);
         }); });
     }); }); });
 }
@@ -1032,7 +1021,7 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
                          u64* side, size_t lds_tables, u64 xrows) {
     FGPU_REQUIRE(xp && xp->usable && ws >= 2 && ws <= 16 && (ws & (ws - 1)) == 0, FGPU_INVALID, "partitioned pull: bad plan / row width");
     FGPU_REQUIRE(mode == 1 || mode == 2, FGPU_INVALID, "partitioned pull: counting hops only");
-    FGPU_REQUIRE(!xp->dense == !xp->gvtx, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
+    FGPU_REQUIRE(!xp->dense == !xp->gvtx.p, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
     ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
     ctx->xp_last_groups.store(xp->ng, std::memory_order_relaxed);
     DevBuf<uint4> partial;

@@ -256,12 +256,6 @@ __global__ __launch_bounds__(1024, WPE) void blocked_mxv_kernel(BlockedView t, c
     }
 }
 
-void blocked_release(fgpu_ctx* ctx, fgpu_tiles* t) {
-    if (!ctx) return;
-    ctx->dev_free(t->bk_seg_off);
-    ctx->dev_free(t->bk_entries);
-}
-
 fgpu_info blocked_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 x_words64, const u64* mask_dev, u64* out_dev) {
     if (t->nentries == 0) return FGPU_OK;
     const u32 ow = 1u << (t->bk_wbits - 5);
@@ -279,7 +273,7 @@ fgpu_info blocked_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 
         case 3: fn = blocked_mxv_kernel<4, 8>; break;
         default: break;
     }
-    BlockedView v{t->bk_seg_off, t->bk_entries, t->bk_wbits, t->bk_nwindows, t->ntiles, t->bk_nsplit};
+    BlockedView v{t->bk_seg_off.p, t->bk_entries.p, t->bk_wbits, t->bk_nwindows, t->ntiles, t->bk_nsplit};
     u32 per_cu = (u32)(ctx->opt.lds_limit / lds);
     if (per_cu > max_per_cu) per_cu = max_per_cu;    // 2 x 1024 threads fill a CU
     if (per_cu < 1) per_cu = 1;
@@ -318,16 +312,16 @@ fgpu_info blocked_build(fgpu_ctx* ctx, const fgpu_mat* m, CsrView mv, fgpu_tiles
     FGPU_TRY(read_u64(ctx, off64.p + nbuckets, &total));
     FGPU_REQUIRE(total < 0xFFFFFFF0ull, FGPU_INVALID, "blocked layout: %llu padded entries exceed the 32-bit offset space",
                  (unsigned long long)total);
-    FGPU_TRY(ctx->dev_alloc((void**)&t->bk_seg_off, ((size_t)nblocks + 1) * sizeof(u32)));     // block offsets
-    FGPU_TRY(ctx->dev_alloc((void**)&t->bk_entries, (size_t)(total ? total : 4) * sizeof(u32)));
+    FGPU_TRY(t->bk_seg_off.alloc(ctx, (size_t)nblocks + 1));     // block offsets
+    FGPU_TRY(t->bk_entries.alloc(ctx, (size_t)(total ? total : 4)));
     FGPU_TRY(scan_u32(ctx, padded.p, seg_off.p, (u64)nbuckets + 1, nullptr));                  // the same prefix in 32 bits
     FGPU_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)nbuckets + 1) * sizeof(u32), ctx->stream()));
     FGPU_TRY(launch(bk_scatter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)nrows, wbits, ntiles, cnt.p,
-                    (const u32*)seg_off.p, t->bk_entries));
+                    (const u32*)seg_off.p, t->bk_entries.p));
     FGPU_TRY(launch(bk_pad_fill_kernel, dim3(cdiv(nbuckets, 256)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p,
-                    (const u32*)seg_off.p, nbuckets, t->bk_entries));
+                    (const u32*)seg_off.p, nbuckets, t->bk_entries.p));
     FGPU_TRY(launch(bk_block_off_kernel, dim3(cdiv((u64)nblocks + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)seg_off.p,
-                    nblocks, t->bk_seg_off));
+                    nblocks, t->bk_seg_off.p));
     FGPU_HIP(hipStreamSynchronize(ctx->stream()));
     t->kind = 1;
     t->bk_wbits = wbits;

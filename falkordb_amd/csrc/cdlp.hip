@@ -437,9 +437,9 @@ extern "C" fgpu_info fgpu_cdlp(fgpu_ctx* ctx, const fgpu_mat* S, const uint64_t*
             FGPU_TRY(coff.alloc(ctx, nch));
             FGPU_TRY(hubmem.alloc(ctx, hub_words));
             FGPU_TRY(launch(cdlp_chunk_len_kernel, dim3(capped_grid(ctx, nch, 256, 8)), dim3(256), 0, st,
-                            (const u32*)S->hub_chunks, nch, clen.p));
+                            (const u32*)S->hub_chunks.p, nch, clen.p));
             FGPU_TRY(scan_u32(ctx, clen.p, coff.p, nch, nullptr));
-            hb.chunks = S->hub_chunks;
+            hb.chunks = S->hub_chunks.p;
             hb.n_chunks = nch;
             hb.coff = coff.p;
             hb.best = hubmem.p;

@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -319,9 +320,15 @@ struct fgpu_tiles;  // tiled.hip: LDS-staged frontier-tile edge layout (accelera
 
 // The stored matrix (dims, rowptr, colidx, vals, hrows) never changes after creation.  The acceleration indexes
 // below are built lazily on first use; every such build happens under `idx_mu`, is complete on the device
-// (stream synchronised) before its pointer is published, and is never replaced afterwards — concurrent readers
+// (stream synchronised) before its holder is moved in, and is never replaced afterwards — concurrent readers
 // on other lanes either see no index (and take the lock) or a finished one.
-namespace fgpu { struct BpXPlan; struct PrParts; }   // bitexpand.hip, pagerank.hip
+namespace fgpu {
+struct BpXPlan;   // bitpart.hip
+struct PrParts;   // pagerank.hip
+struct BpXPlanDelete { void operator()(BpXPlan* p) const; };   // `delete p`, beside the type
+struct PrPartsDelete { void operator()(PrParts* p) const; };
+typedef std::unique_ptr<BpXPlan, BpXPlanDelete> BpXPlanPtr;
+}  // namespace fgpu
 struct fgpu_mat {
     fgpu_ctx* ctx = nullptr;
     mutable std::mutex idx_mu;
@@ -331,18 +338,21 @@ struct fgpu_mat {
     uint32_t* colidx = nullptr; // device
     uint64_t* vals = nullptr;   // device, nullable (BOOL: pattern only)
     uint32_t* hrows = nullptr;  // device, nullable
+    // The four stored arrays above are freed by mat_release; everything below frees itself when mat_release deletes the
+    // matrix, through the context it was allocated from and in REVERSE order of declaration: the sub-objects at the end of
+    // the struct (the partitioned plans, the column ranges, the tiles, and the cached transpose with everything of its own)
+    // go first, then the matrix's own index arrays from bp_split_bits back to hub_chunks.
     // static hub list for the push kernels (rows with degree >= HUB_DEG), device
-    mutable uint32_t* hub_chunks = nullptr;  // triples (row, begin, end)
+    mutable fgpu::DevBuf<uint32_t> hub_chunks;  // triples (row, begin, end)
     mutable uint32_t n_hub_chunks = 0;
     // finer list for the fused push levels (rows >= PUSH_HUB_DEG in PUSH_HUB_CHUNK-edge items): a frontier of a
     // few hundred near-hub rows must spread over the whole chip, not over frontier/4 workgroups
-    mutable uint32_t* push_chunks = nullptr;
+    mutable fgpu::DevBuf<uint32_t> push_chunks;
     mutable uint32_t n_push_chunks = 0;
     mutable uint32_t max_deg = 0;
     mutable std::atomic<bool> finalized{false};       // hub list / max_deg computed (mat_finalize); merges leave it to the first BFS plan
-    mutable uint32_t* pull_col = nullptr; // bfs.hip: column ids with every row reordered hub-first, for the pull levels (lazy, owned)
-    mutable uint32_t* wordrow = nullptr;  // merge.hip: stored-row index of entry 64 w, for w in [0, ceil(nnz/64)] (lazy, owned)
-    mutable fgpu_tiles* tiles = nullptr;  // built on demand by fgpu_mat_build_tiles; owned by the matrix
+    mutable fgpu::DevBuf<uint32_t> pull_col; // bfs.hip: column ids with every row reordered hub-first, for the pull levels (lazy)
+    mutable fgpu::DevBuf<uint32_t> wordrow;  // merge.hip: stored-row index of entry 64 w, for w in [0, ceil(nnz/64)] (lazy)
     // fgpu_bfs (the one-call entry): the plan of the last (this, At) search is kept on the adjacency so that repeated calls
     // do not pay plan creation (pinned allocations, events, head array: 1.3 ms of a 2.2 ms call at RMAT-22).  `bfs_mu`
     // serialises its users; the transpose remembers which adjacency holds a plan over it (one at a time) so that releasing
@@ -354,19 +364,19 @@ struct fgpu_mat {
     mutable uint64_t bfs_plan_epoch = 0;
     mutable struct fgpu_ctx* bfs_plan_ctx = nullptr;   // the context whose one cached plan this is
     mutable const fgpu_mat* bfs_cached_in = nullptr;
-    // bit-parallel expansion (bitexpand.hip): cached pattern transpose of this matrix, and (on that
-    // transpose) its rows cut into items of <= 256 entries
-    mutable fgpu_mat* tcache = nullptr;
-    mutable uint32_t* bp_items = nullptr;  // triples (row, begin, end | split << 31)
+    // bit-parallel expansion (bitexpand.hip), on the cached transpose: its rows cut into items of <= 256 entries
+    mutable fgpu::DevBuf<uint32_t> bp_items;  // triples (row, begin, end | split << 31)
     mutable uint32_t n_bp_items = 0;
-    mutable uint32_t* bp_sitems = nullptr; // the items of split rows only (rows of more than BP_ITEM entries)
+    mutable fgpu::DevBuf<uint32_t> bp_sitems; // the items of split rows only (rows of more than BP_ITEM entries)
     mutable uint32_t n_bp_sitems = 0;
-    mutable uint64_t* bp_split_bits = nullptr;  // on the cached transpose: bit v set <=> row v is cut into several items
-    mutable fgpu::PrParts* pr_parts = nullptr;  // pagerank.hip: this matrix split into 8 column ranges (one per XCD), lazily, owned
-    mutable fgpu::BpXPlan* bp_xplan[4] = {nullptr, nullptr, nullptr, nullptr};   // on the cached transpose: the XCD-partitioned
-                                               // layout of the dense count hop, one per (expand_xp_direct, expand_xp_dense) pair —
-                                               // index direct + 2 x dense (bitpart.hip, built on the first such hop under that pair;
-                                               // released by bp_xplan_release)
+    mutable fgpu::DevBuf<uint64_t> bp_split_bits;  // on the cached transpose: bit v set <=> row v is cut into several items
+    // the sub-objects
+    mutable fgpu::MatRef tcache;               // cached pattern transpose of this matrix (mat_cached_transpose)
+    mutable std::unique_ptr<fgpu_tiles> tiles; // built on demand by tiles_build
+    mutable std::unique_ptr<fgpu::PrParts, fgpu::PrPartsDelete> pr_parts;  // pagerank.hip: this matrix split into column ranges, lazily
+    mutable fgpu::BpXPlanPtr bp_xplan[4];      // on the cached transpose: the XCD-partitioned layout of the dense count hop, one per
+                                               // (expand_xp_direct, expand_xp_dense) pair — index direct + 2 x dense (bitpart.hip,
+                                               // built on the first such hop under that pair)
     bool is_hyper() const { return hrows != nullptr; }
 };
 
@@ -375,20 +385,19 @@ struct fgpu_mat {
 // [c << tile_bits, (c+1) << tile_bits); inside a tile entries are grouped by 64 consecutive rows
 // (one output word) and cut into items of at most 64*vec*k entries.
 struct fgpu_tiles {
-    fgpu_ctx* ctx = nullptr;
     uint32_t tile_bits = 0, ntiles = 0, ngroups = 0, nitems = 0;
     uint32_t vec = 4, k = 1;         // entries per lane per load, loads per lane per item
     uint64_t nentries = 0;           // padded
-    uint32_t* item_off = nullptr;    // nitems + 1
-    uint32_t* item_group = nullptr;  // nitems
-    uint32_t* entries = nullptr;     // packed: bits 0..25 column - tile base (bit tile_bits = pad), 26..31 row & 63
-    uint32_t* tile_item = nullptr;   // ntiles + 1 (device)
-    uint64_t* row_has = nullptr;     // ngroups words: bit set = row has at least one entry
+    fgpu::DevBuf<uint32_t> item_off;    // nitems + 1
+    fgpu::DevBuf<uint32_t> item_group;  // nitems
+    fgpu::DevBuf<uint32_t> entries;     // packed: bits 0..25 column - tile base (bit tile_bits = pad), 26..31 row & 63
+    fgpu::DevBuf<uint32_t> tile_item;   // ntiles + 1 (device)
+    fgpu::DevBuf<uint64_t> row_has;     // ngroups words: bit set = row has at least one entry
     // blocked layout (blocked.hip: output windows in LDS as well; what scales past RMAT-22): kind == 1
     uint32_t kind = 0;
     uint32_t bk_wbits = 0, bk_nwindows = 0, bk_nsplit = 1;
-    uint32_t* bk_seg_off = nullptr;  // nblocks + 1 block offsets (entries, multiples of 256)
-    uint32_t* bk_entries = nullptr;
+    fgpu::DevBuf<uint32_t> bk_seg_off;  // nblocks + 1 block offsets (entries, multiples of 256)
+    fgpu::DevBuf<uint32_t> bk_entries;
 };
 
 namespace fgpu {
@@ -466,14 +475,16 @@ fgpu_info compact_segments(fgpu_ctx* ctx, const u32* data, const u64* off, const
 // ---- matrix helpers (mat.hip) ---------------------------------------------------
 // free a snapshot no other thread has seen (temporaries, failed builds); fgpu_mat_free adds the cross-lane fence
 void mat_release(fgpu_mat* m);
-void bp_xplan_release(fgpu_ctx* ctx, BpXPlan* p);   // bitpart.hip
-void pr_parts_release(fgpu_ctx* ctx, PrParts* p);   // pagerank.hip
 void mat_drop_bfs_plan(const fgpu_mat* a);   // caller holds bfs_link_mu() and a->bfs_mu
 // One process-wide mutex orders every change of the (adjacency <-> transpose) plan links (bfs_plan / bfs_plan_at /
 // bfs_cached_in / fgpu_ctx::bfs_cache_owner): taken BEFORE any matrix' bfs_mu, released before a search runs.
 std::mutex& bfs_link_mu();
 fgpu_info mat_alloc(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, u64 nnz, bool with_vals,
                     u32 nvec_hyper, bool hyper);
+fgpu_info mat_alloc_vals(fgpu_ctx* ctx, fgpu_mat* m);   // the value array of a snapshot built pattern-first (its builder's own)
+// m's cached pattern transpose (fgpu_mat::tcache), built once per snapshot under m->idx_mu; _locked: the caller holds it
+fgpu_info mat_cached_transpose(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out);
+fgpu_info mat_cached_transpose_locked(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out);
 // (m \ dm) U dp, pattern only, on device (K3/K6).
 fgpu_info mat_merge_device(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, const fgpu_mat* dp,
                            const fgpu_mat* dm, bool dm_masks_dp);
@@ -523,12 +534,10 @@ fgpu_info comm_allreduce_sum_u32(fgpu_ctx* ctx, u32* buf, u64 n);
 fgpu_info comm_group_begin();   // ncclGroupStart / End around the calls of several ranks driven by one thread
 fgpu_info comm_group_end();
 
-void tiles_release(fgpu_tiles* t);
 // tiled.hip: build the LDS-tile layout of `m` (0 = automatic parameter) / run out = m (x) x & ~mask
 fgpu_info tiles_build(fgpu_ctx* ctx, const fgpu_mat* m, int tile_bits, int vec, int k, bool rebuild);
 fgpu_info blocked_build(fgpu_ctx* ctx, const fgpu_mat* m, CsrView mv, fgpu_tiles* t);
 fgpu_info blocked_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 x_words64, const u64* mask_dev, u64* out_dev);
-void blocked_release(fgpu_ctx* ctx, fgpu_tiles* t);
 fgpu_info tiles_mxv(fgpu_ctx* ctx, const fgpu_tiles* t, const u64* x_dev, u32 x_words64, const u64* mask_dev,
                     u64* out_dev, bool zero_out);
 

@@ -532,16 +532,12 @@ fgpu_info fgpu_ctx::d2h(void* host, const void* dev, size_t bytes) {
 fgpu_info fgpu_ctx::d2h_widen(uint64_t* host, const uint32_t* dev, size_t count) {
     if (dma_able(host, count * sizeof(u64))) {
         // widened by a kernel, then ONE DMA into the caller's pinned array: no host thread touches the entries
-        void* tmp = nullptr;
-        FGPU_TRY(dev_alloc(&tmp, count * sizeof(u64)));
-        fgpu_info i = fgpu::widen_on_device(this, (u64*)tmp, dev, count);
-        if (i == FGPU_OK && hipMemcpyAsync(host, tmp, count * sizeof(u64), hipMemcpyDeviceToHost, stream()) != hipSuccess) {
-            set_error("d2h_widen: hipMemcpyAsync failed");
-            i = FGPU_DEVICE;
-        }
-        if (i == FGPU_OK && hipStreamSynchronize(stream()) != hipSuccess) { set_error("d2h_widen: stream failed"); i = FGPU_DEVICE; }
-        dev_free(tmp);
-        return i;
+        fgpu::DevBuf<u64> tmp;
+        FGPU_TRY(tmp.alloc(this, count));
+        FGPU_TRY(fgpu::widen_on_device(this, tmp.p, dev, count));
+        FGPU_HIP(hipMemcpyAsync(host, tmp.p, count * sizeof(u64), hipMemcpyDeviceToHost, stream()));
+        FGPU_HIP(hipStreamSynchronize(stream()));
+        return FGPU_OK;
     }
     return d2h_loop(lane(), (const char*)dev, count, sizeof(u32), [&](const char* half, size_t first, size_t n) {
         const u32* s = (const u32*)half;

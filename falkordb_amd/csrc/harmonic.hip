@@ -331,10 +331,10 @@ extern "C" fgpu_info fgpu_harmonic(fgpu_ctx* ctx, const fgpu_mat* A, const uint6
             FGPU_TRY(launch(hc_rows_kernel, dim3(rgrid), dim3(256), 0, st, av, a, src, dst, (const uint8_t*)flag[cur],
                             flag[cur ^ 1], est, sc, n, t + j + 1, prev, c, work));
             if (nch) {
-                FGPU_TRY(launch(hc_hub_partial_kernel, dim3(hgrid), dim3(256), 0, st, (const u32*)A->hub_chunks, nch, av.colidx,
+                FGPU_TRY(launch(hc_hub_partial_kernel, dim3(hgrid), dim3(256), 0, st, (const u32*)A->hub_chunks.p, nch, av.colidx,
                                 a, src, (const uint8_t*)flag[cur], partial.p, prev, work));
                 FGPU_TRY(launch(hc_hub_fold_kernel, dim3(capped_grid(ctx, nch, 4, 8)), dim3(256), 0, st,
-                                (const u32*)A->hub_chunks, nch, av.rowptr, a, src, dst, (const uint4*)partial.p, flag[cur ^ 1],
+                                (const u32*)A->hub_chunks.p, nch, av.rowptr, a, src, dst, (const uint4*)partial.p, flag[cur ^ 1],
                                 est, sc, t + j + 1, prev, c, work));
             }
             cur ^= 1;

@@ -50,25 +50,13 @@ void mat_release(fgpu_mat* m) {
             m->bfs_cached_in = nullptr;
         }
     }
-    fgpu_ctx* c = m->ctx;
-    if (c) {
+    if (fgpu_ctx* c = m->ctx) {
         c->dev_free(m->rowptr);
         c->dev_free(m->colidx);
         c->dev_free(m->vals);
         c->dev_free(m->hrows);
-        c->dev_free(m->hub_chunks);
-        c->dev_free(m->push_chunks);
-        c->dev_free(m->wordrow);
-        c->dev_free(m->pull_col);
     }
-    tiles_release(m->tiles);
-    if (c) c->dev_free(m->bp_items);
-    if (c) c->dev_free(m->bp_sitems);
-    if (c) c->dev_free(m->bp_split_bits);
-    for (fgpu::BpXPlan* xp : m->bp_xplan) if (xp) bp_xplan_release(c, xp);
-    if (m->pr_parts) pr_parts_release(c, m->pr_parts);
-    if (m->tcache) mat_release(m->tcache);
-    delete m;
+    delete m;   // every index and sub-object frees itself (the order: above fgpu_mat's members)
 }
 
 fgpu_info mat_alloc(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, u64 nnz, bool with_vals, u32 nvec_hyper,
@@ -87,10 +75,29 @@ fgpu_info mat_alloc(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, u64 nnz
     m->nvec = hyper ? nvec_hyper : (u32)nrows;
     FGPU_TRY(ctx->dev_alloc((void**)&m->rowptr, ((size_t)m->nvec + 1) * sizeof(u32)));
     FGPU_TRY(ctx->dev_alloc((void**)&m->colidx, (size_t)(nnz ? nnz : 1) * sizeof(u32)));
-    if (with_vals) FGPU_TRY(ctx->dev_alloc((void**)&m->vals, (size_t)(nnz ? nnz : 1) * sizeof(u64)));
+    if (with_vals) FGPU_TRY(mat_alloc_vals(ctx, m.get()));
     if (hyper) FGPU_TRY(ctx->dev_alloc((void**)&m->hrows, (size_t)(m->nvec ? m->nvec : 1) * sizeof(u32)));
     *out = m.release();
     return FGPU_OK;
+}
+
+fgpu_info mat_alloc_vals(fgpu_ctx* ctx, fgpu_mat* m) {
+    return ctx->dev_alloc((void**)&m->vals, (size_t)(m->nnz ? m->nnz : 1) * sizeof(u64));
+}
+
+fgpu_info mat_cached_transpose_locked(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out) {
+    if (!m->tcache.get()) {
+        MatRef t;
+        FGPU_TRY(mat_transpose_pattern(ctx, &t.m, m));
+        FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+        m->tcache = std::move(t);
+    }
+    *out = m->tcache.get();
+    return FGPU_OK;
+}
+fgpu_info mat_cached_transpose(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out) {
+    std::lock_guard<std::mutex> idx_guard(m->idx_mu);
+    return mat_cached_transpose_locked(ctx, m, out);
 }
 
 // max degree + static hub chunk list (rows with >= HUB_DEG entries).
@@ -120,7 +127,7 @@ __global__ void hub_scan_kernel(const u32* __restrict__ rowptr, u32 nvec, u32* _
     }
 }
 
-static fgpu_info build_hub_list(const fgpu_mat* m, u32 deg_min, u32 chunk, u32** out, u32* n_out) {
+static fgpu_info build_hub_list(const fgpu_mat* m, u32 deg_min, u32 chunk, DevBuf<u32>& out, u32* n_out) {
     fgpu_ctx* ctx = m->ctx;
     // every hub chunk holds >= 1 edge and at most nnz / chunk + (#hub rows) chunks exist
     u32 cap = (u32)(m->nnz / chunk + m->nnz / deg_min + 1);
@@ -137,8 +144,8 @@ static fgpu_info build_hub_list(const fgpu_mat* m, u32 deg_min, u32 chunk, u32**
     m->max_deg = h[0];
     *n_out = h[1] < cap ? h[1] : cap;
     if (*n_out) {
-        FGPU_TRY(ctx->dev_alloc((void**)out, (size_t)*n_out * 3 * sizeof(u32)));
-        FGPU_HIP(hipMemcpyAsync(*out, chunks.p, (size_t)*n_out * 3 * sizeof(u32), hipMemcpyDeviceToDevice,
+        FGPU_TRY(out.alloc(ctx, (size_t)*n_out * 3));
+        FGPU_HIP(hipMemcpyAsync(out.p, chunks.p, (size_t)*n_out * 3 * sizeof(u32), hipMemcpyDeviceToDevice,
                                 ctx->stream()));
     }
     return FGPU_OK;
@@ -150,10 +157,13 @@ fgpu_info mat_finalize(const fgpu_mat* m) {
     m->n_hub_chunks = 0;
     m->n_push_chunks = 0;
     if (m->nnz && m->nvec) {
-        FGPU_TRY(build_hub_list(m, HUB_DEG, HUB_CHUNK, &m->hub_chunks, &m->n_hub_chunks));
-        if (m->max_deg >= PUSH_HUB_DEG)
-            FGPU_TRY(build_hub_list(m, PUSH_HUB_DEG, PUSH_HUB_CHUNK, &m->push_chunks, &m->n_push_chunks));
-        FGPU_HIP(hipStreamSynchronize(m->ctx->stream()));   // the chunk copies are complete before the flag is raised
+        DevBuf<u32> hub, push;
+        u32 n_hub = 0, n_push = 0;
+        FGPU_TRY(build_hub_list(m, HUB_DEG, HUB_CHUNK, hub, &n_hub));
+        if (m->max_deg >= PUSH_HUB_DEG) FGPU_TRY(build_hub_list(m, PUSH_HUB_DEG, PUSH_HUB_CHUNK, push, &n_push));
+        FGPU_HIP(hipStreamSynchronize(m->ctx->stream()));   // the chunk copies are complete before the lists are moved in
+        m->hub_chunks = std::move(hub); m->n_hub_chunks = n_hub;
+        m->push_chunks = std::move(push); m->n_push_chunks = n_push;
     }
     m->finalized.store(true, std::memory_order_release);
     return FGPU_OK;

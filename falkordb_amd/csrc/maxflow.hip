@@ -634,7 +634,7 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     FGPU_HIP(hipMemsetAsync(newh.p, 0, (size_t)(nch ? nch : 1) * sizeof(u32), st));
     FGPU_TRY(launch(mf_net_kernel, dim3(capped_grid(ctx, m, 256, 8)), dim3(256), 0, st, view_of(R), m, view_of(C), (const u64*)C->vals,
                     cap.p, r.p, rev.p));
-    if (nch) FGPU_TRY(launch(mf_hfirst_kernel, dim3(cdiv(nch, 256)), dim3(256), 0, st, (const u32*)R->hub_chunks, nch, hfirst.p));
+    if (nch) FGPU_TRY(launch(mf_hfirst_kernel, dim3(cdiv(nch, 256)), dim3(256), 0, st, (const u32*)R->hub_chunks.p, nch, hfirst.p));
     MfRun s;
     s.ctx = ctx;
     s.g.rowptr = R->rowptr;
@@ -647,7 +647,7 @@ extern "C" fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src
     s.g.src = (u32)src;
     s.g.sink = (u32)sink;
     s.g.hmax = 2ull * n < 0xFFFFFFFEull ? 2 * n : 0xFFFFFFFEu;
-    s.hb.hub = R->hub_chunks;
+    s.hb.hub = R->hub_chunks.p;
     s.hb.hfirst = hfirst.p;
     s.hb.n_hub = nch;
     s.hb.bud = bud.p;

@@ -399,21 +399,17 @@ fgpu_info mat_wordrow(fgpu_ctx* ctx, const fgpu_mat* a, const u32** out) {
     *out = nullptr;
     if (a->nnz == 0) return FGPU_OK;
     std::lock_guard<std::mutex> idx_guard(a->idx_mu);
-    if (!a->wordrow) {
+    if (!a->wordrow.p) {
         const u32 nwords = (u32)((a->nnz + 63) >> 6);
-        u32* wr = nullptr;
-        FGPU_TRY(ctx->dev_alloc((void**)&wr, ((size_t)nwords + 1) * sizeof(u32)));
-        fgpu_info i = launch(wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)a->rowptr,
-                             a->nvec, nwords, wr);
-        // complete on the device before it is published: other lanes read it from their own streams
-        if (i == FGPU_OK && ctx->multi_lane()) i = fgpu_sync(ctx);
-        if (i != FGPU_OK) {
-            ctx->dev_free(wr);
-            return i;
-        }
-        a->wordrow = wr;
+        DevBuf<u32> wr;
+        FGPU_TRY(wr.alloc(ctx, (size_t)nwords + 1));
+        FGPU_TRY(launch(wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)a->rowptr, a->nvec,
+                        nwords, wr.p));
+        // complete on the device before it is moved in: other lanes read it from their own streams
+        if (ctx->multi_lane()) FGPU_TRY(fgpu_sync(ctx));
+        a->wordrow = std::move(wr);
     }
-    *out = a->wordrow;
+    *out = a->wordrow.p;
     return FGPU_OK;
 }
 
@@ -569,7 +565,7 @@ fgpu_info mat_from_device_coo_vals(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64
                                    const u32* cols, const u64* vals, u64 n) {
     MatRef a;
     FGPU_TRY(mat_from_device_coo(ctx, &a.m, nrows, ncols, rows, cols, n));   // dense row pointers
-    FGPU_TRY(ctx->dev_alloc((void**)&a->vals, (size_t)(a->nnz ? a->nnz : 1) * sizeof(u64)));
+    FGPU_TRY(mat_alloc_vals(ctx, a.get()));
     if (a->nnz) {
         DevBuf<u32> win;
         FGPU_TRY(win.alloc(ctx, a->nnz));
@@ -607,17 +603,13 @@ __global__ __launch_bounds__(256) void transpose_vals_kernel(Layer a, const u32*
 fgpu_info mat_transpose_vals(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a) {
     MatRef t;
     FGPU_TRY(mat_transpose_pattern(ctx, &t.m, a));
-    if (t->is_hyper()) {  // empty result: fgpu_mat_new form
-        FGPU_TRY(ctx->dev_alloc((void**)&t->vals, sizeof(u64)));
-    } else {
-        FGPU_TRY(ctx->dev_alloc((void**)&t->vals, (size_t)(t->nnz ? t->nnz : 1) * sizeof(u64)));
-        if (a->nnz) {
-            Layer la{};
-            FGPU_TRY(layer_of(ctx, a, la));
-            FGPU_TRY(launch(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la, (const u32*)t->rowptr,
-                            (const u32*)t->colidx, t->vals));
-            FGPU_TRY(fgpu_sync(ctx));
-        }
+    FGPU_TRY(mat_alloc_vals(ctx, t.get()));
+    if (!t->is_hyper() && a->nnz) {   // (hypersparse: the empty result, fgpu_mat_new form)
+        Layer la{};
+        FGPU_TRY(layer_of(ctx, a, la));
+        FGPU_TRY(launch(transpose_vals_kernel, dim3(entry_grid(ctx, la.nnz)), dim3(256), 0, ctx->stream(), la, (const u32*)t->rowptr,
+                        (const u32*)t->colidx, t->vals));
+        FGPU_TRY(fgpu_sync(ctx));
     }
     *out = t.release();
     return FGPU_OK;

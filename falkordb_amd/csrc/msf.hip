@@ -291,7 +291,7 @@ static fgpu_info msf_scan(fgpu_ctx* ctx, const MsfState& s) {
                     s.act, (const u32*)s.parent, n, s.done, s.rowmin, (const u64*)s.best_w, best, s.entries));
     if (W->n_hub_chunks)
         FGPU_TRY(launch((msf_hubs_kernel<VALUED, WPASS>), dim3(hub_grid(ctx, W)), dim3(256), 0, ctx->stream(),
-                        (const u32*)W->hub_chunks, W->n_hub_chunks, (const u32*)W->colidx, (const u64*)W->vals, s.act,
+                        (const u32*)W->hub_chunks.p, W->n_hub_chunks, (const u32*)W->colidx, (const u64*)W->vals, s.act,
                         (const u32*)s.parent, s.cdone, s.chunkmin, (const u64*)s.best_w, best, s.entries));
     return FGPU_OK;
 }

@@ -248,16 +248,12 @@ constexpr u32 PR_NPARTS = 4;      // a power of two that divides 8 (the XCDs)
 constexpr u32 PR_PSHIFT = 2;      // log2(PR_NPARTS)
 constexpr u32 PR_RB = 1024;       // rows per workgroup block
 struct PrParts {
-    u32* prp = nullptr;            // PR_NPARTS x (n + 1) offsets into pcol, range-major
-    u32* pcol = nullptr;           // column ids, range-major
+    DevBuf<u32> prp;               // PR_NPARTS x (n + 1) offsets into pcol, range-major
+    DevBuf<u32> pcol;              // column ids, range-major
     u32 pw = 0;                    // columns per range
     u32 n = 0;
 };
-void pr_parts_release(fgpu_ctx* ctx, PrParts* p) {
-    if (!p) return;
-    if (ctx) { ctx->dev_free(p->prp); ctx->dev_free(p->pcol); }
-    delete p;
-}
+void PrPartsDelete::operator()(PrParts* p) const { delete p; }
 
 // entries of row v in each column range (7 lower bounds in the sorted row)
 __global__ void pr_part_count_kernel(CsrView at, u32 n, u32 pw, u32* __restrict__ cnt) {
@@ -304,30 +300,29 @@ __global__ __launch_bounds__(256) void pr_part_fill_kernel(CsrView at, u32 n, u3
 
 static fgpu_info pr_parts_build(fgpu_ctx* ctx, const fgpu_mat* At, const PrParts** out) {
     std::lock_guard<std::mutex> idx_guard(At->idx_mu);
-    if (At->pr_parts) { *out = At->pr_parts; return FGPU_OK; }
+    if (At->pr_parts) { *out = At->pr_parts.get(); return FGPU_OK; }
     const u32 n = (u32)At->nrows;
-    PrParts* pp = new (std::nothrow) PrParts();
+    std::unique_ptr<PrParts, PrPartsDelete> pp(new (std::nothrow) PrParts());
     FGPU_REQUIRE(pp, FGPU_OOM, "out of host memory");
     pp->n = n;
     pp->pw = (u32)(((u64)At->ncols + PR_NPARTS - 1) / PR_NPARTS);
     if (pp->pw == 0) pp->pw = 1;
     const size_t words = (size_t)PR_NPARTS * (n + 1);
-    fgpu_info i = ctx->dev_alloc((void**)&pp->prp, (words + 1) * sizeof(u32));
-    if (i == FGPU_OK) i = ctx->dev_alloc((void**)&pp->pcol, (size_t)(At->nnz ? At->nnz : 1) * sizeof(u32));
-    if (i == FGPU_OK)
-        i = launch(pr_part_count_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, pp->prp);
+    FGPU_TRY(pp->prp.alloc(ctx, words + 1));
+    FGPU_TRY(pp->pcol.alloc(ctx, (size_t)At->nnz));
+    FGPU_TRY(launch(pr_part_count_kernel, dim3(cdiv((u64)n + 1, 256)), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, pp->prp.p));
     // one exclusive scan over the range-major counts IS the layout: range p's rows follow range p - 1's (the extra slot per
     // range holds 0, so prp[p][n] = prp[p + 1][0])
-    if (i == FGPU_OK) i = scan_u32(ctx, pp->prp, pp->prp, words, nullptr);
-    if (i == FGPU_OK && At->nnz) {
+    FGPU_TRY(scan_u32(ctx, pp->prp.p, pp->prp.p, words, nullptr));
+    if (At->nnz) {
         u32 grid = cdiv(n, 4);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        i = launch(pr_part_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, (const u32*)pp->prp, pp->pcol);
-        if (i == FGPU_OK) i = fgpu_sync(ctx);
+        FGPU_TRY(launch(pr_part_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(At), n, pp->pw, (const u32*)pp->prp.p,
+                        pp->pcol.p));
+        FGPU_TRY(fgpu_sync(ctx));
     }
-    if (i != FGPU_OK) { pr_parts_release(ctx, pp); if (i == FGPU_DEVICE) set_error("pagerank: column-range layout build failed"); return i; }
-    At->pr_parts = pp;
-    *out = pp;
+    *out = pp.get();
+    At->pr_parts = std::move(pp);
     return FGPU_OK;
 }
 
@@ -549,8 +544,8 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
             if (parts) {
                 if (timing) (void)hipEventRecord(ev[1], ctx->stream());
                 const u32 nblk = cdiv(n, PR_RB);
-                FGPU_TRY(launch(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp,
-                                (const u32*)parts->pcol, n, (const float*)w.p, ppart.p, (const int*)state.p));
+                FGPU_TRY(launch(pr_part_spmv_kernel, dim3(nblk * PR_NPARTS), dim3(256), 0, ctx->stream(), (const u32*)parts->prp.p,
+                                (const u32*)parts->pcol.p, n, (const float*)w.p, ppart.p, (const int*)state.p));
                 if (timing) (void)hipEventRecord(ev[2], ctx->stream());
                 FGPU_TRY(launch(pr_part_combine_kernel, dim3(cgrid), dim3(256), 0, ctx->stream(), (const double*)ppart.p,
                                 (const u64*)act.p, n, (const float*)scal.p, (const float*)tp, (const float*)d.p,
@@ -572,10 +567,10 @@ extern "C" fgpu_info fgpu_pagerank_status(fgpu_ctx* ctx, const fgpu_mat* A, cons
                             (const int*)state.p));
             if (timing) (void)hipEventRecord(ev[2], ctx->stream());
             if (At->n_hub_chunks) {
-                FGPU_TRY(launch(pr_hub_kernel, dim3(hub_grid(ctx, At)), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                FGPU_TRY(launch(pr_hub_kernel, dim3(hub_grid(ctx, At)), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks.p,
                                 At->n_hub_chunks, (const u32*)At->colidx, (const u64*)act.p, (const float*)w.p, hpart.p,
                                 (const int*)state.p));
-                FGPU_TRY(launch(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks,
+                FGPU_TRY(launch(pr_hub_finish_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u32*)At->hub_chunks.p,
                                 At->n_hub_chunks, (const u32*)At->rowptr, (const u64*)act.p, (const double*)hpart.p,
                                 (const float*)scal.p, (const float*)tp, rp, part2.p, (const int*)state.p));
             } else {

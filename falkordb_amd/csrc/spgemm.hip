@@ -1540,7 +1540,7 @@ struct fgpu_expand_stream {
     size_t cap = 0;                  // entries per slot
     struct Slot {
         void* host = nullptr;        // pinned, cap * width bytes
-        u64* wide = nullptr;         // device staging of the widened ids (width 8)
+        DevBuf<u64> wide;            // device staging of the widened ids (width 8)
         std::vector<u64> rowptr;     // relative offsets of the chunk's rows
         hipEvent_t ev = nullptr;
         u64 first = 0, nrows = 0;
@@ -1560,8 +1560,8 @@ static fgpu_info stream_enqueue(fgpu_expand_stream* s, int k) {
     for (u64 i = 0; i <= nr; ++i) sl.rowptr[i] = (u64)s->rp[first + i] - b;
     if (n) {
         if (s->width == 8) {
-            FGPU_TRY(fgpu::widen_on_device(s->ctx, sl.wide, s->r->colidx + b, n));
-            FGPU_HIP(hipMemcpyAsync(sl.host, sl.wide, n * 8, hipMemcpyDeviceToHost, s->st));
+            FGPU_TRY(fgpu::widen_on_device(s->ctx, sl.wide.p, s->r->colidx + b, n));
+            FGPU_HIP(hipMemcpyAsync(sl.host, sl.wide.p, n * 8, hipMemcpyDeviceToHost, s->st));
         } else {
             FGPU_HIP(hipMemcpyAsync(sl.host, s->r->colidx + b, n * 4, hipMemcpyDeviceToHost, s->st));
         }
@@ -1579,9 +1579,8 @@ fgpu_info fgpu_expand_stream_close(fgpu_expand_stream* s) {
     for (auto& sl : s->slot) {
         if (sl.ev) (void)hipEventDestroy(sl.ev);
         if (sl.host) ctx->host_free(sl.host);
-        if (sl.wide) ctx->dev_free(sl.wide);
     }
-    delete s;   // (and with it the result on the device)
+    delete s;   // (and with it the slots' device staging, then the result on the device)
     return FGPU_OK;
 }
 
@@ -1628,7 +1627,7 @@ fgpu_info fgpu_expand_stream_open(fgpu_ctx* ctx, const uint64_t* src_ids, uint64
             auto& sl = s->slot[k];
             sl.host = ctx->pinned_alloc((s->cap ? s->cap : 1) * s->width);
             if (!sl.host) { set_error("fgpu_expand_stream_open: pinned host memory exhausted"); i = FGPU_OOM; break; }
-            if (s->width == 8) i = ctx->dev_alloc((void**)&sl.wide, (s->cap ? s->cap : 1) * 8);
+            if (s->width == 8) i = sl.wide.alloc(ctx, s->cap);
             if (i == FGPU_OK && hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) != hipSuccess) {
                 set_error("fgpu_expand_stream_open: hipEventCreate failed");
                 i = FGPU_DEVICE;

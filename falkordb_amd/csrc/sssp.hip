@@ -487,7 +487,7 @@ extern "C" fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, d
             const u32 stamp = (u32)(step % 0xFFFFFFFEull) + 1u;   // never 0, what hubmark[] starts as
             FGPU_TRY(launch(sssp_rows_kernel, dim3(rgrid), dim3(256), 0, st, view_of(W), vals, d.p, ctl.p, ls, infar.p, hubmark.p, stamp));
             if (nch)
-                FGPU_TRY(launch(sssp_hubs_kernel, dim3(hub_grid(ctx, W)), dim3(256), 0, st, (const u32*)W->hub_chunks, nch,
+                FGPU_TRY(launch(sssp_hubs_kernel, dim3(hub_grid(ctx, W)), dim3(256), 0, st, (const u32*)W->hub_chunks.p, nch,
                                 (const u32*)W->colidx, vals, d.p, ctl.p, ls, infar.p, (const u32*)hubmark.p, stamp));
             FGPU_TRY(launch(sssp_control_kernel, dim3(1), dim3(1), 0, st, ctl.p));
             FGPU_TRY(launch(sssp_split_kernel, dim3(vgrid), dim3(256), 0, st, (const u64*)d.p, ctl.p, ls, infar.p));

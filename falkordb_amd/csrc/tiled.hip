@@ -35,23 +35,10 @@ struct TilesView {
 
 static TilesView view_of(const fgpu_tiles* t) {
     TilesView v;
-    v.item_off = t->item_off; v.item_group = t->item_group; v.entries = t->entries;
-    v.tile_item = t->tile_item; v.row_has = t->row_has;
+    v.item_off = t->item_off.p; v.item_group = t->item_group.p; v.entries = t->entries.p;
+    v.tile_item = t->tile_item.p; v.row_has = t->row_has.p;
     v.tile_bits = t->tile_bits; v.ntiles = t->ntiles; v.ngroups = t->ngroups; v.nitems = t->nitems;
     return v;
-}
-
-void tiles_release(fgpu_tiles* t) {
-    if (!t) return;
-    if (t->ctx) {
-        t->ctx->dev_free(t->item_off);
-        t->ctx->dev_free(t->item_group);
-        t->ctx->dev_free(t->entries);
-        t->ctx->dev_free(t->tile_item);
-        t->ctx->dev_free(t->row_has);
-        blocked_release(t->ctx, t);
-    }
-    delete t;
 }
 
 // ---------------------------------------------------------------------------------
@@ -441,14 +428,11 @@ fgpu_info tiles_build(fgpu_ctx* ctx, const fgpu_mat* m, int tile_bits, int vec, 
                 FGPU_TRY(dense_rowptr(ctx, m, drp));
                 bv.rowptr = drp.p; bv.hrows = nullptr; bv.nvec = (u32)m->nrows;
             }
-            fgpu_tiles* bt = new (std::nothrow) fgpu_tiles();
+            std::unique_ptr<fgpu_tiles> bt(new (std::nothrow) fgpu_tiles());
             FGPU_REQUIRE(bt, FGPU_OOM, "out of host memory");
-            bt->ctx = ctx;
             bt->ngroups = (u32)((m->nrows + 63) / 64);
-            fgpu_info bi = blocked_build(ctx, m, bv, bt);
-            if (bi != FGPU_OK) { tiles_release(bt); return bi; }
-            tiles_release(m->tiles);
-            m->tiles = bt;
+            FGPU_TRY(blocked_build(ctx, m, bv, bt.get()));
+            m->tiles = std::move(bt);   // (a rebuild: the old layout's arrays go now)
             return FGPU_OK;
         }
     }
@@ -486,46 +470,36 @@ fgpu_info tiles_build(fgpu_ctx* ctx, const fgpu_mat* m, int tile_bits, int vec, 
     FGPU_TRY(eoff.alloc(ctx, nslots + 1));
     FGPU_HIP(hipMemsetAsync(cnt_e.p + nslots, 0, sizeof(u32), ctx->stream()));
     FGPU_HIP(hipMemsetAsync(cnt_i.p + nslots, 0, sizeof(u32), ctx->stream()));
-    fgpu_tiles* t = new (std::nothrow) fgpu_tiles();
+    std::unique_ptr<fgpu_tiles> t(new (std::nothrow) fgpu_tiles());
     FGPU_REQUIRE(t, FGPU_OOM, "out of host memory");
-    t->ctx = ctx; t->tile_bits = (u32)tile_bits; t->ntiles = ntiles; t->ngroups = ngroups;
+    t->tile_bits = (u32)tile_bits; t->ntiles = ntiles; t->ngroups = ngroups;
     t->vec = (u32)vec; t->k = (u32)k;
-    fgpu_info info = FGPU_OK;
-    do {
-        if ((info = ctx->dev_alloc((void**)&t->row_has, (size_t)ngroups * sizeof(u64))) != FGPU_OK) break;
-        if ((info = ctx->dev_alloc((void**)&t->tile_item, ((size_t)ntiles + 1) * sizeof(u32))) != FGPU_OK) break;
-        u32 grid = cdiv(ngroups, 4);
-        if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
-        if ((info = launch(tiles_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits,
-                           ntiles, (u32)vec, cap, cnt_e.p, cnt_i.p, t->row_has)) != FGPU_OK) break;
-        if ((info = scan_u32_to_u64(ctx, cnt_e.p, eoff.p, nslots + 1, nullptr)) != FGPU_OK) break;
-        if ((info = scan_u32(ctx, cnt_i.p, ioff.p, nslots + 1, nullptr)) != FGPU_OK) break;
-        u64 total_e = 0;
-        u32 total_i = 0;
-        if ((info = read_u64(ctx, eoff.p + nslots, &total_e)) != FGPU_OK) break;
-        if ((info = read_u32(ctx, ioff.p + nslots, &total_i)) != FGPU_OK) break;
-        if (total_e + PAD_HEAD >= 0xFFFFFFFFull) {
-            set_error("tiles: %llu padded entries exceed the 32-bit offset space", (unsigned long long)total_e);
-            info = FGPU_INVALID;
-            break;
-        }
-        total_e += PAD_HEAD;
-        t->nentries = total_e;
-        t->nitems = total_i;
-        if ((info = ctx->dev_alloc((void**)&t->entries, (size_t)total_e * sizeof(u32))) != FGPU_OK) break;
-        if ((info = ctx->dev_alloc((void**)&t->item_off, ((size_t)total_i + 1) * sizeof(u32))) != FGPU_OK) break;
-        if ((info = ctx->dev_alloc((void**)&t->item_group, ((size_t)total_i + 1) * sizeof(u32))) != FGPU_OK) break;
-        if ((info = launch(tiles_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits,
-                           ntiles, (u32)vec, cap, (const u64*)eoff.p, (const u32*)ioff.p, t->entries, t->item_off,
-                           t->item_group)) != FGPU_OK) break;
-        if ((info = launch(tiles_finish_kernel, dim3(cdiv((u64)ntiles + 1, 64)), dim3(64), 0, ctx->stream(), (const u32*)ioff.p,
-                           (const u64*)eoff.p, ngroups, ntiles, (u32)tile_bits, t->tile_item, t->item_off,
-                           t->entries)) != FGPU_OK) break;
-        if (hipStreamSynchronize(ctx->stream()) != hipSuccess) { set_error("tiles build failed"); info = FGPU_DEVICE; break; }
-    } while (0);
-    if (info != FGPU_OK) { tiles_release(t); return info; }
-    tiles_release(m->tiles);
-    m->tiles = t;
+    FGPU_TRY(t->row_has.alloc(ctx, ngroups));
+    FGPU_TRY(t->tile_item.alloc(ctx, (size_t)ntiles + 1));
+    u32 grid = cdiv(ngroups, 4);
+    if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
+    FGPU_TRY(launch(tiles_count_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits, ntiles,
+                    (u32)vec, cap, cnt_e.p, cnt_i.p, t->row_has.p));
+    FGPU_TRY(scan_u32_to_u64(ctx, cnt_e.p, eoff.p, nslots + 1, nullptr));
+    FGPU_TRY(scan_u32(ctx, cnt_i.p, ioff.p, nslots + 1, nullptr));
+    u64 total_e = 0;
+    u32 total_i = 0;
+    FGPU_TRY(read_u64(ctx, eoff.p + nslots, &total_e));
+    FGPU_TRY(read_u32(ctx, ioff.p + nslots, &total_i));
+    FGPU_REQUIRE(total_e + PAD_HEAD < 0xFFFFFFFFull, FGPU_INVALID, "tiles: %llu padded entries exceed the 32-bit offset space",
+                 (unsigned long long)total_e);
+    total_e += PAD_HEAD;
+    t->nentries = total_e;
+    t->nitems = total_i;
+    FGPU_TRY(t->entries.alloc(ctx, (size_t)total_e));
+    FGPU_TRY(t->item_off.alloc(ctx, (size_t)total_i + 1));
+    FGPU_TRY(t->item_group.alloc(ctx, (size_t)total_i + 1));
+    FGPU_TRY(launch(tiles_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), mv, (u32)m->nrows, ngroups, (u32)tile_bits, ntiles,
+                    (u32)vec, cap, (const u64*)eoff.p, (const u32*)ioff.p, t->entries.p, t->item_off.p, t->item_group.p));
+    FGPU_TRY(launch(tiles_finish_kernel, dim3(cdiv((u64)ntiles + 1, 64)), dim3(64), 0, ctx->stream(), (const u32*)ioff.p,
+                    (const u64*)eoff.p, ngroups, ntiles, (u32)tile_bits, t->tile_item.p, t->item_off.p, t->entries.p));
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));
+    m->tiles = std::move(t);   // (a rebuild: the old layout's arrays go now)
     return FGPU_OK;
 }
 
@@ -543,7 +517,7 @@ fgpu_info fgpu_mat_build_tiles(fgpu_ctx* ctx, fgpu_mat* m, int tile_bits, int ve
 fgpu_info fgpu_mat_tiles_info(const fgpu_mat* m, uint64_t info[8]) {
     FGPU_REQUIRE(m && info, FGPU_NULL_POINTER, "fgpu_mat_tiles_info: NULL argument");
     FGPU_REQUIRE(m->tiles, FGPU_NO_VALUE, "matrix has no tiles");
-    const fgpu_tiles* t = m->tiles;
+    const fgpu_tiles* t = m->tiles.get();
     info[0] = t->tile_bits; info[1] = t->ntiles; info[2] = t->ngroups; info[3] = t->nitems;
     info[4] = t->nentries; info[5] = t->vec; info[6] = t->k;
     info[7] = (uint64_t)t->nentries * 4 + (uint64_t)t->nitems * 8 + (uint64_t)t->ngroups * 8;

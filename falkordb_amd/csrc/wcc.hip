@@ -182,7 +182,7 @@ static fgpu_info wcc_link_rows(fgpu_ctx* ctx, const fgpu_mat* m, const u64* act,
                     entries));
     ++*launches;
     if (m->n_hub_chunks) {
-        FGPU_TRY(launch(wcc_link_hubs_kernel, dim3(hub_grid(ctx, m)), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks,
+        FGPU_TRY(launch(wcc_link_hubs_kernel, dim3(hub_grid(ctx, m)), dim3(256), 0, ctx->stream(), (const u32*)m->hub_chunks.p,
                         m->n_hub_chunks, (const u32*)m->rowptr, (const u32*)m->colidx, act, parent, first, giant, entries));
         ++*launches;
     }
