@@ -163,6 +163,126 @@ static fgpu_info transposed_with_items(fgpu_ctx* ctx, const fgpu_mat* m, const f
 }
 
 // ---------------------------------------------------------------------------------
+// the rows of <= BP_ITEM entries as a packed item stream (bp_pull_groups_kernel<.., true, true>)
+// ---------------------------------------------------------------------------------
+// How the short rows of A' are cut into a wavefront's work is fixed per snapshot, and the group kernel derived it in every
+// pass: rowptr of 32 rows -> prefix scan -> the address of the column ids, a dependent round trip in front of the column loads
+// and a 5-step LDS search per entry behind them.  Here the cut is made once: an item is a run of consecutive whole rows
+// v0 .. v0 + r - 1 with r <= BP_GITEM_ROWS and at most BP_ITEM entries, cut greedily in vertex order (an item starts at the next
+// row that holds entries and takes rows while both limits hold; rows of more than BP_ITEM entries count zero, they are the item
+// kernel's; trailing empty rows are dropped).  Item i is a header of four words and a block of BP_ITEM column words at fixed
+// strides, so every address follows from i alone; a column word carries its row-in-item in bits 27..31, and the block's tail
+// holds BP_GITEM_PAD.  Column ids therefore stay below 2^27 - 1.
+// The cut runs on the host over the downloaded row pointers (one sequential pass: an item's first row depends on where the
+// previous one ended); the blocks are filled on the device.
+constexpr u32 BP_GITEM_ROWS = 32;
+constexpr u32 BP_GITEM_COL_BITS = 27;
+constexpr u32 BP_GITEM_COL_MASK = (1u << BP_GITEM_COL_BITS) - 1u;
+constexpr u32 BP_GITEM_PAD = 0xFFFFFFFFu;
+static_assert(BP_GITEM_ROWS == 32 && BP_GITEM_COL_BITS + 5 == 32, "bp_group_items: five row bits above the column id");
+
+// `hdr` (nullable: count only) receives (v0, r, entries, 0) per item; returns the number of items
+static size_t bp_gitems_cut(const u32* rowptr, u32 nrows, u32* hdr) {
+    size_t n = 0;
+    u32 v = 0;
+    while (v < nrows) {
+        u32 d = rowptr[v + 1] - rowptr[v];
+        if (d == 0 || d > BP_ITEM) { ++v; continue; }
+        const u32 v0 = v;
+        u32 cnt = 0, last = v;
+        while (v < nrows && v - v0 < BP_GITEM_ROWS) {
+            d = rowptr[v + 1] - rowptr[v];
+            if (d > BP_ITEM) d = 0;
+            if (cnt + d > BP_ITEM) break;
+            cnt += d;
+            if (d) last = v;
+            ++v;
+        }
+        if (hdr) { hdr[4 * n] = v0; hdr[4 * n + 1] = last - v0 + 1; hdr[4 * n + 2] = cnt; hdr[4 * n + 3] = 0; }
+        ++n;
+    }
+    return n;
+}
+
+// a wavefront per item: the rows' entries to the item's block, tagged with the row; the tail padded
+__global__ __launch_bounds__(256) void bp_gitems_fill_kernel(const u32* __restrict__ rowptr, const u32* __restrict__ colidx,
+                                                            const uint4* __restrict__ hdr, u32 nitems, u32* __restrict__ cols) {
+    const u32 lane = lane_id();
+    const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const u32 nwaves = (gridDim.x * 256) >> 6;
+    for (u32 it = wave; it < nitems; it += nwaves) {
+        const uint4 h = hdr[it];
+        const u32 v0 = h.x, r = h.y;
+        const u32 rp = rowptr[v0 + (lane < r ? lane : r)];   // (r <= 32 rows: lanes 0 .. r hold the r + 1 pointers)
+        const u32 rp1 = (u32)__shfl_down((int)rp, 1, 64);
+        u32 deg = lane < r ? rp1 - rp : 0u;
+        if (deg > BP_ITEM) deg = 0u;
+        u32 incl = deg;
+#pragma unroll
+        for (int d = 1; d < (int)BP_GITEM_ROWS; d <<= 1) {
+            const u32 t = (u32)__shfl_up((int)incl, d, 64);
+            if ((int)lane >= d) incl += t;
+        }
+        const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, BP_GITEM_ROWS - 1);
+        if (total > BP_ITEM) continue;   // (never: the host cut the items from the same row pointers)
+        u32* dst = cols + (size_t)it * BP_ITEM;
+        for (u32 j = 0; j < r; ++j) {
+            const u32 b = (u32)__shfl((int)rp, (int)j, 64), d = (u32)__shfl((int)deg, (int)j, 64);
+            const u32 o = (u32)__shfl((int)(incl - deg), (int)j, 64);
+            for (u32 q = lane; q < d; q += 64) dst[o + q] = colidx[b + q] | (j << BP_GITEM_COL_BITS);
+        }
+        for (u32 q = total + lane; q < BP_ITEM; q += 64) dst[q] = BP_GITEM_PAD;
+    }
+}
+
+static fgpu_info bp_gitems_build(fgpu_ctx* ctx, const fgpu_mat* t, DevBuf<u32>& hdr, DevBuf<u32>& cols, u32* n_out) {
+    const u32 nrows = (u32)t->nrows;
+    std::unique_ptr<u32[]> rp(new (std::nothrow) u32[(size_t)nrows + 1]);
+    FGPU_REQUIRE(rp, FGPU_OOM, "out of host memory");
+    FGPU_TRY(ctx->d2h(rp.get(), t->rowptr, ((size_t)nrows + 1) * sizeof(u32)));
+    const size_t n = bp_gitems_cut(rp.get(), nrows, nullptr);
+    FGPU_REQUIRE(n < (1ull << 22), FGPU_INVALID, "bp_group_items: %zu items", n);   // (x 256 column words: a 32-bit index)
+    std::unique_ptr<u32[]> h(new (std::nothrow) u32[4 * (n ? n : 1)]);
+    FGPU_REQUIRE(h, FGPU_OOM, "out of host memory");
+    bp_gitems_cut(rp.get(), nrows, h.get());
+    FGPU_TRY(hdr.alloc(ctx, 4 * (n ? n : 1)));
+    FGPU_TRY(cols.alloc(ctx, (n ? n : 1) * (size_t)BP_ITEM));
+    if (n) {
+        FGPU_TRY(ctx->h2d(hdr.p, h.get(), 4 * n * sizeof(u32)));
+        u32 grid = cdiv(n, 4);
+        if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
+        FGPU_TRY(launch(bp_gitems_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)t->rowptr, (const u32*)t->colidx,
+                        (const uint4*)hdr.p, (u32)n, cols.p));
+    }
+    FGPU_TRY(fgpu_sync(ctx));
+    *n_out = (u32)n;
+    return FGPU_OK;
+}
+
+// The packed items of `t`, the cached transpose of `m`, built on first use under m->idx_mu.  An optional accelerator like the
+// partitioned plan (bitpart.hip bp_xplan): when it does not apply (column ids of 2^27 - 1 and more) or its build fails, the
+// half-built arrays are freed, the index is marked not usable, the error is dropped and the hop runs the 32-row groups.
+static fgpu_info bp_group_items(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, bool* usable) {
+    std::lock_guard<std::mutex> idx_guard(m->idx_mu);
+    if (!t->bp_gitems_state) {
+        DevBuf<u32> hdr, cols;
+        u32 n = 0;
+        const bool fits = t->ncols < (u64)BP_GITEM_COL_MASK && t->nrows < 0xFFFFFFC0ull && t->nnz < 0x7FFFFFFFull;
+        if (fits && bp_gitems_build(ctx, t, hdr, cols, &n) == FGPU_OK) {
+            t->n_bp_gitems = n;
+            t->bp_gitem_hdr = std::move(hdr);
+            t->bp_gitem_cols = std::move(cols);
+            t->bp_gitems_state = 1;
+        } else {
+            if (fits) { (void)hipGetLastError(); set_error("%s", ""); }
+            t->bp_gitems_state = -1;
+        }
+    }
+    *usable = t->bp_gitems_state > 0;
+    return FGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------
 // F -> X
 // ---------------------------------------------------------------------------------
 // Entry-parallel: F has few rows (a batch of <= a few thousand sources) but after a hop or two its rows hold
@@ -557,7 +677,13 @@ constexpr u32 BP_GROUP_WAVES = 16;  // wavefronts per workgroup at most: they sh
 // REC: `rec` holds a record for every vertex (bp_records_kernel) and answers the fine probe itself — an entry that passes
 // the LDS map loads rec[u]: ~0ull = not live, source indices = OR-ed into the row's accumulator by the lane that loaded
 // them, BP_REC_ESC = compacted into the list for the row gathers.  pr.bits is not read.
-template <int LN, bool REC>
+// PK (with REC): the packed item stream of bp_group_items instead of the 32-row groups.  A wavefront takes an item: its header
+// (wave-uniform) and its four column loads go out together from addresses computed from the item's index, the row of an
+// entry is bits 27..31 of its column word — no rowptr / prefix scan in front of the column ids, no offsets search behind
+// them — and yperm / next_rowptr / later_bits, asked for when the header is there, are used by the flush alone.
+// (Tried and dropped: the NEXT item's header and column words requested behind the current item's record loads and consumed
+// an iteration later — 240.9 us a launch against 228.4 without, profiles/NOTES_r17.md section 4.)
+template <int LN, bool REC, bool PK = false>
 __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(CsrView at, u32 nrows, const u64* __restrict__ x,
                                                                              BpProbe pr, u64* __restrict__ y,
                                                                              uint8_t* __restrict__ yflag,
@@ -565,7 +691,10 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
                                                                              unsigned long long* __restrict__ stats,
                                                                              const u64* __restrict__ later_bits,
                                                                              const u32* __restrict__ yperm /* nullable: row v of Y at slot yperm[v] */,
-                                                                             const u64* __restrict__ rec /* REC: bp_records_kernel's form of X */) {
+                                                                             const u64* __restrict__ rec /* REC: bp_records_kernel's form of X */,
+                                                                             const uint4* __restrict__ ghdr, const u32* __restrict__ gcols,
+                                                                             u32 ngitems /* PK: bp_group_items */) {
+    static_assert(!PK || REC, "bp_pull_groups_kernel: the packed items are read through records");
     // stats (nullable, with next_rowptr): [0] += popcount(Y[v]) * out-degree of v in the next hop's matrix, [1] += rows
     // written — what bp_flops / bp_count_flags would find in a pass of their own.  Rows flagged in `later_bits`
     // (nullable: destinations of a delta layer, whose rows change after this kernel) are left to bp_split_stats_kernel.
@@ -589,6 +718,102 @@ __global__ __launch_bounds__(BP_GROUP_WAVES * 64) void bp_pull_groups_kernel(Csr
     const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
     const u32 ngroups = (nrows + R - 1) / R;
     const u64 below = (1ull << lane) - 1ull;
+    if constexpr (PK) {
+        for (u32 it = wave; it < ngitems; it += nwaves) {
+            const uint4 h = ghdr[it];
+            u32 cw[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) cw[k] = gcols[(size_t)it * BP_ITEM + 64 * k + lane];
+            const u32 v0 = (u32)__builtin_amdgcn_readfirstlane((int)h.x);
+            const u32 r = (u32)__builtin_amdgcn_readfirstlane((int)h.y);   // rows of the item, 1 .. 32
+            // what the flush needs of the item's rows, requested now and off the chain: the next hop's out-degrees, the slots
+            // in Y, and the rows that are summed later (32 rows from any v0: two words of the bitmap, which has a spare one)
+            // (a null array is replaced by one that is there and its word dropped: a load under a wave-uniform branch makes hipcc
+            // count the loads in flight for the worse case, and the wait for the first column word then covers the later ones)
+            const u32 ri = v0 + lane < nrows ? v0 + lane : nrows;
+            const u32 nrp_w = (stats ? next_rowptr : at.rowptr)[ri];
+            const u32 yp_w = (yperm ? yperm : at.rowptr)[ri < nrows ? ri : nrows - 1u];
+            const u32 nrp = stats ? nrp_w : 0u, yp = yperm ? yp_w : ri;
+            const u64 lw0 = later_bits ? later_bits[v0 >> 6] : 0ull, lw1 = later_bits ? later_bits[(v0 >> 6) + 1u] : 0ull;
+            // (every load above is issued before the first column word is looked at)
+            __builtin_amdgcn_sched_barrier(0);
+            u32 un[4], rw[4];
+            bool sv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool in = cw[k] != BP_GITEM_PAD;
+                un[k] = in ? cw[k] & BP_GITEM_COL_MASK : 0xFFFFFFFFu;
+                rw[k] = cw[k] >> BP_GITEM_COL_BITS;
+                const u32 cb = (in ? cw[k] & BP_GITEM_COL_MASK : 0u) >> pr.cshift;
+                sv[k] = in & (((s_co[cb >> 5] >> (cb & 31)) & 1u) != 0u);   // (no `&&`: it is a branch per trip)
+            }
+            u64 rc[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rc[k] = rec[sv[k] ? un[k] : 0u];
+            u32 n_live = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!sv[k]) rc[k] = ~0ull;
+                const bool esc = rc[k] == BP_REC_ESC;
+                const u64 em = __ballot(esc);
+                if (esc) list[n_live + (u32)__popcll(em & below)] = ((u64)rw[k] << 32) | un[k];
+                n_live += (u32)__popcll(em);
+                if (!esc) {
+                    u64* arow = acc + (size_t)rw[k] * LN;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const u32 sid = (u32)(rc[k] >> (16 * j)) & 0xFFFFu;
+                        if (sid < 0xFFFEu) atomicOr((unsigned long long*)&arow[sid >> 6], 1ull << (sid & 63u));
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (u32 i0 = 0; i0 < n_live; i0 += 4 * SLOTS) {
+                u64 pu[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const u32 i = i0 + k * SLOTS + slot;
+                    pu[k] = (i < n_live) ? list[i] : ~0ull;
+                }
+                u64 xv[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const u64 xr = x[(size_t)(pu[k] != ~0ull ? (u32)pu[k] : 0u) * LN + wl];
+                    xv[k] = (pu[k] != ~0ull) ? xr : 0ull;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (xv[k]) atomicOr((unsigned long long*)&acc[(u32)(pu[k] >> 32) * LN + wl], (unsigned long long)xv[k]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // flush of the item's r rows: SLOTS rows per step, a row's LN words on LN consecutive lanes
+            const u32 ndeg = (u32)__shfl_down((int)nrp, 1, 64) - nrp;
+            const u32 sh = v0 & 63u;
+            const u32 later = (u32)((lw0 >> sh) | ((lw1 << 1) << (63u - sh)));
+            for (u32 r0 = 0; r0 < r; r0 += SLOTS) {
+                const u32 row = r0 + slot;
+                const u64 a = row < r ? acc[row * LN + wl] : 0ull;
+                const u32 yrow = (u32)__shfl((int)yp, (int)(row < r ? row : 0u), 64);
+                if (a) {
+                    y[(size_t)yrow * LN + wl] = a;
+                    acc[row * LN + wl] = 0ull;
+                }
+                const u64 nzm = __ballot(a != 0ull);
+                const u64 mine = LN == 64 ? nzm : (nzm >> (slot * LN)) & ((1ull << (LN % 64)) - 1ull);
+                if (wl == 0 && mine) yflag[v0 + row] = 1;
+                if (stats) {   // (wave-uniform)
+                    const u32 dg = (u32)__shfl((int)ndeg, (int)(row < r ? row : 0u), 64);
+                    const bool now = row < r && !((later >> row) & 1u);
+                    if (now && mine && wl == 0) st_rows += 1;
+                    if (now) st_flops += (u64)__popcll(a) * dg;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    } else
     for (u32 g = wave; g < ngroups; g += nwaves) {
         const u32 v0 = g * R;
         const u32 ri = v0 + lane < nrows ? v0 + lane : nrows;
@@ -1426,6 +1651,7 @@ struct HopPlan {
     bool sparse;               // fewer than 1 row in 8 flagged: a flag probe per neighbour first beats gathering 8 W-byte rows
     bool groups;               // ... by row groups: rows of <= BP_ITEM entries by bp_pull_groups_kernel, the split rows' items after
     bool use_rec;              // ... reading records of <= 4 source indices (bp_records_kernel) instead of a flag bit, then the row
+    bool gitems;               // ... the rows of <= BP_ITEM entries from the packed item stream (bp_group_items), not by 32-row groups
     bool fuse_stats;           // ... summing the next hop's traversed-edge count and the flagged rows on the way
     const BpXPlan* xp;         // the counting hop runs in its XCD-partitioned form (bitpart.hip) under this plan
     bool no_touched;           // ... over clean layers: the fold completes every row — no bitmap, prefix, side buffer or read-back
@@ -1472,6 +1698,11 @@ static fgpu_info bp_hop_plan(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* m
     FGPU_REQUIRE(!m->nnz || p.sparse || !s.lazy, FGPU_INVALID, "bit-parallel hop: a lazily zeroed state needs the sparse pull");
     p.groups = p.sparse && mode == 0 && s.ws <= 16 && ctx->opt.expand_row_groups;
     p.use_rec = p.groups && ctx->opt.expand_records && s.nsrc < 0xFFFEu;
+    if (p.use_rec && ctx->opt.expand_group_items) {
+        bool usable = false;
+        FGPU_TRY(bp_group_items(ctx, m, p.t, &usable));
+        p.gitems = usable;
+    }
     // (the next matrix must be plain CSR over the same vertices; rows a delta fix-up changes after the pull are summed after it)
     p.fuse_stats = p.groups && next_m && !next_m->is_hyper() && next_m->nrows == m->ncols;
     // the sparse form, rows wider than 128 bytes, 8-byte rows and mid-chain hops keep the plain pull
@@ -1594,10 +1825,15 @@ static fgpu_info bp_pull_group_rows(fgpu_ctx* ctx, const HopPlan& p, const BitSt
     const size_t lds = pm.lds + gwaves * per_wave;
     u32 wgs = (u32)((size_t)ctx->opt.lds_limit / lds);
     if (wgs * gwaves > 32) wgs = 32 / gwaves;
-    return pick<1, 2, 4, 8, 16>((int)s.ws, [&](auto ln) { return pick(recs != nullptr, [&](auto rec) {
-        return launch(bp_pull_groups_kernel<decltype(ln)::value, decltype(rec)::value>, dim3((u32)ctx->cus * wgs), dim3(gwaves * 64), lds,
+    // the kernel's form: 0 = flag bits, 1 = records, 2 = records over the packed items
+    const int form = !recs ? 0 : p.gitems ? 2 : 1;
+    if (form == 2) ctx->group_item_launches.fetch_add(1, std::memory_order_relaxed);
+    return pick<1, 2, 4, 8, 16>((int)s.ws, [&](auto ln) { return pick<0, 1, 2>(form, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return launch(bp_pull_groups_kernel<decltype(ln)::value, (F >= 1), (F == 2)>, dim3((u32)ctx->cus * wgs), dim3(gwaves * 64), lds,
                       ctx->stream(), view_of(p.t), (u32)p.t->nrows, s.x.p, pm.pr, out.y, out.flag, p.fuse_stats ? next_m->rowptr : nullptr,
-                      (unsigned long long*)st.sums.p, st.later.p, p.operm, recs);
+                      (unsigned long long*)st.sums.p, st.later.p, p.operm, recs, (const uint4*)p.t->bp_gitem_hdr.p,
+                      (const u32*)p.t->bp_gitem_cols.p, form == 2 ? p.t->n_bp_gitems : 0u);
     }); });
 }
 
@@ -2127,3 +2363,30 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
 }
 
 }  // namespace fgpu
+
+using namespace fgpu;
+
+fgpu_info fgpu_mat_group_items(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** hdr, uint32_t** cols, uint64_t* nitems) {
+    FGPU_REQUIRE(ctx && m && hdr && cols && nitems, FGPU_NULL_POINTER, "fgpu_mat_group_items: NULL argument");
+    *hdr = *cols = nullptr;
+    *nitems = 0;
+    FGPU_REQUIRE(m->nnz, FGPU_NO_VALUE, "fgpu_mat_group_items: the matrix is empty");
+    const fgpu_mat* t = nullptr;
+    FGPU_TRY(transposed_with_items(ctx, m, &t));
+    bool usable = false;
+    FGPU_TRY(bp_group_items(ctx, m, t, &usable));
+    FGPU_REQUIRE(usable, FGPU_NO_VALUE, "fgpu_mat_group_items: the transpose has no packed items (column ids of 2^27 - 1 and more, or the build failed)");
+    const size_t n = t->n_bp_gitems;
+    uint32_t* h = (uint32_t*)ctx->result_alloc((n ? n : 1) * 4 * sizeof(uint32_t));
+    uint32_t* c = (uint32_t*)ctx->result_alloc((n ? n : 1) * (size_t)BP_ITEM * sizeof(uint32_t));
+    if (!h || !c) {
+        if (h) ctx->host_free(h);
+        if (c) ctx->host_free(c);
+        FGPU_REQUIRE(false, FGPU_OOM, "out of host memory");
+    }
+    fgpu_info i = n ? ctx->d2h(h, t->bp_gitem_hdr.p, n * 4 * sizeof(uint32_t)) : FGPU_OK;
+    if (i == FGPU_OK && n) i = ctx->d2h(c, t->bp_gitem_cols.p, n * (size_t)BP_ITEM * sizeof(uint32_t));
+    if (i != FGPU_OK) { ctx->host_free(h); ctx->host_free(c); return i; }
+    *hdr = h; *cols = c; *nitems = n;
+    return FGPU_OK;
+}

@@ -162,6 +162,7 @@ struct fgpu_ctx {
     std::atomic<uint64_t> msf_round_entries[32] = {};   // the last fgpu_msf call: entries read in round k, the rounds past 31 in [31] ("msf_last_entries_round<k>")
     std::atomic<int64_t> sssp_last_delta{0};   // the last fgpu_sssp call: log2 of its bucket width, 1024 = one bucket ("sssp_last_delta_log2")
     std::atomic<uint64_t> expand_launches{0};   // kernels launched by fgpu_expand* (fgpu_get_option "expand_kernel_launches")
+    std::atomic<uint64_t> group_item_launches{0};   // launches of bp_pull_groups_kernel in its packed-item forms ("expand_group_item_launches")
     // kernel profiler (measurement hook): off unless fgpu_prof_enable(ctx, 1)
     bool prof_on = false;
     std::mutex prof_mu;
@@ -370,6 +371,13 @@ struct fgpu_mat {
     mutable fgpu::DevBuf<uint32_t> bp_sitems; // the items of split rows only (rows of more than BP_ITEM entries)
     mutable uint32_t n_bp_sitems = 0;
     mutable fgpu::DevBuf<uint64_t> bp_split_bits;  // on the cached transpose: bit v set <=> row v is cut into several items
+    // ... and its rows of <= BP_ITEM entries packed into self-describing items (bp_group_items, built on the first mid-chain hop
+    // that reads records): item i = bp_gitem_hdr[4 i ..] = (first row, rows <= 32, entries <= 256, 0) and the 256 column words
+    // bp_gitem_cols[256 i ..], row-in-item in bits 27..31, the tail 0xFFFFFFFF.  bp_gitems_state: 0 not built, 1 usable, -1 the
+    // build failed or does not apply (no second attempt per snapshot)
+    mutable fgpu::DevBuf<uint32_t> bp_gitem_hdr, bp_gitem_cols;
+    mutable uint32_t n_bp_gitems = 0;
+    mutable int bp_gitems_state = 0;
     // the sub-objects
     mutable fgpu::MatRef tcache;               // cached pattern transpose of this matrix (mat_cached_transpose)
     mutable std::unique_ptr<fgpu_tiles> tiles; // built on demand by tiles_build

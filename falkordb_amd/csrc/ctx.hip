@@ -813,6 +813,8 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     if (const OptRow* r = opt_find(name)) { *value = opt_load(ctx->opt, *r); return FGPU_OK; }
     if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }
     if (!strcmp(name, "sssp_last_delta_log2")) { *value = ctx->sssp_last_delta.load(std::memory_order_relaxed); return FGPU_OK; }
+    if (!strcmp(name, "expand_group_items")) { *value = ctx->opt.expand_group_items; return FGPU_OK; }
+    if (!strcmp(name, "expand_group_item_launches")) { *value = (int64_t)ctx->group_item_launches.load(std::memory_order_relaxed); return FGPU_OK; }
     for (const CounterRow& c : COUNTERS)
         if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
     if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32) {
@@ -835,6 +837,11 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
                      "fgpu_set_option: sssp_delta_log2 must be %d .. %d or %d (auto), not %lld", SSSP_DELTA_MIN, SSSP_DELTA_MAX,
                      SSSP_DELTA_AUTO, (long long)value);
         ctx->opt.sssp_delta_log2 = (int)value;
+        return FGPU_OK;
+    }
+    if (!strcmp(name, "expand_group_items")) {   // set and read by name, like sssp_delta_log2: not a row of the table (options.hpp)
+        FGPU_REQUIRE(value >= 0 && value <= 1, FGPU_INVALID, "fgpu_set_option: expand_group_items must be 0 or 1, not %lld", (long long)value);
+        ctx->opt.expand_group_items = (int)value;
         return FGPU_OK;
     }
     const OptRow* r = opt_find(name);

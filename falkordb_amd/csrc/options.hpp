@@ -83,6 +83,12 @@ struct fgpu_options {  // fgpu_set_option
     int sssp_delta_log2 = 4096; // fgpu_sssp: the bucket width is 2^value, SSSP_DELTA_AUTO = derived on the device from the mean finite
                                // weight and the mean degree (sssp.hip).  Set and read by name in ctx.hip, not a row of the table below:
                                // the table is pinned row for row by tests/test_options_cpu.py
+    int expand_group_items = 1; // sparse mid-chain pull through records, the rows of <= 256 entries: 0 = a wavefront per 32-row group
+                               // derives the cut of its rows in every pass (rowptr -> prefix scan -> column ids), 1 = a wavefront per
+                               // ITEM of the packed stream built once per snapshot (bitexpand.hip bp_group_items: <= 32 whole rows,
+                               // <= 256 entries, the row of an entry in bits 27..31 of its column word; A/B: 277 -> 228 us a launch at
+                               // RMAT-22, profiles/NOTES_r17.md).
+                               // By name in ctx.hip like sssp_delta_log2, for the same reason
 };
 constexpr int SSSP_DELTA_AUTO = 4096, SSSP_DELTA_MIN = -1074, SSSP_DELTA_MAX = 1023;
 

@@ -252,6 +252,15 @@ class Mat:
         vals = self.ctx._take(vv, nnz.value) if vv else None
         return rowptr, colidx, vals
 
+    def group_items(self):
+        """The packed items of the cached transpose (fgpu_mat_group_items): hdr as (n, 4), cols as (n, 256), both uint32."""
+        hp, cp = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        check(self.ctx.lib.fgpu_mat_group_items(self.ctx._h, self._h, C.byref(hp), C.byref(cp), C.byref(n)))
+        hdr = self.ctx._take(hp, max(n.value, 1) * 4, np.uint32)[: n.value * 4].reshape(-1, 4)
+        cols = self.ctx._take(cp, max(n.value, 1) * 256, np.uint32)[: n.value * 256].reshape(-1, 256)
+        return hdr, cols
+
     def extract(self, min_row=0, max_row=2**64 - 1):
         lib = self.ctx.lib
         r, c, v = u64p(), u64p(), u64p()

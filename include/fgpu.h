@@ -262,6 +262,15 @@ fgpu_info fgpu_mat_build_tiles(fgpu_ctx* ctx, fgpu_mat* m, int tile_bits, int ve
 /* info[0]=tile_bits [1]=tiles [2]=64-row groups [3]=items [4]=padded entries [5]=vec [6]=k
  * [7]=device bytes of the index.  FGPU_NO_VALUE when the matrix has no tiles. */
 fgpu_info fgpu_mat_tiles_info(const fgpu_mat* m, uint64_t info[8]);
+/* The packed item stream the sparse mid-chain pull of fgpu_expand* reads the rows of at most 256 entries of m's cached
+ * transpose from (built here if no hop has built it yet): item i is hdr[4 i ..] = (first row, rows 1 .. 32, entries <= 256, 0)
+ * and the 256 words cols[256 i ..], each a column id in bits 0..26 under its row-in-item in bits 27..31, the tail 0xFFFFFFFF.
+ * Items hold whole consecutive rows, cut greedily in row order; rows of more than 256 entries count as empty.  Both arrays are
+ * released with fgpu_free.  FGPU_NO_VALUE when the matrix is empty or the stream does not apply (2^27 - 1 columns or more).
+ * Which form of the pull runs is the option expand_group_items (fgpu_set_option / fgpu_get_option, 0 or 1, kept out of their
+ * lists above because it is stored by name): 0 = a wavefront per 32-row group, 1 = a wavefront per packed item (A/B);
+ * fgpu_get_option reads expand_group_item_launches, the launches of the packed form so far. */
+fgpu_info fgpu_mat_group_items(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** hdr, uint32_t** cols, uint64_t* nitems);
 
 /* ---- products (ANY_PAIR structural semiring) ------------------------------ */
 
