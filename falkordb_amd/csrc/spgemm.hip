@@ -453,6 +453,7 @@ static fgpu_info first_hop_rows(fgpu_ctx* ctx, const fgpu_mat* f, const fgpu_mat
     const bool sum_next = next && !next->is_hyper() && next->nnz && nnz;
     fgpu_info i = FGPU_OK;
     {
+        ProfScope ps(ctx, "first_hop_copy_kernel", 4 * ((u64)k + 1) + 8 * (u64)nnz);   // the row pointers, every entry read + written
         u32 grid = cdiv(nnz ? nnz : 1, 256 * 4);
         if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
         i = launch(first_hop_copy_kernel, dim3(grid ? grid : 1), dim3(256), 0, ctx->stream(), view_of(f), view_of(m), k,
@@ -662,9 +663,12 @@ static fgpu_info first_hop_rows_dirty(fgpu_ctx* ctx, const fgpu_mat* f, const fg
     if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
     FGPU_HIP(hipMemsetAsync(keepm.p + ncm, 0, sizeof(u32), st));
     FGPU_HIP(hipMemsetAsync(keepp.p + ncp, 0, sizeof(u32), st));
-    FGPU_TRY(launch(fhd_cand_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p, (const u32*)cp.p,
-                    ncm, ncp, keepm.p, keepp.p, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr, (u32*)nullptr,
-                    (const u32*)nullptr, 0u, (unsigned long long*)nullptr));
+    {
+        ProfScope ps(ctx, "fhd_cand_kernel", 0);
+        FGPU_TRY(launch(fhd_cand_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, st, vf, vm, vdp, vdm, k, (const u32*)cm.p, (const u32*)cp.p,
+                        ncm, ncp, keepm.p, keepp.p, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr, (u32*)nullptr,
+                        (const u32*)nullptr, 0u, (unsigned long long*)nullptr));
+    }
     FGPU_TRY(scan_u32(ctx, keepm.p, pm.p, (u64)ncm + 1, nullptr));
     FGPU_TRY(scan_u32(ctx, keepp.p, pp.p, (u64)ncp + 1, nullptr));
     DevBuf<u32> rp;
@@ -797,8 +801,11 @@ static fgpu_info compact_source_rows(fgpu_ctx* ctx, const fgpu_mat* f, fgpu_mat*
     u32 grid = cdiv((u64)k + 1, 256);
     const u32 want = cdiv(f->nnz, 256 * 8);
     if (grid < want) grid = want < (u32)ctx->cus * 4 ? want : (u32)ctx->cus * 4;
-    FGPU_TRY(launch(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
-                    (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive));
+    {
+        ProfScope ps(ctx, "cr_build_kernel", 12 * ((u64)k + 1) + 8 * (u64)f->nnz);   // row pointers, ranks, map; the entries read + written
+        FGPU_TRY(launch(cr_build_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)f->rowptr, (const u32*)f->colidx, k,
+                        (u32)f->nnz, (const u32*)rank.p, c->rowptr, c->colidx, map.p, nlive));
+    }
     rank_out = std::move(rank);        // rank[i] = live rows before source row i, rank[k] = nlive: the way back (bp_to_csr)
     *out = c.release();
     return FGPU_OK;
