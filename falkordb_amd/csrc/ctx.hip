@@ -814,6 +814,7 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }
     if (!strcmp(name, "sssp_last_delta_log2")) { *value = ctx->sssp_last_delta.load(std::memory_order_relaxed); return FGPU_OK; }
     if (!strcmp(name, "expand_group_items")) { *value = ctx->opt.expand_group_items; return FGPU_OK; }
+    if (!strcmp(name, "spdag_sides")) { *value = ctx->opt.spdag_sides; return FGPU_OK; }
     if (!strcmp(name, "expand_group_item_launches")) { *value = (int64_t)ctx->group_item_launches.load(std::memory_order_relaxed); return FGPU_OK; }
     for (const CounterRow& c : COUNTERS)
         if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
@@ -842,6 +843,11 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "expand_group_items")) {   // set and read by name, like sssp_delta_log2: not a row of the table (options.hpp)
         FGPU_REQUIRE(value >= 0 && value <= 1, FGPU_INVALID, "fgpu_set_option: expand_group_items must be 0 or 1, not %lld", (long long)value);
         ctx->opt.expand_group_items = (int)value;
+        return FGPU_OK;
+    }
+    if (!strcmp(name, "spdag_sides")) {   // by name, like sssp_delta_log2: not a row of the table (options.hpp)
+        FGPU_REQUIRE(value >= 0 && value <= 3, FGPU_INVALID, "fgpu_set_option: spdag_sides must be 0 .. 3, not %lld", (long long)value);
+        ctx->opt.spdag_sides = (int)value;
         return FGPU_OK;
     }
     const OptRow* r = opt_find(name);

@@ -89,6 +89,10 @@ struct fgpu_options {  // fgpu_set_option
                                // <= 256 entries, the row of an entry in bits 27..31 of its column word; A/B: 277 -> 228 us a launch at
                                // RMAT-22, profiles/NOTES_r17.md).
                                // By name in ctx.hip like sssp_delta_log2, for the same reason
+    int spdag_sides = 0;        // fgpu_shortest_dag: which ball grows.  0 = the side whose frontier has fewer entries to scan (ties
+                               // forward), 1 = forward only, 2 = backward only, 3 = strict alternation starting forward.  Every
+                               // setting returns the same length and pairs, only the stats differ (spdag.hip; the tests hold the
+                               // two-sided search to the one-sided ones).  By name in ctx.hip like sssp_delta_log2, for the same reason
 };
 constexpr int SSSP_DELTA_AUTO = 4096, SSSP_DELTA_MIN = -1074, SSSP_DELTA_MAX = 1023;
 

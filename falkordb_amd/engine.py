@@ -646,6 +646,23 @@ def sssp(ctx: Context, W: Mat, src: int, want_parent: bool = True, stats: bool =
     return dist, parent
 
 
+def shortest_dag(ctx: Context, A: Mat, At: Mat | None, src: int, dst: int, max_hops: int = -1, stats: bool = False):
+    """fgpu_shortest_dag: the shortest-path DAG between src and dst over the pattern A (At its transpose, None = built for the
+    call) — what allShortestPaths' predecessor walk reads.  src == dst asks for the shortest cycle through src.  Returns
+    (length, from uint64[k], to uint64[k], depth uint64[k]) — length -1 and empty arrays when no path of at most max_hops
+    (< 0: unbounded) exists, else the pairs (u, v) with an entry u -> v on some shortest path, sorted by (from, to), depth =
+    d(src, from) — and, when stats=True, a fifth item: the eight counters [forward levels, backward levels, vertices claimed
+    forward, claimed backward, entries scanned by the expansions, by the sweeps, meeting vertices, DAG vertices]."""
+    f, t, d = u64p(), u64p(), u64p()
+    k = C.c_uint64()
+    length = C.c_int64()
+    st = np.zeros(8, dtype=np.uint64) if stats else None
+    check(ctx.lib.fgpu_shortest_dag(ctx._h, A._h, At._h if At else None, C.c_uint64(src), C.c_uint64(dst), C.c_int64(max_hops),
+                                    C.byref(length), C.byref(k), C.byref(f), C.byref(t), C.byref(d), _p(st)))
+    out = (length.value, ctx._take(f, k.value), ctx._take(t, k.value), ctx._take(d, k.value))
+    return out + ([int(x) for x in st],) if stats else out
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

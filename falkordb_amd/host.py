@@ -498,6 +498,21 @@ class Graph:
         rows = [(f[i], t[i], p[offs[i]:offs[i + 1]] if emit_path else None) for i in range(k)]
         return rows, {"frames": int(st[0]), "pruned": int(st[1]), "reach_products": int(st[2])}
 
+    def all_shortest_paths(self, src, dst, types=(), bidirectional=False, reversed=False, max_hops=None, limit=0):
+        """AllShortestPathsOp over one input row (all_shortest_paths.rs:82-303): (length, [[relationship id, ...], ...]) — the
+        shortest paths of allShortestPaths((src)-[:types*..max_hops]->(dst)) in the reference's emission order, src / dst the
+        pattern's from / to node (src == dst: the shortest cycles); length -1 and no path when dst is out of reach.  limit > 0
+        stops after that many paths."""
+        oe, off = u64p(), u64p()
+        n, length = C.c_uint64(), C.c_int64()
+        _ck(self.L.fh_all_shortest_paths(self.h, ",".join(types).encode(), 1 if bidirectional else 0, 1 if reversed else 0,
+                                         C.c_uint32(0xFFFFFFFF if max_hops is None else max_hops), C.c_uint64(src),
+                                         C.c_uint64(dst), C.c_uint64(limit), C.byref(length), C.byref(oe), C.byref(off),
+                                         C.byref(n)))
+        offs = _take(off, n.value + 1).tolist()
+        e = _take(oe, offs[-1]).tolist()
+        return length.value, [e[offs[i]:offs[i + 1]] for i in range(n.value)]
+
     def build_adjacency(self, types=(), symmetric=False):
         """Graph::build_adjacency_matrix / build_symmetric_adjacency_matrix (graph.rs:3870-3907) -> Matrix"""
         h = C.c_void_p()

@@ -593,6 +593,30 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
     });
 }
 
+// AllShortestPathsOp over one input row: the paths flattened as relationship ids plus n_paths + 1 offsets
+int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops, uint64_t src,
+                          uint64_t dst, uint64_t limit, int64_t* length, uint64_t** edges, uint64_t** path_off, uint64_t* n_paths) {
+    return guard([&] {
+        AllShortestPathsOp op;
+        op.types = csv(types);
+        op.bidirectional = bidirectional != 0;
+        op.reversed = reversed != 0;
+        op.max_hops = max_hops;
+        int64_t len = -1;
+        const std::vector<std::vector<u64>> paths = timed([&] { return op.expand_row(g->g, src, dst, limit, &len); });
+        std::vector<u64> e, off{0};
+        for (auto& p : paths) {
+            e.insert(e.end(), p.begin(), p.end());
+            off.push_back(e.size());
+        }
+        *length = len;
+        *edges = hand(e);
+        *path_off = hand(off);
+        *n_paths = paths.size();
+        return 0;
+    });
+}
+
 // fh_algo_bfs and fh_algo_bfs_multi: one call but for the gang (nullptr: the graph's own context); only the single-context
 // entry is a timed operator
 static int algo_bfs_c(fh_graph* g, const std::vector<Context*>* gang, int64_t source, int64_t max_depth, const char* rel_type,

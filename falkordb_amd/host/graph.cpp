@@ -674,6 +674,98 @@ void ExpandIntoOp::expand_batch(const Graph& g, const std::vector<u64>& srcs, co
     for (size_t b = 0; b < back_row.size(); ++b) emit(back_row[b], k + b);
 }
 
+// ---- AllShortestPaths -----------------------------------------------------------------------------------
+std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64 src, u64 dst, u64 limit, int64_t* length) const {
+    std::vector<std::vector<u64>> out;
+    if (length) *length = -1;
+    const u64 n = g.node_cap();
+    if (src >= n || dst >= n || g.is_node_deleted(src) || g.is_node_deleted(dst)) return out;
+    const std::vector<u64> tids = resolve_types(g, types);               // (a name listed twice is walked twice: filter_map)
+    if (tids.empty()) return out;
+    Matrix adj = bidirectional ? g.build_symmetric_adjacency_matrix(types) : g.build_adjacency_matrix(types);
+    Matrix adj_t = bidirectional ? adj : adj.transpose();
+    int64_t L = -1;
+    u64 k = 0;
+    EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth)
+    check(fgpu_shortest_dag(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), src, dst, max_hops == UINT32_MAX ? -1 : (int64_t)max_hops,
+                            &L, &k, &dag.rows, &dag.cols, (uint64_t**)&dag.vals, nullptr),
+          "allShortestPaths");
+    dag.n = k;
+    if (L < 0) return out;
+    if (length) *length = L;
+    const bool cycle = src == dst;
+    // the relationships behind every pair, per type: (u, v), and (v, u) under a bidirectional pattern
+    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
+    std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
+    for (size_t t = 0; t < tids.size(); ++t) {
+        g.relationship_tensors()[tids[t]].get_batch(from, to, fwd[t]);
+        if (bidirectional) g.relationship_tensors()[tids[t]].get_batch(to, from, bwd[t]);
+    }
+    // the pairs are sorted by (from, to): the out-pairs of a vertex are one run
+    std::unordered_map<u64, std::pair<size_t, size_t>> run;
+    for (size_t i = 0; i < k;) {
+        size_t j = i;
+        while (j < k && from[j] == from[i]) ++j;
+        run[from[i]] = {i, j};
+        i = j;
+    }
+    // predecessor lists in the reference's order (:143-262 restricted to the DAG; see the comment in host.hpp).  Node 0 is
+    // src; the other DAG vertices get their node when first reached; in the cycle shape the closing pairs (u, src) lead
+    // to a node of their own, the end of the cycle
+    struct Pred { size_t prev; u64 edge; };
+    std::vector<u64> vertex{src};
+    std::vector<std::vector<Pred>> preds(1);
+    std::unordered_map<u64, size_t> node_of;
+    if (!cycle) node_of[src] = 0;
+    std::vector<size_t> level{0}, next;
+    for (int64_t d = 0; d < L; ++d) {
+        next.clear();
+        for (size_t cur : level) {
+            const auto r = run.find(vertex[cur]);
+            if (r == run.end()) continue;
+            auto reach = [&](size_t pair, const std::vector<u64>& ids) {
+                if (ids.empty()) return;
+                auto [it, fresh] = node_of.try_emplace(to[pair], vertex.size());
+                if (fresh) {
+                    vertex.push_back(to[pair]);
+                    preds.emplace_back();
+                    next.push_back(it->second);
+                }
+                for (u64 e : ids) preds[it->second].push_back({cur, e});
+            };
+            for (size_t t = 0; t < tids.size(); ++t) {
+                for (size_t p = r->second.first; p < r->second.second; ++p) reach(p, fwd[t][p]);          // outgoing by (dst, id)
+                if (bidirectional)
+                    for (size_t p = r->second.first; p < r->second.second; ++p)
+                        if (from[p] != to[p]) reach(p, bwd[t][p]);                                      // incoming by (src, id)
+            }
+        }
+        level.swap(next);
+    }
+    const auto end = node_of.find(dst);
+    if (end == node_of.end()) return out;
+    // the LIFO backtrack (:275-299)
+    std::vector<std::pair<size_t, std::vector<u64>>> stack;
+    stack.push_back({end->second, {}});
+    while (!stack.empty()) {
+        auto [node, path] = std::move(stack.back());
+        stack.pop_back();
+        if (node == 0) {
+            if (!cycle) std::reverse(path.begin(), path.end());
+            if (reversed) std::reverse(path.begin(), path.end());
+            out.push_back(std::move(path));
+            if (limit && out.size() >= limit) break;
+            continue;
+        }
+        for (const Pred& p : preds[node]) {
+            std::vector<u64> longer = path;
+            longer.push_back(p.edge);
+            stack.push_back({p.prev, std::move(longer)});
+        }
+    }
+    return out;
+}
+
 // ---- algo.BFS --------------------------------------------------------------------------------------------
 // The partitioned form of the search below: the adjacency is cut into nnz-balanced column slabs, one
 // per context of `gang` (one context per GPU; several contexts on one device work too and are how this is tested),

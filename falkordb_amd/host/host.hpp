@@ -542,6 +542,34 @@ struct CondVarLenTraverseOp {
                     VarLenStats* stats = nullptr) const;
 };
 
+// AllShortestPathsOp (runtime/ops/all_shortest_paths.rs:82-303): MATCH p = allShortestPaths((a)-[:types*..max]->(b)) with both
+// endpoints bound.  The reference runs a hash-map BFS from `src` that records every predecessor, then a lazy LIFO DFS from `dst`
+// over the predecessors.  Here the BFS is ONE fgpu_shortest_dag call over the pattern matrix — build_adjacency_matrix(types) and
+// its transpose, or build_symmetric_adjacency_matrix(types) for both when bidirectional — which returns exactly the
+// predecessor pairs the DFS can touch; their relationship ids come from batched tensor probes per type (Tensor::get_batch of
+// (u, v), and of (v, u) when bidirectional: no adjacency row of a hub is walked), and the predecessor lists are rebuilt on the
+// host in the reference's order: the DAG is walked level by level from src in queue order, per vertex in the adjacency order
+// of get_node_relationships_by_type (types in order; per type outgoing by (dst, id), then incoming by (src, id), a self-loop
+// once), every relationship of a multi-edge pair a predecessor entry of its own.
+// Why the vertices the device never reported are not needed for that order: the reference's queue holds every reached
+// vertex, but a vertex v of the DAG at depth d + 1 enters it when the FIRST vertex u at depth d with a relationship to v is
+// expanded, and such a u lies on a shortest path src .. u -> v .. dst: it is in the DAG itself.  So the relative queue order of
+// the DAG's vertices at a level depends only on the DAG's vertices one level up and on their adjacency order restricted to DAG
+// neighbours, by induction from src.
+// Edge-attribute filters need the attribute store (out of scope, as for the other operators); min_hops is always 1 (the
+// parser refuses anything else, cypher.rs:1324-1331); the shortestPath() function (eval.rs:1296-1400) is not served.
+struct AllShortestPathsOp {
+    std::vector<std::string> types;
+    bool bidirectional = false;
+    bool reversed = false;                 // AllShortestPaths::Reversed: the pattern is written right to left (:274, :286-288)
+    uint32_t max_hops = UINT32_MAX;        // UINT32_MAX = unbounded (:123)
+    // one input row, src / dst = the pattern's from / to node: the paths as relationship-id lists in the reference's emission
+    // sequence and per-path edge order (non-cycles src -> dst, reversed again under `reversed`; cycles keep the predecessor
+    // chain, :274-289).  limit > 0 stops after that many paths (the reference streams them: a diamond chain holds
+    // exponentially many).  *length (nullable) = the paths' length, -1 without one.
+    std::vector<std::vector<u64>> expand_row(const Graph& g, u64 src, u64 dst, u64 limit = 0, int64_t* length = nullptr) const;
+};
+
 struct BfsResult {
     bool has_row = false;
     std::vector<u64> nodes, edges;

@@ -172,6 +172,15 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
                         uint32_t min_hops, uint32_t max_hops, uint64_t start, int64_t dest, int emit_path, int prune,
                         uint64_t** out_from, uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n,
                         uint64_t stats[3]);
+/* AllShortestPathsOp, one input row (all_shortest_paths.rs:82-303): every shortest path of
+ * allShortestPaths((src)-[:types*..max_hops]->(dst)), src / dst = the pattern's from / to node, as relationship-id lists in the
+ * reference's emission sequence and per-path edge order.  types: a comma list ("" = all); bidirectional: the pattern has no
+ * arrow; reversed: it is written right to left (the lists are reversed once more); max_hops = UINT32_MAX: unbounded.
+ * src == dst asks for the shortest cycles through src.  The search is one fgpu_shortest_dag call (see fgpu.h); limit > 0 stops
+ * the enumeration after that many paths.  *length = the paths' length (-1: none); `edges` holds the paths back to back,
+ * `path_off` (n_paths + 1 offsets) cuts it; both are freed with fh_free.  Edge-attribute filters are not served. */
+int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops, uint64_t src,
+                          uint64_t dst, uint64_t limit, int64_t* length, uint64_t** edges, uint64_t** path_off, uint64_t* n_paths);
 /* source < 0 = NULL; rel_type NULL = all types.  `edges` holds one id per (parent, child) pair that HAS a
  * representative edge among the types, in node order; a pair without one is skipped in `edges` but its child stays in
  * `nodes` — exactly what the reference yields (algo_procedures.rs:1121-1150) — so the two lists are parallel only

@@ -612,6 +612,37 @@ fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src, uint64_t 
  * message instead of running on. */
 fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, double* dist, int64_t* parent, uint64_t stats[4]);
 
+/* The shortest-path DAG between two bound vertices: the numeric core of the reference's AllShortestPathsOp
+ * (runtime/ops/all_shortest_paths.rs:128-267, MATCH p = allShortestPaths((a)-[*]->(b))).  The reference runs a hash-map BFS per
+ * input row and a lazy DFS over the recorded predecessors; the DFS touches exactly the pairs returned here.
+ *   - A is the pattern of a square adjacency (values are ignored, a hypersparse A is accepted), At its transpose or NULL: the
+ *     call then builds the transpose for its own use and releases it.  Nothing is cached on either matrix.  An undirected
+ *     pattern -[*]- is the caller passing S = A U A' for both;
+ *   - max_hops < 0 is unbounded; max_hops == 0 gives no path;
+ *   - src != dst: L = the BFS distance from src to dst over A if it is at most max_hops (the reference's min_hops is always 1
+ *     here: cypher.rs:1324-1331).  Self-loops never matter;
+ *   - src == dst, the cycle shape (:209-235): L = 1 + the least d(src, u) over the in-neighbours u of src, u = src at distance
+ *     0 when src has a self-loop.  Over a symmetric pattern a single edge therefore closes a cycle of length 2, as the
+ *     reference's reuse of an edge in both directions does; there is no trail check.
+ * *length = L, or -1 when there is no path within the bound; then *n_pairs = 0 and the three arrays are NULL.  Otherwise
+ * from / to / depth (fgpu_free each) hold the *n_pairs pairs (u, v) with an entry u -> v and d(src, u) + 1 + d(v, dst) = L —
+ * in the cycle shape d(v, dst) = 0 for the closing pairs (u, src) — in ascending (from, to) order, each once, and
+ * depth[k] = d(src, from[k]) in 0 .. L - 1.  Repeated calls give identical arrays.
+ * The search is bidirectional and level-synchronous: it grows the ball whose frontier has fewer entries to scan, a whole level
+ * at a time, and stops at the first level whose new vertices the other ball already holds (spdag.hip).  The option spdag_sides
+ * (fgpu_set_option / fgpu_get_option, kept out of their name lists like expand_group_items): 0 that rule, 1 forward only,
+ * 2 backward only, 3 strict alternation starting forward; every setting returns the same length and arrays.
+ * stats (nullable): [0] forward levels expanded, [1] backward levels expanded (the cycle shape's first one included),
+ * [2] vertices claimed forward, [3] vertices claimed backward (seeds not counted), [4] entries scanned by the expansions,
+ * [5] entries scanned by the sweeps that collect the DAG, [6] meeting vertices, [7] DAG vertices (the cycle shape counts src
+ * at both ends).  [5] and [7] stay 0 without a path.
+ * Errors: NULL ctx / A / output pointer: FGPU_NULL_POINTER; non-square A or an At of other dimensions: FGPU_DIM_MISMATCH;
+ * src or dst >= nrows: FGPU_OUT_OF_BOUNDS; nrows >= 2^32 - 1 or nnz >= 2^32 - 1: FGPU_INVALID.  nrows == 0 gives no path.
+ * The call runs on the calling thread's lane: concurrent callers on the same matrices are independent. */
+fgpu_info fgpu_shortest_dag(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, uint64_t src, uint64_t dst, int64_t max_hops,
+                            int64_t* length, uint64_t* n_pairs, uint64_t** from, uint64_t** to, uint64_t** depth,
+                            uint64_t stats[8]);
+
 /* The smallest stored value of A under the order of fgpu_msf's K (the IEEE totalOrder with -0.0 = +0.0), as a binary64 bit
  * pattern (LAGraph_Cached_EMin).  *found = 0 when A has no entry; a BOOL snapshot answers 1.0.  A device reduction: no entry
  * visits the host. */

@@ -39,7 +39,13 @@
           stats, the reached vertices, the bucket width, and one fgpu_bfs and one full-pass vxm over the same pattern;
           sssp_sweep = the same under nine bucket widths around the derived one
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|all] [scale]
+  asp     allShortestPaths' core (fgpu_shortest_dag, bidirectional level-synchronous search + the DAG sweeps) on RMAT-22 (or
+          RMAT-<scale>), directed and symmetrised (A + A'), 64 (src, dst) pairs drawn at a fixed seed among the vertices with
+          an out- and an in-entry: per pair L, the DAG pairs, the eight stats and the ms per call under spdag_sides 0 (two-sided)
+          and 1 (forward only), median / min / max of 5 synchronised calls after 1 warm-up, and one fgpu_bfs (levels only) from
+          the same src; then one summary line per graph with the medians over the pairs and the ratios
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|asp|all] [scale]
 """
 import json
 import sys
@@ -472,6 +478,61 @@ def bench_sssp(ctx, scale, sweep=False):
     ctx.set_option("sssp_delta_log2", 4096)
 
 
+def bench_asp(ctx, scale, npairs=64):
+    """fgpu_shortest_dag between 64 seeded (src, dst) pairs of the R-MAT graph, directed (A, A') and symmetrised (S = A + A' for
+    both arguments), two-sided against forward-only, with fgpu_bfs from the same src for scale."""
+    def spread(fn, reps=5, warm=1):
+        for _ in range(warm):
+            r = fn()
+        ctx.sync()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            ctx.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts)), float(min(ts)), float(max(ts)), r
+
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    At = A.transpose()
+    S = A.merge_pattern(At, None)
+    n = A.nrows
+    level = ctx.host_array(n, np.int32)
+    for graph, M, Mt in (("directed", A, At), ("symmetrised", S, S)):
+        rp, _, _ = M.export_csr()
+        rpt, _, _ = Mt.export_csr()
+        live = np.nonzero((np.diff(rp.astype(np.int64)) > 0) & (np.diff(rpt.astype(np.int64)) > 0))[0]
+        rng = np.random.default_rng(0xA5B0 + scale)
+        picks = rng.choice(live, size=(npairs, 2))
+        rows = []
+        for src, dst in picks.tolist():
+            ctx.set_option("spdag_sides", 0)
+            t2, lo2, hi2, (L, f, _, _, st) = spread(lambda: engine.shortest_dag(ctx, M, Mt, src, dst, stats=True))
+            ctx.set_option("spdag_sides", 1)
+            t1, lo1, hi1, (L1, f1, _, _, st1) = spread(lambda: engine.shortest_dag(ctx, M, Mt, src, dst, stats=True))
+            assert L1 == L and len(f1) == len(f)
+            tb, lob, hib, _ = spread(lambda: engine.bfs(ctx, M, Mt, src, -1, want_parent=False, level_out=level), reps=3)
+            rows.append((t2, t1, tb))
+            print(json.dumps({"path": "asp", "graph": graph, "scale": scale, "src": src, "dst": dst, "L": L, "dag_pairs": len(f),
+                              "stats": st, "ms": round(t2, 3), "ms_min_max": [round(lo2, 3), round(hi2, 3)],
+                              "forward_only_ms": round(t1, 3), "forward_only_min_max": [round(lo1, 3), round(hi1, 3)],
+                              "forward_only_stats": st1, "bfs_ms": round(tb, 3), "bfs_min_max": [round(lob, 3), round(hib, 3)]}),
+                  flush=True)
+        ctx.set_option("spdag_sides", 0)
+        r = np.array(rows)
+        q = lambda x: [round(float(v), 3) for v in np.percentile(x, [25, 50, 75])]
+        print(json.dumps({"path": "asp_summary", "graph": graph, "scale": scale, "n": n, "nnz": M.nvals, "pairs": npairs,
+                          "ms_q25_q50_q75": q(r[:, 0]), "forward_only_ms_q25_q50_q75": q(r[:, 1]), "bfs_ms_q25_q50_q75": q(r[:, 2]),
+                          "two_sided_over_forward_only_q25_q50_q75": q(r[:, 0] / r[:, 1]),
+                          "two_sided_over_bfs_q25_q50_q75": q(r[:, 0] / r[:, 2]),
+                          "note": "host clock around a synchronised call; per pair the median of 5 after 1 warm-up (bfs: of 3), the "
+                                  "summary gives the quartiles over the 64 pairs; bfs = fgpu_bfs from src, levels only, on its cached "
+                                  "plan; no outside number exists to compare with"}), flush=True)
+    S.free()
+    At.free()
+    A.free()
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -558,6 +619,10 @@ if __name__ == "__main__":
     if what in ("sssp", "sssp_sweep", "all"):
         c = engine.Context(0)
         bench_sssp(c, scale if scale else 22, sweep=what == "sssp_sweep")
+        c.close()
+    if what in ("asp", "all"):
+        c = engine.Context(0)
+        bench_asp(c, scale if scale else 22)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
