@@ -48,6 +48,7 @@ SIGNATURES = {
     "fgpu_mat_build_tiles": (C.c_int32, [vp, vp, C.c_int, C.c_int, C.c_int]),
     "fgpu_mat_tiles_info": (C.c_int32, [vp, u64p]),
     "fgpu_mat_group_items": (C.c_int32, [vp, vp, C.POINTER(u32p), C.POINTER(u32p), u64p]),
+    "fgpu_mat_xp_chunks": (C.c_int32, [vp, vp, C.POINTER(u32p), u64p]),
     "fgpu_device_info": (C.c_int32, [vp, C.c_char_p, i32p, i32p, i64p, i64p]),
     "fgpu_device_bytes": (C.c_int32, [vp, u64p, u64p]),
     "fgpu_mat_new": (C.c_int32, [vp, vpp, C.c_uint64, C.c_uint64]),

@@ -2390,3 +2390,16 @@ fgpu_info fgpu_mat_group_items(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** hdr,
     *hdr = h; *cols = c; *nitems = n;
     return FGPU_OK;
 }
+
+fgpu_info fgpu_mat_xp_chunks(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** words, uint64_t* nwords) {
+    FGPU_REQUIRE(ctx && m && words && nwords, FGPU_NULL_POINTER, "fgpu_mat_xp_chunks: NULL argument");
+    *words = nullptr;
+    *nwords = 0;
+    FGPU_REQUIRE(m->nnz, FGPU_NO_VALUE, "fgpu_mat_xp_chunks: the matrix is empty");
+    const fgpu_mat* t = nullptr;
+    FGPU_TRY(transposed_with_items(ctx, m, &t));
+    const BpXPlan* xp = nullptr;
+    FGPU_TRY(bp_xplan(ctx, m, t, &xp));
+    FGPU_REQUIRE(xp, FGPU_NO_VALUE, "fgpu_mat_xp_chunks: the transpose has no partitioned plan (expand_xcd = 0, under 4096 entries, or the build failed)");
+    return bp_xplan_chunks(ctx, xp, words, nwords);
+}

@@ -48,6 +48,7 @@ struct BpXPlan;
 // the plan of `t` (= the cached transpose of m), built under m's index mutex on the first dense counting hop over it;
 // *out = nullptr when the partitioned form does not apply (option off, matrix too small / too wide, ids beyond 2^26)
 fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out);
+fgpu_info bp_xplan_chunks(fgpu_ctx* ctx, const BpXPlan* xp, uint32_t** out, uint64_t* nwords);   // the chunk table, read back
 const u32* bp_xplan_perm(const BpXPlan* p);   // slot of row u of X in the state the plan gathers from (nullptr: slot = u)
 // rows of Y = OR of the gathered rows of X, per vertex, counted / check-summed (mode 1 / 2) or — touched rows — stored into
 // their side-buffer slot; `side` is zeroed by the caller, the delta fix-ups and the side-row count follow in bp_hop_count

@@ -47,6 +47,7 @@ struct BpXPlan {
     // spread evenly (scrambled ids) — in every group of 64 vertex ids about 33 lanes do the index work, and then the look-ups, of
     // a row that is zero by construction.  The rows that HAVE an entry are ranked in vertex order, the group tables below are
     // built over 64 consecutive RANKS, and gvtx names the vertex of a slot where the fold needs it (hash, label, touched bit).
+    int cut = 0;                   // the chunk cut the plan was built under and HOLDS (1: whole double trips, xp_cut_cells; 0: the key cut)
     int dense = 0;                 // the form the plan was built under (0: group g = vertices 64 g .. 64 g + 63, gvtx stays null)
     u32 nd = 0;                    // rows of A' with at least one entry (dense form; ng = ceil(nd / 64))
     DevBuf<u32> gvtx;              // [ng * 64] vertex of slot 64 g + r, XP_NO_VTX past rank nd - 1 (a padded slot: no piece, no vertex)
@@ -195,6 +196,84 @@ __global__ void xp_chunks_kernel(const u32* __restrict__ off, const u32* __restr
     }
 }
 
+// ---- the cut on whole double trips (expand_xp_cut = 1) ----------------------------------------------------------------------------
+// The stream kernel consumes two trips of 64 entries per iteration, so a chunk of 128 k + r entries runs on copies of its last
+// entry for the 128 - r slots that are missing (bitpart.hip xp_stream_kernel).  Here every chunk but a partition's last holds a
+// multiple of 128 entries: a partition is counted off in CELLS of 128 entries and SUPER-CELLS of five cells from its first
+// entry; a super-cell that touches at most XP_RUNS runs (the rows of the tile) is one chunk, any other is cut into its cells.
+// With the single-entry runs taken out (expand_xp_direct = 1) a cell touches at most 65 runs; without, a cell may exceed the
+// tile, and such a plan keeps the key cut whole (xp_cut_cells reports it).  Almost every boundary now falls inside a run:
+// its pieces meet through cshared / zrows / atomic_or4 as the pieces of an in-hub's run always did.
+constexpr u32 XP_CELL = 128, XP_SUPER = 5;
+struct XpCells { u32 ps[9], cb[9], sb[9]; };   // first entry, first cell, first super-cell of partition k
+__device__ __forceinline__ u32 xp_part_of(const u32 (&base)[9], u32 i) {
+    u32 x = 0;
+#pragma unroll
+    for (u32 k = 1; k < 8; ++k) x += i >= base[k] ? 1u : 0u;
+    return x;
+}
+// a wavefront per cell: the run starts (XP_FIRST flags) among its entries, and whether its first entry is one
+__global__ __launch_bounds__(256) void xp_cell_flags_kernel(const u32* __restrict__ pcol, XpCells pc, u32* __restrict__ cnt,
+                                                            uint8_t* __restrict__ first) {
+    const u32 lane = lane_id();
+    const u32 wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    for (u32 c = wave; c <= pc.cb[8]; c += nwaves) {
+        u32 k = 0, f = 0;
+        if (c < pc.cb[8]) {
+            const u32 x = xp_part_of(pc.cb, c);
+            const u32 b = pc.ps[x] + XP_CELL * (c - pc.cb[x]), e = pc.ps[x + 1];
+            const u64 lo = __ballot(b + lane < e && (pcol[b + lane < e ? b + lane : b] & XP_FIRST));
+            const u64 hi = __ballot(b + 64 + lane < e && (pcol[b + 64 + lane < e ? b + 64 + lane : b] & XP_FIRST));
+            k = (u32)__popcll(lo) + (u32)__popcll(hi);
+            f = (u32)(lo & 1ull);
+        }
+        if (lane == 0) {
+            cnt[c] = k;                                      // (cnt[cells] = 0: the exclusive scan leaves the total there)
+            if (c < pc.cb[8]) first[c] = (uint8_t)f;
+        }
+    }
+}
+// runs a stretch of cells [c0, c1) touches: the run starts inside it, and the run its first entry continues
+__device__ __forceinline__ u32 xp_cells_touch(const u32* g, const uint8_t* first, u32 c0, u32 c1) { return g[c1] - g[c0] + (first[c0] ? 0u : 1u); }
+// a thread per super-cell: the chunks it becomes (1, or its cells), and the most runs any CELL that must stand alone touches
+__global__ void xp_super_count_kernel(const u32* __restrict__ g, const uint8_t* __restrict__ first, XpCells pc, u32* __restrict__ nch,
+                                      u32* __restrict__ worst) {
+    for (u32 s = blockIdx.x * 256 + threadIdx.x; s <= pc.sb[8]; s += gridDim.x * 256) {
+        u32 k = 0;
+        if (s < pc.sb[8]) {
+            const u32 x = xp_part_of(pc.sb, s);
+            const u32 c0 = pc.cb[x] + XP_SUPER * (s - pc.sb[x]), c1 = c0 + XP_SUPER < pc.cb[x + 1] ? c0 + XP_SUPER : pc.cb[x + 1];
+            k = 1;
+            if (xp_cells_touch(g, first, c0, c1) > XP_RUNS) {
+                k = c1 - c0;
+                u32 w = 0;
+                for (u32 c = c0; c < c1; ++c) w = max(w, xp_cells_touch(g, first, c, c + 1));
+                if (w > XP_RUNS) atomicMax(worst, w);
+            }
+        }
+        nch[s] = k;
+    }
+}
+// what the host needs of the two scans, in one read-back: the first chunk of partition k (k = 8: the chunks) and the worst cell
+__global__ void xp_cut_info_kernel(const u32* __restrict__ cbase, XpCells pc, const u32* __restrict__ worst, u32* __restrict__ info) {
+    if (threadIdx.x < 9) info[threadIdx.x] = cbase[pc.sb[threadIdx.x]];
+    if (threadIdx.x == 9) info[9] = *worst;
+}
+__global__ void xp_super_fill_kernel(const u32* __restrict__ g, const uint8_t* __restrict__ first, XpCells pc, const u32* __restrict__ cbase,
+                                     u32* __restrict__ cstart, u32* __restrict__ crun0, uint8_t* __restrict__ cshared) {
+    for (u32 s = blockIdx.x * 256 + threadIdx.x; s < pc.sb[8]; s += gridDim.x * 256) {
+        const u32 x = xp_part_of(pc.sb, s);
+        const u32 c0 = pc.cb[x] + XP_SUPER * (s - pc.sb[x]);
+        const u32 at = cbase[s], k = cbase[s + 1] - at;
+        for (u32 i = 0; i < k; ++i) {
+            const u32 c = c0 + i;
+            cstart[at + i] = pc.ps[x] + XP_CELL * (c - pc.cb[x]);
+            crun0[at + i] = g[c] + first[c] - 1u;            // run starts up to and including the chunk's first entry, less one
+            cshared[at + i] = first[c] ? 0 : 1;
+        }
+    }
+}
+
 // direct entries (expand_xp_direct = 1).  keep[p] = 0 when entry p is a run of its own: it opens a run and the next entry opens
 // another (a partition's first entry opens one) or the stream ends.  The exclusive scan of keep maps every position of the old
 // stream to the new one — of an entry that stays: its slot; of one that goes: the next staying entry's — so the run starts
@@ -260,9 +339,55 @@ __global__ void xp_rank_kernel(const u32* __restrict__ by_rank, u32 n, u32 prang
     for (u32 r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) perm[by_rank[r]] = (r & 7u) * prange + (r >> 3);
 }
 
-// builds the plan of `t` (= m') under one (direct, dense) pair; the caller holds m->idx_mu.  *out is set when the plan is
+// the chunk table of the cut on whole double trips.  hp = pstart[9] | cbase[9] | ..: fills cbase and the plan's three arrays and
+// sets *done — or leaves everything alone and *done false when a cell touches more runs than the tile has rows
+static fgpu_info xp_cut_cells(fgpu_ctx* ctx, BpXPlan* xp, u32 (&hp)[27], bool* done) {
+    *done = false;
+    hipStream_t st = ctx->stream();
+    XpCells pc;
+    pc.cb[0] = pc.sb[0] = 0;
+    for (int k = 0; k <= 8; ++k) pc.ps[k] = hp[k];
+    for (int k = 0; k < 8; ++k) {
+        const u32 len = hp[k + 1] - hp[k];
+        pc.cb[k + 1] = pc.cb[k] + cdiv(len, XP_CELL);
+        pc.sb[k + 1] = pc.sb[k] + cdiv(len, XP_CELL * XP_SUPER);
+    }
+    const u32 ncells = pc.cb[8], nsuper = pc.sb[8];
+    DevBuf<u32> g, nch, worst, info;
+    DevBuf<uint8_t> first;
+    FGPU_TRY(g.alloc(ctx, (size_t)ncells + 1));
+    FGPU_TRY(first.alloc(ctx, (size_t)ncells + 1));
+    FGPU_TRY(nch.alloc(ctx, (size_t)nsuper + 1));
+    FGPU_TRY(worst.alloc(ctx, 1));
+    FGPU_TRY(info.alloc(ctx, 10));
+    FGPU_HIP(hipMemsetAsync(worst.p, 0, sizeof(u32), st));
+    u32 grid = cdiv((u64)ncells + 1, 4);
+    if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
+    FGPU_TRY(launch(xp_cell_flags_kernel, dim3(grid), dim3(256), 0, st, (const u32*)xp->pcol.p, pc, g.p, first.p));
+    FGPU_TRY(scan_u32(ctx, g.p, g.p, (u64)ncells + 1, nullptr));
+    grid = cdiv((u64)nsuper + 1, 256);
+    FGPU_TRY(launch(xp_super_count_kernel, dim3(grid), dim3(256), 0, st, (const u32*)g.p, (const uint8_t*)first.p, pc, nch.p, worst.p));
+    FGPU_TRY(scan_u32(ctx, nch.p, nch.p, (u64)nsuper + 1, nullptr));
+    // one read-back: the first chunk of every partition (the scan at its first super-cell) and the worst cell
+    u32 got[10];
+    FGPU_TRY(launch(xp_cut_info_kernel, dim3(1), dim3(64), 0, st, (const u32*)nch.p, pc, (const u32*)worst.p, info.p));
+    FGPU_TRY(read_words(ctx, info.p, 10, got));
+    if (got[9] > XP_RUNS) return FGPU_OK;
+    for (int k = 0; k <= 8; ++k) hp[9 + k] = got[k];
+    xp->nchunks = hp[17];
+    FGPU_TRY(xp->cstart.alloc(ctx, ((size_t)xp->nchunks + 1)));   // (+ 1 as under the key cut: never an empty allocation)
+    FGPU_TRY(xp->crun0.alloc(ctx, ((size_t)xp->nchunks + 1)));
+    FGPU_TRY(xp->cshared.alloc(ctx, (size_t)xp->nchunks + 8));   // (the stream kernel reads the byte after a partition's last chunk)
+    FGPU_HIP(hipMemsetAsync(xp->cshared.p, 0, (size_t)xp->nchunks + 8, st));
+    FGPU_TRY(launch(xp_super_fill_kernel, dim3(grid), dim3(256), 0, st, (const u32*)g.p, (const uint8_t*)first.p, pc, (const u32*)nch.p,
+                    xp->cstart.p, xp->crun0.p, xp->cshared.p));
+    *done = true;                                            // (the build synchronises the stream before it hands the plan out)
+    return FGPU_OK;
+}
+
+// builds the plan of `t` (= m') under one (direct, dense, cut) triple; the caller holds m->idx_mu.  *out is set when the plan is
 // complete on the device; an error frees whatever was built so far
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, BpXPlanPtr* out) {
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, int cut, BpXPlanPtr* out) {
     BpXPlanPtr xp(new (std::nothrow) BpXPlan());
     FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
     const u32 n = (u32)t->nrows;
@@ -344,10 +469,15 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     u32 hp[27];                                              // pstart[9] | cbase[9] | first run of partition k [9]
     FGPU_TRY(read_words(ctx, xp->pstart_dev.p, 9, hp));
     for (int k = 0; k <= 8; ++k) FGPU_TRY(read_u32(ctx, ridx.p + (size_t)k * n, &hp[18 + k]));
-    hp[9] = 0;
-    for (int k = 0; k < 8; ++k) {
-        const u64 len = hp[k + 1] - hp[k], runs = hp[19 + k] - hp[18 + k];
-        hp[10 + k] = hp[9 + k] + (len ? (u32)((len - 1 + (u64)XP_RUNW * (runs - 1)) / XP_SPAN) + 1u : 0u);
+    bool cells = false;
+    if (cut) FGPU_TRY(xp_cut_cells(ctx, xp.get(), hp, &cells));
+    xp->cut = cells ? 1 : 0;
+    if (!cells) {
+        hp[9] = 0;
+        for (int k = 0; k < 8; ++k) {
+            const u64 len = hp[k + 1] - hp[k], runs = hp[19 + k] - hp[18 + k];
+            hp[10 + k] = hp[9 + k] + (len ? (u32)((len - 1 + (u64)XP_RUNW * (runs - 1)) / XP_SPAN) + 1u : 0u);
+        }
     }
     for (int k = 0; k <= 8; ++k) { xp->pstart[k] = hp[k]; xp->cbase[k] = hp[9 + k]; }
     xp->nchunks = xp->cbase[8];
@@ -358,12 +488,14 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     if (ggrid > (u32)ctx->cus * 16) ggrid = ctx->cus * 16;
     FGPU_TRY(launch(xp_groups_kernel, dim3(ggrid), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n, ng,
                     (const u32*)xp->gvtx.p, nslots, xp->ne.p, xp->pbase.p));
-    FGPU_TRY(xp->cstart.alloc(ctx, ((size_t)xp->nchunks + 1)));
-    FGPU_TRY(xp->crun0.alloc(ctx, ((size_t)xp->nchunks + 1)));
-    FGPU_TRY(xp->cshared.alloc(ctx, (size_t)xp->nchunks + 8));
-    FGPU_HIP(hipMemsetAsync(xp->cshared.p, 0, (size_t)xp->nchunks + 8, st));
-    FGPU_TRY(launch(xp_chunks_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n,
-                    (const u32*)xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p));
+    if (!cells) {
+        FGPU_TRY(xp->cstart.alloc(ctx, ((size_t)xp->nchunks + 1)));
+        FGPU_TRY(xp->crun0.alloc(ctx, ((size_t)xp->nchunks + 1)));
+        FGPU_TRY(xp->cshared.alloc(ctx, (size_t)xp->nchunks + 8));
+        FGPU_HIP(hipMemsetAsync(xp->cshared.p, 0, (size_t)xp->nchunks + 8, st));
+        FGPU_TRY(launch(xp_chunks_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)off.p, (const u32*)ridx.p, n,
+                        (const u32*)xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p));
+    }
     {   // the shared rows, compacted once (a few thousand among ~10^5 chunks)
         DevBuf<u32> zc;
         FGPU_TRY(zc.alloc(ctx, 1));
@@ -386,18 +518,18 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
 // half-built plan is freed, an empty one is attached as "not usable" (no second attempt per snapshot), the error is dropped
 // and the hop falls back to the plain pull.  (idx_mu is held from the look-up to the attachment: no reader
 // can tell this from attaching the plan first and finishing it afterwards.)
-// A plan is kept per (expand_xp_direct, expand_xp_dense) pair (a plan built under one pair is never handed to a hop expecting
+// A plan is kept per (expand_xp_direct, expand_xp_dense, expand_xp_cut) triple (a plan built under one is never handed to a hop expecting
 // another); the fold takes the form of its plan.
 fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out) {
     *out = nullptr;
     if (!ctx->opt.expand_xcd || !t || t->is_hyper()) return FGPU_OK;
     if (t->ncols >= (1ull << 31) || t->nrows >= 0xFFFFFFC0ull || t->nnz < 4096 || t->nnz >= 0x7FFFFFFFull) return FGPU_OK;
-    const int direct = ctx->opt.expand_xp_direct ? 1 : 0, dense = ctx->opt.expand_xp_dense ? 1 : 0;
+    const int direct = ctx->opt.expand_xp_direct ? 1 : 0, dense = ctx->opt.expand_xp_dense ? 1 : 0, cut = ctx->opt.expand_xp_cut ? 1 : 0;
     std::lock_guard<std::mutex> idx_guard(m->idx_mu);
-    BpXPlanPtr& slot = t->bp_xplan[direct + 2 * dense];
+    BpXPlanPtr& slot = t->bp_xplan[direct + 2 * dense + 4 * cut];
     if (!slot) {
         BpXPlanPtr xp;
-        if (bp_xplan_build(ctx, m, t, direct, dense, &xp) != FGPU_OK) {
+        if (bp_xplan_build(ctx, m, t, direct, dense, cut, &xp) != FGPU_OK) {
             xp.reset(new (std::nothrow) BpXPlan());
             FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
             (void)hipGetLastError();
@@ -406,6 +538,24 @@ fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const Bp
         slot = std::move(xp);
     }
     if (slot->usable) *out = slot.get();
+    return FGPU_OK;
+}
+
+// the chunk table read back (fgpu_mat_xp_chunks): [chunks, cut the plan holds, pstart[9], cbase[9]], then cstart, crun0 and cshared
+// (a word each) of every chunk
+fgpu_info bp_xplan_chunks(fgpu_ctx* ctx, const BpXPlan* xp, uint32_t** out, uint64_t* nwords) {
+    const size_t nc = xp->nchunks, total = 20 + 3 * nc;
+    uint32_t* w = (uint32_t*)ctx->result_alloc(total * sizeof(uint32_t));
+    FGPU_REQUIRE(w, FGPU_OOM, "out of host memory");
+    w[0] = xp->nchunks; w[1] = (u32)xp->cut;
+    for (int k = 0; k <= 8; ++k) { w[2 + k] = xp->pstart[k]; w[11 + k] = xp->cbase[k]; }
+    uint32_t* sh = w + 20 + 2 * nc;
+    fgpu_info i = nc ? ctx->d2h(w + 20, xp->cstart.p, nc * sizeof(u32)) : FGPU_OK;
+    if (i == FGPU_OK && nc) i = ctx->d2h(w + 20 + nc, xp->crun0.p, nc * sizeof(u32));
+    if (i == FGPU_OK && nc) i = ctx->d2h(sh, xp->cshared.p, nc);      // the bytes, packed at the head of their words' space ...
+    if (i != FGPU_OK) { ctx->host_free(w); return i; }
+    for (size_t c = nc; c-- > 0;) sh[c] = reinterpret_cast<const uint8_t*>(sh)[c];   // ... widened from the last one down
+    *out = w; *nwords = total;
     return FGPU_OK;
 }
 
@@ -441,7 +591,13 @@ __global__ __launch_bounds__(256) void xp_zero_rows_kernel(const u32* __restrict
 // the stream pull: QL lanes of 16 bytes per row of X (ws = 2 QL words), 64 / QL slots per wavefront, QL consecutive entries
 // per slot and trip.  WIDE = false: the state is at most 4 GiB, a row's byte offset fits 32 bits (one multiply-add per gather
 // address instead of 64-bit arithmetic: the kernel issues ~100 instructions per 64 entries and is not far from VALU-bound).
-template <int QL, bool WIDE, int NT>
+// LA (expand_xp_lookahead): the loads that run ahead of the trip being consumed do not stop at the chunk's end.  A wavefront takes
+// chunks j, j + nwaves, ... of its partition and knows on entering chunk j where chunk j + nwaves lies, so the column words and
+// the gathers that the chunk's LAST iteration issues ahead (two trips and one trip ahead of the trip it consumes) are the first
+// two trips of that next chunk, which then finds them in registers: the three loads that open a chunk run once per wavefront.
+// Without LA the same three statements reach past the chunk's end and gather 64 copies of its last entry, which are thrown away
+// when the chunk ends — at RMAT-22 a tenth of the gather slots the kernel issues.  With no next chunk the copies stay.
+template <int QL, bool WIDE, int NT, bool LA>
 __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ pcol, const u32* __restrict__ pstart,
                                                         const u32* __restrict__ cstart, const u32* __restrict__ crun0,
                                                         const uint8_t* __restrict__ cshared, const uint4* __restrict__ x,
@@ -461,12 +617,50 @@ __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ 
     const u32 c0 = pstart[9 + part], nch = pstart[10 + part] - c0;
     const u64 upto = (2ull << (slot * QL)) - 1ull;            // entries 0 .. the slot's first one
     const char* xb = reinterpret_cast<const char*>(x) + wl * 16;
+    // entry I + lane, held below LIM (a load past the end repeats the last entry: no branch around a load)
+#define XP_COL(I, LIM) ((NT & 2) ? __builtin_nontemporal_load(&pcol[(I) + lane < (LIM) ? (I) + lane : (LIM) - 1]) : pcol[(I) + lane < (LIM) ? (I) + lane : (LIM) - 1])
+#define XP_GATHER(XV, CW)                                                                                   \
+    _Pragma("unroll") for (int k = 0; k < QL; ++k) {                                                        \
+        const u32 uk = (u32)__shfl((int)(CW), (int)(slot * QL + k), 64) & ~XP_FIRST;                        \
+        if (WIDE) XV[k] = *reinterpret_cast<const uint4*>(xb + (size_t)uk * (QL * 16));                     \
+        else XV[k] = *reinterpret_cast<const uint4*>(xb + (u32)(uk * (u32)(QL * 16)));                      \
+    }
+    // what the table says of chunk j: its entries [B, E), the run (= partial row) of the first one, and whether that run began in
+    // an earlier chunk / the run of the last one goes on in the next (the pieces of such a run meet through atomics)
+    struct Chunk { u32 B, E, R0; bool first_atomic, last_atomic; };
+    // a chunk's shared byte, read as the aligned word that holds it: a scalar load like the other table entries.  (As a byte it is a
+    // vector load, and hipcc waits for vmcnt(0) — the gathers in flight — where it makes the value uniform, at the chunk's head.
+    // The table is a block of its own with 8 spare zero bytes behind the last chunk's: the word of byte nchunks lies inside it.)
+    const u32* shared32 = reinterpret_cast<const u32*>(cshared);
+    auto shared_at = [&](u32 c) { return (((u32)__builtin_amdgcn_readfirstlane((int)shared32[c >> 2]) >> ((c & 3u) * 8u)) & 0xFFu) != 0u; };
+    auto chunk_at = [&](u32 j) {
+        Chunk c;
+        c.B = (u32)__builtin_amdgcn_readfirstlane((int)cstart[c0 + j]);
+        c.E = j + 1 < nch ? (u32)__builtin_amdgcn_readfirstlane((int)cstart[c0 + j + 1]) : pe;
+        c.R0 = (u32)__builtin_amdgcn_readfirstlane((int)crun0[c0 + j]);
+        c.first_atomic = shared_at(c0 + j);
+        c.last_atomic = shared_at(c0 + j + 1) & (j + 1 < nch);   // (loaded whatever j is and masked: no branch around a load)
+        return c;
+    };
+    if (wave >= nch) return;
+    u32 cwE = 0, cwO = 0;
+    uint4 xvE[QL], xvO[QL];
+    Chunk cur{};
+    if (LA) {   // the wavefront's first chunk opens the pipeline; every later one is opened by the chunk before it
+        cur = chunk_at(wave);
+        cwE = XP_COL(cur.B, cur.E);
+        cwO = XP_COL(cur.B + 64, cur.E);
+        XP_GATHER(xvE, cwE)
+    }
     for (u32 j = wave; j < nch; j += nwaves) {
-        const u32 B = (u32)__builtin_amdgcn_readfirstlane((int)cstart[c0 + j]);
-        const u32 E = j + 1 < nch ? (u32)__builtin_amdgcn_readfirstlane((int)cstart[c0 + j + 1]) : pe;
-        const u32 R0 = (u32)__builtin_amdgcn_readfirstlane((int)crun0[c0 + j]);
-        const bool first_atomic = cshared[c0 + j] != 0;      // the run of the chunk's first entry began in an earlier chunk
-        const bool last_atomic = j + 1 < nch && cshared[c0 + j + 1] != 0;   // ... and the run of its last entry goes on in the next
+        // the wavefront's next chunk, read with this one's table entries, a whole chunk before the last iteration needs it.
+        // (Without one the loads repeat this chunk's — no branch around a load — and the look-ahead stays at E - 1.)
+        const bool more = LA && j + nwaves < nch;
+        const Chunk nxt = LA ? chunk_at(more ? j + nwaves : j) : cur;
+        if (!LA) cur = chunk_at(j);
+        const u32 B = cur.B, E = cur.E, R0 = cur.R0;
+        const bool first_atomic = cur.first_atomic, last_atomic = cur.last_atomic;
+        const u32 aheadB = more ? nxt.B : E - 1u, aheadE = more ? nxt.E : E;
         u32 base = 0;                                        // runs of the chunk begun before the current trip (tile row of a carried run)
         // One trip: `mask` = the run starts among its 64 entries (lane = entry), `xv` = the rows of X of this slot's QL
         // consecutive entries.  Entries past the chunk's end are copies of its last entry (the loads clamp): no run starts on
@@ -494,33 +688,29 @@ __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ 
         // moves): the column words run TWO trips ahead of the trip being consumed and the gathers ONE, and every wait is for
         // loads OLDER than the ones that should stay in flight (vmcnt counts in issue order: a column word loaded after the
         // previous trip's gathers would drain them).  Loads past the chunk's end repeat its last entry (no branch around a
-        // load); the extra round of gathers per chunk hits the row it has just gathered.
-#define XP_COL(T) ((NT & 2) ? __builtin_nontemporal_load(&pcol[(T) + lane < E ? (T) + lane : E - 1]) : pcol[(T) + lane < E ? (T) + lane : E - 1])
-#define XP_GATHER(XV, CW)                                                                                   \
-        _Pragma("unroll") for (int k = 0; k < QL; ++k) {                                                    \
-            const u32 uk = (u32)__shfl((int)(CW), (int)(slot * QL + k), 64) & ~XP_FIRST;                    \
-            if (WIDE) XV[k] = *reinterpret_cast<const uint4*>(xb + (size_t)uk * (QL * 16));                 \
-            else XV[k] = *reinterpret_cast<const uint4*>(xb + (u32)(uk * (u32)(QL * 16)));                  \
+        // load); without LA that is an extra round of gathers per chunk, which hits the row it has just gathered.
+        if (!LA) {
+            cwE = XP_COL(B, E);
+            cwO = XP_COL(B + 64, E);
+            XP_GATHER(xvE, cwE)
         }
-        u32 cwE = XP_COL(B);
-        u32 cwO = XP_COL(B + 64);
-        uint4 xvE[QL], xvO[QL];
-        XP_GATHER(xvE, cwE)
         for (u32 t = B; t < E; t += 128) {
             // run starts in entry order (lane = entry); the chunk's first entry never opens a NEW tile row
             const u64 maskE = __ballot(t + lane < E && (cwE & XP_FIRST) && !(t == B && lane == 0));
-            cwE = XP_COL(t + 128);
+            // LA, the chunk's last iteration (uniform): trips t + 128 and t + 192 are trips 0 and 1 of the next chunk — two scalar
+            // selects in front of the same two loads
+            const bool ahead = LA && t + 128 >= E;
+            const u32 at = ahead ? aheadB : t + 128, lim = ahead ? aheadE : E;
+            cwE = XP_COL(at, lim);
             XP_GATHER(xvO, cwO)
             trip(maskE, xvE);
             // (no early exit when the chunk ends in an even trip: the odd one then runs on copies of the last entry — a branch
             // here makes hipcc merge the wait states of the two paths at the loop head into vmcnt(0))
             const u64 maskO = __ballot(t + 64 + lane < E && (cwO & XP_FIRST));
-            cwO = XP_COL(t + 192);
+            cwO = XP_COL(at + 64, lim);
             XP_GATHER(xvE, cwE)
             trip(maskO, xvO);
         }
-#undef XP_COL
-#undef XP_GATHER
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // the chunk's runs leave the tile: run R0 + r, SLOTS rows per step; the first / last one through atomics when other chunks
@@ -539,7 +729,10 @@ __global__ __launch_bounds__(256) void xp_stream_kernel(const u32* __restrict__ 
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        if (LA) cur = nxt;
     }
+#undef XP_COL
+#undef XP_GATHER
 }
 
 // the fold: Y[v] = OR over the partitions of v's partial rows, then exactly what the plain pull does with a finished row —
@@ -978,10 +1171,14 @@ static fgpu_info xp_stream(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, 
     const u32 need = 8 * cdiv(most ? most : 1, 4);
     if (grid > need) grid = need;
     grid = (grid + 7) & ~7u;
+    // expand_xp_stream_wgs: at most that many workgroups per partition (a small graph then has every wavefront walk many chunks)
+    if (ctx->opt.expand_xp_stream_wgs > 0 && grid > 8u * (u32)ctx->opt.expand_xp_stream_wgs) grid = 8u * (u32)ctx->opt.expand_xp_stream_wgs;
     const bool wide = (u64)xp->n * ws * 8 > (1ull << 32) || (u64)t->ncols * ws * 8 > (1ull << 32);
     return pick<1, 2, 4, 8>((int)ql, [&](auto q) { return pick(wide, [&](auto w) { return pick<1, 2, 3, 0>(ctx->opt.expand_nt & 3, [&](auto nt) {
-        return launch(xp_stream_kernel<decltype(q)::value, decltype(w)::value, decltype(nt)::value>, dim3(grid), dim3(256), lds, ctx->stream(),
-                      xp->pcol.p, xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p, (const uint4*)x, partial);
+        return pick(ctx->opt.expand_xp_lookahead != 0, [&](auto la) {
+            return launch(xp_stream_kernel<decltype(q)::value, decltype(w)::value, decltype(nt)::value, decltype(la)::value>, dim3(grid), dim3(256),
+                          lds, ctx->stream(), xp->pcol.p, xp->pstart_dev.p, xp->cstart.p, xp->crun0.p, xp->cshared.p, (const uint4*)x, partial);
+        });
     }); }); });
 }
 
@@ -1024,6 +1221,8 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
     FGPU_REQUIRE(!xp->dense == !xp->gvtx.p, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
     ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
     ctx->xp_last_groups.store(xp->ng, std::memory_order_relaxed);
+    ctx->xp_last_chunks.store(xp->nchunks, std::memory_order_relaxed);
+    ctx->xp_last_shared_rows.store(xp->nzrows - 1, std::memory_order_relaxed);   // (without the spare zero row)
     DevBuf<uint4> partial;
     FGPU_TRY(partial.alloc(ctx, ((size_t)xp->nprows + 1) * (ws / 2)));
     FGPU_TRY(xp_zero_rows(ctx, xp, ws / 2, partial.p));

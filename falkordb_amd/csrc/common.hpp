@@ -158,6 +158,8 @@ struct fgpu_ctx {
     std::atomic<uint64_t> xp_piece_folds{0}, xp_slot_folds{0};   // launches of the two folds so far ("expand_xp_piece_folds" / "expand_xp_slot_folds")
     std::atomic<uint64_t> xp_last_direct{0};    // single-entry runs the fold read from X in the last partitioned count hop ("expand_xp_last_direct")
     std::atomic<uint64_t> xp_last_groups{0};    // 64-row groups the fold of the last partitioned count hop looped over ("expand_xp_last_groups")
+    std::atomic<uint64_t> xp_last_chunks{0};    // chunks of the stream in the plan of the last partitioned count hop ("expand_xp_last_chunks")
+    std::atomic<uint64_t> xp_last_shared_rows{0};   // ... and its chunks that begin inside a run: partial rows zeroed, pieces through atomics ("expand_xp_last_shared_rows")
     std::atomic<uint64_t> hc_last_entries{0}, hc_last_gathered{0};   // the last fgpu_harmonic call: entries of the recomputed rows, sketches gathered ("harmonic_last_*")
     std::atomic<uint64_t> msf_round_entries[32] = {};   // the last fgpu_msf call: entries read in round k, the rounds past 31 in [31] ("msf_last_entries_round<k>")
     std::atomic<int64_t> sssp_last_delta{0};   // the last fgpu_sssp call: log2 of its bucket width, 1024 = one bucket ("sssp_last_delta_log2")
@@ -382,9 +384,9 @@ struct fgpu_mat {
     mutable fgpu::MatRef tcache;               // cached pattern transpose of this matrix (mat_cached_transpose)
     mutable std::unique_ptr<fgpu_tiles> tiles; // built on demand by tiles_build
     mutable std::unique_ptr<fgpu::PrParts, fgpu::PrPartsDelete> pr_parts;  // pagerank.hip: this matrix split into column ranges, lazily
-    mutable fgpu::BpXPlanPtr bp_xplan[4];      // on the cached transpose: the XCD-partitioned layout of the dense count hop, one per
-                                               // (expand_xp_direct, expand_xp_dense) pair — index direct + 2 x dense (bitpart.hip,
-                                               // built on the first such hop under that pair)
+    mutable fgpu::BpXPlanPtr bp_xplan[8];      // on the cached transpose: the XCD-partitioned layout of the dense count hop, one per
+                                               // (expand_xp_direct, expand_xp_dense, expand_xp_cut) triple — index direct + 2 x dense
+                                               // + 4 x cut (bitpart.hip, built on the first such hop under that triple)
     bool is_hyper() const { return hrows != nullptr; }
 };
 

@@ -89,6 +89,13 @@ struct fgpu_options {  // fgpu_set_option
                                // <= 256 entries, the row of an entry in bits 27..31 of its column word; A/B: 277 -> 228 us a launch at
                                // RMAT-22, profiles/NOTES_r17.md).
                                // By name in ctx.hip like sssp_delta_log2, for the same reason
+    int expand_xp_lookahead = 1; // XCD-partitioned count hop, stream kernel: 1 = the loads a chunk's last iteration issues ahead are the first
+                               // two trips of the wavefront's NEXT chunk, 0 = they repeat the chunk's last entry and every chunk opens its own
+                               // pipeline (bitpart.hip xp_stream_kernel; A/B, profiles/NOTES_r18.md).  By name in ctx.hip like sssp_delta_log2
+    int expand_xp_cut = 1;      // ... its chunk table: 1 = every chunk but a partition's last holds a multiple of 128 entries, two whole
+                               // trips of the stream kernel (bitpart.hip xp_cut_cells), 0 = the key cut (entry + 8 x run) / 768.  By name, likewise
+    int expand_xp_stream_wgs = 0; // ... at most this many workgroups of the stream kernel per partition, 0 = as many as the chunks and the
+                               // CUs allow (tests: every wavefront walks many chunks of a small graph; A/B).  By name in ctx.hip, likewise
     int spdag_sides = 0;        // fgpu_shortest_dag: which ball grows.  0 = the side whose frontier has fewer entries to scan (ties
                                // forward), 1 = forward only, 2 = backward only, 3 = strict alternation starting forward.  Every
                                // setting returns the same length and pairs, only the stats differ (spdag.hip; the tests hold the

@@ -261,6 +261,17 @@ class Mat:
         cols = self.ctx._take(cp, max(n.value, 1) * 256, np.uint32)[: n.value * 256].reshape(-1, 256)
         return hdr, cols
 
+    def xp_chunks(self):
+        """The chunk table of the partitioned count hop's plan on the cached transpose (fgpu_mat_xp_chunks), under the options in
+        force: dict(cut, pstart[9], cbase[9], cstart, crun0, cshared), the last three one entry per chunk."""
+        wp = C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        check(self.ctx.lib.fgpu_mat_xp_chunks(self.ctx._h, self._h, C.byref(wp), C.byref(n)))
+        w = self.ctx._take(wp, n.value, np.uint32)
+        nc = int(w[0])
+        return dict(cut=int(w[1]), pstart=w[2:11].copy(), cbase=w[11:20].copy(), cstart=w[20:20 + nc].copy(),
+                    crun0=w[20 + nc:20 + 2 * nc].copy(), cshared=w[20 + 2 * nc:20 + 3 * nc].copy())
+
     def extract(self, min_row=0, max_row=2**64 - 1):
         lib = self.ctx.lib
         r, c, v = u64p(), u64p(), u64p()

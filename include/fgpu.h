@@ -271,6 +271,16 @@ fgpu_info fgpu_mat_tiles_info(const fgpu_mat* m, uint64_t info[8]);
  * lists above because it is stored by name): 0 = a wavefront per 32-row group, 1 = a wavefront per packed item (A/B);
  * fgpu_get_option reads expand_group_item_launches, the launches of the packed form so far. */
 fgpu_info fgpu_mat_group_items(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** hdr, uint32_t** cols, uint64_t* nitems);
+/* The chunk table of the XCD-partitioned count hop's plan on m's cached transpose (built here, under the options in force, if no
+ * hop has built it yet), read back as 32-bit words: [chunks, cut, first entry of partition 0 .. 8, first chunk of partition 0 .. 8],
+ * then for every chunk the first entry, then for every chunk the run (= partial row) of that entry, then for every chunk 1 when
+ * that run began in an earlier chunk.  `cut` is the cut the plan holds: 1 = every chunk but a partition's last is a multiple of 128
+ * entries, 0 = the key cut.  Released with fgpu_free.  FGPU_NO_VALUE when the matrix has no such plan.
+ * The options expand_xp_cut (0 / 1: which cut a new plan gets), expand_xp_lookahead (0 / 1: the stream kernel carries its
+ * look-ahead into the wavefront's next chunk) and expand_xp_stream_wgs (0, or the most workgroups of the stream kernel per
+ * partition) are stored by name like expand_group_items and kept out of the lists above; fgpu_get_option also reads
+ * expand_xp_last_chunks and expand_xp_last_shared_rows, the chunks of the last count hop's plan and those that begin inside a run. */
+fgpu_info fgpu_mat_xp_chunks(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** words, uint64_t* nwords);
 
 /* ---- products (ANY_PAIR structural semiring) ------------------------------ */
 
