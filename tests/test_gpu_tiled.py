@@ -3,13 +3,31 @@
 Small tile widths force many column tiles, padding, multi-item hub groups and partially filled
 last tiles on graphs the oracle finishes in seconds; the RMAT-22 case (BASELINE.json configs[1])
 is checked through the CSR kernel of the same library, itself pinned on the oracle here."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import oracle
 from falkordb_amd import engine
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_options_cpu import OPTIONS  # noqa: E402
+
 pytestmark = pytest.mark.gpu
+
+TOUCHED = ("tiled_u", "tiled_nt", "tiled_threads", "tiled_wgs", "tiled_layout")
+
+
+def saved(ctx, *names):
+    """The options a test is about to change, as they are now: what its `finally` puts back."""
+    return {k: ctx.get_option(k) for k in names}
+
+
+def restore(ctx, before):
+    for k, v in before.items():
+        ctx.set_option(k, v)
 
 
 def up(ctx, a):
@@ -26,6 +44,7 @@ def test_tiled_vxm_matches_oracle(ctx, tile_bits, vec, k):
     At = A.transpose()
     info = At.build_tiles(tile_bits, vec, k)
     assert info["entries"] >= a.nnz and info["entries"] % info["vec"] == 0
+    before = saved(ctx, "tiled_u", "tiled_nt")
     try:
         for u in (1, 2, 4, 8):
             ctx.set_option("tiled_u", u)
@@ -39,8 +58,7 @@ def test_tiled_vxm_matches_oracle(ctx, tile_bits, vec, k):
                         got = engine.vxm(ctx, f, mk, A, At, 3)
                         np.testing.assert_array_equal(got, want)
     finally:
-        ctx.set_option("tiled_u", 4)
-        ctx.set_option("tiled_nt", 0)
+        restore(ctx, before)
 
 
 @pytest.mark.parametrize("threads", [256, 512, 1024])
@@ -50,6 +68,7 @@ def test_tiled_vxm_workgroup_shapes(ctx, threads):
     A = up(ctx, a)
     At = A.transpose()
     At.build_tiles(9, 2, 2)
+    before = saved(ctx, "tiled_threads", "tiled_wgs")
     ctx.set_option("tiled_threads", threads)
     try:
         for wgs in (0, 3, 17):
@@ -57,8 +76,7 @@ def test_tiled_vxm_workgroup_shapes(ctx, threads):
             f = oracle.bits_from_ids(n, np.arange(0, n, 3))
             np.testing.assert_array_equal(engine.vxm(ctx, f, None, A, At, 3), oracle.vxm(a, f, None))
     finally:
-        ctx.set_option("tiled_threads", 1024)
-        ctx.set_option("tiled_wgs", 0)
+        restore(ctx, before)
 
 
 def test_tiled_vxm_ragged_and_empty(ctx):
@@ -108,53 +126,14 @@ def test_tiled_full_pass_rmat22_matches_the_oracle(ctx, bench_graphs):
     np.testing.assert_array_equal(oracle.ids_from_bits(engine.vxm(ctx, full, None, A, At, 3), n), np.nonzero(has_in)[0])
 
 
-# ---- blocked layout (blocked.hip): x tile AND output window in LDS -----------------------------------------------------
+# ---- blocked layout (blocked.hip) at the benchmark's sizes; its small and ragged shapes: tests/test_gpu_blocked.py ------------
 
 @pytest.fixture
 def blocked(ctx):
+    before = saved(ctx, "tiled_layout")
     ctx.set_option("tiled_layout", 2)
     yield
-    ctx.set_option("tiled_layout", 0)
-
-
-@pytest.mark.parametrize("scale", [10, 13, 16])
-def test_blocked_vxm_matches_oracle(ctx, blocked, scale):
-    a = oracle.rmat_csr(scale)
-    n = a.nrows
-    rng = np.random.default_rng(scale)
-    A = up(ctx, a)
-    At = A.transpose()
-    info = At.build_tiles()
-    assert info["entries"] >= a.nnz and info["entries"] % 4 == 0 and info["tile_bits"] == 18
-    for nf in (1, 37, 500, n // 2, n):
-        f = oracle.bits_from_ids(n, rng.choice(n, nf, replace=False))
-        mask = oracle.bits_from_ids(n, rng.choice(n, n // 3, replace=False))
-        for mk in (None, mask):
-            want = oracle.vxm(a, f, mk)
-            for _ in range(3):
-                np.testing.assert_array_equal(engine.vxm(ctx, f, mk, A, At, 3), want)
-
-
-def test_blocked_vxm_ragged_hubs_and_empty(ctx, blocked):
-    # n not a multiple of 64 (nor of the window), empty rows, a hub row spanning several chunks, duplicates of one output
-    # word inside a segment (rows 7 and 7 + 32 k share bits only across segments; row 7's 900 entries hit one word 900 times)
-    n = 1000
-    rows = np.concatenate([np.full(900, 7), np.arange(0, 200, 2), [999]]).astype(np.uint64)
-    cols = np.concatenate([np.arange(900) + 50, np.arange(0, 200, 2) + 1, [0]]).astype(np.uint64)
-    a = oracle.build_csr(n, n, rows, cols)
-    A = up(ctx, a)
-    At = A.transpose()
-    At.build_tiles()
-    rng = np.random.default_rng(5)
-    for nf in (1, 10, 400, n):
-        f = oracle.bits_from_ids(n, rng.choice(n, nf, replace=False))
-        np.testing.assert_array_equal(engine.vxm(ctx, f, None, A, At, 3), oracle.vxm(a, f, None))
-    # the same through the transposed roles (a 900-entry ROW of the matrix being streamed)
-    np.testing.assert_array_equal(engine.vxm(ctx, oracle.bits_from_ids(n, np.arange(n)), None, At, A, 3),
-                                  oracle.vxm(oracle.transpose(a), oracle.bits_from_ids(n, np.arange(n)), None))
-    e = ctx.mat_new(256, 256)
-    info = e.build_tiles()
-    assert info["entries"] == 0
+    restore(ctx, before)
 
 
 @pytest.mark.parametrize("scale", [22, 24, 26])
@@ -171,3 +150,9 @@ def test_blocked_full_pass_matches_the_oracle(ctx, blocked, bench_graphs, scale)
         np.testing.assert_array_equal(engine.vxm(ctx, f, mk, A, At, 3), want)
         if scale < 26 or mk is None:
             np.testing.assert_array_equal(engine.vxm(ctx, f, mk, A, At, 2), want)
+
+
+def test_every_option_this_file_touches_is_back_at_its_default(ctx):
+    defaults = {name: default for name, _, _, _, default in OPTIONS}
+    for k in TOUCHED:
+        assert ctx.get_option(k) == defaults[k], k
