@@ -805,22 +805,17 @@ static const CounterRow COUNTERS[] = {
     FGPU_COUNTER("expand_xp_last_groups", xp_last_groups),
     FGPU_COUNTER("harmonic_last_entries", hc_last_entries),
     FGPU_COUNTER("harmonic_last_gathered", hc_last_gathered),
+    FGPU_COUNTER("sssp_last_delta_log2", sssp_last_delta),
+    FGPU_COUNTER("expand_xp_last_chunks", xp_last_chunks),
+    FGPU_COUNTER("expand_xp_last_shared_rows", xp_last_shared_rows),
+    FGPU_COUNTER("expand_group_item_launches", group_item_launches),
 };
 #undef FGPU_COUNTER
 
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     FGPU_REQUIRE(ctx && name && value, FGPU_NULL_POINTER, "fgpu_get_option: NULL argument");
     if (const OptRow* r = opt_find(name)) { *value = opt_load(ctx->opt, *r); return FGPU_OK; }
-    if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }
-    if (!strcmp(name, "sssp_last_delta_log2")) { *value = ctx->sssp_last_delta.load(std::memory_order_relaxed); return FGPU_OK; }
-    if (!strcmp(name, "expand_group_items")) { *value = ctx->opt.expand_group_items; return FGPU_OK; }
-    if (!strcmp(name, "spdag_sides")) { *value = ctx->opt.spdag_sides; return FGPU_OK; }
-    if (!strcmp(name, "expand_xp_lookahead")) { *value = ctx->opt.expand_xp_lookahead; return FGPU_OK; }
-    if (!strcmp(name, "expand_xp_stream_wgs")) { *value = ctx->opt.expand_xp_stream_wgs; return FGPU_OK; }
-    if (!strcmp(name, "expand_xp_cut")) { *value = ctx->opt.expand_xp_cut; return FGPU_OK; }
-    if (!strcmp(name, "expand_xp_last_chunks")) { *value = (int64_t)ctx->xp_last_chunks.load(std::memory_order_relaxed); return FGPU_OK; }
-    if (!strcmp(name, "expand_xp_last_shared_rows")) { *value = (int64_t)ctx->xp_last_shared_rows.load(std::memory_order_relaxed); return FGPU_OK; }
-    if (!strcmp(name, "expand_group_item_launches")) { *value = (int64_t)ctx->group_item_launches.load(std::memory_order_relaxed); return FGPU_OK; }
+    if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }   // an exponent or auto: no row kind fits
     for (const CounterRow& c : COUNTERS)
         if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
     if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32) {
@@ -838,36 +833,11 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
         ks_set_wb_override((int)value);
         return FGPU_OK;
     }
-    if (!strcmp(name, "sssp_delta_log2")) {   // an exponent or "auto": not a row of the table (options.hpp)
+    if (!strcmp(name, "sssp_delta_log2")) {   // an exponent or auto: no row kind fits (options.hpp)
         FGPU_REQUIRE(value == SSSP_DELTA_AUTO || (value >= SSSP_DELTA_MIN && value <= SSSP_DELTA_MAX), FGPU_INVALID,
                      "fgpu_set_option: sssp_delta_log2 must be %d .. %d or %d (auto), not %lld", SSSP_DELTA_MIN, SSSP_DELTA_MAX,
                      SSSP_DELTA_AUTO, (long long)value);
         ctx->opt.sssp_delta_log2 = (int)value;
-        return FGPU_OK;
-    }
-    if (!strcmp(name, "expand_group_items")) {   // set and read by name, like sssp_delta_log2: not a row of the table (options.hpp)
-        FGPU_REQUIRE(value >= 0 && value <= 1, FGPU_INVALID, "fgpu_set_option: expand_group_items must be 0 or 1, not %lld", (long long)value);
-        ctx->opt.expand_group_items = (int)value;
-        return FGPU_OK;
-    }
-    if (!strcmp(name, "spdag_sides")) {   // by name, like sssp_delta_log2: not a row of the table (options.hpp)
-        FGPU_REQUIRE(value >= 0 && value <= 3, FGPU_INVALID, "fgpu_set_option: spdag_sides must be 0 .. 3, not %lld", (long long)value);
-        ctx->opt.spdag_sides = (int)value;
-        return FGPU_OK;
-    }
-    if (!strcmp(name, "expand_xp_lookahead")) {   // by name, like expand_group_items: not a row of the table (options.hpp)
-        FGPU_REQUIRE(value >= 0 && value <= 1, FGPU_INVALID, "fgpu_set_option: expand_xp_lookahead must be 0 or 1, not %lld", (long long)value);
-        ctx->opt.expand_xp_lookahead = (int)value;
-        return FGPU_OK;
-    }
-    if (!strcmp(name, "expand_xp_cut")) {   // by name, likewise
-        FGPU_REQUIRE(value >= 0 && value <= 1, FGPU_INVALID, "fgpu_set_option: expand_xp_cut must be 0 or 1, not %lld", (long long)value);
-        ctx->opt.expand_xp_cut = (int)value;
-        return FGPU_OK;
-    }
-    if (!strcmp(name, "expand_xp_stream_wgs")) {   // by name, likewise
-        FGPU_REQUIRE(value >= 0 && value <= 65536, FGPU_INVALID, "fgpu_set_option: expand_xp_stream_wgs must be 0 .. 65536, not %lld", (long long)value);
-        ctx->opt.expand_xp_stream_wgs = (int)value;
         return FGPU_OK;
     }
     const OptRow* r = opt_find(name);

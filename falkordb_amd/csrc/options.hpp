@@ -81,25 +81,23 @@ struct fgpu_options {  // fgpu_set_option
     int maxflow_global_every = 0;   // fgpu_maxflow: pulses between two global relabels (0 = MF_GLOBAL_EVERY of maxflow.hip; A/B)
     int bc_direction = 0;      // fgpu_betweenness forward levels: 0 auto (push / pull by entries to read), 1 push over A, 2 pull over At
     int sssp_delta_log2 = 4096; // fgpu_sssp: the bucket width is 2^value, SSSP_DELTA_AUTO = derived on the device from the mean finite
-                               // weight and the mean degree (sssp.hip).  Set and read by name in ctx.hip, not a row of the table below:
-                               // the table is pinned row for row by tests/test_options_cpu.py
+                               // weight and the mean degree (sssp.hip).  Handled in ctx.hip, not a row below: an exponent or auto: no row kind fits
     int expand_group_items = 1; // sparse mid-chain pull through records, the rows of <= 256 entries: 0 = a wavefront per 32-row group
                                // derives the cut of its rows in every pass (rowptr -> prefix scan -> column ids), 1 = a wavefront per
                                // ITEM of the packed stream built once per snapshot (bitexpand.hip bp_group_items: <= 32 whole rows,
                                // <= 256 entries, the row of an entry in bits 27..31 of its column word; A/B: 277 -> 228 us a launch at
-                               // RMAT-22, profiles/NOTES_r17.md).
-                               // By name in ctx.hip like sssp_delta_log2, for the same reason
+                               // RMAT-22, profiles/NOTES_r17.md)
     int expand_xp_lookahead = 1; // XCD-partitioned count hop, stream kernel: 1 = the loads a chunk's last iteration issues ahead are the first
                                // two trips of the wavefront's NEXT chunk, 0 = they repeat the chunk's last entry and every chunk opens its own
-                               // pipeline (bitpart.hip xp_stream_kernel; A/B, profiles/NOTES_r18.md).  By name in ctx.hip like sssp_delta_log2
+                               // pipeline (bitpart.hip xp_stream_kernel; A/B, profiles/NOTES_r18.md)
     int expand_xp_cut = 1;      // ... its chunk table: 1 = every chunk but a partition's last holds a multiple of 128 entries, two whole
-                               // trips of the stream kernel (bitpart.hip xp_cut_cells), 0 = the key cut (entry + 8 x run) / 768.  By name, likewise
+                               // trips of the stream kernel (bitpart.hip xp_cut_cells), 0 = the key cut (entry + 8 x run) / 768
     int expand_xp_stream_wgs = 0; // ... at most this many workgroups of the stream kernel per partition, 0 = as many as the chunks and the
-                               // CUs allow (tests: every wavefront walks many chunks of a small graph; A/B).  By name in ctx.hip, likewise
+                               // CUs allow (tests: every wavefront walks many chunks of a small graph; A/B)
     int spdag_sides = 0;        // fgpu_shortest_dag: which ball grows.  0 = the side whose frontier has fewer entries to scan (ties
                                // forward), 1 = forward only, 2 = backward only, 3 = strict alternation starting forward.  Every
                                // setting returns the same length and pairs, only the stats differ (spdag.hip; the tests hold the
-                               // two-sided search to the one-sided ones).  By name in ctx.hip like sssp_delta_log2, for the same reason
+                               // two-sided search to the one-sided ones)
 };
 constexpr int SSSP_DELTA_AUTO = 4096, SSSP_DELTA_MIN = -1074, SSSP_DELTA_MAX = 1023;
 
@@ -110,7 +108,7 @@ namespace fgpu {
 //   OPT_BOOL   any value, stored as value != 0
 //   OPT_RANGE  lo <= value <= hi
 //   OPT_POW2   lo <= value <= hi and a power of two
-// Not in the table: lds_limit (filled by fgpu_init, not settable) and "transpose_wb" (process-wide, no field: ctx.hip).
+// Not in the table: lds_limit (filled by fgpu_init, not settable), "transpose_wb" (process-wide, no field) and sssp_delta_log2: ctx.hip.
 enum OptKind { OPT_BOOL, OPT_RANGE, OPT_POW2 };
 
 struct OptRow {
@@ -170,6 +168,11 @@ inline constexpr OptRow OPTIONS[] = {
     FGPU_OPT(bc_batch, OPT_RANGE, 0, 64),
     FGPU_OPT(maxflow_global_every, OPT_RANGE, 0, 1 << 20),
     FGPU_OPT(bc_direction, OPT_RANGE, 0, 2),
+    FGPU_OPT(expand_group_items, OPT_RANGE, 0, 1),
+    FGPU_OPT(expand_xp_lookahead, OPT_RANGE, 0, 1),
+    FGPU_OPT(expand_xp_cut, OPT_RANGE, 0, 1),
+    FGPU_OPT(expand_xp_stream_wgs, OPT_RANGE, 0, 65536),
+    FGPU_OPT(spdag_sides, OPT_RANGE, 0, 3),
 };
 #undef FGPU_OPT
 #undef FGPU_OPT64

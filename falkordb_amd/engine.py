@@ -5,6 +5,7 @@ arrays to the plain pointers the ABI takes, and raise FgpuError on any non-zero 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -93,6 +94,21 @@ class Context:
         v = C.c_int64(0)
         check(self.lib.fgpu_get_option(self._h, name.encode(), C.byref(v)))
         return int(v.value)
+
+    @contextlib.contextmanager
+    def options(self, **values):
+        """Sets the options in the order given and, on the way out, puts back the values found, in reverse order, whether the
+        body returned or raised.  A value refused on entry raises after the options set before it have been put back."""
+        found = []
+        try:
+            for name, value in values.items():
+                old = self.get_option(name)
+                self.set_option(name, value)
+                found.append((name, old))
+            yield self
+        finally:
+            for name, old in reversed(found):
+                self.set_option(name, old)
 
     # ---- multi-GPU communicator (RCCL inside libfgpu.so; dist.hip) ----
     def comm_unique_id(self) -> bytes:

@@ -106,6 +106,7 @@ fgpu_info fgpu_sync(fgpu_ctx* ctx);
  *   "expand_bits_ratio"         1 .. 1024           expand_mode 0: a hop goes to bit form when its traversed edges exceed nnz / ratio
  *   "expand_row_groups"         0 / not 0           sparse mid-chain pull: 1 = a wavefront per 32-row group, 0 = a wavefront per row item
  *   "expand_records"            0 / not 0           sparse mid-chain pull: rows of at most 4 bits are read as records of source indices (A/B)
+ *   "expand_group_items"        0, 1                ... its rows of at most 256 entries: 1 = a wavefront per item of the packed stream (fgpu_mat_group_items), 0 = a wavefront per 32-row group (A/B)
  *   "expand_fuse_count"         0 / not 0           fgpu_expand_count: 1 = the last bit-parallel hop counts its rows where it produces them, 0 = a separate pass counts
  *   "expand_compact"            0 / not 0           empty source rows are dropped before the chain goes to bits when that halves the row width (A/B)
  *   "expand_first_hop"          0 / not 0           a clean first hop from one-entry rows copies the source rows (A/B)
@@ -118,6 +119,9 @@ fgpu_info fgpu_sync(fgpu_ctx* ctx);
  *   "expand_xp_fold"            0, 1                ... the fold: 1 = index work once per row, one load per piece that exists, 0 = a slot per row and step loads all 8 partitions' rows (A/B)
  *   "expand_xp_fold_min_words"  2, 4, 8, 16, 32     ... the piece fold runs on bit rows of at least this many 64-bit words (32: none), narrower rows keep the slot fold
  *   "expand_xp_dense"           0, 1                ... the fold's groups: 1 = 64 consecutive ranks among the rows that have an in-edge, 0 = 64 consecutive vertex ids (A/B)
+ *   "expand_xp_cut"             0, 1                ... the chunk table a new plan gets: 1 = chunks of whole double trips, 0 = the key cut (fgpu_mat_xp_chunks)
+ *   "expand_xp_lookahead"       0, 1                ... 1 = the stream kernel carries its look-ahead into the wavefront's next chunk (A/B)
+ *   "expand_xp_stream_wgs"      0 .. 65536          ... at most this many workgroups of the stream kernel per partition, 0 = as many as the chunks and the CUs allow
  *   "expand_scan_min"           0 .. 2^31 - 1       fgpu_expand_count: a call with more source rows than this is a whole-frontier call, cut into passes (0 = never)
  *   "expand_scan_rows"          64 .. 4096, 2^k     ... live rows per pass
  *   "expand_scan_lanes"         1 .. 16             ... lanes the passes are dealt to
@@ -142,6 +146,8 @@ fgpu_info fgpu_sync(fgpu_ctx* ctx);
  *   "bc_batch"                  0 .. 64             fgpu_betweenness: sources per batch, 0 = auto (16 / 32 / 64 by nsrc, halved to fit 3/4 of the free device memory)
  *   "bc_direction"              0 .. 2              fgpu_betweenness forward levels: 0 = auto by the entries each would read, 1 = push over A, 2 = pull over At
  *   "maxflow_global_every"      0 .. 1048576        fgpu_maxflow: pulses between two global relabels, 0 = the built-in period
+ *   "sssp_delta_log2"           -1074 .. 1023, 4096 fgpu_sssp: the bucket width is 2^value, 4096 = derived from the graph
+ *   "spdag_sides"               0 .. 3              fgpu_shortest_dag: which ball grows: 0 = the cheaper frontier, 1 = forward only, 2 = backward only, 3 = alternating
  *   multi-GPU BFS (fgpu_bfs_dist_run)
  *   "dist_collective"           0, 1                frontier exchange: 0 = grouped ncclSend / ncclRecv, 1 = one ncclBroadcast per rank
  *   "dist_timing"               0 / not 0           HIP events around every level kernel and exchange for fgpu_bfs_dist_times (~20 us of stream idle time per level)
@@ -158,11 +164,15 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value);
  *   "expand_xp_slot_folds"      ... and of the slot fold
  *   "expand_xp_last_direct"     entries of A' the last partitioned count hop read straight from X as single-entry runs, 0 when its plan streams every run
  *   "expand_xp_last_groups"     groups its fold looped over: ceil(rows with an in-edge / 64), or ceil(rows / 64)
+ *   "expand_xp_last_chunks"     chunks of the stream in its plan
+ *   "expand_xp_last_shared_rows" ... and those that begin inside a run
+ *   "expand_group_item_launches" launches of the sparse mid-chain pull in its packed-item form so far (expand_group_items)
  *   "bfs_pb_last_levels"        levels the search fgpu_bfs_stats last read ran by propagation blocking
  *   "bfs_cp_last_mask"          bit k: fused launch k of that search ran behind the list kernel (a sparse frontier listed into the queue, or a pull of listed candidates)
  *   "dist_self_calls"           forced self collectives issued so far (dist_force_self; tests/test_gpu_dist.py)
  *   "harmonic_last_entries"     the last fgpu_harmonic call: entries of the recomputed rows
  *   "harmonic_last_gathered"    ... and sketches gathered
+ *   "sssp_last_delta_log2"      the last fgpu_sssp call: log2 of the bucket width it used, 1024 = one bucket for all
  *   "msf_last_entries_round<k>" the last fgpu_msf call: entries read in round k = 0 .. 31, the rounds past 31 in 31 */
 fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value);
 /* name[256]; returns CU count, wave size, LDS bytes per block, total HBM bytes. */
@@ -267,19 +277,15 @@ fgpu_info fgpu_mat_tiles_info(const fgpu_mat* m, uint64_t info[8]);
  * and the 256 words cols[256 i ..], each a column id in bits 0..26 under its row-in-item in bits 27..31, the tail 0xFFFFFFFF.
  * Items hold whole consecutive rows, cut greedily in row order; rows of more than 256 entries count as empty.  Both arrays are
  * released with fgpu_free.  FGPU_NO_VALUE when the matrix is empty or the stream does not apply (2^27 - 1 columns or more).
- * Which form of the pull runs is the option expand_group_items (fgpu_set_option / fgpu_get_option, 0 or 1, kept out of their
- * lists above because it is stored by name): 0 = a wavefront per 32-row group, 1 = a wavefront per packed item (A/B);
- * fgpu_get_option reads expand_group_item_launches, the launches of the packed form so far. */
+ * The option expand_group_items picks the form of the pull that runs, the counter expand_group_item_launches counts the packed one. */
 fgpu_info fgpu_mat_group_items(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** hdr, uint32_t** cols, uint64_t* nitems);
 /* The chunk table of the XCD-partitioned count hop's plan on m's cached transpose (built here, under the options in force, if no
  * hop has built it yet), read back as 32-bit words: [chunks, cut, first entry of partition 0 .. 8, first chunk of partition 0 .. 8],
  * then for every chunk the first entry, then for every chunk the run (= partial row) of that entry, then for every chunk 1 when
  * that run began in an earlier chunk.  `cut` is the cut the plan holds: 1 = every chunk but a partition's last is a multiple of 128
  * entries, 0 = the key cut.  Released with fgpu_free.  FGPU_NO_VALUE when the matrix has no such plan.
- * The options expand_xp_cut (0 / 1: which cut a new plan gets), expand_xp_lookahead (0 / 1: the stream kernel carries its
- * look-ahead into the wavefront's next chunk) and expand_xp_stream_wgs (0, or the most workgroups of the stream kernel per
- * partition) are stored by name like expand_group_items and kept out of the lists above; fgpu_get_option also reads
- * expand_xp_last_chunks and expand_xp_last_shared_rows, the chunks of the last count hop's plan and those that begin inside a run. */
+ * The option expand_xp_cut picks the cut a new plan gets; the counters expand_xp_last_chunks and expand_xp_last_shared_rows
+ * describe the plan of the last count hop. */
 fgpu_info fgpu_mat_xp_chunks(fgpu_ctx* ctx, const fgpu_mat* m, uint32_t** words, uint64_t* nwords);
 
 /* ---- products (ANY_PAIR structural semiring) ------------------------------ */
@@ -639,9 +645,9 @@ fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, double* dist
  * in the cycle shape d(v, dst) = 0 for the closing pairs (u, src) — in ascending (from, to) order, each once, and
  * depth[k] = d(src, from[k]) in 0 .. L - 1.  Repeated calls give identical arrays.
  * The search is bidirectional and level-synchronous: it grows the ball whose frontier has fewer entries to scan, a whole level
- * at a time, and stops at the first level whose new vertices the other ball already holds (spdag.hip).  The option spdag_sides
- * (fgpu_set_option / fgpu_get_option, kept out of their name lists like expand_group_items): 0 that rule, 1 forward only,
- * 2 backward only, 3 strict alternation starting forward; every setting returns the same length and arrays.
+ * at a time, and stops at the first level whose new vertices the other ball already holds (spdag.hip).  The option spdag_sides:
+ * 0 that rule, 1 forward only, 2 backward only, 3 strict alternation starting forward; every setting returns the same length
+ * and arrays.
  * stats (nullable): [0] forward levels expanded, [1] backward levels expanded (the cycle shape's first one included),
  * [2] vertices claimed forward, [3] vertices claimed backward (seeds not counted), [4] entries scanned by the expansions,
  * [5] entries scanned by the sweeps that collect the DAG, [6] meeting vertices, [7] DAG vertices (the cycle shape counts src

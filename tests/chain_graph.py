@@ -20,7 +20,6 @@ hop's copy sum for the decision; the reported flops add the dp products and come
 import numpy as np
 
 import oracle
-from hop_graph import Forced
 
 U64, I64 = np.uint64, np.int64
 SKIP = np.uint64(2**64 - 1)
@@ -44,11 +43,9 @@ def bits_stride(rows):
 
 
 def forced(ctx, **opts):
-    """hop_graph's guard with exactly these options: the chain tests choose expand_mode themselves."""
+    """The context's guard with exactly these options: the chain tests choose expand_mode themselves."""
     assert "expand_mode" in opts
-    g = Forced(ctx)
-    g.opts = dict(opts)
-    return g
+    return ctx.options(**opts)
 
 
 def live_pattern(k, nlive):

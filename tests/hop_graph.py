@@ -206,15 +206,5 @@ class Case:
             m.free()
 
 
-class Forced:
-    def __init__(self, ctx, **opts):
-        self.ctx, self.opts, self.found = ctx, dict(expand_mode=2, expand_xcd_min_mb=0, **opts), {}
-
-    def __enter__(self):
-        for k, v in self.opts.items():
-            self.found[k] = self.ctx.get_option(k)
-            self.ctx.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in reversed(list(self.found.items())):
-            self.ctx.set_option(k, v)
+def Forced(ctx, **opts):
+    return ctx.options(expand_mode=2, expand_xcd_min_mb=0, **opts)

@@ -80,6 +80,7 @@ int main() {
     CHECK(opt_find("") == nullptr);
     CHECK(opt_find("lds_limit") == nullptr);      // filled by fgpu_init, not settable
     CHECK(opt_find("transpose_wb") == nullptr);   // a special case of fgpu_set_option, not a row
+    CHECK(opt_find("sssp_delta_log2") == nullptr);   // likewise: an exponent or auto: no row kind fits
     CHECK(opt_find("tiled_u ") == nullptr);
     return 0;
 }

@@ -5,8 +5,6 @@ partitioned layouts of the count hop) and to the lanes (pools, staging), then `d
 what it returned is freed, and `in_use` must be back at the value read, the second result equal to the first.  The graph is
 the smallest at which bp_to_csr takes its sort path (4096 vertices); the 130 source rows make more than two words of bits per
 vertex, and enough of them are empty (UINT64_MAX) or without out-edges for compact_source_rows to run."""
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -54,18 +52,6 @@ def graph(ctx):
         m.free()
 
 
-@contextlib.contextmanager
-def options(ctx, **kw):
-    before = {k: ctx.get_option(k) for k in kw}
-    try:
-        for k, v in kw.items():
-            ctx.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            ctx.set_option(k, v)
-
-
 def _plain(x):
     """a call's result as something `==` compares: arrays as bytes, containers element-wise"""
     if isinstance(x, np.ndarray):
@@ -110,7 +96,7 @@ def held_and_steady(ctx, call):
 def test_chain_entries_give_back_what_they_allocate(ctx, graph, mode, labelled, dirty):
     g = graph
     lab = g.label if labelled else None
-    with options(ctx, expand_mode=mode):
+    with ctx.options(expand_mode=mode):
         for hops in (2, 3):
             m, dp, dm = g.layers(dirty, hops)
             kw = dict(dp=dp, dm=dm, dst_label_bitmap=lab)
@@ -126,9 +112,9 @@ def test_chain_entries_give_back_what_they_allocate(ctx, graph, mode, labelled, 
         held_and_steady(ctx, lambda: engine.expand_levels(ctx, g.src, m, dp=dp, dm=dm, dst_label_bitmap=lab))
     # whatever form the chain ran in, it reaches what the sorted-CSR products (mode 1) reach
     m, dp, dm = g.layers(dirty, 2)
-    with options(ctx, expand_mode=1):
+    with ctx.options(expand_mode=1):
         rp, dest, _ = engine.expand(ctx, g.src, m, dp=dp, dm=dm, dst_label_bitmap=lab)
-    with options(ctx, expand_mode=mode):
+    with ctx.options(expand_mode=mode):
         rp2, dest2, _ = engine.expand32(ctx, g.src, m, dp=dp, dm=dm, dst_label_bitmap=lab)
     assert np.array_equal(rp, rp2.astype(np.uint64)) and np.array_equal(dest, dest2.astype(np.uint64))
 
@@ -141,7 +127,7 @@ def test_count_gives_back_what_it_allocates_at_every_end(ctx, graph, mode, label
     lab = g.label if labelled else None
     want = None
     for fuse in (0, 1):
-        with options(ctx, expand_mode=mode, expand_fuse_count=fuse):
+        with ctx.options(expand_mode=mode, expand_fuse_count=fuse):
             for hops in (2, 3):
                 m, dp, dm = g.layers(dirty, hops)
                 kw = dict(dp=dp, dm=dm, dst_label_bitmap=lab)
@@ -161,7 +147,7 @@ def test_whole_frontier_count_gives_back_what_it_allocates(ctx, graph, dirty):
     m, dp, dm = g.layers(dirty, 3)
     for src, passes in ((g.src, 2), (g.live_src, 3)):
         want = engine.expand_count(ctx, src, m, dp=dp, dm=dm)
-        with options(ctx, expand_scan_min=64, expand_scan_rows=64, expand_scan_lanes=2):
+        with ctx.options(expand_scan_min=64, expand_scan_rows=64, expand_scan_lanes=2):
             for cs in (True, False):
                 got = held_and_steady(ctx, lambda: engine.expand_count(ctx, src, m, dp=dp, dm=dm, want_checksum=cs))
                 assert ctx.get_option("expand_scan_last_passes") == passes

@@ -9,8 +9,6 @@ The graph has 8192 vertices: out-degree 16 everywhere, one row (HUB_ROW) with 40
 with 4096 more in-edges.  That is the smallest size at which the hub list and the finer push list are both non-empty for A and
 for A' (HUB_DEG = 4096, PUSH_HUB_DEG = 1024), the partitioned count hop has eight full partitions of 1024 rows, and bp_to_csr
 and the item split (BP_ITEM = 256) both run."""
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -50,18 +48,6 @@ def test_the_graph_is_what_the_cases_need():
     assert deg.min() >= D and deg[HUB_ROW] >= 4096 and indeg[HUB_COL] >= 4096
     assert np.sort(deg)[-2] < 1024 and np.sort(indeg)[-2] < 1024            # one hub each way, nothing else on any list
     assert N % 128 == 0 and N // 8 == 1024
-
-
-@contextlib.contextmanager
-def options(ctx, **kw):
-    before = {k: ctx.get_option(k) for k in kw}
-    try:
-        for k, v in kw.items():
-            ctx.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            ctx.set_option(k, v)
 
 
 def _plain(x):
@@ -159,7 +145,7 @@ def test_the_blocked_layout(ctx):
         At = A.transpose()
         want = engine.vxm(ctx, FRONTIER, None, A, At, direction=2)
         made = in_use(ctx)
-        with options(ctx, tiled_layout=2):
+        with ctx.options(tiled_layout=2):
             got = _pull(ctx, A, At)        # the first dense pull builds it
         info = At.tiles_info()
         assert info["tile_bits"] == 18 and info["tiles"] == 1
@@ -180,7 +166,7 @@ def test_a_layout_rebuilt_over_the_other(ctx):
         tiled = At.build_tiles(10, 2, 1)
         out.append(_pull(ctx, A, At))
         held = in_use(ctx)
-        with options(ctx, tiled_layout=2):
+        with ctx.options(tiled_layout=2):
             blocked = At.build_tiles()     # blocked over tiled
         out.append(_pull(ctx, A, At))
         assert blocked["tile_bits"] == 18
@@ -216,12 +202,12 @@ def test_the_cached_transpose_and_its_items_through_a_count(ctx):
         A = adjacency(ctx)
         DP, DM = layers(ctx)
         made = in_use(ctx)
-        with options(ctx, expand_mode=2):
+        with ctx.options(expand_mode=2):
             clean = engine.expand_count(ctx, SRC, [A, A])
             dirty = engine.expand_count(ctx, SRC, [A, A], dp=[DP, DP], dm=[DM, DM])
             rp, dest, _ = engine.expand(ctx, SRC, [A, A])          # bp_to_csr
         assert in_use(ctx) > made
-        with options(ctx, expand_mode=1):
+        with ctx.options(expand_mode=1):
             assert engine.expand_count(ctx, SRC, [A, A])[:2] == clean[:2]
         assert clean[0] == len(dest) == rp[-1]
         for m in (DM, DP, A):
@@ -233,13 +219,13 @@ def test_the_cached_transpose_and_its_items_through_a_count(ctx):
 def test_the_four_partitioned_plans_on_one_matrix(ctx):
     def case():
         A = adjacency(ctx)
-        with options(ctx, expand_mode=1):
+        with ctx.options(expand_mode=1):
             want = engine.expand_count(ctx, SRC, [A, A])
         out = []
-        with options(ctx, expand_mode=2, expand_xcd_min_mb=0):
+        with ctx.options(expand_mode=2, expand_xcd_min_mb=0):
             for direct in (0, 1):
                 for dense in (0, 1):
-                    with options(ctx, expand_xp_direct=direct, expand_xp_dense=dense):
+                    with ctx.options(expand_xp_direct=direct, expand_xp_dense=dense):
                         held = in_use(ctx)
                         folds = ctx.get_option("expand_xp_slot_folds") + ctx.get_option("expand_xp_piece_folds")
                         out.append(engine.expand_count(ctx, SRC, [A, A]))
@@ -255,11 +241,11 @@ def test_the_cached_transpose_alone_through_betweenness(ctx):
     def case():
         A = adjacency(ctx)                 # never expanded: no item list on its transpose
         made = in_use(ctx)
-        with options(ctx, bc_direction=2):
+        with ctx.options(bc_direction=2):
             cent, stats = engine.betweenness(ctx, A, SRC[:8], stats=True)
         assert in_use(ctx) > made
         At = A.transpose()
-        with options(ctx, bc_direction=2):
+        with ctx.options(bc_direction=2):
             given, _ = engine.betweenness(ctx, A, SRC[:8], At=At)
         assert np.array_equal(cent, given)
         At.free()
@@ -272,10 +258,10 @@ def test_the_column_ranges_through_pagerank(ctx):
     def case():
         A = adjacency(ctx)
         At = A.transpose()
-        with options(ctx, pagerank_parts=0):
+        with ctx.options(pagerank_parts=0):
             want = engine.pagerank(ctx, A, At)
         made = in_use(ctx)
-        with options(ctx, pagerank_parts=2):
+        with ctx.options(pagerank_parts=2):
             got = engine.pagerank(ctx, A, At)
         assert in_use(ctx) > made
         assert got[1] == want[1]

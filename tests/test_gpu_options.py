@@ -22,6 +22,9 @@ def _invalid(call, *args):
     ("expand_records", (0, 1), None),
     ("bfs_pb_min_edges", (2 << 20, 1 << 40), 0),
     ("tiled_wgs", (0, 7), 65537),
+    ("spdag_sides", (0, 3), 4),
+    ("expand_xp_stream_wgs", (0, 7), 65537),
+    ("expand_group_items", (1, 0), 2),
 ])
 def test_set_get_reject_restore(ctx, name, legal, illegal):
     found = ctx.get_option(name)
@@ -45,6 +48,11 @@ def test_unknown_names_counters_and_special_cases(ctx):
     assert "no_such_option" in _invalid(ctx.get_option, "no_such_option")
     assert ctx.get_option("expand_kernel_launches") >= 0
     _invalid(ctx.set_option, "expand_kernel_launches", 0)
+    for name in ("expand_xp_last_chunks", "expand_xp_last_shared_rows", "expand_group_item_launches"):
+        assert ctx.get_option(name) >= 0
+        _invalid(ctx.set_option, name, 0)
+    ctx.get_option("sssp_last_delta_log2")       # an exponent: any sign
+    _invalid(ctx.set_option, "sssp_last_delta_log2", 0)
     assert ctx.get_option("msf_last_entries_round3") >= 0
     _invalid(ctx.get_option, "msf_last_entries_round32")
     _invalid(ctx.get_option, "transpose_wb")     # process-wide, no stored value to read

@@ -34,24 +34,12 @@ def device(ctx, a: oracle.CSR):
     return ctx.mat_from_csr(a.nrows, a.ncols, a.rowptr, a.colidx)
 
 
-class Forced:
+def Forced(ctx, direct, **extra):
     """The partitioned form on any state size, the bit-parallel chain, the given direct mode (and whole-frontier settings or any
     other option that has a read-back, expand_mode included); what was set before comes back on exit."""
-
-    def __init__(self, ctx, direct, **extra):
-        self.ctx, self.opts = ctx, dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_direct=direct)
-        self.opts.update(extra)
-        self.found = {}
-
-    def __enter__(self):
-        for k, v in self.opts.items():
-            self.found[k] = self.ctx.get_option(k)
-            self.ctx.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in reversed(list(self.found.items())):
-            self.ctx.set_option(k, v)
-        self.found = {}
+    opts = dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_direct=direct)
+    opts.update(extra)
+    return ctx.options(**opts)
 
 
 # ---- a hand-built graph whose destinations cover every case of the fold ---------------------------------------------------

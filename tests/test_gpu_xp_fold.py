@@ -13,25 +13,12 @@ U64 = np.uint64
 I64 = np.int64
 
 
-class Forced:
+def Forced(ctx, fold, direct, **extra):
     """The partitioned form on any state size, the bit-parallel chain, the given fold and direct modes (plus any other option
     that has a read-back), the piece fold at every row width; what was set before comes back on exit."""
-
-    def __init__(self, ctx, fold, direct, **extra):
-        self.ctx = ctx
-        self.opts = dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_fold=fold, expand_xp_fold_min_words=2, expand_xp_direct=direct)
-        self.opts.update(extra)
-        self.found = {}
-
-    def __enter__(self):
-        for k, v in self.opts.items():
-            self.found[k] = self.ctx.get_option(k)
-            self.ctx.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in reversed(list(self.found.items())):
-            self.ctx.set_option(k, v)
-        self.found = {}
+    opts = dict(expand_mode=2, expand_xcd_min_mb=0, expand_xp_fold=fold, expand_xp_fold_min_words=2, expand_xp_direct=direct)
+    opts.update(extra)
+    return ctx.options(**opts)
 
 
 class Folds:

@@ -58,13 +58,19 @@ OPTIONS = [
     ("bc_batch", "range", 0, 64, 0),
     ("maxflow_global_every", "range", 0, 1 << 20, 0),
     ("bc_direction", "range", 0, 2, 0),
+    ("expand_group_items", "range", 0, 1, 1),
+    ("spdag_sides", "range", 0, 3, 0),
+    ("expand_xp_lookahead", "range", 0, 1, 1),
+    ("expand_xp_cut", "range", 0, 1, 1),
+    ("expand_xp_stream_wgs", "range", 0, 65536, 0),
 ]
 
 # read-only counters of fgpu_get_option (the table in ctx.hip); "msf_last_entries_round<k>" keeps its own parse
 COUNTERS = [
     "dist_self_calls", "expand_kernel_launches", "bfs_cp_last_mask", "bfs_pb_last_levels", "expand_scan_last_live",
     "expand_scan_last_passes", "expand_xp_piece_folds", "expand_xp_slot_folds", "expand_xp_last_direct", "expand_xp_last_groups",
-    "harmonic_last_entries", "harmonic_last_gathered",
+    "harmonic_last_entries", "harmonic_last_gathered", "sssp_last_delta_log2", "expand_xp_last_chunks", "expand_xp_last_shared_rows",
+    "expand_group_item_launches",
 ]
 
 
@@ -94,7 +100,7 @@ def test_header_documents_exactly_the_names_the_library_knows():
         m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*fgpu_info " + fn + r"\(", hdr, flags=re.S)
         assert m, f"no comment above {fn}"
         above[fn] = _quoted_names(m.group(1))
-    settable = {n for n, *_ in OPTIONS} | {"transpose_wb"}
+    settable = {n for n, *_ in OPTIONS} | {"transpose_wb", "sssp_delta_log2"}
     counters = set(COUNTERS) | {"msf_last_entries_round"}
     assert settable - above["fgpu_set_option"] == set(), "settable options the header does not list above fgpu_set_option"
     assert counters - above["fgpu_get_option"] == set(), "counters the header does not list above fgpu_get_option"
@@ -111,3 +117,60 @@ def test_malformed_fgpu_opts_raises_before_any_library_call(monkeypatch):
         with pytest.raises(ValueError) as e:
             engine.Context(0)
         assert repr(bad.split(",")[-1]) in str(e.value)
+
+
+def _stub_context(values, refused=None):
+    """An engine.Context that opens nothing: its options are a dict, every call is recorded, `refused` cannot be set."""
+    from falkordb_amd import _ffi, engine
+
+    class Stub(engine.Context):
+        def __init__(self):
+            self.values, self.calls = dict(values), []
+
+        def get_option(self, name):
+            self.calls.append(("get", name))
+            return self.values[name]
+
+        def set_option(self, name, value):
+            self.calls.append(("set", name, value))
+            if name == refused:
+                raise _ffi.FgpuError(_ffi.FGPU_INVALID, f"{name} refused")
+            self.values[name] = value
+
+        def close(self):
+            pass
+
+    return Stub()
+
+
+def test_options_guard_sets_in_order_and_restores_in_reverse():
+    found = {"a": 1, "b": 2, "c": 3}
+    ctx = _stub_context(found)
+    with ctx.options(a=10, b=20, c=30):
+        assert ctx.values == {"a": 10, "b": 20, "c": 30}
+    assert ctx.values == found
+    assert ctx.calls == [("get", "a"), ("set", "a", 10), ("get", "b"), ("set", "b", 20), ("get", "c"), ("set", "c", 30),
+                         ("set", "c", 3), ("set", "b", 2), ("set", "a", 1)]
+
+
+def test_options_guard_restores_when_the_body_raises():
+    ctx = _stub_context({"a": 1, "b": 2})
+    with pytest.raises(KeyError, match="from the body"):
+        with ctx.options(a=10, b=20):
+            assert ctx.values == {"a": 10, "b": 20}
+            raise KeyError("from the body")
+    assert ctx.values == {"a": 1, "b": 2}
+    assert ctx.calls[-2:] == [("set", "b", 2), ("set", "a", 1)]
+
+
+def test_options_guard_undoes_a_half_made_entry():
+    from falkordb_amd._ffi import FGPU_INVALID, FgpuError
+    ctx = _stub_context({"a": 1, "b": 2, "c": 3}, refused="b")
+    entered = False
+    with pytest.raises(FgpuError) as e:
+        with ctx.options(a=10, b=20, c=30):
+            entered = True
+    assert e.value.code == FGPU_INVALID and not entered
+    assert ctx.values == {"a": 1, "b": 2, "c": 3}
+    # a is put back, b (never changed) is not set again, c is never read or set
+    assert ctx.calls == [("get", "a"), ("set", "a", 10), ("get", "b"), ("set", "b", 20), ("set", "a", 1)]
