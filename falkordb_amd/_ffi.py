@@ -96,6 +96,7 @@ SIGNATURES = {
     "fgpu_maxflow": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(u64p), C.POINTER(u64p),
                                  C.POINTER(C.POINTER(C.c_double)), u64p, u64p]),
     "fgpu_sssp": (C.c_int32, [vp, vp, C.c_uint64, C.POINTER(C.c_double), i64p, u64p]),
+    "fgpu_sssp_hops": (C.c_int32, [vp, vp, C.c_uint64, C.c_int32, C.POINTER(C.c_double), u64p]),
     "fgpu_shortest_dag": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int64, i64p, u64p, C.POINTER(u64p), C.POINTER(u64p),
                                       C.POINTER(u64p), u64p]),
     "fgpu_mat_min_val": (C.c_int32, [vp, vp, u64p, C.POINTER(C.c_int)]),

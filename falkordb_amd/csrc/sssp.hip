@@ -2,6 +2,8 @@
 // (graph/src/runtime/functions/algo_procedures.rs:2156-2257; no LAGraph call stands behind it).  Near / far delta-stepping
 // for the distances, then a level-synchronous search over the tight entries for the parents; the rules (what a weight may be,
 // which distance and which parent come back) are written out in include/fgpu.h.
+// fgpu_sssp_hops, the hop-bounded table that prunes the procedure's enumeration shapes, is the second half of the file; it shares
+// the weight pass, sp_weight and the row kernel's entry-parallel layout.
 //
 // Phase 1, distances.  dist[] holds binary64 bit patterns: non-negative finite doubles order as unsigned integers and
 // 0x7FF0... is "unreached".  T is the upper edge of the current bucket, a multiple of the width delta (a power of two).
@@ -77,6 +79,27 @@ __device__ __forceinline__ u64 sp_weight(const u64* __restrict__ vals, u32 i) {
     if (!vals) return SP_ONE;
     const u64 b = vals[i];
     return b == SP_NEG0 ? 0ull : b;
+}
+
+// the two steps of the entry-parallel layout both rows kernels use: 64 rows per wavefront, their lengths summed along the
+// lanes, then a lane per ENTRY that finds its row in the LDS copy of the sums
+__device__ __forceinline__ u32 wave_inclusive_sum(u32 x, u32 lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 y = __shfl_up(x, d, 64);
+        if (lane >= (u32)d) x += y;
+    }
+    return x;
+}
+// off[0 .. 64]: the exclusive prefix of the 64 rows' lengths; the largest row with off[row] <= e
+__device__ __forceinline__ u32 row_of_entry(const u32* off, u32 e) {
+    u32 lo = 0, hi = 64;
+#pragma unroll
+    for (int it = 0; it < 6; ++it) {
+        const u32 mid = (lo + hi) >> 1;
+        if (off[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // one pass over the values: NaNs and negative weights are counted, the finite ones summed (the mean behind delta)
@@ -234,12 +257,7 @@ __global__ __launch_bounds__(256) void sssp_rows_kernel(CsrView a, const u64* __
                 if (len >= HUB_DEG) { hubmark[u] = stamp; len = 0; }
             }
         }
-        u32 inc = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u32 y = __shfl_up(inc, d, 64);
-            if (lane >= (u32)d) inc += y;
-        }
+        const u32 inc = wave_inclusive_sum(len, lane);
         const u32 total = (u32)__builtin_amdgcn_readlane((int)inc, 63);
         if (!total) continue;   // (wave-uniform)
         __builtin_amdgcn_wave_barrier();   // (the lanes of the trip before are done with the arrays)
@@ -253,12 +271,7 @@ __global__ __launch_bounds__(256) void sssp_rows_kernel(CsrView a, const u64* __
         for (u32 e0 = 0; e0 < total; e0 += 64) {
             const u32 e = e0 + lane;
             const bool valid = e < total;
-            u32 lo = 0, hi = 64;   // largest lo with off[lo] <= e
-#pragma unroll
-            for (int it = 0; it < 6; ++it) {
-                const u32 mid = (lo + hi) >> 1;
-                if (off[mid] <= e) lo = mid; else hi = mid;
-            }
+            const u32 lo = row_of_entry(off, e);
             const u32 idx = valid ? rbs[lo] + (e - off[lo]) : 0u;
             sssp_relax(valid, us[lo], dus[lo], idx, a.colidx, vals, dist, T, ctl, ls, nnext, fcur, infar, lane);
         }
@@ -428,9 +441,240 @@ __global__ __launch_bounds__(256) void sssp_parent_kernel(const u32* __restrict_
         out[v] = par[v] == SP_UNSET ? -1ll : (long long)par[v];
 }
 
+// ---- fgpu_sssp_hops: the hop-bounded table ---------------------------------------------------------------------------------------
+// D_h = the cheapest route of at most h arcs, one row of the table per h (the rules: include/fgpu.h).  Round h is four launches
+// that take every decision on the device (HopsCtl), so the host queues max_hops rounds blindly and reads back once:
+//   copy     D_h = D_{h-1}, every vertex.  A round relaxes INTO D_h and reads only D_{h-1}: one round never travels two arcs;
+//   rows     the frontier (the vertices round h-1 lowered; a vertex that did not change contributed its D_{h-1} already, so
+//            pushing from the changed ones alone is exact), 64 of it per wavefront, rows below HUB_DEG relaxed entry-parallel
+//            as sssp_rows_kernel does, longer rows stamped in hubmark[] with the round;
+//   hubs     a workgroup per hub chunk of a row stamped this round;
+//   control  one thread: the two frontier lists swap, the first round that lowered nothing is recorded.
+// Once the frontier is empty the copy alone runs: the remaining rows repeat the last live one.
+// Concurrency rules, beyond those of phase 1 above:
+//   - D_{h-1} is read-only in round h (plain loads of words earlier launches wrote); D_h is written by the copy launch, then
+//     only lowered by atomicMin in the rows and hubs launches, behind a plain-load filter (a stale word is a larger one);
+//   - a lane whose atomic lowered D_h[v] claims v for the next frontier with atomicExch(&seen[v], h): the one lane that did not
+//     get h back appends, so a vertex is in a frontier once per round and a list of n slots cannot overflow (checked all the same);
+//   - hubmark[] has one value per launch (h), the control block one writer (the control launch) or atomics.
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): hops_init 8 VGPRs, hops_start 2, hops_copy 6, hops_rows 42
+// VGPRs and 5168 B static LDS, hops_hubs 18, hops_control 4; no other LDS, no kernel spills (SGPR or VGPR), no scratch.
+struct HopsCtl {
+    u32 overflow;
+    u32 cur;        // which list is this round's frontier
+    u32 cnt[2];     // list lengths
+    u32 fixed;      // the first round that lowered nothing, 0 = none yet
+    u32 pad;
+    unsigned long long rounds, popped, entries;   // stats[0..2]
+};
+
+__global__ __launch_bounds__(256) void hops_init_kernel(u64* __restrict__ d0, u32* __restrict__ seen, u32* __restrict__ hubmark,
+                                                       u32 n) {
+    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
+        d0[v] = SP_INF;
+        seen[v] = 0;
+        hubmark[v] = 0;
+    }
+}
+
+__global__ void hops_start_kernel(HopsCtl* ctl, u64* __restrict__ d0, u32* __restrict__ list0, u32 src) {
+    d0[src] = 0;
+    list0[0] = src;
+    ctl->cnt[0] = 1;
+}
+
+__global__ __launch_bounds__(256) void hops_copy_kernel(const u64* __restrict__ prev, u64* __restrict__ cur, u32 n) {
+    for (u32 v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) cur[v] = prev[v];
+}
+
+// relaxes the entry at position idx of row u (du = D_{h-1}[u]) into dcur = D_h; every lane of the wavefront calls, `valid` or not
+__device__ __forceinline__ void hops_relax(bool valid, u32 u, u64 du, u32 idx, const u32* __restrict__ col,
+                                           const u64* __restrict__ vals, u64* dcur, u32* seen, u32 h, HopsCtl* ctl,
+                                           u32* ncnt, u32* __restrict__ next, u32 cap, u32 lane) {
+    bool fresh = false;
+    u32 c = 0;
+    if (valid) {
+        c = col[idx];
+        const double s = __longlong_as_double((long long)du) + __longlong_as_double((long long)sp_weight(vals, idx));
+        const u64 nd = (u64)__double_as_longlong(s);
+        if (c != u && nd < SP_INF && dcur[c] > nd && atomicMin((unsigned long long*)&dcur[c], (unsigned long long)nd) > nd)
+            fresh = atomicExch(&seen[c], h) != h;
+    }
+    const u64 mask = __ballot(fresh);
+    if (!mask) return;
+    u32 base = 0;
+    if (lane == 0) base = atomicAdd(ncnt, (u32)__builtin_popcountll(mask));
+    base = __shfl(base, 0, 64);
+    if (fresh) {
+        const u64 at = (u64)base + wave_slot(mask, lane);
+        if (at < cap) next[at] = c;
+        else ctl->overflow = 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void hops_rows_kernel(CsrView a, const u64* __restrict__ vals, const u64* __restrict__ dprev,
+                                                       u64* dcur, HopsCtl* ctl, u32* list0, u32* list1, u32 cap, u32* seen,
+                                                       u32* __restrict__ hubmark, u32 h) {
+    __shared__ u32 s_off[4][65];   // exclusive prefix of the 64 rows' taken lengths
+    __shared__ u32 s_rb[4][64];    // first entry of each row
+    __shared__ u32 s_u[4][64];     // the row
+    __shared__ u64 s_du[4][64];    // its D_{h-1}
+    const u32 lane = lane_id();
+    const u32 wv = threadIdx.x >> 6;
+    const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (gridDim.x * 256) >> 6;
+    const u32 cur = ctl->cur;
+    const u32 count = ctl->cnt[cur];
+    const u32* __restrict__ curv = cur ? list1 : list0;
+    u32* next = cur ? list0 : list1;
+    u32* ncnt = &ctl->cnt[cur ^ 1u];
+    u32* off = s_off[wv];
+    u32* rbs = s_rb[wv];
+    u32* us = s_u[wv];
+    u64* dus = s_du[wv];
+    u64 popped = 0, read = 0;
+    const u32 ngroups = (count + 63) >> 6;
+    for (u32 g = wave; g < ngroups; g += nwaves) {
+        const u32 i = (g << 6) + lane;
+        u32 u = 0, rb = 0, len = 0;
+        u64 du = 0;
+        if (i < count) {
+            u = curv[i];
+            du = dprev[u];
+            ++popped;
+            rb = a.rowptr[u];
+            len = a.rowptr[u + 1] - rb;
+            if (len >= HUB_DEG) { hubmark[u] = h; len = 0; }
+        }
+        const u32 inc = wave_inclusive_sum(len, lane);
+        const u32 total = (u32)__builtin_amdgcn_readlane((int)inc, 63);
+        if (!total) continue;   // (wave-uniform)
+        __builtin_amdgcn_wave_barrier();   // (the lanes of the trip before are done with the arrays)
+        off[lane + 1] = inc;
+        if (lane == 0) off[0] = 0;
+        rbs[lane] = rb;
+        us[lane] = u;
+        dus[lane] = du;
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) read += total;
+        for (u32 e0 = 0; e0 < total; e0 += 64) {
+            const u32 e = e0 + lane;
+            const bool valid = e < total;
+            const u32 lo = row_of_entry(off, e);
+            const u32 idx = valid ? rbs[lo] + (e - off[lo]) : 0u;
+            hops_relax(valid, us[lo], dus[lo], idx, a.colidx, vals, dcur, seen, h, ctl, ncnt, next, cap, lane);
+        }
+    }
+    block_add_u64(popped, &ctl->popped);
+    block_add_u64(read, &ctl->entries);
+}
+
+// the rows of HUB_DEG entries and more: a workgroup per chunk of the snapshot's hub list, for the rows stamped in this round
+__global__ __launch_bounds__(256) void hops_hubs_kernel(const u32* __restrict__ hub, u32 n_hub, const u32* __restrict__ col,
+                                                       const u64* __restrict__ vals, const u64* __restrict__ dprev, u64* dcur,
+                                                       HopsCtl* ctl, u32* list0, u32* list1, u32 cap, u32* seen,
+                                                       const u32* __restrict__ hubmark, u32 h) {
+    const u32 lane = lane_id();
+    const u32 cur = ctl->cur;
+    u32* next = cur ? list0 : list1;
+    u32* ncnt = &ctl->cnt[cur ^ 1u];
+    u64 read = 0;
+    for (u32 k = blockIdx.x; k < n_hub; k += gridDim.x) {
+        const u32 row = hub[3 * k], b = hub[3 * k + 1], e = hub[3 * k + 2];
+        if (hubmark[row] != h) continue;   // (workgroup-uniform: written by the launch before)
+        const u64 du = dprev[row];
+        for (u32 i0 = b; i0 < e; i0 += 256) {   // (whole waves stay in the loop: the ballot of hops_relax)
+            const u32 i = i0 + threadIdx.x;
+            hops_relax(i < e, row, du, i < e ? i : b, col, vals, dcur, seen, h, ctl, ncnt, next, cap, lane);
+        }
+        if (threadIdx.x == 0) read += e - b;
+    }
+    if (threadIdx.x == 0 && read) atomicAdd(&ctl->entries, (unsigned long long)read);
+}
+
+// one thread, after the relaxations of round h
+__global__ void hops_control_kernel(HopsCtl* ctl, u32 h) {
+    const u32 cur = ctl->cur, nxt = cur ^ 1u;
+    if (ctl->cnt[cur]) ++ctl->rounds;
+    if (!ctl->cnt[nxt] && !ctl->fixed) ctl->fixed = h;   // nothing was lowered: D_h == D_{h-1}
+    ctl->cnt[cur] = 0;   // the list just read is the next one to fill
+    ctl->cur = nxt;
+}
+
+// the one reduction pass over W's values in front of either search: a NaN or a negative weight is FGPU_INVALID
+static fgpu_info sssp_check_weights(fgpu_ctx* ctx, const char* who, const fgpu_mat* W, SsspCtl* ctl) {
+    const u64* vals = (const u64*)W->vals;
+    if (!vals || !W->nnz) return FGPU_OK;
+    FGPU_TRY(launch(sssp_weights_kernel, dim3(capped_grid(ctx, W->nnz, 1024, 8)), dim3(256), 0, ctx->stream(), vals, W->nnz, ctl));
+    u32 w[2];
+    FGPU_TRY(read_words(ctx, (const u32*)&ctl->bad, 2, w));
+    FGPU_REQUIRE(!(w[0] | w[1]), FGPU_INVALID, "%s: a weight is NaN or negative", who);
+    return FGPU_OK;
+}
+
 }  // namespace fgpu
 
 using namespace fgpu;
+
+extern "C" fgpu_info fgpu_sssp_hops(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, int32_t max_hops, double* table,
+                                    uint64_t stats[4]) {
+    FGPU_REQUIRE(ctx && W && table, FGPU_NULL_POINTER, "fgpu_sssp_hops: NULL argument");
+    FGPU_TRY(check_adjacency("fgpu_sssp_hops", W, nullptr));
+    FGPU_REQUIRE(max_hops >= 0 && max_hops <= FGPU_SSSP_HOPS_MAX, FGPU_INVALID, "fgpu_sssp_hops: max_hops must be 0 .. %d, not %d",
+                 FGPU_SSSP_HOPS_MAX, (int)max_hops);
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    const u32 n = (u32)W->nrows;
+    if (n == 0) return FGPU_OK;
+    FGPU_REQUIRE(src < W->nrows, FGPU_OUT_OF_BOUNDS, "fgpu_sssp_hops: src out of range");
+    DenseInputs in;
+    FGPU_TRY(in.a(ctx, W, true));   // (a hypersparse W keeps its values)
+    FGPU_TRY(mat_ensure_finalized(W));   // the hub list
+    hipStream_t st = ctx->stream();
+    const u32 nch = W->n_hub_chunks;
+    const u64* vals = (const u64*)W->vals;
+    {
+        DevBuf<SsspCtl> wctl;
+        FGPU_TRY(wctl.alloc(ctx, 1));
+        FGPU_HIP(hipMemsetAsync(wctl.p, 0, sizeof(SsspCtl), st));
+        FGPU_TRY(sssp_check_weights(ctx, "fgpu_sssp_hops", W, wctl.p));
+    }
+    const u32 H = (u32)max_hops;
+    DevBuf<HopsCtl> ctl;
+    DevBuf<u64> tab;
+    DevBuf<u32> list, seen, hubmark;
+    FGPU_TRY(ctl.alloc(ctx, 1));
+    FGPU_TRY(tab.alloc(ctx, ((size_t)H + 1) * n));
+    FGPU_TRY(list.alloc(ctx, 2 * (size_t)n));   // a vertex is in a frontier once per round
+    FGPU_TRY(seen.alloc(ctx, n));
+    FGPU_TRY(hubmark.alloc(ctx, n));
+    FGPU_HIP(hipMemsetAsync(ctl.p, 0, sizeof(HopsCtl), st));
+    const u32 vgrid = capped_grid(ctx, n, 256, 4), rgrid = capped_grid(ctx, n, 256, 8);
+    FGPU_TRY(launch(hops_init_kernel, dim3(vgrid), dim3(256), 0, st, tab.p, seen.p, hubmark.p, n));
+    FGPU_TRY(launch(hops_start_kernel, dim3(1), dim3(1), 0, st, ctl.p, tab.p, list.p, (u32)src));
+    for (u32 h = 1; h <= H; ++h) {   // (h is never 0, what seen[] and hubmark[] start as)
+        const u64* dprev = tab.p + (size_t)(h - 1) * n;
+        u64* dcur = tab.p + (size_t)h * n;
+        FGPU_TRY(launch(hops_copy_kernel, dim3(vgrid), dim3(256), 0, st, dprev, dcur, n));
+        FGPU_TRY(launch(hops_rows_kernel, dim3(rgrid), dim3(256), 0, st, view_of(W), vals, dprev, dcur, ctl.p, list.p, list.p + n, n,
+                        seen.p, hubmark.p, h));
+        if (nch)
+            FGPU_TRY(launch(hops_hubs_kernel, dim3(hub_grid(ctx, W)), dim3(256), 0, st, (const u32*)W->hub_chunks.p, nch,
+                            (const u32*)W->colidx, vals, dprev, dcur, ctl.p, list.p, list.p + n, n, seen.p,
+                            (const u32*)hubmark.p, h));
+        FGPU_TRY(launch(hops_control_kernel, dim3(1), dim3(1), 0, st, ctl.p, h));
+    }
+    HopsCtl hc;
+    FGPU_TRY(ctx->d2h(&hc, ctl.p, sizeof(HopsCtl)));
+    FGPU_REQUIRE(!hc.overflow, FGPU_DEVICE, "fgpu_sssp_hops: a frontier outgrew its bound");
+    FGPU_TRY(ctx->d2h(table, tab.p, ((size_t)H + 1) * n * sizeof(double)));   // one DMA when table[] is pinned
+    if (stats) {
+        stats[0] = hc.rounds;
+        stats[1] = hc.popped;
+        stats[2] = hc.entries;
+        stats[3] = hc.fixed ? hc.fixed : H + 1;
+    }
+    FGPU_HIP(hipStreamSynchronize(st));
+    return FGPU_OK;
+}
 
 extern "C" fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, double* dist, int64_t* parent, uint64_t stats[4]) {
     FGPU_REQUIRE(ctx && W && dist, FGPU_NULL_POINTER, "fgpu_sssp: NULL argument");
@@ -449,12 +693,7 @@ extern "C" fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, d
     DevBuf<SsspCtl> ctl;
     FGPU_TRY(ctl.alloc(ctx, 1));
     FGPU_HIP(hipMemsetAsync(ctl.p, 0, sizeof(SsspCtl), st));
-    if (vals && nnz) {
-        FGPU_TRY(launch(sssp_weights_kernel, dim3(capped_grid(ctx, nnz, 1024, 8)), dim3(256), 0, st, vals, nnz, ctl.p));
-        u32 w[2];
-        FGPU_TRY(read_words(ctx, (const u32*)&ctl.p->bad, 2, w));
-        FGPU_REQUIRE(!(w[0] | w[1]), FGPU_INVALID, "fgpu_sssp: a weight is NaN or negative");
-    }
+    FGPU_TRY(sssp_check_weights(ctx, "fgpu_sssp", W, ctl.p));
     // a launch appends at most one near entry per entry it reads, a split at most n; a vertex is in the far list once
     const u64 ncap64 = (nnz > n ? nnz : (u64)n) + 1;
     FGPU_REQUIRE(ncap64 < 0xFFFFFFFFull, FGPU_INVALID, "fgpu_sssp: too many entries");

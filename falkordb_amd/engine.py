@@ -673,6 +673,23 @@ def sssp(ctx: Context, W: Mat, src: int, want_parent: bool = True, stats: bool =
     return dist, parent
 
 
+def sssp_hops(ctx: Context, W: Mat, src: int, max_hops: int, stats: bool = False, out=None):
+    """fgpu_sssp_hops: the hop-bounded shortest-path table from src over the weight matrix W (fgpu_sssp's rules for W) — row h
+    holds, per vertex, the weight of the cheapest route of at most h arcs, +inf where there is none; max_hops is 0 .. 32.  out: a
+    (max_hops + 1, n) float64 array to fill instead of a fresh one (a Context.host_array() block is filled by DMA).  Returns the
+    (max_hops + 1, n) float64 table and, when stats=True, a second item: the four counters [rounds with a frontier, frontier
+    entries taken, entries read, the first h whose row equals the one before (max_hops + 1: none)]."""
+    n = W.nrows
+    rows = int(max_hops) + 1 if 0 <= max_hops <= 32 else 1   # (out of range: the call refuses before it writes)
+    table = out if out is not None else np.zeros((rows, n), dtype=np.float64)
+    assert table.dtype == np.float64 and table.shape == (rows, n) and table.flags.c_contiguous
+    st = np.zeros(4, dtype=np.uint64) if stats else None
+    check(ctx.lib.fgpu_sssp_hops(ctx._h, W._h, C.c_uint64(src), C.c_int32(max_hops), _p(table, C.POINTER(C.c_double)), _p(st)))
+    if stats:
+        return table, [int(x) for x in st]
+    return table
+
+
 def shortest_dag(ctx: Context, A: Mat, At: Mat | None, src: int, dst: int, max_hops: int = -1, stats: bool = False):
     """fgpu_shortest_dag: the shortest-path DAG between src and dst over the pattern A (At its transpose, None = built for the
     call) — what allShortestPaths' predecessor walk reads.  src == dst asks for the shortest cycle through src.  Returns

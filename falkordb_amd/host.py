@@ -636,6 +636,50 @@ class Graph:
             return None
         return nv, ev, weight.value, cost.value
 
+    def _path_rows(self, fn, head, types, direction, max_len, max_cost, path_count, weights, costs, tail, stats):
+        def attr(d):
+            if d is None:
+                return None, None, 0
+            ids = np.ascontiguousarray(list(d.keys()), dtype=np.uint64)
+            vals = np.ascontiguousarray([float(x) for x in d.values()], dtype=np.float64)
+            return ids.ctypes.data_as(u64p), vals.ctypes.data_as(C.POINTER(C.c_double)), len(ids), (ids, vals)
+        w, c = attr(weights), attr(costs)
+        n = C.c_uint64()
+        off, nodes, edges = u64p(), u64p(), u64p()
+        pw, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        st = (C.c_int64 * 4)()
+        _ck(fn(self.h, *head, ",".join(types).encode(), C.c_int({"outgoing": 0, "incoming": 1, "both": 2}[direction]),
+               C.c_int64(-1 if max_len is None else max_len), C.c_int(0 if max_cost is None else 1),
+               C.c_double(0.0 if max_cost is None else float(max_cost)), C.c_int64(path_count), w[0], w[1], C.c_uint64(w[2]),
+               c[0], c[1], C.c_uint64(c[2]), *tail, C.byref(n), C.byref(off), C.byref(nodes), C.byref(edges), C.byref(pw),
+               C.byref(pc), st))
+        k = n.value
+        o = _take(off, k + 1)
+        total = int(o[-1])
+        nv, ev = _take(nodes, total + k), _take(edges, total)
+        ws, cs = _take(pw, k, np.float64), _take(pc, k, np.float64)
+        rows = [(nv[int(o[r]) + r:int(o[r + 1]) + r + 1], ev[int(o[r]):int(o[r + 1])], float(ws[r]), float(cs[r])) for r in range(k)]
+        if stats:
+            return rows, {"examined": st[0], "pruned_hops": st[1], "pruned_weight": st[2], "table_rows": st[3]}
+        return rows
+
+    def algo_sp_paths_rows(self, source, target, types=(), direction="outgoing", max_len=None, max_cost=None, path_count=1,
+                           weights=None, costs=None, prune=True, max_examined=0, stats=False):
+        """CALL algo.SPpaths({sourceNode, targetNode, relTypes, relDirection, weightProp, costProp, maxLen, maxCost, pathCount})
+        YIELD path, pathWeight, pathCost in every shape -> a list of (nodes uint64[], edges uint64[], weight, cost) in the
+        procedure's order; with stats=True also the walk's counters (see fh_algo_sp_paths_rows).  max_len / max_cost None = not
+        given; weights / costs as algo_sp_paths takes them; prune=False walks as the reference does, without the device's
+        table; max_examined: a budget of examined successors, 0 = none."""
+        return self._path_rows(self.L.fh_algo_sp_paths_rows, (C.c_uint64(source), C.c_uint64(target)), types, direction, max_len,
+                               max_cost, path_count, weights, costs, (C.c_int(1 if prune else 0), C.c_uint64(max_examined)), stats)
+
+    def algo_ss_paths(self, source, types=(), direction="outgoing", max_len=None, max_cost=None, path_count=1, weights=None,
+                      costs=None, max_examined=0, stats=False):
+        """CALL algo.SSpaths({sourceNode, relTypes, relDirection, weightProp, costProp, maxLen, maxCost, pathCount}) YIELD path,
+        pathWeight, pathCost -> rows as algo_sp_paths_rows returns them (see fh_algo_ss_paths)."""
+        return self._path_rows(self.L.fh_algo_ss_paths, (C.c_uint64(source),), types, direction, max_len, max_cost, path_count,
+                               weights, costs, (C.c_uint64(max_examined),), stats)
+
     def algo_betweenness(self, labels=(), types=(), sampling_size=16, sampling_seed=0):
         """CALL algo.betweenness({nodeLabels, relationshipTypes, samplingSize, samplingSeed}) YIELD node, score ->
         (nodes, scores float64).  Several labels select the union of their nodes (see fh_algo_betweenness)."""

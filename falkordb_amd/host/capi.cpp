@@ -839,6 +839,79 @@ int fh_algo_sp_paths(fh_graph* g, uint64_t source, uint64_t target, const char* 
     });
 }
 
+// algo.SPpaths in every shape and algo.SSpaths: the rows flattened — row r has edges[offsets[r] .. offsets[r + 1]) and the
+// nodes[offsets[r] + r .. offsets[r + 1] + r + 1) (one node more than edges)
+static PathQuery path_query(const char* who, const char* types, int direction, int64_t max_len, int has_max_cost, double max_cost,
+                            int64_t path_count, const uint64_t* w_edge_ids, const double* w_vals, uint64_t n_w,
+                            const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int prune, uint64_t max_examined) {
+    if (direction < 0 || direction > 2) throw std::invalid_argument(std::string(who) + ": direction must be 0, 1 or 2");
+    PathQuery q;
+    q.types = csv(types);
+    q.dir = (Direction)direction;
+    q.max_len = max_len < 0 || max_len >= (int64_t)UINT32_MAX ? UINT32_MAX : (uint32_t)max_len;
+    if (has_max_cost) q.max_cost = max_cost;
+    q.path_count = path_count;
+    q.w_edge_ids = w_edge_ids; q.w_vals = w_vals; q.n_w = n_w;
+    q.c_edge_ids = c_edge_ids; q.c_vals = c_vals; q.n_c = n_c;
+    q.prune = prune != 0;
+    q.max_examined = max_examined;
+    return q;
+}
+
+static void hand_paths(const std::vector<PathRow>& rows, const PathEnumStats& st, uint64_t* n_rows, uint64_t** offsets,
+                       uint64_t** nodes, uint64_t** edges, double** weights, double** costs, int64_t stats[4]) {
+    std::vector<u64> off(1, 0), nv, ev;
+    std::vector<double> w, c;
+    for (const PathRow& r : rows) {
+        nv.insert(nv.end(), r.nodes.begin(), r.nodes.end());
+        ev.insert(ev.end(), r.edges.begin(), r.edges.end());
+        off.push_back(ev.size());
+        w.push_back(r.weight);
+        c.push_back(r.cost);
+    }
+    *n_rows = rows.size();
+    *offsets = hand(off);
+    *nodes = hand(nv);
+    *edges = hand(ev);
+    *weights = hand(w);
+    *costs = hand(c);
+    if (stats) {
+        stats[0] = (int64_t)st.examined;
+        stats[1] = (int64_t)st.pruned_hops;
+        stats[2] = (int64_t)st.pruned_weight;
+        stats[3] = st.table_rows;
+    }
+}
+
+int fh_algo_sp_paths_rows(fh_graph* g, uint64_t source, uint64_t target, const char* types, int direction, int64_t max_len,
+                          int has_max_cost, double max_cost, int64_t path_count, const uint64_t* w_edge_ids, const double* w_vals,
+                          uint64_t n_w, const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int prune,
+                          uint64_t max_examined, uint64_t* n_rows, uint64_t** offsets, uint64_t** nodes, uint64_t** edges,
+                          double** weights, double** costs, int64_t stats[4]) {
+    return guard([&] {
+        const PathQuery q = path_query("fh_algo_sp_paths_rows", types, direction, max_len, has_max_cost, max_cost, path_count,
+                                       w_edge_ids, w_vals, n_w, c_edge_ids, c_vals, n_c, prune, max_examined);
+        PathEnumStats st;
+        const std::vector<PathRow> rows = timed([&] { return algo_sp_paths_rows(g->g, source, target, q, &st); });
+        hand_paths(rows, st, n_rows, offsets, nodes, edges, weights, costs, stats);
+        return 0;
+    });
+}
+
+int fh_algo_ss_paths(fh_graph* g, uint64_t source, const char* types, int direction, int64_t max_len, int has_max_cost,
+                     double max_cost, int64_t path_count, const uint64_t* w_edge_ids, const double* w_vals, uint64_t n_w,
+                     const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, uint64_t max_examined, uint64_t* n_rows,
+                     uint64_t** offsets, uint64_t** nodes, uint64_t** edges, double** weights, double** costs, int64_t stats[4]) {
+    return guard([&] {
+        const PathQuery q = path_query("fh_algo_ss_paths", types, direction, max_len, has_max_cost, max_cost, path_count, w_edge_ids,
+                                       w_vals, n_w, c_edge_ids, c_vals, n_c, 0, max_examined);
+        PathEnumStats st;
+        const std::vector<PathRow> rows = timed([&] { return algo_ss_paths(g->g, source, q, &st); });
+        hand_paths(rows, st, n_rows, offsets, nodes, edges, weights, costs, stats);
+        return 0;
+    });
+}
+
 // algo.betweenness: labels / types = comma lists, "" = all
 int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int64_t sampling_size, int64_t sampling_seed,
                         uint64_t** nodes, double** scores, uint64_t* n) {

@@ -1296,57 +1296,90 @@ MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& label
     return res;
 }
 
-// ---- algo.SPpaths (the single cheapest path) ------------------------------------------------------------
-SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
-                           const u64* w_edge_ids, const double* w_vals, u64 n_w,
-                           const u64* c_edge_ids, const double* c_vals, u64 n_c) {
-    SpPathResult res;
-    const u64 n = g.node_cap();
-    if (source == target) return res;                                    // :2559-2567
-    if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return res;
-    std::vector<u64> tids;                                               // the known ones, each once (graph.rs:1803-1810)
+// ---- algo.SPpaths / algo.SSpaths ------------------------------------------------------------------------
+namespace {
+// the tensors a relTypes list selects: none named = every tensor, else the known names in the order listed (graph.rs:1803-1810);
+// `once` drops a repeated name (one matrix entry per pair either way), the enumeration keeps it: its successors come twice
+std::vector<u64> path_tids(const Graph& g, const std::vector<std::string>& types, bool once) {
+    std::vector<u64> tids;
     if (types.empty())
         for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
     else
         for (auto& t : types)
             if (auto id = g.type_id(t))
-                if (std::find(tids.begin(), tids.end(), *id) == tids.end()) tids.push_back(*id);
-    const bool unit = w_edge_ids == nullptr;
-    std::unordered_map<u64, double> wattr, cattr;                        // edge_numeric_attr (:2049-2062)
-    if (!unit) {
-        wattr.reserve(n_w * 2);
-        for (u64 k = 0; k < n_w; ++k) wattr[w_edge_ids[k]] = w_vals[k];
+                if (!once || std::find(tids.begin(), tids.end(), *id) == tids.end()) tids.push_back(*id);
+    return tids;
+}
+
+// weightProp / costProp as data: edge_numeric_attr (:2049-2062)
+struct PathAttrs {
+    bool unit = true;
+    std::unordered_map<u64, double> wattr, cattr;
+    PathAttrs(const u64* w_edge_ids, const double* w_vals, u64 n_w, const u64* c_edge_ids, const double* c_vals, u64 n_c)
+        : unit(w_edge_ids == nullptr) {
+        if (!unit) {
+            wattr.reserve(n_w * 2);
+            for (u64 k = 0; k < n_w; ++k) wattr[w_edge_ids[k]] = w_vals[k];
+        }
+        if (c_edge_ids) {
+            cattr.reserve(n_c * 2);
+            for (u64 k = 0; k < n_c; ++k) cattr[c_edge_ids[k]] = c_vals[k];
+        }
     }
-    if (c_edge_ids) {
-        cattr.reserve(n_c * 2);
-        for (u64 k = 0; k < n_c; ++k) cattr[c_edge_ids[k]] = c_vals[k];
+    double weight(u64 edge) const {
+        if (unit) return 1.0;
+        const auto it = wattr.find(edge);
+        return it != wattr.end() ? it->second : 1.0;
     }
-    // one (weight, relationship) per ordered pair in traversal direction
-    struct Kept { double w; u64 edge; };
-    std::unordered_map<u64, Kept> best;
-    auto offer = [&](u64 from, u64 to, const Kept& y) {
+    double cost(u64 edge) const {
+        const auto it = cattr.find(edge);
+        return it != cattr.end() ? it->second : 0.0;
+    }
+};
+
+// one (weight, relationship) per ordered pair (from << 32 | to) in traversal direction: the smallest weight over the selected
+// tensors and their multi-edges, ties to the smallest id; self-loops and non-finite weights left out, a negative weight throws
+struct PairKept { double w; u64 edge; };
+using PairWeights = std::unordered_map<u64, PairKept>;
+PairWeights pair_weights(const Graph& g, const std::vector<u64>& tids, Direction dir, const PathAttrs& at,
+                         const char* who = "algo.SPpaths") {
+    PairWeights best;
+    auto offer = [&](u64 from, u64 to, const PairKept& y) {
         auto [it, fresh] = best.try_emplace((from << 32) | to, y);
         if (fresh) return;
-        Kept& x = it->second;
+        PairKept& x = it->second;
         if (y.w < x.w || (y.w == x.w && y.edge < x.edge)) x = y;
     };
     for (u64 t : tids) {
         for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
             if (e.row == e.col) continue;
-            double w = 1.0;
-            if (!unit) {
-                const auto it = wattr.find(e.val);
-                if (it != wattr.end()) w = it->second;
-            }
+            double w = at.weight(e.val);
             if (!std::isfinite(w)) continue;                             // never relaxed (:2213)
             if (w < 0.0)
-                throw std::invalid_argument("algo.SPpaths: relationship " + std::to_string(e.val) + " has a negative weight");
+                throw std::invalid_argument(std::string(who) + ": relationship " + std::to_string(e.val) + " has a negative weight");
             if (w == 0.0) w = 0.0;                                       // (-0.0)
-            const Kept y{w, e.val};
+            const PairKept y{w, e.val};
             if (dir != Direction::Incoming) offer(e.row, e.col, y);
             if (dir != Direction::Outgoing) offer(e.col, e.row, y);
         }
     }
+    return best;
+}
+
+// pair_weights' refusal alone, for the walks that need no matrix: the same relationships, the same message
+void refuse_negative_weights(const Graph& g, const std::vector<u64>& tids, const PathAttrs& at, const char* who) {
+    if (at.unit) return;
+    for (u64 t : tids)
+        for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
+            if (e.row == e.col) continue;
+            const double w = at.weight(e.val);
+            if (std::isfinite(w) && w < 0.0)
+                throw std::invalid_argument(std::string(who) + ": relationship " + std::to_string(e.val) + " has a negative weight");
+        }
+}
+
+// ... as the n x n matrix the device searches: BOOL without weightProp, binary64 bit patterns otherwise
+Matrix pair_matrix(const Graph& g, const PairWeights& best, bool unit, u64 n) {
     std::vector<u64> rows, cols, bits;
     rows.reserve(best.size()); cols.reserve(best.size());
     if (!unit) bits.reserve(best.size());
@@ -1360,6 +1393,20 @@ SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::ve
     }
     Matrix w(g.ctx(), unit ? Type::Bool : Type::UInt64, n, n);
     if (!rows.empty()) w.build(rows, cols, unit ? nullptr : &bits);
+    return w;
+}
+}  // namespace
+
+SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
+                           const u64* w_edge_ids, const double* w_vals, u64 n_w,
+                           const u64* c_edge_ids, const double* c_vals, u64 n_c) {
+    SpPathResult res;
+    const u64 n = g.node_cap();
+    if (source == target) return res;                                    // :2559-2567
+    if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return res;
+    const PathAttrs at(w_edge_ids, w_vals, n_w, c_edge_ids, c_vals, n_c);
+    const PairWeights best = pair_weights(g, path_tids(g, types, true), dir, at);
+    Matrix w = pair_matrix(g, best, at.unit, n);
     std::vector<double> dist(n);
     std::vector<int64_t> parent(n);
     sssp(g.ctx(), w.snapshot(), source, dist.data(), parent.data());
@@ -1376,10 +1423,220 @@ SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::ve
     for (size_t k = 0; k + 1 < res.nodes.size(); ++k) {                  // :2250-2254
         const u64 edge = best.at((res.nodes[k] << 32) | res.nodes[k + 1]).edge;
         res.edges.push_back(edge);
-        const auto it = cattr.find(edge);
-        res.cost += it != cattr.end() ? it->second : 0.0;
+        res.cost += at.cost(edge);
     }
     return res;
+}
+
+namespace {
+// cmp_found_path (:2037-2045): ascending weight, then cost, then hop count (the values are finite: partial_cmp never fails)
+int cmp_path(const PathRow& a, const PathRow& b) {
+    if (a.weight != b.weight) return a.weight < b.weight ? -1 : 1;
+    if (a.cost != b.cost) return a.cost < b.cost ? -1 : 1;
+    if (a.edges.size() != b.edges.size()) return a.edges.size() < b.edges.size() ? -1 : 1;
+    return 0;
+}
+
+// record_found_path (:2350-2403)
+void record_path(std::vector<PathRow>& results, PathRow&& found, int64_t path_count, double& bound) {
+    if (path_count == 1) {
+        if (results.empty() || cmp_path(found, results.front()) < 0) {
+            bound = found.weight;
+            results.clear();
+            results.push_back(std::move(found));
+        }
+        return;
+    }
+    if (path_count == 0) {
+        if (results.empty()) {
+            bound = found.weight;
+            results.push_back(std::move(found));
+        } else if (found.weight > results.front().weight) {
+        } else if (found.weight < results.front().weight) {
+            bound = found.weight;
+            results.clear();
+            results.push_back(std::move(found));
+        } else {
+            results.push_back(std::move(found));
+        }
+        return;
+    }
+    const size_t k = (size_t)path_count;
+    if (results.size() == k) {
+        if (cmp_path(found, results[k - 1]) >= 0) return;
+        results.pop_back();
+    }
+    const auto pos = std::partition_point(results.begin(), results.end(), [&](const PathRow& kept) { return cmp_path(kept, found) < 0; });
+    results.insert(pos, std::move(found));
+    if (results.size() == k) bound = results[k - 1].weight;
+}
+
+// what prunes the walk: `rows` rows of n lower bounds on the weight left to the target (rows == 1: one row for every budget)
+struct PathTable {
+    std::vector<double> d;
+    u64 n = 0;
+    uint32_t rows = 0;
+    double slack = 0.0;
+    double at(uint32_t left, u64 v) const { return d[(size_t)(rows == 1 ? 0 : left) * n + v]; }
+};
+
+// enumerate_paths (:2414-2514) + the final sort (:2595); `table` nullable
+std::vector<PathRow> enumerate_paths(const Graph& g, u64 source, std::optional<u64> target, const PathQuery& q, const PathAttrs& at,
+                                     const PathTable* table, double bound, PathEnumStats& st) {
+    struct Succ { u64 edge, far; };
+    struct Live { u64 edge; double weight, cost; };                      // the PREFIX sums up to and including this edge
+    const std::vector<u64> tids = path_tids(g, q.types, false);
+    const bool with_out = q.dir != Direction::Incoming, with_in = q.dir != Direction::Outgoing;
+    auto successors = [&](u64 node) {                                    // node_successors (:2098-2109)
+        std::vector<Succ> out;
+        for (const VlEdge& e : node_relationships(g, node, tids, with_out, with_in))
+            out.push_back({e.id, with_out && e.src == node ? e.dst : e.src});   // far_endpoint (:2066-2085)
+        return out;
+    };
+    std::vector<std::optional<std::vector<Succ>>> levels;
+    std::vector<u64> nodes{source};
+    std::vector<Live> live;
+    std::vector<uint8_t> on_path(g.node_cap(), 0);
+    on_path[source] = 1;
+    levels.push_back(q.max_len > 0 ? std::optional<std::vector<Succ>>(successors(source)) : std::nullopt);
+    std::vector<PathRow> results;
+    for (;;) {
+        const size_t depth = live.size();
+        auto& lv = levels[depth];
+        if (lv && !lv->empty()) {
+            const Succ s = lv->back();
+            lv->pop_back();
+            ++st.examined;
+            if (q.max_examined && st.examined > q.max_examined)
+                throw std::runtime_error("algo.SPpaths: the enumeration spent its budget of " + std::to_string(q.max_examined) +
+                                         " examined successors");
+            if (on_path[s.far]) continue;                                // simple paths only
+            const double w0 = live.empty() ? 0.0 : live.back().weight, c0 = live.empty() ? 0.0 : live.back().cost;
+            const double next_weight = w0 + at.weight(s.edge), next_cost = c0 + at.cost(s.edge);
+            if (!std::isfinite(next_weight) || next_weight > bound) continue;
+            if (!std::isfinite(next_cost) || (q.max_cost && next_cost > *q.max_cost)) continue;
+            if (table) {
+                const double left = table->at(q.max_len - (uint32_t)(depth + 1), s.far);
+                if (std::isinf(left)) { ++st.pruned_hops; continue; }
+                if ((next_weight + left) * (1.0 - table->slack) > bound) { ++st.pruned_weight; continue; }
+            }
+            live.push_back({s.edge, next_weight, next_cost});
+            nodes.push_back(s.far);
+            on_path[s.far] = 1;
+            const bool at_target = !target || s.far == *target;
+            if (at_target) {
+                PathRow found;
+                found.nodes = nodes;
+                for (const Live& e : live) found.edges.push_back(e.edge);
+                found.weight = next_weight;
+                found.cost = next_cost;
+                record_path(results, std::move(found), q.path_count, bound);
+            }
+            const bool expand = !(at_target && target) && live.size() < (size_t)q.max_len;
+            levels.push_back(expand ? std::optional<std::vector<Succ>>(successors(s.far)) : std::nullopt);
+        } else {
+            if (depth == 0) break;
+            levels.pop_back();
+            live.pop_back();
+            on_path[nodes.back()] = 0;
+            nodes.pop_back();
+        }
+    }
+    std::stable_sort(results.begin(), results.end(), [](const PathRow& a, const PathRow& b) { return cmp_path(a, b) < 0; });
+    return results;
+}
+
+// bfs_find_bound's answer (:2267-2320) without its weight: is there a route source -> target of at most maxLen arcs?
+bool reachable_within(const Graph& g, u64 source, u64 target, const PathQuery& q) {
+    const std::vector<u64> tids = path_tids(g, q.types, false);
+    const bool with_out = q.dir != Direction::Incoming, with_in = q.dir != Direction::Outgoing;
+    std::vector<uint8_t> seen(g.node_cap(), 0);
+    std::vector<u64> frontier{source}, next;
+    seen[source] = 1;
+    for (u64 hop = 0; hop < q.max_len && !frontier.empty(); ++hop) {
+        next.clear();
+        for (u64 u : frontier)
+            for (const VlEdge& e : node_relationships(g, u, tids, with_out, with_in)) {
+                const u64 far = with_out && e.src == u ? e.dst : e.src;
+                if (seen[far]) continue;
+                if (far == target) return true;
+                seen[far] = 1;
+                next.push_back(far);
+            }
+        frontier.swap(next);
+    }
+    return false;
+}
+
+void check_path_count(const PathQuery& q) {
+    if (q.path_count < 0) throw std::invalid_argument("pathCount must be a non-negative integer");   // :1940
+}
+}  // namespace
+
+std::vector<PathRow> algo_sp_paths_rows(const Graph& g, u64 source, u64 target, const PathQuery& q, PathEnumStats* stats) {
+    PathEnumStats local;
+    PathEnumStats& st = stats ? *stats : local;
+    st = PathEnumStats();
+    check_path_count(q);
+    if (q.path_count == 1 && !q.max_cost && q.max_len == UINT32_MAX && source != target) {   // the fast shape (:2563-2571)
+        st.table_rows = 0;
+        SpPathResult one = algo_sp_paths(g, source, target, q.types, q.dir, q.w_edge_ids, q.w_vals, q.n_w, q.c_edge_ids, q.c_vals, q.n_c);
+        std::vector<PathRow> rows;
+        if (one.found) rows.push_back({std::move(one.nodes), std::move(one.edges), one.weight, one.cost});
+        return rows;
+    }
+    const u64 n = g.node_cap();
+    const PathAttrs at(q.w_edge_ids, q.w_vals, q.n_w, q.c_edge_ids, q.c_vals, q.n_c);
+    const std::vector<u64> once = path_tids(g, q.types, true);
+    refuse_negative_weights(g, once, at, "algo.SPpaths");                // (pruning or not, whatever the nodes are)
+    if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return {};
+    if (source == target) return {};         // bfs_find_bound never "finds" the source it starts from: None (:2278-2279)
+    const double inf = std::numeric_limits<double>::infinity();
+    if (!q.prune) {
+        // bfs_find_bound's None: no route within maxLen, no enumeration — without it an unreachable target costs every simple
+        // path of the component.  Its weight is not used as a seed: the rows do not depend on the seed.
+        if (!reachable_within(g, source, target, q)) return {};
+        return enumerate_paths(g, source, target, q, at, nullptr, inf, st);
+    }
+    const Direction rev = q.dir == Direction::Outgoing ? Direction::Incoming : q.dir == Direction::Incoming ? Direction::Outgoing : Direction::Both;
+    Matrix wrev = pair_matrix(g, pair_weights(g, once, rev, at), at.unit, n);
+    PathTable table;
+    table.n = n;
+    const bool hop_table = q.max_len <= (uint32_t)FGPU_SSSP_HOPS_MAX && ((u64)q.max_len + 1) * n * sizeof(double) <= (1ull << 30);
+    if (hop_table) {
+        table.rows = q.max_len + 1;
+        table.d.resize((size_t)table.rows * n);
+        sssp_hops(g.ctx(), wrev.snapshot(), target, (int32_t)q.max_len, table.d.data());
+        st.table_rows = (int32_t)table.rows;
+    } else {
+        table.rows = 1;
+        table.d.resize(n);
+        sssp(g.ctx(), wrev.snapshot(), target, table.d.data(), nullptr);
+        st.table_rows = 0;
+    }
+    const u64 m = std::min<u64>(q.max_len, n - 1) + 1;
+    table.slack = 8.0 * (double)m * std::ldexp(1.0, -53);
+    const double reach = table.at(q.max_len, source);
+    if (std::isinf(reach)) return {};                                    // bfs_find_bound's None (:2579-2581)
+    // The one row of the fallback knows no hop budget.  It bounds every completion from below, so it may prune; but it is the
+    // weight of a QUALIFYING path only when a simple path cannot be longer than maxLen anyway (maxLen >= n - 1, "no maxLen"
+    // included).  Below that the cheapest route may need more than maxLen arcs: the row then neither seeds the bound (every
+    // qualifying path would lie above it) nor answers bfs_find_bound's question, which the host BFS answers instead.
+    const bool exact = hop_table || (u64)q.max_len >= n - 1;
+    if (!exact && !reachable_within(g, source, target, q)) return {};
+    const double seed = (exact && q.path_count <= 1 && !q.max_cost) ? reach * (1.0 + table.slack) : inf;
+    return enumerate_paths(g, source, target, q, at, &table, seed, st);
+}
+
+std::vector<PathRow> algo_ss_paths(const Graph& g, u64 source, const PathQuery& q, PathEnumStats* stats) {
+    PathEnumStats local;
+    PathEnumStats& st = stats ? *stats : local;
+    st = PathEnumStats();
+    check_path_count(q);
+    const PathAttrs at(q.w_edge_ids, q.w_vals, q.n_w, q.c_edge_ids, q.c_vals, q.n_c);
+    refuse_negative_weights(g, path_tids(g, q.types, true), at, "algo.SSpaths");
+    if (source >= g.node_cap() || g.is_node_deleted(source)) return {};
+    return enumerate_paths(g, source, std::nullopt, q, at, nullptr, std::numeric_limits<double>::infinity(), st);
 }
 
 // ---- algo.betweenness -----------------------------------------------------------------------------------

@@ -735,8 +735,8 @@ struct SpPathResult {
 };
 // algo.SPpaths (runtime/functions/algo_procedures.rs:2548-2597), its fast branch ONLY: one cheapest path, no maxLen, no
 // maxCost, source != target — what run_path_algo hands to dijkstra_single_path (:2563-2571, :2156-2257).  Every other shape
-// (pathCount 0 or > 1, maxLen, maxCost) and all of algo.SSpaths enumerate simple paths in an exponential host DFS with no matrix
-// work in it; they are not served here.
+// (pathCount 0 or > 1, maxLen, maxCost) and all of algo.SSpaths enumerate simple paths on the host: algo_sp_paths_rows and
+// algo_ss_paths below, the former pruned by fgpu_sssp_hops' table.
 // types empty = every tensor; unknown names are dropped and a name listed twice counts once (get_node_relationships_by_type's
 // filter_map).  source == target gives found = false, with or without a self-loop (:2559-2567); so does a source or target that
 // is deleted or out of range.  The host mirror has no attribute store: weightProp arrives as (w_edge_ids[k], w_vals[k]),
@@ -752,5 +752,76 @@ struct SpPathResult {
 SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
                            const u64* w_edge_ids, const double* w_vals, u64 n_w,
                            const u64* c_edge_ids, const double* c_vals, u64 n_c);
+
+// fgpu_sssp_hops into a host array of (max_hops + 1) * nrows entries
+inline void sssp_hops(const Context& ctx, const fgpu_mat* w, u64 src, int32_t max_hops, double* table) {
+    check(fgpu_sssp_hops(ctx.raw(), w, src, max_hops, table, nullptr), "algo.SPpaths");
+}
+
+// Every shape of algo.SPpaths, and algo.SSpaths: run_path_algo (:2548-2597) whole.
+struct PathQuery {
+    std::vector<std::string> types;            // relTypes: empty = every tensor; unknown names are dropped, a name listed twice
+                                               // contributes its relationships twice (get_node_relationships_by_type's filter_map)
+    Direction dir = Direction::Outgoing;       // relDirection
+    uint32_t max_len = UINT32_MAX;             // maxLen (UINT32_MAX = not given)
+    std::optional<double> max_cost;            // maxCost
+    int64_t path_count = 1;                    // pathCount: 1 the cheapest, 0 all of minimum weight, k > 1 the k cheapest
+    const u64* w_edge_ids = nullptr;           // weightProp / costProp as algo_sp_paths takes them
+    const double* w_vals = nullptr;
+    u64 n_w = 0;
+    const u64* c_edge_ids = nullptr;
+    const double* c_vals = nullptr;
+    u64 n_c = 0;
+    bool prune = true;                         // algo_sp_paths_rows: skip what the hop-bounded table rules out
+    u64 max_examined = 0;                      // budget of popped successors, 0 = none (stands for the reference's timeout poll)
+};
+struct PathRow {
+    std::vector<u64> nodes, edges;             // source .. end, and the relationship of every step
+    double weight = 0, cost = 0;
+};
+struct PathEnumStats {
+    u64 examined = 0;                          // successors popped
+    u64 pruned_hops = 0, pruned_weight = 0;    // skipped: cannot end at the target within maxLen / only above the bound
+    int32_t table_rows = -1;                   // rows of the table the walk was pruned with; -1 none, 0 = fgpu_sssp's one row
+};
+// algo_sp_paths_rows: the fast shape (pathCount 1, no maxLen, no maxCost, source != target) is algo_sp_paths.  Everything else
+// mirrors enumerate_paths + record_found_path + the final stable sort by cmp_found_path (:2350-2514, :2594-2595) step by step:
+// successors in get_node_relationships_by_type's order popped from the back, prefix sums kept per edge, the non-finite tests
+// on next_weight and next_cost, nothing extended past the target, the k-list insertion by partition_point (a new path goes in
+// front of its equals; a candidate that is not Less than the last kept one is dropped).  pathCount < 0 throws
+// std::invalid_argument("pathCount must be a non-negative integer") (:1940); a negative weight among the selected
+// relationships throws as algo_sp_paths does; a spent max_examined throws std::runtime_error.
+//
+// Pruning (q.prune).  The reference's walk enters every prefix under the current weight bound, also those that can never END
+// at the target within maxLen.  Which those are is a matrix question: Wrev = the min-weight matrix per ordered pair in the
+// REVERSE traversal direction (algo_sp_paths' builder with Outgoing and Incoming swapped), and
+//   table[r][v] = fgpu_sssp_hops(Wrev, target, maxLen)[r][v] = the cheapest way from v to the target in at most r arcs
+// when maxLen <= 32 and the table is at most 1 GiB; otherwise the one row fgpu_sssp(Wrev, target) gives.  That row knows no
+// hop budget: it is a valid (weaker) LOWER bound on what is left to the target under every budget, so it may prune, but below
+// maxLen = n - 1 it is not the weight of a qualifying path (the cheapest route may need more than maxLen arcs) — there it
+// neither seeds the bound nor answers bfs_find_bound's question, which a host BFS within maxLen answers instead.  With m = min(maxLen, n - 1) + 1, slack = 8 m 2^-53, and, for a successor `next`
+// pushed as arc number len, L = table[maxLen - len][next]:
+//   - L == +inf: no simple path through this prefix ends at the target in time — skipped (pruned_hops);
+//   - (next_weight + L) (1 - slack) > bound: every completion weighs more than the bound — skipped (pruned_weight);
+//   - the bound starts at table[maxLen][source] (1 + slack) when pathCount is 0 or 1, there is no maxCost and the table is
+//     hop-exact (the hop table, or the one row with maxLen >= n - 1), else at +inf;
+//   - table[maxLen][source] == +inf returns no rows (bfs_find_bound's None, :2579-2581), and so does, under the one row with
+//     maxLen < n - 1, a target the host BFS does not reach within maxLen.
+// Why the rows are the reference's.  (1) A skipped branch holds only paths that do not reach the target within maxLen, or
+// whose forward-folded weight exceeds the bound of that moment; the reference cuts each of the latter at some prefix before or
+// at the target (its `next_weight > bound` test), and bounds only fall: the sequence of record_found_path calls that change
+// anything is the same.  (2) The result does not depend on the seed as long as the seed is at least the forward-folded weight
+// of a cheapest qualifying path: pathCount 1 keeps the first path in DFS order of the cmp-minimal class, pathCount 0 keeps all
+// paths of minimum weight in DFS order, and both sets lie under either seed.  (3) The slack covers the two folds: the table
+// adds a route's weights from the target outward, the walk from the source outward.  For k <= m non-negative terms each fold
+// is within a factor (1 +- g) of the exact sum S, g = (k - 1) u / (1 - (k - 1) u), u = 2^-53 (Higham, Accuracy and Stability,
+// Lemma 3.1; no cancellation: all terms >= 0), so fold_a <= S (1 + g) <= fold_b (1 + g) / (1 - g) <= fold_b (1 + 3 m u) for
+// m u < 1/8.  A completion of weight fold_fwd <= bound therefore has (next_weight + L) <= fold_fwd (1 + 3 m u)(1 + u), below
+// bound / (1 - 8 m u); the seed likewise stays above the forward fold of the table's own cheapest route.
+// A source or target that is deleted or out of range gives no rows.
+std::vector<PathRow> algo_sp_paths_rows(const Graph& g, u64 source, u64 target, const PathQuery& q, PathEnumStats* stats = nullptr);
+// algo.SSpaths: the same walk with no target — every non-empty simple path from source qualifies.  There is nothing to bound
+// against, so no device call is made (table_rows stays -1, q.prune is ignored).
+std::vector<PathRow> algo_ss_paths(const Graph& g, u64 source, const PathQuery& q, PathEnumStats* stats = nullptr);
 
 }  // namespace falkor

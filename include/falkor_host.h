@@ -283,7 +283,7 @@ int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const ui
 /* algo.SPpaths (algo_procedures.rs:2548-2597), the branch that answers ONE cheapest path: pathCount 1, no maxLen, no maxCost,
  * source != target — run_path_algo's call of dijkstra_single_path (:2563-2571), computed by fgpu_sssp, whose comment in fgpu.h
  * states which distance and which parent come back.  The other shapes of algo.SPpaths and all of algo.SSpaths enumerate simple
- * paths on the host and are not served.  types = a comma list, "" / NULL = every type; unknown names are dropped, a name listed
+ * paths on the host: fh_algo_sp_paths_rows and fh_algo_ss_paths below.  types = a comma list, "" / NULL = every type; unknown names are dropped, a name listed
  * twice counts once.  direction: 0 outgoing, 1 incoming, 2 both (relDirection).  The host mirror has no attribute store, so
  * weightProp and costProp are data: w_vals[k] is the weight of relationship w_edge_ids[k], k < n_w; w_edge_ids == NULL means no
  * weightProp; a relationship that is not listed weighs 1.0.  c_edge_ids / c_vals / n_c likewise for the cost, default 0.0.  A
@@ -297,6 +297,36 @@ int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const ui
 int fh_algo_sp_paths(fh_graph* g, uint64_t source, uint64_t target, const char* types, int direction, const uint64_t* w_edge_ids,
                      const double* w_vals, uint64_t n_w, const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int* found,
                      uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, double* weight, double* cost);
+
+/* algo.SPpaths in EVERY shape (run_path_algo, algo_procedures.rs:2548-2597): pathCount 1 without maxLen and maxCost, source !=
+ * target, is fh_algo_sp_paths; every other shape mirrors enumerate_paths + record_found_path + the final sort by
+ * cmp_found_path (:2350-2514) and returns the reference's rows in the reference's order.  types, direction and the weight /
+ * cost lists as fh_algo_sp_paths takes them, except that a type name listed twice contributes its relationships twice (as
+ * get_node_relationships_by_type does).  max_len < 0 = no maxLen; has_max_cost = 0 = no maxCost; path_count: 1 the cheapest
+ * path, 0 every path of minimum weight, k > 1 the k cheapest; a negative one fails with "pathCount must be a non-negative
+ * integer", a negative weight among the selected relationships with "negative weight".  prune != 0 (the default of the C++
+ * layer): the walk skips the successors that cannot end at the target within maxLen, or only above the current weight bound,
+ * as decided by the hop-bounded table fgpu_sssp_hops computes from the target over the reversed min-weight matrix (maxLen <=
+ * 32 and a table of at most 1 GiB; otherwise by fgpu_sssp's one row, which knows no hop budget: it prunes, but seeds the bound
+ * only when maxLen >= n - 1) — host.hpp has the rule and the argument why the rows do
+ * not change.  max_examined: a budget of successors taken off the walk's stacks, 0 = none; once spent the call fails
+ * ("budget"), which stands for the reference's timeout poll.
+ * Result: *n_rows rows; row r has the relationships edges[offsets[r] .. offsets[r + 1]) and the nodes nodes[offsets[r] + r ..
+ * offsets[r + 1] + r + 1), weights[r] and costs[r] folded source -> target in FP64.  stats (nullable): [0] successors
+ * examined, [1] skipped because the target is out of reach within maxLen, [2] skipped because every completion is above the
+ * bound, [3] rows of the table used: -1 none, 0 = fgpu_sssp's one row.  A source or target that is deleted or out of range
+ * gives no rows.  Free the five arrays with fh_free. */
+int fh_algo_sp_paths_rows(fh_graph* g, uint64_t source, uint64_t target, const char* types, int direction, int64_t max_len,
+                          int has_max_cost, double max_cost, int64_t path_count, const uint64_t* w_edge_ids, const double* w_vals,
+                          uint64_t n_w, const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, int prune,
+                          uint64_t max_examined, uint64_t* n_rows, uint64_t** offsets, uint64_t** nodes, uint64_t** edges,
+                          double** weights, double** costs, int64_t stats[4]);
+/* algo.SSpaths: the same walk without a target — every non-empty simple path from source qualifies (within maxLen / maxCost),
+ * kept and ordered by the same rules.  No device call is made: there is nothing to bound against (stats[3] = -1). */
+int fh_algo_ss_paths(fh_graph* g, uint64_t source, const char* types, int direction, int64_t max_len, int has_max_cost,
+                     double max_cost, int64_t path_count, const uint64_t* w_edge_ids, const double* w_vals, uint64_t n_w,
+                     const uint64_t* c_edge_ids, const double* c_vals, uint64_t n_c, uint64_t max_examined, uint64_t* n_rows,
+                     uint64_t** offsets, uint64_t** nodes, uint64_t** edges, double** weights, double** costs, int64_t stats[4]);
 
 /* algo.betweenness (algo_procedures.rs:884-1017; LAGr_Betweenness through lagraph_bindings.rs:539-546 is fgpu_betweenness):
  * labels / types = comma lists, "" / NULL = all; several labels select the UNION of their nodes (an induced subgraph).

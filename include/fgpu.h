@@ -628,6 +628,28 @@ fgpu_info fgpu_maxflow(fgpu_ctx* ctx, const fgpu_mat* C, uint64_t src, uint64_t 
  * message instead of running on. */
 fgpu_info fgpu_sssp(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, double* dist, int64_t* parent, uint64_t stats[4]);
 
+/* The hop-bounded shortest-path table from one source: what prunes algo.SPpaths' enumeration shapes (enumerate_paths,
+ * algo_procedures.rs:2405-2514, walks every simple path under its weight bound; whether a prefix can still END at the target
+ * within maxLen arcs is the cheapest way from the target in at most r arcs over the transposed weights, which is this table).
+ * The reference has no counterpart; these are the rules:
+ *   - W follows fgpu_sssp's rules exactly: square, W(u, v) the weight of the arc u -> v as a binary64 bit pattern, a BOOL
+ *     snapshot means every weight is 1.0, a hypersparse W is accepted, a diagonal entry is ignored, -0.0 is 0.0, a NaN or a
+ *     negative weight anywhere in W is FGPU_INVALID, a relaxation whose sum is not finite is skipped;
+ *   - max_hops is 0 .. FGPU_SSSP_HOPS_MAX.
+ * table[(max_hops + 1) * nrows] (a HOST array; a pinned one — fgpu_host_alloc — is filled by DMA): table[h * nrows + v] =
+ * D_h[v], with D_0[src] = +0.0 and +inf elsewhere, and
+ *   D_h[v] = min(D_{h-1}[v], min over the entries (u, v), u != v, of fl(D_{h-1}[u] + W(u, v)) where that sum is finite).
+ * fl(a + w) is monotone in a for w >= 0, so D_h[v] is the minimum over all routes src -> v of at most h arcs of the route's
+ * weights added left to right from the source in FP64: unique, and identical from run to run.  A round reads D_{h-1} only —
+ * one round never travels two arcs.  Once a round lowers nothing, every later row repeats the last one.
+ * stats (nullable): [0] rounds whose frontier (the vertices the round before lowered; round 1: src) was not empty,
+ * [1] frontier entries taken over all rounds (a vertex is in a frontier once per round), [2] entries read, [3] the first h in
+ * 1 .. max_hops with D_h == D_{h-1} everywhere, max_hops + 1 if there is none.
+ * Errors: NULL ctx / W / table: FGPU_NULL_POINTER; non-square W: FGPU_DIM_MISMATCH; max_hops outside 0 .. FGPU_SSSP_HOPS_MAX,
+ * nrows >= 2^32 - 1: FGPU_INVALID; src >= nrows: FGPU_OUT_OF_BOUNDS.  nrows == 0 is a no-op. */
+#define FGPU_SSSP_HOPS_MAX 32
+fgpu_info fgpu_sssp_hops(fgpu_ctx* ctx, const fgpu_mat* W, uint64_t src, int32_t max_hops, double* table, uint64_t stats[4]);
+
 /* The shortest-path DAG between two bound vertices: the numeric core of the reference's AllShortestPathsOp
  * (runtime/ops/all_shortest_paths.rs:128-267, MATCH p = allShortestPaths((a)-[*]->(b))).  The reference runs a hash-map BFS per
  * input row and a lazy DFS over the recorded predecessors; the DFS touches exactly the pairs returned here.

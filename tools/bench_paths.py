@@ -45,7 +45,16 @@
           and 1 (forward only), median / min / max of 5 synchronised calls after 1 warm-up, and one fgpu_bfs (levels only) from
           the same src; then one summary line per graph with the medians over the pairs and the ratios
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|asp|all] [scale]
+  hops    the hop-bounded table behind algo.SPpaths' enumeration shapes (fgpu_sssp_hops) on RMAT-22 (or RMAT-<scale>)
+          TRANSPOSED, with the hashed integer weights of the sssp leg, from the vertex with the most in-entries of the graph
+          (= most out-entries of the transpose): max_hops 3 and 6 into a pinned table, median of 3 synchronised calls, the
+          stats, the table's bytes and the time of a pinned device-to-host copy of that many bytes on its own (so the device
+          part is the call less that copy); in the same run one fgpu_sssp (distances only), one fgpu_bfs and one fgpu_sssp_hops
+          from a vertex without entries (the fixed part: weight pass, row copies, launches, DMA).  Then, on the host leg's
+          graph (RMAT-18, one type), one algo_sp_paths_rows call (maxLen 4, pathCount 0) with prune on and off: ms and the
+          successors examined, the unpruned walk under a budget of 300 000 successors
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -478,6 +487,108 @@ def bench_sssp(ctx, scale, sweep=False):
     ctx.set_option("sssp_delta_log2", 4096)
 
 
+def bench_hops(ctx, scale, host_scale=18):
+    """fgpu_sssp_hops on the transposed R-MAT graph with bench_sssp's integer weights (the weight of (u, v) hangs on (v, u)),
+    max_hops 3 and 6, beside one fgpu_sssp and one fgpu_bfs from the same vertex; then algo_sp_paths_rows with and without the
+    table on the host leg's graph."""
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.repeat(np.arange(n, dtype=np.uint64), deg)
+    h = (rows * np.uint64(n) + ci) * np.uint64(0x9E3779B97F4A7C15)   # (mod 2^64)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(32)
+    w = ((h >> np.uint64(11)) % np.uint64(100) + np.uint64(1)).astype(np.float64)
+    Wt = ctx.mat_from_coo(n, n, ci, rows, w.view(np.uint64))   # the transpose, values along
+    del h, w
+    indeg = np.bincount(ci.astype(np.int64), minlength=n)
+    src = int(np.argmax(indeg))
+    lone = np.nonzero((deg == 0) & (indeg == 0))[0]
+    del rows
+    At = A.transpose()
+    nnz = A.nvals
+    level = ctx.host_array(n, np.int32)
+    t_bfs, _ = timed(ctx, lambda: engine.bfs(ctx, At, A, src, -1, want_parent=False, level_out=level), reps=5, warm=1)
+    out = (ctx.host_array(n, np.float64), None)
+    t_sssp, (dist, _) = timed(ctx, lambda: engine.sssp(ctx, Wt, src, want_parent=False, out=out), reps=3, warm=1)
+    reached = int(np.isfinite(dist).sum())
+    for hops in (3, 6):
+        table = ctx.host_array((hops + 1) * n, np.float64).reshape(hops + 1, n)
+        t, (tab, st) = timed(ctx, lambda: engine.sssp_hops(ctx, Wt, src, hops, stats=True, out=table), reps=3, warm=1)
+        finite = int(np.isfinite(tab[-1]).sum())   # (before the next call fills the same block)
+        t_fixed = None
+        if len(lone):
+            t_fixed, _ = timed(ctx, lambda: engine.sssp_hops(ctx, Wt, int(lone[0]), hops, out=table), reps=3, warm=1)
+        nbytes = (hops + 1) * n * 8
+        t_dma = None
+        try:   # the same bytes, device to pinned host, on their own
+            import torch
+            d = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+            p = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            ts = []
+            for k in range(6):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                p.copy_(d, non_blocking=True)
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            t_dma = float(np.median(ts[1:]))
+            del d, p
+        except Exception as e:   # noqa: BLE001
+            print(json.dumps({"path": "hops", "dma_probe_failed": str(e)}), flush=True)
+        print(json.dumps({"path": "hops", "scale": scale, "weights": "int_1_100", "n": n, "nnz": nnz, "src": src,
+                          "in_degree_src": int(indeg[src]), "max_hops": hops, "ms": round(t * 1e3, 3),
+                          "table_bytes": nbytes, "ms_dma_alone": round(t_dma * 1e3, 3) if t_dma is not None else None,
+                          "ms_less_dma": round((t - t_dma) * 1e3, 3) if t_dma is not None else None,
+                          "ms_call_without_search": round(t_fixed * 1e3, 3) if t_fixed is not None else None,
+                          "rounds": st[0], "frontier_entries": st[1], "entries_read": st[2], "first_fixed_row": st[3],
+                          "finite_in_last_row": finite, "sssp_dist_only_ms": round(t_sssp * 1e3, 3),
+                          "sssp_reached": reached, "bfs_ms": round(t_bfs * 1e3, 3), "x_sssp": round(t / t_sssp, 3),
+                          "x_bfs": round(t / t_bfs, 2),
+                          "note": "host clock around a synchronised call into a pinned table, median of 3 after 1 warm-up; "
+                                  "dma_alone = a pinned device-to-host copy of table_bytes by itself, median of 5; "
+                                  "call_without_search = the same call from a vertex without entries; sssp = fgpu_sssp, "
+                                  "distances only, bfs = fgpu_bfs, levels only, both from src over the same matrix; no outside "
+                                  "number exists to compare with"}), flush=True)
+    for m in (Wt, At, A):
+        m.free()
+    # the host call, with and without the table
+    from falkordb_amd import host
+    hc = host.Context(0)
+    B = ctx.mat_rmat(host_scale)
+    bn = B.nrows
+    brp, bci, _ = B.export_csr()
+    bdeg = np.diff(brp.astype(np.int64))
+    br = np.repeat(np.arange(bn, dtype=np.uint64), bdeg)
+    g = host.Graph(hc, bn)
+    ty = g.add_type("KNOWS")
+    g.create_edges(ty, br, bci, np.arange(len(bci), dtype=np.uint64))
+    g.commit()
+    Bt = B.transpose()
+    source = int(np.nonzero(bdeg == 8)[0][0])
+    lv, _, _ = engine.bfs(ctx, B, Bt, source, -1, want_parent=False)
+    far = np.nonzero(lv == 3)[0]
+    target = int(far[0]) if len(far) else int(np.nonzero(lv > 0)[0][0])
+    for prune in (True, False):
+        t0 = time.perf_counter()
+        try:
+            rows, st = g.algo_sp_paths_rows(source, target, types=["KNOWS"], max_len=4, path_count=0, prune=prune,
+                                            max_examined=0 if prune else 300000, stats=True)
+            spent = False
+        except host.HostError:
+            rows, st, spent = [], {"examined": 300000, "pruned_hops": None, "pruned_weight": None, "table_rows": -1}, True
+        dt = time.perf_counter() - t0
+        print(json.dumps({"path": "hops_host", "scale": host_scale, "n": bn, "nnz": int(len(bci)), "source": source, "target": target,
+                          "bfs_level_of_target": int(lv[target]), "max_len": 4, "path_count": 0, "prune": prune,
+                          "ms": round(dt * 1e3, 3), "rows": len(rows), "budget_spent": spent, **st,
+                          "note": "one call through ctypes, host clock, not repeated; the unpruned walk stops at a budget of "
+                                  "300 000 examined successors (budget_spent: its ms and examined are then lower bounds)"}),
+              flush=True)
+    hc.close()
+
+
 def bench_asp(ctx, scale, npairs=64):
     """fgpu_shortest_dag between 64 seeded (src, dst) pairs of the R-MAT graph, directed (A, A') and symmetrised (S = A + A' for
     both arguments), two-sided against forward-only, with fgpu_bfs from the same src for scale."""
@@ -619,6 +730,10 @@ if __name__ == "__main__":
     if what in ("sssp", "sssp_sweep", "all"):
         c = engine.Context(0)
         bench_sssp(c, scale if scale else 22, sweep=what == "sssp_sweep")
+        c.close()
+    if what in ("hops", "all"):
+        c = engine.Context(0)
+        bench_hops(c, scale if scale else 22)
         c.close()
     if what in ("asp", "all"):
         c = engine.Context(0)
