@@ -723,6 +723,91 @@ def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bit
     return cent, ([int(x) for x in st] if stats else None)
 
 
+VEC_METRICS = {"euclidean": 0, "cosine": 1, "ip": 2}
+
+
+class VecIndex:
+    """fgpu_vecidx: a dense store of f32 vectors under ids below 2^32 - 1, searched exhaustively on the device — the core of
+    db.idx.vector.queryNodes / queryRelationships (the rules are in include/fgpu.h)."""
+
+    def __init__(self, ctx: Context, dim: int, metric="euclidean"):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        m = VEC_METRICS[metric] if isinstance(metric, str) else int(metric)
+        check(ctx.lib.fgpu_vecidx_new(ctx._h, C.byref(self._h), C.c_uint32(dim), C.c_int(m)))
+
+    def free(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.fgpu_vecidx_free(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            if self.ctx._h:   # (the index points into its context: never touched after fgpu_finalize)
+                self.free()
+        except Exception:
+            pass
+
+    def info(self):
+        """(dim, metric, count)"""
+        d, m, n = C.c_uint32(), C.c_int(), C.c_uint64()
+        check(self.ctx.lib.fgpu_vecidx_info(self._h, C.byref(d), C.byref(m), C.byref(n)))
+        return d.value, m.value, n.value
+
+    @property
+    def dim(self):
+        return self.info()[0]
+
+    @property
+    def count(self):
+        return self.info()[2]
+
+    def _vecs(self, vecs, rows=None):
+        v = np.ascontiguousarray(vecs, dtype=np.float32)
+        v = v.reshape(1, -1) if v.ndim == 1 else v
+        if v.ndim != 2 or v.shape[1] != self.dim or (rows is not None and v.shape[0] != rows):
+            raise ValueError(f"expected {'n' if rows is None else rows} rows of {self.dim} float32 components, got {v.shape}")
+        return v
+
+    def set(self, ids, vecs):
+        """Upsert: vecs[i] becomes the vector of ids[i]; of an id given twice the last row wins."""
+        i = _u64(np.atleast_1d(ids))
+        v = self._vecs(vecs, len(i))
+        check(self.ctx.lib.fgpu_vecidx_set(self.ctx._h, self._h, _p(i), _p(v, C.POINTER(C.c_float)), len(i)))
+
+    def remove(self, ids) -> int:
+        """Removes the ids that are present and returns how many were."""
+        i = _u64(np.atleast_1d(ids))
+        gone = C.c_uint64()
+        check(self.ctx.lib.fgpu_vecidx_remove(self.ctx._h, self._h, _p(i), len(i), C.byref(gone)))
+        return gone.value
+
+    def get(self, id_: int):
+        """The stored vector of id_ (float32[dim]), or None."""
+        v = np.zeros(self.dim, dtype=np.float32)
+        present = C.c_int()
+        check(self.ctx.lib.fgpu_vecidx_get(self.ctx._h, self._h, C.c_uint64(id_), _p(v, C.POINTER(C.c_float)), C.byref(present)))
+        return v if present.value else None
+
+    def knn(self, queries, k: int, stats: bool = False):
+        """The kk = min(k, count) nearest stored vectors of every query: (ids uint64[nq, kk], dist float64[nq, kk]), each row in
+        ascending (dist, id) — and, when stats=True, a third item: the four counters [scoring launches, query tiles, bytes of
+        vectors read by scoring, tied entries the id order decided]."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        kk = min(max(int(k), 0), self.count)
+        ids = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float64)
+        got = C.c_uint64()
+        st = np.zeros(4, dtype=np.uint64) if stats else None
+        check(self.ctx.lib.fgpu_vecidx_knn(self.ctx._h, self._h, _p(q, C.POINTER(C.c_float)), nq, C.c_uint64(max(int(k), 0)),
+                                           _p(ids), _p(dist, C.POINTER(C.c_double)), C.byref(got), _p(st)))
+        assert got.value == (kk if nq else 0)
+        if stats:
+            return ids, dist, [int(x) for x in st]
+        return ids, dist
+
+
 class BfsPlan:
     """fgpu_bfs_plan: resident BFS workspace (+ slab partition state for multi-rank runs)."""
 

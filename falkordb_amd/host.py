@@ -78,6 +78,22 @@ def _take(ptr, n, dtype=np.uint64):
     return out
 
 
+def _f32(x):
+    return np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+
+
+def _pf(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def vec_distance(metric, a, b):
+    """vec.euclideanDistance / vec.cosineDistance (and the ip metric) in FP64 on the host (fh_vec_distance; no GPU)"""
+    x, y = _f32(a), _f32(b)
+    out = C.c_double()
+    _ck(load().fh_vec_distance(metric.encode(), _pf(x), C.c_uint64(x.size), _pf(y), C.c_uint64(y.size), C.byref(out)))
+    return out.value
+
+
 def betweenness_sources(n_nodes, sampling_size=16, sampling_seed=0):
     """algo.betweenness' source indices out of 0..n_nodes (fh_betweenness_sources; no GPU)"""
     out = u64p()
@@ -689,6 +705,64 @@ class Graph:
         _ck(self.L.fh_algo_betweenness(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.c_int64(sampling_size),
                                        C.c_int64(sampling_seed), C.byref(nodes), C.byref(scores), C.byref(n)))
         return _take(nodes, n.value), _take(scores, n.value, np.float64)
+
+    # ---- vector indexes: db.idx.vector.queryNodes / queryRelationships (fh_graph_vector_*, fh_vector_query_*) ----
+    def vector_index_create(self, is_edge, label_or_type_id, attr, dim, similarity=None):
+        _ck(self.L.fh_graph_vector_index_create(self.h, 1 if is_edge else 0, C.c_uint64(label_or_type_id), attr.encode(),
+                                                C.c_uint64(dim), similarity.encode() if similarity is not None else None))
+
+    def vector_index_drop(self, is_edge, label_or_type_id, attr):
+        return _ck(self.L.fh_graph_vector_index_drop(self.h, 1 if is_edge else 0, C.c_uint64(label_or_type_id), attr.encode()),
+                   allow=(0, 1)) == 0
+
+    def vector_set_node(self, label_id, attr, node, vec):
+        v = _f32(vec)
+        _ck(self.L.fh_graph_vector_set_node(self.h, C.c_uint64(label_id), attr.encode(), C.c_uint64(node), _pf(v),
+                                            C.c_uint64(v.size)))
+
+    def vector_set_edge(self, type_id, attr, src, dst, edge_id, vec):
+        v = _f32(vec)
+        _ck(self.L.fh_graph_vector_set_edge(self.h, C.c_uint64(type_id), attr.encode(), C.c_uint64(src), C.c_uint64(dst),
+                                            C.c_uint64(edge_id), _pf(v), C.c_uint64(v.size)))
+
+    def vector_unset_node(self, label_id, attr, node):
+        return _ck(self.L.fh_graph_vector_unset_node(self.h, C.c_uint64(label_id), attr.encode(), C.c_uint64(node)),
+                   allow=(0, 1)) == 0
+
+    def vector_unset_edge(self, type_id, attr, edge_id):
+        return _ck(self.L.fh_graph_vector_unset_edge(self.h, C.c_uint64(type_id), attr.encode(), C.c_uint64(edge_id)),
+                   allow=(0, 1)) == 0
+
+    def vector_query_nodes(self, label, attr, k, query):
+        """CALL db.idx.vector.queryNodes(label, attr, k, query) YIELD node, score -> (nodes, scores float64), ascending."""
+        q = _f32(query)
+        ids, dist, n = u64p(), C.POINTER(C.c_double)(), C.c_uint64()
+        _ck(self.L.fh_vector_query_nodes(self.h, label.encode(), attr.encode(), C.c_int64(k), _pf(q), C.c_uint64(q.size),
+                                         C.byref(ids), C.byref(dist), C.byref(n)))
+        return _take(ids, n.value), _take(dist, n.value, np.float64)
+
+    def vector_query_edges(self, rel_type, attr, k, query):
+        """CALL db.idx.vector.queryRelationships(type, attr, k, query) YIELD relationship, score ->
+        (edge ids, scores float64, srcs, dsts), ascending."""
+        q = _f32(query)
+        ids, dist, srcs, dsts, n = u64p(), C.POINTER(C.c_double)(), u64p(), u64p(), C.c_uint64()
+        _ck(self.L.fh_vector_query_edges(self.h, rel_type.encode(), attr.encode(), C.c_int64(k), _pf(q), C.c_uint64(q.size),
+                                         C.byref(ids), C.byref(dist), C.byref(srcs), C.byref(dsts), C.byref(n)))
+        return _take(ids, n.value), _take(dist, n.value, np.float64), _take(srcs, n.value), _take(dsts, n.value)
+
+    def vector_query_nodes_batch(self, label, attr, k, queries):
+        """queryNodes for every row of queries (nq, dim) in one device call -> (offsets uint64[nq + 1], nodes, scores)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        assert q.ndim == 2
+        nq, qn = q.shape
+        off, ids, dist = u64p(), u64p(), C.POINTER(C.c_double)()
+        _ck(self.L.fh_vector_query_nodes_batch(self.h, label.encode(), attr.encode(), C.c_int64(k), _pf(q), C.c_uint64(qn),
+                                               C.c_uint64(nq), C.byref(off), C.byref(ids), C.byref(dist)))
+        offsets = _take(off, nq + 1)
+        total = int(offsets[-1])
+        return offsets, _take(ids, total), _take(dist, total, np.float64)
+
+    vec_distance = staticmethod(vec_distance)
 
     def algo_bfs(self, source, max_depth=-1, rel_type=None, want_edges=False):
         has = C.c_int()

@@ -933,4 +933,61 @@ int fh_betweenness_sources(uint64_t n_nodes, int64_t sampling_size, int64_t samp
     });
 }
 
+// vector indexes, db.idx.vector.queryNodes / queryRelationships, vec.*Distance
+int fh_graph_vector_index_create(fh_graph* g, int is_edge, uint64_t label_or_type_id, const char* attr, uint64_t dim,
+                                 const char* similarity) {
+    return guard([&] { g->g.vector_index_create(is_edge != 0, label_or_type_id, attr ? attr : "", dim, similarity); return 0; });
+}
+int fh_graph_vector_index_drop(fh_graph* g, int is_edge, uint64_t label_or_type_id, const char* attr) {
+    return guard([&] { return g->g.vector_index_drop(is_edge != 0, label_or_type_id, attr ? attr : "") ? 0 : 1; });
+}
+int fh_graph_vector_set_node(fh_graph* g, uint64_t label_id, const char* attr, uint64_t node, const float* vec, uint64_t n) {
+    return guard([&] { g->g.vector_set_node(label_id, attr ? attr : "", node, vec, n); return 0; });
+}
+int fh_graph_vector_set_edge(fh_graph* g, uint64_t type_id, const char* attr, uint64_t src, uint64_t dst, uint64_t edge_id,
+                             const float* vec, uint64_t n) {
+    return guard([&] { g->g.vector_set_edge(type_id, attr ? attr : "", src, dst, edge_id, vec, n); return 0; });
+}
+int fh_graph_vector_unset_node(fh_graph* g, uint64_t label_id, const char* attr, uint64_t node) {
+    return guard([&] { return g->g.vector_unset_node(label_id, attr ? attr : "", node) ? 0 : 1; });
+}
+int fh_graph_vector_unset_edge(fh_graph* g, uint64_t type_id, const char* attr, uint64_t edge_id) {
+    return guard([&] { return g->g.vector_unset_edge(type_id, attr ? attr : "", edge_id) ? 0 : 1; });
+}
+int fh_vector_query_nodes(fh_graph* g, const char* label, const char* attr, int64_t k, const float* q, uint64_t qn,
+                          uint64_t** ids, double** dist, uint64_t* n) {
+    return guard([&] {
+        VectorHits r = timed([&] { return g->g.vector_query(false, label ? label : "", attr ? attr : "", k, q, qn, 1); });
+        *ids = hand(r.ids);
+        *dist = hand(r.dist);
+        *n = r.ids.size();
+        return 0;
+    });
+}
+int fh_vector_query_edges(fh_graph* g, const char* type, const char* attr, int64_t k, const float* q, uint64_t qn,
+                          uint64_t** ids, double** dist, uint64_t** srcs, uint64_t** dsts, uint64_t* n) {
+    return guard([&] {
+        VectorHits r = timed([&] { return g->g.vector_query(true, type ? type : "", attr ? attr : "", k, q, qn, 1); });
+        *ids = hand(r.ids);
+        *dist = hand(r.dist);
+        *srcs = hand(r.srcs);
+        *dsts = hand(r.dsts);
+        *n = r.ids.size();
+        return 0;
+    });
+}
+int fh_vector_query_nodes_batch(fh_graph* g, const char* label, const char* attr, int64_t k, const float* queries, uint64_t qn,
+                                uint64_t nq, uint64_t** offsets, uint64_t** ids, double** dist) {
+    return guard([&] {
+        VectorHits r = timed([&] { return g->g.vector_query(false, label ? label : "", attr ? attr : "", k, queries, qn, nq); });
+        *offsets = hand(r.offsets);
+        *ids = hand(r.ids);
+        *dist = hand(r.dist);
+        return 0;
+    });
+}
+int fh_vec_distance(const char* metric, const float* a, uint64_t na, const float* b, uint64_t nb, double* out) {
+    return guard([&] { *out = vec_distance(vector_metric(metric), a, na, b, nb); return 0; });
+}
+
 }  // extern "C"

@@ -51,6 +51,7 @@ void Graph::create_edge(u64 type, u64 src, u64 dst, u64 edge_id) {
 
 void Graph::delete_edge(u64 type, u64 src, u64 dst, u64 edge_id) {
     auto emptied = tensors_.at(type).remove_all({{edge_id, src, dst}});
+    if (!vec_indexes_.empty()) drop_entity_vectors(true, type, edge_id);   // (after the removal: an unknown type has thrown)
     if (emptied.empty()) return;
     for (auto& t : tensors_)
         if (t.eff_get(src, dst)) return;   // another type still connects the pair

@@ -24,6 +24,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -315,6 +316,32 @@ class Tensor {
 
 using LabelId = u64;
 
+// One vector index of a graph (index/mod.rs:1768-1823 keeps an HNSW graph per (label or type, attribute); here it is an
+// fgpu_vecidx, searched exhaustively on the device).  Entities are node ids or relationship ids; an edge index remembers the
+// endpoints of every relationship it holds, which is what db.idx.vector.queryRelationships yields beside the id.
+struct VectorIndex {
+    fgpu_ctx* ctx = nullptr;
+    fgpu_vecidx* idx = nullptr;
+    uint32_t dim = 0;
+    int metric = FGPU_VEC_EUCLIDEAN;
+    std::unordered_map<u64, std::pair<u64, u64>> ends;   // edge indexes: relationship id -> (src, dst)
+    VectorIndex() = default;
+    VectorIndex(const VectorIndex&) = delete;
+    VectorIndex& operator=(const VectorIndex&) = delete;
+    ~VectorIndex() { if (idx) fgpu_vecidx_free(idx); }
+};
+// rows of a vector query; a batch of nq queries has offsets[nq + 1] over the other columns, rows in query order
+struct VectorHits {
+    std::vector<u64> ids, srcs, dsts, offsets;
+    std::vector<double> dist;
+};
+// the metric of a similarity name ("euclidean", "cosine", "ip"; NULL = euclidean); anything else throws the reference's text
+// (index/mod.rs:1259-1270)
+int vector_metric(const char* similarity);
+// vec.euclideanDistance / vec.cosineDistance (runtime/vec_distance.rs) in FP64, D of fgpu_vecidx_knn; na != nb throws
+// "Vector dimension mismatch, expected {na} but got {nb}" (spatial.rs:161-166)
+double vec_distance(int metric, const float* a, u64 na, const float* b, u64 nb);
+
 // The traversal-facing slice of graph.rs.
 class Graph {
    public:
@@ -332,7 +359,10 @@ class Graph {
     std::optional<LabelId> label_id(const std::string& name) const;
     std::optional<u64> type_id(const std::string& name) const;
     void label_node(u64 node, LabelId l) { labels_.set(node, l, true); }
-    void delete_node(u64 node) { deleted_[node] = true; }
+    void delete_node(u64 node) {
+        deleted_[node] = true;
+        if (!vec_indexes_.empty()) drop_entity_vectors(false, std::nullopt, node);   // test_vecsim.py test09
+    }
     bool is_node_deleted(u64 node) const { return !deleted_.empty() && deleted_.count(node) != 0; }
     u64 deleted_nodes_count() const { return deleted_.size(); }   // graph.rs deleted_nodes_count
     // graph.rs node_count: the ids below node_cap() that are not deleted (delete_node takes any id: one at or past the
@@ -360,7 +390,28 @@ class Graph {
     Matrix build_symmetric_adjacency_matrix(const std::vector<std::string>& types) const;   // graph.rs:3898-3907 (A + A')
     std::vector<u64> get_src_dest_relationships(u64 src, u64 dst, const std::vector<u64>& type_ids) const;  // :1797-1837
 
+    // Vector indexes (vector_index.cpp), keyed by (label id, attribute) for nodes and (type id, attribute) for relationships.
+    // The attribute store is out of scope: the caller feeds the vectors in, as the reference's indexer is fed by property
+    // writes.  create on an indexed (owner, attribute) throws; drop returns whether there was one.
+    void vector_index_create(bool is_edge, u64 owner, const std::string& attr, u64 dim, const char* similarity);
+    bool vector_index_drop(bool is_edge, u64 owner, const std::string& attr);
+    // upsert / remove one entity's vector; no index on (owner, attr) throws, n != dim throws the dimension mismatch text
+    void vector_set_node(LabelId label, const std::string& attr, u64 node, const float* vec, u64 n);
+    void vector_set_edge(u64 type, const std::string& attr, u64 src, u64 dst, u64 edge_id, const float* vec, u64 n);
+    bool vector_unset_node(LabelId label, const std::string& attr, u64 node);
+    bool vector_unset_edge(u64 type, const std::string& attr, u64 edge_id);
+    // db.idx.vector.queryNodes / queryRelationships for nq queries of qn components each, ONE fgpu_vecidx_knn call
+    // (graph.rs:3408-3457 answers one; NodeByVectorScanOp::next calls it per parent row).  k <= 0 throws "Invalid arguments
+    // for procedure '...'", qn != dim "Vector dimension mismatch, expected {dim} but got {qn}"; an unknown label / type or no
+    // index on (it, attr) gives no rows (indexer.rs:525-536).  Rows per query in ascending (distance, id).
+    VectorHits vector_query(bool is_edge, const std::string& owner_name, const std::string& attr, int64_t k, const float* queries,
+                            u64 qn, u64 nq) const;
+    const VectorIndex* vector_index(bool is_edge, u64 owner, const std::string& attr) const;
+
    private:
+    // delete_node / delete_edge: the entity leaves every index that holds it (of one owner when given)
+    void drop_entity_vectors(bool is_edge, std::optional<u64> owner, u64 entity);
+    std::map<std::tuple<bool, u64, std::string>, std::unique_ptr<VectorIndex>> vec_indexes_;
     Context* ctx_;
     u64 n_;
     VersionedMatrix adj_, labels_;

@@ -339,6 +339,43 @@ int fh_algo_betweenness(fh_graph* g, const char* labels, const char* types, int6
  * LAGr_Betweenness receives them.  Free *out with fh_free. */
 int fh_betweenness_sources(uint64_t n_nodes, int64_t sampling_size, int64_t sampling_seed, uint64_t** out, uint64_t* n);
 
+/* Vector indexes and db.idx.vector.queryNodes / queryRelationships (runtime/ops/node_by_vector_scan.rs,
+ * edge_by_vector_scan.rs; Graph::vector_query_nodes / _edges, graph.rs:3408-3520).  An index is an fgpu_vecidx, whose comment
+ * in fgpu.h states the rules: the search is exhaustive, rows come in ascending (distance, id).  Node indexes are keyed by
+ * (label id, attribute), relationship indexes by (type id, attribute).  The attribute store is out of scope, so the caller
+ * feeds the vectors in, as the reference's indexer is fed by property writes.
+ * similarity = "euclidean", "cosine", "ip" or NULL (euclidean); anything else fails with "Unknown similarity function
+ * '{other}', expected 'euclidean', 'ip', or 'cosine'" (index/mod.rs:1259-1270).  create fails on an (owner, attribute) that
+ * is indexed already; drop returns 0 when there was an index, 1 when not. */
+int fh_graph_vector_index_create(fh_graph* g, int is_edge, uint64_t label_or_type_id, const char* attr, uint64_t dim,
+                                 const char* similarity);
+int fh_graph_vector_index_drop(fh_graph* g, int is_edge, uint64_t label_or_type_id, const char* attr);
+/* Upsert one entity's vector of n components.  No index on (label / type, attr) fails; n other than the index's dimension
+ * fails with "Vector dimension mismatch, expected {dim} but got {n}"; a NaN or infinite component fails.  A relationship index
+ * keeps (src, dst) per relationship id.  unset returns 0 when the entity had a vector, 1 when not.  fh_graph_delete_node and
+ * fh_graph_delete_edge drop the entity's vectors from every index that holds them (test_vecsim.py test09). */
+int fh_graph_vector_set_node(fh_graph* g, uint64_t label_id, const char* attr, uint64_t node, const float* vec, uint64_t n);
+int fh_graph_vector_set_edge(fh_graph* g, uint64_t type_id, const char* attr, uint64_t src, uint64_t dst, uint64_t edge_id,
+                             const float* vec, uint64_t n);
+int fh_graph_vector_unset_node(fh_graph* g, uint64_t label_id, const char* attr, uint64_t node);
+int fh_graph_vector_unset_edge(fh_graph* g, uint64_t type_id, const char* attr, uint64_t edge_id);
+/* CALL db.idx.vector.queryNodes(label, attr, k, q) YIELD node, score: the min(k, indexed) nearest entities, ascending.  k <= 0
+ * fails with "Invalid arguments for procedure 'db.idx.vector.queryNodes'" (queryRelationships' for the edge call); qn other
+ * than the index's dimension fails with "Vector dimension mismatch, expected {dim} but got {qn}"; an unknown label / type, or
+ * no index on (it, attr), gives no rows and is no error (indexer.rs:525-536).  Free the arrays with fh_free. */
+int fh_vector_query_nodes(fh_graph* g, const char* label, const char* attr, int64_t k, const float* q, uint64_t qn,
+                          uint64_t** ids, double** dist, uint64_t* n);
+int fh_vector_query_edges(fh_graph* g, const char* type, const char* attr, int64_t k, const float* q, uint64_t qn,
+                          uint64_t** ids, double** dist, uint64_t** srcs, uint64_t** dsts, uint64_t* n);
+/* What NodeByVectorScanOp::next does for a whole parent batch (<= 1024 rows, batch.rs) in ONE fgpu_vecidx_knn call: queries =
+ * nq rows of qn components.  The rows of query i are ids / dist [offsets[i] .. offsets[i + 1]); offsets has nq + 1 entries. */
+int fh_vector_query_nodes_batch(fh_graph* g, const char* label, const char* attr, int64_t k, const float* queries, uint64_t qn,
+                                uint64_t nq, uint64_t** offsets, uint64_t** ids, double** dist);
+/* vec.euclideanDistance / vec.cosineDistance (spatial.rs:151-203, runtime/vec_distance.rs) on the host in FP64, the D of
+ * fgpu_vecidx_knn: metric = "euclidean", "cosine" or "ip".  na != nb fails with "Vector dimension mismatch, expected {na} but
+ * got {nb}". */
+int fh_vec_distance(const char* metric, const float* a, uint64_t na, const float* b, uint64_t nb, double* out);
+
 #ifdef __cplusplus
 }
 #endif

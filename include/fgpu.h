@@ -681,6 +681,66 @@ fgpu_info fgpu_shortest_dag(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At
                             int64_t* length, uint64_t* n_pairs, uint64_t** from, uint64_t** to, uint64_t** depth,
                             uint64_t stats[8]);
 
+/* Exhaustive vector similarity search: the numeric core of db.idx.vector.queryNodes / queryRelationships
+ * (runtime/ops/node_by_vector_scan.rs, edge_by_vector_scan.rs) and of vec.euclideanDistance / vec.cosineDistance.  The
+ * reference asks an approximate HNSW graph (RediSearch / VecSim, index/mod.rs:1768-1823) for k candidates, recomputes each
+ * candidate's distance from the stored vector and sorts the survivors (graph.rs:3408-3457, runtime/vec_distance.rs), one
+ * query per parent row.  Here every stored vector is scored against a whole batch of queries, so recall is 1 by
+ * construction; RediSearch's source is not vendored, these are the rules:
+ *   - an index holds vectors of one dimension dim = 1 .. FGPU_VECIDX_DIM_MAX under one metric, each under an id below
+ *     2^32 - 1 (a larger id is FGPU_INVALID).  The store is a dense array on the device without holes; its capacity doubles;
+ *   - fgpu_vecidx_set is an upsert of n (id, vector) pairs: a present id is replaced, and of an id given twice in one call
+ *     the last occurrence wins.  fgpu_vecidx_remove moves the last vector into each hole; an absent id is not an error and
+ *     *removed (nullable) counts the ids that were present.  fgpu_vecidx_get copies one stored vector out (*present = 0: no
+ *     such id, vec untouched);
+ *   - a component that is NaN or +-inf, in fgpu_vecidx_set or in a query, is FGPU_INVALID and the call changes nothing.  The
+ *     reference would sort such rows arbitrarily; refusing them is what makes the order below total;
+ *   - the reported distance D(q, x) is computed in FP64 from the stored f32 components, accumulated in index order, for the
+ *     returned entries only, as vec_distance.rs does:
+ *       euclidean  sqrt(sum (q_i - x_i)^2)
+ *       ip         -sum q_i x_i
+ *       cosine     1 - sum q_i x_i / (sqrt(sum q_i^2) * sqrt(sum x_i^2)), and exactly 1.0 when either vector is all zeros;
+ *   - the SELECTION key is f32.  S(q, x) is the dot product as a k-ordered fmaf chain from 0 over i = 0 .. dim - 1 — what
+ *     v_mfma_f32_16x16x4_f32 produces bit for bit, and no kernel splits K across lanes or wavefronts; nx and nq are the same
+ *     chain of x . x and q . q.  Then
+ *       euclidean  key = fl(fl(nq + nx) - 2 S)
+ *       ip         key = -S
+ *       cosine     key = fl(1 - fl(S / fl(fl(sqrt(nq)) * fl(sqrt(nx))))), sqrt and the division correctly rounded, and 1.0
+ *                  when nq or nx is 0.
+ *     The key is a pure function of (q, x): the same for a query alone and for that query inside a batch of 1024.  Keys are
+ *     compared as f32 values with -0.0 = +0.0.  Finite components can still overflow f32 on the way (components near 1e19
+ *     and beyond under euclidean: nq, nx or S becomes inf; a cosine denominator that underflows to 0): a key of -inf or +inf
+ *     orders as the f32 value it is, and a NaN key (inf - inf, 0 / 0) sorts after every other key, +inf included.  With the
+ *     id as the second component the order is total for every input the calls accept; D is FP64 and does not overflow;
+ *   - fgpu_vecidx_knn returns, per query, the kk = min(k, count) entries of smallest (key, id), in ascending (D, id) order:
+ *     *kk_out = kk, and ids / dist (HOST arrays of nq * kk) have row stride kk.  The caller sizes them from fgpu_vecidx_info.
+ *     k == 0 is FGPU_INVALID.  With nq == 0 or count == 0, kk is 0 and the call does nothing (ids / dist may be NULL);
+ *   - stats (nullable): [0] scoring launches, [1] query tiles of 16 (padding tiles included), [2] bytes of stored vectors
+ *     read by scoring, [3] entries whose key tied the kk-th key where more of them tied than places were left, so that the id
+ *     order had to decide;
+ *   - a NULL ctx / index / required array is FGPU_NULL_POINTER;
+ *   - fgpu_vecidx_set, _remove and _free must not run concurrently with any other call on the same index (the reference
+ *     holds the graph's write lock there); fgpu_vecidx_knn / _get / _info calls from several threads on one index are
+ *     independent, each on its caller's lane.
+ * One scoring kernel family serves every nq: the queries are padded to tiles of 16, one reading of the store serves up to 64
+ * of them, and the key images of a chunk of queries go through a radix select on the device; only the final (D, id) ordering
+ * of the kk survivors of a query happens on the host (vecidx.hip).  A chunk is as many queries (16, 32 or a multiple of 64, at
+ * most 4096) as keep the key images (4 bytes per query and stored vector) and the survivors (20 bytes per query and returned
+ * entry) under 256 MiB of device scratch each — never fewer than one tile of 16, whatever that takes. */
+typedef struct fgpu_vecidx fgpu_vecidx;
+#define FGPU_VEC_EUCLIDEAN 0
+#define FGPU_VEC_COSINE 1
+#define FGPU_VEC_IP 2
+#define FGPU_VECIDX_DIM_MAX 4096
+fgpu_info fgpu_vecidx_new(fgpu_ctx* ctx, fgpu_vecidx** out, uint32_t dim, int metric);
+fgpu_info fgpu_vecidx_free(fgpu_vecidx* index);
+fgpu_info fgpu_vecidx_info(const fgpu_vecidx* index, uint32_t* dim, int* metric, uint64_t* count);
+fgpu_info fgpu_vecidx_set(fgpu_ctx* ctx, fgpu_vecidx* index, const uint64_t* ids, const float* vecs /* n * dim */, uint64_t n);
+fgpu_info fgpu_vecidx_remove(fgpu_ctx* ctx, fgpu_vecidx* index, const uint64_t* ids, uint64_t n, uint64_t* removed);
+fgpu_info fgpu_vecidx_get(fgpu_ctx* ctx, const fgpu_vecidx* index, uint64_t id, float* vec /* dim */, int* present);
+fgpu_info fgpu_vecidx_knn(fgpu_ctx* ctx, const fgpu_vecidx* index, const float* queries /* nq * dim */, uint64_t nq, uint64_t k,
+                          uint64_t* ids /* nq * kk */, double* dist /* nq * kk */, uint64_t* kk_out, uint64_t stats[4]);
+
 /* The smallest stored value of A under the order of fgpu_msf's K (the IEEE totalOrder with -0.0 = +0.0), as a binary64 bit
  * pattern (LAGraph_Cached_EMin).  *found = 0 when A has no entry; a BOOL snapshot answers 1.0.  A device reduction: no entry
  * visits the host. */
