@@ -99,6 +99,8 @@ SIGNATURES = {
     "fgpu_sssp_hops": (C.c_int32, [vp, vp, C.c_uint64, C.c_int32, C.POINTER(C.c_double), u64p]),
     "fgpu_shortest_dag": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int64, i64p, u64p, C.POINTER(u64p), C.POINTER(u64p),
                                       C.POINTER(u64p), u64p]),
+    "fgpu_shortest_dag_batch": (C.c_int32, [vp, vp, vp, u64p, u64p, C.c_uint64, C.c_int64, C.c_uint32, i64p, u64p, C.POINTER(u64p),
+                                            C.POINTER(u64p), C.POINTER(u64p), u64p]),
     "fgpu_vecidx_new": (C.c_int32, [vp, vpp, C.c_uint32, C.c_int]),
     "fgpu_vecidx_free": (C.c_int32, [vp]),
     "fgpu_vecidx_info": (C.c_int32, [vp, u32p, C.POINTER(C.c_int), u64p]),

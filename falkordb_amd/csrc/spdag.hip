@@ -46,11 +46,9 @@
 //     only LATER launches read them.  The mark words change by atomicOr only.  Nothing polls or spins.
 // Nothing is cached on the matrices; every temporary is a DevBuf / MatRef / ResultBuf of the call, which runs on the calling
 // thread's lane.  No kernel spills; static LDS: 32 bytes (block_add_u64), 32 KiB in the sort; no dynamic LDS.
-#include "algo.hpp"
+#include "spdag.hpp"
 
 namespace fgpu {
-
-constexpr u32 SD_NONE = 0xFFFFFFFFu;
 
 // the device counters, all cumulative over the call; the host reads them whole after every level (SD_CTL_WORDS words)
 struct SpdagCtl {
@@ -192,44 +190,13 @@ __global__ __launch_bounds__(256) void spdag_sweep_kernel(CsrView m, const u32* 
     block_add_u64(ents, &ctl->sent);
 }
 
-// the depth of a DAG pair: its from-vertex' forward level where set, else L minus its backward level
-struct SdDepth {
-    const u32* df;
-    const u32* db;
-    u32 L;
-    __device__ u64 operator()(u32, u32 r, u32) const { return df[r] != SD_NONE ? df[r] : L - db[r]; }
-};
-
-constexpr u32 SD_SORT_MAX = 4096;   // pairs the one-workgroup sort takes: 32 KiB of keys in LDS
-
-// k <= SD_SORT_MAX pairs: one workgroup sorts the keys from << 32 | to in LDS (bitonic over the next power of two, the padding
-// keys all ones: no vertex id is 0xFFFFFFFF) and writes the three result columns in that order
+// k <= SD_SORT_MAX pairs: one workgroup sorts the keys from << 32 | to in LDS and writes the three result columns in that order
+// (sd_sort_block, spdag.hpp)
 __global__ __launch_bounds__(256) void spdag_sort_small_kernel(const u32* __restrict__ prow, const u32* __restrict__ pcol, u32 k,
                                                               SdDepth depth, u64* __restrict__ ofrom, u64* __restrict__ oto,
                                                               u64* __restrict__ odepth) {
     __shared__ u64 s_key[SD_SORT_MAX];
-    u32 m = 1;
-    while (m < k) m <<= 1;
-    for (u32 i = threadIdx.x; i < m; i += 256) s_key[i] = i < k ? ((u64)prow[i] << 32) | pcol[i] : ~0ull;
-    __syncthreads();
-    for (u32 size = 2; size <= m; size <<= 1) {
-        for (u32 stride = size >> 1; stride; stride >>= 1) {
-            for (u32 t = threadIdx.x; t < (m >> 1); t += 256) {
-                const u32 lo = 2 * t - (t & (stride - 1)), hi = lo + stride;   // the t-th index with bit `stride` clear, its partner
-                const bool up = (lo & size) == 0;
-                const u64 a = s_key[lo], b = s_key[hi];
-                if ((a > b) == up) { s_key[lo] = b; s_key[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (u32 i = threadIdx.x; i < k; i += 256) {
-        const u64 key = s_key[i];
-        const u32 r = (u32)(key >> 32), c = (u32)key;
-        ofrom[i] = r;
-        oto[i] = c;
-        odepth[i] = depth(i, r, c);
-    }
+    sd_sort_block(s_key, prow, pcol, k, depth, ofrom, oto, odepth);
 }
 
 // the whole call's device state and the host's copy of its counters

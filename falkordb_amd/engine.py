@@ -707,6 +707,32 @@ def shortest_dag(ctx: Context, A: Mat, At: Mat | None, src: int, dst: int, max_h
     return out + ([int(x) for x in st],) if stats else out
 
 
+def shortest_dag_batch(ctx: Context, A: Mat, At: Mat | None, srcs, dsts, max_hops: int = -1, slots: int = 0, stats: bool = False):
+    """fgpu_shortest_dag_batch: shortest_dag for the queries (srcs[i], dsts[i]) in one call, `slots` of them searched together
+    (0 = derived from the vertex count, at most 64).  Returns a list with, per query, the tuple shortest_dag returns for it:
+    (length, from, to, depth) and, when stats=True, its eight counters.  The arrays of the queries are slices of three
+    arrays the call returned."""
+    s, d = _u64(srcs), _u64(dsts)
+    assert len(s) == len(d)
+    count = len(s)
+    f, t, dep = u64p(), u64p(), u64p()
+    length = np.zeros(count, dtype=np.int64)
+    off = np.zeros(count + 1, dtype=np.uint64)
+    st = np.zeros(count * 8, dtype=np.uint64) if stats else None
+    check(ctx.lib.fgpu_shortest_dag_batch(ctx._h, A._h, At._h if At else None, _p(s) if count else None, _p(d) if count else None,
+                                          C.c_uint64(count), C.c_int64(max_hops), C.c_uint32(slots),
+                                          length.ctypes.data_as(C.POINTER(C.c_int64)), _p(off), C.byref(f), C.byref(t), C.byref(dep),
+                                          _p(st)))
+    total = int(off[count])
+    cols = [ctx._take(x, total) for x in (f, t, dep)]
+    out = []
+    for i in range(count):
+        lo, hi = int(off[i]), int(off[i + 1])
+        row = (int(length[i]), cols[0][lo:hi], cols[1][lo:hi], cols[2][lo:hi])
+        out.append(row + ([int(x) for x in st[8 * i:8 * i + 8]],) if stats else row)
+    return out
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

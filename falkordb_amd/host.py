@@ -529,6 +529,29 @@ class Graph:
         e = _take(oe, offs[-1]).tolist()
         return length.value, [e[offs[i]:offs[i + 1]] for i in range(n.value)]
 
+    def all_shortest_paths_batch(self, srcs, dsts, types=(), bidirectional=False, reversed=False, max_hops=None, limit=0,
+                                 stats=False):
+        """AllShortestPathsOp over a parent batch of input rows: [(length, paths), ...], row i what all_shortest_paths(srcs[i],
+        dsts[i], ...) returns.  The adjacency is built once and one device call serves every row; a row with an out-of-range or
+        deleted node, and every row under an unknown type, is (-1, []).  stats=True: a second item {"device_calls": 0 | 1}."""
+        s, d = np.ascontiguousarray(srcs, dtype=np.uint64), np.ascontiguousarray(dsts, dtype=np.uint64)
+        assert len(s) == len(d)
+        count = len(s)
+        oe, off = u64p(), u64p()
+        lengths = np.zeros(count, dtype=np.int64)
+        row_off = np.zeros(count + 1, dtype=np.uint64)
+        calls = C.c_uint64()
+        _ck(self.L.fh_all_shortest_paths_batch(self.h, ",".join(types).encode(), 1 if bidirectional else 0, 1 if reversed else 0,
+                                               C.c_uint32(0xFFFFFFFF if max_hops is None else max_hops),
+                                               s.ctypes.data_as(u64p), d.ctypes.data_as(u64p), C.c_uint64(count), C.c_uint64(limit),
+                                               lengths.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(oe), C.byref(off),
+                                               row_off.ctypes.data_as(u64p), C.byref(calls)))
+        ro = row_off.tolist()
+        offs = _take(off, ro[-1] + 1).tolist()
+        e = _take(oe, offs[-1]).tolist()
+        rows = [(int(lengths[i]), [e[offs[p]:offs[p + 1]] for p in range(ro[i], ro[i + 1])]) for i in range(count)]
+        return (rows, {"device_calls": int(calls.value)}) if stats else rows
+
     def build_adjacency(self, types=(), symmetric=False):
         """Graph::build_adjacency_matrix / build_symmetric_adjacency_matrix (graph.rs:3870-3907) -> Matrix"""
         h = C.c_void_p()

@@ -617,6 +617,38 @@ int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int
     });
 }
 
+// AllShortestPathsOp over a parent batch of rows: the paths of all rows flattened, path_off cuts them into paths, row_off the
+// paths into rows
+int fh_all_shortest_paths_batch(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops,
+                                const uint64_t* srcs, const uint64_t* dsts, uint64_t count, uint64_t limit, int64_t* lengths,
+                                uint64_t** edges, uint64_t** path_off, uint64_t* row_off, uint64_t* device_calls) {
+    return guard([&] {
+        AllShortestPathsOp op;
+        op.types = csv(types);
+        op.bidirectional = bidirectional != 0;
+        op.reversed = reversed != 0;
+        op.max_hops = max_hops;
+        const std::vector<u64> s(srcs, srcs + count), d(dsts, dsts + count);
+        std::vector<int64_t> len;
+        u64 calls = 0;
+        const auto rows = timed([&] { return op.expand_batch(g->g, s, d, limit, &len, &calls); });
+        std::vector<u64> e, off{0};
+        row_off[0] = 0;
+        for (u64 i = 0; i < count; ++i) {
+            for (auto& p : rows[i]) {
+                e.insert(e.end(), p.begin(), p.end());
+                off.push_back(e.size());
+            }
+            row_off[i + 1] = off.size() - 1;
+            lengths[i] = len[i];
+        }
+        *edges = hand(e);
+        *path_off = hand(off);
+        if (device_calls) *device_calls = calls;
+        return 0;
+    });
+}
+
 // fh_algo_bfs and fh_algo_bfs_multi: one call but for the gang (nullptr: the graph's own context); only the single-context
 // entry is a timed operator
 static int algo_bfs_c(fh_graph* g, const std::vector<Context*>* gang, int64_t source, int64_t max_depth, const char* rel_type,

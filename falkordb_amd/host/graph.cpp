@@ -676,37 +676,21 @@ void ExpandIntoOp::expand_batch(const Graph& g, const std::vector<u64>& srcs, co
 }
 
 // ---- AllShortestPaths -----------------------------------------------------------------------------------
-std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64 src, u64 dst, u64 limit, int64_t* length) const {
+// What both entry points do once the device has answered: the predecessor lists of ONE query's DAG — the pairs [p0, p0 + k) of
+// from / to, sorted by (from, to), with fwd[t][p] / bwd[t][p] the relationship ids of type t behind pair p and behind its reverse
+// — rebuilt in the reference's order, then the LIFO backtrack.  (A batch passes slices of the arrays of all its rows.)
+static std::vector<std::vector<u64>> asp_walk(const AllShortestPathsOp& op, size_t ntypes, u64 src, u64 dst, int64_t L, u64 limit,
+                                              const std::vector<u64>& from, const std::vector<u64>& to, size_t p0, size_t k,
+                                              const std::vector<std::vector<std::vector<u64>>>& fwd,
+                                              const std::vector<std::vector<std::vector<u64>>>& bwd) {
     std::vector<std::vector<u64>> out;
-    if (length) *length = -1;
-    const u64 n = g.node_cap();
-    if (src >= n || dst >= n || g.is_node_deleted(src) || g.is_node_deleted(dst)) return out;
-    const std::vector<u64> tids = resolve_types(g, types);               // (a name listed twice is walked twice: filter_map)
-    if (tids.empty()) return out;
-    Matrix adj = bidirectional ? g.build_symmetric_adjacency_matrix(types) : g.build_adjacency_matrix(types);
-    Matrix adj_t = bidirectional ? adj : adj.transpose();
-    int64_t L = -1;
-    u64 k = 0;
-    EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth)
-    check(fgpu_shortest_dag(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), src, dst, max_hops == UINT32_MAX ? -1 : (int64_t)max_hops,
-                            &L, &k, &dag.rows, &dag.cols, (uint64_t**)&dag.vals, nullptr),
-          "allShortestPaths");
-    dag.n = k;
-    if (L < 0) return out;
-    if (length) *length = L;
-    const bool cycle = src == dst;
-    // the relationships behind every pair, per type: (u, v), and (v, u) under a bidirectional pattern
-    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
-    std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
-    for (size_t t = 0; t < tids.size(); ++t) {
-        g.relationship_tensors()[tids[t]].get_batch(from, to, fwd[t]);
-        if (bidirectional) g.relationship_tensors()[tids[t]].get_batch(to, from, bwd[t]);
-    }
+    const bool cycle = src == dst, bidirectional = op.bidirectional;
+    const size_t p1 = p0 + k;
     // the pairs are sorted by (from, to): the out-pairs of a vertex are one run
     std::unordered_map<u64, std::pair<size_t, size_t>> run;
-    for (size_t i = 0; i < k;) {
+    for (size_t i = p0; i < p1;) {
         size_t j = i;
-        while (j < k && from[j] == from[i]) ++j;
+        while (j < p1 && from[j] == from[i]) ++j;
         run[from[i]] = {i, j};
         i = j;
     }
@@ -734,7 +718,7 @@ std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64
                 }
                 for (u64 e : ids) preds[it->second].push_back({cur, e});
             };
-            for (size_t t = 0; t < tids.size(); ++t) {
+            for (size_t t = 0; t < ntypes; ++t) {
                 for (size_t p = r->second.first; p < r->second.second; ++p) reach(p, fwd[t][p]);          // outgoing by (dst, id)
                 if (bidirectional)
                     for (size_t p = r->second.first; p < r->second.second; ++p)
@@ -753,7 +737,7 @@ std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64
         stack.pop_back();
         if (node == 0) {
             if (!cycle) std::reverse(path.begin(), path.end());
-            if (reversed) std::reverse(path.begin(), path.end());
+            if (op.reversed) std::reverse(path.begin(), path.end());
             out.push_back(std::move(path));
             if (limit && out.size() >= limit) break;
             continue;
@@ -763,6 +747,84 @@ std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64
             longer.push_back(p.edge);
             stack.push_back({p.prev, std::move(longer)});
         }
+    }
+    return out;
+}
+
+std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64 src, u64 dst, u64 limit, int64_t* length) const {
+    std::vector<std::vector<u64>> out;
+    if (length) *length = -1;
+    const u64 n = g.node_cap();
+    if (src >= n || dst >= n || g.is_node_deleted(src) || g.is_node_deleted(dst)) return out;
+    const std::vector<u64> tids = resolve_types(g, types);               // (a name listed twice is walked twice: filter_map)
+    if (tids.empty()) return out;
+    Matrix adj = bidirectional ? g.build_symmetric_adjacency_matrix(types) : g.build_adjacency_matrix(types);
+    Matrix adj_t = bidirectional ? adj : adj.transpose();
+    int64_t L = -1;
+    u64 k = 0;
+    EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth)
+    check(fgpu_shortest_dag(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), src, dst, max_hops == UINT32_MAX ? -1 : (int64_t)max_hops,
+                            &L, &k, &dag.rows, &dag.cols, (uint64_t**)&dag.vals, nullptr),
+          "allShortestPaths");
+    dag.n = k;
+    if (L < 0) return out;
+    if (length) *length = L;
+    // the relationships behind every pair, per type: (u, v), and (v, u) under a bidirectional pattern
+    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
+    std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
+    for (size_t t = 0; t < tids.size(); ++t) {
+        g.relationship_tensors()[tids[t]].get_batch(from, to, fwd[t]);
+        if (bidirectional) g.relationship_tensors()[tids[t]].get_batch(to, from, bwd[t]);
+    }
+    return asp_walk(*this, tids.size(), src, dst, L, limit, from, to, 0, k, fwd, bwd);
+}
+
+std::vector<std::vector<std::vector<u64>>> AllShortestPathsOp::expand_batch(const Graph& g, const std::vector<u64>& srcs,
+                                                                            const std::vector<u64>& dsts, u64 limit,
+                                                                            std::vector<int64_t>* lengths, u64* device_calls) const {
+    if (srcs.size() != dsts.size()) throw std::invalid_argument("allShortestPaths: srcs and dsts differ in length");
+    const size_t count = srcs.size();
+    std::vector<std::vector<std::vector<u64>>> out(count);
+    if (lengths) lengths->assign(count, -1);
+    if (device_calls) *device_calls = 0;
+    const u64 n = g.node_cap();
+    const std::vector<u64> tids = resolve_types(g, types);
+    if (tids.empty()) return out;
+    // the rows the device sees: both nodes in range and alive
+    std::vector<size_t> row;
+    std::vector<u64> s, d;
+    for (size_t i = 0; i < count; ++i) {
+        if (srcs[i] >= n || dsts[i] >= n || g.is_node_deleted(srcs[i]) || g.is_node_deleted(dsts[i])) continue;
+        row.push_back(i);
+        s.push_back(srcs[i]);
+        d.push_back(dsts[i]);
+    }
+    if (row.empty()) return out;
+    // the pattern matrix and its transpose, once for the batch
+    Matrix adj = bidirectional ? g.build_symmetric_adjacency_matrix(types) : g.build_adjacency_matrix(types);
+    Matrix adj_t = bidirectional ? adj : adj.transpose();
+    std::vector<int64_t> L(row.size(), -1);
+    std::vector<u64> off(row.size() + 1, 0);
+    EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth) of every row
+    check(fgpu_shortest_dag_batch(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), s.data(), d.data(), row.size(),
+                                  max_hops == UINT32_MAX ? -1 : (int64_t)max_hops, 0, L.data(), off.data(), &dag.rows, &dag.cols,
+                                  (uint64_t**)&dag.vals, nullptr),
+          "allShortestPaths");
+    if (device_calls) *device_calls = 1;
+    const size_t k = off.back();
+    dag.n = k;
+    // the relationships behind the pairs of ALL rows: one probe per type and direction
+    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
+    std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
+    if (k)
+        for (size_t t = 0; t < tids.size(); ++t) {
+            g.relationship_tensors()[tids[t]].get_batch(from, to, fwd[t]);
+            if (bidirectional) g.relationship_tensors()[tids[t]].get_batch(to, from, bwd[t]);
+        }
+    for (size_t j = 0; j < row.size(); ++j) {
+        if (L[j] < 0) continue;
+        if (lengths) (*lengths)[row[j]] = L[j];
+        out[row[j]] = asp_walk(*this, tids.size(), s[j], d[j], L[j], limit, from, to, off[j], off[j + 1] - off[j], fwd, bwd);
     }
     return out;
 }

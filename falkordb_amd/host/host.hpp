@@ -619,6 +619,14 @@ struct AllShortestPathsOp {
     // chain, :274-289).  limit > 0 stops after that many paths (the reference streams them: a diamond chain holds
     // exponentially many).  *length (nullable) = the paths' length, -1 without one.
     std::vector<std::vector<u64>> expand_row(const Graph& g, u64 src, u64 dst, u64 limit = 0, int64_t* length = nullptr) const;
+    // a parent batch of rows, what the reference's operator is fed: out[i] and (*lengths)[i] are what expand_row(g, srcs[i],
+    // dsts[i], limit) gives.  The pattern matrix and its transpose are built ONCE, the rows whose nodes are in range and alive
+    // go to the device in ONE fgpu_shortest_dag_batch call (no resolvable type: none does), the relationship ids behind the
+    // pairs of all rows come from one Tensor::get_batch per type and direction, and every row then takes expand_row's walk.
+    // *device_calls (nullable) = the fgpu_shortest_dag_batch calls made: 0 or 1.
+    std::vector<std::vector<std::vector<u64>>> expand_batch(const Graph& g, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
+                                                            u64 limit = 0, std::vector<int64_t>* lengths = nullptr,
+                                                            u64* device_calls = nullptr) const;
 };
 
 struct BfsResult {

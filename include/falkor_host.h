@@ -181,6 +181,16 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
  * `path_off` (n_paths + 1 offsets) cuts it; both are freed with fh_free.  Edge-attribute filters are not served. */
 int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops, uint64_t src,
                           uint64_t dst, uint64_t limit, int64_t* length, uint64_t** edges, uint64_t** path_off, uint64_t* n_paths);
+/* AllShortestPathsOp over a parent batch of `count` input rows, row i = (srcs[i], dsts[i]): lengths[i] and the paths of row i are
+ * what fh_all_shortest_paths gives for that row under the same limit (applied per row).  The pattern matrix and its transpose
+ * are built once, ONE fgpu_shortest_dag_batch call serves every row whose nodes are in range and alive (a row with an
+ * out-of-range or deleted node, and every row when no type resolves, has length -1 and no path and never reaches the device),
+ * and the relationship ids come from one tensor probe per type and direction.  `edges` holds all paths back to back,
+ * `path_off` (row_off[count] + 1 offsets) cuts it into paths, row_off (count + 1 entries, the caller's) the paths into rows;
+ * edges and path_off are freed with fh_free.  *device_calls (nullable) = the fgpu_shortest_dag_batch calls made, 0 or 1. */
+int fh_all_shortest_paths_batch(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops,
+                                const uint64_t* srcs, const uint64_t* dsts, uint64_t count, uint64_t limit, int64_t* lengths,
+                                uint64_t** edges, uint64_t** path_off, uint64_t* row_off, uint64_t* device_calls);
 /* source < 0 = NULL; rel_type NULL = all types.  `edges` holds one id per (parent, child) pair that HAS a
  * representative edge among the types, in node order; a pair without one is skipped in `edges` but its child stays in
  * `nodes` — exactly what the reference yields (algo_procedures.rs:1121-1150) — so the two lists are parallel only

@@ -681,6 +681,34 @@ fgpu_info fgpu_shortest_dag(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At
                             int64_t* length, uint64_t* n_pairs, uint64_t** from, uint64_t** to, uint64_t** depth,
                             uint64_t stats[8]);
 
+/* fgpu_shortest_dag for a whole batch of queries over one adjacency: what an AllShortestPathsOp fed a parent batch of rows asks
+ * for.  The single call is bound by its launches and counter read-backs, not by its work; here `slots` queries at a time advance
+ * in lock-step rounds and share every round's launches and its one read-back (spdag_batch.hip).
+ *   - query i is (src[i], dst[i]) under the one max_hops of the call; A, At and max_hops mean what they mean above;
+ *   - length[i] is what fgpu_shortest_dag returns for query i, -1 without a path;
+ *   - pair_off has count + 1 entries, pair_off[0] = 0: the slice pair_off[i] .. pair_off[i + 1] of from / to / depth holds
+ *     exactly the single call's three arrays for query i, in its order.  A query without a path has an empty slice;
+ *   - stats (nullable, count * 8 words): stats[8 i .. 8 i + 8) are the single call's stats for query i.  Every query picks its
+ *     side by the single call's rule from its own frontier counts (the cycle shape keeps its first backward expansion), so this
+ *     holds under every spdag_sides setting, with At given or NULL;
+ *   - the queries are independent: duplicates and any order are allowed, and permuting the queries permutes the output;
+ *   - from / to / depth are freed with fgpu_free each; they are NULL when pair_off[count] == 0.  count == 0 returns FGPU_OK with
+ *     pair_off[0] = 0.  Repeated calls give identical arrays.
+ * slots is the number of queries searched together, at most FGPU_SPDAG_SLOTS_MAX.  Every slot has dense level words and mark
+ * bits of its own, 8 nrows + nrows / 4 bytes; every other temporary grows with the entries scanned.  slots = 0 derives it:
+ * min(count, FGPU_SPDAG_SLOTS_MAX, max(1, 2 GiB / (8 nrows))) — the level words of a group stay within 2 GiB, which is 64 slots
+ * up to 2^22 vertices.  The result does not depend on slots.
+ * A missing At is built once per call and released with it; nothing is cached on either matrix.
+ * Errors: NULL ctx / A / length / pair_off / from / to / depth, or NULL src / dst with count > 0: FGPU_NULL_POINTER; non-square
+ * A or an At of other dimensions: FGPU_DIM_MISMATCH; slots > FGPU_SPDAG_SLOTS_MAX, nrows >= 2^32 - 1 or nnz >= 2^32 - 1:
+ * FGPU_INVALID; any src[i] or dst[i] >= nrows: FGPU_OUT_OF_BOUNDS for the whole call, before any work — the message names i,
+ * no output is written or allocated.  nrows == 0 gives no path for every query.
+ * The call runs on the calling thread's lane: concurrent callers on the same matrices are independent. */
+#define FGPU_SPDAG_SLOTS_MAX 64
+fgpu_info fgpu_shortest_dag_batch(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_mat* At, const uint64_t* src, const uint64_t* dst,
+                                  uint64_t count, int64_t max_hops, uint32_t slots, int64_t* length, uint64_t* pair_off,
+                                  uint64_t** from, uint64_t** to, uint64_t** depth, uint64_t* stats);
+
 /* Exhaustive vector similarity search: the numeric core of db.idx.vector.queryNodes / queryRelationships
  * (runtime/ops/node_by_vector_scan.rs, edge_by_vector_scan.rs) and of vec.euclideanDistance / vec.cosineDistance.  The
  * reference asks an approximate HNSW graph (RediSearch / VecSim, index/mod.rs:1768-1823) for k candidates, recomputes each

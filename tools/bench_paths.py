@@ -45,6 +45,12 @@
           and 1 (forward only), median / min / max of 5 synchronised calls after 1 warm-up, and one fgpu_bfs (levels only) from
           the same src; then one summary line per graph with the medians over the pairs and the ratios
 
+  asp_batch  fgpu_shortest_dag_batch against a loop of fgpu_shortest_dag, in ONE process, on the graph and the 64 seeded pairs of
+          the asp leg, directed and symmetrised: (a) the loop of 64 single calls, (b) one batch of the same 64, (c) one batch of
+          1024 seeded pairs at slots = 0.  Median / min / max of 5 after 1 warm-up, ms per query, the entries scanned (stats [4]
+          and [5] summed), and that (b) returned what (a) did; with the host operator's batch against its per-row loop on the
+          host leg's graph (RMAT-18, one type, 64 rows, fh_last_op_ns)
+
   hops    the hop-bounded table behind algo.SPpaths' enumeration shapes (fgpu_sssp_hops) on RMAT-22 (or RMAT-<scale>)
           TRANSPOSED, with the hashed integer weights of the sssp leg, from the vertex with the most in-entries of the graph
           (= most out-entries of the transpose): max_hops 3 and 6 into a pinned table, median of 3 synchronised calls, the
@@ -644,6 +650,86 @@ def bench_asp(ctx, scale, npairs=64):
     A.free()
 
 
+def bench_asp_batch(ctx, scale, npairs=64, nbig=1024, host_scale=18):
+    """fgpu_shortest_dag_batch against the loop of single calls over the same pairs, same process, same handles"""
+    def spread(fn, reps=5, warm=1):
+        for _ in range(warm):
+            r = fn()
+        ctx.sync()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            ctx.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts)), float(min(ts)), float(max(ts)), r
+
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    At = A.transpose()
+    S = A.merge_pattern(At, None)
+    n = A.nrows
+    ctx.set_option("spdag_sides", 0)
+    for graph, M, Mt in (("directed", A, At), ("symmetrised", S, S)):
+        rp, _, _ = M.export_csr()
+        rpt, _, _ = Mt.export_csr()
+        live = np.nonzero((np.diff(rp.astype(np.int64)) > 0) & (np.diff(rpt.astype(np.int64)) > 0))[0]
+        rng = np.random.default_rng(0xA5B0 + scale)
+        picks = rng.choice(live, size=(npairs, 2))           # the asp leg's pairs
+        big = np.random.default_rng(0xB16 + scale).choice(live, size=(nbig, 2))
+        src, dst = picks[:, 0].tolist(), picks[:, 1].tolist()
+        ta, loa, hia, one = spread(lambda: [engine.shortest_dag(ctx, M, Mt, s, d, stats=True) for s, d in zip(src, dst)])
+        tb, lob, hib, bat = spread(lambda: engine.shortest_dag_batch(ctx, M, Mt, src, dst, stats=True))
+        equal = all(x[0] == y[0] and x[4] == y[4] and all(np.array_equal(p, q) for p, q in zip(x[1:4], y[1:4]))
+                    for x, y in zip(one, bat))
+        tc, loc, hic, bigr = spread(lambda: engine.shortest_dag_batch(ctx, M, Mt, big[:, 0], big[:, 1], stats=True))
+        scanned = lambda rs: int(sum(r[4][4] + r[4][5] for r in rs))
+        print(json.dumps({"path": "asp_batch", "graph": graph, "scale": scale, "n": n, "nnz": M.nvals, "pairs": npairs,
+                          "a_loop_ms_per_query": round(ta / npairs, 4), "a_loop_ms_min_max": [round(loa, 3), round(hia, 3)],
+                          "b_batch_ms_per_query": round(tb / npairs, 4), "b_batch_ms_min_max": [round(lob, 3), round(hib, 3)],
+                          "a_over_b": round(ta / tb, 2), "b_equals_a": bool(equal), "entries_scanned_64": scanned(bat),
+                          "found_64": int(sum(r[0] > 0 for r in bat)), "dag_pairs_64": int(sum(len(r[1]) for r in bat)),
+                          "c_pairs": nbig, "c_batch_ms_per_query": round(tc / nbig, 4), "c_batch_ms_min_max": [round(loc, 3), round(hic, 3)],
+                          "c_entries_scanned": scanned(bigr), "c_found": int(sum(r[0] > 0 for r in bigr)),
+                          "c_dag_pairs": int(sum(len(r[1]) for r in bigr)),
+                          "note": "host clock around synchronised calls in one process, median of 5 after 1 warm-up; (a) 64 "
+                                  "fgpu_shortest_dag calls in a loop, (b) one fgpu_shortest_dag_batch of the same 64, (c) one of 1024 "
+                                  "seeded pairs at slots = 0; stats on, transpose given, spdag_sides 0"}), flush=True)
+    S.free()
+    At.free()
+    A.free()
+    # the host operator on the host leg's graph: one batch of 64 rows against the per-row loop, the operator's own clock
+    from falkordb_amd import host
+    hc = host.Context(0)
+    B = ctx.mat_rmat(host_scale)
+    bn = B.nrows
+    brp, bci, _ = B.export_csr()
+    bdeg = np.diff(brp.astype(np.int64))
+    g = host.Graph(hc, bn)
+    ty = g.add_type("KNOWS")
+    g.create_edges(ty, np.repeat(np.arange(bn, dtype=np.uint64), bdeg), bci, np.arange(len(bci), dtype=np.uint64))
+    g.commit()
+    B.free()
+    live = np.nonzero(bdeg > 0)[0]
+    rows = np.random.default_rng(0xA5B0 + host_scale).choice(live, size=(npairs, 2))
+    loop_ms, batch_ms = [], []
+    for rep in range(4):   # (the first repetition warms both up)
+        t = 0
+        per_row = []
+        for s, d in rows.tolist():
+            per_row.append(g.all_shortest_paths(s, d, types=["KNOWS"], limit=16))
+            t += g.L.fh_last_op_ns() / 1e9
+        got = g.all_shortest_paths_batch(rows[:, 0], rows[:, 1], types=["KNOWS"], limit=16)
+        if rep:
+            loop_ms.append(t * 1e3)
+            batch_ms.append(g.L.fh_last_op_ns() / 1e9 * 1e3)
+    print(json.dumps({"path": "asp_batch_host", "scale": host_scale, "n": bn, "nnz": int(len(bci)), "rows": npairs, "limit": 16,
+                      "loop_ms_per_row": round(float(np.median(loop_ms)) / npairs, 4),
+                      "batch_ms_per_row": round(float(np.median(batch_ms)) / npairs, 4), "equal": got == per_row,
+                      "note": "fh_last_op_ns around the operator, median of 3 after 1 warm-up; the loop builds the adjacency per row"}),
+          flush=True)
+    hc.close()
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -738,6 +824,10 @@ if __name__ == "__main__":
     if what in ("asp", "all"):
         c = engine.Context(0)
         bench_asp(c, scale if scale else 22)
+        c.close()
+    if what in ("asp_batch", "all"):
+        c = engine.Context(0)
+        bench_asp_batch(c, scale if scale else 22)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
