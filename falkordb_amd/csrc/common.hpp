@@ -478,6 +478,10 @@ fgpu_info scan_u32_to_u64(fgpu_ctx* ctx, const u32* in, u64* out, u64 n, u64* to
 // `dirty` (nullable): segments with dirty[s]==0 are skipped (cnt[s] pre-filled by the caller).
 fgpu_info segsort_unique(fgpu_ctx* ctx, u32* data, const u64* off, u32 nseg, u32 key_bound,
                          u32* cnt, const uint8_t* dirty);
+// Sort the listed segments [off[s], off[s + 1]), s = list[k], of 64-bit keys ascending in place (keys below ~0).  Segments
+// of up to 64 keys sort in a wavefront, up to 4096 in a workgroup; longer ones are left as they are (the caller's).  *dup_flag
+// (device) is set to 1 when a sorted segment holds two equal keys.
+fgpu_info segsort_u64(fgpu_ctx* ctx, u64* data, const u32* off, const u32* list, u32 nlist, u32* dup_flag);
 // Gather the unique prefixes into a dense CSR; rowptr = exclusive scan of cnt (nseg+1 entries).
 fgpu_info compact_segments(fgpu_ctx* ctx, const u32* data, const u64* off, const u32* rowptr,
                            u32 nseg, u32* col_out);
@@ -516,6 +520,8 @@ void ks_set_wb_override(int wb);   // experiment knob: low-digit bits of the cou
 fgpu_info mat_transpose_counting(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a);
 // stable sort of n (key, value) pairs by key < nkeys: out_val = the values in key order, keyptr[nkeys + 1] = start of every key's run
 fgpu_info sort_u32_pairs_by_key(fgpu_ctx* ctx, const u32* key, const u32* val, u64 n, u64 nkeys, u32* out_val, u32* keyptr);
+// the same sort in the form the builders pick for (n, nkeys); FGPU_NO_VALUE below 4096 pairs or past 2^31 keys
+fgpu_info sort_u32_pairs_stable(fgpu_ctx* ctx, const u32* key, const u32* val, u64 n, u64 nkeys, u32* out_val, u32* keyptr);
 // stable partition of the entries of a CSR by slot / div (slot = slot_of[column], or the column): (slot, row) pairs, part by part
 fgpu_info partition_csr_entries(fgpu_ctx* ctx, const u32* colidx, const u32* rowptr, u32 nrows, u64 nnz, const u32* slot_of, u32 div,
                                 u32 nparts, uint2* out_pairs, u32* pstart_dev);

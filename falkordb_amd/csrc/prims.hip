@@ -339,6 +339,85 @@ fgpu_info segsort_unique(fgpu_ctx* ctx, u32* data, const u64* off, u32 nseg, u32
 }
 
 // ---------------------------------------------------------------------------------
+// segsort_u64: the listed segments of 64-bit keys, ascending in place (the edge-id runs of a bulk load, edges.hip)
+// ---------------------------------------------------------------------------------
+constexpr u64 KEY64_INF = ~0ull;
+
+// One wavefront per LISTED segment of up to 64 keys (longer ones belong to the next kernel): the same network as above.
+__global__ __launch_bounds__(256) void segsort64_wave_kernel(u64* __restrict__ data, const u32* __restrict__ off,
+                                                            const u32* __restrict__ list, u32 nlist,
+                                                            u32* __restrict__ dup_flag) {
+    const u32 lane = lane_id();
+    const u32 it = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (it >= nlist) return;
+    const u32 seg = list[it];
+    const u32 b = off[seg];
+    const u32 len = off[seg + 1] - b;
+    if (len > SEG_WAVE_MAX || len <= 1) return;
+    unsigned long long x = (lane < len) ? data[b + lane] : KEY64_INF;
+#pragma unroll
+    for (u32 k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (u32 j = k >> 1; j >= 1; j >>= 1) {
+            unsigned long long y = __shfl_xor(x, j, 64);
+            bool up = ((lane & k) == 0);
+            bool lower = ((lane & j) == 0);
+            unsigned long long mn = x < y ? x : y, mx = x < y ? y : x;
+            x = (lower == up) ? mn : mx;
+        }
+    }
+    unsigned long long prev = __shfl_up(x, 1, 64);
+    if (lane < len) {
+        data[b + lane] = x;
+        if (lane > 0 && x == prev) *dup_flag = 1u;
+    }
+}
+
+// One workgroup per listed segment of 65..4096 keys: bitonic sort in LDS (32 KiB).
+__global__ __launch_bounds__(256) void segsort64_block_kernel(u64* __restrict__ data, const u32* __restrict__ off,
+                                                             const u32* __restrict__ list, u32 nlist,
+                                                             u32* __restrict__ dup_flag) {
+    __shared__ u64 s[SEG_BLOCK_MAX];
+    for (u32 it = blockIdx.x; it < nlist; it += gridDim.x) {
+        const u32 seg = list[it];
+        const u32 b = off[seg];
+        const u32 len = off[seg + 1] - b;
+        if (len <= SEG_WAVE_MAX || len > SEG_BLOCK_MAX) continue;   // (uniform over the workgroup)
+        u32 p2 = 128;
+        while (p2 < len) p2 <<= 1;
+        for (u32 i = threadIdx.x; i < p2; i += 256) s[i] = (i < len) ? data[b + i] : KEY64_INF;
+        __syncthreads();
+        for (u32 k = 2; k <= p2; k <<= 1) {
+            for (u32 j = k >> 1; j >= 1; j >>= 1) {
+                for (u32 t = threadIdx.x; t < (p2 >> 1); t += 256) {
+                    u32 i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // index with bit j clear
+                    u32 l = i | j;
+                    u64 a = s[i], c = s[l];
+                    bool up = ((i & k) == 0);
+                    if ((a > c) == up) { s[i] = c; s[l] = a; }
+                }
+                __syncthreads();
+            }
+        }
+        for (u32 i = threadIdx.x; i < len; i += 256) {
+            const u64 x = s[i];
+            data[b + i] = x;
+            if (i > 0 && s[i - 1] == x) *dup_flag = 1u;
+        }
+        __syncthreads();
+    }
+}
+
+fgpu_info segsort_u64(fgpu_ctx* ctx, u64* data, const u32* off, const u32* list, u32 nlist, u32* dup_flag) {
+    if (nlist == 0) return FGPU_OK;
+    FGPU_TRY(launch(segsort64_wave_kernel, dim3(cdiv(nlist, 4)), dim3(256), 0, ctx->stream(), data, off, list, nlist, dup_flag));
+    u32 grid = ctx->cus * 8;
+    if (grid > nlist) grid = nlist;
+    FGPU_TRY(launch(segsort64_block_kernel, dim3(grid), dim3(256), 0, ctx->stream(), data, off, list, nlist, dup_flag));
+    return FGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------
 // compaction of the unique prefixes into a dense CSR
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void compact_segments_kernel(const u32* __restrict__ data,

@@ -867,6 +867,13 @@ fgpu_info sort_u32_pairs_by_key(fgpu_ctx* ctx, const u32* key, const u32* val, u
     return i;
 }
 
+// ... and in whichever of the two forms applies to (n, nkeys), as the builders below pick it (the tuple sort of the bulk edge
+// load, edges.hip).  FGPU_NO_VALUE = neither applies: fewer than 4096 pairs, or a key space past 2^31.
+fgpu_info sort_u32_pairs_stable(fgpu_ctx* ctx, const u32* key, const u32* val, u64 n, u64 nkeys, u32* out_val, u32* keyptr) {
+    if (n < 4096) return FGPU_NO_VALUE;
+    return sort_pairs(ctx, key, val, nullptr, 0, n, nkeys, out_val, keyptr, nullptr);
+}
+
 fgpu_info mat_transpose_counting(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a) {
     if (a->is_hyper() || a->nnz < 4096 || a->nrows == 0) return FGPU_NO_VALUE;
     bool staged = false;

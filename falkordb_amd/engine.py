@@ -634,6 +634,27 @@ def msf(ctx: Context, W: Mat, active_bitmap=None, stats: bool = False, out=None)
     return comp, rows, cols, weights, ([int(x) for x in st] if stats else None)
 
 
+def edges_build(ctx: Context, nrows: int, ncols: int, srcs, dsts, ids, stats: bool = False):
+    """fgpu_edges_build: one relationship type's bulk batch of (src, dst, edge id) tuples as a Tensor holds it.  Returns (fwd,
+    bwd, multi_key, multi_off, multi_ids[, stats]) — fwd the UINT64 matrix with the edge id of a pair that has one edge and
+    MULTI_EDGE (~0) for a pair that has several, bwd the BOOL transposed pattern, multi_key the ascending compound keys
+    (src << 32 | dst) of the multi-edge pairs, multi_ids[multi_off[r] : multi_off[r + 1]] the ascending ids of pair r; stats the
+    eight counters of include/fgpu.h when stats=True."""
+    srcs, dsts, ids = _u64(srcs), _u64(dsts), _u64(ids)
+    if not (len(srcs) == len(dsts) == len(ids)):
+        raise ValueError("edges_build: srcs, dsts and ids differ in length")
+    fwd, bwd = C.c_void_p(), C.c_void_p()
+    mk, mo, mi = u64p(), u64p(), u64p()
+    nm = C.c_uint64()
+    st = np.zeros(8, dtype=np.uint64)
+    check(ctx.lib.fgpu_edges_build(ctx._h, C.c_uint64(nrows), C.c_uint64(ncols), _p(srcs), _p(dsts), _p(ids), len(srcs),
+                                   C.byref(fwd), C.byref(bwd), C.byref(mk), C.byref(mo), C.byref(mi), C.byref(nm), _p(st)))
+    off = ctx._take(mo, nm.value + 1)
+    total = int(off[-1])
+    out = (Mat(ctx, fwd), Mat(ctx, bwd), ctx._take(mk, nm.value), off, ctx._take(mi, total))
+    return out + ([int(x) for x in st],) if stats else out
+
+
 def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
     """fgpu_maxflow: LAGr_MaxFlow's result for algo.maxFlow over the capacity matrix C_ — a valued snapshot carries one binary64
     bit pattern per entry, a BOOL one means capacity 1.0; diagonal entries and capacities <= 0 are ignored, a NaN or infinite

@@ -390,6 +390,22 @@ class Graph:
         s, d, i = _u64(srcs), _u64(dsts), _u64(ids)
         _ck(self.L.fh_graph_create_edges(self.h, C.c_uint64(type_id), _p(s), _p(d), _p(i), C.c_uint64(len(s))))
 
+    def bulk_insert_edges(self, type_id, srcs, dsts, ids):
+        """fh_graph_bulk_insert_edges: one type's bulk batch through the device build; returns what it did as a dict."""
+        s, d, i = _u64(srcs), _u64(dsts), _u64(ids)
+        if not (len(s) == len(d) == len(i)):
+            raise ValueError("bulk_insert_edges: srcs, dsts and ids differ in length")
+        st = (C.c_uint64 * 6)()
+        _ck(self.L.fh_graph_bulk_insert_edges(self.h, C.c_uint64(type_id), _p(s), _p(d), _p(i), C.c_uint64(len(s)), st))
+        return dict(zip(("device_edges", "fallback_edges", "distinct_pairs", "multi_pairs", "unsorted_runs", "host_sorted_runs"),
+                        (int(x) for x in st)))
+
+    def last_bulk_phases_ms(self):
+        """fh_last_bulk_phases_ns: host-clock ms of the last bulk_insert_edges of this thread, by phase."""
+        ns = (C.c_uint64 * 4)()
+        _ck(self.L.fh_last_bulk_phases_ns(ns))
+        return dict(zip(("edges_build", "fold_adopt", "me_fill", "adjacency_union"), (x / 1e6 for x in ns)))
+
     def delete_edge(self, type_id, src, dst, edge_id):
         _ck(self.L.fh_graph_delete_edge(self.h, C.c_uint64(type_id), C.c_uint64(src), C.c_uint64(dst),
                                         C.c_uint64(edge_id)))

@@ -291,6 +291,24 @@ int fh_tensor_get(fh_graph* g, uint64_t type_id, uint64_t src, uint64_t dst, uin
         return 0;
     });
 }
+
+static thread_local uint64_t g_last_bulk_ns[4] = {0, 0, 0, 0};   // phases of this thread's last bulk insert (fh_last_bulk_phases_ns)
+int fh_last_bulk_phases_ns(uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_last_bulk_ns[k];
+    return 0;
+}
+int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* srcs, const uint64_t* dsts,
+                               const uint64_t* ids, uint64_t n, uint64_t stats[6]) {
+    return guard([&] {
+        BulkStats bs = g->g.bulk_insert_edges(type_id, srcs, dsts, ids, n);
+        for (int k = 0; k < 4; ++k) g_last_bulk_ns[k] = bs.phase_ns[k];
+        if (stats) {
+            stats[0] = bs.device_edges; stats[1] = bs.fallback_edges; stats[2] = bs.distinct_pairs;
+            stats[3] = bs.multi_pairs; stats[4] = bs.unsorted_runs; stats[5] = bs.host_sorted_runs;
+        }
+        return 0;
+    });
+}
 int fh_tensor_edge_count(fh_graph* g, uint64_t type_id, uint64_t* out) {
     return guard([&] { *out = g->g.relationship_tensors().at(type_id).edge_count(); return 0; });
 }

@@ -66,6 +66,28 @@ void Graph::create_edges(u64 type, const std::vector<u64>& srcs, const std::vect
     adj_.set_all(pairs, false);
 }
 
+BulkStats Graph::bulk_insert_edges(u64 type, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
+                                   const std::vector<u64>& ids) {
+    if (srcs.size() != dsts.size() || srcs.size() != ids.size())
+        throw GrbError(FGPU_INVALID, "bulk_insert_edges: slices differ in length");
+    return bulk_insert_edges(type, srcs.data(), dsts.data(), ids.data(), srcs.size());
+}
+
+BulkStats Graph::bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n) {
+    std::optional<Matrix> built;
+    BulkStats bs = tensors_.at(type).bulk_insert(srcs, dsts, ids, n, &built);
+    const u64 t0 = bulk_clock_ns();
+    if (built) {
+        adj_.union_base(*built);
+    } else if (bs.fallback_edges) {
+        std::vector<std::pair<u64, u64>> pairs(n);
+        for (size_t k = 0; k < n; ++k) pairs[k] = {srcs[k], dsts[k]};
+        adj_.set_all(pairs, false);
+    }
+    bs.phase_ns[3] = bulk_clock_ns() - t0;
+    return bs;
+}
+
 void Graph::new_version() {
     adj_ = adj_.dup();
     labels_ = labels_.dup();

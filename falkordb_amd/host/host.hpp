@@ -236,6 +236,11 @@ class VersionedMatrix {
     void remove(u64 i, u64 j);                                             // :780-791
     void remove_mask(const Matrix& mask);                                  // :799-816
     void set_all(const std::vector<std::pair<u64, u64>>& entries, bool is_new);   // :1006-1035
+    // bulk load (no reference counterpart: flush_for_bulk, graph.rs:2129-2140, ends folded and so does this): fold_all folds
+    // whatever dp / dm hold into m now; union_base does that and then m = pattern(m) U pattern(arg), one device merge.  The
+    // base is REPLACED, never mutated: dup()ed versions and extracted matrices keep the snapshot they share
+    void fold_all();
+    void union_base(const Matrix& pattern);
     VersionedMatrix dup() const;                                           // :1038-1051
     void fold_oversized();                                                 // :953-965
     void fold_latched();                                                   // :940-951
@@ -253,8 +258,18 @@ class VersionedMatrix {
 };
 
 constexpr u64 MULTI_EDGE = ~0ull;                        // tensor.rs:207
+// What a bulk insert did (Tensor::bulk_insert / Graph::bulk_insert_edges): the batch went through the device build
+// (device_edges = n) or, because one of its pairs already held an edge, through set_all_from_slices (fallback_edges = n);
+// the other four are fgpu_edges_build's stats [0], [1], [4], [6] of the batch.
+struct BulkStats {
+    u64 device_edges = 0, fallback_edges = 0, distinct_pairs = 0, multi_pairs = 0, unsorted_runs = 0, host_sorted_runs = 0;
+    // host clock, ns (a measurement hook, tools/bench_paths.py load): [0] the fgpu_edges_build call, [1] folding the layers
+    // and adopting / merging the built pieces (or the whole fallback), [2] filling me, [3] the adjacency union
+    u64 phase_ns[4] = {0, 0, 0, 0};
+};
 constexpr u64 GrB_INDEX_MAX = (1ull << 60) - 1;          // tensor.rs:136
 u64 compound_key(u64 src, u64 dst);                      // tensor.rs:154-163 (throws when an id needs > 32 bits)
+u64 bulk_clock_ns();                                     // the host clock of BulkStats::phase_ns
 
 // Tensor (tensor.rs:184-205): per-relationship-type edge storage with inline edge ids.  Forward layers
 // (m, dp UINT64; dm BOOL) and the BOOL transpose `mt` live on the device.  `me` — all ids of the pairs
@@ -274,6 +289,16 @@ class Tensor {
                    std::vector<std::vector<u64>>& ids) const;
     void set_all_from_slices(const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                              const std::vector<u64>& ids);                 // :333-455
+    // One relationship type's bulk batch (the shape of Graph::create_relationships_bulk + flush_for_bulk, graph.rs:2062-2140):
+    // fgpu_edges_build sorts and groups the batch, the layers are folded, and the built forward matrix / transposed pattern /
+    // multi-edge runs become the tensor's base — adopted when the tensor is empty, merged in when the batch touches no pair
+    // that holds an edge.  A batch that does goes through set_all_from_slices whole.  Ends folded (dp = dm = 0) on the device
+    // path.  `built` (nullable) receives the batch's forward matrix on the device path, for the adjacency union.  An invalid
+    // batch (fgpu_edges_build's rules) throws before anything changed.
+    BulkStats bulk_insert(const std::vector<u64>& srcs, const std::vector<u64>& dsts, const std::vector<u64>& ids,
+                          std::optional<Matrix>* built = nullptr);
+    // (the same over the caller's arrays: a load of 2^26 tuples is 1.6 GB that need not be copied into vectors first)
+    BulkStats bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built = nullptr);
     std::vector<std::pair<u64, u64>> remove_all(const std::vector<std::array<u64, 3>>& rels);  // :461-657
     bool has_multi_edge() const { return !me_.empty(); }
     void resize(u64 nrows, u64 ncols);                                     // :659-726
@@ -377,6 +402,11 @@ class Graph {
     void delete_edge(u64 type, u64 src, u64 dst, u64 edge_id);             // graph.rs:1623-1700 (effect only)
     void create_edges(u64 type, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                       const std::vector<u64>& ids);                        // bulk form of create_edge
+    // the bulk LOAD of one type: Tensor::bulk_insert, then the adjacency's base U= the batch's pattern (on the fallback the
+    // adjacency set_all of create_edges).  Matrices built or versions dup()ed earlier are untouched.
+    BulkStats bulk_insert_edges(u64 type, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
+                                const std::vector<u64>& ids);
+    BulkStats bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n);
     void new_version();              // graph.rs:851-890: every matrix dup()s (fold decisions latch here)
     void fold_oversized_deltas();    // graph.rs:2155-2172, called at MVCC commit (mvcc_graph.rs:161-180)
 

@@ -1,6 +1,7 @@
 // tensor.cpp — Tensor: per-relationship-type edge storage with inline edge ids
 // (mirrors graph/src/graph/graphblas/tensor.rs; per-pair state diagram at tensor.rs:72-108).
 #include <algorithm>
+#include <chrono>
 
 #include <unordered_map>
 
@@ -162,6 +163,89 @@ void Tensor::set_all_from_slices(const std::vector<u64>& srcs, const std::vector
         }
         dp_.insert(s, d, id);
     }
+}
+
+namespace {
+struct EngineArray {   // a result array of the engine, given back on every exit
+    fgpu_ctx* ctx;
+    u64* p = nullptr;
+    explicit EngineArray(fgpu_ctx* c) : ctx(c) {}
+    ~EngineArray() { if (p) fgpu_free(ctx, p); }
+    EngineArray(const EngineArray&) = delete;
+    EngineArray& operator=(const EngineArray&) = delete;
+};
+}  // namespace
+
+u64 bulk_clock_ns() {
+    return (u64)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+BulkStats Tensor::bulk_insert(const std::vector<u64>& srcs, const std::vector<u64>& dsts, const std::vector<u64>& ids,
+                              std::optional<Matrix>* built) {
+    if (srcs.size() != dsts.size() || srcs.size() != ids.size())
+        throw GrbError(FGPU_INVALID, "bulk_insert: slices differ in length");
+    return bulk_insert(srcs.data(), dsts.data(), ids.data(), srcs.size(), built);
+}
+
+BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built) {
+    BulkStats bs;
+    if (built) built->reset();
+    if (n == 0) return bs;
+    Context& ctx = m_.ctx();
+    fgpu_ctx* c = ctx.raw();
+    // the build reads nothing of the tensor: an invalid batch throws here, before any layer moved
+    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
+    EngineArray key(c), off(c), run_ids(c);
+    u64 n_multi = 0, st[8] = {0};
+    u64 t0 = bulk_clock_ns();
+    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &key.p,
+                           &off.p, &run_ids.p, &n_multi, st),
+          "Tensor::bulk_insert");
+    Matrix fwd = Matrix::adopt(ctx, Type::UInt64, fwd_h);
+    Matrix bwd = Matrix::adopt(ctx, Type::Bool, bwd_h);
+    bs.phase_ns[0] = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    // a bulk insert ends folded (flush_for_bulk): whatever dp / dm hold goes into m first
+    flush();
+    dp_.wait();
+    dm_.wait();
+    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
+        dp_.latch(true);
+        dm_.latch(true);
+        needs_flush_ = true;
+        flush();
+    }
+    mt_.fold_all();
+    const bool empty = m_.nvals() == 0;
+    if (!empty && m_.intersection_nvals(fwd) != 0) {
+        // a pair of the batch holds an edge already: its promotion is the edge-by-edge path's
+        set_all_from_slices(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), std::vector<u64>(ids, ids + n));
+        bs.fallback_edges = n;
+        bs.phase_ns[1] = bulk_clock_ns() - t0;
+        return bs;
+    }
+    if (empty) {
+        m_ = fwd;
+        mt_ = VersionedMatrix::from_matrix(bwd);
+    } else {
+        fgpu_mat* merged = nullptr;
+        check(fgpu_mat_merge(c, &merged, m_.snapshot(), fwd.snapshot(), nullptr, 0), "Tensor::bulk_insert");
+        Matrix new_m = Matrix::adopt(ctx, Type::UInt64, merged);
+        mt_.union_base(bwd);
+        m_ = new_m;
+    }
+    bs.phase_ns[1] = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    for (u64 r = 0; r < n_multi; ++r)   // (ascending keys: the hint is the place when the map held nothing above them)
+        me_.emplace_hint(me_.end(), key.p[r], std::vector<u64>(run_ids.p + off.p[r], run_ids.p + off.p[r + 1]));
+    bs.phase_ns[2] = bulk_clock_ns() - t0;
+    bs.device_edges = n;
+    bs.distinct_pairs = st[0];
+    bs.multi_pairs = st[1];
+    bs.unsorted_runs = st[4];
+    bs.host_sorted_runs = st[6];
+    if (built) *built = fwd;
+    return bs;
 }
 
 std::vector<std::pair<u64, u64>> Tensor::remove_all(const std::vector<std::array<u64, 3>>& rels) {

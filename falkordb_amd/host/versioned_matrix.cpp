@@ -245,6 +245,25 @@ void VersionedMatrix::set_all(const std::vector<std::pair<u64, u64>>& entries, b
     }
 }
 
+void VersionedMatrix::fold_all() {
+    flush();
+    wait_all();
+    if (dp_.nvals() == 0 && dm_.nvals() == 0) return;
+    dp_.latch(true);
+    dm_.latch(true);
+    needs_flush_ = true;
+    flush();
+}
+
+void VersionedMatrix::union_base(const Matrix& pattern) {
+    if (pattern.nrows() != m_.nrows() || pattern.ncols() != m_.ncols())
+        throw GrbError(FGPU_DIM_MISMATCH, "VersionedMatrix::union_base: dimensions differ");
+    fold_all();
+    fgpu_mat* o = nullptr;
+    check(fgpu_mat_merge_pattern(m_.ctx().raw(), &o, m_.snapshot(), pattern.snapshot(), nullptr, 0), "VersionedMatrix::union_base");
+    m_ = Matrix::adopt(m_.ctx(), Type::Bool, o);
+}
+
 VersionedMatrix VersionedMatrix::dup() const {
     u64 base = m_.nvals();
     bool fold_dp = dp_.fold_decision(should_fold, base);

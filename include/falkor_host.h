@@ -94,6 +94,18 @@ int fh_graph_delete_node(fh_graph* g, uint64_t node);
 int fh_graph_create_edge(fh_graph* g, uint64_t type_id, uint64_t src, uint64_t dst, uint64_t edge_id);
 int fh_graph_create_edges(fh_graph* g, uint64_t type_id, const uint64_t* srcs, const uint64_t* dsts,
                           const uint64_t* ids, uint64_t n);   /* Tensor::set_all_from_slices + adjacency set_all */
+/* The bulk load of one relationship type (the shape of Graph::create_relationships_bulk + flush_for_bulk, graph.rs:2062-2140):
+ * one fgpu_edges_build, the result adopted as (or merged into) the tensor's base, the adjacency's base U= its pattern; ends
+ * folded.  A batch with a pair that already holds an edge goes through the create_edges path whole.  stats (nullable):
+ * [0] edges through the device build, [1] edges through the fallback, [2] distinct pairs, [3] multi-edge pairs, [4] runs that
+ * arrived out of id order, [5] of those, sorted by the host.  An invalid batch (a node id at or past the capacity, an id equal
+ * to MULTI_EDGE, the same (src, dst, id) twice) returns the engine's code and leaves the graph as it was. */
+int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* srcs, const uint64_t* dsts,
+                               const uint64_t* ids, uint64_t n, uint64_t stats[6]);
+/* host-clock phases (ns) of this thread's last fh_graph_bulk_insert_edges (a measurement hook, tools/bench_paths.py load):
+ * [0] the fgpu_edges_build call, [1] folding the layers and adopting / merging the built pieces (or the whole fallback),
+ * [2] filling the multi-edge map, [3] the adjacency union */
+int fh_last_bulk_phases_ns(uint64_t out[4]);
 int fh_graph_delete_edge(fh_graph* g, uint64_t type_id, uint64_t src, uint64_t dst, uint64_t edge_id);
 /* MVCC commit of every matrix: dup() (fold decision) then fold_oversized, as mvcc_graph.rs:161-180 does */
 int fh_graph_commit(fh_graph* g);

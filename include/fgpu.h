@@ -195,6 +195,32 @@ fgpu_info fgpu_mat_from_coo(fgpu_ctx* ctx, fgpu_mat** out, uint64_t nrows, uint6
                             const uint64_t* rows, const uint64_t* cols, const uint64_t* vals,
                             uint64_t n);
 
+/* The inline value of a pair that holds several edges (MULTI_EDGE, tensor.rs:207). */
+#define FGPU_MULTI_EDGE (~0ull)
+
+/* One relationship type's bulk batch -> the three things a Tensor holds for it (tensor.rs:184-205, 333-455 run on an empty
+ * tensor and folded; the batch shape of Graph::create_relationships_bulk + flush_for_bulk, graph.rs:2062-2140):
+ *   fwd   UINT64 nrows x ncols, one entry per DISTINCT (src, dst): the edge id when the batch holds one edge of the pair,
+ *         FGPU_MULTI_EDGE when it holds several;
+ *   bwd   BOOL ncols x nrows, the transposed pattern;
+ *   the multi-edge rows: multi_key[n_multi] ascending compound keys (src << 32 | dst), multi_off[n_multi + 1], and
+ *         multi_ids[multi_off[n_multi]] with every run's ids ASCENDING whatever the input order.
+ * Host arrays in; the arrays out are engine-owned (fgpu_free; multi_key and multi_ids are NULL when n_multi == 0, multi_off
+ * always has its n_multi + 1 entries), the matrices the caller's until fgpu_mat_free.  n == 0 gives two empty matrices and
+ * n_multi == 0.  Unlike fgpu_mat_from_coo with values ("the last duplicate wins") no id of a repeated pair is lost.
+ * FGPU_INVALID, with fgpu_last_error set and nothing allocated, for: a coordinate at or past its dimension; a dimension past
+ * the 32-bit id space (2^32 - 1 or more); n >= 2^32 - 1; an id equal to FGPU_MULTI_EDGE; the same (src, dst, id) triple
+ * twice (edge ids are unique in the reference; the edge-by-edge path would leave a MULTI_EDGE pair with a one-id list).  The
+ * context stays usable after an error.
+ * stats (nullable): [0] distinct pairs, [1] multi-edge pairs, [2] ids in multi-edge runs, [3] longest run, [4] runs that
+ * arrived out of ascending order — 0 for freshly allocated ascending ids — [5] of those, sorted on the device (up to 64 ids
+ * in a wavefront, up to 4096 in a workgroup), [6] of those, longer than 4096 ids and sorted by the host after the read-back,
+ * [7] sort path taken: 0 one workgroup (n < 4096), 1 the stable counting sort, 2 the same sort in 16-bit digits (a dimension
+ * past 2^31). */
+fgpu_info fgpu_edges_build(fgpu_ctx* ctx, uint64_t nrows, uint64_t ncols, const uint64_t* srcs, const uint64_t* dsts,
+                           const uint64_t* ids, uint64_t n, fgpu_mat** fwd, fgpu_mat** bwd, uint64_t** multi_key,
+                           uint64_t** multi_off, uint64_t** multi_ids, uint64_t* n_multi, uint64_t stats[8]);
+
 /* Host CSR (what GxB_unload_Matrix_into_Container yields: p, i, x [, h];
  * matrix.rs:508-546) -> device snapshot.  rowptr has nvec+1 entries when
  * `hyper_rows` (sorted non-empty row ids, nvec of them) is given, else

@@ -60,7 +60,15 @@
           graph (RMAT-18, one type), one algo_sp_paths_rows call (maxLen 4, pathCount 0) with prune on and off: ms and the
           successors examined, the unpruned walk under a budget of 300 000 successors
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  load    the host layer's graph load: Graph::create_edges (edge by edge through the pending logs) against
+          Graph::bulk_insert_edges (one fgpu_edges_build, the result adopted as the tensor's base) on twin graphs of the distinct
+          RMAT-18 and RMAT-20 edges, both in this process, alternating, a host clock around load + commit (both end in a sync),
+          one warm-up, median of 3; then bulk_insert_edges alone on the RAW 16 x 2^22 tuples of RMAT-22, repeated pairs
+          included, so multi-edge pairs occur — with the host phases (fh_last_bulk_phases_ns), the device phases of one
+          fgpu_edges_build of the same tuples on the engine context (fgpu_prof_*), and on that graph the host leg's figures for
+          one 1024-row 2-hop batch (operator22).  `load <scale>`: the twin comparison at that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -225,6 +233,119 @@ def bench_pagerank(ctx, scale):
                       "note": "whole fgpu_pagerank call incl. one host sync per four iterations and the D2H of the scores"}), flush=True)
 
 
+def load_edges(g, t, srcs, dsts, ids):
+    """The host-layer load of a leg's graph: the bulk call from 2^18 edges on, edge by edge below."""
+    if len(srcs) >= 1 << 18:
+        g.bulk_insert_edges(t, srcs, dsts, ids)
+    else:
+        g.create_edges(t, srcs, dsts, ids)
+
+
+def operator_figures(g, ctx, A, src):
+    """One 1024-row 2-hop batch: CondTraverseOp::expand_batch (its own clock) against the bare fgpu_expand call."""
+    from falkordb_amd import host
+    spec = host.cond_spec(hops=[(["KNOWS"], []), (["KNOWS"], [])])
+    srcl = src.tolist()
+    for _ in range(2):
+        (rows, _, _), nulls, flops = g.cond_traverse_batch(spec, srcl, as_arrays=True)
+    t0 = time.perf_counter()
+    (rows, _, _), nulls, flops = g.cond_traverse_batch(spec, srcl, as_arrays=True)
+    t_host = time.perf_counter() - t0
+    t_cpp = g.L.fh_last_op_ns() / 1e9
+    for _ in range(2):
+        rowptr, dest, fl = engine.expand(ctx, src, [A, A])
+    t0 = time.perf_counter()
+    rowptr, dest, fl = engine.expand(ctx, src, [A, A])
+    t_raw = time.perf_counter() - t0
+    assert len(rows) == len(dest) and fl == flops
+    return {"hops": 2, "batch_rows": len(src), "rows_out": len(rows), "flops": flops, "ms_cpp_expand_batch": round(t_cpp * 1e3, 3),
+            "ms_through_ctypes": round(t_host * 1e3, 3), "ms_bare_fgpu_expand": round(t_raw * 1e3, 3)}
+
+
+def bench_load(scales=(18, 20), raw_scale=22):
+    from falkordb_amd import host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+    note = ("host clock around load + commit, both ending in a sync; twin graphs in one process, alternating, one warm-up, "
+            "median of 3")
+    for scale in scales:
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        ids = np.arange(len(ci), dtype=np.uint64)
+        del rp
+        A.free()
+
+        def run(bulk):
+            g = host.Graph(hc, n)
+            t = g.add_type("KNOWS")
+            t0 = time.perf_counter()
+            st = g.bulk_insert_edges(t, r, ci, ids) if bulk else g.create_edges(t, r, ci, ids)
+            t1 = time.perf_counter()
+            g.commit()
+            t2 = time.perf_counter()
+            return t1 - t0, t2 - t1, (g.tensor_edge_count(t), g.tensor_state(t)["m"], len(g.layer(None, "dp"))), st
+
+        times = {False: [], True: []}
+        for rep in range(4):                     # (rep 0 warms both up)
+            for bulk in (False, True):
+                call, commit, state, st = run(bulk)
+                assert state[0] == len(ci) and (not bulk or state == (len(ci), len(ci), 0)), state
+                print(f"# load scale {scale} rep {rep} {'bulk' if bulk else 'create_edges'}: {call + commit:.3f} s", file=sys.stderr, flush=True)
+                if rep:
+                    times[bulk].append((call + commit, call, commit))
+        med = {b: [float(np.median([x[k] for x in times[b]])) for k in range(3)] for b in times}
+        print(json.dumps({"path": "graph_load", "scale": scale, "edges": len(ci),
+                          "create_edges": {"s": round(med[False][0], 3), "call_s": round(med[False][1], 3), "commit_s": round(med[False][2], 3),
+                                           "us_per_edge": round(med[False][0] / len(ci) * 1e6, 4)},
+                          "bulk_insert_edges": {"s": round(med[True][0], 4), "call_s": round(med[True][1], 4), "commit_s": round(med[True][2], 4),
+                                                "us_per_edge": round(med[True][0] / len(ci) * 1e6, 5), "stats": st},
+                          "speedup": round(med[False][0] / med[True][0], 1), "note": note}), flush=True)
+        del r, ci, ids
+    if not raw_scale:
+        return
+    import oracle
+    u, v = oracle.rmat_edges(raw_scale)          # the generator's stream before the duplicates collapse
+    n = 1 << raw_scale
+    ids = np.arange(len(u), dtype=np.uint64)
+    runs = []
+    for rep in range(4):
+        g = host.Graph(hc, n)
+        t = g.add_type("KNOWS")
+        t0 = time.perf_counter()
+        st = g.bulk_insert_edges(t, u, v, ids)
+        dt = time.perf_counter() - t0
+        runs.append((dt, g.last_bulk_phases_ms()))
+        if rep == 0 and dt > 60:                 # (a load this slow is reported from its one run)
+            break
+    timed_runs = runs[1:] or runs
+    k = int(np.argsort([x[0] for x in timed_runs])[len(timed_runs) // 2])
+    dt, phases = timed_runs[k]
+    assert g.tensor_edge_count(t) == len(u)
+    ctx.prof_enable(True)
+    pieces = engine.edges_build(ctx, n, n, u, v, ids, stats=True)
+    ctx.sync()
+    dev = {p["kernel"]: round(p["ms"], 3) for p in ctx.prof_read() if p["kernel"].startswith("eb_")}
+    ctx.prof_enable(False)
+    est = pieces[-1]
+    del pieces
+    print(json.dumps({"path": "graph_load_raw", "scale": raw_scale, "tuples": len(u), "distinct_pairs": st["distinct_pairs"],
+                      "multi_pairs": st["multi_pairs"], "ids_in_multi_runs": est[2], "longest_run": est[3],
+                      "unsorted_runs": st["unsorted_runs"], "bulk_insert_edges_s": round(dt, 3),
+                      "us_per_edge": round(dt / len(u) * 1e6, 5), "runs_s": [round(x[0], 3) for x in runs],
+                      "host_phases_ms": {k_: round(v_, 2) for k_, v_ in phases.items()},
+                      "device_phases_ms": dev,
+                      "note": "one warm-up, median of 3 (host clock, the call ends in a sync); host_phases = the C++ layer's own "
+                              "clock: the fgpu_edges_build call (marshalling, H2D, sort, runs, transpose, read-back), fold + adopt, "
+                              "me fill, adjacency union; device_phases = HIP events around the stages of one fgpu_edges_build of "
+                              "the same tuples on the engine context (eb_h2d includes the staged host copies)"}), flush=True)
+    A = ctx.mat_from_coo(n, n, u, v)
+    src = np.random.default_rng(3).choice(n, 1024, replace=False).astype(np.uint64)
+    print(json.dumps(dict({"path": "operator22", "scale": raw_scale}, **operator_figures(g, ctx, A, src))), flush=True)
+
+
 def bench_host(scale):
     """expand_batch through libfalkor_host.so (label probes, layer waits, result hand-off) vs bare fgpu_expand."""
     from falkordb_amd import host
@@ -238,7 +359,7 @@ def bench_host(scale):
     t = g.add_type("KNOWS")
     lp = g.add_label("P")
     t0 = time.perf_counter()
-    g.create_edges(t, r, ci, np.arange(len(ci), dtype=np.uint64))
+    load_edges(g, t, r, ci, np.arange(len(ci), dtype=np.uint64))
     g.commit()
     build = time.perf_counter() - t0
     rng = np.random.default_rng(3)
@@ -570,7 +691,7 @@ def bench_hops(ctx, scale, host_scale=18):
     br = np.repeat(np.arange(bn, dtype=np.uint64), bdeg)
     g = host.Graph(hc, bn)
     ty = g.add_type("KNOWS")
-    g.create_edges(ty, br, bci, np.arange(len(bci), dtype=np.uint64))
+    load_edges(g, ty, br, bci, np.arange(len(bci), dtype=np.uint64))
     g.commit()
     Bt = B.transpose()
     source = int(np.nonzero(bdeg == 8)[0][0])
@@ -706,7 +827,7 @@ def bench_asp_batch(ctx, scale, npairs=64, nbig=1024, host_scale=18):
     bdeg = np.diff(brp.astype(np.int64))
     g = host.Graph(hc, bn)
     ty = g.add_type("KNOWS")
-    g.create_edges(ty, np.repeat(np.arange(bn, dtype=np.uint64), bdeg), bci, np.arange(len(bci), dtype=np.uint64))
+    load_edges(g, ty, np.repeat(np.arange(bn, dtype=np.uint64), bdeg), bci, np.arange(len(bci), dtype=np.uint64))
     g.commit()
     B.free()
     live = np.nonzero(bdeg > 0)[0]
@@ -836,3 +957,5 @@ if __name__ == "__main__":
         c.close()
     if what in ("host", "all"):
         bench_host(scale or 18)
+    if what == "load":                           # (minutes of edge-by-edge loading: not part of `all`)
+        bench_load(*(((scale,), 0) if scale else ()))

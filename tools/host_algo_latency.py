@@ -13,7 +13,11 @@ rp, ci, _ = A.export_csr()
 r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
 g = host.Graph(hc, n)
 t = g.add_type("KNOWS")
-g.create_edges(t, r, ci, np.arange(len(ci), dtype=np.uint64))
+ids = np.arange(len(ci), dtype=np.uint64)
+if len(ci) >= 1 << 18:
+    g.bulk_insert_edges(t, r, ci, ids)
+else:
+    g.create_edges(t, r, ci, ids)
 g.commit()
 src = int(np.argmax(np.diff(rp)))
 for name, fn in (("algo.BFS", lambda: g.algo_bfs(src)), ("algo.pageRank", lambda: g.algo_pagerank(None, None))):
