@@ -257,6 +257,19 @@ class Mat:
     def nvals(self):
         return self._get(self.ctx.lib.fgpu_mat_nvals)
 
+    @property
+    def has_values(self) -> bool:
+        """True for a UINT64 snapshot (also an empty one), False for BOOL."""
+        v = C.c_int32()
+        check(self.ctx.lib.fgpu_mat_has_values(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def min_val(self):
+        """fgpu_mat_min_val: the smallest stored value read as binary64 (-0.0 counts as +0.0), None without entries."""
+        bits, found = C.c_uint64(), C.c_int()
+        check(self.ctx.lib.fgpu_mat_min_val(self.ctx._h, self._h, C.byref(bits), C.byref(found)))
+        return float(np.array([bits.value], dtype=U64).view(np.float64)[0]) if found.value else None
+
     def export_csr(self):
         lib = self.ctx.lib
         rp, ci, vv = u64p(), u64p(), u64p()
