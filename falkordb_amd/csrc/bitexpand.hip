@@ -342,7 +342,9 @@ __global__ __launch_bounds__(256) void bp_flag_count_kernel(const uint8_t* __res
 // tab[k][j][x] = sum of row_hash(64 k + 4 j + b) over the set bits b of the nibble x: 16 look-ups per word replace a
 // loop over its set bits (divergent: a wavefront ran as long as its fullest word) with two 64-bit multiplies each.
 // (rowmap, nullable: bit i of a row stands for source row rowmap[i], i < nsrc — a chain over compacted source rows)
-__global__ void bp_cs_table_kernel(u32 w, u64* __restrict__ tab, const u32* __restrict__ rowmap, u32 nsrc) {
+// (rowhash, nullable: bit i's hash itself, i < nsrc — bits that stand for classes of call rows; it then replaces rowmap here)
+__global__ void bp_cs_table_kernel(u32 w, u64* __restrict__ tab, const u32* __restrict__ rowmap, const u64* __restrict__ rowhash,
+                                   u32 nsrc) {
     const u32 t = blockIdx.x * 256 + threadIdx.x;     // (k, j, x)
     if (t >= w * 256) return;
     const u32 k = t >> 8, j = (t >> 4) & 15, x = t & 15;
@@ -350,7 +352,9 @@ __global__ void bp_cs_table_kernel(u32 w, u64* __restrict__ tab, const u32* __re
     for (u32 b = 0; b < 4; ++b)
         if ((x >> b) & 1u) {
             const u32 bit = k * 64 + 4 * j + b;
-            s += cs_row_hash(rowmap ? (bit < nsrc ? (u64)rowmap[bit] : 0ull) : (u64)bit);   // (bits >= nsrc are never set)
+            // (bits >= nsrc are never set)
+            if (rowhash) s += bit < nsrc ? rowhash[bit] : 0ull;
+            else s += cs_row_hash(rowmap ? (bit < nsrc ? (u64)rowmap[bit] : 0ull) : (u64)bit);
         }
     tab[t] = s;
 }
@@ -1595,7 +1599,7 @@ static fgpu_info bp_cs_tables(fgpu_ctx* ctx, const BitState& s, DevBuf<u64>& tab
                  "expand checksum: %u source rows need %zu B of LDS tables (limit %d); batch the sources", s.nsrc, lds,
                  ctx->opt.lds_limit);
     FGPU_TRY(tab.alloc(ctx, (size_t)s.w * 256));
-    return launch(bp_cs_table_kernel, dim3(s.w), dim3(256), 0, ctx->stream(), s.w, tab.p, s.rowmap.p, s.nsrc);
+    return launch(bp_cs_table_kernel, dim3(s.w), dim3(256), 0, ctx->stream(), s.w, tab.p, s.rowmap.p, s.rowhash.p, s.nsrc);
 }
 
 // count `nrows` rows of y into acc — with `tab` their checksum too; at most `per_cu` workgroups a CU, a quarter of that with the

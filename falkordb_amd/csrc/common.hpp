@@ -579,7 +579,10 @@ struct BitState {
     // (bitpart.hip BpXPlan::perm, owned by the next hop's matrix); only the state that FEEDS a count hop is ever permuted
     const u32* perm = nullptr;
     DevBuf<u32> rowmap;
-    DevBuf<u32> rowrank;   // nsrc_full + 1 entries: live rows before source row i (the way back for chains that emit rows)
+    // nullable, one per bit: the checksum's row hash of bit i, for bits that stand for a CLASS of call rows (spgemm.hip
+    // expand_count_scan: the sum of the members' cs_row_hash, or 0); absent, bit i hashes as cs_row_hash(rowmap[i])
+    DevBuf<u64> rowhash;
+    DevBuf<u32> rowrank;  // nsrc_full + 1 entries: live rows before source row i (the way back for chains that emit rows)
     u32 nsrc_full = 0;     // source rows before the compaction (0: not compacted)
 };
 fgpu_info bp_from_csr(fgpu_ctx* ctx, BitState& s, const fgpu_mat* f);

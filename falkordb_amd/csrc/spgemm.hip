@@ -107,16 +107,17 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(const u32* __restrict
     }
 }
 
-// (rowmap, nullable: row r of c stands for row rowmap[r] of the call — a pass of a whole-frontier call)
+// (rowmap, nullable: row r of c stands for row rowmap[r] of the call — a pass of a whole-frontier call; rowhash, nullable:
+// row r's hash itself — a pass whose rows stand for classes of call rows, expand_count_scan below)
 __global__ __launch_bounds__(256) void checksum_kernel(CsrView c, u32 nrows, unsigned long long* __restrict__ acc,
-                                                       const u32* __restrict__ rowmap) {
+                                                       const u32* __restrict__ rowmap, const u64* __restrict__ rowhash) {
     const u32 lane = lane_id();
     const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const u32 nwaves = (gridDim.x * 256) >> 6;
     u64 sum = 0;
     for (u32 r = wave; r < nrows; r += nwaves) {
         const u32 rb = c.rowptr[r], re = c.rowptr[r + 1];
-        const u64 hr = cs_row_hash(rowmap ? rowmap[r] : r);
+        const u64 hr = rowhash ? rowhash[r] : cs_row_hash(rowmap ? rowmap[r] : r);
         for (u32 i = rb + lane; i < re; i += 64) sum += hr * cs_dest_hash(c.colidx[i]);
     }
 #pragma unroll
@@ -143,7 +144,8 @@ static fgpu_info mxm_flops(fgpu_ctx* ctx, const fgpu_mat* F, const fgpu_mat* B, 
 // entry-parallel form for results with few, very long rows (dense k-hop results: ~10^6 entries per row):
 // each lane takes one entry and finds its row in the short row-pointer array
 __global__ __launch_bounds__(256) void checksum_entries_kernel(CsrView c, u32 nrows, u32 nnz,
-                                                              unsigned long long* __restrict__ acc, const u32* __restrict__ rowmap) {
+                                                              unsigned long long* __restrict__ acc, const u32* __restrict__ rowmap,
+                                                              const u64* __restrict__ rowhash) {
     u64 sum = 0;
     for (u32 q = blockIdx.x * 256 + threadIdx.x; q < nnz; q += gridDim.x * 256) {
         u32 lo = 0, hi = nrows - 1;
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256) void checksum_entries_kernel(CsrView c, u32 nr
             u32 mid = (lo + hi + 1) >> 1;
             if (c.rowptr[mid] <= q) lo = mid; else hi = mid - 1;
         }
-        sum += cs_row_hash(rowmap ? rowmap[lo] : lo) * cs_dest_hash(c.colidx[q]);
+        sum += (rowhash ? rowhash[lo] : cs_row_hash(rowmap ? rowmap[lo] : lo)) * cs_dest_hash(c.colidx[q]);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
@@ -816,6 +818,7 @@ static fgpu_info compact_source_rows(fgpu_ctx* ctx, const fgpu_mat* f, fgpu_mat*
 struct ChainSources {
     MatRef f;                        // taken over by the chain
     DevBuf<u32>* rowmap = nullptr;   // moved into the bit state while the chain runs, handed back when it ends in CSR form
+    DevBuf<u64>* rowhash = nullptr;  // nullable: the hash of every row, for rows that stand for classes of call rows; moved like rowmap
 };
 
 // the caller's destination-label bitmap (one bit per column; nullptr: no filter, bm.p stays nullptr) on the device
@@ -982,6 +985,7 @@ static fgpu_info chain_end(fgpu_ctx* ctx, const ChainRequest& rq, Chain& ch, Cha
         ch.f = std::move(c);
     }
     if (rq.pre && rq.pre->rowmap) *rq.pre->rowmap = std::move(ch.bs.rowmap);
+    if (rq.pre && rq.pre->rowhash) *rq.pre->rowhash = std::move(ch.bs.rowhash);
     out.mat = std::move(ch.f);
     out.kind = ChainResult::Csr;
     return FGPU_OK;
@@ -994,6 +998,7 @@ static fgpu_info expand_device(fgpu_ctx* ctx, const ChainRequest& rq, ChainResul
     if (rq.pre) {
         ch.f = std::move(rq.pre->f);
         if (rq.pre->rowmap) ch.bs.rowmap = std::move(*rq.pre->rowmap);
+        if (rq.pre->rowhash) ch.bs.rowhash = std::move(*rq.pre->rowhash);
     } else {
         FGPU_TRY(check_hops(L, rq.nsrc));
         FGPU_TRY(upload_sources(ctx, &ch.f.m, rq.src_ids, rq.nsrc, L.m[0]->nrows));
@@ -1163,8 +1168,10 @@ __global__ __launch_bounds__(256) void probe_csr_rows_kernel(CsrView f, CsrView 
     }
 }
 
-// nnz (+ checksum) of a chain that ended in CSR form; rowmap (nullable) = the call's row of every row of r
-static fgpu_info count_csr_result(fgpu_ctx* ctx, const fgpu_mat* r, const u32* rowmap, u64* out_nnz, u64* checksum) {
+// nnz (+ checksum) of a chain that ended in CSR form; rowmap (nullable) = the call's row of every row of r, rowhash (nullable)
+// = the hash of every row of r, which then stands in for cs_row_hash(rowmap[.])
+static fgpu_info count_csr_result(fgpu_ctx* ctx, const fgpu_mat* r, const u32* rowmap, const u64* rowhash, u64* out_nnz,
+                                  u64* checksum) {
     *out_nnz = r->nnz;
     if (!checksum) return FGPU_OK;
     *checksum = 0;
@@ -1176,12 +1183,12 @@ static fgpu_info count_csr_result(fgpu_ctx* ctx, const fgpu_mat* r, const u32* r
         u32 grid = cdiv(r->nnz, 256);
         if (grid > (u32)ctx->cus * 32) grid = ctx->cus * 32;
         FGPU_TRY(launch(checksum_entries_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
-                        (u32)r->nrows, (u32)r->nnz, (unsigned long long*)acc.p, rowmap));
+                        (u32)r->nrows, (u32)r->nnz, (unsigned long long*)acc.p, rowmap, rowhash));
     } else {
         u32 grid = cdiv(r->nrows, 4);
         if (grid > (u32)ctx->cus * 16) grid = ctx->cus * 16;
         FGPU_TRY(launch(checksum_kernel, dim3(grid), dim3(256), 0, ctx->stream(), view_of(r),
-                        (u32)r->nrows, (unsigned long long*)acc.p, rowmap));
+                        (u32)r->nrows, (unsigned long long*)acc.p, rowmap, rowhash));
     }
     return read_u64(ctx, acc.p, checksum);
 }
@@ -1195,7 +1202,9 @@ static fgpu_info count_csr_result(fgpu_ctx* ctx, const fgpu_mat* r, const u32* r
 //   1. the sources are filtered on the device: a row takes part when its source has an entry in m[0] or dp[0] (every other
 //      row's result is empty whatever follows), and the live rows are compacted — (source id, row of the call) pairs;
 //   2. the live rows are cut into PASSES of `expand_scan_rows` rows (1024: 16 words = one 128-byte line per vertex) — the
-//      width is picked from the LIVE rows, not from the caller's batch size;
+//      width is picked from the LIVE rows, not from the caller's batch size; over a clean hop 0 the sources of out-degree one
+//      that share their target first become one row per class and power of two ("classes of degree-one sources" below), which
+//      takes 5 % of the passes off an R-MAT label scan;
 //   3. the passes are dealt to `expand_scan_lanes` lanes of the context (the calling thread + worker threads, each on its own
 //      stream and pool: a chain makes ~10 host-side decisions per pass — product sizes, the CSR -> bit-form switch, the
 //      counts — during which ITS stream idles), so one pass's launch-bound head and tail run under another's count hop;
@@ -1218,17 +1227,196 @@ __global__ void scan_compact_kernel(const u32* __restrict__ ids, const u32* __re
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && flag[i]) { lid[pos[i]] = ids[i]; lrow[pos[i]] = i; }
 }
-__global__ void scan_pass_kernel(const u32* __restrict__ lid, const u32* __restrict__ lrow, u32 first, u32 k, u32* __restrict__ rowptr,
-                                 u32* __restrict__ colidx, u32* __restrict__ rowmap) {
+// (lhash, nullable: the rows carry their hashes — a classed row list, below)
+__global__ void scan_pass_kernel(const u32* __restrict__ lid, const u32* __restrict__ lrow, const u64* __restrict__ lhash, u32 first,
+                                 u32 k, u32* __restrict__ rowptr, u32* __restrict__ colidx, u32* __restrict__ rowmap,
+                                 u64* __restrict__ rowhash) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i <= k) rowptr[i] = i;
-    if (i < k) { colidx[i] = lid[first + i]; rowmap[i] = lrow[first + i]; }
+    if (i < k) {
+        colidx[i] = lid[first + i];
+        rowmap[i] = lrow[first + i];
+        if (lhash) rowhash[i] = lhash[first + i];
+    }
+}
+
+// ---- classes of degree-one sources ----------------------------------------------------------------------------------------
+// nnz, flops and the checksum sum_(row, dest) cs_row_hash(row) * cs_dest_hash(dest) are 64-bit wrap-around sums that are LINEAR in
+// the rows, and two sources with the same out-neighbour set over m[0] have identical result rows: they need one bit of a pass,
+// whose hash is the sum of their row hashes and whose nnz and flops count twice.  A label scan of an R-MAT graph has such
+// sources in bulk among those of out-degree ONE (28 % of the live rows of RMAT-22, on 3/4 as many targets; equal sets of two
+// and more entries are one source in 10^5 there and are not looked for).  Over a clean hop 0 the live rows are therefore CLASSED
+// by their single target:
+//   * a class of m sources appears once in the pass group of scale 2^k for every set bit k < kmax of m, and m >> kmax times
+//     in the top group; group 0 also holds the plain rows.  A pass holds rows of one scale, its nnz and flops are multiplied
+//     by it on the host, and no kernel of the chain knows;
+//   * the class's hash sum rides on the first of its rows in the lowest group it appears in, its other rows carry 0;
+//   * kmax in [0, SCAN_KMAX] minimises the passes, sum_k ceil(rows_k / expand_scan_rows) (ties: the smaller; 0 = the live list
+//     as it is), from one read-back of the classes' bit counts.
+// The plan is deterministic: a class is named by its first member in live order, and every group lists its rows in that order.
+// In group 0 the classes' rows stay BETWEEN the plain rows, where their first members were: its passes then hold the mix of
+// light and heavy sources the chain's form decisions were measured on.  (Plain rows first and class rows after them made 22
+// passes per RMAT-22 scan of degree-one sources only; ten of those stayed in CSR form up to the count hop and took its plain
+// pull, 1.8 ms a launch, which cost 3/4 of what the saved passes gained: profiles/NOTES_scan_classes.md.)
+constexpr u32 SCAN_KMAX = 5;
+constexpr u32 SCAN_NOKEY = 0xFFFFFFFFu;
+
+// key[i] = the single out-neighbour of live row i (SCAN_NOKEY: not of degree one); rep[t] = the first live row with key t
+// (rep: ncols entries, all ones)
+__global__ void scan_class_key_kernel(const u32* __restrict__ lid, u32 nlive, CsrView m0, u32 ncols, u32* __restrict__ key,
+                                      u32* __restrict__ rep) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nlive) return;
+    u32 b, e;
+    row_range(m0, lid[i], b, e);
+    u32 t = SCAN_NOKEY;
+    if (e - b == 1 && m0.colidx[b] < ncols) {
+        t = m0.colidx[b];
+        atomicMin(&rep[t], i);
+    }
+    key[i] = t;
+}
+// members and hash sum of every class, at its first member (cnt and hsum zeroed, one entry per live row)
+__global__ void scan_class_sum_kernel(const u32* __restrict__ lrow, const u32* __restrict__ key, const u32* __restrict__ rep, u32 nlive,
+                                      u32* __restrict__ cnt, unsigned long long* __restrict__ hsum) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nlive || key[i] == SCAN_NOKEY) return;
+    const u32 r = rep[key[i]];
+    atomicAdd(&cnt[r], 1u);
+    atomicAdd(&hsum[r], (unsigned long long)cs_row_hash(lrow[i]));
+}
+// stats[k] = classes with bit k of m set, stats[SCAN_KMAX + 1 + k] = sum of m >> k, k = 0 .. SCAN_KMAX
+// (a grid-stride loop and a sum per workgroup: twelve atomics per wavefront of a launch over all live rows took 92 us on the
+// twelve words)
+__global__ __launch_bounds__(256) void scan_class_stats_kernel(const u32* __restrict__ cnt, u32 nlive, u32* __restrict__ stats) {
+    __shared__ u32 s_sum[2 * (SCAN_KMAX + 1)];
+    if (threadIdx.x < 2 * (SCAN_KMAX + 1)) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    u32 a[SCAN_KMAX + 1] = {}, s[SCAN_KMAX + 1] = {};
+    for (u32 i = blockIdx.x * 256 + threadIdx.x; i < nlive; i += gridDim.x * 256) {
+        const u32 m = cnt[i];                       // (0 everywhere but at a class's first member)
+#pragma unroll
+        for (u32 k = 0; k <= SCAN_KMAX; ++k) { a[k] += (m >> k) & 1u; s[k] += m >> k; }
+    }
+#pragma unroll
+    for (u32 k = 0; k <= SCAN_KMAX; ++k) {
+        u32 x = a[k], y = s[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { x += __shfl_xor(x, d, 64); y += __shfl_xor(y, d, 64); }
+        if (lane_id() == 0 && x) atomicAdd(&s_sum[k], x);
+        if (lane_id() == 0 && y) atomicAdd(&s_sum[SCAN_KMAX + 1 + k], y);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * (SCAN_KMAX + 1) && s_sum[threadIdx.x]) atomicAdd(&stats[threadIdx.x], s_sum[threadIdx.x]);
+}
+// rows live row i contributes to group k of the row list (kmax >= 1; m = cnt[i]: 0 but at a class's first member)
+__device__ __forceinline__ u32 scan_class_rows_of(u32 k, u32 key, u32 m, u32 kmax) {
+    if (key == SCAN_NOKEY) return k == 0;
+    return k < kmax ? (m >> k) & 1u : m >> kmax;
+}
+__global__ void scan_class_rows_kernel(const u32* __restrict__ key, const u32* __restrict__ cnt, u32 nlive, u32 kmax, u32* __restrict__ c) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) c[(u64)(kmax + 1) * nlive] = 0;
+    if (i >= nlive) return;
+    for (u32 k = 0; k <= kmax; ++k) c[(u64)k * nlive + i] = scan_class_rows_of(k, key[i], cnt[i], kmax);
+}
+// the row list: (source id, row of the call, row hash) at the scanned positions, nrows of them
+__global__ void scan_class_fill_kernel(const u32* __restrict__ lid, const u32* __restrict__ lrow, const u32* __restrict__ key,
+                                       const u32* __restrict__ cnt, const u64* __restrict__ hsum, const u32* __restrict__ pos, u32 nlive,
+                                       u32 kmax, u32 nrows, u32* __restrict__ rid, u32* __restrict__ rrow, u64* __restrict__ rhash) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 k = blockIdx.y;
+    if (i >= nlive) return;
+    const u32 m = cnt[i];
+    const u32 n = scan_class_rows_of(k, key[i], m, kmax);
+    if (!n) return;
+    u64 h;
+    if (key[i] == SCAN_NOKEY) h = cs_row_hash(lrow[i]);
+    else {
+        const u32 low = (u32)__ffs(m) - 1;                       // the lowest group of the class: its lowest set bit, or the top group
+        h = (k == (low < kmax ? low : kmax)) ? hsum[i] : 0ull;
+    }
+    const u32 p = pos[(u64)k * nlive + i];
+    for (u32 q = 0; q < n && p + q < nrows; ++q) {
+        rid[p + q] = lid[i];
+        rrow[p + q] = lrow[i];
+        rhash[p + q] = q ? 0ull : h;
+    }
+}
+
+struct ScanPass { u32 first, rows, scale; };
+
+// the passes of `groups` consecutive row groups (rows[g] rows at scale 2^g): `pass_rows` rows each, never across a group boundary
+static void scan_cut_passes(const u32* rows, u32 groups, u32 pass_rows, std::vector<ScanPass>& out) {
+    u32 first = 0;
+    for (u32 g = 0; g < groups; ++g) {
+        for (u32 o = 0; o < rows[g]; o += pass_rows) out.push_back({first + o, std::min(pass_rows, rows[g] - o), 1u << g});
+        first += rows[g];
+    }
+}
+
+// the classed row list of a whole-frontier call over a clean hop 0 (above); kmax = 0 on return: the live list stays as it is
+struct ScanClasses {
+    DevBuf<u32> rid, rrow;
+    DevBuf<u64> rhash;
+    u32 kmax = 0;
+    u32 rows[SCAN_KMAX + 1] = {};
+};
+static fgpu_info scan_build_classes(fgpu_ctx* ctx, const fgpu_mat* m0, const u32* lid, const u32* lrow, u32 nlive, u32 pass_rows,
+                                    ScanClasses& sc) {
+    ProfScope ps(ctx, "scan classes", 0);
+    DevBuf<u32> key, rep, cnt, stats;
+    DevBuf<u64> hsum;
+    const u32 grid = cdiv(nlive, 256);
+    FGPU_TRY(key.alloc(ctx, nlive));
+    FGPU_TRY(cnt.alloc(ctx, nlive));
+    FGPU_TRY(hsum.alloc(ctx, nlive));
+    FGPU_TRY(rep.alloc(ctx, m0->ncols));
+    FGPU_TRY(stats.alloc(ctx, 2 * (SCAN_KMAX + 1)));
+    FGPU_HIP(hipMemsetAsync(rep.p, 0xFF, (size_t)m0->ncols * sizeof(u32), ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(cnt.p, 0, (size_t)nlive * sizeof(u32), ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(hsum.p, 0, (size_t)nlive * sizeof(u64), ctx->stream()));
+    FGPU_HIP(hipMemsetAsync(stats.p, 0, 2 * (SCAN_KMAX + 1) * sizeof(u32), ctx->stream()));
+    FGPU_TRY(launch(scan_class_key_kernel, dim3(grid), dim3(256), 0, ctx->stream(), lid, nlive, view_of(m0), (u32)m0->ncols, key.p,
+                    rep.p));
+    FGPU_TRY(launch(scan_class_sum_kernel, dim3(grid), dim3(256), 0, ctx->stream(), lrow, (const u32*)key.p, (const u32*)rep.p, nlive,
+                    cnt.p, (unsigned long long*)hsum.p));
+    FGPU_TRY(launch(scan_class_stats_kernel, dim3(std::min(grid, 32u)), dim3(256), 0, ctx->stream(), (const u32*)cnt.p, nlive, stats.p));
+    u32 st[2 * (SCAN_KMAX + 1)];
+    FGPU_TRY(read_words(ctx, stats.p, 2 * (SCAN_KMAX + 1), st));
+    const u32* bits = st;                       // classes with bit k of m set
+    const u32* top = st + SCAN_KMAX + 1;        // sum of m >> k
+    const u32 nplain = nlive - top[0];
+    u32 best = 0;
+    for (u32 kmax = 0; kmax <= SCAN_KMAX; ++kmax) {
+        u32 passes = 0;
+        for (u32 k = 0; k <= kmax; ++k) passes += cdiv((k ? 0u : nplain) + (k < kmax ? bits[k] : top[k]), pass_rows);
+        if (kmax == 0 || passes < best) { best = passes; sc.kmax = kmax; }
+    }
+    if (sc.kmax == 0) return FGPU_OK;
+    const u32 kmax = sc.kmax;
+    u32 nrows = 0;
+    for (u32 k = 0; k <= kmax; ++k) nrows += sc.rows[k] = (k ? 0u : nplain) + (k < kmax ? bits[k] : top[k]);
+    DevBuf<u32> c, pos;
+    const u64 nc = (u64)(kmax + 1) * nlive + 1;
+    FGPU_TRY(c.alloc(ctx, nc));
+    FGPU_TRY(pos.alloc(ctx, nc));
+    FGPU_TRY(sc.rid.alloc(ctx, nrows));
+    FGPU_TRY(sc.rrow.alloc(ctx, nrows));
+    FGPU_TRY(sc.rhash.alloc(ctx, nrows));
+    FGPU_TRY(launch(scan_class_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream(), (const u32*)key.p, (const u32*)cnt.p, nlive, kmax, c.p));
+    FGPU_TRY(scan_u32(ctx, c.p, pos.p, nc, nullptr));
+    FGPU_TRY(launch(scan_class_fill_kernel, dim3(grid, kmax + 1), dim3(256), 0, ctx->stream(), lid, lrow, (const u32*)key.p,
+                    (const u32*)cnt.p, (const u64*)hsum.p, (const u32*)pos.p, nlive, kmax, nrows, sc.rid.p, sc.rrow.p, sc.rhash.p));
+    return FGPU_OK;
 }
 
 struct ScanJob {
     fgpu_ctx* ctx;
-    const u32 *lid, *lrow;
-    u32 nlive, pass_rows, npasses;
+    const u32 *lid, *lrow;               // the row list: source id and row of the call ...
+    const u64* lhash = nullptr;          // ... and, for a classed list, the row's hash
+    std::vector<ScanPass> passes;
+    u32 npasses;
     Layers L;
     const uint64_t* label;
     bool want_cs, want_flops;
@@ -1242,21 +1430,29 @@ struct ScanJob {
 
 static fgpu_info scan_one_pass(ScanJob& j, u32 p, u64* nnz, u64* cs, u64* fl) {
     fgpu_ctx* ctx = j.ctx;
-    const u32 first = p * j.pass_rows;
-    const u32 k = std::min(j.pass_rows, j.nlive - first);
+    const ScanPass& ps = j.passes[p];
+    const u32 first = ps.first, k = ps.rows;
+    const u64* lhash = j.want_cs ? j.lhash : nullptr;      // (only the checksum reads the hashes)
     DevBuf<u32> rm;
+    DevBuf<u64> rh;
     ChainSources pre;
     FGPU_TRY(rm.alloc(ctx, k));
+    if (lhash) FGPU_TRY(rh.alloc(ctx, k));
     FGPU_TRY(mat_alloc(ctx, &pre.f.m, k, j.L.m[0]->nrows, k, false, 0, false));
-    FGPU_TRY(launch(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, first, k,
-                    pre.f->rowptr, pre.f->colidx, rm.p));
+    FGPU_TRY(launch(scan_pass_kernel, dim3(cdiv((u64)k + 1, 256)), dim3(256), 0, ctx->stream(), j.lid, j.lrow, lhash, first, k,
+                    pre.f->rowptr, pre.f->colidx, rm.p, rh.p));
     pre.rowmap = &rm;
+    if (lhash) pre.rowhash = &rh;
     *fl = 0;
     const ChainRequest rq{nullptr, k, j.L, j.label, j.want_flops ? fl : nullptr, j.want_cs ? ChainEnd::CountSum : ChainEnd::Count, &pre};
     ChainResult r;
     FGPU_TRY(expand_device(ctx, rq, r));
-    if (r.kind == ChainResult::Counts) { *nnz = r.nnz; *cs = r.checksum; return FGPU_OK; }
-    return count_csr_result(ctx, r.mat.get(), rm.p, nnz, j.want_cs ? cs : nullptr);
+    if (r.kind == ChainResult::Counts) { *nnz = r.nnz; *cs = r.checksum; }
+    else FGPU_TRY(count_csr_result(ctx, r.mat.get(), rm.p, rh.p, nnz, j.want_cs ? cs : nullptr));
+    // every row of the pass stands for `scale` rows of the call with the same result row (the checksum's hashes say so already)
+    *nnz *= ps.scale;
+    *fl *= ps.scale;
+    return FGPU_OK;
 }
 
 static void scan_worker(ScanJob* j) {
@@ -1317,11 +1513,23 @@ static fgpu_info expand_count_scan(fgpu_ctx* ctx, const uint64_t* src_ids, uint6
     FGPU_TRY(lrow.alloc(ctx, nlive));
     FGPU_TRY(launch(scan_compact_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream(), (const u32*)dids.p, (const u32*)flag.p,
                     (const u32*)pos.p, n, lid.p, lrow.p));
-    FGPU_HIP(hipStreamSynchronize(ctx->stream()));           // the other lanes read the live list
+    const u32 pass_rows = (u32)ctx->opt.expand_scan_rows;
+    // over a clean hop 0 the degree-one sources are classed by their target (scan_build_classes); over a dirty one a row of m[0]
+    // is not the source's out-neighbour set, and every row stays a row of scale 1
+    const fgpu_mat* dm0 = L.dm_at(0) && L.dm_at(0)->nnz ? L.dm_at(0) : nullptr;
+    ScanClasses sc;
+    if (!dp0 && !dm0) FGPU_TRY(scan_build_classes(ctx, m[0], lid.p, lrow.p, nlive, pass_rows, sc));
+    FGPU_HIP(hipStreamSynchronize(ctx->stream()));           // the other lanes read the row list
     ScanJob j;
-    j.ctx = ctx; j.lid = lid.p; j.lrow = lrow.p; j.nlive = nlive;
-    j.pass_rows = (u32)ctx->opt.expand_scan_rows;
-    j.npasses = cdiv(nlive, j.pass_rows);
+    j.ctx = ctx;
+    if (sc.kmax) {
+        j.lid = sc.rid.p; j.lrow = sc.rrow.p; j.lhash = sc.rhash.p;
+        scan_cut_passes(sc.rows, sc.kmax + 1, pass_rows, j.passes);
+    } else {
+        j.lid = lid.p; j.lrow = lrow.p;
+        scan_cut_passes(&nlive, 1, pass_rows, j.passes);
+    }
+    j.npasses = (u32)j.passes.size();
     j.L = L; j.label = dst_label_bitmap;
     j.want_cs = checksum != nullptr; j.want_flops = flops != nullptr;
     ctx->scan_last_passes.store(j.npasses, std::memory_order_relaxed);
@@ -1721,7 +1929,7 @@ fgpu_info fgpu_expand_count(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsr
         if (checksum) *checksum = res.checksum;
         return FGPU_OK;
     }
-    return count_csr_result(ctx, res.mat.get(), nullptr, out_nnz, checksum);
+    return count_csr_result(ctx, res.mat.get(), nullptr, nullptr, out_nnz, checksum);
 }
 
 fgpu_info fgpu_expand_levels(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,

@@ -427,7 +427,12 @@ fgpu_info fgpu_expand_stream_close(fgpu_expand_stream* s);
  * order-independent checksum come back (full-size configs whose output would not
  * fit a host buffer): checksum = sum over the (row, dest) entries of
  * mix64(row) * (mix64(dest ^ 0x9e3779b97f4a7c15) | 1) mod 2^64, mix64 = the splitmix64 finaliser (a product of a row
- * hash and a destination hash: the bit-parallel state sums it per vertex through look-up tables instead of per entry). */
+ * hash and a destination hash: the bit-parallel state sums it per vertex through look-up tables instead of per entry).
+ * A call with more source rows than the whole-frontier bound (see fgpu_set_option) is cut into passes of live rows.  All
+ * three sums are linear in the rows, so over a hop 0 without delta entries the sources whose ONLY out-edge in m[0] ends at
+ * the same vertex are counted as one row: the row carries the sum of their row hashes, and its nnz and flops are multiplied
+ * by the number of sources it stands for.  The results are those of the row-by-row count, bit for bit; the passes counter
+ * reports the passes that ran, the live counter the live source rows. */
 fgpu_info fgpu_expand_count(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc,
                             const fgpu_mat* const* m, const fgpu_mat* const* dp,
                             const fgpu_mat* const* dm, int nhops,
