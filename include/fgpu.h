@@ -769,8 +769,10 @@ fgpu_info fgpu_shortest_dag_batch(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_m
  *     The key is a pure function of (q, x): the same for a query alone and for that query inside a batch of 1024.  Keys are
  *     compared as f32 values with -0.0 = +0.0.  Finite components can still overflow f32 on the way (components near 1e19
  *     and beyond under euclidean: nq, nx or S becomes inf; a cosine denominator that underflows to 0): a key of -inf or +inf
- *     orders as the f32 value it is, and a NaN key (inf - inf, 0 / 0) sorts after every other key, +inf included.  With the
- *     id as the second component the order is total for every input the calls accept; D is FP64 and does not overflow;
+ *     orders as the f32 value it is, and a NaN key (inf - inf, 0 / 0) sorts after every other key, +inf included.  The chain
+ *     itself never gives a NaN: fmaf(a, b, +-inf) with finite a and b adds the exact, finite product and is that infinity, so
+ *     an S that overflowed keeps its sign, and under ip every key is a number or -inf or +inf.  With the id as the second
+ *     component the order is total for every input the calls accept; D is FP64 and does not overflow;
  *   - fgpu_vecidx_knn returns, per query, the kk = min(k, count) entries of smallest (key, id), in ascending (D, id) order:
  *     *kk_out = kk, and ids / dist (HOST arrays of nq * kk) have row stride kk.  The caller sizes them from fgpu_vecidx_info.
  *     k == 0 is FGPU_INVALID.  With nq == 0 or count == 0, kk is 0 and the call does nothing (ids / dist may be NULL);

@@ -95,8 +95,10 @@ def test_identical_vectors_are_decided_by_id(ctx, new_index, metric):
     got_ids, _ = idx.knn(queries, k)
     assert np.array_equal(got_ids, np.tile(np.sort(ids)[:k], (nq, 1)))
     assert st[3] == nq * count          # every entry tied the k-th key, in every query
+    assert st[3] == sum(vc.expected_ties(k, vc.keys64(metric, q, x), ids) for q in queries)
     st_all = check_exact(idx, metric, ids, x, queries, count)
     assert st_all[3] == 0               # ... and when all of them fit there is nothing to decide
+    assert st_all[3] == sum(vc.expected_ties(count, vc.keys64(metric, q, x), ids) for q in queries)
 
 
 def test_ties_are_counted(ctx, new_index):
@@ -107,6 +109,7 @@ def test_ties_are_counted(ctx, new_index):
     idx = make(new_index, "euclidean", ids, x)
     st = check_exact(idx, "euclidean", ids, x, np.zeros((1, 2), dtype=np.float32), 3)
     assert st[3] > 0
+    assert st[3] == vc.expected_ties(3, vc.keys64("euclidean", np.zeros(2, dtype=np.float32), x), ids)
 
 
 @pytest.mark.parametrize("dim,places", [(4, (0, 1, 2, 3)), (16, (1, 6, 11, 12)), (33, (0, 5, 18, 32)), (33, (15, 16, 31, 32))])
