@@ -55,6 +55,8 @@ SIGNATURES = {
     "fgpu_mat_from_coo": (C.c_int32, [vp, vpp, C.c_uint64, C.c_uint64, u64p, u64p, u64p, C.c_uint64]),
     "fgpu_edges_build": (C.c_int32, [vp, C.c_uint64, C.c_uint64, u64p, u64p, u64p, C.c_uint64, vpp, vpp, C.POINTER(u64p),
                                      C.POINTER(u64p), C.POINTER(u64p), u64p, u64p]),
+    "fgpu_nodes_detach": (C.c_int32, [vp, vp, vp, u64p, C.c_uint64, C.c_int, vpp, vpp, C.POINTER(u64p), C.POINTER(u64p),
+                                      C.POINTER(u64p), u64p, u64p, u64p]),
     "fgpu_mat_from_csr": (C.c_int32, [vp, vpp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int,
                                       u64p, u64p, C.c_uint64]),
     "fgpu_mat_rmat": (C.c_int32, [vp, vpp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -668,6 +668,27 @@ def edges_build(ctx: Context, nrows: int, ncols: int, srcs, dsts, ids, stats: bo
     return out + ([int(x) for x in st],) if stats else out
 
 
+def nodes_detach(ctx: Context, m: Mat, mt: "Mat | None", nodes, sides: int = 3, want_list: bool = True, stats: bool = False):
+    """fgpu_nodes_detach: the matrix m (and its transposed pattern mt, or None) without the entries whose row (sides bit 0) or
+    column (bit 1) is one of `nodes`.  Returns (m_out, mt_out or None, rem_row, rem_col, rem_val, n_rem_out[, stats]): the
+    first n_rem_out triples of the removal list are the out entries in ascending (src, dst), the others the in entries in
+    ascending (dst, src); want_list=False asks for no list (three empty arrays, n_rem_out 0); stats the eight counters of
+    include/fgpu.h when stats=True."""
+    nodes = _u64(nodes).reshape(-1)
+    mo, mto = C.c_void_p(), C.c_void_p()
+    rr, rc, rv = u64p(), u64p(), u64p()
+    n, n_out = C.c_uint64(), C.c_uint64()
+    st = np.zeros(8, dtype=np.uint64)
+    check(ctx.lib.fgpu_nodes_detach(ctx._h, m._h, mt._h if mt is not None else None, _p(nodes), len(nodes), int(sides),
+                                    C.byref(mo), C.byref(mto) if mt is not None else None,
+                                    C.byref(rr) if want_list else None, C.byref(rc) if want_list else None,
+                                    C.byref(rv) if want_list else None, C.byref(n) if want_list else None,
+                                    C.byref(n_out) if want_list else None, _p(st)))
+    out = (Mat(ctx, mo), Mat(ctx, mto) if mt is not None else None, ctx._take(rr, n.value), ctx._take(rc, n.value),
+           ctx._take(rv, n.value), int(n_out.value))
+    return out + ([int(x) for x in st],) if stats else out
+
+
 def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
     """fgpu_maxflow: LAGr_MaxFlow's result for algo.maxFlow over the capacity matrix C_ — a valued snapshot carries one binary64
     bit pattern per entry, a BOOL one means capacity 1.0; diagonal entries and capacities <= 0 are ignored, a NaN or infinite

@@ -406,6 +406,36 @@ class Graph:
         _ck(self.L.fh_last_bulk_phases_ns(ns))
         return dict(zip(("edges_build", "fold_adopt", "me_fill", "adjacency_union"), (x / 1e6 for x in ns)))
 
+    def delete_nodes_bulk(self, nodes, skip_ids=(), stats=False, as_arrays=False):
+        """fh_graph_delete_nodes_bulk: DETACH DELETE of a node set in one call.  Returns the removed edges as a list of
+        (edge id, src, dst) in the reference's order (ids in skip_ids are removed too, but not listed) — as three uint64
+        arrays (ids, srcs, dsts) with as_arrays=True; with stats=True also what it did as a dict."""
+        v, k = _u64(nodes).reshape(-1), _u64(list(skip_ids)).reshape(-1)
+        i, s, d = u64p(), u64p(), u64p()
+        n = C.c_uint64()
+        st = (C.c_uint64 * 6)()
+        _ck(self.L.fh_graph_delete_nodes_bulk(self.h, _p(v), C.c_uint64(len(v)), _p(k), C.c_uint64(len(k)), C.byref(i), C.byref(s),
+                                              C.byref(d), C.byref(n), st))
+        rels = (_take(i, n.value), _take(s, n.value), _take(d, n.value))
+        if not as_arrays:
+            rels = list(zip(*(x.tolist() for x in rels)))
+        if not stats:
+            return rels
+        return rels, dict(zip(("nodes", "edges_removed", "edges_listed", "label_entries", "adjacency_entries", "multi_pairs"),
+                              (int(x) for x in st)))
+
+    def tensor_version(self, type_id):
+        """fh_graph_tensor_version: the dup() Graph::new_version takes of one type's tensor, as a Tensor of its own."""
+        h = C.c_void_p()
+        _ck(self.L.fh_graph_tensor_version(self.h, C.c_uint64(type_id), C.byref(h)))
+        return Tensor(self.ctx, _h=h)
+
+    def last_detach_phases_ms(self):
+        """fh_last_detach_phases_ns: host-clock ms of the last delete_nodes_bulk of this thread, by phase."""
+        ns = (C.c_uint64 * 4)()
+        _ck(self.L.fh_last_detach_phases_ns(ns))
+        return dict(zip(("tensors_detach", "list_expand", "labels", "adjacency"), (x / 1e6 for x in ns)))
+
     def delete_edge(self, type_id, src, dst, edge_id):
         _ck(self.L.fh_graph_delete_edge(self.h, C.c_uint64(type_id), C.c_uint64(src), C.c_uint64(dst),
                                         C.c_uint64(edge_id)))

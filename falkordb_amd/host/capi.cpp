@@ -309,6 +309,32 @@ int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* sr
         return 0;
     });
 }
+
+static thread_local uint64_t g_last_detach_ns[4] = {0, 0, 0, 0};   // phases of this thread's last bulk node delete
+int fh_last_detach_phases_ns(uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_last_detach_ns[k];
+    return 0;
+}
+int fh_graph_delete_nodes_bulk(fh_graph* g, const uint64_t* nodes, uint64_t n_nodes, const uint64_t* skip_ids, uint64_t n_skip,
+                               uint64_t** ids, uint64_t** srcs, uint64_t** dsts, uint64_t* n, uint64_t stats[6]) {
+    return guard([&] {
+        DetachStats ds;
+        auto rels = g->g.delete_nodes_bulk(std::vector<u64>(nodes, nodes + n_nodes),
+                                           skip_ids ? std::vector<u64>(skip_ids, skip_ids + n_skip) : std::vector<u64>(), &ds);
+        for (int k = 0; k < 4; ++k) g_last_detach_ns[k] = ds.phase_ns[k];
+        std::vector<u64> i(rels.size()), s(rels.size()), d(rels.size());
+        for (size_t k = 0; k < rels.size(); ++k) { i[k] = rels[k][0]; s[k] = rels[k][1]; d[k] = rels[k][2]; }
+        *ids = hand(i);
+        *srcs = hand(s);
+        *dsts = hand(d);
+        *n = rels.size();
+        if (stats) {
+            stats[0] = ds.nodes; stats[1] = ds.edges_removed; stats[2] = ds.edges_listed;
+            stats[3] = ds.label_entries; stats[4] = ds.adjacency_entries; stats[5] = ds.multi_pairs;
+        }
+        return 0;
+    });
+}
 int fh_tensor_edge_count(fh_graph* g, uint64_t type_id, uint64_t* out) {
     return guard([&] { *out = g->g.relationship_tensors().at(type_id).edge_count(); return 0; });
 }
@@ -345,7 +371,10 @@ void fh_tn_free(fh_tn* t) { delete t; }
 int fh_tn_dup(fh_tn* t, fh_tn** out) {
     return guard([&] { *out = new fh_tn{t->t.dup()}; return 0; });
 }
-int fh_tn_set_all(fh_tn* t, const uint64_t* srcs, const uint64_t* dsts, const uint64_t* ids, uint64_t n) {
+int fh_graph_tensor_version(fh_graph* g, uint64_t type_id, fh_tn** out) {
+    return guard([&] { *out = new fh_tn{g->g.relationship_tensors().at(type_id).dup()}; return 0; });
+}
+int fh_tn_set_all(fh_tn* t,const uint64_t* srcs, const uint64_t* dsts, const uint64_t* ids, uint64_t n) {
     return guard([&] {
         t->t.set_all_from_slices(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n),
                                  std::vector<u64>(ids, ids + n));

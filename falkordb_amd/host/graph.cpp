@@ -88,6 +88,51 @@ BulkStats Graph::bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, c
     return bs;
 }
 
+std::vector<std::array<u64, 3>> Graph::delete_nodes_bulk(const std::vector<u64>& nodes, const std::vector<u64>& skip_ids,
+                                                         DetachStats* stats) {
+    std::vector<std::array<u64, 3>> out;
+    DetachStats ds;
+    if (nodes.empty()) {
+        if (stats) *stats = ds;
+        return out;
+    }
+    for (u64 v : nodes)
+        if (v >= n_)
+            throw GrbError(FGPU_INVALID, "delete_nodes_bulk: node " + std::to_string(v) + " is at or past the capacity " +
+                                             std::to_string(n_));
+    const std::unordered_set<u64> skip(skip_ids.begin(), skip_ids.end());
+    ds.per_type.assign(tensors_.size(), 0);
+    DetachCounts dc;
+    for (size_t t = 0; t < tensors_.size(); ++t) {
+        const u64 before = dc.removed;
+        const size_t listed0 = out.size(), skipped0 = dc.skipped.size();
+        auto rels = tensors_[t].detach_nodes(nodes, skip, &dc);
+        out.insert(out.end(), rels.begin(), rels.end());
+        ds.per_type[t] = dc.removed - before;
+        if (!vec_indexes_.empty()) {   // every removed edge leaves the indexes of its type, as delete_edge makes it
+            for (size_t k = listed0; k < out.size(); ++k) drop_entity_vectors(true, t, out[k][0]);
+            for (size_t k = skipped0; k < dc.skipped.size(); ++k) drop_entity_vectors(true, t, dc.skipped[k]);
+        }
+    }
+    ds.edges_removed = dc.removed;
+    ds.edges_listed = out.size();
+    ds.multi_pairs = dc.multi_pairs;
+    ds.phase_ns[0] = dc.phase_ns[0];
+    ds.phase_ns[1] = dc.phase_ns[1];
+    u64 t0 = bulk_clock_ns();
+    ds.label_entries = labels_.detach_base(nodes, 1);     // graph.rs:1753-1768
+    ds.phase_ns[2] = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    ds.adjacency_entries = adj_.detach_base(nodes, 3);
+    ds.phase_ns[3] = bulk_clock_ns() - t0;
+    std::unordered_set<u64> seen;
+    for (u64 v : nodes)
+        if (seen.insert(v).second) delete_node(v);
+    ds.nodes = seen.size();
+    if (stats) *stats = ds;
+    return out;
+}
+
 void Graph::new_version() {
     adj_ = adj_.dup();
     labels_ = labels_.dup();

@@ -26,6 +26,7 @@
 #include <string>
 #include <tuple>
 #include <unordered_map>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -241,6 +242,12 @@ class VersionedMatrix {
     // base is REPLACED, never mutated: dup()ed versions and extracted matrices keep the snapshot they share
     void fold_all();
     void union_base(const Matrix& pattern);
+    // bulk DETACH DELETE (the label rows of Graph::delete_nodes, graph.rs:1753-1768, and the adjacency's share of
+    // delete_implicit_edges, as ONE device pass): fold_all, then the base is replaced by fgpu_nodes_detach's result — without
+    // the entries whose row (sides bit 0) or column (bit 1) is one of `nodes` (any order, duplicates allowed).  Returns the
+    // number of entries removed; a node outside the dimension it indexes throws before anything changed.  No tombstone is left
+    // to fold later, and dup()ed versions keep the base they share.
+    u64 detach_base(const std::vector<u64>& nodes, int sides);
     VersionedMatrix dup() const;                                           // :1038-1051
     void fold_oversized();                                                 // :953-965
     void fold_latched();                                                   // :940-951
@@ -265,6 +272,21 @@ struct BulkStats {
     u64 device_edges = 0, fallback_edges = 0, distinct_pairs = 0, multi_pairs = 0, unsorted_runs = 0, host_sorted_runs = 0;
     // host clock, ns (a measurement hook, tools/bench_paths.py load): [0] the fgpu_edges_build call, [1] folding the layers
     // and adopting / merging the built pieces (or the whole fallback), [2] filling me, [3] the adjacency union
+    u64 phase_ns[4] = {0, 0, 0, 0};
+};
+// What Tensor::detach_nodes did beside the list it returns (accumulated: a Graph adds every type's into one)
+struct DetachCounts {
+    u64 removed = 0;             // edges taken out of the tensor, the skipped ones included
+    u64 multi_pairs = 0;         // multi-edge pairs among them (their me rows are erased)
+    std::vector<u64> skipped;    // the removed ids that skip_ids kept out of the list
+    u64 phase_ns[2] = {0, 0};    // host clock: [0] fold + fgpu_nodes_detach + adoption, [1] expanding and ordering the list
+};
+// What Graph::delete_nodes_bulk did, in the shape of BulkStats
+struct DetachStats {
+    u64 nodes = 0, edges_removed = 0, edges_listed = 0, label_entries = 0, adjacency_entries = 0, multi_pairs = 0;
+    std::vector<u64> per_type;   // edges removed per relationship type (the skipped ones included)
+    // host clock, ns (a measurement hook, tools/bench_paths.py detach): [0] the tensors' folds and fgpu_nodes_detach calls,
+    // [1] expanding and ordering their lists, [2] the label matrix, [3] the adjacency
     u64 phase_ns[4] = {0, 0, 0, 0};
 };
 constexpr u64 GrB_INDEX_MAX = (1ull << 60) - 1;          // tensor.rs:136
@@ -299,6 +321,19 @@ class Tensor {
                           std::optional<Matrix>* built = nullptr);
     // (the same over the caller's arrays: a load of 2^26 tuples is 1.6 GB that need not be copied into vectors first)
     BulkStats bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built = nullptr);
+    // This type's share of Graph::delete_implicit_edges (graph.rs:2386-2494) for the node set `nodes` (any order, duplicates
+    // allowed), as one device pass: m / dp / dm and mt are folded, ONE fgpu_nodes_detach takes every entry incident to the nodes
+    // out of m and mt and its results are adopted as the bases — the tensor ends folded (dp = dm = 0), no tombstone is left —
+    // and the me rows of the removed multi-edge pairs are erased.  Returns (edge id, src, dst) in the reference's order
+    // (:2405-2427): per node ascending, first its out edges by ascending dst, then its in edges from sources that are not
+    // deleted themselves by ascending src; the ids of a multi-edge pair ascending.  A self-loop and an edge between two
+    // deleted nodes are listed once, from the source.
+    // Ids in `skip_ids` (the reference's explicit_rels, which delete_relationships handles) are LEFT OUT of the returned list,
+    // but their entries are removed like the others: the reference leaves them to the explicit delete that follows, here that
+    // later delete_edge finds the pair absent and does nothing — the state after both steps is the reference's.
+    // A node at or past the dimension throws before anything changed.  Versions dup()ed earlier keep the bases they share.
+    std::vector<std::array<u64, 3>> detach_nodes(const std::vector<u64>& nodes, const std::unordered_set<u64>& skip_ids = {},
+                                                 DetachCounts* counts = nullptr);
     std::vector<std::pair<u64, u64>> remove_all(const std::vector<std::array<u64, 3>>& rels);  // :461-657
     bool has_multi_edge() const { return !me_.empty(); }
     void resize(u64 nrows, u64 ncols);                                     // :659-726
@@ -407,6 +442,15 @@ class Graph {
     BulkStats bulk_insert_edges(u64 type, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                                 const std::vector<u64>& ids);
     BulkStats bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n);
+    // bulk DETACH DELETE (Pending::commit's Graph::delete_nodes + delete_implicit_edges, graph.rs:1698-1772, 2386-2494, as one
+    // call): every node gets delete_node's effects; every tensor detach_nodes — the returned list is their lists in ascending
+    // type id — and every removed edge leaves the vector indexes as delete_edge makes it; the node x label matrix loses the
+    // nodes' rows (sides = 1) and the adjacency every entry incident to them (sides = 3).  That removes the (deleted, deleted)
+    // pairs too, which the reference leaves in the adjacency as unreachable (:2381-2383): it is what the edge-by-edge path
+    // produces and what the algo.* builders should see.  An empty `nodes` does nothing; a node at or past node_cap() throws
+    // before anything changed.
+    std::vector<std::array<u64, 3>> delete_nodes_bulk(const std::vector<u64>& nodes, const std::vector<u64>& skip_ids = {},
+                                                      DetachStats* stats = nullptr);
     void new_version();              // graph.rs:851-890: every matrix dup()s (fold decisions latch here)
     void fold_oversized_deltas();    // graph.rs:2155-2172, called at MVCC commit (mvcc_graph.rs:161-180)
 

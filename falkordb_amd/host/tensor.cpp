@@ -248,6 +248,78 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
     return bs;
 }
 
+std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nodes, const std::unordered_set<u64>& skip_ids,
+                                                     DetachCounts* counts) {
+    std::vector<std::array<u64, 3>> out;
+    if (nodes.empty()) return out;
+    for (u64 v : nodes)
+        if (v >= m_.nrows() || v >= m_.ncols())
+            throw GrbError(FGPU_INVALID, "Tensor::detach_nodes: node " + std::to_string(v) + " is outside the tensor");
+    Context& ctx = m_.ctx();
+    fgpu_ctx* c = ctx.raw();
+    u64 t0 = bulk_clock_ns();
+    // fold first, as bulk_insert does before it adopts a base: the device pass reads m and mt alone
+    flush();
+    dp_.wait();
+    dm_.wait();
+    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
+        dp_.latch(true);
+        dm_.latch(true);
+        needs_flush_ = true;
+        flush();
+    }
+    mt_.fold_all();
+    fgpu_mat *mo = nullptr, *mto = nullptr;
+    EngineArray rr(c), rc(c), rv(c);
+    u64 n_rem = 0, n_out = 0, st[8] = {0};
+    check(fgpu_nodes_detach(c, m_.snapshot(), mt_.m().snapshot(), nodes.data(), nodes.size(), 3, &mo, &mto, &rr.p, &rc.p, &rv.p, &n_rem,
+                            &n_out, st),
+          "Tensor::detach_nodes");
+    Matrix new_m = Matrix::adopt(ctx, Type::UInt64, mo);
+    Matrix new_mt = Matrix::adopt(ctx, Type::Bool, mto);
+    if (n_rem) {   // (nothing incident: the bases stay the snapshots they are)
+        m_ = new_m;
+        mt_ = VersionedMatrix::from_matrix(new_mt);
+    }
+    if (counts) counts->phase_ns[0] += bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    // the reference's order (graph.rs:2405-2427): per node of D ascending its out edges, then its in edges.  The out segment
+    // ascends in (src, dst) and the in segment in (dst, src), so one cursor on each walks the nodes in step
+    out.reserve(n_rem);
+    u64 removed = 0, multi = 0;
+    auto emit = [&](u64 k) {
+        const u64 s = rr.p[k], d = rc.p[k], v = rv.p[k];
+        if (v != MULTI_EDGE) {
+            ++removed;
+            if (skip_ids.empty() || !skip_ids.count(v)) out.push_back({v, s, d});
+            else if (counts) counts->skipped.push_back(v);
+            return;
+        }
+        auto it = me_.find(compound_key(s, d));
+        if (it == me_.end()) return;
+        ++multi;
+        for (u64 id : it->second) {   // ascending
+            ++removed;
+            if (skip_ids.empty() || !skip_ids.count(id)) out.push_back({id, s, d});
+            else if (counts) counts->skipped.push_back(id);
+        }
+        me_.erase(it);
+    };
+    u64 i = 0, j = n_out;
+    while (i < n_out || j < n_rem) {
+        const u64 a = i < n_out ? rr.p[i] : ~0ull, b = j < n_rem ? rc.p[j] : ~0ull;
+        const u64 node = std::min(a, b);
+        while (i < n_out && rr.p[i] == node) emit(i++);
+        while (j < n_rem && rc.p[j] == node) emit(j++);
+    }
+    if (counts) {
+        counts->removed += removed;
+        counts->multi_pairs += multi;
+        counts->phase_ns[1] += bulk_clock_ns() - t0;
+    }
+    return out;
+}
+
 std::vector<std::pair<u64, u64>> Tensor::remove_all(const std::vector<std::array<u64, 3>>& rels) {
     std::vector<std::pair<u64, u64>> emptied;
     if (rels.empty()) return emptied;

@@ -264,6 +264,23 @@ void VersionedMatrix::union_base(const Matrix& pattern) {
     m_ = Matrix::adopt(m_.ctx(), Type::Bool, o);
 }
 
+u64 VersionedMatrix::detach_base(const std::vector<u64>& nodes, int sides) {
+    if (nodes.empty()) return 0;
+    for (u64 v : nodes)
+        if (((sides & 1) && v >= m_.nrows()) || ((sides & 2) && v >= m_.ncols()))
+            throw GrbError(FGPU_INVALID, "VersionedMatrix::detach_base: node " + std::to_string(v) + " is outside the matrix");
+    fold_all();
+    fgpu_mat* o = nullptr;
+    u64 st[8] = {0};
+    check(fgpu_nodes_detach(m_.ctx().raw(), m_.snapshot(), nullptr, nodes.data(), nodes.size(), sides, &o, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, st),
+          "VersionedMatrix::detach_base");
+    Matrix fresh = Matrix::adopt(m_.ctx(), Type::Bool, o);
+    const u64 removed = m_.nvals() - st[4];
+    if (removed) m_ = fresh;   // (nothing incident: the base stays the snapshot it is)
+    return removed;
+}
+
 VersionedMatrix VersionedMatrix::dup() const {
     u64 base = m_.nvals();
     bool fold_dp = dp_.fold_decision(should_fold, base);

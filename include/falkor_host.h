@@ -106,6 +106,23 @@ int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* sr
  * [0] the fgpu_edges_build call, [1] folding the layers and adopting / merging the built pieces (or the whole fallback),
  * [2] filling the multi-edge map, [3] the adjacency union */
 int fh_last_bulk_phases_ns(uint64_t out[4]);
+/* DETACH DELETE of a node set in one call (what Pending::commit does with Graph::delete_nodes + delete_implicit_edges,
+ * graph.rs:1698-1772, 2386-2494): every node gets fh_graph_delete_node's effects; per relationship type one fgpu_nodes_detach
+ * takes the incident edges out of the tensor, which ends folded; the node x label matrix loses the nodes' rows and the adjacency
+ * every entry incident to them (also the pairs with BOTH ends deleted, which the reference leaves behind as unreachable).
+ * ids / srcs / dsts (malloc'ed, fh_free; n of each) are the removed edges in the reference's order: types ascending; per type
+ * the nodes ascending; per node its out edges by ascending dst, then its in edges from surviving sources by ascending src; the
+ * ids of one pair ascending.  The n_skip ids of skip_ids (the reference's explicit_rels; nullable) are left out of the list,
+ * but their edges leave the graph like the others: a later fh_graph_delete_edge of one finds the pair absent and does nothing.
+ * stats (nullable): [0] distinct nodes, [1] edges removed (the skipped ones included), [2] edges listed, [3] label entries
+ * removed, [4] adjacency entries removed, [5] multi-edge pairs removed.  An empty node list does nothing; a node at or past the
+ * node capacity returns the engine's code before anything changed. */
+int fh_graph_delete_nodes_bulk(fh_graph* g, const uint64_t* nodes, uint64_t n_nodes, const uint64_t* skip_ids, uint64_t n_skip,
+                               uint64_t** ids, uint64_t** srcs, uint64_t** dsts, uint64_t* n, uint64_t stats[6]);
+/* host-clock phases (ns) of this thread's last fh_graph_delete_nodes_bulk (a measurement hook, tools/bench_paths.py detach):
+ * [0] the tensors' fgpu_nodes_detach calls with their folds, [1] expanding and ordering the lists on the host, [2] the label
+ * matrix, [3] the adjacency */
+int fh_last_detach_phases_ns(uint64_t out[4]);
 int fh_graph_delete_edge(fh_graph* g, uint64_t type_id, uint64_t src, uint64_t dst, uint64_t edge_id);
 /* MVCC commit of every matrix: dup() (fold decision) then fold_oversized, as mvcc_graph.rs:161-180 does */
 int fh_graph_commit(fh_graph* g);
@@ -139,6 +156,9 @@ int fh_tn_state(fh_tn* t, uint64_t out[8]);
  * default codec is this library's plain list; a GxB_Vector_serialize blob needs GraphBLAS (see serialize.cpp). */
 int fh_tn_encode(fh_tn* t, uint8_t** bytes, uint64_t* len);
 int fh_tn_decode(fh_ctx* ctx, const uint8_t* bytes, uint64_t len, fh_tn** out, uint64_t* consumed);
+/* the dup() Graph::new_version takes of one type's tensor (graph.rs:851-890), as a handle of its own (fh_tn_free): the version
+ * a reader holds while the graph goes on being written */
+int fh_graph_tensor_version(fh_graph* g, uint64_t type_id, fh_tn** out);
 
 /* Raw layer dump for tests: type_id < 0 = the adjacency matrix; which 0 = m, 1 = dp, 2 = dm. */
 int fh_graph_layer_iter(fh_graph* g, int64_t type_id, int which, uint64_t** rows, uint64_t** cols,

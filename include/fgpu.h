@@ -221,6 +221,34 @@ fgpu_info fgpu_edges_build(fgpu_ctx* ctx, uint64_t nrows, uint64_t ncols, const 
                            const uint64_t* ids, uint64_t n, fgpu_mat** fwd, fgpu_mat** bwd, uint64_t** multi_key,
                            uint64_t** multi_off, uint64_t** multi_ids, uint64_t* n_multi, uint64_t stats[8]);
 
+/* DETACH DELETE of a node set on one matrix (Graph::delete_nodes + delete_implicit_edges, graph.rs:1698-1772, 2386-2494): the
+ * entries incident to the nodes leave the matrix and its transposed pattern, and come back as the removal list.
+ *   m      a BOOL or UINT64 snapshot; mt (nullable) the BOOL transposed pattern of m, what a Tensor holds as `mt`;
+ *   nodes  a host array of n_nodes ids, any order, duplicates allowed; D is its set;
+ *   sides  bit 0: the entries whose ROW is in D are dropped; bit 1: the entries whose COLUMN is in D are dropped.  1 serves the
+ *          node x label matrix, 3 tensors and the adjacency.
+ * m_out is m without the dropped entries: the same type, dimensions and values, sorted unique rows, stored hypersparse exactly
+ * when fgpu_mat_from_coo would store that many populated rows of that dimension so.  mt_out is the same for mt with rows and
+ * columns swapped; it must be non-NULL exactly when mt is.  Both are NEW snapshots (fgpu_mat_free): m and mt are untouched, and
+ * whoever still reads them keeps reading them.
+ * The removal list is wanted when rem_row is non-NULL (then rem_col, rem_val, n_rem and n_rem_out must be too) and needs mt:
+ *   the first n_rem_out triples (rem_row, rem_col, rem_val)[k] = (s, d, v) are the OUT entries, those with s in D under bit 0, in
+ *   ascending (s, d) — a self-loop on a node of D appears here only;
+ *   the other n_rem - n_rem_out are the IN entries, those with d in D under bit 1 that are not out entries (s not in D when bit
+ *   0 is set), in ascending (d, s): the order in which a walk of mt's rows meets them.
+ * v is the value m stores — for a tensor the inline edge id or FGPU_MULTI_EDGE — and 0 for a BOOL m.  The arrays are
+ * engine-owned (fgpu_free) and NULL when n_rem == 0.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated and the context still usable, for: a node id at or past a dimension
+ * it indexes (the rows under bit 0, the columns under bit 1); sides outside 1..3; a list wanted with bit 1 on a matrix that is
+ * not square; mt of other dimensions than ncols x nrows, or valued; a list wanted without mt.  n_nodes == 0 gives copies of the
+ * inputs and an empty list.
+ * stats (nullable): [0] distinct nodes in D, [1] out entries and [2] in entries of the list (0 when none is wanted), [3] removed
+ * entries of m whose value is FGPU_MULTI_EDGE, [4] entries kept in m_out, [5] entries kept in mt_out; [6], [7] are 0.
+ * Work: one lane per stored entry of m and of mt, every output placed by a scan. */
+fgpu_info fgpu_nodes_detach(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt, const uint64_t* nodes, uint64_t n_nodes,
+                            int sides, fgpu_mat** m_out, fgpu_mat** mt_out, uint64_t** rem_row, uint64_t** rem_col,
+                            uint64_t** rem_val, uint64_t* n_rem, uint64_t* n_rem_out, uint64_t stats[8]);
+
 /* Host CSR (what GxB_unload_Matrix_into_Container yields: p, i, x [, h];
  * matrix.rs:508-546) -> device snapshot.  rowptr has nvec+1 entries when
  * `hyper_rows` (sorted non-empty row ids, nvec of them) is given, else

@@ -68,7 +68,16 @@
           fgpu_edges_build of the same tuples on the engine context (fgpu_prof_*), and on that graph the host leg's figures for
           one 1024-row 2-hop batch (operator22).  `load <scale>`: the twin comparison at that scale only.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  detach  the host layer's cascade delete: Graph::delete_nodes_bulk (one fgpu_nodes_detach per tensor, the label matrix and the
+          adjacency) against the path that existed before it — one delete_edge per incident edge, then delete_node — on twin
+          graphs of the distinct RMAT-12, RMAT-18 and RMAT-20 edges loaded with bulk_insert_edges, the same seeded 1 %, 10 % and
+          100 % of the nodes, a host clock around delete + commit.  The bulk twin: one warm-up, median of 3, a fresh twin each.
+          The edge-by-edge twin: one run under a deadline (60 s at RMAT-12, 10 s beyond), us per edge and the extrapolation
+          when it did not finish.  Then the raw fgpu_nodes_detach on the RMAT-22 tensor of the load leg (UINT64 base + transposed
+          pattern) for 1 % and 10 % of the nodes, with list and mt and on m alone, its device phases, beside one fgpu_mat_merge
+          of the same matrix with 0.1 % deltas.  `detach <scale>`: the twin comparison at that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -344,6 +353,132 @@ def bench_load(scales=(18, 20), raw_scale=22):
     A = ctx.mat_from_coo(n, n, u, v)
     src = np.random.default_rng(3).choice(n, 1024, replace=False).astype(np.uint64)
     print(json.dumps(dict({"path": "operator22", "scale": raw_scale}, **operator_figures(g, ctx, A, src))), flush=True)
+
+
+def bench_detach(scales=(18, 20), small_scale=12, raw_scale=22, deadline_s=10.0):
+    from falkordb_amd import host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+    fracs = (0.01, 0.1, 1.0)
+
+    def graph_of(scale):
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        A.free()
+        return n, r, ci, np.arange(len(ci), dtype=np.uint64)
+
+    def loaded(n, r, ci, ids):
+        g = host.Graph(hc, n)
+        t = g.add_type("KNOWS")
+        g.bulk_insert_edges(t, r, ci, ids)
+        g.commit()
+        return g, t
+
+    def nodes_of(n, frac):
+        return np.sort(np.random.default_rng(int(frac * 1000)).choice(n, max(1, int(n * frac)), replace=False)).astype(np.uint64)
+
+    def bulk(n, r, ci, ids, D, incident):
+        ts = []
+        for rep in range(4):                     # (rep 0 warms up; every rep deletes from a freshly loaded twin)
+            g, t = loaded(n, r, ci, ids)
+            t0 = time.perf_counter()
+            rels, st = g.delete_nodes_bulk(D, stats=True, as_arrays=True)
+            t1 = time.perf_counter()
+            g.commit()
+            t2 = time.perf_counter()
+            assert st["edges_removed"] == incident == len(rels[0]) and g.tensor_edge_count(t) == len(ci) - incident
+            ts.append((t2 - t0, t1 - t0, g.last_detach_phases_ms()))
+            del rels, g
+        k = int(np.argsort([x[0] for x in ts[1:]])[1]) + 1
+        return ts[k]
+
+    def edge_by_edge(n, r, ci, ids, D, mask, deadline):
+        """today's path on a fresh twin: delete_edge per incident edge, then delete_node; stops at the deadline"""
+        g, t = loaded(n, r, ci, ids)
+        t0 = time.perf_counter()
+        if len(ci) <= 1 << 20:                   # (the collection today's caller pays; past 2^20 edges the loaded arrays stand in)
+            es = [e for e in g.tensor_iter_edges(t) if mask[e[0]] or mask[e[1]]]
+        else:
+            k = np.nonzero(mask[r] | mask[ci])[0]
+            es = list(zip(r[k].tolist(), ci[k].tolist(), ids[k].tolist()))
+        t_collect = time.perf_counter() - t0
+        done = 0
+        t0 = time.perf_counter()
+        for s, d, i in es:
+            g.delete_edge(t, s, d, i)
+            done += 1
+            if (done & 63) == 0 and time.perf_counter() - t0 > deadline:
+                break
+        finished = done == len(es)
+        if finished:
+            for v in D.tolist():
+                g.delete_node(v)
+            g.commit()
+        dt = time.perf_counter() - t0
+        return {"collect_s": round(t_collect, 3), "edges_done": done, "edges": len(es), "finished": finished, "s": round(dt, 3),
+                "us_per_edge": round(dt / max(done, 1) * 1e6, 2),
+                "s_extrapolated": round(dt / max(done, 1) * len(es), 2)}
+
+    for scale in (small_scale,) + tuple(scales):
+        n, r, ci, ids = graph_of(scale)
+        for frac in fracs:
+            D = nodes_of(n, frac)
+            mask = np.zeros(n, dtype=bool)
+            mask[D.astype(np.int64)] = True
+            incident = int((mask[r] | mask[ci]).sum())
+            total, call, phases = bulk(n, r, ci, ids, D, incident)
+            ebe = edge_by_edge(n, r, ci, ids, D, mask, deadline_s * (6 if scale == small_scale else 1))
+            ref = ebe["s"] if ebe["finished"] else ebe["s_extrapolated"]
+            print(json.dumps({"path": "graph_detach", "scale": scale, "edges": len(ci), "nodes_deleted": len(D), "frac": frac,
+                              "incident_edges": incident,
+                              "delete_nodes_bulk": {"s": round(total, 5), "call_s": round(call, 5),
+                                                    "us_per_edge": round(total / max(incident, 1) * 1e6, 5),
+                                                    "host_phases_ms": {k_: round(v_, 3) for k_, v_ in phases.items()}},
+                              "edge_by_edge": ebe, "quotient": round(ref / total, 1),
+                              "note": "twin graphs loaded with bulk_insert_edges + commit in one process; host clock around delete + "
+                                      "commit; bulk: one warm-up, median of 3, a fresh twin each; edge by edge: one run, stopped at "
+                                      "its deadline (finished = false: s_extrapolated = us_per_edge x edges, and the quotient uses it)"}),
+                  flush=True)
+        del r, ci, ids
+    if not raw_scale:
+        return
+    import oracle
+    u, v = oracle.rmat_edges(raw_scale)
+    n = 1 << raw_scale
+    fwd, bwd, _, _, _ = engine.edges_build(ctx, n, n, u, v, np.arange(len(u), dtype=np.uint64))
+    del u, v
+    rng = np.random.default_rng(5)
+    dp, dm = deltas(ctx, fwd, 0.001, rng, valued=True)
+    t_merge, merged = timed(ctx, lambda: fwd.merge(dp, dm), reps=5, warm=2)
+    del merged
+    for frac in (0.01, 0.1):
+        D = nodes_of(n, frac)
+        t_call, res = timed(ctx, lambda: engine.nodes_detach(ctx, fwd, bwd, D, stats=True), reps=3, warm=1)
+        st = res[-1]
+        del res
+        t_nolist, res = timed(ctx, lambda: engine.nodes_detach(ctx, fwd, None, D, want_list=False), reps=3, warm=1)
+        del res
+        ctx.prof_enable(True)
+        res = engine.nodes_detach(ctx, fwd, bwd, D)
+        ctx.sync()
+        dev = {}
+        for p in ctx.prof_read():
+            if p["kernel"].startswith("dt_"):
+                dev[p["kernel"]] = round(dev.get(p["kernel"], 0.0) + p["ms"], 3)
+        ctx.prof_enable(False)
+        del res
+        print(json.dumps({"path": "nodes_detach_raw", "scale": raw_scale, "nnz": fwd.nvals, "frac": frac, "nodes": len(D), "stats": st[:6],
+                          "ms_call_with_list_and_mt": round(t_call * 1e3, 3), "ms_call_m_only_no_list": round(t_nolist * 1e3, 3),
+                          "device_phases_ms": dev, "ms_fgpu_mat_merge_0.1pct_deltas": round(t_merge * 1e3, 3),
+                          "quotient_m_only_over_merge": round(t_nolist / t_merge, 2),
+                          "note": "the UINT64 tensor base of the raw RMAT stream (fgpu_edges_build) and its transposed pattern; median "
+                                  "of 3 synchronised calls after 1 warm-up, list read-back included; device_phases = HIP events of one "
+                                  "more call (flags + scans of both passes, both emissions, the list's read-back); the merge is "
+                                  "fgpu_mat_merge of the same matrix with 0.1 % valued adds and 0.1 % tombstones, median of 5"}),
+              flush=True)
 
 
 def bench_host(scale):
@@ -959,3 +1094,5 @@ if __name__ == "__main__":
         bench_host(scale or 18)
     if what == "load":                           # (minutes of edge-by-edge loading: not part of `all`)
         bench_load(*(((scale,), 0) if scale else ()))
+    if what == "detach":                         # (edge-by-edge deletes up to their deadlines: not part of `all`)
+        bench_detach(*(((), scale, 0) if scale else ()))
