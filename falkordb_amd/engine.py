@@ -689,6 +689,32 @@ def nodes_detach(ctx: Context, m: Mat, mt: "Mat | None", nodes, sides: int = 3, 
     return out + ([int(x) for x in st],) if stats else out
 
 
+def edges_remove(ctx: Context, m: Mat, mt: "Mat | None", srcs, dsts, ids, multi_key=(), multi_off=(0,), multi_ids=(),
+                 want_hit: bool = True, stats: bool = False):
+    """fgpu_edges_remove: the tensor base m (UINT64: inline edge id or MULTI_EDGE) and its transposed pattern mt without the
+    edges the (src, dst, id) triples name; multi_key / multi_off / multi_ids are the multi-edge rows of the touched pairs in
+    edges_build's shape.  Returns (m_out, mt_out, hit uint8[n] or None, multi_taken uint8[len(multi_ids)], emp_row, emp_col[,
+    stats]): hit[k] = triple k named a stored edge, multi_taken[j] = multi_ids[j] was removed, (emp_row, emp_col) the pairs that
+    left m in ascending (src, dst); stats the eight counters of include/fgpu.h when stats=True."""
+    srcs, dsts, ids = _u64(srcs).reshape(-1), _u64(dsts).reshape(-1), _u64(ids).reshape(-1)
+    if not (len(srcs) == len(dsts) == len(ids)):
+        raise ValueError("edges_remove: srcs, dsts and ids differ in length")
+    mk, mo, mi = _u64(multi_key).reshape(-1), _u64(multi_off).reshape(-1), _u64(multi_ids).reshape(-1)
+    if len(mo) != len(mk) + 1 or (len(mk) and int(mo[-1]) != len(mi)):
+        raise ValueError("edges_remove: multi_off does not describe multi_key / multi_ids")
+    mout, mtout = C.c_void_p(), C.c_void_p()
+    hit = np.zeros(len(srcs), dtype=np.uint8) if want_hit else None
+    taken = np.zeros(len(mi), dtype=np.uint8)
+    er, ec = u64p(), u64p()
+    ne = C.c_uint64()
+    st = np.zeros(8, dtype=np.uint64)
+    check(ctx.lib.fgpu_edges_remove(ctx._h, m._h, mt._h if mt is not None else None, _p(srcs), _p(dsts), _p(ids), len(srcs),
+                                    _p(mk), _p(mo), _p(mi), len(mk), C.byref(mout), C.byref(mtout), _p(hit, u8p), _p(taken, u8p),
+                                    C.byref(er), C.byref(ec), C.byref(ne), _p(st)))
+    out = (Mat(ctx, mout), Mat(ctx, mtout), hit, taken, ctx._take(er, ne.value), ctx._take(ec, ne.value))
+    return out + ([int(x) for x in st],) if stats else out
+
+
 def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
     """fgpu_maxflow: LAGr_MaxFlow's result for algo.maxFlow over the capacity matrix C_ — a valued snapshot carries one binary64
     bit pattern per entry, a BOOL one means capacity 1.0; diagonal entries and capacities <= 0 are ignored, a NaN or infinite

@@ -436,6 +436,37 @@ class Graph:
         _ck(self.L.fh_last_detach_phases_ns(ns))
         return dict(zip(("tensors_detach", "list_expand", "labels", "adjacency"), (x / 1e6 for x in ns)))
 
+    def delete_edges_bulk(self, types, srcs, dsts, ids, stats=False, as_arrays=False):
+        """fh_graph_delete_edges_bulk: DELETE r of a batch of edges in one call; `types` is one type id per edge, or one id for
+        all.  Returns the removed edges as a list of (edge id, src, dst) — types ascending, input order within a type — as three
+        uint64 arrays (ids, srcs, dsts) with as_arrays=True; with stats=True also what it did as a dict."""
+        s, d, i = _u64(srcs).reshape(-1), _u64(dsts).reshape(-1), _u64(ids).reshape(-1)
+        t = _u64(types).reshape(-1)
+        if t.size == 1 and len(s) != 1:
+            t = np.full(len(s), t[0], dtype=np.uint64)
+        if not (len(t) == len(s) == len(d) == len(i)):
+            raise ValueError("delete_edges_bulk: types, srcs, dsts and ids differ in length")
+        oi, os_, od, pt = u64p(), u64p(), u64p(), u64p()
+        n, nt = C.c_uint64(), C.c_uint64()
+        st = (C.c_uint64 * 5)()
+        _ck(self.L.fh_graph_delete_edges_bulk(self.h, _p(t), _p(s), _p(d), _p(i), C.c_uint64(len(s)), C.byref(oi), C.byref(os_),
+                                              C.byref(od), C.byref(n), st, C.byref(pt), C.byref(nt)))
+        rels = (_take(oi, n.value), _take(os_, n.value), _take(od, n.value))
+        per_type = _take(pt, nt.value).tolist()
+        if not as_arrays:
+            rels = list(zip(*(x.tolist() for x in rels)))
+        if not stats:
+            return rels
+        out = dict(zip(("edges_named", "edges_removed", "pairs_emptied", "pairs_demoted", "adjacency_entries"), (int(x) for x in st)))
+        out["per_type"] = per_type
+        return rels, out
+
+    def last_edge_delete_phases_ms(self):
+        """fh_last_edge_delete_phases_ns: host-clock ms of the last delete_edges_bulk of this thread, by phase."""
+        ns = (C.c_uint64 * 4)()
+        _ck(self.L.fh_last_edge_delete_phases_ns(ns))
+        return dict(zip(("gather_rows", "edges_remove", "me_rewrite", "adjacency"), (x / 1e6 for x in ns)))
+
     def delete_edge(self, type_id, src, dst, edge_id):
         _ck(self.L.fh_graph_delete_edge(self.h, C.c_uint64(type_id), C.c_uint64(src), C.c_uint64(dst),
                                         C.c_uint64(edge_id)))

@@ -335,6 +335,35 @@ int fh_graph_delete_nodes_bulk(fh_graph* g, const uint64_t* nodes, uint64_t n_no
         return 0;
     });
 }
+static thread_local uint64_t g_last_edge_delete_ns[4] = {0, 0, 0, 0};   // phases of this thread's last bulk edge delete
+int fh_last_edge_delete_phases_ns(uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_last_edge_delete_ns[k];
+    return 0;
+}
+int fh_graph_delete_edges_bulk(fh_graph* g, const uint64_t* types, const uint64_t* srcs, const uint64_t* dsts, const uint64_t* edge_ids,
+                               uint64_t n_edges, uint64_t** ids, uint64_t** out_srcs, uint64_t** out_dsts, uint64_t* n,
+                               uint64_t stats[5], uint64_t** per_type, uint64_t* n_types) {
+    return guard([&] {
+        EdgeDeleteStats es;
+        auto rels = g->g.delete_edges_bulk(types, srcs, dsts, edge_ids, n_edges, &es);
+        for (int k = 0; k < 4; ++k) g_last_edge_delete_ns[k] = es.phase_ns[k];
+        std::vector<u64> i(rels.size()), s(rels.size()), d(rels.size());
+        for (size_t k = 0; k < rels.size(); ++k) { i[k] = rels[k][0]; s[k] = rels[k][1]; d[k] = rels[k][2]; }
+        *ids = hand(i);
+        *out_srcs = hand(s);
+        *out_dsts = hand(d);
+        *n = rels.size();
+        if (stats) {
+            stats[0] = es.edges_named; stats[1] = es.edges_removed; stats[2] = es.pairs_emptied;
+            stats[3] = es.pairs_demoted; stats[4] = es.adjacency_entries;
+        }
+        if (per_type) {
+            *per_type = hand(es.per_type);
+            *n_types = es.per_type.size();
+        }
+        return 0;
+    });
+}
 int fh_tensor_edge_count(fh_graph* g, uint64_t type_id, uint64_t* out) {
     return guard([&] { *out = g->g.relationship_tensors().at(type_id).edge_count(); return 0; });
 }

@@ -133,6 +133,90 @@ std::vector<std::array<u64, 3>> Graph::delete_nodes_bulk(const std::vector<u64>&
     return out;
 }
 
+std::vector<std::array<u64, 3>> Graph::delete_edges_bulk(const u64* types, const u64* srcs, const u64* dsts, const u64* ids, u64 n,
+                                                         EdgeDeleteStats* stats) {
+    std::vector<std::array<u64, 3>> out;
+    EdgeDeleteStats es;
+    es.per_type.assign(tensors_.size(), 0);
+    es.edges_named = n;
+    // nothing moves before the whole batch is known to be addressable
+    bool one_type = true;
+    for (u64 k = 0; k < n; ++k) {
+        if (types[k] >= tensors_.size())
+            throw GrbError(FGPU_INVALID, "delete_edges_bulk: edge " + std::to_string(k) + " names the unknown relationship type " +
+                                             std::to_string(types[k]));
+        if (srcs[k] >= n_ || dsts[k] >= n_)
+            throw GrbError(FGPU_INVALID, "delete_edges_bulk: edge " + std::to_string(k) + " = (" + std::to_string(srcs[k]) + ", " +
+                                             std::to_string(dsts[k]) + ") is at or past the capacity " + std::to_string(n_));
+        one_type = one_type && types[k] == types[0];
+    }
+    // group by type (graph.rs:2285-2301); a batch of one type is handed on as it came
+    std::map<u64, std::vector<u64>> by_type;   // type id -> positions in the batch, in input order
+    if (n && one_type) by_type[types[0]];
+    else
+        for (u64 k = 0; k < n; ++k) by_type[types[k]].push_back(k);
+    std::vector<std::pair<u64, u64>> cand;   // pairs some tensor emptied
+    RemoveCounts rc;
+    std::vector<u64> gs, gd, gi;
+    for (auto& grp : by_type) {
+        const u64 t = grp.first;
+        const std::vector<u64>& pos = grp.second;
+        const u64 cnt = one_type ? n : pos.size();
+        const u64 *s = srcs, *d = dsts, *i = ids;
+        if (!one_type) {
+            gs.resize(cnt); gd.resize(cnt); gi.resize(cnt);
+            for (size_t k = 0; k < cnt; ++k) { gs[k] = srcs[pos[k]]; gd[k] = dsts[pos[k]]; gi[k] = ids[pos[k]]; }
+            s = gs.data(); d = gd.data(); i = gi.data();
+        }
+        auto emptied = tensors_[t].remove_bulk(s, d, i, cnt, &rc);
+        cand.insert(cand.end(), emptied.begin(), emptied.end());
+        es.pairs_emptied += emptied.size();
+        es.pairs_demoted += rc.demoted;
+        const size_t listed0 = out.size();
+        if (rc.hits == rc.removed) {   // as many hitting triples as edges that left: none is repeated
+            for (size_t k = 0; k < cnt; ++k)
+                if (rc.hit[k]) out.push_back({i[k], s[k], d[k]});
+        } else {
+            std::unordered_set<u64> listed;
+            for (size_t k = 0; k < cnt; ++k)
+                if (rc.hit[k] && listed.insert(i[k]).second) out.push_back({i[k], s[k], d[k]});
+        }
+        es.per_type[t] = out.size() - listed0;
+        if (!vec_indexes_.empty())   // every named id leaves the indexes of its type, as delete_edge makes it
+            for (size_t k = 0; k < cnt; ++k) drop_entity_vectors(true, t, i[k]);
+    }
+    es.edges_removed = out.size();
+    for (int k = 0; k < 3; ++k) es.phase_ns[k] = rc.phase_ns[k];
+    const u64 t0 = bulk_clock_ns();
+    std::sort(cand.begin(), cand.end());
+    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+    if (!cand.empty() && tensors_.size() > 1) {   // another type may still connect the pair: one batched probe per tensor
+        std::vector<u64> cs(cand.size()), cd(cand.size());
+        for (size_t k = 0; k < cand.size(); ++k) { cs[k] = cand[k].first; cd[k] = cand[k].second; }
+        std::vector<uint8_t> held(cand.size(), 0), present;
+        for (auto& t : tensors_) {
+            t.contains_batch(cs, cd, present);
+            for (size_t k = 0; k < cand.size(); ++k) held[k] |= present[k];
+        }
+        size_t left = 0;
+        for (size_t k = 0; k < cand.size(); ++k)
+            if (!held[k]) cand[left++] = cand[k];
+        cand.resize(left);
+    }
+    if (!cand.empty()) {
+        std::vector<u64> mr(cand.size()), mc(cand.size());
+        for (size_t k = 0; k < cand.size(); ++k) { mr[k] = cand[k].first; mc[k] = cand[k].second; }
+        Matrix mask(*ctx_, Type::Bool, n_, n_);
+        mask.build(mr, mc);
+        const u64 before = adj_.nvals();
+        adj_.remove_mask(mask);
+        es.adjacency_entries = before - adj_.nvals();
+    }
+    es.phase_ns[3] = bulk_clock_ns() - t0;
+    if (stats) *stats = es;
+    return out;
+}
+
 void Graph::new_version() {
     adj_ = adj_.dup();
     labels_ = labels_.dup();

@@ -289,6 +289,23 @@ struct DetachStats {
     // [1] expanding and ordering their lists, [2] the label matrix, [3] the adjacency
     u64 phase_ns[4] = {0, 0, 0, 0};
 };
+// What Tensor::remove_bulk did beside the emptied pairs it returns
+struct RemoveCounts {
+    std::vector<uint8_t> hit;    // per triple of the batch: it named a stored edge (every duplicate of one too)
+    u64 hits = 0;                // the ones in `hit`
+    u64 removed = 0;             // edges that left the tensor: hits, a repeated triple counted once
+    u64 emptied_multi = 0;       // multi-edge pairs among the emptied ones
+    u64 demoted = 0;             // multi-edge pairs left with one edge, stored inline again
+    u64 phase_ns[3] = {0, 0, 0}; // host clock: [0] gathering the me rows, [1] fold + fgpu_edges_remove + adoption, [2] rewriting me
+};
+// What Graph::delete_edges_bulk did, in the shape of DetachStats
+struct EdgeDeleteStats {
+    u64 edges_named = 0, edges_removed = 0, pairs_emptied = 0, pairs_demoted = 0, adjacency_entries = 0;
+    std::vector<u64> per_type;   // edges removed per relationship type
+    // host clock, ns (a measurement hook, tools/bench_paths.py edel): [0] gathering the me rows, [1] the tensors' folds and
+    // fgpu_edges_remove calls, [2] rewriting me, [3] the adjacency
+    u64 phase_ns[4] = {0, 0, 0, 0};
+};
 constexpr u64 GrB_INDEX_MAX = (1ull << 60) - 1;          // tensor.rs:136
 u64 compound_key(u64 src, u64 dst);                      // tensor.rs:154-163 (throws when an id needs > 32 bits)
 u64 bulk_clock_ns();                                     // the host clock of BulkStats::phase_ns
@@ -335,6 +352,18 @@ class Tensor {
     std::vector<std::array<u64, 3>> detach_nodes(const std::vector<u64>& nodes, const std::unordered_set<u64>& skip_ids = {},
                                                  DetachCounts* counts = nullptr);
     std::vector<std::pair<u64, u64>> remove_all(const std::vector<std::array<u64, 3>>& rels);  // :461-657
+    // remove_all's slow path (tensor.rs:497-629) for a whole batch of (src, dst, id) triples, as one device pass: m / dp / dm and
+    // mt are folded as detach_nodes folds them; when the tensor holds multi-edge pairs, ONE probe of m finds the batch's pairs
+    // whose value is MULTI_EDGE and their me rows go along, sorted unique by key (no walk of the whole map); ONE
+    // fgpu_edges_remove decides every triple; when anything hit its results are adopted as the bases — the tensor ends folded,
+    // no tombstone is left — and the supplied me rows lose the taken ids, a row left with fewer than 2 is erased (its pair was
+    // demoted or emptied on the device).  Returns the pairs left without an edge, ascending in (src, dst).  A removal applies
+    // only where the id is there: an unknown id, an id of another pair and an absent pair change nothing, a repeated triple
+    // counts once — unlike remove_all's no-multi fast path, which drops the pair whatever the id.  A coordinate at or past its
+    // dimension throws before anything changed.  Versions dup()ed earlier keep the bases they share.
+    std::vector<std::pair<u64, u64>> remove_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, RemoveCounts* counts = nullptr);
+    // effective presence of every pair (eff_get(src, dst).has_value()): three device probes for the whole list
+    void contains_batch(const std::vector<u64>& srcs, const std::vector<u64>& dsts, std::vector<uint8_t>& present) const;
     bool has_multi_edge() const { return !me_.empty(); }
     void resize(u64 nrows, u64 ncols);                                     // :659-726
     void flush();                                                          // :741-797
@@ -451,6 +480,14 @@ class Graph {
     // before anything changed.
     std::vector<std::array<u64, 3>> delete_nodes_bulk(const std::vector<u64>& nodes, const std::vector<u64>& skip_ids = {},
                                                       DetachStats* stats = nullptr);
+    // bulk DELETE r (the shape of Graph::delete_relationships, graph.rs:2303-2372): the n edges (types, srcs, dsts, ids)[k] are
+    // grouped by type and each group goes through Tensor::remove_bulk, in ascending type id; every named id leaves the vector
+    // indexes of its type as delete_edge makes it; the pairs some tensor emptied and no tensor still holds leave the adjacency
+    // through one remove_mask.  Returns the removed (edge id, src, dst): types ascending, input order within a type, only the
+    // triples that named a stored edge, a repeated one once.  An unknown type or a node at or past node_cap() throws before
+    // anything changed.
+    std::vector<std::array<u64, 3>> delete_edges_bulk(const u64* types, const u64* srcs, const u64* dsts, const u64* ids, u64 n,
+                                                      EdgeDeleteStats* stats = nullptr);
     void new_version();              // graph.rs:851-890: every matrix dup()s (fold decisions latch here)
     void fold_oversized_deltas();    // graph.rs:2155-2172, called at MVCC commit (mvcc_graph.rs:161-180)
 

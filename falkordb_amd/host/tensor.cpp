@@ -423,6 +423,101 @@ std::vector<std::pair<u64, u64>> Tensor::remove_all(const std::vector<std::array
     return emptied;
 }
 
+void Tensor::contains_batch(const std::vector<u64>& srcs, const std::vector<u64>& dsts, std::vector<uint8_t>& present) const {
+    wait_fwd();
+    std::vector<u64> vals;
+    eff_get_batch(m_, dp_.layer(), dm_.layer(), srcs, dsts, present, vals);
+}
+
+std::vector<std::pair<u64, u64>> Tensor::remove_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, RemoveCounts* counts) {
+    std::vector<std::pair<u64, u64>> emptied;
+    if (counts) counts->hit.assign(n, 0);
+    if (n == 0) return emptied;
+    for (u64 k = 0; k < n; ++k)
+        if (srcs[k] >= m_.nrows() || dsts[k] >= m_.ncols())
+            throw GrbError(FGPU_INVALID, "Tensor::remove_bulk: edge (" + std::to_string(srcs[k]) + ", " + std::to_string(dsts[k]) +
+                                             ") is outside the tensor");
+    Context& ctx = m_.ctx();
+    fgpu_ctx* c = ctx.raw();
+    u64 t0 = bulk_clock_ns();
+    // fold first, as detach_nodes does: the device pass reads m and mt alone
+    flush();
+    dp_.wait();
+    dm_.wait();
+    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
+        dp_.latch(true);
+        dm_.latch(true);
+        needs_flush_ = true;
+        flush();
+    }
+    mt_.fold_all();
+    const u64 fold_ns = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    // the me rows of the batch's multi-edge pairs, sorted unique by key: one probe of the folded base, then one find per such pair
+    std::vector<u64> key, off{0}, run;
+    std::vector<std::map<u64, std::vector<u64>>::iterator> rows;
+    if (has_multi_edge()) {
+        std::vector<uint8_t> in_m;
+        std::vector<u64> mv;
+        m_.probe(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), in_m, &mv);
+        for (u64 k = 0; k < n; ++k)
+            if (in_m[k] && mv[k] == MULTI_EDGE) key.push_back(compound_key(srcs[k], dsts[k]));
+        std::sort(key.begin(), key.end());
+        key.erase(std::unique(key.begin(), key.end()), key.end());
+        size_t kept = 0;
+        for (u64 x : key) {
+            auto it = me_.find(x);
+            if (it == me_.end() || it->second.size() < 2) continue;   // (the device reports the pair when a triple needs its row)
+            key[kept++] = x;
+            rows.push_back(it);
+            run.insert(run.end(), it->second.begin(), it->second.end());
+            off.push_back(run.size());
+        }
+        key.resize(kept);
+    }
+    std::vector<uint8_t> taken(run.size(), 0), hit_local;
+    std::vector<uint8_t>& hit = counts ? counts->hit : hit_local;
+    hit.assign(n, 0);
+    const u64 gather_ns = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    fgpu_mat *mo = nullptr, *mto = nullptr;
+    EngineArray er(c), ec(c);
+    u64 n_emp = 0, st[8] = {0};
+    check(fgpu_edges_remove(c, m_.snapshot(), mt_.m().snapshot(), srcs, dsts, ids, n, key.data(), off.data(), run.data(), key.size(),
+                            &mo, &mto, hit.data(), taken.data(), &er.p, &ec.p, &n_emp, st),
+          "Tensor::remove_bulk");
+    Matrix new_m = Matrix::adopt(ctx, Type::UInt64, mo);
+    Matrix new_mt = Matrix::adopt(ctx, Type::Bool, mto);
+    if (st[0]) {   // (nothing hit: the bases stay the snapshots they are)
+        m_ = new_m;
+        mt_ = VersionedMatrix::from_matrix(new_mt);
+    }
+    emptied.reserve(n_emp);
+    for (u64 k = 0; k < n_emp; ++k) emptied.push_back({er.p[k], ec.p[k]});
+    const u64 device_ns = fold_ns + (bulk_clock_ns() - t0);
+    t0 = bulk_clock_ns();
+    for (size_t r = 0; r < rows.size(); ++r) {
+        std::vector<u64>& v = rows[r]->second;
+        const uint8_t* tk = taken.data() + off[r];
+        size_t left = 0;
+        for (size_t j = 0; j < v.size(); ++j)
+            if (!tk[j]) v[left++] = v[j];
+        if (left == v.size()) continue;
+        if (left < 2) me_.erase(rows[r]);   // demoted (the survivor is inline in m now) or emptied
+        else v.resize(left);
+    }
+    if (counts) {
+        counts->hits = st[0];
+        counts->removed = (n_emp - st[2]) + (u64)std::count(taken.begin(), taken.end(), (uint8_t)1);
+        counts->emptied_multi = st[2];
+        counts->demoted = st[3];
+        counts->phase_ns[0] += gather_ns;
+        counts->phase_ns[1] += device_ns;
+        counts->phase_ns[2] += bulk_clock_ns() - t0;
+    }
+    return emptied;
+}
+
 void Tensor::resize(u64 nrows, u64 ncols) {
     if (nrows < m_.nrows() || ncols < m_.ncols()) flush();
     m_.wait();

@@ -123,6 +123,22 @@ int fh_graph_delete_nodes_bulk(fh_graph* g, const uint64_t* nodes, uint64_t n_no
  * [0] the tensors' fgpu_nodes_detach calls with their folds, [1] expanding and ordering the lists on the host, [2] the label
  * matrix, [3] the adjacency */
 int fh_last_detach_phases_ns(uint64_t out[4]);
+/* DELETE r of n_edges edges in one call (the shape of Graph::delete_relationships, graph.rs:2268-2373): edge k is (types[k],
+ * srcs[k], dsts[k], edge_ids[k]).  The batch is grouped by type; per type, ascending, one fgpu_edges_remove takes the named edges
+ * out of the tensor, which ends folded: a single-edge pair leaves, a multi-edge pair shrinks, is demoted to an inline id or
+ * leaves.  Every named id leaves the vector indexes of its type; the pairs a tensor emptied and no type still connects leave the
+ * adjacency.  A removal applies only where the id is there: an unknown id, an id of another pair and an absent pair change nothing.
+ * ids / out_srcs / out_dsts (malloc'ed, fh_free; n of each) are the removed edges: types ascending, input order within a type,
+ * a repeated edge once.  stats (nullable): [0] edges named, [1] edges removed, [2] pairs emptied (summed over the types),
+ * [3] multi-edge pairs demoted, [4] adjacency entries removed.  per_type (nullable; malloc'ed, n_types entries) = edges removed
+ * per type.  An unknown type or a node id at or past the capacity returns the engine's code before anything changed. */
+int fh_graph_delete_edges_bulk(fh_graph* g, const uint64_t* types, const uint64_t* srcs, const uint64_t* dsts, const uint64_t* edge_ids,
+                               uint64_t n_edges, uint64_t** ids, uint64_t** out_srcs, uint64_t** out_dsts, uint64_t* n,
+                               uint64_t stats[5], uint64_t** per_type, uint64_t* n_types);
+/* host-clock phases (ns) of this thread's last fh_graph_delete_edges_bulk (a measurement hook, tools/bench_paths.py edel):
+ * [0] gathering the multi-edge rows of the touched pairs, [1] the tensors' folds and fgpu_edges_remove calls, [2] rewriting the
+ * multi-edge map, [3] the adjacency */
+int fh_last_edge_delete_phases_ns(uint64_t out[4]);
 int fh_graph_delete_edge(fh_graph* g, uint64_t type_id, uint64_t src, uint64_t dst, uint64_t edge_id);
 /* MVCC commit of every matrix: dup() (fold decision) then fold_oversized, as mvcc_graph.rs:161-180 does */
 int fh_graph_commit(fh_graph* g);

@@ -249,6 +249,38 @@ fgpu_info fgpu_nodes_detach(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt
                             int sides, fgpu_mat** m_out, fgpu_mat** mt_out, uint64_t** rem_row, uint64_t** rem_col,
                             uint64_t** rem_val, uint64_t* n_rem, uint64_t* n_rem_out, uint64_t stats[8]);
 
+/* DELETE r of a batch of edges on one relationship type (Graph::delete_relationships over Tensor::remove_all, graph.rs:2268-2373,
+ * tensor.rs:454-629): n triples (srcs, dsts, ids)[k] leave the tensor's matrices.
+ *   m      the tensor's folded UINT64 base: a value is an inline edge id or FGPU_MULTI_EDGE; mt its BOOL transposed pattern;
+ *   multi_key / multi_off / multi_ids  the multi-edge rows of the pairs the caller believes the batch touches, in the shape
+ *          fgpu_edges_build returns them: n_multi keys src << 32 | dst strictly ascending, multi_off[0] = 0, every run at least 2
+ *          ids long and strictly ascending.  A key that is not a FGPU_MULTI_EDGE entry of m is ignored.
+ * The slow path of tensor.rs:497-629 restated as set operations (it applies a removal only where the id is there, so the order
+ * of the batch does not matter): a triple HITS when (src, dst) is stored in m and either its inline value equals id, or the value
+ * is FGPU_MULTI_EDGE and id is in the pair's supplied row.  hit[k] (the caller's n bytes, nullable) = 1 for every hitting triple,
+ * each duplicate of one included; multi_taken[j] (the caller's multi_off[n_multi] bytes, required when n_multi > 0) = 1 iff some
+ * triple hit multi_ids[j].  A single-edge pair that is hit leaves m and mt.  A multi-edge pair with 2 or more ids left keeps
+ * FGPU_MULTI_EDGE; with 1 left it is demoted: m_out stores the surviving id inline; with 0 left it leaves m and mt.  An unknown
+ * id, an id of another pair and an absent pair change nothing.  This is the reference's result whenever every triple names a
+ * stored edge, which Graph::delete_relationships guarantees by resolving the ids first.  On an unknown id the reference's
+ * no-multi fast path (tensor.rs:467-495) drops the pair whatever the id; this call deliberately does not.
+ * m_out / mt_out are NEW snapshots (fgpu_mat_free) with sorted unique rows, stored hypersparse exactly when fgpu_mat_from_coo
+ * would store that many populated rows of that dimension so; m and mt are untouched.  emp_row / emp_col [n_emp] are the pairs
+ * that left m, ascending in (src, dst): engine-owned (fgpu_free), NULL when n_emp == 0.  n == 0 gives copies of the inputs.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated and the context still usable, for: a coordinate at or past its
+ * dimension; n >= 2^32 - 1; an id equal to FGPU_MULTI_EDGE; m not valued; mt missing, valued or of other dimensions than
+ * ncols x nrows; keys not strictly ascending, a run shorter than 2, ids not ascending in a run; a triple whose pair holds
+ * FGPU_MULTI_EDGE in m with no row supplied for it (counted on the device and read back with the totals).
+ * stats (nullable): [0] triples that hit, [1] pairs emptied, [2] of those, pairs that were multi-edge, [3] pairs demoted,
+ * [4] entries kept in m_out, [5] entries kept in mt_out, [6] triples whose pair is absent, [7] triples whose pair is stored but
+ * whose id is unknown.
+ * Work: a lane per triple (binary searches), a lane per supplied row, a lane per stored entry of m and of mt; every output is
+ * placed by a scan. */
+fgpu_info fgpu_edges_remove(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt, const uint64_t* srcs, const uint64_t* dsts,
+                            const uint64_t* ids, uint64_t n, const uint64_t* multi_key, const uint64_t* multi_off,
+                            const uint64_t* multi_ids, uint64_t n_multi, fgpu_mat** m_out, fgpu_mat** mt_out, uint8_t* hit,
+                            uint8_t* multi_taken, uint64_t** emp_row, uint64_t** emp_col, uint64_t* n_emp, uint64_t stats[8]);
+
 /* Host CSR (what GxB_unload_Matrix_into_Container yields: p, i, x [, h];
  * matrix.rs:508-546) -> device snapshot.  rowptr has nvec+1 entries when
  * `hyper_rows` (sorted non-empty row ids, nvec of them) is given, else

@@ -77,7 +77,16 @@
           pattern) for 1 % and 10 % of the nodes, with list and mt and on m alone, its device phases, beside one fgpu_mat_merge
           of the same matrix with 0.1 % deltas.  `detach <scale>`: the twin comparison at that scale only.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  edel    the host layer's explicit edge delete: Graph::delete_edges_bulk (one fgpu_edges_remove per tensor, one adjacency mask)
+          against the path that existed before it — one delete_edge per edge — on twin graphs of the distinct RMAT-18 and
+          RMAT-20 edges loaded with bulk_insert_edges, the same seeded, shuffled 10 % of the edges, a host clock around delete +
+          commit.  The bulk twin: one warm-up, median of 3, a fresh twin each, with the host phases
+          (fh_last_edge_delete_phases_ns).  The edge-by-edge twin: one run under a 10 s deadline, us per edge and the
+          extrapolation.  Then the raw fgpu_edges_remove on the RMAT-22 tensor of the load leg (UINT64 base, transposed pattern,
+          the multi-edge rows of the touched pairs) for a seeded 1 % and 10 % of the raw tuples, its device phases, beside one
+          fgpu_mat_merge(m, NULL, dm) whose dm holds the same pairs.  `edel <scale>`: the twin comparison at that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -479,6 +488,120 @@ def bench_detach(scales=(18, 20), small_scale=12, raw_scale=22, deadline_s=10.0)
                                   "more call (flags + scans of both passes, both emissions, the list's read-back); the merge is "
                                   "fgpu_mat_merge of the same matrix with 0.1 % valued adds and 0.1 % tombstones, median of 5"}),
               flush=True)
+
+
+def bench_edel(scales=(18, 20), raw_scale=22, deadline_s=10.0):
+    from falkordb_amd import host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+
+    def loaded(n, r, ci, ids):
+        g = host.Graph(hc, n)
+        t = g.add_type("KNOWS")
+        g.bulk_insert_edges(t, r, ci, ids)
+        g.commit()
+        return g, t
+
+    for scale in scales:
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        ids = np.arange(len(ci), dtype=np.uint64)
+        A.free()
+        k = np.random.default_rng(100).choice(len(ci), len(ci) // 10, replace=False)    # a seeded tenth of the edges, shuffled
+        tk = np.zeros(len(k), dtype=np.uint64)
+        ts = []
+        for rep in range(4):                     # (rep 0 warms up; every rep deletes from a freshly loaded twin)
+            g, t = loaded(n, r, ci, ids)
+            t0 = time.perf_counter()
+            rels, st = g.delete_edges_bulk(tk, r[k], ci[k], ids[k], stats=True, as_arrays=True)
+            t1 = time.perf_counter()
+            g.commit()
+            t2 = time.perf_counter()
+            assert st["edges_removed"] == len(k) == len(rels[0]) and g.tensor_edge_count(t) == len(ci) - len(k)
+            ts.append((t2 - t0, t1 - t0, g.last_edge_delete_phases_ms(), st))
+            del rels, g
+        total, call, phases, st = ts[int(np.argsort([x[0] for x in ts[1:]])[1]) + 1]
+        g, t = loaded(n, r, ci, ids)             # the twin: one delete_edge per edge, stopped at the deadline
+        es = list(zip(r[k].tolist(), ci[k].tolist(), ids[k].tolist()))
+        done = 0
+        t0 = time.perf_counter()
+        for s, d, i in es:
+            g.delete_edge(t, s, d, i)
+            done += 1
+            if (done & 63) == 0 and time.perf_counter() - t0 > deadline_s:
+                break
+        finished = done == len(es)
+        if finished:
+            g.commit()
+        dt = time.perf_counter() - t0
+        ref = dt if finished else dt / max(done, 1) * len(es)
+        print(json.dumps({"path": "graph_edge_delete", "scale": scale, "edges": len(ci), "edges_deleted": len(k),
+                          "delete_edges_bulk": {"s": round(total, 5), "call_s": round(call, 5),
+                                                "us_per_edge": round(total / len(k) * 1e6, 5),
+                                                "host_phases_ms": {k_: round(v_, 3) for k_, v_ in phases.items()},
+                                                "stats": {k_: v_ for k_, v_ in st.items() if k_ != "per_type"}},
+                          "edge_by_edge": {"edges_done": done, "finished": finished, "s": round(dt, 3),
+                                           "us_per_edge": round(dt / max(done, 1) * 1e6, 2), "s_extrapolated": round(ref, 2)},
+                          "quotient": round(ref / total, 1),
+                          "note": "twin graphs loaded with bulk_insert_edges + commit in one process; host clock around delete + "
+                                  "commit; bulk: one warm-up, median of 3, a fresh twin each; edge by edge: one run, stopped at "
+                                  "its deadline (finished = false: s_extrapolated = us_per_edge x edges, and the quotient uses it)"}),
+              flush=True)
+        del r, ci, ids, g
+    if not raw_scale:
+        return
+    import oracle
+    u, v = (np.asarray(x, dtype=np.uint64) for x in oracle.rmat_edges(raw_scale))
+    n = 1 << raw_scale
+    ids = np.arange(len(u), dtype=np.uint64)
+    fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, ids)
+    mkey, moff, mids = np.array(mkey), np.array(moff), np.array(mids)
+    for frac in (0.01, 0.1):
+        k = np.random.default_rng(int(frac * 1000)).choice(len(u), int(len(u) * frac), replace=False)
+        s, d, i = u[k], v[k], ids[k]
+        t0 = time.perf_counter()
+        keys = np.unique((s << np.uint64(32)) | d)                       # the multi-edge rows of the touched pairs, as the host layer gathers them
+        at = np.searchsorted(mkey, keys)
+        at = at[(at < len(mkey)) & (mkey[np.minimum(at, len(mkey) - 1)] == keys)]
+        lens = (moff[at + 1] - moff[at]).astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        pos = np.repeat(moff[at].astype(np.int64) - off[:-1].astype(np.int64), lens) + np.arange(int(off[-1]))
+        rows = (mkey[at], off, mids[pos])
+        t_gather = time.perf_counter() - t0
+        t_call, res = timed(ctx, lambda: engine.edges_remove(ctx, fwd, bwd, s, d, i, *rows, stats=True), reps=3, warm=1)
+        st = res[-1]
+        del res
+        ctx.prof_enable(True)
+        res = engine.edges_remove(ctx, fwd, bwd, s, d, i, *rows)
+        ctx.sync()
+        dev = {}
+        for p in ctx.prof_read():
+            if p["kernel"].startswith(("er_", "dt_")):
+                dev[p["kernel"]] = round(dev.get(p["kernel"], 0.0) + p["ms"], 3)
+        ctx.prof_enable(False)
+        del res
+        dm = ctx.mat_from_coo(n, n, s, d)
+        t_merge, merged = timed(ctx, lambda: fwd.merge(None, dm), reps=5, warm=2)
+        nnz_merged = merged.nvals
+        del merged
+        print(json.dumps({"path": "edges_remove_raw", "scale": raw_scale, "nnz": fwd.nvals, "frac": frac, "triples": len(k),
+                          "multi_rows_supplied": len(at), "ids_in_supplied_rows": int(off[-1]), "stats": st,
+                          "ms_call": round(t_call * 1e3, 3), "ms_numpy_row_gather": round(t_gather * 1e3, 3),
+                          "device_phases_ms": dev, "ms_call_outside_device_phases": round(t_call * 1e3 - sum(dev.values()), 3),
+                          "ms_fgpu_mat_merge_m_minus_dm": round(t_merge * 1e3, 3),
+                          "nnz_dm": dm.nvals, "nnz_merged": nnz_merged, "quotient_call_over_merge": round(t_call / t_merge, 2),
+                          "note": "the UINT64 tensor base of the raw RMAT stream (fgpu_edges_build), its transposed pattern and the "
+                                  "multi-edge rows of the touched pairs; median of 3 synchronised calls after 1 warm-up, host-side "
+                                  "validation, H2D of triples and rows and the read-back of hit / taken / emptied included; "
+                                  "device_phases = HIP events of one more call (er_h2d = the staged uploads, dt_emit = both emissions, er_readback = "
+                                  "emptied pairs, taken and hit flags); outside them: validation and narrowing of the triples on the host, "
+                                  "allocation, the row-pointer passes; the merge is "
+                                  "fgpu_mat_merge(m, NULL, dm) with dm the BOOL matrix of the same pairs, median of 5 after 2 warm-up: "
+                                  "it drops the whole pair where the call removes single edges"}), flush=True)
+        del dm
 
 
 def bench_host(scale):
@@ -1096,3 +1219,5 @@ if __name__ == "__main__":
         bench_load(*(((scale,), 0) if scale else ()))
     if what == "detach":                         # (edge-by-edge deletes up to their deadlines: not part of `all`)
         bench_detach(*(((), scale, 0) if scale else ()))
+    if what == "edel":                           # (edge-by-edge deletes up to their deadlines: not part of `all`)
+        bench_edel(*(((scale,), 0) if scale else ()))
