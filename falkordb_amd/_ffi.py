@@ -59,6 +59,8 @@ SIGNATURES = {
                                       C.POINTER(u64p), u64p, u64p, u64p]),
     "fgpu_edges_remove": (C.c_int32, [vp, vp, vp, u64p, u64p, u64p, C.c_uint64, u64p, u64p, u64p, C.c_uint64, vpp, vpp,
                                       u8p, u8p, C.POINTER(u64p), C.POINTER(u64p), u64p, u64p]),
+    "fgpu_edges_union": (C.c_int32, [vp, vp, vp, u64p, u64p, u64p, C.c_uint64, vp, vp, u64p, u64p, u64p, C.c_uint64, vpp, vpp,
+                                     C.POINTER(u64p), C.POINTER(u64p), C.POINTER(u64p), u64p, u64p]),
     "fgpu_mat_from_csr": (C.c_int32, [vp, vpp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int,
                                       u64p, u64p, C.c_uint64]),
     "fgpu_mat_rmat": (C.c_int32, [vp, vpp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),

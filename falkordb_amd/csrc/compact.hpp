@@ -8,7 +8,8 @@
 //   rows     rowptr'[r] = E[rowptr[r]], a lane per row — no per-row loop; a hypersparse input goes through its hrows, and the
 //            output is hypersparse exactly when fgpu_mat_from_coo would store that many populated rows so (mat_prefer_hyper)
 //
-// The kernels are static: each of the two translation units carries its own copy.
+// The kernels are static: each translation unit carries its own copy.  edges_union.hip (fgpu_edges_union) includes this file
+// for the wordrow index alone — over its batch's entries and over the offsets of its out rows.
 #pragma once
 #include "common.hpp"
 

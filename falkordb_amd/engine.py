@@ -715,6 +715,34 @@ def edges_remove(ctx: Context, m: Mat, mt: "Mat | None", srcs, dsts, ids, multi_
     return out + ([int(x) for x in st],) if stats else out
 
 
+def _rows(name, key, off, ids):
+    key, off, ids = _u64(key).reshape(-1), _u64(off).reshape(-1), _u64(ids).reshape(-1)
+    if len(off) != len(key) + 1 or (len(key) and int(off[-1]) != len(ids)):
+        raise ValueError(f"edges_union: {name}_off does not describe {name}_key / {name}_ids")
+    return key, off, ids
+
+
+def edges_union(ctx: Context, m: Mat, mt: "Mat | None", a_key, a_off, a_ids, fwd: Mat, bwd: "Mat | None", b_key, b_off, b_ids,
+                stats: bool = False):
+    """fgpu_edges_union: the tensor base m and its transposed pattern mt joined with one built batch (fwd, bwd, b rows: what
+    edges_build returned); a_key / a_off / a_ids are the multi-edge rows of the pairs of m the batch touches.  Returns (m_out,
+    mt_out, o_key, o_off, o_ids[, stats]): a pair new to m enters with fwd's value, a pair stored in both holds MULTI_EDGE and
+    its ids are o_ids[o_off[r] : o_off[r + 1]] — the ascending merge of both sides — under o_key[r]; stats the eight counters of
+    include/fgpu.h when stats=True."""
+    ak, ao, ai = _rows("a", a_key, a_off, a_ids)
+    bk, bo, bi = _rows("b", b_key, b_off, b_ids)
+    mout, mtout = C.c_void_p(), C.c_void_p()
+    ok, oo, oi = u64p(), u64p(), u64p()
+    no = C.c_uint64()
+    st = np.zeros(8, dtype=np.uint64)
+    check(ctx.lib.fgpu_edges_union(ctx._h, m._h, mt._h if mt is not None else None, _p(ak), _p(ao), _p(ai), len(ak), fwd._h,
+                                   bwd._h if bwd is not None else None, _p(bk), _p(bo), _p(bi), len(bk), C.byref(mout),
+                                   C.byref(mtout), C.byref(ok), C.byref(oo), C.byref(oi), C.byref(no), _p(st)))
+    off = ctx._take(oo, no.value + 1)
+    out = (Mat(ctx, mout), Mat(ctx, mtout), ctx._take(ok, no.value), off, ctx._take(oi, int(off[-1])))
+    return out + ([int(x) for x in st],) if stats else out
+
+
 def maxflow(ctx: Context, C_: Mat, src: int, sink: int, stats: bool = False):
     """fgpu_maxflow: LAGr_MaxFlow's result for algo.maxFlow over the capacity matrix C_ — a valued snapshot carries one binary64
     bit pattern per entry, a BOOL one means capacity 1.0; diagonal entries and capacities <= 0 are ignored, a NaN or infinite

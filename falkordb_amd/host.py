@@ -406,6 +406,23 @@ class Graph:
         _ck(self.L.fh_last_bulk_phases_ns(ns))
         return dict(zip(("edges_build", "fold_adopt", "me_fill", "adjacency_union"), (x / 1e6 for x in ns)))
 
+    def append_edges_bulk(self, type_id, srcs, dsts, ids):
+        """fh_graph_append_edges_bulk: one type's batch onto a graph that holds edges, every edge through the device (pairs that
+        hold an edge already are promoted or extended there); returns what it did as a dict."""
+        s, d, i = _u64(srcs).reshape(-1), _u64(dsts).reshape(-1), _u64(ids).reshape(-1)
+        if not (len(s) == len(d) == len(i)):
+            raise ValueError("append_edges_bulk: srcs, dsts and ids differ in length")
+        st = (C.c_uint64 * 8)()
+        _ck(self.L.fh_graph_append_edges_bulk(self.h, C.c_uint64(type_id), _p(s), _p(d), _p(i), C.c_uint64(len(s)), st))
+        return dict(zip(("edges", "distinct_pairs", "multi_pairs", "colliding_pairs", "promoted_pairs", "extended_pairs", "me_rows",
+                         "host_sorted_runs"), (int(x) for x in st)))
+
+    def last_append_phases_ms(self):
+        """fh_last_append_phases_ns: host-clock ms of the last append_edges_bulk of this thread, by phase."""
+        ns = (C.c_uint64 * 4)()
+        _ck(self.L.fh_last_append_phases_ns(ns))
+        return dict(zip(("edges_build", "fold_union", "me_rewrite", "adjacency_union"), (x / 1e6 for x in ns)))
+
     def delete_nodes_bulk(self, nodes, skip_ids=(), stats=False, as_arrays=False):
         """fh_graph_delete_nodes_bulk: DETACH DELETE of a node set in one call.  Returns the removed edges as a list of
         (edge id, src, dst) in the reference's order (ids in skip_ids are removed too, but not listed) — as three uint64

@@ -310,6 +310,24 @@ int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* sr
     });
 }
 
+static thread_local uint64_t g_last_append_ns[4] = {0, 0, 0, 0};   // phases of this thread's last bulk append
+int fh_last_append_phases_ns(uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_last_append_ns[k];
+    return 0;
+}
+int fh_graph_append_edges_bulk(fh_graph* g, uint64_t type_id, const uint64_t* srcs, const uint64_t* dsts, const uint64_t* ids,
+                               uint64_t n, uint64_t stats[8]) {
+    return guard([&] {
+        AppendStats as = g->g.append_edges_bulk(type_id, srcs, dsts, ids, n);
+        for (int k = 0; k < 4; ++k) g_last_append_ns[k] = as.phase_ns[k];
+        if (stats) {
+            stats[0] = as.edges; stats[1] = as.distinct_pairs; stats[2] = as.multi_pairs; stats[3] = as.colliding;
+            stats[4] = as.promoted; stats[5] = as.extended; stats[6] = as.me_rows; stats[7] = as.host_sorted_runs;
+        }
+        return 0;
+    });
+}
+
 static thread_local uint64_t g_last_detach_ns[4] = {0, 0, 0, 0};   // phases of this thread's last bulk node delete
 int fh_last_detach_phases_ns(uint64_t out[4]) {
     for (int k = 0; k < 4; ++k) out[k] = g_last_detach_ns[k];

@@ -88,6 +88,15 @@ BulkStats Graph::bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, c
     return bs;
 }
 
+AppendStats Graph::append_edges_bulk(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n) {
+    std::optional<Matrix> built;
+    AppendStats as = tensors_.at(type).append_bulk(srcs, dsts, ids, n, &built);
+    const u64 t0 = bulk_clock_ns();
+    if (built) adj_.union_base(*built);
+    as.phase_ns[3] = bulk_clock_ns() - t0;
+    return as;
+}
+
 std::vector<std::array<u64, 3>> Graph::delete_nodes_bulk(const std::vector<u64>& nodes, const std::vector<u64>& skip_ids,
                                                          DetachStats* stats) {
     std::vector<std::array<u64, 3>> out;

@@ -274,6 +274,15 @@ struct BulkStats {
     // and adopting / merging the built pieces (or the whole fallback), [2] filling me, [3] the adjacency union
     u64 phase_ns[4] = {0, 0, 0, 0};
 };
+// What a bulk append did (Tensor::append_bulk / Graph::append_edges_bulk): edges = n, the batch's distinct and multi-edge pairs
+// (fgpu_edges_build's stats [0], [1]), the pairs that collided with a stored one and how (fgpu_edges_union's stats [1..3]), the me
+// rows written, and the runs the build had the host sort (its stats [6])
+struct AppendStats {
+    u64 edges = 0, distinct_pairs = 0, multi_pairs = 0, colliding = 0, promoted = 0, extended = 0, me_rows = 0, host_sorted_runs = 0;
+    // host clock, ns (a measurement hook, tools/bench_paths.py append): [0] the fgpu_edges_build call, [1] the folds, the row
+    // gather and the fgpu_edges_union call, [2] rewriting me, [3] the adjacency union
+    u64 phase_ns[4] = {0, 0, 0, 0};
+};
 // What Tensor::detach_nodes did beside the list it returns (accumulated: a Graph adds every type's into one)
 struct DetachCounts {
     u64 removed = 0;             // edges taken out of the tensor, the skipped ones included
@@ -338,6 +347,15 @@ class Tensor {
                           std::optional<Matrix>* built = nullptr);
     // (the same over the caller's arrays: a load of 2^26 tuples is 1.6 GB that need not be copied into vectors first)
     BulkStats bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built = nullptr);
+    // A bulk batch onto a tensor that may hold edges on the batch's pairs (set_all_from_slices' result, tensor.rs:333-447, for the
+    // whole batch on the device; it never falls back): fgpu_edges_build first, so an invalid batch throws before any layer
+    // moved; the layers are folded as bulk_insert folds them; an empty tensor adopts the built pieces; otherwise, when the tensor
+    // holds multi-edge pairs, ONE probe of m finds the batch's pairs whose value is MULTI_EDGE and their me rows go along, sorted
+    // unique by key; ONE fgpu_edges_union gives the new bases, which are adopted (replaced, never mutated: a dup()ed version or
+    // a matrix built earlier keeps its snapshot), and me takes the batch's rows of new multi-edge pairs and the merged rows of the
+    // colliding ones.  Ends folded.  An id already stored on its pair (the union's FGPU_INVALID) throws with the effective state
+    // unchanged.  `built` (nullable) receives the batch's forward matrix, for the adjacency union.
+    AppendStats append_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built = nullptr);
     // This type's share of Graph::delete_implicit_edges (graph.rs:2386-2494) for the node set `nodes` (any order, duplicates
     // allowed), as one device pass: m / dp / dm and mt are folded, ONE fgpu_nodes_detach takes every entry incident to the nodes
     // out of m and mt and its results are adopted as the bases — the tensor ends folded (dp = dm = 0), no tombstone is left —
@@ -471,6 +489,10 @@ class Graph {
     BulkStats bulk_insert_edges(u64 type, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                                 const std::vector<u64>& ids);
     BulkStats bulk_insert_edges(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n);
+    // CREATE of one type's batch onto a graph that holds edges: Tensor::append_bulk — every edge through the device, whatever
+    // pairs the batch touches — then the adjacency's base U= the batch's pattern.  An invalid batch (a node at or past the
+    // capacity, the marker as an id, a triple twice, an id already stored on its pair) throws with the graph as it was.
+    AppendStats append_edges_bulk(u64 type, const u64* srcs, const u64* dsts, const u64* ids, u64 n);
     // bulk DETACH DELETE (Pending::commit's Graph::delete_nodes + delete_implicit_edges, graph.rs:1698-1772, 2386-2494, as one
     // call): every node gets delete_node's effects; every tensor detach_nodes — the returned list is their lists in ascending
     // type id — and every removed edge leaves the vector indexes as delete_edge makes it; the node x label matrix loses the

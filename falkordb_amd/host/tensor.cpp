@@ -248,6 +248,104 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
     return bs;
 }
 
+AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built) {
+    AppendStats as;
+    if (built) built->reset();
+    if (n == 0) return as;
+    Context& ctx = m_.ctx();
+    fgpu_ctx* c = ctx.raw();
+    // the build reads nothing of the tensor: an invalid batch throws here, before any layer moved
+    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
+    EngineArray bkey(c), boff(c), bids(c);
+    u64 n_b = 0, st[8] = {0};
+    u64 t0 = bulk_clock_ns();
+    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &bkey.p, &boff.p, &bids.p, &n_b, st),
+          "Tensor::append_bulk");
+    Matrix fwd = Matrix::adopt(ctx, Type::UInt64, fwd_h);
+    Matrix bwd = Matrix::adopt(ctx, Type::Bool, bwd_h);
+    as.phase_ns[0] = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    // fold first, as bulk_insert does: the device pass reads m and mt alone
+    flush();
+    dp_.wait();
+    dm_.wait();
+    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
+        dp_.latch(true);
+        dm_.latch(true);
+        needs_flush_ = true;
+        flush();
+    }
+    mt_.fold_all();
+    as.edges = n;
+    as.distinct_pairs = st[0];
+    as.multi_pairs = st[1];
+    as.host_sorted_runs = st[6];
+    if (m_.nvals() == 0) {
+        m_ = fwd;
+        mt_ = VersionedMatrix::from_matrix(bwd);
+        as.phase_ns[1] = bulk_clock_ns() - t0;
+        t0 = bulk_clock_ns();
+        for (u64 r = 0; r < n_b; ++r)
+            me_.insert_or_assign(me_.end(), bkey.p[r], std::vector<u64>(bids.p + boff.p[r], bids.p + boff.p[r + 1]));
+        as.me_rows = n_b;
+        as.phase_ns[2] = bulk_clock_ns() - t0;
+        if (built) *built = fwd;
+        return as;
+    }
+    // the me rows of the batch's pairs that hold MULTI_EDGE, sorted unique by key: one probe of the folded base, then one find each
+    std::vector<u64> akey, aoff{0}, arun;
+    if (has_multi_edge()) {
+        std::vector<uint8_t> in_m;
+        std::vector<u64> mv;
+        m_.probe(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), in_m, &mv);
+        for (u64 k = 0; k < n; ++k)
+            if (in_m[k] && mv[k] == MULTI_EDGE) akey.push_back(compound_key(srcs[k], dsts[k]));
+        std::sort(akey.begin(), akey.end());
+        akey.erase(std::unique(akey.begin(), akey.end()), akey.end());
+        size_t kept = 0;
+        for (u64 x : akey) {
+            auto it = me_.find(x);
+            if (it == me_.end() || it->second.size() < 2) continue;   // (the device reports the pair: it needs the row)
+            akey[kept++] = x;
+            arun.insert(arun.end(), it->second.begin(), it->second.end());
+            aoff.push_back(arun.size());
+        }
+        akey.resize(kept);
+    }
+    fgpu_mat *mo = nullptr, *mto = nullptr;
+    EngineArray okey(c), ooff(c), oids(c);
+    u64 n_o = 0, us[8] = {0};
+    // an id already stored on its pair fails here: the layers are folded, the state they hold is what it was
+    check(fgpu_edges_union(c, m_.snapshot(), mt_.m().snapshot(), akey.data(), aoff.data(), arun.data(), akey.size(), fwd.snapshot(),
+                           bwd.snapshot(), bkey.p, boff.p, bids.p, n_b, &mo, &mto, &okey.p, &ooff.p, &oids.p, &n_o, us),
+          "Tensor::append_bulk");
+    m_ = Matrix::adopt(ctx, Type::UInt64, mo);
+    mt_ = VersionedMatrix::from_matrix(Matrix::adopt(ctx, Type::Bool, mto));
+    as.phase_ns[1] = bulk_clock_ns() - t0;
+    t0 = bulk_clock_ns();
+    // b and o ascend by key, one cursor each: a multi-edge pair only the batch names brings its b row, a colliding pair its o row
+    auto hint = me_.begin();
+    u64 i = 0, j = 0;
+    while (i < n_b || j < n_o) {
+        const u64 kb = i < n_b ? bkey.p[i] : ~0ull, ko = j < n_o ? okey.p[j] : ~0ull;
+        if (ko <= kb) {
+            hint = std::next(me_.insert_or_assign(hint, ko, std::vector<u64>(oids.p + ooff.p[j], oids.p + ooff.p[j + 1])));
+            ++j;
+            if (kb == ko) ++i;
+        } else {
+            hint = std::next(me_.insert_or_assign(hint, kb, std::vector<u64>(bids.p + boff.p[i], bids.p + boff.p[i + 1])));
+            ++i;
+        }
+        ++as.me_rows;
+    }
+    as.phase_ns[2] = bulk_clock_ns() - t0;
+    as.colliding = us[1];
+    as.promoted = us[2];
+    as.extended = us[3];
+    if (built) *built = fwd;
+    return as;
+}
+
 std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nodes, const std::unordered_set<u64>& skip_ids,
                                                      DetachCounts* counts) {
     std::vector<std::array<u64, 3>> out;

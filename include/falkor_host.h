@@ -106,6 +106,21 @@ int fh_graph_bulk_insert_edges(fh_graph* g, uint64_t type_id, const uint64_t* sr
  * [0] the fgpu_edges_build call, [1] folding the layers and adopting / merging the built pieces (or the whole fallback),
  * [2] filling the multi-edge map, [3] the adjacency union */
 int fh_last_bulk_phases_ns(uint64_t out[4]);
+/* CREATE of one relationship type's batch onto a graph that already holds edges (Tensor::set_all_from_slices under
+ * Graph::create_relationships_bulk, tensor.rs:333-447, graph.rs:2062-2121, for the whole batch on the device): one
+ * fgpu_edges_build, the layers folded, one fgpu_edges_union of the tensor's base with the built batch — a pair that already
+ * holds an edge is promoted to MULTI_EDGE or its row extended — the results adopted as the bases, the multi-edge map rewritten
+ * for the touched pairs, the adjacency's base U= the batch's pattern; ends folded and never takes the create_edges path.
+ * stats (nullable): [0] edges, [1] distinct pairs of the batch, [2] its multi-edge pairs, [3] pairs that collided with a stored
+ * one, [4] of those promoted (one edge before), [5] extended (MULTI_EDGE before), [6] rows of the multi-edge map written,
+ * [7] runs sorted by the host.  An invalid batch (a node id at or past the capacity, an id equal to MULTI_EDGE, the same
+ * (src, dst, id) twice, an id already stored on its pair) returns the engine's code and leaves the graph as it was. */
+int fh_graph_append_edges_bulk(fh_graph* g, uint64_t type_id, const uint64_t* srcs, const uint64_t* dsts, const uint64_t* ids,
+                               uint64_t n, uint64_t stats[8]);
+/* host-clock phases (ns) of this thread's last fh_graph_append_edges_bulk (a measurement hook, tools/bench_paths.py append):
+ * [0] the fgpu_edges_build call, [1] the folds, the gather of the multi-edge rows and the fgpu_edges_union call, [2] rewriting
+ * the multi-edge map, [3] the adjacency union */
+int fh_last_append_phases_ns(uint64_t out[4]);
 /* DETACH DELETE of a node set in one call (what Pending::commit does with Graph::delete_nodes + delete_implicit_edges,
  * graph.rs:1698-1772, 2386-2494): every node gets fh_graph_delete_node's effects; per relationship type one fgpu_nodes_detach
  * takes the incident edges out of the tensor, which ends folded; the node x label matrix loses the nodes' rows and the adjacency

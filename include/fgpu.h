@@ -281,6 +281,42 @@ fgpu_info fgpu_edges_remove(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt
                             const uint64_t* multi_ids, uint64_t n_multi, fgpu_mat** m_out, fgpu_mat** mt_out, uint8_t* hit,
                             uint8_t* multi_taken, uint64_t** emp_row, uint64_t** emp_col, uint64_t* n_emp, uint64_t stats[8]);
 
+/* CREATE of a built batch onto a relationship type that already holds edges (Tensor::set_all_from_slices under
+ * Graph::create_relationships_bulk, tensor.rs:333-447, graph.rs:2062-2121): the union of a loaded tensor with one batch, both in
+ * the shape fgpu_edges_build returns.
+ *   m / mt      the tensor's folded UINT64 base (a value is an inline edge id or FGPU_MULTI_EDGE) and its BOOL transposed pattern;
+ *   fwd / bwd   the same two matrices of the batch, of m's and mt's dimensions;
+ *   a_key / a_off / a_ids [n_a]  the multi-edge rows of the pairs of m the caller believes the batch touches;
+ *   b_key / b_off / b_ids [n_b]  the rows fgpu_edges_build returned with fwd.
+ * Row arrays follow fgpu_edges_remove's rules: keys src << 32 | dst strictly ascending, off[0] = 0, every run at least 2 ids long
+ * and strictly ascending.  An a key that is not a FGPU_MULTI_EDGE entry of m, or that names a pair the batch does not, is
+ * ignored; so is a b key that is not a FGPU_MULTI_EDGE entry of fwd.
+ * The per-edge transitions of tensor.rs:383-418 restated per pair of fwd: a pair absent from m enters m_out with fwd's value;
+ * a pair stored in both COLLIDES — m_out holds FGPU_MULTI_EDGE and the pair's id list is the ascending merge of m's side (the
+ * inline id, or the a row under FGPU_MULTI_EDGE) with fwd's side (the inline id, or the b row).  Pairs of m the batch does not
+ * name keep their value.  mt_out is the pattern union of mt and bwd.
+ * o_key / o_off / o_ids hold one row per colliding pair, keys and ids ascending, every row at least 2 ids long; the rows of
+ * multi-edge pairs only the batch names are the caller's b rows and are not copied back.  The arrays are engine-owned
+ * (fgpu_free); o_key and o_ids are NULL when n_o == 0, o_off always has n_o + 1 entries.
+ * m_out / mt_out are NEW snapshots (fgpu_mat_free) with sorted unique rows, stored hypersparse exactly when fgpu_mat_from_coo
+ * would store that many populated rows of that dimension so; the four input matrices are untouched.  An empty fwd gives copies of
+ * m and mt and n_o = 0.  The call keeps no device memory.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated and the context still usable, for: m or fwd not valued; mt or bwd
+ * missing, valued or of other dimensions than ncols x nrows; fwd of other dimensions than m; keys not strictly ascending, a run
+ * shorter than 2, ids not ascending in a run, an id equal to FGPU_MULTI_EDGE in a row; a colliding pair that holds
+ * FGPU_MULTI_EDGE in m with no a row, or in fwd with no b row; an id on BOTH sides of a colliding pair (the edge is already
+ * stored: edge ids are unique, the same stance as fgpu_edges_build's "same triple twice") — the last three counted on the
+ * device and read back before any output is allocated; row ids and entries of fwd that could merge into 2^32 - 1 ids or more.
+ * stats (nullable): [0] pairs new to m, [1] colliding pairs (= n_o), [2] of those, pairs that held an inline id in m (promoted),
+ * [3] of those, pairs that held FGPU_MULTI_EDGE in m (extended), [4] ids in the out rows, [5] longest out row, [6] entries of
+ * m_out, [7] entries of mt_out.
+ * Work: a lane per stored entry of fwd and of bwd (binary searches), a lane per output id (a co-rank search over the two
+ * sides), a lane per stored entry of m and of mt; every output is placed by a scan. */
+fgpu_info fgpu_edges_union(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt, const uint64_t* a_key, const uint64_t* a_off,
+                           const uint64_t* a_ids, uint64_t n_a, const fgpu_mat* fwd, const fgpu_mat* bwd, const uint64_t* b_key,
+                           const uint64_t* b_off, const uint64_t* b_ids, uint64_t n_b, fgpu_mat** m_out, fgpu_mat** mt_out,
+                           uint64_t** o_key, uint64_t** o_off, uint64_t** o_ids, uint64_t* n_o, uint64_t stats[8]);
+
 /* Host CSR (what GxB_unload_Matrix_into_Container yields: p, i, x [, h];
  * matrix.rs:508-546) -> device snapshot.  rowptr has nvec+1 entries when
  * `hyper_rows` (sorted non-empty row ids, nvec of them) is given, else

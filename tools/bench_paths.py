@@ -86,7 +86,17 @@
           the multi-edge rows of the touched pairs) for a seeded 1 % and 10 % of the raw tuples, its device phases, beside one
           fgpu_mat_merge(m, NULL, dm) whose dm holds the same pairs.  `edel <scale>`: the twin comparison at that scale only.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  append  the host layer's bulk insert onto a loaded graph: Graph::append_edges_bulk (fgpu_edges_build + one fgpu_edges_union,
+          every edge on the device) against what Graph::bulk_insert_edges does with the same batch — one pair that holds an
+          edge sends it through set_all_from_slices whole — on twin graphs of the distinct RMAT-18 and RMAT-20 edges plus a
+          second edge on a seeded 5 % of the pairs, loaded with bulk_insert_edges.  The batch is a seeded, shuffled 10 % as many
+          new edges: half on loaded pairs (so a twentieth of those on multi-edge pairs), the rest on pairs the graph does not
+          hold.  A host clock around the call + commit, one warm-up, median of 3, a fresh twin each, with the host phases
+          (fh_last_append_phases_ns).  Then the raw fgpu_edges_union on the RMAT-22 tensor of the load leg for batches of 1 %
+          and 10 % as many tuples built by fgpu_edges_build, its device phases, beside one fgpu_mat_merge(m, fwd, NULL) over
+          the same pairs.  `append <scale>`: the twin comparison at that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -602,6 +612,139 @@ def bench_edel(scales=(18, 20), raw_scale=22, deadline_s=10.0):
                                   "fgpu_mat_merge(m, NULL, dm) with dm the BOOL matrix of the same pairs, median of 5 after 2 warm-up: "
                                   "it drops the whole pair where the call removes single edges"}), flush=True)
         del dm
+
+
+def bench_append(scales=(18, 20), raw_scale=22):
+    from falkordb_amd import host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+    for scale in scales:
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        A.free()
+        E = len(ci)
+        rng = np.random.default_rng(200 + scale)
+        dup = rng.choice(E, E // 20, replace=False)                     # a second edge on 5 % of the pairs
+        ls, ld = np.r_[r, r[dup]], np.r_[ci, ci[dup]]
+        lid = np.arange(len(ls), dtype=np.uint64)
+        nb = E // 10
+        on = rng.choice(E, nb // 2, replace=False)                       # half of the batch lands on loaded pairs
+        keys = (r << np.uint64(32)) | ci                                 # (ascending: CSR order)
+        fs, fd = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+        while len(fs) < nb - nb // 2:                                    # ... the rest on pairs the graph does not hold
+            s, d = rng.integers(0, n, nb, dtype=np.uint64), rng.integers(0, n, nb, dtype=np.uint64)
+            k = (s << np.uint64(32)) | d
+            at = np.minimum(np.searchsorted(keys, k), E - 1)
+            new = keys[at] != k
+            fs, fd = np.r_[fs, s[new]], np.r_[fd, d[new]]
+        mix = rng.permutation(nb)
+        bs, bd = np.r_[r[on], fs[:nb - nb // 2]][mix], np.r_[ci[on], fd[:nb - nb // 2]][mix]
+        bi = np.arange(len(ls), len(ls) + nb, dtype=np.uint64)
+        on_multi = int(np.isin(on, dup).sum())
+
+        def loaded():
+            g = host.Graph(hc, n)
+            t = g.add_type("KNOWS")
+            g.bulk_insert_edges(t, ls, ld, lid)
+            g.commit()
+            return g, t
+
+        ts = []
+        for rep in range(4):                     # (rep 0 warms up; every rep appends to freshly loaded twins)
+            g, t = loaded()
+            t0 = time.perf_counter()
+            st = g.append_edges_bulk(t, bs, bd, bi)
+            t1 = time.perf_counter()
+            g.commit()
+            t2 = time.perf_counter()
+            phases = g.last_append_phases_ms()
+            g2, _ = loaded()
+            t3 = time.perf_counter()
+            st2 = g2.bulk_insert_edges(t, bs, bd, bi)
+            t4 = time.perf_counter()
+            g2.commit()
+            t5 = time.perf_counter()
+            assert st2["fallback_edges"] == nb and st["edges"] == nb
+            assert g.tensor_edge_count(t) == g2.tensor_edge_count(t) == len(ls) + nb
+            assert g.tensor_state(t)["multi_pairs"] == g2.tensor_state(t)["multi_pairs"]
+            ts.append((t2 - t0, t1 - t0, phases, st, t5 - t3, t4 - t3))
+            del g, g2
+        total, call, phases, st, _, _ = ts[int(np.argsort([x[0] for x in ts[1:]])[1]) + 1]
+        _, _, _, _, ftotal, fcall = ts[int(np.argsort([x[4] for x in ts[1:]])[1]) + 1]
+        print(json.dumps({"path": "graph_append", "scale": scale, "edges_loaded": len(ls), "pairs_loaded": E,
+                          "multi_pairs_loaded": len(dup), "edges_appended": nb, "on_loaded_pairs": nb // 2,
+                          "on_multi_pairs": on_multi,
+                          "append_edges_bulk": {"s": round(total, 5), "call_s": round(call, 5), "us_per_edge": round(total / nb * 1e6, 5),
+                                                "host_phases_ms": {k_: round(v_, 3) for k_, v_ in phases.items()}, "stats": st},
+                          "bulk_insert_edges_fallback": {"s": round(ftotal, 5), "call_s": round(fcall, 5),
+                                                         "us_per_edge": round(ftotal / nb * 1e6, 5)},
+                          "quotient": round(ftotal / total, 1),
+                          "note": "twin graphs loaded with bulk_insert_edges + commit in one process; host clock around the call + "
+                                  "commit; one warm-up, median of 3, fresh twins each; the twin's bulk_insert_edges takes "
+                                  "set_all_from_slices for the whole batch (fallback_edges = the batch), which is what this batch cost "
+                                  "before append_edges_bulk"}), flush=True)
+        del r, ci, ls, ld, lid, keys
+    if not raw_scale:
+        return
+    import oracle
+    u, v = (np.asarray(x, dtype=np.uint64) for x in oracle.rmat_edges(raw_scale))
+    n = 1 << raw_scale
+    fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, np.arange(len(u), dtype=np.uint64))
+    mkey, moff, mids = np.array(mkey), np.array(moff), np.array(mids)
+    for frac in (0.01, 0.1):
+        rng = np.random.default_rng(int(frac * 1000))
+        nb = int(len(u) * frac)
+        k = rng.choice(len(u), nb // 2, replace=False)
+        s = np.r_[u[k], rng.integers(0, n, nb - nb // 2, dtype=np.uint64)]
+        d = np.r_[v[k], rng.integers(0, n, nb - nb // 2, dtype=np.uint64)]
+        mix = rng.permutation(nb)
+        s, d = s[mix], d[mix]
+        t0 = time.perf_counter()
+        bf, bb, bk, bo, bids = engine.edges_build(ctx, n, n, s, d, np.arange(len(u), len(u) + nb, dtype=np.uint64))
+        ctx.sync()
+        t_build = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        keys = np.unique((s << np.uint64(32)) | d)                       # the multi-edge rows of the touched pairs, as the host layer gathers them
+        at = np.searchsorted(mkey, keys)
+        at = at[(at < len(mkey)) & (mkey[np.minimum(at, len(mkey) - 1)] == keys)]
+        lens = (moff[at + 1] - moff[at]).astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        pos = np.repeat(moff[at].astype(np.int64) - off[:-1].astype(np.int64), lens) + np.arange(int(off[-1]))
+        rows = (mkey[at], off, mids[pos])
+        t_gather = time.perf_counter() - t0
+        t_call, res = timed(ctx, lambda: engine.edges_union(ctx, fwd, bwd, *rows, bf, bb, bk, bo, bids, stats=True), reps=3, warm=1)
+        st = res[-1]
+        del res
+        ctx.prof_enable(True)
+        res = engine.edges_union(ctx, fwd, bwd, *rows, bf, bb, bk, bo, bids)
+        ctx.sync()
+        dev = {}
+        for p in ctx.prof_read():
+            if p["kernel"].startswith("eu_"):
+                dev[p["kernel"]] = round(dev.get(p["kernel"], 0.0) + p["ms"], 3)
+        ctx.prof_enable(False)
+        del res
+        t_merge, merged = timed(ctx, lambda: fwd.merge(bf, None), reps=5, warm=2)
+        nnz_merged = merged.nvals
+        del merged
+        print(json.dumps({"path": "edges_union_raw", "scale": raw_scale, "nnz": fwd.nvals, "frac": frac, "tuples": nb,
+                          "nnz_fwd": bf.nvals, "a_rows_supplied": len(at), "ids_in_a_rows": int(off[-1]), "b_rows": len(bk), "stats": st,
+                          "ms_call": round(t_call * 1e3, 3), "ms_edges_build_of_the_batch": round(t_build * 1e3, 3),
+                          "ms_numpy_row_gather": round(t_gather * 1e3, 3), "device_phases_ms": dev,
+                          "ms_call_outside_device_phases": round(t_call * 1e3 - sum(dev.values()), 3),
+                          "ms_fgpu_mat_merge_m_with_fwd": round(t_merge * 1e3, 3), "nnz_merged": nnz_merged,
+                          "quotient_call_over_merge": round(t_call / t_merge, 2),
+                          "note": "the UINT64 tensor base of the raw RMAT stream (fgpu_edges_build), its transposed pattern, a built "
+                                  "batch and the multi-edge rows of the touched pairs; median of 3 synchronised calls after 1 warm-up, "
+                                  "host-side validation, H2D of the rows and the read-back of the out rows included; device_phases = "
+                                  "HIP events of one more call (eu_h2d = the staged uploads, eu_place = both placements, eu_readback = "
+                                  "the out rows); outside them: validation of the rows on the host, allocation, the histogram, its "
+                                  "scan and the row-pointer passes; the merge is fgpu_mat_merge(m, fwd, NULL) on the forward matrix "
+                                  "alone, median of 5 after 2 warm-up: the batch's value wins, no promotion, no ids, no mt"}), flush=True)
+        del bf, bb
 
 
 def bench_host(scale):
@@ -1221,3 +1364,5 @@ if __name__ == "__main__":
         bench_detach(*(((), scale, 0) if scale else ()))
     if what == "edel":                           # (edge-by-edge deletes up to their deadlines: not part of `all`)
         bench_edel(*(((scale,), 0) if scale else ()))
+    if what == "append":                         # (seconds of edge-by-edge inserts per twin: not part of `all`)
+        bench_append(*(((scale,), 0) if scale else ()))
