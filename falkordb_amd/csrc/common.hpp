@@ -497,6 +497,7 @@ fgpu_info mat_alloc(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 ncols, u64 nnz
                     u32 nvec_hyper, bool hyper);
 fgpu_info mat_alloc_vals(fgpu_ctx* ctx, fgpu_mat* m);   // the value array of a snapshot built pattern-first (its builder's own)
 bool mat_prefer_hyper(u64 nrows, u64 nvec);   // the storage form fgpu_mat_from_coo gives nvec populated rows of nrows: hypersparse?
+constexpr u64 HYPER_MIN_ROWS = 4096;          // never with this many rows or fewer: a builder need not count the populated ones
 // m's cached pattern transpose (fgpu_mat::tcache), built once per snapshot under m->idx_mu; _locked: the caller holds it
 fgpu_info mat_cached_transpose(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out);
 fgpu_info mat_cached_transpose_locked(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat** out);

@@ -1,36 +1,19 @@
 // compact.hpp — the compaction half shared by detach.hip (fgpu_nodes_detach) and edges_remove.hip (fgpu_edges_remove): both
 // decide keep or drop per stored entry position of a snapshot, scan the flags, and place everything by the scan.
 //
-//   wordrow  the stored row of every 64th entry, a lane per word: a lane that needs the row of entry p searches the row
-//            pointers between wordrow[p / 64] and wordrow[p / 64 + 1] only
+//   wordrow  the per-call index of bulk.hpp over the pass's matrix (dt_wordrow)
 //   E        the exclusive scan of keep over nnz + 1 flags (keep[nnz] = 0), so that E[nnz] is the number of kept entries;
 //            entry p stays exactly when E[p + 1] != E[p], and then goes to position E[p] of the output
 //   rows     rowptr'[r] = E[rowptr[r]], a lane per row — no per-row loop; a hypersparse input goes through its hrows, and the
 //            output is hypersparse exactly when fgpu_mat_from_coo would store that many populated rows so (mat_prefer_hyper)
 //
-// The kernels are static: each translation unit carries its own copy.  edges_union.hip (fgpu_edges_union) includes this file
-// for the wordrow index alone — over its batch's entries and over the offsets of its out rows.
+// The kernels are static: each translation unit carries its own copy.  The searches, the counters and the marshalling of the
+// callers' arrays are bulk.hpp's, which this file includes; edges_union.hip (fgpu_edges_union) and edges.hip (fgpu_edges_build)
+// compact nothing and include bulk.hpp alone.
 #pragma once
-#include "common.hpp"
+#include "bulk.hpp"
 
 namespace fgpu {
-
-// largest i in [lo, hi] with rp[i] <= p (rows may be empty: equal row pointers)
-__device__ __forceinline__ u32 dt_row_of(const u32* __restrict__ rp, u32 lo, u32 hi, u32 p) {
-    while (lo < hi) {
-        const u32 mid = (lo + hi + 1) >> 1;
-        if (rp[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// stored-row index of the first entry of each 64-entry word; wordrow[nwords] = last stored row
-static __global__ __launch_bounds__(256) void dt_wordrow_kernel(const u32* __restrict__ rp, u32 nvec, u32 nwords,
-                                                               u32* __restrict__ wordrow) {
-    const u32 w = blockIdx.x * 256 + threadIdx.x;
-    if (w > nwords) return;
-    wordrow[w] = w < nwords ? dt_row_of(rp, 0, nvec - 1, w << 6) : nvec - 1;
-}
 
 // E / O: the scans of keep / list.  A kept entry goes to out_col / out_val; a listed one to lrow / lcol / lval at lbase + O[p] —
 // as (row, col, value) of this matrix, or with `swap` (the pass over the transposed pattern) as (col, row, value of (col, row) in
@@ -52,9 +35,7 @@ static __global__ __launch_bounds__(256) void dt_emit_kernel(CsrView a, const u6
     if (!O) return;
     const u32 o0 = O[p];
     if (O[p + 1] == o0) return;
-    const u32 w = p >> 6;
-    const u32 i = dt_row_of(a.rowptr, wordrow[w], wordrow[w + 1], p);
-    const u32 r = a.hrows ? a.hrows[i] : i;
+    const u32 r = entry_row(a, wordrow, p);
     const u32 at = lbase + o0;
     if (!swap) {
         lrow[at] = r;
@@ -64,14 +45,8 @@ static __global__ __launch_bounds__(256) void dt_emit_kernel(CsrView a, const u6
     }
     u64 v = 0;
     if (fwd_vals) {
-        u32 b, e;
-        row_range(fwd, c, b, e);
-        u32 lo = b, hi = e;
-        while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
-            if (fwd.colidx[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        if (lo < e && fwd.colidx[lo] == r) v = fwd_vals[lo];
+        const u32 q = probe(fwd, c, r);
+        if (q != ~0u) v = fwd_vals[q];
     }
     lrow[at] = c;
     lcol[at] = r;
@@ -105,16 +80,7 @@ static __global__ __launch_bounds__(256) void dt_rows_full_kernel(const u32* __r
                                                                  u64 nrows, const u32* __restrict__ E, u32* __restrict__ rp_out) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r > nrows) return;
-    u32 i = (u32)r;
-    if (hrows) {
-        u32 lo = 0, hi = nvec;
-        while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
-            if (hrows[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        i = lo;
-    }
-    rp_out[r] = E[rp[i]];
+    rp_out[r] = E[rp[hrows ? lower_bound(hrows, 0u, nvec, (u32)r) : (u32)r]];
 }
 
 // one matrix' pass, in two halves around the read-back of the totals: its flags and scans are the caller's, dt_emit is shared
@@ -122,16 +88,9 @@ struct DtPass {
     const fgpu_mat* a = nullptr;
     DevBuf<u32> wordrow, E, O;
     bool listed = false;
+    // wordrow of a (which holds an entry)
+    fgpu_info index(fgpu_ctx* ctx) { return wordrow_build(ctx, a->rowptr, a->nvec, a->nnz, wordrow); }
 };
-
-// ps.wordrow of ps.a (which holds an entry)
-static fgpu_info dt_wordrow(fgpu_ctx* ctx, DtPass& ps) {
-    const fgpu_mat* a = ps.a;
-    const u32 nwords = (u32)((a->nnz + 63) >> 6);
-    FGPU_TRY(ps.wordrow.alloc(ctx, (size_t)nwords + 1));
-    return launch(dt_wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)a->rowptr, a->nvec,
-                  nwords, ps.wordrow.p);
-}
 
 // the output snapshot of a pass (its row pointers here, its entries by dt_emit_kernel), then the emission
 static fgpu_info dt_emit(fgpu_ctx* ctx, DtPass& ps, u64 kept, MatRef& out, u32* lrow, u32* lcol, u64* lval, u32 lbase, bool swap,
@@ -143,7 +102,7 @@ static fgpu_info dt_emit(fgpu_ctx* ctx, DtPass& ps, u64 kept, MatRef& out, u32* 
     u32 nvec_out = 0;
     bool hyper = false;
     DevBuf<u32> F;
-    if (nrows > 4096) {   // (below that no builder stores a matrix hypersparse)
+    if (nrows > HYPER_MIN_ROWS) {
         FGPU_TRY(F.alloc(ctx, (size_t)nvec + 1));
         DevBuf<u32> tot;
         FGPU_TRY(tot.alloc(ctx, 1));

@@ -16,8 +16,9 @@
 //           column not": the scan orders the in-list in ascending (dst, src), the order a walk of mt's rows meets them.  Each in
 //           entry takes its value by a binary search for dst in row src of the forward matrix
 //
-// No wavefront per row anywhere: a hub row of 10^6 entries is 10^6 lanes like any other 10^6 entries.  The wordrow, emit and rows
-// steps live in compact.hpp, which fgpu_edges_remove (edges_remove.hip) places its outputs with too.
+// No wavefront per row anywhere: a hub row of 10^6 entries is 10^6 lanes like any other 10^6 entries.  The emit and rows steps
+// live in compact.hpp, which fgpu_edges_remove (edges_remove.hip) places its outputs with too; the wordrow index, the searches
+// and the counters in bulk.hpp, the prelude of every bulk mutation.
 #include <algorithm>
 
 #include "compact.hpp"
@@ -35,8 +36,7 @@ __global__ __launch_bounds__(256) void dt_bitmap_kernel(const u32* __restrict__ 
         const u32 v = nodes[i], bit = 1u << (v & 31);
         fresh = (atomicOr(&bits[v >> 5], bit) & bit) == 0;
     }
-    const u64 b = __ballot(fresh);
-    if (lane_id() == 0 && b) atomicAdd(n_distinct, (u32)__popcll(b));
+    count_if(fresh, n_distinct);
 }
 
 // keep[p] = the entry stays; list[p] (nullable) = the entry goes to this pass's list: its row is in D (row_side) and, with
@@ -47,10 +47,8 @@ __global__ __launch_bounds__(256) void dt_flag_kernel(CsrView a, const u64* __re
     const u64 p64 = (u64)blockIdx.x * 256 + threadIdx.x;
     bool multi = false;
     if (p64 < nnz) {
-        const u32 p = (u32)p64, w = p >> 6;
-        const u32 i = dt_row_of(a.rowptr, wordrow[w], wordrow[w + 1], p);
-        const u32 r = a.hrows ? a.hrows[i] : i;
-        const u32 c = a.colidx[p];
+        const u32 p = (u32)p64;
+        const u32 r = entry_row(a, wordrow, p), c = a.colidx[p];
         const bool dr = row_side && dt_bit(bits, r);
         const bool dc = col_side && dt_bit(bits, c);
         keep[p] = (dr || dc) ? 0u : 1u;
@@ -60,10 +58,7 @@ __global__ __launch_bounds__(256) void dt_flag_kernel(CsrView a, const u64* __re
         keep[nnz] = 0u;
         if (list) list[nnz] = 0u;
     }
-    if (n_multi) {
-        const u64 b = __ballot(multi);
-        if (lane_id() == 0 && b) atomicAdd(n_multi, (u32)__popcll(b));
-    }
+    if (n_multi) count_if(multi, n_multi);
 }
 
 static fgpu_info dt_flags(fgpu_ctx* ctx, DtPass& ps, const fgpu_mat* a, const u32* bits, bool row_side, bool col_side, bool excl_col,
@@ -80,7 +75,7 @@ static fgpu_info dt_flags(fgpu_ctx* ctx, DtPass& ps, const fgpu_mat* a, const u3
         return FGPU_OK;
     }
     ProfScope prof(ctx, "dt_flags", nnz * (a->vals ? 12 : 4) + (listed ? 16 : 8) * nnz);
-    FGPU_TRY(dt_wordrow(ctx, ps));
+    FGPU_TRY(ps.index(ctx));
     FGPU_TRY(launch(dt_flag_kernel, dim3(cdiv(nnz + 1, 256)), dim3(256), 0, st, view_of(a), (const u64*)a->vals,
                     (const u32*)ps.wordrow.p, (u32)nnz, bits, row_side, col_side, excl_col, ps.E.p, listed ? ps.O.p : nullptr,
                     n_multi_dev));
@@ -108,10 +103,7 @@ static fgpu_info nodes_detach_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_
                  "fgpu_nodes_detach: mt_out must be given exactly when mt is");
     FGPU_REQUIRE(sides >= 1 && sides <= 3, FGPU_INVALID, "fgpu_nodes_detach: sides = %d is not 1, 2 or 3", sides);
     FGPU_REQUIRE(!want_list || mt, FGPU_INVALID, "fgpu_nodes_detach: the removal list needs the transposed pattern mt");
-    FGPU_REQUIRE(!mt || (mt->nrows == m->ncols && mt->ncols == m->nrows && !mt->vals), FGPU_INVALID,
-                 "fgpu_nodes_detach: mt must be the BOOL %llu x %llu pattern (got %llu x %llu%s)", (unsigned long long)m->ncols,
-                 (unsigned long long)m->nrows, (unsigned long long)mt->nrows, (unsigned long long)mt->ncols,
-                 mt->vals ? ", valued" : "");
+    if (mt) FGPU_TRY(require_pattern_of("fgpu_nodes_detach", "mt", mt, m));
     FGPU_REQUIRE(!(want_list && (sides & 2)) || m->nrows == m->ncols, FGPU_INVALID,
                  "fgpu_nodes_detach: a list over both sides needs a square matrix (got %llu x %llu)", (unsigned long long)m->nrows,
                  (unsigned long long)m->ncols);
@@ -197,8 +189,6 @@ using namespace fgpu;
 extern "C" fgpu_info fgpu_nodes_detach(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt, const uint64_t* nodes, uint64_t n_nodes,
                                        int sides, fgpu_mat** m_out, fgpu_mat** mt_out, uint64_t** rem_row, uint64_t** rem_col,
                                        uint64_t** rem_val, uint64_t* n_rem, uint64_t* n_rem_out, uint64_t stats[8]) {
-    fgpu_info i_ = nodes_detach_impl(ctx, m, mt, nodes, n_nodes, sides, m_out, mt_out, rem_row, rem_col, rem_val, n_rem, n_rem_out,
-                                     stats);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handles may go to another thread
-    return i_;
+    return published(ctx, nodes_detach_impl(ctx, m, mt, nodes, n_nodes, sides, m_out, mt_out, rem_row, rem_col, rem_val, n_rem,
+                                            n_rem_out, stats));
 }

@@ -19,7 +19,7 @@
 // No wavefront per row and no atomics anywhere: every list is placed by a scan, the flags are plain stores of 1.
 #include <algorithm>
 
-#include "common.hpp"
+#include "bulk.hpp"
 
 namespace fgpu {
 
@@ -153,12 +153,7 @@ __global__ __launch_bounds__(256) void eb_rowptr_kernel(const u64* __restrict__ 
                                                        u32 n_distinct, u64 nrows, u32* __restrict__ rowptr) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r > nrows) return;
-    const u64 target = r << 32;
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (key[mid] < target) lo = mid + 1; else hi = mid;
-    }
+    const u32 lo = lower_bound(key, 0u, (u32)n, r << 32);
     rowptr[r] = lo < n ? E[lo] : n_distinct;
 }
 
@@ -206,17 +201,8 @@ static fgpu_info edges_build_impl(fgpu_ctx* ctx, u64 nrows, u64 ncols, const u64
         DevBuf<u32> dsrc, ddst;
         DevBuf<u64> dids;
         {
-            std::vector<u32> s32(n), d32(n);
-            for (u64 i = 0; i < n; ++i) {
-                FGPU_REQUIRE(srcs[i] < nrows && dsts[i] < ncols, FGPU_INVALID,
-                             "fgpu_edges_build: tuple %llu = (%llu, %llu) outside %llu x %llu", (unsigned long long)i,
-                             (unsigned long long)srcs[i], (unsigned long long)dsts[i], (unsigned long long)nrows,
-                             (unsigned long long)ncols);
-                FGPU_REQUIRE(ids[i] != FGPU_MULTI_EDGE, FGPU_INVALID, "fgpu_edges_build: tuple %llu carries the MULTI_EDGE marker as its id",
-                             (unsigned long long)i);
-                s32[i] = (u32)srcs[i];
-                d32[i] = (u32)dsts[i];
-            }
+            std::vector<u32> s32, d32;
+            FGPU_TRY(marshal_triples("fgpu_edges_build", srcs, dsts, ids, n, nrows, ncols, s32, d32));
             ProfScope ps(ctx, "eb_h2d", 16 * n);
             FGPU_TRY(dsrc.alloc(ctx, n));
             FGPU_TRY(ddst.alloc(ctx, n));
@@ -359,7 +345,6 @@ using namespace fgpu;
 extern "C" fgpu_info fgpu_edges_build(fgpu_ctx* ctx, uint64_t nrows, uint64_t ncols, const uint64_t* srcs, const uint64_t* dsts,
                                       const uint64_t* ids, uint64_t n, fgpu_mat** fwd, fgpu_mat** bwd, uint64_t** multi_key,
                                       uint64_t** multi_off, uint64_t** multi_ids, uint64_t* n_multi, uint64_t stats[8]) {
-    fgpu_info i_ = edges_build_impl(ctx, nrows, ncols, srcs, dsts, ids, n, fwd, bwd, multi_key, multi_off, multi_ids, n_multi, stats);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handles may go to another thread
-    return i_;
+    return published(ctx, edges_build_impl(ctx, nrows, ncols, srcs, dsts, ids, n, fwd, bwd, multi_key, multi_off, multi_ids, n_multi,
+                                           stats));
 }

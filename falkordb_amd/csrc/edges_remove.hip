@@ -21,35 +21,6 @@
 
 namespace fgpu {
 
-// position of column c in [b, e) of colidx, or ~0u
-__device__ __forceinline__ u32 er_find(const u32* __restrict__ colidx, u32 b, u32 e, u32 c) {
-    u32 lo = b, hi = e;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (colidx[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return (lo < e && colidx[lo] == c) ? lo : ~0u;
-}
-__device__ __forceinline__ u32 er_probe(const CsrView& a, u32 r, u32 c) {
-    u32 b, e;
-    row_range(a, r, b, e);
-    return er_find(a.colidx, b, e, c);
-}
-// position of key in the ascending keys[0, n), or ~0u
-__device__ __forceinline__ u32 er_find64(const u64* __restrict__ keys, u32 b, u32 e, u64 key) {
-    u32 lo = b, hi = e;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < e && keys[lo] == key) ? lo : ~0u;
-}
-
-__device__ __forceinline__ void er_count(bool flag, u32* __restrict__ counter) {
-    const u64 b = __ballot(flag);
-    if (lane_id() == 0 && b) atomicAdd(counter, (u32)__popcll(b));
-}
-
 // keep[p] = 1 for p < nnz, keep[nnz] = 0 (so that the scan ends in the total)
 __global__ __launch_bounds__(256) void er_fill_kernel(u32* __restrict__ keep, u32 nnz) {
     const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
@@ -68,7 +39,7 @@ __global__ __launch_bounds__(256) void er_triple_kernel(CsrView m, const u64* __
     if (k64 < n) {
         const u32 k = (u32)k64, s = srcs[k], d = dsts[k];
         const u64 id = ids[k];
-        const u32 p = er_probe(m, s, d);
+        const u32 p = probe(m, s, d);
         if (p == ~0u) {
             absent = true;
         } else {
@@ -77,17 +48,17 @@ __global__ __launch_bounds__(256) void er_triple_kernel(CsrView m, const u64* __
                 if (v == id) {
                     is_hit = true;
                     keep[p] = 0u;
-                    const u32 q = er_probe(mt, d, s);
+                    const u32 q = probe(mt, d, s);
                     if (q != ~0u) keep_t[q] = 0u;
                 } else {
                     unknown = true;
                 }
             } else {
-                const u32 r = er_find64(mkey, 0, n_multi, ((u64)s << 32) | d);
+                const u32 r = find(mkey, 0u, n_multi, ((u64)s << 32) | d);
                 if (r == ~0u) {
                     missing = true;
                 } else {
-                    const u32 j = er_find64(mids, moff[r], moff[r + 1], id);
+                    const u32 j = find(mids, moff[r], moff[r + 1], id);
                     if (j != ~0u) { is_hit = true; taken[j] = 1u; }
                     else unknown = true;
                 }
@@ -95,10 +66,10 @@ __global__ __launch_bounds__(256) void er_triple_kernel(CsrView m, const u64* __
         }
         if (hit) hit[k] = is_hit ? 1 : 0;
     }
-    er_count(is_hit, cnt + 0);
-    er_count(absent, cnt + 1);
-    er_count(unknown, cnt + 2);
-    er_count(missing, cnt + 3);
+    count_if(is_hit, cnt + 0);
+    count_if(absent, cnt + 1);
+    count_if(unknown, cnt + 2);
+    count_if(missing, cnt + 3);
 }
 
 // a lane per supplied row; S = the scan of taken.  dem_p (prefilled ~0u) / dem_id: position in m and surviving id of a demoted
@@ -116,19 +87,19 @@ __global__ __launch_bounds__(256) void er_multi_kernel(CsrView m, const u64* __r
         if (removed) {   // (some triple hit an id of the row, so the pair is a MULTI_EDGE entry of m)
             const u64 key = mkey[r];
             const u32 s = (u32)(key >> 32), d = (u32)key;
-            const u32 p = er_probe(m, s, d);
+            const u32 p = probe(m, s, d);
             const u32 left = e - b - removed;
             if (p != ~0u && vals[p] == FGPU_MULTI_EDGE && left <= 1) {
                 if (left == 0) {
                     emptied = true;
                     keep[p] = 0u;
-                    const u32 q = er_probe(mt, d, s);
+                    const u32 q = probe(mt, d, s);
                     if (q != ~0u) keep_t[q] = 0u;
                 } else {
                     // untaken ids in [b, j] = (j + 1 - b) - (S[j + 1] - S[b]), ascending in j: the survivor is the first j at 1
                     u32 lo = b, hi = e - 1;
                     while (lo < hi) {
-                        const u32 mid = (lo + hi) >> 1;
+                        const u32 mid = lo + ((hi - lo) >> 1);
                         if ((mid + 1 - b) - (S[mid + 1] - sb) >= 1u) hi = mid; else lo = mid + 1;
                     }
                     demoted = true;
@@ -138,8 +109,8 @@ __global__ __launch_bounds__(256) void er_multi_kernel(CsrView m, const u64* __r
             }
         }
     }
-    er_count(emptied, cnt + 0);
-    er_count(demoted, cnt + 1);
+    count_if(emptied, cnt + 0);
+    count_if(demoted, cnt + 1);
 }
 
 // multi_taken[j] = taken[j], read off its scan
@@ -164,9 +135,7 @@ __global__ __launch_bounds__(256) void er_emptied_kernel(CsrView a, const u32* _
     if (p64 >= nnz) return;
     const u32 p = (u32)p64, e0 = E[p];
     if (E[p + 1] != e0) return;
-    const u32 w = p >> 6;
-    const u32 i = dt_row_of(a.rowptr, wordrow[w], wordrow[w + 1], p);
-    lrow[p - e0] = a.hrows ? a.hrows[i] : i;
+    lrow[p - e0] = entry_row(a, wordrow, p);
     lcol[p - e0] = a.colidx[p];
 }
 
@@ -189,45 +158,20 @@ static fgpu_info edges_remove_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_
     FGPU_REQUIRE(n_multi == 0 || (multi_key && multi_off && multi_ids && multi_taken), FGPU_NULL_POINTER,
                  "fgpu_edges_remove: NULL multi-edge rows or multi_taken");
     FGPU_REQUIRE(m->vals, FGPU_INVALID, "fgpu_edges_remove: m must be the tensor's UINT64 base (got a BOOL matrix)");
-    FGPU_REQUIRE(mt, FGPU_INVALID, "fgpu_edges_remove: the transposed pattern mt is missing");
-    FGPU_REQUIRE(mt->nrows == m->ncols && mt->ncols == m->nrows && !mt->vals, FGPU_INVALID,
-                 "fgpu_edges_remove: mt must be the BOOL %llu x %llu pattern (got %llu x %llu%s)", (unsigned long long)m->ncols,
-                 (unsigned long long)m->nrows, (unsigned long long)mt->nrows, (unsigned long long)mt->ncols,
-                 mt->vals ? ", valued" : "");
+    FGPU_TRY(require_pattern_of("fgpu_edges_remove", "mt", mt, m));
     FGPU_REQUIRE(n < 0xFFFFFFFFull, FGPU_INVALID, "fgpu_edges_remove: %llu triples exceed the 32-bit position space",
                  (unsigned long long)n);
     FGPU_REQUIRE(n_multi < 0xFFFFFFFFull, FGPU_INVALID, "fgpu_edges_remove: %llu multi-edge rows exceed the 32-bit position space",
                  (unsigned long long)n_multi);
-    std::vector<u32> s32(n), d32(n);
-    for (u64 k = 0; k < n; ++k) {
-        FGPU_REQUIRE(srcs[k] < m->nrows && dsts[k] < m->ncols, FGPU_INVALID,
-                     "fgpu_edges_remove: triple %llu = (%llu, %llu) outside %llu x %llu", (unsigned long long)k,
-                     (unsigned long long)srcs[k], (unsigned long long)dsts[k], (unsigned long long)m->nrows,
-                     (unsigned long long)m->ncols);
-        FGPU_REQUIRE(ids[k] != FGPU_MULTI_EDGE, FGPU_INVALID, "fgpu_edges_remove: triple %llu carries the MULTI_EDGE marker as its id",
-                     (unsigned long long)k);
-        s32[k] = (u32)srcs[k];
-        d32[k] = (u32)dsts[k];
-    }
-    std::vector<u32> off32((size_t)n_multi + 1, 0u);
-    FGPU_REQUIRE(n_multi == 0 || multi_off[0] == 0, FGPU_INVALID, "fgpu_edges_remove: multi_off[0] is not 0");
-    for (u64 r = 0; r < n_multi; ++r) {
-        FGPU_REQUIRE(r == 0 || multi_key[r - 1] < multi_key[r], FGPU_INVALID,
-                     "fgpu_edges_remove: multi-edge key %llu is not above the one before it", (unsigned long long)r);
-        const u64 b = multi_off[r], e = multi_off[r + 1];
-        FGPU_REQUIRE(e >= b + 2 && e < 0xFFFFFFFFull, FGPU_INVALID,
-                     "fgpu_edges_remove: multi-edge row %llu holds fewer than 2 ids (offsets %llu, %llu)", (unsigned long long)r,
-                     (unsigned long long)b, (unsigned long long)e);
-        for (u64 j = b + 1; j < e; ++j)
-            FGPU_REQUIRE(multi_ids[j - 1] < multi_ids[j], FGPU_INVALID, "fgpu_edges_remove: the ids of multi-edge row %llu do not ascend",
-                         (unsigned long long)r);
-        off32[r + 1] = (u32)e;
-    }
-    const u64 T = n_multi ? multi_off[n_multi] : 0;
+    std::vector<u32> s32, d32;
+    FGPU_TRY(marshal_triples("fgpu_edges_remove", srcs, dsts, ids, n, m->nrows, m->ncols, s32, d32));
+    MultiRows rows;
+    FGPU_TRY(rows.check("fgpu_edges_remove", "multi", multi_key, multi_off, multi_ids, n_multi));
+    const u64 T = rows.total();
     hipStream_t st = ctx->stream();
     // ---- flags ----------------------------------------------------------------------------------------------------------
-    DevBuf<u32> tot, dsrc, ddst, doff, taken, dem_p;
-    DevBuf<u64> dids, dkey, dmids, dem_id;
+    DevBuf<u32> tot, dsrc, ddst, taken, dem_p;
+    DevBuf<u64> dids, dem_id;
     DevBuf<uint8_t> dhit, dtaken8;
     // [0] kept in m [1] kept in mt [2] hits [3] absent [4] unknown [5] MULTI_EDGE without a row [6] multi emptied [7] demoted
     FGPU_TRY(tot.alloc(ctx, 8));
@@ -236,16 +180,10 @@ static fgpu_info edges_remove_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_
     FGPU_TRY(er_fill(ctx, pm, m));
     FGPU_TRY(er_fill(ctx, pt, mt));
     if (n_multi) {
-        FGPU_TRY(dkey.alloc(ctx, n_multi));
-        FGPU_TRY(doff.alloc(ctx, n_multi + 1));
-        FGPU_TRY(dmids.alloc(ctx, T));
         FGPU_TRY(taken.alloc(ctx, T + 1));
         FGPU_TRY(dem_p.alloc(ctx, n_multi));
         FGPU_TRY(dem_id.alloc(ctx, n_multi));
-        ProfScope prof(ctx, "er_h2d", n_multi * 12 + T * 8);
-        FGPU_TRY(ctx->h2d(dkey.p, multi_key, n_multi * sizeof(u64)));
-        FGPU_TRY(ctx->h2d(doff.p, off32.data(), (n_multi + 1) * sizeof(u32)));
-        FGPU_TRY(ctx->h2d(dmids.p, multi_ids, T * sizeof(u64)));
+        FGPU_TRY(rows.upload(ctx, "er_h2d"));
         FGPU_HIP(hipMemsetAsync(taken.p, 0, (T + 1) * sizeof(u32), st));
         FGPU_HIP(hipMemsetAsync(dem_p.p, 0xFF, n_multi * sizeof(u32), st));
     }
@@ -262,15 +200,15 @@ static fgpu_info edges_remove_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_
         }
         ProfScope prof(ctx, "er_triples", n * 16);   // (plus one 64-byte line per probe step: the searches are the cost)
         FGPU_TRY(launch(er_triple_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, view_of(m), (const u64*)m->vals, view_of(mt),
-                        (const u32*)dsrc.p, (const u32*)ddst.p, (const u64*)dids.p, (u32)n, (const u64*)dkey.p, (const u32*)doff.p,
-                        (const u64*)dmids.p, (u32)n_multi, pm.E.p, pt.E.p, taken.p, dhit.p, tot.p + 2));
+                        (const u32*)dsrc.p, (const u32*)ddst.p, (const u64*)dids.p, (u32)n, (const u64*)rows.key.p, (const u32*)rows.off.p,
+                        (const u64*)rows.ids.p, (u32)n_multi, pm.E.p, pt.E.p, taken.p, dhit.p, tot.p + 2));
     }
     if (n_multi) {
         ProfScope prof(ctx, "er_multi", T * 8 + n_multi * 24);
         FGPU_TRY(scan_u32(ctx, taken.p, taken.p, T + 1, nullptr));
         FGPU_TRY(launch(er_multi_kernel, dim3(cdiv(n_multi, 256)), dim3(256), 0, st, view_of(m), (const u64*)m->vals, view_of(mt),
-                        (const u64*)dkey.p, (const u32*)doff.p, (const u64*)dmids.p, (u32)n_multi, (const u32*)taken.p, pm.E.p, pt.E.p,
-                        dem_p.p, dem_id.p, tot.p + 6));
+                        (const u64*)rows.key.p, (const u32*)rows.off.p, (const u64*)rows.ids.p, (u32)n_multi, (const u32*)taken.p, pm.E.p,
+                        pt.E.p, dem_p.p, dem_id.p, tot.p + 6));
     }
     {
         ProfScope prof(ctx, "er_scans", 8 * (m->nnz + mt->nnz));
@@ -290,7 +228,7 @@ static fgpu_info edges_remove_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_
         FGPU_TRY(lcol.alloc(ctx, emptied));
         FGPU_REQUIRE(rr.alloc(ctx, emptied * sizeof(u64)) && rc.alloc(ctx, emptied * sizeof(u64)), FGPU_OOM,
                      "fgpu_edges_remove: out of host memory");
-        FGPU_TRY(dt_wordrow(ctx, pm));
+        FGPU_TRY(pm.index(ctx));
     }
     if (n_multi) FGPU_TRY(dtaken8.alloc(ctx, T));
     MatRef om, ot;
@@ -341,8 +279,6 @@ extern "C" fgpu_info fgpu_edges_remove(fgpu_ctx* ctx, const fgpu_mat* m, const f
                                        const uint64_t* multi_ids, uint64_t n_multi, fgpu_mat** m_out, fgpu_mat** mt_out, uint8_t* hit,
                                        uint8_t* multi_taken, uint64_t** emp_row, uint64_t** emp_col, uint64_t* n_emp,
                                        uint64_t stats[8]) {
-    fgpu_info i_ = edges_remove_impl(ctx, m, mt, srcs, dsts, ids, n, multi_key, multi_off, multi_ids, n_multi, m_out, mt_out, hit,
-                                     multi_taken, emp_row, emp_col, n_emp, stats);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handles may go to another thread
-    return i_;
+    return published(ctx, edges_remove_impl(ctx, m, mt, srcs, dsts, ids, n, multi_key, multi_off, multi_ids, n_multi, m_out, mt_out,
+                                            hit, multi_taken, emp_row, emp_col, n_emp, stats));
 }

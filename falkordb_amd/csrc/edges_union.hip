@@ -5,7 +5,7 @@
 // extends the row (tensor.rs:383-418).  On sets that is a union per pair: a pair only the batch names enters with the batch's
 // value; a pair stored on both sides ends MULTI_EDGE with the ascending merge of both id lists; the rest of m stays.
 //
-//   classify  a lane per stored entry q of fwd (its row from the wordrow index of compact.hpp, hrows included): binary search of
+//   classify  a lane per stored entry q of fwd (its row from the wordrow index of bulk.hpp, hrows included): binary search of
 //             row src of m for dst gives lb[q], the entry of m it meets or the position it would be inserted at.  Met = the pair
 //             collides: each side is its inline id or, under MULTI_EDGE, the supplied row found by a search of a_key / b_key.
 //             The same search of bwd's entries in mt, without the sides
@@ -22,57 +22,9 @@
 //
 // A lane per item everywhere, no wavefront or loop per row or per run.  The atomics count: a ballot and one add per wavefront
 // for the counters, one add per new entry into the histogram that the scan turns into shifts.  They place nothing.
-#include "compact.hpp"
+#include "bulk.hpp"
 
 namespace fgpu {
-
-__device__ __forceinline__ u32 eu_lower32(const u32* __restrict__ a, u32 b, u32 e, u32 x) {
-    u32 lo = b, hi = e;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// position of key in the ascending keys[0, n), or ~0u
-__device__ __forceinline__ u32 eu_find64(const u64* __restrict__ keys, u32 n, u64 key) {
-    u32 lo = 0, hi = n;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < n && keys[lo] == key) ? lo : ~0u;
-}
-// first entry of the first stored row at or past r (r <= nrows)
-__device__ __forceinline__ u32 eu_row_begin(const CsrView& a, u32 r) {
-    if (!a.hrows) return a.rowptr[r];
-    return a.rowptr[eu_lower32(a.hrows, 0, a.nvec, r)];
-}
-// the entry (r, c) of a, or the position it would be inserted at (r < nrows)
-__device__ __forceinline__ u32 eu_locate(const CsrView& a, u32 r, u32 c, bool& found) {
-    u32 b, e;
-    if (!a.hrows) {
-        b = a.rowptr[r];
-        e = a.rowptr[r + 1];
-    } else {
-        const u32 i = eu_lower32(a.hrows, 0, a.nvec, r);
-        if (i == a.nvec || a.hrows[i] != r) { found = false; return a.rowptr[i]; }
-        b = a.rowptr[i];
-        e = a.rowptr[i + 1];
-    }
-    const u32 lo = eu_lower32(a.colidx, b, e, c);
-    found = lo < e && a.colidx[lo] == c;
-    return lo;
-}
-__device__ __forceinline__ u32 eu_entry_row(const CsrView& a, const u32* __restrict__ wordrow, u32 q) {
-    const u32 w = q >> 6;
-    const u32 i = dt_row_of(a.rowptr, wordrow[w], wordrow[w + 1], q);
-    return a.hrows ? a.hrows[i] : i;
-}
-__device__ __forceinline__ void eu_count(bool flag, u32* __restrict__ counter) {
-    const u64 b = __ballot(flag);
-    if (lane_id() == 0 && b) atomicAdd(counter, (u32)__popcll(b));
-}
 
 // a lane per entry q of fwd (q == nnz: the closing zeros of the three scans).
 // cnt: [0] promoted [1] extended [2] MULTI_EDGE in m without an a row [3] MULTI_EDGE in fwd without a b row
@@ -88,9 +40,9 @@ __global__ __launch_bounds__(256) void eu_classify_kernel(CsrView m, const u64* 
     if (q64 == nnz) isnew[nnz] = collide[nnz] = len[nnz] = 0u;
     if (q64 < nnz) {
         const u32 q = (u32)q64;
-        const u32 src = eu_entry_row(f, wordrow, q), dst = f.colidx[q];
+        const u32 src = entry_row(f, wordrow, q), dst = f.colidx[q];
         bool found;
-        const u32 p = eu_locate(m, src, dst, found);
+        const u32 p = locate(m, src, dst, found);
         u32 la = 0, sa = 0, lbn = 0, sb = 0;
         if (found) {
             const u64 key = ((u64)src << 32) | dst;
@@ -100,7 +52,7 @@ __global__ __launch_bounds__(256) void eu_classify_kernel(CsrView m, const u64* 
                 sa = p;
             } else {
                 extended = true;
-                const u32 r = eu_find64(akey, n_a, key);
+                const u32 r = find(akey, 0u, n_a, key);
                 if (r == ~0u) missA = true;
                 else { sa = aoff[r]; la = aoff[r + 1] - sa; }
             }
@@ -108,7 +60,7 @@ __global__ __launch_bounds__(256) void eu_classify_kernel(CsrView m, const u64* 
                 lbn = 1u;
                 sb = q;
             } else {
-                const u32 r = eu_find64(bkey, n_b, key);
+                const u32 r = find(bkey, 0u, n_b, key);
                 if (r == ~0u) missB = true;
                 else { sb = boff[r]; lbn = boff[r + 1] - sb; }
             }
@@ -121,10 +73,10 @@ __global__ __launch_bounds__(256) void eu_classify_kernel(CsrView m, const u64* 
         lenA[q] = la;
         startB[q] = sb;
     }
-    eu_count(promoted, cnt + 0);
-    eu_count(extended, cnt + 1);
-    eu_count(missA, cnt + 2);
-    eu_count(missB, cnt + 3);
+    count_if(promoted, cnt + 0);
+    count_if(extended, cnt + 1);
+    count_if(missA, cnt + 2);
+    count_if(missB, cnt + 3);
 }
 
 // the pattern side: a lane per entry q of bwd against mt
@@ -135,7 +87,7 @@ __global__ __launch_bounds__(256) void eu_locate_kernel(CsrView a, CsrView b, co
     if (q64 == nnz) { isnew[nnz] = 0u; return; }
     const u32 q = (u32)q64;
     bool found;
-    lb[q] = eu_locate(a, eu_entry_row(b, wordrow, q), b.colidx[q], found);
+    lb[q] = locate(a, entry_row(b, wordrow, q), b.colidx[q], found);
     isnew[q] = found ? 0u : 1u;
 }
 
@@ -151,7 +103,7 @@ __global__ __launch_bounds__(256) void eu_rows_kernel(CsrView f, const u32* __re
         const u32 r = C[q];
         if (C[q + 1] != r) {
             rowq[r] = q;
-            okey[r] = ((u64)eu_entry_row(f, wordrow, q) << 32) | f.colidx[q];
+            okey[r] = ((u64)entry_row(f, wordrow, q) << 32) | f.colidx[q];
             ooff[r] = L[q];
             mine = L[q + 1] - L[q];
         }
@@ -173,8 +125,7 @@ __global__ __launch_bounds__(256) void eu_ids_kernel(const u32* __restrict__ oof
     const u64 t64 = (u64)blockIdx.x * 256 + threadIdx.x;
     bool equal = false;
     if (t64 < total) {
-        const u32 t = (u32)t64, w = t >> 6;
-        const u32 r = dt_row_of(ooff, idrow[w], idrow[w + 1], t);
+        const u32 t = (u32)t64, r = entry_vec(ooff, idrow, t);
         const u32 o0 = ooff[r], k = t - o0, q = rowq[r];
         const u32 la = lenA[q], lbn = ooff[r + 1] - o0 - la;
         const u64* __restrict__ A = (la == 1u ? mvals : aids) + startA[q];    // (a supplied row holds at least 2 ids)
@@ -182,7 +133,7 @@ __global__ __launch_bounds__(256) void eu_ids_kernel(const u32* __restrict__ oof
         // i = ids of A among the first k of the merge (A first on a tie): the least i with A[i] > B[k - i - 1]
         u32 lo = k > lbn ? k - lbn : 0u, hi = k < la ? k : la;
         while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
+            const u32 mid = lo + ((hi - lo) >> 1);
             if (A[mid] <= B[k - mid - 1]) lo = mid + 1; else hi = mid;
         }
         const u32 i = lo, j = k - lo;
@@ -190,7 +141,7 @@ __global__ __launch_bounds__(256) void eu_ids_kernel(const u32* __restrict__ oof
         equal = i < la && j < lbn && x == y;
         out[t] = (j >= lbn || (i < la && x <= y)) ? x : y;
     }
-    eu_count(equal, both);
+    count_if(equal, both);
 }
 
 // H[lb[q]] += 1 for every new entry q of the batch: the scan of H is the shift of the base's entries
@@ -231,7 +182,7 @@ __global__ __launch_bounds__(256) void eu_rowptr_kernel(CsrView a, CsrView b, co
                                                        u32* __restrict__ rp) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r > nrows) return;
-    rp[r] = eu_row_begin(a, (u32)r) + N[eu_row_begin(b, (u32)r)];
+    rp[r] = row_begin(a, (u32)r) + N[row_begin(b, (u32)r)];
 }
 __global__ __launch_bounds__(256) void eu_rowflag_kernel(const u32* __restrict__ rp, u64 nrows, u32* __restrict__ F) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
@@ -253,17 +204,16 @@ __global__ __launch_bounds__(256) void eu_rows_hyper_kernel(const u32* __restric
 struct EuSide {
     const fgpu_mat* a = nullptr;
     const fgpu_mat* b = nullptr;
-    DtPass wr;            // b's wordrow index
+    DevBuf<u32> wordrow;  // b's
     DevBuf<u32> lb, N;    // per entry of b; N has nnz + 1 entries
 };
 
 static fgpu_info eu_side_alloc(fgpu_ctx* ctx, EuSide& s, const fgpu_mat* a, const fgpu_mat* b) {
     s.a = a;
     s.b = b;
-    s.wr.a = b;
     FGPU_TRY(s.lb.alloc(ctx, b->nnz));
     FGPU_TRY(s.N.alloc(ctx, b->nnz + 1));
-    if (b->nnz) return dt_wordrow(ctx, s.wr);
+    if (b->nnz) return wordrow_build(ctx, b->rowptr, b->nvec, b->nnz, s.wordrow);
     FGPU_HIP(hipMemsetAsync(s.N.p, 0, sizeof(u32), ctx->stream()));
     return FGPU_OK;
 }
@@ -285,7 +235,7 @@ static fgpu_info eu_place(fgpu_ctx* ctx, const EuSide& s, u64 n_new, MatRef& out
                     orp.p));
     u32 nvec_out = 0;
     bool hyper = false;
-    if (nrows > 4096) {   // (below that no builder stores a matrix hypersparse)
+    if (nrows > HYPER_MIN_ROWS) {
         DevBuf<u32> tot;
         FGPU_TRY(tot.alloc(ctx, 1));
         FGPU_TRY(F.alloc(ctx, nrows + 1));
@@ -311,45 +261,6 @@ static fgpu_info eu_place(fgpu_ctx* ctx, const EuSide& s, u64 n_new, MatRef& out
     return FGPU_OK;
 }
 
-// the row arrays of one side checked as fgpu_edges_remove checks its own, offsets narrowed to 32 bits
-static fgpu_info eu_check_rows(const char* side, const u64* key, const u64* off, const u64* ids, u64 n, std::vector<u32>& off32) {
-    off32.assign((size_t)n + 1, 0u);
-    FGPU_REQUIRE(n == 0 || off[0] == 0, FGPU_INVALID, "fgpu_edges_union: %s_off[0] is not 0", side);
-    for (u64 r = 0; r < n; ++r) {
-        FGPU_REQUIRE(r == 0 || key[r - 1] < key[r], FGPU_INVALID, "fgpu_edges_union: %s key %llu is not above the one before it", side,
-                     (unsigned long long)r);
-        const u64 b = off[r], e = off[r + 1];
-        FGPU_REQUIRE(e >= b + 2 && e < 0xFFFFFFFFull, FGPU_INVALID,
-                     "fgpu_edges_union: %s row %llu holds fewer than 2 ids (offsets %llu, %llu)", side, (unsigned long long)r,
-                     (unsigned long long)b, (unsigned long long)e);
-        for (u64 j = b + 1; j < e; ++j)
-            FGPU_REQUIRE(ids[j - 1] < ids[j], FGPU_INVALID, "fgpu_edges_union: the ids of %s row %llu do not ascend", side,
-                         (unsigned long long)r);
-        FGPU_REQUIRE(ids[e - 1] != FGPU_MULTI_EDGE, FGPU_INVALID, "fgpu_edges_union: %s row %llu carries the MULTI_EDGE marker as an id",
-                     side, (unsigned long long)r);
-        off32[r + 1] = (u32)e;
-    }
-    return FGPU_OK;
-}
-
-struct EuRows {   // one side's rows on the device
-    DevBuf<u64> key, ids;
-    DevBuf<u32> off;
-};
-static fgpu_info eu_upload_rows(fgpu_ctx* ctx, EuRows& d, const u64* key, const std::vector<u32>& off32, const u64* ids, u64 n) {
-    const u64 T = off32[n];
-    FGPU_TRY(d.key.alloc(ctx, n));
-    FGPU_TRY(d.off.alloc(ctx, n + 1));
-    FGPU_TRY(d.ids.alloc(ctx, T));
-    ProfScope prof(ctx, "eu_h2d", n * 12 + T * 8);
-    FGPU_TRY(ctx->h2d(d.off.p, off32.data(), (n + 1) * sizeof(u32)));
-    if (n) {
-        FGPU_TRY(ctx->h2d(d.key.p, key, n * sizeof(u64)));
-        FGPU_TRY(ctx->h2d(d.ids.p, ids, T * sizeof(u64)));
-    }
-    return FGPU_OK;
-}
-
 static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* mt, const u64* a_key, const u64* a_off,
                                   const u64* a_ids, u64 n_a, const fgpu_mat* fwd, const fgpu_mat* bwd, const u64* b_key,
                                   const u64* b_off, const u64* b_ids, u64 n_b, fgpu_mat** m_out, fgpu_mat** mt_out, u64** o_key,
@@ -367,26 +278,20 @@ static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_m
     FGPU_REQUIRE(fwd->nrows == m->nrows && fwd->ncols == m->ncols, FGPU_INVALID,
                  "fgpu_edges_union: fwd is %llu x %llu, m is %llu x %llu", (unsigned long long)fwd->nrows,
                  (unsigned long long)fwd->ncols, (unsigned long long)m->nrows, (unsigned long long)m->ncols);
-    for (const fgpu_mat* t : {mt, bwd}) {
-        const char* name = t == mt ? "mt" : "bwd";
-        FGPU_REQUIRE(t, FGPU_INVALID, "fgpu_edges_union: the transposed pattern %s is missing", name);
-        FGPU_REQUIRE(t->nrows == m->ncols && t->ncols == m->nrows && !t->vals, FGPU_INVALID,
-                     "fgpu_edges_union: %s must be the BOOL %llu x %llu pattern (got %llu x %llu%s)", name,
-                     (unsigned long long)m->ncols, (unsigned long long)m->nrows, (unsigned long long)t->nrows,
-                     (unsigned long long)t->ncols, t->vals ? ", valued" : "");
-    }
+    FGPU_TRY(require_pattern_of("fgpu_edges_union", "mt", mt, m));
+    FGPU_TRY(require_pattern_of("fgpu_edges_union", "bwd", bwd, m));
     FGPU_REQUIRE(n_a < 0xFFFFFFFFull && n_b < 0xFFFFFFFFull, FGPU_INVALID,
                  "fgpu_edges_union: %llu + %llu rows exceed the 32-bit position space", (unsigned long long)n_a,
                  (unsigned long long)n_b);
-    std::vector<u32> aoff32, boff32;
-    FGPU_TRY(eu_check_rows("a", a_key, a_off, a_ids, n_a, aoff32));
-    FGPU_TRY(eu_check_rows("b", b_key, b_off, b_ids, n_b, boff32));
+    MultiRows da, db;
+    FGPU_TRY(da.check("fgpu_edges_union", "a", a_key, a_off, a_ids, n_a));
+    FGPU_TRY(db.check("fgpu_edges_union", "b", b_key, b_off, b_ids, n_b));
     const u64 nf = fwd->nnz;
     FGPU_REQUIRE(m->nnz + nf < 0xFFFFFFFFull && mt->nnz + bwd->nnz < 0xFFFFFFFFull, FGPU_INVALID,
                  "fgpu_edges_union: %llu + %llu entries exceed the 32-bit position space", (unsigned long long)m->nnz,
                  (unsigned long long)nf);
     // every out row is at most a row of a or one inline id, plus a row of b or one inline id
-    FGPU_REQUIRE((u64)aoff32[n_a] + boff32[n_b] + 2 * nf < 0xFFFFFFFFull, FGPU_INVALID,
+    FGPU_REQUIRE(da.total() + db.total() + 2 * nf < 0xFFFFFFFFull, FGPU_INVALID,
                  "fgpu_edges_union: the merged ids may reach 2^32 - 1, the limit of the 32-bit scans");
     hipStream_t st = ctx->stream();
     // ---- classify + scans -------------------------------------------------------------------------------------------------
@@ -395,12 +300,11 @@ static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_m
     DevBuf<u32> tot, C, L, startA, lenA, startB;
     FGPU_TRY(tot.alloc(ctx, 10));
     FGPU_HIP(hipMemsetAsync(tot.p, 0, 10 * sizeof(u32), st));
-    EuRows da, db;
     EuSide sf, sb;
     u32 h[8] = {0};
     if (nf) {
-        FGPU_TRY(eu_upload_rows(ctx, da, a_key, aoff32, a_ids, n_a));
-        FGPU_TRY(eu_upload_rows(ctx, db, b_key, boff32, b_ids, n_b));
+        FGPU_TRY(da.upload(ctx, "eu_h2d"));
+        FGPU_TRY(db.upload(ctx, "eu_h2d"));
     }
     FGPU_TRY(eu_side_alloc(ctx, sf, m, fwd));
     FGPU_TRY(eu_side_alloc(ctx, sb, mt, bwd));
@@ -413,7 +317,7 @@ static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_m
         {
             ProfScope prof(ctx, "eu_classify", nf * 40);   // (plus one 64-byte line per probe step: the searches are the cost)
             FGPU_TRY(launch(eu_classify_kernel, dim3(cdiv(nf + 1, 256)), dim3(256), 0, st, view_of(m), (const u64*)m->vals, view_of(fwd),
-                            (const u64*)fwd->vals, (const u32*)sf.wr.wordrow.p, (u32)nf, (const u64*)da.key.p, (const u32*)da.off.p,
+                            (const u64*)fwd->vals, (const u32*)sf.wordrow.p, (u32)nf, (const u64*)da.key.p, (const u32*)da.off.p,
                             (u32)n_a, (const u64*)db.key.p, (const u32*)db.off.p, (u32)n_b, sf.lb.p, sf.N.p, C.p, L.p, startA.p, lenA.p,
                             startB.p, tot.p + 4));
         }
@@ -425,7 +329,7 @@ static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_m
     if (bwd->nnz) {
         ProfScope prof(ctx, "eu_locate_t", bwd->nnz * 16);
         FGPU_TRY(launch(eu_locate_kernel, dim3(cdiv(bwd->nnz + 1, 256)), dim3(256), 0, st, view_of(mt), view_of(bwd),
-                        (const u32*)sb.wr.wordrow.p, (u32)bwd->nnz, sb.lb.p, sb.N.p));
+                        (const u32*)sb.wordrow.p, (u32)bwd->nnz, sb.lb.p, sb.N.p));
         FGPU_TRY(scan_u32(ctx, sb.N.p, sb.N.p, bwd->nnz + 1, tot.p + 3));
     }
     if (nf || bwd->nnz) FGPU_TRY(read_words(ctx, tot.p, 8, h));
@@ -440,16 +344,13 @@ static fgpu_info edges_union_impl(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_m
     u32 h2[2] = {0, 0};
     FGPU_TRY(ooff.alloc(ctx, n_o + 1));
     if (n_o) {
-        const u32 nwords = (u32)((total + 63) >> 6);
         FGPU_TRY(rowq.alloc(ctx, n_o));
         FGPU_TRY(okey.alloc(ctx, n_o));
         FGPU_TRY(oids.alloc(ctx, total));
-        FGPU_TRY(idrow.alloc(ctx, (size_t)nwords + 1));
         ProfScope prof(ctx, "eu_ids", nf * 12 + total * 24);
-        FGPU_TRY(launch(eu_rows_kernel, dim3(cdiv(nf, 256)), dim3(256), 0, st, view_of(fwd), (const u32*)sf.wr.wordrow.p, (u32)nf,
+        FGPU_TRY(launch(eu_rows_kernel, dim3(cdiv(nf, 256)), dim3(256), 0, st, view_of(fwd), (const u32*)sf.wordrow.p, (u32)nf,
                         (const u32*)C.p, (const u32*)L.p, (u32)n_o, rowq.p, okey.p, ooff.p, tot.p + 9));
-        FGPU_TRY(launch(dt_wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, st, (const u32*)ooff.p, (u32)n_o, nwords,
-                        idrow.p));
+        FGPU_TRY(wordrow_build(ctx, ooff.p, (u32)n_o, total, idrow));
         FGPU_TRY(launch(eu_ids_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const u32*)ooff.p, (const u32*)idrow.p, (u32)total,
                         (const u32*)rowq.p, (const u32*)startA.p, (const u32*)lenA.p, (const u32*)startB.p, (const u64*)m->vals,
                         (const u64*)da.ids.p, (const u64*)fwd->vals, (const u64*)db.ids.p, oids.p, tot.p + 8));
@@ -505,8 +406,6 @@ extern "C" fgpu_info fgpu_edges_union(fgpu_ctx* ctx, const fgpu_mat* m, const fg
                                       const fgpu_mat* bwd, const uint64_t* b_key, const uint64_t* b_off, const uint64_t* b_ids,
                                       uint64_t n_b, fgpu_mat** m_out, fgpu_mat** mt_out, uint64_t** o_key, uint64_t** o_off,
                                       uint64_t** o_ids, uint64_t* n_o, uint64_t stats[8]) {
-    fgpu_info i_ = edges_union_impl(ctx, m, mt, a_key, a_off, a_ids, n_a, fwd, bwd, b_key, b_off, b_ids, n_b, m_out, mt_out, o_key, o_off,
-                                    o_ids, n_o, stats);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handles may go to another thread
-    return i_;
+    return published(ctx, edges_union_impl(ctx, m, mt, a_key, a_off, a_ids, n_a, fwd, bwd, b_key, b_off, b_ids, n_b, m_out, mt_out, o_key,
+                                           o_off, o_ids, n_o, stats));
 }

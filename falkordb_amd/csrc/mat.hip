@@ -261,7 +261,7 @@ static fgpu_info upload_host_csr(fgpu_ctx* ctx, fgpu_mat** out, u64 nrows, u64 n
 
 // Decide the storage form of a host-built matrix: hypersparse when few rows are populated
 // (delta layers are pinned hypersparse in the reference, versioned_matrix.rs Delta::new).
-static bool prefer_hyper(u64 nrows, u64 nvec) { return nrows > 4096 && nvec * 16 <= nrows; }
+static bool prefer_hyper(u64 nrows, u64 nvec) { return nrows > HYPER_MIN_ROWS && nvec * 16 <= nrows; }
 bool mat_prefer_hyper(u64 nrows, u64 nvec) { return prefer_hyper(nrows, nvec); }   // (the same rule for fgpu_nodes_detach's outputs)
 
 // ---------------------------------------------------------------------------------

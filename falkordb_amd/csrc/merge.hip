@@ -23,7 +23,7 @@
 //                kept entries (binary search in the other layer's row; both rows are sorted)
 // HBM traffic (pattern): 2 x 4 nnz(m) read + 4 nnz(out) written + O(N) row arrays, against
 // B_alg = 4(nnz(m)+nnz(dp)+nnz(dm)) + 4 nnz(out) + 8(N+1).
-#include "common.hpp"
+#include "bulk.hpp"
 
 namespace fgpu {
 
@@ -33,15 +33,6 @@ struct Layer {        // one layer: the (possibly hypersparse) CSR view, its val
     const u32* wordrow;
     u32 nnz;
 };
-
-// largest i in [lo, hi] with rp[i] <= p (rows may be empty: equal row pointers)
-__device__ __forceinline__ u32 row_of(const u32* __restrict__ rp, u32 lo, u32 hi, u32 p) {
-    while (lo < hi) {
-        u32 mid = (lo + hi + 1) >> 1;
-        if (rp[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ u32 lower_bound_col(const u32* __restrict__ col, u32 b, u32 e, u32 key) {
     while (b < e) {
@@ -64,13 +55,6 @@ __device__ __forceinline__ u32 kept_before(const u64* __restrict__ kb, const u32
     u64 w = kb[p >> 6];
     u32 s = p & 63;
     return ks[p >> 6] + (u32)__popcll(s ? (w & ((1ull << s) - 1ull)) : 0ull);
-}
-
-// stored-row index of the first entry of each 64-entry word; wordrow[nwords] = last stored row
-__global__ void wordrow_kernel(const u32* __restrict__ rp, u32 nvec, u32 nwords, u32* __restrict__ wordrow) {
-    u32 w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w > nwords) return;
-    wordrow[w] = w < nwords ? row_of(rp, 0, nvec - 1, w << 6) : nvec - 1;
 }
 
 __global__ void rowbits_kernel(CsrView d, u32* __restrict__ bits) {
@@ -400,11 +384,8 @@ fgpu_info mat_wordrow(fgpu_ctx* ctx, const fgpu_mat* a, const u32** out) {
     if (a->nnz == 0) return FGPU_OK;
     std::lock_guard<std::mutex> idx_guard(a->idx_mu);
     if (!a->wordrow.p) {
-        const u32 nwords = (u32)((a->nnz + 63) >> 6);
         DevBuf<u32> wr;
-        FGPU_TRY(wr.alloc(ctx, (size_t)nwords + 1));
-        FGPU_TRY(launch(wordrow_kernel, dim3(cdiv((u64)nwords + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)a->rowptr, a->nvec,
-                        nwords, wr.p));
+        FGPU_TRY(wordrow_build(ctx, a->rowptr, a->nvec, a->nnz, wr));
         // complete on the device before it is moved in: other lanes read it from their own streams
         if (ctx->multi_lane()) FGPU_TRY(fgpu_sync(ctx));
         a->wordrow = std::move(wr);
@@ -643,15 +624,11 @@ extern "C" {
 
 fgpu_info fgpu_mat_merge_pattern(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* m, const fgpu_mat* dp,
                                  const fgpu_mat* dm, int dm_masks_dp) {
-    fgpu_info i_ = mat_merge_pattern_impl(ctx, out, m, dp, dm, dm_masks_dp);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handle may go to another thread
-    return i_;
+    return fgpu::published(ctx, mat_merge_pattern_impl(ctx, out, m, dp, dm, dm_masks_dp));
 }
 
 fgpu_info fgpu_mat_resize(fgpu_ctx* ctx, fgpu_mat** out, const fgpu_mat* a, uint64_t nrows, uint64_t ncols) {
-    fgpu_info i_ = mat_resize_impl(ctx, out, a, nrows, ncols);
-    if (i_ == FGPU_OK && ctx) i_ = ctx->publish();   // the new handle may go to another thread
-    return i_;
+    return fgpu::published(ctx, mat_resize_impl(ctx, out, a, nrows, ncols));
 }
 
 }  // extern "C"

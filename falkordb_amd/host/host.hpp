@@ -414,6 +414,21 @@ class Tensor {
     void wait() const { wait_fwd(); mt_.wait(); }                           // Tensor::wait: every layer materialised
 
    private:
+    using MeRow = std::map<u64, std::vector<u64>>::iterator;
+    struct BuiltBatch;   // what fgpu_edges_build made of a batch (tensor.cpp)
+    // The steps the bulk mutations share.  fold_for_bulk: a bulk mutation starts folded (flush_for_bulk) — whatever dp / dm and
+    // mt's deltas hold goes into the bases, which are all the device pass reads.  gather_me_rows: the me rows of the batch's
+    // pairs that hold MULTI_EDGE, sorted unique by key, as fgpu_edges_union / fgpu_edges_remove take them (off starts as {0});
+    // ONE probe of the folded base, then one find per such pair; `rows` (nullable) receives the map positions.  build_batch:
+    // fgpu_edges_build of a batch, its pieces adopted.  adopt_bases: the results of a device pass become m and mt (replaced,
+    // never mutated: a dup()ed version keeps its snapshot).
+    void fold_for_bulk();
+    void gather_me_rows(const u64* srcs, const u64* dsts, u64 n, std::vector<u64>& key, std::vector<u64>& off, std::vector<u64>& run,
+                        std::vector<MeRow>* rows);
+    BuiltBatch build_batch(const u64* srcs, const u64* dsts, const u64* ids, u64 n, const char* who) const;
+    void adopt_bases(const Matrix& m, const Matrix& mt);
+    void adopt_bases(fgpu_mat* mo, fgpu_mat* mto, bool changed);   // (engine-made outputs: owned from here on either way)
+
     Matrix m_;
     mutable Delta dp_, dm_;
     VersionedMatrix mt_;

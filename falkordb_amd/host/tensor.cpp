@@ -171,6 +171,7 @@ struct EngineArray {   // a result array of the engine, given back on every exit
     u64* p = nullptr;
     explicit EngineArray(fgpu_ctx* c) : ctx(c) {}
     ~EngineArray() { if (p) fgpu_free(ctx, p); }
+    EngineArray(EngineArray&& o) : ctx(o.ctx), p(o.p) { o.p = nullptr; }
     EngineArray(const EngineArray&) = delete;
     EngineArray& operator=(const EngineArray&) = delete;
 };
@@ -178,6 +179,74 @@ struct EngineArray {   // a result array of the engine, given back on every exit
 
 u64 bulk_clock_ns() {
     return (u64)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct Tensor::BuiltBatch {
+    Matrix fwd, bwd;               // the batch's UINT64 matrix and its transposed pattern
+    EngineArray key, off, ids;     // its multi-edge runs, ascending by key
+    u64 n_multi;
+    u64 st[8];                     // fgpu_edges_build's stats
+};
+
+// the build reads nothing of the tensor: an invalid batch throws here, before any layer moved
+Tensor::BuiltBatch Tensor::build_batch(const u64* srcs, const u64* dsts, const u64* ids, u64 n, const char* who) const {
+    Context& ctx = m_.ctx();
+    fgpu_ctx* c = ctx.raw();
+    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
+    EngineArray key(c), off(c), run(c);
+    u64 n_multi = 0, st[8] = {0};
+    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &key.p, &off.p, &run.p, &n_multi, st), who);
+    BuiltBatch b{Matrix::adopt(ctx, Type::UInt64, fwd_h), Matrix::adopt(ctx, Type::Bool, bwd_h), std::move(key), std::move(off),
+                 std::move(run), n_multi, {}};
+    std::copy(st, st + 8, b.st);
+    return b;
+}
+
+void Tensor::fold_for_bulk() {
+    flush();
+    dp_.wait();
+    dm_.wait();
+    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
+        dp_.latch(true);
+        dm_.latch(true);
+        needs_flush_ = true;
+        flush();
+    }
+    mt_.fold_all();
+}
+
+void Tensor::gather_me_rows(const u64* srcs, const u64* dsts, u64 n, std::vector<u64>& key, std::vector<u64>& off, std::vector<u64>& run,
+                            std::vector<MeRow>* rows) {
+    if (!has_multi_edge()) return;
+    std::vector<uint8_t> in_m;
+    std::vector<u64> mv;
+    m_.probe(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), in_m, &mv);
+    for (u64 k = 0; k < n; ++k)
+        if (in_m[k] && mv[k] == MULTI_EDGE) key.push_back(compound_key(srcs[k], dsts[k]));
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    size_t kept = 0;
+    for (u64 x : key) {
+        auto it = me_.find(x);
+        if (it == me_.end() || it->second.size() < 2) continue;   // (the device reports the pair when it needs the row)
+        key[kept++] = x;
+        if (rows) rows->push_back(it);
+        run.insert(run.end(), it->second.begin(), it->second.end());
+        off.push_back(run.size());
+    }
+    key.resize(kept);
+}
+
+void Tensor::adopt_bases(const Matrix& m, const Matrix& mt) {
+    m_ = m;
+    mt_ = VersionedMatrix::from_matrix(mt);
+}
+
+// the outputs of a device pass over the folded bases; one that changed nothing leaves the bases the snapshots they are
+void Tensor::adopt_bases(fgpu_mat* mo, fgpu_mat* mto, bool changed) {
+    Matrix new_m = Matrix::adopt(m_.ctx(), Type::UInt64, mo);
+    Matrix new_mt = Matrix::adopt(m_.ctx(), Type::Bool, mto);
+    if (changed) adopt_bases(new_m, new_mt);
 }
 
 BulkStats Tensor::bulk_insert(const std::vector<u64>& srcs, const std::vector<u64>& dsts, const std::vector<u64>& ids,
@@ -193,29 +262,12 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
     if (n == 0) return bs;
     Context& ctx = m_.ctx();
     fgpu_ctx* c = ctx.raw();
-    // the build reads nothing of the tensor: an invalid batch throws here, before any layer moved
-    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
-    EngineArray key(c), off(c), run_ids(c);
-    u64 n_multi = 0, st[8] = {0};
     u64 t0 = bulk_clock_ns();
-    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &key.p,
-                           &off.p, &run_ids.p, &n_multi, st),
-          "Tensor::bulk_insert");
-    Matrix fwd = Matrix::adopt(ctx, Type::UInt64, fwd_h);
-    Matrix bwd = Matrix::adopt(ctx, Type::Bool, bwd_h);
+    BuiltBatch b = build_batch(srcs, dsts, ids, n, "Tensor::bulk_insert");
+    const Matrix &fwd = b.fwd, &bwd = b.bwd;
     bs.phase_ns[0] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
-    // a bulk insert ends folded (flush_for_bulk): whatever dp / dm hold goes into m first
-    flush();
-    dp_.wait();
-    dm_.wait();
-    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
-        dp_.latch(true);
-        dm_.latch(true);
-        needs_flush_ = true;
-        flush();
-    }
-    mt_.fold_all();
+    fold_for_bulk();
     const bool empty = m_.nvals() == 0;
     if (!empty && m_.intersection_nvals(fwd) != 0) {
         // a pair of the batch holds an edge already: its promotion is the edge-by-edge path's
@@ -225,8 +277,7 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
         return bs;
     }
     if (empty) {
-        m_ = fwd;
-        mt_ = VersionedMatrix::from_matrix(bwd);
+        adopt_bases(fwd, bwd);
     } else {
         fgpu_mat* merged = nullptr;
         check(fgpu_mat_merge(c, &merged, m_.snapshot(), fwd.snapshot(), nullptr, 0), "Tensor::bulk_insert");
@@ -236,14 +287,14 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
     }
     bs.phase_ns[1] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
-    for (u64 r = 0; r < n_multi; ++r)   // (ascending keys: the hint is the place when the map held nothing above them)
-        me_.emplace_hint(me_.end(), key.p[r], std::vector<u64>(run_ids.p + off.p[r], run_ids.p + off.p[r + 1]));
+    for (u64 r = 0; r < b.n_multi; ++r)   // (ascending keys: the hint is the place when the map held nothing above them)
+        me_.emplace_hint(me_.end(), b.key.p[r], std::vector<u64>(b.ids.p + b.off.p[r], b.ids.p + b.off.p[r + 1]));
     bs.phase_ns[2] = bulk_clock_ns() - t0;
     bs.device_edges = n;
-    bs.distinct_pairs = st[0];
-    bs.multi_pairs = st[1];
-    bs.unsorted_runs = st[4];
-    bs.host_sorted_runs = st[6];
+    bs.distinct_pairs = b.st[0];
+    bs.multi_pairs = b.st[1];
+    bs.unsorted_runs = b.st[4];
+    bs.host_sorted_runs = b.st[6];
     if (built) *built = fwd;
     return bs;
 }
@@ -252,37 +303,21 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
     AppendStats as;
     if (built) built->reset();
     if (n == 0) return as;
-    Context& ctx = m_.ctx();
-    fgpu_ctx* c = ctx.raw();
-    // the build reads nothing of the tensor: an invalid batch throws here, before any layer moved
-    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
-    EngineArray bkey(c), boff(c), bids(c);
-    u64 n_b = 0, st[8] = {0};
+    fgpu_ctx* c = m_.ctx().raw();
     u64 t0 = bulk_clock_ns();
-    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &bkey.p, &boff.p, &bids.p, &n_b, st),
-          "Tensor::append_bulk");
-    Matrix fwd = Matrix::adopt(ctx, Type::UInt64, fwd_h);
-    Matrix bwd = Matrix::adopt(ctx, Type::Bool, bwd_h);
+    BuiltBatch b = build_batch(srcs, dsts, ids, n, "Tensor::append_bulk");
+    const Matrix &fwd = b.fwd, &bwd = b.bwd;
+    const EngineArray &bkey = b.key, &boff = b.off, &bids = b.ids;
+    const u64 n_b = b.n_multi;
     as.phase_ns[0] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
-    // fold first, as bulk_insert does: the device pass reads m and mt alone
-    flush();
-    dp_.wait();
-    dm_.wait();
-    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
-        dp_.latch(true);
-        dm_.latch(true);
-        needs_flush_ = true;
-        flush();
-    }
-    mt_.fold_all();
+    fold_for_bulk();
     as.edges = n;
-    as.distinct_pairs = st[0];
-    as.multi_pairs = st[1];
-    as.host_sorted_runs = st[6];
+    as.distinct_pairs = b.st[0];
+    as.multi_pairs = b.st[1];
+    as.host_sorted_runs = b.st[6];
     if (m_.nvals() == 0) {
-        m_ = fwd;
-        mt_ = VersionedMatrix::from_matrix(bwd);
+        adopt_bases(fwd, bwd);
         as.phase_ns[1] = bulk_clock_ns() - t0;
         t0 = bulk_clock_ns();
         for (u64 r = 0; r < n_b; ++r)
@@ -292,26 +327,8 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
         if (built) *built = fwd;
         return as;
     }
-    // the me rows of the batch's pairs that hold MULTI_EDGE, sorted unique by key: one probe of the folded base, then one find each
     std::vector<u64> akey, aoff{0}, arun;
-    if (has_multi_edge()) {
-        std::vector<uint8_t> in_m;
-        std::vector<u64> mv;
-        m_.probe(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), in_m, &mv);
-        for (u64 k = 0; k < n; ++k)
-            if (in_m[k] && mv[k] == MULTI_EDGE) akey.push_back(compound_key(srcs[k], dsts[k]));
-        std::sort(akey.begin(), akey.end());
-        akey.erase(std::unique(akey.begin(), akey.end()), akey.end());
-        size_t kept = 0;
-        for (u64 x : akey) {
-            auto it = me_.find(x);
-            if (it == me_.end() || it->second.size() < 2) continue;   // (the device reports the pair: it needs the row)
-            akey[kept++] = x;
-            arun.insert(arun.end(), it->second.begin(), it->second.end());
-            aoff.push_back(arun.size());
-        }
-        akey.resize(kept);
-    }
+    gather_me_rows(srcs, dsts, n, akey, aoff, arun, nullptr);
     fgpu_mat *mo = nullptr, *mto = nullptr;
     EngineArray okey(c), ooff(c), oids(c);
     u64 n_o = 0, us[8] = {0};
@@ -319,8 +336,7 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
     check(fgpu_edges_union(c, m_.snapshot(), mt_.m().snapshot(), akey.data(), aoff.data(), arun.data(), akey.size(), fwd.snapshot(),
                            bwd.snapshot(), bkey.p, boff.p, bids.p, n_b, &mo, &mto, &okey.p, &ooff.p, &oids.p, &n_o, us),
           "Tensor::append_bulk");
-    m_ = Matrix::adopt(ctx, Type::UInt64, mo);
-    mt_ = VersionedMatrix::from_matrix(Matrix::adopt(ctx, Type::Bool, mto));
+    adopt_bases(mo, mto, true);
     as.phase_ns[1] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
     // b and o ascend by key, one cursor each: a multi-edge pair only the batch names brings its b row, a colliding pair its o row
@@ -353,32 +369,16 @@ std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nod
     for (u64 v : nodes)
         if (v >= m_.nrows() || v >= m_.ncols())
             throw GrbError(FGPU_INVALID, "Tensor::detach_nodes: node " + std::to_string(v) + " is outside the tensor");
-    Context& ctx = m_.ctx();
-    fgpu_ctx* c = ctx.raw();
+    fgpu_ctx* c = m_.ctx().raw();
     u64 t0 = bulk_clock_ns();
-    // fold first, as bulk_insert does before it adopts a base: the device pass reads m and mt alone
-    flush();
-    dp_.wait();
-    dm_.wait();
-    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
-        dp_.latch(true);
-        dm_.latch(true);
-        needs_flush_ = true;
-        flush();
-    }
-    mt_.fold_all();
+    fold_for_bulk();
     fgpu_mat *mo = nullptr, *mto = nullptr;
     EngineArray rr(c), rc(c), rv(c);
     u64 n_rem = 0, n_out = 0, st[8] = {0};
     check(fgpu_nodes_detach(c, m_.snapshot(), mt_.m().snapshot(), nodes.data(), nodes.size(), 3, &mo, &mto, &rr.p, &rc.p, &rv.p, &n_rem,
                             &n_out, st),
           "Tensor::detach_nodes");
-    Matrix new_m = Matrix::adopt(ctx, Type::UInt64, mo);
-    Matrix new_mt = Matrix::adopt(ctx, Type::Bool, mto);
-    if (n_rem) {   // (nothing incident: the bases stay the snapshots they are)
-        m_ = new_m;
-        mt_ = VersionedMatrix::from_matrix(new_mt);
-    }
+    adopt_bases(mo, mto, n_rem != 0);   // (nothing incident: nothing changed)
     if (counts) counts->phase_ns[0] += bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
     // the reference's order (graph.rs:2405-2427): per node of D ascending its out edges, then its in edges.  The out segment
@@ -535,44 +535,14 @@ std::vector<std::pair<u64, u64>> Tensor::remove_bulk(const u64* srcs, const u64*
         if (srcs[k] >= m_.nrows() || dsts[k] >= m_.ncols())
             throw GrbError(FGPU_INVALID, "Tensor::remove_bulk: edge (" + std::to_string(srcs[k]) + ", " + std::to_string(dsts[k]) +
                                              ") is outside the tensor");
-    Context& ctx = m_.ctx();
-    fgpu_ctx* c = ctx.raw();
+    fgpu_ctx* c = m_.ctx().raw();
     u64 t0 = bulk_clock_ns();
-    // fold first, as detach_nodes does: the device pass reads m and mt alone
-    flush();
-    dp_.wait();
-    dm_.wait();
-    if (dp_.nvals() != 0 || dm_.nvals() != 0) {
-        dp_.latch(true);
-        dm_.latch(true);
-        needs_flush_ = true;
-        flush();
-    }
-    mt_.fold_all();
+    fold_for_bulk();
     const u64 fold_ns = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
-    // the me rows of the batch's multi-edge pairs, sorted unique by key: one probe of the folded base, then one find per such pair
     std::vector<u64> key, off{0}, run;
-    std::vector<std::map<u64, std::vector<u64>>::iterator> rows;
-    if (has_multi_edge()) {
-        std::vector<uint8_t> in_m;
-        std::vector<u64> mv;
-        m_.probe(std::vector<u64>(srcs, srcs + n), std::vector<u64>(dsts, dsts + n), in_m, &mv);
-        for (u64 k = 0; k < n; ++k)
-            if (in_m[k] && mv[k] == MULTI_EDGE) key.push_back(compound_key(srcs[k], dsts[k]));
-        std::sort(key.begin(), key.end());
-        key.erase(std::unique(key.begin(), key.end()), key.end());
-        size_t kept = 0;
-        for (u64 x : key) {
-            auto it = me_.find(x);
-            if (it == me_.end() || it->second.size() < 2) continue;   // (the device reports the pair when a triple needs its row)
-            key[kept++] = x;
-            rows.push_back(it);
-            run.insert(run.end(), it->second.begin(), it->second.end());
-            off.push_back(run.size());
-        }
-        key.resize(kept);
-    }
+    std::vector<MeRow> rows;
+    gather_me_rows(srcs, dsts, n, key, off, run, &rows);
     std::vector<uint8_t> taken(run.size(), 0), hit_local;
     std::vector<uint8_t>& hit = counts ? counts->hit : hit_local;
     hit.assign(n, 0);
@@ -584,12 +554,7 @@ std::vector<std::pair<u64, u64>> Tensor::remove_bulk(const u64* srcs, const u64*
     check(fgpu_edges_remove(c, m_.snapshot(), mt_.m().snapshot(), srcs, dsts, ids, n, key.data(), off.data(), run.data(), key.size(),
                             &mo, &mto, hit.data(), taken.data(), &er.p, &ec.p, &n_emp, st),
           "Tensor::remove_bulk");
-    Matrix new_m = Matrix::adopt(ctx, Type::UInt64, mo);
-    Matrix new_mt = Matrix::adopt(ctx, Type::Bool, mto);
-    if (st[0]) {   // (nothing hit: the bases stay the snapshots they are)
-        m_ = new_m;
-        mt_ = VersionedMatrix::from_matrix(new_mt);
-    }
+    adopt_bases(mo, mto, st[0] != 0);   // (nothing hit: nothing changed)
     emptied.reserve(n_emp);
     for (u64 k = 0; k < n_emp; ++k) emptied.push_back({er.p[k], ec.p[k]});
     const u64 device_ns = fold_ns + (bulk_clock_ns() - t0);

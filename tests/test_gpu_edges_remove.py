@@ -306,6 +306,8 @@ def test_rejections_leave_the_context_usable(ctx):
     short = off.copy()
     short[1:] -= off[1] - U64(1)                                          # the first run keeps one id
     short_ids = np.r_[ids[:1], ids[int(off[1]):]]
+    marker = ids.copy()
+    marker[int(off[1]) - 1] = MULTI
     cases = [
         lambda: call(m, mt, [300], [0], [1]),                             # a source at its dimension
         lambda: call(m, mt, [0], [2**40], [1]),                           # a destination past it
@@ -320,6 +322,7 @@ def test_rejections_leave_the_context_usable(ctx):
         lambda: call(m, mt, [1], [2], [1], key, short, short_ids),        # a run shorter than 2
         lambda: call(m, mt, [1], [2], [1], key, off, swapped),            # ids descending in a run
         lambda: call(m, mt, [1], [2], [1], key, off, equal),              # ... or repeated
+        lambda: call(m, mt, [1], [2], [1], key, off, marker),             # the marker as the last id of a run
         lambda: call(m, mt, [e[0], s], [e[1], d], [e[2], run[0]], key[1:], off[1:] - off[1], ids[int(off[1]):]),   # no row for (s, d)
         lambda: call(m, mt, [s], [d], [5], [], [0], []),                  # ... even when the id would be unknown
     ]

@@ -429,3 +429,32 @@ def test_a_call_keeps_no_device_memory(ctx):
     second = call()
     ctx.sync()
     assert ctx.device_bytes()[0] == in_use and second == first
+
+
+@pytest.mark.parametrize("form", ["full", "hyper"])
+def test_union_then_remove_gives_back_the_inputs(ctx, form):
+    """The shapes of test_a_call_keeps_no_device_memory: the batch joins, then every id of the batch leaves again through
+    fgpu_edges_remove, with the union's out rows and the batch-only b rows as the multi-edge rows.  What is left is m and mt entry
+    for entry: a promoted pair is demoted to the id it held, an extended pair keeps its own run, a pair only the batch named is
+    emptied.  Once over matrices stored full and once with the base, and the union's output before it goes to the removal,
+    stored hypersparse: both entry points search both forms."""
+    n, hyper = 5000, form == "hyper"
+    pairs, rows = multigraph(304, n, 20000)
+    bpairs, brows = batch_on(7, pairs, n, n, 6000, 3000)
+    m, mt = build(ctx, n, n, pairs, hyper)
+    fwd, bwd = build(ctx, n, n, bpairs)
+    mo, mto, ok, oo, oi = engine.edges_union(ctx, m, mt, *flat(rows), fwd, bwd, *flat(brows))
+    if hyper:
+        rp, ci, vals = mo.export_csr()
+        r = np.repeat(np.arange(n), np.diff(rp).astype(np.int64))
+        mo = build(ctx, n, n, dict(zip(zip(r.tolist(), ci.tolist()), vals.tolist())), hyper=True)[0]
+    supplied = {k: v for k, v in brows.items() if k not in pairs}
+    supplied.update({(k >> 32, k & 0xFFFFFFFF): oi[int(oo[j]):int(oo[j + 1])].tolist() for j, k in enumerate(ok.tolist())})
+    t = np.array([(s, d, x) for (s, d), v in bpairs.items() for x in (brows[(s, d)] if v == MULTI else [v])], dtype=U64)
+    sk, so, si = flat(supplied)
+    m2, mt2, hit, taken, er, ec = engine.edges_remove(ctx, mo, mto, t[:, 0], t[:, 1], t[:, 2], sk, so, si)
+    assert_matrix(m2, n, n, pairs, True)
+    assert_matrix(mt2, n, n, transposed(pairs), False)
+    assert len(hit) == len(t) and hit.all()
+    assert list(zip(er.tolist(), ec.tolist())) == sorted(k for k in bpairs if k not in pairs)
+    assert np.array_equal(taken, np.isin(si, t[:, 2]).astype(np.uint8))
