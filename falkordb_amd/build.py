@@ -112,7 +112,7 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     libfgpu.so only through include/fgpu.h (rpath $ORIGIN, both libraries live in falkordb_amd/lib)."""
     build_lib(force=False, verbose=verbose)
     srcs = [os.path.join(HOST_DIR, f) for f in HOST_SOURCES]
-    deps = srcs + [os.path.join(HOST_DIR, "host.hpp")] + [
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("host.hpp", "owned.hpp")] + [
         os.path.join(os.path.dirname(HERE), "include", f) for f in ("fgpu.h", "falkor_host.h")]
     dg = _digest(deps, "host -O2")
     if not force and not _stale(HOST_LIB, dg):
@@ -140,7 +140,7 @@ def build_shim(force: bool = False, verbose: bool = False) -> str:
     the reference's matrix.rs binds, for BOOL / UINT64 + ANY_PAIR, on this engine."""
     build_host(force=False, verbose=verbose)
     src = os.path.join(HERE, "shim", "graphblas_shim.cpp")
-    deps = [src, os.path.join(HOST_DIR, "host.hpp"), HOST_LIB + ".sha"]
+    deps = [src, os.path.join(HOST_DIR, "host.hpp"), os.path.join(HOST_DIR, "owned.hpp"), HOST_LIB + ".sha"]
     deps.append(os.path.join(HERE, "shim", "shim_internal.hpp"))
     dg = _digest(deps, "shim -O2")
     if force or _stale(SHIM_LIB, dg):

@@ -493,17 +493,15 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
         if (flops) *flops = fl;
         lap("fgpu_expand_probe");
     } else {
-    void* prow = nullptr;
-    uint32_t* pdest = nullptr;
     const int row_bits = k > 65536 ? 32 : 16;                // (more than 64 child batches coalesced into one call)
+    rows.row_pin = EngineBuf<uint16_t>(ctx);
+    rows.row_pin32 = EngineBuf<uint32_t>(ctx);
+    rows.dest_pin = EngineBuf<uint32_t>(ctx);
+    void** prow = row_bits == 16 ? (void**)rows.row_pin.out() : (void**)rows.row_pin32.out();
     check(fgpu_expand_pairs32(ctx, src_ids.data(), k, hl.m.data(), hl.dp.data(), hl.dm.data(), (int)hops.size(),
-                              bitmap.empty() ? nullptr : bitmap.data(), pinned_to.empty() ? nullptr : pinned_to.data(), row_bits, &prow,
-                              &pdest, &np, &fl),
+                              bitmap.empty() ? nullptr : bitmap.data(), pinned_to.empty() ? nullptr : pinned_to.data(), row_bits, prow,
+                              rows.dest_pin.out(), &np, &fl),
           "CondTraverse::expand_batch");
-    rows.pin_ctx = ctx;
-    rows.row_pin = row_bits == 16 ? (const uint16_t*)prow : nullptr;
-    rows.row_pin32 = row_bits == 32 ? (const uint32_t*)prow : nullptr;
-    rows.dest_pin = pdest;
     rows.n_pin = np;
     if (flops) *flops = fl;
     lap("fgpu_expand_pairs");
@@ -547,20 +545,11 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
     return true;
 }
 
-void ExpandedRows::release_pinned() {
-    if (pin_ctx) {
-        if (row_pin) fgpu_free(pin_ctx, (void*)row_pin);
-        if (row_pin32) fgpu_free(pin_ctx, (void*)row_pin32);
-        if (dest_pin) fgpu_free(pin_ctx, (void*)dest_pin);
-    }
-    pin_ctx = nullptr; row_pin = nullptr; row_pin32 = nullptr; dest_pin = nullptr; n_pin = 0;
-}
-
 void ExpandedRows::materialize() {
     if (!pinned()) return;
     active_row.resize(n_pin);
     dest.resize(n_pin);
-    for (size_t i = 0; i < n_pin; ++i) { active_row[i] = row_pin ? (u64)row_pin[i] : (u64)row_pin32[i]; dest[i] = dest_pin[i]; }
+    for (size_t i = 0; i < n_pin; ++i) { active_row[i] = row_pin.p ? (u64)row_pin.p[i] : (u64)row_pin32.p[i]; dest[i] = dest_pin.p[i]; }
     release_pinned();
 }
 
@@ -924,13 +913,13 @@ std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64
     u64 k = 0;
     EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth)
     check(fgpu_shortest_dag(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), src, dst, max_hops == UINT32_MAX ? -1 : (int64_t)max_hops,
-                            &L, &k, &dag.rows, &dag.cols, (uint64_t**)&dag.vals, nullptr),
+                            &L, &k, dag.rows.out(), dag.cols.out(), (uint64_t**)dag.vals.out(), nullptr),
           "allShortestPaths");
     dag.n = k;
     if (L < 0) return out;
     if (length) *length = L;
     // the relationships behind every pair, per type: (u, v), and (v, u) under a bidirectional pattern
-    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
+    const std::vector<u64> from(dag.rows.p, dag.rows.p + k), to(dag.cols.p, dag.cols.p + k);
     std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
     for (size_t t = 0; t < tids.size(); ++t) {
         g.relationship_tensors()[tids[t]].get_batch(from, to, fwd[t]);
@@ -967,14 +956,14 @@ std::vector<std::vector<std::vector<u64>>> AllShortestPathsOp::expand_batch(cons
     std::vector<u64> off(row.size() + 1, 0);
     EdgeList dag(g.ctx());                                               // (rows, cols, vals) = (from, to, depth) of every row
     check(fgpu_shortest_dag_batch(g.ctx().raw(), adj.snapshot(), adj_t.snapshot(), s.data(), d.data(), row.size(),
-                                  max_hops == UINT32_MAX ? -1 : (int64_t)max_hops, 0, L.data(), off.data(), &dag.rows, &dag.cols,
-                                  (uint64_t**)&dag.vals, nullptr),
+                                  max_hops == UINT32_MAX ? -1 : (int64_t)max_hops, 0, L.data(), off.data(), dag.rows.out(), dag.cols.out(),
+                                  (uint64_t**)dag.vals.out(), nullptr),
           "allShortestPaths");
     if (device_calls) *device_calls = 1;
     const size_t k = off.back();
     dag.n = k;
     // the relationships behind the pairs of ALL rows: one probe per type and direction
-    const std::vector<u64> from(dag.rows, dag.rows + k), to(dag.cols, dag.cols + k);
+    const std::vector<u64> from(dag.rows.p, dag.rows.p + k), to(dag.cols.p, dag.cols.p + k);
     std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
     if (k)
         for (size_t t = 0; t < tids.size(); ++t) {
@@ -1010,39 +999,39 @@ static void bfs_partitioned(const Graph& g, const std::vector<Context*>& gang, c
         gc->key = key;
         gc->gang = raw;
         gc->splits.assign((size_t)nr + 1, 0);
-        gc->slabs.assign(nr, nullptr);
-        gc->slabs_t.assign(nr, nullptr);
-        gc->plans.assign(nr, nullptr);
+        gc->slabs.resize(nr);
+        gc->slabs_t.resize(nr);
+        gc->plans.resize(nr);
         check(fgpu_mat_balanced_splits(c0, adj.snapshot(), nr, gc->splits.data()), "fgpu_mat_balanced_splits");
         const u64 n = g.node_cap();
         for (int r = 0; r < nr; ++r) {
             fgpu_ctx* cr = raw[r];
-            fgpu_mat* local = nullptr;
-            check(fgpu_mat_col_slab(c0, &local, adj.snapshot(), gc->splits[r], gc->splits[r + 1] < n ? gc->splits[r + 1] : n),
+            SnapshotRef local;
+            check(fgpu_mat_col_slab(c0, local.out(), adj.snapshot(), gc->splits[r], gc->splits[r + 1] < n ? gc->splits[r + 1] : n),
                   "fgpu_mat_col_slab");
             if (cr == c0) {
-                gc->slabs[r] = local;
+                gc->slabs[r] = std::move(local);
             } else {
-                u64 *rp = nullptr, *ci = nullptr, nnz = 0;
-                fgpu_info i = fgpu_mat_export_csr(c0, local, &rp, &ci, nullptr, &nnz);
-                fgpu_mat_free(local);
-                check(i, "GxB_unload_Matrix_into_Container");
-                i = fgpu_mat_from_csr(cr, &gc->slabs[r], n, n, nnz, rp, 64, ci, 64, nullptr, nullptr, 0);
-                fgpu_free(c0, rp);
-                fgpu_free(c0, ci);
-                check(i, "GxB_load_Matrix_from_Container");
+                EngineBuf<u64> rp(c0), ci(c0);
+                u64 nnz = 0;
+                check(fgpu_mat_export_csr(c0, local.get(), rp.out(), ci.out(), nullptr, &nnz), "GxB_unload_Matrix_into_Container");
+                local.reset();   // (the host arrays are all that travels: c0's copy goes before cr's is built)
+                check(fgpu_mat_from_csr(cr, gc->slabs[r].out(), n, n, nnz, rp.p, 64, ci.p, 64, nullptr, nullptr, 0),
+                      "GxB_load_Matrix_from_Container");
             }
-            check(fgpu_mat_transpose(cr, &gc->slabs_t[r], gc->slabs[r]), "GrB_transpose");
-            check(fgpu_bfs_plan_create_slab(cr, &gc->plans[r], gc->slabs[r], gc->slabs_t[r], r, nr, gc->splits.data()),
+            check(fgpu_mat_transpose(cr, gc->slabs_t[r].out(), gc->slabs[r].get()), "GrB_transpose");
+            check(fgpu_bfs_plan_create_slab(cr, gc->plans[r].out(), gc->slabs[r].get(), gc->slabs_t[r].get(), r, nr, gc->splits.data()),
                   "fgpu_bfs_plan_create_slab");
         }
         g.bfs_gang_cache_ = gc;            // (an exception above leaves the old cache in place; gc frees what it built)
         Graph::register_gang_cache(gc);
     }
-    check(fgpu_bfs_dist_run(gc->plans.data(), nr, source, max_depth < 0 ? -1 : max_depth, want_edges ? 1 : 0),
+    std::vector<fgpu_bfs_plan*> plans(nr);
+    for (int r = 0; r < nr; ++r) plans[r] = gc->plans[r].get();
+    check(fgpu_bfs_dist_run(plans.data(), nr, source, max_depth < 0 ? -1 : max_depth, want_edges ? 1 : 0),
           "LAGr_BreadthFirstSearch (partitioned)");
     for (int r = 0; r < nr; ++r)   // every rank fills its own range [splits[r], splits[r+1])
-        check(fgpu_bfs_fetch(gc->plans[r], level.data(), want_edges ? parent.data() : nullptr), "fgpu_bfs_fetch");
+        check(fgpu_bfs_fetch(plans[r], level.data(), want_edges ? parent.data() : nullptr), "fgpu_bfs_fetch");
 }
 
 BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
@@ -1078,14 +1067,12 @@ BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
         if (!pc || pc->key != key || pc->adj.snapshot() != adj.snapshot()) {
             // a new adjacency (the layers changed, or another type): new plan; a clean committed graph keeps handing
             // out the same snapshot (VersionedMatrix::extract shares the base) and its cached transpose
-            pc = std::make_shared<Graph::BfsPlanCache>(adj, adj.transpose());
+            pc = std::make_shared<Graph::BfsPlanCache>(adj, adj.transpose(), g.ctx().raw());
             pc->key = key;
             // plans index dense row pointers: a hypersparse adjacency (an unknown type's empty matrix, a tiny delta-only
             // graph) goes through the one-shot entry point below, which densifies it
-            if (fgpu_bfs_plan_create(g.ctx().raw(), &pc->plan, pc->adj.snapshot(), pc->adj_t.snapshot(), 0, 1) != FGPU_OK) {
-                pc->plan = nullptr;
+            if (fgpu_bfs_plan_create(g.ctx().raw(), pc->plan.out(), pc->adj.snapshot(), pc->adj_t.snapshot(), 0, 1) != FGPU_OK)
                 pc.reset();
-            }
             g.bfs_cache_ = pc;
         }
         if (pc) {
@@ -1096,19 +1083,16 @@ BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
     if (partitioned) {
         // levels / parents were assembled from the ranks above
     } else if (pc) {
-        fgpu_ctx* raw = g.ctx().raw();
         if (pc->pin_rows < n) {                                          // (a new cache entry, or the node capacity grew)
-            if (pc->level_pin) { fgpu_free(pc->raw, pc->level_pin); pc->level_pin = nullptr; }
-            if (pc->parent_pin) { fgpu_free(pc->raw, pc->parent_pin); pc->parent_pin = nullptr; }
-            pc->raw = raw;
+            pc->parent_pin.reset();
             pc->pin_rows = 0;
-            check(fgpu_host_alloc(raw, n * sizeof(int32_t), (void**)&pc->level_pin), "fgpu_host_alloc");
+            pc->level_pin.alloc(n, "fgpu_host_alloc");                   // (the old block goes first)
             pc->pin_rows = n;
         }
-        if (want_edges && !pc->parent_pin) check(fgpu_host_alloc(raw, pc->pin_rows * sizeof(int64_t), (void**)&pc->parent_pin), "fgpu_host_alloc");
-        check(fgpu_bfs_run(pc->plan, *source, max_depth < 0 ? -1 : max_depth, want_edges ? 1 : 0), "LAGr_BreadthFirstSearch");
-        check(fgpu_bfs_fetch(pc->plan, pc->level_pin, want_edges ? pc->parent_pin : nullptr), "LAGr_BreadthFirstSearch");
-        level = pc->level_pin; parent = pc->parent_pin;
+        if (want_edges && !pc->parent_pin.p) pc->parent_pin.alloc(pc->pin_rows, "fgpu_host_alloc");
+        check(fgpu_bfs_run(pc->plan.get(), *source, max_depth < 0 ? -1 : max_depth, want_edges ? 1 : 0), "LAGr_BreadthFirstSearch");
+        check(fgpu_bfs_fetch(pc->plan.get(), pc->level_pin.p, want_edges ? pc->parent_pin.p : nullptr), "LAGr_BreadthFirstSearch");
+        level = pc->level_pin.p; parent = pc->parent_pin.p;
     } else {
         level_v.resize(n);
         parent_v.resize(want_edges ? n : 0);

@@ -31,18 +31,18 @@
 #include <vector>
 
 #include "../../include/fgpu.h"
+#include "owned.hpp"
 
 namespace falkor {
 
 using u64 = uint64_t;
 
 // GrB_Info other than GrB_SUCCESS / GrB_NO_VALUE.  The Rust wrappers debug_assert on these
-// (matrix.rs passim); here they surface as exceptions which the C surface (capi.cpp) turns back into codes.
+// (matrix.rs passim); here they surface as exceptions (check(), owned.hpp) which the C surface (capi.cpp) turns back into codes.
 struct GrbError : std::runtime_error {
     fgpu_info info;
     GrbError(fgpu_info i, const std::string& what) : std::runtime_error(what), info(i) {}
 };
-void check(fgpu_info i, const char* where);
 
 // matrix::init / matrix::shutdown (graphblas/matrix.rs:116-221): one engine context per process+device.
 class Context {
@@ -99,7 +99,7 @@ void write_container(ByteWriter& w, const ContainerData& c);  // Encode<19> for 
 class Matrix {
    public:
     Matrix(Context& ctx, Type t, u64 nrows, u64 ncols);   // Matrix::new   matrix.rs:1151-1156, 1214-1235
-    static Matrix adopt(Context& ctx, Type t, fgpu_mat* snapshot);  // wrap an engine-made snapshot
+    static Matrix adopt(Context& ctx, Type t, SnapshotRef&& snapshot);  // wrap an engine-made snapshot
 
     Type type() const;
     Context& ctx() const;
@@ -148,7 +148,7 @@ class Matrix {
     struct State;
     std::shared_ptr<State> s_;
     explicit Matrix(std::shared_ptr<State> s) : s_(std::move(s)) {}
-    void replace(fgpu_mat* fresh) const;
+    void replace(SnapshotRef&& fresh) const;
 };
 
 // matrix::Iter<E> (matrix.rs:1471-1605): a reusable streaming cursor over the entries of rows [min, max] in
@@ -427,7 +427,7 @@ class Tensor {
                         std::vector<MeRow>* rows);
     BuiltBatch build_batch(const u64* srcs, const u64* dsts, const u64* ids, u64 n, const char* who) const;
     void adopt_bases(const Matrix& m, const Matrix& mt);
-    void adopt_bases(fgpu_mat* mo, fgpu_mat* mto, bool changed);   // (engine-made outputs: owned from here on either way)
+    void adopt_bases(SnapshotRef&& mo, SnapshotRef&& mto, bool changed);   // (engine-made outputs of a device pass)
 
     Matrix m_;
     mutable Delta dp_, dm_;
@@ -573,24 +573,19 @@ class Graph {
     // long as the adjacency it was built on is the same immutable snapshot — creating one costs more than the search
     struct BfsPlanCache {
         Matrix adj, adj_t;                 // keep the snapshots (and their cached indexes) alive
-        fgpu_bfs_plan* plan = nullptr;
         std::string key;                   // relationship types the adjacency was built for
-        // level[] / parent[] in pinned blocks of the context's pool (fgpu_host_alloc): fgpu_bfs_fetch DMAs into them — the
-        // procedure reads the vectors element by element afterwards (algo_procedures.rs:1096-1160), it never needs a copy
-        fgpu_ctx* raw = nullptr;
-        int32_t* level_pin = nullptr;
-        int64_t* parent_pin = nullptr;
+        // level[] / parent[] in pinned blocks of the context's pool: fgpu_bfs_fetch DMAs into them — the procedure reads the
+        // vectors element by element afterwards (algo_procedures.rs:1096-1160), it never needs a copy.  Members are destroyed
+        // in reverse order of declaration: the pinned blocks are declared BEFORE the plan so that the plan is freed first
+        EngineBuf<int32_t> level_pin;
+        EngineBuf<int64_t> parent_pin;
         u64 pin_rows = 0;
+        PlanRef plan;
         // one search at a time runs on the cached plan AND reads its pinned result blocks: the reference's worker pool calls
         // algo.BFS on a shared const Graph from several threads (threadpool.rs:89-128); a second caller that finds the plan
         // busy takes the one-shot path with vectors of its own instead of waiting
         std::mutex mu;
-        BfsPlanCache(Matrix a, Matrix at) : adj(std::move(a)), adj_t(std::move(at)) {}
-        ~BfsPlanCache() {
-            if (plan) fgpu_bfs_plan_free(plan);
-            if (level_pin) fgpu_free(raw, level_pin);
-            if (parent_pin) fgpu_free(raw, parent_pin);
-        }
+        BfsPlanCache(Matrix a, Matrix at, fgpu_ctx* raw) : adj(std::move(a)), adj_t(std::move(at)), level_pin(raw), parent_pin(raw) {}
     };
     mutable std::shared_ptr<BfsPlanCache> bfs_cache_;
     mutable std::mutex bfs_cache_mu_;      // orders readers and replacers of bfs_cache_ (the entry itself has its own lock)
@@ -602,8 +597,8 @@ class Graph {
         std::string key;
         std::vector<fgpu_ctx*> gang;
         std::vector<u64> splits;
-        std::vector<fgpu_mat*> slabs, slabs_t;
-        std::vector<fgpu_bfs_plan*> plans;
+        std::vector<SnapshotRef> slabs, slabs_t;
+        std::vector<PlanRef> plans;
         std::mutex mu;
         explicit BfsGangCache(Matrix a) : adj(std::move(a)) {}
         // frees the device objects (idempotent).  Called by the destructor and by Context::~Context of ANY context of the
@@ -611,10 +606,7 @@ class Graph {
         // may be touched once one of those is gone
         void release() {
             std::lock_guard<std::mutex> g(mu);
-            for (auto* p : plans) if (p) fgpu_bfs_plan_free(p);
-            for (auto* m : slabs_t) if (m) fgpu_mat_free(m);
-            for (auto* m : slabs) if (m) fgpu_mat_free(m);
-            plans.clear(); slabs_t.clear(); slabs.clear(); gang.clear();
+            plans.clear(); slabs_t.clear(); slabs.clear(); gang.clear();   // in this order: plans, transposed slabs, slabs
         }
         ~BfsGangCache() { release(); }
     };
@@ -646,22 +638,16 @@ struct ExpandedRows {
     // pool filled by DMA — 16-bit row indices (a child batch holds at most 1024 rows, batch.rs:81; 32-bit ones when a host layer
     // coalesces more than 65536 rows into one call) and the destinations as the 32-bit node ids the device works in (every node
     // id of a traversed graph fits 32 bits: tensor.rs:154-163 demands it of the multi-edge keys); row_at / dest_at widen on
-    // access, which is where the reference's NodeId(u64) is needed.  They are owned until clear(); materialize() copies them into
-    // the vectors above for the rare consumers that edit the columns in place.
-    fgpu_ctx* pin_ctx = nullptr;
-    const uint16_t* row_pin = nullptr;
-    const uint32_t* row_pin32 = nullptr;
-    const uint32_t* dest_pin = nullptr;
+    // access, which is where the reference's NodeId(u64) is needed.  They are owned until clear(), and make the struct move-only;
+    // materialize() copies them into the vectors above for the rare consumers that edit the columns in place.
+    EngineBuf<uint16_t> row_pin;
+    EngineBuf<uint32_t> row_pin32, dest_pin;
     size_t n_pin = 0;
-    ExpandedRows() = default;
-    ExpandedRows(const ExpandedRows&) = delete;
-    ExpandedRows& operator=(const ExpandedRows&) = delete;
-    ~ExpandedRows() { release_pinned(); }
-    bool pinned() const { return dest_pin != nullptr; }
+    bool pinned() const { return dest_pin.p != nullptr; }
     size_t size() const { return pinned() ? n_pin : dest.size(); }
-    u64 row_at(size_t i) const { return pinned() ? (row_pin ? (u64)row_pin[i] : (u64)row_pin32[i]) : active_row[i]; }
-    u64 dest_at(size_t i) const { return pinned() ? (u64)dest_pin[i] : dest[i]; }
-    void release_pinned();
+    u64 row_at(size_t i) const { return pinned() ? (row_pin.p ? (u64)row_pin.p[i] : (u64)row_pin32.p[i]) : active_row[i]; }
+    u64 dest_at(size_t i) const { return pinned() ? (u64)dest_pin.p[i] : dest[i]; }
+    void release_pinned() { row_pin.reset(); row_pin32.reset(); dest_pin.reset(); n_pin = 0; }
     void materialize();
     void clear() { active_row.clear(); dest.clear(); edge.clear(); release_pinned(); }
 };
@@ -878,23 +864,18 @@ BetweennessResult algo_betweenness(const Graph& g, const std::vector<std::string
 // The (row, col, value) result arrays of one engine call (fgpu_msf's forest, fgpu_maxflow's flow): n triples in (row, col)
 // order, owned here and returned to the context's result pool with the scope.
 struct EdgeList {
-    u64 *rows = nullptr, *cols = nullptr, n = 0;
-    double* vals = nullptr;
-    explicit EdgeList(const Context& ctx) : ctx_(ctx.raw()) {}
-    EdgeList(const EdgeList&) = delete;
-    EdgeList& operator=(const EdgeList&) = delete;
-    ~EdgeList() { fgpu_free(ctx_, rows); fgpu_free(ctx_, cols); fgpu_free(ctx_, vals); }
-
-   private:
-    fgpu_ctx* ctx_;
+    EngineBuf<u64> rows, cols;
+    EngineBuf<double> vals;
+    u64 n = 0;
+    explicit EdgeList(const Context& ctx) : rows(ctx.raw()), cols(ctx.raw()), vals(ctx.raw()) {}
 };
 // fgpu_msf / fgpu_maxflow into an EdgeList of `ctx`; a failure throws as check() does, named after the LAGraph call
 inline void msf(const Context& ctx, const fgpu_mat* w, const u64* active_bitmap, int64_t* component, EdgeList& forest) {
-    check(fgpu_msf(ctx.raw(), w, active_bitmap, component, &forest.rows, &forest.cols, &forest.vals, &forest.n, nullptr),
+    check(fgpu_msf(ctx.raw(), w, active_bitmap, component, forest.rows.out(), forest.cols.out(), forest.vals.out(), &forest.n, nullptr),
           "LAGraph_msf");
 }
 inline void maxflow(const Context& ctx, const fgpu_mat* cap, u64 src, u64 sink, double* value, EdgeList& flow) {
-    check(fgpu_maxflow(ctx.raw(), cap, src, sink, value, &flow.rows, &flow.cols, &flow.vals, &flow.n, nullptr), "LAGr_MaxFlow");
+    check(fgpu_maxflow(ctx.raw(), cap, src, sink, value, flow.rows.out(), flow.cols.out(), flow.vals.out(), &flow.n, nullptr), "LAGr_MaxFlow");
 }
 // fgpu_sssp into host arrays of nrows entries (the reference calls no library here: the name is the procedure's)
 inline void sssp(const Context& ctx, const fgpu_mat* w, u64 src, double* dist, int64_t* parent) {

@@ -53,16 +53,13 @@ Context::~Context() {
 // ---- Matrix state ----------------------------------------------------------------------------
 namespace {
 struct Snap {  // one immutable device snapshot; shared between a matrix and its dup()s until either mutates
-    fgpu_mat* h = nullptr;
+    SnapshotRef h;
     // the transpose of an immutable snapshot is itself immutable: computed once, shared by every Matrix::transpose()
     // of every handle on this snapshot (the reference keeps `mt` per tensor for the same reason, tensor.rs:814-816;
     // algo.BFS / algo.pageRank on a clean committed graph would otherwise pay a 13 ms transpose per call at RMAT-22)
     std::shared_ptr<Snap> transposed;
     std::mutex tmu;
-    explicit Snap(fgpu_mat* m) : h(m) {}
-    ~Snap() { if (h) fgpu_mat_free(h); }
-    Snap(const Snap&) = delete;
-    Snap& operator=(const Snap&) = delete;
+    explicit Snap(SnapshotRef&& m) : h(std::move(m)) {}
 };
 }  // namespace
 
@@ -89,9 +86,9 @@ struct Matrix::State {
     std::mutex lock;
 };
 
-static fgpu_mat* new_empty(Context& ctx, u64 nrows, u64 ncols) {
-    fgpu_mat* h = nullptr;
-    check(fgpu_mat_new(ctx.raw(), &h, nrows, ncols), "GrB_Matrix_new");
+static SnapshotRef new_empty(Context& ctx, u64 nrows, u64 ncols) {
+    SnapshotRef h;
+    check(fgpu_mat_new(ctx.raw(), h.out(), nrows, ncols), "GrB_Matrix_new");
     return h;
 }
 
@@ -103,13 +100,13 @@ Matrix::Matrix(Context& ctx, Type t, u64 nrows, u64 ncols) : s_(std::make_shared
     s_->snap = std::make_shared<Snap>(new_empty(ctx, nrows, ncols));
 }
 
-Matrix Matrix::adopt(Context& ctx, Type t, fgpu_mat* snapshot) {
+Matrix Matrix::adopt(Context& ctx, Type t, SnapshotRef&& snapshot) {
     auto s = std::make_shared<State>();
     s->ctx = &ctx;
     s->type = t;
-    check(fgpu_mat_nrows(snapshot, &s->nrows), "GrB_Matrix_nrows");
-    check(fgpu_mat_ncols(snapshot, &s->ncols), "GrB_Matrix_ncols");
-    s->snap = std::make_shared<Snap>(snapshot);
+    check(fgpu_mat_nrows(snapshot.get(), &s->nrows), "GrB_Matrix_nrows");
+    check(fgpu_mat_ncols(snapshot.get(), &s->ncols), "GrB_Matrix_ncols");
+    s->snap = std::make_shared<Snap>(std::move(snapshot));   // (until here the caller owns it)
     return Matrix(std::move(s));
 }
 
@@ -120,8 +117,8 @@ u64 Matrix::ncols() const { return s_->ncols; }
 bool Matrix::pending() const { return s_->has_pending.load(std::memory_order_acquire); }
 bool Matrix::is_synced() const { return !s_->has_pending.load(std::memory_order_acquire); }
 
-void Matrix::replace(fgpu_mat* fresh) const {
-    s_->snap = std::make_shared<Snap>(fresh);
+void Matrix::replace(SnapshotRef&& fresh) const {
+    s_->snap = std::make_shared<Snap>(std::move(fresh));
     s_->pend.clear();
     s_->has_pending.store(false, std::memory_order_release);
 }
@@ -142,26 +139,21 @@ void Matrix::wait() const {
         }
     }
     fgpu_ctx* c = s_->ctx->raw();
-    fgpu_mat *adds = nullptr, *dels = nullptr, *out = nullptr;
-    fgpu_info i = FGPU_OK;
+    SnapshotRef adds, dels, out;
     if (!ar.empty())
-        i = fgpu_mat_from_coo(c, &adds, s_->nrows, s_->ncols, ar.data(), ac.data(),
-                              s_->type == Type::UInt64 ? av.data() : nullptr, ar.size());
-    if (i == FGPU_OK && !dr.empty())
-        i = fgpu_mat_from_coo(c, &dels, s_->nrows, s_->ncols, dr.data(), dc.data(), nullptr, dr.size());
+        check(fgpu_mat_from_coo(c, adds.out(), s_->nrows, s_->ncols, ar.data(), ac.data(),
+                                s_->type == Type::UInt64 ? av.data() : nullptr, ar.size()),
+              "GrB_Matrix_wait");
+    if (!dr.empty())
+        check(fgpu_mat_from_coo(c, dels.out(), s_->nrows, s_->ncols, dr.data(), dc.data(), nullptr, dr.size()), "GrB_Matrix_wait");
     // GrB_Matrix_wait(MATERIALIZE): zombies leave, pending tuples land (a stored value is overwritten)
-    if (i == FGPU_OK) i = fgpu_mat_merge(c, &out, s_->snap->h, adds, dels, 0);
-    if (adds) fgpu_mat_free(adds);
-    if (dels) fgpu_mat_free(dels);
-    check(i, "GrB_Matrix_wait");
-    s_->snap = std::make_shared<Snap>(out);
-    s_->pend.clear();
-    s_->has_pending.store(false, std::memory_order_release);
+    check(fgpu_mat_merge(c, out.out(), s_->snap->h.get(), adds.get(), dels.get(), 0), "GrB_Matrix_wait");
+    replace(std::move(out));
 }
 
 const fgpu_mat* Matrix::snapshot() const {
     wait();
-    return s_->snap->h;
+    return s_->snap->h.get();
 }
 
 u64 Matrix::nvals() const {
@@ -174,16 +166,16 @@ void Matrix::build(const std::vector<u64>& rows, const std::vector<u64>& cols, c
     if (rows.size() != cols.size() || (vals && vals->size() != rows.size()))
         throw GrbError(FGPU_INVALID, "Matrix::build: slices differ in length");
     if (nvals() != 0) throw GrbError(FGPU_INVALID, "Matrix::build: output already has entries (GrB_OUTPUT_NOT_EMPTY)");
-    fgpu_mat* h = nullptr;
+    SnapshotRef h;
     const u64* v = (s_->type == Type::UInt64 && vals) ? vals->data() : nullptr;
     std::vector<u64> ones;
     if (s_->type == Type::UInt64 && !vals) {
         ones.assign(rows.size(), 1);
         v = ones.data();
     }
-    check(fgpu_mat_from_coo(s_->ctx->raw(), &h, s_->nrows, s_->ncols, rows.data(), cols.data(), v, rows.size()),
+    check(fgpu_mat_from_coo(s_->ctx->raw(), h.out(), s_->nrows, s_->ncols, rows.data(), cols.data(), v, rows.size()),
           "GrB_Matrix_build");
-    replace(h);
+    replace(std::move(h));
 }
 
 void Matrix::set_element(u64 i, u64 j, u64 v) {
@@ -227,15 +219,13 @@ bool Matrix::contains(u64 i, u64 j) const {
 }
 
 std::vector<Entry> Matrix::iter(u64 min_row, u64 max_row) const {
-    u64 *r = nullptr, *c = nullptr, *v = nullptr, n = 0;
     fgpu_ctx* ctx = s_->ctx->raw();
-    check(fgpu_mat_extract(ctx, snapshot(), min_row, max_row, &r, &c, s_->type == Type::UInt64 ? &v : nullptr, &n),
+    EngineBuf<u64> r(ctx), c(ctx), v(ctx);
+    u64 n = 0;
+    check(fgpu_mat_extract(ctx, snapshot(), min_row, max_row, r.out(), c.out(), s_->type == Type::UInt64 ? v.out() : nullptr, &n),
           "GxB_rowIterator");
     std::vector<Entry> out(n);
-    for (u64 k = 0; k < n; ++k) out[k] = Entry{r[k], c[k], v ? v[k] : 1};
-    fgpu_free(ctx, r);
-    fgpu_free(ctx, c);
-    fgpu_free(ctx, v);
+    for (u64 k = 0; k < n; ++k) out[k] = Entry{r[k], c[k], v.p ? v[k] : 1};
     return out;
 }
 
@@ -296,9 +286,9 @@ Matrix Matrix::transpose() const {
     {
         std::lock_guard<std::mutex> g(base->tmu);
         if (!base->transposed) {
-            fgpu_mat* t = nullptr;
-            check(fgpu_mat_transpose(s_->ctx->raw(), &t, base->h), "GrB_transpose");
-            base->transposed = std::make_shared<Snap>(t);
+            SnapshotRef t;
+            check(fgpu_mat_transpose(s_->ctx->raw(), t.out(), base->h.get()), "GrB_transpose");
+            base->transposed = std::make_shared<Snap>(std::move(t));
         }
         tr = base->transposed;
     }
@@ -312,15 +302,15 @@ Matrix Matrix::transpose() const {
 }
 
 Matrix Matrix::grown(u64 nrows, u64 ncols) const {
-    fgpu_mat* g = nullptr;
-    check(fgpu_mat_resize(s_->ctx->raw(), &g, snapshot(), nrows, ncols), "GrB_Matrix_resize");
-    return adopt(*s_->ctx, s_->type, g);
+    SnapshotRef g;
+    check(fgpu_mat_resize(s_->ctx->raw(), g.out(), snapshot(), nrows, ncols), "GrB_Matrix_resize");
+    return adopt(*s_->ctx, s_->type, std::move(g));
 }
 
 void Matrix::resize(u64 nrows, u64 ncols) {
-    fgpu_mat* g = nullptr;
-    check(fgpu_mat_resize(s_->ctx->raw(), &g, snapshot(), nrows, ncols), "GrB_Matrix_resize");
-    replace(g);
+    SnapshotRef g;
+    check(fgpu_mat_resize(s_->ctx->raw(), g.out(), snapshot(), nrows, ncols), "GrB_Matrix_resize");
+    replace(std::move(g));
     s_->nrows = nrows;
     s_->ncols = ncols;
 }
@@ -328,34 +318,34 @@ void Matrix::resize(u64 nrows, u64 ncols) {
 void Matrix::clear() { replace(new_empty(*s_->ctx, s_->nrows, s_->ncols)); }
 
 void Matrix::lmxm(const Matrix& b) {
-    fgpu_mat* c = nullptr;
-    check(fgpu_mxm(s_->ctx->raw(), &c, snapshot(), b.snapshot()), "GrB_mxm");
-    replace(c);
+    SnapshotRef c;
+    check(fgpu_mxm(s_->ctx->raw(), c.out(), snapshot(), b.snapshot()), "GrB_mxm");
+    replace(std::move(c));
     s_->ncols = b.ncols();
 }
 
 void Matrix::rmxm(const Matrix& b) {
-    fgpu_mat* c = nullptr;
-    check(fgpu_mxm(s_->ctx->raw(), &c, b.snapshot(), snapshot()), "GrB_mxm");
-    replace(c);
+    SnapshotRef c;
+    check(fgpu_mxm(s_->ctx->raw(), c.out(), b.snapshot(), snapshot()), "GrB_mxm");
+    replace(std::move(c));
     s_->nrows = b.nrows();
 }
 
 void Matrix::delta_lmxm(const Matrix& m, const Matrix& dp, const Matrix& dm) {
-    fgpu_mat* c = nullptr;
-    check(fgpu_delta_lmxm(s_->ctx->raw(), &c, snapshot(), m.snapshot(), dp.snapshot(), dm.snapshot()),
+    SnapshotRef c;
+    check(fgpu_delta_lmxm(s_->ctx->raw(), c.out(), snapshot(), m.snapshot(), dp.snapshot(), dm.snapshot()),
           "GrB_mxm (delta_lmxm)");
-    replace(c);
+    replace(std::move(c));
     s_->ncols = m.ncols();
 }
 
-static fgpu_mat* merged(Context& ctx, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, bool dm_masks_dp,
-                        bool pattern_only, const char* where) {
-    fgpu_mat* o = nullptr;
+static SnapshotRef merged(Context& ctx, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, bool dm_masks_dp,
+                          bool pattern_only, const char* where) {
+    SnapshotRef o;
     if (pattern_only)
-        check(fgpu_mat_merge_pattern(ctx.raw(), &o, m, dp, dm, dm_masks_dp ? 1 : 0), where);
+        check(fgpu_mat_merge_pattern(ctx.raw(), o.out(), m, dp, dm, dm_masks_dp ? 1 : 0), where);
     else
-        check(fgpu_mat_merge(ctx.raw(), &o, m, dp, dm, dm_masks_dp ? 1 : 0), where);
+        check(fgpu_mat_merge(ctx.raw(), o.out(), m, dp, dm, dm_masks_dp ? 1 : 0), where);
     return o;
 }
 
@@ -381,22 +371,19 @@ void Matrix::element_wise_add(const Matrix* mask, const Matrix* a, const Matrix*
 void Matrix::element_wise_multiply(const Matrix* a, const Matrix* b) {
     const Matrix& A = a ? *a : *this;
     const Matrix& B = b ? *b : *this;
-    fgpu_mat* o = nullptr;
+    SnapshotRef o;
     if (s_->type == Type::Bool) {
         // ANY_PAIR result is iso true: keep the structure only (entries of B found in A carry no values
         // when the second operand is the BOOL one)
         const Matrix& valued = A.type() == Type::UInt64 ? A : B;
         const Matrix& other = &valued == &A ? B : A;
-        check(fgpu_mat_intersect(s_->ctx->raw(), &o, valued.snapshot(), other.snapshot()), "GrB_eWiseMult");
-        if (other.type() == Type::UInt64) {  // both valued: strip the values
-            fgpu_mat* p = merged(*s_->ctx, o, nullptr, nullptr, false, true, "GrB_eWiseMult");
-            fgpu_mat_free(o);
-            o = p;
-        }
+        check(fgpu_mat_intersect(s_->ctx->raw(), o.out(), valued.snapshot(), other.snapshot()), "GrB_eWiseMult");
+        if (other.type() == Type::UInt64)   // both valued: strip the values
+            o = merged(*s_->ctx, o.get(), nullptr, nullptr, false, true, "GrB_eWiseMult");
     } else {
-        check(fgpu_mat_intersect(s_->ctx->raw(), &o, A.snapshot(), B.snapshot()), "GrB_eWiseMult");
+        check(fgpu_mat_intersect(s_->ctx->raw(), o.out(), A.snapshot(), B.snapshot()), "GrB_eWiseMult");
     }
-    replace(o);
+    replace(std::move(o));
 }
 
 void Matrix::set_pattern(const Matrix* mask, const Matrix& a, Descriptor d) {
@@ -404,13 +391,9 @@ void Matrix::set_pattern(const Matrix* mask, const Matrix& a, Descriptor d) {
     if (mask && d != Descriptor::C)
         throw GrbError(FGPU_INVALID, "set_pattern: only the (mask, C) form is used (graph.rs:2520-2549)");
     // self<!mask> U= pattern(a): the addition is masked, what self already holds stays
-    fgpu_mat* add = merged(*s_->ctx, a.snapshot(), nullptr, mask ? mask->snapshot() : nullptr, false, true,
-                           "GrB_Matrix_apply (set_pattern)");
-    fgpu_mat* o = nullptr;
-    fgpu_info i = fgpu_mat_merge_pattern(s_->ctx->raw(), &o, snapshot(), add, nullptr, 0);
-    fgpu_mat_free(add);
-    check(i, "GrB_Matrix_apply (set_pattern)");
-    replace(o);
+    SnapshotRef add = merged(*s_->ctx, a.snapshot(), nullptr, mask ? mask->snapshot() : nullptr, false, true,
+                             "GrB_Matrix_apply (set_pattern)");
+    replace(merged(*s_->ctx, snapshot(), add.get(), nullptr, false, true, "GrB_Matrix_apply (set_pattern)"));
 }
 
 u64 Matrix::intersection_nvals(const Matrix& b) const {

@@ -204,16 +204,16 @@ void write_container(ByteWriter& w, const ContainerData& c) {
 // Decode<19> for Matrix<T> (matrix.rs:428-504): the arrays go to the device as they are
 Matrix Matrix::decode(Context& ctx, ByteReader& r) {
     ContainerData c = parse_container(r);
-    fgpu_mat* snap = nullptr;
+    SnapshotRef snap;
     const u64 nvec = c.p.size() - 1;
     // fgpu_mat_from_csr reads "hypersparse" off a non-NULL hyper list: a hypersparse container without stored rows
     // (p = [0], h = [] — every clean dp / dm layer of a real graph) has an empty vector whose data() is NULL
     static const u64 no_rows = 0;
     const u64* hlist = c.hyper ? (c.h.empty() ? &no_rows : c.h.data()) : nullptr;
-    check(fgpu_mat_from_csr(ctx.raw(), &snap, c.nrows, c.ncols, c.nvals, c.p.data(), 64, c.i.data(), 64,
+    check(fgpu_mat_from_csr(ctx.raw(), snap.out(), c.nrows, c.ncols, c.nvals, c.p.data(), 64, c.i.data(), 64,
                             c.valued ? c.x.data() : nullptr, hlist, c.hyper ? nvec : 0),
           "GxB_load_Matrix_from_Container");
-    return Matrix::adopt(ctx, c.valued ? Type::UInt64 : Type::Bool, snap);
+    return Matrix::adopt(ctx, c.valued ? Type::UInt64 : Type::Bool, std::move(snap));
 }
 
 // Encode<19> for Matrix<T> (matrix.rs:506-546): the wait()ed state, sparse row-major (hypersparse when most rows are empty)
@@ -222,12 +222,14 @@ void Matrix::encode(ByteWriter& w) const {
     c.nrows = nrows();
     c.ncols = ncols();
     c.valued = type() == Type::UInt64;
-    u64 *rp = nullptr, *ci = nullptr, *vals = nullptr, nnz = 0;
     fgpu_ctx* raw = ctx().raw();
-    check(fgpu_mat_export_csr(raw, snapshot(), &rp, &ci, c.valued ? &vals : nullptr, &nnz), "GxB_unload_Matrix_into_Container");
+    EngineBuf<u64> rp(raw), ci(raw), vals(raw);
+    u64 nnz = 0;
+    check(fgpu_mat_export_csr(raw, snapshot(), rp.out(), ci.out(), c.valued ? vals.out() : nullptr, &nnz),
+          "GxB_unload_Matrix_into_Container");
     c.nvals = nnz;
-    c.i.assign(ci, ci + nnz);
-    if (c.valued) c.x.assign(vals, vals + nnz);
+    c.i.assign(ci.p, ci.p + nnz);
+    if (c.valued) c.x.assign(vals.p, vals.p + nnz);
     u64 stored = 0;
     for (u64 r = 0; r < c.nrows; ++r) stored += rp[r + 1] > rp[r] ? 1 : 0;
     c.hyper = c.nrows > 1024 && stored * 16 < c.nrows;     // what the deltas are pinned to (into_hyper, matrix.rs:558-575)
@@ -236,11 +238,8 @@ void Matrix::encode(ByteWriter& w) const {
         for (u64 r = 0; r < c.nrows; ++r)
             if (rp[r + 1] > rp[r]) { c.h.push_back(r); c.p.push_back(rp[r + 1]); }
     } else {
-        c.p.assign(rp, rp + c.nrows + 1);
+        c.p.assign(rp.p, rp.p + c.nrows + 1);
     }
-    fgpu_free(raw, rp);
-    fgpu_free(raw, ci);
-    if (vals) fgpu_free(raw, vals);
     write_container(w, c);
 }
 

@@ -165,25 +165,13 @@ void Tensor::set_all_from_slices(const std::vector<u64>& srcs, const std::vector
     }
 }
 
-namespace {
-struct EngineArray {   // a result array of the engine, given back on every exit
-    fgpu_ctx* ctx;
-    u64* p = nullptr;
-    explicit EngineArray(fgpu_ctx* c) : ctx(c) {}
-    ~EngineArray() { if (p) fgpu_free(ctx, p); }
-    EngineArray(EngineArray&& o) : ctx(o.ctx), p(o.p) { o.p = nullptr; }
-    EngineArray(const EngineArray&) = delete;
-    EngineArray& operator=(const EngineArray&) = delete;
-};
-}  // namespace
-
 u64 bulk_clock_ns() {
     return (u64)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 struct Tensor::BuiltBatch {
     Matrix fwd, bwd;               // the batch's UINT64 matrix and its transposed pattern
-    EngineArray key, off, ids;     // its multi-edge runs, ascending by key
+    EngineBuf<u64> key, off, ids;  // its multi-edge runs, ascending by key
     u64 n_multi;
     u64 st[8];                     // fgpu_edges_build's stats
 };
@@ -192,12 +180,14 @@ struct Tensor::BuiltBatch {
 Tensor::BuiltBatch Tensor::build_batch(const u64* srcs, const u64* dsts, const u64* ids, u64 n, const char* who) const {
     Context& ctx = m_.ctx();
     fgpu_ctx* c = ctx.raw();
-    fgpu_mat *fwd_h = nullptr, *bwd_h = nullptr;
-    EngineArray key(c), off(c), run(c);
+    SnapshotRef fwd_h, bwd_h;
+    EngineBuf<u64> key(c), off(c), run(c);
     u64 n_multi = 0, st[8] = {0};
-    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, &fwd_h, &bwd_h, &key.p, &off.p, &run.p, &n_multi, st), who);
-    BuiltBatch b{Matrix::adopt(ctx, Type::UInt64, fwd_h), Matrix::adopt(ctx, Type::Bool, bwd_h), std::move(key), std::move(off),
-                 std::move(run), n_multi, {}};
+    check(fgpu_edges_build(c, m_.nrows(), m_.ncols(), srcs, dsts, ids, n, fwd_h.out(), bwd_h.out(), key.out(), off.out(), run.out(),
+                           &n_multi, st),
+          who);
+    BuiltBatch b{Matrix::adopt(ctx, Type::UInt64, std::move(fwd_h)), Matrix::adopt(ctx, Type::Bool, std::move(bwd_h)), std::move(key),
+                 std::move(off), std::move(run), n_multi, {}};
     std::copy(st, st + 8, b.st);
     return b;
 }
@@ -243,9 +233,9 @@ void Tensor::adopt_bases(const Matrix& m, const Matrix& mt) {
 }
 
 // the outputs of a device pass over the folded bases; one that changed nothing leaves the bases the snapshots they are
-void Tensor::adopt_bases(fgpu_mat* mo, fgpu_mat* mto, bool changed) {
-    Matrix new_m = Matrix::adopt(m_.ctx(), Type::UInt64, mo);
-    Matrix new_mt = Matrix::adopt(m_.ctx(), Type::Bool, mto);
+void Tensor::adopt_bases(SnapshotRef&& mo, SnapshotRef&& mto, bool changed) {
+    Matrix new_m = Matrix::adopt(m_.ctx(), Type::UInt64, std::move(mo));
+    Matrix new_mt = Matrix::adopt(m_.ctx(), Type::Bool, std::move(mto));
     if (changed) adopt_bases(new_m, new_mt);
 }
 
@@ -279,9 +269,9 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
     if (empty) {
         adopt_bases(fwd, bwd);
     } else {
-        fgpu_mat* merged = nullptr;
-        check(fgpu_mat_merge(c, &merged, m_.snapshot(), fwd.snapshot(), nullptr, 0), "Tensor::bulk_insert");
-        Matrix new_m = Matrix::adopt(ctx, Type::UInt64, merged);
+        SnapshotRef merged;
+        check(fgpu_mat_merge(c, merged.out(), m_.snapshot(), fwd.snapshot(), nullptr, 0), "Tensor::bulk_insert");
+        Matrix new_m = Matrix::adopt(ctx, Type::UInt64, std::move(merged));
         mt_.union_base(bwd);
         m_ = new_m;
     }
@@ -307,7 +297,7 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
     u64 t0 = bulk_clock_ns();
     BuiltBatch b = build_batch(srcs, dsts, ids, n, "Tensor::append_bulk");
     const Matrix &fwd = b.fwd, &bwd = b.bwd;
-    const EngineArray &bkey = b.key, &boff = b.off, &bids = b.ids;
+    const EngineBuf<u64> &bkey = b.key, &boff = b.off, &bids = b.ids;
     const u64 n_b = b.n_multi;
     as.phase_ns[0] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
@@ -329,14 +319,14 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
     }
     std::vector<u64> akey, aoff{0}, arun;
     gather_me_rows(srcs, dsts, n, akey, aoff, arun, nullptr);
-    fgpu_mat *mo = nullptr, *mto = nullptr;
-    EngineArray okey(c), ooff(c), oids(c);
+    SnapshotRef mo, mto;
+    EngineBuf<u64> okey(c), ooff(c), oids(c);
     u64 n_o = 0, us[8] = {0};
     // an id already stored on its pair fails here: the layers are folded, the state they hold is what it was
     check(fgpu_edges_union(c, m_.snapshot(), mt_.m().snapshot(), akey.data(), aoff.data(), arun.data(), akey.size(), fwd.snapshot(),
-                           bwd.snapshot(), bkey.p, boff.p, bids.p, n_b, &mo, &mto, &okey.p, &ooff.p, &oids.p, &n_o, us),
+                           bwd.snapshot(), bkey.p, boff.p, bids.p, n_b, mo.out(), mto.out(), okey.out(), ooff.out(), oids.out(), &n_o, us),
           "Tensor::append_bulk");
-    adopt_bases(mo, mto, true);
+    adopt_bases(std::move(mo), std::move(mto), true);
     as.phase_ns[1] = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
     // b and o ascend by key, one cursor each: a multi-edge pair only the batch names brings its b row, a colliding pair its o row
@@ -372,13 +362,13 @@ std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nod
     fgpu_ctx* c = m_.ctx().raw();
     u64 t0 = bulk_clock_ns();
     fold_for_bulk();
-    fgpu_mat *mo = nullptr, *mto = nullptr;
-    EngineArray rr(c), rc(c), rv(c);
+    SnapshotRef mo, mto;
+    EngineBuf<u64> rr(c), rc(c), rv(c);
     u64 n_rem = 0, n_out = 0, st[8] = {0};
-    check(fgpu_nodes_detach(c, m_.snapshot(), mt_.m().snapshot(), nodes.data(), nodes.size(), 3, &mo, &mto, &rr.p, &rc.p, &rv.p, &n_rem,
+    check(fgpu_nodes_detach(c, m_.snapshot(), mt_.m().snapshot(), nodes.data(), nodes.size(), 3, mo.out(), mto.out(), rr.out(), rc.out(), rv.out(), &n_rem,
                             &n_out, st),
           "Tensor::detach_nodes");
-    adopt_bases(mo, mto, n_rem != 0);   // (nothing incident: nothing changed)
+    adopt_bases(std::move(mo), std::move(mto), n_rem != 0);   // (nothing incident: nothing changed)
     if (counts) counts->phase_ns[0] += bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
     // the reference's order (graph.rs:2405-2427): per node of D ascending its out edges, then its in edges.  The out segment
@@ -548,13 +538,13 @@ std::vector<std::pair<u64, u64>> Tensor::remove_bulk(const u64* srcs, const u64*
     hit.assign(n, 0);
     const u64 gather_ns = bulk_clock_ns() - t0;
     t0 = bulk_clock_ns();
-    fgpu_mat *mo = nullptr, *mto = nullptr;
-    EngineArray er(c), ec(c);
+    SnapshotRef mo, mto;
+    EngineBuf<u64> er(c), ec(c);
     u64 n_emp = 0, st[8] = {0};
     check(fgpu_edges_remove(c, m_.snapshot(), mt_.m().snapshot(), srcs, dsts, ids, n, key.data(), off.data(), run.data(), key.size(),
-                            &mo, &mto, hit.data(), taken.data(), &er.p, &ec.p, &n_emp, st),
+                            mo.out(), mto.out(), hit.data(), taken.data(), er.out(), ec.out(), &n_emp, st),
           "Tensor::remove_bulk");
-    adopt_bases(mo, mto, st[0] != 0);   // (nothing hit: nothing changed)
+    adopt_bases(std::move(mo), std::move(mto), st[0] != 0);   // (nothing hit: nothing changed)
     emptied.reserve(n_emp);
     for (u64 k = 0; k < n_emp; ++k) emptied.push_back({er.p[k], ec.p[k]});
     const u64 device_ns = fold_ns + (bulk_clock_ns() - t0);
@@ -633,10 +623,10 @@ void Tensor::fold_oversized() {
 
 Matrix Tensor::extract() const {
     wait_fwd();
-    fgpu_mat* o = nullptr;
-    check(fgpu_mat_merge_pattern(m_.ctx().raw(), &o, m_.snapshot(), dp_.layer().snapshot(), dm_.layer().snapshot(), 0),
+    SnapshotRef o;
+    check(fgpu_mat_merge_pattern(m_.ctx().raw(), o.out(), m_.snapshot(), dp_.layer().snapshot(), dm_.layer().snapshot(), 0),
           "Tensor::extract");
-    return Matrix::adopt(m_.ctx(), Type::Bool, o);
+    return Matrix::adopt(m_.ctx(), Type::Bool, std::move(o));
 }
 
 Tensor Tensor::dup() const {

@@ -121,10 +121,10 @@ Matrix VersionedMatrix::extract() const {
     // copy — the result is a fresh handle exactly as versioned_matrix.rs:609-620 returns, and a caller that mutates
     // it (set_pattern in build_relationship_matrix_unrestricted) gets its own snapshot on the first write
     if (m_.type() == Type::Bool && dp_.layer().nvals() == 0 && dm_.layer().nvals() == 0) return m_.dup();
-    fgpu_mat* o = nullptr;
-    check(fgpu_mat_merge_pattern(m_.ctx().raw(), &o, m_.snapshot(), dp_.layer().snapshot(), dm_.layer().snapshot(), 0),
+    SnapshotRef o;
+    check(fgpu_mat_merge_pattern(m_.ctx().raw(), o.out(), m_.snapshot(), dp_.layer().snapshot(), dm_.layer().snapshot(), 0),
           "VersionedMatrix::extract");
-    return Matrix::adopt(m_.ctx(), Type::Bool, o);
+    return Matrix::adopt(m_.ctx(), Type::Bool, std::move(o));
 }
 
 std::optional<bool> VersionedMatrix::get(u64 i, u64 j) const {
@@ -259,9 +259,9 @@ void VersionedMatrix::union_base(const Matrix& pattern) {
     if (pattern.nrows() != m_.nrows() || pattern.ncols() != m_.ncols())
         throw GrbError(FGPU_DIM_MISMATCH, "VersionedMatrix::union_base: dimensions differ");
     fold_all();
-    fgpu_mat* o = nullptr;
-    check(fgpu_mat_merge_pattern(m_.ctx().raw(), &o, m_.snapshot(), pattern.snapshot(), nullptr, 0), "VersionedMatrix::union_base");
-    m_ = Matrix::adopt(m_.ctx(), Type::Bool, o);
+    SnapshotRef o;
+    check(fgpu_mat_merge_pattern(m_.ctx().raw(), o.out(), m_.snapshot(), pattern.snapshot(), nullptr, 0), "VersionedMatrix::union_base");
+    m_ = Matrix::adopt(m_.ctx(), Type::Bool, std::move(o));
 }
 
 u64 VersionedMatrix::detach_base(const std::vector<u64>& nodes, int sides) {
@@ -270,12 +270,12 @@ u64 VersionedMatrix::detach_base(const std::vector<u64>& nodes, int sides) {
         if (((sides & 1) && v >= m_.nrows()) || ((sides & 2) && v >= m_.ncols()))
             throw GrbError(FGPU_INVALID, "VersionedMatrix::detach_base: node " + std::to_string(v) + " is outside the matrix");
     fold_all();
-    fgpu_mat* o = nullptr;
+    SnapshotRef o;
     u64 st[8] = {0};
-    check(fgpu_nodes_detach(m_.ctx().raw(), m_.snapshot(), nullptr, nodes.data(), nodes.size(), sides, &o, nullptr, nullptr, nullptr,
+    check(fgpu_nodes_detach(m_.ctx().raw(), m_.snapshot(), nullptr, nodes.data(), nodes.size(), sides, o.out(), nullptr, nullptr, nullptr,
                             nullptr, nullptr, nullptr, st),
           "VersionedMatrix::detach_base");
-    Matrix fresh = Matrix::adopt(m_.ctx(), Type::Bool, o);
+    Matrix fresh = Matrix::adopt(m_.ctx(), Type::Bool, std::move(o));
     const u64 removed = m_.nvals() - st[4];
     if (removed) m_ = fresh;   // (nothing incident: the base stays the snapshot it is)
     return removed;

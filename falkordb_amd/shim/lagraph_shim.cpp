@@ -118,8 +118,10 @@ struct ResultVector {
     ResultVector& operator=(const ResultVector&) = delete;
     ~ResultVector() { GrB_Vector_free(&vec); }
     void alloc(GrB_Type type, uint64_t n, int absent, const char* where) {
-        check(fgpu_host_alloc(fgshim::context()->raw(), (n ? n : 1) * sizeof(T), (void**)&data), where);
-        vec = fgshim::vector_over_pinned(type, n, data, absent);
+        falkor::EngineBuf<T> pin(fgshim::context()->raw());
+        pin.alloc(n, where);
+        vec = fgshim::vector_over_pinned(type, n, pin.p, absent);
+        data = pin.release();   // (the vector owns the block from here on)
     }
     GrB_Vector release() {
         GrB_Vector v = vec;
@@ -131,21 +133,20 @@ struct ResultVector {
 #ifndef FG_LAGRAPHX
 // degree(i) = entries of A(i,:) as a GrB_INT64 vector that stores only the non-zero degrees (lagraph_bindings.rs:115-116)
 GrB_Vector degrees_of(const Matrix& m) {
-    falkor::Context* c = fgshim::context();
+    fgpu_ctx* raw = fgshim::context()->raw();
     const uint64_t n = m.nrows();
-    int64_t* out = nullptr;
-    check(fgpu_host_alloc(c->raw(), (n ? n : 1) * sizeof(int64_t), (void**)&out), "LAGraph_Cached_OutDegree");
+    falkor::EngineBuf<int64_t> out(raw);
+    out.alloc(n, "LAGraph_Cached_OutDegree");
     if (n) {
         // the engine writes 32-bit degrees; a pinned block is device-visible, so the kernel fills it directly
-        uint32_t* d32 = nullptr;
-        fgpu_info r = fgpu_host_alloc(c->raw(), n * sizeof(uint32_t), (void**)&d32);
-        if (r == FGPU_OK) r = fgpu_mat_row_degrees(c->raw(), m.snapshot(), d32);
-        if (r == FGPU_OK)
-            for (uint64_t i = 0; i < n; ++i) out[i] = d32[i];
-        if (d32) (void)fgpu_free(c->raw(), d32);
-        if (r != FGPU_OK) { (void)fgpu_free(c->raw(), out); check(r, "LAGraph_Cached_OutDegree"); }
+        falkor::EngineBuf<uint32_t> d32(raw);
+        d32.alloc(n, "LAGraph_Cached_OutDegree");
+        check(fgpu_mat_row_degrees(raw, m.snapshot(), d32.p), "LAGraph_Cached_OutDegree");
+        for (uint64_t i = 0; i < n; ++i) out[i] = d32[i];
     }
-    return fgshim::vector_over_pinned(fgshim::type_int64(), n, out, 2);
+    GrB_Vector v = fgshim::vector_over_pinned(fgshim::type_int64(), n, out.p, 2);
+    out.release();   // (the vector owns the block from here on)
+    return v;
 }
 #endif
 }  // namespace
@@ -442,8 +443,8 @@ static std::unique_ptr<GB_Matrix_opaque> fp64_matrix_from(const falkor::EdgeList
     out->fp64 = true;
     if (e.n) {
         std::vector<uint64_t> bits(e.n);
-        memcpy(bits.data(), e.vals, e.n * sizeof(uint64_t));
-        out->m.build(std::vector<uint64_t>(e.rows, e.rows + e.n), std::vector<uint64_t>(e.cols, e.cols + e.n), &bits);
+        memcpy(bits.data(), e.vals.p, e.n * sizeof(uint64_t));
+        out->m.build(std::vector<uint64_t>(e.rows.p, e.rows.p + e.n), std::vector<uint64_t>(e.cols.p, e.cols.p + e.n), &bits);
     }
     return out;
 }

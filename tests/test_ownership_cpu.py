@@ -1,6 +1,7 @@
 """CPU: MatRef of falkordb_amd/csrc/common.hpp releases what it holds exactly once, and it is the only place outside mat.hip
 that names mat_release: every temporary snapshot of the engine is held by one.  DevBuf does the same for device memory:
-every cached index of a snapshot is one, and no file below the matrix layer allocates or frees a block by hand."""
+every cached index of a snapshot is one, and no file below the matrix layer allocates or frees a block by hand.  The host layer
+above the C ABI does the same with SnapshotRef, PlanRef and EngineBuf of falkordb_amd/host/owned.hpp."""
 import os
 import subprocess
 
@@ -33,6 +34,13 @@ def test_devbuf_frees_once_alone_and_as_a_member(tmp_path):
     _run_host_check(tmp_path, "devbuf_check")
 
 
+def test_host_owners_free_once_on_every_way_out(tmp_path):
+    """tests/host/owned_check.cpp asserts it for SnapshotRef, PlanRef and EngineBuf<T> (the seven element types in use), with
+    counting engine functions of its own: destruction, out(), release(), reset(), both moves, a self-move, a growing vector,
+    a failed alloc(), the context fgpu_free receives, and an exception between out() and the end of the scope."""
+    _run_host_check(tmp_path, "owned_check")
+
+
 def test_only_the_holder_and_mat_hip_name_mat_release():
     """A function that builds a snapshot holds it in a MatRef from mat_alloc until `*out = ref.release()`, so no file but
     common.hpp (the holder) and mat.hip (the definition, the public free, the transpose cache) releases one by hand."""
@@ -59,3 +67,22 @@ def test_only_the_holder_the_pool_and_mat_hip_name_dev_alloc():
     assert raw == ["common.hpp", "ctx.hip", "mat.hip"], raw
     for gone in ("xp_free_buffers", "blocked_release", "pr_parts_release(", "bc_cached_transpose"):
         assert gone not in text, gone
+
+
+def test_only_owned_hpp_frees_or_pins_in_the_host_layer():
+    """Above the C ABI every engine handle is held by an owner of owned.hpp from the call that makes it: no other file of
+    falkordb_amd/host or falkordb_amd/shim names fgpu_mat_free or fgpu_bfs_plan_free at all, or calls fgpu_host_alloc;
+    fgpu_free is called by owned.hpp and by graphblas_shim.cpp alone (a GrB_Vector over a pinned block is that block's owner)."""
+    names = ("fgpu_mat_free", "fgpu_bfs_plan_free", "fgpu_free(", "fgpu_host_alloc(", "struct EngineArray")
+    naming = {n: [] for n in names}
+    for d in ("host", "shim"):
+        for f in sorted(os.listdir(os.path.join(ROOT, "falkordb_amd", d))):
+            src = open(os.path.join(ROOT, "falkordb_amd", d, f)).read()
+            for n in names:
+                if n in src:
+                    naming[n].append(f)
+    assert naming["fgpu_mat_free"] == ["owned.hpp"], naming
+    assert naming["fgpu_bfs_plan_free"] == ["owned.hpp"], naming
+    assert naming["fgpu_free("] == ["owned.hpp", "graphblas_shim.cpp"], naming
+    assert naming["fgpu_host_alloc("] == ["owned.hpp"], naming
+    assert naming["struct EngineArray"] == [], naming
