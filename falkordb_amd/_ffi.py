@@ -89,6 +89,12 @@ SIGNATURES = {
     "fgpu_expand_probe": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u8p, u64p]),
     "fgpu_expand_pairs": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, C.c_int, vpp, C.POINTER(u64p), u64p, u64p]),
     "fgpu_expand_pairs32": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, C.c_int, vpp, C.POINTER(u32p), u64p, u64p]),
+    "fgpu_multi_new": (C.c_int32, [vp, u64p, u64p, u64p, C.c_uint64, vpp]),
+    "fgpu_multi_free": (C.c_int32, [vp]),
+    "fgpu_multi_size": (C.c_int32, [vp, u64p, u64p]),
+    "fgpu_expand_edges": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, u64p, u64p,
+                                      C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u8p), u64p,
+                                      u64p]),
     "fgpu_expand_levels": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fgpu_expand_trail_counts": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, C.c_int, C.POINTER(u64p),
                                              C.POINTER(u64p), C.POINTER(u64p), u64p]),

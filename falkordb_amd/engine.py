@@ -217,6 +217,43 @@ class Context:
         check(self.lib.fgpu_mat_rmat(self._h, C.byref(h), scale, edge_factor, seed, a16, b16, c16))
         return Mat(self, h)
 
+    # ---- relationship-emitting traversal (expand_edges.hip) ----
+    def multi_new(self, key, off, ids) -> "Multi":
+        """fgpu_multi_new: one tensor's multi-edge rows on the device, in fgpu_edges_build's shape (key = src << 32 | dst
+        ascending, off[0] = 0, every run at least 2 ascending ids)."""
+        key, off, ids = _u64(key).reshape(-1), _u64(off).reshape(-1), _u64(ids).reshape(-1)
+        h = C.c_void_p()
+        check(self.lib.fgpu_multi_new(self._h, _p(key), _p(off), _p(ids), len(key), C.byref(h)))
+        return Multi(self, h)
+
+    def expand_edges(self, from_ids, to_ids, m, dp=None, dm=None, mt_m=None, mt_dp=None, mt_dm=None, multi=None, transposed=False,
+                     bidirectional=False, first_only=False, from_bitmap=None, to_bitmap=None, want_pass=False):
+        """fgpu_expand_edges: CondTraverse's per-row path for a whole batch.  from_ids / to_ids: node id or None (unbound);
+        m .. multi: one entry per relationship type in scan order (Mat / Multi or None; the optional lists may be None whole).
+        Returns (row, from, to, id[, pass], stats): numpy views of the engine's result blocks, stats the eight of fgpu.h."""
+        enc = lambda v: (1 << 64) - 1 if v is None else int(v)
+        f = np.asarray([enc(v) for v in from_ids], dtype=U64)
+        t = np.asarray([enc(v) for v in to_ids], dtype=U64)
+        assert len(f) == len(t)
+        T = len(m)
+        arrs = [_hop_arrays(x) if x is not None else None for x in (m, dp, dm, mt_m, mt_dp, mt_dm, multi)]
+        assert all(a is None or len(a) == T for a in arrs)
+        fb = _u64(from_bitmap) if from_bitmap is not None else None
+        tb = _u64(to_bitmap) if to_bitmap is not None else None
+        prow, pfrom, pto = _ffi.u32p(), _ffi.u32p(), _ffi.u32p()
+        pid, ppass = u64p(), u8p()
+        n = C.c_uint64()
+        st = (C.c_uint64 * 8)()
+        flags = (1 if transposed else 0) | (2 if bidirectional else 0) | (4 if first_only else 0)
+        check(self.lib.fgpu_expand_edges(self._h, _p(f), _p(t), len(f), *arrs, T, flags, _p(fb), _p(tb), C.byref(prow),
+                                         C.byref(pfrom), C.byref(pto), C.byref(pid), C.byref(ppass) if want_pass else None,
+                                         C.byref(n), st))
+        cols = [self._take(prow, n.value, np.uint32), self._take(pfrom, n.value, np.uint32),
+                self._take(pto, n.value, np.uint32), self._take(pid, n.value, U64)]
+        if want_pass:
+            cols.append(self._take(ppass, n.value, np.uint8))
+        return (*cols, [int(x) for x in st])
+
 
 class Mat:
     """fgpu_mat: immutable device snapshot of one matrix layer."""
@@ -398,6 +435,31 @@ class Mat:
         h = C.c_void_p()
         check(self.ctx.lib.fgpu_mat_row_slab(self.ctx._h, C.byref(h), self._h, lo, hi))
         return Mat(self.ctx, h)
+
+
+class Multi:
+    """fgpu_multi: one tensor's multi-edge rows, resident on the device (Context.multi_new)."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self._h = ctx, h
+
+    def size(self):
+        """(rows, ids) held"""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(self.ctx.lib.fgpu_multi_size(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def free(self):
+        if self._h:
+            self.ctx.lib.fgpu_multi_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            if self.ctx._h:
+                self.free()
+        except Exception:
+            pass
 
 
 def _hop_arrays(mats):

@@ -578,6 +578,39 @@ class Graph:
         return list(zip(_take(orow, n.value).tolist(), _take(of, n.value).tolist(), _take(ot, n.value).tolist(),
                         _take(oe, n.value).tolist()))
 
+    def cond_traverse_edges_batch(self, spec, from_ids, to_ids, transposed=False, used_edges=None, dedup=False,
+                                  as_arrays=False):
+        """The same input batch through ONE fgpu_expand_edges (fh_cond_traverse_edges_batch): from / to as cond_traverse_rows
+        takes them; used_edges = None or one list of sibling-bound ids PER ROW; dedup = the caller would pass dedup_src.
+        Returns None when the op declines (nothing ran), else (rows, null_rows, stats) with rows = [(row, from, to, edge)] in
+        emission order — four arrays with as_arrays — and stats = fgpu_expand_edges' eight."""
+        enc = lambda v: -1 if v is None else (-2 if isinstance(v, str) else int(v))
+        k = len(from_ids)
+        f = np.asarray([enc(v) for v in from_ids], dtype=np.int64)
+        t = np.asarray([enc(v) for v in to_ids], dtype=np.int64)
+        used, n_used = None, 0
+        if used_edges is not None:
+            n_used = max((len(u) for u in used_edges), default=0)
+            used = np.full((k, max(n_used, 1)), (1 << 64) - 1, dtype=np.uint64)
+            for i, u in enumerate(used_edges):
+                used[i, :len(u)] = list(u)
+            used = np.ascontiguousarray(used[:, :n_used]) if n_used else None
+        batched = C.c_int()
+        orow, of, ot, oe, onull = u64p(), u64p(), u64p(), u64p(), u64p()
+        n, nn = C.c_uint64(), C.c_uint64()
+        st = (C.c_uint64 * 8)()
+        _ck(self.L.fh_cond_traverse_edges_batch(self.h, spec, f.ctypes.data_as(i64p), t.ctypes.data_as(i64p), C.c_uint64(k),
+                                                1 if transposed else 0, 1 if dedup else 0, _p(used) if used is not None else None,
+                                                C.c_uint64(n_used), C.byref(batched), C.byref(orow), C.byref(of), C.byref(ot),
+                                                C.byref(oe), C.byref(n), C.byref(onull), C.byref(nn), st))
+        cols = [_take(p, n.value) for p in (orow, of, ot, oe)]
+        nulls = _take(onull, nn.value)
+        if not batched.value:
+            return None
+        if as_arrays:
+            return cols, nulls, list(st)
+        return list(zip(*(c.tolist() for c in cols))), nulls.tolist(), list(st)
+
     def expand_into(self, types, srcs, dsts, bidirectional=False, emit_relationship=True, batched=True):
         s, d = _u64(srcs), _u64(dsts)
         orow, osrc, odst, oedge = u64p(), u64p(), u64p(), u64p()

@@ -618,6 +618,35 @@ int fh_cond_traverse_rows(fh_graph* g, const char* spec, const int64_t* from_ids
     });
 }
 
+int fh_cond_traverse_edges_batch(fh_graph* g, const char* spec, const int64_t* from_ids, const int64_t* to_ids, uint64_t k,
+                                 int transposed, int cross_row_dedup, const uint64_t* used_edges, uint64_t n_used, int* batched,
+                                 uint64_t** out_row, uint64_t** out_from, uint64_t** out_to, uint64_t** out_edge, uint64_t* n,
+                                 uint64_t** null_rows, uint64_t* n_null, uint64_t stats[8]) {
+    return guard([&] {
+        CondTraverseOp op = parse_spec(spec);
+        std::vector<Value> f(k), t(k);
+        for (u64 i = 0; i < k; ++i) {
+            f[i] = to_value(from_ids[i]);
+            t[i] = to_value(to_ids[i]);
+        }
+        CondTraverseOp::EdgeRows rows;
+        std::vector<u64> nulls;
+        bool ok = timed([&] {
+            return op.expand_batch_edges(g->g, f, t, transposed != 0, used_edges, used_edges ? n_used : 0, rows, nulls, stats,
+                                         cross_row_dedup != 0);
+        });
+        *batched = ok ? 1 : 0;
+        *n = rows.size();
+        *out_row = hand(rows.row);
+        *out_from = hand(rows.from);
+        *out_to = hand(rows.to);
+        *out_edge = hand(rows.edge);
+        *n_null = nulls.size();
+        *null_rows = hand(nulls);
+        return 0;
+    });
+}
+
 int fh_cond_traverse_row(fh_graph* g, const char* spec, int64_t from_id, int64_t to_id, int transposed,
                          uint64_t** out_from, uint64_t** out_to, uint64_t** out_edge, uint64_t* n) {
     uint64_t* rows = nullptr;

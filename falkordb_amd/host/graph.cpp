@@ -391,6 +391,24 @@ bool hop_layers(const Graph& g, const std::vector<Hop>& hops, HopLayers& hl, std
     }
     return true;
 }
+
+// ok[c] = nodes[c] carries every label of lids: node_has_label_id for the whole list, one batch of probes per layer of the
+// label matrix and label
+void nodes_have_labels(const Graph& g, const std::vector<LabelId>& lids, const std::vector<u64>& nodes, std::vector<uint8_t>& ok) {
+    ok.assign(nodes.size(), 1);
+    if (lids.empty() || nodes.empty()) return;
+    const VersionedMatrix& lab = g.node_labels_matrix();
+    lab.wait();
+    for (LabelId l : lids) {
+        std::vector<u64> cols(nodes.size(), l);
+        std::vector<uint8_t> in_m, in_dm, in_dp;
+        lab.m().probe(nodes, cols, in_m, nullptr);
+        lab.dm().probe(nodes, cols, in_dm, nullptr);
+        lab.dp().probe(nodes, cols, in_dp, nullptr);
+        for (size_t c = 0; c < nodes.size(); ++c)
+            if (!((in_m[c] && !in_dm[c]) || (!in_m[c] && in_dp[c]))) ok[c] = 0;
+    }
+}
 }  // namespace
 
 bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src, const std::vector<Value>* to_bound,
@@ -439,21 +457,8 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
         cand_rows.push_back(i);
         cand_nodes.push_back(src[i].id);
     }
-    std::vector<uint8_t> ok(cand_rows.size(), 1);
-    if (!src_lids->empty() && !cand_rows.empty()) {
-        // node_has_label_id for every (row, label) in one batch of probes per layer of the label matrix
-        const VersionedMatrix& lab = g.node_labels_matrix();
-        lab.wait();
-        for (LabelId l : *src_lids) {
-            std::vector<u64> cols(cand_nodes.size(), l);
-            std::vector<uint8_t> in_m, in_dm, in_dp;
-            lab.m().probe(cand_nodes, cols, in_m, nullptr);
-            lab.dm().probe(cand_nodes, cols, in_dm, nullptr);
-            lab.dp().probe(cand_nodes, cols, in_dp, nullptr);
-            for (size_t c = 0; c < cand_nodes.size(); ++c)
-                if (!((in_m[c] && !in_dm[c]) || (!in_m[c] && in_dp[c]))) ok[c] = 0;
-        }
-    }
+    std::vector<uint8_t> ok;
+    nodes_have_labels(g, *src_lids, cand_nodes, ok);   // node_has_label_id for every (row, label), batched
     bool any = false;
     for (size_t c = 0; c < cand_rows.size(); ++c)
         if (ok[c]) { src_ids[cand_rows[c]] = cand_nodes[c]; any = true; }
@@ -641,6 +646,140 @@ void CondTraverseOp::expand_row(const Graph& g, std::optional<u64> from_id, std:
             ++i;
         }
     }
+}
+
+bool CondTraverseOp::edges_batch_eligible(bool cross_row_dedup) const {
+    return hops.size() == 1 && !has_inline_attrs && (emit_relationship || bidirectional || has_sibling_edges) && !cross_row_dedup;
+}
+
+bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>& from, const std::vector<Value>& to, bool transposed,
+                                        const u64* used, u64 n_used, EdgeRows& rows, std::vector<u64>& null_rows, u64* stats,
+                                        bool cross_row_dedup) const {
+    rows.clear();
+    null_rows.clear();
+    if (stats) std::fill(stats, stats + 8, 0);
+    if (!edges_batch_eligible(cross_row_dedup)) return false;
+    const u64 k = from.size();
+    if (to.size() != k) throw GrbError(FGPU_INVALID, "expand_batch_edges: from and to differ in length");
+    auto finish = [&]() {                                                // OPTIONAL: the rows without an emission
+        if (!optional) return true;
+        std::vector<uint8_t> matched(k, 0);
+        for (u64 r : rows.row) matched[r] = 1;
+        for (u64 i = 0; i < k; ++i)
+            if (!matched[i]) null_rows.push_back(i);
+        return true;
+    };
+    const Hop& h = hops.at(0);
+    // build_state (cond_traverse.rs:362-440), as expand_row: a single unknown type or an alternation of unknown names is
+    // no_match, unknown names of an alternation are dropped, an unknown label is no_match
+    std::vector<u64> scan;
+    if (!resolve_hop_types(g, h.types, scan)) return finish();
+    auto from_l = g.resolve_label_ids(src_labels);
+    auto to_l = g.resolve_label_ids(h.dst_labels);
+    if (!from_l || !to_l) return finish();
+    // No type named: every tensor, in id order (edge_type_indices, :418-426).  The reference walks the ADJACENCY there and the
+    // device walks the union of the tensors' structures: the same pairs, by the Graph invariant that the adjacency is that union
+    // (create_edge / delete_edge and the four bulk mutations write both sides together).
+    if (h.types.empty())
+        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) scan.push_back(t);
+
+    // the rows: ~0 = unbound; a row bound to a non-node is skipped (:796-805), one with nothing bound is the host's
+    std::vector<u64> f(k, ~0ull), t(k, ~0ull);
+    std::vector<uint8_t> live(k, 0), full_walk(k, 0);
+    bool all_from = true, all_to = true, any = false;
+    for (u64 i = 0; i < k; ++i) {
+        const Value::Kind fk = from[i].kind, tk = to[i].kind;
+        if (fk == Value::Null || fk == Value::Other || tk == Value::Null || tk == Value::Other) continue;
+        if (fk == Value::Unbound && tk == Value::Unbound) { full_walk[i] = 1; continue; }
+        live[i] = 1;
+        any = true;
+        if (fk == Value::Node) f[i] = from[i].id; else all_from = false;
+        if (tk == Value::Node) t[i] = to[i].id; else all_to = false;
+    }
+    // labels: from_node carries the source labels and to_node the destination labels in both passes (fgpu.h).  A side every live
+    // row has bound is that row's from_node / to_node: probed here; otherwise the bitmap goes to the device
+    std::vector<u64> from_bm, to_bm;
+    auto side_labels = [&](const std::vector<LabelId>& lids, bool all_bound, std::vector<u64>& ids, std::vector<u64>& bm) {
+        if (lids.empty() || !any) return;
+        if (!all_bound) { bm = g.label_bitmap(lids); return; }
+        std::vector<u64> idx, nodes;
+        for (u64 i = 0; i < k; ++i)
+            if (live[i]) { idx.push_back(i); nodes.push_back(ids[i]); }
+        std::vector<uint8_t> ok;
+        nodes_have_labels(g, lids, nodes, ok);
+        for (size_t c = 0; c < idx.size(); ++c)
+            if (!ok[c]) live[idx[c]] = 0;
+    };
+    side_labels(*from_l, all_from, f, from_bm);
+    side_labels(*to_l, all_to, t, to_bm);
+    for (u64 i = 0; i < k; ++i)
+        if (!live[i]) f[i] = t[i] = ~0ull;                               // (the device skips a row with nothing bound)
+
+    // the layers of every scanned tensor, as they lie on the device
+    const size_t T = scan.size();
+    std::vector<const fgpu_mat*> m(T), dp(T), dm(T), tm(T), tdp(T), tdm(T);
+    std::vector<const fgpu_multi*> multi(T);
+    for (size_t x = 0; x < T; ++x) {
+        const Tensor& ten = g.relationship_tensors()[scan[x]];
+        ten.wait();
+        const VersionedMatrix& mt = ten.matrix_t();
+        m[x] = ten.fwd_m().snapshot();
+        dp[x] = ten.fwd_dp().nvals() ? ten.fwd_dp().snapshot() : nullptr;
+        dm[x] = ten.fwd_dm().nvals() ? ten.fwd_dm().snapshot() : nullptr;
+        tm[x] = mt.m().snapshot();
+        tdp[x] = mt.dp().nvals() ? mt.dp().snapshot() : nullptr;
+        tdm[x] = mt.dm().nvals() ? mt.dm().snapshot() : nullptr;
+        multi[x] = ten.multi_table();
+    }
+    const bool filter = used && n_used;
+    const bool first_only = !emit_relationship;
+    const int flags = (transposed ? FGPU_EDGES_TRANSPOSED : 0) | (bidirectional ? FGPU_EDGES_BIDIRECTIONAL : 0) |
+                      (first_only && !filter ? FGPU_EDGES_FIRST_ONLY : 0);
+    fgpu_ctx* ctx = g.ctx().raw();
+    EngineBuf<uint32_t> orow(ctx), ofrom(ctx), oto(ctx);
+    EngineBuf<u64> oid(ctx);
+    EngineBuf<uint8_t> opass(ctx);
+    u64 n = 0;
+    if (T && any)
+        check(fgpu_expand_edges(ctx, f.data(), t.data(), k, m.data(), dp.data(), dm.data(), tm.data(), tdp.data(), tdm.data(), multi.data(),
+                                (int)T, flags, from_bm.empty() ? nullptr : from_bm.data(), to_bm.empty() ? nullptr : to_bm.data(),
+                                orow.out(), ofrom.out(), oto.out(), oid.out(), filter ? opass.out() : nullptr, &n, stats),
+              "CondTraverse::expand_batch_edges");
+
+    // the columns, the full-matrix rows spliced in at their place, the sibling-bound ids dropped
+    size_t q = 0;
+    auto device_rows_below = [&](u64 bound) {
+        uint32_t g_row = ~0u, g_from = 0, g_to = 0;
+        uint8_t g_pass = 0;
+        bool g_done = false;
+        for (; q < n && orow[q] < bound; ++q) {
+            const u64 r = orow[q];
+            if (filter) {
+                if (orow[q] != g_row || ofrom[q] != g_from || oto[q] != g_to || opass[q] != g_pass) {
+                    g_row = orow[q]; g_from = ofrom[q]; g_to = oto[q]; g_pass = opass[q];
+                    g_done = false;
+                }
+                if (g_done) continue;
+                const u64* u = used + r * n_used;
+                if (std::find(u, u + n_used, oid[q]) != u + n_used) continue;
+                if (first_only) g_done = true;
+            }
+            rows.row.push_back(r);
+            rows.from.push_back(ofrom[q]);
+            rows.to.push_back(oto[q]);
+            rows.edge.push_back(oid[q]);
+        }
+    };
+    for (u64 i = 0; i < k; ++i) {
+        if (!full_walk[i]) continue;
+        device_rows_below(i);
+        std::vector<std::array<u64, 3>> out;
+        const std::vector<u64> u(filter ? used + i * n_used : nullptr, filter ? used + (i + 1) * n_used : nullptr);
+        expand_row(g, std::nullopt, std::nullopt, transposed, u, out);
+        for (auto& x : out) { rows.row.push_back(i); rows.from.push_back(x[0]); rows.to.push_back(x[1]); rows.edge.push_back(x[2]); }
+    }
+    device_rows_below(k);
+    return finish();
 }
 
 // ---- CondVarLenTraverse ---------------------------------------------------------------------------------

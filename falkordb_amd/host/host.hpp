@@ -383,7 +383,11 @@ class Tensor {
     // effective presence of every pair (eff_get(src, dst).has_value()): three device probes for the whole list
     void contains_batch(const std::vector<u64>& srcs, const std::vector<u64>& dsts, std::vector<uint8_t>& present) const;
     bool has_multi_edge() const { return !me_.empty(); }
-    void resize(u64 nrows, u64 ncols);                                     // :659-726
+    // me as an fgpu_multi for fgpu_expand_edges (nullptr while no pair holds several edges): built from the map on the first
+    // batch that needs it — the map is key-ordered, which is the table's order — and dropped by every method that may write me.
+    // Copies of the tensor (dup) share the table until one of them writes and drops its own reference
+    const fgpu_multi* multi_table() const;
+    void resize(u64 nrows, u64 ncols);                                     // :659-726 (me's keys are not touched)
     void flush();                                                          // :741-797
     void fold_oversized();                                                 // :815-833
     Matrix extract() const;                                                // :838-850
@@ -433,6 +437,7 @@ class Tensor {
     mutable Delta dp_, dm_;
     VersionedMatrix mt_;
     std::map<u64, std::vector<u64>> me_;   // compound key -> ascending edge ids (pairs with >= 2 edges)
+    mutable std::shared_ptr<MultiRef> multi_;   // me_ on the device (multi_table), or empty
     bool needs_flush_ = false;
 };
 
@@ -682,6 +687,29 @@ struct CondTraverseOp {
     void expand_row(const Graph& g, std::optional<u64> from_id, std::optional<u64> to_id, bool transposed,
                     const std::vector<u64>& used_edges, std::vector<std::array<u64, 3>>& out,
                     BidirDedup* dedup = nullptr, std::optional<u64> dedup_src = std::nullopt) const;
+
+    // The batches batched_eligible() sends to expand_row, on the device (fgpu_expand_edges): a single hop without static inline
+    // attributes that emits the relationship, is bidirectional or has sibling edge aliases.  Fused chains are never any of the
+    // three (fuse_anonymous_traverse.rs:83-188), and `cross_row_dedup` — the (scan source, final dest) dedup of :262-299, whose
+    // swap_remove order depends on what earlier rows emitted — stays per row.
+    bool edges_batch_eligible(bool cross_row_dedup = false) const;
+    // Rows of expand_batch_edges: (input row, from, to, edge id) in the order expand_row emits them row by row
+    struct EdgeRows {
+        std::vector<u64> row, from, to, edge;
+        size_t size() const { return row.size(); }
+        void clear() { row.clear(); from.clear(); to.clear(); edge.clear(); }
+    };
+    // expand_row for a whole input batch with ONE fgpu_expand_edges: types and labels resolved as expand_row resolves them; the
+    // labels of a side every row has bound are checked with the batched probes of expand_batch, the other side's go along as
+    // a bitmap; a row bound to a non-node is skipped (:796-805); a row with both endpoints unbound (the full-matrix walk) runs
+    // through expand_row and is spliced in at its place.  `used` (nullable): k * n_used edge ids, row i's sibling-bound ids at
+    // used[i * n_used ..] (pad with ~0): the device then runs in all-ids mode and the host drops the used ids and, without
+    // emit_relationship, keeps the first survivor of each (row, pass, pair) — exact, because the ids arrive in the reference's
+    // scan order.  OPTIONAL: the input rows without an emission go to `null_rows`.  Returns false, with nothing run, when
+    // edges_batch_eligible() is false.  stats (nullable): fgpu_expand_edges' eight.
+    bool expand_batch_edges(const Graph& g, const std::vector<Value>& from, const std::vector<Value>& to, bool transposed,
+                            const u64* used, u64 n_used, EdgeRows& rows, std::vector<u64>& null_rows, u64* stats = nullptr,
+                            bool cross_row_dedup = false) const;
 };
 
 // ExpandIntoOp (runtime/ops/expand_into.rs:121-258)

@@ -30,6 +30,7 @@ struct HandleRef {
 };
 using SnapshotRef = HandleRef<fgpu_mat, fgpu_mat_free>;        // a snapshot the engine made, until a Matrix shares it
 using PlanRef = HandleRef<fgpu_bfs_plan, fgpu_bfs_plan_free>;  // a BFS plan
+using MultiRef = HandleRef<fgpu_multi, fgpu_multi_free>;       // a tensor's multi-edge rows resident on the device
 
 // One block that goes back with fgpu_free(ctx, p): a result array of the engine, or a pinned block of fgpu_host_alloc.
 template <typename T>

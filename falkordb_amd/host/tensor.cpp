@@ -100,6 +100,7 @@ static void me_insert(std::map<u64, std::vector<u64>>& me, u64 key, u64 id) {
 
 void Tensor::set_all_from_slices(const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                                  const std::vector<u64>& ids) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     if (srcs.size() != dsts.size() || srcs.size() != ids.size())
         throw GrbError(FGPU_INVALID, "set_all_from_slices: slices differ in length");
     if (srcs.empty()) return;
@@ -247,6 +248,7 @@ BulkStats Tensor::bulk_insert(const std::vector<u64>& srcs, const std::vector<u6
 }
 
 BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     BulkStats bs;
     if (built) built->reset();
     if (n == 0) return bs;
@@ -290,6 +292,7 @@ BulkStats Tensor::bulk_insert(const u64* srcs, const u64* dsts, const u64* ids, 
 }
 
 AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, std::optional<Matrix>* built) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     AppendStats as;
     if (built) built->reset();
     if (n == 0) return as;
@@ -354,6 +357,7 @@ AppendStats Tensor::append_bulk(const u64* srcs, const u64* dsts, const u64* ids
 
 std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nodes, const std::unordered_set<u64>& skip_ids,
                                                      DetachCounts* counts) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     std::vector<std::array<u64, 3>> out;
     if (nodes.empty()) return out;
     for (u64 v : nodes)
@@ -409,6 +413,7 @@ std::vector<std::array<u64, 3>> Tensor::detach_nodes(const std::vector<u64>& nod
 }
 
 std::vector<std::pair<u64, u64>> Tensor::remove_all(const std::vector<std::array<u64, 3>>& rels) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     std::vector<std::pair<u64, u64>> emptied;
     if (rels.empty()) return emptied;
     flush();
@@ -511,6 +516,26 @@ std::vector<std::pair<u64, u64>> Tensor::remove_all(const std::vector<std::array
     return emptied;
 }
 
+const fgpu_multi* Tensor::multi_table() const {
+    if (me_.empty()) return nullptr;
+    // readers of one const Graph run on several threads (threadpool.rs:89-128): the first of them builds the table
+    static std::mutex build_mu;
+    std::lock_guard<std::mutex> lock(build_mu);
+    if (multi_) return multi_->get();
+    std::vector<u64> key, off{0}, run;
+    key.reserve(me_.size());
+    for (auto& kv : me_) {
+        if (kv.second.size() < 2) continue;   // (an inline pair needs no row)
+        key.push_back(kv.first);
+        run.insert(run.end(), kv.second.begin(), kv.second.end());
+        off.push_back(run.size());
+    }
+    auto t = std::make_shared<MultiRef>();
+    check(fgpu_multi_new(m_.ctx().raw(), key.data(), off.data(), run.data(), key.size(), t->out()), "Tensor::multi_table");
+    multi_ = std::move(t);
+    return multi_->get();
+}
+
 void Tensor::contains_batch(const std::vector<u64>& srcs, const std::vector<u64>& dsts, std::vector<uint8_t>& present) const {
     wait_fwd();
     std::vector<u64> vals;
@@ -518,6 +543,7 @@ void Tensor::contains_batch(const std::vector<u64>& srcs, const std::vector<u64>
 }
 
 std::vector<std::pair<u64, u64>> Tensor::remove_bulk(const u64* srcs, const u64* dsts, const u64* ids, u64 n, RemoveCounts* counts) {
+    multi_.reset();   // me_ may change: the resident table is rebuilt on the next batch that needs it
     std::vector<std::pair<u64, u64>> emptied;
     if (counts) counts->hit.assign(n, 0);
     if (n == 0) return emptied;

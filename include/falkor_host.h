@@ -220,6 +220,16 @@ int fh_cond_traverse_rows(fh_graph* g, const char* spec, const int64_t* from_ids
                           const int64_t* dedup_src, uint64_t k, int transposed, const uint64_t* used_edges,
                           uint64_t n_used, uint64_t** out_row, uint64_t** out_from, uint64_t** out_to,
                           uint64_t** out_edge, uint64_t* n);
+/* The same input batch on the device (CondTraverseOp::expand_batch_edges over ONE fgpu_expand_edges): the same spec and the same
+ * four columns, row-equal to fh_cond_traverse_rows, for a single hop without inline attributes that emits the relationship, is
+ * bidirectional or has sibling edge aliases.  *batched = 0, with nothing run and every output empty, when the op declines: a
+ * fused chain, a pattern the matrix path serves, or cross_row_dedup != 0 (the caller would pass dedup_src: that case stays per
+ * row).  used_edges (nullable): k * n_used ids, row i's sibling-bound ids at used_edges[i * n_used ..], padded with ~0.
+ * null_rows: the input rows an OPTIONAL traverse null-pads, those without an emission.  stats (nullable): fgpu_expand_edges'. */
+int fh_cond_traverse_edges_batch(fh_graph* g, const char* spec, const int64_t* from_ids, const int64_t* to_ids, uint64_t k,
+                                 int transposed, int cross_row_dedup, const uint64_t* used_edges, uint64_t n_used, int* batched,
+                                 uint64_t** out_row, uint64_t** out_from, uint64_t** out_to, uint64_t** out_edge, uint64_t* n,
+                                 uint64_t** null_rows, uint64_t* n_null, uint64_t stats[8]);
 /* types: comma list ("" = all).  batched != 0 runs the whole input through one set of device probes. */
 int fh_expand_into(fh_graph* g, const char* types, int bidirectional, int emit_relationship, int batched,
                    const uint64_t* srcs, const uint64_t* dsts, uint64_t k, uint64_t** out_row,

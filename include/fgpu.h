@@ -497,6 +497,64 @@ fgpu_info fgpu_expand_probe(fgpu_ctx* ctx, const uint64_t* src_ids, const uint64
                             const fgpu_mat* const* m, const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
                             const uint64_t* dst_label_bitmap, uint8_t* present, uint64_t* flops);
 
+/* One tensor's multi-edge rows (`me`, tensor.rs:184-205) resident on the device, in the shape fgpu_edges_build returns them and
+ * fgpu_edges_remove checks them: n_multi keys src << 32 | dst strictly ascending, off[0] = 0, every run at least 2 ids long and
+ * strictly ascending, no id equal to FGPU_MULTI_EDGE.  Host arrays in (copied); n_multi == 0 gives an empty table.  A malformed
+ * table returns FGPU_INVALID with nothing kept.  fgpu_multi_size: rows and ids held (either pointer nullable). */
+typedef struct fgpu_multi fgpu_multi;
+fgpu_info fgpu_multi_new(fgpu_ctx* ctx, const uint64_t* key, const uint64_t* off, const uint64_t* ids, uint64_t n_multi,
+                         fgpu_multi** out);
+fgpu_info fgpu_multi_free(fgpu_multi* t);
+fgpu_info fgpu_multi_size(const fgpu_multi* t, uint64_t* n_multi, uint64_t* n_ids);
+
+/* The per-row path of CondTraverse (CondTraverseOp::expand_row + process_pairs, cond_traverse.rs:758-1117, without the
+ * attribute filters, the sibling-edge filter and the cross-row dedup) for a whole batch of k rows over n_types relationship
+ * tensors given in SCAN order (edge_type_indices, :418-426 — the order of the pattern's names, not ascending ids).
+ *   from / to [k]   a node id, or ~0 for unbound.  A row with both unbound is skipped (the full-matrix walk stays host code).
+ *   m / dp / dm     per type the forward layers: m UINT64 (inline edge id or FGPU_MULTI_EDGE), dp UINT64 and dm (pattern) nullable —
+ *                   the array itself or any element; all square and of one dimension n < 2^32 - 1.
+ *   mt_m / mt_dp / mt_dm   per type the BOOL layers of the transposed structure (Tensor::matrix_t); mt_m is required exactly when
+ *                   some pass of some row walks incoming entries (its matrix destination is bound and its source is not).
+ *   multi           per type the tensor's fgpu_multi, nullable when it holds no FGPU_MULTI_EDGE.
+ *   flags           FGPU_EDGES_TRANSPOSED: the pattern runs against the storage direction (`from` is the matrix destination);
+ *                   FGPU_EDGES_BIDIRECTIONAL: a second pass with the endpoints swapped, self-loops dropped there;
+ *                   FGPU_EDGES_FIRST_ONLY: one representative id per pair, as !emit_relationship (:1063-1081).
+ *   from_bitmap / to_bitmap   nullable (n + 63) / 64-word node sets, applied to the ORIENTED from_node / to_node of every pair.
+ *                   build_state (:376-389) hands process_pairs the labels of the matrix source and destination per pass:
+ *                   (from, to) forward and (to, from) in reverse, swapped again under `transposed`; process_pairs orients the
+ *                   pair by the same rule (from_node = the matrix destination on a reverse walk), so in both passes and under
+ *                   `transposed` the four lists reduce to: from_node carries the source labels, to_node the destination labels.
+ * Per row: the forward pass has matrix source = transposed ? to : from and the other endpoint as matrix destination.  A bound
+ * source walks that row of the effective structure (pattern(m) \ dm) U pattern(dp) by ascending column, cut to the destination
+ * when that is bound too; with only the destination bound, that row of the transposed structure by ascending source.  The
+ * bidirectional pass follows the row's forward pass.  The pair set is the union over the types; per pair, in that order, the
+ * types are scanned in the given order and each emits the ids of Tensor::get(mat_src, mat_dst) ascending: dp's value wins over
+ * m's, a dm entry hides m's, FGPU_MULTI_EDGE expands to the table's row.  FIRST_ONLY keeps the first id of each (row, pass, pair).
+ * Out: out_row / out_from / out_to (uint32_t) and out_id (uint64_t), *out_n entries each, row ascending and then as above;
+ * duplicate rows of the batch each get their own output rows.  out_pass (nullable: not wanted) receives a fifth column, 0 for an id
+ * of the forward pass and 1 for the reverse pass — what tells the pair (a, b) walked forward from the pair (b, a) walked in
+ * reverse, which orient to the same (from_node, to_node).  Engine-owned blocks (pinned from 256 KiB up, filled by DMA),
+ * released with fgpu_free; NULL when *out_n == 0.  k == 0 or n_types == 0 gives *out_n = 0.  The call keeps no device memory.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated and the context still usable, for: a bound id at or past n; layers
+ * that are not all n x n; an unvalued m (or dp); a missing mt_m where one is needed; k above 2^24, n_types above 64, unknown flag
+ * bits; walked entries or emitted ids that reach 2^32 - 1; a visited pair that holds FGPU_MULTI_EDGE with no table row (counted
+ * on the device and read back before any output is allocated, as fgpu_edges_remove does).
+ * stats (nullable): [0] stored entries walked outgoing, [1] stored entries walked incoming, [2] ids emitted, [3] multi-edge
+ * pairs expanded, [4] longest emitted list of one (pair, type), [5] the ordering path: 0 = the entry positions gave the order (one
+ * type, no dp layer), 1 = one stable sort on (row, pass, other node), 2 = two stable sorts (other node, then (row, pass)),
+ * [6] (pair, type) items that emitted, [7] row segments (row x pass x type x layer) of the batch.
+ * Work: a lane per segment (binary searches), a lane per walked entry (value resolved by binary search), a lane per emitted id;
+ * every output is placed by a scan; no wavefront-per-row loop. */
+#define FGPU_EDGES_TRANSPOSED 1
+#define FGPU_EDGES_BIDIRECTIONAL 2
+#define FGPU_EDGES_FIRST_ONLY 4
+fgpu_info fgpu_expand_edges(fgpu_ctx* ctx, const uint64_t* from, const uint64_t* to, uint64_t k, const fgpu_mat* const* m,
+                            const fgpu_mat* const* dp, const fgpu_mat* const* dm, const fgpu_mat* const* mt_m,
+                            const fgpu_mat* const* mt_dp, const fgpu_mat* const* mt_dm, const fgpu_multi* const* multi,
+                            int n_types, int flags, const uint64_t* from_bitmap, const uint64_t* to_bitmap, uint32_t** out_row,
+                            uint32_t** out_from, uint32_t** out_to, uint64_t** out_id, uint8_t** out_pass, uint64_t* out_n,
+                            uint64_t stats[8]);
+
 /* The same chain with the result STREAMED to the host in chunks of whole source rows — the shape in which
  * CondTraverseOp::expand_batch consumes it (cond_traverse.rs:644-751: walk (row_i, dest) ascending, emit an output batch
  * every 1024 pairs): the chain runs once, F stays on the device, and chunks of at most `chunk_rows` consecutive source

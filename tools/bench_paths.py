@@ -96,7 +96,14 @@
           and 10 % as many tuples built by fgpu_edges_build, its device phases, beside one fgpu_mat_merge(m, fwd, NULL) over
           the same pairs.  `append <scale>`: the twin comparison at that scale only.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  edges   the relationship-emitting CondTraverse batch: one 1024-row batch of (a:P)-[r]->(b) and one of (a:P)-[r]-(b) through
+          Graph.cond_traverse_edges_batch (ONE fgpu_expand_edges) against cond_traverse_rows (the per-row path, 8 rows a call,
+          stopped at a 10 s deadline and extrapolated) on one host-layer graph of the distinct RMAT-18 and RMAT-20 edges loaded
+          with bulk_insert_edges, 1 % of the pairs multi-edge; medians of 5 calls after 2 warm-ups, with the stats of the call.
+          Then the bare fgpu_expand_edges beside fgpu_expand_pairs32 on the same sources and the same tensor (fgpu_edges_build
+          on the engine context), with its device phases.  `edges <scale>`: that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|edges|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -612,6 +619,97 @@ def bench_edel(scales=(18, 20), raw_scale=22, deadline_s=10.0):
                                   "fgpu_mat_merge(m, NULL, dm) with dm the BOOL matrix of the same pairs, median of 5 after 2 warm-up: "
                                   "it drops the whole pair where the call removes single edges"}), flush=True)
         del dm
+
+
+def bench_edges(scales=(18, 20), deadline_s=10.0, k=1024):
+    """The relationship-emitting CondTraverse batch (fgpu_expand_edges under Graph.cond_traverse_edges_batch) against the per-row
+    path it takes over (cond_traverse_rows), and the bare call beside fgpu_expand_pairs32 on the same sources."""
+    import ctypes as C
+    from falkordb_amd import _ffi, host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+    for scale in scales:
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        A.free()
+        rng = np.random.default_rng(200 + scale)
+        twice = rng.choice(len(ci), len(ci) // 100, replace=False)          # 1 % of the pairs hold a second edge
+        u, v = np.concatenate([r, r[twice]]), np.concatenate([ci, ci[twice]])
+        ids = np.arange(len(u), dtype=np.uint64)
+        g = host.Graph(hc, n)
+        t = g.add_type("KNOWS")
+        g.bulk_insert_edges(t, u, v, ids)
+        lid = g.add_label("P")
+        srcs = rng.choice(n, k, replace=False)
+        for x in np.concatenate([srcs, rng.choice(n, k, replace=False)]).tolist():
+            g.label_node(int(x), lid)
+        g.commit()
+        srcs = srcs.tolist()
+        none = [None] * k
+        out = {"path": "cond_traverse_edges", "scale": scale, "edges": len(u), "multi_pairs": len(twice), "rows": k}
+        for name, bidir in (("out", False), ("both", True)):
+            spec = host.cond_spec(src_labels=["P"], hops=[(["KNOWS"], [])], emit=True, bidir=bidir)
+            ts, res = [], None
+            for rep in range(7):                                            # (2 warm-ups: the first builds the resident table)
+                t0 = time.perf_counter()
+                res = g.cond_traverse_edges_batch(spec, srcs, none, as_arrays=True)
+                ts.append(time.perf_counter() - t0)
+            cols, _, st = res
+            done, got, t0 = 0, 0, time.perf_counter()
+            while done < k:                                                 # the per-row path, 8 rows a call, up to the deadline
+                got += len(g.cond_traverse_rows(spec, srcs[done:done + 8], none[:8]))
+                done += 8
+                if time.perf_counter() - t0 > deadline_s:
+                    break
+            dt = time.perf_counter() - t0
+            ref = dt / done * k
+            if done >= k:
+                assert got == len(cols[0])
+            out[name] = {"batch_ms_median_of_5": round(float(np.median(ts[2:])) * 1e3, 3), "batch_ms_all": [round(x * 1e3, 3) for x in ts],
+                         "ids": int(len(cols[0])), "stats": st,
+                         "per_row": {"rows_done": min(done, k), "finished": done >= k, "s": round(dt, 3),
+                                     "ms_per_row": round(dt / done * 1e3, 3), "s_for_the_batch": round(ref, 3)},
+                         "quotient": round(ref / float(np.median(ts[2:])), 1)}
+        # the bare calls on the same sources: the tensor as fgpu_edges_build makes it, on the engine context
+        fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, ids)
+        multi = ctx.multi_new(np.array(mkey), np.array(moff), np.array(mids))
+        for name, bidir in (("out", False), ("both", True)):
+            t_call, res = timed(ctx, lambda: ctx.expand_edges(srcs, none, [fwd], None, None, [bwd], None, None, [multi],
+                                                              bidirectional=bidir), reps=5, warm=2)
+            out["raw_" + name] = {"ms": round(t_call * 1e3, 3), "stats": res[-1]}
+            del res
+        ctx.prof_enable(True)
+        res = ctx.expand_edges(srcs, none, [fwd], None, None, [bwd], None, None, [multi])
+        ctx.sync()
+        out["raw_out"]["device_phases_ms"] = {p["kernel"]: round(p["ms"], 3) for p in ctx.prof_read() if p["kernel"].startswith("ee_")}
+        ctx.prof_enable(False)
+        del res
+        src64 = np.asarray(srcs, dtype=np.uint64)
+        arr = (C.c_void_p * 1)(fwd._h)
+
+        def pairs32():
+            prow, pdest = C.c_void_p(), _ffi.u32p()
+            np_, fl = C.c_uint64(), C.c_uint64()
+            _ffi.check(ctx.lib.fgpu_expand_pairs32(ctx._h, src64.ctypes.data_as(_ffi.u64p), k, arr, None, None, 1, None, None, 16,
+                                                   C.byref(prow), C.byref(pdest), C.byref(np_), C.byref(fl)))
+            ctx.lib.fgpu_free(ctx._h, prow)
+            ctx.lib.fgpu_free(ctx._h, C.cast(pdest, C.c_void_p))
+            return np_.value
+
+        t_pairs, npairs = timed(ctx, pairs32, reps=5, warm=2)
+        out["raw_pairs32"] = {"ms": round(t_pairs * 1e3, 3), "pairs": npairs}
+        out["raw_quotient_edges_over_pairs32"] = round(out["raw_out"]["ms"] / (t_pairs * 1e3), 2)
+        out["note"] = ("one host-layer graph loaded with bulk_insert_edges + commit (distinct RMAT edges, a second edge on a seeded 1 % of "
+                       "the pairs), 1024 seeded sources carrying :P; host clock around the Python call, results copied out included; "
+                       "batch: 2 warm-ups, median of 5; per row: cond_traverse_rows 8 rows a call up to the deadline (finished = "
+                       "false: s_for_the_batch = ms_per_row x rows, and the quotient uses it); raw: the same tensor from "
+                       "fgpu_edges_build on the engine context, median of 5 synchronised calls after 2 warm-ups, uploads and the "
+                       "read-back of the columns included")
+        print(json.dumps(out), flush=True)
+        del g, fwd, bwd, multi
 
 
 def bench_append(scales=(18, 20), raw_scale=22):
@@ -1364,5 +1462,7 @@ if __name__ == "__main__":
         bench_detach(*(((), scale, 0) if scale else ()))
     if what == "edel":                           # (edge-by-edge deletes up to their deadlines: not part of `all`)
         bench_edel(*(((scale,), 0) if scale else ()))
+    if what == "edges":                          # (the per-row path up to its deadlines: not part of `all`)
+        bench_edges(*(((scale,),) if scale else ()))
     if what == "append":                         # (seconds of edge-by-edge inserts per twin: not part of `all`)
         bench_append(*(((scale,), 0) if scale else ()))
