@@ -1972,6 +1972,71 @@ fgpu_info bp_hop(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* 
     return bp_hop_finish(ctx, p, s, o, next_m, st, pull_idx);
 }
 
+// ---- the top hub's out-rows of a clean partitioned count hop (bitpart.hip bp_xplan_hub) ---------------------------------------
+// When row h of X holds all nsrc bits, Y[v] = OR over in(v) of X[u] holds them for every v of out(h) — 56 % of the entries of
+// A' at RMAT-22 — and the hop runs under the reduced plan, which does not know those rows.  Their share of the sums is exact:
+// nsrc bits per row, and the checksum's sum of (row hash) x (destination hash) over a block of ones factors into
+// (sum of the bits' hashes) x (sum of the rows' hashes).  The test reads the device's own state, never what the host believes
+// about the sources (spgemm.hip orders a scan's sources so that whole passes pass it; nothing here relies on that).
+// out[0] = 1 when row `slot` of x is nsrc ones and nothing else; out[1] = the sum of the bits' checksum hashes
+__global__ __launch_bounds__(256) void bp_hub_check_kernel(const u64* __restrict__ x, u32 slot, u32 ws, u32 nsrc, const u32* __restrict__ rowmap,
+                                                           const u64* __restrict__ rowhash, u64* __restrict__ out) {
+    __shared__ u64 s_h[4];
+    bool bad = false;
+    for (u32 k = threadIdx.x; k < ws; k += 256) {
+        const u32 lo = k * 64;
+        const u64 want = nsrc >= lo + 64 ? ~0ull : nsrc > lo ? (1ull << (nsrc - lo)) - 1ull : 0ull;   // (the last word may be partial)
+        bad |= x[(size_t)slot * ws + k] != want;
+    }
+    u64 hs = 0;
+    for (u32 i = threadIdx.x; i < nsrc; i += 256) hs += rowhash ? rowhash[i] : cs_row_hash(rowmap ? (u64)rowmap[i] : (u64)i);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) hs += (u64)__shfl_xor((long long)hs, d, 64);
+    if (lane_id() == 0) s_h[threadIdx.x >> 6] = hs;
+    const int nbad = __syncthreads_count(bad ? 1 : 0);
+    if (threadIdx.x == 0) {
+        out[0] = nbad == 0 && nsrc ? 1ull : 0ull;
+        out[1] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
+    }
+}
+// the sums of the rows out(h), all of nsrc ones: acc[0] += nsrc per counted row, acc[1] += (hash sum of the bits) x (hash of the
+// row).  Without a label every row counts and the plan's constants say it all (one thread); with one, a pass over the list
+__global__ __launch_bounds__(256) void bp_hub_sums_kernel(const u32* __restrict__ rows, u32 deg, u64 dsum, const u64* __restrict__ label,
+                                                          u32 nsrc, const u64* __restrict__ hsum, int with_sum,
+                                                          unsigned long long* __restrict__ acc) {
+    u64 cnt = 0, ds = 0;
+    if (!label) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { cnt = deg; ds = dsum; }
+    } else {
+        for (u32 i = blockIdx.x * 256 + threadIdx.x; i < deg; i += gridDim.x * 256) {
+            const u32 v = rows[i];
+            if ((label[v >> 6] >> (v & 63u)) & 1ull) { ++cnt; ds += cs_dest_hash(v); }
+        }
+    }
+    bp_block_add2(cnt * nsrc, with_sum ? ds * hsum[0] : 0ull, acc);
+}
+// *hub = the reduced plan when the state saturates the hub's row (its rows' sums are then in acc already), nullptr otherwise
+static fgpu_info bp_hub_rows(fgpu_ctx* ctx, const BitState& s, const BpXPlan* xp, int mode, const u64* label_dev, u64* acc,
+                             const BpXPlan** hub) {
+    *hub = nullptr;
+    BpXHub hb;
+    if (!bp_xplan_hub(xp, &hb) || hb.slot >= s.n || !s.nsrc) return FGPU_OK;
+    DevBuf<u64> chk;
+    FGPU_TRY(chk.alloc(ctx, 2));
+    FGPU_TRY(launch(bp_hub_check_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, hb.slot, s.ws, s.nsrc,
+                    (const u32*)s.rowmap.p, (const u64*)s.rowhash.p, chk.p));
+    u32 sat = 0;
+    FGPU_TRY(read_u32(ctx, (const u32*)chk.p, &sat));
+    if (!sat) return FGPU_OK;
+    ProfScope ps(ctx, "xp_hub_rows", (u64)hb.deg * (label_dev ? 4 : 0));
+    u32 grid = label_dev ? cdiv(hb.deg, 256) : 1u;
+    if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
+    FGPU_TRY(launch(bp_hub_sums_kernel, dim3(grid), dim3(256), 0, ctx->stream(), hb.rows, hb.deg, hb.dsum, label_dev, s.nsrc,
+                    (const u64*)(chk.p + 1), mode == 2 ? 1 : 0, (unsigned long long*)acc));
+    *hub = hb.plan;                                          // (chk returns to this lane's pool: reused in stream order)
+    return FGPU_OK;
+}
+
 fgpu_info bp_hop_count(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, u64* flops,
                        const u64* label_dev, u64* nnz, u64* checksum) {
     HopPlan p;
@@ -1988,10 +2053,29 @@ fgpu_info bp_hop_count(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu
     if (p.mode == 2) FGPU_TRY(bp_cs_tables(ctx, s, tab));
     const HopOut out = {side.p, nullptr, BpFinal{tbits.p, tpref.p, label_dev, tab.p, (unsigned long long*)acc.p, s.w}};
     const u64 xrows = s.nz_rows < (u64)s.n ? s.nz_rows : (u64)s.n;
-    if (p.xp) FGPU_TRY(bp_xpull_count(ctx, p.xp, p.t, s.x.p, s.ws, p.mode, out.fin, side.p, p.lds_tables, xrows));
+    // a clean partitioned hop whose state saturates the top hub's row leaves that hub's out-rows to their closed form
+    const BpXPlan* hub = nullptr;
+    if (p.no_touched) FGPU_TRY(bp_hub_rows(ctx, s, p.xp, p.mode, label_dev, acc.p, &hub));
+    if (p.xp) FGPU_TRY(bp_xpull_count(ctx, hub ? hub : p.xp, p.t, s.x.p, s.ws, p.mode, out.fin, side.p, p.lds_tables, xrows));
     else if (p.t) FGPU_TRY(bp_pull(ctx, p, s, out, nullptr, nullptr, nullptr));
     FGPU_TRY(bp_delta_fixups(ctx, p, s, out));
     return bp_count_finish(ctx, s, n_out, ntouched, out, nnz, checksum);
+}
+
+// *in_bits = the in-neighbours of m's top hub, a bit per vertex, when a count hop over m from a state of `nsrc` bits per row has a
+// reduced plan to run under (nullptr otherwise): what a whole-frontier scan orders its sources by
+fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64** in_bits) {
+    *in_bits = nullptr;
+    BitState lay;
+    bp_layout(lay, (u32)m->nrows, nsrc);
+    if (!m->nnz || m->is_hyper() || !bp_xcd_applies(ctx, lay.n, lay.ws)) return FGPU_OK;
+    const fgpu_mat* t = nullptr;
+    const BpXPlan* xp = nullptr;
+    BpXHub hb;
+    FGPU_TRY(transposed_with_items(ctx, m, &t));
+    FGPU_TRY(bp_xplan(ctx, m, t, &xp));
+    if (bp_xplan_hub(xp, &hb)) *in_bits = hb.in_bits;
+    return FGPU_OK;
 }
 
 // ---------------------------------------------------------------------------------

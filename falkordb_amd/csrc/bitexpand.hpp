@@ -50,6 +50,17 @@ struct BpXPlan;
 fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const BpXPlan** out);
 fgpu_info bp_xplan_chunks(fgpu_ctx* ctx, const BpXPlan* xp, uint32_t** out, uint64_t* nwords);   // the chunk table, read back
 const u32* bp_xplan_perm(const BpXPlan* p);   // slot of row u of X in the state the plan gathers from (nullptr: slot = u)
+// the top hub h of a plan's matrix and the reduced plan kept beside it: A' with the rows out(h) emptied, gathering from the same
+// layout of X.  false when the plan has none (out(h) holds under a quarter of the entries, or the build failed)
+struct BpXHub {
+    const BpXPlan* plan;     // the reduced plan
+    u32 slot;                // h's row of X in the plan's layout
+    u32 deg;                 // |out(h)|
+    u64 dsum;                // sum of cs_dest_hash over out(h)
+    const u32* rows;         // out(h), deg entries
+    const u64* in_bits;      // bit u: (u, h) is an entry of the matrix
+};
+bool bp_xplan_hub(const BpXPlan* xp, BpXHub* out);
 // rows of Y = OR of the gathered rows of X, per vertex, counted / check-summed (mode 1 / 2) or — touched rows — stored into
 // their side-buffer slot; `side` is zeroed by the caller, the delta fix-ups and the side-row count follow in bp_hop_count
 fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, const u64* x, u32 ws, int mode, const BpFinal& fin,

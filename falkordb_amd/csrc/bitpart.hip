@@ -79,6 +79,17 @@ struct BpXPlan {
     // the same heat, where vertex order puts a hot row next to a random one — the L2's capacity for hot rows doubles
     // (simulated: hit rate 0.75 -> 0.85 at RMAT-22).  The hop that PRODUCES the state writes row v at slot perm[v] (bitexpand.hip).
     DevBuf<u32> perm;
+    // the top hub's out-rows (bp_xplan_hub below).  h = the row of m with the most entries (smallest id on a tie); out(h) = the
+    // rows of A' that have h as an in-neighbour.  When row slot(h) of X is all ones, every row of out(h) of Y is all ones
+    // with no gather at all, and the hop runs under `hub`: the plan of A' with the rows out(h) emptied, gathering from the SAME
+    // layout of X (it is built with this plan's perm and keeps none of its own).  Only the full plan of a triple carries these.
+    BpXPlanPtr hub;                // null: no reduced plan (share of out(h) under XP_HUB_MIN_SHARE, or its build failed: not retried)
+    u32 hub_v = 0, hub_slot = 0;   // h and its slot in X (perm[h], or h)
+    u32 hub_deg = 0;               // |out(h)|
+    u64 hub_dsum = 0;              // sum of cs_dest_hash(v) over out(h), mod 2^64
+    DevBuf<u32> hub_rows;          // out(h), as m lists it
+    DevBuf<u64> hub_in;            // bit u: u has an edge to h in m (ncols bits): what a scan orders its sources by (spgemm.hip)
+    const BpXPlan* full = nullptr; // on a reduced plan: the full plan that owns it
 };
 const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm.p : nullptr; }
 void BpXPlanDelete::operator()(BpXPlan* p) const { delete p; }
@@ -385,9 +396,16 @@ static fgpu_info xp_cut_cells(fgpu_ctx* ctx, BpXPlan* xp, u32 (&hp)[27], bool* d
     return FGPU_OK;
 }
 
+// what the builder reads of A': the cached transpose, or a temporary copy of it with some rows emptied
+struct XpSource {
+    const u32 *rowptr, *colidx;
+    u64 nrows, ncols, nnz;
+};
 // builds the plan of `t` (= m') under one (direct, dense, cut) triple; the caller holds m->idx_mu.  *out is set when the plan is
-// complete on the device; an error frees whatever was built so far
-static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, int cut, BpXPlanPtr* out) {
+// complete on the device; an error frees whatever was built so far.  `layout` (nullable): the plan whose layout of X this one
+// gathers from too — its perm is used as it is and the new plan keeps none
+static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const XpSource* t, int direct, int dense, int cut, const BpXPlan* layout,
+                                BpXPlanPtr* out) {
     BpXPlanPtr xp(new (std::nothrow) BpXPlan());
     FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
     const u32 n = (u32)t->nrows;
@@ -413,7 +431,8 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     FGPU_TRY(off.alloc(ctx, total + 1));
     FGPU_TRY(ridx.alloc(ctx, total + 1));
     const u32 prange = (u32)((((t->ncols + 7) / 8) + 15) & ~15ull);
-    if (ctx->opt.expand_xcd_relabel && !m->is_hyper() && m->nrows == t->ncols && t->ncols % 128 == 0 && (u64)prange * 8 == t->ncols) {
+    const u32* perm = layout ? layout->perm.p : nullptr;
+    if (!layout && ctx->opt.expand_xcd_relabel && !m->is_hyper() && m->nrows == t->ncols && t->ncols % 128 == 0 && (u64)prange * 8 == t->ncols) {
         // rank the rows of X by out-degree (descending, ties by id) and deal the ranks to the partitions
         const u32 nu = (u32)t->ncols;
         DevBuf<u32> dkey, dval, by_rank, kptr;
@@ -425,13 +444,14 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
         FGPU_TRY(launch(xp_deg_key_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)m->rowptr, nu, dkey.p, dval.p));
         FGPU_TRY(sort_u32_pairs_by_key(ctx, dkey.p, dval.p, nu, 65536, by_rank.p, kptr.p));
         FGPU_TRY(launch(xp_rank_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)by_rank.p, nu, prange, xp->perm.p));
+        perm = xp->perm.p;
     }
     FGPU_TRY(xp->pstart_dev.alloc(ctx, 27));
     FGPU_TRY(xp->pcol.alloc(ctx, ((size_t)t->nnz + 64)));
     {
         DevBuf<uint2> pairs;
         FGPU_TRY(pairs.alloc(ctx, t->nnz));
-        FGPU_TRY(partition_csr_entries(ctx, t->colidx, t->rowptr, n, t->nnz, xp->perm.p, prange, 8, pairs.p, xp->pstart_dev.p));
+        FGPU_TRY(partition_csr_entries(ctx, t->colidx, t->rowptr, n, t->nnz, perm, prange, 8, pairs.p, xp->pstart_dev.p));
         u32 rgrid = cdiv(t->nnz, 256 * 4);
         if (rgrid > (u32)ctx->cus * 16) rgrid = ctx->cus * 16;
         FGPU_TRY(launch(xp_runs_kernel, dim3(rgrid), dim3(256), 0, st, (const uint2*)pairs.p, (const u32*)xp->pstart_dev.p, n, (u32)t->nnz,
@@ -514,6 +534,138 @@ static fgpu_info bp_xplan_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat
     return FGPU_OK;
 }
 
+// ---- the top hub's out-rows (once per plan) -----------------------------------------------------------------------------------
+// At RMAT-22 the vertex of largest out-degree h has 97 939 out-neighbours, and those rows of A' — 4.9 % of the rows with
+// entries — hold 56 % of the entries: every one of them gathers row h of X among its in-neighbours' rows.  When that row is
+// all ones (every source of the pass reaches h in the hops before) their result is known before the hop starts, and the hop
+// runs under a second plan from which they are gone (bitexpand.hip bp_hop_count decides, on the device's own state).
+// The threshold is a design constant: the second plan costs (1 - share) of a plan's memory, and below a quarter of the entries it
+// buys little.
+constexpr u32 XP_HUB_MIN_SHARE_DEN = 4;   // out(h) must hold at least 1 / 4 of the entries of A'
+// best = max over the rows of (entries << 32 | ~row): the most entries, the smallest id on a tie.  (Not by_rank[0] of the
+// relabel sort: its key stops at 65 535 entries, above which rows tie by id alone.)
+__global__ __launch_bounds__(256) void xp_hub_pick_kernel(const u32* __restrict__ rowptr, u32 nrows, unsigned long long* __restrict__ best) {
+    u64 k = 0;
+    for (u32 u = blockIdx.x * 256 + threadIdx.x; u < nrows; u += gridDim.x * 256) {
+        const u64 key = ((u64)(rowptr[u + 1] - rowptr[u]) << 32) | (u64)(~u);
+        k = key > k ? key : k;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u64 o = (u64)__shfl_xor((long long)k, d, 64);
+        k = o > k ? o : k;
+    }
+    if (lane_id() == 0 && k) atomicMax(best, (unsigned long long)k);
+}
+// out(h) = row h of m: the list, a flag per row of A' (drop[v] = 1), and sums[0] = entries of those rows, sums[1] = the sum of
+// their destination hashes
+__global__ __launch_bounds__(256) void xp_hub_rows_kernel(const u32* __restrict__ mrowptr, const u32* __restrict__ mcol, u32 h, u32 n,
+                                                          const u32* __restrict__ trowptr, u32* __restrict__ list, u32* __restrict__ drop,
+                                                          unsigned long long* __restrict__ sums) {
+    const u32 b = mrowptr[h], deg = mrowptr[h + 1] - b;
+    u64 ent = 0, ds = 0;
+    for (u32 i = blockIdx.x * 256 + threadIdx.x; i < deg; i += gridDim.x * 256) {
+        const u32 v = mcol[b + i];
+        list[i] = v;
+        if (v < n) {                                          // (a column of m is a row of A')
+            drop[v] = 1u;
+            ent += trowptr[v + 1] - trowptr[v];
+        }
+        ds += cs_dest_hash(v);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        ent += (u64)__shfl_xor((long long)ent, d, 64);
+        ds += (u64)__shfl_xor((long long)ds, d, 64);
+    }
+    if (lane_id() == 0) {
+        if (ent) atomicAdd(sums, (unsigned long long)ent);
+        atomicAdd(sums + 1, (unsigned long long)ds);
+    }
+}
+// kd[v] = entries row v keeps (kd[n] = 0: the scan leaves the total there)
+__global__ void xp_hub_kept_kernel(const u32* __restrict__ trowptr, const u32* __restrict__ drop, u32 n, u32* __restrict__ kd) {
+    for (u32 v = blockIdx.x * 256 + threadIdx.x; v <= n; v += gridDim.x * 256) kd[v] = v < n && !drop[v] ? trowptr[v + 1] - trowptr[v] : 0u;
+}
+// the kept rows' column ids, compacted: a wavefront per row
+__global__ __launch_bounds__(256) void xp_hub_compact_kernel(const u32* __restrict__ trowptr, const u32* __restrict__ tcol,
+                                                             const u32* __restrict__ rp, u32 n, u32* __restrict__ col) {
+    const u32 lane = lane_id();
+    const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (gridDim.x * 256) >> 6;
+    for (u32 v = wave; v < n; v += nwaves) {
+        const u32 o = rp[v], k = rp[v + 1] - o, b = trowptr[v];
+        for (u32 i = lane; i < k; i += 64) col[o + i] = tcol[b + i];
+    }
+}
+// bit u of `bits`: u is an in-neighbour of h (row h of A')
+__global__ void xp_hub_in_kernel(const u32* __restrict__ trowptr, const u32* __restrict__ tcol, u32 h, u64* __restrict__ bits) {
+    const u32 b = trowptr[h], e = trowptr[h + 1];
+    for (u32 q = b + blockIdx.x * 256 + threadIdx.x; q < e; q += gridDim.x * 256)
+        atomicOr((unsigned long long*)&bits[tcol[q] >> 6], 1ull << (tcol[q] & 63u));
+}
+
+// names the hub of the finished full plan `xp` and, when its out-rows hold their share of A', builds the reduced plan beside it
+static fgpu_info bp_xplan_hub_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, int cut, BpXPlan* xp) {
+    if (m->is_hyper() || m->nrows >= 0xFFFFFFFFull || m->ncols != t->nrows || m->nrows != t->ncols) return FGPU_OK;
+    hipStream_t st = ctx->stream();
+    const u32 n = (u32)t->nrows, nu = (u32)m->nrows;
+    DevBuf<u64> sums;                                        // [0] the pick, [1] entries of out(h), [2] their hash sum
+    FGPU_TRY(sums.alloc(ctx, 3));
+    FGPU_HIP(hipMemsetAsync(sums.p, 0, 3 * sizeof(u64), st));
+    u32 grid = cdiv(nu, 256);
+    if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
+    FGPU_TRY(launch(xp_hub_pick_kernel, dim3(grid), dim3(256), 0, st, (const u32*)m->rowptr, nu, (unsigned long long*)sums.p));
+    u64 best = 0;
+    FGPU_TRY(read_u64(ctx, sums.p, &best));
+    const u32 deg = (u32)(best >> 32), h = ~(u32)best;
+    if (!deg || h >= nu) return FGPU_OK;
+    DevBuf<u32> list, drop, kd, rp, col;
+    FGPU_TRY(list.alloc(ctx, deg));
+    FGPU_TRY(drop.alloc(ctx, (size_t)n + 1));
+    FGPU_HIP(hipMemsetAsync(drop.p, 0, ((size_t)n + 1) * sizeof(u32), st));
+    grid = cdiv(deg, 256);
+    if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
+    FGPU_TRY(launch(xp_hub_rows_kernel, dim3(grid), dim3(256), 0, st, (const u32*)m->rowptr, (const u32*)m->colidx, h, n,
+                    (const u32*)t->rowptr, list.p, drop.p, (unsigned long long*)(sums.p + 1)));
+    u32 got[4];
+    FGPU_TRY(read_words(ctx, (const u32*)(sums.p + 1), 4, got));
+    const u64 gone = (u64)got[0] | ((u64)got[1] << 32);
+    if (gone * XP_HUB_MIN_SHARE_DEN < t->nnz || gone >= t->nnz) return FGPU_OK;   // (too small a share, or nothing would be left)
+    // t': the rows out(h) emptied — row pointers from a scan of the kept degrees, column ids compacted
+    FGPU_TRY(kd.alloc(ctx, (size_t)n + 1));
+    FGPU_TRY(rp.alloc(ctx, (size_t)n + 1));
+    FGPU_TRY(launch(xp_hub_kept_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)drop.p, n, kd.p));
+    FGPU_TRY(scan_u32(ctx, kd.p, rp.p, (u64)n + 1, nullptr));
+    u32 kept = 0;                                            // (t' is sized by what the scan says, whatever the sum above said)
+    FGPU_TRY(read_u32(ctx, rp.p + n, &kept));
+    FGPU_REQUIRE(kept >= 1 && (u64)kept + gone == t->nnz, FGPU_INVALID, "partitioned pull: the hub's rows hold %llu of %llu entries, %u stay",
+                 (unsigned long long)gone, (unsigned long long)t->nnz, kept);
+    FGPU_TRY(col.alloc(ctx, kept));
+    FGPU_TRY(launch(xp_hub_compact_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)t->colidx,
+                    (const u32*)rp.p, n, col.p));
+    const XpSource src = {rp.p, col.p, t->nrows, t->ncols, kept};
+    BpXPlanPtr reduced;
+    FGPU_TRY(bp_xplan_build(ctx, m, &src, direct, dense, cut, xp, &reduced));   // (synchronised: t' may go)
+    const size_t nwords = ((size_t)t->ncols + 63) / 64;
+    FGPU_TRY(xp->hub_in.alloc(ctx, nwords + 1));
+    FGPU_HIP(hipMemsetAsync(xp->hub_in.p, 0, (nwords + 1) * sizeof(u64), st));
+    if (h < n) FGPU_TRY(launch(xp_hub_in_kernel, dim3(64), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)t->colidx, h, xp->hub_in.p));
+    u32 slot = h;
+    if (xp->perm.p) FGPU_TRY(read_u32(ctx, xp->perm.p + h, &slot));
+    FGPU_HIP(hipStreamSynchronize(st));
+    xp->hub_v = h; xp->hub_slot = slot; xp->hub_deg = deg;
+    xp->hub_dsum = (u64)got[2] | ((u64)got[3] << 32);
+    xp->hub_rows = std::move(list);
+    reduced->full = xp;
+    xp->hub = std::move(reduced);
+    return FGPU_OK;
+}
+bool bp_xplan_hub(const BpXPlan* xp, BpXHub* out) {
+    if (!xp || !xp->hub || !xp->hub->usable) return false;
+    *out = BpXHub{xp->hub.get(), xp->hub_slot, xp->hub_deg, xp->hub_dsum, xp->hub_rows.p, xp->hub_in.p};
+    return true;
+}
+
 // The plan is an optional accelerator: when its build fails (its temporaries are large — 64 bytes per vertex and 8 per entry) the
 // half-built plan is freed, an empty one is attached as "not usable" (no second attempt per snapshot), the error is dropped
 // and the hop falls back to the plain pull.  (idx_mu is held from the look-up to the attachment: no reader
@@ -529,9 +681,16 @@ fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const Bp
     BpXPlanPtr& slot = t->bp_xplan[direct + 2 * dense + 4 * cut];
     if (!slot) {
         BpXPlanPtr xp;
-        if (bp_xplan_build(ctx, m, t, direct, dense, cut, &xp) != FGPU_OK) {
+        const XpSource src = {t->rowptr, t->colidx, t->nrows, t->ncols, t->nnz};
+        if (bp_xplan_build(ctx, m, &src, direct, dense, cut, nullptr, &xp) != FGPU_OK) {
             xp.reset(new (std::nothrow) BpXPlan());
             FGPU_REQUIRE(xp, FGPU_OOM, "out of host memory");
+            (void)hipGetLastError();
+            set_error("%s", "");
+        } else if (bp_xplan_hub_build(ctx, m, t, direct, dense, cut, xp.get()) != FGPU_OK) {
+            // (the reduced plan is an accelerator of the accelerator: the full plan stays usable, and there is no second attempt)
+            xp->hub.reset();
+            (void)hipStreamSynchronize(ctx->stream());
             (void)hipGetLastError();
             set_error("%s", "");
         }
@@ -1219,10 +1378,14 @@ fgpu_info bp_xpull_count(fgpu_ctx* ctx, const BpXPlan* xp, const fgpu_mat* t, co
     FGPU_REQUIRE(xp && xp->usable && ws >= 2 && ws <= 16 && (ws & (ws - 1)) == 0, FGPU_INVALID, "partitioned pull: bad plan / row width");
     FGPU_REQUIRE(mode == 1 || mode == 2, FGPU_INVALID, "partitioned pull: counting hops only");
     FGPU_REQUIRE(!xp->dense == !xp->gvtx.p, FGPU_INVALID, "partitioned pull: the plan's form and its slots disagree");
-    ctx->xp_last_direct.store(xp->ndirect, std::memory_order_relaxed);
-    ctx->xp_last_groups.store(xp->ng, std::memory_order_relaxed);
-    ctx->xp_last_chunks.store(xp->nchunks, std::memory_order_relaxed);
-    ctx->xp_last_shared_rows.store(xp->nzrows - 1, std::memory_order_relaxed);   // (without the spare zero row)
+    // the read-only counters describe the hop's plan over ALL of A', also when the hop runs under the reduced plan beside it: which
+    // pass of a whole-frontier call ends last is up to its lanes, and the counters of a snapshot must not depend on it (the
+    // profiler scope xp_hub_rows says which hops took the short cut)
+    const BpXPlan* rep = xp->full ? xp->full : xp;
+    ctx->xp_last_direct.store(rep->ndirect, std::memory_order_relaxed);
+    ctx->xp_last_groups.store(rep->ng, std::memory_order_relaxed);
+    ctx->xp_last_chunks.store(rep->nchunks, std::memory_order_relaxed);
+    ctx->xp_last_shared_rows.store(rep->nzrows - 1, std::memory_order_relaxed);   // (without the spare zero row)
     DevBuf<uint4> partial;
     FGPU_TRY(partial.alloc(ctx, ((size_t)xp->nprows + 1) * (ws / 2)));
     FGPU_TRY(xp_zero_rows(ctx, xp, ws / 2, partial.p));
