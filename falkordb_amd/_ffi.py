@@ -18,6 +18,7 @@ FGPU_NULL_POINTER = -2
 FGPU_INVALID = -3
 FGPU_DIM_MISMATCH = -6
 FGPU_OOM = -102
+FGPU_INSUFFICIENT_SPACE = -103
 FGPU_OUT_OF_BOUNDS = -105
 FGPU_DEVICE = -7002
 
@@ -95,6 +96,9 @@ SIGNATURES = {
     "fgpu_expand_edges": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, u64p, u64p,
                                       C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u8p), u64p,
                                       u64p]),
+    "fgpu_expand_trails": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, C.c_uint32,
+                                       C.c_uint32, u64p, C.c_uint64, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p),
+                                       C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u32p), C.POINTER(u64p), u64p, u64p]),
     "fgpu_expand_levels": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fgpu_expand_trail_counts": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, C.c_int, C.POINTER(u64p),
                                              C.POINTER(u64p), C.POINTER(u64p), u64p]),

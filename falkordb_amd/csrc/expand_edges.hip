@@ -16,27 +16,10 @@
 //             over O and reads the inline id, or its id of the table row
 //
 // The only atomics are counters that place nothing.  No wavefront per row: a hub row is as many lanes as it has entries.
-#include "bulk.hpp"
-
-struct fgpu_multi {
-    fgpu_ctx* ctx = nullptr;
-    uint64_t n = 0, total = 0;
-    fgpu::DevBuf<uint64_t> key, ids;
-    fgpu::DevBuf<uint32_t> off;
-};
+#include "edge_layers.hpp"
 
 namespace fgpu {
 
-constexpr u64 EE_MAX_ROWS = 1ull << 24;
-constexpr int EE_MAX_TYPES = 64;
-
-struct EeType {   // one relationship type; an absent or empty layer is a view of no rows
-    CsrView m, dp, dm, tm, tdp, tdm;
-    const u64 *mval, *dpval;
-    const u64 *mkey, *mids;
-    const u32* moff;
-    u32 n_multi;
-};
 struct EeBatch {
     const u32 *from, *to;      // k each, ~0u = unbound
     const EeType* ty;          // T
@@ -61,24 +44,6 @@ __device__ __forceinline__ EeWalk ee_walk(const EeBatch& b, u32 s) {
     w.mdst = w.rev ? f : t;
     return w;
 }
-// Tensor::eff_get (tensor.rs:286-299): dp's value wins, a dm entry hides m's
-__device__ __forceinline__ bool ee_value(const EeType& y, u32 s, u32 d, u64& v) {
-    u32 q = probe(y.dp, s, d);
-    if (q != ~0u) { v = y.dpval[q]; return true; }
-    if (probe(y.dm, s, d) != ~0u) return false;
-    q = probe(y.m, s, d);
-    if (q == ~0u) return false;
-    v = y.mval[q];
-    return true;
-}
-__device__ __forceinline__ bool ee_bit(const u64* __restrict__ bm, u32 v) { return (bm[v >> 6] >> (v & 63)) & 1ull; }
-// *total += the sum of x over the wavefront (every lane calls it)
-__device__ __forceinline__ void ee_add(u64 x, u64* __restrict__ total) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, WAVE);
-    if (lane_id() == 0 && x) atomicAdd((unsigned long long*)total, (unsigned long long)x);
-}
-
 // seg_b[s] = first position of the run, seg_len[s] = its length (seg_len[nseg] = 0, so that the scan ends in the total)
 __global__ __launch_bounds__(256) void ee_segment_kernel(EeBatch b, u32 nseg, u32* __restrict__ seg_b, u32* __restrict__ seg_len,
                                                         u64* __restrict__ total) {
@@ -235,14 +200,6 @@ __global__ __launch_bounds__(256) void ee_fill_kernel(EeBatch b, const u32* __re
     out_id[o] = (tyw & 0x80000000u) ? b.ty[tyw & 63u].mids[(u32)v + (o - off[j])] : v;
 }
 
-static CsrView ee_view(const fgpu_mat* a) {
-    if (a && a->nnz) return view_of(a);
-    CsrView none;
-    none.rowptr = nullptr; none.colidx = nullptr; none.hrows = nullptr; none.nvec = 0; none.nrows = 0;
-    return none;
-}
-static const fgpu_mat* ee_at(const fgpu_mat* const* a, int t) { return a ? a[t] : nullptr; }
-
 static fgpu_info expand_edges_impl(fgpu_ctx* ctx, const u64* from, const u64* to, u64 k, const fgpu_mat* const* m,
                                    const fgpu_mat* const* dp, const fgpu_mat* const* dm, const fgpu_mat* const* mt_m,
                                    const fgpu_mat* const* mt_dp, const fgpu_mat* const* mt_dm, const fgpu_multi* const* multi,
@@ -263,33 +220,10 @@ static fgpu_info expand_edges_impl(fgpu_ctx* ctx, const u64* from, const u64* to
     FGPU_REQUIRE((flags & ~7) == 0, FGPU_INVALID, "%s: unknown flag bits in %d", fn, flags);
     if (k == 0 || n_types == 0) return FGPU_OK;
     // ---- the layers ------------------------------------------------------------------------------------------------------
-    FGPU_REQUIRE(m[0], FGPU_NULL_POINTER, "%s: m[0] is NULL", fn);
-    const u64 n = m[0]->nrows;
-    FGPU_REQUIRE(n < 0xFFFFFFFFull, FGPU_INVALID, "%s: dimension %llu is past the 32-bit id space", fn, (unsigned long long)n);
+    u64 n = 0;
     bool any_dp = false;
-    std::vector<EeType> hty((size_t)n_types);
-    for (int t = 0; t < n_types; ++t) {
-        FGPU_REQUIRE(m[t], FGPU_NULL_POINTER, "%s: m[%d] is NULL", fn, t);
-        const fgpu_mat* layer[6] = {m[t], ee_at(dp, t), ee_at(dm, t), ee_at(mt_m, t), ee_at(mt_dp, t), ee_at(mt_dm, t)};
-        static const char* const names[6] = {"m", "dp", "dm", "mt_m", "mt_dp", "mt_dm"};
-        for (int l = 0; l < 6; ++l)
-            FGPU_REQUIRE(!layer[l] || (layer[l]->nrows == n && layer[l]->ncols == n), FGPU_INVALID,
-                         "%s: %s[%d] is %llu x %llu, not %llu x %llu", fn, names[l], t, (unsigned long long)layer[l]->nrows,
-                         (unsigned long long)layer[l]->ncols, (unsigned long long)n, (unsigned long long)n);
-        FGPU_REQUIRE(m[t]->vals || !m[t]->nnz, FGPU_INVALID, "%s: m[%d] must be the tensor's UINT64 base (got a BOOL matrix)", fn, t);
-        FGPU_REQUIRE(!layer[1] || !layer[1]->nnz || layer[1]->vals, FGPU_INVALID, "%s: dp[%d] must be UINT64 (got a BOOL matrix)", fn, t);
-        EeType& y = hty[t];
-        y.m = ee_view(layer[0]); y.dp = ee_view(layer[1]); y.dm = ee_view(layer[2]);
-        y.tm = ee_view(layer[3]); y.tdp = ee_view(layer[4]); y.tdm = ee_view(layer[5]);
-        y.mval = m[t]->vals;
-        y.dpval = layer[1] ? layer[1]->vals : nullptr;
-        const fgpu_multi* mu = multi ? multi[t] : nullptr;
-        y.mkey = mu ? mu->key.p : nullptr;
-        y.mids = mu ? mu->ids.p : nullptr;
-        y.moff = mu ? mu->off.p : nullptr;
-        y.n_multi = mu ? (u32)mu->n : 0u;
-        any_dp = any_dp || y.dp.rowptr || y.tdp.rowptr;
-    }
+    std::vector<EeType> hty;
+    FGPU_TRY(ee_types(fn, m, dp, dm, mt_m, mt_dp, mt_dm, multi, n_types, hty, n, any_dp));
     // ---- the rows --------------------------------------------------------------------------------------------------------
     const bool transposed = flags & FGPU_EDGES_TRANSPOSED, bidir = flags & FGPU_EDGES_BIDIRECTIONAL;
     std::vector<u32> f32(k), t32(k);

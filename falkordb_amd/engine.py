@@ -254,6 +254,43 @@ class Context:
             cols.append(self._take(ppass, n.value, np.uint8))
         return (*cols, [int(x) for x in st])
 
+    # ---- variable-length traversal (expand_trails.hip) ----
+    def expand_trails(self, starts, dests, m, dp=None, dm=None, mt_m=None, mt_dp=None, mt_dm=None, multi=None, reversed=False,
+                      bidirectional=False, paths=False, min_hops=1, max_hops=None, dst_label_bitmap=None, max_items=1 << 22,
+                      stats_out=None):
+        """fgpu_expand_trails: CondVarLenTraverse for a whole batch.  starts: node ids; dests: None, or per row a node id or
+        None (unbound); m .. multi as for expand_edges; max_hops None = unbounded.  Returns (row, from, to, hops[, path_off,
+        path_node, path_edge], stats): numpy views of the engine's result blocks, stats the eight of fgpu.h.  stats_out (a
+        list) receives the eight whatever the call returns: FGPU_INSUFFICIENT_SPACE raises with the counts so far in it."""
+        s = _u64(starts).reshape(-1)
+        d = None
+        if dests is not None:
+            d = np.asarray([(1 << 64) - 1 if v is None else int(v) for v in dests], dtype=U64)
+            assert len(d) == len(s)
+        T = len(m)
+        arrs = [_hop_arrays(x) if x is not None else None for x in (m, dp, dm, mt_m, mt_dp, mt_dm, multi)]
+        assert all(a is None or len(a) == T for a in arrs)
+        bm = _u64(dst_label_bitmap) if dst_label_bitmap is not None else None
+        prow, pfrom, pto, phops, pnode = _ffi.u32p(), _ffi.u32p(), _ffi.u32p(), _ffi.u32p(), _ffi.u32p()
+        poff, pedge = u64p(), u64p()
+        n = C.c_uint64()
+        st = (C.c_uint64 * 8)()
+        flags = (1 if reversed else 0) | (2 if bidirectional else 0) | (4 if paths else 0)
+        code = self.lib.fgpu_expand_trails(self._h, _p(s), _p(d), len(s), *arrs, T, flags, min_hops,
+                                           0xFFFFFFFF if max_hops is None else max_hops, _p(bm), max_items, C.byref(prow),
+                                           C.byref(pfrom), C.byref(pto), C.byref(phops), C.byref(poff) if paths else None,
+                                           C.byref(pnode) if paths else None, C.byref(pedge) if paths else None, C.byref(n), st)
+        if stats_out is not None:
+            stats_out[:] = [int(x) for x in st]
+        check(code)
+        cols = [self._take(prow, n.value, np.uint32), self._take(pfrom, n.value, np.uint32),
+                self._take(pto, n.value, np.uint32), self._take(phops, n.value, np.uint32)]
+        if paths:
+            off = self._take(poff, n.value + 1 if n.value else 0, U64)
+            total = int(off[-1]) if n.value else 0
+            cols += [off, self._take(pnode, total + n.value, np.uint32), self._take(pedge, max(total, 1) if n.value else 0, U64)[:total]]
+        return (*cols, [int(x) for x in st])
+
 
 class Mat:
     """fgpu_mat: immutable device snapshot of one matrix layer."""

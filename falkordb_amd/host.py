@@ -641,6 +641,36 @@ class Graph:
         rows = [(f[i], t[i], p[offs[i]:offs[i + 1]] if emit_path else None) for i in range(k)]
         return rows, {"frames": int(st[0]), "pruned": int(st[1]), "reach_products": int(st[2])}
 
+    def var_len_traverse_batch(self, starts, dests=None, types=(), min_hops=1, max_hops=None, reversed=False, bidirectional=False,
+                               dst_labels=(), emit_path=False, prune=True, device_budget=None, as_arrays=False):
+        """CondVarLenTraverse over an input batch on the device (fh_var_len_traverse_batch, fgpu_expand_trails underneath):
+        [(row, from, to, path | None)] — row i's part is what var_len_traverse(starts[i], dest=dests[i]) gives — plus {frames,
+        pruned, reach_products, device_calls}.  dests: None, or per row a node id or None.  device_budget: frames + emissions
+        one device call may hold (None = the operator's default); a batch past it is bisected.  as_arrays: the columns (row,
+        from, to, path, path_off) as numpy arrays instead of the row tuples."""
+        s = _u64(starts)
+        d = None if dests is None else np.asarray([-1 if v is None else int(v) for v in dests], dtype=np.int64)
+        orow, of, ot, op_, off = u64p(), u64p(), u64p(), u64p(), u64p()
+        n, calls = C.c_uint64(), C.c_uint64()
+        st = (C.c_uint64 * 3)()
+        _ck(self.L.fh_var_len_traverse_batch(self.h, ",".join(types).encode(), ",".join(dst_labels).encode(),
+                                             1 if reversed else 0, 1 if bidirectional else 0, C.c_uint32(min_hops),
+                                             C.c_uint32(0xFFFFFFFF if max_hops is None else max_hops), _p(s),
+                                             d.ctypes.data_as(i64p) if d is not None else None, C.c_uint64(len(s)),
+                                             1 if emit_path else 0, 1 if prune else 0, C.c_uint64(device_budget or 0),
+                                             C.byref(orow), C.byref(of), C.byref(ot), C.byref(op_), C.byref(off), C.byref(n), st,
+                                             C.byref(calls)))
+        k = n.value
+        stats = {"frames": int(st[0]), "pruned": int(st[1]), "reach_products": int(st[2]), "device_calls": int(calls.value)}
+        if as_arrays:
+            offs = _take(off, k + 1)
+            return (_take(orow, k), _take(of, k), _take(ot, k), _take(op_, int(offs[-1])), offs), stats
+        offs = _take(off, k + 1).tolist()
+        r, f, t = _take(orow, k).tolist(), _take(of, k).tolist(), _take(ot, k).tolist()
+        p = _take(op_, offs[-1]).tolist()
+        rows = [(r[i], f[i], t[i], p[offs[i]:offs[i + 1]] if emit_path else None) for i in range(k)]
+        return rows, stats
+
     def all_shortest_paths(self, src, dst, types=(), bidirectional=False, reversed=False, max_hops=None, limit=0):
         """AllShortestPathsOp over one input row (all_shortest_paths.rs:82-303): (length, [[relationship id, ...], ...]) — the
         shortest paths of allShortestPaths((src)-[:types*..max_hops]->(dst)) in the reference's emission order, src / dst the

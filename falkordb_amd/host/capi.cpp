@@ -716,6 +716,52 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
     });
 }
 
+int fh_var_len_traverse_batch(fh_graph* g, const char* types, const char* dst_labels, int reversed, int bidirectional,
+                              uint32_t min_hops, uint32_t max_hops, const uint64_t* starts, const int64_t* dests, uint64_t k,
+                              int emit_path, int prune, uint64_t device_budget, uint64_t** out_row, uint64_t** out_from,
+                              uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n, uint64_t stats[3],
+                              uint64_t* device_calls) {
+    return guard([&] {
+        CondVarLenTraverseOp op;
+        op.types = csv(types);
+        op.dst_labels = csv(dst_labels);
+        op.reversed = reversed != 0;
+        op.bidirectional = bidirectional != 0;
+        op.min_hops = min_hops;
+        op.max_hops = max_hops;
+        op.emit_path = emit_path != 0;
+        op.prune = prune != 0;
+        if (device_budget) op.device_budget = device_budget;
+        std::vector<std::optional<u64>> d;
+        if (dests)
+            for (u64 i = 0; i < k; ++i) d.push_back(dests[i] >= 0 ? std::optional<u64>((u64)dests[i]) : std::nullopt);
+        std::vector<u64> rows_of;
+        std::vector<VarLenRow> rows;
+        VarLenStats st;
+        u64 calls = 0;
+        timed([&] { op.expand_batch(g->g, std::vector<u64>(starts, starts + k), d, rows_of, rows, &st, &calls); return 0; });
+        std::vector<u64> f, t, p, off{0};
+        f.reserve(rows.size());
+        t.reserve(rows.size());
+        off.reserve(rows.size() + 1);
+        for (auto& r : rows) {
+            f.push_back(r.from);
+            t.push_back(r.to);
+            p.insert(p.end(), r.path.begin(), r.path.end());
+            off.push_back(p.size());
+        }
+        *out_row = hand(rows_of);
+        *out_from = hand(f);
+        *out_to = hand(t);
+        *path = hand(p);
+        *path_off = hand(off);
+        *n = rows.size();
+        if (stats) { stats[0] = st.frames; stats[1] = st.pruned; stats[2] = st.reach_products; }
+        if (device_calls) *device_calls = calls;
+        return 0;
+    });
+}
+
 // AllShortestPathsOp over one input row: the paths flattened as relationship ids plus n_paths + 1 offsets
 int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops, uint64_t src,
                           uint64_t dst, uint64_t limit, int64_t* length, uint64_t** edges, uint64_t** path_off, uint64_t* n_paths) {

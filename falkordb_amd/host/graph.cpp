@@ -910,6 +910,146 @@ void CondVarLenTraverseOp::expand_row(const Graph& g, u64 start, std::optional<u
     }
 }
 
+void CondVarLenTraverseOp::expand_batch(const Graph& g, const std::vector<u64>& starts, const std::vector<std::optional<u64>>& dests,
+                                        std::vector<u64>& out_row, std::vector<VarLenRow>& out, VarLenStats* stats,
+                                        u64* device_calls) const {
+    out_row.clear();
+    out.clear();
+    VarLenStats local;
+    VarLenStats& st = stats ? *stats : local;
+    if (device_calls) *device_calls = 0;
+    const u64 k = starts.size();
+    if (!dests.empty() && dests.size() != k) throw GrbError(FGPU_INVALID, "CondVarLenTraverse::expand_batch: starts and dests differ in length");
+    // types and labels as expand_row resolves them
+    std::vector<u64> tids;
+    if (types.empty())
+        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+    else
+        for (auto& t : types)
+            if (auto id = g.type_id(t)) tids.push_back(*id);
+    std::vector<LabelId> dl;
+    for (auto& l : dst_labels) {
+        if (auto id = g.label_id(l)) dl.push_back(*id);
+        else return;                                                     // an unknown label suppresses every emission (:100-107)
+    }
+    std::vector<u64> bitmap;
+    if (!dl.empty()) bitmap = g.label_bitmap(dl);
+    auto dest_of = [&](u64 i) { return dests.empty() ? std::optional<u64>() : dests[i]; };
+
+    // the rows the device takes, and the layers of every walked tensor as they lie there (as expand_batch_edges gathers them)
+    const u64 cap = g.node_cap();
+    auto sendable = [&](u64 v) { return v < cap && !g.is_node_deleted(v); };
+    std::vector<u64> idx, ds, dd;
+    for (u64 i = 0; i < k; ++i) {
+        const auto d = dest_of(i);
+        if (!sendable(starts[i]) || (d && !sendable(*d))) continue;
+        idx.push_back(i);
+        ds.push_back(starts[i]);
+        dd.push_back(d ? *d : ~0ull);
+    }
+    const size_t T = tids.size();
+    std::vector<const fgpu_mat*> m(T), dp(T), dm(T), tm(T), tdp(T), tdm(T);
+    std::vector<const fgpu_multi*> multi(T);
+    for (size_t x = 0; x < T && !idx.empty(); ++x) {
+        const Tensor& ten = g.relationship_tensors()[tids[x]];
+        ten.wait();
+        const VersionedMatrix& mt = ten.matrix_t();
+        m[x] = ten.fwd_m().snapshot();
+        dp[x] = ten.fwd_dp().nvals() ? ten.fwd_dp().snapshot() : nullptr;
+        dm[x] = ten.fwd_dm().nvals() ? ten.fwd_dm().snapshot() : nullptr;
+        tm[x] = mt.m().snapshot();
+        tdp[x] = mt.dp().nvals() ? mt.dp().snapshot() : nullptr;
+        tdm[x] = mt.dm().nvals() ? mt.dm().snapshot() : nullptr;
+        multi[x] = ten.multi_table();
+    }
+    fgpu_ctx* ctx = g.ctx().raw();
+    const int flags = (reversed ? FGPU_TRAILS_REVERSED : 0) | (bidirectional ? FGPU_TRAILS_BIDIRECTIONAL : 0) |
+                      (emit_path ? FGPU_TRAILS_PATHS : 0);
+
+    // the device's answers, in the order of idx: one chunk per call that fitted, or per single row the host walked instead
+    struct Chunk {
+        size_t lo, hi;
+        EngineBuf<uint32_t> row, from, to, hops, pnode;
+        EngineBuf<u64> poff, pedge;
+        u64 n = 0;
+        std::vector<VarLenRow> host_rows;
+        bool host = false;
+    };
+    std::vector<Chunk> chunks;
+    std::vector<std::pair<size_t, size_t>> todo{{0, idx.size()}};        // a stack: the left half is answered first
+    while (!todo.empty()) {
+        const auto [lo, hi] = todo.back();
+        todo.pop_back();
+        if (lo == hi) continue;
+        Chunk c;
+        c.lo = lo; c.hi = hi;
+        c.row = EngineBuf<uint32_t>(ctx); c.from = EngineBuf<uint32_t>(ctx); c.to = EngineBuf<uint32_t>(ctx);
+        c.hops = EngineBuf<uint32_t>(ctx); c.pnode = EngineBuf<uint32_t>(ctx);
+        c.poff = EngineBuf<u64>(ctx); c.pedge = EngineBuf<u64>(ctx);
+        u64 dstats[8] = {0};
+        if (device_calls) ++*device_calls;
+        const fgpu_info info = fgpu_expand_trails(
+            ctx, ds.data() + lo, dests.empty() ? nullptr : dd.data() + lo, hi - lo, m.data(), dp.data(), dm.data(), tm.data(), tdp.data(),
+            tdm.data(), multi.data(), (int)T, flags, min_hops, max_hops, bitmap.empty() ? nullptr : bitmap.data(), device_budget,
+            c.row.out(), c.from.out(), c.to.out(), c.hops.out(), emit_path ? c.poff.out() : nullptr, emit_path ? c.pnode.out() : nullptr,
+            emit_path ? c.pedge.out() : nullptr, &c.n, dstats);
+        if (info == FGPU_INSUFFICIENT_SPACE) {
+            if (hi - lo == 1) {
+                c.host = true;
+                expand_row(g, ds[lo], dest_of(idx[lo]), c.host_rows, &st);
+                chunks.push_back(std::move(c));
+            } else {
+                const size_t mid = lo + (hi - lo) / 2;
+                todo.push_back({mid, hi});
+                todo.push_back({lo, mid});
+            }
+            continue;
+        }
+        check(info, "CondVarLenTraverse::expand_batch");
+        st.frames += dstats[0];
+        chunks.push_back(std::move(c));
+    }
+
+    // the rows in input order, the host's spliced in at their place
+    u64 next = 0, total = 0;                                             // the first input row not yet written
+    for (const Chunk& c : chunks) total += c.host ? c.host_rows.size() : c.n;
+    out.reserve(total);
+    out_row.reserve(total);
+    auto host_rows_below = [&](u64 bound) {
+        for (; next < bound; ++next) {
+            const size_t before = out.size();                            // (a row between two device rows is the host's)
+            expand_row(g, starts[next], dest_of(next), out, &st);
+            out_row.insert(out_row.end(), out.size() - before, next);
+        }
+    };
+    for (Chunk& c : chunks) {
+        u64 q = 0;
+        for (size_t x = c.lo; x < c.hi; ++x) {
+            host_rows_below(idx[x]);
+            next = idx[x] + 1;
+            if (c.host) {
+                out_row.insert(out_row.end(), c.host_rows.size(), idx[x]);
+                for (auto& r : c.host_rows) out.push_back(std::move(r));
+                continue;
+            }
+            for (; q < c.n && c.row[q] == x - c.lo; ++q) {
+                VarLenRow r;
+                r.from = c.from[q];
+                r.to = c.to[q];
+                if (emit_path) {
+                    const u64 b = c.poff[q], h = c.poff[q + 1] - b;
+                    r.path.reserve(2 * h + 1);
+                    for (u64 j = 0; j < h; ++j) { r.path.push_back(c.pnode[b + q + j]); r.path.push_back(c.pedge[b + j]); }
+                    r.path.push_back(c.pnode[b + q + h]);
+                }
+                out_row.push_back(idx[x]);
+                out.push_back(std::move(r));
+            }
+        }
+    }
+    host_rows_below(k);
+}
+
 // ---- ExpandInto ---------------------------------------------------------------------------------------
 static std::vector<u64> resolve_types(const Graph& g, const std::vector<std::string>& types) {
     std::vector<u64> tids;

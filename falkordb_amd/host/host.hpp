@@ -753,6 +753,22 @@ struct CondVarLenTraverseOp {
     // one input row: DFS from `start`; `dest` = the other endpoint when it is bound too
     void expand_row(const Graph& g, u64 start, std::optional<u64> dest, std::vector<VarLenRow>& out,
                     VarLenStats* stats = nullptr) const;
+
+    // expand_row for a whole input batch on the device (fgpu_expand_trails): out holds, rows ascending, exactly what
+    // expand_row(g, starts[i], dests[i]) gives for every i, and out_row[j] the input row of out[j].  dests: empty = none bound.
+    // Types and destination labels are resolved as expand_row resolves them: unknown types are dropped (with none resolvable the
+    // call still runs, for the 0-hop rows), an unknown destination label gives no rows and no device call; the label set goes
+    // along as a bitmap.  A row whose start or dest is at or past node_cap(), or deleted, runs through expand_row and is spliced
+    // in at its place.  The device holds at most device_budget frames + emissions per call: on FGPU_INSUFFICIENT_SPACE the batch
+    // is split in two and each half retried; a single row that does not fit runs expand_row, with `prune` as set.  The device does
+    // not prune for a bound destination (the reach sets stay expand_row's): it filters emissions, so a batch of bound rows over
+    // long hop ranges pays for every frame — raise device_budget, or leave such rows to expand_row.
+    // stats (nullable): frames = the frames of the device calls that answered plus the fallback rows' own; pruned and
+    // reach_products count only the fallback rows.  device_calls (nullable): fgpu_expand_trails calls made, refused ones included.
+    u64 device_budget = 1ull << 22;
+    void expand_batch(const Graph& g, const std::vector<u64>& starts, const std::vector<std::optional<u64>>& dests,
+                      std::vector<u64>& out_row, std::vector<VarLenRow>& out, VarLenStats* stats = nullptr,
+                      u64* device_calls = nullptr) const;
 };
 
 // AllShortestPathsOp (runtime/ops/all_shortest_paths.rs:82-303): MATCH p = allShortestPaths((a)-[:types*..max]->(b)) with both

@@ -245,6 +245,19 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
                         uint32_t min_hops, uint32_t max_hops, uint64_t start, int64_t dest, int emit_path, int prune,
                         uint64_t** out_from, uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n,
                         uint64_t stats[3]);
+/* The same operator over an input batch of k rows on the device (CondVarLenTraverseOp::expand_batch over fgpu_expand_trails):
+ * row i of the result is exactly what fh_var_len_traverse gives for (starts[i], dests[i]), rows ascending, out_row the input row
+ * of every emission.  dests: nullable (none bound), else per row a node id or < 0.  A row whose start or dest is at or past the
+ * node capacity, or deleted, runs on the host and is spliced in at its place; an unknown destination label gives no rows and no
+ * device call.  device_budget: the frames + emissions one device call may hold (0 = the operator's default, 2^22): a batch that
+ * does not fit is split in two, a single row that does not fit runs on the host, with `prune` as set.  The device does not prune.
+ * stats (nullable): frames (device calls that answered + host rows), pruned and reach products (host rows only).  device_calls
+ * (nullable): fgpu_expand_trails calls made, refused ones included. */
+int fh_var_len_traverse_batch(fh_graph* g, const char* types, const char* dst_labels, int reversed, int bidirectional,
+                              uint32_t min_hops, uint32_t max_hops, const uint64_t* starts, const int64_t* dests, uint64_t k,
+                              int emit_path, int prune, uint64_t device_budget, uint64_t** out_row, uint64_t** out_from,
+                              uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n, uint64_t stats[3],
+                              uint64_t* device_calls);
 /* AllShortestPathsOp, one input row (all_shortest_paths.rs:82-303): every shortest path of
  * allShortestPaths((src)-[:types*..max_hops]->(dst)), src / dst = the pattern's from / to node, as relationship-id lists in the
  * reference's emission sequence and per-path edge order.  types: a comma list ("" = all); bidirectional: the pattern has no

@@ -59,6 +59,7 @@ typedef int32_t fgpu_info;
 #define FGPU_INVALID (-3)          /* GrB_INVALID_VALUE          */
 #define FGPU_DIM_MISMATCH (-6)     /* GrB_DIMENSION_MISMATCH     */
 #define FGPU_OOM (-102)            /* GrB_OUT_OF_MEMORY          */
+#define FGPU_INSUFFICIENT_SPACE (-103) /* GrB_INSUFFICIENT_SPACE  */
 #define FGPU_OUT_OF_BOUNDS (-105)  /* GrB_INDEX_OUT_OF_BOUNDS    */
 #define FGPU_DEVICE (-7002)        /* GxB_GPU_ERROR              */
 
@@ -554,6 +555,60 @@ fgpu_info fgpu_expand_edges(fgpu_ctx* ctx, const uint64_t* from, const uint64_t*
                             int n_types, int flags, const uint64_t* from_bitmap, const uint64_t* to_bitmap, uint32_t** out_row,
                             uint32_t** out_from, uint32_t** out_to, uint64_t** out_id, uint8_t** out_pass, uint64_t* out_n,
                             uint64_t stats[8]);
+
+/* CondVarLenTraverse, the [*min..max] operator (cond_var_len_traverse.rs:81-387, VarLenIter), for a whole batch of k rows in one
+ * call, without the attribute / WHERE filters.  start [k]: the bound endpoint of every row; dest (nullable array): a node id the
+ * other endpoint must equal, or ~0 for unbound.  m .. multi, n_types: the relationship tensors in the pattern's order, as for
+ * fgpu_expand_edges.  dst_label_bitmap: nullable (n + 63) / 64-word node set the emitted endpoint must lie in.
+ *   Direction   no flag: the walk follows outgoing edges; FGPU_TRAILS_REVERSED: incoming edges; FGPU_TRAILS_BIDIRECTIONAL: both.
+ *               The two together are FGPU_INVALID (the reference never builds that combination, :534).
+ *   Adjacency   of a node v (get_node_relationships_by_type, graph.rs:1797-1835): the types in the given order — a type listed
+ *               twice is walked twice — and per type first the outgoing half, by ascending (dst, id) over the effective structure
+ *               (m \ dm) U dp, the ids those of Tensor::get (dp's value wins, FGPU_MULTI_EDGE expands to the table row, ascending),
+ *               then, when incoming edges are walked, the incoming half by ascending (src, id) over the transposed layers, the
+ *               self-loop left out of it only when the outgoing half was walked too.  This is type-major, not the pair-major order
+ *               of fgpu_expand_edges.
+ *   Trails      a frame is (node, used edge ids, depth); the root is (start, {}, 0).  A candidate whose edge id is already on
+ *               the frame's trail is dropped — by id only, across types and directions (:247).  A child at hop = depth + 1 emits
+ *               when hop >= min_hops, its node equals the row's dest if one is bound, and its node passes the bitmap; it goes on
+ *               as a frame when hop < max_hops (UINT32_MAX = unbounded).  The 0-hop row (start, start) comes first when
+ *               min_hops == 0 and the start passes the dest and bitmap tests, with n_types == 0 too.
+ *   Order       rows ascending; within a row exactly the reference's: frames are visited in DFS preorder with the children
+ *               visited last-first (the LIFO stack), and a visited frame contributes its emitting children in adjacency order,
+ *               all before any deeper frame does (:379-383).  Duplicate rows of the batch each get their own output.
+ *   Out         out_row / out_from / out_to / out_hops (uint32_t), *out_n entries: (from, to) oriented to the pattern — (start,
+ *               other), or (other, start) under REVERSED; out_hops the trail's length.  With FGPU_TRAILS_PATHS emission i has
+ *               out_path_off[i + 1] - out_path_off[i] edges at out_path_edge[out_path_off[i] ..] and one more node at
+ *               out_path_node[out_path_off[i] + i ..], both in pattern order, that is reversed under REVERSED (path_value,
+ *               :134-147); without the flag the three path pointers must be NULL.  Engine-owned blocks (pinned from 256 KiB up,
+ *               filled by DMA), released with fgpu_free; all NULL when *out_n == 0.  The call keeps no device memory.
+ *   Budget      trails grow exponentially, so the caller sets max_items: the frames (the k roots included) plus the emissions the
+ *               call may hold.  Past it the call returns FGPU_INSUFFICIENT_SPACE with nothing allocated for output and stats
+ *               holding what was counted up to that point; exactly at the budget is FGPU_OK.  The same code when a trail would go
+ *               on as a frame deeper than FGPU_TRAILS_MAX_DEPTH edges (frames at that depth are still expanded, so max_hops up to
+ *               FGPU_TRAILS_MAX_DEPTH + 1 always fits, and an unbounded pattern fits when no trail outgrows the depth), or when
+ *               one level walks 2^32 - 1 entries or more.  The level's counts are read back before its buffers are allocated.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated and the context still usable, for: a start or bound dest at or past
+ * n; non-square or mismatched layers; an unvalued m (or dp); a missing mt_m when incoming entries are walked; k above 2^24, n_types
+ * above 64, unknown flag bits or REVERSED with BIDIRECTIONAL; path pointers without PATHS; a walked pair that holds
+ * FGPU_MULTI_EDGE without a table row; max_items == 0 or at or past 2^32 - 1.
+ * stats (nullable): [0] frames expanded, [1] adjacency entries walked, [2] candidates dropped as already used, [3] emissions,
+ * [4] levels run, [5] how the level step orders a node's entries: 0 = the entry positions are the adjacency order (no dp layer in
+ * any type), 1 = the m and dp runs of every (frame, type, half) are merged by rank (a binary search per entry; no sort is needed
+ * for two sorted runs), [6] multi-edge pairs expanded, [7] peak items held (frames + emissions).
+ * Work: level-synchronous — a lane per (frame, type, half, layer) segment, a lane per walked entry, a lane per candidate id, every
+ * frame and emission placed by a scan; the order is two scans per level more. */
+#define FGPU_TRAILS_REVERSED 1
+#define FGPU_TRAILS_BIDIRECTIONAL 2
+#define FGPU_TRAILS_PATHS 4
+#define FGPU_TRAILS_MAX_DEPTH 64
+fgpu_info fgpu_expand_trails(fgpu_ctx* ctx, const uint64_t* start, const uint64_t* dest, uint64_t k, const fgpu_mat* const* m,
+                             const fgpu_mat* const* dp, const fgpu_mat* const* dm, const fgpu_mat* const* mt_m,
+                             const fgpu_mat* const* mt_dp, const fgpu_mat* const* mt_dm, const fgpu_multi* const* multi,
+                             int n_types, int flags, uint32_t min_hops, uint32_t max_hops, const uint64_t* dst_label_bitmap,
+                             uint64_t max_items, uint32_t** out_row, uint32_t** out_from, uint32_t** out_to, uint32_t** out_hops,
+                             uint64_t** out_path_off, uint32_t** out_path_node, uint64_t** out_path_edge, uint64_t* out_n,
+                             uint64_t stats[8]);
 
 /* The same chain with the result STREAMED to the host in chunks of whole source rows — the shape in which
  * CondTraverseOp::expand_batch consumes it (cond_traverse.rs:644-751: walk (row_i, dest) ascending, emit an output batch

@@ -103,7 +103,13 @@
           Then the bare fgpu_expand_edges beside fgpu_expand_pairs32 on the same sources and the same tensor (fgpu_edges_build
           on the engine context), with its device phases.  `edges <scale>`: that scale only.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|edges|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  varlen_batch   CondVarLenTraverse batches: (a:P)-[*1..2]->(b), (a:P)-[*1..3]->(b) and (a:P)-[*1..2]-(b) over 1024 :P rows of one
+          RMAT-18 graph through Graph.var_len_traverse_batch (fgpu_expand_trails) against the loop of the per-row DFS over the same
+          rows (stopped at a 10 s deadline and extrapolated), the rows compared inside the run; then the bare call with and
+          without paths.  A pattern one device call cannot hold over all rows is timed on the lightest rows: the longest halved prefix,
+          by out-degree, that fits.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|edges|varlen_batch|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -710,6 +716,123 @@ def bench_edges(scales=(18, 20), deadline_s=10.0, k=1024):
                        "read-back of the columns included")
         print(json.dumps(out), flush=True)
         del g, fwd, bwd, multi
+
+
+def bench_varlen(scale=18, deadline_s=10.0, k=1024, fit_items=1 << 26):
+    """CondVarLenTraverse batches (fgpu_expand_trails under Graph.var_len_traverse_batch) against the loop of expand_row over the
+    same rows (fh_var_len_traverse row by row: the path every batch took before), and the bare call with and without paths."""
+    import ctypes as C
+    from falkordb_amd import _ffi, host
+    hc = host.Context(0)
+    ctx = engine.Context(0)
+    A = ctx.mat_rmat(scale)
+    n = A.nrows
+    rp, ci, _ = A.export_csr()
+    r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+    ci = np.array(ci, dtype=np.uint64)
+    A.free()
+    deg = np.diff(rp).astype(np.int64)
+    rng = np.random.default_rng(300 + scale)
+    twice = rng.choice(len(ci), len(ci) // 100, replace=False)              # 1 % of the pairs hold a second edge
+    u, v = np.concatenate([r, r[twice]]), np.concatenate([ci, ci[twice]])
+    ids = np.arange(len(u), dtype=np.uint64)
+    g = host.Graph(hc, n)
+    t = g.add_type("KNOWS")
+    g.bulk_insert_edges(t, u, v, ids)
+    lid = g.add_label("P")
+    srcs = rng.choice(n, k, replace=False)
+    for x in srcs.tolist():
+        g.label_node(int(x), lid)
+    g.commit()
+    fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, ids)
+    multi = ctx.multi_new(np.array(mkey), np.array(moff), np.array(mids))
+    quart = lambda ts: [round(float(x) * 1e3, 3) for x in np.percentile(ts, [25, 50, 75])]
+
+    def one_row(start, lo, hi, bidir):                                      # fh_var_len_traverse without the Python row tuples
+        of, ot, op_, off = host.u64p(), host.u64p(), host.u64p(), host.u64p()
+        cnt = C.c_uint64()
+        host._ck(g.L.fh_var_len_traverse(g.h, b"KNOWS", b"", 0, 1 if bidir else 0, C.c_uint32(lo), C.c_uint32(hi), C.c_uint64(start),
+                                         C.c_int64(-1), 0, 1, C.byref(of), C.byref(ot), C.byref(op_), C.byref(off), C.byref(cnt), None))
+        ft = (host._take(of, cnt.value), host._take(ot, cnt.value))
+        for q in (op_, off):
+            g.L.fh_free(C.cast(q, C.c_void_p))
+        return ft
+
+    for name, lo, hi, bidir in (("out_1_2", 1, 2, False), ("out_1_3", 1, 3, False), ("both_1_2", 1, 2, True)):
+        out = {"path": "varlen_batch", "pattern": name, "scale": scale, "edges": len(u), "multi_pairs": len(twice)}
+        # the rows: all k when one device call holds them in fit_items; else the k rows lightest first (by out-degree) and the
+        # longest halved prefix of those that fits
+        rows, st, order = k, [], srcs
+        while rows:
+            try:
+                res = ctx.expand_trails(order[:rows], None, [fwd], None, None, [bwd], None, None, [multi], bidirectional=bidir,
+                                        min_hops=lo, max_hops=hi, max_items=fit_items, stats_out=st)
+                del res
+                break
+            except engine.FgpuError as e:
+                if e.code != _ffi.FGPU_INSUFFICIENT_SPACE:
+                    raise
+                out.setdefault("all_rows_hold_more_than", int(st[7]))
+                order = srcs[np.argsort(deg[srcs], kind="stable")]
+                rows //= 2
+        if rows == 0:
+            out.update(rows=0, rows_asked=k, stats=st, note="not even the lightest row fits one device call of fit_items")
+            print(json.dumps(out), flush=True)
+            continue
+        budget = max(1 << 22, 1 << int(st[7]).bit_length())
+        out.update(rows=rows, rows_asked=k, device_budget=budget, stats=st)
+        sub = order[:rows]
+        for paths in (False, True):                                         # the bare call
+            ts = []
+            for rep in range(7):
+                t0 = time.perf_counter()
+                res = ctx.expand_trails(sub, None, [fwd], None, None, [bwd], None, None, [multi], bidirectional=bidir, paths=paths,
+                                        min_hops=lo, max_hops=hi, max_items=budget)
+                ctx.sync()
+                ts.append(time.perf_counter() - t0)
+                del res
+            out["raw_paths" if paths else "raw"] = {"ms_q1_median_q3_of_5": quart(ts[2:])}
+        ts, cols = [], None
+        for rep in range(7):                                                # the operator's batch (2 warm-ups)
+            t0 = time.perf_counter()
+            cols, hst = g.var_len_traverse_batch(sub, types=["KNOWS"], min_hops=lo, max_hops=hi, bidirectional=bidir,
+                                                 device_budget=budget, as_arrays=True)
+            ts.append(time.perf_counter() - t0)
+        # the loop of expand_row, lightest rows first (a row cannot be interrupted: one is started only while the rows done so
+        # far predict that it ends by the deadline), each row compared with its part of the batch
+        per = np.bincount(cols[0].astype(np.int64), minlength=rows)
+        first = np.concatenate([[0], np.cumsum(per)])
+        light = np.argsort(per, kind="stable")
+        one_row(int(sub[light[0]]), lo, hi, bidir)                          # (warm)
+        done, at, equal, rate, t0 = 0, 0, True, 2e-4, time.perf_counter()   # (rate: s per emitted row, until one is measured)
+        for i in light.tolist():
+            if done and (time.perf_counter() - t0) + per[i] * rate > deadline_s:
+                break
+            if not done and per[i] * rate > 10 * deadline_s:
+                break
+            f, to = one_row(int(sub[i]), lo, hi, bidir)
+            equal = equal and np.array_equal(f, cols[1][first[i]:first[i + 1]]) and np.array_equal(to, cols[2][first[i]:first[i + 1]])
+            at += len(f)
+            done += 1
+            if at >= 1000:                                                  # (a handful of rows says nothing about a hub)
+                rate = (time.perf_counter() - t0) / at
+            print("loop", name, done, at, round(time.perf_counter() - t0, 2), file=sys.stderr, flush=True)
+        dt = time.perf_counter() - t0
+        assert equal, "the batch and the loop differ"
+        ref = dt / at * len(cols[0]) if at else float("nan")              # (by emitted rows: the hubs carry the time)
+        out["batch"] = {"ms_q1_median_q3_of_5": quart(ts[2:]), "emissions": int(len(cols[0])), "stats": hst}
+        out["loop"] = {"rows_done": done, "finished": done >= rows, "emissions_done": at, "s": round(dt, 3),
+                       "s_for_the_batch": round(ref, 3), "rows_equal_to_the_batch": bool(equal)}
+        out["quotient_loop_over_batch"] = round(ref / float(np.median(ts[2:])), 1)
+        out["note"] = ("one host-layer graph of the distinct RMAT edges loaded with bulk_insert_edges + commit (a second edge on a "
+                       "seeded 1 % of the pairs), the seeded :P sources as rows; host clock around the call, the columns copied out "
+                       "as arrays included on both sides; batch: 2 warm-ups, quartiles of 5; loop: fh_var_len_traverse row by row "
+                       "(the unchanged expand_row), lightest rows first, none started past the deadline, then extrapolated by emitted "
+                       "rows, every row's (from, to) compared with the batch's inside the run; rows < rows_asked: one device call "
+                       "did not hold the pattern over all rows in fit_items (all_rows_hold_more_than: the items counted when it "
+                       "gave up), so the rows were ordered by out-degree and the longest halved prefix that fits was timed; raw: the same "
+                       "tensor from fgpu_edges_build on the engine context, synchronised calls, uploads and read-back included")
+        print(json.dumps(out), flush=True)
 
 
 def bench_append(scales=(18, 20), raw_scale=22):
@@ -1464,5 +1587,7 @@ if __name__ == "__main__":
         bench_edel(*(((scale,), 0) if scale else ()))
     if what == "edges":                          # (the per-row path up to its deadlines: not part of `all`)
         bench_edges(*(((scale,),) if scale else ()))
+    if what == "varlen_batch":                   # (the loop of expand_row up to its deadlines: not part of `all`)
+        bench_varlen(*((scale,) if scale else ()))
     if what == "append":                         # (seconds of edge-by-edge inserts per twin: not part of `all`)
         bench_append(*(((scale,), 0) if scale else ()))
