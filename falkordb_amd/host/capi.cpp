@@ -544,6 +544,51 @@ static Value to_value(int64_t x) {
     return Value{};
 }
 
+// the (row, from, to, edge) columns of an operator's rows, handed out
+static void hand_edge_rows(const CondTraverseOp::EdgeRows& rows, uint64_t** out_row, uint64_t** out_from, uint64_t** out_to,
+                           uint64_t** out_edge, uint64_t* n) {
+    *out_row = hand(rows.row);
+    *out_from = hand(rows.from);
+    *out_to = hand(rows.to);
+    *out_edge = hand(rows.edge);
+    *n = rows.size();
+}
+
+static CondVarLenTraverseOp var_len_op(const char* types, const char* dst_labels, int reversed, int bidirectional, uint32_t min_hops,
+                                       uint32_t max_hops, int emit_path, int prune) {
+    CondVarLenTraverseOp op;
+    op.types = csv(types);
+    op.dst_labels = csv(dst_labels);
+    op.reversed = reversed != 0;
+    op.bidirectional = bidirectional != 0;
+    op.min_hops = min_hops;
+    op.max_hops = max_hops;
+    op.emit_path = emit_path != 0;
+    op.prune = prune != 0;
+    return op;
+}
+
+// VarLenRows flattened: the endpoints, the paths end to end and rows + 1 offsets into them.  The columns are reserved up
+// front for the batch binding's sake, whose calls hand out very many rows.
+static void hand_var_len_rows(const std::vector<VarLenRow>& rows, uint64_t** out_from, uint64_t** out_to, uint64_t** path,
+                              uint64_t** path_off, uint64_t* n) {
+    std::vector<u64> f, t, p, off{0};
+    f.reserve(rows.size());
+    t.reserve(rows.size());
+    off.reserve(rows.size() + 1);
+    for (auto& r : rows) {
+        f.push_back(r.from);
+        t.push_back(r.to);
+        p.insert(p.end(), r.path.begin(), r.path.end());
+        off.push_back(p.size());
+    }
+    *out_from = hand(f);
+    *out_to = hand(t);
+    *path = hand(p);
+    *path_off = hand(off);
+    *n = rows.size();
+}
+
 uint64_t fh_last_op_ns(void) { return g_last_op_ns; }
 
 int fh_cond_traverse_eligible(const char* spec) { return parse_spec(spec).batched_eligible() ? 1 : 0; }
@@ -598,7 +643,7 @@ int fh_cond_traverse_rows(fh_graph* g, const char* spec, const int64_t* from_ids
         CondTraverseOp op = parse_spec(spec);
         CondTraverseOp::BidirDedup dd;                       // one input batch: fresh dedup state (:1268-1270)
         std::vector<u64> used(used_edges, used_edges + (used_edges ? n_used : 0));
-        std::vector<u64> r, f, t, e;
+        CondTraverseOp::EdgeRows rows;
         for (u64 i = 0; i < k; ++i) {
             if (from_ids[i] == -2 || to_ids[i] == -2) continue;   // bound to a non-node: no rows (:792-803)
             std::vector<std::array<u64, 3>> out;
@@ -607,13 +652,9 @@ int fh_cond_traverse_rows(fh_graph* g, const char* spec, const int64_t* from_ids
                           to_ids[i] >= 0 ? std::optional<u64>((u64)to_ids[i]) : std::nullopt, transposed != 0, used, out,
                           dedup ? &dd : nullptr,
                           dedup && dedup_src[i] >= 0 ? std::optional<u64>((u64)dedup_src[i]) : std::nullopt);
-            for (auto& x : out) { r.push_back(i); f.push_back(x[0]); t.push_back(x[1]); e.push_back(x[2]); }
+            for (auto& x : out) rows.push(i, x[0], x[1], x[2]);
         }
-        *out_row = hand(r);
-        *out_from = hand(f);
-        *out_to = hand(t);
-        *out_edge = hand(e);
-        *n = r.size();
+        hand_edge_rows(rows, out_row, out_from, out_to, out_edge, n);
         return 0;
     });
 }
@@ -636,11 +677,7 @@ int fh_cond_traverse_edges_batch(fh_graph* g, const char* spec, const int64_t* f
                                          cross_row_dedup != 0);
         });
         *batched = ok ? 1 : 0;
-        *n = rows.size();
-        *out_row = hand(rows.row);
-        *out_from = hand(rows.from);
-        *out_to = hand(rows.to);
-        *out_edge = hand(rows.edge);
+        hand_edge_rows(rows, out_row, out_from, out_to, out_edge, n);
         *n_null = nulls.size();
         *null_rows = hand(nulls);
         return 0;
@@ -670,14 +707,10 @@ int fh_expand_into(fh_graph* g, const char* types, int bidirectional, int emit_r
         } else {
             for (u64 i = 0; i < k; ++i) per_row[i] = op.expand_row(g->g, srcs[i], dsts[i]);
         }
-        std::vector<u64> r, s, d, e;
+        CondTraverseOp::EdgeRows rows;                       // (src, dst) in the from / to columns
         for (u64 i = 0; i < k; ++i)
-            for (auto& x : per_row[i]) { r.push_back(i); s.push_back(x[0]); d.push_back(x[1]); e.push_back(x[2]); }
-        *out_row = hand(r);
-        *out_src = hand(s);
-        *out_dst = hand(d);
-        *out_edge = hand(e);
-        *n = r.size();
+            for (auto& x : per_row[i]) rows.push(i, x[0], x[1], x[2]);
+        hand_edge_rows(rows, out_row, out_src, out_dst, out_edge, n);
         return 0;
     });
 }
@@ -687,30 +720,11 @@ int fh_var_len_traverse(fh_graph* g, const char* types, const char* dst_labels, 
                         uint64_t** out_from, uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n,
                         uint64_t stats[3]) {
     return guard([&] {
-        CondVarLenTraverseOp op;
-        op.types = csv(types);
-        op.dst_labels = csv(dst_labels);
-        op.reversed = reversed != 0;
-        op.bidirectional = bidirectional != 0;
-        op.min_hops = min_hops;
-        op.max_hops = max_hops;
-        op.emit_path = emit_path != 0;
-        op.prune = prune != 0;
+        const CondVarLenTraverseOp op = var_len_op(types, dst_labels, reversed, bidirectional, min_hops, max_hops, emit_path, prune);
         std::vector<VarLenRow> rows;
         VarLenStats st;
         op.expand_row(g->g, start, dest >= 0 ? std::optional<u64>((u64)dest) : std::nullopt, rows, &st);
-        std::vector<u64> f, t, p, off{0};
-        for (auto& r : rows) {
-            f.push_back(r.from);
-            t.push_back(r.to);
-            p.insert(p.end(), r.path.begin(), r.path.end());
-            off.push_back(p.size());
-        }
-        *out_from = hand(f);
-        *out_to = hand(t);
-        *path = hand(p);
-        *path_off = hand(off);
-        *n = rows.size();
+        hand_var_len_rows(rows, out_from, out_to, path, path_off, n);
         if (stats) { stats[0] = st.frames; stats[1] = st.pruned; stats[2] = st.reach_products; }
         return 0;
     });
@@ -722,15 +736,7 @@ int fh_var_len_traverse_batch(fh_graph* g, const char* types, const char* dst_la
                               uint64_t** out_to, uint64_t** path, uint64_t** path_off, uint64_t* n, uint64_t stats[3],
                               uint64_t* device_calls) {
     return guard([&] {
-        CondVarLenTraverseOp op;
-        op.types = csv(types);
-        op.dst_labels = csv(dst_labels);
-        op.reversed = reversed != 0;
-        op.bidirectional = bidirectional != 0;
-        op.min_hops = min_hops;
-        op.max_hops = max_hops;
-        op.emit_path = emit_path != 0;
-        op.prune = prune != 0;
+        CondVarLenTraverseOp op = var_len_op(types, dst_labels, reversed, bidirectional, min_hops, max_hops, emit_path, prune);
         if (device_budget) op.device_budget = device_budget;
         std::vector<std::optional<u64>> d;
         if (dests)
@@ -740,22 +746,8 @@ int fh_var_len_traverse_batch(fh_graph* g, const char* types, const char* dst_la
         VarLenStats st;
         u64 calls = 0;
         timed([&] { op.expand_batch(g->g, std::vector<u64>(starts, starts + k), d, rows_of, rows, &st, &calls); return 0; });
-        std::vector<u64> f, t, p, off{0};
-        f.reserve(rows.size());
-        t.reserve(rows.size());
-        off.reserve(rows.size() + 1);
-        for (auto& r : rows) {
-            f.push_back(r.from);
-            t.push_back(r.to);
-            p.insert(p.end(), r.path.begin(), r.path.end());
-            off.push_back(p.size());
-        }
         *out_row = hand(rows_of);
-        *out_from = hand(f);
-        *out_to = hand(t);
-        *path = hand(p);
-        *path_off = hand(off);
-        *n = rows.size();
+        hand_var_len_rows(rows, out_from, out_to, path, path_off, n);
         if (stats) { stats[0] = st.frames; stats[1] = st.pruned; stats[2] = st.reach_products; }
         if (device_calls) *device_calls = calls;
         return 0;

@@ -319,74 +319,81 @@ bool CondTraverseOp::batched_eligible() const {
 }
 
 namespace {
+// ---- type names -> tensor ids: every operator and procedure below resolves its relationship types through these two --------
+// The known names among `names`, in the order listed, a name listed twice kept twice: the `filter_map` of
+// get_node_relationships_by_type (graph.rs:1803-1810), build_relationship_matrix_unrestricted (graph.rs:2524-2527) and
+// edge_type_indices (cond_traverse.rs:418-426).
+std::vector<u64> named_type_ids(const Graph& g, const std::vector<std::string>& names) {
+    std::vector<u64> ids;
+    for (auto& t : names)
+        if (auto id = g.type_id(t)) ids.push_back(*id);
+    return ids;
+}
+
+// The tensors a type list scans: none named = every tensor in id order, else named_type_ids.  Names of which none is known
+// scan NOTHING — what that means is the caller's: CondTraverse's no_match (`!names.empty() && ids.empty()`: a single unknown
+// type, cond_traverse.rs:481-490, or an alternation of unknown names) returns before anything runs, the other operators run
+// over an empty scan.
+std::vector<u64> scanned_type_ids(const Graph& g, const std::vector<std::string>& names) {
+    if (!names.empty()) return named_type_ids(g, names);
+    std::vector<u64> ids(g.relationship_tensors().size());
+    for (u64 t = 0; t < ids.size(); ++t) ids[t] = t;
+    return ids;
+}
+
+// ---- device layers -----------------------------------------------------------------------------------------------------
+// The three layers of a delta matrix as the device wants them: an empty delta goes as null.  `on_device` turns a layer into
+// its device handle.  The VersionedMatrix forms wait on that matrix alone; a tensor's forward layers are waited on by the
+// caller (wait_fwd() on the hot forward hop, wait() where `mt` is read too): which layers a site materialises is its choice.
+struct Layers { const fgpu_mat *m, *dp, *dm; };
+
+template <class F>
+Layers layers_of(const Matrix& m, const Matrix& dp, const Matrix& dm, F on_device) {
+    return {on_device(m), dp.nvals() ? on_device(dp) : nullptr, dm.nvals() ? on_device(dm) : nullptr};
+}
+const fgpu_mat* snapshot_of(const Matrix& x) { return x.snapshot(); }
+template <class F>
+Layers layers_of(const VersionedMatrix& v, F on_device) {   // the adjacency, a tensor's `mt`
+    v.wait();
+    return layers_of(v.m(), v.dp(), v.dm(), on_device);
+}
+Layers layers_of(const VersionedMatrix& v) { return layers_of(v, snapshot_of); }
+Layers fwd_layers(const Tensor& t) {                         // after the caller's wait_fwd() or wait()
+    return layers_of(t.fwd_m(), t.fwd_dp(), t.fwd_dm(), snapshot_of);
+}
+
 struct HopLayers {
-    // keeps temporaries (materialized unions) alive for the duration of the call
+    // keeps temporaries (materialized unions, transposes) alive for the duration of the call
     std::vector<Matrix> owned;
     std::vector<const fgpu_mat*> m, dp, dm;
+    const fgpu_mat* keep(Matrix x) { owned.push_back(std::move(x)); return owned.back().snapshot(); }
+    void push(Layers l) { m.push_back(l.m); dp.push_back(l.dp); dm.push_back(l.dm); }
 };
-
-// Type names of one hop -> tensor ids, the way the reference resolves them: a single unknown type is no_match
-// (cond_traverse.rs:481-490), an alternation drops its unknown names (`filter_map` in
-// build_relationship_matrix_unrestricted, graph.rs:2524-2527, and in edge_type_indices, cond_traverse.rs:418-426)
-// and is no_match only when none is known.  Returns false for no_match.
-bool resolve_hop_types(const Graph& g, const std::vector<std::string>& types, std::vector<u64>& ids) {
-    ids.clear();
-    for (auto& t : types)
-        if (auto id = g.type_id(t)) ids.push_back(*id);
-    return types.empty() || !ids.empty();
-}
 
 // Matrix choice per hop (cond_traverse.rs:478-505): no type -> adjacency; one type -> that tensor's forward
 // layers; an alternation -> materialized union of its known types with clean deltas (also when only one of them
-// is known: the reference branches on the number of NAMES).  Returns false for no_match.
+// is known: the reference branches on the number of NAMES).  `transposed`: the structures build_transposed_iter walks
+// (cond_traverse.rs:221-235), as device layers: the transposes of the adjacency layers (cached on their snapshots: paid
+// once per matrix version), the tensor's own `mt` (kept by every insert / delete, Tensor::matrix_t), the transpose of the
+// materialized alternation.  type_ids gets the tensors each hop scans.  Returns false for no_match.
 bool hop_layers(const Graph& g, const std::vector<Hop>& hops, HopLayers& hl, std::vector<std::vector<u64>>& type_ids,
                 bool transposed = false) {
     hl.owned.reserve(3 * hops.size());
+    auto kept_transpose = [&](const Matrix& x) { return hl.keep(x.transpose()); };
     for (auto& h : hops) {
-        std::vector<u64> ids;
-        if (!resolve_hop_types(g, h.types, ids)) return false;
-        type_ids.push_back(ids);
-        if (transposed) {
-            // the structures build_transposed_iter walks (cond_traverse.rs:221-235), as device layers: the tensor's own `mt`
-            // (kept by every insert / delete, Tensor::matrix_t), the transposes of the adjacency layers (cached on their
-            // snapshots: paid once per matrix version), the transpose of a materialized alternation
-            auto keep = [&](Matrix m) { hl.owned.push_back(std::move(m)); return hl.owned.back().snapshot(); };
-            if (h.types.size() == 1) {
-                const VersionedMatrix& mt = g.relationship_tensors()[ids[0]].matrix_t();
-                mt.wait();
-                hl.m.push_back(mt.m().snapshot());
-                hl.dp.push_back(mt.dp().nvals() ? mt.dp().snapshot() : nullptr);
-                hl.dm.push_back(mt.dm().nvals() ? mt.dm().snapshot() : nullptr);
-            } else if (h.types.empty()) {
-                const VersionedMatrix& a = g.adjacency_matrix();
-                a.wait();
-                hl.m.push_back(keep(a.m().transpose()));
-                hl.dp.push_back(a.dp().nvals() ? keep(a.dp().transpose()) : nullptr);
-                hl.dm.push_back(a.dm().nvals() ? keep(a.dm().transpose()) : nullptr);
-            } else {
-                hl.m.push_back(keep(g.build_relationship_matrix_unrestricted(ids).transpose()));
-                hl.dp.push_back(nullptr);
-                hl.dm.push_back(nullptr);
-            }
-            continue;
-        }
+        type_ids.push_back(scanned_type_ids(g, h.types));
+        const std::vector<u64>& ids = type_ids.back();
+        if (!h.types.empty() && ids.empty()) return false;
         if (h.types.empty()) {
             const VersionedMatrix& a = g.adjacency_matrix();
-            a.wait();
-            hl.m.push_back(a.m().snapshot());
-            hl.dp.push_back(a.dp().nvals() ? a.dp().snapshot() : nullptr);
-            hl.dm.push_back(a.dm().nvals() ? a.dm().snapshot() : nullptr);
+            hl.push(transposed ? layers_of(a, kept_transpose) : layers_of(a));
         } else if (h.types.size() == 1) {
             const Tensor& t = g.relationship_tensors()[ids[0]];
-            t.wait_fwd();
-            hl.m.push_back(t.fwd_m().snapshot());
-            hl.dp.push_back(t.fwd_dp().nvals() ? t.fwd_dp().snapshot() : nullptr);
-            hl.dm.push_back(t.fwd_dm().nvals() ? t.fwd_dm().snapshot() : nullptr);
+            if (!transposed) t.wait_fwd();               // (the forward hop never materialises a pending transpose)
+            hl.push(transposed ? layers_of(t.matrix_t()) : fwd_layers(t));
         } else {
-            hl.owned.push_back(g.build_relationship_matrix_unrestricted(ids));
-            hl.m.push_back(hl.owned.back().snapshot());
-            hl.dp.push_back(nullptr);
-            hl.dm.push_back(nullptr);
+            Matrix u = g.build_relationship_matrix_unrestricted(ids);
+            hl.push({hl.keep(transposed ? u.transpose() : std::move(u)), nullptr, nullptr});
         }
     }
     return true;
@@ -409,6 +416,36 @@ void nodes_have_labels(const Graph& g, const std::vector<LabelId>& lids, const s
             if (!((in_m[c] && !in_dm[c]) || (!in_m[c] && in_dp[c]))) ok[c] = 0;
     }
 }
+
+// The layers of every scanned tensor as they lie on the device, forward and transposed, with the multi-edge table: the seven
+// parallel arrays fgpu_expand_edges and fgpu_expand_trails take.  Tensor::wait() materialises both directions.
+struct TensorLayerArrays {
+    std::vector<const fgpu_mat*> m, dp, dm, tm, tdp, tdm;
+    std::vector<const fgpu_multi*> multi;
+    size_t size() const { return m.size(); }
+};
+TensorLayerArrays gather(const Graph& g, const std::vector<u64>& tids) {
+    TensorLayerArrays a;
+    for (u64 t : tids) {
+        const Tensor& ten = g.relationship_tensors()[t];
+        ten.wait();
+        const Layers f = fwd_layers(ten), b = layers_of(ten.matrix_t());
+        a.m.push_back(f.m); a.dp.push_back(f.dp); a.dm.push_back(f.dm);
+        a.tm.push_back(b.m); a.tdp.push_back(b.dp); a.tdm.push_back(b.dm);
+        a.multi.push_back(ten.multi_table());
+    }
+    return a;
+}
+
+// OPTIONAL (cond_traverse.rs:737-747): the input rows i < k without an emission, ascending, appended to null_rows;
+// row_of(r) = the input row of emission r < n_emitted
+template <class RowOf>
+void append_rows_without_emission(u64 k, size_t n_emitted, RowOf row_of, std::vector<u64>& null_rows) {
+    std::vector<uint8_t> matched(k, 0);
+    for (size_t r = 0; r < n_emitted; ++r) matched[row_of(r)] = 1;
+    for (u64 i = 0; i < k; ++i)
+        if (!matched[i]) null_rows.push_back(i);
+}
 }  // namespace
 
 bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src, const std::vector<Value>* to_bound,
@@ -417,9 +454,8 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
     null_rows.clear();
     if (flops) *flops = 0;
     const u64 k = src.size();
-    auto no_match = [&]() {
-        if (optional)
-            for (u64 i = 0; i < k; ++i) null_rows.push_back(i);
+    auto null_pad = [&]() {                  // OPTIONAL: the rows without an emission (:737-747); on no_match, every row
+        if (optional) append_rows_without_emission(k, rows.size(), [&](size_t r) { return rows.row_at(r); }, null_rows);
         return true;
     };
     // FH_TIMING=1: phase times of every call on stderr (tools/bench_paths.py host)
@@ -440,11 +476,11 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
     // looked up as (reached, bound) — and gives what the per-row path gives row by row.  One hop only (a transposed operator
     // is never fused, fuse_anonymous_traverse.rs:118-122).
     if (transposed && hops.size() != 1) return false;
-    if (!hop_layers(g, hops, hl, type_ids, transposed)) return no_match();          // unknown type (:485-490)
+    if (!hop_layers(g, hops, hl, type_ids, transposed)) return null_pad();          // no_match: unknown type (:485-490)
     lap("hop_layers");
     auto last_dst = g.resolve_label_ids(hops.back().dst_labels);
     auto src_lids = g.resolve_label_ids(src_labels);
-    if (!last_dst || !src_lids) return no_match();                      // unknown label
+    if (!last_dst || !src_lids) return null_pad();                      // no_match: unknown label
 
     // F[i, src_i] = 1 for bound Node sources passing ALL source labels (:556-601)
     std::vector<u64> src_ids(k, ~0ull);
@@ -462,7 +498,7 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
     bool any = false;
     for (size_t c = 0; c < cand_rows.size(); ++c)
         if (ok[c]) { src_ids[cand_rows[c]] = cand_nodes[c]; any = true; }
-    if (!any) return no_match();
+    if (!any) return null_pad();
 
     std::vector<u64> bitmap;
     if (!last_dst->empty()) bitmap = g.label_bitmap(*last_dst);         // dst label filter of the LAST hop (:647-651)
@@ -511,12 +547,9 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
     if (flops) *flops = fl;
     lap("fgpu_expand_pairs");
     }
-    std::vector<uint8_t> matched(k, 0);
     if (want_edge) {
         // representative edge: first id found scanning the types in order (:663-695), batched per type
-        std::vector<u64> tids = type_ids[0];
-        if (tids.empty())
-            for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+        const std::vector<u64>& tids = type_ids[0];
         rows.materialize();                                          // (this path drops and annotates pairs in place)
         const size_t n = rows.dest.size();
         std::vector<u64> es(n);
@@ -542,12 +575,7 @@ bool CondTraverseOp::expand_batch(const Graph& g, const std::vector<Value>& src,
         rows.dest.resize(o);
         rows.edge.resize(o);
     }
-    if (optional) {
-        for (size_t r = 0; r < rows.size(); ++r) matched[rows.row_at(r)] = 1;
-        for (u64 i = 0; i < k; ++i)
-            if (!matched[i]) null_rows.push_back(i);
-    }
-    return true;
+    return null_pad();
 }
 
 void ExpandedRows::materialize() {
@@ -564,8 +592,8 @@ void CondTraverseOp::expand_row(const Graph& g, std::optional<u64> from_id, std:
     const Hop& h = hops.at(0);
     // build_state (cond_traverse.rs:362-440): labels of the matrix source / destination for the forward pass and,
     // for a bidirectional pattern, for the reverse pass; any unknown label or an unresolvable type is no_match
-    std::vector<u64> tids;
-    if (!resolve_hop_types(g, h.types, tids)) return;                    // build_unrestricted_iter -> None
+    const std::vector<u64> scan = scanned_type_ids(g, h.types);          // edge_type_indices (:418-426)
+    if (!h.types.empty() && scan.empty()) return;                        // no_match: build_unrestricted_iter -> None
     auto from_l = g.resolve_label_ids(src_labels);
     auto to_l = g.resolve_label_ids(h.dst_labels);
     if (!from_l || !to_l) return;
@@ -573,20 +601,17 @@ void CondTraverseOp::expand_row(const Graph& g, std::optional<u64> from_id, std:
     const std::vector<LabelId>& fwd_dst_l = transposed ? *from_l : *to_l;
     const std::vector<LabelId>& rev_src_l = transposed ? *from_l : *to_l;       // :376-389
     const std::vector<LabelId>& rev_dst_l = transposed ? *to_l : *from_l;
-    std::vector<u64> scan = tids;                                        // edge_type_indices (:418-426)
-    if (h.types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) scan.push_back(t);
 
     // rows [lo, hi] of the unrestricted pair matrix in ascending (row, col) order (build_unrestricted_iter :196-209)
     auto fwd_rows = [&](u64 lo, u64 hi) {
         if (h.types.empty()) return g.adjacency_matrix().iter(lo, hi);
-        if (h.types.size() == 1) return g.relationship_tensors()[tids[0]].structural_iter(lo, hi);
-        return g.build_relationship_matrix_unrestricted(tids).iter(lo, hi);
+        if (h.types.size() == 1) return g.relationship_tensors()[scan[0]].structural_iter(lo, hi);
+        return g.build_relationship_matrix_unrestricted(scan).iter(lo, hi);
     };
     // row d of the TRANSPOSED pair matrix: (dest, src) ascending (build_transposed_iter :221-235)
     auto bwd_row = [&](u64 d) {
-        if (h.types.size() == 1) return g.relationship_tensors()[tids[0]].matrix_t().iter(d, d);
-        Matrix a = h.types.empty() ? g.adjacency_matrix().extract() : g.build_relationship_matrix_unrestricted(tids);
+        if (h.types.size() == 1) return g.relationship_tensors()[scan[0]].matrix_t().iter(d, d);
+        Matrix a = h.types.empty() ? g.adjacency_matrix().extract() : g.build_relationship_matrix_unrestricted(scan);
         return a.transpose().iter(d, d);
     };
     // (src, dst) matrix coordinates of one pass (:852-874 / :897-921)
@@ -662,26 +687,20 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
     const u64 k = from.size();
     if (to.size() != k) throw GrbError(FGPU_INVALID, "expand_batch_edges: from and to differ in length");
     auto finish = [&]() {                                                // OPTIONAL: the rows without an emission
-        if (!optional) return true;
-        std::vector<uint8_t> matched(k, 0);
-        for (u64 r : rows.row) matched[r] = 1;
-        for (u64 i = 0; i < k; ++i)
-            if (!matched[i]) null_rows.push_back(i);
+        if (optional) append_rows_without_emission(k, rows.size(), [&](size_t r) { return rows.row[r]; }, null_rows);
         return true;
     };
     const Hop& h = hops.at(0);
     // build_state (cond_traverse.rs:362-440), as expand_row: a single unknown type or an alternation of unknown names is
-    // no_match, unknown names of an alternation are dropped, an unknown label is no_match
-    std::vector<u64> scan;
-    if (!resolve_hop_types(g, h.types, scan)) return finish();
-    auto from_l = g.resolve_label_ids(src_labels);
-    auto to_l = g.resolve_label_ids(h.dst_labels);
-    if (!from_l || !to_l) return finish();
+    // no_match, unknown names of an alternation are dropped, an unknown label is no_match.
     // No type named: every tensor, in id order (edge_type_indices, :418-426).  The reference walks the ADJACENCY there and the
     // device walks the union of the tensors' structures: the same pairs, by the Graph invariant that the adjacency is that union
     // (create_edge / delete_edge and the four bulk mutations write both sides together).
-    if (h.types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) scan.push_back(t);
+    const std::vector<u64> scan = scanned_type_ids(g, h.types);
+    if (!h.types.empty() && scan.empty()) return finish();
+    auto from_l = g.resolve_label_ids(src_labels);
+    auto to_l = g.resolve_label_ids(h.dst_labels);
+    if (!from_l || !to_l) return finish();
 
     // the rows: ~0 = unbound; a row bound to a non-node is skipped (:796-805), one with nothing bound is the host's
     std::vector<u64> f(k, ~0ull), t(k, ~0ull);
@@ -715,22 +734,8 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
     for (u64 i = 0; i < k; ++i)
         if (!live[i]) f[i] = t[i] = ~0ull;                               // (the device skips a row with nothing bound)
 
-    // the layers of every scanned tensor, as they lie on the device
-    const size_t T = scan.size();
-    std::vector<const fgpu_mat*> m(T), dp(T), dm(T), tm(T), tdp(T), tdm(T);
-    std::vector<const fgpu_multi*> multi(T);
-    for (size_t x = 0; x < T; ++x) {
-        const Tensor& ten = g.relationship_tensors()[scan[x]];
-        ten.wait();
-        const VersionedMatrix& mt = ten.matrix_t();
-        m[x] = ten.fwd_m().snapshot();
-        dp[x] = ten.fwd_dp().nvals() ? ten.fwd_dp().snapshot() : nullptr;
-        dm[x] = ten.fwd_dm().nvals() ? ten.fwd_dm().snapshot() : nullptr;
-        tm[x] = mt.m().snapshot();
-        tdp[x] = mt.dp().nvals() ? mt.dp().snapshot() : nullptr;
-        tdm[x] = mt.dm().nvals() ? mt.dm().snapshot() : nullptr;
-        multi[x] = ten.multi_table();
-    }
+    const TensorLayerArrays tl = gather(g, scan);                        // the layers of every scanned tensor
+    const size_t T = tl.size();
     const bool filter = used && n_used;
     const bool first_only = !emit_relationship;
     const int flags = (transposed ? FGPU_EDGES_TRANSPOSED : 0) | (bidirectional ? FGPU_EDGES_BIDIRECTIONAL : 0) |
@@ -741,8 +746,9 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
     EngineBuf<uint8_t> opass(ctx);
     u64 n = 0;
     if (T && any)
-        check(fgpu_expand_edges(ctx, f.data(), t.data(), k, m.data(), dp.data(), dm.data(), tm.data(), tdp.data(), tdm.data(), multi.data(),
-                                (int)T, flags, from_bm.empty() ? nullptr : from_bm.data(), to_bm.empty() ? nullptr : to_bm.data(),
+        check(fgpu_expand_edges(ctx, f.data(), t.data(), k, tl.m.data(), tl.dp.data(), tl.dm.data(), tl.tm.data(), tl.tdp.data(),
+                                tl.tdm.data(), tl.multi.data(), (int)T, flags, from_bm.empty() ? nullptr : from_bm.data(),
+                                to_bm.empty() ? nullptr : to_bm.data(),
                                 orow.out(), ofrom.out(), oto.out(), oid.out(), filter ? opass.out() : nullptr, &n, stats),
               "CondTraverse::expand_batch_edges");
 
@@ -764,10 +770,7 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
                 if (std::find(u, u + n_used, oid[q]) != u + n_used) continue;
                 if (first_only) g_done = true;
             }
-            rows.row.push_back(r);
-            rows.from.push_back(ofrom[q]);
-            rows.to.push_back(oto[q]);
-            rows.edge.push_back(oid[q]);
+            rows.push(r, ofrom[q], oto[q], oid[q]);
         }
     };
     for (u64 i = 0; i < k; ++i) {
@@ -776,7 +779,7 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
         std::vector<std::array<u64, 3>> out;
         const std::vector<u64> u(filter ? used + i * n_used : nullptr, filter ? used + (i + 1) * n_used : nullptr);
         expand_row(g, std::nullopt, std::nullopt, transposed, u, out);
-        for (auto& x : out) { rows.row.push_back(i); rows.from.push_back(x[0]); rows.to.push_back(x[1]); rows.edge.push_back(x[2]); }
+        for (auto& x : out) rows.push(i, x[0], x[1], x[2]);
     }
     device_rows_below(k);
     return finish();
@@ -804,28 +807,30 @@ std::vector<VlEdge> node_relationships(const Graph& g, u64 id, const std::vector
     }
     return out;
 }
+
+// What a CondVarLenTraverse walks and filters by, resolved once per row or batch.  Types: none named = every tensor; named =
+// the known ones (filter_map, graph.rs:1803-1810) — with none known the walk is empty and the 0-hop rows still appear.
+// Destination labels: an unknown one suppresses every emission (:100-107).
+struct VarLenScan {
+    std::vector<u64> tids;
+    std::vector<LabelId> dl;
+    bool label_missing = false;
+    VarLenScan(const Graph& g, const CondVarLenTraverseOp& op) : tids(scanned_type_ids(g, op.types)) {
+        for (auto& l : op.dst_labels) {
+            if (auto id = g.label_id(l)) dl.push_back(*id);
+            else label_missing = true;
+        }
+    }
+};
 }  // namespace
 
 void CondVarLenTraverseOp::expand_row(const Graph& g, u64 start, std::optional<u64> dest, std::vector<VarLenRow>& out,
                                       VarLenStats* stats) const {
     VarLenStats local;
     VarLenStats& st = stats ? *stats : local;
-    // types: none named = every tensor; named = the known ones (filter_map, graph.rs:1803-1810)
-    std::vector<u64> tids;
-    if (types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
-    else
-        for (auto& t : types)
-            if (auto id = g.type_id(t)) tids.push_back(*id);
-    // destination labels resolved once per row; an unknown label suppresses every emission (:100-107)
-    std::vector<LabelId> dl;
-    bool label_missing = false;
-    for (auto& l : dst_labels) {
-        if (auto id = g.label_id(l)) dl.push_back(*id);
-        else label_missing = true;
-    }
+    const VarLenScan scan(g, *this);
     auto labels_ok = [&](u64 v) {
-        for (LabelId l : dl)
+        for (LabelId l : scan.dl)
             if (!g.node_has_label_id(v, l)) return false;
         return true;
     };
@@ -841,14 +846,14 @@ void CondVarLenTraverseOp::expand_row(const Graph& g, u64 start, std::optional<u
         out.push_back(std::move(r));
     };
     // 0-hop emission (:153-171)
-    if (min_hops == 0 && (!dest || *dest == start) && !label_missing && labels_ok(start)) emit(start, {start});
+    if (min_hops == 0 && (!dest || *dest == start) && !scan.label_missing && labels_ok(start)) emit(start, {start});
 
     // reach[r] (r >= 1): nodes from which `dest` is reachable by a walk of 1..r steps in the direction the DFS moves.
     // Walking back from dest: the DFS follows A (outgoing), A' (reversed) or A + A' (bidirectional), so the sets grow by
     // products with A', A or A + A'.  Only worth it for a bound destination and a finite budget.
     std::vector<std::vector<uint64_t>> reach;
     const u64 n = g.node_cap();
-    if (prune && dest && max_hops != UINT32_MAX && max_hops >= 2 && max_hops <= 64 && !tids.empty()) {
+    if (prune && dest && max_hops != UINT32_MAX && max_hops >= 2 && max_hops <= 64 && !scan.tids.empty()) {
         // (build_adjacency_matrix takes the names: none = the adjacency of every type, unknown names are skipped)
         Matrix back = bidirectional ? g.build_symmetric_adjacency_matrix(types)
                                     : (reversed ? g.build_adjacency_matrix(types) : g.build_adjacency_matrix(types).transpose());
@@ -885,7 +890,7 @@ void CondVarLenTraverseOp::expand_row(const Graph& g, u64 start, std::optional<u
         if (hop > max_hops) continue;
         ++st.frames;
         auto it = adj_cache.find(fr.node);
-        if (it == adj_cache.end()) it = adj_cache.emplace(fr.node, node_relationships(g, fr.node, tids, with_out, with_in)).first;
+        if (it == adj_cache.end()) it = adj_cache.emplace(fr.node, node_relationships(g, fr.node, scan.tids, with_out, with_in)).first;
         scratch.clear();
         for (const VlEdge& e : it->second) {
             if (std::find(fr.used.begin(), fr.used.end(), e.id) != fr.used.end()) continue;   // relationship uniqueness
@@ -894,7 +899,7 @@ void CondVarLenTraverseOp::expand_row(const Graph& g, u64 start, std::optional<u
             else if (bidirectional && e.dst == fr.node) scratch.push_back({e.id, e.src});
         }
         for (auto& [eid, nb] : scratch) {
-            const bool will_emit = hop >= min_hops && (!dest || *dest == nb) && !label_missing && labels_ok(nb);
+            const bool will_emit = hop >= min_hops && (!dest || *dest == nb) && !scan.label_missing && labels_ok(nb);
             bool will_continue = hop < max_hops;
             if (will_continue && !can_reach(nb, max_hops - hop)) { will_continue = false; ++st.pruned; }
             if (!will_emit && !will_continue) continue;
@@ -920,23 +925,13 @@ void CondVarLenTraverseOp::expand_batch(const Graph& g, const std::vector<u64>& 
     if (device_calls) *device_calls = 0;
     const u64 k = starts.size();
     if (!dests.empty() && dests.size() != k) throw GrbError(FGPU_INVALID, "CondVarLenTraverse::expand_batch: starts and dests differ in length");
-    // types and labels as expand_row resolves them
-    std::vector<u64> tids;
-    if (types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
-    else
-        for (auto& t : types)
-            if (auto id = g.type_id(t)) tids.push_back(*id);
-    std::vector<LabelId> dl;
-    for (auto& l : dst_labels) {
-        if (auto id = g.label_id(l)) dl.push_back(*id);
-        else return;                                                     // an unknown label suppresses every emission (:100-107)
-    }
+    const VarLenScan scan(g, *this);                                     // types and labels as expand_row resolves them
+    if (scan.label_missing) return;                                      // no emission (:100-107), so no device call either
     std::vector<u64> bitmap;
-    if (!dl.empty()) bitmap = g.label_bitmap(dl);
+    if (!scan.dl.empty()) bitmap = g.label_bitmap(scan.dl);
     auto dest_of = [&](u64 i) { return dests.empty() ? std::optional<u64>() : dests[i]; };
 
-    // the rows the device takes, and the layers of every walked tensor as they lie there (as expand_batch_edges gathers them)
+    // the rows the device takes, and the layers of every walked tensor as they lie there
     const u64 cap = g.node_cap();
     auto sendable = [&](u64 v) { return v < cap && !g.is_node_deleted(v); };
     std::vector<u64> idx, ds, dd;
@@ -947,21 +942,7 @@ void CondVarLenTraverseOp::expand_batch(const Graph& g, const std::vector<u64>& 
         ds.push_back(starts[i]);
         dd.push_back(d ? *d : ~0ull);
     }
-    const size_t T = tids.size();
-    std::vector<const fgpu_mat*> m(T), dp(T), dm(T), tm(T), tdp(T), tdm(T);
-    std::vector<const fgpu_multi*> multi(T);
-    for (size_t x = 0; x < T && !idx.empty(); ++x) {
-        const Tensor& ten = g.relationship_tensors()[tids[x]];
-        ten.wait();
-        const VersionedMatrix& mt = ten.matrix_t();
-        m[x] = ten.fwd_m().snapshot();
-        dp[x] = ten.fwd_dp().nvals() ? ten.fwd_dp().snapshot() : nullptr;
-        dm[x] = ten.fwd_dm().nvals() ? ten.fwd_dm().snapshot() : nullptr;
-        tm[x] = mt.m().snapshot();
-        tdp[x] = mt.dp().nvals() ? mt.dp().snapshot() : nullptr;
-        tdm[x] = mt.dm().nvals() ? mt.dm().snapshot() : nullptr;
-        multi[x] = ten.multi_table();
-    }
+    const TensorLayerArrays tl = idx.empty() ? TensorLayerArrays() : gather(g, scan.tids);   // (no row to send: no layer waited on)
     fgpu_ctx* ctx = g.ctx().raw();
     const int flags = (reversed ? FGPU_TRAILS_REVERSED : 0) | (bidirectional ? FGPU_TRAILS_BIDIRECTIONAL : 0) |
                       (emit_path ? FGPU_TRAILS_PATHS : 0);
@@ -989,8 +970,9 @@ void CondVarLenTraverseOp::expand_batch(const Graph& g, const std::vector<u64>& 
         u64 dstats[8] = {0};
         if (device_calls) ++*device_calls;
         const fgpu_info info = fgpu_expand_trails(
-            ctx, ds.data() + lo, dests.empty() ? nullptr : dd.data() + lo, hi - lo, m.data(), dp.data(), dm.data(), tm.data(), tdp.data(),
-            tdm.data(), multi.data(), (int)T, flags, min_hops, max_hops, bitmap.empty() ? nullptr : bitmap.data(), device_budget,
+            ctx, ds.data() + lo, dests.empty() ? nullptr : dd.data() + lo, hi - lo, tl.m.data(), tl.dp.data(), tl.dm.data(), tl.tm.data(),
+            tl.tdp.data(), tl.tdm.data(), tl.multi.data(), (int)tl.size(), flags, min_hops, max_hops,
+            bitmap.empty() ? nullptr : bitmap.data(), device_budget,
             c.row.out(), c.from.out(), c.to.out(), c.hops.out(), emit_path ? c.poff.out() : nullptr, emit_path ? c.pnode.out() : nullptr,
             emit_path ? c.pedge.out() : nullptr, &c.n, dstats);
         if (info == FGPU_INSUFFICIENT_SPACE) {
@@ -1051,23 +1033,12 @@ void CondVarLenTraverseOp::expand_batch(const Graph& g, const std::vector<u64>& 
 }
 
 // ---- ExpandInto ---------------------------------------------------------------------------------------
-static std::vector<u64> resolve_types(const Graph& g, const std::vector<std::string>& types) {
-    std::vector<u64> tids;
-    if (types.empty()) {
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
-        return tids;
-    }
-    for (auto& t : types)
-        if (auto id = g.type_id(t)) tids.push_back(*id);
-    return tids;
-}
-
 std::vector<std::array<u64, 3>> ExpandIntoOp::expand_row(const Graph& g, u64 src, u64 dst,
                                                          const std::vector<u64>& used_edges) const {
     std::vector<std::array<u64, 3>> out;
     std::vector<std::pair<u64, u64>> pairs{{src, dst}};
     if (bidirectional && src != dst) pairs.push_back({dst, src});
-    auto tids = resolve_types(g, types);
+    auto tids = scanned_type_ids(g, types);
     for (auto& pr : pairs) {
         size_t before = out.size();
         for (u64 t : tids)
@@ -1084,7 +1055,7 @@ void ExpandIntoOp::expand_batch(const Graph& g, const std::vector<u64>& srcs, co
                                 std::vector<std::vector<std::array<u64, 3>>>& out) const {
     const size_t k = srcs.size();
     out.assign(k, {});
-    auto tids = resolve_types(g, types);
+    auto tids = scanned_type_ids(g, types);
     // probe list: (src, dst) of every row, then (dst, src) of the rows that also look backwards
     std::vector<u64> ps(srcs), pd(dsts);
     std::vector<size_t> back_row;
@@ -1184,7 +1155,7 @@ std::vector<std::vector<u64>> AllShortestPathsOp::expand_row(const Graph& g, u64
     if (length) *length = -1;
     const u64 n = g.node_cap();
     if (src >= n || dst >= n || g.is_node_deleted(src) || g.is_node_deleted(dst)) return out;
-    const std::vector<u64> tids = resolve_types(g, types);               // (a name listed twice is walked twice: filter_map)
+    const std::vector<u64> tids = scanned_type_ids(g, types);            // (a name listed twice is walked twice: filter_map)
     if (tids.empty()) return out;
     Matrix adj = bidirectional ? g.build_symmetric_adjacency_matrix(types) : g.build_adjacency_matrix(types);
     Matrix adj_t = bidirectional ? adj : adj.transpose();
@@ -1216,7 +1187,7 @@ std::vector<std::vector<std::vector<u64>>> AllShortestPathsOp::expand_batch(cons
     if (lengths) lengths->assign(count, -1);
     if (device_calls) *device_calls = 0;
     const u64 n = g.node_cap();
-    const std::vector<u64> tids = resolve_types(g, types);
+    const std::vector<u64> tids = scanned_type_ids(g, types);
     if (tids.empty()) return out;
     // the rows the device sees: both nodes in range and alive
     std::vector<size_t> row;
@@ -1394,7 +1365,7 @@ BfsResult algo_bfs(const Graph& g, std::optional<u64> source, int64_t max_depth,
     }
     if (want_edges && !res.nodes.empty()) {
         // edges[k] = first id of get_src_dest_relationships(parent, child, types), batched per type
-        const std::vector<u64> tids = resolve_types(g, types);
+        const std::vector<u64> tids = scanned_type_ids(g, types);
         std::vector<std::optional<u64>> rep(ps.size());
         for (u64 t : tids) {
             std::vector<std::vector<u64>> ids;
@@ -1555,10 +1526,15 @@ CdlpResult algo_cdlp(const Graph& g, const std::vector<std::string>& labels, con
 }
 
 // ---- algo.HarmonicCentrality ----------------------------------------------------------------------------
+// algo.HarmonicCentrality and algo.MSF refuse an unknown relationship type, the first one listed, before anything else
+static void require_types(const Graph& g, const std::vector<std::string>& types) {
+    for (auto& t : types)
+        if (!g.type_id(t)) throw std::invalid_argument("Relationship type '" + t + "' does not exist");
+}
+
 HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::string>& labels,
                                         const std::vector<std::string>& types) {
-    for (auto& t : types)                                                // before the empty-graph exit (:2648-2652)
-        if (!g.type_id(t)) throw std::invalid_argument("Relationship type '" + t + "' does not exist");
+    require_types(g, types);                                             // before the empty-graph exit (:2648-2652)
     HarmonicResult res;
     const u64 n = g.node_cap();
     if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:2654-2656)
@@ -1591,12 +1567,7 @@ HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::s
 // ---- algo.MSF -------------------------------------------------------------------------------------------
 MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types, bool maximize,
                    const u64* edge_ids, const double* weights, u64 n_weights) {
-    std::vector<u64> tids;
-    for (auto& t : types) {                                              // before the empty-graph exit (:1287-1295)
-        const auto tid = g.type_id(t);
-        if (!tid) throw std::invalid_argument("Relationship type '" + t + "' does not exist");
-        tids.push_back(*tid);
-    }
+    require_types(g, types);                                             // before the empty-graph exit (:1287-1295)
     MsfResult res;
     const u64 n = g.node_cap();
     if (g.live_nodes() == 0) return res;                                 // node_count() == 0 (:1323-1325)
@@ -1604,8 +1575,7 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
     // renumbers them 0..k-1; here they are an induced subgraph, and the order of the ids — all the forest depends on — is kept
     const NodeSelection sel = labels.empty() ? select_live_nodes(g) : select_nodes(g, labels);
     if (sel.count == 0) return res;
-    if (types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
+    const std::vector<u64> tids = scanned_type_ids(g, types);
     // the score of a relationship (msf_score, :143-165)
     const bool unit = edge_ids == nullptr;
     std::unordered_map<u64, double> attr;
@@ -1784,17 +1754,13 @@ MaxFlowResult algo_maxflow(const Graph& g, const std::vector<std::string>& label
 
 // ---- algo.SPpaths / algo.SSpaths ------------------------------------------------------------------------
 namespace {
-// the tensors a relTypes list selects: none named = every tensor, else the known names in the order listed (graph.rs:1803-1810);
-// `once` drops a repeated name (one matrix entry per pair either way), the enumeration keeps it: its successors come twice
-std::vector<u64> path_tids(const Graph& g, const std::vector<std::string>& types, bool once) {
-    std::vector<u64> tids;
-    if (types.empty())
-        for (u64 t = 0; t < g.relationship_tensors().size(); ++t) tids.push_back(t);
-    else
-        for (auto& t : types)
-            if (auto id = g.type_id(t))
-                if (!once || std::find(tids.begin(), tids.end(), *id) == tids.end()) tids.push_back(*id);
-    return tids;
+// the tensors a relTypes list selects are scanned_type_ids; the enumeration keeps a repeated name — its successors come twice —
+// and the weight matrices, one entry per pair either way, take each tensor once
+std::vector<u64> each_once(const std::vector<u64>& tids) {
+    std::vector<u64> out;
+    for (u64 t : tids)
+        if (std::find(out.begin(), out.end(), t) == out.end()) out.push_back(t);
+    return out;
 }
 
 // weightProp / costProp as data: edge_numeric_attr (:2049-2062)
@@ -1891,7 +1857,7 @@ SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::ve
     if (source == target) return res;                                    // :2559-2567
     if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return res;
     const PathAttrs at(w_edge_ids, w_vals, n_w, c_edge_ids, c_vals, n_c);
-    const PairWeights best = pair_weights(g, path_tids(g, types, true), dir, at);
+    const PairWeights best = pair_weights(g, each_once(scanned_type_ids(g, types)), dir, at);
     Matrix w = pair_matrix(g, best, at.unit, n);
     std::vector<double> dist(n);
     std::vector<int64_t> parent(n);
@@ -1971,7 +1937,7 @@ std::vector<PathRow> enumerate_paths(const Graph& g, u64 source, std::optional<u
                                      const PathTable* table, double bound, PathEnumStats& st) {
     struct Succ { u64 edge, far; };
     struct Live { u64 edge; double weight, cost; };                      // the PREFIX sums up to and including this edge
-    const std::vector<u64> tids = path_tids(g, q.types, false);
+    const std::vector<u64> tids = scanned_type_ids(g, q.types);
     const bool with_out = q.dir != Direction::Incoming, with_in = q.dir != Direction::Outgoing;
     auto successors = [&](u64 node) {                                    // node_successors (:2098-2109)
         std::vector<Succ> out;
@@ -2034,7 +2000,7 @@ std::vector<PathRow> enumerate_paths(const Graph& g, u64 source, std::optional<u
 
 // bfs_find_bound's answer (:2267-2320) without its weight: is there a route source -> target of at most maxLen arcs?
 bool reachable_within(const Graph& g, u64 source, u64 target, const PathQuery& q) {
-    const std::vector<u64> tids = path_tids(g, q.types, false);
+    const std::vector<u64> tids = scanned_type_ids(g, q.types);
     const bool with_out = q.dir != Direction::Incoming, with_in = q.dir != Direction::Outgoing;
     std::vector<uint8_t> seen(g.node_cap(), 0);
     std::vector<u64> frontier{source}, next;
@@ -2073,7 +2039,7 @@ std::vector<PathRow> algo_sp_paths_rows(const Graph& g, u64 source, u64 target, 
     }
     const u64 n = g.node_cap();
     const PathAttrs at(q.w_edge_ids, q.w_vals, q.n_w, q.c_edge_ids, q.c_vals, q.n_c);
-    const std::vector<u64> once = path_tids(g, q.types, true);
+    const std::vector<u64> once = each_once(scanned_type_ids(g, q.types));
     refuse_negative_weights(g, once, at, "algo.SPpaths");                // (pruning or not, whatever the nodes are)
     if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return {};
     if (source == target) return {};         // bfs_find_bound never "finds" the source it starts from: None (:2278-2279)
@@ -2120,7 +2086,7 @@ std::vector<PathRow> algo_ss_paths(const Graph& g, u64 source, const PathQuery& 
     st = PathEnumStats();
     check_path_count(q);
     const PathAttrs at(q.w_edge_ids, q.w_vals, q.n_w, q.c_edge_ids, q.c_vals, q.n_c);
-    refuse_negative_weights(g, path_tids(g, q.types, true), at, "algo.SSpaths");
+    refuse_negative_weights(g, each_once(scanned_type_ids(g, q.types)), at, "algo.SSpaths");
     if (source >= g.node_cap() || g.is_node_deleted(source)) return {};
     return enumerate_paths(g, source, std::nullopt, q, at, nullptr, std::numeric_limits<double>::infinity(), st);
 }

@@ -697,6 +697,7 @@ struct CondTraverseOp {
     struct EdgeRows {
         std::vector<u64> row, from, to, edge;
         size_t size() const { return row.size(); }
+        void push(u64 r, u64 f, u64 t, u64 e) { row.push_back(r); from.push_back(f); to.push_back(t); edge.push_back(e); }
         void clear() { row.clear(); from.clear(); to.clear(); edge.clear(); }
     };
     // expand_row for a whole input batch with ONE fgpu_expand_edges: types and labels resolved as expand_row resolves them; the

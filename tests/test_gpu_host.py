@@ -840,6 +840,7 @@ CASES = [
     dict(types=["Nope", "Nada"], src_labels=[], dst_labels=[], chain=[], optional=True),   # no known type: no_match
     dict(types=["A"], src_labels=[], dst_labels=[], chain=[(["Nope", "B"], [])]),      # the same in a fused hop
     dict(types=["B", "Nope"], src_labels=[], dst_labels=[], chain=[], bind=True),      # representative edge scan skips unknowns
+    dict(types=["A", "A"], src_labels=[], dst_labels=[], chain=[], bind=True),         # a name listed twice is scanned twice
 ]
 
 
@@ -1001,6 +1002,8 @@ ROW_CASES = [
     dict(types=[], emit=False, bidir=True, from_labels=["P"], to_labels=["Q"]),
     dict(types=["A", "B"], emit=True, bidir=True, to_labels=["P"]),
     dict(types=["A", "Nope"], emit=False),                       # an alternation drops its unknown names
+    dict(types=["A", "A"], emit=True),                           # a name listed twice stays twice: its ids come twice
+    dict(types=["A", "A"], emit=False, bidir=True),
     dict(types=["Nope"], emit=True),                             # a single unknown type: no rows
     dict(types=["Nope", "Nada"], emit=True, bidir=True),         # an alternation with no known type: no rows
     dict(types=["B"], emit=True, transposed=True, from_labels=["Q"]),

@@ -155,18 +155,28 @@ def test_full_matrix_rows_are_spliced_in(twin):
                                   dict(types=[], emit=False, bidir=True, from_labels=["P"]),
                                   dict(types=["B"], emit=True, transposed=True, to_labels=["Q"]),
                                   dict(types=["A", "B"], emit=False, siblings=True),
-                                  dict(types=["Nope"], emit=True), dict(types=["A", "Nope"], emit=True)], ids=str)
+                                  dict(types=["Nope"], emit=True), dict(types=["A", "Nope"], emit=True),
+                                  dict(types=["Nope", "A"], emit=True),                  # the unknown name first
+                                  dict(types=["A", "A"], emit=True),                     # a name listed twice stays twice
+                                  dict(types=["A", "A"], emit=False, bidir=True),
+                                  dict(types=["Nope", "Nada"], emit=True, optional=True)], ids=str)
 def test_batch_equals_the_per_row_path(twin, case):
     tw, og = twin
     rows = batch_rows(tw)[:40] + [("x", None)]
     f, t = [r[0] for r in rows], [r[1] for r in rows]
     used = sorted(e for pt in tw.per_type for es in list(pt.values())[::3] for e in es[:1]) if case.get("siblings") else []
     spec = host.cond_spec(src_labels=case.get("from_labels", []), hops=[(case["types"], case.get("to_labels", []))],
-                          emit=case["emit"], bidir=case.get("bidir", False), siblings=case.get("siblings", False))
+                          emit=case["emit"], bidir=case.get("bidir", False), siblings=case.get("siblings", False),
+                          optional=case.get("optional", False))
     tr = case.get("transposed", False)
-    got, _, _ = tw.g.cond_traverse_edges_batch(spec, f, t, transposed=tr, used_edges=[used] * len(rows) if used else None)
+    got, nulls, _ = tw.g.cond_traverse_edges_batch(spec, f, t, transposed=tr, used_edges=[used] * len(rows) if used else None)
     assert got == tw.g.cond_traverse_rows(spec, f, t, transposed=tr, used_edges=used)
-    if "Nope" not in case["types"]:
+    if case["types"] == ["A", "A"] and case["emit"]:
+        single = host.cond_spec(hops=[(["A"], [])], emit=True)
+        assert sorted(got) == sorted(2 * tw.g.cond_traverse_rows(single, f, t))           # every id of A, twice
+    if case.get("optional"):
+        assert got == [] and nulls == list(range(len(rows)))                             # no known type: every row null-pads
+    elif "Nope" not in case["types"]:
         assert len(got) > 20
 
 

@@ -62,6 +62,12 @@ def test_batch_equals_the_rows_one_by_one(hctx, seed, commit):
         assert g.var_len_traverse_batch(starts, **args)[0] == per_row(g, starts, **args)[0] == oracle_rows(og, starts, **args)
         args = dict(types=["LIKES", "NOPE"], max_hops=2, **kw)                       # an unknown type is dropped
         assert g.var_len_traverse_batch(starts, **args)[0] == per_row(g, starts, **args)[0]
+        args = dict(types=["NOPE", "LIKES"], max_hops=2, **kw)                       # the unknown name first
+        assert g.var_len_traverse_batch(starts, **args)[0] == per_row(g, starts, **args)[0] == oracle_rows(og, starts, **args)
+        args = dict(types=["KNOWS", "KNOWS"], max_hops=2, emit_path=True, **kw)      # a name listed twice is walked twice
+        got = g.var_len_traverse_batch(starts, **args)[0]
+        assert got == per_row(g, starts, **args)[0] == oracle_rows(og, starts, **args)
+        assert len(got) > len(g.var_len_traverse_batch(starts, **dict(args, types=["KNOWS"]))[0])
         got, st = g.var_len_traverse_batch(starts, types=["NOPE"], min_hops=0, max_hops=2, **kw)   # none resolvable: the 0-hop rows
         assert got == [(i, s, s, None) for i, s in enumerate(starts)] and st["device_calls"] == 1
         got, st = g.var_len_traverse_batch(starts, max_hops=2, dst_labels=["MISSING"], **kw)
