@@ -99,6 +99,8 @@ SIGNATURES = {
     "fgpu_expand_trails": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, C.c_uint32,
                                        C.c_uint32, u64p, C.c_uint64, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p),
                                        C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u32p), C.POINTER(u64p), u64p, u64p]),
+    "fgpu_pair_weights": (C.c_int32, [vp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, u64p, u64p, C.POINTER(C.c_double), C.c_uint64,
+                                      C.c_double, vpp, vpp, u64p, u64p]),
     "fgpu_expand_levels": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fgpu_expand_trail_counts": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, C.c_int, C.POINTER(u64p),
                                              C.POINTER(u64p), C.POINTER(u64p), u64p]),

@@ -291,6 +291,44 @@ class Context:
             cols += [off, self._take(pnode, total + n.value, np.uint32), self._take(pedge, max(total, 1) if n.value else 0, U64)[:total]]
         return (*cols, [int(x) for x in st])
 
+    # ---- the algorithms' weighted pair matrix (pair_weights.hip) ----
+    def pair_weights(self, m, dp=None, dm=None, multi=None, *, out=True, inc=False, negate=False, drop_nonfinite=False,
+                     refuse_negative=False, active_bitmap=None, attr_ids=None, attr_vals=None, missing=1.0, want_w=True,
+                     want_k=True):
+        """fgpu_pair_weights: per ordered node pair the smallest weight over the relationship types m .. multi (one entry per
+        type, as for expand_edges), their multi-edges and the direction (out / inc), and the relationship kept.  attr_ids
+        (strictly ascending) / attr_vals: the weight attribute, an id that is not listed weighs `missing`; attr_ids None: every
+        relationship weighs 1.0 and W is a BOOL pattern.  Returns (W, K, stats): two Mats of one pattern (None where want_w /
+        want_k is False) and the eight stats of fgpu.h.  A refused negative weight raises FgpuError with the smallest refused
+        relationship id in its `refused_id`."""
+        T = len(m)
+        arrs = [_hop_arrays(x) if x is not None else None for x in (m, dp, dm, multi)]
+        assert all(a is None or len(a) == T for a in arrs)
+        act = _u64(active_bitmap) if active_bitmap is not None else None
+        ids = vals = None
+        n_attr = 0
+        if attr_ids is not None:
+            ids = _u64(attr_ids).reshape(-1)
+            n_attr = len(ids)
+            vals = np.ascontiguousarray(attr_vals, dtype=np.float64).reshape(-1)
+            assert len(ids) == len(vals)
+            if len(ids) == 0:   # (a list of nothing is still a list: keep the pointer non-NULL)
+                ids, vals = np.zeros(1, dtype=U64), np.zeros(1, dtype=np.float64)
+        flags = ((1 if out else 0) | (2 if inc else 0) | (4 if negate else 0) | (8 if drop_nonfinite else 0) |
+                 (16 if refuse_negative else 0))
+        w, k = C.c_void_p(), C.c_void_p()
+        refused = C.c_uint64((1 << 64) - 1)
+        st = (C.c_uint64 * 8)()
+        code = self.lib.fgpu_pair_weights(self._h, *arrs, T, flags, _p(act), _p(ids), _p(vals, C.POINTER(C.c_double)),
+                                          n_attr, float(missing),
+                                          C.byref(w) if want_w else None, C.byref(k) if want_k else None, C.byref(refused), st)
+        try:
+            check(code)
+        except _ffi.FgpuError as e:
+            e.refused_id = None if refused.value == (1 << 64) - 1 else int(refused.value)
+            raise
+        return (Mat(self, w) if want_w else None, Mat(self, k) if want_k else None, [int(x) for x in st])
+
 
 class Mat:
     """fgpu_mat: immutable device snapshot of one matrix layer."""

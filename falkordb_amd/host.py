@@ -55,6 +55,14 @@ def load():
     return _lib
 
 
+def _attr_arrays(attr):
+    """an attribute as the C API takes it, (ids uint64[], values float64[]): a {relationship id: number} dict, or a sequence of
+    (relationship id, number) pairs in any order — of a repeated id the last pair stands"""
+    pairs = list(attr.items()) if hasattr(attr, "items") else list(attr)
+    return (np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.uint64),
+            np.ascontiguousarray([float(v) for _, v in pairs], dtype=np.float64))
+
+
 def _ck(code, allow=(0,)):
     if code not in allow:
         raise HostError(code, (load().fh_last_error() or b"").decode())
@@ -765,8 +773,7 @@ class Graph:
         fh_algo_msf).  An unknown relationship type is an error."""
         ids = wts = None
         if weights is not None:
-            ids = np.ascontiguousarray(list(weights.keys()), dtype=np.uint64)
-            wts = np.ascontiguousarray([float(x) for x in weights.values()], dtype=np.float64)
+            ids, wts = _attr_arrays(weights)
         nt = C.c_uint64()
         noff, nodes, eoff, edges = u64p(), u64p(), u64p(), u64p()
         _ck(self.L.fh_algo_msf(self.h, ",".join(labels).encode(), ",".join(types).encode(), C.c_int(1 if maximize else 0),
@@ -778,6 +785,13 @@ class Graph:
         no, eo = _take(noff, t + 1), _take(eoff, t + 1)
         nv, ev = _take(nodes, int(no[-1])), _take(edges, int(eo[-1]))
         return [(nv[int(no[i]):int(no[i + 1])], ev[int(eo[i]):int(eo[i + 1])]) for i in range(t)]
+
+    def pair_stats(self):
+        """The eight stats of the last fgpu_pair_weights call algo_msf / algo_sp_paths / algo_sp_paths_rows made on this graph
+        (fh_graph_pair_stats): [2] candidates and [3] pairs of the weight matrix the device built."""
+        st = (C.c_uint64 * 8)()
+        _ck(self.L.fh_graph_pair_stats(self.h, st))
+        return [int(x) for x in st]
 
     def algo_maxflow(self, sources, targets, types, capacities=None, default_capacity=None, labels=(), attribute_exists=None):
         """CALL algo.maxFlow({sourceNodes, targetNodes, relationshipTypes, capacityProperty, defaultCapacity, nodeLabels})
@@ -814,8 +828,7 @@ class Graph:
         def attr(d):
             if d is None:
                 return None, None, 0
-            ids = np.ascontiguousarray(list(d.keys()), dtype=np.uint64)
-            vals = np.ascontiguousarray([float(x) for x in d.values()], dtype=np.float64)
+            ids, vals = _attr_arrays(d)
             return ids.ctypes.data_as(u64p), vals.ctypes.data_as(C.POINTER(C.c_double)), len(ids), (ids, vals)
         w, c = attr(weights), attr(costs)
         found = C.c_int()
@@ -836,8 +849,7 @@ class Graph:
         def attr(d):
             if d is None:
                 return None, None, 0
-            ids = np.ascontiguousarray(list(d.keys()), dtype=np.uint64)
-            vals = np.ascontiguousarray([float(x) for x in d.values()], dtype=np.float64)
+            ids, vals = _attr_arrays(d)
             return ids.ctypes.data_as(u64p), vals.ctypes.data_as(C.POINTER(C.c_double)), len(ids), (ids, vals)
         w, c = attr(weights), attr(costs)
         n = C.c_uint64()

@@ -991,6 +991,15 @@ int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize
     });
 }
 
+// the eight stats of the last fgpu_pair_weights call an algorithm made on g (fgpu.h), all 0 before the first
+int fh_graph_pair_stats(fh_graph* g, uint64_t stats[8]) {
+    return guard([&] {
+        const std::array<u64, 8> st = g->g.pair_stats();
+        std::copy(st.begin(), st.end(), stats);
+        return 0;
+    });
+}
+
 // algo.maxFlow: labels / types = comma lists; the capacity attribute as (edge_ids[k], caps[k])
 int fh_algo_maxflow(fh_graph* g, const char* labels, const char* types, const uint64_t* sources, uint64_t n_sources,
                     const uint64_t* targets, uint64_t n_targets, int has_attribute, const uint64_t* edge_ids, const double* caps,

@@ -1564,6 +1564,85 @@ HarmonicResult algo_harmonic_centrality(const Graph& g, const std::vector<std::s
     return res;
 }
 
+// ---- the algorithms' weighted pair matrix (fgpu_pair_weights) ---------------------------------------------
+namespace {
+// An attribute list (edge_ids[k], vals[k]) in any order as fgpu_pair_weights takes it: the ids strictly ascending.  Of equal ids
+// the last one stands, which is what assigning them to a map in turn gave.  A list that ascends already is passed through.
+struct AttrList {
+    const u64* ids = nullptr;   // nullptr: no such attribute, every relationship weighs 1.0
+    const double* vals = nullptr;
+    u64 n = 0;
+    std::vector<u64> own_ids;
+    std::vector<double> own_vals;
+    AttrList(const u64* edge_ids, const double* v, u64 count) {
+        static const u64 no_id = 0;
+        static const double no_val = 0.0;
+        if (!edge_ids) return;
+        ids = &no_id; vals = &no_val;                                    // (a list of nothing is still a list)
+        if (count == 0) return;
+        bool ascending = true;
+        for (u64 k = 1; k < count && ascending; ++k) ascending = edge_ids[k - 1] < edge_ids[k];
+        if (ascending) { ids = edge_ids; vals = v; n = count; return; }
+        std::vector<u64> order(count);
+        for (u64 k = 0; k < count; ++k) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](u64 a, u64 b) { return edge_ids[a] < edge_ids[b]; });
+        own_ids.reserve(count); own_vals.reserve(count);
+        for (u64 k = 0; k < count; ++k) {
+            if (k + 1 < count && edge_ids[order[k + 1]] == edge_ids[order[k]]) continue;   // a later one of the same id follows
+            own_ids.push_back(edge_ids[order[k]]);
+            own_vals.push_back(v[order[k]]);
+        }
+        ids = own_ids.data(); vals = own_vals.data(); n = own_ids.size();
+    }
+};
+
+// W (weights, or the BOOL pattern without an attribute) and K (the kept relationship per pair) over the tensors' own layers
+struct PairMatrices {
+    SnapshotRef w, k;
+    std::optional<Matrix> none;   // no tensor is selected: one empty n x n matrix stands for both
+    const fgpu_mat* W() const { return none ? none->snapshot() : w.get(); }
+    const fgpu_mat* K() const { return none ? none->snapshot() : k.get(); }
+};
+PairMatrices device_pair_weights(const Graph& g, const std::vector<u64>& tids, int flags, const u64* active, const AttrList& attr,
+                                 double missing, const char* who, bool want_k = true) {
+    PairMatrices out;
+    u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (tids.empty()) {
+        out.none.emplace(g.ctx(), attr.ids ? Type::UInt64 : Type::Bool, g.node_cap(), g.node_cap());
+        g.set_pair_stats(stats);
+        return out;
+    }
+    std::vector<const fgpu_mat*> m, dp, dm;
+    std::vector<const fgpu_multi*> multi;
+    for (u64 t : tids) {
+        const Tensor& ten = g.relationship_tensors()[t];
+        ten.wait_fwd();
+        const Layers f = fwd_layers(ten);
+        m.push_back(f.m); dp.push_back(f.dp); dm.push_back(f.dm);
+        multi.push_back(ten.multi_table());
+    }
+    u64 refused = ~0ull;
+    const fgpu_info info = fgpu_pair_weights(g.ctx().raw(), m.data(), dp.data(), dm.data(), multi.data(), (int)tids.size(), flags, active,
+                                             attr.ids, attr.vals, attr.n, missing, out.w.out(), want_k ? out.k.out() : nullptr, &refused, stats);
+    g.set_pair_stats(stats);
+    if (info == FGPU_INVALID && refused != ~0ull)
+        throw std::invalid_argument(std::string(who) + ": relationship " + std::to_string(refused) + " has a negative weight");
+    check(info, who);
+    return out;
+}
+
+// the kept relationship of every (rows[i], cols[i]), i < n: one batched probe of K
+std::vector<u64> kept_relationships(const Graph& g, const fgpu_mat* K, const u64* rows, const u64* cols, u64 n, const char* who) {
+    std::vector<u64> kept(n);
+    if (n == 0) return kept;
+    std::vector<uint8_t> present(n);
+    check(fgpu_mat_probe(g.ctx().raw(), K, rows, cols, n, present.data(), kept.data()), who);
+    for (u64 i = 0; i < n; ++i)
+        if (!present[i]) throw std::runtime_error(std::string(who) + ": a chosen pair has no kept relationship");
+    return kept;
+}
+}  // namespace
+
 // ---- algo.MSF -------------------------------------------------------------------------------------------
 MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const std::vector<std::string>& types, bool maximize,
                    const u64* edge_ids, const double* weights, u64 n_weights) {
@@ -1576,49 +1655,16 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
     const NodeSelection sel = labels.empty() ? select_live_nodes(g) : select_nodes(g, labels);
     if (sel.count == 0) return res;
     const std::vector<u64> tids = scanned_type_ids(g, types);
-    // the score of a relationship (msf_score, :143-165)
-    const bool unit = edge_ids == nullptr;
-    std::unordered_map<u64, double> attr;
-    if (!unit) {
-        attr.reserve(n_weights * 2);
-        for (u64 k = 0; k < n_weights; ++k) attr[edge_ids[k]] = weights[k];
-    }
-    auto score_of = [&](u64 edge) {
-        if (unit) return 1.0;
-        const auto it = attr.find(edge);
-        if (it == attr.end()) return std::numeric_limits<double>::infinity();   // (-inf negated under maximize)
-        return maximize ? -it->second : it->second;
-    };
-    // one (score, relationship) per unordered pair: over the selected tensors' effective edges, multi-edges included, both
-    // directions folded together (msf_keep_min_score, :237-255)
-    struct Scored { double score; u64 edge; };
-    std::unordered_map<u64, Scored> best;
-    for (u64 t : tids) {
-        for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
-            if (e.row == e.col || !sel.has(e.row) || !sel.has(e.col)) continue;
-            const u64 lo = e.row < e.col ? e.row : e.col, hi = e.row < e.col ? e.col : e.row;
-            const Scored y{score_of(e.val), e.val};
-            auto [it, fresh] = best.try_emplace((lo << 32) | hi, y);
-            if (fresh) continue;
-            Scored& x = it->second;
-            if (y.score < x.score || (y.score == x.score && y.edge < x.edge)) x = y;
-        }
-    }
-    // the symmetric weighted matrix, one binary64 bit pattern per entry (weighted_adj, :1690-1704)
-    std::vector<u64> rows, cols, bits;
-    rows.reserve(2 * best.size()); cols.reserve(2 * best.size()); bits.reserve(2 * best.size());
-    for (auto& kv : best) {
-        const u64 lo = kv.first >> 32, hi = kv.first & 0xFFFFFFFFull;
-        u64 b;
-        memcpy(&b, &kv.second.score, sizeof b);
-        rows.push_back(lo); cols.push_back(hi); bits.push_back(b);
-        rows.push_back(hi); cols.push_back(lo); bits.push_back(b);
-    }
-    Matrix w(g.ctx(), Type::UInt64, n, n);
-    if (!rows.empty()) w.build(rows, cols, &bits);
+    // One (score, relationship) per unordered pair, on the device: the score of a relationship is msf_score (:143-165) — 1.0
+    // without a weight attribute, +inf when it has none (under either objective), negated under maximize — over the selected
+    // tensors' effective edges, multi-edges included, both directions folded together, ties to the smallest id
+    // (msf_keep_min_score, :237-255).  W is the symmetric weighted matrix of weighted_adj (:1690-1704), BOOL in the unit case.
+    const AttrList attr(edge_ids, weights, n_weights);
+    const PairMatrices pm = device_pair_weights(g, tids, FGPU_PAIRS_OUT | FGPU_PAIRS_IN | (maximize ? FGPU_PAIRS_NEGATE : 0),
+                                                sel.bits.data(), attr, std::numeric_limits<double>::infinity(), "algo.MSF");
     std::vector<int64_t> comp(n);
     EdgeList forest(g.ctx());
-    msf(g.ctx(), w.snapshot(), sel.bits.data(), comp.data(), forest);
+    msf(g.ctx(), pm.W(), sel.bits.data(), comp.data(), forest);
     // trees in ascending order of their smallest node id = their component label (:1778-1848)
     std::vector<int64_t> tree_of(n, -1);
     for (u64 v = 0; v < n; ++v) {
@@ -1630,9 +1676,8 @@ MsfResult algo_msf(const Graph& g, const std::vector<std::string>& labels, const
         }
         res.tree_nodes[(size_t)tree_of[(size_t)comp[v]]].push_back(v);   // (comp[v] <= v: its tree exists already)
     }
-    for (u64 i = 0; i < forest.n; ++i)
-        res.tree_edges[(size_t)tree_of[(size_t)comp[forest.rows[i]]]].push_back(
-            best.at((forest.rows[i] << 32) | forest.cols[i]).edge);
+    const std::vector<u64> kept = kept_relationships(g, pm.K(), forest.rows.p, forest.cols.p, forest.n, "algo.MSF");
+    for (u64 i = 0; i < forest.n; ++i) res.tree_edges[(size_t)tree_of[(size_t)comp[forest.rows[i]]]].push_back(kept[i]);
     return res;
 }
 
@@ -1789,36 +1834,17 @@ struct PathAttrs {
     }
 };
 
-// one (weight, relationship) per ordered pair (from << 32 | to) in traversal direction: the smallest weight over the selected
-// tensors and their multi-edges, ties to the smallest id; self-loops and non-finite weights left out, a negative weight throws
-struct PairKept { double w; u64 edge; };
-using PairWeights = std::unordered_map<u64, PairKept>;
-PairWeights pair_weights(const Graph& g, const std::vector<u64>& tids, Direction dir, const PathAttrs& at,
-                         const char* who = "algo.SPpaths") {
-    PairWeights best;
-    auto offer = [&](u64 from, u64 to, const PairKept& y) {
-        auto [it, fresh] = best.try_emplace((from << 32) | to, y);
-        if (fresh) return;
-        PairKept& x = it->second;
-        if (y.w < x.w || (y.w == x.w && y.edge < x.edge)) x = y;
-    };
-    for (u64 t : tids) {
-        for (const Entry& e : g.relationship_tensors()[t].iter_edges()) {
-            if (e.row == e.col) continue;
-            double w = at.weight(e.val);
-            if (!std::isfinite(w)) continue;                             // never relaxed (:2213)
-            if (w < 0.0)
-                throw std::invalid_argument(std::string(who) + ": relationship " + std::to_string(e.val) + " has a negative weight");
-            if (w == 0.0) w = 0.0;                                       // (-0.0)
-            const PairKept y{w, e.val};
-            if (dir != Direction::Incoming) offer(e.row, e.col, y);
-            if (dir != Direction::Outgoing) offer(e.col, e.row, y);
-        }
-    }
-    return best;
+// The weight matrix of a search in traversal direction `dir`, on the device: one (weight, relationship) per ordered pair
+// (from, to), the smallest weight over the selected tensors and their multi-edges, ties to the smallest id; self-loops and
+// non-finite weights (never relaxed, :2213) left out, an unlisted relationship weighs 1.0, a negative weight throws
+PairMatrices path_pair_weights(const Graph& g, const std::vector<u64>& tids, Direction dir, const AttrList& weight, bool want_k = true,
+                               const char* who = "algo.SPpaths") {
+    const int flags = (dir != Direction::Incoming ? FGPU_PAIRS_OUT : 0) | (dir != Direction::Outgoing ? FGPU_PAIRS_IN : 0) |
+                      FGPU_PAIRS_DROP_NONFINITE | FGPU_PAIRS_REFUSE_NEGATIVE;
+    return device_pair_weights(g, tids, flags, nullptr, weight, 1.0, who, want_k);
 }
 
-// pair_weights' refusal alone, for the walks that need no matrix: the same relationships, the same message
+// path_pair_weights' refusal alone, for the walks that need no matrix: the same relationships, the same message
 void refuse_negative_weights(const Graph& g, const std::vector<u64>& tids, const PathAttrs& at, const char* who) {
     if (at.unit) return;
     for (u64 t : tids)
@@ -1830,23 +1856,6 @@ void refuse_negative_weights(const Graph& g, const std::vector<u64>& tids, const
         }
 }
 
-// ... as the n x n matrix the device searches: BOOL without weightProp, binary64 bit patterns otherwise
-Matrix pair_matrix(const Graph& g, const PairWeights& best, bool unit, u64 n) {
-    std::vector<u64> rows, cols, bits;
-    rows.reserve(best.size()); cols.reserve(best.size());
-    if (!unit) bits.reserve(best.size());
-    for (auto& kv : best) {
-        rows.push_back(kv.first >> 32); cols.push_back(kv.first & 0xFFFFFFFFull);
-        if (!unit) {
-            u64 b;
-            memcpy(&b, &kv.second.w, sizeof b);
-            bits.push_back(b);
-        }
-    }
-    Matrix w(g.ctx(), unit ? Type::Bool : Type::UInt64, n, n);
-    if (!rows.empty()) w.build(rows, cols, unit ? nullptr : &bits);
-    return w;
-}
 }  // namespace
 
 SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::vector<std::string>& types, Direction dir,
@@ -1856,12 +1865,11 @@ SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::ve
     const u64 n = g.node_cap();
     if (source == target) return res;                                    // :2559-2567
     if (source >= n || target >= n || g.is_node_deleted(source) || g.is_node_deleted(target)) return res;
-    const PathAttrs at(w_edge_ids, w_vals, n_w, c_edge_ids, c_vals, n_c);
-    const PairWeights best = pair_weights(g, each_once(scanned_type_ids(g, types)), dir, at);
-    Matrix w = pair_matrix(g, best, at.unit, n);
+    const PathAttrs at(nullptr, nullptr, 0, c_edge_ids, c_vals, n_c);   // (the costs alone: the weights stay a list for the device)
+    const PairMatrices pm = path_pair_weights(g, each_once(scanned_type_ids(g, types)), dir, AttrList(w_edge_ids, w_vals, n_w));
     std::vector<double> dist(n);
     std::vector<int64_t> parent(n);
-    sssp(g.ctx(), w.snapshot(), source, dist.data(), parent.data());
+    sssp(g.ctx(), pm.W(), source, dist.data(), parent.data());
     if (!std::isfinite(dist[target])) return res;
     res.found = true;
     res.weight = dist[target];
@@ -1872,11 +1880,8 @@ SpPathResult algo_sp_paths(const Graph& g, u64 source, u64 target, const std::ve
     }
     res.nodes.push_back(source);
     std::reverse(res.nodes.begin(), res.nodes.end());
-    for (size_t k = 0; k + 1 < res.nodes.size(); ++k) {                  // :2250-2254
-        const u64 edge = best.at((res.nodes[k] << 32) | res.nodes[k + 1]).edge;
-        res.edges.push_back(edge);
-        res.cost += at.cost(edge);
-    }
+    res.edges = kept_relationships(g, pm.K(), res.nodes.data(), res.nodes.data() + 1, res.nodes.size() - 1, "algo.SPpaths");
+    for (u64 edge : res.edges) res.cost += at.cost(edge);               // :2250-2254
     return res;
 }
 
@@ -2051,19 +2056,19 @@ std::vector<PathRow> algo_sp_paths_rows(const Graph& g, u64 source, u64 target, 
         return enumerate_paths(g, source, target, q, at, nullptr, inf, st);
     }
     const Direction rev = q.dir == Direction::Outgoing ? Direction::Incoming : q.dir == Direction::Incoming ? Direction::Outgoing : Direction::Both;
-    Matrix wrev = pair_matrix(g, pair_weights(g, once, rev, at), at.unit, n);
+    const PairMatrices wrev = path_pair_weights(g, once, rev, AttrList(q.w_edge_ids, q.w_vals, q.n_w), false);   // (the table needs no K)
     PathTable table;
     table.n = n;
     const bool hop_table = q.max_len <= (uint32_t)FGPU_SSSP_HOPS_MAX && ((u64)q.max_len + 1) * n * sizeof(double) <= (1ull << 30);
     if (hop_table) {
         table.rows = q.max_len + 1;
         table.d.resize((size_t)table.rows * n);
-        sssp_hops(g.ctx(), wrev.snapshot(), target, (int32_t)q.max_len, table.d.data());
+        sssp_hops(g.ctx(), wrev.W(), target, (int32_t)q.max_len, table.d.data());
         st.table_rows = (int32_t)table.rows;
     } else {
         table.rows = 1;
         table.d.resize(n);
-        sssp(g.ctx(), wrev.snapshot(), target, table.d.data(), nullptr);
+        sssp(g.ctx(), wrev.W(), target, table.d.data(), nullptr);
         st.table_rows = 0;
     }
     const u64 m = std::min<u64>(q.max_len, n - 1) + 1;

@@ -617,6 +617,20 @@ class Graph {
     };
     static void register_gang_cache(const std::shared_ptr<BfsGangCache>& c);   // (matrix.cpp, next to Context::~Context)
     mutable std::shared_ptr<BfsGangCache> bfs_gang_cache_;
+    // the eight stats of the last fgpu_pair_weights call an algorithm made on this graph (algo_msf, algo_sp_paths and the
+    // pruning table of algo_sp_paths_rows build their weight matrix with it); all 0 before the first
+    mutable std::array<u64, 8> pair_stats_{};
+    mutable std::mutex pair_stats_mu_;
+
+   public:
+    std::array<u64, 8> pair_stats() const {
+        std::lock_guard<std::mutex> lock(pair_stats_mu_);
+        return pair_stats_;
+    }
+    void set_pair_stats(const u64* stats) const {
+        std::lock_guard<std::mutex> lock(pair_stats_mu_);
+        std::copy(stats, stats + 8, pair_stats_.begin());
+    }
 };
 
 // A bound value of one batch row, reduced to what the traversal operators inspect.

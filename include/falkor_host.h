@@ -353,6 +353,13 @@ int fh_algo_msf(fh_graph* g, const char* labels, const char* types, int maximize
                 uint64_t n_weights, uint64_t* n_trees, uint64_t** node_off, uint64_t** nodes, uint64_t** edge_off,
                 uint64_t** edges);
 
+/* fh_algo_msf, fh_algo_sp_paths and the pruning table of fh_algo_sp_paths_rows build their weight matrix on the device, with one
+ * fgpu_pair_weights over the selected tensors' own layers (fgpu.h).  stats receives the eight stats of the last such call on g:
+ * [0] stored entries examined, [1] relationships examined, [2] candidates, [3] pairs out, [4] dropped as non-finite, [5] took the
+ * default, [6] multi-edge pairs expanded, [7] most candidates of one pair; all 0 before the first call, after a call that
+ * selected no tensor, and after a refused negative weight. */
+int fh_graph_pair_stats(fh_graph* g, uint64_t stats[8]);
+
 /* algo.maxFlow (algo_procedures.rs:2786-3248; LAGr_MaxFlow through lagraphx_bindings.rs:610-618 is fgpu_maxflow, whose comment
  * in fgpu.h states what the returned flow satisfies): labels = a comma list, "" / NULL = all nodes, else a relationship counts
  * when both its ends carry one of the labels; types = exactly one relationship type.  sources / targets: the node ids of

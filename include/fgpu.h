@@ -610,6 +610,56 @@ fgpu_info fgpu_expand_trails(fgpu_ctx* ctx, const uint64_t* start, const uint64_
                              uint64_t** out_path_off, uint32_t** out_path_node, uint64_t** out_path_edge, uint64_t* out_n,
                              uint64_t stats[8]);
 
+/* The weighted pair matrix algo.MSF (algo_procedures.rs:1403-1704), algo.SPpaths (:2156-2257, :2405-2514) and the hop-bounded
+ * pruning table start from, built from the tensors' own layers in one call: per ordered node pair the smallest weight over the
+ * selected relationship types, their multi-edges and the traversal direction, and the relationship that was kept.
+ *   m / dp / dm / multi   the forward layers and multi-edge tables of n_types tensors, as for fgpu_expand_edges and under the same
+ *                   rules: all n x n with n = m[0]'s dimension < 2^32 - 1, m and dp valued, dp / dm / multi nullable (the array or
+ *                   any element), 1 to 64 types.  No transposed layer is needed.  A type given twice (the same four handles)
+ *                   changes nothing, the stats included.
+ *   Examined        per type the effective relationships of Tensor::iter_edges: every pair of (pattern(m) \ dm) U pattern(dp), dp's
+ *                   value winning over m's, FGPU_MULTI_EDGE expanding to the table's row.  Self-loops are not examined at all,
+ *                   neither is a relationship with an end outside active_bitmap (nullable, (n + 63) / 64 words): they are not
+ *                   counted and not refused.
+ *   Weight          attr_ids [n_attr] strictly ascending (checked on the device), attr_vals [n_attr].  A relationship weighs
+ *                   attr_vals[k] where attr_ids[k] equals its id (binary search); an id that is not listed - below the first,
+ *                   above the last or in a gap - weighs `missing`.  Then, in this order: FGPU_PAIRS_NEGATE negates a LISTED value
+ *                   (`missing` is not negated); -0.0 becomes +0.0; FGPU_PAIRS_DROP_NONFINITE leaves NaN and +-inf relationships
+ *                   out; FGPU_PAIRS_REFUSE_NEGATIVE fails the call on a finite weight < 0.  attr_ids == NULL: every relationship
+ *                   weighs 1.0, `missing` and NEGATE are ignored.
+ *   Direction       FGPU_PAIRS_OUT: a relationship (src, dst) is a candidate of the ordered pair (src, dst); FGPU_PAIRS_IN: of
+ *                   (dst, src); both: of both, and the result is symmetric.
+ *   Kept            per ordered pair the candidate with the smallest (key(weight), id), key the order of fgpu_msf: IEEE totalOrder
+ *                   of the binary64 bit pattern with -0.0 = +0.0.  A NaN that was not dropped is ordered by its bits.  The kept
+ *                   candidate is a function of the candidate set only; no floating-point atomic takes part.
+ *   Out             *W: n x n UINT64 of binary64 bit patterns - a BOOL pattern when attr_ids == NULL; *K: the same pattern, UINT64,
+ *                   the kept relationship id (with attr_ids == NULL the smallest id of the pair).  Ordinary snapshots with sorted
+ *                   columns, freed with fgpu_mat_free, usable by fgpu_msf / fgpu_sssp / fgpu_sssp_hops / fgpu_mat_probe as they
+ *                   are.  W == NULL or K == NULL: that matrix is not wanted.  Nothing examined gives empty n x n matrices.  The call
+ *                   keeps no device memory on its inputs.
+ * FGPU_INVALID, with fgpu_last_error set, nothing allocated, *W and *K untouched and the context still usable, for: n_types outside
+ * 1 .. 64 (with no type there is no dimension); layers that are not all n x n; an unvalued m (or dp); unknown flag bits, or neither
+ * OUT nor IN; attr_ids not strictly ascending; stored entries, relationships or candidates that reach 2^32 - 1; an examined pair
+ * that holds FGPU_MULTI_EDGE with no table row (counted on the device and read back before any output is allocated, as
+ * fgpu_expand_edges does); a refused weight - *refused_id (nullable) is then the smallest refused relationship id and
+ * fgpu_last_error reads "fgpu_pair_weights: relationship <id> has a negative weight".
+ * stats (nullable; all 0 after a failure): [0] stored entries examined (live pairs of a type), [1] relationships examined (after
+ * multi-edge expansion), [2] candidates (after the drop and the direction), [3] pairs out, [4] relationships dropped as non-finite,
+ * [5] relationships that took `missing`, [6] multi-edge pairs expanded, [7] most candidates of one pair.
+ * Work: a lane per stored entry of every m and dp (the dm / dp checks by binary search), a lane per relationship (the ids of a
+ * multi-edge row placed by a scan, the attribute by binary search), candidates placed by a scan and grouped per pair by the stable
+ * counting sorts of fgpu_edges_build, a lane per sorted position closing the runs and taking the run's minimum through integer
+ * atomicMin, row pointers off a scan; no wavefront-per-row loop. */
+#define FGPU_PAIRS_OUT 1
+#define FGPU_PAIRS_IN 2
+#define FGPU_PAIRS_NEGATE 4
+#define FGPU_PAIRS_DROP_NONFINITE 8
+#define FGPU_PAIRS_REFUSE_NEGATIVE 16
+fgpu_info fgpu_pair_weights(fgpu_ctx* ctx, const fgpu_mat* const* m, const fgpu_mat* const* dp, const fgpu_mat* const* dm,
+                            const fgpu_multi* const* multi, int n_types, int flags, const uint64_t* active_bitmap,
+                            const uint64_t* attr_ids, const double* attr_vals, uint64_t n_attr, double missing,
+                            fgpu_mat** W, fgpu_mat** K, uint64_t* refused_id, uint64_t stats[8]);
+
 /* The same chain with the result STREAMED to the host in chunks of whole source rows — the shape in which
  * CondTraverseOp::expand_batch consumes it (cond_traverse.rs:644-751: walk (row_i, dest) ascending, emit an output batch
  * every 1024 pairs): the chain runs once, F stays on the device, and chunks of at most `chunk_rows` consecutive source
