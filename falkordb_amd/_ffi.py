@@ -121,6 +121,8 @@ SIGNATURES = {
                                       C.POINTER(u64p), u64p]),
     "fgpu_shortest_dag_batch": (C.c_int32, [vp, vp, vp, u64p, u64p, C.c_uint64, C.c_int64, C.c_uint32, i64p, u64p, C.POINTER(u64p),
                                             C.POINTER(u64p), C.POINTER(u64p), u64p]),
+    "fgpu_shortest_path_batch": (C.c_int32, [vp, vp, vp, u64p, u64p, C.c_uint64, C.c_int64, C.c_uint32, i64p, u64p, C.POINTER(u64p),
+                                             u64p]),
     "fgpu_vecidx_new": (C.c_int32, [vp, vpp, C.c_uint32, C.c_int]),
     "fgpu_vecidx_free": (C.c_int32, [vp]),
     "fgpu_vecidx_info": (C.c_int32, [vp, u32p, C.POINTER(C.c_int), u64p]),

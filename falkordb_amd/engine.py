@@ -979,6 +979,32 @@ def shortest_dag_batch(ctx: Context, A: Mat, At: Mat | None, srcs, dsts, max_hop
     return out
 
 
+def shortest_path_batch(ctx: Context, F: Mat, B: Mat | None, srcs, dsts, max_hops: int = -1, slots: int = 0, stats: bool = False):
+    """fgpu_shortest_path_batch: the reference's shortestPath() for the queries (srcs[i], dsts[i]) in one call — the ONE path its
+    bidirectional search returns, to the vertex.  F is the pattern the forward side walks, B the one the backward side walks
+    (None = F's transpose, built for the call; an undirected pattern passes S = F U F' for both), `slots` the queries searched
+    together (0 = derived from the vertex count, at most 64).  Returns a list with, per query, the node ids of its path as a
+    uint64 array (length + 1 of them), or None without a path within max_hops (< 0: unbounded) — and, when stats=True, a
+    (path, stats) tuple with the eight counters [forward levels, backward levels, vertices claimed forward, claimed backward,
+    entries walked, meeting vertex (2^64 - 1: none), meeting candidates of the last level, 0]."""
+    s, d = _u64(srcs), _u64(dsts)
+    assert len(s) == len(d)
+    count = len(s)
+    nodes = u64p()
+    length = np.zeros(count, dtype=np.int64)
+    off = np.zeros(count + 1, dtype=np.uint64)
+    st = np.zeros(count * 8, dtype=np.uint64) if stats else None
+    check(ctx.lib.fgpu_shortest_path_batch(ctx._h, F._h, B._h if B else None, _p(s) if count else None, _p(d) if count else None,
+                                           C.c_uint64(count), C.c_int64(max_hops), C.c_uint32(slots),
+                                           length.ctypes.data_as(C.POINTER(C.c_int64)), _p(off), C.byref(nodes), _p(st)))
+    flat = ctx._take(nodes, int(off[count]))
+    out = []
+    for i in range(count):
+        path = flat[int(off[i]):int(off[i + 1])] if length[i] >= 0 else None
+        out.append((path, [int(x) for x in st[8 * i:8 * i + 8]]) if stats else path)
+    return out
+
+
 def betweenness(ctx: Context, A: Mat, sources, At: Mat | None = None, active_bitmap=None, stats: bool = False, out=None):
     """fgpu_betweenness: LAGr_Betweenness' unnormalised scores for algo.betweenness — the sum over `sources` (vertex ids, taken
     as given: a duplicate counts twice) of every vertex's dependency, 0 outside active_bitmap.  At = None uses A's cached

@@ -717,6 +717,50 @@ class Graph:
         rows = [(int(lengths[i]), [e[offs[p]:offs[p + 1]] for p in range(ro[i], ro[i + 1])]) for i in range(count)]
         return (rows, {"device_calls": int(calls.value)}) if stats else rows
 
+    @staticmethod
+    def _sp_endpoint(v):
+        """an endpoint of shortest_path: a node id, None for Null, anything else for a value that is not a node"""
+        if v is None:
+            return -1
+        return int(v) if isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0 else -2
+
+    def shortest_path(self, src, dst, types=(), directed=True, min_hops=1, max_hops=None):
+        """shortestPath((src)-[:types*min_hops..max_hops]->(dst)) for one row, on the host (eval.rs:1301-1513): (nodes, edges) —
+        the node ids of the ONE path the reference returns and the relationship of each consecutive pair (a pair without one
+        adds none) — or None without a path.  src / dst: a node id, None for Null (-> None); any other value raises "A
+        shortestPath requires bound nodes".  min_hops 0 with src == dst is ([src], [])."""
+        on, oe = u64p(), u64p()
+        nn, ne, null = C.c_uint64(), C.c_uint64(), C.c_int()
+        _ck(self.L.fh_shortest_path(self.h, ",".join(types).encode(), 1 if directed else 0, C.c_uint32(min_hops),
+                                    C.c_uint32(0xFFFFFFFF if max_hops is None else max_hops), C.c_int64(self._sp_endpoint(src)),
+                                    C.c_int64(self._sp_endpoint(dst)), C.byref(null), C.byref(on), C.byref(nn), C.byref(oe),
+                                    C.byref(ne)))
+        nodes, edges = _take(on, nn.value).tolist(), _take(oe, ne.value).tolist()
+        return None if null.value else (nodes, edges)
+
+    def shortest_path_batch(self, srcs, dsts, types=(), directed=True, min_hops=1, max_hops=None, stats=False):
+        """shortestPath() over a parent batch of rows: [(nodes, edges) | None, ...], row i what shortest_path(srcs[i], dsts[i],
+        ...) returns.  The patterns are built once and ONE fgpu_shortest_path_batch call serves every row whose two nodes are in
+        range, alive and different; the other rows are evaluated on the host.  stats=True: a second item {"device_calls":
+        0 | 1}."""
+        s = np.asarray([self._sp_endpoint(v) for v in srcs], dtype=np.int64)
+        d = np.asarray([self._sp_endpoint(v) for v in dsts], dtype=np.int64)
+        assert len(s) == len(d)
+        count = len(s)
+        on, oe = u64p(), u64p()
+        null = np.zeros(max(count, 1), dtype=np.uint8)
+        noff, eoff = np.zeros(count + 1, dtype=np.uint64), np.zeros(count + 1, dtype=np.uint64)
+        calls = C.c_uint64()
+        _ck(self.L.fh_shortest_path_batch(self.h, ",".join(types).encode(), 1 if directed else 0, C.c_uint32(min_hops),
+                                          C.c_uint32(0xFFFFFFFF if max_hops is None else max_hops), s.ctypes.data_as(i64p),
+                                          d.ctypes.data_as(i64p), C.c_uint64(count), null.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          C.byref(on), noff.ctypes.data_as(u64p), C.byref(oe), eoff.ctypes.data_as(u64p),
+                                          C.byref(calls)))
+        no, eo = noff.tolist(), eoff.tolist()
+        nodes, edges = _take(on, no[-1]).tolist(), _take(oe, eo[-1]).tolist()
+        rows = [None if null[i] else (nodes[no[i]:no[i + 1]], edges[eo[i]:eo[i + 1]]) for i in range(count)]
+        return (rows, {"device_calls": int(calls.value)}) if stats else rows
+
     def build_adjacency(self, types=(), symmetric=False):
         """Graph::build_adjacency_matrix / build_symmetric_adjacency_matrix (graph.rs:3870-3907) -> Matrix"""
         h = C.c_void_p()

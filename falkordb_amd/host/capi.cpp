@@ -810,6 +810,56 @@ int fh_all_shortest_paths_batch(fh_graph* g, const char* types, int bidirectiona
     });
 }
 
+// shortestPath(): an endpoint of the C surface is a node id, -1 for Null, anything below for a value that is not a node
+static Value sp_value(int64_t v) { return v >= 0 ? Value::node((u64)v) : v == -1 ? Value::null() : Value{Value::Other, 0}; }
+static ShortestPathFn sp_fn(const char* types, int directed, uint32_t min_hops, uint32_t max_hops) {
+    ShortestPathFn fn;
+    fn.types = csv(types);
+    fn.directed = directed != 0;
+    fn.min_hops = min_hops;
+    fn.max_hops = max_hops;
+    return fn;
+}
+
+int fh_shortest_path(fh_graph* g, const char* types, int directed, uint32_t min_hops, uint32_t max_hops, int64_t src, int64_t dst,
+                     int* is_null, uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, uint64_t* n_edges) {
+    return guard([&] {
+        const ShortestPathFn fn = sp_fn(types, directed, min_hops, max_hops);
+        const ShortestPathFn::Path p = timed([&] { return fn.eval_row(g->g, sp_value(src), sp_value(dst)); });
+        *is_null = p.null ? 1 : 0;
+        *nodes = hand(p.nodes);
+        *n_nodes = p.nodes.size();
+        *edges = hand(p.edges);
+        *n_edges = p.edges.size();
+        return 0;
+    });
+}
+
+int fh_shortest_path_batch(fh_graph* g, const char* types, int directed, uint32_t min_hops, uint32_t max_hops, const int64_t* srcs,
+                           const int64_t* dsts, uint64_t count, uint8_t* is_null, uint64_t** nodes, uint64_t* node_off,
+                           uint64_t** edges, uint64_t* edge_off, uint64_t* device_calls) {
+    return guard([&] {
+        const ShortestPathFn fn = sp_fn(types, directed, min_hops, max_hops);
+        std::vector<Value> s, d;
+        for (u64 i = 0; i < count; ++i) { s.push_back(sp_value(srcs[i])); d.push_back(sp_value(dsts[i])); }
+        u64 calls = 0;
+        const std::vector<ShortestPathFn::Path> rows = timed([&] { return fn.eval_batch(g->g, s, d, &calls); });
+        std::vector<u64> nv, ev;
+        node_off[0] = edge_off[0] = 0;
+        for (u64 i = 0; i < count; ++i) {
+            is_null[i] = rows[i].null ? 1 : 0;
+            nv.insert(nv.end(), rows[i].nodes.begin(), rows[i].nodes.end());
+            ev.insert(ev.end(), rows[i].edges.begin(), rows[i].edges.end());
+            node_off[i + 1] = nv.size();
+            edge_off[i + 1] = ev.size();
+        }
+        *nodes = hand(nv);
+        *edges = hand(ev);
+        if (device_calls) *device_calls = calls;
+        return 0;
+    });
+}
+
 // fh_algo_bfs and fh_algo_bfs_multi: one call but for the gang (nullptr: the graph's own context); only the single-context
 // entry is a timed operator
 static int algo_bfs_c(fh_graph* g, const std::vector<Context*>* gang, int64_t source, int64_t max_depth, const char* rel_type,

@@ -1228,6 +1228,175 @@ std::vector<std::vector<std::vector<u64>>> AllShortestPathsOp::expand_batch(cons
     return out;
 }
 
+// ---- shortestPath() ---------------------------------------------------------------------------------------
+namespace {
+// NeighborIter (eval.rs:140-244): the row of `node` in every matrix of the set, one sorted stream per matrix (the layers merged
+// by the versioned iterators); several streams are sorted together and deduplicated (:238-241)
+struct SpNeighbors {
+    std::vector<const VersionedMatrix*> plain;   // iter()
+    std::vector<const Tensor*> structural;       // structural_iter()
+    std::vector<u64> operator()(u64 node) const {
+        std::vector<u64> buf;
+        for (const Tensor* t : structural)
+            if (node < t->nrows())
+                for (const Entry& e : t->structural_iter(node, node)) buf.push_back(e.col);
+        for (const VersionedMatrix* m : plain)
+            if (node < m->nrows())
+                for (const Entry& e : m->iter(node, node)) buf.push_back(e.col);
+        if (plain.size() + structural.size() > 1) {
+            std::sort(buf.begin(), buf.end());
+            buf.erase(std::unique(buf.begin(), buf.end()), buf.end());
+        }
+        return buf;
+    }
+};
+
+// NeighborIter::new (:153-187) and new_reversed (:193-217).  Names of which none exists leave the set empty: no neighbour
+SpNeighbors sp_neighbors(const Graph& g, const std::vector<std::string>& types, bool directed, bool reversed) {
+    SpNeighbors nb;
+    const std::vector<u64> tids = scanned_type_ids(g, types);
+    if (reversed) {
+        for (u64 t : tids) nb.plain.push_back(&g.relationship_tensors()[t].matrix_t());
+        return nb;
+    }
+    if (types.empty()) {
+        nb.plain.push_back(&g.adjacency_matrix());
+    } else {
+        for (u64 t : tids) nb.structural.push_back(&g.relationship_tensors()[t]);
+    }
+    if (!directed)
+        for (u64 t : tids) nb.plain.push_back(&g.relationship_tensors()[t].matrix_t());
+    return nb;
+}
+
+// the first relationship from u to v over the types in order, else the first from v to u (eval.rs:1502-1505)
+template <class Ids>
+void sp_first_edge(const Ids& forward, const Ids& backward, std::vector<u64>& edges) {
+    for (const Ids* side : {&forward, &backward})
+        for (const auto& ids : *side)
+            if (!ids->empty()) { edges.push_back(ids->front()); return; }
+}
+}  // namespace
+
+ShortestPathFn::Path ShortestPathFn::eval_row(const Graph& g, const Value& src_val, const Value& dst_val) const {
+    Path out;
+    for (const Value* v : {&src_val, &dst_val}) {   // (:1314-1323: the source is looked at first)
+        if (v->kind == Value::Null) return out;
+        if (v->kind != Value::Node) throw GrbError(FGPU_INVALID, "A shortestPath requires bound nodes");
+    }
+    const u64 src = src_val.id, dst = dst_val.id;
+    if (min_hops == 0 && src == dst) {              // :1329-1332
+        out.null = false;
+        out.nodes.push_back(src);
+        return out;
+    }
+    if (src == dst) return out;                     // :1406-1408
+    const SpNeighbors nbrs[2] = {sp_neighbors(g, types, directed, false), sp_neighbors(g, types, directed, directed)};
+    // bfs_shortest_path (:1410-1471): (parent, depth) per visited node
+    std::unordered_map<u64, std::pair<u64, u64>> ball[2];
+    ball[0][src] = {src, 0};
+    ball[1][dst] = {dst, 0};
+    std::vector<u64> front[2] = {{src}, {dst}}, next;
+    u64 depth[2] = {0, 0};
+    const u64 max_level = max_hops == UINT32_MAX ? ~0ull : (u64)max_hops;
+    bool met = false;
+    u64 best_od = 0, meet = 0;
+    while (!met) {
+        if (front[0].empty() || front[1].empty() || depth[0] + depth[1] >= max_level) return out;
+        const int s = front[0].size() <= front[1].size() ? 0 : 1;
+        next.clear();
+        for (u64 cur : front[s])
+            for (u64 nb : nbrs[s](cur)) {
+                if (ball[s].count(nb)) continue;
+                ball[s][nb] = {cur, depth[s] + 1};
+                const auto o = ball[s ^ 1].find(nb);
+                if (o == ball[s ^ 1].end()) { next.push_back(nb); continue; }
+                if (!met || o->second.second < best_od) { met = true; best_od = o->second.second; meet = nb; }
+            }
+        front[s].swap(next);
+        ++depth[s];
+    }
+    std::vector<u64> nodes{meet};                   // :1475-1488
+    while (nodes.back() != src) nodes.push_back(ball[0].at(nodes.back()).first);
+    std::reverse(nodes.begin(), nodes.end());
+    while (nodes.back() != dst) nodes.push_back(ball[1].at(nodes.back()).first);
+    if (nodes.size() - 1 < min_hops) return out;    // :1491-1493
+    const std::vector<u64> tids = scanned_type_ids(g, types);
+    for (size_t i = 0; i + 1 < nodes.size(); ++i) {
+        std::vector<std::vector<u64>> fwd, bwd;
+        for (u64 t : tids) {
+            fwd.push_back(g.relationship_tensors()[t].get(nodes[i], nodes[i + 1]));
+            bwd.push_back(g.relationship_tensors()[t].get(nodes[i + 1], nodes[i]));
+        }
+        std::vector<const std::vector<u64>*> f, b;
+        for (size_t t = 0; t < tids.size(); ++t) { f.push_back(&fwd[t]); b.push_back(&bwd[t]); }
+        sp_first_edge(f, b, out.edges);
+    }
+    out.null = false;
+    out.nodes = std::move(nodes);
+    return out;
+}
+
+std::vector<ShortestPathFn::Path> ShortestPathFn::eval_batch(const Graph& g, const std::vector<Value>& srcs,
+                                                             const std::vector<Value>& dsts, u64* device_calls) const {
+    if (srcs.size() != dsts.size()) throw std::invalid_argument("shortestPath: srcs and dsts differ in length");
+    const size_t count = srcs.size();
+    std::vector<Path> out(count);
+    if (device_calls) *device_calls = 0;
+    const u64 n = g.node_cap();
+    const std::vector<u64> tids = scanned_type_ids(g, types);
+    // the rows the device sees: two nodes in range and alive, src != dst, and a pattern with a type behind it.  The others
+    // are eval_row's, in place (a non-node endpoint throws there, as it does per row)
+    std::vector<size_t> row;
+    std::vector<u64> s, d;
+    for (size_t i = 0; i < count; ++i) {
+        const Value &a = srcs[i], &b = dsts[i];
+        if (!tids.empty() && a.kind == Value::Node && b.kind == Value::Node && a.id != b.id && a.id < n && b.id < n &&
+            !g.is_node_deleted(a.id) && !g.is_node_deleted(b.id)) {
+            row.push_back(i);
+            s.push_back(a.id);
+            d.push_back(b.id);
+        } else {
+            out[i] = eval_row(g, a, b);
+        }
+    }
+    if (row.empty()) return out;
+    // F and B (the table in include/fgpu.h), once for the batch
+    Matrix f = directed ? g.build_adjacency_matrix(types) : g.build_symmetric_adjacency_matrix(types);
+    Matrix b = directed ? f.transpose() : f;
+    std::vector<int64_t> L(row.size(), -1);
+    std::vector<u64> off(row.size() + 1, 0);
+    EngineBuf<u64> nodes(g.ctx().raw());
+    check(fgpu_shortest_path_batch(g.ctx().raw(), f.snapshot(), b.snapshot(), s.data(), d.data(), row.size(),
+                                   max_hops == UINT32_MAX ? -1 : (int64_t)max_hops, 0, L.data(), off.data(), nodes.out(), nullptr),
+          "shortestPath");
+    if (device_calls) *device_calls = 1;
+    // the relationships behind the consecutive pairs of ALL rows: one probe per type and direction
+    std::vector<u64> pu, pv;
+    for (size_t j = 0; j < row.size(); ++j)
+        for (u64 k = off[j]; k + 1 < off[j + 1]; ++k) { pu.push_back(nodes[k]); pv.push_back(nodes[k + 1]); }
+    std::vector<std::vector<std::vector<u64>>> fwd(tids.size()), bwd(tids.size());
+    if (!pu.empty())
+        for (size_t t = 0; t < tids.size(); ++t) {
+            g.relationship_tensors()[tids[t]].get_batch(pu, pv, fwd[t]);
+            g.relationship_tensors()[tids[t]].get_batch(pv, pu, bwd[t]);
+        }
+    size_t pair = 0;
+    for (size_t j = 0; j < row.size(); ++j) {
+        if (L[j] < 0) continue;
+        Path& p = out[row[j]];
+        p.nodes.assign(nodes.p + off[j], nodes.p + off[j + 1]);
+        std::vector<const std::vector<u64>*> fw(tids.size()), bw(tids.size());
+        for (int64_t e = 0; e < L[j]; ++e, ++pair) {
+            for (size_t t = 0; t < tids.size(); ++t) { fw[t] = &fwd[t][pair]; bw[t] = &bwd[t][pair]; }
+            sp_first_edge(fw, bw, p.edges);
+        }
+        p.null = (u64)L[j] < min_hops;   // (never: a found path has an edge and min_hops is 0 or 1)
+        if (p.null) { p.nodes.clear(); p.edges.clear(); }
+    }
+    return out;
+}
+
 // ---- algo.BFS --------------------------------------------------------------------------------------------
 // The partitioned form of the search below: the adjacency is cut into nnz-balanced column slabs, one
 // per context of `gang` (one context per GPU; several contexts on one device work too and are how this is tested),

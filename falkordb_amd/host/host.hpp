@@ -801,7 +801,8 @@ struct CondVarLenTraverseOp {
 // the DAG's vertices at a level depends only on the DAG's vertices one level up and on their adjacency order restricted to DAG
 // neighbours, by induction from src.
 // Edge-attribute filters need the attribute store (out of scope, as for the other operators); min_hops is always 1 (the
-// parser refuses anything else, cypher.rs:1324-1331); the shortestPath() function (eval.rs:1296-1400) is not served.
+// parser refuses anything else, cypher.rs:1324-1331); the shortestPath() function (eval.rs:1296-1513) returns ONE particular path
+// and is served by ShortestPathFn below, over a search of its own.
 struct AllShortestPathsOp {
     std::vector<std::string> types;
     bool bidirectional = false;
@@ -820,6 +821,37 @@ struct AllShortestPathsOp {
     std::vector<std::vector<std::vector<u64>>> expand_batch(const Graph& g, const std::vector<u64>& srcs, const std::vector<u64>& dsts,
                                                             u64 limit = 0, std::vector<int64_t>* lengths = nullptr,
                                                             u64* device_calls = nullptr) const;
+};
+
+// shortestPath((a)-[:types*min..max]->(b)) (runtime/eval.rs:1301-1513), an expression the reference evaluates once per row: a
+// bidirectional BFS over hash maps that returns ONE path, fixed by the order of its frontiers, by the side it grows (fewer
+// frontier vertices) and by the first discoverer of every vertex (the rules are restated in include/fgpu.h).  min_hops is 0 or
+// 1 and there is no edge filter (the parser, cypher.rs:1802-1831); for (b)<-[*]-(a) the source is a.
+struct ShortestPathFn {
+    std::vector<std::string> types;
+    bool directed = true;
+    uint32_t min_hops = 1;                 // 0 or 1
+    uint32_t max_hops = UINT32_MAX;        // UINT32_MAX = unbounded
+    struct Path {
+        bool null = true;
+        std::vector<u64> nodes, edges;     // nodes: length + 1 ids; edges: see below (a pair without a relationship adds none)
+    };
+    // One row, the CPU mirror of the reference: the rows are walked through the versioned matrices' iterators in the iterator
+    // sets of eval.rs:153-217 — no type named: the adjacency forward, every tensor's transpose backward; types named: the
+    // existing ones' tensors and transposes, none existing: no iterator, so no path; undirected: both on both sides, sorted and
+    // deduplicated — and the search is bfs_shortest_path.  A Null endpoint gives a null path, an endpoint that is not a node
+    // throws GrbError "A shortestPath requires bound nodes"; min_hops == 0 with src == dst is the one-node path; a found path
+    // shorter than min_hops is null.  The relationship of each consecutive pair (u, v) is the first id of
+    // get_src_dest_relationships(u, v, types) (graph.rs:2496-2513: types in the order given, or the graph's; ids in Tensor::get's
+    // order), else the first of (v, u) — tried in the directed case too — else none.
+    Path eval_row(const Graph& g, const Value& src, const Value& dst) const;
+    // A parent batch of rows: out[i] equals eval_row(g, srcs[i], dsts[i]).  F and B are built ONCE
+    // (build_adjacency_matrix(types) and its transpose, or build_symmetric_adjacency_matrix(types) for both), every row whose two
+    // nodes are below node_cap() and alive and differ goes to ONE fgpu_shortest_path_batch call (no resolvable type: none
+    // does), the ids of all rows' pairs come from one Tensor::get_batch per type and direction, and the other rows go through
+    // eval_row in place.  *device_calls (nullable) = the fgpu_shortest_path_batch calls made: 0 or 1.
+    std::vector<Path> eval_batch(const Graph& g, const std::vector<Value>& srcs, const std::vector<Value>& dsts,
+                                 u64* device_calls = nullptr) const;
 };
 
 struct BfsResult {

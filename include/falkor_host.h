@@ -277,6 +277,25 @@ int fh_all_shortest_paths(fh_graph* g, const char* types, int bidirectional, int
 int fh_all_shortest_paths_batch(fh_graph* g, const char* types, int bidirectional, int reversed, uint32_t max_hops,
                                 const uint64_t* srcs, const uint64_t* dsts, uint64_t count, uint64_t limit, int64_t* lengths,
                                 uint64_t** edges, uint64_t** path_off, uint64_t* row_off, uint64_t* device_calls);
+/* shortestPath((src)-[:types*min_hops..max_hops]->(dst)) for one row (eval.rs:1301-1513): the ONE path the reference's
+ * bidirectional search returns (the rules are in fgpu.h under fgpu_shortest_path_batch), walked on the host through the versioned
+ * matrices' iterators.  types: a comma list ("" = none named); directed 0: the pattern has no arrow; min_hops 0 or 1;
+ * max_hops = UINT32_MAX: unbounded.  src / dst: a node id, -1 for Null (the path is null), below -1 for a value that is not a
+ * node (fails with "A shortestPath requires bound nodes").  *is_null = 1: no path, both lists empty.  Otherwise `nodes` holds
+ * the path's node ids (one with min_hops 0 and src == dst) and `edges` the relationship of each consecutive pair (u, v): the
+ * first id from u to v over the types in order, else the first from v to u, else none — so n_edges may be below n_nodes - 1.
+ * Both are freed with fh_free. */
+int fh_shortest_path(fh_graph* g, const char* types, int directed, uint32_t min_hops, uint32_t max_hops, int64_t src, int64_t dst,
+                     int* is_null, uint64_t** nodes, uint64_t* n_nodes, uint64_t** edges, uint64_t* n_edges);
+/* shortestPath() over a parent batch of `count` rows, row i = (srcs[i], dsts[i]): what fh_shortest_path gives for each row.
+ * The forward and backward patterns are built once, ONE fgpu_shortest_path_batch call serves every row whose two nodes are in
+ * range, alive and different (no row when no type resolves), the relationship ids come from one tensor probe per type and
+ * direction, and the other rows are evaluated on the host in place.  is_null, node_off and edge_off are the caller's (count,
+ * count + 1 and count + 1 entries): nodes[node_off[i] .. node_off[i + 1]) and edges[edge_off[i] .. edge_off[i + 1]) are row i's.
+ * nodes and edges are freed with fh_free.  *device_calls (nullable) = the fgpu_shortest_path_batch calls made, 0 or 1. */
+int fh_shortest_path_batch(fh_graph* g, const char* types, int directed, uint32_t min_hops, uint32_t max_hops, const int64_t* srcs,
+                           const int64_t* dsts, uint64_t count, uint8_t* is_null, uint64_t** nodes, uint64_t* node_off,
+                           uint64_t** edges, uint64_t* edge_off, uint64_t* device_calls);
 /* source < 0 = NULL; rel_type NULL = all types.  `edges` holds one id per (parent, child) pair that HAS a
  * representative edge among the types, in node order; a pair without one is skipped in `edges` but its child stays in
  * `nodes` — exactly what the reference yields (algo_procedures.rs:1121-1150) — so the two lists are parallel only

@@ -999,6 +999,52 @@ fgpu_info fgpu_shortest_dag_batch(fgpu_ctx* ctx, const fgpu_mat* A, const fgpu_m
                                   uint64_t count, int64_t max_hops, uint32_t slots, int64_t* length, uint64_t* pair_off,
                                   uint64_t** from, uint64_t** to, uint64_t** depth, uint64_t* stats);
 
+/* shortestPath((a)-[:T*..k]->(b)) for a whole batch of bound pairs: the ONE path the reference's per-row bidirectional search
+ * returns (runtime/eval.rs:1386-1513, bfs_shortest_path, over the neighbour streams of eval.rs:140-244), to the vertex.
+ * fgpu_shortest_dag_batch cannot serve it: which of several shortest paths comes back is fixed by the order of the frontiers, by
+ * the side that grows and by the first discoverer of every vertex, and this call keeps all three (spath_batch.hip).
+ * Neighbours.  neighbors(v) of a side is the set of columns of row v of its pattern, ascending, each once.  The forward side
+ * reads F, the backward side reads B: for a directed pattern F is the union of the types' matrices (the adjacency when no type
+ * is named) and B its transpose — B == NULL builds the transpose for the call and releases it with it; for an undirected
+ * pattern the caller passes S = F U F' for both.  Values are ignored, hypersparse patterns are accepted, nothing is cached on
+ * either matrix.
+ * Start.  src == dst gives no path (the caller serves the single-node path of min_hops == 0 itself).  Each ball starts as its
+ * seed at depth 0, each frontier as its seed, df = db = 0.
+ * A round.
+ *   1. If either frontier is empty, or df + db >= max_hops (max_hops < 0: unbounded; 0: no path), there is no path.
+ *   2. The forward side expands iff it has at most as many frontier VERTICES as the backward side (not entries).
+ *   3. The expanding side walks its frontier in frontier order and each row in ascending column order; the position of an
+ *      entry in that concatenation is its key.
+ *   4. A vertex not yet in the side's own ball is claimed by the smallest key that reaches it: its parent is the frontier
+ *      vertex of that key's row, its depth the side's depth + 1.
+ *   5. A claimed vertex that the other ball already holds is a meeting candidate; the other claimed vertices form the side's
+ *      next frontier, in ascending key order.
+ *   6. The level always runs to its end, and the side's depth grows by one.
+ *   7. With candidates, the meeting vertex is the candidate of the least other-side depth, then of the least key, and the
+ *      search ends.
+ * Result.  The forward parents from the meeting vertex back to src, reversed, then the backward parents on to dst:
+ * length + 1 node ids.
+ *   - length[i] is the edge count of query i's path, -1 without one;
+ *   - node_off has count + 1 entries, node_off[0] = 0: nodes[node_off[i] .. node_off[i + 1]) is the path of query i, empty
+ *     without one.  *nodes is NULL when node_off[count] == 0, else freed with fgpu_free;
+ *   - stats (nullable, count * 8 words) of query i: [0] forward levels, [1] backward levels, [2] vertices claimed forward,
+ *     [3] vertices claimed backward (seeds not counted, candidates counted), [4] entries walked, [5] the meeting vertex or
+ *     2^64 - 1, [6] meeting candidates of the last level (0 without a path), [7] 0;
+ *   - the queries are independent: duplicates and any order are allowed.  The result does not depend on slots, on the calling
+ *     thread or on the run.
+ * slots is the number of queries searched together, at most FGPU_SPATH_SLOTS_MAX.  Every slot has a dense claim word and a
+ * parent per vertex and side, 24 nrows bytes; every other temporary grows with the entries walked.  slots = 0 derives it:
+ * min(count, FGPU_SPATH_SLOTS_MAX, max(1, 2 GiB / (24 nrows))).
+ * Errors: NULL ctx / F / length / node_off / nodes, or NULL src / dst with count > 0: FGPU_NULL_POINTER; non-square F or a B of
+ * other dimensions: FGPU_DIM_MISMATCH; slots > FGPU_SPATH_SLOTS_MAX, nrows >= 2^32 - 1 or nnz >= 2^32 - 1: FGPU_INVALID; any
+ * src[i] or dst[i] >= nrows: FGPU_OUT_OF_BOUNDS for the whole call, before any work — the message names i, no output is written
+ * or allocated.  count == 0 returns FGPU_OK with node_off[0] = 0; nrows == 0 gives no path for every query.
+ * The call runs on the calling thread's lane: concurrent callers on the same matrices are independent. */
+#define FGPU_SPATH_SLOTS_MAX 64
+fgpu_info fgpu_shortest_path_batch(fgpu_ctx* ctx, const fgpu_mat* F, const fgpu_mat* B, const uint64_t* src, const uint64_t* dst,
+                                   uint64_t count, int64_t max_hops, uint32_t slots, int64_t* length, uint64_t* node_off,
+                                   uint64_t** nodes, uint64_t* stats);
+
 /* Exhaustive vector similarity search: the numeric core of db.idx.vector.queryNodes / queryRelationships
  * (runtime/ops/node_by_vector_scan.rs, edge_by_vector_scan.rs) and of vec.euclideanDistance / vec.cosineDistance.  The
  * reference asks an approximate HNSW graph (RediSearch / VecSim, index/mod.rs:1768-1823) for k candidates, recomputes each

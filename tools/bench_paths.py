@@ -51,6 +51,12 @@
           and [5] summed), and that (b) returned what (a) did; with the host operator's batch against its per-row loop on the
           host leg's graph (RMAT-18, one type, 64 rows, fh_last_op_ns)
 
+  shortest_path  fgpu_shortest_path_batch (shortestPath()'s one path per query) on the graph and the seeded pairs of the asp_batch
+          leg, directed and symmetrised, in ONE process: (a) a loop of 64 calls of one query, (b) one call of the same 64, (c) one
+          of the 1024 pairs at slots = 0, (d) / (e) fgpu_shortest_dag_batch on the pairs of (b) / (c) as the yardstick.  Median /
+          min / max of 5 after 1 warm-up, ms per query, the entries walked, and that (b) returned what (a) did; with the host
+          function's batch against its eval_row loop on the host leg's graph (RMAT-18, one type, 64 rows, fh_last_op_ns)
+
   hops    the hop-bounded table behind algo.SPpaths' enumeration shapes (fgpu_sssp_hops) on RMAT-22 (or RMAT-<scale>)
           TRANSPOSED, with the hashed integer weights of the sssp leg, from the vertex with the most in-entries of the graph
           (= most out-entries of the transpose): max_hops 3 and 6 into a pinned table, median of 3 synchronised calls, the
@@ -1473,6 +1479,96 @@ def bench_asp_batch(ctx, scale, npairs=64, nbig=1024, host_scale=18):
     hc.close()
 
 
+def bench_shortest_path(ctx, scale, npairs=64, nbig=1024, host_scale=18):
+    """fgpu_shortest_path_batch: one batch against a loop of one-query calls and against fgpu_shortest_dag_batch on the same
+    pairs, same process, same handles; then the host function's batch against its per-row loop"""
+    def spread(fn, reps=5, warm=1):
+        for _ in range(warm):
+            r = fn()
+        ctx.sync()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            ctx.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts)), float(min(ts)), float(max(ts)), r
+
+    A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
+    At = A.transpose()
+    S = A.merge_pattern(At, None)
+    n = A.nrows
+    ctx.set_option("spdag_sides", 0)
+    for graph, M, Mt in (("directed", A, At), ("symmetrised", S, S)):
+        rp, _, _ = M.export_csr()
+        rpt, _, _ = Mt.export_csr()
+        live = np.nonzero((np.diff(rp.astype(np.int64)) > 0) & (np.diff(rpt.astype(np.int64)) > 0))[0]
+        picks = np.random.default_rng(0xA5B0 + scale).choice(live, size=(npairs, 2))           # the asp leg's pairs
+        big = np.random.default_rng(0xB16 + scale).choice(live, size=(nbig, 2))                # the asp_batch leg's
+        src, dst = picks[:, 0].tolist(), picks[:, 1].tolist()
+        ta, loa, hia, one = spread(lambda: [engine.shortest_path_batch(ctx, M, Mt, [s], [d], stats=True)[0] for s, d in zip(src, dst)])
+        tb, lob, hib, bat = spread(lambda: engine.shortest_path_batch(ctx, M, Mt, src, dst, stats=True))
+        equal = all((x[0] is None) == (y[0] is None) and (x[0] is None or np.array_equal(x[0], y[0])) and x[1] == y[1]
+                    for x, y in zip(one, bat))
+        tc, loc, hic, bigr = spread(lambda: engine.shortest_path_batch(ctx, M, Mt, big[:, 0], big[:, 1], stats=True))
+        td, lod, hid, dag = spread(lambda: engine.shortest_dag_batch(ctx, M, Mt, src, dst, stats=True))
+        te, loe, hie, dagbig = spread(lambda: engine.shortest_dag_batch(ctx, M, Mt, big[:, 0], big[:, 1], stats=True))
+        same_len = all((p is None and r[0] < 0) or (p is not None and len(p) - 1 == r[0]) for (p, _), r in zip(bat, dag))
+        walked = lambda rs: int(sum(st[4] for _, st in rs))
+        rounds = lambda rs: int(max(st[0] + st[1] for _, st in rs))
+        print(json.dumps({"path": "shortest_path", "graph": graph, "scale": scale, "n": n, "nnz": M.nvals, "pairs": npairs,
+                          "a_loop_ms_per_query": round(ta / npairs, 4), "a_loop_ms_min_max": [round(loa, 3), round(hia, 3)],
+                          "b_batch_ms_per_query": round(tb / npairs, 4), "b_batch_ms_min_max": [round(lob, 3), round(hib, 3)],
+                          "a_over_b": round(ta / tb, 2), "b_equals_a": bool(equal), "entries_walked_64": walked(bat),
+                          "found_64": int(sum(p is not None for p, _ in bat)), "rounds_64": rounds(bat),
+                          "c_pairs": nbig, "c_batch_ms_per_query": round(tc / nbig, 4), "c_batch_ms_min_max": [round(loc, 3), round(hic, 3)],
+                          "c_entries_walked": walked(bigr), "c_found": int(sum(p is not None for p, _ in bigr)),
+                          "d_dag_batch_ms_per_query": round(td / npairs, 4), "d_dag_batch_ms_min_max": [round(lod, 3), round(hid, 3)],
+                          "d_lengths_equal_b": bool(same_len), "d_entries_scanned_64": int(sum(r[4][4] + r[4][5] for r in dag)),
+                          "e_dag_batch_1024_ms_per_query": round(te / nbig, 4), "e_min_max": [round(loe, 3), round(hie, 3)],
+                          "b_over_d": round(tb / td, 2), "c_over_e": round(tc / te, 2),
+                          "note": "host clock around synchronised calls in one process, median of 5 after 1 warm-up; (a) 64 "
+                                  "fgpu_shortest_path_batch calls of one query in a loop, (b) one call of the same 64, (c) one of 1024 "
+                                  "seeded pairs at slots = 0, (d) / (e) fgpu_shortest_dag_batch on the pairs of (b) / (c); stats on, "
+                                  "backward pattern given; rounds_64 = the most levels any query of (b) ran"}), flush=True)
+    S.free()
+    At.free()
+    A.free()
+    # the host function on the host leg's graph: one batch of 64 rows against the per-row loop, the function's own clock
+    from falkordb_amd import host
+    hc = host.Context(0)
+    B = ctx.mat_rmat(host_scale)
+    bn = B.nrows
+    brp, bci, _ = B.export_csr()
+    bdeg = np.diff(brp.astype(np.int64))
+    g = host.Graph(hc, bn)
+    ty = g.add_type("KNOWS")
+    load_edges(g, ty, np.repeat(np.arange(bn, dtype=np.uint64), bdeg), bci, np.arange(len(bci), dtype=np.uint64))
+    g.commit()
+    B.free()
+    live = np.nonzero(bdeg > 0)[0]
+    rows = np.random.default_rng(0xA5B0 + host_scale).choice(live, size=(npairs, 2)).tolist()
+    batch_ms = []
+    for rep in range(4):   # (the first repetition warms up)
+        got = g.shortest_path_batch([s for s, _ in rows], [d for _, d in rows], types=["KNOWS"])
+        if rep:
+            batch_ms.append(g.L.fh_last_op_ns() / 1e9 * 1e3)
+    t, per_row, t0 = 0, [], time.perf_counter()
+    for s, d in rows:      # eval_row fetches one matrix row per iterator call: once through, up to a deadline
+        per_row.append(g.shortest_path(s, d, types=["KNOWS"]))
+        t += g.L.fh_last_op_ns() / 1e9
+        if time.perf_counter() - t0 > 90:
+            break
+    print(json.dumps({"path": "shortest_path_host", "scale": host_scale, "n": bn, "nnz": int(len(bci)), "rows": npairs,
+                      "loop_rows_timed": len(per_row), "loop_ms_per_row": round(t * 1e3 / len(per_row), 4),
+                      "batch_ms_per_row": round(float(np.median(batch_ms)) / npairs, 4), "equal": got[:len(per_row)] == per_row,
+                      "found": int(sum(r is not None for r in got)),
+                      "note": "fh_last_op_ns around the function; the batch: median of 3 after 1 warm-up; the loop is eval_row, "
+                              "which walks the versioned matrices' rows one iterator call at a time: once through, cut off "
+                              "after 90 s (loop_rows_timed)"}), flush=True)
+    hc.close()
+
+
 def bench_betweenness(ctx, scale):
     from falkordb_amd import host
     A = ctx.mat_rmat(scale, 16, 0x5EED1234 + scale)          # bench.py's graph of that scale
@@ -1571,6 +1667,10 @@ if __name__ == "__main__":
     if what in ("asp_batch", "all"):
         c = engine.Context(0)
         bench_asp_batch(c, scale if scale else 22)
+        c.close()
+    if what in ("shortest_path", "all"):
+        c = engine.Context(0)
+        bench_shortest_path(c, scale if scale else 22)
         c.close()
     if what in ("betweenness", "all"):
         c = engine.Context(0)
