@@ -88,6 +88,7 @@ SIGNATURES = {
                                   C.POINTER(u32p), u64p, u64p]),
     "fgpu_expand_mat": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, vpp, u64p]),
     "fgpu_expand_probe": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u8p, u64p]),
+    "fgpu_expand_exists": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, u64p, u64p]),
     "fgpu_expand_pairs": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, C.c_int, vpp, C.POINTER(u64p), u64p, u64p]),
     "fgpu_expand_pairs32": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, C.c_int, u64p, u64p, C.c_int, vpp, C.POINTER(u32p), u64p, u64p]),
     "fgpu_multi_new": (C.c_int32, [vp, u64p, u64p, u64p, C.c_uint64, vpp]),

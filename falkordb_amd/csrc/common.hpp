@@ -601,6 +601,13 @@ fgpu_info bp_to_csr(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, fgpu
 fgpu_info bp_probe_rows(fgpu_ctx* ctx, const BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm,
                         const u32* dst_dev, const u32* bit_dev, const u32* sdst_dev, const u32* srow_dev, u32 k,
                         uint8_t* hit_m, uint8_t* hit_dm, uint8_t* hit_dp);
+// the last hop of a pattern predicate (fgpu_expand_exists, exists.hip): which rows reach ANYTHING through the last layers, from
+// the CSR frontier `f` (row i = the frontier of row i) or, when f is nullptr, from the bit state `s`.  Bit i of `sure` (zeroed
+// by the caller, `words` u64 each): row i reaches a destination no tombstone can mask; bit i of `maybe`: it reaches one that
+// occurs as a column of dm, so only the whole row decides.  Bits of a compacted state are live-row numbers (BitState::rowrank).
+// *entries += the adjacency entries read.
+fgpu_info exists_rows(fgpu_ctx* ctx, const fgpu_mat* f, const BitState* s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm,
+                      const u64* label_dev, u32 k, u64* sure, u64* maybe, u32 words, u64* entries);
 // nnz + order-independent checksum of the result read straight from the bit state (fgpu_expand_count)
 fgpu_info bp_count(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, u64* nnz, u64* checksum);
 // the LAST hop of a count-only chain: the hop and the count in one pass — the result rows are counted where they are

@@ -1802,6 +1802,87 @@ fgpu_info fgpu_expand_probe(fgpu_ctx* ctx, const uint64_t* src_ids, const uint64
     return FGPU_OK;
 }
 
+// The pattern predicate (SemiApply / AntiSemiApply over a CondTraverse with an unbound destination, semi_apply.rs:85-106): bit i
+// = row i of fgpu_expand over the same arguments is not empty.  The chain up to the last hop runs as in the probe; the last hop
+// is never expanded (exists.hip): it settles every row that reaches a destination no tombstone can mask, and the rows that only
+// reach columns of the last dm — where the row-level mask of Matrix::delta_lmxm decides — go through the whole chain once more,
+// those rows alone.
+fgpu_info fgpu_expand_exists(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m, const fgpu_mat* const* dp,
+                             const fgpu_mat* const* dm, int nhops, const uint64_t* dst_label_bitmap, uint64_t* match_bits, uint64_t* flops,
+                             uint64_t stats[4]) {
+    FGPU_REQUIRE(ctx && match_bits && (nsrc == 0 || src_ids), FGPU_NULL_POINTER, "fgpu_expand_exists: NULL argument");
+    if (flops) *flops = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    const Layers L{m, dp, dm, nhops};
+    FGPU_TRY(check_hops(L, nsrc));
+    if (nsrc == 0) return FGPU_OK;
+    const u32 k = (u32)nsrc, kw = (k + 63) / 64;
+    memset(match_bits, 0, (size_t)kw * sizeof(uint64_t));
+    const fgpu_mat *ml = m[nhops - 1], *dpl = L.dp_at(nhops - 1), *dml = L.dm_at(nhops - 1);
+    // the chain up to the last hop: a sorted-CSR frontier (f), or the bit state it ended in (bs)
+    ChainResult res;
+    if (nhops == 1) FGPU_TRY(upload_sources(ctx, &res.mat.m, src_ids, nsrc, m[0]->nrows));
+    else FGPU_TRY(expand_device(ctx, {src_ids, nsrc, {m, dp, dm, nhops - 1}, nullptr, flops, ChainEnd::Bits}, res));
+    const fgpu_mat* f = res.kind == ChainResult::Bits ? nullptr : res.mat.get();
+    BitState& bs = res.bits;
+    DevBuf<u64> bm, out;
+    FGPU_TRY(label_to_device(ctx, dst_label_bitmap, ml->ncols, bm));
+    const u32 words = f ? kw : (bs.w > kw ? bs.w : kw);          // sure, then maybe
+    FGPU_TRY(out.alloc(ctx, (size_t)2 * words));
+    FGPU_HIP(hipMemsetAsync(out.p, 0, (size_t)2 * words * sizeof(u64), ctx->stream()));
+    u64 entries = 0;
+    const fgpu_info ei = exists_rows(ctx, f, f ? nullptr : &bs, ml, dpl, dml, bm.p, k, out.p, out.p + words, words, &entries);
+    std::vector<u64> h((size_t)2 * words);
+    std::vector<u32> rank;
+    fgpu_info di = ei;
+    if (di == FGPU_OK) di = ctx->d2h(h.data(), out.p, h.size() * sizeof(u64));
+    if (di == FGPU_OK && !f && bs.nsrc_full) {
+        rank.resize((size_t)bs.nsrc_full + 1);
+        di = ctx->d2h(rank.data(), bs.rowrank.p, rank.size() * sizeof(u32));
+    }
+    if (!f) bp_finish(ctx, bs);
+    FGPU_TRY(di);
+    // bit j of a compacted state is live row j: source row i is live (rank[i + 1] > rank[i]) or was dropped as empty
+    std::vector<u64> src_left;
+    std::vector<u32> row_left;
+    u64 matched = 0;
+    for (u32 i = 0; i < k; ++i) {
+        u32 j = i;
+        if (!rank.empty()) {
+            if (rank[i + 1] == rank[i]) continue;
+            j = rank[i];
+        }
+        if (src_ids[i] == UINT64_MAX) continue;
+        const u64 bit = 1ull << (j & 63);
+        if (h[j >> 6] & bit) { match_bits[i >> 6] |= 1ull << (i & 63); ++matched; }
+        else if (h[words + (j >> 6)] & bit) { src_left.push_back(src_ids[i]); row_left.push_back(i); }
+    }
+    if (!src_left.empty()) {
+        // the undecided rows: every destination they reach is a column of dm, so only the row-level mask tells — the chain
+        // itself, over these rows alone, and its row pointers
+        ChainResult ex;
+        FGPU_TRY(expand_device(ctx, {src_left.data(), src_left.size(), {m, dp, dm, nhops}, dst_label_bitmap, nullptr, ChainEnd::Csr}, ex));
+        const fgpu_mat* r = ex.mat.get();
+        const u32 nl = (u32)src_left.size();
+        if (r->nnz) {
+            if (r->is_hyper()) {
+                std::vector<u32> hr(r->nvec), srp((size_t)r->nvec + 1);
+                FGPU_TRY(ctx->d2h(srp.data(), r->rowptr, srp.size() * sizeof(u32)));
+                if (r->nvec) FGPU_TRY(ctx->d2h(hr.data(), r->hrows, (size_t)r->nvec * sizeof(u32)));
+                for (u32 q = 0; q < r->nvec; ++q)
+                    if (srp[q + 1] > srp[q] && hr[q] < nl) { match_bits[row_left[hr[q]] >> 6] |= 1ull << (row_left[hr[q]] & 63); ++matched; }
+            } else {
+                std::vector<u32> rp((size_t)nl + 1);
+                FGPU_TRY(ctx->d2h(rp.data(), r->rowptr, rp.size() * sizeof(u32)));
+                for (u32 q = 0; q < nl; ++q)
+                    if (rp[q + 1] > rp[q]) { match_bits[row_left[q] >> 6] |= 1ull << (row_left[q] & 63); ++matched; }
+            }
+        }
+    }
+    if (stats) { stats[0] = matched; stats[1] = src_left.size(); stats[2] = entries; stats[3] = f ? 0 : 1; }
+    return FGPU_OK;
+}
+
 // ---- streamed result (include/fgpu.h fgpu_expand_stream_*) ----------------------------------------------------------
 struct fgpu_expand_stream {
     static constexpr int NS = 4;

@@ -1269,6 +1269,27 @@ def expand_pairs(ctx: Context, src_ids, m, dp=None, dm=None, dst_label_bitmap=No
     return rows, dest, flops.value
 
 
+def expand_exists(ctx: Context, src_ids, m, dp=None, dm=None, dst_label_bitmap=None):
+    """fgpu_expand_exists: match[i] = row i of fgpu_expand over the same arguments is non-empty (the pattern predicate of
+    SemiApply); the last hop is not expanded.  Returns (match as a bool array, flops of the hops that ran, stats = [rows
+    matched, undecided rows sent through the exact pass, adjacency entries the last step read, 0 CSR frontier / 1 bit state])."""
+    src = _u64(src_ids)
+    am = _hop_arrays(m)
+    adp = _hop_arrays(dp) if dp is not None else None
+    adm = _hop_arrays(dm) if dm is not None else None
+    lab = _u64(dst_label_bitmap) if dst_label_bitmap is not None else None
+    words = np.full(max((len(src) + 63) // 64, 1), 2**64 - 1, dtype=np.uint64)   # (the call clears its words, padding included)
+    flops = C.c_uint64()
+    stats = np.zeros(4, dtype=np.uint64)
+    check(ctx.lib.fgpu_expand_exists(ctx._h, _p(src), len(src), am, adp, adm, len(m), _p(lab), words.ctypes.data_as(u64p),
+                                     C.byref(flops), stats.ctypes.data_as(u64p)))
+    if len(src) == 0:
+        return np.zeros(0, dtype=bool), flops.value, [int(x) for x in stats]
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    assert not bits[len(src):].any(), "fgpu_expand_exists left padding bits set"
+    return bits[:len(src)].astype(bool), flops.value, [int(x) for x in stats]
+
+
 def expand_probe(ctx: Context, src_ids, dst_ids, m, dp=None, dm=None, dst_label_bitmap=None):
     """fgpu_expand_probe: present[i] = dst_ids[i] is reached from src_ids[i] by the chain (every row of the batch has a
     pre-bound destination); returns (present as a bool array, flops of the hops that ran)."""

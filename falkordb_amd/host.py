@@ -619,6 +619,54 @@ class Graph:
             return cols, nulls, list(st)
         return list(zip(*(c.tolist() for c in cols))), nulls.tolist(), list(st)
 
+    SEMI_TIERS = {0: "none", 1: "exists", 2: "collect", 3: "rows"}
+
+    def semi_apply(self, spec, from_ids, to_ids=None, anti=False, transposed=False, device_exists=True):
+        """SemiApplyOp::filter_batch (fh_semi_apply): the rows that pass the pattern predicate `spec` — from / to as
+        cond_traverse_rows takes them (None unbound, a str Null / non-node), to_ids=None when no row has it bound.  Returns
+        (passing rows ascending, tier name, [fgpu_expand_exists' four stats summed, calls])."""
+        enc = lambda v: -1 if v is None else (-2 if isinstance(v, str) else int(v))
+        k = len(from_ids)
+        f = np.asarray([enc(v) for v in from_ids], dtype=np.int64)
+        t = np.asarray([enc(v) for v in to_ids], dtype=np.int64) if to_ids is not None else None
+        out, n, tier = u64p(), C.c_uint64(), C.c_int()
+        st = (C.c_uint64 * 5)()
+        _ck(self.L.fh_semi_apply(self.h, spec, 1 if anti else 0, 1 if device_exists else 0, f.ctypes.data_as(i64p),
+                                 t.ctypes.data_as(i64p) if t is not None else None, C.c_uint64(k), 1 if transposed else 0,
+                                 C.byref(out), C.byref(n), C.byref(tier), st))
+        return _take(out, n.value).tolist(), self.SEMI_TIERS[tier.value], list(st)
+
+    def or_apply(self, branches, from_ids, to_ids=None, device_exists=True):
+        """OrApplyMultiplexerOp::filter_batch (fh_or_apply).  branches: (spec or a boolean column, anti) or (spec, anti,
+        transposed).  Returns (passing rows ascending, [tier name per branch], [stats per branch])."""
+        enc = lambda v: -1 if v is None else (-2 if isinstance(v, str) else int(v))
+        k, nb = len(from_ids), len(branches)
+        f = np.asarray([enc(v) for v in from_ids], dtype=np.int64)
+        t = np.asarray([enc(v) for v in to_ids], dtype=np.int64) if to_ids is not None else None
+        specs = (C.c_char_p * nb)()
+        cols = (C.POINTER(C.c_uint8) * nb)()
+        anti, tr = (C.c_int * nb)(), (C.c_int * nb)()
+        keep = []
+        for b, br in enumerate(branches):
+            what = br[0]
+            anti[b] = 1 if br[1] else 0
+            tr[b] = 1 if len(br) > 2 and br[2] else 0
+            if isinstance(what, (bytes, str)):
+                specs[b] = what if isinstance(what, bytes) else what.encode()
+            else:
+                col = np.ascontiguousarray(np.asarray(what, dtype=bool).astype(np.uint8))
+                assert len(col) == k
+                keep.append(col)
+                cols[b] = col.ctypes.data_as(C.POINTER(C.c_uint8))
+        out, n = u64p(), C.c_uint64()
+        tiers = (C.c_int * nb)()
+        st = (C.c_uint64 * (5 * nb))()
+        _ck(self.L.fh_or_apply(self.h, specs, cols, anti, tr, nb, 1 if device_exists else 0, f.ctypes.data_as(i64p),
+                               t.ctypes.data_as(i64p) if t is not None else None, C.c_uint64(k), C.byref(out), C.byref(n),
+                               tiers, st))
+        return (_take(out, n.value).tolist(), [self.SEMI_TIERS[x] for x in tiers],
+                [list(st[5 * b:5 * b + 5]) for b in range(nb)])
+
     def expand_into(self, types, srcs, dsts, bidirectional=False, emit_relationship=True, batched=True):
         s, d = _u64(srcs), _u64(dsts)
         orow, osrc, odst, oedge = u64p(), u64p(), u64p(), u64p()

@@ -684,6 +684,70 @@ int fh_cond_traverse_edges_batch(fh_graph* g, const char* spec, const int64_t* f
     });
 }
 
+static void hand_semi_stats(const SemiApplyOp::Stats& st, int* tier, uint64_t stats[5]) {
+    if (tier) *tier = st.tier;
+    if (stats) {
+        for (int j = 0; j < 4; ++j) stats[j] = st.device[j];
+        stats[4] = st.calls;
+    }
+}
+
+int fh_semi_apply(fh_graph* g, const char* spec, int anti, int device_exists, const int64_t* from_ids, const int64_t* to_ids,
+                  uint64_t k, int transposed, uint64_t** passing, uint64_t* n, int* tier, uint64_t stats[5]) {
+    return guard([&] {
+        SemiApplyOp op;
+        op.pattern = parse_spec(spec);
+        op.anti = anti != 0;
+        op.device_exists = device_exists != 0;
+        std::vector<Value> f(k), t(k);
+        for (u64 i = 0; i < k; ++i) {
+            f[i] = to_value(from_ids[i]);
+            if (to_ids) t[i] = to_value(to_ids[i]);
+        }
+        std::vector<u64> pass;
+        SemiApplyOp::Stats st;
+        timed([&] { op.filter_batch(g->g, f, to_ids ? &t : nullptr, transposed != 0, pass, &st); return 0; });
+        *passing = hand(pass);
+        *n = pass.size();
+        hand_semi_stats(st, tier, stats);
+        return 0;
+    });
+}
+
+int fh_or_apply(fh_graph* g, const char* const* specs, const uint8_t* const* columns, const int* anti, const int* transposed,
+                int n_branches, int device_exists, const int64_t* from_ids, const int64_t* to_ids, uint64_t k,
+                uint64_t** passing, uint64_t* n, int* tiers, uint64_t* stats) {
+    return guard([&] {
+        OrApplyMultiplexerOp op;
+        for (int b = 0; b < n_branches; ++b) {
+            OrApplyMultiplexerOp::Branch br;
+            br.anti = anti && anti[b];
+            br.transposed = transposed && transposed[b];
+            if (specs && specs[b]) {
+                br.semi.emplace();
+                br.semi->pattern = parse_spec(specs[b]);
+                br.semi->device_exists = device_exists != 0;
+            } else {
+                if (!columns || !columns[b]) throw GrbError(FGPU_NULL_POINTER, "fh_or_apply: a branch needs a spec or a column");
+                br.column.assign(columns[b], columns[b] + k);
+            }
+            op.branches.push_back(std::move(br));
+        }
+        std::vector<Value> f(k), t(k);
+        for (u64 i = 0; i < k; ++i) {
+            f[i] = to_value(from_ids[i]);
+            if (to_ids) t[i] = to_value(to_ids[i]);
+        }
+        std::vector<u64> pass;
+        std::vector<SemiApplyOp::Stats> st;
+        timed([&] { op.filter_batch(g->g, f, to_ids ? &t : nullptr, pass, &st); return 0; });
+        *passing = hand(pass);
+        *n = pass.size();
+        for (int b = 0; b < n_branches; ++b) hand_semi_stats(st[b], tiers ? tiers + b : nullptr, stats ? stats + 5 * b : nullptr);
+        return 0;
+    });
+}
+
 int fh_cond_traverse_row(fh_graph* g, const char* spec, int64_t from_id, int64_t to_id, int transposed,
                          uint64_t** out_from, uint64_t** out_to, uint64_t** out_edge, uint64_t* n) {
     uint64_t* rows = nullptr;

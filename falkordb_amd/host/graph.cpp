@@ -785,6 +785,145 @@ bool CondTraverseOp::expand_batch_edges(const Graph& g, const std::vector<Value>
     return finish();
 }
 
+// ---- SemiApply / AntiSemiApply / OrApplyMultiplexer ---------------------------------------------------------------------
+void SemiApplyOp::match_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to, bool transposed,
+                              std::vector<uint8_t>& matched, Stats* stats) const {
+    const u64 k = from.size();
+    matched.assign(k, 0);
+    Stats st;
+    if (to && to->size() != k) throw GrbError(FGPU_INVALID, "SemiApply: from and to differ in length");
+    // the rows that can emit at all: the bound alias is a node, and `to` is a node or unbound (:796-805)
+    std::vector<u64> live;
+    std::vector<Value> lf, lt;
+    u64 n_bound = 0;
+    for (u64 i = 0; i < k; ++i) {
+        if (from[i].kind != Value::Node) continue;
+        const Value t = to ? (*to)[i] : Value{};
+        if (t.kind == Value::Null || t.kind == Value::Other) continue;
+        live.push_back(i);
+        lf.push_back(from[i]);
+        lt.push_back(t);
+        if (t.kind == Value::Node) ++n_bound;
+    }
+    const u64 n = live.size();
+    auto done = [&]() { if (stats) *stats = st; };
+    if (n == 0) return done();
+    CondTraverseOp p = pattern;                  // the branch as this call runs it: never optional, in the caller's direction
+    p.optional = false;
+    p.transposed = transposed;
+    const bool matrix = p.batched_eligible() && (!transposed || p.hops.size() == 1);
+    const bool edges = p.edges_batch_eligible();
+    fgpu_ctx* ctx = g.ctx().raw();
+
+    // one fgpu_expand_exists over the layers of one direction: the bound node carries the source labels, the node it reaches
+    // the last hop's; false = no_match (an unknown type or label: nothing can match)
+    auto exists_over = [&](bool over_transposed, std::vector<uint64_t>& bits) {
+        HopLayers hl;
+        std::vector<std::vector<u64>> type_ids;
+        if (!hop_layers(g, p.hops, hl, type_ids, over_transposed)) return false;
+        auto last_dst = g.resolve_label_ids(p.hops.back().dst_labels);
+        auto src_lids = g.resolve_label_ids(p.src_labels);
+        if (!last_dst || !src_lids) return false;
+        std::vector<u64> nodes(n), src_ids(n, ~0ull);
+        for (u64 c = 0; c < n; ++c) nodes[c] = lf[c].id;
+        std::vector<uint8_t> ok;
+        nodes_have_labels(g, *src_lids, nodes, ok);
+        bool any = false;
+        for (u64 c = 0; c < n; ++c)
+            if (ok[c]) { src_ids[c] = nodes[c]; any = true; }
+        if (!any) return true;
+        std::vector<u64> bitmap;
+        if (!last_dst->empty()) bitmap = g.label_bitmap(*last_dst);
+        std::vector<uint64_t> got((n + 63) / 64, 0);
+        u64 ds[4] = {0, 0, 0, 0};
+        check(fgpu_expand_exists(ctx, src_ids.data(), n, hl.m.data(), hl.dp.data(), hl.dm.data(), (int)p.hops.size(),
+                                 bitmap.empty() ? nullptr : bitmap.data(), got.data(), nullptr, ds),
+              "SemiApply::match_batch");
+        for (size_t w = 0; w < got.size(); ++w) bits[w] |= got[w];
+        ++st.calls;
+        for (int j = 0; j < 3; ++j) st.device[j] += ds[j];
+        st.device[3] = ds[3];
+        return true;
+    };
+    auto from_bits = [&](const std::vector<uint64_t>& bits) {
+        for (u64 c = 0; c < n; ++c)
+            if ((bits[c >> 6] >> (c & 63)) & 1ull) matched[live[c]] = 1;
+    };
+
+    if (device_exists && matrix && n_bound == 0) {
+        st.tier = Exists;
+        std::vector<uint64_t> bits((n + 63) / 64, 0);
+        exists_over(transposed, bits);
+        from_bits(bits);
+        return done();
+    }
+    if (device_exists && !matrix && edges && !p.emit_relationship && !p.has_sibling_edges && n_bound == 0) {
+        st.tier = Exists;                        // bidirectional: either direction, the same label roles
+        std::vector<uint64_t> bits((n + 63) / 64, 0);
+        if (exists_over(false, bits)) exists_over(true, bits);
+        from_bits(bits);
+        return done();
+    }
+    if (matrix) {
+        // every row bound: expand_batch answers with its probe, nothing expanded (the ExpandInto shape) — the existence
+        // tier; otherwise the pairs, and the rows that occur
+        st.tier = (device_exists && n_bound == n) ? Exists : Collect;
+        ExpandedRows rows;
+        std::vector<u64> nulls;
+        if (p.expand_batch(g, lf, n_bound ? &lt : nullptr, rows, nulls)) {
+            for (size_t r = 0; r < rows.size(); ++r) matched[live[rows.row_at(r)]] = 1;
+            rows.release_pinned();
+            return done();
+        }
+    } else if (edges) {
+        st.tier = Collect;
+        CondTraverseOp::EdgeRows rows;
+        std::vector<u64> nulls;
+        if (p.expand_batch_edges(g, lf, lt, transposed, nullptr, 0, rows, nulls)) {
+            for (u64 r : rows.row) matched[live[r]] = 1;
+            return done();
+        }
+    }
+    st.tier = PerRow;
+    if (p.hops.size() != 1) throw GrbError(FGPU_INVALID, "SemiApply: a fused chain that the batch path declines has no per-row form");
+    for (u64 c = 0; c < n; ++c) {
+        std::vector<std::array<u64, 3>> out;
+        p.expand_row(g, lf[c].id, lt[c].kind == Value::Node ? std::optional<u64>(lt[c].id) : std::nullopt, transposed, {}, out);
+        if (!out.empty()) matched[live[c]] = 1;
+    }
+    done();
+}
+
+void SemiApplyOp::filter_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to, bool transposed,
+                               std::vector<u64>& passing, Stats* stats) const {
+    std::vector<uint8_t> matched;
+    match_batch(g, from, to, transposed, matched, stats);
+    passing.clear();
+    for (u64 i = 0; i < matched.size(); ++i)
+        if ((matched[i] != 0) != anti) passing.push_back(i);
+}
+
+void OrApplyMultiplexerOp::filter_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to,
+                                        std::vector<u64>& passing, std::vector<SemiApplyOp::Stats>* stats) const {
+    const u64 k = from.size();
+    std::vector<uint8_t> pass(k, 0), matched;
+    if (stats) stats->assign(branches.size(), SemiApplyOp::Stats{});
+    for (size_t b = 0; b < branches.size(); ++b) {
+        const Branch& br = branches[b];
+        if (br.semi) {
+            br.semi->match_batch(g, from, to, br.transposed, matched, stats ? &(*stats)[b] : nullptr);
+        } else {
+            if (br.column.size() != k) throw GrbError(FGPU_INVALID, "OrApplyMultiplexer: a column branch needs one byte per row");
+            matched = br.column;
+        }
+        for (u64 i = 0; i < k; ++i)
+            if ((matched[i] != 0) != br.anti) pass[i] = 1;
+    }
+    passing.clear();
+    for (u64 i = 0; i < k; ++i)
+        if (pass[i]) passing.push_back(i);
+}
+
 // ---- CondVarLenTraverse ---------------------------------------------------------------------------------
 namespace {
 struct VlEdge { u64 src, dst, id; };

@@ -740,6 +740,53 @@ struct ExpandIntoOp {
                       std::vector<std::vector<std::array<u64, 3>>>& out) const;
 };
 
+// SemiApply / AntiSemiApply (runtime/ops/semi_apply.rs:85-106): a row passes iff (the right branch emits at least one row for
+// it) XOR anti.  The right branch is `pattern` fed by the argument batch — the planner's CondTraverse or ExpandInto over the
+// pattern predicate (planner/mod.rs:1279-1392).  The reference runs the branch over the batch, emits every match and keeps
+// the set of origin rows; a predicate is one bit per row, so the answer comes from one of three tiers, all row-equal:
+//   Exists    nothing is expanded.  The matrix path (batched_eligible(), fused chains included) with no row's `to` bound is one
+//             fgpu_expand_exists — types, labels and layers resolved as expand_batch resolves them; with every row's `to`
+//             bound it is expand_batch's probe (the ExpandInto shape); a bidirectional single hop that emits no relationship
+//             and has no sibling edges, `to` unbound, is two fgpu_expand_exists, over the forward and over the transposed
+//             layers, OR-ed (the forward pass already sees the self-loops the reverse pass drops).
+//   Collect   any other batch-eligible shape, and everything when device_exists is false: expand_batch / expand_batch_edges
+//             and the rows that occur — the reference's own method, the baseline.
+//   PerRow    otherwise, expand_row row by row.
+// A row whose bound alias is Null or not a node emits nothing, so it does not match, and costs no device work.
+struct SemiApplyOp {
+    CondTraverseOp pattern;
+    bool anti = false;
+    bool device_exists = true;
+    enum Tier { NoRows = 0, Exists = 1, Collect = 2, PerRow = 3 };
+    struct Stats {
+        int tier = NoRows;
+        u64 calls = 0;                    // fgpu_expand_exists calls made
+        u64 device[4] = {0, 0, 0, 0};     // their stats summed ([3]: the form of the last call)
+    };
+    // matched[i] = the branch emits for row i (before `anti`).  `to` nullable: no row has it bound.  `transposed` as
+    // expand_row / expand_batch_edges take it: the bound alias `from` is the matrix destination
+    void match_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to, bool transposed,
+                     std::vector<uint8_t>& matched, Stats* stats = nullptr) const;
+    // the passing input rows, ascending
+    void filter_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to, bool transposed,
+                      std::vector<u64>& passing, Stats* stats = nullptr) const;
+};
+
+// OrApplyMultiplexer (runtime/ops/or_apply_multiplexer.rs:85-123): every branch sees all rows; a row passes when any branch
+// passes, an anti branch inverted by itself.  A branch is a pattern (its SemiApplyOp's own `anti` is not read: the branch's
+// flag is) or a caller-supplied boolean column — a filter branch such as `p.id = 0`, which needs the attribute store.
+struct OrApplyMultiplexerOp {
+    struct Branch {
+        std::optional<SemiApplyOp> semi;   // empty: `column`
+        std::vector<uint8_t> column;       // one byte per row
+        bool anti = false;
+        bool transposed = false;
+    };
+    std::vector<Branch> branches;
+    void filter_batch(const Graph& g, const std::vector<Value>& from, const std::vector<Value>* to, std::vector<u64>& passing,
+                      std::vector<SemiApplyOp::Stats>* stats = nullptr) const;
+};
+
 // CondVarLenTraverse (runtime/ops/cond_var_len_traverse.rs:81-387): the per-row DFS of `(a)-[:T*min..max]->(b)` with
 // Cypher trail semantics (a relationship is used at most once per path, nodes may repeat), in the reference's emission
 // order: frames leave a LIFO stack, a frame's emissions follow its adjacency order (types in order; per type the

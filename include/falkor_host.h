@@ -230,6 +230,23 @@ int fh_cond_traverse_edges_batch(fh_graph* g, const char* spec, const int64_t* f
                                  int transposed, int cross_row_dedup, const uint64_t* used_edges, uint64_t n_used, int* batched,
                                  uint64_t** out_row, uint64_t** out_from, uint64_t** out_to, uint64_t** out_edge, uint64_t* n,
                                  uint64_t** null_rows, uint64_t* n_null, uint64_t stats[8]);
+/* SemiApply / AntiSemiApply (semi_apply.rs:85-106) over one argument batch: the pattern predicate `WHERE (a)-[:T]->()`,
+ * `WHERE NOT ...`, the anti-join `WHERE NOT (a)-[:T]->(c)`.  spec: the CondTraverse spec above, the right branch.  from_ids /
+ * to_ids as fh_cond_traverse_rows takes them (a node id, -1 unbound, -2 Null or not a node: such a row emits nothing, so it does
+ * not match); to_ids nullable: no row has it bound.  A row passes iff (the branch emits for it) XOR anti; *passing (fh_free):
+ * the passing input rows, ascending.  *tier (nullable): 1 the existence tier answered (fgpu_expand_exists, or the probe when
+ * every row has `to` bound: nothing expanded), 2 the collect tier (the pairs expanded and the rows that occur: the reference's
+ * method, and all that runs with device_exists == 0), 3 row by row, 0 no row could match.  stats (nullable): fgpu_expand_exists'
+ * four summed over the calls made, then the number of calls. */
+int fh_semi_apply(fh_graph* g, const char* spec, int anti, int device_exists, const int64_t* from_ids, const int64_t* to_ids,
+                  uint64_t k, int transposed, uint64_t** passing, uint64_t* n, int* tier, uint64_t stats[5]);
+/* OrApplyMultiplexer (or_apply_multiplexer.rs:85-123): n_branches branches over the same rows; a row passes when any branch
+ * passes, branch b inverted when anti[b].  Branch b is the pattern specs[b], or — specs[b] NULL — the caller's boolean column
+ * columns[b] (k bytes: a filter branch such as `p.id = 0`).  anti / transposed nullable (all 0); tiers (n_branches) and stats
+ * (5 per branch) nullable, per branch as fh_semi_apply reports them. */
+int fh_or_apply(fh_graph* g, const char* const* specs, const uint8_t* const* columns, const int* anti, const int* transposed,
+                int n_branches, int device_exists, const int64_t* from_ids, const int64_t* to_ids, uint64_t k,
+                uint64_t** passing, uint64_t* n, int* tiers, uint64_t* stats);
 /* types: comma list ("" = all).  batched != 0 runs the whole input through one set of device probes. */
 int fh_expand_into(fh_graph* g, const char* types, int bidirectional, int emit_relationship, int batched,
                    const uint64_t* srcs, const uint64_t* dsts, uint64_t k, uint64_t** out_row,

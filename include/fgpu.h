@@ -498,6 +498,24 @@ fgpu_info fgpu_expand_probe(fgpu_ctx* ctx, const uint64_t* src_ids, const uint64
                             const fgpu_mat* const* m, const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
                             const uint64_t* dst_label_bitmap, uint8_t* present, uint64_t* flops);
 
+/* The same chain as a PATTERN PREDICATE — `WHERE (p)-[:KNOWS]->()`, `WHERE NOT ...`, the right branch of SemiApply /
+ * AntiSemiApply / OrApplyMultiplexer with an unbound destination (semi_apply.rs:85-106; the reference runs the branch over
+ * the batch, emits every match and keeps the set of origin rows).  Contract: bit i of match_bits is set iff row i of
+ * fgpu_expand over the same arguments is non-empty.  The conventions are fgpu_expand's and fgpu_expand_probe's:
+ * src_ids[i] == UINT64_MAX leaves row i empty, dp / dm are nullable as arrays and per hop, hypersparse layers are taken, the
+ * errors are fgpu_expand's.  The hops before the last run as in fgpu_expand; the last hop is NOT expanded: a row matches as
+ * soon as one frontier vertex has a label-passing dp entry, or a label-passing m entry whose column no entry of the last dm
+ * names (no tombstone can mask it for any row).  The last hop's rule is the row-level mask (F·m)<not (F·dm)> U (F·dp), so the
+ * rows that reach only columns named by dm are undecided: they run the whole chain once more, those rows alone.
+ *   match_bits   HOST array of (nsrc + 63) / 64 words, bit i & 63 of word i >> 6; the padding bits past nsrc are 0.
+ *   flops        nullable: the traversed edges of the hops that ran (hops 0 .. nhops - 2 of the call; not the exact pass).
+ *   stats        nullable: [0] rows matched, [1] undecided rows sent through the exact pass, [2] adjacency entries the last
+ *                step read (all layers), [3] the form that answered: 0 a sorted-CSR frontier, 1 the bit state.
+ * nsrc == 0 is a no-op. */
+fgpu_info fgpu_expand_exists(fgpu_ctx* ctx, const uint64_t* src_ids, uint64_t nsrc, const fgpu_mat* const* m,
+                             const fgpu_mat* const* dp, const fgpu_mat* const* dm, int nhops,
+                             const uint64_t* dst_label_bitmap, uint64_t* match_bits, uint64_t* flops, uint64_t stats[4]);
+
 /* One tensor's multi-edge rows (`me`, tensor.rs:184-205) resident on the device, in the shape fgpu_edges_build returns them and
  * fgpu_edges_remove checks them: n_multi keys src << 32 | dst strictly ascending, off[0] = 0, every run at least 2 ids long and
  * strictly ascending, no id equal to FGPU_MULTI_EDGE.  Host arrays in (copied); n_multi == 0 gives an empty table.  A malformed
