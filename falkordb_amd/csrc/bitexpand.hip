@@ -1978,32 +1978,50 @@ fgpu_info bp_hop(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* 
 // nsrc bits per row, and the checksum's sum of (row hash) x (destination hash) over a block of ones factors into
 // (sum of the bits' hashes) x (sum of the rows' hashes).  The test reads the device's own state, never what the host believes
 // about the sources (spgemm.hip orders a scan's sources so that whole passes pass it; nothing here relies on that).
-// out[0] = 1 when row `slot` of x is nsrc ones and nothing else; out[1] = the sum of the bits' checksum hashes
-__global__ __launch_bounds__(256) void bp_hub_check_kernel(const u64* __restrict__ x, u32 slot, u32 ws, u32 nsrc, const u32* __restrict__ rowmap,
-                                                           const u64* __restrict__ rowhash, u64* __restrict__ out) {
+// out[0] = the level the state saturates: 2 when the rows of ALL `nh` hubs of the set (slots[0 .. nh), slots[0] = the top hub's) hold
+// nsrc ones and nothing else, 1 when the top hub's row `slot` alone does, 0 otherwise (slots = nullptr: the plan has no set, the
+// answer is 0 or 1); out[1] = the sum of the bits' checksum hashes.  A slot beyond the n rows of x saturates nothing
+__global__ __launch_bounds__(256) void bp_hub_check_kernel(const u64* __restrict__ x, u32 n, u32 slot, const u32* __restrict__ slots, u32 nh,
+                                                           u32 ws, u32 nsrc, const u32* __restrict__ rowmap, const u64* __restrict__ rowhash,
+                                                           u64* __restrict__ out) {
     __shared__ u64 s_h[4];
-    bool bad = false;
-    for (u32 k = threadIdx.x; k < ws; k += 256) {
-        const u32 lo = k * 64;
+    __shared__ u32 s_bad[2];
+    if (threadIdx.x < 2) s_bad[threadIdx.x] = 0u;
+    __syncthreads();
+    if (!slots) nh = 1;
+    bool bad1 = false, bad2 = false;                         // a word of the top hub's row / of another hub's row is not all ones
+    for (u32 k = threadIdx.x; k < nh * ws; k += 256) {
+        const u32 i = k / ws, wd = k - i * ws;
+        const u32 r = i ? slots[i] : slot;
+        const u32 lo = wd * 64;
         const u64 want = nsrc >= lo + 64 ? ~0ull : nsrc > lo ? (1ull << (nsrc - lo)) - 1ull : 0ull;   // (the last word may be partial)
-        bad |= x[(size_t)slot * ws + k] != want;
+        const bool bad = r >= n || x[(size_t)r * ws + wd] != want;
+        if (i) bad2 |= bad;
+        else bad1 |= bad;
     }
     u64 hs = 0;
     for (u32 i = threadIdx.x; i < nsrc; i += 256) hs += rowhash ? rowhash[i] : cs_row_hash(rowmap ? (u64)rowmap[i] : (u64)i);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) hs += (u64)__shfl_xor((long long)hs, d, 64);
     if (lane_id() == 0) s_h[threadIdx.x >> 6] = hs;
-    const int nbad = __syncthreads_count(bad ? 1 : 0);
+    if (bad1) s_bad[0] = 1u;
+    if (bad2) s_bad[1] = 1u;
+    __syncthreads();
     if (threadIdx.x == 0) {
-        out[0] = nbad == 0 && nsrc ? 1ull : 0ull;
+        const u32 level = s_bad[0] || !nsrc ? 0u : (nh >= 2 && !s_bad[1]) ? 2u : 1u;
+        out[0] = level;
         out[1] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
     }
 }
-// the sums of the rows out(h), all of nsrc ones: acc[0] += nsrc per counted row, acc[1] += (hash sum of the bits) x (hash of the
-// row).  Without a label every row counts and the plan's constants say it all (one thread); with one, a pass over the list
+// the sums of the rows the closed form covers, all of nsrc ones — LEVEL 1: out(h), LEVEL 2: the union of the hub set's out-rows,
+// each once (the level is a template parameter so that a kernel trace tells the two apart): acc[0] += nsrc per counted row,
+// acc[1] += (hash sum of the bits) x (hash of the row).  Without a label every row counts and the plan's constants say it all
+// (one thread); with one, a pass over the list
+template <int LEVEL>
 __global__ __launch_bounds__(256) void bp_hub_sums_kernel(const u32* __restrict__ rows, u32 deg, u64 dsum, const u64* __restrict__ label,
                                                           u32 nsrc, const u64* __restrict__ hsum, int with_sum,
                                                           unsigned long long* __restrict__ acc) {
+    static_assert(LEVEL == 1 || LEVEL == 2, "one reduced plan, or two");
     u64 cnt = 0, ds = 0;
     if (!label) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { cnt = deg; ds = dsum; }
@@ -2015,7 +2033,8 @@ __global__ __launch_bounds__(256) void bp_hub_sums_kernel(const u32* __restrict_
     }
     bp_block_add2(cnt * nsrc, with_sum ? ds * hsum[0] : 0ull, acc);
 }
-// *hub = the reduced plan when the state saturates the hub's row (its rows' sums are then in acc already), nullptr otherwise
+// *hub = the deepest reduced plan whose hubs' rows the state saturates (the sums of the rows it leaves out are then in acc
+// already), nullptr when it does not saturate the top hub's.  One check kernel and one read-back whatever the levels
 static fgpu_info bp_hub_rows(fgpu_ctx* ctx, const BitState& s, const BpXPlan* xp, int mode, const u64* label_dev, u64* acc,
                              const BpXPlan** hub) {
     *hub = nullptr;
@@ -2023,17 +2042,28 @@ static fgpu_info bp_hub_rows(fgpu_ctx* ctx, const BitState& s, const BpXPlan* xp
     if (!bp_xplan_hub(xp, &hb) || hb.slot >= s.n || !s.nsrc) return FGPU_OK;
     DevBuf<u64> chk;
     FGPU_TRY(chk.alloc(ctx, 2));
-    FGPU_TRY(launch(bp_hub_check_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, hb.slot, s.ws, s.nsrc,
-                    (const u32*)s.rowmap.p, (const u64*)s.rowhash.p, chk.p));
-    u32 sat = 0;
-    FGPU_TRY(read_u32(ctx, (const u32*)chk.p, &sat));
-    if (!sat) return FGPU_OK;
-    ProfScope ps(ctx, "xp_hub_rows", (u64)hb.deg * (label_dev ? 4 : 0));
-    u32 grid = label_dev ? cdiv(hb.deg, 256) : 1u;
+    FGPU_TRY(launch(bp_hub_check_kernel, dim3(1), dim3(256), 0, ctx->stream(), (const u64*)s.x.p, s.n, hb.slot,
+                    hb.set_plan ? hb.set_slots : nullptr, hb.set_plan ? hb.set_n : 1u, s.ws, s.nsrc, (const u32*)s.rowmap.p,
+                    (const u64*)s.rowhash.p, chk.p));
+    u32 level = 0;
+    FGPU_TRY(read_u32(ctx, (const u32*)chk.p, &level));
+    if (!level) return FGPU_OK;
+    const bool set = level >= 2 && hb.set_plan;
+    const u32 deg = set ? hb.set_deg : hb.deg;
+    ProfScope ps(ctx, "xp_hub_rows", (u64)deg * (label_dev ? 4 : 0));
+    u32 grid = label_dev ? cdiv(deg, 256) : 1u;
     if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
-    FGPU_TRY(launch(bp_hub_sums_kernel, dim3(grid), dim3(256), 0, ctx->stream(), hb.rows, hb.deg, hb.dsum, label_dev, s.nsrc,
-                    (const u64*)(chk.p + 1), mode == 2 ? 1 : 0, (unsigned long long*)acc));
-    *hub = hb.plan;                                          // (chk returns to this lane's pool: reused in stream order)
+    const u64* hsum = chk.p + 1;
+    const int with_sum = mode == 2 ? 1 : 0;
+    if (set) {
+        ProfScope ps2(ctx, "xp_hub_set", 0);
+        FGPU_TRY(launch(bp_hub_sums_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream(), hb.set_rows, deg, hb.set_dsum, label_dev, s.nsrc,
+                        hsum, with_sum, (unsigned long long*)acc));
+    } else {
+        FGPU_TRY(launch(bp_hub_sums_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream(), hb.rows, deg, hb.dsum, label_dev, s.nsrc, hsum,
+                        with_sum, (unsigned long long*)acc));
+    }
+    *hub = set ? hb.set_plan : hb.plan;                      // (chk returns to this lane's pool: reused in stream order)
     return FGPU_OK;
 }
 
@@ -2064,8 +2094,10 @@ fgpu_info bp_hop_count(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu
 
 // *in_bits = the in-neighbours of m's top hub, a bit per vertex, when a count hop over m from a state of `nsrc` bits per row has a
 // reduced plan to run under (nullptr otherwise): what a whole-frontier scan orders its sources by
-fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64** in_bits) {
+fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64** in_bits, const u32** hub_mask, u32* set_n) {
     *in_bits = nullptr;
+    *hub_mask = nullptr;
+    *set_n = 0;
     BitState lay;
     bp_layout(lay, (u32)m->nrows, nsrc);
     if (!m->nnz || m->is_hyper() || !bp_xcd_applies(ctx, lay.n, lay.ws)) return FGPU_OK;
@@ -2074,7 +2106,10 @@ fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64*
     BpXHub hb;
     FGPU_TRY(transposed_with_items(ctx, m, &t));
     FGPU_TRY(bp_xplan(ctx, m, t, &xp));
-    if (bp_xplan_hub(xp, &hb)) *in_bits = hb.in_bits;
+    if (bp_xplan_hub(xp, &hb)) {
+        *in_bits = hb.in_bits;
+        if (hb.set_plan) { *hub_mask = hb.hub_mask; *set_n = hb.set_n; }
+    }
     return FGPU_OK;
 }
 

@@ -59,6 +59,15 @@ struct BpXHub {
     u64 dsum;                // sum of cs_dest_hash over out(h)
     const u32* rows;         // out(h), deg entries
     const u64* in_bits;      // bit u: (u, h) is an entry of the matrix
+    // the second level: the hub set H (H[0] = h) and the plan with the rows of the union of out(H[i]) emptied; set_plan =
+    // nullptr when the plan has none (one hub, or the union's extra rows hold under an eighth of the entries)
+    const BpXPlan* set_plan = nullptr;
+    u32 set_n = 0;                    // |H|, at most 32
+    const u32* set_slots = nullptr;   // [set_n] H[i]'s row of X in the plan's layout (device)
+    u32 set_deg = 0;                  // rows of the union, each once
+    u64 set_dsum = 0;                 // sum of cs_dest_hash over the union
+    const u32* set_rows = nullptr;    // the union, set_deg entries
+    const u32* hub_mask = nullptr;    // a word per vertex u: bit i says (u, H[i]) is an entry of the matrix
 };
 bool bp_xplan_hub(const BpXPlan* xp, BpXHub* out);
 // rows of Y = OR of the gathered rows of X, per vertex, counted / check-summed (mode 1 / 2) or — touched rows — stored into

@@ -25,6 +25,8 @@
 // issued — at every use of a load (the first version wrote finished runs every trip: 723 us).
 // No row is long or short: an in-hub with 20 K entries in a partition is a few dozen chunks of one run each, whose pieces
 // meet in the (pre-zeroed) partial row through atomics — the only atomics of the kernel, at most two rows per chunk.
+#include <algorithm>
+
 #include "bitexpand.hpp"
 
 namespace fgpu {
@@ -89,6 +91,19 @@ struct BpXPlan {
     u64 hub_dsum = 0;              // sum of cs_dest_hash(v) over out(h), mod 2^64
     DevBuf<u32> hub_rows;          // out(h), as m lists it
     DevBuf<u64> hub_in;            // bit u: u has an edge to h in m (ncols bits): what a scan orders its sources by (spgemm.hip)
+    u64 hub_gone = 0;              // entries of A' in the rows out(h)
+    // the hub set H (bp_xplan_hub_set_build below): h and the rows of m with at least a quarter of its entries, at most
+    // XP_HUB_SET_MAX of them, by (entries descending, id ascending) — H[0] = h.  When EVERY row slot(H[i]) of X is all ones the hop
+    // runs under `hub2`, the plan of A' with the rows of the union of out(H[i]) emptied (same layout of X again), and the closed
+    // form covers that union.  Kept only beside a level-1 plan.
+    BpXPlanPtr hub2;               // null: no second level (|H| < 2, the extra rows' share under XP_HUB_SET_MIN_SHARE, build failed)
+    u32 hset_n = 0;                // |H|
+    u32 hset_v[32] = {};           // H
+    DevBuf<u32> hset_slots;        // [hset_n] slot of H[i] in X
+    u32 hset_deg = 0;              // rows in the union of out(H[i]), each once
+    u64 hset_dsum = 0;             // sum of cs_dest_hash over them
+    DevBuf<u32> hset_rows;         // the union, ascending
+    DevBuf<u32> hub_mask;          // [ncols of A'] bit i of word u: (u, H[i]) is an entry of m
     const BpXPlan* full = nullptr; // on a reduced plan: the full plan that owns it
 };
 const u32* bp_xplan_perm(const BpXPlan* p) { return p ? p->perm.p : nullptr; }
@@ -655,14 +670,186 @@ static fgpu_info bp_xplan_hub_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu
     FGPU_HIP(hipStreamSynchronize(st));
     xp->hub_v = h; xp->hub_slot = slot; xp->hub_deg = deg;
     xp->hub_dsum = (u64)got[2] | ((u64)got[3] << 32);
+    xp->hub_gone = gone;
     xp->hub_rows = std::move(list);
     reduced->full = xp;
     xp->hub = std::move(reduced);
     return FGPU_OK;
 }
+
+// ---- the hub set: the tier of hubs under the top one (once per plan, after the first reduced plan) -------------------------------
+// R-MAT has one top hub and then a tier of `scale` hubs of about 0.39 of its degree (at RMAT-22: hubs 2 .. 23, 38 K entries each,
+// before a third tier at 14 K).  With the rows of the union of their out-rows gone as well a plan holds 16 % of the entries of A'
+// instead of 44 %, and 55 % of the live sources of a label scan reach ALL 23 in exactly two hops.  The plans nest: a pass runs
+// under the deepest one whose hubs its state saturates (bitexpand.hip bp_hub_rows).  The quarter separates the second tier from
+// the third; the eighth is what the extra rows must hold for a third plan's memory to pay.
+constexpr u32 XP_HUB_SET_DEG_DEN = 4;         // H: the rows of m with at least 1 / 4 of the top hub's entries ...
+constexpr u32 XP_HUB_SET_MAX = 32;            // ... the 32 largest of them (a bit each of hub_mask's words)
+constexpr u32 XP_HUB_SET_MIN_SHARE_DEN = 8;   // the union's rows outside out(h) must hold at least 1 / 8 of the entries of A'
+constexpr u32 XP_HUB_SET_LIST = 1024;         // first bound of the list of qualifying rows (listed again at its true length beyond)
+static_assert(XP_HUB_SET_MAX == 32, "hub_mask is a u32 per vertex, BpXPlan::hset_v holds 32");
+// every row of m with at least `mindeg` entries as (entries << 32 | ~row), in no order, up to `cap`; *cnt = how many there are
+__global__ __launch_bounds__(256) void xp_hub_set_list_kernel(const u32* __restrict__ rowptr, u32 nrows, u32 mindeg, u32 cap,
+                                                              u64* __restrict__ keys, u32* __restrict__ cnt) {
+    for (u32 u = blockIdx.x * 256 + threadIdx.x; u < nrows; u += gridDim.x * 256) {
+        const u32 d = rowptr[u + 1] - rowptr[u];
+        if (d >= mindeg) {
+            const u32 i = atomicAdd(cnt, 1u);
+            if (i < cap) keys[i] = ((u64)d << 32) | (u64)(~u);
+        }
+    }
+}
+// drop[v] = 1 for every v of out(hs[blockIdx.y]) (hubs share out-neighbours: the same value from whoever stores it)
+__global__ __launch_bounds__(256) void xp_hub_set_rows_kernel(const u32* __restrict__ mrowptr, const u32* __restrict__ mcol,
+                                                              const u32* __restrict__ hs, u32 n, u32* __restrict__ drop) {
+    const u32 h = hs[blockIdx.y];
+    const u32 b = mrowptr[h], deg = mrowptr[h + 1] - b;
+    for (u32 i = blockIdx.x * 256 + threadIdx.x; i < deg; i += gridDim.x * 256) {
+        const u32 v = mcol[b + i];
+        if (v < n) drop[v] = 1u;
+    }
+}
+// over the flagged rows, each once: sums[0] = their entries in A', sums[1] = the sum of their destination hashes
+__global__ __launch_bounds__(256) void xp_hub_set_sums_kernel(const u32* __restrict__ trowptr, const u32* __restrict__ drop, u32 n,
+                                                              unsigned long long* __restrict__ sums) {
+    u64 ent = 0, ds = 0;
+    for (u32 v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
+        if (drop[v]) {
+            ent += trowptr[v + 1] - trowptr[v];
+            ds += cs_dest_hash(v);
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        ent += (u64)__shfl_xor((long long)ent, d, 64);
+        ds += (u64)__shfl_xor((long long)ds, d, 64);
+    }
+    if (lane_id() == 0) {
+        if (ent) atomicAdd(sums, (unsigned long long)ent);
+        if (ds) atomicAdd(sums + 1, (unsigned long long)ds);
+    }
+}
+// the flagged rows, ascending: pos = the exclusive scan of the flags
+__global__ void xp_hub_set_compact_kernel(const u32* __restrict__ drop, const u32* __restrict__ pos, u32 n, u32* __restrict__ list) {
+    for (u32 v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
+        if (drop[v]) list[pos[v]] = v;
+}
+// mask[u] |= 1 << i for every in-neighbour u of hs[i] (row hs[i] of A'), i = blockIdx.y
+__global__ __launch_bounds__(256) void xp_hub_set_mask_kernel(const u32* __restrict__ trowptr, const u32* __restrict__ tcol,
+                                                              const u32* __restrict__ hs, u32 n, u32 ncols, u32* __restrict__ mask) {
+    const u32 h = hs[blockIdx.y];
+    if (h >= n) return;
+    const u32 b = trowptr[h], e = trowptr[h + 1];
+    for (u32 q = b + blockIdx.x * 256 + threadIdx.x; q < e; q += gridDim.x * 256) {
+        const u32 u = tcol[q];
+        if (u < ncols) atomicOr(&mask[u], 1u << blockIdx.y);
+    }
+}
+__global__ void xp_hub_set_slots_kernel(const u32* __restrict__ hs, const u32* __restrict__ perm, u32 nh, u32* __restrict__ slots) {
+    if (threadIdx.x < nh) slots[threadIdx.x] = perm ? perm[hs[threadIdx.x]] : hs[threadIdx.x];
+}
+
+// names the hub set of a plan that has its first reduced plan and, when the union's extra rows hold their share, builds the
+// second one beside it
+static fgpu_info bp_xplan_hub_set_build(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, int direct, int dense, int cut, BpXPlan* xp) {
+    if (!xp->hub || !xp->hub->usable || !xp->hub_deg) return FGPU_OK;
+    hipStream_t st = ctx->stream();
+    const u32 n = (u32)t->nrows, nu = (u32)m->nrows;
+    const u32 mindeg = cdiv(xp->hub_deg, XP_HUB_SET_DEG_DEN);
+    DevBuf<u64> keys;
+    DevBuf<u32> cnt;
+    FGPU_TRY(cnt.alloc(ctx, 1));
+    u32 grid = cdiv(nu, 256);
+    if (grid > (u32)ctx->cus * 8) grid = ctx->cus * 8;
+    u32 cap = XP_HUB_SET_LIST, found = 0;
+    for (int round = 0; round < 2; ++round) {                // (which rows a full list holds is up to the atomics: list them all)
+        FGPU_TRY(keys.alloc(ctx, cap));
+        FGPU_HIP(hipMemsetAsync(cnt.p, 0, sizeof(u32), st));
+        FGPU_TRY(launch(xp_hub_set_list_kernel, dim3(grid), dim3(256), 0, st, (const u32*)m->rowptr, nu, mindeg, cap, keys.p, cnt.p));
+        FGPU_TRY(read_u32(ctx, cnt.p, &found));
+        if (found <= cap) break;
+        cap = found;
+    }
+    if (found < 2 || found > cap) return FGPU_OK;
+    std::vector<u64> hk(found);
+    FGPU_TRY(ctx->d2h(hk.data(), keys.p, (size_t)found * sizeof(u64)));
+    std::sort(hk.begin(), hk.end(), [](u64 a, u64 b) { return a > b; });   // entries descending, ids ascending
+    const u32 nh = found < XP_HUB_SET_MAX ? found : XP_HUB_SET_MAX;
+    u32 hv[XP_HUB_SET_MAX] = {};
+    for (u32 i = 0; i < nh; ++i) hv[i] = ~(u32)hk[i];
+    if (hv[0] != xp->hub_v) return FGPU_OK;
+    DevBuf<u32> hs, drop, pos, list, kd, rp, col, slots, mask;
+    DevBuf<u64> sums;
+    FGPU_TRY(hs.alloc(ctx, XP_HUB_SET_MAX));
+    FGPU_TRY(ctx->h2d(hs.p, hv, sizeof(hv)));
+    FGPU_TRY(drop.alloc(ctx, (size_t)n + 1));
+    FGPU_HIP(hipMemsetAsync(drop.p, 0, ((size_t)n + 1) * sizeof(u32), st));
+    FGPU_TRY(sums.alloc(ctx, 2));
+    FGPU_HIP(hipMemsetAsync(sums.p, 0, 2 * sizeof(u64), st));
+    grid = cdiv(xp->hub_deg, 256);                           // (no row of m is longer than the top hub's)
+    if (grid > (u32)ctx->cus * 4) grid = ctx->cus * 4;
+    FGPU_TRY(launch(xp_hub_set_rows_kernel, dim3(grid, nh), dim3(256), 0, st, (const u32*)m->rowptr, (const u32*)m->colidx,
+                    (const u32*)hs.p, n, drop.p));
+    FGPU_TRY(launch(xp_hub_set_sums_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)drop.p, n,
+                    (unsigned long long*)sums.p));
+    u32 got[4];
+    FGPU_TRY(read_words(ctx, (const u32*)sums.p, 4, got));
+    const u64 gone = (u64)got[0] | ((u64)got[1] << 32);
+    if (gone < xp->hub_gone || gone >= t->nnz) return FGPU_OK;                    // (nothing would be left)
+    if ((gone - xp->hub_gone) * XP_HUB_SET_MIN_SHARE_DEN < t->nnz) return FGPU_OK;  // (too small a share beyond out(h))
+    // the union, each row once
+    FGPU_TRY(pos.alloc(ctx, (size_t)n + 1));
+    FGPU_TRY(scan_u32(ctx, drop.p, pos.p, (u64)n + 1, nullptr));
+    u32 nrows_u = 0;
+    FGPU_TRY(read_u32(ctx, pos.p + n, &nrows_u));
+    FGPU_REQUIRE(nrows_u >= xp->hub_deg && nrows_u <= n, FGPU_INVALID, "partitioned pull: the hub set's union holds %u rows, the top hub's %u",
+                 nrows_u, xp->hub_deg);
+    FGPU_TRY(list.alloc(ctx, nrows_u));
+    FGPU_TRY(launch(xp_hub_set_compact_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)drop.p, (const u32*)pos.p, n, list.p));
+    // t'': the union's rows emptied, as bp_xplan_hub_build empties out(h)
+    FGPU_TRY(kd.alloc(ctx, (size_t)n + 1));
+    FGPU_TRY(rp.alloc(ctx, (size_t)n + 1));
+    FGPU_TRY(launch(xp_hub_kept_kernel, dim3(ctx->cus * 8), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)drop.p, n, kd.p));
+    FGPU_TRY(scan_u32(ctx, kd.p, rp.p, (u64)n + 1, nullptr));
+    u32 kept = 0;
+    FGPU_TRY(read_u32(ctx, rp.p + n, &kept));
+    FGPU_REQUIRE(kept >= 1 && (u64)kept + gone == t->nnz, FGPU_INVALID, "partitioned pull: the hub set's rows hold %llu of %llu entries, %u stay",
+                 (unsigned long long)gone, (unsigned long long)t->nnz, kept);
+    FGPU_TRY(col.alloc(ctx, kept));
+    FGPU_TRY(launch(xp_hub_compact_kernel, dim3(ctx->cus * 16), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)t->colidx,
+                    (const u32*)rp.p, n, col.p));
+    const XpSource src = {rp.p, col.p, t->nrows, t->ncols, kept};
+    BpXPlanPtr reduced;
+    FGPU_TRY(bp_xplan_build(ctx, m, &src, direct, dense, cut, xp, &reduced));   // (synchronised: t'' may go)
+    FGPU_TRY(mask.alloc(ctx, (size_t)t->ncols + 1));
+    FGPU_HIP(hipMemsetAsync(mask.p, 0, ((size_t)t->ncols + 1) * sizeof(u32), st));
+    FGPU_TRY(launch(xp_hub_set_mask_kernel, dim3(64, nh), dim3(256), 0, st, (const u32*)t->rowptr, (const u32*)t->colidx,
+                    (const u32*)hs.p, n, (u32)t->ncols, mask.p));
+    FGPU_TRY(slots.alloc(ctx, XP_HUB_SET_MAX));
+    FGPU_TRY(launch(xp_hub_set_slots_kernel, dim3(1), dim3(64), 0, st, (const u32*)hs.p, (const u32*)xp->perm.p, nh, slots.p));
+    FGPU_HIP(hipStreamSynchronize(st));
+    xp->hset_n = nh;
+    memcpy(xp->hset_v, hv, sizeof(hv));
+    xp->hset_slots = std::move(slots);
+    xp->hset_deg = nrows_u;
+    xp->hset_dsum = (u64)got[2] | ((u64)got[3] << 32);
+    xp->hset_rows = std::move(list);
+    xp->hub_mask = std::move(mask);
+    reduced->full = xp;
+    xp->hub2 = std::move(reduced);
+    return FGPU_OK;
+}
 bool bp_xplan_hub(const BpXPlan* xp, BpXHub* out) {
     if (!xp || !xp->hub || !xp->hub->usable) return false;
     *out = BpXHub{xp->hub.get(), xp->hub_slot, xp->hub_deg, xp->hub_dsum, xp->hub_rows.p, xp->hub_in.p};
+    if (xp->hub2 && xp->hub2->usable) {
+        out->set_plan = xp->hub2.get();
+        out->set_n = xp->hset_n;
+        out->set_slots = xp->hset_slots.p;
+        out->set_deg = xp->hset_deg;
+        out->set_dsum = xp->hset_dsum;
+        out->set_rows = xp->hset_rows.p;
+        out->hub_mask = xp->hub_mask.p;
+    }
     return true;
 }
 
@@ -690,6 +877,12 @@ fgpu_info bp_xplan(fgpu_ctx* ctx, const fgpu_mat* m, const fgpu_mat* t, const Bp
         } else if (bp_xplan_hub_build(ctx, m, t, direct, dense, cut, xp.get()) != FGPU_OK) {
             // (the reduced plan is an accelerator of the accelerator: the full plan stays usable, and there is no second attempt)
             xp->hub.reset();
+            (void)hipStreamSynchronize(ctx->stream());
+            (void)hipGetLastError();
+            set_error("%s", "");
+        } else if (bp_xplan_hub_set_build(ctx, m, t, direct, dense, cut, xp.get()) != FGPU_OK) {
+            // (likewise one level down: the full plan and the first reduced plan stay exactly as they are)
+            xp->hub2.reset();
             (void)hipStreamSynchronize(ctx->stream());
             (void)hipGetLastError();
             set_error("%s", "");

@@ -615,8 +615,10 @@ fgpu_info bp_count(fgpu_ctx* ctx, const BitState& s, const u64* label_dev, u64* 
 fgpu_info bp_hop_count(fgpu_ctx* ctx, BitState& s, const fgpu_mat* m, const fgpu_mat* dp, const fgpu_mat* dm, u64* flops,
                        const u64* label_dev, u64* nnz, u64* checksum);
 // the in-neighbours of m's top hub as a bitmap, when a count hop over m from `nsrc`-bit rows can skip that hub's out-rows
-// (bitpart.hip bp_xplan_hub; *in_bits = nullptr otherwise).  Builds and caches the hop's plan like the hop itself would
-fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64** in_bits);
+// (bitpart.hip bp_xplan_hub; *in_bits = nullptr otherwise).  Builds and caches the hop's plan like the hop itself would.
+// *hub_mask = a word per vertex u, bit i: (u, H[i]) is an entry, H the set of *set_n hubs of the second reduced plan (H[0] = the
+// top hub), when the plan has one (nullptr, 0 otherwise)
+fgpu_info bp_count_hub_in(fgpu_ctx* ctx, const fgpu_mat* m, u32 nsrc, const u64** in_bits, const u32** hub_mask, u32* set_n);
 // u |= x (u is allocated, zeroed, on first use): DISTINCT union over the hops of a [*1..k] pattern
 fgpu_info bp_accumulate(fgpu_ctx* ctx, BitState& u, const BitState& x);
 // The chain is done with `s`: its block goes back to the pool, re-zeroed by its flagged rows and marked "zero" when that is

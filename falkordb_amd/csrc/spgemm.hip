@@ -1368,34 +1368,71 @@ __global__ void scan_strong_kernel(const u32* __restrict__ lid, u32 nlive, CsrVi
     }
     weak[i] = w;
 }
+// With a second reduced plan (bitpart.hip bp_xplan_hub_set_build) the strong sources come in two tiers: tier A reaches EVERY hub of
+// the set H in exactly two hops — its passes run under the second plan — tier B reaches the top hub but not all of H.  The list
+// becomes A, B, weak, each in its old order.  mask[t] = bit i: t has an edge to H[i]; `all` = the nh low bits.
+// mid[i] = 1 when live row i is of tier B, weak[i] = 1 when it is weak (both 0 at i = nlive, for the scans' totals)
+__global__ void scan_tier_kernel(const u32* __restrict__ lid, u32 nlive, CsrView m0, const u32* __restrict__ mask, u32 nbits, u32 all,
+                                 u32* __restrict__ mid, u32* __restrict__ weak) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nlive) return;
+    u32 got = all;
+    if (i < nlive) {
+        u32 b, e;
+        row_range(m0, lid[i], b, e);
+        got = 0;
+        for (u32 q = b; q < e && got != all; ++q) {
+            const u32 t = m0.colidx[q];
+            if (t < nbits) got |= mask[t] & all;
+        }
+    }
+    mid[i] = (got & 1u) && got != all ? 1u : 0u;
+    weak[i] = (got & 1u) ? 0u : 1u;
+}
+// mid / mpos = nullptr: two tiers (strong, weak)
 __global__ void scan_strong_move_kernel(const u32* __restrict__ lid, const u32* __restrict__ lrow, const u32* __restrict__ weak,
-                                        const u32* __restrict__ wpos, u32 nlive, u32* __restrict__ olid, u32* __restrict__ olrow) {
+                                        const u32* __restrict__ wpos, const u32* __restrict__ mid, const u32* __restrict__ mpos,
+                                        u32 nlive, u32* __restrict__ olid, u32* __restrict__ olrow) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nlive) return;
-    const u32 p = weak[i] ? nlive - wpos[nlive] + wpos[i] : i - wpos[i];
+    const u32 nweak = wpos[nlive], nmid = mid ? mpos[nlive] : 0u, mbefore = mid ? mpos[i] : 0u;
+    const u32 p = weak[i]               ? nlive - nweak + wpos[i]
+                  : (mid && mid[i])     ? nlive - nweak - nmid + mbefore
+                                        : i - wpos[i] - mbefore;
     olid[p] = lid[i];
     olrow[p] = lrow[i];
 }
 // reorders (lid, lrow) strong-first when the call is a clean 3-hop chain whose last two hops run over one snapshot that has a
-// reduced plan for the count hop; leaves them alone otherwise
+// reduced plan for the count hop — tier A, tier B, weak when it has two; leaves them alone otherwise
 static fgpu_info scan_strong_first(fgpu_ctx* ctx, const Layers& L, DevBuf<u32>& lid, DevBuf<u32>& lrow, u32 nlive, u32 pass_rows) {
     if (L.nhops != 3 || L.m[1] != L.m[2] || L.m[0]->ncols != L.m[1]->nrows) return FGPU_OK;
     for (int h = 0; h < 3; ++h)
         if ((L.dp_at(h) && L.dp_at(h)->nnz) || (L.dm_at(h) && L.dm_at(h)->nnz)) return FGPU_OK;
     const u64* in_h = nullptr;
-    FGPU_TRY(bp_count_hub_in(ctx, L.m[2], pass_rows, &in_h));
+    const u32* mask = nullptr;
+    u32 nh = 0;
+    FGPU_TRY(bp_count_hub_in(ctx, L.m[2], pass_rows, &in_h, &mask, &nh));
     if (!in_h) return FGPU_OK;
     ProfScope ps(ctx, "scan strong first", 0);
-    DevBuf<u32> weak, wpos, olid, olrow;
+    DevBuf<u32> weak, wpos, mid, mpos, olid, olrow;
     FGPU_TRY(weak.alloc(ctx, (size_t)nlive + 1));
     FGPU_TRY(wpos.alloc(ctx, (size_t)nlive + 1));
     FGPU_TRY(olid.alloc(ctx, nlive));
     FGPU_TRY(olrow.alloc(ctx, nlive));
-    FGPU_TRY(launch(scan_strong_kernel, dim3(cdiv((u64)nlive + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)lid.p, nlive,
-                    view_of(L.m[0]), in_h, (u32)L.m[1]->nrows, weak.p));
+    if (mask && nh >= 2) {
+        FGPU_TRY(mid.alloc(ctx, (size_t)nlive + 1));
+        FGPU_TRY(mpos.alloc(ctx, (size_t)nlive + 1));
+        const u32 all = nh >= 32 ? 0xFFFFFFFFu : (1u << nh) - 1u;
+        FGPU_TRY(launch(scan_tier_kernel, dim3(cdiv((u64)nlive + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)lid.p, nlive,
+                        view_of(L.m[0]), mask, (u32)L.m[1]->nrows, all, mid.p, weak.p));
+        FGPU_TRY(scan_u32(ctx, mid.p, mpos.p, (u64)nlive + 1, nullptr));
+    } else {
+        FGPU_TRY(launch(scan_strong_kernel, dim3(cdiv((u64)nlive + 1, 256)), dim3(256), 0, ctx->stream(), (const u32*)lid.p, nlive,
+                        view_of(L.m[0]), in_h, (u32)L.m[1]->nrows, weak.p));
+    }
     FGPU_TRY(scan_u32(ctx, weak.p, wpos.p, (u64)nlive + 1, nullptr));
     FGPU_TRY(launch(scan_strong_move_kernel, dim3(cdiv(nlive, 256)), dim3(256), 0, ctx->stream(), (const u32*)lid.p, (const u32*)lrow.p,
-                    (const u32*)weak.p, (const u32*)wpos.p, nlive, olid.p, olrow.p));
+                    (const u32*)weak.p, (const u32*)wpos.p, (const u32*)mid.p, (const u32*)mpos.p, nlive, olid.p, olrow.p));
     lid = std::move(olid);
     lrow = std::move(olrow);
     return FGPU_OK;
