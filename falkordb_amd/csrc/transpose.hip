@@ -26,52 +26,15 @@
 // "the same stable sort with every scattered store staged through LDS"): 60 B per entry, but in runs of whole lines — 1.30 ms
 // against 2.43 ms for RMAT-22.  The two-level form above stays for narrow key spaces and as transpose_mode 3.
 #include "common.hpp"
+#include "sort_plan.hpp"
 
 namespace fgpu {
 
 constexpr u32 KS_INVALID = 0xFFFFFFFFu;   // value marking a dropped tuple (self-loops of the R-MAT generator)
-constexpr u32 KS_MAX_BUCKETS = 8192;      // pass-1 LDS cursors: 32 KiB
-constexpr u32 KS_MAX_WB = 13;             // pass-2 LDS counters: 4 quarters x 2^13 x 4 B = 128 KiB
-
-struct KsGeom {
-    u32 wb;     // low-digit bits
-    u32 B;      // buckets
-    u32 bbits;  // ballots needed to tell buckets apart
-    u32 EB;     // entries per pass-1 block
-    u32 nblk;   // pass-1 blocks
-};
 
 static int g_ks_wb_override = 0;   // experiment knob (option "transpose_wb"): low-digit bits, 0 = pick
 void ks_set_wb_override(int wb) { g_ks_wb_override = wb; }
-
-static bool ks_geometry(u64 n, u64 nkeys, KsGeom& g) {
-    u32 kb = 1;
-    while (kb < 32 && (1ull << kb) < nkeys) ++kb;
-    // split the key bits between the two digits so that neither LDS footprint starves its kernel of wavefronts:
-    // pass 1 keeps B x 4 B per single-wavefront workgroup, pass 2 keeps 4 x 2^wb x 4 B per 4-wavefront workgroup
-    // Sweep at 2^22 keys (RMAT-22, tools/transpose_wb_sweep.py; count / scatter / bucket ms): wb 10: .29 / 1.38 / .86;
-    // 11: .18 / 1.46 / .99; 12: .13 / 1.01 / 1.23; 13: .11 / .66 / 2.26 — fewer pass-1 buckets mean longer runs per
-    // bucket (the scattered 8 B pairs combine into lines before they leave L2 / MALL), more pass-2 keys mean LDS
-    // counters that leave one workgroup per CU.  Smaller pass-1 blocks (4096, 2048 entries) changed nothing.
-    u32 wb = kb > 22 ? kb - 12 : (kb > 12 ? 12 : (kb > 11 ? 11 : 8));   // 2^22 keys: 1024 x 4096; 2^24: 4096 x 4096; 2^26: 8192 x 8192
-    if (wb < 8) wb = 8;                                // a pass-2 thread owns 2^wb / 256 keys
-    if (kb > wb + 13) wb = kb - 13;
-    if (g_ks_wb_override >= 8 && g_ks_wb_override <= (int)KS_MAX_WB && (u32)g_ks_wb_override + 13 >= kb) wb = (u32)g_ks_wb_override;
-    if (wb > KS_MAX_WB) wb = KS_MAX_WB;
-    const u64 B = (nkeys + (1ull << wb) - 1) >> wb;
-    if (B > KS_MAX_BUCKETS) return false;      // > 2^26 keys: three digits would be needed
-    g.wb = wb;
-    g.B = (u32)(B ? B : 1);
-    g.bbits = 0;
-    while ((1u << g.bbits) < g.B) ++g.bbits;
-    u64 eb = 16384;
-    while ((n + eb - 1) / eb > 4096) eb <<= 1;  // the count matrix stays <= B x 4096
-
-    g.EB = (u32)eb;
-    g.nblk = (u32)((n + eb - 1) / eb);
-    if (g.nblk == 0) g.nblk = 1;
-    return true;
-}
+static bool ks_geometry(u64 n, u64 nkeys, KsGeom& g) { return ks_geometry(n, nkeys, g_ks_wb_override, g); }   // sort_plan.hpp
 
 // row of CSR entry i (largest r with rowptr[r] <= i), searched in [lo, hi]
 __device__ __forceinline__ u32 row_of_entry(const u32* __restrict__ rowptr, u32 lo, u32 hi, u32 i) {
@@ -335,8 +298,6 @@ fgpu_info sort_pairs_by_key(fgpu_ctx* ctx, const u32* key, const u32* val, const
 //              consecutive threads -> consecutive slots -> consecutive addresses of a run
 //
 // The last level writes the values alone, and the key pointers are the starts of the "segments" one level further down.
-constexpr u32 KP_EB = 2048;
-constexpr u32 KP_MAX_D = 512;
 constexpr bool KP_AUTO = true;    // transpose_mode 0 picks the staged levels from 2^17 keys
 struct KpLevel {
     u32 shift;   // digit = (key >> shift) & (D - 1)
@@ -651,23 +612,9 @@ __global__ __launch_bounds__(256) void kp_scatter_kernel(const u32* __restrict__
     }
 }
 
-// digit widths, most significant first: as few levels as 9 bits a level allow, at least ... balanced
-static int kp_widths(u64 nkeys, u32* w) {
-    u32 kb = 1;
-    while (kb < 32 && (1ull << kb) < nkeys) ++kb;
-    int L = (int)((kb + 8) / 9);
-    if (L < 1) L = 1;
-    if (kb >= 17 && L < 3) L = 3;                 // (runs of whole lines need <= 512 buckets a level; 3 levels from 2^17 keys)
-    if ((u32)L > kb) L = (int)kb;
-    // the wider digits last: a level's runs are KP_EB / D entries long, and the last level moves 4-byte values in segments
-    // that mostly fit one block (written as one contiguous piece whatever D is)
-    for (int l = 0; l < L; ++l) w[l] = kb / L + ((u32)(L - 1 - l) < kb % L ? 1u : 0u);
-    return L;
-}
-
 fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val, const u32* rowptr, u32 nrows, u64 n,
                                    u64 nkeys, u32* out_val, u32* keyptr, u32* n_valid_out) {
-    if (n == 0 || n >= 0xFFFFFFFFull - KP_EB || nkeys == 0 || nkeys > (1ull << 31)) return FGPU_NO_VALUE;
+    if (!kp_accepts(n, nkeys)) return FGPU_NO_VALUE;
     const bool implicit = val == nullptr;
     u32 w[8];
     const int L = kp_widths(nkeys, w);
@@ -681,12 +628,8 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
     DevBuf<uint4> desc;
     DevBuf<uint2> brows;
     // upper bounds: a level with S segments has at most n / KP_EB + S blocks
-    u64 S_max = 1;
-    {
-        u32 done = 0;
-        for (int l = 0; l + 1 < L; ++l) { done += w[l]; S_max = 1ull << done; }
-    }
-    const u64 nb_top = n / KP_EB + 9 + S_max;
+    const u64 S_max = kp_s_max(w, L);
+    const u64 nb_top = kp_nb_top(n, S_max);
     u32 dmax = 0;
     for (int l = 0; l < L; ++l) dmax = std::max(dmax, 1u << w[l]);
     FGPU_TRY(segstart.alloc(ctx, S_max + 2));
@@ -708,8 +651,8 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
         lv.S = 1u << done;
         lv.div = 0;
         const bool first = l == 0, last = l == L - 1;
-        const u64 nb_max = (n / KP_EB + 1 + lv.S + 7) & ~7ull;
-        const size_t ncnt = (size_t)lv.D * nb_max + 1;
+        const u64 nb_max = kp_nb_max(n, lv.S);
+        const size_t ncnt = kp_ncnt(lv.D, nb_max);
         FGPU_TRY(launch(kp_blk_table_kernel, dim3(cdiv(nb_max, 256)), dim3(256), 0, st, (const u32*)segstart.p, (const u32*)blkstart.p, lv,
                         (u32)nb_max, desc.p, first && implicit ? rowptr : (const u32*)nullptr, nrows, brows.p, cnt.p));
         {
@@ -723,7 +666,7 @@ fgpu_info sort_pairs_by_key_staged(fgpu_ctx* ctx, const u32* key, const u32* val
         }
         FGPU_TRY(scan_u32(ctx, cnt.p, pos.p, ncnt, nullptr));
         uint2* outp = last ? nullptr : (l == 0 ? bufA.p : (in == bufA.p ? bufB.p : bufA.p));
-        const size_t lds = ((size_t)2 * KP_EB + (size_t)6 * lv.D) * sizeof(u32);
+        const size_t lds = kp_scatter_lds_bytes(lv.D);
         {
             static const char* const names[] = {"kp_scatter_kernel L1", "kp_scatter_kernel L2", "kp_scatter_kernel L3", "kp_scatter_kernel L4"};
             ProfScope ps(ctx, names[l < 4 ? l : 3], (first ? (implicit ? 4 : 8) : 8) * n + (last ? 4 : 8) * n + 4 * ncnt);
@@ -798,7 +741,7 @@ __global__ __launch_bounds__(256) void dedup_scatter_kernel(const u32* __restric
 // 0 = the staged levels where the key space is wide enough for the store shape to matter; false = neither applies
 static bool ks_applicable(fgpu_ctx* ctx, u64 n, u64 nkeys, bool* staged) {
     const int mode = ctx->opt.transpose_mode;
-    const bool can = nkeys >= 2 && nkeys <= (1ull << 31) && n < 0xFFFFFFFFull - KP_EB;
+    const bool can = nkeys >= 2 && kp_accepts(n, nkeys);
     *staged = can && (mode == 2 || (mode == 0 && KP_AUTO && nkeys >= (1ull << 17)));
     if (*staged) return true;
     KsGeom g;
@@ -827,8 +770,8 @@ fgpu_info partition_csr_entries(fgpu_ctx* ctx, const u32* colidx, const u32* row
     lv.S = 1;
     lv.div = div;
     hipStream_t st = ctx->stream();
-    const u64 nb_max = (nnz / KP_EB + 2 + 7) & ~7ull;
-    const size_t ncnt = (size_t)lv.D * nb_max + 1;
+    const u64 nb_max = kp_nb_max(nnz, lv.S);
+    const size_t ncnt = kp_ncnt(lv.D, nb_max);
     DevBuf<u32> segstart, blkstart, cnt, pos, slots;
     DevBuf<uint4> desc;
     DevBuf<uint2> brows;
@@ -850,7 +793,7 @@ fgpu_info partition_csr_entries(fgpu_ctx* ctx, const u32* colidx, const u32* row
     FGPU_TRY(scan_u32(ctx, cnt.p, pos.p, ncnt, nullptr));
     {
         ProfScope ps(ctx, "kp_scatter_kernel part", 4 * nnz + 8 * nnz + 4 * ncnt);
-        const size_t lds = ((size_t)2 * KP_EB + (size_t)6 * lv.D) * sizeof(u32);
+        const size_t lds = kp_scatter_lds_bytes(lv.D);
         FGPU_TRY(launch((kp_scatter_kernel<true, true, false, true>), dim3((u32)nb_max), dim3(256), lds, st,
                         slot_of ? (const u32*)slots.p : colidx, (const u32*)nullptr, rowptr, nrows, (const uint2*)nullptr, lv,
                         (const uint4*)desc.p, (const uint2*)brows.p, (const u32*)pos.p, out_pairs, (u32*)nullptr, (const u32*)nullptr));

@@ -37,7 +37,7 @@ DIRECTIONS = ("out", "in", "both")
 
 
 def kp_levels(nkeys):
-    """the level count kp_widths (transpose.hip) gives a key space of nkeys"""
+    """the level count kp_widths (sort_plan.hpp) gives a key space of nkeys"""
     kb = 1
     while kb < 32 and (1 << kb) < nkeys:
         kb += 1

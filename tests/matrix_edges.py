@@ -130,6 +130,7 @@ def value_of(r, c, salt=0):
 SORT_LENGTHS = (2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8193)
 SORT_PATTERNS = ("interleave", "below", "identical", "ends")
 KEY_SPACES = (4100, 10007, (1 << 20) + 3)
+WIDE_KEY_SPACES = ((1 << 31) + 5, (1 << 32) - 2)   # column ids with bit 31 set, up to the largest legal one (numpy reference only)
 DUP_COUNTS = (64, 65, 4097)
 
 

@@ -25,7 +25,7 @@ MODEL_DIR = {"out": {}, "in": {"reversed": True}, "both": {"bidirectional": True
 
 # ---- the constants ---------------------------------------------------------------------------------------------------------
 def test_the_constants_are_the_sources():
-    src = {f: open(os.path.join(CSRC, f)).read() for f in ("bulk.hpp", "prims.hip", "transpose.hip", "expand_edges.hip",
+    src = {f: open(os.path.join(CSRC, f)).read() for f in ("bulk.hpp", "prims.hip", "sort_plan.hpp", "expand_edges.hip",
                                                            "expand_trails.hip", "edge_layers.hpp")}
     hdr = open(os.path.join(ROOT, "include", "fgpu.h")).read()
     const = lambda text, name: int(re.search(r"constexpr\s+[\w ]+?\b" + name + r"\s*=\s*(\d+)(?:ull|u)?\s*;", text).group(1))
@@ -36,9 +36,9 @@ def test_the_constants_are_the_sources():
         assert set(re.findall(r"blockIdx\.x \* (\d+) \+ threadIdx\.x", src[f])) == {str(ec.BLOCK)}, f
     assert const(src["prims.hip"], "SCAN_THREADS") * const(src["prims.hip"], "SCAN_SUBTILES") == ec.SCAN_TILE
     assert re.search(r"SCAN_TILE\s*=\s*SCAN_THREADS \* SCAN_SUBTILES;", src["prims.hip"])
-    assert const(src["transpose.hip"], "KP_EB") == ec.KP_EB
-    assert "(kb + %d) / %d" % (ec.KP_BITS - 1, ec.KP_BITS) in src["transpose.hip"]
-    assert "if (kb >= %d && L < 3) L = 3;" % ec.KP_THREE_LEVELS_KB in src["transpose.hip"]
+    assert const(src["sort_plan.hpp"], "KP_EB") == ec.KP_EB   # (the sorts' shape decisions: transpose.hip takes them from this header)
+    assert "(kb + %d) / %d" % (ec.KP_BITS - 1, ec.KP_BITS) in src["sort_plan.hpp"]
+    assert "if (kb >= %d && L < 3) L = 3;" % ec.KP_THREE_LEVELS_KB in src["sort_plan.hpp"]
     m = re.search(r"if \(nrp \* n <= \(1ull << (\d+)\)\)", src["expand_edges.hip"])
     assert m and 1 << int(m.group(1)) == ec.ONE_KEY_LIMIT
     assert const(src["edge_layers.hpp"], "EE_MAX_TYPES") == ec.EE_MAX_TYPES

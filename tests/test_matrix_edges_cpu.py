@@ -22,7 +22,29 @@ def orc(a: me.Csr) -> oracle.CSR:
     return oracle.CSR(a.nrows, a.ncols, a.rowptr, a.colidx)
 
 
-@pytest.mark.parametrize("N", me.KEY_SPACES)
+@pytest.mark.parametrize("N", me.WIDE_KEY_SPACES)
+def test_wide_sort_cases_reach_the_largest_legal_id(N):
+    """Past 2^31 the numpy references stand alone (the oracle's product allocates per column): every claim below holds for
+    them too, keys with bit 31 set are in every class, and N - 1 — one below the sorts' padding value at 2^32 - 2 — is stored."""
+    assert (1 << 31) < N <= (1 << 32) - 2
+    sc = me.sort_cases(N)
+    assert int(sc.B.colidx.max()) == N - 1 == int(sc.C.colidx.max()) and int(sc.B.colidx.min()) == 0
+    for i, (name, L, uniq) in sc.claims.items():
+        if name.endswith(("-ends", "-below")):
+            assert int(sc.C.row(i).max()) == N - 1 and int(sc.C.row(i).min()) == 0, name
+            assert len(sc.C.row(i)) == uniq == L, name
+    assert sc.dup_key == N // 3
+    r, c = sc.coo()
+    assert len(r) >= 4096 and int(c.max()) == N - 1
+    assert me.build(sc.F.nrows, N, r, c).to_set() == sc.C.to_set()
+    m, dp, dm = sc.layers()
+    assert me.merge(m, dp, None).to_set() == sc.C.to_set()
+    for mat in (m, dp, dm):
+        assert int(mat.colidx.max()) >= 1 << 31 and mat.nrows == sc.F.nrows
+    assert sc.F.nrows < 4096 and sc.B.nrows < 8192                 # entry-sized: nothing here is as long as the key space
+
+
+@pytest.mark.parametrize("N", me.KEY_SPACES + me.WIDE_KEY_SPACES)
 def test_sort_cases_have_the_lengths_and_unique_counts_they_name(N):
     sc = me.sort_cases(N)
     names = {name for name, _, _ in sc.claims.values()}
