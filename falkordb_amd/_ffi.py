@@ -22,6 +22,9 @@ FGPU_INSUFFICIENT_SPACE = -103
 FGPU_OUT_OF_BOUNDS = -105
 FGPU_DEVICE = -7002
 
+FGPU_DEGREE_OUT = 1   # fgpu_node_degrees' flags
+FGPU_DEGREE_IN = 2
+
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -97,6 +100,7 @@ SIGNATURES = {
     "fgpu_expand_edges": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, u64p, u64p,
                                       C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u8p), u64p,
                                       u64p]),
+    "fgpu_node_degrees": (C.c_int32, [vp, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, u64p, u64p, u64p]),
     "fgpu_expand_trails": (C.c_int32, [vp, u64p, u64p, C.c_uint64, vpp, vpp, vpp, vpp, vpp, vpp, vpp, C.c_int, C.c_int, C.c_uint32,
                                        C.c_uint32, u64p, C.c_uint64, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p),
                                        C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u32p), C.POINTER(u64p), u64p, u64p]),

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libfgpu.so")
-SOURCES = ["ctx.hip", "prims.hip", "mat.hip", "bfs.hip", "spgemm.hip", "tiled.hip", "blocked.hip", "bitexpand.hip", "exists.hip", "bitpart.hip", "merge.hip", "pagerank.hip", "algo.hip", "wcc.hip", "cdlp.hip", "harmonic.hip", "msf.hip", "maxflow.hip", "sssp.hip", "spdag.hip", "spdag_batch.hip", "spath_batch.hip", "vecidx.hip", "betweenness.hip", "transpose.hip", "edges.hip", "detach.hip", "edges_remove.hip", "edges_union.hip", "expand_edges.hip", "expand_trails.hip", "pair_weights.hip", "dist.hip"]
+SOURCES = ["ctx.hip", "prims.hip", "mat.hip", "bfs.hip", "spgemm.hip", "tiled.hip", "blocked.hip", "bitexpand.hip", "exists.hip", "bitpart.hip", "merge.hip", "pagerank.hip", "algo.hip", "wcc.hip", "cdlp.hip", "harmonic.hip", "msf.hip", "maxflow.hip", "sssp.hip", "spdag.hip", "spdag_batch.hip", "spath_batch.hip", "vecidx.hip", "betweenness.hip", "transpose.hip", "edges.hip", "detach.hip", "edges_remove.hip", "edges_union.hip", "expand_edges.hip", "degrees.hip", "expand_trails.hip", "pair_weights.hip", "dist.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

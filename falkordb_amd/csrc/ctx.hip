@@ -816,6 +816,7 @@ fgpu_info fgpu_get_option(fgpu_ctx* ctx, const char* name, int64_t* value) {
     FGPU_REQUIRE(ctx && name && value, FGPU_NULL_POINTER, "fgpu_get_option: NULL argument");
     if (const OptRow* r = opt_find(name)) { *value = opt_load(ctx->opt, *r); return FGPU_OK; }
     if (!strcmp(name, "sssp_delta_log2")) { *value = ctx->opt.sssp_delta_log2; return FGPU_OK; }   // an exponent or auto: no row kind fits
+    if (!strcmp(name, "degree_window_rows")) { *value = ctx->opt.degree_window_rows; return FGPU_OK; }   // beside the table (options.hpp)
     for (const CounterRow& c : COUNTERS)
         if (!strcmp(name, c.name)) { *value = c.load(ctx); return FGPU_OK; }
     if (!strncmp(name, "msf_last_entries_round", 22) && name[22] >= '0' && name[22] <= '9' && atoi(name + 22) < 32) {
@@ -838,6 +839,13 @@ fgpu_info fgpu_set_option(fgpu_ctx* ctx, const char* name, int64_t value) {
                      "fgpu_set_option: sssp_delta_log2 must be %d .. %d or %d (auto), not %lld", SSSP_DELTA_MIN, SSSP_DELTA_MAX,
                      SSSP_DELTA_AUTO, (long long)value);
         ctx->opt.sssp_delta_log2 = (int)value;
+        return FGPU_OK;
+    }
+    if (!strcmp(name, "degree_window_rows")) {   // beside the table (options.hpp)
+        FGPU_REQUIRE(value >= DEGREE_WINDOW_MIN && value <= DEGREE_WINDOW_MAX, FGPU_INVALID,
+                     "fgpu_set_option: degree_window_rows must be %d .. %d, not %lld", DEGREE_WINDOW_MIN, DEGREE_WINDOW_MAX,
+                     (long long)value);
+        ctx->opt.degree_window_rows = (int)value;
         return FGPU_OK;
     }
     const OptRow* r = opt_find(name);

@@ -98,8 +98,13 @@ struct fgpu_options {  // fgpu_set_option
                                // forward), 1 = forward only, 2 = backward only, 3 = strict alternation starting forward.  Every
                                // setting returns the same length and pairs, only the stats differ (spdag.hip; the tests hold the
                                // two-sided search to the one-sided ones)
+    int degree_window_rows = 1 << 24; // fgpu_node_degrees: positions per window (degrees.hip): a call walks its batch, or the whole
+                               // graph, in windows of at most this many rows, so the segment and entry spaces of one window stay
+                               // inside 32 bits.  Handled in ctx.hip like sssp_delta_log2, not a row below
 };
 constexpr int SSSP_DELTA_AUTO = 4096, SSSP_DELTA_MIN = -1074, SSSP_DELTA_MAX = 1023;
+// the values "degree_window_rows" accepts: range-checked in ctx.hip
+constexpr int DEGREE_WINDOW_MIN = 64, DEGREE_WINDOW_MAX = 1 << 24;
 
 namespace fgpu {
 
@@ -108,7 +113,8 @@ namespace fgpu {
 //   OPT_BOOL   any value, stored as value != 0
 //   OPT_RANGE  lo <= value <= hi
 //   OPT_POW2   lo <= value <= hi and a power of two
-// Not in the table: lds_limit (filled by fgpu_init, not settable), "transpose_wb" (process-wide, no field) and sssp_delta_log2: ctx.hip.
+// Not in the table: lds_limit (filled by fgpu_init, not settable), "transpose_wb" (process-wide, no field), sssp_delta_log2 and
+// degree_window_rows: ctx.hip.
 enum OptKind { OPT_BOOL, OPT_RANGE, OPT_POW2 };
 
 struct OptRow {

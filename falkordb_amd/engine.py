@@ -254,6 +254,27 @@ class Context:
             cols.append(self._take(ppass, n.value, np.uint8))
         return (*cols, [int(x) for x in st])
 
+    # ---- indegree() / outdegree() (degrees.hip) ----
+    def node_degrees(self, nodes, m, dp=None, dm=None, mt_m=None, mt_dp=None, mt_dm=None, multi=None, out=True, incoming=False):
+        """fgpu_node_degrees: the relationships that leave (out) and / or enter (incoming) every node of `nodes`; m .. multi as
+        for expand_edges.  nodes None is the whole-graph form: position i is node i, for every i below m[0]'s dimension.
+        Returns (out, in, stats): uint64 arrays of one entry per position (None for a direction not asked for) and the eight
+        stats of fgpu.h."""
+        T = len(m)
+        arrs = [_hop_arrays(x) if x is not None else None for x in (m, dp, dm, mt_m, mt_dp, mt_dm, multi)]
+        assert all(a is None or len(a) == T for a in arrs)
+        if nodes is None:
+            ids, k = None, (m[0].nrows if T else 0)
+        else:
+            ids = _u64(nodes).reshape(-1)
+            k = len(ids)
+        o = np.zeros(k, dtype=U64) if out else None
+        i = np.zeros(k, dtype=U64) if incoming else None
+        st = (C.c_uint64 * 8)()
+        flags = (_ffi.FGPU_DEGREE_OUT if out else 0) | (_ffi.FGPU_DEGREE_IN if incoming else 0)
+        check(self.lib.fgpu_node_degrees(self._h, _p(ids), k, *arrs, T, flags, _p(o), _p(i), st))
+        return o, i, [int(x) for x in st]
+
     # ---- variable-length traversal (expand_trails.hip) ----
     def expand_trails(self, starts, dests, m, dp=None, dm=None, mt_m=None, mt_dp=None, mt_dm=None, multi=None, reversed=False,
                       bidirectional=False, paths=False, min_hops=1, max_hops=None, dst_label_bitmap=None, max_items=1 << 22,

@@ -809,6 +809,25 @@ class Graph:
         rows = [None if null[i] else (nodes[no[i]:no[i + 1]], edges[eo[i]:eo[i + 1]]) for i in range(count)]
         return (rows, {"device_calls": int(calls.value)}) if stats else rows
 
+    def node_degrees(self, ids, incoming=False, types=(), batched=True, stats=False):
+        """outdegree(n [, types]) / indegree(n [, types]) (entity.rs:268-381) for the node ids `ids`: a uint64 array, one count
+        per id, the relationships of a multi-edge pair counted one by one.  types: none = every tensor, a name listed twice
+        counts once, unknown names are dropped, no known name answers 0.  batched: ONE fgpu_node_degrees call per 64 resolved
+        tensors; False: one row at a time on the host, the reference's loop.  stats=True: a second item {"device_calls": n}."""
+        v = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        out = np.zeros(len(v), dtype=np.uint64)
+        calls = C.c_uint64()
+        _ck(self.L.fh_node_degrees(self.h, ",".join(types).encode(), 1 if incoming else 0, v.ctypes.data_as(u64p), C.c_uint64(len(v)),
+                                   1 if batched else 0, out.ctypes.data_as(u64p), C.byref(calls)))
+        return (out, {"device_calls": int(calls.value)}) if stats else out
+
+    def node_degrees_all(self, incoming=False, types=()):
+        """The same for every node id below the node capacity, through fgpu_node_degrees' whole-graph form: a uint64 array
+        indexed by node id."""
+        p, n = u64p(), C.c_uint64()
+        _ck(self.L.fh_node_degrees_all(self.h, ",".join(types).encode(), 1 if incoming else 0, C.byref(p), C.byref(n)))
+        return _take(p, n.value)
+
     def build_adjacency(self, types=(), symmetric=False):
         """Graph::build_adjacency_matrix / build_symmetric_adjacency_matrix (graph.rs:3870-3907) -> Matrix"""
         h = C.c_void_p()

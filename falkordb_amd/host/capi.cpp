@@ -924,6 +924,42 @@ int fh_shortest_path_batch(fh_graph* g, const char* types, int directed, uint32_
     });
 }
 
+int fh_node_degrees(fh_graph* g, const char* types, int incoming, const uint64_t* ids, uint64_t k, int mode, uint64_t* out,
+                    uint64_t* device_calls) {
+    return guard([&] {
+        if (mode != 0 && mode != 1) throw std::invalid_argument("fh_node_degrees: mode must be 0 (per row) or 1 (batch)");
+        DegreeFn fn;
+        fn.incoming = incoming != 0;
+        fn.types = csv(types);
+        const std::vector<u64> v(ids, ids + k);
+        u64 calls = 0;
+        const std::vector<u64> deg = timed([&] {
+            if (mode == 1) return fn.eval_batch(g->g, v, &calls);
+            for (u64 id : v)   // (every id before the first result, as the batch checks them)
+                if (id >= g->g.node_cap())
+                    throw std::out_of_range("fh_node_degrees: node id " + std::to_string(id) + " is at or past the node capacity");
+            std::vector<u64> rows(k);
+            for (u64 i = 0; i < k; ++i) rows[i] = fn.eval_row(g->g, v[i]);
+            return rows;
+        });
+        if (k) memcpy(out, deg.data(), k * sizeof(u64));
+        if (device_calls) *device_calls = calls;
+        return 0;
+    });
+}
+
+int fh_node_degrees_all(fh_graph* g, const char* types, int incoming, uint64_t** out, uint64_t* n) {
+    return guard([&] {
+        DegreeFn fn;
+        fn.incoming = incoming != 0;
+        fn.types = csv(types);
+        const std::vector<u64> deg = timed([&] { return fn.eval_all(g->g); });
+        *out = hand(deg);
+        *n = deg.size();
+        return 0;
+    });
+}
+
 // fh_algo_bfs and fh_algo_bfs_multi: one call but for the gang (nullptr: the graph's own context); only the single-context
 // entry is a timed operator
 static int algo_bfs_c(fh_graph* g, const std::vector<Context*>* gang, int64_t source, int64_t max_depth, const char* rel_type,

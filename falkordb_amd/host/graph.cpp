@@ -1536,6 +1536,68 @@ std::vector<ShortestPathFn::Path> ShortestPathFn::eval_batch(const Graph& g, con
     return out;
 }
 
+// ---- indegree() / outdegree() ----------------------------------------------------------------------------
+namespace {
+// parse_degree_args + get_node_*degree_by_type: none named = every tensor, else the known names, each once, in the order of
+// their first mention
+std::vector<u64> degree_type_ids(const Graph& g, const std::vector<std::string>& names) {
+    if (names.empty()) return scanned_type_ids(g, names);
+    std::vector<u64> ids;
+    for (u64 id : named_type_ids(g, names))
+        if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
+    return ids;
+}
+void require_node_ids(const Graph& g, const std::vector<u64>& ids, const char* who) {
+    for (u64 id : ids)
+        if (id >= g.node_cap())
+            throw std::out_of_range(std::string(who) + ": node id " + std::to_string(id) + " is at or past the node capacity " +
+                                    std::to_string(g.node_cap()));
+}
+// ids == nullptr: the whole-graph form, k = node_cap()
+std::vector<u64> device_degrees(const Graph& g, const std::vector<u64>& tids, bool incoming, const u64* ids, u64 k, u64* device_calls) {
+    std::vector<u64> out(k, 0), part(k);
+    if (device_calls) *device_calls = 0;
+    if (k == 0) return out;
+    for (size_t t0 = 0; t0 < tids.size(); t0 += 64) {
+        const std::vector<u64> group(tids.begin() + t0, tids.begin() + std::min(tids.size(), t0 + 64));
+        TensorLayerArrays a;
+        if (incoming) {
+            a = gather(g, group);
+        } else {   // outgoing: the transposed layers are not read, so a pending transpose is not materialised
+            for (u64 t : group) {
+                const Tensor& ten = g.relationship_tensors()[t];
+                ten.wait_fwd();
+                const Layers f = fwd_layers(ten);
+                a.m.push_back(f.m); a.dp.push_back(f.dp); a.dm.push_back(f.dm);
+                a.multi.push_back(ten.multi_table());
+            }
+        }
+        check(fgpu_node_degrees(g.ctx().raw(), ids, k, a.m.data(), a.dp.data(), a.dm.data(), incoming ? a.tm.data() : nullptr,
+                                incoming ? a.tdp.data() : nullptr, incoming ? a.tdm.data() : nullptr, a.multi.data(), (int)a.size(),
+                                incoming ? FGPU_DEGREE_IN : FGPU_DEGREE_OUT, incoming ? nullptr : part.data(),
+                                incoming ? part.data() : nullptr, nullptr),
+              incoming ? "indegree" : "outdegree");
+        if (device_calls) ++*device_calls;
+        for (u64 i = 0; i < k; ++i) out[i] += part[i];
+    }
+    return out;
+}
+}  // namespace
+
+u64 DegreeFn::eval_row(const Graph& g, u64 id) const {
+    require_node_ids(g, {id}, incoming ? "indegree" : "outdegree");
+    return node_relationships(g, id, degree_type_ids(g, types), !incoming, incoming).size();
+}
+
+std::vector<u64> DegreeFn::eval_batch(const Graph& g, const std::vector<u64>& ids, u64* device_calls) const {
+    require_node_ids(g, ids, incoming ? "indegree" : "outdegree");
+    return device_degrees(g, degree_type_ids(g, types), incoming, ids.data(), ids.size(), device_calls);
+}
+
+std::vector<u64> DegreeFn::eval_all(const Graph& g, u64* device_calls) const {
+    return device_degrees(g, degree_type_ids(g, types), incoming, nullptr, g.node_cap(), device_calls);
+}
+
 // ---- algo.BFS --------------------------------------------------------------------------------------------
 // The partitioned form of the search below: the adjacency is cut into nnz-balanced column slabs, one
 // per context of `gang` (one context per GPU; several contexts on one device work too and are how this is tested),

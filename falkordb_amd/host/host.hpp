@@ -901,6 +901,26 @@ struct ShortestPathFn {
                                  u64* device_calls = nullptr) const;
 };
 
+// indegree(n [, types]) / outdegree(n [, types]) (runtime/functions/entity.rs:268-381, runtime.rs:1727-1796, graph.rs:1839-1887):
+// an expression, evaluated per row by the reference as one versioned row iterator per node and tensor with every id of a
+// multi-edge list walked.  Types as parse_degree_args + get_node_*degree_by_type resolve them: none named = every tensor; a
+// name listed twice counts once (entity.rs:340, :367); an unknown name is dropped; names of which none is known answer 0.
+// The value is the graph's own count, pending creations and deletions (dp / dm) included; what the reference's runtime adds
+// for the query's uncommitted `Pending` overlay (runtime.rs:1737-1741) stays with the caller.  A node id at or past
+// node_cap() throws std::out_of_range before any result; a deleted node's rows are empty once its relationships are gone, so
+// it answers 0.
+struct DegreeFn {
+    bool incoming = false;
+    std::vector<std::string> types;
+    // one row: the reference's loop, the count of get_node_relationships_by_type in the one direction.  No device degree call.
+    u64 eval_row(const Graph& g, u64 id) const;
+    // a parent batch: out[i] = eval_row(g, ids[i]).  The layers and multi-edge tables of the resolved tensors go to ONE
+    // fgpu_node_degrees call per 64 of them, summed across the groups.  *device_calls (nullable) = the calls made.
+    std::vector<u64> eval_batch(const Graph& g, const std::vector<u64>& ids, u64* device_calls = nullptr) const;
+    // every node id below node_cap(), through the call's whole-graph form: node_cap() values
+    std::vector<u64> eval_all(const Graph& g, u64* device_calls = nullptr) const;
+};
+
 struct BfsResult {
     bool has_row = false;
     std::vector<u64> nodes, edges;

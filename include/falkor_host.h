@@ -313,6 +313,19 @@ int fh_shortest_path(fh_graph* g, const char* types, int directed, uint32_t min_
 int fh_shortest_path_batch(fh_graph* g, const char* types, int directed, uint32_t min_hops, uint32_t max_hops, const int64_t* srcs,
                            const int64_t* dsts, uint64_t count, uint8_t* is_null, uint64_t** nodes, uint64_t* node_off,
                            uint64_t** edges, uint64_t* edge_off, uint64_t* device_calls);
+/* indegree(n [, types]) / outdegree(n [, types]) (entity.rs:268-381, graph.rs:1839-1887) for `k` node ids: out[i] = the number
+ * of relationships that enter (incoming != 0) or leave ids[i], the relationships of a multi-edge pair counted one by one, a
+ * self-loop once per direction.  types: a comma list; "" = every tensor, a name listed twice counts once, an unknown name is
+ * dropped, and when no listed name is known every answer is 0.  mode 0: one row at a time on the host, the count of the
+ * reference's iterator loop; mode 1: the layers of the resolved tensors go to ONE fgpu_node_degrees call per 64 of them.
+ * Pending creations and deletions (dp / dm) are counted in both modes.  An id at or past the node capacity fails before any
+ * result; a deleted node answers 0 once its relationships are gone.  out is the caller's (k entries); *device_calls
+ * (nullable) = the fgpu_node_degrees calls made. */
+int fh_node_degrees(fh_graph* g, const char* types, int incoming, const uint64_t* ids, uint64_t k, int mode, uint64_t* out,
+                    uint64_t* device_calls);
+/* The same for every node id below the node capacity, through the whole-graph form of fgpu_node_degrees: (*out)[v], v < *n,
+ * with *n the node capacity.  *out is freed with fh_free. */
+int fh_node_degrees_all(fh_graph* g, const char* types, int incoming, uint64_t** out, uint64_t* n);
 /* source < 0 = NULL; rel_type NULL = all types.  `edges` holds one id per (parent, child) pair that HAS a
  * representative edge among the types, in node order; a pair without one is skipped in `edges` but its child stays in
  * `nodes` — exactly what the reference yields (algo_procedures.rs:1121-1150) — so the two lists are parallel only

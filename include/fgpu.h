@@ -574,6 +574,49 @@ fgpu_info fgpu_expand_edges(fgpu_ctx* ctx, const uint64_t* from, const uint64_t*
                             uint32_t** out_from, uint32_t** out_to, uint64_t** out_id, uint8_t** out_pass, uint64_t* out_n,
                             uint64_t stats[8]);
 
+/* indegree(n [, types]) / outdegree(n [, types]) (entity.rs:268-381, runtime.rs:1727-1796, graph.rs:1839-1887) for a batch of k
+ * nodes, or for every node, in one call: per position and direction the number of (src, dst, id) triples that
+ * Tensor::iter(id, id, transposed) yields, summed over the n_types tensors in the given order — a type given twice counts
+ * twice (graph.rs:1856-1860).
+ *   nodes [k]       node ids, each below the dimension n; a repeated id gets its own answer per position; k <= 2^24.
+ *                   NULL is the WHOLE-GRAPH form: k must equal n, position i is node i, and any n the layers allow is taken.
+ *   m .. multi      the tensors' layers and tables exactly as fgpu_expand_edges takes them (0 to 64 types; dp / dm / mt_* / multi
+ *                   nullable as array or element).  The transposed layers are read only under FGPU_DEGREE_IN, and a missing
+ *                   mt_m[t] is then FGPU_INVALID.
+ *   flags           FGPU_DEGREE_OUT, FGPU_DEGREE_IN or both; 0 and any other bit are FGPU_INVALID.
+ *   out_degree / in_degree   HOST arrays of k words, required with the matching flag and not touched without it.
+ * Value: over the effective structure (pattern(m) \ dm) U pattern(dp) of the node's row (outgoing), or of its row in the
+ * transposed layers (incoming), 1 per pair whose Tensor::eff_get value is an inline id and the length of the table row per pair
+ * that holds FGPU_MULTI_EDGE; a pair in both dp and m counts once, with dp's value; a self-loop counts once in each direction.
+ * On every input fgpu_expand_edges accepts this is the number of rows it emits for from = node (outgoing), or for to = node
+ * under the storage direction (incoming), with no flag and no bitmap.  The incoming half of that equality assumes mt_* hold
+ * the transposed structure of the forward layers, as a Tensor keeps them: a (type, incoming) answered from the row pointers of
+ * mt_m never looks at the forward dp / dm, where fgpu_expand_edges reads the forward value of every incoming entry.
+ * Both forms walk their positions in windows of at most "degree_window_rows" rows (an engine option read and set through
+ * fgpu_get_option / fgpu_set_option: 64 .. 2^24, default 2^24; it is kept beside the option table), fewer when rows x
+ * directions x types x layers of a window would reach 2^31 segments.
+ * FGPU_INVALID, with fgpu_last_error set and the context still usable, for: an id at or past n (before anything is written);
+ * k above 2^24 in the batch form, k != n in the whole-graph form; layers that are not all n x n, an unvalued m (or dp);
+ * n_types above 64; a window whose walked entries reach 2^32 - 1 (lower degree_window_rows); a pair read as FGPU_MULTI_EDGE
+ * whose table has no row (counted on the device and read back before the window's results are copied out; the windows before it
+ * of a whole-graph call have been written).  n_types == 0 or k == 0 gives zeros and FGPU_OK.
+ * stats (nullable, all 0 after a failure): [0] (position, type, direction) triples answered by the row-pointer tier, [1] stored
+ * entries walked outgoing, [2] stored entries walked incoming, [3] multi-edge pairs met, [4] longest id list met, [5] the sum
+ * of the out-degrees, [6] the sum of the in-degrees, [7] windows walked.
+ * Work: a (type, direction) whose walked side has no dp, no dm and no table (multi[t] NULL or empty: fgpu_multi's contract lets
+ * that be only when the tensor holds no FGPU_MULTI_EDGE) is the row-pointer tier: a lane per (position, type, direction) adds
+ * the row's length and reads no entry.  Every other one is the entry tier, fgpu_expand_edges' segments and gather without its
+ * sort, placement and columns: a lane per segment, one scan, a lane per walked entry that applies the shadow and tombstone
+ * searches and resolves 1 or the list length, then the wavefront's counts are summed by position with shuffles and added with
+ * one 64-bit atomic per (wavefront, position, direction).  Integer sums commute: the result does not depend on scheduling.
+ * The outputs are k words per direction; the call keeps no device memory. */
+#define FGPU_DEGREE_OUT 1
+#define FGPU_DEGREE_IN 2
+fgpu_info fgpu_node_degrees(fgpu_ctx* ctx, const uint64_t* nodes, uint64_t k, const fgpu_mat* const* m,
+                            const fgpu_mat* const* dp, const fgpu_mat* const* dm, const fgpu_mat* const* mt_m,
+                            const fgpu_mat* const* mt_dp, const fgpu_mat* const* mt_dm, const fgpu_multi* const* multi,
+                            int n_types, int flags, uint64_t* out_degree, uint64_t* in_degree, uint64_t stats[8]);
+
 /* CondVarLenTraverse, the [*min..max] operator (cond_var_len_traverse.rs:81-387, VarLenIter), for a whole batch of k rows in one
  * call, without the attribute / WHERE filters.  start [k]: the bound endpoint of every row; dest (nullable array): a node id the
  * other endpoint must equal, or ~0 for unbound.  m .. multi, n_types: the relationship tensors in the pattern's order, as for

@@ -115,7 +115,14 @@
           without paths.  A pattern one device call cannot hold over all rows is timed on the lightest rows: the longest halved prefix,
           by out-degree, that fits.
 
-usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|edges|varlen_batch|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
+  degrees  indegree() / outdegree() batches (fgpu_node_degrees) on the tensor fgpu_edges_build makes of the distinct RMAT-18, -20
+          and -22 edges, 1 % of the pairs multi-edge: the 1024 first and all of the :P rows (a seeded sixteenth of the nodes), out
+          and in, against fgpu_expand_edges with the other endpoint unbound + a bincount of its row column, in one process,
+          medians of 5 after 2 warm-ups; at RMAT-18 also Graph.node_degrees against its per-row loop (stopped at a 10 s deadline
+          and extrapolated).  Then the whole-graph form on the clean RMAT-22 tensor beside one fgpu_mat_row_degrees of m, and on
+          the raw RMAT-22 stream with its multi-edge pairs.  `degrees <scale>`: the batches at that scale only.
+
+usage: python tools/bench_paths.py [merge|expand|reach|host|load|detach|edel|append|edges|degrees|varlen_batch|pagerank|wcc|cdlp|harmonic|betweenness|sssp|sssp_sweep|hops|asp|all] [scale]
 """
 import json
 import sys
@@ -722,6 +729,136 @@ def bench_edges(scales=(18, 20), deadline_s=10.0, k=1024):
                        "read-back of the columns included")
         print(json.dumps(out), flush=True)
         del g, fwd, bwd, multi
+
+
+def bench_degrees(scales=(18, 20, 22), host_scale=18, whole_scale=22, deadline_s=10.0, k=1024):
+    """indegree() / outdegree() batches (fgpu_node_degrees) against the only way the parent commit had to these numbers —
+    fgpu_expand_edges with `to` unbound and a bincount of its row column — and, at host_scale, against the per-row host loop."""
+    import ctypes as C
+    import torch
+    from falkordb_amd import _ffi, host
+    ctx = engine.Context(0)
+    for scale in scales:
+        A = ctx.mat_rmat(scale)
+        n = A.nrows
+        rp, ci, _ = A.export_csr()
+        r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+        ci = np.array(ci, dtype=np.uint64)
+        A.free()
+        rng = np.random.default_rng(300 + scale)
+        twice = rng.choice(len(ci), len(ci) // 100, replace=False)          # 1 % of the pairs hold a second edge
+        u, v = np.concatenate([r, r[twice]]), np.concatenate([ci, ci[twice]])
+        ids = np.arange(len(u), dtype=np.uint64)
+        P = np.sort(rng.choice(n, n // 16, replace=False)).astype(np.uint64)   # the :P rows: a seeded sixteenth of the nodes
+        fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, ids)
+        multi = ctx.multi_new(np.array(mkey), np.array(moff), np.array(mids))
+        out = {"path": "node_degrees", "scale": scale, "edges": len(u), "multi_pairs": len(twice), "P_rows": len(P)}
+        layers = [engine._hop_arrays(x) if x is not None else None for x in ([fwd], None, None, [bwd], None, None, [multi])]
+        for name, nodes in (("first_1024", P[:k]), ("every_P_row", P)):
+            unbound = np.full(len(nodes), (1 << 64) - 1, dtype=np.uint64)
+            leg = {"rows": len(nodes)}
+            for dname, kw in (("out", dict(out=True, incoming=False)), ("in", dict(out=False, incoming=True))):
+                t_new, res = timed(ctx, lambda: ctx.node_degrees(nodes, [fwd], None, None, [bwd], None, None, [multi], **kw), reps=5, warm=2)
+                deg = res[0] if dname == "out" else res[1]
+
+                def old():   # (the arrays are made once, outside the clock: engine.expand_edges would encode two Python lists per call)
+                    f, t = (nodes, unbound) if dname == "out" else (unbound, nodes)
+                    prow, pfrom, pto, pid = _ffi.u32p(), _ffi.u32p(), _ffi.u32p(), _ffi.u64p()
+                    cnt = C.c_uint64()
+                    _ffi.check(ctx.lib.fgpu_expand_edges(ctx._h, engine._p(f), engine._p(t), len(nodes), *layers, 1, 0, None, None,
+                                                         C.byref(prow), C.byref(pfrom), C.byref(pto), C.byref(pid), None, C.byref(cnt), None))
+                    row, *_ = [ctx._take(p, cnt.value, dt) for p, dt in ((prow, np.uint32), (pfrom, np.uint32), (pto, np.uint32), (pid, np.uint64))]
+                    return np.bincount(row, minlength=len(nodes))
+
+                t_old, cnt = timed(ctx, old, reps=5, warm=2)
+                assert np.array_equal(cnt.astype(np.uint64), deg)
+                leg[dname] = {"node_degrees_ms": round(t_new * 1e3, 3), "expand_edges_bincount_ms": round(t_old * 1e3, 3),
+                              "quotient": round(t_old / t_new, 2), "degree_sum": int(deg.sum()), "stats": res[2]}
+            out[name] = leg
+        ctx.prof_enable(True)
+        ctx.node_degrees(P[:k], [fwd], None, None, [bwd], None, None, [multi])
+        ctx.sync()
+        out["first_1024"]["out"]["device_phases_ms"] = {p["kernel"]: round(p["ms"], 3) for p in ctx.prof_read() if p["kernel"].startswith("dg_")}
+        ctx.prof_enable(False)
+        del fwd, bwd, multi
+        if scale == host_scale:   # the reference's per-row loop (DegreeFn::eval_row), 8 rows a call up to the deadline
+            hc = host.Context(0)
+            g = host.Graph(hc, n)
+            t = g.add_type("KNOWS")
+            g.bulk_insert_edges(t, u, v, ids)
+            g.commit()
+            ts = []
+            for rep in range(7):
+                t0 = time.perf_counter()
+                got = g.node_degrees(P[:k])
+                ts.append(time.perf_counter() - t0)
+            done, t0 = 0, time.perf_counter()
+            while done < k:
+                per_row = g.node_degrees(P[done:done + 8], batched=False)
+                assert np.array_equal(per_row, got[done:done + 8])
+                done += 8
+                if time.perf_counter() - t0 > deadline_s:
+                    break
+            dt = time.perf_counter() - t0
+            out["host_first_1024_out"] = {"eval_batch_ms_median_of_5": round(float(np.median(ts[2:])) * 1e3, 3),
+                                          "eval_row": {"rows_done": min(done, k), "finished": done >= k, "s": round(dt, 3),
+                                                       "ms_per_row": round(dt / done * 1e3, 3), "s_for_the_batch": round(dt / done * k, 3)},
+                                          "quotient": round(dt / done * k / float(np.median(ts[2:])), 1)}
+            del g
+            hc.close()
+        out["note"] = ("the tensor fgpu_edges_build makes of the distinct RMAT edges plus a second edge on a seeded 1 % of the pairs, on the "
+                       "engine context; :P = a seeded sixteenth of the node ids, ascending; both methods in this process on this tensor, "
+                       "median of 5 synchronised calls after 2 warm-ups, uploads, read-backs and (for expand_edges) the bincount included; "
+                       "host: Graph.node_degrees on a host-layer graph of the same edges, host clock around the Python call, eval_row 8 rows "
+                       "a call up to the deadline (finished = false: s_for_the_batch = ms_per_row x rows)")
+        print(json.dumps(out), flush=True)
+    if not whole_scale:
+        ctx.close()
+        return
+    # the whole-graph form: the clean tensor beside one fgpu_mat_row_degrees of m, then the raw stream with its multi-edge pairs
+    import oracle
+    n = 1 << whole_scale
+    A = ctx.mat_rmat(whole_scale)
+    rp, ci, _ = A.export_csr()
+    r = np.repeat(np.arange(n, dtype=np.uint64), np.diff(rp).astype(np.int64))
+    ci = np.array(ci, dtype=np.uint64)
+    fwd, bwd, *_ = engine.edges_build(ctx, n, n, r, ci, np.arange(len(ci), dtype=np.uint64))
+    dev = torch.empty(n, dtype=torch.int32, device="cuda")
+
+    def row_degrees():
+        fwd.row_degrees(dev.data_ptr())
+        ctx.sync()
+        return dev.cpu().numpy()
+
+    t_rd, rd = timed(ctx, row_degrees, reps=5, warm=2)
+    t_out, res = timed(ctx, lambda: ctx.node_degrees(None, [fwd]), reps=5, warm=2)
+    assert np.array_equal(res[0], rd.astype(np.uint64))
+    t_both, both = timed(ctx, lambda: ctx.node_degrees(None, [fwd], mt_m=[bwd], incoming=True), reps=5, warm=2)
+    line = {"path": "node_degrees_whole_graph", "scale": whole_scale, "n": n,
+            "clean": {"edges": len(ci), "out_ms": round(t_out * 1e3, 3), "out_and_in_ms": round(t_both * 1e3, 3),
+                      "mat_row_degrees_plus_copy_ms": round(t_rd * 1e3, 3), "stats_out": res[2], "stats_both": both[2]}}
+    del fwd, bwd, res, both
+    A.free()
+    u, v = (np.asarray(x, dtype=np.uint64) for x in oracle.rmat_edges(whole_scale))
+    fwd, bwd, mkey, moff, mids = engine.edges_build(ctx, n, n, u, v, np.arange(len(u), dtype=np.uint64))
+    multi = ctx.multi_new(np.array(mkey), np.array(moff), np.array(mids))
+    t_out, res = timed(ctx, lambda: ctx.node_degrees(None, [fwd], multi=[multi]), reps=5, warm=2)
+    t_both, both = timed(ctx, lambda: ctx.node_degrees(None, [fwd], mt_m=[bwd], multi=[multi], incoming=True), reps=5, warm=2)
+    assert int(res[0].sum()) == len(u) == int(both[1].sum())
+    ctx.prof_enable(True)
+    ctx.node_degrees(None, [fwd], mt_m=[bwd], multi=[multi], incoming=True)
+    ctx.sync()
+    phases = {p["kernel"]: round(p["ms"], 3) for p in ctx.prof_read() if p["kernel"].startswith("dg_")}
+    ctx.prof_enable(False)
+    line["raw_stream"] = {"tuples": len(u), "pairs": fwd.nvals, "multi_pairs": multi.size()[0], "out_ms": round(t_out * 1e3, 3),
+                          "out_and_in_ms": round(t_both * 1e3, 3), "stats_out": res[2], "stats_both": both[2],
+                          "device_phases_ms_both": phases}
+    line["note"] = ("median of 5 synchronised calls after 2 warm-ups, the k-word results copied to pageable host arrays included; clean: "
+                    "the distinct edges, no table given, so every triple is the row-pointer tier's; fgpu_mat_row_degrees writes 32-bit "
+                    "counts to device memory, timed with a device-to-host copy of them; raw_stream: every generated tuple, repeated "
+                    "pairs as multi-edges with their table, so every entry goes through the entry tier")
+    print(json.dumps(line), flush=True)
+    ctx.close()
 
 
 def bench_varlen(scale=18, deadline_s=10.0, k=1024, fit_items=1 << 26):
@@ -1687,6 +1824,8 @@ if __name__ == "__main__":
         bench_edel(*(((scale,), 0) if scale else ()))
     if what == "edges":                          # (the per-row path up to its deadlines: not part of `all`)
         bench_edges(*(((scale,),) if scale else ()))
+    if what == "degrees":                        # (the eval_row loop up to its deadline: not part of `all`)
+        bench_degrees(*(((scale,), 18, 0) if scale else ()))
     if what == "varlen_batch":                   # (the loop of expand_row up to its deadlines: not part of `all`)
         bench_varlen(*((scale,) if scale else ()))
     if what == "append":                         # (seconds of edge-by-edge inserts per twin: not part of `all`)
